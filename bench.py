@@ -14,6 +14,7 @@ launch, results rotating over 6 output buffers (384 MB: more than the Infinity C
 dominant kernel (find_kernel) from HIP events around back-to-back launches; N=1 also carries the SURVEY 8d stream table,
 the configs[2] (find + sparse Adagrad) rows and `cpu_baseline` (the in-repo CPU oracle, "port": the reference snapshot has
 no implementation) on the configuration the GPU number is quoted on; N>1 carries `xgmi` (bytes on the busiest link).
+--dump-outputs DIR writes what the last timed step returned (see dump_outputs); the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -31,6 +32,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured streaming copy)
+DUMP_BYTES = 64_000_000   # --dump-outputs: at most this many bytes in all
 
 
 def algorithmic_bytes_per_lookup(dim: int) -> int:
@@ -71,6 +73,20 @@ def lookup_batches(synth, n_keys, batch, n_batches, dist_name, dev, seed):
             idx = torch.randint(0, n_keys, (batch,), device=dev, generator=g)
         out.append(synth.mix64_t((idx + 1) * synth._s64(synth._GOLDEN) + synth._s64(1)))
     return out
+
+
+def dump_outputs(path, rows, found):
+    """--dump-outputs: what the last timed step returned to its caller — DIR/rows.npy (float32 [m, dim]), DIR/found.npy (float32 [m], 1 = found)
+    and DIR/index.npy (float64 [m]: the batch positions they belong to).  m = the whole batch when it fits DUMP_BYTES, else that many evenly
+    spaced positions (the same for every run with the same --batch and --dim)."""
+    n, dim = rows.shape
+    m = min(n, (DUMP_BYTES - 3 * 128) // (4 * dim + 4 + 8))   # (128: an .npy header)
+    idx = np.arange(m, dtype=np.int64) * n // m
+    it = torch.from_numpy(idx).to(rows.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rows.npy"), rows.index_select(0, it).to(torch.float32).cpu().numpy())
+    np.save(os.path.join(path, "found.npy"), found.index_select(0, it).to(torch.float32).cpu().numpy())
+    np.save(os.path.join(path, "index.npy"), idx.astype(np.float64))
 
 
 def _physical_cores(allowed) -> int:
@@ -833,7 +849,12 @@ def main():
                          "needs ~260 GB of HBM and ~115 GB of host RAM — scaled to what the box has) -> also.tier_share_one_gpu")
     ap.add_argument("--tier-share-keys", type=str, default="1250000000,800000000", help="--tier-share: total keys, keys in HBM[, cap on the cold keys of the training pair] (smaller = a rehearsal)")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (rank 0's rows and found flags, float32; a fixed sample of the "
+                         "batch positions when the whole exceeds 64 MB) as DIR/rows.npy, DIR/found.npy and DIR/index.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1: the result line is per timed step")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -902,6 +923,12 @@ def main():
     n_out = max(1, args.out_buffers) if (not sharded and not train) else 1
     outs = [out] + [torch.empty_like(out) for _ in range(n_out - 1)]
     founds = [found] + [torch.empty_like(found) for _ in range(n_out - 1)]
+
+    def seeded_grads(seed):   # train mode's gradient rows: seeded, so that the same arguments give the same inputs from run to run
+        g_ = torch.Generator(device=dev)
+        g_.manual_seed(seed)
+        return [torch.randn(batch, dim, device=dev, generator=g_) * 0.01 for _ in range(4)]
+
     store_hint = None   # the caller's cache-policy hint for the rotating case, chosen by a short probe below
     find_flags = None   # the cache policy this request queue passes with every call (mee_find_ex); None = the library's default rule
 
@@ -1040,7 +1067,7 @@ def main():
                 else:
                     log("p2p transport disagrees with the rccl path: not used")
         if train:   # the data-parallel training step: lookup, then every rank's gradients go to the owners, which apply
-            grads = [torch.randn(batch, dim, device=dev) * 0.01 for _ in range(4)]
+            grads = seeded_grads(12 + rank)
             find_step, via_peer = step, carrier == "p2p"
 
             def step(i):
@@ -1061,7 +1088,7 @@ def main():
                 shs[0].apply_adagrad(batches[i % n_batches], grads[i % 4], lr=0.01, eps=1e-10, dedup=args.dedup)
             return r_
     elif train:
-        grads = [torch.randn(batch, dim, device=dev) * 0.01 for _ in range(4)]   # N(0, 1e-2), SURVEY §8d config 3
+        grads = seeded_grads(12)   # N(0, 1e-2), SURVEY §8d config 3
 
         slots = torch.empty(batch, dtype=torch.int64, device=dev)
 
@@ -1106,7 +1133,7 @@ def main():
     # ---- the timed region: EXACTLY --steps steps between barrier + synchronize pairs --------------------------------------
     # N=1 find mode issues the K steps as ONE hipGraph replay (K kernel nodes chained on one stream: the same launches, the
     # same in-order semantics, without K host-side launch calls in the region); --launch eager keeps one host call per step.
-    graph = None
+    graph = graph_last = None   # graph_last: the buffers the replay's last step writes (what that step returned when it was captured)
     launch_mode = "eager (one host launch call per step)"
     if args.launch == "graph" and not sharded and not train and args.steps > 0:
         try:
@@ -1115,7 +1142,7 @@ def main():
             g_ = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g_, stream=gs_):
                 for i in range(args.steps):
-                    step(i)
+                    graph_last = step(i)
             g_.replay()                       # one untimed replay: upload + first-run costs stay out of the region
             torch.cuda.synchronize(dev)
             graph, launch_mode = g_, f"hipGraph: the {args.steps} steps captured as {args.steps} chained kernel nodes, one replay"
@@ -1132,9 +1159,10 @@ def main():
         ev0.record()
         if graph is not None:
             graph.replay()
+            r_ = graph_last
         else:
             for i_ in range(args.steps):
-                step(i_)
+                r_ = step(i_)
         ev1.record()
         torch.cuda.synchronize(dev)
         if sharded:
@@ -1144,7 +1172,7 @@ def main():
             tt_ = torch.tensor([el_], dtype=torch.float64, device=ctrl)
             dist.all_reduce(tt_, op=dist.ReduceOp.MAX)
             el_ = float(tt_.item())
-        return el_, ev0.elapsed_time(ev1)
+        return el_, ev0.elapsed_time(ev1), r_
 
     def transport_verdict():
         """collective: 1 only if the transport that carried the timed steps reports no overflow / time-out on ANY rank (the peer-mapped
@@ -1166,7 +1194,7 @@ def main():
         dist.all_reduce(okt, op=dist.ReduceOp.MIN)
         return int(okt.item())
 
-    elapsed, ev_ms = timed_region()
+    elapsed, ev_ms, last_r = timed_region()
     if sharded and carrier != "rccl" and transport_verdict() == 0:
         # a measured number must not come from steps that dropped keys or timed out: every rank switches to the torch.distributed
         # path and the region is run again (an automated N = 2 / 4 / 8 sweep still gets its line, labelled with what happened)
@@ -1177,7 +1205,10 @@ def main():
         for i in range(max(args.warmup, 2)):
             step(i)
         torch.cuda.synchronize(dev)
-        elapsed, ev_ms = timed_region()
+        elapsed, ev_ms, last_r = timed_region()
+    if args.dump_outputs and rank == 0:   # before anything else runs: the peer-mapped transport's results are views, valid until its next find
+        dump_outputs(args.dump_outputs, *last_r)
+        log(f"outputs of timed step {args.steps - 1} written to {args.dump_outputs}")
 
     # ---- N > 1: SURVEY 8d config 4 (iii) in the SAME line: the uniform stream and Zipf(1.05) without and with pre-exchange dedup, each over every
     # carrier that can run it (verified against the torch.distributed path in the probe), best one reported with its bytes on the busiest link.

@@ -62,6 +62,46 @@ def test_bench_single_gpu_contract(dev):
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs(dev, tmp_path):
+    """--dump-outputs: what the last timed step returned, float32 / float64 .npy files within 64 MB, the same from run to run (seeded inputs).
+    Find mode at the default 256K-key batch (64 MB of rows: a fixed sample of positions); train mode at a batch that fits whole."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from meepoembedding_amd import synth
+
+    def run(tag, *extra):
+        d = tmp_path / tag
+        res = _one_json_line([sys.executable, "bench.py", "--steps", "7", "--warmup", "3", "--keys", "2000000", "--no-streams", "--no-cpu-baseline",
+                              "--dump-outputs", str(d), *extra])
+        assert res["steps"] == 7 and res["ms_per_step"] > 0
+        assert abs(res["value"] * res["ms_per_step"] / 1e3 - res["config"]["batch_per_rank"]) < 1e-6 * res["value"]
+        files = sorted(os.listdir(d))
+        assert files == ["found.npy", "index.npy", "rows.npy"], files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64_000_000
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        return res, arrs
+
+    res, a = run("find_a")
+    batch = res["config"]["batch_per_rank"]
+    idx = a["index"].astype(np.int64)
+    assert 0 < len(idx) < batch and np.all(np.diff(idx) > 0) and idx[-1] < batch and a["rows"].shape == (len(idx), 64)
+    last = bench.lookup_batches(synth, 2_000_000, batch, 64, "uniform", dev, seed=3)[7 - 1]   # the 7th timed step's batch
+    want = synth.rows_t(last[torch.from_numpy(idx).to(dev)], 64, 2).cpu().numpy()
+    assert np.all(a["found"] == 1.0) and np.array_equal(a["rows"], want)
+    _, b = run("find_b")
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    _, a = run("train_a", "--mode", "train", "--batch", "65536")
+    _, b = run("train_b", "--mode", "train", "--batch", "65536")
+    assert np.array_equal(a["index"], np.arange(65536)) and np.all(a["found"] == 1.0)
+    np.testing.assert_array_equal(a["found"], b["found"])
+    np.testing.assert_allclose(a["rows"], b["rows"], rtol=1e-6, atol=1e-9)
+
+
+@pytest.mark.gpu
 def test_bench_two_rank_rehearsal(dev):
     res = _one_json_line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--backend", "gloo", "--keys", "2000000", "--batch", "65536",

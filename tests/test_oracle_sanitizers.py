@@ -10,7 +10,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_oracle_under_asan_ubsan(built):
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "asan"])
     libasan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"], text=True).strip()
-    env = dict(os.environ, LD_PRELOAD=libasan, ASAN_OPTIONS="detect_leaks=0")
+    # the ASan runtime must come first; anything the environment already preloads stays behind it
+    preload = " ".join(p for p in (libasan, os.environ.get("LD_PRELOAD", "")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "asan_oracle.py")], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "run clean" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
@@ -31,6 +33,5 @@ def test_cabi_host_side_under_sanitizers(built, sanitizer):
     subprocess.check_call(["bash", os.path.join(ROOT, "tests", "cabi", "build_sanitized.sh"), sanitizer, out], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     env = dict(os.environ, MEE_RCCL_LIB=os.path.join(out, "libfake_rccl.so"), MEE_FAKE_RCCL_SLOT_MB="8", ASAN_OPTIONS="detect_leaks=0",
                TSAN_OPTIONS="halt_on_error=1 exitcode=66")
-    env.pop("LD_PRELOAD", None)
     r = subprocess.run([os.path.join(out, "sanitize_host"), "8"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "sanitize_host ok" in r.stdout and "Sanitizer" not in r.stderr, r.stdout[-1000:] + r.stderr[-6000:]
