@@ -187,6 +187,27 @@ int mee_hits_scan(mee_table* t, uint32_t min_hits, uint32_t max_hits, int reset,
 enum { MEE_POOL_SUM = 0, MEE_POOL_MEAN = 1 };
 int mee_find_pooled(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, float* d_out,
                     uint8_t* d_found, int mode, void* stream);
+/* Weighted pooled lookup (torch.nn.EmbeddingBag with per_sample_weights; SUM only): d_weights = one fp32 weight per key position
+ * (device, indexed like d_keys).  d_out[b,:] = the rows mee_find would return for the bag's positions, each multiplied by its weight
+ * and added in position order in fp32: acc = w_first * row_first, then acc = acc + (w_i * row_i) — every product rounded, then every
+ * sum (no fma).  With all weights 1.0f the result is bit-identical to mee_find_pooled(MEE_POOL_SUM).  An empty bag gives zeros; absent
+ * and reserved keys contribute w_i * the default row.  d_found (nullable) as in mee_find_pooled.  d_located_out (nullable, int64[n])
+ * receives each position's slot handle in the format of mee_find_located (-1 = absent): mee_apply_*_located and
+ * mee_pooled_weighted_backward of the same step accept it.  Offsets past n are cut at n, a decreasing pair is an empty bag. */
+int mee_find_pooled_weighted(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
+                             const float* d_weights, float* d_out, uint8_t* d_found, int64_t* d_located_out, void* stream);
+/* Its backward, before the table step: d_grads_out[i,:] = d_weights[i] * d_bag_grads[bag(i),:] (one fp32 multiply per element;
+ * d_bag_grads = [n_bags, dim]) and, when d_weight_grads_out (nullable, fp32[n]) is given, d_weight_grads_out[i] = sum_j
+ * d_bag_grads[bag(i), j] * row_i[j], row_i = the row mee_find returns for key i at the time of the call (the default row when absent):
+ * products and sum in fp64, rounded once to fp32 (the order of the sum is unspecified).  Without d_weight_grads_out no table row is
+ * read.  d_located (nullable) = the handles mee_find_pooled_weighted of this step wrote: the rows are read through them instead of a
+ * probe (a handle of another layout epoch is probed again).  Positions that no bag covers are not written (nor do they get a handle
+ * from the forward), so the table step may only be given covered positions: the step is exactly mee_apply_*(d_keys, d_grads_out) —
+ * or mee_apply_*_located with the same handles — when the bags partition [0, n) (d_bag_offsets[0] = 0, d_bag_offsets[n_bags] = n,
+ * non-decreasing), as a batch of samples' bags does. */
+int mee_pooled_weighted_backward(const mee_table* t, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,
+                                 size_t n_bags, const float* d_weights, const float* d_bag_grads, float* d_grads_out, float* d_weight_grads_out,
+                                 void* stream);
 /* upsert; duplicate keys: last occurrence wins. */
 int mee_insert(mee_table* t, const int64_t* d_keys, const float* d_values, size_t n, void* stream);
 /* overwrite only if present; d_found nullable; duplicates: last occurrence wins. */
@@ -293,6 +314,14 @@ int mee_group_apply_adagrad_pooled(mee_group* g, const int64_t* d_keys, const ui
 int mee_group_apply_adam_pooled(mee_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table,
                                 const float* d_bag_grads, const uint32_t* d_grad_index, const int64_t* d_located, size_t n, float lr,
                                 float beta1, float beta2, float eps, uint64_t step, void* stream);
+/* The weighted forms over the collection: mee_find_pooled_weighted / mee_pooled_weighted_backward on every member, bag b belonging to
+ * member b / bags_per_table, in one launch each.  d_located_out / d_located are in the group's format (as mee_group_find_pooled's); the
+ * step after the backward is mee_group_apply_*(d_keys, member offsets, d_grads_out) — the grads are per position, not per bag. */
+int mee_group_find_pooled_weighted(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                                   const float* d_weights, float* d_out, uint8_t* d_found, int64_t* d_located_out, void* stream);
+int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,
+                                       size_t bags_per_table, const float* d_weights, const float* d_bag_grads, float* d_grads_out,
+                                       float* d_weight_grads_out, void* stream);
 
 /* ---- sparse optimizers (north_star "sparse-optimizer (Adagrad/Adam) scatter-update"; SPEC.md §4) -------- */
 int mee_apply_adagrad(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, float lr, float eps,

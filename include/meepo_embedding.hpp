@@ -68,6 +68,10 @@ public:
     void find_pooled(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, float* d_out, uint8_t* d_found = nullptr, int mode = MEE_POOL_SUM, void* stream = nullptr) const {
         check(mee_find_pooled(t_, d_keys, n, d_bag_offsets, n_bags, d_out, d_found, mode, stream));
     }
+    // weighted embedding bag (SUM): d_out[b,:] = sum of d_weights[i] * row_i over the bag in position order; d_located_out = mee_find_located handles
+    void find_pooled_weighted(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const float* d_weights, float* d_out, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, void* stream = nullptr) const { check(mee_find_pooled_weighted(t_, d_keys, n, d_bag_offsets, n_bags, d_weights, d_out, d_found, d_located_out, stream)); }
+    // its backward: d_grads_out[i,:] = d_weights[i] * d_bag_grads[bag(i),:] (feed to apply_*), d_weight_grads_out[i] = <d_bag_grads[bag(i)], row_i> (nullable)
+    void pooled_weighted_backward(const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const float* d_weights, const float* d_bag_grads, float* d_grads_out, float* d_weight_grads_out = nullptr, void* stream = nullptr) const { check(mee_pooled_weighted_backward(t_, d_keys, d_located, n, d_bag_offsets, n_bags, d_weights, d_bag_grads, d_grads_out, d_weight_grads_out, stream)); }
     // second-tier pass: fills only the positions an earlier find (on another table) left with d_found == 0
     void find_missing(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream = nullptr) const { check(mee_find_missing(t_, d_keys, n, d_out, d_found, stream)); }
     void insert(const int64_t* d_keys, const float* d_values, size_t n, void* stream = nullptr) { check(mee_insert(t_, d_keys, d_values, n, stream)); }
@@ -152,6 +156,9 @@ public:
     void apply_adam(const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr, uint64_t step, float beta1 = 0.9f, float beta2 = 0.999f, float eps = 1e-8f, void* stream = nullptr) {
         check(mee_group_apply_adam(g_, d_keys, d_offsets, d_grads, n, lr, beta1, beta2, eps, step, stream));
     }
+    // the weighted embedding-bag collection: bag b belongs to member b / bags_per_table (mee_group_find_pooled_weighted / mee_group_pooled_weighted_backward)
+    void find_pooled_weighted(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights, float* d_out, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, void* stream = nullptr) { check(mee_group_find_pooled_weighted(g_, d_keys, n, d_bag_offsets, bags_per_table, d_weights, d_out, d_found, d_located_out, stream)); }
+    void pooled_weighted_backward(const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights, const float* d_bag_grads, float* d_grads_out, float* d_weight_grads_out = nullptr, void* stream = nullptr) { check(mee_group_pooled_weighted_backward(g_, d_keys, d_located, n, d_bag_offsets, bags_per_table, d_weights, d_bag_grads, d_grads_out, d_weight_grads_out, stream)); }
 private:
     mee_group* g_ = nullptr;
 };

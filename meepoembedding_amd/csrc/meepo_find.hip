@@ -295,12 +295,14 @@ __global__ __launch_bounds__(256) void find_missing_kernel(const int64_t* __rest
 // other tiles' registers (shuffles), so a long bag has 4U keys in flight instead of U.
 constexpr uint32_t kPoolLong = 16;
 
-// probe + row load of up to U keys per tile (the find_kernel pattern); row[u] is only defined where inb[u]
-template <int DIM4, int U, int C>
+// probe + row load of up to U keys per tile (the find_kernel pattern); row[u] is only defined where inb[u].
+// located (nullable) receives tag | slot per position: tag = member << kGroupSlotBits for a group (EMPTY when absent), or the table's
+// handle tag (handle_tag_of) for one table with TAGGED (-1 when absent: the format of mee_find_located)
+template <int DIM4, int U, int C, bool TAGGED = false>
 __device__ __forceinline__ void pooled_fetch(const int64_t* __restrict__ tkeys, const float4* __restrict__ values, uint64_t nb,
                                              uint32_t dim4, const int64_t (&key)[U], const uint64_t (&pos)[U],
                                              const bool (&inb)[U], int tile, int tl, float4 def4, float4 (&row)[U][C],
-                                             uint8_t* __restrict__ found, int64_t* __restrict__ located = nullptr, uint64_t member = 0) {
+                                             uint8_t* __restrict__ found, int64_t* __restrict__ located = nullptr, uint64_t tag = 0) {
     int64_t slot[U], kb[U];
     uint64_t bk[U];
     bool act[U];
@@ -335,27 +337,31 @@ __device__ __forceinline__ void pooled_fetch(const int64_t* __restrict__ tkeys, 
             if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4)
                 row[u][c] = slot[u] >= 0 ? values[(uint64_t)slot[u] * dim4 + c * 16 + tl] : def4;
         if (found && inb[u] && tl == 0) found[pos[u]] = slot[u] >= 0;
-        // the located row (member << 48 | slot, EMPTY when absent): lets the backward skip its own probe pass
-        if (located && inb[u] && tl == 0) located[pos[u]] = slot[u] >= 0 ? (int64_t)((member << kGroupSlotBits) | (uint64_t)slot[u]) : kEmpty;
+        // the located row: lets the backward skip its own probe pass
+        if (located && inb[u] && tl == 0) located[pos[u]] = slot[u] >= 0 ? (int64_t)(tag | (uint64_t)slot[u]) : (TAGGED ? -1 : kEmpty);
     }
 }
 
 // BPW = bags per wave: 4 = the hybrid above (batches of mostly short bags), 1 = every bag gets a whole wave (batches whose
 // AVERAGE bag is long: a wave that had to walk four long bags one after the other would be latency-bound).
 // GROUPED (mee_group_find_pooled): bag b belongs to member table b / bags_per_table; the planes come from its descriptor.
-template <int DIM4, int U, int BPW, bool GROUPED = false>
+// WEIGHTED (mee_find_pooled_weighted / mee_group_find_pooled_weighted): position i adds weights[i] * row_i — the product rounded, then
+// the sum (no fma; the first position's product is the initial sum); SUM only.  A single table's located rows then carry its handle tag.
+template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restrict__ tkeys_, const float4* __restrict__ values_,
                                                           uint64_t nb_, const int64_t* __restrict__ keys,
                                                           const uint64_t* __restrict__ offsets, uint64_t n_bags,
                                                           float4* __restrict__ out, uint8_t* __restrict__ found, float defv,
                                                           uint32_t dim4_rt, int mean, const GroupDesc* __restrict__ desc = nullptr,
                                                           uint64_t bags_per_table = 1, int64_t* __restrict__ located = nullptr,
-                                                          uint64_t n_keys = ~0ull) {
+                                                          uint64_t n_keys = ~0ull, const float* __restrict__ weights = nullptr,
+                                                          int64_t handle_tag = 0) {
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
     const uint32_t dim4 = DIM4 ? DIM4 : dim4_rt;
     constexpr int C = DIM4 ? DIM4 / 16 : 16;   // float4 per lane per row (any dim: up to 1024 floats = 16 per lane)
+    constexpr bool TAGGED = WEIGHTED && !GROUPED;
     for (uint64_t b0 = wave * BPW; b0 < n_bags; b0 += n_waves * BPW) {
         const uint64_t bag = BPW == 4 ? b0 + tile : b0;
         const bool has = bag < n_bags;
@@ -383,24 +389,36 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
             for (int c = 0; c < C; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
             // a short bag has fewer than 16 keys: its tile fetches them all with one coalesced load, lane tl holds key begin + tl
             const int64_t kpre = (!is_long && begin + tl < end) ? keys[begin + tl] : kEmpty;
+            float wpre = 0.f;   // the same for the weights
+            if constexpr (WEIGHTED) wpre = (!is_long && begin + tl < end) ? weights[begin + tl] : 0.f;
             while (__any(i < end)) {  // wave-uniform; tiles whose bag is done idle through the ballots
                 uint64_t pos[U];
                 int64_t kv[U];
+                float wv[U];
                 bool inb[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     pos[u] = i + u; inb[u] = pos[u] < end;
                     kv[u] = __shfl(kpre, tile * 16 + (int)((pos[u] - begin) & 15));
+                    if constexpr (WEIGHTED) wv[u] = __shfl(wpre, tile * 16 + (int)((pos[u] - begin) & 15));
                 }
-                pooled_fetch<DIM4, U, C>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located, member);
+                pooled_fetch<DIM4, U, C, TAGGED>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located,
+                                                 GROUPED ? member << kGroupSlotBits : (TAGGED ? (uint64_t)handle_tag : 0));
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     if (!inb[u]) continue;
 #pragma unroll
                     for (int c = 0; c < C; ++c)
                         if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
-                            if (first) acc[c] = row[u][c];
-                            else { acc[c].x += row[u][c].x; acc[c].y += row[u][c].y; acc[c].z += row[u][c].z; acc[c].w += row[u][c].w; }
+                            if constexpr (WEIGHTED) {   // (the unweighted instances keep their code exactly)
+                                float4 v = row[u][c];
+                                v.x = wv[u] * v.x; v.y = wv[u] * v.y; v.z = wv[u] * v.z; v.w = wv[u] * v.w;
+                                if (first) acc[c] = v;
+                                else { acc[c].x += v.x; acc[c].y += v.y; acc[c].z += v.z; acc[c].w += v.w; }
+                            } else {
+                                if (first) acc[c] = row[u][c];
+                                else { acc[c].x += row[u][c].x; acc[c].y += row[u][c].y; acc[c].z += row[u][c].z; acc[c].w += row[u][c].w; }
+                            }
                         }
                     first = false;
                 }
@@ -434,20 +452,28 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
             for (uint64_t i = bq; i < eq; i += 4 * U) {   // wave-uniform
                 uint64_t pos[U];
                 int64_t kv[U];
+                float wv[U];
                 bool inb[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) { pos[u] = i + (uint64_t)u * 4 + tile; inb[u] = pos[u] < eq; kv[u] = inb[u] ? keys[pos[u]] : kEmpty; }
-                pooled_fetch<DIM4, U, C>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located, member);
+                for (int u = 0; u < U; ++u) {
+                    pos[u] = i + (uint64_t)u * 4 + tile; inb[u] = pos[u] < eq; kv[u] = inb[u] ? keys[pos[u]] : kEmpty;
+                    if constexpr (WEIGHTED) wv[u] = inb[u] ? weights[pos[u]] : 0.f;   // next to the key
+                }
+                pooled_fetch<DIM4, U, C, TAGGED>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located,
+                                                 GROUPED ? member << kGroupSlotBits : (TAGGED ? (uint64_t)handle_tag : 0));
 #pragma unroll
                 for (int u = 0; u < U; ++u)
 #pragma unroll
                     for (int src = 0; src < 4; ++src) {
                         if (i + (uint64_t)u * 4 + src >= eq) continue;   // wave-uniform
+                        float w = 0.f;
+                        if constexpr (WEIGHTED) w = __shfl(wv[u], src * 16 + tl);
 #pragma unroll
                         for (int c = 0; c < C; ++c) {
                             float4 v;   // every tile reads the row tile `src` fetched: all four keep the same running sum
                             v.x = __shfl(row[u][c].x, src * 16 + tl); v.y = __shfl(row[u][c].y, src * 16 + tl);
                             v.z = __shfl(row[u][c].z, src * 16 + tl); v.w = __shfl(row[u][c].w, src * 16 + tl);
+                            if constexpr (WEIGHTED) { v.x = w * v.x; v.y = w * v.y; v.z = w * v.z; v.w = w * v.w; }
                             if (first) acc[c] = v;
                             else { acc[c].x += v.x; acc[c].y += v.y; acc[c].z += v.z; acc[c].w += v.w; }
                         }
@@ -463,6 +489,160 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                         if (mean && eq > bq) { v.x = v.x / len; v.y = v.y / len; v.z = v.z / len; v.w = v.w / len; }
                         out[(b0 + q) * dim4 + c * 16 + tl] = v;
                     }
+            }
+        }
+    }
+}
+
+// ---- backward of the weighted pooled lookup (SPEC.md §3) ------------------------------------------------------------------
+// grads[i] = weights[i] * bag_grads[bag(i)] (one fp32 multiply per element) and, when weight_grads is given, weight_grads[i] =
+// sum_j bag_grads[bag(i), j] * row_i[j] in fp64, rounded once.  The bag-to-wave geometry of find_pooled_kernel: a tile per short bag,
+// the wave's four tiles on one long bag (tile t takes positions i + 4u + t), or a wave per bag (BPW 1).  The bag's grad row is loaded
+// into registers once.  Nothing here depends on the order of positions, so a long bag needs no exchange between tiles.
+
+// the U positions one tile handles in one round: store w * G, then (weight_grads) fetch the rows and reduce the dot products across
+// the tile's 16 lanes.  A row comes through its handle when the caller passed one (`handles`), otherwise from a probe (pooled_fetch);
+// a handle of an absent key reads the default row, a handle the table cannot vouch for (another layout epoch, out of range, another
+// member) falls back to the probe.
+template <int DIM4, int U, int C, bool GROUPED>
+__device__ __forceinline__ void pooled_bwd_positions(const int64_t* __restrict__ tkeys, const float4* __restrict__ values, uint64_t nb,
+                                                     uint64_t capacity, uint32_t dim4, const int64_t (&key)[U], const uint64_t (&pos)[U],
+                                                     const bool (&inb)[U], const float (&w)[U], const int64_t* __restrict__ handles,
+                                                     int64_t handle_tag, uint64_t member, int tile, int tl, float4 def4, const float4 (&g)[C],
+                                                     float4* __restrict__ grads, float* __restrict__ weight_grads) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (!inb[u]) continue;
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4)
+                grads[pos[u] * dim4 + c * 16 + tl] = make_float4(w[u] * g[c].x, w[u] * g[c].y, w[u] * g[c].z, w[u] * g[c].w);
+    }
+    if (!weight_grads) return;   // kernel-uniform: no table row is read
+    bool probe[U];
+    int64_t hs[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        hs[u] = -1;
+        probe[u] = inb[u];
+        if (handles && inb[u]) {
+            const int64_t h = handles[pos[u]];
+            if (h < 0) probe[u] = false;   // absent when the forward ran: the default row
+            else if constexpr (GROUPED) {
+                const uint64_t s = (uint64_t)h & ((1ull << kGroupSlotBits) - 1);
+                if (((uint64_t)h >> kGroupSlotBits) == member && s < capacity) { hs[u] = (int64_t)s; probe[u] = false; }
+            } else {
+                bool stale;
+                hs[u] = handle_slot(h, handle_tag, capacity, stale);
+                probe[u] = hs[u] < 0;
+            }
+        }
+    }
+    float4 row[U][C];
+    pooled_fetch<DIM4, U, C>(tkeys, values, nb, dim4, key, pos, probe, tile, tl, def4, row, nullptr);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (hs[u] >= 0) {
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+                if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) row[u][c] = values[(uint64_t)hs[u] * dim4 + c * 16 + tl];
+        }
+        double s = 0.0;
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            if (inb[u] && (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4)) {
+                s += (double)g[c].x * (double)row[u][c].x; s += (double)g[c].y * (double)row[u][c].y;
+                s += (double)g[c].z * (double)row[u][c].z; s += (double)g[c].w * (double)row[u][c].w;
+            }
+#pragma unroll
+        for (int m = 8; m >= 1; m >>= 1) s += __shfl_xor(s, m);   // across the tile's 16 lanes
+        if (inb[u] && tl == 0) weight_grads[pos[u]] = (float)s;
+    }
+}
+
+template <int DIM4, int U, int BPW, bool GROUPED = false>
+__global__ __launch_bounds__(256) void pooled_weighted_backward_kernel(const int64_t* __restrict__ tkeys_, const float4* __restrict__ values_,
+                                                                       uint64_t nb_, uint64_t capacity_, const int64_t* __restrict__ keys,
+                                                                       const int64_t* __restrict__ handles, int64_t handle_tag,
+                                                                       const uint64_t* __restrict__ offsets, uint64_t n_bags,
+                                                                       const float* __restrict__ weights, const float4* __restrict__ bag_grads,
+                                                                       float4* __restrict__ grads, float* __restrict__ weight_grads, float defv,
+                                                                       uint32_t dim4_rt, const GroupDesc* __restrict__ desc,
+                                                                       uint64_t bags_per_table, uint64_t n_keys) {
+    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    const uint32_t dim4 = DIM4 ? DIM4 : dim4_rt;
+    constexpr int C = DIM4 ? DIM4 / 16 : 16;
+    for (uint64_t b0 = wave * BPW; b0 < n_bags; b0 += n_waves * BPW) {
+        const uint64_t bag = BPW == 4 ? b0 + tile : b0;
+        const bool has = bag < n_bags;
+        uint64_t begin = has ? offsets[bag] : 0, end = has ? offsets[bag + 1] : 0;
+        end = end < n_keys ? end : n_keys;          // the forward's clamps: never past the key array,
+        begin = begin < end ? begin : end;          // and a decreasing pair is an empty bag
+        const int64_t* tkeys = tkeys_;
+        const float4* values = values_;
+        uint64_t nb = nb_, capacity = capacity_;
+        float4 def4 = make_float4(defv, defv, defv, defv);
+        uint64_t member = 0;
+        if constexpr (GROUPED) {
+            member = (has ? bag : 0) / bags_per_table;
+            const GroupDesc d = desc[member];
+            tkeys = d.tkeys; values = d.values; nb = d.nb; capacity = d.nb * kW; def4 = make_float4(d.defv, d.defv, d.defv, d.defv);
+        }
+        const bool is_long = BPW == 1 || end - begin >= kPoolLong;
+        float4 g[C];
+        // ---- short bags: one tile per bag ----
+        if constexpr (BPW == 4) {
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+                g[c] = (has && !is_long && end > begin && (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4)) ? bag_grads[bag * dim4 + c * 16 + tl]
+                                                                                                         : make_float4(0.f, 0.f, 0.f, 0.f);
+            uint64_t i = is_long ? end : begin;
+            const int64_t kpre = (!is_long && begin + tl < end) ? keys[begin + tl] : kEmpty;
+            const float wpre = (!is_long && begin + tl < end) ? weights[begin + tl] : 0.f;
+            while (__any(i < end)) {  // wave-uniform
+                uint64_t pos[U];
+                int64_t kv[U];
+                float wv[U];
+                bool inb[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    pos[u] = i + u; inb[u] = pos[u] < end;
+                    kv[u] = __shfl(kpre, tile * 16 + (int)((pos[u] - begin) & 15));
+                    wv[u] = __shfl(wpre, tile * 16 + (int)((pos[u] - begin) & 15));
+                }
+                pooled_bwd_positions<DIM4, U, C, GROUPED>(tkeys, values, nb, capacity, dim4, kv, pos, inb, wv, handles, handle_tag, member,
+                                                          tile, tl, def4, g, grads, weight_grads);
+                i += U;
+            }
+        }
+        // ---- long bags: the four tiles share one bag at a time ----
+        const uint64_t long_mask = __ballot(is_long && has);
+        if (!long_mask) continue;   // wave-uniform
+        for (int q = 0; q < BPW; ++q) {
+            if (!((long_mask >> (q * 16)) & 1)) continue;   // wave-uniform
+            const uint64_t bq = __shfl(begin, q * 16), eq = __shfl(end, q * 16);
+            if constexpr (GROUPED && BPW == 4) {
+                member = (b0 + q) / bags_per_table;
+                const GroupDesc d = desc[member];
+                tkeys = d.tkeys; values = d.values; nb = d.nb; capacity = d.nb * kW; def4 = make_float4(d.defv, d.defv, d.defv, d.defv);
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+                g[c] = (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) ? bag_grads[(b0 + q) * dim4 + c * 16 + tl] : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (uint64_t i = bq; i < eq; i += 4 * U) {   // wave-uniform
+                uint64_t pos[U];
+                int64_t kv[U];
+                float wv[U];
+                bool inb[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    pos[u] = i + (uint64_t)u * 4 + tile; inb[u] = pos[u] < eq;
+                    kv[u] = inb[u] ? keys[pos[u]] : kEmpty; wv[u] = inb[u] ? weights[pos[u]] : 0.f;
+                }
+                pooled_bwd_positions<DIM4, U, C, GROUPED>(tkeys, values, nb, capacity, dim4, kv, pos, inb, wv, handles, handle_tag, member,
+                                                          tile, tl, def4, g, grads, weight_grads);
             }
         }
     }
@@ -671,6 +851,42 @@ int mee_find_pooled(const mee_table* t, const int64_t* d_keys, size_t n, const u
     return MEE_OK;
 }
 
+int mee_find_pooled_weighted(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
+                             const float* d_weights, float* d_out, uint8_t* d_found, int64_t* d_located_out, void* stream) {
+    MEE_RANGE("mee_find_pooled_weighted");
+    if (!t || (n_bags && (!d_bag_offsets || !d_out)) || (n && (!d_keys || !d_weights)))
+        return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_weighted: null argument");
+    if (n_bags == 0) return MEE_OK;
+    DeviceGuard g(t->device);
+    hipStream_t st = as_stream(stream);
+    const bool wave_per_bag = n / n_bags >= 12;   // the launch shapes of mee_find_pooled
+    const int64_t tag = handle_tag_of(t);          // located rows in the format of mee_find_located
+#define WPOOLED(D4, U1, U4) do { if (wave_per_bag) find_pooled_kernel<D4, U1, 1, false, true><<<grid_for(n_bags, 4, 1u << 20), 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, t->default_value, t->dim4, 0, nullptr, 1, d_located_out, n, d_weights, tag); \
+                                 else find_pooled_kernel<D4, U4, 4, false, true><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, t->default_value, t->dim4, 0, nullptr, 1, d_located_out, n, d_weights, tag); } while (0)
+    if (t->dim4 == 16) WPOOLED(16, 4, 2); else if (t->dim4 == 32) WPOOLED(32, 2, 1); else WPOOLED(0, 1, 1);
+#undef WPOOLED
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+int mee_pooled_weighted_backward(const mee_table* t, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,
+                                 size_t n_bags, const float* d_weights, const float* d_bag_grads, float* d_grads_out, float* d_weight_grads_out,
+                                 void* stream) {
+    MEE_RANGE("mee_pooled_weighted_backward");
+    if (!t || (n_bags && (!d_bag_offsets || !d_bag_grads)) || (n && (!d_keys || !d_weights || !d_grads_out)))
+        return fail(MEE_ERR_INVALID_ARG, "mee_pooled_weighted_backward: null argument");
+    if (n_bags == 0) return MEE_OK;
+    DeviceGuard g(t->device);
+    hipStream_t st = as_stream(stream);
+    const bool wave_per_bag = n / n_bags >= 12;
+#define WBWD(D4, U1, U4) do { if (wave_per_bag) pooled_weighted_backward_kernel<D4, U1, 1><<<grid_for(n_bags, 4, 1u << 20), 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, t->capacity, d_keys, d_located, handle_tag_of(t), d_bag_offsets, n_bags, d_weights, (const float4*)d_bag_grads, (float4*)d_grads_out, d_weight_grads_out, t->default_value, t->dim4, nullptr, 1, n); \
+                              else pooled_weighted_backward_kernel<D4, U4, 4><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, t->capacity, d_keys, d_located, handle_tag_of(t), d_bag_offsets, n_bags, d_weights, (const float4*)d_bag_grads, (float4*)d_grads_out, d_weight_grads_out, t->default_value, t->dim4, nullptr, 1, n); } while (0)
+    if (t->dim4 == 16) WBWD(16, 4, 2); else if (t->dim4 == 32) WBWD(32, 2, 1); else WBWD(0, 1, 1);
+#undef WBWD
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
 int mee_find_plane(const mee_table* t, uint32_t plane, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream) {
     MEE_RANGE("mee_find_plane");
     if (!t || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_plane: null argument");
@@ -695,6 +911,45 @@ int mee_group_find_pooled(mee_group* g, const int64_t* d_keys, size_t n, const u
                                  else find_pooled_kernel<D4, U4, 4, true><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, mode == MEE_POOL_MEAN, g->d_desc, bags_per_table, d_located_out, n); } while (0)
     if (g->dim4 == 16) GPOOLED(16, 4, 2); else if (g->dim4 == 32) GPOOLED(32, 2, 1); else GPOOLED(0, 1, 1);
 #undef GPOOLED
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+int mee_group_find_pooled_weighted(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                                   const float* d_weights, float* d_out, uint8_t* d_found, int64_t* d_located_out, void* stream) {
+    MEE_RANGE("mee_group_find_pooled_weighted");
+    if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && (!d_keys || !d_weights)))
+        return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_weighted: null argument");
+    if (bags_per_table == 0) return MEE_OK;
+    if (int rc = group_refresh(g, stream)) return rc;
+    DeviceGuard guard(g->device);
+    hipStream_t st = as_stream(stream);
+    const uint64_t n_bags = (uint64_t)g->n_tables * bags_per_table;
+    const bool wave_per_bag = n / n_bags >= 12;
+#define GWPOOLED(D4, U1, U4) do { if (wave_per_bag) find_pooled_kernel<D4, U1, 1, true, true><<<grid_for(n_bags, 4, 1u << 20), 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, 0, g->d_desc, bags_per_table, d_located_out, n, d_weights); \
+                                  else find_pooled_kernel<D4, U4, 4, true, true><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, 0, g->d_desc, bags_per_table, d_located_out, n, d_weights); } while (0)
+    if (g->dim4 == 16) GWPOOLED(16, 4, 2); else if (g->dim4 == 32) GWPOOLED(32, 2, 1); else GWPOOLED(0, 1, 1);
+#undef GWPOOLED
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,
+                                       size_t bags_per_table, const float* d_weights, const float* d_bag_grads, float* d_grads_out,
+                                       float* d_weight_grads_out, void* stream) {
+    MEE_RANGE("mee_group_pooled_weighted_backward");
+    if (!g || (bags_per_table && (!d_bag_offsets || !d_bag_grads)) || (n && (!d_keys || !d_weights || !d_grads_out)))
+        return fail(MEE_ERR_INVALID_ARG, "mee_group_pooled_weighted_backward: null argument");
+    if (bags_per_table == 0) return MEE_OK;
+    if (int rc = group_refresh(g, stream)) return rc;
+    DeviceGuard guard(g->device);
+    hipStream_t st = as_stream(stream);
+    const uint64_t n_bags = (uint64_t)g->n_tables * bags_per_table;
+    const bool wave_per_bag = n / n_bags >= 12;
+#define GWBWD(D4, U1, U4) do { if (wave_per_bag) pooled_weighted_backward_kernel<D4, U1, 1, true><<<grid_for(n_bags, 4, 1u << 20), 256, 0, st>>>(nullptr, nullptr, 0, 0, d_keys, d_located, 0, d_bag_offsets, n_bags, d_weights, (const float4*)d_bag_grads, (float4*)d_grads_out, d_weight_grads_out, 0.f, g->dim4, g->d_desc, bags_per_table, n); \
+                               else pooled_weighted_backward_kernel<D4, U4, 4, true><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>(nullptr, nullptr, 0, 0, d_keys, d_located, 0, d_bag_offsets, n_bags, d_weights, (const float4*)d_bag_grads, (float4*)d_grads_out, d_weight_grads_out, 0.f, g->dim4, g->d_desc, bags_per_table, n); } while (0)
+    if (g->dim4 == 16) GWBWD(16, 4, 2); else if (g->dim4 == 32) GWBWD(32, 2, 1); else GWBWD(0, 1, 1);
+#undef GWBWD
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }

@@ -9,6 +9,8 @@
     meepo::lookup_located / meepo::apply_grad_located                 the same pair over ONE HBM table: the forward
                                                                                  (find[_or_insert]_located) hands every key's slot
                                                                                  to the backward, whose apply then does not probe
+    meepo::lookup_pooled[_weighted] / meepo::apply_grad_pooled[_weighted]   embedding bags (sum / mean; weighted sum with the grad of
+                                                                                 the per-sample weights)
 
 The update happens INSIDE backward, so the layer has no torch parameters and needs no torch optimizer.  Both ops have
 fake (meta) kernels, so a model containing the layer traces and exports; they are opaque to the tracer (the table is
@@ -218,6 +220,73 @@ def _backward_pooled(ctx, grad_out, _grad_located):
 lookup_pooled.register_autograd(_backward_pooled, setup_context=_setup_pooled)
 
 
+# ---- weighted pooled (torch.nn.EmbeddingBag's per_sample_weights; SUM only): bag = sum of w_i * row_i ----------------------
+# forward = find_pooled(weights=...), which also hands every position's handle to the backward; backward = pooled_weighted_backward
+# (grads [n, dim] = w_i * the bag's grad row, and the grad of the weights when they need one), then the table's step on those grads
+@torch.library.custom_op("meepo::lookup_pooled_weighted", mutates_args=())
+def lookup_pooled_weighted(keys: torch.Tensor, bag_offsets: torch.Tensor, weights: torch.Tensor, anchor: torch.Tensor,
+                           table_id: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """-> (pooled rows [n_bags, dim], located rows [n] — per-position handles the backward of this step reuses)"""
+    layer = _layer(table_id)
+    if layer.create_missing and layer.training and keys.numel():
+        if hasattr(layer.table, "apply_pooled"):
+            bpt = (bag_offsets.numel() - 1) // len(layer.table.tables)
+            layer.table.find_or_insert(keys, bag_offsets[::bpt].contiguous())
+        else:
+            layer.table.find_or_insert(keys)
+    located = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
+    out, _ = layer.table.find_pooled(keys, bag_offsets, "sum", weights=weights.contiguous(), located=located)
+    return out, located
+
+
+@lookup_pooled_weighted.register_fake
+def _(keys, bag_offsets, weights, anchor, table_id):
+    return (keys.new_empty((bag_offsets.numel() - 1, _layer(table_id).table.dim), dtype=torch.float32), keys.new_empty(keys.numel()))
+
+
+@torch.library.custom_op("meepo::apply_grad_pooled_weighted", mutates_args=())
+def apply_grad_pooled_weighted(keys: torch.Tensor, bag_offsets: torch.Tensor, weights: torch.Tensor, grad_bags: torch.Tensor,
+                               located: torch.Tensor, table_id: int, weight_grad: bool) -> torch.Tensor:
+    """The table step of a weighted bag; -> the grad of the weights ([n]; empty unless weight_grad)."""
+    layer = _layer(table_id)
+    loc = located if located.numel() == keys.numel() else None
+    grads, wg = layer.table.pooled_weighted_backward(keys, bag_offsets, weights.contiguous(), grad_bags.contiguous(), located=loc,
+                                                     want_weight_grads=weight_grad)
+    layer.step += 1
+    kw = dict(lr=layer.lr, eps=layer.eps) if layer.optimizer == "adagrad" else \
+        dict(lr=layer.lr, beta1=layer.betas[0], beta2=layer.betas[1], eps=layer.eps, step=layer.step)
+    apply = layer.table.apply_adagrad if layer.optimizer == "adagrad" else layer.table.apply_adam
+    if hasattr(layer.table, "apply_pooled"):   # a TableGroup: one grouped step over the members' key segments (it probes for itself)
+        apply(keys, bag_offsets[::(bag_offsets.numel() - 1) // len(layer.table.tables)].contiguous(), grads, **kw)
+    else:
+        apply(keys, grads, slots=loc, **kw)
+    return wg if wg is not None else grads.new_empty(0)
+
+
+@apply_grad_pooled_weighted.register_fake
+def _(keys, bag_offsets, weights, grad_bags, located, table_id, weight_grad):
+    return grad_bags.new_empty(keys.numel() if weight_grad else 0)
+
+
+def _setup_pooled_weighted(ctx, inputs, output):
+    keys, bag_offsets, weights, _, table_id = inputs
+    ctx.save_for_backward(keys, bag_offsets, weights, output[1])
+    ctx.table_id = table_id
+    ctx.layout_epoch = getattr(_layer(table_id).table, "layout_epoch", None)   # as _setup_pooled
+    ctx.mark_non_differentiable(output[1])
+
+
+def _backward_pooled_weighted(ctx, grad_out, _grad_located):
+    keys, bag_offsets, weights, located = ctx.saved_tensors
+    if getattr(_layer(ctx.table_id).table, "layout_epoch", None) != ctx.layout_epoch:
+        located = located.new_empty(0)   # a table changed between forward and backward: the backward probes for itself
+    wg = apply_grad_pooled_weighted(keys, bag_offsets, weights, grad_out.contiguous(), located, ctx.table_id, ctx.needs_input_grad[2])
+    return None, None, (wg.view(weights.shape) if ctx.needs_input_grad[2] else None), None, None
+
+
+lookup_pooled_weighted.register_autograd(_backward_pooled_weighted, setup_context=_setup_pooled_weighted)
+
+
 # ---- the same pair of ops over a TableGroup: the whole embedding collection of a model in one lookup / one update -------
 @torch.library.custom_op("meepo::lookup_jagged", mutates_args=())
 def lookup_jagged(keys: torch.Tensor, offsets: torch.Tensor, anchor: torch.Tensor, table_id: int, insert_missing: bool) -> torch.Tensor:
@@ -304,8 +373,14 @@ class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
         self.table, self.mode, self.create_missing = table, mode, create_missing
         self._init_settings(optimizer, lr, eps, betas)
 
-    def forward(self, keys: torch.Tensor, bag_offsets: torch.Tensor) -> torch.Tensor:
-        return lookup_pooled(keys, bag_offsets, self._anchor, self.table_id, self.mode == "mean")[0]
+    def forward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, per_sample_weights: torch.Tensor | None = None) -> torch.Tensor:
+        """per_sample_weights (fp32 [n], mode "sum" only): the bag is the sum of w_i * row_i; backward also yields their grad.
+        The weighted backward updates every position, so its bags must partition the keys: bag_offsets[0] = 0, bag_offsets[-1] = n."""
+        if per_sample_weights is None:
+            return lookup_pooled(keys, bag_offsets, self._anchor, self.table_id, self.mode == "mean")[0]
+        if self.mode != "sum":
+            raise ValueError("per_sample_weights are only supported for mode='sum', as in torch.nn.EmbeddingBag")
+        return lookup_pooled_weighted(keys, bag_offsets, per_sample_weights, self._anchor, self.table_id)[0]
 
 
 class DynamicEmbedding(torch.nn.Module):

@@ -22,6 +22,15 @@ def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def _check_weights(weights: torch.Tensor, mode: str, n: int, device: torch.device) -> torch.Tensor:
+    """per_sample_weights of a weighted pooled lookup: checked like bag_offsets, before any launch"""
+    if mode != "sum":
+        raise ValueError(f"weighted pooling supports mode='sum' only (got {mode!r}), as torch.nn.EmbeddingBag does")
+    if weights.dtype != torch.float32 or weights.device != device or weights.numel() != n or not weights.is_contiguous():
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"weights must be contiguous float32 with one entry per key ({n}) on {device}")
+    return weights.view(-1)
+
+
 class LookupTable:
     """One HBM-resident shard: int64 key -> fp32[dim] row (+ optimizer state planes)."""
 
@@ -121,22 +130,59 @@ class LookupTable:
         check(_lib.lib().mee_find_many(self._h, reqs, len(requests), self._s()))
         return [(o, f) for o, f, _ in res]
 
-    def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
-                    found: torch.Tensor | None = None):
-        """Embedding-bag lookup: bag b = keys[bag_offsets[b]:bag_offsets[b+1]] (int64 offsets on the device) -> ([n_bags, dim]
-        sums or means in position order, per-key found mask).  One output row per bag is written instead of one per key."""
-        k = self._keys(keys) if keys.numel() else keys
+    def _bag_offsets(self, bag_offsets: torch.Tensor) -> int:
         if bag_offsets.device != self.device or bag_offsets.dtype not in (torch.int64, torch.uint64) or not bag_offsets.is_contiguous() \
                 or bag_offsets.numel() < 1:
             raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_offsets must be contiguous int64 on {self.device} with n_bags + 1 entries")
-        n_bags = bag_offsets.numel() - 1
+        return bag_offsets.numel() - 1
+
+    def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
+                    found: torch.Tensor | None = None, weights: torch.Tensor | None = None, located: torch.Tensor | None = None):
+        """Embedding-bag lookup: bag b = keys[bag_offsets[b]:bag_offsets[b+1]] (int64 offsets on the device) -> ([n_bags, dim]
+        sums or means in position order, per-key found mask).  One output row per bag is written instead of one per key.
+        weights (fp32 [n], mee_find_pooled_weighted; mode "sum" only): the bag is the sum of weights[i] * row_i.  located (int64[n]
+        buffer, weighted form only) receives each key's slot handle for pooled_weighted_backward / apply_*(slots=...) of the same step."""
+        k = self._keys(keys) if keys.numel() else keys
+        n_bags = self._bag_offsets(bag_offsets)
+        if weights is not None:
+            w = _check_weights(weights, mode, k.numel(), self.device)
+        elif located is not None:
+            raise ValueError("find_pooled(located=...) is the weighted form's output: pass weights (all ones for a plain sum)")
+        if located is not None and (located.dtype != torch.int64 or located.device != self.device or located.numel() != k.numel()
+                                    or not located.is_contiguous()):
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"located must be a contiguous int64 buffer of {k.numel()} entries on {self.device}")
         if out is None:
             out = torch.empty((n_bags, self.dim), dtype=torch.float32, device=self.device)
         if found is None:
             found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
+        if weights is not None:
+            check(_lib.lib().mee_find_pooled_weighted(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), n_bags, w.data_ptr(), out.data_ptr(),
+                                                      found.data_ptr(), located.data_ptr() if located is not None else None, self._s()))
+            return out, found
         check(_lib.lib().mee_find_pooled(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), n_bags, out.data_ptr(), found.data_ptr(),
                                          {"sum": 0, "mean": 1}[mode], self._s()))
         return out, found
+
+    def pooled_weighted_backward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, weights: torch.Tensor, bag_grads: torch.Tensor,
+                                 located: torch.Tensor | None = None, want_weight_grads: bool = True, grads: torch.Tensor | None = None,
+                                 weight_grads: torch.Tensor | None = None):
+        """Backward of find_pooled(weights=...) (mee_pooled_weighted_backward) -> (grads [n, dim] = weights[i] * bag_grads[bag(i)],
+        weight_grads [n] = <bag_grads[bag(i)], row_i> or None).  The table step is then apply_*(keys, grads[, slots=located]) — for bags
+        that partition [0, n): positions no bag covers get no grads (nor handles from the forward).
+        located = the handles find_pooled(weights=..., located=...) of this step wrote (the rows are read through them)."""
+        k = self._keys(keys) if keys.numel() else keys
+        n_bags = self._bag_offsets(bag_offsets)
+        w = _check_weights(weights, "sum", k.numel(), self.device)
+        g = self._rows(bag_grads, n_bags)
+        loc = self._slots(located, k.numel()) if located is not None else None
+        if grads is None:
+            grads = torch.empty((k.numel(), self.dim), dtype=torch.float32, device=self.device)
+        if weight_grads is None and want_weight_grads:
+            weight_grads = torch.empty(k.numel(), dtype=torch.float32, device=self.device)
+        check(_lib.lib().mee_pooled_weighted_backward(self._h, k.data_ptr(), loc.data_ptr() if loc is not None else None, k.numel(),
+                                                      bag_offsets.data_ptr(), n_bags, w.data_ptr(), g.data_ptr(), grads.data_ptr(),
+                                                      weight_grads.data_ptr() if weight_grads is not None else None, self._s()))
+        return grads, weight_grads
 
     def find_missing(self, keys: torch.Tensor, out: torch.Tensor, found: torch.Tensor) -> None:
         """Second-tier pass: fill the positions an earlier find (on another table) left with found == 0."""
@@ -571,15 +617,22 @@ class TableGroup:
         return nb // len(self.tables)
 
     def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
-                    found: torch.Tensor | None = None, located: torch.Tensor | None = None):
+                    found: torch.Tensor | None = None, located: torch.Tensor | None = None, weights: torch.Tensor | None = None):
         """find_pooled of every member in one launch -> ([n_tables * bags_per_table, dim], per-key found mask).
-        located (optional int64[n] buffer) receives the located rows for apply_pooled(located=...) of the same step."""
+        located (optional int64[n] buffer) receives the located rows for apply_pooled(located=...) of the same step.
+        weights (fp32 [n], mode "sum" only): the weighted form, LookupTable.find_pooled(weights=...) per member."""
         bpt = self._check_bags(bag_offsets)
         k = self.tables[0]._keys(keys) if keys.numel() else keys
         if out is None:
             out = torch.empty((bpt * len(self.tables), self.dim), dtype=torch.float32, device=self.device)
         if found is None:
             found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
+        if weights is not None:
+            w = _check_weights(weights, mode, k.numel(), self.device)
+            check(_lib.lib().mee_group_find_pooled_weighted(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), bpt, w.data_ptr(), out.data_ptr(),
+                                                            found.data_ptr(), located.data_ptr() if located is not None else None,
+                                                            _stream_ptr(self.device)))
+            return out, found
         check(_lib.lib().mee_group_find_pooled(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), bpt, out.data_ptr(), found.data_ptr(),
                                                located.data_ptr() if located is not None else None,
                                                {"sum": 0, "mean": 1}[mode], _stream_ptr(self.device)))
@@ -602,6 +655,25 @@ class TableGroup:
         else:
             check(L.mee_group_apply_adam_pooled(self._h, k.data_ptr(), bag_offsets.data_ptr(), bpt, g.data_ptr(), gi.data_ptr(), loc, k.numel(),
                                                 lr, beta1, beta2, 1e-8 if eps is None else eps, step, s))
+
+    def pooled_weighted_backward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, weights: torch.Tensor, bag_grads: torch.Tensor,
+                                 located: torch.Tensor | None = None, want_weight_grads: bool = True, grads: torch.Tensor | None = None,
+                                 weight_grads: torch.Tensor | None = None):
+        """LookupTable.pooled_weighted_backward per member, in one launch -> (grads [n, dim], weight_grads [n] or None).  The step is
+        then apply_adagrad / apply_adam(keys, bag_offsets[::bags_per_table].contiguous(), grads): the grads are per position."""
+        bpt = self._check_bags(bag_offsets)
+        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        w = _check_weights(weights, "sum", k.numel(), self.device)
+        g = self.tables[0]._rows(bag_grads, bpt * len(self.tables))
+        loc = self.tables[0]._slots(located, k.numel()) if located is not None else None
+        if grads is None:
+            grads = torch.empty((k.numel(), self.dim), dtype=torch.float32, device=self.device)
+        if weight_grads is None and want_weight_grads:
+            weight_grads = torch.empty(k.numel(), dtype=torch.float32, device=self.device)
+        check(_lib.lib().mee_group_pooled_weighted_backward(self._h, k.data_ptr(), loc.data_ptr() if loc is not None else None, k.numel(),
+                                                            bag_offsets.data_ptr(), bpt, w.data_ptr(), g.data_ptr(), grads.data_ptr(),
+                                                            weight_grads.data_ptr() if weight_grads is not None else None, _stream_ptr(self.device)))
+        return grads, weight_grads
 
     def find_or_insert(self, keys: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None):
         """find that first creates absent keys in their member table (initial row / state); found = present before."""
