@@ -10,10 +10,13 @@
 
 A step = one pass of the hot path over one batch of synthetic keys already resident in HBM.  N=1: one mee_find
 launch, results rotating over 6 output buffers (384 MB: more than the Infinity Cache absorbs).  N>1: one sharded find
-(partition, keys to their owners, local find, rows back, un-permute).  Rank 0 prints ONE JSON line.  `roofline` is for the
-dominant kernel (find_kernel) from HIP events around back-to-back launches; N=1 also carries the SURVEY 8d stream table,
-the configs[2] (find + sparse Adagrad) rows and `cpu_baseline` (the in-repo CPU oracle, "port": the reference snapshot has
-no implementation) on the configuration the GPU number is quoted on; N>1 carries `xgmi` (bytes on the busiest link).
+(partition, keys to their owners, local find, rows back, un-permute).  Rank 0 prints ONE JSON line; N>1 carries `xgmi`
+(bytes on the busiest link).  A plain run does only what that line's headline needs: set up, warm up, time the steps, write
+--dump-outputs, print; its `roofline` prices the timed steps themselves.  --full adds everything else: `roofline` for the
+dominant kernel (find_kernel) from HIP events around back-to-back launches of its own, the eager-launch comparison, the
+key-stream table (N=1: SURVEY 8d; N>1: over every verified transport), the configs[2] (find + sparse Adagrad) rows and
+`cpu_baseline` (the in-repo CPU oracle, "port": the reference snapshot has no implementation) on the configuration the
+GPU number is quoted on.
 --dump-outputs DIR writes what the last timed step returned (see dump_outputs); the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
@@ -840,7 +843,7 @@ def main():
     ap.add_argument("--out-buffers", type=int, default=6,
                     help="N=1 find mode: the timed lookups rotate over this many dense output buffers (6 x 64 MB > the 256 MiB Infinity Cache: every "
                          "result has to reach HBM, as the results of independent requests do); 1 = every step overwrites one buffer")
-    ap.add_argument("--no-configs2", action="store_true", help="N=1 find mode: skip the configs[2] (find + sparse Adagrad) rows that the default line carries")
+    ap.add_argument("--no-configs2", action="store_true", help="N=1 find mode, --full: skip the configs[2] (find + sparse Adagrad) rows that its line carries")
     ap.add_argument("--tier-1b", action="store_true",
                     help="N=1 only: after the headline, also measure the LITERAL 1B-key dim-64 table on this one GPU through the hot/cold tier "
                          "(800M keys in HBM + 200M keys with rows in pinned host DRAM; needs ~270 GB of HBM and ~55 GB of pinned host memory); result under `also`")
@@ -848,6 +851,11 @@ def main():
                     help="N=1: also run configs[4]'s per-GPU share (1.25B keys: 800M in HBM + 450M rows in pinned host DRAM, Zipf, rebalance rounds; "
                          "needs ~260 GB of HBM and ~115 GB of host RAM — scaled to what the box has) -> also.tier_share_one_gpu")
     ap.add_argument("--tier-share-keys", type=str, default="1250000000,800000000", help="--tier-share: total keys, keys in HBM[, cap on the cold keys of the training pair] (smaller = a rehearsal)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the kernel's own roofline windows, the eager-launch comparison, the reused-buffer "
+                         "figure, the key-stream table (N>1: over every verified transport), the configs[2] rows and the CPU baseline (each of the last "
+                         "three can be left out again with its --no-* option); without it a run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the line, whose `roofline` then prices the timed steps themselves")
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them returned (rank 0's rows and found flags, float32; a fixed sample of the "
@@ -1214,7 +1222,7 @@ def main():
     # carrier that can run it (verified against the torch.distributed path in the probe), best one reported with its bytes on the busiest link.
     # Every rank takes part (collectives inside); short windows (3 + 6 steps per candidate): well under a second per row.
     dist_streams = None
-    if sharded and world > 1 and not train and not args.no_streams:
+    if sharded and world > 1 and not train and args.full and not args.no_streams:
         dist_streams = {}
         if verified_native and not args.dedup:
             # the exchange behind the C-ABI de-duplicates per CONTEXT (MEE_SHARDED_DEDUP): one more context for the dedup row, checked against the
@@ -1280,7 +1288,7 @@ def main():
         lk = batches[last % n_batches]
         assert bool(founds[last % n_out].all()) and torch.equal(outs[last % n_out][-4096:], synth.rows_t(lk[-4096:], dim, 2)), \
             "the timed steps did not leave the last batch's rows in its output buffer"
-        if graph is not None:   # the same K steps issued eagerly (one host launch call per step), HIP events: reported beside the graph number
+        if graph is not None and args.full:   # the same K steps issued eagerly (one host launch call per step), HIP events: reported beside the graph number
             torch.cuda.synchronize(dev)
             ev0.record()
             for i_ in range(args.steps):
@@ -1290,13 +1298,15 @@ def main():
             launch_cmp = {"graph_us_per_step": ev_ms * 1e3 / args.steps, "eager_us_per_step": ev0.elapsed_time(ev1) * 1e3 / args.steps,
                           "graph_wall_us_per_step": elapsed / args.steps * 1e6}
 
-    # dominant kernel (find_kernel) alone in its own fixed window (5 x 200 launches, HIP events on the launch stream): the
-    # roofline object does not depend on --steps
+    # --full: the dominant kernel (find_kernel) alone in its own fixed window (5 x 200 launches, HIP events on the launch stream): the
+    # roofline object does not depend on --steps.  A plain run launches nothing more and prices the timed steps themselves.
     roof_n = batch          # lookups per launch of the kernel the roofline object prices
     xgmi = None
     if train and not sharded:
         kern_s = ev_ms / 1e3 / args.steps
         kern_min_s = kern_s
+    elif not args.full:
+        kern_s = kern_min_s = (elapsed if sharded else ev_ms / 1e3) / args.steps
     elif sharded and world > 1:
         # the local find_kernel as the sharded step runs it: over keys THIS shard owns (what arrives from the G sources), about `batch` of them
         mine_ = torch.cat([b_[hash_batch(b_, 1, world)[2] == rank] for b_ in batches])
@@ -1304,6 +1314,10 @@ def main():
         roof_n = kb[0].numel()
         med_us, min_us = kernel_window(table, kb, out[:roof_n], found[:roof_n], dev, launches=50, regions=3, warm=5)
         kern_s, kern_min_s = med_us / 1e6, min_us / 1e6
+    else:
+        med_us, min_us = kernel_window(table, batches, outs, founds, dev, flags=find_flags)   # as the timed steps run: rotating output buffers, the caller's per-call hints
+        kern_s, kern_min_s = med_us / 1e6, min_us / 1e6
+    if sharded and world > 1:
         busiest, total_b = link_traffic(shs[0].router, batches, carrier, native.segment_capacity if (carrier == "native" and native is not None) else 0,
                                         dim, world, ctrl, payload_dim=dim if train else 0)
         t_step = elapsed / args.steps
@@ -1312,14 +1326,11 @@ def main():
                 "links_are_xgmi": args.backend == "nccl",
                 "note": "algorithmic bytes per step on the busiest ordered GPU pair (keys out + rows and found bytes back; padded segments at their "
                         "constant size), from the owner counts of a representative batch; fraction of the nominal 76.8 GB/s per link direction (SURVEY 8e)"}
-    else:
-        med_us, min_us = kernel_window(table, batches, outs, founds, dev, flags=find_flags)   # as the timed steps run: rotating output buffers, the caller's per-call hints
-        kern_s, kern_min_s = med_us / 1e6, min_us / 1e6
     bpl = algorithmic_bytes_per_lookup(dim)
     reused_us = None
-    if not sharded and not train and n_out > 1:   # the same launches into ONE reused 64 MB buffer under the library's default policy (what round 2 reported)
+    if args.full and not sharded and not train and n_out > 1:   # the same launches into ONE reused 64 MB buffer under the library's default policy (what round 2 reported)
         reused_us = kernel_window(table, batches, out, found, dev)
-    whole = train and not sharded   # sharded runs always price the local find_kernel alone
+    whole = train and not sharded   # sharded runs price the find's 528 B per lookup: the local find_kernel alone (--full) or the whole sharded step
     if whole:
         # fwd 528 B/lookup + bwd 264 B/lookup + 1032 B per unique key (Adagrad); here the whole step is priced
         uniq = sum(int(torch.unique(b_).numel()) for b_ in batches[:8]) / 8
@@ -1350,6 +1361,18 @@ def main():
                                         "the step's kernels summed: " + ", ".join(aj["kernels"]) + ")")
             except Exception:
                 step_traffic = None
+        if whole:
+            roof_kernel, roof_window = "whole step (find_prepare_kernel: the located find + the apply's partition; bkt_apply_kernel: dedup + update)", "the timed steps"
+        elif not args.full:
+            roof_kernel = (f"whole sharded step ({'lookup, gradient exchange, sparse-Adagrad apply' if train else 'partition, exchange, local find_kernel, un-permute'})"
+                           if sharded else "find_kernel")
+            roof_window = ("the timed steps: wall clock of the region, the slowest rank" if sharded else
+                           "the timed steps: HIP events around the region, one find_kernel launch per step")
+        elif sharded and world > 1:
+            roof_kernel, roof_window = "find_kernel", ("median of 3 HIP-event windows of 50 back-to-back launches of the LOCAL find_kernel over keys this shard owns "
+                                                       "(what arrives from the G sources per step), on rank 0")
+        else:
+            roof_kernel, roof_window = "find_kernel", "median of 5 HIP-event windows of 200 back-to-back launches on the launch stream (independent of --steps)"
         res = {
             "metric": "key-lookups/sec" if not train else "train-step keys/sec (find + sparse Adagrad apply)", "value": value, "unit": "key-lookups/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -1364,7 +1387,7 @@ def main():
                        "launch_comparison": launch_cmp, "output_buffers": (f"{n_out} x {batch * dim * 4 >> 20} MB dense result buffers in rotation" if n_out > 1 else "one reused result buffer"),
                        "parallelism": (f"row-shard x{world}" + (f", {args.pipeline} steps in flight" if args.pipeline > 1 else "") + (", pre-exchange dedup" + (" (lookup keys and summed gradient rows)" if train else "") if args.dedup else "")) if sharded else "single GPU"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic if not whole else step_traffic, "kernel": "find_kernel" if not whole else "whole step (find_prepare_kernel: the located find + the apply's partition; bkt_apply_kernel: dedup + update)",
+                         "traffic": traffic if not whole else step_traffic, "kernel": roof_kernel,
                          "traffic_source": (("profiles/find_traffic.json (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, FETCH_SIZE x2 per the gfx950 correction)"
                                              if traffic is not None else None) if not whole else step_traffic_src),
                          "avg_launch_us": kern_s * 1e6, "min_launch_us": kern_min_s * 1e6,
@@ -1376,7 +1399,7 @@ def main():
                          "frac_out_reused": (batch * bpl / reused_us[0] / 1e3 / HBM_PEAK_GBS) if reused_us is not None else None,
                          "out_reused_avg_launch_us": reused_us[0] if reused_us is not None else None,
                          "out_buffers": n_out, "out_store_policy": store_hint,
-                         "window": "median of 5 HIP-event windows of 200 back-to-back launches on the launch stream (independent of --steps)" if not whole else "the timed steps",
+                         "window": roof_window,
                          "algorithmic_bytes_per_lookup": bpl if not whole else step_bytes / batch,
                          "read_only_GBps": roof_n * (16 + 4 * dim) / kern_s / 1e9 if not whole else None,
                          "lookups_per_launch": roof_n},
@@ -1385,28 +1408,26 @@ def main():
             res["streams"] = dist_streams
         if xgmi is not None:
             res["xgmi"] = xgmi
-            res["roofline"]["window"] = ("median of 3 HIP-event windows of 50 back-to-back launches of the LOCAL find_kernel over keys this shard owns "
-                                         "(what arrives from the G sources per step), on rank 0")
-        if not sharded and not train and not args.no_streams:
+        if args.full and not sharded and not train and not args.no_streams:
             try:
                 res["streams"] = stream_table(table, synth, n_keys, batch, dim, dev, out, found, bpl, batches, reused_us if reused_us is not None else (kern_s * 1e6, kern_min_s * 1e6))
                 res["streams"]["note"] = "every row but north_star_batch_1M and the two_output_buffers rows: launches into ONE reused result buffer, default cache policy"
             except Exception as e:  # noqa: BLE001
                 res["streams"] = {"error": repr(e)}
-        if whole and not args.no_streams:
+        if args.full and whole and not args.no_streams:
             try:
                 res["streams"] = train_streams(table, synth, n_keys, batch, dim, dev, out, found, bpl)
             except Exception as e:  # noqa: BLE001
                 res["streams"] = {"error": repr(e)}
-        if not sharded and not args.no_cpu_baseline:
+        if args.full and not sharded and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(synth, dim, batch, keys_per_gpu, args.load)
         if not sharded and not train and args.extras:
             try:  # never allowed to break the headline line
                 res["also"] = {"two_caller_streams": two_stream_extra(table, batches, dim, dev, bpl)}
             except Exception as e:  # noqa: BLE001
                 res.setdefault("also", {})["error"] = repr(e)
-        if not sharded and not train and not args.no_streams and not args.no_configs2:
-            try:  # configs[2] beside the headline, in the line the driver records (never allowed to break it)
+        if args.full and not sharded and not train and not args.no_streams and not args.no_configs2:
+            try:  # configs[2] beside the headline, in the --full line (never allowed to break it)
                 del outs, founds
                 res["configs2"] = configs2_rows(table, synth, n_keys, dim, dev, chunk, batch, bpl)
             except Exception as e:  # noqa: BLE001

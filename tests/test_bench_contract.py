@@ -29,7 +29,7 @@ def _one_json_line(cmd):
 
 @pytest.mark.gpu
 def test_bench_single_gpu_contract(dev):
-    res = _one_json_line([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--keys", "2000000", "--no-extras"])
+    res = _one_json_line([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--keys", "2000000", "--no-extras", "--full"])
     assert REQUIRED <= set(res) and "cpu_baseline" in res
     assert res["n_gpus"] == 1 and res["steps"] == 20 and res["warmup"] == 5 and res["vs_baseline"] is None and res["value"] > 1e8
     rf = res["roofline"]
@@ -59,6 +59,21 @@ def test_bench_single_gpu_contract(dev):
         assert c2[name]["step_adam"]["us"] > c2[name]["apply_alone_adam"]["us"] > 0 and 0 < c2[name]["step_adam"]["frac_of_hbm_roofline"] < 1
     assert c2["zipf_1.05"]["unique_keys_per_batch"] < c2["uniform"]["unique_keys_per_batch"]
     assert cb["table_keys"] == 2_000_000 and str(cb["cores"]) in cb["by_threads"] and cb["value"] == max(cb["by_threads"].values())
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean(dev):
+    """Without --full the line carries the headline and nothing that needs launches of its own: `roofline` prices the timed steps,
+    and the key-stream table, configs[2] rows, CPU baseline and eager-launch comparison are left to --full."""
+    res = _one_json_line([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--keys", "2000000"])
+    assert REQUIRED <= set(res) and res["steps"] == 20 and res["warmup"] == 5 and res["value"] > 1e8 and res["higher_is_better"] is True
+    assert abs(res["value"] * res["ms_per_step"] / 1e3 - res["config"]["batch_per_rank"]) < 1e-6 * res["value"]
+    assert not {"streams", "configs2", "cpu_baseline", "also"} & set(res) and res["config"]["launch_comparison"] is None
+    rf = res["roofline"]
+    assert rf["kernel"] == "find_kernel" and rf["window"].startswith("the timed steps") and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-9
+    # HIP events inside the region's host clock: a step priced by the events cannot take longer than the wall-clock step
+    assert 0 < rf["avg_launch_us"] <= res["ms_per_step"] * 1e3 * 1.001 and rf["frac_out_reused"] is None
+    assert "mee_find_ex_flags" in rf["out_store_policy"]   # the probe that picks the timed steps' cache hints still runs
 
 
 @pytest.mark.gpu
@@ -105,7 +120,7 @@ def test_bench_dump_outputs(dev, tmp_path):
 def test_bench_two_rank_rehearsal(dev):
     res = _one_json_line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--backend", "gloo", "--keys", "2000000", "--batch", "65536",
-                          "--steps", "5", "--warmup", "2"])
+                          "--steps", "5", "--warmup", "2", "--full"])
     assert REQUIRED <= set(res) and res["n_gpus"] == 2 and res["scaling"] == "weak" and res["value"] > 0
     assert "transport" in res["config"]["workload"]
     # SURVEY 8d config 4 (iii) in the one line: the uniform stream and Zipf(1.05) without and with pre-exchange dedup, each with its value, the
@@ -124,7 +139,7 @@ def test_bench_self_launches_its_ranks(dev):
     """`python bench.py --gpus 2` with NO launcher around it: the command starts its own two ranks (before it touches the GPU), relays rank 0's
     line and exits with the ranks' code — the form a driver uses for every N.  gloo backend: both ranks share this box's one GPU."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--keys", "2000000", "--batch", "65536", "--steps", "5", "--warmup", "2"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--keys", "2000000", "--batch", "65536", "--steps", "5", "--warmup", "2", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -9,15 +9,15 @@ mkdir -p $R
 part=${1:-all}
 python3 -c "from meepoembedding_amd import _lib; import json; print(json.dumps(_lib.device_calibration(0)))" 2>/dev/null | tail -1 > $O/calibration_part$part.json
 if [ "$part" = 1 ] || [ "$part" = all ]; then
-timeout -k 10 500 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 500 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "bench default done"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/prof_find -o run -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-streams > $O/bench_profiled.json 2> $O/bench_profiled.err
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/pmc_fetch -o run -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-streams > /dev/null 2> $O/pmc_fetch.err
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $R/pmc_write -o run -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-streams > /dev/null 2> $O/pmc_write.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/prof_find -o run -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-streams > $O/bench_profiled.json 2> $O/bench_profiled.err
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/pmc_fetch -o run -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-streams > /dev/null 2> $O/pmc_fetch.err
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $R/pmc_write -o run -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-streams > /dev/null 2> $O/pmc_write.err
 python3 tools/pmc_traffic.py "find_kernel<16, 2" $R/pmc_fetch $R/pmc_write --out $O/find_traffic.json --meta batch=262144 dim=64 keys=100000000 > /dev/null
 echo "find traffic done"
-timeout -k 10 300 python3 bench.py --mode train --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_train.json 2> $O/bench_train.err
-timeout -k 10 300 python3 bench.py --mode train --dist zipf --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_train_zipf.json 2> $O/bench_train_zipf.err
+timeout -k 10 300 python3 bench.py --full --mode train --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_train.json 2> $O/bench_train.err
+timeout -k 10 300 python3 bench.py --full --mode train --dist zipf --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_train_zipf.json 2> $O/bench_train_zipf.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/prof_train -o run -- python3 bench.py --mode train --steps 100 --warmup 10 --no-cpu-baseline --no-streams > $O/bench_train_profiled.json 2> $O/bench_train_profiled.err
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/pmc_train_fetch -o run -- python3 bench.py --mode train --steps 100 --warmup 10 --no-cpu-baseline --no-streams > /dev/null 2> $O/pmc_train_fetch.err
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $R/pmc_train_write -o run -- python3 bench.py --mode train --steps 100 --warmup 10 --no-cpu-baseline --no-streams > /dev/null 2> $O/pmc_train_write.err
