@@ -56,7 +56,8 @@ def _stream(kind, step, n, rng, pool):
 
 
 @pytest.mark.parametrize("kind,n,dim", [("uniform", 5000, 64), ("uniform", 300_000, 64), ("zipf", 300_000, 64), ("zipf", 120_000, 128),
-                                         ("hot_mix", 300_000, 16), ("hot_mix", 200_000, 40), ("one_key", 70_000, 64), ("zipf", 1_000_000, 16)])
+                                         ("hot_mix", 300_000, 16), ("hot_mix", 200_000, 40), ("one_key", 70_000, 64), ("zipf", 1_000_000, 16),
+                                         ("hot_mix", 200_000, 100), ("one_key", 70_000, 260), ("zipf", 300_000, 32)])
 def test_dedup_sum_padded_over_a_stream(dev, kind, n, dim):
     rng = np.random.default_rng(zlib.crc32(f"{kind}/{n}/{dim}".encode()))
     pool = synth.keys_np(811, 0, max(2000, n // 2))

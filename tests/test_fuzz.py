@@ -24,3 +24,9 @@ def test_fuzz_dedup_sum(dev, seed):
 @pytest.mark.parametrize("seed", [201, 202])
 def test_fuzz_apply(dev, seed):
     assert _tool("fuzz_apply").run(3, seed, quiet=True) >= 3
+
+
+@pytest.mark.parametrize("opt,seed", [("adagrad", 203), ("adam", 204)])
+def test_fuzz_apply_wide_dims(dev, opt, seed):
+    """The same streams at row widths beyond one 16-lane column chunk of the run-time instance (100, 260) and at DIM4 = 32 (128), both optimizers."""
+    assert _tool("fuzz_apply").run(3, seed, quiet=True, dims=[100, 128, 260], opt=opt) >= 3

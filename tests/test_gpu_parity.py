@@ -1,6 +1,7 @@
 """GPU parity: every operator of the HIP backend through the C-ABI vs the CPU oracle on the same seeded inputs.
 Bar: bit-exact for hashing / found-masks / copied rows / size / key-sorted export; ≤1e-6 relative (atol 1e-9) for
 fp32 optimizer state (SPEC.md §4)."""
+import functools
 import json
 import os
 
@@ -58,7 +59,7 @@ def test_published_known_answers_on_device(dev):
 
 
 @pytest.mark.parametrize("dim,n,load", [(16, 20000, 0.75), (64, 50000, 0.75), (128, 8192, 0.9), (4, 1000, 0.5), (40, 3000, 0.75),
-                                        (256, 2000, 0.75)])
+                                        (256, 2000, 0.75), (100, 5000, 0.75)])
 def test_insert_find_assign_export(dev, dim, n, load):
     keys = synth.keys_np(1, 0, 2 * n)
     present, absent = keys[:n], keys[n:]
@@ -464,22 +465,25 @@ def test_optimizer_every_group_size(dev, opt, dim, layout):
     np.testing.assert_allclose(got.cpu().numpy(), exp, rtol=RTOL, atol=ATOL)
 
 
+@functools.lru_cache(maxsize=None)
 def _keys_of_apply_bucket_zero(count, seed):
     """Distinct keys whose mix64 has 13 leading zero bits: for ANY bucket count up to 8192 the bucketed apply puts them all into bucket 0
-    (and the table into the first 1/8192 of its buckets)."""
+    (and the table into the first 1/8192 of its buckets).  Cached per (count, seed), read-only: the search hashes millions of candidates."""
     rng = np.random.default_rng(seed)
     got = []
     while sum(len(g) for g in got) < count:
         cand = rng.integers(-(1 << 62), 1 << 62, size=1 << 22, dtype=np.int64)
         mix, _, _ = oracle.hash_batch(cand, 1, 1)
         got.append(cand[mix < (np.uint64(1) << np.uint64(51))])
-    return np.unique(np.concatenate(got))[:count]
+    keys = np.unique(np.concatenate(got))[:count]
+    keys.flags.writeable = False
+    return keys
 
 
-@pytest.mark.parametrize("opt", ["adagrad", "adam"])
-@pytest.mark.parametrize("kernel", ["auto", "lean", "full"])
-@pytest.mark.parametrize("case", ["one_key", "one_bucket_many_keys", "forty_hot_keys", "one_bucket_two_keys", "bucket_of_900_distinct", "bucket_of_300_warm"])
-def test_bucketed_apply_extremes(dev, case, opt, kernel):
+EXTREME_CASES = ["one_key", "one_bucket_many_keys", "forty_hot_keys", "one_bucket_two_keys", "bucket_of_900_distinct", "bucket_of_300_warm"]
+
+
+def _bucketed_apply_extremes(dev, case, opt, kernel, dim):
     """The rare ways through the bucketed apply (meepo_apply.hip), each forced by construction, plain and located, against the oracle:
     one_key — a single key fills 400K of a 410K-position batch: ~780 slabs of one bucket each emit a record of that key, more records of ONE key
     than a merge pass holds (mono_pass);  one_bucket_many_keys — 3000 keys that all fall into apply bucket 0, 100+ occurrences each: every slab
@@ -491,8 +495,10 @@ def test_bucketed_apply_extremes(dev, case, opt, kernel):
     same path with runs.
     kernel: which apply kernel takes the batches — "lean" (block = bucket; a split bucket is taken by its own block one key at a time: what the
     FIRST skewed batch of a stream gets), "full" (slabs, pending records, merges; from the second step on also the hot keys' own buckets, which the
-    first step's kernel reported), "auto" (the library's choice: lean for step 0, full for step 1)."""
-    dim, n_bg = 64, 20000
+    first step's kernel reported), "auto" (the library's choice: lean for step 0, full for step 1).
+    Rows wider than 64 draw their gradients on the device (host normals of 100M values cost seconds per step) and forty_hot_keys gets a smaller
+    uniform part; the hot keys' counts, which make each case what it is, are the same at every dim."""
+    n_bg = 20000
     rng = np.random.default_rng(5)
     bg = synth.keys_np(321, 0, n_bg)
     if case == "one_key":
@@ -500,7 +506,7 @@ def test_bucketed_apply_extremes(dev, case, opt, kernel):
     elif case == "one_bucket_many_keys":
         hot = _keys_of_apply_bucket_zero(3000, 7); reps = rng.integers(100, 140, size=3000); n_fill = 20_000
     elif case == "forty_hot_keys":
-        hot = synth.keys_np(323, 0, 40); reps = rng.integers(5000, 7000, size=40); n_fill = 150_000
+        hot = synth.keys_np(323, 0, 40); reps = rng.integers(5000, 7000, size=40); n_fill = 150_000 if dim <= 64 else 30_000
     elif case == "one_bucket_two_keys":
         hot = _keys_of_apply_bucket_zero(2, 9); reps = np.array([150_000, 150_001]); n_fill = 5_000
     elif case == "bucket_of_900_distinct":
@@ -521,10 +527,15 @@ def test_bucketed_apply_extremes(dev, case, opt, kernel):
         t.set_tuning("apply_kernel", {"auto": -1, "lean": 0, "full": 1}[kernel])
     o.insert(keys, rows)
     bkt = T(bk, dev)
+    gen = torch.Generator(device=dev); gen.manual_seed(dim)
     for s in range(3 if kernel == "full" else 2):
         torch.cuda.synchronize()   # (the host sizes step s + 1 by what step s reported: hot keys' buckets exist from the second full step on)
-        g = (rng.standard_normal((n, dim)) * 0.01).astype(np.float32)
-        gt = T(g, dev)
+        if dim <= 64:
+            g = (rng.standard_normal((n, dim)) * 0.01).astype(np.float32)
+            gt = T(g, dev)
+        else:
+            gt = torch.randn(n, dim, device=dev, generator=gen) * 0.01
+            g = gt.cpu().numpy()
         _, _, slots = tb.find_located(bkt, prepare_apply=(s == 1))
         if opt == "adagrad":
             ta.apply_adagrad(bkt, gt, lr=0.05); tb.apply_adagrad(bkt, gt, lr=0.05, slots=slots); o.apply_adagrad(bk, g, 0.05, 1e-10)
@@ -551,6 +562,24 @@ def test_bucketed_apply_extremes(dev, case, opt, kernel):
     exp, _ = o.find(bg)
     assert bool(found.all()) and ta.status() == 0
     np.testing.assert_allclose(got.cpu().numpy(), exp, rtol=RTOL, atol=ATOL)
+
+
+@pytest.mark.parametrize("opt", ["adagrad", "adam"])
+@pytest.mark.parametrize("kernel", ["auto", "lean", "full"])
+@pytest.mark.parametrize("case", EXTREME_CASES)
+def test_bucketed_apply_extremes(dev, case, opt, kernel):
+    """The rare ways through the bucketed apply at dim 64, the compile-time instance DIM4 = 16 (_bucketed_apply_extremes)."""
+    _bucketed_apply_extremes(dev, case, opt, kernel, 64)
+
+
+@pytest.mark.parametrize("opt,dim", [("adagrad", 128), ("adam", 128), ("adam", 100), ("adagrad", 260), ("adam", 32)])
+@pytest.mark.parametrize("kernel", ["lean", "full"])
+@pytest.mark.parametrize("case", EXTREME_CASES)
+def test_bucketed_apply_extremes_wide(dev, case, kernel, opt, dim):
+    """The same rare ways through the other instances of the row shape, LEAN and FULL forced: dim 128 = DIM4 32, both optimizers (two full 16-lane
+    column chunks, fp64 partial rows in memory); the run-time instance DIM4 = 0 at dim 100 (a second chunk with 9 of 16 lanes live, partial rows in
+    memory), 260 (five chunks, the last with one live lane) and 32 (one chunk with 8 idle lanes, partial rows in LDS)."""
+    _bucketed_apply_extremes(dev, case, opt, kernel, dim)
 
 
 @pytest.mark.parametrize("sync_every_step", [True, False], ids=["host_in_step", "host_runs_ahead"])
@@ -700,7 +729,7 @@ def test_find_or_insert_located(dev, dim):
     assert small.status() & STATUS_TABLE_FULL and int((s_ >= 0).sum()) == small.size() and int((s_ < 0).sum()) == 1000 - small.size()
 
 
-@pytest.mark.parametrize("opt,dim", [("adagrad", 64), ("adam", 128), ("adagrad", 24)])
+@pytest.mark.parametrize("opt,dim", [("adagrad", 64), ("adam", 128), ("adagrad", 24), ("adam", 100)])
 def test_located_apply_equals_plain_apply(dev, opt, dim):
     """find_located + apply_*(slots=…) — the forward's slot handles instead of a probe — must give the table the plain apply
     gives (and the oracle's), with duplicates, absent keys (handle -1), reserved keys and both settings of the side-stream knob."""
@@ -776,7 +805,7 @@ def test_located_apply_equals_plain_apply(dev, opt, dim):
 
 
 @pytest.mark.parametrize("opt", ["adagrad", "adam"])
-@pytest.mark.parametrize("dim,n_keys,batch", [(64, 200000, 131072), (128, 3000, 2000), (24, 50000, 40000)])
+@pytest.mark.parametrize("dim,n_keys,batch", [(64, 200000, 131072), (128, 3000, 2000), (24, 50000, 40000), (100, 50000, 40000)])
 def test_training_forward_prepares_the_apply(dev, opt, dim, n_keys, batch):
     """find_located(prepare_apply=True) — ONE launch: the located find + the partition of the step's apply, run by the launch's first blocks —
     followed by apply_*(slots=…) must leave the table exactly as find_located + apply_* does, and return the same rows; uniform and skewed
@@ -902,6 +931,37 @@ def test_concurrent_insert_stress(dev):
     assert len(np.unique(gk)) == n and np.array_equal(np.sort(gk), np.sort(keys))
     out, found = t.find(T(keys, dev))
     assert found.all() and np.array_equal(out.cpu().numpy(), rows)
+
+
+def test_config0_roundtrip_gpu(dev):
+    """BASELINE configs[0] (1M int64 keys, dim 16) through the HIP backend: the steps of test_oracle_kat.py::test_config0_roundtrip_cpu — insert,
+    find of every key and of 1M absent ones, assign of every second key and of absent ones, export — bit-exact against the oracle."""
+    n, dim = 1_000_000, 16
+    keys = synth.keys_np(1, 0, n)
+    rows = synth.rows_np(keys, dim, 2)
+    t = LookupTable(int(n / 0.75), dim, device=dev, max_batch=n)
+    o = oracle.OracleTable(int(n / 0.75), dim)
+    assert t.capacity == o.capacity
+    t.insert(T(keys, dev), T(rows, dev)); o.insert(keys, rows)
+    assert t.size() == o.size() == n and t.status() == 0
+    out, found = t.find(T(keys, dev))
+    assert bool(found.all()) and np.array_equal(out.cpu().numpy(), rows)
+    absent = synth.keys_np(99, 0, n)
+    out, found = t.find(T(absent, dev))
+    assert not bool(found.any()) and not bool(out.any())
+    sub = keys[::2]
+    new = synth.rows_np(sub, dim, 5)
+    fa = t.assign(T(sub, dev), T(new, dev)); fo = o.assign(sub, new)
+    assert bool(fa.all()) and np.array_equal(fa.cpu().numpy(), fo)
+    fa = t.assign(T(absent[:1000], dev), T(new[:1000], dev)); fo = o.assign(absent[:1000], new[:1000])
+    assert not bool(fa.any()) and np.array_equal(fa.cpu().numpy(), fo)
+    out, found = t.find(T(keys, dev)); eo, ef = o.find(keys)
+    assert np.array_equal(found.cpu().numpy(), ef) and np.array_equal(out.cpu().numpy(), eo)
+    assert np.array_equal(eo[::2], new) and np.array_equal(eo[1::2], rows[1::2])
+    gk, gv = t.export(); ok, ov = o.export()
+    gk, gv = sorted_export(gk.cpu().numpy(), gv.cpu().numpy()); ok, ov = sorted_export(ok, ov)
+    assert np.array_equal(gk, ok) and np.array_equal(gv, ov) and np.array_equal(gk, np.sort(keys))
+    assert t.size() == n and t.status() == 0
 
 
 def test_large_round_trip_properties(dev):
@@ -1356,6 +1416,74 @@ def test_grouped_apply_equals_per_table_apply(dev, opt, dim):
     grp.close()
 
 
+@pytest.mark.parametrize("opt,dim", [("adam", 100), ("adagrad", 128)])
+def test_grouped_apply_forced_kernels(dev, opt, dim):
+    """The grouped apply with its kernel forced (TableGroup.set_tuning("apply_kernel", 0) = LEAN for two steps, then 1 = FULL for two more: the
+    instances bkt_apply_kernel<K, D4, true, true, LEAN / FULL>) at the run-time instance (dim 100) and at DIM4 = 32 (dim 128).  Member 0 gets a key
+    of ~150 000 occurrences (split buckets) and 300 keys of apply bucket 0 with runs; the other members uniform traffic, absent keys, padding and
+    an empty segment every other step.  Per member == apply_* on a table of its own == the oracle."""
+    from meepoembedding_amd import TableGroup
+    rng = np.random.default_rng(17 + dim)
+    kind, okind = (OPT_ADAGRAD, oracle.OPT_ADAGRAD) if opt == "adagrad" else (OPT_ADAM, oracle.OPT_ADAM)
+    n_tables, cap, max_apply = 3, 1 << 15, 1 << 18
+    hot, warm = synth.keys_np(561, 0, 1), _keys_of_apply_bucket_zero(300, 12)
+    grouped, solo, oracles, universes = [], [], [], []
+    for j in range(n_tables):
+        u = synth.keys_np(570 + j, 0, 12_000)
+        if j == 0:
+            u = np.concatenate([u, hot, warm])
+        rows = rng.standard_normal((u.size, dim)).astype(np.float32)
+        a = LookupTable(cap, dim, device=dev, optimizer=kind, max_batch=max_apply, initial_accumulator=0.1)
+        b = LookupTable(cap, dim, device=dev, optimizer=kind, max_batch=max_apply, initial_accumulator=0.1)
+        o = oracle.OracleTable(cap, dim, optimizer=okind, initial_accumulator=0.1)
+        a.insert(T(u, dev), T(rows, dev)); b.insert(T(u, dev), T(rows, dev)); o.insert(u, rows)
+        grouped.append(a); solo.append(b); oracles.append(o); universes.append(u)
+    grp = TableGroup(grouped, max_apply_batch=max_apply)
+    for step in range(1, 5):
+        if step in (1, 3):
+            grp.set_tuning("apply_kernel", 0 if step == 1 else 1)
+        u0 = universes[0][:12_000]
+        k0 = np.concatenate([np.repeat(hot, 150_000 + step), np.repeat(warm, rng.integers(1, 7, size=300)), u0[rng.integers(0, u0.size, 5000)]])
+        rng.shuffle(k0)
+        segs = [k0]
+        for j in range(1, n_tables):
+            if j == 2 and step % 2 == 0:
+                segs.append(np.zeros(0, np.int64))
+                continue
+            k = universes[j][rng.integers(0, universes[j].size, 20_000)]
+            k[rng.integers(0, k.size, 40)] = synth.keys_np(580 + j, 40 * step, 40)      # absent
+            k[7] = oracle.EMPTY_KEY                                                     # padding
+            segs.append(k)
+        keys = np.concatenate(segs)
+        assert keys.size <= max_apply
+        grads = (rng.standard_normal((keys.size, dim)) * 0.01).astype(np.float32)
+        offs = torch.tensor(np.concatenate([[0], np.cumsum([x.size for x in segs])]), dtype=torch.int64, device=dev)
+        if opt == "adagrad":
+            grp.apply_adagrad(T(keys, dev), offs, T(grads, dev), lr=0.05, eps=1e-10)
+        else:
+            grp.apply_adam(T(keys, dev), offs, T(grads, dev), lr=0.01, step=step)
+        p = 0
+        for j, k in enumerate(segs):
+            gseg = grads[p:p + k.size]; p += k.size
+            if not k.size:
+                continue
+            if opt == "adagrad":
+                solo[j].apply_adagrad(T(k, dev), T(gseg, dev), lr=0.05, eps=1e-10); oracles[j].apply_adagrad(k, gseg, 0.05, 1e-10)
+            else:
+                solo[j].apply_adam(T(k, dev), T(gseg, dev), lr=0.01, step=step); oracles[j].apply_adam(k, gseg, 0.01, 0.9, 0.999, 1e-8, step)
+    for j in range(n_tables):
+        ga = [x.cpu().numpy() for x in grouped[j].export(with_state=True) if x is not None]
+        sa = [x.cpu().numpy() for x in solo[j].export(with_state=True) if x is not None]
+        oa = [x for x in oracles[j].export(with_state=True) if x is not None]
+        ia, ib, ic = np.argsort(ga[0]), np.argsort(sa[0]), np.argsort(oa[0])
+        assert np.array_equal(ga[0][ia], sa[0][ib]) and np.array_equal(ga[0][ia], oa[0][ic])
+        for x, y, z in zip(ga[1:], sa[1:], oa[1:]):
+            np.testing.assert_allclose(x[ia], y[ib], rtol=RTOL, atol=ATOL)
+            np.testing.assert_allclose(x[ia], z[ic], rtol=RTOL, atol=ATOL)
+        assert grouped[j].status() == solo[j].status() == oracles[j].status() == 0
+    grp.close()
+
+
 @pytest.mark.parametrize("opt,dim", [("adagrad", 64), ("adam", 24), ("none", 128)])
 def test_grouped_find_or_insert_equals_per_table(dev, opt, dim):
     """mee_group_find_or_insert == find_or_insert per table == the oracle: rows, present-before masks, the created keys'
@@ -1413,7 +1541,8 @@ def test_grouped_find_or_insert_equals_per_table(dev, opt, dim):
     grp.close()
 
 
-@pytest.mark.parametrize("dim,mode", [(64, "sum"), (128, "mean"), (24, "sum"), (1024, "mean")])
+@pytest.mark.parametrize("dim,mode", [(64, "sum"), (128, "mean"), (24, "sum"), (1024, "mean"), (100, "sum"), (100, "mean"), (1020, "sum"),
+                                      (1020, "mean")])
 def test_find_pooled_bit_exact(dev, dim, mode):
     """mee_find_pooled == segment-sum (position order, fp32) of find's rows: bit-exact, with empty bags, bags of one, long
     bags, absent and reserved keys, odd bag lengths (the kernel keeps two keys in flight)."""
@@ -1483,7 +1612,7 @@ def test_indexed_apply_is_apply_of_gathered_grads(dev, opt):
             np.testing.assert_allclose(x.cpu()[ia].numpy(), z[io], rtol=RTOL, atol=ATOL)
 
 
-@pytest.mark.parametrize("dim,mode,opt", [(64, "sum", "adagrad"), (128, "mean", "adam"), (24, "sum", "adagrad")])
+@pytest.mark.parametrize("dim,mode,opt", [(64, "sum", "adagrad"), (128, "mean", "adam"), (24, "sum", "adagrad"), (100, "sum", "adam")])
 def test_group_pooled_equals_per_table_pooled(dev, dim, mode, opt):
     """The embedding-bag collection: mee_group_find_pooled == find_pooled per member (bit-exact), and its backward
     (mee_group_apply_*_pooled) == apply_*_indexed per member == the oracle."""

@@ -202,7 +202,7 @@ assert [wave_per_bag(x) for x in SHAPES] == [False, True, True] and max(SHAPES[0
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim", [4, 24, 64, 128, 1024])
+@pytest.mark.parametrize("dim", [4, 24, 64, 128, 1024, 100, 1020])
 def test_weighted_forward_bit_exact(dev, dim):
     t, u, rng = _filled_table(dev, dim, 3000, 60 + dim)
     for lens in SHAPES:
@@ -226,7 +226,7 @@ def test_weighted_forward_bit_exact(dev, dim):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim", [64, 128, 24])
+@pytest.mark.parametrize("dim", [64, 128, 24, 100])
 def test_group_weighted_ops_equal_per_member(dev, dim):
     """mee_group_find_pooled_weighted / mee_group_pooled_weighted_backward == the single-table operators per member, bit-exact, in
     both launch shapes; the group backward gives the same results through the forward's handles and by probe."""
@@ -269,7 +269,7 @@ def test_group_weighted_ops_equal_per_member(dev, dim):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim", [64, 128, 24, 1024])
+@pytest.mark.parametrize("dim", [64, 128, 24, 1024, 100, 1020])
 def test_weighted_backward(dev, dim):
     """grads bit-exact, weight_grads within the SPEC bound of fp64, identical with and without handles, none without weight_grads."""
     t, u, rng = _filled_table(dev, dim, 3000, 90 + dim)
