@@ -478,9 +478,11 @@ int mee_sharded_create(mee_table* local, void* nccl_comm, uint64_t max_batch /* 
  *          else in the cold one.  Which keys are hot is the caller's policy (mee_find_plane / mee_assign_plane move a key with its state).
  *   MEE_SHARDED_DEDUP   lookups (find, find_or_insert) exchange only the batch's DISTINCT keys: mee_dedup_keys on a scratch table of the
  *          context's own -> the padded unique list is partitioned (padding belongs to no shard) -> keys out, rows back -> every occurrence
- *          takes its key's row.  Optimizer applies (apply_adagrad, apply_adam) send ONE (key, summed gradient row) pair per distinct key of the
+ *          takes its key's row.  mee_sharded_apply_adagrad sends ONE (key, summed gradient row) pair per distinct key of the
  *          rank's batch: mee_dedup_sum adds the rank's rows of a key up in fp64 and rounds once, the owner's apply adds the ranks' partial sums
  *          up in fp64 again — within 1e-6 (relative) of the un-aggregated update, not bit-identical to it (one extra rounding per rank and key).
+ *          mee_sharded_apply_adam sends its pairs un-aggregated under this flag too: Adam's step hardly depends on the size of the gradient, so
+ *          where the ranks' partial sums cancel, one rounding of a partial sum would reach the row as a large relative error (SPEC.md §5).
  *          On skewed key streams the bytes on xGMI then scale with the distinct keys, in both directions of a training step, while the result
  *          counts lookups.  Costs ~0.1-0.2 ms of local work per 1M keys: it pays where the saved link time exceeds that. */
 enum { MEE_SHARDED_DEDUP = 1u };

@@ -820,11 +820,13 @@ static int sharded_apply(mee_sharded* c, const int64_t* d_keys, const float* d_g
     hipStream_t st = (hipStream_t)stream;
     uint64_t rt = 0;
     if (int rc = ensure_send_rows(c)) return rc;
-    if (c->dedup) {
+    if (c->dedup && !a.adam) {
         // pre-exchange aggregation: the rank's gradient rows of one key are added up (fp64, rounded once) BEFORE they travel — one (key, row) pair per distinct
         // key of the batch crosses xGMI.  The owner's apply then sums the ranks' partial sums in fp64 again: the update differs from the un-aggregated one by
         // the one extra rounding of each rank's partial sum (<= 1 ulp of the partial sum, far inside SPEC.md §4's 1e-6).  Sync-free: the padded unique list
         // goes through mee_partition_padded, which gives the padding to no shard.
+        // Not for Adam: its step m / (sqrt(v) + eps) hardly depends on the size of g, so where the ranks' partial sums cancel, the rounding of a partial sum
+        // (an ulp of the PARTIAL sum) becomes a large relative error of g and passes into the row unshrunk (SPEC.md §5).  Adam's pairs travel as they are.
         if (n) if (int rc = mee_dedup_sum(c->dd, d_keys, d_grads, n, c->uniq, c->urows, nullptr, nullptr, 0, stream)) return rc;
         if (int rc = push(c, c->uniq, c->urows, n, st, &rt, /*skip_padding=*/true)) return rc;
     } else if (int rc = push(c, d_keys, d_grads ? d_grads : c->send_rows, n, st, &rt)) return rc;

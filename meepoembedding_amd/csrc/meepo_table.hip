@@ -48,6 +48,13 @@ const Roctx& roctx_api() {
     return api;
 }
 
+// Bind roctx while the library is being loaded, not at the first API call: loading the roctx library registers it with
+// rocprofiler-register, which calls setenv / unsetenv.  Done lazily, that happened inside the first call of whichever host thread
+// came first, while the caller's other threads could be reading the environment (getenv walking environ as it is rebuilt:
+// SIGSEGV in the G-rank-threads run of tests/cabi/sharded_mp_test.cpp).  At load time the environment is not yet shared with threads
+// that use this library.
+__attribute__((constructor)) static void bind_roctx_at_load() { (void)roctx_api(); }
+
 }  // namespace mee
 
 namespace mee {

@@ -213,7 +213,8 @@ class PeerShardedFind:
 
     def apply_adam(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999,
                    eps: float = 1e-8, step: int = 1, check_overflow: bool = True, dedup: bool = False) -> None:
-        self._deliver(keys, grads, aggregate=dedup)
+        """dedup is accepted, but Adam's pairs travel un-aggregated (ShardedLookupTable.apply_adam says why)."""
+        self._deliver(keys, grads)
         self.local.apply_adam(self.inbox_keys, self.inbox_rows, lr, beta1, beta2, eps, step)
         self._done(check_overflow)
 

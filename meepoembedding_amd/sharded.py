@@ -123,7 +123,7 @@ class ShardedLookupTable:
     def _aggregate(self, keys: torch.Tensor, grads: torch.Tensor):
         """Pre-exchange gradient aggregation: one (key, summed row) pair per distinct key of this rank's batch (fp64 sums rounded once, mee_dedup_sum) —
         on skewed streams the backward's bytes on xGMI scale with the distinct keys.  The owner's apply adds the ranks' partial sums up in fp64 again:
-        within 1e-6 of the un-aggregated update (one extra rounding per rank and key)."""
+        within 1e-6 of the un-aggregated update (one extra rounding per rank and key).  Adagrad only (see apply_adam)."""
         keys = keys.contiguous().view(-1)
         uniq, gsum, _, _ = self.local.dedup_sum(keys, grads.contiguous().view(keys.numel(), -1), compact=True)   # (this path synchronises for its split sizes anyway)
         return uniq, gsum
@@ -136,8 +136,8 @@ class ShardedLookupTable:
 
     def apply_adam(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999,
                    eps: float = 1e-8, step: int = 1, dedup: bool = False) -> None:
-        if dedup:
-            keys, grads = self._aggregate(keys, grads)
+        """dedup is accepted like apply_adagrad's, but Adam's pairs are never aggregated before the exchange: its update barely depends on the size of
+        g, so the rounding of a rank's partial sum, where the ranks' sums cancel, would reach the row as a large relative error (SPEC.md §5)."""
         rk, rg, *_ = self._push(keys, grads)
         self.local.apply_adam(rk, rg, lr, beta1, beta2, eps, step)
 

@@ -3,7 +3,7 @@
 // Linked against the host-only build of csrc/*.hip, tests/cabi/hip_host_stub.cpp (device memory = host memory, launches do nothing) and — through
 // MEE_RCCL_LIB — tests/cabi/fake_rccl.cpp.  G rank THREADS (default 8: the node's GPU count) each create a communicator handle, tables (a hot one, a cold one,
 // one per context flavour) and sharded contexts (exact, padded, padded + dedup, exact + dedup over a hot/cold pair), run every mee_sharded_* operator a few
-// times, the single-table operators the contexts are built on, routers and peer contexts, and tear everything down.  Kernels do not run, so no VALUE is
+// times (the last flavour's tables train with Adam), the single-table operators the contexts are built on, routers and peer contexts, and tear everything down.  Kernels do not run, so no VALUE is
 // checked — only return codes: what the sanitizers watch is the library's own bookkeeping (offsets and sizes of every copy, lifetimes, the process-wide state
 // rank threads share: the lazy RCCL / roctx binders, the abort registry, the calibration cache, the per-table output ring, the thread-local error slot).
 #include <hip/hip_runtime.h>
@@ -22,10 +22,10 @@
 static char g_id[MEE_COMM_ID_BYTES];
 static std::atomic<int> g_id_ready{0};
 
-static mee_table* make_table(uint64_t cap, uint32_t dim, uint64_t max_batch, uint32_t mem) {
+static mee_table* make_table(uint64_t cap, uint32_t dim, uint64_t max_batch, uint32_t mem, uint32_t optimizer = MEE_OPT_ADAGRAD) {
     mee_config c;
     memset(&c, 0, sizeof c);
-    c.struct_size = sizeof c; c.capacity = cap; c.dim = dim; c.optimizer = MEE_OPT_ADAGRAD; c.max_batch = max_batch; c.value_memory = mem; c.flags = MEE_FLAG_TRACK_HITS;
+    c.struct_size = sizeof c; c.capacity = cap; c.dim = dim; c.optimizer = optimizer; c.max_batch = max_batch; c.value_memory = mem; c.flags = MEE_FLAG_TRACK_HITS;
     mee_table* t = nullptr;
     return mee_table_create(&c, &t) == MEE_OK ? t : nullptr;
 }
@@ -45,10 +45,12 @@ static int run_rank(int rank, int G) {
     std::vector<uint8_t> found(B);
     std::vector<int64_t> slots(B), uniq(B), inverse(B);
     std::vector<uint32_t> counts(B);
-    struct Flavour { double slack; uint32_t flags; bool cold; } flavours[] = {{0.0, 0u, false}, {1.5, 0u, false}, {1.25, MEE_SHARDED_DEDUP, false}, {0.0, MEE_SHARDED_DEDUP, true}};
+    struct Flavour { double slack; uint32_t flags; bool cold; bool adam; } flavours[] = {
+        {0.0, 0u, false, false}, {1.5, 0u, false, false}, {1.25, MEE_SHARDED_DEDUP, false, false}, {0.0, MEE_SHARDED_DEDUP, true, false}, {1.25, MEE_SHARDED_DEDUP, true, true}};
     for (const Flavour& f : flavours) {
-        mee_table* hot = make_table(1 << 15, dim, (uint64_t)G * (B + 2048), MEE_MEM_HBM);
-        mee_table* cold = f.cold ? make_table(1 << 15, dim, (uint64_t)G * (B + 2048), MEE_MEM_HOST_PINNED) : nullptr;
+        const uint32_t opt = f.adam ? MEE_OPT_ADAM : MEE_OPT_ADAGRAD;
+        mee_table* hot = make_table(1 << 15, dim, (uint64_t)G * (B + 2048), MEE_MEM_HBM, opt);
+        mee_table* cold = f.cold ? make_table(1 << 15, dim, (uint64_t)G * (B + 2048), MEE_MEM_HOST_PINNED, opt) : nullptr;
         if (!hot || (f.cold && !cold)) { fprintf(stderr, "[rank %d] table: %s\n", rank, mee_last_error()); return 4; }
         mee_sharded_options o;
         memset(&o, 0, sizeof o);
@@ -61,7 +63,8 @@ static int run_rank(int rank, int G) {
             MEECK(mee_sharded_find(s, keys.data(), n, out.data(), found.data(), nullptr));
             MEECK(mee_sharded_find_or_insert(s, keys.data(), n, out.data(), found.data(), nullptr));
             MEECK(mee_sharded_assign(s, keys.data(), rows.data(), n, found.data(), nullptr));
-            MEECK(mee_sharded_apply_adagrad(s, keys.data(), rows.data(), n, 0.01f, 1e-10f, nullptr));
+            if (f.adam) MEECK(mee_sharded_apply_adam(s, keys.data(), rows.data(), n, 0.01f, 0.8f, 0.99f, 1e-6f, (uint64_t)rep + 1, nullptr));
+            else MEECK(mee_sharded_apply_adagrad(s, keys.data(), rows.data(), n, 0.01f, 1e-10f, nullptr));
             MEECK(mee_sharded_remove(s, keys.data(), n / 2, found.data(), nullptr));
             size_t total = 0;
             MEECK(mee_sharded_size(s, &total, nullptr));
@@ -73,7 +76,8 @@ static int run_rank(int rank, int G) {
         MEECK(mee_find(hot, keys.data(), B, out.data(), found.data(), nullptr));
         MEECK(mee_find_ex(hot, keys.data(), B, out.data() + (rank & 1) * dim, found.data(), MEE_FIND_STREAM_ROWS, nullptr));
         MEECK(mee_find_located_prepare(hot, keys.data(), B, out.data(), found.data(), slots.data(), nullptr));
-        MEECK(mee_apply_adagrad_located(hot, keys.data(), slots.data(), rows.data(), B, 0.01f, 1e-10f, nullptr));
+        if (f.adam) MEECK(mee_apply_adam_located(hot, keys.data(), slots.data(), rows.data(), B, 0.01f, 0.9f, 0.999f, 1e-8f, 1, nullptr));
+        else MEECK(mee_apply_adagrad_located(hot, keys.data(), slots.data(), rows.data(), B, 0.01f, 1e-10f, nullptr));
         MEECK(mee_dedup_keys(hot, keys.data(), B, uniq.data(), inverse.data(), -1, nullptr));
         MEECK(mee_dedup_sum(hot, keys.data(), rows.data(), B, uniq.data(), out.data(), counts.data(), inverse.data(), -1, nullptr));
         MEECK(mee_assign(hot, keys.data(), rows.data(), B, found.data(), nullptr));

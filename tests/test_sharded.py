@@ -15,6 +15,10 @@ from meepoembedding_amd import synth
 from meepoembedding_amd.sharded import ShardedLookupTable
 
 DIM, NKEYS, BATCH = 16, 6000, 4000
+OPTS = {"adagrad": oracle.OPT_ADAGRAD, "adam": oracle.OPT_ADAM}
+# Adam runs two steps: the defaults first, then step 2 with other betas and eps (SPEC §4: every call carries its own)
+ADAM = {1: dict(lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8, step=1), 2: dict(lr=0.005, beta1=0.8, beta2=0.99, eps=1e-6, step=2)}
+N_PLANES = {"adagrad": 1, "adam": 2}   # optimizer state planes an export carries
 
 
 def _free_port():
@@ -35,41 +39,72 @@ def _batches(world, dim=DIM):
     return out
 
 
-def _global_reference(world, dim=DIM):
+def _adam_extra(rank, dim):
+    """Keys (and rows) a rank inserts besides its batch under Adam: step 1 leaves them alone, step 2 meets them with m = v = 0."""
+    k = synth.keys_np(5, rank * 200, 200)
+    return k, synth.rows_np(k, dim, 3)
+
+
+def _adam_step2(rank, keys, dim):
+    """Adam's second step on a rank: a third of its step-1 batch `keys` (duplicates included), keys removed after step 1 (ignored) and
+    keys step 1 never touched (some twice)."""
+    xk = _adam_extra(rank, dim)[0]
+    k2 = np.concatenate([keys[::3], _removed(rank)[:40], xk, xk[:50]])
+    g2 = (np.random.default_rng(200 + rank).standard_normal((k2.size, dim)) * 0.01).astype(np.float32)
+    return k2, g2
+
+
+def _global_reference(world, dim=DIM, opt="adagrad"):
     """One table, batches applied in rank order == SPEC §5 'ordered by source rank then batch position'."""
-    o = oracle.OracleTable(16384, dim, optimizer=oracle.OPT_ADAGRAD, initial_accumulator=0.1)
+    o = oracle.OracleTable(16384, dim, optimizer=OPTS[opt], initial_accumulator=0.1)
     b = _batches(world, dim)
     o.insert(np.concatenate([x[0] for x in b]), np.concatenate([x[1] for x in b]))
-    o.apply_adagrad(np.concatenate([x[0] for x in b]), np.concatenate([x[2] for x in b]), 0.05, 1e-10)
+    if opt == "adagrad":
+        o.apply_adagrad(np.concatenate([x[0] for x in b]), np.concatenate([x[2] for x in b]), 0.05, 1e-10)
+    else:
+        x = [_adam_extra(r, dim) for r in range(world)]
+        o.insert(np.concatenate([k for k, _ in x]), np.concatenate([v for _, v in x]))
+        o.apply_adam(np.concatenate([x[0] for x in b]), np.concatenate([x[2] for x in b]), **ADAM[1])
     for r in range(world):
         o.remove(_removed(r))
+    if opt == "adam":
+        s2 = [_adam_step2(r, b[r][0], dim) for r in range(world)]
+        o.apply_adam(np.concatenate([k for k, _ in s2]), np.concatenate([g for _, g in s2]), **ADAM[2])
     return o
+
+
+def _apply(t, opt, step, keys, grads, lr, **kw):
+    """Optimizer step `step` of the flows below on any sharded table: Adagrad at `lr` (eps 1e-10), or Adam with ADAM[step]."""
+    if opt == "adagrad":
+        t.apply_adagrad(keys, grads, lr=lr, eps=1e-10, **kw)
+    else:
+        t.apply_adam(keys, grads, **ADAM[step], **kw)
 
 
 def _removed(rank):
     return synth.keys_np(1, 0, NKEYS)[rank * 7::101]
 
 
-def _run_rank(rank, world, port, backend, q, tiered=False, dim=DIM):
+def _run_rank(rank, world, port, backend, q, tiered=False, dim=DIM, opt="adagrad"):
     try:
-        _run_rank_body(rank, world, port, backend, q, tiered, dim)
+        _run_rank_body(rank, world, port, backend, q, tiered, dim, opt)
     except BaseException as e:   # report at once: the parent must not sit out its queue timeout on the GPU box
         import traceback
         q.put(("error", rank, "".join(traceback.format_exception(type(e), e, e.__traceback__))))
         raise
 
 
-def _run_rank_body(rank, world, port, backend, q, tiered=False, DIM=DIM):
+def _run_rank_body(rank, world, port, backend, q, tiered=False, DIM=DIM, opt="adagrad"):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     if backend == "gloo":
         from _cpu_backend import CpuRouter, CpuTable
         dist.init_process_group("gloo", rank=rank, world_size=world)
         dev = torch.device("cpu")
-        mk_local = lambda: CpuTable(16384, DIM, optimizer=oracle.OPT_ADAGRAD, initial_accumulator=0.1)
+        mk_local = lambda: CpuTable(16384, DIM, optimizer=OPTS[opt], initial_accumulator=0.1)
         if tiered:   # BASELINE configs[4]: every shard is a hot/cold pair
             from meepoembedding_amd.tiered import TieredLookupTable
             mk_flat = mk_local
-            mk_local = lambda: TieredLookupTable(CpuTable(2048, DIM, optimizer=oracle.OPT_ADAGRAD, initial_accumulator=0.1), mk_flat(), hot_key_limit=1200)
+            mk_local = lambda: TieredLookupTable(CpuTable(2048, DIM, optimizer=OPTS[opt], initial_accumulator=0.1), mk_flat(), hot_key_limit=1200)
         local = mk_local()
         router = CpuRouter(world)
     elif backend in ("gloo-gpu", "fake-rccl"):
@@ -77,38 +112,46 @@ def _run_rank_body(rank, world, port, backend, q, tiered=False, DIM=DIM):
             os.environ["MEE_RCCL_LIB"] = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "build", "libfake_rccl.so")
         # several ranks share ONE GPU; the exchange is staged through host memory over gloo — every HIP kernel of the
         # multi-rank path (partition with G > 1, find on received keys, un-permute) runs for real
-        from meepoembedding_amd import OPT_ADAGRAD, LookupTable, Router
+        from meepoembedding_amd import LookupTable, Router
         dev = torch.device("cuda", 0)
         torch.cuda.set_device(dev)
         dist.init_process_group("gloo", rank=rank, world_size=world)
-        mk_local = lambda: LookupTable(16384, DIM, device=dev, optimizer=OPT_ADAGRAD, initial_accumulator=0.1, max_batch=world * BATCH)
+        mk_local = lambda: LookupTable(16384, DIM, device=dev, optimizer=OPTS[opt], initial_accumulator=0.1, max_batch=world * BATCH)
         if tiered:   # configs[4] on the real backend: HBM table in front of a pinned-host-DRAM table, per shard
             from meepoembedding_amd import _lib
             from meepoembedding_amd.tiered import TieredLookupTable
             mk_local = lambda: TieredLookupTable(
-                LookupTable(2048, DIM, device=dev, optimizer=OPT_ADAGRAD, initial_accumulator=0.1, max_batch=world * BATCH),
-                LookupTable(16384, DIM, device=dev, optimizer=OPT_ADAGRAD, initial_accumulator=0.1, max_batch=world * BATCH,
+                LookupTable(2048, DIM, device=dev, optimizer=OPTS[opt], initial_accumulator=0.1, max_batch=world * BATCH),
+                LookupTable(16384, DIM, device=dev, optimizer=OPTS[opt], initial_accumulator=0.1, max_batch=world * BATCH,
                             value_memory=_lib.MEM_HOST_PINNED), hot_key_limit=1200)
         local = mk_local()
         router = Router(world, BATCH, device=dev)
     else:
-        from meepoembedding_amd import OPT_ADAGRAD, LookupTable, Router
+        from meepoembedding_amd import LookupTable, Router
         dev = torch.device("cuda", rank)
         torch.cuda.set_device(dev)
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
-        mk_local = lambda: LookupTable(16384, DIM, device=dev, optimizer=OPT_ADAGRAD, initial_accumulator=0.1, max_batch=world * BATCH)
+        mk_local = lambda: LookupTable(16384, DIM, device=dev, optimizer=OPTS[opt], initial_accumulator=0.1, max_batch=world * BATCH)
         local = mk_local()
         router = Router(world, BATCH, device=dev)
     try:
         sh = ShardedLookupTable(local, router)
-        keys, rows, grads = (torch.from_numpy(x).to(dev) for x in _batches(world, DIM)[rank])
+        batch = _batches(world, DIM)[rank]
+        keys, rows, grads = (torch.from_numpy(x).to(dev) for x in batch)
         sh.insert(keys, rows)
+        if opt == "adam":
+            sh.insert(*(torch.from_numpy(x).to(dev) for x in _adam_extra(rank, DIM)))
         # odd ranks aggregate their gradients before the exchange (one summed row per distinct key of the rank's batch travels), even ranks send every
-        # occurrence: the owners' applies add both kinds up in fp64 — the global reference (un-aggregated, one table) must still be met within 1e-6
-        sh.apply_adagrad(keys, grads, lr=0.05, eps=1e-10, dedup=bool(rank & 1))
+        # occurrence: the owners' applies add both kinds up in fp64 — the global reference (un-aggregated, one table) must still be met within 1e-6.
+        # (Adam's applies take dedup=True but never aggregate, SPEC §5: at dim 100 one element whose three rows cancel would be 1.8e-5 off)
+        _apply(sh, opt, 1, keys, grads, 0.05, dedup=bool(rank & 1))
         dist.barrier()
         sh.remove(torch.from_numpy(_removed(rank)).to(dev))
         dist.barrier()
+        if opt == "adam":   # a second step: removed keys must be ignored, keys that step 1 left alone start from m = v = 0 with step 2's bias correction
+            k2, g2 = (torch.from_numpy(x).to(dev) for x in _adam_step2(rank, batch[0], DIM))
+            sh.apply_adam(k2, g2, **ADAM[2], dedup=bool(rank & 1))
+            dist.barrier()
         probe = torch.from_numpy(np.concatenate([synth.keys_np(1, 0, NKEYS)[rank::3], synth.keys_np(9, rank * 50, 50)])).to(dev)
         out, found = sh.find(probe)
         # the same lookup with pre-exchange dedup on a duplicate-heavy batch (+ a reserved key) must give the same answer
@@ -139,7 +182,7 @@ def _run_rank_body(rank, world, port, backend, q, tiered=False, DIM=DIM):
             pf.close()
             # mutators over the payload inboxes (padded, fixed n, no all-to-all) == the all-to-all mutators
             cap = int(BATCH / world * 1.25) + 4096
-            mk = lambda: LookupTable(16384, DIM, device=dev, optimizer=OPT_ADAGRAD, initial_accumulator=0.1, max_batch=world * cap)
+            mk = lambda: LookupTable(16384, DIM, device=dev, optimizer=OPTS[opt], initial_accumulator=0.1, max_batch=world * cap)
             la, lb = mk(), mk()
             pt = PeerShardedFind(la, Router(world, BATCH, device=dev), max_batch=BATCH, payload=True)
             sb = ShardedLookupTable(lb, router)
@@ -147,18 +190,18 @@ def _run_rank_body(rank, world, port, backend, q, tiered=False, DIM=DIM):
             hot_g = torch.cat([grads[::2], grads[:2000]])
             for t in (pt, sb):
                 t.insert(keys, rows)
-                t.apply_adagrad(keys, grads, lr=0.05, eps=1e-10)
+                _apply(t, opt, 1, keys, grads, 0.05)
                 t.assign(keys[:300], rows[300:600])
                 # the peer-mapped path aggregates before it pushes (sync-free mee_dedup_sum + padded partition), the all-to-all path does not: same update within 1e-6
                 if t is pt:
-                    t.apply_adagrad(hot_k, hot_g, lr=0.01, eps=1e-10, dedup=True)
+                    _apply(t, opt, 2, hot_k, hot_g, 0.01, dedup=True)
                 else:
-                    t.apply_adagrad(hot_k, hot_g, lr=0.01, eps=1e-10)
+                    _apply(t, opt, 2, hot_k, hot_g, 0.01)
             dist.barrier()
             ea_, eb_ = la.export(with_state=True), lb.export(with_state=True)
             ia, ib = torch.argsort(ea_[0]), torch.argsort(eb_[0])
             assert torch.equal(ea_[0][ia], eb_[0][ib]) and la.status() == 0
-            for xa, xb in zip(ea_[1:3], eb_[1:3]):
+            for xa, xb in zip(ea_[1:2 + N_PLANES[opt]], eb_[1:2 + N_PLANES[opt]]):
                 torch.testing.assert_close(xa[ia], xb[ib], rtol=1e-6, atol=1e-9)
             o4, f4 = pt.find(probe)
             o5, f5 = sb.find(probe)
@@ -178,7 +221,7 @@ def _run_rank_body(rank, world, port, backend, q, tiered=False, DIM=DIM):
                 PeerShardedFind(local, Router(world, 1 << 16, device=dev), max_batch=1 << 16, payload=True)
             pt.close()
         if backend in ("nccl", "fake-rccl"):
-            _native_rccl_checks(rank, world, dev, DIM, keys, rows, grads, probe, dup, router)
+            _native_rccl_checks(rank, world, dev, DIM, keys, rows, grads, probe, dup, router, opt)
         if backend in ("nccl", "fake-rccl", "gloo-gpu") and not tiered:
             _pipelined_lookup_checks(rank, world, dev, DIM, sh, local, probe, dup, backend)
         if not tiered:
@@ -197,22 +240,23 @@ def _run_rank_body(rank, world, port, backend, q, tiered=False, DIM=DIM):
             if rank == 0:
                 import shutil
                 shutil.rmtree(ck, ignore_errors=True)
-        ek, ev, ea, _ = sh.export_local(with_state=True)
-        q.put((rank, probe.cpu().numpy(), out.cpu().numpy(), found.cpu().numpy(), total, ek.cpu().numpy(), ev.cpu().numpy(), ea.cpu().numpy()))
+        ek, ev, ea, eb = sh.export_local(with_state=True)
+        q.put((rank, probe.cpu().numpy(), out.cpu().numpy(), found.cpu().numpy(), total, ek.cpu().numpy(), ev.cpu().numpy(), ea.cpu().numpy(),
+               None if eb is None else eb.cpu().numpy()))
         dist.barrier()
     finally:
         dist.destroy_process_group()
 
 
-def _native_rccl_checks(rank, world, dev, dim, keys, rows, grads, probe, dup, router):
+def _native_rccl_checks(rank, world, dev, dim, keys, rows, grads, probe, dup, router, opt="adagrad"):
     """The exchange behind the C-ABI (mee_sharded_*: grouped ncclSend/ncclRecv inside the library), exact and padded segment layouts, with
     pre-exchange dedup, over a hot/cold pair (BASELINE configs[4]) and over a local table too small for one apply of what arrives (chunked
     by key range) — all against the torch.distributed path on tables of their own: same op sequence -> same exports, same lookups."""
-    from meepoembedding_amd import OPT_ADAGRAD, LookupTable, MeepoError, _lib
+    from meepoembedding_amd import LookupTable, MeepoError, _lib
     from meepoembedding_amd.sharded import RcclShardedTable
     cap_pad = int(np.ceil(BATCH / world * 1.5)) + 1024
     big = max(world * BATCH, world * cap_pad)
-    mk = lambda mb=big, cap=16384, **kw: LookupTable(cap, dim, device=dev, optimizer=OPT_ADAGRAD, initial_accumulator=0.1, max_batch=mb, **kw)
+    mk = lambda mb=big, cap=16384, **kw: LookupTable(cap, dim, device=dev, optimizer=OPTS[opt], initial_accumulator=0.1, max_batch=mb, **kw)
     l_ref, l_exact, l_pad, l_dd, l_ddp, l_small = mk(), mk(), mk(), mk(), mk(), mk(mb=BATCH // 2)
     l_hot, l_cold = mk(cap=8192), mk(value_memory=_lib.MEM_HOST_PINNED)
     ref = ShardedLookupTable(l_ref, router)
@@ -229,10 +273,10 @@ def _native_rccl_checks(rank, world, dev, dim, keys, rows, grads, probe, dup, ro
     tables = (ref, exact, padded, dd_exact, dd_pad, small, tiered)
     for t in tables:
         t.insert(keys, rows)
-        t.apply_adagrad(keys, grads, lr=0.05, eps=1e-10)
+        _apply(t, opt, 1, keys, grads, 0.05)
         fa = t.assign(keys[:300], rows[300:600])
         fr = t.remove(torch.from_numpy(_removed(rank)).to(dev))
-        t.apply_adagrad(keys[::2], grads[::2], lr=0.01, eps=1e-10)
+        _apply(t, opt, 2, keys[::2], grads[::2], 0.01)
         o_p, f_p = t.find(probe)
         o_d, f_d = t.find(dup[:BATCH])
         o_m, f_m = t.find_or_insert(mix)
@@ -254,7 +298,7 @@ def _native_rccl_checks(rank, world, dev, dim, keys, rows, grads, probe, dup, ro
         e = t.export_local(with_state=True)
         i = torch.argsort(e[0])
         assert torch.equal(e[0][i], e_ref[0][i_ref]) and t.local.status() == 0
-        for xa, xb in zip(e[1:3], e_ref[1:3]):
+        for xa, xb in zip(e[1:2 + N_PLANES[opt]], e_ref[1:2 + N_PLANES[opt]]):
             torch.testing.assert_close(xa[i], xb[i_ref], rtol=1e-6, atol=1e-9)
     # the pair really is two tiers, each key in exactly one of them
     n_hot, n_cold = l_hot.size(), l_cold.size()
@@ -329,29 +373,31 @@ def _pipelined_lookup_checks(rank, world, dev, dim, sh, local, probe, dup, backe
     dist.barrier()
 
 
-def _check(results, world, dim=DIM):
-    o = _global_reference(world, dim)
-    allk, allv, alla = [], [], []
-    for rank, probe, out, found, total, ek, ev, ea in results:
+def _check(results, world, dim=DIM, opt="adagrad"):
+    o = _global_reference(world, dim, opt)
+    allk, allv, alla, allb = [], [], [], []
+    for rank, probe, out, found, total, ek, ev, ea, eb in results:
         eo, ef = o.find(probe)
         assert np.array_equal(found, ef)
         np.testing.assert_allclose(out, eo, rtol=1e-6, atol=1e-9)
         assert total == o.size()
         assert (oracle.hash_batch(ek, 1, world)[2] == rank).all(), "shard holds a key it does not own"
-        allk.append(ek); allv.append(ev); alla.append(ea)
+        allk.append(ek); allv.append(ev); alla.append(ea); allb.append(eb)
     gk, gv, ga = np.concatenate(allk), np.concatenate(allv), np.concatenate(alla)
-    ok, ov, oa, _ = o.export(with_state=True)
+    ok, ov, oa, ob = o.export(with_state=True)
     a, b = np.argsort(gk), np.argsort(ok)
     assert np.array_equal(gk[a], ok[b])
     np.testing.assert_allclose(gv[a], ov[b], rtol=1e-6, atol=1e-9)
     np.testing.assert_allclose(ga[a], oa[b], rtol=1e-6, atol=1e-9)
+    if opt == "adam":   # v as well: a key updated twice in one step (or with another step's betas) shows in it
+        np.testing.assert_allclose(np.concatenate(allb)[a], ob[b], rtol=1e-6, atol=1e-9)
 
 
-def _launch(world, backend, tiered=False, dim=DIM):
+def _launch(world, backend, tiered=False, dim=DIM, opt="adagrad"):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_run_rank, args=(r, world, port, backend, q, tiered, dim)) for r in range(world)]
+    procs = [ctx.Process(target=_run_rank, args=(r, world, port, backend, q, tiered, dim, opt)) for r in range(world)]
     for p in procs:
         p.start()
     results = []
@@ -370,10 +416,17 @@ def _launch(world, backend, tiered=False, dim=DIM):
     return sorted(results, key=lambda x: x[0])
 
 
-@pytest.mark.parametrize("world", [2, 3, 8])
-def test_sharded_gloo_cpu(built, world):
+def _cases(adagrad, other):
+    """Parameter sets: the Adagrad cases keep their ids (no optimizer in them), the others carry theirs."""
+    adagrad = [c if isinstance(c, tuple) else (c,) for c in adagrad]
+    return [pytest.param(*c, "adagrad", id="-".join(map(str, c))) for c in adagrad] + \
+        [pytest.param(*c, id="-".join(map(str, c))) for c in other]
+
+
+@pytest.mark.parametrize("world,opt", _cases([2, 3, 8], [(2, "adam")]))
+def test_sharded_gloo_cpu(built, world, opt):
     """(8 = the node's GPU count: the host logic's segment bookkeeping at G = 8, on oracle-backed shards)"""
-    _check(_launch(world, "gloo"), world)
+    _check(_launch(world, "gloo", opt=opt), world, opt=opt)
 
 
 def test_sharded_tiered_gloo_cpu(built):
@@ -381,29 +434,40 @@ def test_sharded_tiered_gloo_cpu(built):
     _check(_launch(2, "gloo", tiered=True), 2)
 
 
-# dims: 16 = configs[0], 64 = the metric's / configs[4]'s, 128 = configs[3]'s
+def test_sharded_tiered_gloo_cpu_adam(built):
+    _check(_launch(2, "gloo", tiered=True, opt="adam"), 2, opt="adam")
+
+
+def test_sharded_gloo_cpu_adam_wide(built):
+    """dim 100: three gradient rows of one key (two of them from rank 1, which asks for dedup) add up to 4e-8.  Had rank 1 sent its rounded partial
+    sum, Adam's row would be 1.8e-5 off the one-table reference (SPEC §5: Adam's pairs are never aggregated)."""
+    _check(_launch(2, "gloo", dim=100, opt="adam"), 2, 100, "adam")
+
+
+# dims: 16 = configs[0], 64 = the metric's / configs[4]'s, 128 = configs[3]'s; 100 and 260 (dim/4 = 25, 65) give the exchange's and the
+# tiers' 16-lane row loops a ragged last pass
 @pytest.mark.gpu
 # (5 ranks + this process: the most processes the GPU box lets one job keep on its card at once — G = 8 runs as threads of one process: tests/cabi/sharded_mp_test.cpp)
-@pytest.mark.parametrize("world,dim", [(2, 16), (4, 16), (2, 64), (4, 128), (2, 128), (5, 64)])
-def test_sharded_multi_rank_on_one_gpu(dev, world, dim):
-    _check(_launch(world, "gloo-gpu", dim=dim), world, dim)
+@pytest.mark.parametrize("world,dim,opt", _cases([(2, 16), (4, 16), (2, 64), (4, 128), (2, 128), (5, 64)], [(2, 100, "adam"), (3, 260, "adagrad")]))
+def test_sharded_multi_rank_on_one_gpu(dev, world, dim, opt):
+    _check(_launch(world, "gloo-gpu", dim=dim, opt=opt), world, dim, opt)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim", [16, 64])
-def test_sharded_tiered_multi_rank_on_one_gpu(dev, dim):
+@pytest.mark.parametrize("dim,opt", _cases([16, 64], [(100, "adam")]))
+def test_sharded_tiered_multi_rank_on_one_gpu(dev, dim, opt):
     """configs[4] shape on the HIP backend: two ranks, every shard an HBM table backed by a pinned-host table."""
-    _check(_launch(2, "gloo-gpu", tiered=True, dim=dim), 2, dim)
+    _check(_launch(2, "gloo-gpu", tiered=True, dim=dim, opt=opt), 2, dim, opt)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world,dim", [(2, 64), (3, 16), (4, 128)])
-def test_native_exchange_multi_rank_on_one_gpu(dev, world, dim):
+@pytest.mark.parametrize("world,dim,opt", _cases([(2, 64), (3, 16), (4, 128)], [(2, 100, "adam"), (3, 260, "adam")]))
+def test_native_exchange_multi_rank_on_one_gpu(dev, world, dim, opt):
     """The exchange behind the C-ABI (mee_sharded_*: partition, counts exchange, grouped send/recv of keys and rows, the way back,
     un-permute; exact AND padded segment layouts) with 2-4 ranks.  RCCL refuses several ranks on one device, so the library binds a
     shared-memory stand-in for librccl (MEE_RCCL_LIB; tests/cabi/fake_rccl.cpp) — the library's own bookkeeping for G > 1 is what
     runs, and it must agree with the torch.distributed path and, through it, with ONE global oracle table."""
-    _check(_launch(world, "fake-rccl", dim=dim), world, dim)
+    _check(_launch(world, "fake-rccl", dim=dim, opt=opt), world, dim, opt)
 
 
 @pytest.mark.gpu

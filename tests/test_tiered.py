@@ -82,9 +82,10 @@ def test_tiered_cpu_logic(built, opt):
     assert 0 < hot.size() <= 600 and cold.size() > 0, "both tiers must have been used"
 
 
-# dims: 16 = configs[0], 64 = configs[4] (the hot/cold tier's stated shape), 128 = configs[3]
+# dims: 16 = configs[0], 64 = configs[4] (the hot/cold tier's stated shape), 128 = configs[3]; 100 and 260 (dim/4 = 25, 65): the cold pass's
+# 16-lane row loop (find_missing_kernel) and the migrations get a ragged last column chunk
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim", [16, 64, 128])
+@pytest.mark.parametrize("dim", [16, 64, 128, 100, 260])
 @pytest.mark.parametrize("opt", [oracle.OPT_ADAGRAD, oracle.OPT_ADAM])
 def test_tiered_hbm_plus_pinned_host(dev, opt, dim):
     from meepoembedding_amd import LookupTable, _lib
