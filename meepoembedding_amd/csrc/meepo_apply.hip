@@ -1535,13 +1535,16 @@ int bucket_apply_launch(mee_table* t, const float* d_grads, uint32_t n, const Op
     // one block per bucket (+ the blocks a skewed stream's slabs need); on a skewed batch the blocks work through a list of units, the slabs of the
     // split buckets first (run_units)
     const bool full = t->part_full;   // as the partition decided: FULL = a skewed stream (hot keys' buckets may exist, the grid is one round of the block slots)
-    const uint32_t grid = full ? t->part_grid : A.nbk;   // LEAN: block = bucket
-#define BK_FULL (t->bk.dev_copy)
-#define BKT(K, D4, LOC) do { if (full) bkt_apply_kernel<K, D4, LOC, false, true><<<grid, kApplyThreads, 0, st>>>(A, BK_FULL); else bkt_apply_kernel<K, D4, LOC, false, false><<<grid, kApplyThreads, 0, st>>>(A, t->bk); } while (0)
-#define BKT_L(K, D4) do { if (d_desc) { if (full) bkt_apply_kernel<K, D4, true, true, true><<<grid, kApplyThreads, 0, st>>>(A, BK_FULL); else bkt_apply_kernel<K, D4, true, true, false><<<grid, kApplyThreads, 0, st>>>(A, t->bk); } \
-                          else if (d_slots) BKT(K, D4, true); else BKT(K, D4, false); } while (0)
-#define BKT_D(K) do { if (t->dim4 == 16) BKT_L(K, 16); else if (t->dim4 == 32) BKT_L(K, 32); else BKT_L(K, 0); } while (0)
-    if (a.kind == MEE_OPT_ADAGRAD) BKT_D(MEE_OPT_ADAGRAD); else BKT_D(MEE_OPT_ADAM);
+    // the bucketed apply on `grid` blocks.  Its rows: a table group's (located), located (d_slots) or by key.  FULL reads the partition's scratch
+    // from device memory (t->bk.dev_copy), LEAN takes it as kernel arguments.
+    const int rows = d_desc ? 2 : d_slots ? 1 : 0;
+    auto apply = [&](bool full, uint32_t grid) {
+        with_value<MEE_OPT_ADAGRAD, MEE_OPT_ADAM>(a.kind, [&](auto kind) { with_row_shape(t->dim4, [&](auto d4) { with_value<2, 1, 0>(rows, [&](auto r) { with_flag(full, [&](auto f) {
+            auto bk = [&] { if constexpr (f) return t->bk.dev_copy; else return t->bk; };
+            bkt_apply_kernel<kind, d4, (r >= 1), (r == 2), f><<<grid, kApplyThreads, 0, st>>>(A, bk());
+        }); }); }); });
+    };
+    apply(full, full ? t->part_grid : A.nbk);   // LEAN: block = bucket
     // The FULL kernel needs scratch memory (124-192 B per lane), the LEAN kernel none.  A queue gets its scratch when the first launch that needs it arrives: the
     // runtime allocates it on the host and re-submits — 147 us measured between a stream's forward and its first FULL apply (the second skewed step of a stream: 230-290 us
     // against 95 from the third on).  So the first LEAN apply a table sees on a stream is followed by ONE empty launch of the FULL kernel (same instance, same grid, no batch:
@@ -1553,16 +1556,10 @@ int bucket_apply_launch(mee_table* t, const float* d_grads, uint32_t n, const Op
             for (uint32_t i = 3; i > 0; --i) t->full_ready[i] = t->full_ready[i - 1];
             t->full_ready[0] = (void*)st;
             if (t->full_ready_n < 4) ++t->full_ready_n;
-            const bool full = true;
-            const uint32_t grid = t->part_grid ? t->part_grid : A.nbk;   // (the FULL kernel's grid: one round of the block slots)
             A.part_blocks = 0;
-            if (a.kind == MEE_OPT_ADAGRAD) BKT_D(MEE_OPT_ADAGRAD); else BKT_D(MEE_OPT_ADAM);
+            apply(true, t->part_grid ? t->part_grid : A.nbk);   // (the FULL kernel's grid: one round of the block slots)
         }
     }
-#undef BKT_D
-#undef BKT_L
-#undef BKT
-#undef BK_FULL
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }

@@ -1001,9 +1001,7 @@ int bucket_dedup_sum(mee_table* t, const int64_t* d_keys, const float* d_grads, 
     A.hand_items = reinterpret_cast<uint4*>(t->bs.occ); A.hand_flag = t->bk_dd.pend_cnt; A.hand_head = t->bk_dd.pend_cnt + A.d.nbk_hash;
     A.handoff = d_grads && A.d.nbk != A.d.nbk_hash && (uint64_t)A.d.nbk_hash * kHandK * sizeof(uint4) <= (uint64_t)t->max_batch * 4;
     const uint32_t grid = A.d.nbk + hot_window_blocks(A.d, n, kSumWindow);
-    if (t->dim4 == 16) bkt_dedup_sum_kernel<16><<<grid, kDedupThreads, 0, st>>>(A, t->bk_dd);
-    else if (t->dim4 == 32) bkt_dedup_sum_kernel<32><<<grid, kDedupThreads, 0, st>>>(A, t->bk_dd);
-    else bkt_dedup_sum_kernel<0><<<grid, kDedupThreads, 0, st>>>(A, t->bk_dd);
+    with_row_shape(t->dim4, [&](auto d4) { bkt_dedup_sum_kernel<d4><<<grid, kDedupThreads, 0, st>>>(A, t->bk_dd); });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -1028,9 +1026,7 @@ int bucket_assign(mee_table* t, float* plane, const int64_t* d_keys, const float
     if (int rc = dedup_partition(t, d_keys, n, st, A.d, nullptr, nullptr, 0, d_found, nullptr, t->bk_dd.slots / kApplyBlocksPerCU * kAssignBlocksPerCU, kSumBucketMax)) return rc;
     A.tkeys = t->keys; A.rows = (float4*)plane; A.nb = t->nb; A.dim4 = t->dim4; A.values = (const float4*)d_values; A.found = d_found;
     const uint32_t grid = A.d.nbk + hot_window_blocks(A.d, n);
-    if (t->dim4 == 16) bkt_assign_kernel<16><<<grid, kDedupThreads, 0, st>>>(A, t->bk_dd);
-    else if (t->dim4 == 32) bkt_assign_kernel<32><<<grid, kDedupThreads, 0, st>>>(A, t->bk_dd);
-    else bkt_assign_kernel<0><<<grid, kDedupThreads, 0, st>>>(A, t->bk_dd);
+    with_row_shape(t->dim4, [&](auto d4) { bkt_assign_kernel<d4><<<grid, kDedupThreads, 0, st>>>(A, t->bk_dd); });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }

@@ -680,63 +680,59 @@ static bool outputs_rotate(const mee_table* t, const void* d_out, uint64_t bytes
     return distinct >= 2 && total > (64ull << 20);
 }
 
-// every dense lookup of one plane (declared with its defaults in meepo_table_int.h: find_or_insert's first pass calls it too)
+// The launch shape of a pooled lookup.  n (the number of keys, a host value) only picks it: mostly short bags -> four bags per wave on a grid of
+// n_bags / 16 blocks, a long average (12 keys or more per bag) -> one bag per wave on n_bags / 4.  f(d4, unroll, bags_per_wave, grid).
+template <class F> void with_pooled_shape(uint32_t dim4, size_t n, uint64_t n_bags, F&& f) {
+    with_row_shape(dim4, [&](auto d4) {
+        if (n / n_bags >= 12) f(d4, std::integral_constant<int, RowShape<d4>::pooled_unroll_1>{}, std::integral_constant<int, 1>{}, grid_for(n_bags, 4, 1u << 20));
+        else f(d4, std::integral_constant<int, RowShape<d4>::pooled_unroll_4>{}, std::integral_constant<int, 4>{}, grid_for(n_bags, 16, 1u << 20));
+    });
+}
+
+// every dense lookup of one plane (declared with FindPath in meepo_table_int.h: find_or_insert's first pass calls it too)
 int find_plane(const mee_table* t, const float* plane, float miss_value, const int64_t* d_keys, size_t n, float* d_out,
-               uint8_t* d_found, void* stream, bool missing_only, bool counted, bool rows_only,
-               int64_t* d_slots_out, bool unordered, bool skip_padding, int nt_call /* this call's cache policy (mee_find_ex); -1: the table's */) {
+               uint8_t* d_found, void* stream, FindPath path) {
     if (n == 0) return MEE_OK;
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
-    int R = t->find_rounds > 0 ? t->find_rounds : (t->dim4 == 16 ? 2 : 1);
-    if (t->dim4 != 16 && R > 4) R = 4;
-    if (t->dim4 != 16 && t->dim4 != 32 && R > 2) R = 2;
-    R = R >= 8 ? 8 : R >= 4 ? 4 : R >= 2 ? 2 : 1;
     const unsigned fblock = t->find_block == 64 || t->find_block == 128 ? (unsigned)t->find_block : 256u;   // (launch bound of find_kernel: 256)
-    const unsigned grid = grid_for(n, (fblock / 64u) * 4u * (unsigned)R, t->find_grid_cap > 0 ? (unsigned)t->find_grid_cap : (1u << 22));
-#define FIND1(D4, RR, NT) do { if (unordered) hipExtLaunchKernelGGL((find_kernel<D4, RR, NT>), dim3(grid), dim3(256), 0, st, nullptr, nullptr, hipExtAnyOrderLaunch, \
-                                        (const int64_t*)t->keys, (const f32x4*)plane, t->nb, d_keys, (uint64_t)n, (f32x4*)d_out, d_found, miss_value, t->dim4, (uint32_t*)nullptr, (int64_t*)nullptr, (int64_t)0); \
-                               else find_kernel<D4, RR, NT><<<grid, fblock, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, nullptr); } while (0)
-    const int nt = nt_call >= 0 ? nt_call : t->find_nt >= 0 ? (t->find_nt & 7)
-                 : ((uint64_t)n * t->dim * 4 <= (128ull << 20) && !outputs_rotate(t, d_out, (uint64_t)n * t->dim * 4) ? 4 : 0);
-#define FIND(D4, RR) do { switch (nt) { case 0: FIND1(D4, RR, 0); break; case 1: FIND1(D4, RR, 1); break; case 2: FIND1(D4, RR, 2); break; case 3: FIND1(D4, RR, 3); break; case 4: FIND1(D4, RR, 4); break; case 5: FIND1(D4, RR, 5); break; case 6: FIND1(D4, RR, 6); break; default: FIND1(D4, RR, 7); } } while (0)
-    if (skip_padding) {   // owner pass of a padded sharded exchange: EMPTY positions get neither a row nor a found byte (nobody reads them)
-        const bool cached = nt & 4;
-#define FINDP(D4, RR) do { if (cached) find_kernel<D4, RR, 132><<<grid, 256, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, nullptr); \
-                           else find_kernel<D4, RR, 128><<<grid, 256, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, nullptr); } while (0)
-        if (t->dim4 == 16) { if (R >= 2) FINDP(16, 2); else FINDP(16, 1); }
-        else if (t->dim4 == 32) { if (R >= 2) FINDP(32, 2); else FINDP(32, 1); }
-        else { if (R >= 2) FINDP(0, 2); else FINDP(0, 1); }
-#undef FINDP
-    } else
-    if (d_slots_out) {   // located find: the plain kernel + one 8-byte store per key
-        // cache policy of `out`: this is the forward of a TRAINING step — the apply that follows sweeps the Infinity Cache before the next
-        // forward, so keeping the dense output cached buys nothing and streaming stores win (136.9 -> 132.5 us per find + Adagrad step)
-        const bool cached_out = t->find_nt >= 0 && (t->find_nt & 4);
-#define FINDL(D4, RR) do { if (cached_out) find_kernel<D4, RR, 68><<<grid, fblock, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, nullptr, d_slots_out, handle_tag_of(t)); \
-                           else find_kernel<D4, RR, 64><<<grid, fblock, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, nullptr, d_slots_out, handle_tag_of(t)); } while (0)
-        if (t->dim4 == 16) { if (R >= 2) FINDL(16, 2); else FINDL(16, 1); }
-        else if (t->dim4 == 32) { if (R >= 2) FINDL(32, 2); else FINDL(32, 1); }
-        else { if (R >= 2) FINDL(0, 2); else FINDL(0, 1); }
-#undef FINDL
-    } else
-    if (missing_only) {
-        const unsigned gm = grid_for(n, 256, 8192);
-#define FMISS(F) find_missing_kernel<F><<<gm, 256, 0, st>>>(t->keys, (const float4*)plane, t->nb, t->dim4, d_keys, n, (float4*)d_out, d_found, t->hits)
-        if (rows_only) FMISS(0); else if (counted) FMISS(3); else FMISS(1);
-#undef FMISS
-    } else if (counted) {  // sampled statistics pass: one key in flight per tile
-        const unsigned g1 = grid_for(n, 16, 1u << 22);
-#define FINDX(D4, NT) find_kernel<D4, 1, NT><<<g1, 256, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, t->hits)
-#define FINDX_D(NT) do { if (t->dim4 == 16) FINDX(16, NT); else if (t->dim4 == 32) FINDX(32, NT); else FINDX(0, NT); } while (0)
-        FINDX_D(20);
-#undef FINDX_D
-#undef FINDX
-    } else
-    if (t->dim4 == 16) { if (R == 8) FIND(16, 8); else if (R == 4) FIND(16, 4); else if (R == 2) FIND(16, 2); else FIND(16, 1); }
-    else if (t->dim4 == 32) { if (R == 4) FIND(32, 4); else if (R == 2) FIND(32, 2); else FIND(32, 1); }
-    else { if (R == 2) FIND(0, 2); else FIND(0, 1); }
-#undef FIND
-#undef FIND1
+    const int nt = path.nt >= 0 ? path.nt : t->find_nt >= 0 ? (t->find_nt & 7)
+                 : ((uint64_t)n * t->dim * 4 <= kCachedOutputBytes && !outputs_rotate(t, d_out, (uint64_t)n * t->dim * 4) ? 4 : 0);
+    if (path.kind == FindPath::Missing || path.kind == FindPath::CountedMissing) {
+        with_value<3, 1>(path.kind == FindPath::CountedMissing ? 3 : 1, [&](auto flags) {
+            find_missing_kernel<flags><<<grid_for(n, 256, 8192), 256, 0, st>>>(t->keys, (const float4*)plane, t->nb, t->dim4, d_keys, n, (float4*)d_out, d_found, t->hits);
+        });
+    } else with_row_shape(t->dim4, [&](auto d4) {
+        constexpr int D4 = d4;
+        int R = t->find_rounds > 0 ? t->find_rounds : RowShape<D4>::rows_per_tile;
+        if (D4 != 16 && R > 4) R = 4;
+        if (D4 != 16 && D4 != 32 && R > 2) R = 2;
+        R = R >= 8 ? 8 : R >= 4 ? 4 : R >= 2 ? 2 : 1;
+        const unsigned grid = grid_for(n, (fblock / 64u) * 4u * (unsigned)R, t->find_grid_cap > 0 ? (unsigned)t->find_grid_cap : (1u << 22));
+        auto find = [&](auto rr, auto ntc, unsigned grid_x, unsigned block, uint32_t* hits = nullptr, int64_t* slots_out = nullptr, int64_t tag = 0) {
+            find_kernel<D4, rr, ntc><<<grid_x, block, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, hits, slots_out, tag);
+        };
+        if (path.kind == FindPath::SkipPadding) {   // owner pass of a padded sharded exchange: EMPTY positions get neither a row nor a found byte (nobody reads them)
+            with_value<2, 1>(R >= 2 ? 2 : 1, [&](auto rr) { with_value<132, 128>(nt & 4 ? 132 : 128, [&](auto ntc) { find(rr, ntc, grid, 256); }); });
+        } else if (path.kind == FindPath::Located) {   // located find: the plain kernel + one 8-byte store per key
+            // cache policy of `out`: this is the forward of a TRAINING step — the apply that follows sweeps the Infinity Cache before the next
+            // forward, so keeping the dense output cached buys nothing and streaming stores win (136.9 -> 132.5 us per find + Adagrad step)
+            const bool cached_out = t->find_nt >= 0 && (t->find_nt & 4);
+            with_value<2, 1>(R >= 2 ? 2 : 1, [&](auto rr) { with_value<68, 64>(cached_out ? 68 : 64, [&](auto ntc) { find(rr, ntc, grid, fblock, nullptr, path.slots_out, handle_tag_of(t)); }); });
+        } else if (path.kind == FindPath::Counted) {   // sampled statistics pass: one key in flight per tile
+            find(std::integral_constant<int, 1>{}, std::integral_constant<int, 20>{}, grid_for(n, 16, 1u << 22), 256, t->hits);
+        } else {
+            auto plain = [&](auto rr) { with_value<0, 1, 2, 3, 4, 5, 6, 7>(nt, [&](auto ntc) {
+                if (path.kind == FindPath::Unordered)   // (any block order, at find_kernel's launch bound; the launch takes the parameters' exact types)
+                    hipExtLaunchKernelGGL((find_kernel<D4, rr, ntc>), dim3(grid), dim3(256), 0, st, nullptr, nullptr, hipExtAnyOrderLaunch, (const int64_t*)t->keys,
+                                          (const f32x4*)plane, t->nb, d_keys, (uint64_t)n, (f32x4*)d_out, d_found, miss_value, t->dim4, (uint32_t*)nullptr, (int64_t*)nullptr, (int64_t)0);
+                else find(rr, ntc, grid, fblock);
+            }); };
+            if constexpr (D4 == 16) with_value<8, 4, 2, 1>(R, plain);
+            else if constexpr (D4 == 32) with_value<4, 2, 1>(R, plain);
+            else with_value<2, 1>(R, plain);
+        }
+    });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -760,9 +756,9 @@ int mee_find_ex(const mee_table* t, const int64_t* d_keys, size_t n, float* d_ou
     if (flags == MEE_FIND_DEFAULT) return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream);
     // the kernel's policy bits: 1 = streaming row loads, 2 = streaming bucket loads, 4 = cached stores of the dense output
     const bool cached_out = (flags & MEE_FIND_CACHED_STORES) ||
-                            (!(flags & MEE_FIND_STREAM_STORES) && (uint64_t)n * t->dim * 4 <= (128ull << 20) && !outputs_rotate(t, d_out, (uint64_t)n * t->dim * 4));
+                            (!(flags & MEE_FIND_STREAM_STORES) && (uint64_t)n * t->dim * 4 <= kCachedOutputBytes && !outputs_rotate(t, d_out, (uint64_t)n * t->dim * 4));
     const int nt = (flags & MEE_FIND_STREAM_ROWS ? 1 : 0) | (flags & MEE_FIND_STREAM_BUCKETS ? 2 : 0) | (cached_out ? 4 : 0);
-    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, false, false, false, nullptr, false, false, nt);
+    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {FindPath::Plain, nullptr, nt});
 }
 
 }  // extern "C"
@@ -771,7 +767,7 @@ namespace mee {
 // they get neither a default row nor a found byte
 int find_skip_padding(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream) {
     if (!t || (n && (!d_keys || !d_out || !d_found))) return fail(MEE_ERR_INVALID_ARG, "find_skip_padding: null argument");
-    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, false, false, false, nullptr, false, /*skip_padding=*/true);
+    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {FindPath::SkipPadding});
 }
 }  // namespace mee
 extern "C" {
@@ -779,7 +775,7 @@ extern "C" {
 int mee_find_located(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, int64_t* d_slots_out, void* stream) {
     MEE_RANGE("mee_find_located");
     if (!t || (n && (!d_keys || !d_out || !d_slots_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_located: null argument");
-    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, false, false, false, d_slots_out);
+    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {FindPath::Located, d_slots_out});
 }
 
 int mee_find_many(const mee_table* t, const mee_find_request* reqs, uint32_t count, void* stream) {
@@ -788,7 +784,7 @@ int mee_find_many(const mee_table* t, const mee_find_request* reqs, uint32_t cou
     if (count == 0) return MEE_OK;
     if (count > (uint32_t)kMaxFindRequests) return fail(MEE_ERR_INVALID_ARG, "mee_find_many: %u requests (at most %d per call)", count, kMaxFindRequests);
     FindMany m{};
-    const int R = t->dim4 == 16 ? 2 : 1;
+    const int R = with_row_shape(t->dim4, [](auto d4) { return RowShape<d4>::rows_per_tile; });
     uint64_t blocks = 0, out_bytes = 0;
     uint32_t used = 0;
     for (uint32_t q = 0; q < count; ++q) {
@@ -805,11 +801,10 @@ int mee_find_many(const mee_table* t, const mee_find_request* reqs, uint32_t cou
     m.first_block[used] = (uint32_t)blocks; m.count = used;
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
-    const bool cached_out = out_bytes <= (128ull << 20);   // same policy as mee_find, on the total output of the launch
-#define FM(D4, RR) do { if (cached_out) find_many_kernel<D4, RR, 4><<<(unsigned)blocks, 256, 0, st>>>(t->keys, (const f32x4*)t->values, t->nb, m, t->default_value, t->dim4); \
-                        else find_many_kernel<D4, RR, 0><<<(unsigned)blocks, 256, 0, st>>>(t->keys, (const f32x4*)t->values, t->nb, m, t->default_value, t->dim4); } while (0)
-    if (t->dim4 == 16) FM(16, 2); else if (t->dim4 == 32) FM(32, 1); else FM(0, 1);
-#undef FM
+    const bool cached_out = out_bytes <= kCachedOutputBytes;   // same policy as mee_find, on the total output of the launch
+    with_row_shape(t->dim4, [&](auto d4) { with_value<4, 0>(cached_out ? 4 : 0, [&](auto ntc) {
+        find_many_kernel<d4, RowShape<d4>::rows_per_tile, ntc><<<(unsigned)blocks, 256, 0, st>>>(t->keys, (const f32x4*)t->values, t->nb, m, t->default_value, t->dim4);
+    }); });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -817,20 +812,20 @@ int mee_find_many(const mee_table* t, const mee_find_request* reqs, uint32_t cou
 int mee_find_unordered(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream) {
     MEE_RANGE("mee_find_unordered");
     if (!t || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_unordered: null argument");
-    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, false, false, false, nullptr, /*unordered=*/true);
+    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {FindPath::Unordered});
 }
 
 int mee_find_missing(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream) {
     MEE_RANGE("mee_find_missing");
     if (!t || (n && (!d_keys || !d_out || !d_found))) return fail(MEE_ERR_INVALID_ARG, "mee_find_missing: null argument");
-    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, true);
+    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {FindPath::Missing});
 }
 
 int mee_find_counted(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, int missing_only, void* stream) {
     MEE_RANGE("mee_find_counted");
     if (!t || (n && (!d_keys || !d_out || !d_found))) return fail(MEE_ERR_INVALID_ARG, "mee_find_counted: null argument");
     if (!t->hits) return fail(MEE_ERR_UNSUPPORTED, "mee_find_counted: table was created without MEE_FLAG_TRACK_HITS");
-    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, missing_only != 0, true);
+    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {missing_only ? FindPath::CountedMissing : FindPath::Counted});
 }
 
 int mee_find_pooled(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, float* d_out,
@@ -841,12 +836,10 @@ int mee_find_pooled(const mee_table* t, const int64_t* d_keys, size_t n, const u
     if (n_bags == 0) return MEE_OK;
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
-    // n (the number of keys, a host value) only picks the launch shape: mostly short bags -> four bags per wave, long average -> one
-    const bool wave_per_bag = n / n_bags >= 12;
-#define POOLED(D4, U1, U4) do { if (wave_per_bag) find_pooled_kernel<D4, U1, 1><<<grid_for(n_bags, 4, 1u << 20), 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, t->default_value, t->dim4, mode == MEE_POOL_MEAN, nullptr, 1, nullptr, n); \
-                                else find_pooled_kernel<D4, U4, 4><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, t->default_value, t->dim4, mode == MEE_POOL_MEAN, nullptr, 1, nullptr, n); } while (0)
-    if (t->dim4 == 16) POOLED(16, 4, 2); else if (t->dim4 == 32) POOLED(32, 2, 1); else POOLED(0, 1, 1);
-#undef POOLED
+    with_pooled_shape(t->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
+        find_pooled_kernel<d4, u, bpw><<<grid, 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found,
+                                                             t->default_value, t->dim4, mode == MEE_POOL_MEAN, nullptr, 1, nullptr, n);
+    });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -859,12 +852,11 @@ int mee_find_pooled_weighted(const mee_table* t, const int64_t* d_keys, size_t n
     if (n_bags == 0) return MEE_OK;
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
-    const bool wave_per_bag = n / n_bags >= 12;   // the launch shapes of mee_find_pooled
-    const int64_t tag = handle_tag_of(t);          // located rows in the format of mee_find_located
-#define WPOOLED(D4, U1, U4) do { if (wave_per_bag) find_pooled_kernel<D4, U1, 1, false, true><<<grid_for(n_bags, 4, 1u << 20), 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, t->default_value, t->dim4, 0, nullptr, 1, d_located_out, n, d_weights, tag); \
-                                 else find_pooled_kernel<D4, U4, 4, false, true><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, t->default_value, t->dim4, 0, nullptr, 1, d_located_out, n, d_weights, tag); } while (0)
-    if (t->dim4 == 16) WPOOLED(16, 4, 2); else if (t->dim4 == 32) WPOOLED(32, 2, 1); else WPOOLED(0, 1, 1);
-#undef WPOOLED
+    const int64_t tag = handle_tag_of(t);   // located rows in the format of mee_find_located
+    with_pooled_shape(t->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
+        find_pooled_kernel<d4, u, bpw, false, true><<<grid, 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found,
+                                                                          t->default_value, t->dim4, 0, nullptr, 1, d_located_out, n, d_weights, tag);
+    });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -878,11 +870,10 @@ int mee_pooled_weighted_backward(const mee_table* t, const int64_t* d_keys, cons
     if (n_bags == 0) return MEE_OK;
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
-    const bool wave_per_bag = n / n_bags >= 12;
-#define WBWD(D4, U1, U4) do { if (wave_per_bag) pooled_weighted_backward_kernel<D4, U1, 1><<<grid_for(n_bags, 4, 1u << 20), 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, t->capacity, d_keys, d_located, handle_tag_of(t), d_bag_offsets, n_bags, d_weights, (const float4*)d_bag_grads, (float4*)d_grads_out, d_weight_grads_out, t->default_value, t->dim4, nullptr, 1, n); \
-                              else pooled_weighted_backward_kernel<D4, U4, 4><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, t->capacity, d_keys, d_located, handle_tag_of(t), d_bag_offsets, n_bags, d_weights, (const float4*)d_bag_grads, (float4*)d_grads_out, d_weight_grads_out, t->default_value, t->dim4, nullptr, 1, n); } while (0)
-    if (t->dim4 == 16) WBWD(16, 4, 2); else if (t->dim4 == 32) WBWD(32, 2, 1); else WBWD(0, 1, 1);
-#undef WBWD
+    with_pooled_shape(t->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
+        pooled_weighted_backward_kernel<d4, u, bpw><<<grid, 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, t->capacity, d_keys, d_located, handle_tag_of(t), d_bag_offsets,
+                                                                          n_bags, d_weights, (const float4*)d_bag_grads, (float4*)d_grads_out, d_weight_grads_out, t->default_value, t->dim4, nullptr, 1, n);
+    });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -906,11 +897,10 @@ int mee_group_find_pooled(mee_group* g, const int64_t* d_keys, size_t n, const u
     DeviceGuard guard(g->device);
     hipStream_t st = as_stream(stream);
     const uint64_t n_bags = (uint64_t)g->n_tables * bags_per_table;
-    const bool wave_per_bag = n / n_bags >= 12;
-#define GPOOLED(D4, U1, U4) do { if (wave_per_bag) find_pooled_kernel<D4, U1, 1, true><<<grid_for(n_bags, 4, 1u << 20), 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, mode == MEE_POOL_MEAN, g->d_desc, bags_per_table, d_located_out, n); \
-                                 else find_pooled_kernel<D4, U4, 4, true><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, mode == MEE_POOL_MEAN, g->d_desc, bags_per_table, d_located_out, n); } while (0)
-    if (g->dim4 == 16) GPOOLED(16, 4, 2); else if (g->dim4 == 32) GPOOLED(32, 2, 1); else GPOOLED(0, 1, 1);
-#undef GPOOLED
+    with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
+        find_pooled_kernel<d4, u, bpw, true><<<grid, 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4,
+                                                                   mode == MEE_POOL_MEAN, g->d_desc, bags_per_table, d_located_out, n);
+    });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -925,11 +915,10 @@ int mee_group_find_pooled_weighted(mee_group* g, const int64_t* d_keys, size_t n
     DeviceGuard guard(g->device);
     hipStream_t st = as_stream(stream);
     const uint64_t n_bags = (uint64_t)g->n_tables * bags_per_table;
-    const bool wave_per_bag = n / n_bags >= 12;
-#define GWPOOLED(D4, U1, U4) do { if (wave_per_bag) find_pooled_kernel<D4, U1, 1, true, true><<<grid_for(n_bags, 4, 1u << 20), 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, 0, g->d_desc, bags_per_table, d_located_out, n, d_weights); \
-                                  else find_pooled_kernel<D4, U4, 4, true, true><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, 0, g->d_desc, bags_per_table, d_located_out, n, d_weights); } while (0)
-    if (g->dim4 == 16) GWPOOLED(16, 4, 2); else if (g->dim4 == 32) GWPOOLED(32, 2, 1); else GWPOOLED(0, 1, 1);
-#undef GWPOOLED
+    with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
+        find_pooled_kernel<d4, u, bpw, true, true><<<grid, 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4,
+                                                                         0, g->d_desc, bags_per_table, d_located_out, n, d_weights);
+    });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -945,11 +934,10 @@ int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, cons
     DeviceGuard guard(g->device);
     hipStream_t st = as_stream(stream);
     const uint64_t n_bags = (uint64_t)g->n_tables * bags_per_table;
-    const bool wave_per_bag = n / n_bags >= 12;
-#define GWBWD(D4, U1, U4) do { if (wave_per_bag) pooled_weighted_backward_kernel<D4, U1, 1, true><<<grid_for(n_bags, 4, 1u << 20), 256, 0, st>>>(nullptr, nullptr, 0, 0, d_keys, d_located, 0, d_bag_offsets, n_bags, d_weights, (const float4*)d_bag_grads, (float4*)d_grads_out, d_weight_grads_out, 0.f, g->dim4, g->d_desc, bags_per_table, n); \
-                               else pooled_weighted_backward_kernel<D4, U4, 4, true><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>(nullptr, nullptr, 0, 0, d_keys, d_located, 0, d_bag_offsets, n_bags, d_weights, (const float4*)d_bag_grads, (float4*)d_grads_out, d_weight_grads_out, 0.f, g->dim4, g->d_desc, bags_per_table, n); } while (0)
-    if (g->dim4 == 16) GWBWD(16, 4, 2); else if (g->dim4 == 32) GWBWD(32, 2, 1); else GWBWD(0, 1, 1);
-#undef GWBWD
+    with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
+        pooled_weighted_backward_kernel<d4, u, bpw, true><<<grid, 256, 0, st>>>(nullptr, nullptr, 0, 0, d_keys, d_located, 0, d_bag_offsets, n_bags, d_weights,
+                                                                                (const float4*)d_bag_grads, (float4*)d_grads_out, d_weight_grads_out, 0.f, g->dim4, g->d_desc, bags_per_table, n);
+    });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -970,18 +958,18 @@ int mee_find_located_prepare(mee_table* t, const int64_t* d_keys, size_t n, floa
     const uint32_t nbk_hash = bucket_count_for(t, n, st, &apply_grid, &nbk, &apply_full);
     uint32_t part_blocks, per_block;
     part_geometry((uint32_t)n, kFindPrepareThreads, part_blocks, per_block);
-    const int R = t->dim4 == 16 ? kFindPrepareR : t->dim4 == 32 ? 2 : 1;
-    const unsigned find_cap = t->prepare_debug >> 8;
-    const unsigned find_blocks = grid_for(n, (kFindPrepareThreads / 64) * 4u * (unsigned)R, find_cap ? find_cap : 1u << 22);
     const bool separate = t->prepare_debug & 1;
     if (separate) part_blocks = 0;
     const bool cached_out = t->find_nt >= 0 && (t->find_nt & 4);
-#define FINDLP1(D4, RR, NT) find_prepare_kernel<D4, RR, NT><<<part_blocks + find_blocks, kFindPrepareThreads, sizeof(PartHot) + nbk * 4, st>>>(t->keys, (const f32x4*)t->values, t->nb, d_keys, n, (f32x4*)d_out, d_found, \
-        t->default_value, t->dim4, d_slots_out, handle_tag_of(t), part_blocks, nbk_hash, nbk, per_block, t->bk, &t->ctr->status, t->op, t->bk.xcd_split)
-#define FINDLP(D4, RR) do { if (cached_out) FINDLP1(D4, RR, 68); else FINDLP1(D4, RR, 64); } while (0)
-    if (t->dim4 == 16) FINDLP(16, kFindPrepareR); else if (t->dim4 == 32) FINDLP(32, 2); else FINDLP(0, 1);
-#undef FINDLP
-#undef FINDLP1
+    with_row_shape(t->dim4, [&](auto d4) {
+        constexpr int R = d4 == 16 ? kFindPrepareR : d4 == 32 ? 2 : 1;
+        const unsigned find_cap = t->prepare_debug >> 8;
+        const unsigned find_blocks = grid_for(n, (kFindPrepareThreads / 64) * 4u * (unsigned)R, find_cap ? find_cap : 1u << 22);
+        with_value<68, 64>(cached_out ? 68 : 64, [&](auto ntc) {
+            find_prepare_kernel<d4, R, ntc><<<part_blocks + find_blocks, kFindPrepareThreads, sizeof(PartHot) + nbk * 4, st>>>(t->keys, (const f32x4*)t->values, t->nb, d_keys, n,
+                (f32x4*)d_out, d_found, t->default_value, t->dim4, d_slots_out, handle_tag_of(t), part_blocks, nbk_hash, nbk, per_block, t->bk, &t->ctr->status, t->op, t->bk.xcd_split);
+        });
+    });
     MEE_HIP(hipGetLastError());
     if (separate) { if (int rc = bucket_apply_prepare(t, d_keys, (uint32_t)n, st)) return rc; }
     else { t->part_blocks = part_blocks; t->part_per_block = per_block; t->part_nbk = nbk; t->part_nbk_hash = nbk_hash; t->part_grid = apply_grid; t->part_full = apply_full; }

@@ -289,19 +289,14 @@ int mee_group_destroy(mee_group* g) {
 
 static int launch_find_grouped(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, float* d_out, uint8_t* d_found,
                                hipStream_t st) {
-    const bool stream_out = (uint64_t)n * g->dim * 4 > (128ull << 20);   // find_kernel's store policy
+    const bool stream_out = (uint64_t)n * g->dim * 4 > kCachedOutputBytes;   // find_kernel's store policy
     // every block starts by staging the offsets in LDS (a global round trip + a barrier): blocks must live long enough to
     // amortise it, so the grid is capped and strides (measured: 8192 blocks best from 200K to 1M positions)
     const unsigned grid_cap = 8192;
-#define GROUPED(D4, RR, PER)                                                                                                          \
-    do {                                                                                                                              \
-        if (stream_out) find_grouped_kernel<D4, RR, true><<<grid_for(n, PER, grid_cap), 256, 0, st>>>(g->d_desc, g->n_tables, d_offsets, d_keys, n, (float4*)d_out, d_found, g->dim4); \
-        else find_grouped_kernel<D4, RR, false><<<grid_for(n, PER, grid_cap), 256, 0, st>>>(g->d_desc, g->n_tables, d_offsets, d_keys, n, (float4*)d_out, d_found, g->dim4);       \
-    } while (0)
-    if (g->dim4 == 16) GROUPED(16, 2, 32);
-    else if (g->dim4 == 32) GROUPED(32, 1, 16);
-    else GROUPED(0, 1, 16);
-#undef GROUPED
+    with_row_shape(g->dim4, [&](auto d4) { with_flag(stream_out, [&](auto so) {
+        constexpr int R = RowShape<d4>::rows_per_tile;   // (a block: 16 tiles of R keys in flight)
+        find_grouped_kernel<d4, R, so><<<grid_for(n, 16 * R, grid_cap), 256, 0, st>>>(g->d_desc, g->n_tables, d_offsets, d_keys, n, (float4*)d_out, d_found, g->dim4);
+    }); });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }

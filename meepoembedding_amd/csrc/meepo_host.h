@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdarg>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/meepo_embedding.h"
 
@@ -102,6 +103,29 @@ inline unsigned grid_for(size_t work_items, unsigned per_block, unsigned cap) {
     if (g > cap) g = cap;
     return (unsigned)g;
 }
+
+// A dense output up to this size stays in the Infinity Cache: cached stores by default, streaming stores beyond (each site adds its own conditions)
+constexpr uint64_t kCachedOutputBytes = 128ull << 20;
+
+// ---- compile-time dispatch: a run-time choice becomes a constant for a generic lambda.  The row shapes: every row kernel has one instance for dim4 16
+// (dim 64), one for dim4 32 (dim 128), and DIM4 = 0 for every other width, which loops at run time; this is the only place that says which widths have their own.
+template <class F> decltype(auto) with_row_shape(uint32_t dim4, F&& f) {
+    if (dim4 == 16) return f(std::integral_constant<int, 16>{});
+    if (dim4 == 32) return f(std::integral_constant<int, 32>{});
+    return f(std::integral_constant<int, 0>{});
+}
+template <class F> void with_flag(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+// only the listed values are instantiated; the last one also takes any value that matches none (the `default:` of a switch)
+template <int V, int... Rest, class F> void with_value(int v, F&& f) {
+    if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, V>{});
+    else if (v == V) f(std::integral_constant<int, V>{});
+    else with_value<Rest...>(v, f);
+}
+template <int DIM4> struct RowShape {   // what the row kernels' launches share per row shape
+    static constexpr int rows_per_tile = DIM4 == 16 ? 2 : 1;                     // keys in flight per 16-lane tile (R): the plain finds' default
+    static constexpr int pooled_unroll_1 = DIM4 == 16 ? 4 : DIM4 == 32 ? 2 : 1;   // keys in flight per tile of a pooled lookup, one bag per wave
+    static constexpr int pooled_unroll_4 = DIM4 == 16 ? 2 : 1;                    // ... four bags per wave
+};
 
 }  // namespace mee
 

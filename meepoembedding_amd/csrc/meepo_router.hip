@@ -389,15 +389,9 @@ static int partition_common(mee_router* r, const int64_t* d_keys, size_t n, int6
     DeviceGuard g(r->device);
     hipStream_t st = (hipStream_t)stream;
     const uint32_t nblk = (uint32_t)((n + kPartBlock - 1) / kPartBlock);
-    if (nblk) {
-        if (skip_pad) part_count_kernel<true><<<nblk, kPartBlock, 0, st>>>(d_keys, (uint32_t)n, r->n_shards, r->blockcnt);
-        else part_count_kernel<false><<<nblk, kPartBlock, 0, st>>>(d_keys, (uint32_t)n, r->n_shards, r->blockcnt);
-    }
+    if (nblk) with_flag(skip_pad, [&](auto sp) { part_count_kernel<sp><<<nblk, kPartBlock, 0, st>>>(d_keys, (uint32_t)n, r->n_shards, r->blockcnt); });
     part_scan_kernel<<<1, 1024, 0, st>>>(r->blockcnt, nblk, r->n_shards, r->base, d_counts);
-    if (nblk) {
-        if (skip_pad) part_scatter_kernel<true><<<nblk, kPartBlock, 0, st>>>(d_keys, (uint32_t)n, r->n_shards, r->blockcnt, r->base, d_send_keys, d_perm);
-        else part_scatter_kernel<false><<<nblk, kPartBlock, 0, st>>>(d_keys, (uint32_t)n, r->n_shards, r->blockcnt, r->base, d_send_keys, d_perm);
-    }
+    if (nblk) with_flag(skip_pad, [&](auto sp) { part_scatter_kernel<sp><<<nblk, kPartBlock, 0, st>>>(d_keys, (uint32_t)n, r->n_shards, r->blockcnt, r->base, d_send_keys, d_perm); });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -576,10 +570,10 @@ int mee_p2p_find(mee_p2p* c, const mee_table* t, void* stream) {
     DeviceGuard g(c->device);
     const dim3 grid(grid_for(c->cap, 32, 1u << 16), c->n_shards);
     hipStream_t st = (hipStream_t)stream;
-#define P2PFIND(D4, RR) p2p_find_kernel<D4, RR><<<grid, 256, 0, st>>>(v.keys, (const float4*)v.values, v.nb, v.dim4, v.default_value, c->inbox_keys, \
-                                                                      c->inbox_dst, c->inbox_cnt, p2p_peers(c), c->cap)
-    if (v.dim4 == 16) P2PFIND(16, 2); else if (v.dim4 == 32) P2PFIND(32, 1); else P2PFIND(0, 1);
-#undef P2PFIND
+    with_row_shape(v.dim4, [&](auto d4) {
+        p2p_find_kernel<d4, RowShape<d4>::rows_per_tile><<<grid, 256, 0, st>>>(v.keys, (const float4*)v.values, v.nb, v.dim4, v.default_value, c->inbox_keys,
+                                                                               c->inbox_dst, c->inbox_cnt, p2p_peers(c), c->cap);
+    });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }

@@ -660,10 +660,10 @@ static int upsert_common(mee_table* t, float* plane, const int64_t* d_keys, cons
         next_epoch(t, st);
         long long* slotof = t->g.sres;   // S >= 2 * max_batch entries: lent as the per-position slot list (as mee_remove does)
         const unsigned gd = grid_for(n, 32, 1u << 16);
-#define DIRECT(D4) insert_direct_kernel<D4><<<gd, 256, 0, st>>>(t->keys, (float4*)plane, (float4*)t->s1, (float4*)t->s2, t->nb, t->dim4, d_keys, (const float4*)d_values, \
-                                                               nn, skip, t->bs.fmask, slotof, t->bs.hidx, t->optimizer, t->init_acc, t->ctr, t->hits, t->epoch)
-        if (t->dim4 == 16) DIRECT(16); else if (t->dim4 == 32) DIRECT(32); else DIRECT(0);
-#undef DIRECT
+        with_row_shape(t->dim4, [&](auto d4) {
+            insert_direct_kernel<d4><<<gd, 256, 0, st>>>(t->keys, (float4*)plane, (float4*)t->s1, (float4*)t->s2, t->nb, t->dim4, d_keys, (const float4*)d_values,
+                                                         nn, skip, t->bs.fmask, slotof, t->bs.hidx, t->optimizer, t->init_acc, t->ctr, t->hits, t->epoch);
+        });
         group_last_kernel<<<gl, 256, 0, st>>>(d_keys, nn, t->g, t->bs, t->ctr, t->bs.fmask, t->epoch, &t->ctr->election);
         insert_join_kernel<<<grid_for(n, 256, 2048), 256, 0, st>>>(d_keys, nn, t->bs.fmask, slotof, t->g, t->bs.hidx, t->ctr, t->epoch);
         insert_settle_kernel<<<grid_for(n, 16, 2048), 256, 0, st>>>((float4*)plane, t->dim4, (const float4*)d_values, nn, slotof, t->bs.hidx, t->g, t->ctr, t->epoch);
@@ -726,7 +726,7 @@ static int find_or_insert_common(mee_table* t, const int64_t* d_keys, size_t n, 
     // yields the "present before the call" mask; pass 2 runs the insert machinery over the missing positions only.
     uint8_t* fmask = d_found ? d_found : t->bs.fmask;
     if (own_find_pass)
-        if (int rc = find_plane(t, t->values, t->default_value, d_keys, n, d_out, fmask, stream, false, false, false, d_slots_out)) return rc;
+        if (int rc = find_plane(t, t->values, t->default_value, d_keys, n, d_out, fmask, stream, {d_slots_out ? FindPath::Located : FindPath::Plain, d_slots_out})) return rc;
     // pass 2: every position the mask leaves missing claims its key (or meets the occurrence that did) and writes the key's initial row
     // into the table (creator) and into d_out (everybody): nothing is left for a third pass
     ensure_direct_kernel<64><<<grid_for(n, 256, 8192), 256, 0, st>>>(t->keys, (float4*)t->values, (float4*)t->s1, (float4*)t->s2, t->nb, t->dim4,

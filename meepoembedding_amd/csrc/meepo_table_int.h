@@ -201,8 +201,11 @@ void zero_words(void* p, size_t bytes, hipStream_t st);            // zeroing of
 void fill_keys(int64_t* p, uint64_t n, int64_t v, hipStream_t st); // a key plane set to one value
 int check_batch(mee_table* t, size_t n, const char* op, void* stream, bool needs_group_table = true, bool drop_pending = true);
 // (meepo_find.hip)
-int find_plane(const mee_table* t, const float* plane, float miss_value, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream,
-               bool missing_only = false, bool counted = false, bool rows_only = false, int64_t* d_slots_out = nullptr, bool unordered = false,
-               bool skip_padding = false, int nt_call = -1);
+struct FindPath {   // which lookup find_plane runs
+    enum Kind { Plain, Located, Missing, Counted, CountedMissing, Unordered, SkipPadding } kind = Plain;
+    int64_t* slots_out = nullptr;   // Located: one slot handle per key
+    int nt = -1;                    // Plain: this call's cache policy (mee_find_ex); -1: the table's
+};
+int find_plane(const mee_table* t, const float* plane, float miss_value, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream, FindPath path = {});
 
 }  // namespace mee
