@@ -23,6 +23,8 @@ print("stored keys:", table.size(), "| new in this batch:", int((existed == 0).s
 
 out, found = table.find(torch.cat([keys[:5], torch.tensor([42], device=dev)]))   # inference lookup: absent -> default row
 print("found mask:", found.tolist())
+out16, _ = table.find(keys[:5], out_dtype=torch.bfloat16)   # bf16 rows for a bf16 model: rounded once by the lookup, no cast behind it
+print("bf16 rows equal the cast fp32 rows:", torch.equal(out16, out[:5].to(torch.bfloat16)))
 table.remove(keys[:1000])
 ek, ev = table.export()                                    # checkpoint: int64 keys[N], fp32 values[N, 64]
 print("after remove:", table.size(), "exported", tuple(ev.shape))

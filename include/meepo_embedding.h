@@ -323,6 +323,42 @@ int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, cons
                                        size_t bags_per_table, const float* d_weights, const float* d_bag_grads, float* d_grads_out,
                                        float* d_weight_grads_out, void* stream);
 
+/* ---- typed output: the lookups above with fp32 OR bf16 result rows (SPEC.md §3 "Output type") --------------------------------
+ * The models these tables feed run in bf16; a lookup that writes bf16 itself saves the cast in front of the first dense layer and half
+ * of its own store traffic.  Tables, optimizer state and every accumulation stay fp32: with out_dtype = MEE_DTYPE_BF16 the result is, by
+ * definition, the fp32 result of the same operator with every element rounded ONCE to bfloat16, round to nearest even
+ *     u = bits(x);  bf16_bits(x) = (u + 0x7FFF + ((u >> 16) & 1)) >> 16      (x not a NaN; a NaN gives a NaN)
+ * — ±0, ±inf and denormals follow from the formula (denormals are not flushed, a finite value beyond the largest bf16 becomes inf);
+ * for a pooled lookup it is the FINISHED bag row that is rounded, no intermediate.  d_found, slot handles, status bits, the partition a
+ * *_prepare form leaves behind and (find_or_insert) the table afterwards are those of the fp32 call.  With MEE_DTYPE_F32 every form below
+ * IS the operator it is named after, bit for bit.  d_out: [rows, dim] of the chosen type; a bf16 buffer must be 8-byte aligned, anything
+ * else — like an unknown out_dtype — is MEE_ERR_INVALID_ARG.  The "find_rounds" knob does not apply to bf16 lookups.
+ *   mee_find_as                              flags as mee_find_ex (MEE_FIND_DEFAULT: the library's own choice, as mee_find)
+ *   mee_find_pooled_as                       d_weights nullable (non-null: mee_find_pooled_weighted, MEE_POOL_SUM only); d_located_out
+ *                                            (nullable) is the weighted form's output
+ *   mee_group_find_pooled_as                 d_weights nullable (non-null: mee_group_find_pooled_weighted)
+ * No typed form exists for find_missing / find_counted / find_plane / find_many / find_unordered / find_or_insert_admit /
+ * find_or_insert_missing, the mee_sharded_* and mee_p2p_* lookups and mee_export: they return fp32.  Gradients handed to mee_apply_* are fp32. */
+enum { MEE_DTYPE_F32 = 0, MEE_DTYPE_BF16 = 1 };
+int mee_find_as(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, uint32_t flags, void* stream);
+int mee_find_located_as(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out,
+                        void* stream);
+int mee_find_located_prepare_as(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out,
+                                void* stream);
+int mee_find_or_insert_as(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, void* stream);
+int mee_find_or_insert_located_as(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
+                                  int64_t* d_slots_out, void* stream);
+int mee_find_or_insert_located_prepare_as(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
+                                          int64_t* d_slots_out, void* stream);
+int mee_find_pooled_as(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const float* d_weights,
+                       void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream);
+int mee_find_grouped_as(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
+                        void* stream);
+int mee_group_find_or_insert_as(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype,
+                                uint8_t* d_found, void* stream);
+int mee_group_find_pooled_as(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                             const float* d_weights, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream);
+
 /* ---- sparse optimizers (north_star "sparse-optimizer (Adagrad/Adam) scatter-update"; SPEC.md §4) -------- */
 int mee_apply_adagrad(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, float lr, float eps,
                       void* stream);

@@ -86,6 +86,19 @@ public:
         check(prepare ? mee_find_located_prepare(t_, d_keys, n, d_out, d_found, d_slots_out, stream) : mee_find_located(t_, d_keys, n, d_out, d_found, d_slots_out, stream));
     }
     void find_or_insert_located_prepare(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, int64_t* d_slots_out, void* stream = nullptr) { check(mee_find_or_insert_located_prepare(t_, d_keys, n, d_out, d_found, d_slots_out, stream)); }
+    // the same lookups with fp32 or bf16 result rows (out_dtype = MEE_DTYPE_F32 | MEE_DTYPE_BF16: the fp32 result rounded once to bf16; d_out 8-byte aligned)
+    void find_as(const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found = nullptr, uint32_t flags = MEE_FIND_DEFAULT, void* stream = nullptr) const { check(mee_find_as(t_, d_keys, n, d_out, out_dtype, d_found, flags, stream)); }
+    void find_located_as(const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out, bool prepare = false, void* stream = nullptr) {
+        check(prepare ? mee_find_located_prepare_as(t_, d_keys, n, d_out, out_dtype, d_found, d_slots_out, stream) : mee_find_located_as(t_, d_keys, n, d_out, out_dtype, d_found, d_slots_out, stream));
+    }
+    void find_or_insert_as(const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_find_or_insert_as(t_, d_keys, n, d_out, out_dtype, d_found, stream)); }
+    void find_or_insert_located_as(const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out, bool prepare = false, void* stream = nullptr) {
+        check(prepare ? mee_find_or_insert_located_prepare_as(t_, d_keys, n, d_out, out_dtype, d_found, d_slots_out, stream) : mee_find_or_insert_located_as(t_, d_keys, n, d_out, out_dtype, d_found, d_slots_out, stream));
+    }
+    // d_weights nullable (non-null: the weighted sum, whose d_located_out receives mee_find_located handles)
+    void find_pooled_as(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const float* d_weights, void* d_out, uint32_t out_dtype, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, int mode = MEE_POOL_SUM, void* stream = nullptr) const {
+        check(mee_find_pooled_as(t_, d_keys, n, d_bag_offsets, n_bags, d_weights, d_out, out_dtype, d_found, d_located_out, mode, stream));
+    }
     void apply_adagrad_located(const int64_t* d_keys, const int64_t* d_slots, const float* d_grads, size_t n, float lr, float eps = 1e-10f, void* stream = nullptr) { check(mee_apply_adagrad_located(t_, d_keys, d_slots, d_grads, n, lr, eps, stream)); }
     void apply_adam_located(const int64_t* d_keys, const int64_t* d_slots, const float* d_grads, size_t n, float lr, uint64_t step, float beta1 = 0.9f, float beta2 = 0.999f, float eps = 1e-8f, void* stream = nullptr) {
         check(mee_apply_adam_located(t_, d_keys, d_slots, d_grads, n, lr, beta1, beta2, eps, step, stream));
@@ -148,6 +161,12 @@ public:
     // segment j = d_keys[d_offsets[j] .. d_offsets[j+1]); d_offsets: n_tables + 1 values in DEVICE memory; n = total positions
     void find(const int64_t* d_keys, const uint64_t* d_offsets, size_t n, float* d_out, uint8_t* d_found, void* stream = nullptr) {
         check(mee_find_grouped(g_, d_keys, d_offsets, n, d_out, d_found, stream));
+    }
+    // the grouped lookups with fp32 or bf16 result rows (MEE_DTYPE_*): mee_find_grouped_as / mee_group_find_or_insert_as / mee_group_find_pooled_as
+    void find_as(const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, void* stream = nullptr) { check(mee_find_grouped_as(g_, d_keys, d_offsets, n, d_out, out_dtype, d_found, stream)); }
+    void find_or_insert_as(const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, void* stream = nullptr) { check(mee_group_find_or_insert_as(g_, d_keys, d_offsets, n, d_out, out_dtype, d_found, stream)); }
+    void find_pooled_as(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights, void* d_out, uint32_t out_dtype, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, int mode = MEE_POOL_SUM, void* stream = nullptr) {
+        check(mee_group_find_pooled_as(g_, d_keys, n, d_bag_offsets, bags_per_table, d_weights, d_out, out_dtype, d_found, d_located_out, mode, stream));
     }
     void set_tuning(const char* name, int value) { check(mee_group_set_tuning(g_, name, value)); }   // knobs of the group's own apply; never change results
     void apply_adagrad(const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr, float eps = 1e-10f, void* stream = nullptr) {

@@ -23,6 +23,7 @@ STATUS_TABLE_FULL, STATUS_RESERVED_KEY, STATUS_STALE_HANDLE, STATUS_INTERNAL = 1
 FIND_DEFAULT, FIND_STREAM_STORES, FIND_CACHED_STORES, FIND_STREAM_ROWS, FIND_STREAM_BUCKETS = 0, 1, 2, 4, 8   # mee_find_ex flags
 HANDLE_SLOT_MASK = (1 << 40) - 1   # a located-find handle: bits 0..39 the slot (as mee_locate reports it), bits 40..61 the table's layout epoch
 MEM_HBM, MEM_HOST_PINNED = 0, 1
+DTYPE_F32, DTYPE_BF16 = 0, 1   # MEE_DTYPE_*: the row type of a typed-output lookup (mee_*_as)
 FLAG_TRACK_HITS, FLAG_ADMISSION = 1, 2
 ABI_VERSION = 2   # MEE_ABI_VERSION of include/meepo_embedding.h this loader was written against
 EMPTY_KEY = -(1 << 63)
@@ -83,6 +84,17 @@ PROTOTYPES = {
     "mee_set_tuning": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "mee_find": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "mee_find_ex": (C.c_int, [_vp, _vp, _sz, _vp, _vp, C.c_uint32, _vp]),
+    # typed output (fp32 | bf16 rows): d_out is followed by out_dtype
+    "mee_find_as": (C.c_int, [_vp, _vp, _sz, _vp, _u32, _vp, _u32, _vp]),
+    "mee_find_located_as": (C.c_int, [_vp, _vp, _sz, _vp, _u32, _vp, _vp, _vp]),
+    "mee_find_located_prepare_as": (C.c_int, [_vp, _vp, _sz, _vp, _u32, _vp, _vp, _vp]),
+    "mee_find_or_insert_as": (C.c_int, [_vp, _vp, _sz, _vp, _u32, _vp, _vp]),
+    "mee_find_or_insert_located_as": (C.c_int, [_vp, _vp, _sz, _vp, _u32, _vp, _vp, _vp]),
+    "mee_find_or_insert_located_prepare_as": (C.c_int, [_vp, _vp, _sz, _vp, _u32, _vp, _vp, _vp]),
+    "mee_find_pooled_as": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _u32, _vp, _vp, C.c_int, _vp]),
+    "mee_find_grouped_as": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _u32, _vp, _vp]),
+    "mee_group_find_or_insert_as": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _u32, _vp, _vp]),
+    "mee_group_find_pooled_as": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _u32, _vp, _vp, C.c_int, _vp]),
     "mee_find_missing": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "mee_find_counted": (C.c_int, [_vp, _vp, _sz, _vp, _vp, C.c_int, _vp]),
     "mee_hits_scan": (C.c_int, [_vp, _u32, _u32, C.c_int, _vp, _sz, C.POINTER(_sz), _vp]),

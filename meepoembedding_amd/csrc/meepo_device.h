@@ -113,6 +113,32 @@ __device__ __forceinline__ int64_t tile_locate(int64_t* __restrict__ tkeys, uint
     return slot;
 }
 
+// ---- bf16 output of the lookups (SPEC.md §3 "Output type") ------------------------------------------------------------------
+// A lane that holds a float4 of a row stores it as 4 bf16 = 8 bytes; a row of dim bf16 is dim4 such 8-byte groups, so group g of
+// output row i sits at index i * dim4 + g of a u32x2 array — the SAME index the fp32 kernels use on their f32x4 array.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+// two fp32 -> two bfloat16 in one word, round to nearest even: plain casts, which gfx950 does with its packed convert (v_cvt_pk_bf16_f32).  It agrees
+// with the integer rule of the spec on every finite value, denormals included (HIP kernels run with fp32 denormals on), sends a finite value beyond
+// the largest bf16 to inf and a NaN to a NaN: tests/test_bf16_out.py checks exactly these on the device.  (The integer rule written out costs ~30
+// VALU instructions per float4 in the wave's dependent tail — +0.4 us on a latency-bound dim-16 lookup — and a __builtin_convertvector of float2
+// pairs made two pooled instances spill 32 B: profiles/bf16_out.md, profiles/bf16_out_resource_usage.txt.)
+__device__ __forceinline__ uint32_t bf16x2_of(float a, float b) {
+    return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)a) | ((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)b) << 16);
+}
+__device__ __forceinline__ u32x2 bf16x4_of(float a, float b, float c, float d) {
+    u32x2 p;
+    p.x = bf16x2_of(a, b);
+    p.y = bf16x2_of(c, d);
+    return p;
+}
+// the store of one such group; CACHED = false: a streaming (non-temporal) store, as the fp32 kernels use for outputs nothing re-reads from cache
+template <bool CACHED, class V4>
+__device__ __forceinline__ void store_bf16x4(void* out, uint64_t idx, const V4& v) {
+    const u32x2 p = bf16x4_of(v.x, v.y, v.z, v.w);
+    if constexpr (CACHED) reinterpret_cast<u32x2*>(out)[idx] = p;
+    else __builtin_nontemporal_store(p, reinterpret_cast<u32x2*>(out) + idx);
+}
+
 // SPEC.md §3 "Initial row", four consecutive elements starting at j0
 __device__ __forceinline__ float4 initial_row4(int64_t key, uint32_t j0, uint32_t initializer, float init_scale,
                                                uint64_t init_seed, float default_value) {

@@ -16,6 +16,7 @@ namespace mee {
 // ---- find (SPEC.md §3) — the headline kernel --------------------------------------------------------------
 // One tile per key, R keys in flight per tile: the R bucket lines are requested back to back, then the R rows.
 // DIM4 = dim/4 when it is a multiple of 16 (each lane moves DIM4/16 float4 per row), 0 = any dim at run time.
+// NT & 256: `out` is a bf16 array (SPEC.md §3 "Output type") — the lane's float4 leaves as 4 bf16 in one 8-byte store (store_bf16x4); nothing else differs.
 
 // the find of n positions by `n_waves` waves of which this is wave `wave` (each wave step takes 4R consecutive positions)
 template <int DIM4, int R, int NT>
@@ -100,7 +101,10 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
                 for (int r = 0; r < R; ++r) {
                     const uint64_t i = base + r * 4 + tile;
 #pragma unroll
-                    for (int c = 0; c < C; ++c) { if (NT & 4) out[i * DIM4 + c * 16 + tl] = row[r][c]; else __builtin_nontemporal_store(row[r][c], &out[i * DIM4 + c * 16 + tl]); }
+                    for (int c = 0; c < C; ++c) {
+                        if constexpr ((NT & 256) != 0) store_bf16x4<(NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, row[r][c]);
+                        else { if (NT & 4) out[i * DIM4 + c * 16 + tl] = row[r][c]; else __builtin_nontemporal_store(row[r][c], &out[i * DIM4 + c * 16 + tl]); }
+                    }
                 }
             } else {
 #pragma unroll
@@ -113,7 +117,10 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
                     const uint64_t i = base + r * 4 + tile;
                     if (inb[r] && (!(NT & 8) || slot[r] >= 0)) {
 #pragma unroll
-                        for (int c = 0; c < C; ++c) { if (NT & 4) out[i * DIM4 + c * 16 + tl] = row[r][c]; else __builtin_nontemporal_store(row[r][c], &out[i * DIM4 + c * 16 + tl]); }
+                        for (int c = 0; c < C; ++c) {
+                            if constexpr ((NT & 256) != 0) store_bf16x4<(NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, row[r][c]);
+                            else { if (NT & 4) out[i * DIM4 + c * 16 + tl] = row[r][c]; else __builtin_nontemporal_store(row[r][c], &out[i * DIM4 + c * 16 + tl]); }
+                        }
                     }
                 }
             }
@@ -122,8 +129,10 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
             for (int r = 0; r < R; ++r) {
                 const uint64_t i = base + r * 4 + tile;
                 if (inb[r] && (!(NT & 8) || slot[r] >= 0))
-                    for (uint32_t c = tl; c < dim4; c += 16)
-                        out[i * dim4 + c] = slot[r] >= 0 ? values[(uint64_t)slot[r] * dim4 + c] : def4;
+                    for (uint32_t c = tl; c < dim4; c += 16) {
+                        if constexpr ((NT & 256) != 0) store_bf16x4<true>(out, i * dim4 + c, slot[r] >= 0 ? values[(uint64_t)slot[r] * dim4 + c] : def4);
+                        else out[i * dim4 + c] = slot[r] >= 0 ? values[(uint64_t)slot[r] * dim4 + c] : def4;
+                    }
             }
         }
         if constexpr ((NT & 64) != 0) {  // mee_find_located: the slot of every position (-1 = absent), for the apply of the same step
@@ -347,7 +356,9 @@ __device__ __forceinline__ void pooled_fetch(const int64_t* __restrict__ tkeys, 
 // GROUPED (mee_group_find_pooled): bag b belongs to member table b / bags_per_table; the planes come from its descriptor.
 // WEIGHTED (mee_find_pooled_weighted / mee_group_find_pooled_weighted): position i adds weights[i] * row_i — the product rounded, then
 // the sum (no fma; the first position's product is the initial sum); SUM only.  A single table's located rows then carry its handle tag.
-template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false>
+// BF16: `out` holds bf16 rows — the FINISHED bag row (after the mean's division) is rounded once at its store (SPEC.md §3 "Output type");
+// the accumulation is the same fp32 code, and the fp32 instances (BF16 = false) are the code they were before the parameter existed.
+template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false>
 __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restrict__ tkeys_, const float4* __restrict__ values_,
                                                           uint64_t nb_, const int64_t* __restrict__ keys,
                                                           const uint64_t* __restrict__ offsets, uint64_t n_bags,
@@ -431,7 +442,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                     if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
                         float4 v = acc[c];
                         if (mean && end > begin) { v.x = v.x / len; v.y = v.y / len; v.z = v.z / len; v.w = v.w / len; }
-                        out[bag * dim4 + c * 16 + tl] = v;
+                        if constexpr (BF16) store_bf16x4<true>(out, bag * dim4 + c * 16 + tl, v); else out[bag * dim4 + c * 16 + tl] = v;
                     }
             }
         }
@@ -487,7 +498,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                     if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
                         float4 v = acc[c];
                         if (mean && eq > bq) { v.x = v.x / len; v.y = v.y / len; v.z = v.z / len; v.w = v.w / len; }
-                        out[(b0 + q) * dim4 + c * 16 + tl] = v;
+                        if constexpr (BF16) store_bf16x4<true>(out, (b0 + q) * dim4 + c * 16 + tl, v); else out[(b0 + q) * dim4 + c * 16 + tl] = v;
                     }
             }
         }
@@ -696,13 +707,30 @@ int find_plane(const mee_table* t, const float* plane, float miss_value, const i
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
     const unsigned fblock = t->find_block == 64 || t->find_block == 128 ? (unsigned)t->find_block : 256u;   // (launch bound of find_kernel: 256)
+    const bool bf16 = path.out_dtype == MEE_DTYPE_BF16;   // d_out holds bf16 rows (Plain and Located only: the entry points see to that)
+    const uint64_t out_bytes = (uint64_t)n * t->dim * (bf16 ? 2 : 4);   // what the call really writes
     const int nt = path.nt >= 0 ? path.nt : t->find_nt >= 0 ? (t->find_nt & 7)
-                 : ((uint64_t)n * t->dim * 4 <= kCachedOutputBytes && !outputs_rotate(t, d_out, (uint64_t)n * t->dim * 4) ? 4 : 0);
+                 : (out_bytes <= kCachedOutputBytes && !outputs_rotate(t, d_out, out_bytes) ? 4 : 0);
     if (path.kind == FindPath::Missing || path.kind == FindPath::CountedMissing) {
         with_value<3, 1>(path.kind == FindPath::CountedMissing ? 3 : 1, [&](auto flags) {
             find_missing_kernel<flags><<<grid_for(n, 256, 8192), 256, 0, st>>>(t->keys, (const float4*)plane, t->nb, t->dim4, d_keys, n, (float4*)d_out, d_found, t->hits);
         });
-    } else with_row_shape(t->dim4, [&](auto d4) {
+    } else if (bf16) with_row_shape(t->dim4, [&](auto d4) {
+        // bf16 rows: the same kernel with NT | 256, instantiated for each row shape's default keys in flight only ("find_rounds" does not apply)
+        constexpr int D4 = d4;
+        constexpr int R = RowShape<D4>::rows_per_tile;
+        const unsigned grid = grid_for(n, (fblock / 64u) * 4u * (unsigned)R, t->find_grid_cap > 0 ? (unsigned)t->find_grid_cap : (1u << 22));
+        auto find = [&](auto ntc, int64_t* slots_out, int64_t tag) {
+            find_kernel<D4, R, ntc><<<grid, fblock, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, nullptr, slots_out, tag);
+        };
+        if (path.kind == FindPath::Located) {   // (the store policy of the fp32 located find)
+            const bool cached_out = t->find_nt >= 0 && (t->find_nt & 4);
+            with_value<256 + 68, 256 + 64>(cached_out ? 256 + 68 : 256 + 64, [&](auto ntc) { find(ntc, path.slots_out, handle_tag_of(t)); });
+        } else {
+            with_value<256, 257, 258, 259, 260, 261, 262, 263>(256 | nt, [&](auto ntc) { find(ntc, nullptr, 0); });
+        }
+    });
+    else with_row_shape(t->dim4, [&](auto d4) {
         constexpr int D4 = d4;
         int R = t->find_rounds > 0 ? t->find_rounds : RowShape<D4>::rows_per_tile;
         if (D4 != 16 && R > 4) R = 4;
@@ -740,6 +768,24 @@ int find_plane(const mee_table* t, const float* plane, float miss_value, const i
 }  // namespace mee
 extern "C" {
 
+// mee_find_ex / mee_find_as: the call's hints become the kernel's policy bits; the output's size is counted in its own element type
+static int find_hinted(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint8_t* d_found, uint32_t flags, uint32_t out_dtype, void* stream,
+                       const char* name) {
+    if (!t || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
+    if (flags & ~(uint32_t)(MEE_FIND_STREAM_STORES | MEE_FIND_CACHED_STORES | MEE_FIND_STREAM_ROWS | MEE_FIND_STREAM_BUCKETS))
+        return fail(MEE_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x", name, flags);
+    if ((flags & MEE_FIND_STREAM_STORES) && (flags & MEE_FIND_CACHED_STORES))
+        return fail(MEE_ERR_INVALID_ARG, "%s: MEE_FIND_STREAM_STORES and MEE_FIND_CACHED_STORES exclude each other", name);
+    if (flags == MEE_FIND_DEFAULT) return find_plane(t, t->values, t->default_value, d_keys, n, (float*)d_out, d_found, stream, {FindPath::Plain, nullptr, -1, out_dtype});
+    // the kernel's policy bits: 1 = streaming row loads, 2 = streaming bucket loads, 4 = cached stores of the dense output
+    const uint64_t out_bytes = (uint64_t)n * t->dim * (out_dtype == MEE_DTYPE_BF16 ? 2 : 4);
+    const bool cached_out = (flags & MEE_FIND_CACHED_STORES) ||
+                            (!(flags & MEE_FIND_STREAM_STORES) && out_bytes <= kCachedOutputBytes && !outputs_rotate(t, d_out, out_bytes));
+    const int nt = (flags & MEE_FIND_STREAM_ROWS ? 1 : 0) | (flags & MEE_FIND_STREAM_BUCKETS ? 2 : 0) | (cached_out ? 4 : 0);
+    return find_plane(t, t->values, t->default_value, d_keys, n, (float*)d_out, d_found, stream, {FindPath::Plain, nullptr, nt, out_dtype});
+}
+
 int mee_find(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream) {
     MEE_RANGE("mee_find");
     if (!t || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find: null argument");
@@ -748,17 +794,12 @@ int mee_find(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, 
 
 int mee_find_ex(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, uint32_t flags, void* stream) {
     MEE_RANGE("mee_find_ex");
-    if (!t || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_ex: null argument");
-    if (flags & ~(uint32_t)(MEE_FIND_STREAM_STORES | MEE_FIND_CACHED_STORES | MEE_FIND_STREAM_ROWS | MEE_FIND_STREAM_BUCKETS))
-        return fail(MEE_ERR_INVALID_ARG, "mee_find_ex: unknown flag bits 0x%x", flags);
-    if ((flags & MEE_FIND_STREAM_STORES) && (flags & MEE_FIND_CACHED_STORES))
-        return fail(MEE_ERR_INVALID_ARG, "mee_find_ex: MEE_FIND_STREAM_STORES and MEE_FIND_CACHED_STORES exclude each other");
-    if (flags == MEE_FIND_DEFAULT) return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream);
-    // the kernel's policy bits: 1 = streaming row loads, 2 = streaming bucket loads, 4 = cached stores of the dense output
-    const bool cached_out = (flags & MEE_FIND_CACHED_STORES) ||
-                            (!(flags & MEE_FIND_STREAM_STORES) && (uint64_t)n * t->dim * 4 <= kCachedOutputBytes && !outputs_rotate(t, d_out, (uint64_t)n * t->dim * 4));
-    const int nt = (flags & MEE_FIND_STREAM_ROWS ? 1 : 0) | (flags & MEE_FIND_STREAM_BUCKETS ? 2 : 0) | (cached_out ? 4 : 0);
-    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {FindPath::Plain, nullptr, nt});
+    return find_hinted(t, d_keys, n, d_out, d_found, flags, MEE_DTYPE_F32, stream, "mee_find_ex");
+}
+
+int mee_find_as(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, uint32_t flags, void* stream) {
+    MEE_RANGE("mee_find_as");
+    return find_hinted(t, d_keys, n, d_out, d_found, flags, out_dtype, stream, "mee_find_as");
 }
 
 }  // extern "C"
@@ -776,6 +817,12 @@ int mee_find_located(const mee_table* t, const int64_t* d_keys, size_t n, float*
     MEE_RANGE("mee_find_located");
     if (!t || (n && (!d_keys || !d_out || !d_slots_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_located: null argument");
     return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {FindPath::Located, d_slots_out});
+}
+int mee_find_located_as(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out, void* stream) {
+    MEE_RANGE("mee_find_located_as");
+    if (!t || (n && (!d_keys || !d_out || !d_slots_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_located_as: null argument");
+    if (int rc = check_out_dtype(d_out, out_dtype, "mee_find_located_as")) return rc;
+    return find_plane(t, t->values, t->default_value, d_keys, n, (float*)d_out, d_found, stream, {FindPath::Located, d_slots_out, -1, out_dtype});
 }
 
 int mee_find_many(const mee_table* t, const mee_find_request* reqs, uint32_t count, void* stream) {
@@ -828,20 +875,30 @@ int mee_find_counted(const mee_table* t, const int64_t* d_keys, size_t n, float*
     return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {missing_only ? FindPath::CountedMissing : FindPath::Counted});
 }
 
+// every pooled lookup of one table: mode SUM | MEAN, or d_weights (SUM only; located rows in the format of mee_find_located); fp32 or bf16 bag rows
+static int find_pooled_common(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const float* d_weights, void* d_out,
+                              uint32_t out_dtype, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
+    if (n_bags == 0) return MEE_OK;
+    DeviceGuard g(t->device);
+    hipStream_t st = as_stream(stream);
+    const int64_t tag = handle_tag_of(t);   // located rows in the format of mee_find_located
+    with_pooled_shape(t->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(d_weights != nullptr, [&](auto weighted) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
+        auto launch = [&](auto kernel) {
+            kernel<<<grid, 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, t->default_value, t->dim4,
+                                         mode == MEE_POOL_MEAN, nullptr, 1, weighted ? d_located_out : nullptr, n, d_weights, weighted ? tag : 0);
+        };
+        launch(find_pooled_kernel<d4, u, bpw, false, weighted, bf16>);
+    }); }); });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
 int mee_find_pooled(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, float* d_out,
                     uint8_t* d_found, int mode, void* stream) {
     MEE_RANGE("mee_find_pooled");
     if (!t || (n_bags && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled: null argument");
     if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
-    if (n_bags == 0) return MEE_OK;
-    DeviceGuard g(t->device);
-    hipStream_t st = as_stream(stream);
-    with_pooled_shape(t->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
-        find_pooled_kernel<d4, u, bpw><<<grid, 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found,
-                                                             t->default_value, t->dim4, mode == MEE_POOL_MEAN, nullptr, 1, nullptr, n);
-    });
-    MEE_HIP(hipGetLastError());
-    return MEE_OK;
+    return find_pooled_common(t, d_keys, n, d_bag_offsets, n_bags, nullptr, d_out, MEE_DTYPE_F32, d_found, nullptr, mode, stream);
 }
 
 int mee_find_pooled_weighted(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
@@ -849,16 +906,18 @@ int mee_find_pooled_weighted(const mee_table* t, const int64_t* d_keys, size_t n
     MEE_RANGE("mee_find_pooled_weighted");
     if (!t || (n_bags && (!d_bag_offsets || !d_out)) || (n && (!d_keys || !d_weights)))
         return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_weighted: null argument");
-    if (n_bags == 0) return MEE_OK;
-    DeviceGuard g(t->device);
-    hipStream_t st = as_stream(stream);
-    const int64_t tag = handle_tag_of(t);   // located rows in the format of mee_find_located
-    with_pooled_shape(t->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
-        find_pooled_kernel<d4, u, bpw, false, true><<<grid, 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found,
-                                                                          t->default_value, t->dim4, 0, nullptr, 1, d_located_out, n, d_weights, tag);
-    });
-    MEE_HIP(hipGetLastError());
-    return MEE_OK;
+    return find_pooled_common(t, d_keys, n, d_bag_offsets, n_bags, d_weights /* null only with n = 0: every bag is empty, the plain sum's zeros */, d_out, MEE_DTYPE_F32, d_found, d_located_out, MEE_POOL_SUM, stream);
+}
+
+int mee_find_pooled_as(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const float* d_weights,
+                       void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
+    MEE_RANGE("mee_find_pooled_as");
+    if (!t || (n_bags && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: null argument");
+    if (int rc = check_out_dtype(d_out, out_dtype, "mee_find_pooled_as")) return rc;
+    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
+    if (d_weights && mode != MEE_POOL_SUM) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: weighted pooling is MEE_POOL_SUM only");
+    if (d_located_out && !d_weights) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: d_located_out is the weighted form's output (pass weights of 1.0f for a plain sum)");
+    return find_pooled_common(t, d_keys, n, d_bag_offsets, n_bags, d_weights, d_out, out_dtype, d_found, d_located_out, mode, stream);
 }
 
 int mee_pooled_weighted_backward(const mee_table* t, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,
@@ -887,22 +946,30 @@ int mee_find_plane(const mee_table* t, uint32_t plane, const int64_t* d_keys, si
 }
 
 // ---- the embedding-bag collection: pooled lookups of a whole group in one launch, and their backward -----------------------
-int mee_group_find_pooled(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
-                          float* d_out, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
-    MEE_RANGE("mee_group_find_pooled");
-    if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled: null argument");
-    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
+static int group_find_pooled_common(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights,
+                                    void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
     if (bags_per_table == 0) return MEE_OK;
     if (int rc = group_refresh(g, stream)) return rc;
     DeviceGuard guard(g->device);
     hipStream_t st = as_stream(stream);
     const uint64_t n_bags = (uint64_t)g->n_tables * bags_per_table;
-    with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
-        find_pooled_kernel<d4, u, bpw, true><<<grid, 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4,
-                                                                   mode == MEE_POOL_MEAN, g->d_desc, bags_per_table, d_located_out, n);
-    });
+    with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(d_weights != nullptr, [&](auto weighted) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
+        auto launch = [&](auto kernel) {
+            kernel<<<grid, 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, mode == MEE_POOL_MEAN, g->d_desc, bags_per_table,
+                                         d_located_out, n, d_weights, 0);
+        };
+        launch(find_pooled_kernel<d4, u, bpw, true, weighted, bf16>);
+    }); }); });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
+}
+
+int mee_group_find_pooled(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                          float* d_out, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
+    MEE_RANGE("mee_group_find_pooled");
+    if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled: null argument");
+    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
+    return group_find_pooled_common(g, d_keys, n, d_bag_offsets, bags_per_table, nullptr, d_out, MEE_DTYPE_F32, d_found, d_located_out, mode, stream);
 }
 
 int mee_group_find_pooled_weighted(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
@@ -910,17 +977,17 @@ int mee_group_find_pooled_weighted(mee_group* g, const int64_t* d_keys, size_t n
     MEE_RANGE("mee_group_find_pooled_weighted");
     if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && (!d_keys || !d_weights)))
         return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_weighted: null argument");
-    if (bags_per_table == 0) return MEE_OK;
-    if (int rc = group_refresh(g, stream)) return rc;
-    DeviceGuard guard(g->device);
-    hipStream_t st = as_stream(stream);
-    const uint64_t n_bags = (uint64_t)g->n_tables * bags_per_table;
-    with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
-        find_pooled_kernel<d4, u, bpw, true, true><<<grid, 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4,
-                                                                         0, g->d_desc, bags_per_table, d_located_out, n, d_weights);
-    });
-    MEE_HIP(hipGetLastError());
-    return MEE_OK;
+    return group_find_pooled_common(g, d_keys, n, d_bag_offsets, bags_per_table, d_weights /* null only with n = 0 */, d_out, MEE_DTYPE_F32, d_found, d_located_out, MEE_POOL_SUM, stream);
+}
+
+int mee_group_find_pooled_as(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights,
+                             void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
+    MEE_RANGE("mee_group_find_pooled_as");
+    if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_as: null argument");
+    if (int rc = check_out_dtype(d_out, out_dtype, "mee_group_find_pooled_as")) return rc;
+    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_as: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
+    if (d_weights && mode != MEE_POOL_SUM) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_as: weighted pooling is MEE_POOL_SUM only");
+    return group_find_pooled_common(g, d_keys, n, d_bag_offsets, bags_per_table, d_weights, d_out, out_dtype, d_found, d_located_out, mode, stream);
 }
 
 int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,
@@ -942,15 +1009,16 @@ int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, cons
     return MEE_OK;
 }
 
+}  // extern "C"
 // The training forward: mee_find_located whose launch also carries mee_apply_prepare for the SAME keys (the partition half of the bucketed
 // apply, run by the launch's first blocks beside the row gather).  (Table without optimizer: plain mee_find_located.)
-int mee_find_located_prepare(mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, int64_t* d_slots_out, void* stream) {
-    MEE_RANGE("mee_find_located_prepare");
-    if (!t || (n && (!d_keys || !d_out || !d_slots_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_located_prepare: null argument");
-    if (t->prepared_n) return fail(MEE_ERR_INVALID_ARG, "mee_find_located_prepare: a prepared apply is already pending");
+int mee::find_located_prepare(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out, void* stream, const char* name) {
+    if (!t || (n && (!d_keys || !d_out || !d_slots_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
+    if (t->prepared_n) return fail(MEE_ERR_INVALID_ARG, "%s: a prepared apply is already pending", name);
     if (n == 0) return MEE_OK;
-    if (t->optimizer == MEE_OPT_NONE) return mee_find_located(t, d_keys, n, d_out, d_found, d_slots_out, stream);
-    if (n > t->max_batch) return fail(MEE_ERR_BATCH_TOO_LARGE, "mee_find_located_prepare: n=%zu exceeds config.max_batch=%llu", n, (unsigned long long)t->max_batch);
+    if (t->optimizer == MEE_OPT_NONE) return find_plane(t, t->values, t->default_value, d_keys, n, (float*)d_out, d_found, stream, {FindPath::Located, d_slots_out, -1, out_dtype});
+    if (n > t->max_batch) return fail(MEE_ERR_BATCH_TOO_LARGE, "%s: n=%zu exceeds config.max_batch=%llu", name, n, (unsigned long long)t->max_batch);
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
     uint32_t apply_grid, nbk;
@@ -965,16 +1033,28 @@ int mee_find_located_prepare(mee_table* t, const int64_t* d_keys, size_t n, floa
         constexpr int R = d4 == 16 ? kFindPrepareR : d4 == 32 ? 2 : 1;
         const unsigned find_cap = t->prepare_debug >> 8;
         const unsigned find_blocks = grid_for(n, (kFindPrepareThreads / 64) * 4u * (unsigned)R, find_cap ? find_cap : 1u << 22);
-        with_value<68, 64>(cached_out ? 68 : 64, [&](auto ntc) {
+        auto launch = [&](auto ntc) {
             find_prepare_kernel<d4, R, ntc><<<part_blocks + find_blocks, kFindPrepareThreads, sizeof(PartHot) + nbk * 4, st>>>(t->keys, (const f32x4*)t->values, t->nb, d_keys, n,
                 (f32x4*)d_out, d_found, t->default_value, t->dim4, d_slots_out, handle_tag_of(t), part_blocks, nbk_hash, nbk, per_block, t->bk, &t->ctr->status, t->op, t->bk.xcd_split);
-        });
+        };
+        if (out_dtype == MEE_DTYPE_BF16) with_value<256 + 68, 256 + 64>(cached_out ? 256 + 68 : 256 + 64, launch);   // NT | 256: bf16 rows (find_span)
+        else with_value<68, 64>(cached_out ? 68 : 64, launch);
     });
     MEE_HIP(hipGetLastError());
     if (separate) { if (int rc = bucket_apply_prepare(t, d_keys, (uint32_t)n, st)) return rc; }
     else { t->part_blocks = part_blocks; t->part_per_block = per_block; t->part_nbk = nbk; t->part_nbk_hash = nbk_hash; t->part_grid = apply_grid; t->part_full = apply_full; }
     t->prepared_n = n; t->prepared_keys = d_keys; t->prepared_by_forward = true;
     return MEE_OK;
+}
+extern "C" {
+
+int mee_find_located_prepare(mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, int64_t* d_slots_out, void* stream) {
+    MEE_RANGE("mee_find_located_prepare");
+    return find_located_prepare(t, d_keys, n, d_out, MEE_DTYPE_F32, d_found, d_slots_out, stream, "mee_find_located_prepare");
+}
+int mee_find_located_prepare_as(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out, void* stream) {
+    MEE_RANGE("mee_find_located_prepare_as");
+    return find_located_prepare(t, d_keys, n, d_out, out_dtype, d_found, d_slots_out, stream, "mee_find_located_prepare_as");
 }
 
 #if MEE_FIND_TIMELINE

@@ -18,13 +18,12 @@
 
 namespace mee {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 
 // One tile per key, R keys in flight per tile (same shape as find_kernel).  DIM4 = dim/4 when it is 16 or 32, 0 = any.
 // LOCATE: no rows move; gslot[i] = member << 48 | slot of the key (kEmpty when absent / reserved / outside the segments) —
 // the first pass of a grouped apply.
-template <int DIM4, int R, bool STREAM_OUT, bool LOCATE = false>
+// BF16: `out` holds bf16 rows (SPEC.md §3 "Output type"): the lane's float4 leaves as 4 bf16 in one 8-byte store; BF16 = false is the code it was.
+template <int DIM4, int R, bool STREAM_OUT, bool LOCATE = false, bool BF16 = false>
 __global__ __launch_bounds__(256) void find_grouped_kernel(const GroupDesc* __restrict__ desc, uint32_t n_tables,
                                                            const uint64_t* __restrict__ offsets, const int64_t* __restrict__ keys,
                                                            uint64_t n, float4* __restrict__ out, uint8_t* __restrict__ found,
@@ -105,7 +104,9 @@ __global__ __launch_bounds__(256) void find_grouped_kernel(const GroupDesc* __re
                 if (inb[r])
 #pragma unroll
                     for (int c = 0; c < C; ++c) {
-                        if constexpr (STREAM_OUT) {   // a dense output beyond the Infinity Cache: streaming stores (find_kernel's policy)
+                        if constexpr (BF16) {
+                            store_bf16x4<!STREAM_OUT>(out, i * DIM4 + c * 16 + tl, row[r][c]);
+                        } else if constexpr (STREAM_OUT) {   // a dense output beyond the Infinity Cache: streaming stores (find_kernel's policy)
                             const f32x4 v = {row[r][c].x, row[r][c].y, row[r][c].z, row[r][c].w};
                             __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out) + i * DIM4 + c * 16 + tl);
                         } else {
@@ -118,9 +119,11 @@ __global__ __launch_bounds__(256) void find_grouped_kernel(const GroupDesc* __re
             for (int r = 0; r < R; ++r) {
                 const uint64_t i = base + r * 4 + tile;
                 if (inb[r])
-                    for (uint32_t c = tl; c < dim4; c += 16)
-                        out[i * dim4 + c] = slot[r] >= 0 ? d[r].values[(uint64_t)slot[r] * dim4 + c]
-                                                         : make_float4(d[r].defv, d[r].defv, d[r].defv, d[r].defv);
+                    for (uint32_t c = tl; c < dim4; c += 16) {
+                        const float4 v = slot[r] >= 0 ? d[r].values[(uint64_t)slot[r] * dim4 + c]
+                                                      : make_float4(d[r].defv, d[r].defv, d[r].defv, d[r].defv);
+                        if constexpr (BF16) store_bf16x4<true>(out, i * dim4 + c, v); else out[i * dim4 + c] = v;
+                    }
             }
         }
         if (found) {
@@ -137,6 +140,8 @@ __global__ __launch_bounds__(256) void find_grouped_kernel(const GroupDesc* __re
 // got there first) its key's slot in its member table; the tile whose CAS created the key writes the initial row, the
 // initial optimizer state and a zero hit counter, and every such tile writes that same initial row — a function of the
 // key and its table's initializer alone — into `out`, so nothing has to read the created rows back.  One tile per position.
+// BF16: `out` holds bf16 rows — the returned copy is rounded, the table's row is not.
+template <bool BF16 = false>
 __global__ __launch_bounds__(256) void ensure_grouped_kernel(const GroupDesc* __restrict__ desc, const GroupInit* __restrict__ init,
                                                              uint32_t n_tables, const uint64_t* __restrict__ offsets,
                                                              const int64_t* __restrict__ keys, uint64_t n,
@@ -168,7 +173,7 @@ __global__ __launch_bounds__(256) void ensure_grouped_kernel(const GroupDesc* __
             if (slot >= 0) {
                 for (uint32_t c = tl; c < dim4; c += 16) {
                     const float4 row = initial_row4(key, c * 4, in.initializer, in.init_scale, in.init_seed, d.defv);
-                    out[i * dim4 + c] = row;
+                    if constexpr (BF16) store_bf16x4<true>(out, i * dim4 + c, row); else out[i * dim4 + c] = row;
                     if (is_new) {
                         d.values[(uint64_t)slot * dim4 + c] = row;
                         if (in.optimizer == MEE_OPT_ADAGRAD) d.s1[(uint64_t)slot * dim4 + c] = make_float4(in.init_acc, in.init_acc, in.init_acc, in.init_acc);
@@ -287,16 +292,50 @@ int mee_group_destroy(mee_group* g) {
 
 }  // extern "C"
 
-static int launch_find_grouped(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, float* d_out, uint8_t* d_found,
+static int launch_find_grouped(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
                                hipStream_t st) {
-    const bool stream_out = (uint64_t)n * g->dim * 4 > kCachedOutputBytes;   // find_kernel's store policy
+    const bool bf16 = out_dtype == MEE_DTYPE_BF16;
+    const bool stream_out = (uint64_t)n * g->dim * (bf16 ? 2 : 4) > kCachedOutputBytes;   // find_kernel's store policy, on the bytes really written
     // every block starts by staging the offsets in LDS (a global round trip + a barrier): blocks must live long enough to
     // amortise it, so the grid is capped and strides (measured: 8192 blocks best from 200K to 1M positions)
     const unsigned grid_cap = 8192;
     with_row_shape(g->dim4, [&](auto d4) { with_flag(stream_out, [&](auto so) {
         constexpr int R = RowShape<d4>::rows_per_tile;   // (a block: 16 tiles of R keys in flight)
-        find_grouped_kernel<d4, R, so><<<grid_for(n, 16 * R, grid_cap), 256, 0, st>>>(g->d_desc, g->n_tables, d_offsets, d_keys, n, (float4*)d_out, d_found, g->dim4);
+        if (bf16) find_grouped_kernel<d4, R, so, false, true><<<grid_for(n, 16 * R, grid_cap), 256, 0, st>>>(g->d_desc, g->n_tables, d_offsets, d_keys, n, (float4*)d_out, d_found, g->dim4);
+        else find_grouped_kernel<d4, R, so><<<grid_for(n, 16 * R, grid_cap), 256, 0, st>>>(g->d_desc, g->n_tables, d_offsets, d_keys, n, (float4*)d_out, d_found, g->dim4);
     }); });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+static int find_grouped_common(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
+                               void* stream, const char* name) {
+    if (!g || !d_offsets || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
+    if (n == 0) return MEE_OK;
+    if (int rc = group_refresh(g, stream)) return rc;
+    DeviceGuard guard(g->device);
+    return launch_find_grouped(g, d_keys, d_offsets, n, d_out, out_dtype, d_found, (hipStream_t)stream);
+}
+
+static int group_find_or_insert_common(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
+                                       void* stream, const char* name) {
+    if (!g || !d_offsets || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
+    if (n == 0) return MEE_OK;
+    if (!d_found) {
+        if (n > g->max_apply_batch)
+            return fail(MEE_ERR_BATCH_TOO_LARGE, "%s: without a found buffer n=%zu must be <= max_apply_batch=%llu", name, n, (unsigned long long)g->max_apply_batch);
+        d_found = g->d_fmask;
+    }
+    if (int rc = group_refresh(g, stream)) return rc;
+    DeviceGuard guard(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    // 1) the ordinary grouped find serves every stored key and yields the present-before mask
+    if (int rc = launch_find_grouped(g, d_keys, d_offsets, n, d_out, out_dtype, d_found, st)) return rc;
+    // 2) missing positions create their key (one creator per distinct key: the CAS decides) and return its initial row
+    if (out_dtype == MEE_DTYPE_BF16) ensure_grouped_kernel<true><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_init, g->n_tables, d_offsets, d_keys, n, d_found, g->dim4, (float4*)d_out);
+    else ensure_grouped_kernel<false><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_init, g->n_tables, d_offsets, d_keys, n, d_found, g->dim4, (float4*)d_out);
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -306,32 +345,23 @@ extern "C" {
 int mee_find_grouped(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, float* d_out, uint8_t* d_found,
                      void* stream) {
     MEE_RANGE("mee_find_grouped");
-    if (!g || !d_offsets || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_grouped: null argument");
-    if (n == 0) return MEE_OK;
-    if (int rc = group_refresh(g, stream)) return rc;
-    DeviceGuard guard(g->device);
-    return launch_find_grouped(g, d_keys, d_offsets, n, d_out, d_found, (hipStream_t)stream);
+    return find_grouped_common(g, d_keys, d_offsets, n, d_out, MEE_DTYPE_F32, d_found, stream, "mee_find_grouped");
+}
+int mee_find_grouped_as(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
+                        void* stream) {
+    MEE_RANGE("mee_find_grouped_as");
+    return find_grouped_common(g, d_keys, d_offsets, n, d_out, out_dtype, d_found, stream, "mee_find_grouped_as");
 }
 
 int mee_group_find_or_insert(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, float* d_out, uint8_t* d_found,
                              void* stream) {
     MEE_RANGE("mee_group_find_or_insert");
-    if (!g || !d_offsets || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_or_insert: null argument");
-    if (n == 0) return MEE_OK;
-    if (!d_found) {
-        if (n > g->max_apply_batch)
-            return fail(MEE_ERR_BATCH_TOO_LARGE, "mee_group_find_or_insert: without a found buffer n=%zu must be <= max_apply_batch=%llu", n, (unsigned long long)g->max_apply_batch);
-        d_found = g->d_fmask;
-    }
-    if (int rc = group_refresh(g, stream)) return rc;
-    DeviceGuard guard(g->device);
-    hipStream_t st = (hipStream_t)stream;
-    // 1) the ordinary grouped find serves every stored key and yields the present-before mask
-    if (int rc = launch_find_grouped(g, d_keys, d_offsets, n, d_out, d_found, st)) return rc;
-    // 2) missing positions create their key (one creator per distinct key: the CAS decides) and return its initial row
-    ensure_grouped_kernel<<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_init, g->n_tables, d_offsets, d_keys, n, d_found, g->dim4, (float4*)d_out);
-    MEE_HIP(hipGetLastError());
-    return MEE_OK;
+    return group_find_or_insert_common(g, d_keys, d_offsets, n, d_out, MEE_DTYPE_F32, d_found, stream, "mee_group_find_or_insert");
+}
+int mee_group_find_or_insert_as(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
+                                void* stream) {
+    MEE_RANGE("mee_group_find_or_insert_as");
+    return group_find_or_insert_common(g, d_keys, d_offsets, n, d_out, out_dtype, d_found, stream, "mee_group_find_or_insert_as");
 }
 
 }  // extern "C"

@@ -27,6 +27,13 @@ inline int fail(int code, const char* fmt, ...) {
                                "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+// the typed-output forms (mee_*_as): fp32 or bf16 rows; a bf16 row group is one 8-byte store, so the buffer is 8-byte aligned
+inline int check_out_dtype(const void* d_out, uint32_t out_dtype, const char* name) {
+    if (out_dtype != MEE_DTYPE_F32 && out_dtype != MEE_DTYPE_BF16) return fail(MEE_ERR_INVALID_ARG, "%s: unknown out_dtype %u (MEE_DTYPE_F32 or MEE_DTYPE_BF16)", name, out_dtype);
+    if (out_dtype == MEE_DTYPE_BF16 && ((uintptr_t)d_out & 7)) return fail(MEE_ERR_INVALID_ARG, "%s: a bf16 output must be 8-byte aligned", name);
+    return MEE_OK;
+}
+
 // roctx ranges around every operator of the C-ABI (tracing), so that `rocprofv3 --marker-trace --kernel-trace` groups the kernels by the
 // operator that launched them.  The marker library (librocprofiler-sdk-roctx.so.1, part of ROCm) is bound with dlopen at the first operator call; when
 // it is not there — or MEE_ROCTX=0 — a range is one predictable branch.  Without a profiler attached a push / pop pair costs ~0.1 us of host time.

@@ -374,14 +374,16 @@ __global__ __launch_bounds__(256) void remove_mark_kernel(int64_t* tkeys, const 
 // it, when another occurrence of the key got there first: the CAS decides the one creator); the creating tile writes the
 // hashed initial row, the initial optimizer state and a zero hit counter.  A wave with nothing missing leaves at once —
 // the steady state of a trained vocabulary costs one pass over keys + found.  The rows are read by a last find pass.
-template <int P>   // positions per wave step (64; 32 and 16 measured no faster on batches of new keys — the pass is bound by its claims — and
+// BF16 (ensure_direct_bf16_kernel): `out` holds bf16 rows — the returned copy of an initial row is rounded (SPEC.md §3 "Output type"), the table's is not.
+template <int P,   // positions per wave step (64; 32 and 16 measured no faster on batches of new keys — the pass is bound by its claims — and
                    // 3-7 % slower when nearly every key is present: tools/foi_bench.py)
-__global__ __launch_bounds__(256) void ensure_direct_kernel(int64_t* tkeys, float4* values, float4* s1, float4* s2, uint64_t nb,
-                                                            uint32_t dim4, const int64_t* __restrict__ keys, uint32_t n,
-                                                            const uint8_t* __restrict__ found, uint32_t optimizer, float init_acc,
-                                                            uint32_t initializer, float init_scale, uint64_t init_seed,
-                                                            float default_value, Counters* ctr, uint32_t* hits, float4* __restrict__ out,
-                                                            long long* __restrict__ slots_out = nullptr, long long handle_tag = 0) {
+          bool BF16>
+__device__ __forceinline__ void ensure_direct_body(int64_t* tkeys, float4* values, float4* s1, float4* s2, uint64_t nb,
+                                                   uint32_t dim4, const int64_t* __restrict__ keys, uint32_t n,
+                                                   const uint8_t* __restrict__ found, uint32_t optimizer, float init_acc,
+                                                   uint32_t initializer, float init_scale, uint64_t init_seed,
+                                                   float default_value, Counters* ctr, uint32_t* hits, float4* __restrict__ out,
+                                                   long long* __restrict__ slots_out, long long handle_tag) {
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const uint32_t n_waves = gridDim.x * (blockDim.x >> 6);
@@ -408,7 +410,7 @@ __global__ __launch_bounds__(256) void ensure_direct_kernel(int64_t* tkeys, floa
                 // (bit-identical to what the creator stores), so no third pass has to read the created rows back.
                 for (uint32_t c = tl; c < dim4; c += 16) {
                     const float4 row = initial_row4(key, c * 4, initializer, init_scale, init_seed, default_value);
-                    if (out) out[(uint64_t)(base + p) * dim4 + c] = row;
+                    if (out) { if constexpr (BF16) store_bf16x4<true>(out, (uint64_t)(base + p) * dim4 + c, row); else out[(uint64_t)(base + p) * dim4 + c] = row; }
                     if (is_new) {
                         values[(uint64_t)slot * dim4 + c] = row;
                         if (optimizer == MEE_OPT_ADAGRAD) s1[(uint64_t)slot * dim4 + c] = make_float4(init_acc, init_acc, init_acc, init_acc);
@@ -428,6 +430,14 @@ __global__ __launch_bounds__(256) void ensure_direct_kernel(int64_t* tkeys, floa
         }
     }
 }
+#define MEE_ENSURE_PARAMS int64_t* tkeys, float4* values, float4* s1, float4* s2, uint64_t nb, uint32_t dim4, const int64_t* __restrict__ keys, uint32_t n, \
+                          const uint8_t* __restrict__ found, uint32_t optimizer, float init_acc, uint32_t initializer, float init_scale, uint64_t init_seed,   \
+                          float default_value, Counters* ctr, uint32_t* hits, float4* __restrict__ out, long long* __restrict__ slots_out = nullptr, long long handle_tag = 0
+#define MEE_ENSURE_ARGS tkeys, values, s1, s2, nb, dim4, keys, n, found, optimizer, init_acc, initializer, init_scale, init_seed, default_value, ctr, hits, out, slots_out, handle_tag
+template <int P> __global__ __launch_bounds__(256) void ensure_direct_kernel(MEE_ENSURE_PARAMS) { ensure_direct_body<P, false>(MEE_ENSURE_ARGS); }
+template <int P> __global__ __launch_bounds__(256) void ensure_direct_bf16_kernel(MEE_ENSURE_PARAMS) { ensure_direct_body<P, true>(MEE_ENSURE_ARGS); }
+#undef MEE_ENSURE_PARAMS
+#undef MEE_ENSURE_ARGS
 
 // =========================================================================================================
 // host side
@@ -714,9 +724,21 @@ int mee_remove(mee_table* t, const int64_t* d_keys, size_t n, uint8_t* d_found, 
 }
 
 // shared by mee_find_or_insert (own find pass) and mee_find_or_insert_missing (mask supplied by the caller)
-static int find_or_insert_common(mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream,
-                                 bool own_find_pass, const char* name, int64_t* d_slots_out = nullptr) {
+// the pass of find_or_insert that creates the missing keys and returns their initial rows (fp32 or bf16 `d_out`)
+static void launch_ensure(mee_table* t, const int64_t* d_keys, uint32_t n, const uint8_t* mask, void* d_out, uint32_t out_dtype, int64_t* d_slots_out, hipStream_t st) {
+    auto launch = [&](auto kernel) {
+        kernel<<<grid_for(n, 256, 8192), 256, 0, st>>>(t->keys, (float4*)t->values, (float4*)t->s1, (float4*)t->s2, t->nb, t->dim4, d_keys, n, mask, t->optimizer, t->init_acc,
+                                                       t->initializer, t->init_scale, t->init_seed, t->default_value, t->ctr, t->hits, (float4*)d_out, (long long*)d_slots_out,
+                                                       (long long)(d_slots_out ? handle_tag_of(t) : 0));
+    };
+    if (out_dtype == MEE_DTYPE_BF16) launch(ensure_direct_bf16_kernel<64>);
+    else launch(ensure_direct_kernel<64>);
+}
+
+static int find_or_insert_common(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint8_t* d_found, void* stream,
+                                 bool own_find_pass, const char* name, int64_t* d_slots_out = nullptr, uint32_t out_dtype = MEE_DTYPE_F32) {
     if (!t || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
     if (int rc = check_batch(t, n, name, stream)) return rc;
     if (n == 0) return MEE_OK;
     DeviceGuard g(t->device);
@@ -726,12 +748,10 @@ static int find_or_insert_common(mee_table* t, const int64_t* d_keys, size_t n, 
     // yields the "present before the call" mask; pass 2 runs the insert machinery over the missing positions only.
     uint8_t* fmask = d_found ? d_found : t->bs.fmask;
     if (own_find_pass)
-        if (int rc = find_plane(t, t->values, t->default_value, d_keys, n, d_out, fmask, stream, {d_slots_out ? FindPath::Located : FindPath::Plain, d_slots_out})) return rc;
+        if (int rc = find_plane(t, t->values, t->default_value, d_keys, n, (float*)d_out, fmask, stream, {d_slots_out ? FindPath::Located : FindPath::Plain, d_slots_out, -1, out_dtype})) return rc;
     // pass 2: every position the mask leaves missing claims its key (or meets the occurrence that did) and writes the key's initial row
     // into the table (creator) and into d_out (everybody): nothing is left for a third pass
-    ensure_direct_kernel<64><<<grid_for(n, 256, 8192), 256, 0, st>>>(t->keys, (float4*)t->values, (float4*)t->s1, (float4*)t->s2, t->nb, t->dim4,
-                                                                d_keys, nn, fmask, t->optimizer, t->init_acc, t->initializer, t->init_scale,
-                                                                t->init_seed, t->default_value, t->ctr, t->hits, (float4*)d_out, (long long*)d_slots_out, (long long)handle_tag_of(t));
+    launch_ensure(t, d_keys, nn, fmask, d_out, out_dtype, d_slots_out, st);
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -744,6 +764,15 @@ int mee_find_or_insert_located(mee_table* t, const int64_t* d_keys, size_t n, fl
 int mee_find_or_insert(mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream) {
     MEE_RANGE("mee_find_or_insert");
     return find_or_insert_common(t, d_keys, n, d_out, d_found, stream, true, "mee_find_or_insert");
+}
+int mee_find_or_insert_as(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, void* stream) {
+    MEE_RANGE("mee_find_or_insert_as");
+    return find_or_insert_common(t, d_keys, n, d_out, d_found, stream, true, "mee_find_or_insert_as", nullptr, out_dtype);
+}
+int mee_find_or_insert_located_as(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out, void* stream) {
+    MEE_RANGE("mee_find_or_insert_located_as");
+    if (n && !d_slots_out) return fail(MEE_ERR_INVALID_ARG, "mee_find_or_insert_located_as: null argument");
+    return find_or_insert_common(t, d_keys, n, d_out, d_found, stream, true, "mee_find_or_insert_located_as", d_slots_out, out_dtype);
 }
 int mee_find_or_insert_admit(mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, uint32_t min_count, void* stream) {
     MEE_RANGE("mee_find_or_insert_admit");
@@ -902,23 +931,30 @@ int mee_apply_prepare(mee_table* t, const int64_t* d_keys, size_t n, void* strea
     return MEE_OK;
 }
 
-int mee_find_or_insert_located_prepare(mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, int64_t* d_slots_out, void* stream) {
-    MEE_RANGE("mee_find_or_insert_located_prepare");
-    if (!t || (n && (!d_keys || !d_out || !d_slots_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_or_insert_located_prepare: null argument");
-    if (t->optimizer == MEE_OPT_NONE) return mee_find_or_insert_located(t, d_keys, n, d_out, d_found, d_slots_out, stream);
-    if (int rc = check_batch(t, n, "mee_find_or_insert_located_prepare", stream, true, false)) return rc;   // (refuses while another prepared apply is pending)
+static int find_or_insert_located_prepare(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out, void* stream,
+                                          const char* name) {
+    if (!t || (n && (!d_keys || !d_out || !d_slots_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (t->optimizer == MEE_OPT_NONE) return find_or_insert_common(t, d_keys, n, d_out, d_found, stream, true, name, d_slots_out, out_dtype);
+    if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
+    if (int rc = check_batch(t, n, name, stream, true, false)) return rc;   // (refuses while another prepared apply is pending)
     if (n == 0) return MEE_OK;
     uint8_t* fmask = d_found ? d_found : t->bs.fmask;
     // pass 1: the training forward's launch (located find of the stored keys + the partition of the backward); pass 2: the missing positions
     // claim their keys and write the initial rows (table, d_out) and the slot handles, as in mee_find_or_insert_located — it touches none of the
     // scratch the partition left for the apply, and the partition depends on the batch's keys alone
-    if (int rc = mee_find_located_prepare(t, d_keys, n, d_out, fmask, d_slots_out, stream)) return rc;
+    if (int rc = find_located_prepare(t, d_keys, n, d_out, out_dtype, fmask, d_slots_out, stream, name)) return rc;
     DeviceGuard g(t->device);
-    ensure_direct_kernel<64><<<grid_for(n, 256, 8192), 256, 0, as_stream(stream)>>>(t->keys, (float4*)t->values, (float4*)t->s1, (float4*)t->s2, t->nb, t->dim4,
-                                                                d_keys, (uint32_t)n, fmask, t->optimizer, t->init_acc, t->initializer, t->init_scale,
-                                                                t->init_seed, t->default_value, t->ctr, t->hits, (float4*)d_out, (long long*)d_slots_out, (long long)handle_tag_of(t));
+    launch_ensure(t, d_keys, (uint32_t)n, fmask, d_out, out_dtype, d_slots_out, as_stream(stream));
     MEE_HIP(hipGetLastError());
     return MEE_OK;
+}
+int mee_find_or_insert_located_prepare(mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, int64_t* d_slots_out, void* stream) {
+    MEE_RANGE("mee_find_or_insert_located_prepare");
+    return find_or_insert_located_prepare(t, d_keys, n, d_out, MEE_DTYPE_F32, d_found, d_slots_out, stream, "mee_find_or_insert_located_prepare");
+}
+int mee_find_or_insert_located_prepare_as(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out, void* stream) {
+    MEE_RANGE("mee_find_or_insert_located_prepare_as");
+    return find_or_insert_located_prepare(t, d_keys, n, d_out, out_dtype, d_found, d_slots_out, stream, "mee_find_or_insert_located_prepare_as");
 }
 
 int mee_apply_discard(mee_table* t, void* stream) {

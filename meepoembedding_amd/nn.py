@@ -29,6 +29,21 @@ _LAYERS: "weakref.WeakValueDictionary[int, DynamicEmbedding]" = weakref.WeakValu
 _IDS = itertools.count(1)
 
 
+def _check_out_dtype(table, out_dtype: torch.dtype) -> torch.dtype:
+    """A layer's out_dtype: fp32, or bf16 where the table's lookups can write it (LookupTable, TableGroup).  Refused at construction."""
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16 (got {out_dtype})")
+    if out_dtype != torch.float32 and not getattr(table, "supports_out_dtype", False):
+        raise ValueError(f"{type(table).__name__} has no bf16 lookup (tiered, sharded and peer-mapped tables return fp32 rows): use out_dtype=torch.float32 and "
+                         "cast in the model")
+    return out_dtype
+
+
+def _dtype_kw(layer) -> dict:
+    """the lookup's out_dtype keyword — only when it is not the default, so tables without the keyword keep working at fp32"""
+    return {} if layer.out_dtype == torch.float32 else {"out_dtype": layer.out_dtype}
+
+
 def _layer(table_id: int) -> "DynamicEmbedding":
     try:
         return _LAYERS[table_id]
@@ -73,7 +88,7 @@ def _setup(ctx, inputs, output):
 
 def _backward(ctx, grad_out):
     (keys,) = ctx.saved_tensors
-    apply_grad(keys, grad_out.contiguous(), ctx.table_id)
+    apply_grad(keys, grad_out.contiguous().to(torch.float32), ctx.table_id)
     return None, None, None, None
 
 
@@ -94,7 +109,8 @@ def lookup_located(keys: torch.Tensor, anchor: torch.Tensor, table_id: int, inse
         table.apply_discard()
         table._nn_prepared = None
     prepare = prepare and flat.is_contiguous() and flat.numel() > 0 and flat.numel() <= table.max_batch
-    rows, _, slots = (table.find_or_insert_located(flat, prepare_apply=prepare) if insert_missing else table.find_located(flat, prepare_apply=prepare))
+    rows, _, slots = (table.find_or_insert_located(flat, prepare_apply=prepare, **_dtype_kw(layer)) if insert_missing
+                      else table.find_located(flat, prepare_apply=prepare, **_dtype_kw(layer)))
     if prepare:
         table._nn_prepared = (flat.data_ptr(), flat.numel())
     return rows.reshape(*keys.shape, table.dim), slots   # fresh tensors: nothing aliases the table
@@ -102,7 +118,8 @@ def lookup_located(keys: torch.Tensor, anchor: torch.Tensor, table_id: int, inse
 
 @lookup_located.register_fake
 def _(keys, anchor, table_id, insert_missing, prepare=False):
-    return keys.new_empty((*keys.shape, _layer(table_id).table.dim), dtype=torch.float32), keys.new_empty(keys.numel())
+    layer = _layer(table_id)
+    return keys.new_empty((*keys.shape, layer.table.dim), dtype=layer.out_dtype), keys.new_empty(keys.numel())
 
 
 @torch.library.custom_op("meepo::apply_grad_located", mutates_args=())
@@ -141,7 +158,7 @@ def _backward_located(ctx, grad_out, _grad_located):
     keys, located = ctx.saved_tensors
     if getattr(_layer(ctx.table_id).table, "layout_epoch", None) != ctx.layout_epoch:
         located = located.new_empty(0)   # the table changed between forward and backward: the apply probes for itself
-    apply_grad_located(keys, grad_out.contiguous(), located, ctx.table_id)
+    apply_grad_located(keys, grad_out.contiguous().to(torch.float32), located, ctx.table_id)   # a bf16 layer's grad is widened (exact): the step is the fp32 step
     return None, None, None, None, None
 
 
@@ -163,16 +180,16 @@ def lookup_pooled(keys: torch.Tensor, bag_offsets: torch.Tensor, anchor: torch.T
             layer.table.find_or_insert(keys)
     if hasattr(layer.table, "apply_pooled"):   # a TableGroup
         located = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
-        out, _ = layer.table.find_pooled(keys, bag_offsets, "mean" if mean else "sum", located=located)
+        out, _ = layer.table.find_pooled(keys, bag_offsets, "mean" if mean else "sum", located=located, **_dtype_kw(layer))
         return out, located
-    out, _ = layer.table.find_pooled(keys, bag_offsets, "mean" if mean else "sum")
+    out, _ = layer.table.find_pooled(keys, bag_offsets, "mean" if mean else "sum", **_dtype_kw(layer))
     return out, keys.new_empty(0)
 
 
 @lookup_pooled.register_fake
 def _(keys, bag_offsets, anchor, table_id, mean):
     layer = _layer(table_id)
-    return (keys.new_empty((bag_offsets.numel() - 1, layer.table.dim), dtype=torch.float32),
+    return (keys.new_empty((bag_offsets.numel() - 1, layer.table.dim), dtype=layer.out_dtype),
             keys.new_empty(keys.numel() if hasattr(layer.table, "apply_pooled") else 0))
 
 
@@ -213,7 +230,7 @@ def _backward_pooled(ctx, grad_out, _grad_located):
     keys, bag_offsets, located = ctx.saved_tensors
     if getattr(_layer(ctx.table_id).table, "layout_epoch", None) != ctx.layout_epoch:
         located = located.new_empty(0)   # a table changed between forward and backward: the apply probes for itself
-    apply_grad_pooled(keys, bag_offsets, grad_out.contiguous(), located, ctx.table_id, ctx.mean)
+    apply_grad_pooled(keys, bag_offsets, grad_out.contiguous().to(torch.float32), located, ctx.table_id, ctx.mean)   # widened BEFORE the mean's division
     return None, None, None, None, None
 
 
@@ -235,13 +252,14 @@ def lookup_pooled_weighted(keys: torch.Tensor, bag_offsets: torch.Tensor, weight
         else:
             layer.table.find_or_insert(keys)
     located = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
-    out, _ = layer.table.find_pooled(keys, bag_offsets, "sum", weights=weights.contiguous(), located=located)
+    out, _ = layer.table.find_pooled(keys, bag_offsets, "sum", weights=weights.contiguous(), located=located, **_dtype_kw(layer))
     return out, located
 
 
 @lookup_pooled_weighted.register_fake
 def _(keys, bag_offsets, weights, anchor, table_id):
-    return (keys.new_empty((bag_offsets.numel() - 1, _layer(table_id).table.dim), dtype=torch.float32), keys.new_empty(keys.numel()))
+    layer = _layer(table_id)
+    return (keys.new_empty((bag_offsets.numel() - 1, layer.table.dim), dtype=layer.out_dtype), keys.new_empty(keys.numel()))
 
 
 @torch.library.custom_op("meepo::apply_grad_pooled_weighted", mutates_args=())
@@ -280,7 +298,7 @@ def _backward_pooled_weighted(ctx, grad_out, _grad_located):
     keys, bag_offsets, weights, located = ctx.saved_tensors
     if getattr(_layer(ctx.table_id).table, "layout_epoch", None) != ctx.layout_epoch:
         located = located.new_empty(0)   # a table changed between forward and backward: the backward probes for itself
-    wg = apply_grad_pooled_weighted(keys, bag_offsets, weights, grad_out.contiguous(), located, ctx.table_id, ctx.needs_input_grad[2])
+    wg = apply_grad_pooled_weighted(keys, bag_offsets, weights, grad_out.contiguous().to(torch.float32), located, ctx.table_id, ctx.needs_input_grad[2])
     return None, None, (wg.view(weights.shape) if ctx.needs_input_grad[2] else None), None, None
 
 
@@ -291,13 +309,14 @@ lookup_pooled_weighted.register_autograd(_backward_pooled_weighted, setup_contex
 @torch.library.custom_op("meepo::lookup_jagged", mutates_args=())
 def lookup_jagged(keys: torch.Tensor, offsets: torch.Tensor, anchor: torch.Tensor, table_id: int, insert_missing: bool) -> torch.Tensor:
     layer = _layer(table_id)
-    rows, _ = layer.group.find_or_insert(keys, offsets) if insert_missing else layer.group.find(keys, offsets)
+    rows, _ = layer.group.find_or_insert(keys, offsets, **_dtype_kw(layer)) if insert_missing else layer.group.find(keys, offsets, **_dtype_kw(layer))
     return rows
 
 
 @lookup_jagged.register_fake
 def _(keys, offsets, anchor, table_id, insert_missing):
-    return keys.new_empty((keys.numel(), _layer(table_id).group.dim), dtype=torch.float32)
+    layer = _layer(table_id)
+    return keys.new_empty((keys.numel(), layer.group.dim), dtype=layer.out_dtype)
 
 
 @torch.library.custom_op("meepo::apply_grad_jagged", mutates_args=())
@@ -324,7 +343,7 @@ def _setup_jagged(ctx, inputs, output):
 
 def _backward_jagged(ctx, grad_out):
     keys, offsets = ctx.saved_tensors
-    apply_grad_jagged(keys, offsets, grad_out.contiguous(), ctx.table_id)
+    apply_grad_jagged(keys, offsets, grad_out.contiguous().to(torch.float32), ctx.table_id)
     return None, None, None, None, None
 
 
@@ -332,9 +351,10 @@ lookup_jagged.register_autograd(_backward_jagged, setup_context=_setup_jagged)
 
 
 class _SparseOptimizerSettings:
-    def _init_settings(self, optimizer, lr, eps, betas):
+    def _init_settings(self, optimizer, lr, eps, betas, table=None, out_dtype: torch.dtype = torch.float32):
         if optimizer not in ("adagrad", "adam"):
             raise ValueError("optimizer must be 'adagrad' or 'adam'")
+        self.out_dtype = _check_out_dtype(table, out_dtype)
         self.optimizer, self.lr, self.betas = optimizer, lr, betas
         self.eps = eps if eps is not None else (1e-10 if optimizer == "adagrad" else 1e-8)
         self.step = 0
@@ -347,12 +367,14 @@ class _SparseOptimizerSettings:
 class DynamicEmbeddingCollection(torch.nn.Module, _SparseOptimizerSettings):
     """All embedding tables of a model behind one module: keys = the tables' id batches concatenated, offsets = the
     n_tables + 1 segment bounds (int64, on the device) -> fp32 [len(keys), dim].  Forward is ONE grouped find_or_insert
-    (find in eval mode), backward ONE grouped optimizer step, whatever the number of tables (TableGroup in table.py)."""
+    (find in eval mode), backward ONE grouped optimizer step, whatever the number of tables (TableGroup in table.py).
+    out_dtype=torch.bfloat16: the lookup itself writes bf16 rows (the tables stay fp32; a bf16 grad is widened, which is exact)."""
 
-    def __init__(self, group, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999)):
+    def __init__(self, group, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
+                 out_dtype: torch.dtype = torch.float32):
         super().__init__()
         self.group = group
-        self._init_settings(optimizer, lr, eps, betas)
+        self._init_settings(optimizer, lr, eps, betas, group, out_dtype)
 
     def forward(self, keys: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
         return lookup_jagged(keys, offsets, self._anchor, self.table_id, self.training)
@@ -366,12 +388,13 @@ class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
     hashed initial row first (one more pass over the ids); otherwise absent ids read the default row and are not trained."""
 
     def __init__(self, table, mode: str = "sum", optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
-                 create_missing: bool = False):
+                 create_missing: bool = False, out_dtype: torch.dtype = torch.float32):
+        """out_dtype=torch.bfloat16: the bag is accumulated in fp32 and the finished row rounded once by the lookup; backward widens the bf16 grad."""
         super().__init__()
         if mode not in ("sum", "mean"):
             raise ValueError("mode must be 'sum' or 'mean'")
         self.table, self.mode, self.create_missing = table, mode, create_missing
-        self._init_settings(optimizer, lr, eps, betas)
+        self._init_settings(optimizer, lr, eps, betas, table, out_dtype)
 
     def forward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, per_sample_weights: torch.Tensor | None = None) -> torch.Tensor:
         """per_sample_weights (fp32 [n], mode "sum" only): the bag is the sum of w_i * row_i; backward also yields their grad.
@@ -384,12 +407,16 @@ class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
 
 
 class DynamicEmbedding(torch.nn.Module):
-    """ids (any int64 tensor) -> fp32 [..., dim].  The table must have been created with the matching optimizer planes."""
+    """ids (any int64 tensor) -> fp32 [..., dim].  The table must have been created with the matching optimizer planes.
+    out_dtype=torch.bfloat16 (a LookupTable in HBM only): the lookup writes bf16 rows — what `.to(torch.bfloat16)` on the fp32 rows would give —
+    and backward widens the bf16 grad before the table's fp32 step."""
 
-    def __init__(self, table, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999)):
+    def __init__(self, table, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
+                 out_dtype: torch.dtype = torch.float32):
         super().__init__()
         if optimizer not in ("adagrad", "adam"):
             raise ValueError("optimizer must be 'adagrad' or 'adam'")
+        self.out_dtype = _check_out_dtype(table, out_dtype)
         self.table, self.optimizer, self.lr, self.betas = table, optimizer, lr, betas
         self.eps = eps if eps is not None else (1e-10 if optimizer == "adagrad" else 1e-8)
         self.step = 0

@@ -31,8 +31,28 @@ def _check_weights(weights: torch.Tensor, mode: str, n: int, device: torch.devic
     return weights.view(-1)
 
 
+_OUT_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16}
+
+
+def _out_dtype(out_dtype: torch.dtype, out: torch.Tensor | None = None) -> int:
+    """MEE_DTYPE_* of a lookup's result rows (SPEC.md §3 "Output type"); a caller's `out` must have that dtype.  Checked before any launch."""
+    if out_dtype not in _OUT_DTYPES:
+        raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16 (got {out_dtype}): the lookups write fp32 rows or their bf16 rounding")
+    if out is not None and out.dtype != out_dtype:
+        raise ValueError(f"out has dtype {out.dtype} but out_dtype is {out_dtype}")
+    return _OUT_DTYPES[out_dtype]
+
+
+def _fp32_only(out: torch.Tensor | None, op: str) -> None:
+    """operators without a bf16 form say so instead of writing fp32 bytes into a bf16 buffer"""
+    if out is not None and out.dtype != torch.float32:
+        raise ValueError(f"{op} returns fp32 rows only (out has dtype {out.dtype}); bf16 output exists for find, find_located, find_or_insert, "
+                         "find_or_insert_located, find_pooled and the TableGroup lookups")
+
+
 class LookupTable:
     """One HBM-resident shard: int64 key -> fp32[dim] row (+ optimizer state planes)."""
+    supports_out_dtype = True   # its lookups can write bf16 rows (out_dtype=torch.bfloat16); the tiered / sharded / peer tables cannot
 
     def __init__(self, capacity: int, dim: int, *, device: int | torch.device = 0, optimizer: int = OPT_NONE,
                  max_batch: int = 1 << 20, default_value: float = 0.0, initial_accumulator: float = 0.0,
@@ -94,18 +114,26 @@ class LookupTable:
 
     # -- operators (SPEC.md §3) ----------------------------------------------------------------------------
     def find(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
-             want_found: bool = True, unordered: bool = False, flags: int | None = None):
+             want_found: bool = True, unordered: bool = False, flags: int | None = None, out_dtype: torch.dtype = torch.float32):
         """unordered=True (mee_find_unordered): the launch is not ordered behind EARLIER work of the current stream — only for independent
         requests whose keys are complete and whose output buffers nothing earlier in the stream still touches.
-        flags (mee_find_ex): this call's cache policy, an OR of _lib.FIND_* — e.g. FIND_STREAM_STORES for result buffers that rotate."""
+        flags (mee_find_ex): this call's cache policy, an OR of _lib.FIND_* — e.g. FIND_STREAM_STORES for result buffers that rotate.
+        out_dtype=torch.bfloat16 (mee_find_as): the rows rounded once to bf16 by the lookup itself (SPEC.md §3 "Output type")."""
         if flags is not None and unordered:
             raise ValueError("find(flags=..., unordered=True): mee_find_ex and mee_find_unordered are separate entry points; pass one of the two")
+        dt = _out_dtype(out_dtype, out)
+        if dt != _lib.DTYPE_F32 and unordered:
+            raise ValueError("find(unordered=True) has no bf16 form: mee_find_unordered returns fp32 rows")
         k = self._keys(keys)
         n = k.numel()
         if out is None:
-            out = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
+            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
         if found is None and want_found:
             found = torch.empty(n, dtype=torch.uint8, device=self.device)
+        if dt != _lib.DTYPE_F32:
+            check(_lib.lib().mee_find_as(self._h, k.data_ptr(), n, out.data_ptr(), dt, found.data_ptr() if found is not None else None,
+                                         int(flags or 0), self._s()))
+            return out, found
         if flags is not None:
             check(_lib.lib().mee_find_ex(self._h, k.data_ptr(), n, out.data_ptr(), found.data_ptr() if found is not None else None, int(flags), self._s()))
             return out, found
@@ -119,6 +147,7 @@ class LookupTable:
         reqs, res = (_lib.FindRequest * len(requests))(), []
         for q, r in enumerate(requests):
             keys, out, found = (r if isinstance(r, tuple) else (r, None, None))
+            _fp32_only(out, "find_many")
             k = self._keys(keys)
             n = k.numel()
             if out is None:
@@ -137,11 +166,14 @@ class LookupTable:
         return bag_offsets.numel() - 1
 
     def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
-                    found: torch.Tensor | None = None, weights: torch.Tensor | None = None, located: torch.Tensor | None = None):
+                    found: torch.Tensor | None = None, weights: torch.Tensor | None = None, located: torch.Tensor | None = None,
+                    out_dtype: torch.dtype = torch.float32):
         """Embedding-bag lookup: bag b = keys[bag_offsets[b]:bag_offsets[b+1]] (int64 offsets on the device) -> ([n_bags, dim]
         sums or means in position order, per-key found mask).  One output row per bag is written instead of one per key.
         weights (fp32 [n], mee_find_pooled_weighted; mode "sum" only): the bag is the sum of weights[i] * row_i.  located (int64[n]
-        buffer, weighted form only) receives each key's slot handle for pooled_weighted_backward / apply_*(slots=...) of the same step."""
+        buffer, weighted form only) receives each key's slot handle for pooled_weighted_backward / apply_*(slots=...) of the same step.
+        out_dtype=torch.bfloat16 (mee_find_pooled_as): the bag is accumulated in fp32 as always and the finished row rounded once."""
+        dt = _out_dtype(out_dtype, out)
         k = self._keys(keys) if keys.numel() else keys
         n_bags = self._bag_offsets(bag_offsets)
         if weights is not None:
@@ -152,9 +184,14 @@ class LookupTable:
                                     or not located.is_contiguous()):
             raise MeepoError(_lib.ERR_INVALID_ARG, f"located must be a contiguous int64 buffer of {k.numel()} entries on {self.device}")
         if out is None:
-            out = torch.empty((n_bags, self.dim), dtype=torch.float32, device=self.device)
+            out = torch.empty((n_bags, self.dim), dtype=out_dtype, device=self.device)
         if found is None:
             found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
+        if dt != _lib.DTYPE_F32:
+            check(_lib.lib().mee_find_pooled_as(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), n_bags, w.data_ptr() if weights is not None else None,
+                                                out.data_ptr(), dt, found.data_ptr(), located.data_ptr() if located is not None else None,
+                                                {"sum": 0, "mean": 1}[mode], self._s()))
+            return out, found
         if weights is not None:
             check(_lib.lib().mee_find_pooled_weighted(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), n_bags, w.data_ptr(), out.data_ptr(),
                                                       found.data_ptr(), located.data_ptr() if located is not None else None, self._s()))
@@ -186,12 +223,14 @@ class LookupTable:
 
     def find_missing(self, keys: torch.Tensor, out: torch.Tensor, found: torch.Tensor) -> None:
         """Second-tier pass: fill the positions an earlier find (on another table) left with found == 0."""
+        _fp32_only(out, "find_missing")
         k = self._keys(keys)
         check(_lib.lib().mee_find_missing(self._h, k.data_ptr(), k.numel(), out.data_ptr(), found.data_ptr(), self._s()))
 
     def find_counted(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
                      missing_only: bool = False):
         """find (or find_missing) that also bumps the hit counter of every key it finds (track_hits tables)."""
+        _fp32_only(out, "find_counted")
         k = self._keys(keys)
         n = k.numel()
         if out is None:
@@ -221,6 +260,7 @@ class LookupTable:
 
     def find_or_insert_missing(self, keys: torch.Tensor, out: torch.Tensor, found: torch.Tensor) -> None:
         """find_or_insert restricted to the positions with found == 0; rows of those positions are written into out."""
+        _fp32_only(out, "find_or_insert_missing")
         k = self._keys(keys)
         check(_lib.lib().mee_find_or_insert_missing(self._h, k.data_ptr(), k.numel(), out.data_ptr(), found.data_ptr(), self._s()))
 
@@ -255,36 +295,49 @@ class LookupTable:
         return found
 
     def find_or_insert(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
-                       min_count: int | None = None):
+                       min_count: int | None = None, out_dtype: torch.dtype = torch.float32):
         """min_count (tables created with admission=True): an absent key is created only once the table's count-min sketch has seen it
-        requested at least min_count times (this batch included); until then its positions return the default row."""
+        requested at least min_count times (this batch included); until then its positions return the default row.
+        out_dtype=torch.bfloat16 (mee_find_or_insert_as): only the returned copy is rounded, the table's rows are created in fp32."""
+        dt = _out_dtype(out_dtype, out)
+        if dt != _lib.DTYPE_F32 and min_count is not None:
+            raise ValueError("find_or_insert(min_count=...) has no bf16 form: mee_find_or_insert_admit returns fp32 rows")
         k = self._keys(keys)
         n = k.numel()
         if out is None:
-            out = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
+            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
         if found is None:
             found = torch.empty(n, dtype=torch.uint8, device=self.device)
-        if min_count is not None:
+        if dt != _lib.DTYPE_F32:
+            check(_lib.lib().mee_find_or_insert_as(self._h, k.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(), self._s()))
+        elif min_count is not None:
             check(_lib.lib().mee_find_or_insert_admit(self._h, k.data_ptr(), n, out.data_ptr(), found.data_ptr(), int(min_count), self._s()))
         else:
             check(_lib.lib().mee_find_or_insert(self._h, k.data_ptr(), n, out.data_ptr(), found.data_ptr(), self._s()))
         return out, found
 
     def find_or_insert_located(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
-                               slots: torch.Tensor | None = None, prepare_apply: bool = False):
+                               slots: torch.Tensor | None = None, prepare_apply: bool = False, out_dtype: torch.dtype = torch.float32):
         """find_or_insert() that also returns where every key lives now (-1: reserved key / table full): the handles for
         apply_*(…, slots=…) of the same training step — the forward of a step over a growing vocabulary.
         prepare_apply: as in find_located — the launch also partitions the batch for the apply of the SAME `keys` tensor that must follow."""
+        return self._located(keys, out, found, slots, out_dtype, "mee_find_or_insert_located_prepare" if prepare_apply else "mee_find_or_insert_located")
+
+    def _located(self, keys, out, found, slots, out_dtype, fn: str):
+        """the four located lookups: (rows, found, slot handles); bf16 rows through the entry point's typed form (fn + "_as")"""
+        dt = _out_dtype(out_dtype, out)
         k = self._keys(keys)
         n = k.numel()
         if out is None:
-            out = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
+            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
         if found is None:
             found = torch.empty(n, dtype=torch.uint8, device=self.device)
         if slots is None:
             slots = torch.empty(n, dtype=torch.int64, device=self.device)
-        fn = _lib.lib().mee_find_or_insert_located_prepare if prepare_apply else _lib.lib().mee_find_or_insert_located
-        check(fn(self._h, k.data_ptr(), n, out.data_ptr(), found.data_ptr(), slots.data_ptr(), self._s()))
+        if dt != _lib.DTYPE_F32:
+            check(getattr(_lib.lib(), fn + "_as")(self._h, k.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(), slots.data_ptr(), self._s()))
+        else:
+            check(getattr(_lib.lib(), fn)(self._h, k.data_ptr(), n, out.data_ptr(), found.data_ptr(), slots.data_ptr(), self._s()))
         return out, found, slots
 
     def admission_decay(self, shift: int = 1) -> None:
@@ -456,21 +509,11 @@ class LookupTable:
         return slots.contiguous()
 
     def find_located(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
-                     slots: torch.Tensor | None = None, prepare_apply: bool = False):
+                     slots: torch.Tensor | None = None, prepare_apply: bool = False, out_dtype: torch.dtype = torch.float32):
         """find() that also returns each key's slot handle (-1 = absent) for apply_*(…, slots=…) of the same training step.
         prepare_apply: the training forward (mee_find_located_prepare) — the launch also partitions the batch for the apply of the SAME
         `keys` tensor that must follow (its grad-independent half runs beside the row gather)."""
-        k = self._keys(keys)
-        n = k.numel()
-        if out is None:
-            out = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
-        if found is None:
-            found = torch.empty(n, dtype=torch.uint8, device=self.device)
-        if slots is None:
-            slots = torch.empty(n, dtype=torch.int64, device=self.device)
-        fn = _lib.lib().mee_find_located_prepare if prepare_apply else _lib.lib().mee_find_located
-        check(fn(self._h, k.data_ptr(), n, out.data_ptr(), found.data_ptr(), slots.data_ptr(), self._s()))
-        return out, found, slots
+        return self._located(keys, out, found, slots, out_dtype, "mee_find_located_prepare" if prepare_apply else "mee_find_located")
 
     def apply_adagrad(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10,
                       grad_index: torch.Tensor | None = None, slots: torch.Tensor | None = None) -> None:
@@ -554,6 +597,7 @@ class TableGroup:
 
     keys = the tables' key batches concatenated, offsets = n_tables + 1 int64/uint64 bounds ON THE DEVICE (segment j =
     keys[offsets[j]:offsets[j+1]]).  Returns (rows [n, dim], found [n]) — identical to find() per table."""
+    supports_out_dtype = True
 
     def __init__(self, tables, max_apply_batch: int = 0):
         self.tables = list(tables)
@@ -617,16 +661,24 @@ class TableGroup:
         return nb // len(self.tables)
 
     def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
-                    found: torch.Tensor | None = None, located: torch.Tensor | None = None, weights: torch.Tensor | None = None):
+                    found: torch.Tensor | None = None, located: torch.Tensor | None = None, weights: torch.Tensor | None = None,
+                    out_dtype: torch.dtype = torch.float32):
         """find_pooled of every member in one launch -> ([n_tables * bags_per_table, dim], per-key found mask).
         located (optional int64[n] buffer) receives the located rows for apply_pooled(located=...) of the same step.
         weights (fp32 [n], mode "sum" only): the weighted form, LookupTable.find_pooled(weights=...) per member."""
+        dt = _out_dtype(out_dtype, out)
         bpt = self._check_bags(bag_offsets)
         k = self.tables[0]._keys(keys) if keys.numel() else keys
         if out is None:
-            out = torch.empty((bpt * len(self.tables), self.dim), dtype=torch.float32, device=self.device)
+            out = torch.empty((bpt * len(self.tables), self.dim), dtype=out_dtype, device=self.device)
         if found is None:
             found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
+        if dt != _lib.DTYPE_F32:   # mee_group_find_pooled_as: the finished bag rows rounded once to bf16
+            w = _check_weights(weights, mode, k.numel(), self.device) if weights is not None else None
+            check(_lib.lib().mee_group_find_pooled_as(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), bpt, w.data_ptr() if w is not None else None,
+                                                      out.data_ptr(), dt, found.data_ptr(), located.data_ptr() if located is not None else None,
+                                                      {"sum": 0, "mean": 1}[mode], _stream_ptr(self.device)))
+            return out, found
         if weights is not None:
             w = _check_weights(weights, mode, k.numel(), self.device)
             check(_lib.lib().mee_group_find_pooled_weighted(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), bpt, w.data_ptr(), out.data_ptr(),
@@ -675,21 +727,28 @@ class TableGroup:
                                                             weight_grads.data_ptr() if weight_grads is not None else None, _stream_ptr(self.device)))
         return grads, weight_grads
 
-    def find_or_insert(self, keys: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None):
+    def find_or_insert(self, keys: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
+                       out_dtype: torch.dtype = torch.float32):
         """find that first creates absent keys in their member table (initial row / state); found = present before."""
-        return self.find(keys, offsets, out, found, _fn="mee_group_find_or_insert")
+        return self.find(keys, offsets, out, found, _fn="mee_group_find_or_insert", out_dtype=out_dtype)
 
     def find(self, keys: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
-             _fn: str = "mee_find_grouped"):
+             _fn: str = "mee_find_grouped", out_dtype: torch.dtype = torch.float32):
+        """out_dtype=torch.bfloat16 (mee_find_grouped_as / mee_group_find_or_insert_as): LookupTable.find(out_dtype=...) per member."""
+        dt = _out_dtype(out_dtype, out)
         k = self.tables[0]._keys(keys) if keys.numel() else keys
         n = k.numel()
         self._check_offsets(offsets)
         if out is None:
-            out = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
+            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
         if found is None:
             found = torch.empty(n, dtype=torch.uint8, device=self.device)
-        check(getattr(_lib.lib(), _fn)(self._h, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), found.data_ptr(),
-                                       _stream_ptr(self.device)))
+        if dt != _lib.DTYPE_F32:
+            check(getattr(_lib.lib(), _fn + "_as")(self._h, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(),
+                                                   _stream_ptr(self.device)))
+        else:
+            check(getattr(_lib.lib(), _fn)(self._h, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), found.data_ptr(),
+                                           _stream_ptr(self.device)))
         return out, found
 
 
