@@ -338,7 +338,10 @@ int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, cons
  *                                            (nullable) is the weighted form's output
  *   mee_group_find_pooled_as                 d_weights nullable (non-null: mee_group_find_pooled_weighted)
  * No typed form exists for find_missing / find_counted / find_plane / find_many / find_unordered / find_or_insert_admit /
- * find_or_insert_missing, the mee_sharded_* and mee_p2p_* lookups and mee_export: they return fp32.  Gradients handed to mee_apply_* are fp32. */
+ * find_or_insert_missing, the mee_p2p_* lookups and mee_export: they return fp32.  Gradients handed to mee_apply_* are fp32.
+ * The sharded lookups have typed forms of their own, mee_sharded_find_as / mee_sharded_find_or_insert_as (declared with the other mee_sharded_*
+ * operators): there the OWNER of a key rounds its row, before the rows travel — a lookup then puts 8 + 2·dim + 1 bytes on the wire (key out, bf16
+ * row and found byte back) instead of 8 + 4·dim + 1: 137 instead of 265 B at dim 64. */
 enum { MEE_DTYPE_F32 = 0, MEE_DTYPE_BF16 = 1 };
 int mee_find_as(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, uint32_t flags, void* stream);
 int mee_find_located_as(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out,
@@ -535,6 +538,24 @@ int mee_sharded_destroy(mee_sharded* s);
 int mee_sharded_info(const mee_sharded* s, uint32_t* n_shards, uint32_t* rank, uint64_t* segment_capacity /* 0 = exact layout */);
 int mee_sharded_find(mee_sharded* s, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found /* nullable */, void* stream);
 int mee_sharded_find_or_insert(mee_sharded* s, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream);
+/* The two lookups with fp32 OR bf16 result rows (MEE_DTYPE_*, "typed output" above).  MEE_DTYPE_F32: they ARE mee_sharded_find /
+ * mee_sharded_find_or_insert, bit for bit and byte for byte on the wire.  MEE_DTYPE_BF16: d_out is [n, dim] bf16, 8-byte aligned; the result is
+ * the fp32 result of the same call with every element rounded once to bf16 — by the key's OWNER, before the rows travel, so the rows leg of the
+ * way back carries 2·dim bytes per key instead of 4·dim and no fp32 row crosses the link (a tiered shard rounds after its two fp32 tier passes).
+ * d_found, the status bits, the table after a find_or_insert and the keys an overflowing padded segment drops are those of the fp32 call;
+ * dropped keys get bf16(default_value) and found = 0.  COLLECTIVE like every mee_sharded_* operator, and every rank passes the SAME out_dtype
+ * to a given call: a mismatch is a message-size mismatch between the two ends of a send/receive pair.  fp32 and bf16 calls may alternate freely
+ * on one context. */
+int mee_sharded_find_as(mee_sharded* s, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found /* nullable */, void* stream);
+int mee_sharded_find_or_insert_as(mee_sharded* s, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, void* stream);
+/* Bytes this context has handed to ncclSend / ncclRecv since it was created (either pointer nullable): a host-side counter, never synchronises.
+ * Counted: every message to or from ANOTHER rank — keys, payload rows, rows and found bytes on the way back, and the exact layout's counts
+ * exchange (8 B to and from every peer per operator).  Not counted: the segment a rank keeps for itself (a device copy) and the all-reduces of
+ * creation and mee_sharded_size.  One exact-layout lookup without MEE_SHARDED_DEDUP, with k_out of the rank's keys owned by other ranks, k_in
+ * keys arriving from other ranks and e = 4 (fp32) or 2 (bf16) bytes per element:
+ *     sent     = 8·k_out + (e·dim + 1)·k_in  + 8·(G - 1)
+ *     received = 8·k_in  + (e·dim + 1)·k_out + 8·(G - 1) */
+int mee_sharded_traffic(const mee_sharded* s, uint64_t* sent_bytes, uint64_t* received_bytes);
 int mee_sharded_insert(mee_sharded* s, const int64_t* d_keys, const float* d_values, size_t n, void* stream);
 int mee_sharded_assign(mee_sharded* s, const int64_t* d_keys, const float* d_values, size_t n, uint8_t* d_found, void* stream);
 int mee_sharded_remove(mee_sharded* s, const int64_t* d_keys, size_t n, uint8_t* d_found, void* stream);

@@ -279,6 +279,11 @@ public:
     ShardedTable& operator=(const ShardedTable&) = delete;
     void find(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_sharded_find(s_, d_keys, n, d_out, d_found, stream)); }
     void find_or_insert(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_sharded_find_or_insert(s_, d_keys, n, d_out, d_found, stream)); }
+    // the lookups with fp32 or bf16 result rows (MEE_DTYPE_*; bf16: the owner rounds, half the row bytes travel; the same out_dtype on every rank)
+    void find_as(const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_sharded_find_as(s_, d_keys, n, d_out, out_dtype, d_found, stream)); }
+    void find_or_insert_as(const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_sharded_find_or_insert_as(s_, d_keys, n, d_out, out_dtype, d_found, stream)); }
+    // bytes handed to ncclSend / ncclRecv since creation (host counters, no synchronisation)
+    void traffic(uint64_t* sent_bytes, uint64_t* received_bytes) const { check(mee_sharded_traffic(s_, sent_bytes, received_bytes)); }
     void insert(const int64_t* d_keys, const float* d_values, size_t n, void* stream = nullptr) { check(mee_sharded_insert(s_, d_keys, d_values, n, stream)); }
     void assign(const int64_t* d_keys, const float* d_values, size_t n, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_sharded_assign(s_, d_keys, d_values, n, d_found, stream)); }
     void remove(const int64_t* d_keys, size_t n, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_sharded_remove(s_, d_keys, n, d_found, stream)); }

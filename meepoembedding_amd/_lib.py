@@ -180,6 +180,9 @@ PROTOTYPES = {
     "mee_sharded_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u64)]),
     "mee_sharded_find": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "mee_sharded_find_or_insert": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "mee_sharded_find_as": (C.c_int, [_vp, _vp, _sz, _vp, _u32, _vp, _vp]),
+    "mee_sharded_find_or_insert_as": (C.c_int, [_vp, _vp, _sz, _vp, _u32, _vp, _vp]),
+    "mee_sharded_traffic": (C.c_int, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "mee_sharded_insert": (C.c_int, [_vp, _vp, _vp, _sz, _vp]),
     "mee_sharded_assign": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "mee_sharded_remove": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),

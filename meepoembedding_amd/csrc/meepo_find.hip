@@ -707,7 +707,7 @@ int find_plane(const mee_table* t, const float* plane, float miss_value, const i
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
     const unsigned fblock = t->find_block == 64 || t->find_block == 128 ? (unsigned)t->find_block : 256u;   // (launch bound of find_kernel: 256)
-    const bool bf16 = path.out_dtype == MEE_DTYPE_BF16;   // d_out holds bf16 rows (Plain and Located only: the entry points see to that)
+    const bool bf16 = path.out_dtype == MEE_DTYPE_BF16;   // d_out holds bf16 rows (Plain, Located and SkipPadding only: the entry points see to that)
     const uint64_t out_bytes = (uint64_t)n * t->dim * (bf16 ? 2 : 4);   // what the call really writes
     const int nt = path.nt >= 0 ? path.nt : t->find_nt >= 0 ? (t->find_nt & 7)
                  : (out_bytes <= kCachedOutputBytes && !outputs_rotate(t, d_out, out_bytes) ? 4 : 0);
@@ -726,6 +726,8 @@ int find_plane(const mee_table* t, const float* plane, float miss_value, const i
         if (path.kind == FindPath::Located) {   // (the store policy of the fp32 located find)
             const bool cached_out = t->find_nt >= 0 && (t->find_nt & 4);
             with_value<256 + 68, 256 + 64>(cached_out ? 256 + 68 : 256 + 64, [&](auto ntc) { find(ntc, path.slots_out, handle_tag_of(t)); });
+        } else if (path.kind == FindPath::SkipPadding) {   // owner pass of a padded sharded exchange whose rows travel as bf16 (the fp32 one's store policy)
+            with_value<256 + 132, 256 + 128>(nt & 4 ? 256 + 132 : 256 + 128, [&](auto ntc) { find(ntc, nullptr, 0); });
         } else {
             with_value<256, 257, 258, 259, 260, 261, 262, 263>(256 | nt, [&](auto ntc) { find(ntc, nullptr, 0); });
         }
@@ -805,10 +807,12 @@ int mee_find_as(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out
 }  // extern "C"
 namespace mee {
 // mee_find for the owner side of a padded sharded exchange (meepo_sharded.hip): MEE_EMPTY_KEY positions are padding that nobody reads —
-// they get neither a default row nor a found byte
-int find_skip_padding(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream) {
+// they get neither a default row nor a found byte.  out_dtype = MEE_DTYPE_BF16: d_out holds bf16 rows (the rows of a bf16 sharded lookup are
+// rounded here, on the owner, before they travel)
+int find_skip_padding(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint8_t* d_found, void* stream, uint32_t out_dtype) {
     if (!t || (n && (!d_keys || !d_out || !d_found))) return fail(MEE_ERR_INVALID_ARG, "find_skip_padding: null argument");
-    return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {FindPath::SkipPadding});
+    if (int rc = check_out_dtype(d_out, out_dtype, "find_skip_padding")) return rc;
+    return find_plane(t, t->values, t->default_value, d_keys, n, (float*)d_out, d_found, stream, {FindPath::SkipPadding, nullptr, -1, out_dtype});
 }
 }  // namespace mee
 extern "C" {

@@ -9,6 +9,10 @@
 //     the local table's operator on what arrived (ordered by source rank, then batch position: last-wins across ranks)
 //     rows + found bytes back to the requesters, ONE grouped exchange                -> un-permute kernel into batch order
 //
+// bf16 lookups (mee_sharded_find_as / mee_sharded_find_or_insert_as with MEE_DTYPE_BF16): the OWNER rounds every row once (SPEC.md §3 "Output
+// type") and bf16 rows travel — 8 + 2·dim + 1 bytes per lookup on the wire instead of 8 + 4·dim + 1 (137 against 265 B at dim 64); the
+// requester-side kernels move the 16-bit patterns unchanged, so nothing is rounded twice.  mee_sharded_traffic counts what a context sent.
+//
 // Two segment layouts:
 //   exact  (pad_slack = 0): a counts exchange (8 B per peer) and ONE host synchronisation give every message its exact size.
 //   padded (pad_slack > 0): every (source, owner) segment has the fixed capacity cap = max_batch / G * pad_slack + 1024 and is
@@ -34,6 +38,7 @@
 
 #include <dlfcn.h>
 
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -152,16 +157,23 @@ __global__ __launch_bounds__(256) void shard_pack_rows_kernel(const float4* __re
 // Padded layout: positions j >= cap of a segment were never sent (the segment overflowed: status bit 0): they get the default row and
 // found = 0 — a dropped lookup must not hand the caller uninitialised memory.  The owner's find skips MEE_EMPTY_KEY positions as padding
 // (no row, no found byte), so a reserved key the CALLER put into its batch is answered here, on the requester side, with the default row.
-__global__ __launch_bounds__(256) void shard_return_kernel(const float4* __restrict__ back_rows, const uint8_t* __restrict__ back_found,
+// BF16: the rows are bf16 — a row is dim4 8-byte groups (u32x2: 4 bf16) where the fp32 row is dim4 float4, same indices; a lane moves one group
+// per pass, bit for bit (the owner rounded them), and the default row is bf16(default_value).  An 8-byte access per lane runs below the 16-byte
+// rate per byte on this chip, so the kernel's time does not halve with its bytes; what halves is the rows leg on the link in front of it.
+template <bool BF16> struct RowGroup { using type = float4; };
+template <> struct RowGroup<true> { using type = u32x2; };
+template <bool BF16>
+__global__ __launch_bounds__(256) void shard_return_kernel(const typename RowGroup<BF16>::type* __restrict__ back_rows, const uint8_t* __restrict__ back_found,
                                                            const int64_t* __restrict__ perm, const uint64_t* __restrict__ counts,
-                                                           uint64_t cap /* 0 = exact */, uint32_t dim4, float4* __restrict__ out,
+                                                           uint64_t cap /* 0 = exact */, uint32_t dim4, typename RowGroup<BF16>::type* __restrict__ out,
                                                            uint8_t* __restrict__ found, float defv, const int64_t* __restrict__ send_keys) {
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint32_t p = blockIdx.y;
     const uint64_t cnt = counts[p], take = (cap && cnt > cap) ? cap : cnt, b0 = seg_base(counts, p);
     const uint64_t off = cap ? (uint64_t)p * cap : b0;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-    const float4 def4 = make_float4(defv, defv, defv, defv);
+    typename RowGroup<BF16>::type def4;
+    if constexpr (BF16) def4 = bf16x4_of(defv, defv, defv, defv); else def4 = make_float4(defv, defv, defv, defv);
     for (uint64_t j0 = wave * 4; j0 < cnt; j0 += n_waves * 4) {
         const uint64_t j = j0 + tile;
         if (j >= cnt) continue;
@@ -176,9 +188,11 @@ __global__ __launch_bounds__(256) void shard_return_kernel(const float4* __restr
 // pre-exchange dedup, last step: every occurrence takes the row of its distinct key: out[i] = urows[inverse[i]], found likewise
 // (four positions in flight per 16-lane tile: index, then row, then a streamed store — with one position per tile the kernel was a chain of two dependent loads per
 // row at 3.3 TB/s: 108 us per 1M dim-64 rows)
-__global__ __launch_bounds__(256) void shard_expand_kernel(const float4* __restrict__ urows, const uint8_t* __restrict__ ufound,
+// BF16: urows and out hold bf16 rows (8-byte groups, see shard_return_kernel): the same four positions in flight, the same streamed store.
+template <bool BF16>
+__global__ __launch_bounds__(256) void shard_expand_kernel(const typename RowGroup<BF16>::type* __restrict__ urows, const uint8_t* __restrict__ ufound,
                                                            const int64_t* __restrict__ inverse, uint64_t n, uint32_t dim4,
-                                                           float4* __restrict__ out, uint8_t* __restrict__ found) {
+                                                           typename RowGroup<BF16>::type* __restrict__ out, uint8_t* __restrict__ found) {
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
     for (uint64_t i0 = wave * 16; i0 < n; i0 += n_waves * 16) {
@@ -186,13 +200,14 @@ __global__ __launch_bounds__(256) void shard_expand_kernel(const float4* __restr
 #pragma unroll
         for (int q = 0; q < 4; ++q) { const uint64_t i = i0 + q * 4 + tile; u[q] = i < n ? (uint64_t)inverse[i] : 0ull; }
         for (uint32_t c = tl; c < dim4; c += 16) {
-            float4 r[4];
+            typename RowGroup<BF16>::type r[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) r[q] = urows[u[q] * dim4 + c];   // (cached loads: a skewed batch reads its hot rows many times)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const uint64_t i = i0 + q * 4 + tile;
-                if (i < n) __builtin_nontemporal_store(f32x4{r[q].x, r[q].y, r[q].z, r[q].w}, reinterpret_cast<f32x4*>(out) + i * dim4 + c);
+                if constexpr (BF16) { if (i < n) __builtin_nontemporal_store(r[q], out + i * dim4 + c); }
+                else if (i < n) __builtin_nontemporal_store(f32x4{r[q].x, r[q].y, r[q].z, r[q].w}, reinterpret_cast<f32x4*>(out) + i * dim4 + c);
             }
         }
         if (found && tl < 4) {   // lane tl of the tile: the found byte of the tile's position q = tl
@@ -208,6 +223,24 @@ __global__ void shard_or_kernel(uint8_t* __restrict__ a, const uint8_t* __restri
 __global__ void shard_fill_row_kernel(float* __restrict__ row, uint32_t dim, float v, uint8_t* found_byte) {
     for (uint32_t i = threadIdx.x; i < dim; i += blockDim.x) row[i] = v;
     if (threadIdx.x == 0) *found_byte = 0;
+}
+// the default row of the bf16 view of urows (row max_batch of [max_batch + 1][dim] bf16): it lies inside the fp32 view's row max_batch / 2, which
+// fp32 lookups and applies overwrite — every bf16 lookup of a dedup context writes it again before its expand kernel reads it
+__global__ void shard_fill_row_bf16_kernel(u32x2* __restrict__ row, uint32_t dim4, float v, uint8_t* found_byte) {
+    for (uint32_t i = threadIdx.x; i < dim4; i += blockDim.x) row[i] = bf16x4_of(v, v, v, v);
+    if (threadIdx.x == 0) *found_byte = 0;
+}
+// owner side of a bf16 lookup over a tiered shard: the tiers' fp32 passes (mee_find, mee_find_missing, mee_find_or_insert_missing share one fp32
+// buffer) are left as they are, then the n rows are rounded into the bf16 wire buffer — one 16-lane tile per row, a float4 in, 4 bf16 out.  Not in
+// place: bf16 row j overlaps fp32 row j / 2.  One more pass over rows of a path that PCIe bounds (the cold rows come from pinned host DRAM).
+__global__ __launch_bounds__(256) void shard_narrow_rows_kernel(const float4* __restrict__ rows, uint64_t n, uint32_t dim4, u32x2* __restrict__ wire) {
+    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t j0 = wave * 4; j0 < n; j0 += n_waves * 4) {
+        const uint64_t j = j0 + tile;
+        if (j >= n) continue;
+        for (uint32_t c = tl; c < dim4; c += 16) store_bf16x4<true>(wire, j * dim4 + c, rows[j * dim4 + c]);
+    }
 }
 // chunked apply: a key -> mix64(key), padding stays padding.  Partitioning the images by owner_of() splits a shard's arrivals by bits that
 // are independent of the bits that sent them to this shard.
@@ -261,6 +294,8 @@ struct mee_sharded {
     float* recv_rows;          // payload received / rows found
     uint8_t *recv_found, *recv_found2;   // second mask: the cold tier's answer (OR-ed into the first)
     uint32_t* status;          // device: bit 0 = a padded segment overflowed
+    void* wire_rows;           // tiered shard, bf16 lookups: the rows found (fp32, recv_rows) rounded for the way back (made by the first such call)
+    std::atomic<uint64_t> sent_bytes, recv_bytes;   // host counters of mee_sharded_traffic: bytes handed to ncclSend / ncclRecv
     // chunked apply (exact layout, arrivals beyond the local table's max_batch): made on first need
     mee_router* sub_router; uint32_t sub_chunks;
     int64_t *img_keys, *keys2, *perm2; uint64_t* counts2; float* rows2; uint64_t* h_counts2;
@@ -271,7 +306,7 @@ namespace mee {
 
 static void sharded_free(mee_sharded* c) {
     void* dev[] = {c->send_keys, c->perm, c->pad_keys, c->counts, c->d_recv_counts, c->send_rows, c->back_rows, c->back_found,
-                   c->recv_keys, c->recv_rows, c->recv_found, c->recv_found2, c->status, c->uniq, c->inverse, c->urows, c->ufound,
+                   c->recv_keys, c->recv_rows, c->recv_found, c->recv_found2, c->status, c->wire_rows, c->uniq, c->inverse, c->urows, c->ufound,
                    c->img_keys, c->keys2, c->perm2, c->counts2, c->rows2};
     for (void* p : dev) if (p) (void)hipFree(p);
     if (c->h_counts) (void)hipHostFree(c->h_counts);
@@ -284,6 +319,13 @@ static void sharded_free(mee_sharded* c) {
 static int ensure_send_rows(mee_sharded* c) {
     if (c->send_rows) return MEE_OK;
     MEE_HIP(hipMalloc((void**)&c->send_rows, c->send_slots * (uint64_t)c->dim * 4));
+    return MEE_OK;
+}
+
+// bf16 lookup of a tiered shard: the wire buffer, made BEFORE the call's first exchange step (no rank drops out for memory between two steps)
+static int ensure_wire_rows(mee_sharded* c) {
+    if (c->wire_rows) return MEE_OK;
+    MEE_HIP(hipMalloc(&c->wire_rows, c->recv_slots * (uint64_t)c->dim * 2));
     return MEE_OK;
 }
 
@@ -342,8 +384,8 @@ static int exchange(mee_sharded* c, const Leg* legs, int n_legs, bool reverse, h
         for (int l = 0; l < n_legs && first_err == ncclSuccess; ++l) {
             const size_t row = legs[l].elems * legs[l].elem_bytes;
             // zero-length messages are skipped on both sides (the two ends agree on every count)
-            if (sc[p]) first_err = api->Send((const char*)legs[l].send + sd[p] * row, sc[p] * legs[l].elems, legs[l].dt, (int)p, c->comm, st);
-            if (rc[p] && first_err == ncclSuccess) first_err = api->Recv((char*)legs[l].recv + rd[p] * row, rc[p] * legs[l].elems, legs[l].dt, (int)p, c->comm, st);
+            if (sc[p]) { first_err = api->Send((const char*)legs[l].send + sd[p] * row, sc[p] * legs[l].elems, legs[l].dt, (int)p, c->comm, st); c->sent_bytes += sc[p] * row; }
+            if (rc[p] && first_err == ncclSuccess) { first_err = api->Recv((char*)legs[l].recv + rd[p] * row, rc[p] * legs[l].elems, legs[l].dt, (int)p, c->comm, st); c->recv_bytes += rc[p] * row; }
         }
     }
     const ncclResult_t end_err = api->GroupEnd();
@@ -376,7 +418,8 @@ static int route(mee_sharded* c, const int64_t* d_keys, size_t n, hipStream_t st
         for (uint32_t p = 0; p < c->G && first_err == ncclSuccess; ++p) {
             if (p == c->rank) continue;
             first_err = api->Send(c->counts + p, 1, ncclUint64, (int)p, c->comm, st);
-            if (first_err == ncclSuccess) first_err = api->Recv(c->d_recv_counts + p, 1, ncclUint64, (int)p, c->comm, st);
+            c->sent_bytes += 8;
+            if (first_err == ncclSuccess) { first_err = api->Recv(c->d_recv_counts + p, 1, ncclUint64, (int)p, c->comm, st); c->recv_bytes += 8; }
         }
         const ncclResult_t end_err = api->GroupEnd();
         if (first_err != ncclSuccess || end_err != ncclSuccess) return rccl_failed(c, api, first_err != ncclSuccess ? first_err : end_err, "counts exchange");
@@ -411,15 +454,21 @@ static int pack_rows(mee_sharded* c, const float* d_rows, hipStream_t st) {
 
 // rows / found bytes back to the requesters, then into batch order (`d_out` / `d_found`: caller buffers, or the unique-order buffers of a
 // de-duplicated lookup)
-static int give_back(mee_sharded* c, bool rows, float* d_out, uint8_t* d_found, hipStream_t st) {
+// bf16 (lookups only): the owner's rows are bf16 already (recv_rows viewed as bf16; a tiered shard: wire_rows) and so are back_rows and d_out
+static int give_back(mee_sharded* c, bool rows, void* d_out, uint8_t* d_found, hipStream_t st, bool bf16 = false) {
     Leg legs[2];
     int nl = 0;
-    if (rows) legs[nl++] = Leg{c->recv_rows, c->back_rows, c->dim, 4, ncclFloat};
+    if (rows) legs[nl++] = bf16 ? Leg{c->cold ? c->wire_rows : (void*)c->recv_rows, c->back_rows, c->dim, 2, ncclBfloat16}
+                                : Leg{c->recv_rows, c->back_rows, c->dim, 4, ncclFloat};
     legs[nl++] = Leg{c->recv_found, c->back_found, 1, 1, ncclUint8};
     if (int rc = exchange(c, legs, nl, /*reverse=*/true, st)) return rc;
     const dim3 grid(grid_for(c->max_batch / c->G + 64, 16, 4096), c->G);
-    shard_return_kernel<<<grid, 256, 0, st>>>(rows ? (const float4*)c->back_rows : nullptr, c->back_found, c->perm, c->counts, c->cap, c->dim4,
-                                              (float4*)d_out, d_found, c->defv, c->send_keys);
+    if (bf16)
+        shard_return_kernel<true><<<grid, 256, 0, st>>>(rows ? (const u32x2*)c->back_rows : nullptr, c->back_found, c->perm, c->counts, c->cap, c->dim4,
+                                                        (u32x2*)d_out, d_found, c->defv, c->send_keys);
+    else
+        shard_return_kernel<false><<<grid, 256, 0, st>>>(rows ? (const float4*)c->back_rows : nullptr, c->back_found, c->perm, c->counts, c->cap, c->dim4,
+                                                         (float4*)d_out, d_found, c->defv, c->send_keys);
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -458,27 +507,37 @@ static int hot_has_room(mee_sharded* c, uint64_t n, void* stream, bool* room) {
     return MEE_OK;
 }
 
-static int owner_lookup(mee_sharded* c, uint64_t rt, bool insert_missing, void* stream) {
+// bf16: the rows leave this function as bf16, rounded once.  A shard without a cold tier writes them straight from the lookup into recv_rows (viewed
+// as bf16: no extra pass).  A tiered shard keeps its fp32 passes over recv_rows — the second-tier passes have no typed form — and narrows the
+// result into wire_rows at the end.
+static int owner_lookup(mee_sharded* c, uint64_t rt, bool insert_missing, void* stream, bool bf16 = false) {
     if (rt == 0) return MEE_OK;
     if (!c->cold && insert_missing) {
         for (uint64_t s = 0; s < rt; s += c->local_max_batch) {   // find_or_insert is sequentially consistent: chunks are fine
             const uint64_t m = rt - s < c->local_max_batch ? rt - s : c->local_max_batch;
-            if (int rc = mee_find_or_insert(c->local, c->recv_keys + s, m, c->recv_rows + s * c->dim, c->recv_found + s, stream)) return rc;
+            if (int rc = bf16 ? mee_find_or_insert_as(c->local, c->recv_keys + s, m, (uint16_t*)c->recv_rows + s * c->dim, MEE_DTYPE_BF16, c->recv_found + s, stream)
+                              : mee_find_or_insert(c->local, c->recv_keys + s, m, c->recv_rows + s * c->dim, c->recv_found + s, stream)) return rc;
         }
         return MEE_OK;
     }
+    if (bf16 && !c->cold)
+        return c->cap ? find_skip_padding(c->local, c->recv_keys, rt, c->recv_rows, c->recv_found, stream, MEE_DTYPE_BF16)
+                      : mee_find_as(c->local, c->recv_keys, rt, c->recv_rows, MEE_DTYPE_BF16, c->recv_found, MEE_FIND_DEFAULT, stream);
     // padded segments: EMPTY positions are padding nobody reads — the find writes neither a default row nor a found byte for them
     if (int rc = c->cap ? find_skip_padding(c->local, c->recv_keys, rt, c->recv_rows, c->recv_found, stream)
                         : mee_find(c->local, c->recv_keys, rt, c->recv_rows, c->recv_found, stream)) return rc;
     if (!c->cold) return MEE_OK;
     if (int rc = mee_find_missing(c->cold, c->recv_keys, rt, c->recv_rows, c->recv_found, stream)) return rc;   // second tier, same buffers, no sync
-    if (!insert_missing) return MEE_OK;
-    for (uint64_t s = 0; s < rt; s += c->local_max_batch) {   // keys in neither tier are created: hot while there is room, else cold
+    for (uint64_t s = 0; insert_missing && s < rt; s += c->local_max_batch) {   // keys in neither tier are created: hot while there is room, else cold
         const uint64_t m = rt - s < c->local_max_batch ? rt - s : c->local_max_batch;
         bool room = false;
         if (int rc = hot_has_room(c, m, stream, &room)) return rc;
         if (int rc = mee_find_or_insert_missing(room ? c->local : c->cold, c->recv_keys + s, m, c->recv_rows + s * c->dim, c->recv_found + s, stream)) return rc;
         if (room) c->hot_ub += m;
+    }
+    if (bf16) {   // (padding positions of a padded layout hold nothing: whatever is rounded there travels and is never read)
+        shard_narrow_rows_kernel<<<grid_for(rt, 16, 1u << 16), 256, 0, (hipStream_t)stream>>>((const float4*)c->recv_rows, rt, c->dim4, (u32x2*)c->wire_rows);
+        MEE_HIP(hipGetLastError());
     }
     return MEE_OK;
 }
@@ -736,26 +795,33 @@ int mee_sharded_create(mee_table* local, void* nccl_comm, uint64_t max_batch, do
     return mee_sharded_create_ex(local, nccl_comm, &o, out);
 }
 
-static int sharded_lookup(mee_sharded* c, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream, bool insert_missing,
+static int sharded_lookup(mee_sharded* c, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, void* stream, bool insert_missing,
                           const char* name) {
     if (int rc = check_call(c, n, name)) return rc;
     if (n && (!d_keys || !d_out)) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
+    const bool bf16 = out_dtype == MEE_DTYPE_BF16;
     DeviceGuard g(c->device);
     hipStream_t st = (hipStream_t)stream;
     uint64_t rt = 0;
+    if (bf16 && c->cold) if (int rc = ensure_wire_rows(c)) return rc;   // (before the first exchange step)
     if (!c->dedup) {
         if (int rc = push(c, d_keys, nullptr, n, st, &rt)) return rc;   // collective even when n == 0: peers may have keys for this shard
-        if (int rc = owner_lookup(c, rt, insert_missing, stream)) return rc;
-        return give_back(c, true, d_out, d_found, st);
+        if (int rc = owner_lookup(c, rt, insert_missing, stream, bf16)) return rc;
+        return give_back(c, true, d_out, d_found, st, bf16);
     }
     // pre-exchange dedup: only the batch's DISTINCT keys travel (keys out, rows back); uniq = the distinct keys followed by EMPTY padding
     // (which belongs to no shard), inverse[i] = the index of position i's key in uniq (max_batch for reserved keys: the default row)
     if (n) if (int rc = mee_dedup_keys(c->dd, d_keys, n, c->uniq, c->inverse, (int64_t)c->max_batch, stream)) return rc;
     if (int rc = push(c, c->uniq, nullptr, n, st, &rt, /*skip_padding=*/true)) return rc;
-    if (int rc = owner_lookup(c, rt, insert_missing, stream)) return rc;
-    if (int rc = give_back(c, true, c->urows, c->ufound, st)) return rc;
-    if (n) {
-        shard_expand_kernel<<<grid_for(n, 64, 1u << 16), 256, 0, st>>>((const float4*)c->urows, c->ufound, c->inverse, n, c->dim4, (float4*)d_out, d_found);
+    if (int rc = owner_lookup(c, rt, insert_missing, stream, bf16)) return rc;
+    if (int rc = give_back(c, true, c->urows, c->ufound, st, bf16)) return rc;
+    if (n && bf16) {   // urows as [max_batch + 1][dim] bf16: its default row is not the fp32 view's, and fp32 calls write over it
+        shard_fill_row_bf16_kernel<<<1, 256, 0, st>>>((u32x2*)c->urows + c->max_batch * (uint64_t)c->dim4, c->dim4, c->defv, c->ufound + c->max_batch);
+        shard_expand_kernel<true><<<grid_for(n, 64, 1u << 16), 256, 0, st>>>((const u32x2*)c->urows, c->ufound, c->inverse, n, c->dim4, (u32x2*)d_out, d_found);
+        MEE_HIP(hipGetLastError());
+    } else if (n) {
+        shard_expand_kernel<false><<<grid_for(n, 64, 1u << 16), 256, 0, st>>>((const float4*)c->urows, c->ufound, c->inverse, n, c->dim4, (float4*)d_out, d_found);
         MEE_HIP(hipGetLastError());
     }
     return MEE_OK;
@@ -763,11 +829,19 @@ static int sharded_lookup(mee_sharded* c, const int64_t* d_keys, size_t n, float
 
 int mee_sharded_find(mee_sharded* c, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream) {
     MEE_RANGE("mee_sharded_find");
-    return sharded_lookup(c, d_keys, n, d_out, d_found, stream, false, "mee_sharded_find");
+    return sharded_lookup(c, d_keys, n, d_out, MEE_DTYPE_F32, d_found, stream, false, "mee_sharded_find");
 }
 int mee_sharded_find_or_insert(mee_sharded* c, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream) {
     MEE_RANGE("mee_sharded_find_or_insert");
-    return sharded_lookup(c, d_keys, n, d_out, d_found, stream, true, "mee_sharded_find_or_insert");
+    return sharded_lookup(c, d_keys, n, d_out, MEE_DTYPE_F32, d_found, stream, true, "mee_sharded_find_or_insert");
+}
+int mee_sharded_find_as(mee_sharded* c, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, void* stream) {
+    MEE_RANGE("mee_sharded_find_as");
+    return sharded_lookup(c, d_keys, n, d_out, out_dtype, d_found, stream, false, "mee_sharded_find_as");
+}
+int mee_sharded_find_or_insert_as(mee_sharded* c, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, void* stream) {
+    MEE_RANGE("mee_sharded_find_or_insert_as");
+    return sharded_lookup(c, d_keys, n, d_out, out_dtype, d_found, stream, true, "mee_sharded_find_or_insert_as");
 }
 
 int mee_sharded_insert(mee_sharded* c, const int64_t* d_keys, const float* d_values, size_t n, void* stream) {
@@ -886,6 +960,13 @@ int mee_sharded_clear_status(mee_sharded* c, void* stream) {
     if (!c) return fail(MEE_ERR_INVALID_ARG, "mee_sharded_clear_status: null context");
     DeviceGuard g(c->device);
     MEE_HIP(hipMemsetAsync(c->status, 0, 4, (hipStream_t)stream));
+    return MEE_OK;
+}
+
+int mee_sharded_traffic(const mee_sharded* c, uint64_t* sent_bytes, uint64_t* received_bytes) {
+    if (!c) return fail(MEE_ERR_INVALID_ARG, "mee_sharded_traffic: null context");
+    if (sent_bytes) *sent_bytes = c->sent_bytes.load(std::memory_order_relaxed);
+    if (received_bytes) *received_bytes = c->recv_bytes.load(std::memory_order_relaxed);
     return MEE_OK;
 }
 

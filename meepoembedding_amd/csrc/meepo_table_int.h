@@ -205,7 +205,7 @@ struct FindPath {   // which lookup find_plane runs
     enum Kind { Plain, Located, Missing, Counted, CountedMissing, Unordered, SkipPadding } kind = Plain;
     int64_t* slots_out = nullptr;   // Located: one slot handle per key
     int nt = -1;                    // Plain: this call's cache policy (mee_find_ex); -1: the table's
-    uint32_t out_dtype = MEE_DTYPE_F32;   // Plain, Located: MEE_DTYPE_BF16 = d_out holds bf16 rows
+    uint32_t out_dtype = MEE_DTYPE_F32;   // Plain, Located, SkipPadding: MEE_DTYPE_BF16 = d_out holds bf16 rows
 };
 // the training forward and find_or_insert with the output type as a parameter (the C-ABI's fp32 and typed forms forward here)
 int find_located_prepare(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out, void* stream, const char* name);

@@ -7,6 +7,9 @@ is used by the CPU tests of this host logic).  Per sharded find:
     local find on the received keys (HIP kernel)     ->  all-to-all rows (dim*4 B each) + found-mask back
     scatter through perm into batch order
 
+out_dtype=torch.bfloat16 on find / find_or_insert: the owner's lookup writes bf16 rows (rounded once, SPEC.md §3 "Output type") and those travel:
+dim*2 B per row on the way back.
+
 Reference anchor: /root/reference/README.md:2 ("A distributed … Embedding"); the snapshot has no code.
 
 This module is host logic only: `local` is any object with the LookupTable operator methods and `router` any
@@ -16,6 +19,8 @@ from __future__ import annotations
 
 import torch
 import torch.distributed as dist
+
+from .table import _out_dtype
 
 
 class ShardedLookupTable:
@@ -45,6 +50,8 @@ class ShardedLookupTable:
         return send_keys, perm, both[0].tolist(), both[1].tolist()
 
     def _a2a(self, t: torch.Tensor, in_splits, out_splits) -> torch.Tensor:
+        if t.dtype == torch.bfloat16:   # bf16 rows travel as their bytes, so that no backend's dtype support matters (gloo moves neither bf16 nor int16)
+            return self._a2a(t.contiguous().view(torch.uint8), in_splits, out_splits).view(torch.bfloat16)
         if self._stage and t.is_cuda:
             src = t.contiguous().cpu()
             dst = torch.empty((sum(out_splits),) + tuple(t.shape[1:]), dtype=t.dtype)
@@ -55,38 +62,49 @@ class ShardedLookupTable:
         return out
 
     # -- operators ---------------------------------------------------------------------------------------
-    def _lookup(self, keys: torch.Tensor, insert_missing: bool, dedup: bool = False):
+    def _typed(self, out_dtype: torch.dtype) -> dict:
+        """the local lookup's out_dtype keyword (none at fp32: a `local` without the keyword keeps working); refused before anything is exchanged"""
+        if _out_dtype(out_dtype) == 0:
+            return {}
+        if not getattr(self.local, "supports_out_dtype", False):
+            raise ValueError(f"{type(self.local).__name__} has no bf16 lookup: use out_dtype=torch.float32 and cast the result")
+        return {"out_dtype": out_dtype}
+
+    def _lookup(self, keys: torch.Tensor, insert_missing: bool, dedup: bool = False, out_dtype: torch.dtype = torch.float32):
+        typed = self._typed(out_dtype)
         keys = keys.contiguous().view(-1)
         if dedup:
-            return self._lookup_dedup(keys, insert_missing)
+            return self._lookup_dedup(keys, insert_missing, out_dtype, typed)
         send_keys, perm, ss, rs = self._route(keys)
         recv_keys = self._a2a(send_keys, ss, rs)
         if insert_missing:
-            rows, found = self.local.find_or_insert(recv_keys)
+            rows, found = self.local.find_or_insert(recv_keys, **typed)
         else:
-            rows, found = self.local.find(recv_keys)
+            rows, found = self.local.find(recv_keys, **typed)
         rows_back = self._a2a(rows, rs, ss)
         found_back = self._a2a(found, rs, ss)
         return self.router.scatter_rows(rows_back, perm), self.router.scatter_rows(found_back, perm)
 
-    def _lookup_dedup(self, keys: torch.Tensor, insert_missing: bool):
+    def _lookup_dedup(self, keys: torch.Tensor, insert_missing: bool, out_dtype: torch.dtype = torch.float32, typed: dict | None = None):
         """Pre-exchange duplicate elimination: only the batch's DISTINCT keys cross xGMI (keys out, rows back); every
         occurrence is then served from its distinct key's row.  On skewed streams the link traffic scales with the
         number of unique keys while the metric counts lookups (SURVEY §7 hard part 1)."""
         uniq, _, _, inverse = self.local.dedup_sum(keys, compact=True)   # (this path synchronises for its split sizes anyway)
-        rows_u, found_u = self._lookup(uniq, insert_missing)
+        rows_u, found_u = self._lookup(uniq, insert_missing, out_dtype=out_dtype)
         # reserved keys have inverse -1: point them at an extra all-default "missing" row
-        miss_row, _ = self.local.find(keys.new_full((1,), -(1 << 63)))
+        miss_row, _ = self.local.find(keys.new_full((1,), -(1 << 63)), **(typed or {}))
         rows_u = torch.cat([rows_u, miss_row])
         found_u = torch.cat([found_u, found_u.new_zeros(1)])
         inverse = torch.where(inverse < 0, torch.full_like(inverse, uniq.numel()), inverse)
         return self.router.gather_rows(rows_u, inverse, n_out=keys.numel()), self.router.gather_rows(found_u, inverse, n_out=keys.numel())
 
-    def find(self, keys: torch.Tensor, dedup: bool = False):
-        return self._lookup(keys, False, dedup)
+    def find(self, keys: torch.Tensor, dedup: bool = False, out_dtype: torch.dtype = torch.float32):
+        """out_dtype=torch.bfloat16: the fp32 result rounded once to bf16 — by each key's owner, so bf16 rows cross the link (`local` must have a
+        bf16 lookup: a LookupTable; a tiered table has none and is refused with ValueError)."""
+        return self._lookup(keys, False, dedup, out_dtype)
 
-    def find_or_insert(self, keys: torch.Tensor, dedup: bool = False):
-        return self._lookup(keys, True, dedup)
+    def find_or_insert(self, keys: torch.Tensor, dedup: bool = False, out_dtype: torch.dtype = torch.float32):
+        return self._lookup(keys, True, dedup, out_dtype)
 
     def remove(self, keys: torch.Tensor) -> torch.Tensor:
         keys = keys.contiguous().view(-1)
@@ -237,21 +255,36 @@ class RcclShardedTable:
             raise self._lib.MeepoError(self._lib.ERR_INVALID_ARG, f"rows must be float32 [{n},{self.dim}] on {self.device}")
         return rows.contiguous()
 
-    def _lookup(self, fn, keys, out, found):
+    def _lookup(self, name, keys, out, found, out_dtype):
+        dt = _out_dtype(out_dtype, out)   # (ValueError before any call)
         k = self._k(keys)
         n = k.numel()
         if out is None:
-            out = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
+            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
         if found is None:
             found = torch.empty(n, dtype=torch.uint8, device=self.device)
-        self._check(fn(self._h, k.data_ptr(), n, out.data_ptr(), found.data_ptr(), self._s()))
+        L = self._lib.lib()
+        if dt == self._lib.DTYPE_F32:   # the fp32 entry points keep their code path
+            self._check(getattr(L, name)(self._h, k.data_ptr(), n, out.data_ptr(), found.data_ptr(), self._s()))
+        else:
+            self._check(getattr(L, name + "_as")(self._h, k.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(), self._s()))
         return out, found
 
-    def find(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None):
-        return self._lookup(self._lib.lib().mee_sharded_find, keys, out, found)
+    def find(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None, out_dtype: torch.dtype = torch.float32):
+        """out_dtype=torch.bfloat16 (mee_sharded_find_as): every row rounded once by its key's OWNER, so half the row bytes come back over the
+        link.  Collective: every rank passes the same out_dtype to a given call."""
+        return self._lookup("mee_sharded_find", keys, out, found, out_dtype)
 
-    def find_or_insert(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None):
-        return self._lookup(self._lib.lib().mee_sharded_find_or_insert, keys, out, found)
+    def find_or_insert(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
+                       out_dtype: torch.dtype = torch.float32):
+        """out_dtype=torch.bfloat16 (mee_sharded_find_or_insert_as): only the returned copy is rounded, the shards create their rows in fp32."""
+        return self._lookup("mee_sharded_find_or_insert", keys, out, found, out_dtype)
+
+    def traffic(self) -> tuple[int, int]:
+        """(sent, received): bytes this context has handed to ncclSend / ncclRecv since it was created (mee_sharded_traffic; no synchronisation)"""
+        s, r = self._C.c_uint64(), self._C.c_uint64()
+        self._check(self._lib.lib().mee_sharded_traffic(self._h, self._C.byref(s), self._C.byref(r)))
+        return s.value, r.value
 
     def insert(self, keys: torch.Tensor, values: torch.Tensor) -> None:
         k = self._k(keys)
