@@ -42,7 +42,6 @@ namespace mee {
 // written back, random rows of a 64 MB plane pair) in a grid shaped like the apply's, three times, and the host compares the mean block time by block-index parity:
 // the same sign in both measured launches and at least 5 % apart — the even bucket gets the share that equalises the two; anything else — even halves.  ~2 ms, once
 // per device and process (mee_device_calibration reports what was measured).
-constexpr int kPartThreads = 1024;
 constexpr int kApplyThreads = 512;
 constexpr int kApplyWaves = kApplyThreads / 64;
 constexpr uint32_t kLdsSlots = kBucketCap;   // the LDS hash table: as many slots as a block holds sources (a bucket of kBucketCap DISTINCT keys fills it to the
@@ -51,61 +50,19 @@ constexpr uint32_t kChunk = 8;            // sources one tile sums in one go (fo
 constexpr uint32_t kMaxQuads = 192;       // wave items (quads of four chunks) of one slab: at most m / 32 + (runs longer than a chunk: m / 9) = 32 + 113 at m = 1024
 constexpr uint32_t kLdsPartRows = 16;     // fp64 partial rows a slab keeps in LDS (a slab that is ONE key of 512 occurrences: 16 quads)
 
-// Buckets and apply blocks for a batch of n keys.  One block per bucket and one round of equal blocks (bucket_count_for_host) — unless the
-// latest batch was skewed: its S slabs were units of their own in front of the buckets, and S + buckets beyond the resident block slots ran as
-// a second round behind the first (25 us units: a Zipf(1.05) batch of 256K keys, 146 slabs + 768 buckets on 768 slots, ended at 75-80 us
-// instead of ~50).  Key streams keep their skew from batch to batch, so the next batch gets S (+ 1/16) fewer, larger buckets and as many
-// blocks as before: slabs and buckets together fill the slots once.  S comes back through a pinned host word the apply kernel writes — read
-// here without any synchronisation (a stale or zero value costs time, never results: the kernel works through whatever units there are).
-// A launch that is being CAPTURED into a hipGraph is replayed for batches the host never sees: what the host knows about the stream right now is frozen into
-// the graph.  Such launches take the FULL kernel (correct and quick for uniform AND skewed batches; LEAN's slow path would be replayed for ever on a stream
-// that turns skewed), keep buckets for hot keys (the hot-key set itself lives on the device and follows the stream from replay to replay), and — when the
-// host has no skew report at capture time — still leave a twelfth of the block slots to agents.
+// The plan of a batch's partition (part_plan_for, meepo_apply_part.h) from the state of the stream: S, the units the latest batch had beyond its hash
+// buckets, comes back through a pinned host word the apply kernel writes — read here without any synchronisation (a stale or zero value costs time,
+// never results: the kernel works through whatever units there are).  ONE call per partition: it ages skew_sticky.
 static bool stream_is_capturing(hipStream_t st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     return hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
 }
-// (slots_of / bucket_max_of: the geometry of another consumer of the partition — mee_dedup_sum's blocks, six per CU, want ONE round of buckets of up to ~680 positions)
-uint32_t bucket_count_for(mee_table* t, uint64_t n, hipStream_t st, uint32_t* grid_out, uint32_t* nbk_total_out, bool* full_out, uint32_t slots_of, uint32_t bucket_max_of,
-                          BucketScratch* state) {
-    BucketScratch& sk = state ? *state : t->bk;
-    const uint32_t slots = slots_of ? slots_of : sk.slots;
-    uint32_t full = bucket_count_for_host(n, slots, bucket_max_of ? bucket_max_of : sk.bucket_max ? sk.bucket_max : kBucketMax);
-    // The scratch (totals, run matrices, pending counters, tickets) is strided for n_buckets_max buckets, sized at creation for the DEFAULT bucket size at
-    // max_batch (+ the hot keys' buckets): a smaller "apply_bucket_max" must not ask for more buckets than that — it gets larger buckets instead.
-    const uint32_t room = sk.n_buckets_max - kHotCap;
-    if (full > room) full = room >= slots ? room / slots * slots : room;
-    uint32_t nbk = full;
+PartPlan bucket_plan(BucketScratch& sk, uint64_t n, hipStream_t st, uint32_t threads, uint32_t slots_of, uint32_t bucket_max_of) {
     const bool capturing = sk.skew_adapt && stream_is_capturing(st);
     const uint32_t s_prev = sk.h_slabs && sk.skew_adapt ? *(volatile uint32_t*)sk.h_slabs : 0u;
-    // which kernel (bkt_apply_kernel): FULL behind a skewed batch — and for the 64 batches after the last one: a stream whose skew comes and
-    // goes must not fall into the LEAN kernel's slow path every other batch —, else LEAN
     if (s_prev) sk.skew_sticky = 64;
     else if (sk.skew_sticky) --sk.skew_sticky;
-    if (full_out) *full_out = sk.kernel_choice >= 0 ? sk.kernel_choice != 0 : (capturing || s_prev != 0 || sk.skew_sticky != 0);
-    // (a batch with more keys than its buckets hold whole: every bucket is a list of slabs — the FULL kernel's business, whatever the knob says)
-    if (full_out && n > (uint64_t)full * (kBucketCap * 3 / 4)) *full_out = true;
-    const uint32_t units = s_prev ? s_prev : capturing && full_out && *full_out ? slots / 12 : 0u;
-    if (units && n > (uint64_t)slots * 128) {
-        uint32_t adj = units + units / 16 + 1;
-        if (adj > slots / 2) adj = slots / 2;
-        if (adj > full / 2) adj = full / 2;
-        nbk = full - adj;
-        if (!bucket_max_of) while ((uint64_t)nbk * 2 * kBucketMax < n && nbk < full) ++nbk;   // (never more than ~700 positions per bucket on average: kBucketCap stays 12 sigma away)
-        // (a consumer that asked for its own bucket size — mee_dedup_sum, whose units beyond the hash buckets are windows of 1024 positions of the hot keys' buckets,
-        // about three quarters full on average: what is left for the hash buckets must still fit them.  The block slots the windows get this way run them beside the
-        // hash buckets from the kernel's first microsecond instead of behind them)
-        if (bucket_max_of) {
-            const uint64_t in_windows = (uint64_t)units * 768, rest = n > in_windows ? n - in_windows : 0;
-            while ((uint64_t)nbk * bucket_max_of < rest && nbk < full) ++nbk;
-        }
-    }
-    if (grid_out) *grid_out = full;
-    // behind a skewed batch the keys that batch reported as hot get buckets of their own, behind the hash buckets (meepo_apply_part.h) — the
-    // FULL kernel's business
-    const bool hot = (s_prev || capturing) && nbk + kHotCap <= sk.n_buckets_max && (!full_out || *full_out);
-    if (nbk_total_out) *nbk_total_out = hot ? nbk + kHotCap : nbk;
-    return nbk;
+    return part_plan_for(n, threads, PartInputs{sk.slots, sk.bucket_max, sk.n_buckets_max, s_prev, capturing, sk.skew_sticky != 0, sk.kernel_choice, slots_of, bucket_max_of});
 }
 
 // ---- the partition kernel of an apply (the role itself: meepo_apply_part.h) ----------------------------------------------------------------
@@ -142,9 +99,10 @@ __global__ __launch_bounds__(256) void bkt_totals_kernel(BucketScratch bk, uint3
         if (tot > kBucketCap) bk.has_split[parity] = 1u;
     }
 }
-bool bucket_totals_by_atomics(uint32_t blocks, uint32_t nbk) { return (uint64_t)blocks * nbk <= 160000; }
-int bucket_totals_launch(mee_table* t, uint32_t nbk, uint32_t blocks, hipStream_t st, const BucketScratch* bk) {
-    bkt_totals_kernel<<<(nbk + 63) / 64, 256, 0, st>>>(bk ? *bk : t->bk, nbk, blocks);
+// (nothing to launch when the partition blocks' atomics added the totals up)
+int bucket_totals_launch(const BucketScratch& bk, const PartPlan& plan, hipStream_t st) {
+    if (plan.totals_by_atomics) return MEE_OK;
+    bkt_totals_kernel<<<(plan.nbk + 63) / 64, 256, 0, st>>>(bk, plan.nbk, plan.blocks);
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -1421,15 +1379,21 @@ int bucket_scratch_alloc(mee_table* t) {
     alloc((void**)&bk.ent, bk.fast_max * sizeof(PartEntry));
     alloc((void**)&bk.cnt_mat, (uint64_t)kPartBlocksMax * bk.n_buckets_max * 4);
     alloc((void**)&bk.off_mat, (uint64_t)kPartBlocksMax * bk.n_buckets_max * 4);
-    alloc((void**)&bk.tot, 2ull * bk.n_buckets_max * 4);
-    alloc((void**)&bk.seq, 8 * 4);   // seq[0], seq[1], has_split[0], has_split[1]: ONE line of one page, read by every apply block with ONE load; [4]: the LEAN kernel's slab count; [5]: shadow of the pinned host word; [6]: largest slab count published for this batch (report_slabs)
-    bk.has_split = bk.seq ? bk.seq + 2 : nullptr;
-    alloc((void**)&bk.hot_key, 2ull * kHotSlots * 8); alloc((void**)&bk.hot_idx, 2ull * kHotSlots * 4); alloc((void**)&bk.hot_n, 2 * 4);
-    if (e == hipSuccess) e = hipMemset(bk.hot_key, 0, 2ull * kHotSlots * 8);
-    if (e == hipSuccess) e = hipMemset(bk.hot_idx, 0xFF, 2ull * kHotSlots * 4);
-    if (e == hipSuccess) e = hipMemset(bk.hot_n, 0, 2 * 4);
-    if (e == hipSuccess) e = hipMemset(bk.seq, 0, 8 * 4);
-    if (e == hipSuccess) e = hipMemset(bk.tot, 0, 2ull * bk.n_buckets_max * 4);   // (every partition launch zeroes the copy the next one adds to)
+    // the skew state of one key stream: the totals' two copies, the parity words, the hot-key set and the pinned word (the apply's here, the raw-stream operators' below)
+    auto alloc_skew_state = [&](BucketScratch& s) {
+        alloc((void**)&s.tot, 2ull * s.n_buckets_max * 4);
+        alloc((void**)&s.seq, 8 * 4);   // seq[0], seq[1], has_split[0], has_split[1]: ONE line of one page, read by every apply block with ONE load; [4]: the LEAN kernel's slab count; [5]: shadow of the pinned host word; [6]: largest slab count published for this batch (report_slabs)
+        s.has_split = s.seq ? s.seq + 2 : nullptr;
+        alloc((void**)&s.hot_key, 2ull * kHotSlots * 8); alloc((void**)&s.hot_idx, 2ull * kHotSlots * 4); alloc((void**)&s.hot_n, 2 * 4);
+        if (e == hipSuccess) e = hipMemset(s.hot_key, 0, 2ull * kHotSlots * 8);
+        if (e == hipSuccess) e = hipMemset(s.hot_idx, 0xFF, 2ull * kHotSlots * 4);
+        if (e == hipSuccess) e = hipMemset(s.hot_n, 0, 2 * 4);
+        if (e == hipSuccess) e = hipMemset(s.seq, 0, 8 * 4);
+        if (e == hipSuccess) e = hipMemset(s.tot, 0, 2ull * s.n_buckets_max * 4);   // (every partition launch zeroes the copy the next one adds to)
+        if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_slabs, 64, hipHostMallocMapped | hipHostMallocPortable);
+        if (e == hipSuccess) { *s.h_slabs = 0u; e = hipHostGetDevicePointer((void**)&s.h_slabs_dev, s.h_slabs, 0); }
+    };
+    alloc_skew_state(bk);
     alloc((void**)&bk.pend_cnt, (uint64_t)bk.n_buckets_max * 4);
     alloc((void**)&bk.ticket, (uint64_t)bk.n_buckets_max * 4);
     if (t->optimizer != MEE_OPT_NONE) {   // pending records of split buckets: the sparse-optimizer apply alone (dedup and elections take a bucket of any size whole)
@@ -1440,8 +1404,6 @@ int bucket_scratch_alloc(mee_table* t) {
     // mee_dedup_sum cuts a hot key's own bucket into windows of 1024 positions that leave one fp64 partial row each (meepo_dedup.hip): at most max_batch / 1024 + kHotCap
     bk.sum_part_rows = (uint32_t)(bk.fast_max / 1024 + kHotCap + 8);
     alloc((void**)&bk.sum_part, (uint64_t)bk.sum_part_rows * t->dim * sizeof(double));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&bk.h_slabs, 64, hipHostMallocMapped | hipHostMallocPortable);
-    if (e == hipSuccess) { *bk.h_slabs = 0u; e = hipHostGetDevicePointer((void**)&bk.h_slabs_dev, bk.h_slabs, 0); }
     bk.skew_adapt = 1; bk.skew_sticky = 0; bk.kernel_choice = -1;
     bk.xcd_split = t->optimizer != MEE_OPT_NONE && t->value_memory == MEE_MEM_HBM ? xcd_split_for_device(t->device) : 0u;   // (only the apply's blocks care)
     // the device-resident copy the FULL apply kernel reads (everything the DEVICE uses of this struct is fixed from here on; the tuning fields are the host's)
@@ -1453,30 +1415,19 @@ int bucket_scratch_alloc(mee_table* t) {
     dd = bk;
     dd.dev_copy = nullptr; dd.h_slabs = nullptr; dd.h_slabs_dev = nullptr;
     dd.tot = nullptr; dd.seq = nullptr; dd.hot_key = nullptr; dd.hot_idx = nullptr; dd.hot_n = nullptr;
-    alloc((void**)&dd.tot, 2ull * bk.n_buckets_max * 4);
-    alloc((void**)&dd.seq, 8 * 4);
-    dd.has_split = dd.seq ? dd.seq + 2 : nullptr;
-    alloc((void**)&dd.hot_key, 2ull * kHotSlots * 8); alloc((void**)&dd.hot_idx, 2ull * kHotSlots * 4); alloc((void**)&dd.hot_n, 2 * 4);
-    if (e == hipSuccess) e = hipMemset(dd.hot_key, 0, 2ull * kHotSlots * 8);
-    if (e == hipSuccess) e = hipMemset(dd.hot_idx, 0xFF, 2ull * kHotSlots * 4);
-    if (e == hipSuccess) e = hipMemset(dd.hot_n, 0, 2 * 4);
-    if (e == hipSuccess) e = hipMemset(dd.seq, 0, 8 * 4);
-    if (e == hipSuccess) e = hipMemset(dd.tot, 0, 2ull * bk.n_buckets_max * 4);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&dd.h_slabs, 64, hipHostMallocMapped | hipHostMallocPortable);
-    if (e == hipSuccess) { *dd.h_slabs = 0u; e = hipHostGetDevicePointer((void**)&dd.h_slabs_dev, dd.h_slabs, 0); }
+    alloc_skew_state(dd);
     if (e != hipSuccess) return fail(MEE_ERR_OUT_OF_MEMORY, "hipMalloc for the apply scratch: %s", hipGetErrorString(e));
     return MEE_OK;
 }
 void bucket_scratch_free(mee_table* t) {
     BucketScratch& bk = t->bk;
-    void* dev[] = {bk.ent, bk.cnt_mat, bk.off_mat, bk.tot, bk.seq, bk.hot_key, bk.hot_idx, bk.hot_n, bk.pend_cnt, bk.ticket, bk.pend_key, bk.pend_slot, bk.pend_row, bk.sum_part};
+    void* dev[] = {bk.ent, bk.cnt_mat, bk.off_mat, bk.pend_cnt, bk.ticket, bk.pend_key, bk.pend_slot, bk.pend_row, bk.sum_part, bk.dev_copy};
     for (void* p : dev) if (p) (void)hipFree(p);
-    if (bk.h_slabs) (void)hipHostFree(bk.h_slabs);
-    if (bk.dev_copy) (void)hipFree(bk.dev_copy);
-    BucketScratch& dd = t->bk_dd;
-    void* dev_dd[] = {dd.tot, dd.seq, dd.hot_key, dd.hot_idx, dd.hot_n};
-    for (void* p : dev_dd) if (p) (void)hipFree(p);
-    if (dd.h_slabs) (void)hipHostFree(dd.h_slabs);
+    for (BucketScratch* s : {&t->bk, &t->bk_dd}) {   // (alloc_skew_state)
+        void* state[] = {s->tot, s->seq, s->hot_key, s->hot_idx, s->hot_n};
+        for (void* p : state) if (p) (void)hipFree(p);
+        if (s->h_slabs) (void)hipHostFree(s->h_slabs);
+    }
 }
 
 #if MEE_APPLY_TIMELINE
@@ -1486,26 +1437,16 @@ extern "C" int mee_debug_timeline(unsigned long long* host_out, uint64_t n_words
     return hipMemcpy(host_out, g_dbg, n_words * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
 }
 #endif
-int bucket_apply_prepare(mee_table* t, const int64_t* d_keys, uint32_t n, hipStream_t st) {
-    uint32_t grid, nbk;
-    bool full;
-    const uint32_t nbk_hash = bucket_count_for(t, n, st, &grid, &nbk, &full);
-    t->part_full = full;
-    uint32_t blocks, per_block;
-    part_geometry(n, kPartThreads, blocks, per_block);
-    t->part_blocks = blocks; t->part_per_block = per_block; t->part_nbk = nbk; t->part_nbk_hash = nbk_hash; t->part_grid = grid;
-    const bool atom = bucket_totals_by_atomics(blocks, nbk);
-    bkt_sort_kernel<<<blocks, kPartThreads, sizeof(PartHot) + nbk * 4, st>>>(d_keys, n, nbk_hash, nbk, per_block, t->bk, &t->ctr->status, t->op, atom, t->bk.xcd_split);
+// the partition of an apply as launches of its own: `plan` as bucket_plan(t->bk, n, st, kPartThreads) made it
+int bucket_partition_launch(mee_table* t, const int64_t* d_keys, uint32_t n, const PartPlan& plan, hipStream_t st) {
+    bkt_sort_kernel<<<plan.blocks, kPartThreads, sizeof(PartHot) + plan.nbk * 4, st>>>(d_keys, n, plan.nbk_hash, plan.nbk, plan.per_block, t->bk, &t->ctr->status, t->op,
+                                                                                       plan.totals_by_atomics, t->bk.xcd_split);
     MEE_HIP(hipGetLastError());
-    return atom ? MEE_OK : bucket_totals_launch(t, nbk, blocks, st);
+    return bucket_totals_launch(t->bk, plan, st);
 }
-
-// the same partition for another consumer (meepo_dedup.hip: last-wins elections), with the geometry the caller chose
-int bucket_apply_prepare_as(mee_table* t, const int64_t* d_keys, uint32_t n, hipStream_t st, uint32_t nbk_hash, uint32_t nbk, uint32_t blocks, uint32_t per_block) {
-    const bool atom = bucket_totals_by_atomics(blocks, nbk);
-    bkt_sort_kernel<<<blocks, kPartThreads, sizeof(PartHot) + nbk * 4, st>>>(d_keys, n, nbk_hash, nbk, per_block, t->bk, &t->ctr->status, t->op, atom, 0u);
-    MEE_HIP(hipGetLastError());
-    return atom ? MEE_OK : bucket_totals_launch(t, nbk, blocks, st);
+int bucket_apply_prepare(mee_table* t, const int64_t* d_keys, uint32_t n, hipStream_t st, PartPlan& plan) {
+    plan = bucket_plan(t->bk, n, st, kPartThreads);
+    return bucket_partition_launch(t, d_keys, n, plan, st);
 }
 
 // a prepared partition that no apply will consume (mee_apply_discard): count it as consumed, so that the next partition fills the other copy
@@ -1516,7 +1457,9 @@ int bucket_apply_discard(mee_table* t, hipStream_t st) {
     return MEE_OK;
 }
 
-int bucket_apply_launch(mee_table* t, const float* d_grads, uint32_t n, const OptArgs& a, const uint32_t* d_gidx, const int64_t* d_slots, hipStream_t st,
+// `plan`: the one this batch was partitioned with.  Nothing else says how many buckets there are, which strides the run matrices were written with and which
+// kernel takes them: a tuning call between the partition and the apply changes nothing about the pending batch.
+int bucket_apply_launch(mee_table* t, const PartPlan& plan, const float* d_grads, uint32_t n, const OptArgs& a, const uint32_t* d_gidx, const int64_t* d_slots, hipStream_t st,
                         const GroupDesc* d_desc, uint32_t n_tables) {
     ApplyArgs A{};
     A.tkeys = t->keys; A.values = (float4*)t->values; A.s1 = (float4*)t->s1; A.s2 = (float4*)t->s2; A.nb = t->nb; A.dim4 = t->dim4;
@@ -1530,11 +1473,10 @@ int bucket_apply_launch(mee_table* t, const float* d_grads, uint32_t n, const Op
 #endif
     A.desc = d_desc; A.n_tables = n_tables;   // a table group's apply (d_slots = the batch's located rows = its keys; t = the group's scratch table)
     A.hot_count = hot_count_for(n);
-    A.nbk = t->part_nbk; A.nbk_hash = t->part_nbk_hash; A.part_blocks = t->part_blocks; A.per_block = t->part_per_block;   // as whoever partitioned this batch left them (a tuning
-    // call between the partition and the apply — "apply_bucket_max" — must not change the stride the run matrices were written with)
+    A.nbk = plan.nbk; A.nbk_hash = plan.nbk_hash; A.part_blocks = plan.blocks; A.per_block = plan.per_block;
     // one block per bucket (+ the blocks a skewed stream's slabs need); on a skewed batch the blocks work through a list of units, the slabs of the
     // split buckets first (run_units)
-    const bool full = t->part_full;   // as the partition decided: FULL = a skewed stream (hot keys' buckets may exist, the grid is one round of the block slots)
+    const bool full = plan.full;   // FULL = a skewed stream (hot keys' buckets may exist, the grid is one round of the block slots)
     // the bucketed apply on `grid` blocks.  Its rows: a table group's (located), located (d_slots) or by key.  FULL reads the partition's scratch
     // from device memory (t->bk.dev_copy), LEAN takes it as kernel arguments.
     const int rows = d_desc ? 2 : d_slots ? 1 : 0;
@@ -1544,7 +1486,7 @@ int bucket_apply_launch(mee_table* t, const float* d_grads, uint32_t n, const Op
             bkt_apply_kernel<kind, d4, (r >= 1), (r == 2), f><<<grid, kApplyThreads, 0, st>>>(A, bk());
         }); }); }); });
     };
-    apply(full, full ? t->part_grid : A.nbk);   // LEAN: block = bucket
+    apply(full, full ? plan.grid : A.nbk);   // LEAN: block = bucket
     // The FULL kernel needs scratch memory (124-192 B per lane), the LEAN kernel none.  A queue gets its scratch when the first launch that needs it arrives: the
     // runtime allocates it on the host and re-submits — 147 us measured between a stream's forward and its first FULL apply (the second skewed step of a stream: 230-290 us
     // against 95 from the third on).  So the first LEAN apply a table sees on a stream is followed by ONE empty launch of the FULL kernel (same instance, same grid, no batch:
@@ -1557,7 +1499,7 @@ int bucket_apply_launch(mee_table* t, const float* d_grads, uint32_t n, const Op
             t->full_ready[0] = (void*)st;
             if (t->full_ready_n < 4) ++t->full_ready_n;
             A.part_blocks = 0;
-            apply(true, t->part_grid ? t->part_grid : A.nbk);   // (the FULL kernel's grid: one round of the block slots)
+            apply(true, plan.grid ? plan.grid : A.nbk);   // (the FULL kernel's grid: one round of the block slots)
         }
     }
     MEE_HIP(hipGetLastError());

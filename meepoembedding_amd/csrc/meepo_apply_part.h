@@ -1,11 +1,13 @@
 // meepo_apply_part.h — the partition half of the bucketed sparse-optimizer apply (see meepo_apply.hip), as device code two kernels share:
-// the partition kernel of an apply (meepo_apply.hip) and the training forward mee_find_located_prepare (meepo_table.hip), whose launch gives
-// its first blocks this role so that the partition of the step's backward runs beside — hidden behind — the forward's row gather.
+// the partition kernel of an apply (meepo_apply.hip) and the training forward mee_find_located_prepare (meepo_find.hip), whose launch gives
+// its first blocks this role so that the partition of the step's backward runs beside — hidden behind — the forward's row gather.  And the host's
+// decision in front of every partition, as one value: PartPlan.
 #pragma once
 #include "meepo_table_int.h"
 
 namespace mee {
 
+constexpr int kPartThreads = 1024;       // threads of a partition block of its own launch (the training forward's launch: kFindPrepareThreads)
 constexpr int kPartBlocks = 128;          // blocks that share the partition of one batch, at most (2 x 64: a wave of the apply kernel scans their run lengths, two per lane)
 constexpr int kPartBlocksMax = 128;       // ... of a dedup / an election (meepo_dedup.hip).  (256 blocks for 1M-key batches were measured: the partition gets 2.6 us faster, its
                                           // consumers 7 us slower — twice the runs per bucket: DESIGN.md §8)
@@ -50,10 +52,70 @@ inline void part_geometry(uint32_t n, uint32_t threads, uint32_t& blocks, uint32
     if (blocks < 1) blocks = 1;
     per_block = (n + blocks - 1) / blocks;
 }
+// who adds up the bucket totals: the partition blocks' atomics, or — large batches — bkt_totals_kernel behind them (sort_role)
+inline bool bucket_totals_by_atomics(uint32_t blocks, uint32_t nbk) { return (uint64_t)blocks * nbk <= 160000; }
+
+// What a PartPlan (meepo_table_int.h) is made from: the scratch's geometry and tuning, and what the host knows about the stream right now.
+struct PartInputs {
+    uint32_t slots, bucket_max, n_buckets_max;   // BucketScratch's (bucket_max 0 = kBucketMax)
+    uint32_t prev_units;                         // units the latest batch had beyond its hash buckets (the pinned word; 0: none, or no skew adaptation)
+    bool capturing;                              // the launch is being captured into a graph
+    bool sticky;                                 // a skewed batch was seen within the last 64
+    int kernel_choice;                           // BucketScratch::kernel_choice
+    uint32_t slots_of, bucket_max_of;            // the geometry of a consumer other than the apply (0: the apply's): mee_dedup_sum's blocks, six per CU, want ONE round of buckets of up to ~680 positions
+};
+// Buckets and apply blocks for a batch of n keys, partitioned by blocks of `threads` threads.  One block per bucket and one round of equal blocks
+// (bucket_count_for_host) — unless the latest batch was skewed: its S slabs were units of their own in front of the buckets, and S + buckets beyond
+// the resident block slots ran as a second round behind the first (25 us units: a Zipf(1.05) batch of 256K keys, 146 slabs + 768 buckets on 768
+// slots, ended at 75-80 us instead of ~50).  Key streams keep their skew from batch to batch, so the next batch gets S (+ 1/16) fewer, larger buckets
+// and as many blocks as before: slabs and buckets together fill the slots once.
+// A launch that is being CAPTURED into a hipGraph is replayed for batches the host never sees: what the host knows about the stream right now is frozen into
+// the graph.  Such launches take the FULL kernel (correct and quick for uniform AND skewed batches; LEAN's slow path would be replayed for ever on a stream
+// that turns skewed), keep buckets for hot keys (the hot-key set itself lives on the device and follows the stream from replay to replay), and — when the
+// host has no skew report at capture time — still leave a twelfth of the block slots to agents.
+inline PartPlan part_plan_for(uint64_t n, uint32_t threads, const PartInputs& in) {
+    PartPlan p{};
+    const uint32_t slots = in.slots_of ? in.slots_of : in.slots, bucket_max_of = in.bucket_max_of;
+    uint32_t full = bucket_count_for_host(n, slots, bucket_max_of ? bucket_max_of : in.bucket_max ? in.bucket_max : kBucketMax);
+    // The scratch (totals, run matrices, pending counters, tickets) is strided for n_buckets_max buckets, sized at creation for the DEFAULT bucket size at
+    // max_batch (+ the hot keys' buckets): a smaller "apply_bucket_max" must not ask for more buckets than that — it gets larger buckets instead.
+    const uint32_t room = in.n_buckets_max - kHotCap;
+    if (full > room) full = room >= slots ? room / slots * slots : room;
+    uint32_t nbk = full;
+    const uint32_t s_prev = in.prev_units;
+    // which kernel (bkt_apply_kernel): FULL behind a skewed batch — and for the 64 batches after the last one: a stream whose skew comes and
+    // goes must not fall into the LEAN kernel's slow path every other batch —, else LEAN
+    p.full = in.kernel_choice >= 0 ? in.kernel_choice != 0 : (in.capturing || s_prev != 0 || in.sticky);
+    // (a batch with more keys than its buckets hold whole: every bucket is a list of slabs — the FULL kernel's business, whatever the knob says)
+    if (n > (uint64_t)full * (kBucketCap * 3 / 4)) p.full = true;
+    const uint32_t units = s_prev ? s_prev : in.capturing && p.full ? slots / 12 : 0u;
+    if (units && n > (uint64_t)slots * 128) {
+        uint32_t adj = units + units / 16 + 1;
+        if (adj > slots / 2) adj = slots / 2;
+        if (adj > full / 2) adj = full / 2;
+        nbk = full - adj;
+        if (!bucket_max_of) while ((uint64_t)nbk * 2 * kBucketMax < n && nbk < full) ++nbk;   // (never more than ~700 positions per bucket on average: kBucketCap stays 12 sigma away)
+        // (a consumer that asked for its own bucket size — mee_dedup_sum, whose units beyond the hash buckets are windows of 1024 positions of the hot keys' buckets,
+        // about three quarters full on average: what is left for the hash buckets must still fit them.  The block slots the windows get this way run them beside the
+        // hash buckets from the kernel's first microsecond instead of behind them)
+        if (bucket_max_of) {
+            const uint64_t in_windows = (uint64_t)units * 768, rest = n > in_windows ? n - in_windows : 0;
+            while ((uint64_t)nbk * bucket_max_of < rest && nbk < full) ++nbk;
+        }
+    }
+    p.grid = full;
+    // behind a skewed batch the keys that batch reported as hot get buckets of their own, behind the hash buckets — the FULL kernel's business
+    const bool hot = (s_prev || in.capturing) && nbk + kHotCap <= in.n_buckets_max && p.full;
+    p.nbk_hash = nbk;
+    p.nbk = hot ? nbk + kHotCap : nbk;
+    part_geometry((uint32_t)n, threads, p.blocks, p.per_block);
+    p.totals_by_atomics = bucket_totals_by_atomics(p.blocks, p.nbk);
+    return p;
+}
 
 // the same bits, scaled the same way, as the key's table bucket (bucket_of): a block's keys live in one contiguous 1/nbk slice of the table
 __device__ __forceinline__ uint32_t apply_bucket_of(int64_t key, uint32_t nbk) { return (uint32_t)__umul64hi(mix64((uint64_t)key), (uint64_t)nbk); }
-// The pinned host word that tells the next partition how many units the latest batch had beyond its hash buckets (bucket_count_for).  It is written
+// The pinned host word that tells the next partition how many units the latest batch had beyond its hash buckets (bucket_plan).  It is written
 // only when the value CHANGES (bk.seq[5] shadows it on the device): a uniform stream reports 0 with every batch and need not cross PCIe for that
 // (measured: no difference in step time either way, 85.9-88.0 against 87.5-87.7 us per uniform apply; it just keeps the bus quiet).
 __device__ __forceinline__ void report_units(const BucketScratch& bk, uint32_t* h_units, uint32_t v) {

@@ -24,7 +24,7 @@
 
 namespace mee {
 
-// The partition's geometry is the apply's (bucket_count_for: 3072 buckets of 341 per 1M keys, 128 partition blocks).  Measured alternatives, DESIGN.md §8: a bucket count
+// The partition's geometry is the apply's (part_plan_for: 3072 buckets of 341 per 1M keys, 128 partition blocks).  Measured alternatives, DESIGN.md §8: a bucket count
 // by this file's own block slots (2048 buckets of <= 512: one round) — dedup_keys 70.9 -> 75.7 us per 1M keys —, 256 partition blocks — 70.2 -> 75.6 us (twice the runs per bucket).
 constexpr int kDedupThreads = 256;
 constexpr int kDedupWaves = kDedupThreads / 64;
@@ -954,19 +954,15 @@ __global__ __launch_bounds__(kDedupThreads, kSumBlocksPerCU) void bkt_dedup_sum_
 static uint32_t hot_window_blocks(const DedupArgs& A, uint32_t n, uint32_t window = kHotWindow) { return A.nbk != A.nbk_hash ? n / window + (A.nbk - A.nbk_hash) : 0u; }
 static int dedup_partition(mee_table* t, const int64_t* d_keys, uint32_t n, hipStream_t st, DedupArgs& A, int64_t* d_uniq, int64_t* d_inverse, int64_t miss_index, uint8_t* d_found,
                            uint32_t* d_counts = nullptr, uint32_t slots_of = 0, uint32_t bucket_max_of = 0) {
-    uint32_t grid, nbk;
-    bool full;
-    const uint32_t nbk_hash = bucket_count_for(t, n, st, &grid, &nbk, &full, slots_of, bucket_max_of, &t->bk_dd);
     // (hot keys' buckets whenever the latest batch reported any: a dedup has no FULL / LEAN kernels, its one kernel takes buckets of any size)
-    uint32_t blocks, per_block;
-    part_geometry(n, 1024, blocks, per_block, kPartBlocks);
-    A.nbk = nbk; A.nbk_hash = nbk_hash; A.part_blocks = blocks; A.per_block = per_block; A.hot_count = hot_count_for(n); A.op = t->op; A.h_slabs = t->bk_dd.h_slabs_dev; A.status = &t->ctr->status;
-    const bool atom = bucket_totals_by_atomics(blocks, nbk);
+    const PartPlan plan = bucket_plan(t->bk_dd, n, st, kPartThreads, slots_of, bucket_max_of);
+    A.nbk = plan.nbk; A.nbk_hash = plan.nbk_hash; A.part_blocks = plan.blocks; A.per_block = plan.per_block; A.hot_count = hot_count_for(n); A.op = t->op; A.h_slabs = t->bk_dd.h_slabs_dev; A.status = &t->ctr->status;
     // an assign without hot keys' buckets needs no bucket totals: nobody numbers anything across buckets, and a bucket's size is the sum of its runs
-    A.size_from_runs = !atom && !d_uniq && nbk == nbk_hash;
-    bkt_sort_dedup_kernel<<<blocks, 1024, sizeof(PartHot) + nbk * 4, st>>>(d_keys, n, nbk_hash, nbk, per_block, t->bk_dd, &t->ctr->status, t->op, d_uniq, d_inverse, miss_index, d_found, atom, d_counts);
+    A.size_from_runs = !plan.totals_by_atomics && !d_uniq && plan.nbk == plan.nbk_hash;
+    bkt_sort_dedup_kernel<<<plan.blocks, kPartThreads, sizeof(PartHot) + plan.nbk * 4, st>>>(d_keys, n, plan.nbk_hash, plan.nbk, plan.per_block, t->bk_dd, &t->ctr->status, t->op, d_uniq, d_inverse,
+                                                                                             miss_index, d_found, plan.totals_by_atomics, d_counts);
     MEE_HIP(hipGetLastError());
-    return atom || A.size_from_runs ? MEE_OK : bucket_totals_launch(t, nbk, blocks, st, &t->bk_dd);
+    return A.size_from_runs ? MEE_OK : bucket_totals_launch(t->bk_dd, plan, st);
 }
 
 int bucket_dedup_keys(mee_table* t, const int64_t* d_keys, uint32_t n, int64_t* d_uniq, int64_t* d_inverse, int64_t miss_index, hipStream_t st) {

@@ -221,8 +221,8 @@ extern "C" {
 int mee_reserve(mee_table* t, uint64_t new_capacity, void* stream) {
     MEE_RANGE("mee_reserve");
     if (!t || new_capacity == 0) return fail(MEE_ERR_INVALID_ARG, "mee_reserve: null table or zero capacity");
-    if (t->prepared_n) {
-        if (!t->prepared_by_forward) return fail(MEE_ERR_INVALID_ARG, "mee_reserve: a prepared apply is pending on this table (finish it with mee_apply_* or mee_apply_discard)");
+    if (t->pending.n) {
+        if (!t->pending.by_forward) return fail(MEE_ERR_INVALID_ARG, "mee_reserve: a prepared apply is pending on this table (finish it with mee_apply_* or mee_apply_discard)");
         if (int rc = mee_apply_discard(t, stream)) return rc;   // a training forward's partition: the apply that follows partitions its batch again
     }
     size_t stored = 0;

@@ -1019,35 +1019,30 @@ int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, cons
 int mee::find_located_prepare(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out, void* stream, const char* name) {
     if (!t || (n && (!d_keys || !d_out || !d_slots_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
     if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
-    if (t->prepared_n) return fail(MEE_ERR_INVALID_ARG, "%s: a prepared apply is already pending", name);
+    if (t->pending.n) return fail(MEE_ERR_INVALID_ARG, "%s: a prepared apply is already pending", name);
     if (n == 0) return MEE_OK;
     if (t->optimizer == MEE_OPT_NONE) return find_plane(t, t->values, t->default_value, d_keys, n, (float*)d_out, d_found, stream, {FindPath::Located, d_slots_out, -1, out_dtype});
     if (n > t->max_batch) return fail(MEE_ERR_BATCH_TOO_LARGE, "%s: n=%zu exceeds config.max_batch=%llu", name, n, (unsigned long long)t->max_batch);
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
-    uint32_t apply_grid, nbk;
-    bool apply_full;
-    const uint32_t nbk_hash = bucket_count_for(t, n, st, &apply_grid, &nbk, &apply_full);
-    uint32_t part_blocks, per_block;
-    part_geometry((uint32_t)n, kFindPrepareThreads, part_blocks, per_block);
-    const bool separate = t->prepare_debug & 1;
-    if (separate) part_blocks = 0;
+    const bool separate = t->prepare_debug & 1;   // the partition as launches of its own behind the find
+    const PartPlan plan = bucket_plan(t->bk, n, st, separate ? kPartThreads : kFindPrepareThreads);
+    const uint32_t part_blocks = separate ? 0u : plan.blocks;
     const bool cached_out = t->find_nt >= 0 && (t->find_nt & 4);
     with_row_shape(t->dim4, [&](auto d4) {
         constexpr int R = d4 == 16 ? kFindPrepareR : d4 == 32 ? 2 : 1;
         const unsigned find_cap = t->prepare_debug >> 8;
         const unsigned find_blocks = grid_for(n, (kFindPrepareThreads / 64) * 4u * (unsigned)R, find_cap ? find_cap : 1u << 22);
         auto launch = [&](auto ntc) {
-            find_prepare_kernel<d4, R, ntc><<<part_blocks + find_blocks, kFindPrepareThreads, sizeof(PartHot) + nbk * 4, st>>>(t->keys, (const f32x4*)t->values, t->nb, d_keys, n,
-                (f32x4*)d_out, d_found, t->default_value, t->dim4, d_slots_out, handle_tag_of(t), part_blocks, nbk_hash, nbk, per_block, t->bk, &t->ctr->status, t->op, t->bk.xcd_split);
+            find_prepare_kernel<d4, R, ntc><<<part_blocks + find_blocks, kFindPrepareThreads, sizeof(PartHot) + plan.nbk * 4, st>>>(t->keys, (const f32x4*)t->values, t->nb, d_keys, n,
+                (f32x4*)d_out, d_found, t->default_value, t->dim4, d_slots_out, handle_tag_of(t), part_blocks, plan.nbk_hash, plan.nbk, plan.per_block, t->bk, &t->ctr->status, t->op, t->bk.xcd_split);
         };
         if (out_dtype == MEE_DTYPE_BF16) with_value<256 + 68, 256 + 64>(cached_out ? 256 + 68 : 256 + 64, launch);   // NT | 256: bf16 rows (find_span)
         else with_value<68, 64>(cached_out ? 68 : 64, launch);
     });
     MEE_HIP(hipGetLastError());
-    if (separate) { if (int rc = bucket_apply_prepare(t, d_keys, (uint32_t)n, st)) return rc; }
-    else { t->part_blocks = part_blocks; t->part_per_block = per_block; t->part_nbk = nbk; t->part_nbk_hash = nbk_hash; t->part_grid = apply_grid; t->part_full = apply_full; }
-    t->prepared_n = n; t->prepared_keys = d_keys; t->prepared_by_forward = true;
+    if (separate) { if (int rc = bucket_partition_launch(t, d_keys, (uint32_t)n, plan, st)) return rc; }
+    t->pending = {plan, n, d_keys, true};
     return MEE_OK;
 }
 extern "C" {

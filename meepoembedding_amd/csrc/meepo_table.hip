@@ -471,8 +471,8 @@ namespace mee {
 // that follows finds nothing prepared and partitions its batch again (same results, one partition launch more).  `stream`: where the mutator
 // runs.  A partition the caller asked for explicitly (mee_apply_prepare, perhaps on another stream) is the caller's to finish or discard.
 int check_batch(mee_table* t, size_t n, const char* op, void* stream, bool needs_group_table, bool drop_pending) {
-    if (t->prepared_n && needs_group_table) {
-        if (!drop_pending || !t->prepared_by_forward)
+    if (t->pending.n && needs_group_table) {
+        if (!drop_pending || !t->pending.by_forward)
             return fail(MEE_ERR_INVALID_ARG, "%s: a prepared apply is pending on this table (finish it with mee_apply_* or mee_apply_discard)", op);
         if (int rc = mee_apply_discard(t, stream)) return rc;
     }
@@ -821,7 +821,6 @@ int mee_locate(const mee_table* t, const int64_t* d_keys, size_t n, int64_t* d_s
     return MEE_OK;
 }
 
-// group the batch's keys and plan the duplicate reduction (everything that does not need the grads)
 // One sparse-optimizer step: the bucketed apply (meepo_apply.hip) — partition by hash bucket (skipped after mee_apply_prepare / a training
 // forward that carried it), then ONE kernel of block-local LDS dedup + update.  (Rounds 1-3 kept a second implementation beside it, a global
 // group table with five launches per step; it is gone: batches of any size up to max_batch take this path.)
@@ -835,20 +834,22 @@ static int apply_common(mee_table* t, const int64_t* d_keys, const float* d_grad
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
     const uint32_t nn = (uint32_t)n;
-    if (t->prepared_n) {  // the grad-independent half was done ahead of time (mee_apply_prepare), possibly on another stream
-        if (t->prepared_n != n || t->prepared_keys != d_keys)
+    PartPlan plan;
+    if (t->pending.n) {  // the grad-independent half was done ahead of time (mee_apply_prepare), possibly on another stream
+        if (t->pending.n != n || t->pending.keys != d_keys)
             return fail(MEE_ERR_INVALID_ARG, "%s: keys/n differ from the pending mee_apply_prepare", name);
-        t->prepared_n = 0; t->prepared_keys = nullptr;
-    } else if (int rc = bucket_apply_prepare(t, d_keys, nn, st)) return rc;
-    return bucket_apply_launch(t, d_grads, nn, a, d_gidx, d_slots, st);
+        plan = t->pending.plan;
+        t->pending = {};
+    } else if (int rc = bucket_apply_prepare(t, d_keys, nn, st, plan)) return rc;
+    return bucket_apply_launch(t, plan, d_grads, nn, a, d_gidx, d_slots, st);
 }
 
 static OptArgs adam_args(float lr, float beta1, float beta2, float eps, uint64_t step);
 
 // ---- grouped apply: ONE sparse-optimizer step over the jagged batch of a whole group (meepo_group.hip holds the group) ----
-// locate (member << 48 | slot per position) -> the ordinary group / plan passes with the located rows as "keys" (two
-// occurrences of a key of one table are the same row; keys of different tables never collide) -> the three apply passes
-// with the probe replaced by decoding the located row.  The group's scratch table lends the group table / lists / counters.
+// locate (member << 48 | slot per position) -> the bucketed apply with the located rows as "keys" (two occurrences of a key of one
+// table are the same row; keys of different tables never collide) and as slot handles: its probe is replaced by decoding the located
+// row.  The group's scratch table lends the partition's scratch and the counters.
 static int group_apply_common(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n,
                               const OptArgs& a, void* stream, const char* name, uint64_t off_stride = 1, const uint32_t* d_gidx = nullptr,
                               const int64_t* d_located = nullptr) {
@@ -871,8 +872,9 @@ static int group_apply_common(mee_group* g, const int64_t* d_keys, const uint64_
     // the located rows are perfect keys (member << 48 | slot; absent positions EMPTY): the bucketed apply takes them as the batch's keys AND as
     // its slot handles — partition, then one dedup + update kernel whose work items fetch their member's planes from the descriptors (r1-r2: a
     // plan pass over a group table + three kernels; 5 launches, 26 tables x 8192 keys 158 us)
-    if (int rc = bucket_apply_prepare(t, gslot, nn, st)) return rc;
-    return bucket_apply_launch(t, d_grads, nn, a, d_gidx, gslot, st, g->d_desc, g->n_tables);
+    PartPlan plan;
+    if (int rc = bucket_apply_prepare(t, gslot, nn, st, plan)) return rc;
+    return bucket_apply_launch(t, plan, d_grads, nn, a, d_gidx, gslot, st, g->d_desc, g->n_tables);
 }
 
 int mee_group_apply_adagrad(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr,
@@ -886,12 +888,7 @@ int mee_group_apply_adam(mee_group* g, const int64_t* d_keys, const uint64_t* d_
                          float beta1, float beta2, float eps, uint64_t step, void* stream) {
     MEE_RANGE("mee_group_apply_adam");
     if (step == 0) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_adam: step must be >= 1");
-    OptArgs a{};
-    a.kind = MEE_OPT_ADAM; a.eps = eps;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    a.step_size = (float)((double)lr * sqrt(bc2) / bc1);  // SPEC.md §4
-    a.omb1 = 1.0f - beta1; a.omb2 = 1.0f - beta2;
-    return group_apply_common(g, d_keys, d_offsets, d_grads, n, a, stream, "mee_group_apply_adam");
+    return group_apply_common(g, d_keys, d_offsets, d_grads, n, adam_args(lr, beta1, beta2, eps, step), stream, "mee_group_apply_adam");
 }
 
 int mee_group_apply_adagrad_pooled(mee_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table,
@@ -922,12 +919,13 @@ int mee_apply_prepare(mee_table* t, const int64_t* d_keys, size_t n, void* strea
     MEE_RANGE("mee_apply_prepare");
     if (!t || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_apply_prepare: null argument");
     if (t->optimizer == MEE_OPT_NONE) return fail(MEE_ERR_UNSUPPORTED, "mee_apply_prepare: table has no optimizer");
-    if (t->prepared_n) return fail(MEE_ERR_INVALID_ARG, "mee_apply_prepare: a prepared apply is already pending");
+    if (t->pending.n) return fail(MEE_ERR_INVALID_ARG, "mee_apply_prepare: a prepared apply is already pending");
     if (n > t->max_batch) return fail(MEE_ERR_BATCH_TOO_LARGE, "mee_apply_prepare: n=%zu exceeds config.max_batch=%llu", n, (unsigned long long)t->max_batch);
     if (n == 0) return MEE_OK;
     DeviceGuard g(t->device);
-    if (int rc = bucket_apply_prepare(t, d_keys, (uint32_t)n, as_stream(stream))) return rc;   // the partition half of the apply: positions and keys in bucket order
-    t->prepared_n = n; t->prepared_keys = d_keys; t->prepared_by_forward = false;
+    PartPlan plan;
+    if (int rc = bucket_apply_prepare(t, d_keys, (uint32_t)n, as_stream(stream), plan)) return rc;   // the partition half of the apply: positions and keys in bucket order
+    t->pending = {plan, n, d_keys, false};
     return MEE_OK;
 }
 
@@ -960,12 +958,10 @@ int mee_find_or_insert_located_prepare_as(mee_table* t, const int64_t* d_keys, s
 int mee_apply_discard(mee_table* t, void* stream) {
     MEE_RANGE("mee_apply_discard");
     if (!t) return fail(MEE_ERR_INVALID_ARG, "mee_apply_discard: null table");
-    if (!t->prepared_n) return MEE_OK;
+    if (!t->pending.n) return MEE_OK;
     DeviceGuard g(t->device);
-    const uint32_t nn = (uint32_t)t->prepared_n;
-    (void)nn;
     if (int rc = bucket_apply_discard(t, as_stream(stream))) return rc;   // (counts the partition as consumed; it leaves nothing else behind)
-    t->prepared_n = 0; t->prepared_keys = nullptr;
+    t->pending = {};
     return MEE_OK;
 }
 

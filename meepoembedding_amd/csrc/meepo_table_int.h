@@ -39,7 +39,7 @@ __device__ __forceinline__ void group_release_entry(const GroupTable& g, uint32_
 }
 struct BatchScratch {          // max_batch entries, indexed by batch position unless noted
     uint32_t *hidx;            // insert: the group-table index of each position's key; mee_dedup_sum: the sorted source lists of buckets beyond the LDS list
-    uint32_t *occ;             // lent to the bucketed machinery as its position list (BucketScratch::pos); the admission pass's skip bytes
+    uint32_t *occ;             // mee_dedup_sum: the hand-over items of its long runs; the admission pass's skip bytes
     uint8_t* fmask;            // found mask of find_or_insert's first pass when the caller passes none
     double* gacc;              // [max_part][dim] fp64 partial-sum rows of the bucketed apply's long runs (tables with an optimizer)
     uint32_t max_part;         // rows of gacc
@@ -79,6 +79,15 @@ struct BucketScratch {
     uint32_t sum_part_rows;
     BucketScratch* dev_copy;   // this struct in device memory (what the FULL apply kernel reads instead of 40 SGPRs of kernel arguments)
 };
+// How one batch is partitioned and applied: decided once on the host in front of the partition (part_plan_for, meepo_apply_part.h), read by the partition
+// launch and by every consumer of it.  (Here and not beside its arithmetic because mee_table keeps the plan of a pending batch.)
+struct PartPlan {
+    uint32_t nbk_hash, nbk;      // hash buckets; hash buckets + one bucket per hot key
+    uint32_t grid;               // blocks of the FULL apply kernel: one round of the block slots (LEAN: block = bucket, nbk blocks)
+    bool full;                   // the apply kernel: FULL | LEAN (meepo_apply.hip)
+    uint32_t blocks, per_block;  // partition blocks, batch positions per partition block
+    bool totals_by_atomics;      // the partition blocks add up the bucket totals themselves (else: bkt_totals_kernel behind them)
+};
 
 }  // namespace mee
 
@@ -105,9 +114,13 @@ struct mee_table {
     uint64_t table_bytes, workspace_bytes;
     uint64_t generation;        // bumped whenever the planes move (mee_reserve): cached descriptors (mee_group) re-read them
     uint32_t handle_epoch;      // bumped by every call that can move or free a row (remove / clear / reserve): tags the slot handles of mee_find_located
-    // a prepared (grouped + planned) apply waiting for its grads: mee_apply_prepare .. mee_apply_*
-    uint64_t prepared_n;
-    const int64_t* prepared_keys;
+    // a partitioned batch waiting for its grads (mee_apply_prepare / a training forward .. mee_apply_*): the only partition that outlives the call that made it
+    struct Pending {
+        mee::PartPlan plan;     // as the partition was launched: all the apply reads about it
+        uint64_t n;             // 0: nothing pending
+        const int64_t* keys;
+        bool by_forward;        // it came with a training forward (mee_find*_located_prepare): a mutator in between drops it
+    } pending;
     uint32_t epoch;             // batch number of insert / apply launches (tags insert's election flag; never 0)
     // performance knobs (never change results): see mee_set_tuning()
     int find_rounds;            // keys in flight per tile in the find kernel: 1, 2, 4 or 8
@@ -127,12 +140,8 @@ struct mee_table {
     // RAW key stream of a batch — dedup_keys, dedup_sum, assign.  A training step on one table runs them beside an apply over the batch's DISTINCT keys (the sharded paths with
     // pre-exchange aggregation): the apply's "no skew" report sent the next dedup of the (skewed) raw stream back to its first-skewed-batch path, every step.
     mee::BucketScratch bk_dd;
-    bool prepared_by_forward;   // the pending partition came with a training forward (mee_find*_located_prepare): a mutator in between drops it
-    uint32_t part_nbk_hash;   // ... of which the first part_nbk_hash are hash buckets (the rest: one per hot key)
-    bool part_full;           // ... and the apply kernel chosen for it (FULL | LEAN: meepo_apply.hip)
     void* full_ready[4];      // streams whose queue already holds the FULL kernel's scratch (bucket_apply_launch), newest first
     uint32_t full_ready_n;
-    uint32_t part_blocks, part_per_block, part_nbk, part_grid;   // bucketed apply: how the latest partition split the batch (blocks, batch positions per block, buckets) and the apply grid that goes with it
 };
 
 namespace mee {
@@ -168,20 +177,19 @@ __device__ __forceinline__ void update_row(const OptArgs& a, float4* values, flo
 uint32_t xcd_split_for_device(int device);   // the calibrated share of a bucket pair's hash range that goes to the even bucket (0 = even halves)
 int bucket_scratch_alloc(mee_table* t);
 void bucket_scratch_free(mee_table* t);
-int bucket_apply_prepare(mee_table* t, const int64_t* d_keys, uint32_t n, hipStream_t st);
+// the plan of one partition from the stream's skew state `sk` (t->bk: the apply's; t->bk_dd: the raw-stream operators'); once per partition: it ages sk.skew_sticky
+PartPlan bucket_plan(BucketScratch& sk, uint64_t n, hipStream_t st, uint32_t threads, uint32_t slots_of = 0, uint32_t bucket_max_of = 0);
+int bucket_partition_launch(mee_table* t, const int64_t* d_keys, uint32_t n, const PartPlan& plan, hipStream_t st);
+int bucket_totals_launch(const BucketScratch& bk, const PartPlan& plan, hipStream_t st);
+int bucket_apply_prepare(mee_table* t, const int64_t* d_keys, uint32_t n, hipStream_t st, PartPlan& plan);   // bucket_plan + bucket_partition_launch
 int bucket_apply_discard(mee_table* t, hipStream_t st);
-int bucket_apply_launch(mee_table* t, const float* d_grads, uint32_t n, const OptArgs& a, const uint32_t* d_gidx, const int64_t* d_slots, hipStream_t st,
+int bucket_apply_launch(mee_table* t, const PartPlan& plan, const float* d_grads, uint32_t n, const OptArgs& a, const uint32_t* d_gidx, const int64_t* d_slots, hipStream_t st,
                         const GroupDesc* d_desc = nullptr, uint32_t n_tables = 0);
-bool bucket_totals_by_atomics(uint32_t blocks, uint32_t nbk);
-int bucket_totals_launch(mee_table* t, uint32_t nbk, uint32_t blocks, hipStream_t st, const mee::BucketScratch* bk = nullptr /* default: the apply's */);
-int bucket_apply_prepare_as(mee_table* t, const int64_t* d_keys, uint32_t n, hipStream_t st, uint32_t nbk_hash, uint32_t nbk, uint32_t blocks, uint32_t per_block);
 // duplicate elimination and last-wins elections on the same partition (meepo_dedup.hip)
 int bucket_dedup_keys(mee_table* t, const int64_t* d_keys, uint32_t n, int64_t* d_uniq, int64_t* d_inverse, int64_t miss_index, hipStream_t st);
 int bucket_assign(mee_table* t, float* plane, const int64_t* d_keys, const float* d_values, uint32_t n, uint8_t* d_found, hipStream_t st);
 int bucket_dedup_sum(mee_table* t, const int64_t* d_keys, const float* d_grads, uint32_t n, int64_t* d_uniq, float* d_gsum, uint32_t* d_counts, int64_t* d_inverse, int64_t miss_index,
                      hipStream_t st);
-uint32_t bucket_count_for(mee_table* t, uint64_t n, hipStream_t st, uint32_t* grid_out = nullptr, uint32_t* nbk_total_out = nullptr, bool* full_out = nullptr,
-                          uint32_t slots_of = 0, uint32_t bucket_max_of = 0, mee::BucketScratch* state = nullptr /* whose skew state plans the batch; default: the apply's (t->bk) */);
 
 // ---- host helpers the table's translation units share (meepo_table.hip, meepo_find.hip, meepo_export.hip) ------------------------------
 inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }

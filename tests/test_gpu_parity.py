@@ -1249,6 +1249,33 @@ def test_apply_prepare_split(dev):
     np.testing.assert_allclose(g_[2][a], o_[2][b], rtol=RTOL, atol=ATOL)
 
 
+def test_apply_prepare_then_tuning(dev):
+    """mee_set_tuning between mee_apply_prepare and the apply changes nothing about the pending batch: the apply runs with the bucket count, the
+    strides and the kernel (LEAN / FULL) its partition was planned with.  A skewed batch (duplicates and one hot key) prepared under the default
+    knobs and applied under "apply_bucket_max" 128 / FULL / no skew adaptation, then one prepared under those and applied under the defaults."""
+    dim, n_keys, batch = 64, 20000, 30000
+    keys = synth.keys_np(72, 0, n_keys); rows = synth.rows_np(keys, dim, 2)
+    t = LookupTable(32768, dim, device=dev, optimizer=OPT_ADAGRAD, max_batch=batch, initial_accumulator=0.1)
+    o = oracle.OracleTable(32768, dim, optimizer=oracle.OPT_ADAGRAD, initial_accumulator=0.1)
+    t.insert(T(keys, dev), T(rows, dev)); o.insert(keys, rows)
+    rng = np.random.default_rng(10)
+    knobs = ("apply_bucket_max", "apply_kernel", "apply_skew_adapt")
+    for at_apply in ((128, 1, 0), (0, 0, 1)):
+        bk = keys[np.minimum(rng.zipf(1.3, size=batch) - 1, n_keys - 1)]
+        g = (rng.standard_normal((batch, dim)) * 0.01).astype(np.float32)
+        dk, dg = T(bk, dev), T(g, dev)
+        t.apply_prepare(dk)
+        for name, value in zip(knobs, at_apply):
+            t.set_tuning(name, value)
+        t.apply_adagrad(dk, dg, lr=0.01, eps=1e-10); o.apply_adagrad(bk, g, 0.01, 1e-10)
+    assert t.status() == 0
+    g_ = [x.cpu().numpy() for x in t.export(with_state=True)[:3]]; o_ = o.export(with_state=True)[:3]
+    a, b = np.argsort(g_[0]), np.argsort(o_[0])
+    assert np.array_equal(g_[0][a], o_[0][b])
+    np.testing.assert_allclose(g_[1][a], o_[1][b], rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(g_[2][a], o_[2][b], rtol=RTOL, atol=ATOL)
+
+
 def test_export_import_roundtrip_with_state(dev):
     """export(with_state) -> import_ into a fresh table of another capacity (chunked by max_batch): identical table."""
     dim, n = 32, 25000
