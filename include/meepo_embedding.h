@@ -433,6 +433,32 @@ int mee_scatter_rows(const void* d_rows, const int64_t* d_perm, size_t n, size_t
 int mee_gather_rows(const void* d_rows, const int64_t* d_perm, size_t n, size_t row_bytes, void* d_out,
                     void* stream);
 
+/* ---- embedding bags over a sharded table (SPEC.md §5 "Pooled lookups"): the partition is stable, so the positions of bag b owned by rank p are
+ * one contiguous RUN of destination segment p.  The owner pools every run (mee_find_pooled over the received keys) and one row per run travels
+ * instead of one per key.  All three take a stream, never synchronise and can be captured.  Caller data is never used as an address unchecked:
+ * perm entries are only compared, bags and run indices are kept inside their arrays (as mee_apply_*_indexed clamps d_grad_index).
+ *
+ * mee_bag_runs — the source's side.  d_perm[n] / d_counts[n_shards] are what mee_partition wrote for the batch, d_bag_offsets[n_bags + 1] the bags of
+ * the batch (they must partition [0, n): offsets[0] = 0, non-decreasing, offsets[n_bags] = n).  A run starts at the first entry of a segment and
+ * wherever the bag of perm[q] differs from the bag of perm[q - 1] (the bag of a position: by search in d_bag_offsets; empty bags have no run).
+ *   d_run_bag[R]  (uint32) the bag of each run        d_run_len[R]  (uint32) its positions        d_run_counts[n_shards]  (uint64) runs per segment
+ * Runs are listed in segment order, R = sum(d_run_counts) <= n: size d_run_bag / d_run_len for n.  n <= the router's max_batch. */
+int mee_bag_runs(mee_router* r, const int64_t* d_perm, const uint64_t* d_counts, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
+                 uint32_t* d_run_bag, uint32_t* d_run_len, uint64_t* d_run_counts, void* stream);
+/* mee_run_offsets — the owner's side.  d_run_len[n_runs] = the run lengths received from all ranks, in source-rank order (n_runs <= n_shards x
+ * max_batch).  d_offsets[n_runs + 1] (uint64) = their exclusive prefix sum: the d_bag_offsets of mee_find_pooled over the received keys, one
+ * "bag" per run.  d_run_of_key[n_keys] (uint32, nullable) = the run of every received key: the d_grad_index of mee_apply_*_indexed over one
+ * gradient row per run. */
+int mee_run_offsets(mee_router* r, const uint32_t* d_run_len, size_t n_runs, uint64_t* d_offsets, uint32_t* d_run_of_key, size_t n_keys,
+                    void* stream);
+/* mee_combine_bag_runs — back at the source.  d_partials[n_runs, dim] (fp32, 16-byte aligned) = the owners' pooled rows of this rank's runs, in
+ * the order mee_bag_runs listed them; d_run_bag / d_run_counts as it wrote them.  d_out[n_bags, dim], fp32 or bf16 (out_dtype = MEE_DTYPE_*):
+ * the partial rows of bag b in ascending owner rank — the first one copied, each further one added in fp32 (no fma) —, for MEE_POOL_MEAN
+ * then divided by (float)(bag length), for bf16 then rounded once; a bag without a run (an empty bag) is zeros.  No atomics: the order is this
+ * one on every run.  dim: a positive multiple of 4. */
+int mee_combine_bag_runs(mee_router* r, const float* d_partials, const uint32_t* d_run_bag, const uint64_t* d_run_counts, size_t n_runs,
+                         const uint64_t* d_bag_offsets, size_t n_bags, uint32_t dim, int mode, void* d_out, uint32_t out_dtype, void* stream);
+
 /* ---- sharded find over peer-mapped memory (README.md:2 "distributed"; SPEC.md §5) ---------------------------------
  * One context per rank; all ranks use the same n_shards / slots_per_peer / max_batch / dim.  The local buffers
  * (key inbox, destination inbox, fill counts, result rows, found bytes, and the payload-row inbox if any) are exported as HIP IPC handles, the caller

@@ -168,6 +168,10 @@ PROTOTYPES = {
     "mee_p2p_status": (C.c_int, [_vp, C.POINTER(_u32), _vp]),
     "mee_scatter_rows": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "mee_gather_rows": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    # embedding bags over a sharded table: run bookkeeping and the combination of the owners' partial rows (meepo_router.hip)
+    "mee_bag_runs": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "mee_run_offsets": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "mee_combine_bag_runs": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _u32, C.c_int, _vp, _u32, _vp]),
     # row-sharded table over RCCL (meepo_sharded.hip)
     "mee_comm_unique_id": (C.c_int, [_vp]),
     "mee_comm_create": (C.c_int, [_vp, _u32, _u32, _i32, C.POINTER(_vp)]),

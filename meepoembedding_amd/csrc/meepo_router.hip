@@ -21,6 +21,8 @@ struct mee_router {
     uint32_t max_blocks;
     uint32_t* blockcnt;  // [max_blocks][n_shards] counts, then exclusive offsets inside the shard segment
     uint64_t* base;      // [n_shards] start of each shard segment
+    uint64_t* run_base;  // [n_shards] start of each segment's runs (mee_bag_runs: the partition's own `base` stays as the partition left it)
+    uint64_t* run_sums;  // [max_blocks * n_shards + 1] per-block sums of received run lengths (mee_run_offsets)
 };
 
 struct mee_p2p {
@@ -171,6 +173,253 @@ static int permute_rows(const void* d_rows, const int64_t* d_perm, size_t n, siz
     }
     MEE_HIP(hipGetLastError());
     return MEE_OK;
+}
+
+// ---- embedding bags over a sharded table (SPEC.md §5 "Pooled lookups") ------------------------------------------------------
+// The partition is stable, so inside a destination segment the batch positions ascend and the bags of those positions never decrease: the
+// positions of bag b owned by rank p are one contiguous RUN of segment p.  The source lists its runs (bag_runs: the same three-launch
+// counting sort as the partition, with "first position of a run in segment p" in the place of "key owned by p"), the owner turns the
+// received run lengths into the bag_offsets / grad_index of its local pooled lookup / indexed apply (run_offsets), and the source adds
+// the owners' partial rows up in rank order (combine_bag_runs).  Nothing here trusts caller data with an address: perm entries are only
+// compared, bags come out of a search over [0, n_bags), run indices are kept inside [0, n_runs).
+constexpr int kRunBlock = 1024;   // positions per block of the run kernels (one per thread)
+
+// the last b in [0, m) with off[b] <= i (m >= 1): the bag of batch position i under bag_offsets, the run of received key i under run offsets
+__device__ __forceinline__ uint32_t last_not_above(const uint64_t* __restrict__ off, uint32_t m, uint64_t i) {
+    uint32_t lo = 0, hi = m - 1;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (off[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+struct RunPos {
+    bool head;        // this position starts a run
+    uint32_t seg;     // its destination segment (0xFFFFFFFF when it is no run start: the owner id of the counting sort)
+    uint32_t bag;
+    uint32_t seg_end; // one past the segment's last position
+};
+
+// what position q = blockIdx.x * kRunBlock + threadIdx.x is; all threads of the block call it (LDS staging + barriers)
+__device__ __forceinline__ RunPos run_position(const int64_t* __restrict__ perm, const uint64_t* __restrict__ counts, uint32_t g, uint32_t n,
+                                               const uint64_t* __restrict__ off, uint32_t n_bags, uint32_t* s_end, uint32_t* s_bag) {
+    if (threadIdx.x == 0) {   // segment ends, never past n whatever the counts say
+        uint64_t acc = 0;
+        for (uint32_t p = 0; p < g; ++p) {
+            const uint64_t c = counts[p];
+            acc += c < n ? c : n;
+            acc = acc < n ? acc : n;
+            s_end[p] = (uint32_t)acc;
+        }
+    }
+    __syncthreads();
+    const uint32_t q = blockIdx.x * kRunBlock + threadIdx.x;
+    const bool inb = q < s_end[g - 1];
+    uint32_t seg = 0;
+    while (seg + 1 < g && s_end[seg] <= q) ++seg;   // g <= 64 LDS words
+    const uint32_t seg_begin = seg ? s_end[seg - 1] : 0;
+    const uint32_t bag = inb ? last_not_above(off, n_bags, (uint64_t)perm[q]) : 0;
+    s_bag[threadIdx.x] = bag;
+    __syncthreads();
+    uint32_t prev = 0;
+    if (inb && q > seg_begin) prev = threadIdx.x ? s_bag[threadIdx.x - 1] : last_not_above(off, n_bags, (uint64_t)perm[q - 1]);
+    RunPos r;
+    r.head = inb && (q == seg_begin || bag != prev);
+    r.seg = r.head ? seg : 0xFFFFFFFFu;
+    r.bag = bag;
+    r.seg_end = s_end[seg];
+    return r;
+}
+
+__global__ __launch_bounds__(kRunBlock) void run_count_kernel(const int64_t* __restrict__ perm, const uint64_t* __restrict__ counts, uint32_t g, uint32_t n,
+                                                              const uint64_t* __restrict__ off, uint32_t n_bags, uint32_t* blockcnt) {
+    __shared__ uint32_t s_end[kMaxShards], s_bag[kRunBlock], wcnt[kRunBlock / 64][kMaxShards];
+    const RunPos r = run_position(perm, counts, g, n, off, n_bags, s_end, s_bag);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (uint32_t p = 0; p < g; ++p) {
+        const uint64_t m = __ballot(r.seg == p);
+        if (lane == 0) wcnt[w][p] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    if (threadIdx.x < g) {
+        uint32_t c = 0;
+#pragma unroll
+        for (int ww = 0; ww < kRunBlock / 64; ++ww) c += wcnt[ww][threadIdx.x];
+        blockcnt[(uint64_t)blockIdx.x * g + threadIdx.x] = c;
+    }
+}
+
+__global__ __launch_bounds__(kRunBlock) void run_scatter_kernel(const int64_t* __restrict__ perm, const uint64_t* __restrict__ counts, uint32_t g, uint32_t n,
+                                                                const uint64_t* __restrict__ off, uint32_t n_bags, const uint32_t* __restrict__ blockoff,
+                                                                const uint64_t* __restrict__ run_base, uint32_t* __restrict__ run_bag,
+                                                                uint32_t* __restrict__ run_len) {
+    __shared__ uint32_t s_end[kMaxShards], s_bag[kRunBlock], wcnt[kRunBlock / 64][kMaxShards];
+    const RunPos r = run_position(perm, counts, g, n, off, n_bags, s_end, s_bag);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t rank = 0;
+    for (uint32_t p = 0; p < g; ++p) {
+        const uint64_t m = __ballot(r.seg == p);
+        if (r.seg == p) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1));
+        if (lane == 0) wcnt[w][p] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    if (r.head) {
+        for (int ww = 0; ww < w; ++ww) rank += wcnt[ww][r.seg];
+        const uint64_t dst = run_base[r.seg] + blockoff[(uint64_t)blockIdx.x * g + r.seg] + rank;   // < the number of run starts <= n
+        const uint32_t q = blockIdx.x * kRunBlock + threadIdx.x;
+        // the run ends at the segment's first position of a later bag: positions ascend inside a segment
+        const uint64_t bag_end = off[r.bag + 1];
+        uint32_t lo = q + 1, hi = r.seg_end;
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if ((uint64_t)perm[mid] < bag_end) lo = mid + 1; else hi = mid;
+        }
+        run_bag[dst] = r.bag;
+        run_len[dst] = lo - q;
+    }
+}
+
+// exclusive scan of one value per thread over the block; `total` = the block's sum.  s_w: blockDim.x / 64 words of LDS
+__device__ __forceinline__ uint64_t block_scan_exclusive(uint64_t v, uint64_t* s_w, uint64_t& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    uint64_t incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t t = __shfl_up(incl, d);
+        if (lane >= d) incl += t;
+    }
+    if (lane == 63) s_w[w] = incl;
+    __syncthreads();
+    uint64_t before = 0;
+    total = 0;
+    for (int ww = 0; ww < nw; ++ww) {
+        if (ww < w) before += s_w[ww];
+        total += s_w[ww];
+    }
+    __syncthreads();   // s_w may be written again
+    return before + incl - v;
+}
+
+__global__ __launch_bounds__(kRunBlock) void run_len_sum_kernel(const uint32_t* __restrict__ run_len, uint64_t n_runs, uint64_t* __restrict__ sums) {
+    __shared__ uint64_t s_w[kRunBlock / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
+    uint64_t total;
+    (void)block_scan_exclusive(i < n_runs ? run_len[i] : 0, s_w, total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// one block: the block sums become their exclusive prefix
+__global__ __launch_bounds__(kRunBlock) void run_len_scan_kernel(uint64_t* sums, uint32_t n_blocks) {
+    __shared__ uint64_t s_w[kRunBlock / 64];
+    uint64_t carry = 0;
+    for (uint32_t b0 = 0; b0 < n_blocks; b0 += kRunBlock) {   // block-uniform
+        const uint32_t b = b0 + threadIdx.x;
+        uint64_t total;
+        const uint64_t ex = block_scan_exclusive(b < n_blocks ? sums[b] : 0, s_w, total);
+        if (b < n_blocks) sums[b] = carry + ex;
+        carry += total;
+    }
+}
+
+__global__ __launch_bounds__(kRunBlock) void run_offsets_kernel(const uint32_t* __restrict__ run_len, uint64_t n_runs, const uint64_t* __restrict__ sums,
+                                                                uint64_t* __restrict__ offsets) {
+    __shared__ uint64_t s_w[kRunBlock / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
+    const uint64_t len = i < n_runs ? run_len[i] : 0;
+    uint64_t total;
+    const uint64_t ex = sums[blockIdx.x] + block_scan_exclusive(len, s_w, total);
+    if (i < n_runs) offsets[i] = ex;
+    if (i + 1 == n_runs) offsets[n_runs] = ex + len;
+}
+
+__global__ void run_of_key_kernel(const uint64_t* __restrict__ offsets, uint32_t n_runs, uint64_t n_keys, uint32_t* __restrict__ run_of_key) {
+    for (uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k < n_keys; k += (uint64_t)gridDim.x * blockDim.x)
+        run_of_key[k] = last_not_above(offsets, n_runs, k);   // in [0, n_runs) whatever the lengths add up to
+}
+
+// out[b] = the partial rows of bag b added up in ascending segment (= owner rank) order: the first one copied, each further one added in fp32 (no
+// fma: the file is compiled with -ffp-contract=off), MEAN then divides by (float)length; a bag without a partial is zeros.  One 16-lane tile per
+// bag, four bags per wave.  The bag's run in segment p is found by binary search (run_bag ascends inside a segment): lane tl of the tile searches
+// segment 16 k + tl, so the searches of 16 segments are in flight together, and their results come back to the whole tile by shuffles in segment
+// order.  Rows move as float4, up to four of them in flight per tile; the column groups of a row wider than the instance (run-time dim) are
+// independent sums and take one sweep over the found runs each, so no accumulator array is indexed at run time.
+template <int DIM4, bool BF16>
+__global__ __launch_bounds__(256) void combine_bag_runs_kernel(const float4* __restrict__ partials, const uint32_t* __restrict__ run_bag,
+                                                               const uint64_t* __restrict__ run_counts, uint32_t g, uint64_t n_runs,
+                                                               const uint64_t* __restrict__ bag_offsets, uint64_t n_bags, uint32_t dim4_rt, int mean,
+                                                               void* __restrict__ out) {
+    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    const uint32_t dim4 = DIM4 ? DIM4 : dim4_rt;
+    // lane l holds the run range of segment l (g <= 64), never past n_runs
+    uint64_t seg_hi = 0;
+    {
+        const uint64_t c = (uint32_t)lane < g ? run_counts[lane] : 0;
+        uint64_t incl = c < n_runs ? c : n_runs;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint64_t t = __shfl_up(incl, d);
+            if (lane >= d) incl += t;
+        }
+        seg_hi = incl < n_runs ? incl : n_runs;
+    }
+    const uint64_t seg_lo_all = __shfl_up(seg_hi, 1);
+    const uint64_t seg_lo = lane ? seg_lo_all : 0;
+    for (uint64_t b0 = wave * 4; b0 < n_bags; b0 += n_waves * 4) {   // wave-uniform
+        const uint64_t bag = b0 + tile;
+        const bool has = bag < n_bags;
+        const uint64_t begin = has ? bag_offsets[bag] : 0, end = has ? bag_offsets[bag + 1] : 0;
+        const float len = end > begin ? (float)(end - begin) : 0.f;
+        // lane tl searches segments tl, 16 + tl, 32 + tl, 48 + tl (g <= 64): where is the bag's run there?
+        int64_t mine[kMaxShards / 16];
+#pragma unroll
+        for (int k = 0; k < kMaxShards / 16; ++k) {
+            mine[k] = -1;
+            if ((uint32_t)k * 16 >= g) continue;   // wave-uniform
+            const uint32_t p = (uint32_t)k * 16 + tl;
+            uint64_t lo = __shfl(seg_lo, (int)p), hi = __shfl(seg_hi, (int)p);
+            if (p >= g || !has) hi = lo;
+            const uint64_t stop = hi;
+            while (lo < hi) {
+                const uint64_t mid = lo + (hi - lo) / 2;
+                if (run_bag[mid] < bag) lo = mid + 1; else hi = mid;
+            }
+            if (lo < stop && run_bag[lo] == bag) mine[k] = (int64_t)lo;
+        }
+        for (uint32_t c0 = 0; c0 < dim4; c0 += 16) {   // wave-uniform: one column group of 16 float4 per sweep
+            const uint32_t c = c0 + tl;
+            const bool col = DIM4 != 0 || c < dim4;
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            bool first = true;
+#pragma unroll
+            for (int k = 0; k < kMaxShards / 16; ++k) {
+                if ((uint32_t)k * 16 >= g) continue;   // wave-uniform
+#pragma unroll
+                for (int j0 = 0; j0 < 16; j0 += 4) {
+                    int64_t r[4];
+                    float4 row[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) r[u] = __shfl(mine[k], tile * 16 + j0 + u);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) row[u] = (r[u] >= 0 && col) ? partials[(uint64_t)r[u] * dim4 + c] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        if (r[u] < 0) continue;
+                        if (first) acc = row[u];
+                        else { acc.x += row[u].x; acc.y += row[u].y; acc.z += row[u].z; acc.w += row[u].w; }
+                        first = false;
+                    }
+                }
+            }
+            if (has && col) {
+                if (mean && !first && len > 0.f) { acc.x = acc.x / len; acc.y = acc.y / len; acc.z = acc.z / len; acc.w = acc.w / len; }
+                if constexpr (BF16) store_bf16x4<true>(out, bag * dim4 + c, acc);
+                else reinterpret_cast<float4*>(out)[bag * dim4 + c] = acc;
+            }
+        }
+    }
 }
 
 // ---- peer-to-peer sharded find (SPEC.md §5 without the all-to-alls) ---------------------------------------------
@@ -353,6 +602,8 @@ int mee_router_destroy(mee_router* r) {
     DeviceGuard g(r->device);
     if (r->blockcnt) (void)hipFree(r->blockcnt);
     if (r->base) (void)hipFree(r->base);
+    if (r->run_base) (void)hipFree(r->run_base);
+    if (r->run_sums) (void)hipFree(r->run_sums);
     delete r;
     return MEE_OK;
 }
@@ -372,9 +623,10 @@ int mee_router_create(int32_t device, uint64_t max_batch, uint32_t n_shards, mee
     if (!r) return fail(MEE_ERR_OUT_OF_MEMORY, "host allocation failed");
     r->device = device; r->max_batch = max_batch; r->n_shards = n_shards;
     r->max_blocks = (uint32_t)((max_batch + kPartBlock - 1) / kPartBlock);
-    r->blockcnt = nullptr; r->base = nullptr;
+    r->blockcnt = nullptr; r->base = nullptr; r->run_base = nullptr; r->run_sums = nullptr;
     if (hipMalloc((void**)&r->blockcnt, (size_t)r->max_blocks * n_shards * 4) != hipSuccess ||
-        hipMalloc((void**)&r->base, n_shards * 8) != hipSuccess) {
+        hipMalloc((void**)&r->base, n_shards * 8) != hipSuccess || hipMalloc((void**)&r->run_base, n_shards * 8) != hipSuccess ||
+        hipMalloc((void**)&r->run_sums, ((size_t)r->max_blocks * n_shards + 1) * 8) != hipSuccess) {
         mee_router_destroy(r);
         return fail(MEE_ERR_OUT_OF_MEMORY, "mee_router_create: hipMalloc failed");
     }
@@ -404,6 +656,67 @@ int mee_partition_padded(mee_router* r, const int64_t* d_keys, size_t n, int64_t
                          void* stream) {
     MEE_RANGE("mee_partition_padded");
     return partition_common(r, d_keys, n, d_send_keys, d_counts, d_perm, stream, true, "mee_partition_padded");
+}
+
+// ---- embedding bags over a sharded table: run bookkeeping and the combination of the owners' partial rows -------------------
+int mee_bag_runs(mee_router* r, const int64_t* d_perm, const uint64_t* d_counts, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
+                 uint32_t* d_run_bag, uint32_t* d_run_len, uint64_t* d_run_counts, void* stream) {
+    MEE_RANGE("mee_bag_runs");
+    if (!r || !d_counts || !d_bag_offsets || !d_run_counts || (n && (!d_perm || !d_run_bag || !d_run_len)))
+        return fail(MEE_ERR_INVALID_ARG, "mee_bag_runs: null argument");
+    if (n > r->max_batch) return fail(MEE_ERR_BATCH_TOO_LARGE, "mee_bag_runs: n=%zu exceeds max_batch=%llu", n, (unsigned long long)r->max_batch);
+    if (n_bags > 0xFFFFFFFFull || (n && n_bags == 0)) return fail(MEE_ERR_INVALID_ARG, "mee_bag_runs: n_bags must be in [1, 2^32) when there are positions (the bags partition them)");
+    DeviceGuard g(r->device);
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t nblk = (uint32_t)((n + kRunBlock - 1) / kRunBlock);
+    if (nblk) run_count_kernel<<<nblk, kRunBlock, 0, st>>>(d_perm, d_counts, r->n_shards, (uint32_t)n, d_bag_offsets, (uint32_t)n_bags, r->blockcnt);
+    part_scan_kernel<<<1, 1024, 0, st>>>(r->blockcnt, nblk, r->n_shards, r->run_base, d_run_counts);
+    if (nblk) run_scatter_kernel<<<nblk, kRunBlock, 0, st>>>(d_perm, d_counts, r->n_shards, (uint32_t)n, d_bag_offsets, (uint32_t)n_bags, r->blockcnt, r->run_base, d_run_bag, d_run_len);
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+int mee_run_offsets(mee_router* r, const uint32_t* d_run_len, size_t n_runs, uint64_t* d_offsets, uint32_t* d_run_of_key, size_t n_keys, void* stream) {
+    MEE_RANGE("mee_run_offsets");
+    if (!r || !d_offsets || (n_runs && !d_run_len)) return fail(MEE_ERR_INVALID_ARG, "mee_run_offsets: null argument");
+    if (n_runs > (size_t)r->max_batch * r->n_shards)
+        return fail(MEE_ERR_BATCH_TOO_LARGE, "mee_run_offsets: n_runs=%zu exceeds n_shards x max_batch=%llu", n_runs, (unsigned long long)(r->max_batch * r->n_shards));
+    if (n_runs > 0xFFFFFFFFull) return fail(MEE_ERR_BATCH_TOO_LARGE, "mee_run_offsets: n_runs=%zu does not fit the 32-bit run index", n_runs);
+    if (d_run_of_key && n_keys && n_runs == 0) return fail(MEE_ERR_INVALID_ARG, "mee_run_offsets: %zu keys but no run", n_keys);
+    DeviceGuard g(r->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_runs == 0) {
+        MEE_HIP(hipMemsetAsync(d_offsets, 0, 8, st));
+        return MEE_OK;
+    }
+    const uint32_t nblk = (uint32_t)((n_runs + kRunBlock - 1) / kRunBlock);   // <= max_blocks * n_shards
+    run_len_sum_kernel<<<nblk, kRunBlock, 0, st>>>(d_run_len, n_runs, r->run_sums);
+    run_len_scan_kernel<<<1, kRunBlock, 0, st>>>(r->run_sums, nblk);
+    run_offsets_kernel<<<nblk, kRunBlock, 0, st>>>(d_run_len, n_runs, r->run_sums, d_offsets);
+    if (d_run_of_key && n_keys) run_of_key_kernel<<<grid_for(n_keys, 256, 1u << 16), 256, 0, st>>>(d_offsets, (uint32_t)n_runs, n_keys, d_run_of_key);
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+int mee_combine_bag_runs(mee_router* r, const float* d_partials, const uint32_t* d_run_bag, const uint64_t* d_run_counts, size_t n_runs,
+                         const uint64_t* d_bag_offsets, size_t n_bags, uint32_t dim, int mode, void* d_out, uint32_t out_dtype, void* stream) {
+    MEE_RANGE("mee_combine_bag_runs");
+    if (!r || !d_run_counts || (n_bags && (!d_bag_offsets || !d_out)) || (n_runs && (!d_partials || !d_run_bag)))
+        return fail(MEE_ERR_INVALID_ARG, "mee_combine_bag_runs: null argument");
+    if (int rc = check_out_dtype(d_out, out_dtype, "mee_combine_bag_runs")) return rc;
+    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_combine_bag_runs: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
+    if (dim < 4 || (dim & 3) || ((uintptr_t)d_partials & 15) || (out_dtype == MEE_DTYPE_F32 && ((uintptr_t)d_out & 15)))
+        return fail(MEE_ERR_INVALID_ARG, "mee_combine_bag_runs: dim must be a positive multiple of 4 and fp32 rows 16-byte aligned");
+    if (n_runs > 0xFFFFFFFFull) return fail(MEE_ERR_BATCH_TOO_LARGE, "mee_combine_bag_runs: n_runs=%zu", n_runs);
+    if (n_bags == 0) return MEE_OK;
+    DeviceGuard g(r->device);
+    hipStream_t st = (hipStream_t)stream;
+    with_row_shape(dim / 4, [&](auto d4) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
+        combine_bag_runs_kernel<d4, bf16><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>((const float4*)d_partials, d_run_bag, d_run_counts, r->n_shards, n_runs,
+                                                                                         d_bag_offsets, n_bags, dim / 4, mode == MEE_POOL_MEAN, d_out);
+    }); });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
 }
 
 // ---- peer-to-peer exchange: lifetime and IPC ----------------------------------------------------------------------

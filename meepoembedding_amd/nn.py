@@ -171,6 +171,10 @@ def lookup_pooled(keys: torch.Tensor, bag_offsets: torch.Tensor, anchor: torch.T
     """-> (pooled rows [n_bags, dim], located rows [n] — per-position handles the backward of this step reuses; empty for a
     single table, whose apply probes for itself)"""
     layer = _layer(table_id)
+    if getattr(layer.table, "pools_with_insert", False):   # a ShardedLookupTable: the owners create unseen ids inside the pooled lookup's own exchange
+        out, _ = layer.table.find_pooled(keys, bag_offsets, "mean" if mean else "sum", insert_missing=layer.create_missing and layer.training,
+                                         **_dtype_kw(layer))
+        return out, keys.new_empty(0)
     if layer.create_missing and layer.training and keys.numel():
         # dynamic vocabulary: unseen ids enter their table (hashed initial row + optimizer state) before the pooled lookup
         if hasattr(layer.table, "apply_pooled"):

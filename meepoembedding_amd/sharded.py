@@ -10,12 +10,22 @@ is used by the CPU tests of this host logic).  Per sharded find:
 out_dtype=torch.bfloat16 on find / find_or_insert: the owner's lookup writes bf16 rows (rounded once, SPEC.md §3 "Output type") and those travel:
 dim*2 B per row on the way back.
 
+Embedding bags (find_pooled, apply_*(grad_index=...); SPEC.md §5 "Pooled lookups"): the partition is stable, so the positions of one bag that one
+owner holds are a contiguous run of that owner's segment.  The owner pools each run and ONE fp32 row per run travels (back in the lookup, out in
+the backward) instead of one per key:
+
+    partition(keys)  ->  bag_runs  ->  all-to-all key counts + run counts  ->  all-to-all keys (8 B) and run lengths (4 B)
+    owner: run_offsets, local find_pooled(sum) over the runs  ->  all-to-all partial rows (dim*4 B per RUN) + found-mask back
+    combine_bag_runs: the partial rows of a bag added up in rank order (mean / bf16 rounding here, at the source)
+
 Reference anchor: /root/reference/README.md:2 ("A distributed … Embedding"); the snapshot has no code.
 
 This module is host logic only: `local` is any object with the LookupTable operator methods and `router` any
 object with partition / gather_rows / scatter_rows (the HIP-backed LookupTable / Router in production).
 """
 from __future__ import annotations
+
+import math
 
 import torch
 import torch.distributed as dist
@@ -32,26 +42,43 @@ class ShardedLookupTable:
         # path on a single-GPU box; production uses the "nccl" backend = RCCL over xGMI, no staging)
         self._stage = dist.get_backend(group) == "gloo"
         self.dim = local.dim
+        self._sent = self._received = 0   # traffic()
         if router.n_shards != self.world:
             raise ValueError(f"router has {router.n_shards} shards, process group has {self.world} ranks")
 
     # -- exchange plumbing -------------------------------------------------------------------------------
-    def _route(self, keys: torch.Tensor):
-        """partition + counts exchange. Returns (send_keys, perm, send_splits, recv_splits)."""
-        send_keys, counts, perm = self.router.partition(keys)
+    def _swap_counts(self, counts: torch.Tensor):
+        """all-to-all of per-destination counts ([G] or [G, m] int64: m values for every rank) -> (sent, received) on the host"""
+        self._sent += counts.numel() // self.world * (self.world - 1) * 8
+        self._received += counts.numel() // self.world * (self.world - 1) * 8
         if self._stage and counts.is_cuda:
             c_host = counts.cpu()
             r_host = torch.empty_like(c_host)
             dist.all_to_all_single(r_host, c_host, group=self.group)
-            return send_keys, perm, c_host.tolist(), r_host.tolist()
+            return c_host, r_host
         recv_counts = torch.empty_like(counts)
         dist.all_to_all_single(recv_counts, counts, group=self.group)
         both = torch.stack([counts, recv_counts]).cpu()  # the one host sync of the exchange
-        return send_keys, perm, both[0].tolist(), both[1].tolist()
+        return both[0], both[1]
+
+    def _route(self, keys: torch.Tensor):
+        """partition + counts exchange. Returns (send_keys, perm, send_splits, recv_splits)."""
+        send_keys, counts, perm = self.router.partition(keys)
+        sent, received = self._swap_counts(counts)
+        return send_keys, perm, sent.tolist(), received.tolist()
+
+    def traffic(self) -> tuple[int, int]:
+        """(sent, received): bytes handed to the process group for OTHER ranks since this table was made — every _a2a and every count exchange;
+        the rank's own segment never leaves the device and is not counted, and staging through host memory (gloo) counts the same bytes.
+        Mirrors RcclShardedTable.traffic()."""
+        return self._sent, self._received
 
     def _a2a(self, t: torch.Tensor, in_splits, out_splits) -> torch.Tensor:
         if t.dtype == torch.bfloat16:   # bf16 rows travel as their bytes, so that no backend's dtype support matters (gloo moves neither bf16 nor int16)
             return self._a2a(t.contiguous().view(torch.uint8), in_splits, out_splits).view(torch.bfloat16)
+        row_bytes = t.element_size() * math.prod(t.shape[1:])
+        self._sent += (sum(in_splits) - in_splits[self.rank]) * row_bytes
+        self._received += (sum(out_splits) - out_splits[self.rank]) * row_bytes
         if self._stage and t.is_cuda:
             src = t.contiguous().cpu()
             dst = torch.empty((sum(out_splits),) + tuple(t.shape[1:]), dtype=t.dtype)
@@ -146,16 +173,97 @@ class ShardedLookupTable:
         uniq, gsum, _, _ = self.local.dedup_sum(keys, grads.contiguous().view(keys.numel(), -1), compact=True)   # (this path synchronises for its split sizes anyway)
         return uniq, gsum
 
-    def apply_adagrad(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10, dedup: bool = False) -> None:
+    # -- embedding bags (SPEC.md §5 "Pooled lookups") ------------------------------------------------------
+    def _bag_route(self, keys: torch.Tensor, bag_offsets: torch.Tensor):
+        """partition + the runs of the batch + ONE exchange of key counts and run counts.
+        Returns (send_keys, perm, key splits out / in, run_bag [R], run_len [R], run_counts, run splits out / in)."""
+        send_keys, counts, perm = self.router.partition(keys)
+        run_bag, run_len, run_counts = self.router.bag_runs(perm, counts, bag_offsets)
+        sent, received = self._swap_counts(torch.stack([counts, run_counts], dim=1))
+        ss, rss = sent[:, 0].tolist(), sent[:, 1].tolist()
+        rs, rrs = received[:, 0].tolist(), received[:, 1].tolist()
+        r = sum(rss)
+        return send_keys, perm, ss, rs, run_bag[:r], run_len[:r], run_counts, rss, rrs
+
+    def _check_bags(self, keys: torch.Tensor, bag_offsets: torch.Tensor) -> None:
+        if not hasattr(self.router, "bag_runs"):
+            raise ValueError(f"{type(self.router).__name__} has no bag_runs / run_offsets / combine_bag_runs: pooled lookups need the HIP Router")
+        if bag_offsets.numel() < 1 or (keys.numel() and bag_offsets.numel() < 2):
+            raise ValueError("bag_offsets must hold n_bags + 1 entries, and at least one bag when there are keys (the bags partition the batch)")
+
+    def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", insert_missing: bool = False,
+                    out_dtype: torch.dtype = torch.float32):
+        """Embedding-bag lookup over the sharded table -> ([n_bags, dim] sums or means, per-key found mask as find reports it).  Bags are defined
+        on this rank's batch as in LookupTable.find_pooled and must partition it.  Every owner pools its part of every bag in batch order (one
+        row per run travels back), the parts are added up here in rank order, then mean divides and bf16 rounds — once, at the source.  One rank:
+        bit-identical to LookupTable.find_pooled; more: a different, fixed summation order of the same terms.
+        insert_missing: the owners find_or_insert the received keys first (found = existed before).  Collective, also for a rank without keys
+        or without bags."""
+        if mode not in ("sum", "mean"):
+            raise ValueError(f"mode must be 'sum' or 'mean' (got {mode!r})")
+        _out_dtype(out_dtype)
+        if not hasattr(self.local, "find_pooled"):   # refused on every rank alike, before anything is exchanged
+            raise ValueError(f"{type(self.local).__name__} has no find_pooled: pooled lookups need a LookupTable shard")
+        keys = keys.contiguous().view(-1)
+        self._check_bags(keys, bag_offsets)
+        send_keys, perm, ss, rs, run_bag, run_len, run_counts, rss, rrs = self._bag_route(keys, bag_offsets)
+        recv_keys = self._a2a(send_keys, ss, rs)
+        recv_len = self._a2a(run_len, rss, rrs)
+        offsets, _ = self.router.run_offsets(recv_len)
+        if insert_missing:
+            _, found = self.local.find_or_insert(recv_keys)
+            partial, _ = self.local.find_pooled(recv_keys, offsets, "sum")
+        else:
+            partial, found = self.local.find_pooled(recv_keys, offsets, "sum")
+        partial_back = self._a2a(partial, rrs, rss)       # fp32: rounding at the owner would round twice
+        found_back = self._a2a(found, rs, ss)
+        out = self.router.combine_bag_runs(partial_back, run_bag, run_counts, bag_offsets, mode, out_dtype=out_dtype)
+        return out, self.router.scatter_rows(found_back, perm)
+
+    def _apply_bags(self, keys: torch.Tensor, grads: torch.Tensor, grad_index: torch.Tensor, dedup: bool):
+        """The pooled backward: one gradient row per run travels to the owner.  -> (received keys, received run rows, run of every received key)"""
+        if dedup:
+            raise ValueError("dedup=True aggregates one row per key and cannot be combined with grad_index (one row per bag)")
+        keys = keys.contiguous().view(-1)
+        g = grads.contiguous().view(-1, self.dim)
+        gi = grad_index.contiguous().view(-1)
+        if gi.numel() != keys.numel():
+            raise ValueError("grad_index must hold one entry per key")
+        # the calling convention of the pooled backward: grad_index is the bag of every position (checked before anything is exchanged)
+        if gi.numel() and bool((gi[1:] < gi[:-1]).any() | (gi[0] < 0) | (gi[-1] >= g.shape[0])):
+            raise ValueError("sharded apply_*(grad_index=...) takes the pooled backward: grad_index non-decreasing over the batch, inside [0, rows of grads)")
+        bag_offsets = torch.searchsorted(gi.to(torch.int64), torch.arange(g.shape[0] + 1, device=gi.device))
+        self._check_bags(keys, bag_offsets)
+        send_keys, perm, ss, rs, run_bag, run_len, run_counts, rss, rrs = self._bag_route(keys, bag_offsets)
+        run_rows = self.router.gather_rows(g, run_bag.to(torch.int64))
+        rk = self._a2a(send_keys, ss, rs)
+        recv_len = self._a2a(run_len, rss, rrs)
+        recv_rows = self._a2a(run_rows, rss, rrs)
+        _, run_of_key = self.router.run_offsets(recv_len, rk.numel())
+        return rk, recv_rows, run_of_key
+
+    def apply_adagrad(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10, dedup: bool = False,
+                      grad_index: torch.Tensor | None = None) -> None:
+        """grad_index (the pooled backward): position i takes row grad_index[i] of grads, the bag's gradient row — non-decreasing over the batch.
+        One row per (bag, owner) run travels; the owner reduces duplicates over all ranks' contributions in one indexed apply."""
+        if grad_index is not None:
+            rk, rg, run_of_key = self._apply_bags(keys, grads, grad_index, dedup)
+            self.local.apply_adagrad(rk, rg, lr, eps, grad_index=run_of_key)
+            return
         if dedup:
             keys, grads = self._aggregate(keys, grads)
         rk, rg, *_ = self._push(keys, grads)
         self.local.apply_adagrad(rk, rg, lr, eps)
 
     def apply_adam(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999,
-                   eps: float = 1e-8, step: int = 1, dedup: bool = False) -> None:
+                   eps: float = 1e-8, step: int = 1, dedup: bool = False, grad_index: torch.Tensor | None = None) -> None:
         """dedup is accepted like apply_adagrad's, but Adam's pairs are never aggregated before the exchange: its update barely depends on the size of
-        g, so the rounding of a rank's partial sum, where the ranks' sums cancel, would reach the row as a large relative error (SPEC.md §5)."""
+        g, so the rounding of a rank's partial sum, where the ranks' sums cancel, would reach the row as a large relative error (SPEC.md §5).
+        grad_index: as apply_adagrad's."""
+        if grad_index is not None:
+            rk, rg, run_of_key = self._apply_bags(keys, grads, grad_index, dedup)
+            self.local.apply_adam(rk, rg, lr, beta1, beta2, eps, step, grad_index=run_of_key)
+            return
         rk, rg, *_ = self._push(keys, grads)
         self.local.apply_adam(rk, rg, lr, beta1, beta2, eps, step)
 
@@ -183,6 +291,12 @@ class ShardedLookupTable:
 
     def _dev(self):
         return getattr(self.local, "device", torch.device("cpu"))
+
+    @property
+    def device(self):
+        return self._dev()
+
+    pools_with_insert = True   # find_pooled(insert_missing=True): what DynamicEmbeddingBag(create_missing=True) calls instead of a find_or_insert of its own
 
 
 class RcclShardedTable:

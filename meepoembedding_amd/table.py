@@ -31,6 +31,14 @@ def _check_weights(weights: torch.Tensor, mode: str, n: int, device: torch.devic
     return weights.view(-1)
 
 
+def _n_bags(bag_offsets: torch.Tensor, device: torch.device) -> int:
+    """the bag_offsets of a pooled lookup, checked before any launch -> the number of bags"""
+    if bag_offsets.device != device or bag_offsets.dtype not in (torch.int64, torch.uint64) or not bag_offsets.is_contiguous() \
+            or bag_offsets.numel() < 1:
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_offsets must be contiguous int64 on {device} with n_bags + 1 entries")
+    return bag_offsets.numel() - 1
+
+
 _OUT_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16}
 
 
@@ -160,10 +168,7 @@ class LookupTable:
         return [(o, f) for o, f, _ in res]
 
     def _bag_offsets(self, bag_offsets: torch.Tensor) -> int:
-        if bag_offsets.device != self.device or bag_offsets.dtype not in (torch.int64, torch.uint64) or not bag_offsets.is_contiguous() \
-                or bag_offsets.numel() < 1:
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_offsets must be contiguous int64 on {self.device} with n_bags + 1 entries")
-        return bag_offsets.numel() - 1
+        return _n_bags(bag_offsets, self.device)
 
     def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
                     found: torch.Tensor | None = None, weights: torch.Tensor | None = None, located: torch.Tensor | None = None,
@@ -824,4 +829,41 @@ class Router:
             out = torch.empty((n,) + tuple(r.shape[1:]), dtype=r.dtype, device=r.device)
         with torch.cuda.device(self.device):
             check(_lib.lib().mee_gather_rows(r.data_ptr(), perm.data_ptr(), n, rb, out.data_ptr(), _stream_ptr(self.device)))
+        return out
+
+    # -- embedding bags over a sharded table (SPEC.md §5 "Pooled lookups") -----------------------------------------------
+    def bag_runs(self, perm: torch.Tensor, counts: torch.Tensor, bag_offsets: torch.Tensor):
+        """The runs of a partitioned batch (mee_bag_runs): (run_bag [n], run_len [n], run_counts [n_shards]) — int32 / int32 / int64, the
+        runs in segment order; only the first run_counts.sum() entries of run_bag / run_len are meaningful.  Sync-free."""
+        n, n_bags = perm.numel(), _n_bags(bag_offsets, self.device)
+        run_bag = torch.empty(n, dtype=torch.int32, device=self.device)
+        run_len = torch.empty(n, dtype=torch.int32, device=self.device)
+        run_counts = torch.empty(self.n_shards, dtype=torch.int64, device=self.device)
+        check(_lib.lib().mee_bag_runs(self._h, perm.data_ptr(), counts.data_ptr(), n, bag_offsets.data_ptr(), n_bags, run_bag.data_ptr(),
+                                      run_len.data_ptr(), run_counts.data_ptr(), _stream_ptr(self.device)))
+        return run_bag, run_len, run_counts
+
+    def run_offsets(self, run_len: torch.Tensor, n_keys: int | None = None):
+        """The owner's side (mee_run_offsets): received run lengths -> (offsets [R + 1] int64 = the bag_offsets of the local find_pooled,
+        run_of_key [n_keys] int32 = the grad_index of the local indexed apply, or None without n_keys)."""
+        rl = run_len.contiguous()
+        offsets = torch.empty(rl.numel() + 1, dtype=torch.int64, device=self.device)
+        rok = torch.empty(n_keys, dtype=torch.int32, device=self.device) if n_keys is not None else None
+        check(_lib.lib().mee_run_offsets(self._h, rl.data_ptr(), rl.numel(), offsets.data_ptr(), rok.data_ptr() if rok is not None else None,
+                                         n_keys or 0, _stream_ptr(self.device)))
+        return offsets, rok
+
+    def combine_bag_runs(self, partials: torch.Tensor, run_bag: torch.Tensor, run_counts: torch.Tensor, bag_offsets: torch.Tensor,
+                         mode: str = "sum", out: torch.Tensor | None = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """out[b] = the owners' partial rows of bag b added up in rank order (mee_combine_bag_runs), mean then divided by the bag length,
+        bf16 then rounded once.  partials [R, dim] fp32 in the run order of bag_runs."""
+        dt = _out_dtype(out_dtype, out)
+        n_bags = _n_bags(bag_offsets, self.device)
+        p = partials.contiguous()
+        if p.dtype != torch.float32 or p.dim() != 2:
+            raise MeepoError(_lib.ERR_INVALID_ARG, "partials must be float32 [n_runs, dim]")
+        if out is None:
+            out = torch.empty((n_bags, p.shape[1]), dtype=out_dtype, device=self.device)
+        check(_lib.lib().mee_combine_bag_runs(self._h, p.data_ptr(), run_bag.data_ptr(), run_counts.data_ptr(), p.shape[0], bag_offsets.data_ptr(),
+                                              n_bags, p.shape[1], {"sum": 0, "mean": 1}[mode], out.data_ptr(), dt, _stream_ptr(self.device)))
         return out
