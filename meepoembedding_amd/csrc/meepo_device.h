@@ -113,6 +113,44 @@ __device__ __forceinline__ int64_t tile_locate(int64_t* __restrict__ tkeys, uint
     return slot;
 }
 
+// The read-only probe of the lookups, with the keys already in flight: the caller has computed b = bucket_of(key, nb) and requested that
+// bucket's line, k = tkeys[b * kW + tl] (kEmpty where !act) — for ALL the keys its tile handles, back to back, before it examines any of
+// them; that is the whole point of the shape (a request per probe made every key wait for its predecessor's round trip).  From there the
+// tile walks the key's SPEC.md §2 sequence until it meets the key, an EMPTY slot, or has visited all nb buckets.  Must be called by ALL
+// 64 lanes in convergent control flow; tiles without work pass act = false.  Plain loads (see load_table_key), and it never writes:
+// nothing is claimed, so no table key may change while the kernel runs.  Returns the slot or -1.
+__device__ __forceinline__ int64_t tile_probe(const int64_t* __restrict__ tkeys, uint64_t nb, int64_t key, bool act, uint64_t b, int64_t k,
+                                              int tile, int tl) {
+    int64_t slot = -1;
+    bool pend = act;
+    uint64_t steps = 0;
+    while (true) {
+        const uint32_t tm = tile_bits(__ballot(pend && k == key), tile);
+        const uint32_t te = tile_bits(__ballot(pend && k == kEmpty), tile);
+        if (pend) {
+            if (tm) { slot = (int64_t)(b * kW) + (__ffs(tm) - 1); pend = false; }
+            else if (te || ++steps >= nb) pend = false;
+            else b = next_bucket(b, step_of(key, nb), nb);
+        }
+        if (!__any(pend)) break;
+        k = pend ? tkeys[b * kW + tl] : kEmpty;
+    }
+    return slot;
+}
+
+// A wave step of a 4R-position kernel leaves tile t's result of round r in slot[r] of that tile's lanes; lane j < 4R collects the slot of
+// position base + j (round j / 4, tile j % 4), so that the step's slots leave as ONE coalesced store.  All 64 lanes call it; lanes >= 4R get -1.
+template <int R>
+__device__ __forceinline__ int64_t collect_slots(const int64_t (&slot)[R], int lane) {
+    int64_t mine = -1;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int64_t v = __shfl(slot[r], (lane & 3) * kW);
+        if ((lane >> 2) == r) mine = v;
+    }
+    return mine;
+}
+
 // ---- bf16 output of the lookups (SPEC.md §3 "Output type") ------------------------------------------------------------------
 // A lane that holds a float4 of a row stores it as 4 bf16 = 8 bytes; a row of dim bf16 is dim4 such 8-byte groups, so group g of
 // output row i sits at index i * dim4 + g of a u32x2 array — the SAME index the fp32 kernels use on their f32x4 array.

@@ -60,23 +60,7 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
             kb[r] = act[r] ? ((NT & 2) ? __builtin_nontemporal_load(&tkeys[b[r] * kW + tl]) : tkeys[b[r] * kW + tl]) : kEmpty;
         }
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            slot[r] = -1;
-            bool pend = act[r];
-            uint64_t bb = b[r], steps = 0;
-            int64_t k = kb[r];
-            while (true) {
-                const uint32_t tm = tile_bits(__ballot(pend && k == key[r]), tile);
-                const uint32_t te = tile_bits(__ballot(pend && k == kEmpty), tile);
-                if (pend) {
-                    if (tm) { slot[r] = (int64_t)(bb * kW) + (__ffs(tm) - 1); pend = false; }
-                    else if (te || ++steps >= nb) pend = false;
-                    else bb = next_bucket(bb, step_of(key[r], nb), nb);
-                }
-                if (!__any(pend)) break;
-                k = pend ? tkeys[bb * kW + tl] : kEmpty;
-            }
-        }
+        for (int r = 0; r < R; ++r) slot[r] = tile_probe(tkeys, nb, key[r], act[r], b[r], kb[r], tile, tl);
         if constexpr ((NT & 16) != 0) {  // access statistics for the hot/cold policy (sampled calls only)
 #pragma unroll
             for (int r = 0; r < R; ++r)
@@ -136,13 +120,7 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
             }
         }
         if constexpr ((NT & 64) != 0) {  // mee_find_located: the slot of every position (-1 = absent), for the apply of the same step
-            // lane j < 4R collects the slot of position base + j (round j / 4, tile j % 4): ONE coalesced store per wave step
-            int64_t mine = -1;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int64_t v = __shfl(slot[r], (lane & 3) * kW);
-                if ((lane >> 2) == r) mine = v;
-            }
+            const int64_t mine = collect_slots(slot, lane);   // ONE coalesced store per wave step
             if (lane < KPW && base + lane < n) slots_out[base + lane] = mine >= 0 ? (mine | handle_tag) : mine;   // tag: the table's layout epoch (see handle_tag_of)
         }
         if (found && !(NT & 32)) {  // NT&32: rows only (last pass of find_or_insert: found keeps meaning "present before")
@@ -322,23 +300,7 @@ __device__ __forceinline__ void pooled_fetch(const int64_t* __restrict__ tkeys, 
         kb[u] = act[u] ? tkeys[bk[u] * kW + tl] : kEmpty;
     }
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        slot[u] = -1;
-        bool pend = act[u];
-        uint64_t bb = bk[u], steps = 0;
-        int64_t k = kb[u];
-        while (true) {
-            const uint32_t tm = tile_bits(__ballot(pend && k == key[u]), tile);
-            const uint32_t te = tile_bits(__ballot(pend && k == kEmpty), tile);
-            if (pend) {
-                if (tm) { slot[u] = (int64_t)(bb * kW) + (__ffs(tm) - 1); pend = false; }
-                else if (te || ++steps >= nb) pend = false;
-                else bb = next_bucket(bb, step_of(key[u], nb), nb);
-            }
-            if (!__any(pend)) break;
-            k = pend ? tkeys[bb * kW + tl] : kEmpty;
-        }
-    }
+    for (int u = 0; u < U; ++u) slot[u] = tile_probe(tkeys, nb, key[u], act[u], bk[u], kb[u], tile, tl);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
 #pragma unroll

@@ -64,23 +64,7 @@ __global__ __launch_bounds__(256) void find_grouped_kernel(const GroupDesc* __re
             kb[r] = act[r] ? d[r].tkeys[b[r] * kW + tl] : kEmpty;
         }
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            slot[r] = -1;
-            bool pend = act[r];
-            uint64_t bb = b[r], steps = 0;
-            int64_t k = kb[r];
-            while (true) {
-                const uint32_t tm = tile_bits(__ballot(pend && k == key[r]), tile);
-                const uint32_t te = tile_bits(__ballot(pend && k == kEmpty), tile);
-                if (pend) {
-                    if (tm) { slot[r] = (int64_t)(bb * kW) + (__ffs(tm) - 1); pend = false; }
-                    else if (te || ++steps >= d[r].nb) pend = false;
-                    else bb = next_bucket(bb, step_of(key[r], d[r].nb), d[r].nb);
-                }
-                if (!__any(pend)) break;
-                k = pend ? d[r].tkeys[bb * kW + tl] : kEmpty;
-            }
-        }
+        for (int r = 0; r < R; ++r) slot[r] = tile_probe(d[r].tkeys, d[r].nb, key[r], act[r], b[r], kb[r], tile, tl);
         if constexpr (LOCATE) {
 #pragma unroll
             for (int r = 0; r < R; ++r) {

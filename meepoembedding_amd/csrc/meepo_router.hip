@@ -4,7 +4,10 @@
 // SPEC.md §1 (hashing) and §5 (sharding).  The partition is a three-kernel counting sort by owner that keeps
 // batch order inside each shard segment: per-block histograms (wave ballot + popcount per shard), a per-shard
 // scan over blocks (one wave per shard, shuffle prefix-sum), and a scatter that recomputes each key's rank
-// from the same ballots.
+// from the same ballots.  The run bookkeeping of the sharded embedding bags (bag_runs) is the same sort with
+// "first position of a run in segment p" in the place of "key owned by p": both go through count_owners.
+// Further down: the run offsets and the combination of the owners' partial bag rows, and the peer-to-peer
+// sharded find, whose owner-side kernel probes with the lookups' tile_probe (meepo_device.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -45,8 +48,47 @@ struct mee_p2p {
 
 namespace mee {
 
-constexpr int kPartBlock = 1024;  // keys per block in the partition kernels (one per thread): 4x fewer rows for the scan
+constexpr int kPartBlock = 1024;  // positions per block in the partition and run kernels (one per thread): 4x fewer rows for the scan
 constexpr int kMaxShards = 64;
+constexpr uint32_t kNoOwner = 0xFFFFFFFFu;   // a position the counting sort leaves out
+
+// inclusive prefix sum over the wave's 64 lanes
+template <class T>
+__device__ __forceinline__ T wave_scan_inclusive(T v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const T t = __shfl_up(v, d);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+
+// The block step of the stable counting sort: thread t holds position blockIdx.x * kPartBlock + t, whose owner is o < g (kNoOwner: none).
+// Fills wcnt[w][p] = how many positions of wave w have owner p; with RANK returns how many EARLIER positions of the block have the
+// thread's own owner (0 for kNoOwner).  All kPartBlock threads call it (ballots, one barrier).
+template <bool RANK>
+__device__ __forceinline__ uint32_t count_owners(uint32_t o, uint32_t g, uint32_t (&wcnt)[kPartBlock / 64][kMaxShards]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t r = 0;
+    for (uint32_t p = 0; p < g; ++p) {
+        const uint64_t m = __ballot(o == p);
+        if (RANK && o == p) r = (uint32_t)__popcll(m & ((1ull << lane) - 1));
+        if (lane == 0) wcnt[w][p] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    if (RANK && o != kNoOwner)
+        for (int ww = 0; ww < w; ++ww) r += wcnt[ww][o];
+    return r;
+}
+// after count_owners: the block's count per owner, one row of blockcnt
+__device__ __forceinline__ void store_block_counts(const uint32_t (&wcnt)[kPartBlock / 64][kMaxShards], uint32_t g, uint32_t* blockcnt) {
+    if (threadIdx.x < g) {
+        uint32_t c = 0;
+#pragma unroll
+        for (int ww = 0; ww < kPartBlock / 64; ++ww) c += wcnt[ww][threadIdx.x];
+        blockcnt[(uint64_t)blockIdx.x * g + threadIdx.x] = c;
+    }
+}
 
 __global__ void hash_batch_kernel(const int64_t* __restrict__ keys, uint64_t n, uint64_t nb, uint32_t g, uint64_t* mix_out,
                                   uint64_t* bucket_out, uint32_t* owner_out) {
@@ -64,21 +106,10 @@ __global__ __launch_bounds__(kPartBlock) void part_count_kernel(const int64_t* _
                                                                 uint32_t* blockcnt) {
     __shared__ uint32_t wcnt[kPartBlock / 64][kMaxShards];
     const uint32_t i = blockIdx.x * kPartBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t key = i < n ? keys[i] : kEmpty;
     const bool inb = i < n && !(SKIP_PAD && key == kEmpty);
-    const uint32_t o = inb ? owner_of(key, g) : 0xFFFFFFFFu;
-    for (uint32_t p = 0; p < g; ++p) {
-        const uint64_t m = __ballot(o == p);
-        if (lane == 0) wcnt[w][p] = (uint32_t)__popcll(m);
-    }
-    __syncthreads();
-    if (threadIdx.x < g) {
-        uint32_t c = 0;
-#pragma unroll
-        for (int ww = 0; ww < kPartBlock / 64; ++ww) c += wcnt[ww][threadIdx.x];
-        blockcnt[(uint64_t)blockIdx.x * g + threadIdx.x] = c;
-    }
+    count_owners<false>(inb ? owner_of(key, g) : kNoOwner, g, wcnt);
+    store_block_counts(wcnt, g, blockcnt);
 }
 
 // one block; wave w scans shards w, w+nwaves, … over all key blocks
@@ -91,12 +122,7 @@ __global__ __launch_bounds__(1024) void part_scan_kernel(uint32_t* blockcnt, uin
         for (uint32_t b0 = 0; b0 < n_blocks; b0 += 64) {
             const uint32_t b = b0 + lane;
             const uint32_t c = b < n_blocks ? blockcnt[(uint64_t)b * g + p] : 0;
-            uint32_t incl = c;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t t = __shfl_up(incl, d);
-                if (lane >= d) incl += t;
-            }
+            const uint32_t incl = wave_scan_inclusive(c, lane);
             if (b < n_blocks) blockcnt[(uint64_t)b * g + p] = run + incl - c;
             run += __shfl(incl, 63);
         }
@@ -120,19 +146,11 @@ __global__ __launch_bounds__(kPartBlock) void part_scatter_kernel(const int64_t*
                                                                   int64_t* perm) {
     __shared__ uint32_t wcnt[kPartBlock / 64][kMaxShards];
     const uint32_t i = blockIdx.x * kPartBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t key = i < n ? keys[i] : kEmpty;
     const bool inb = i < n && !(SKIP_PAD && key == kEmpty);
-    const uint32_t o = inb ? owner_of(key, g) : 0xFFFFFFFFu;
-    uint32_t r = 0;
-    for (uint32_t p = 0; p < g; ++p) {
-        const uint64_t m = __ballot(o == p);
-        if (o == p) r = (uint32_t)__popcll(m & ((1ull << lane) - 1));
-        if (lane == 0) wcnt[w][p] = (uint32_t)__popcll(m);
-    }
-    __syncthreads();
+    const uint32_t o = inb ? owner_of(key, g) : kNoOwner;
+    const uint32_t r = count_owners<true>(o, g, wcnt);
     if (inb) {
-        for (int ww = 0; ww < w; ++ww) r += wcnt[ww][o];
         const uint64_t dst = base[o] + blockoff[(uint64_t)blockIdx.x * g + o] + r;
         send_keys[dst] = key;
         perm[dst] = (int64_t)i;
@@ -182,8 +200,6 @@ static int permute_rows(const void* d_rows, const int64_t* d_perm, size_t n, siz
 // received run lengths into the bag_offsets / grad_index of its local pooled lookup / indexed apply (run_offsets), and the source adds
 // the owners' partial rows up in rank order (combine_bag_runs).  Nothing here trusts caller data with an address: perm entries are only
 // compared, bags come out of a search over [0, n_bags), run indices are kept inside [0, n_runs).
-constexpr int kRunBlock = 1024;   // positions per block of the run kernels (one per thread)
-
 // the last b in [0, m) with off[b] <= i (m >= 1): the bag of batch position i under bag_offsets, the run of received key i under run offsets
 __device__ __forceinline__ uint32_t last_not_above(const uint64_t* __restrict__ off, uint32_t m, uint64_t i) {
     uint32_t lo = 0, hi = m - 1;
@@ -196,12 +212,12 @@ __device__ __forceinline__ uint32_t last_not_above(const uint64_t* __restrict__ 
 
 struct RunPos {
     bool head;        // this position starts a run
-    uint32_t seg;     // its destination segment (0xFFFFFFFF when it is no run start: the owner id of the counting sort)
+    uint32_t seg;     // its destination segment (kNoOwner when it is no run start: the owner id of the counting sort)
     uint32_t bag;
     uint32_t seg_end; // one past the segment's last position
 };
 
-// what position q = blockIdx.x * kRunBlock + threadIdx.x is; all threads of the block call it (LDS staging + barriers)
+// what position q = blockIdx.x * kPartBlock + threadIdx.x is; all threads of the block call it (LDS staging + barriers)
 __device__ __forceinline__ RunPos run_position(const int64_t* __restrict__ perm, const uint64_t* __restrict__ counts, uint32_t g, uint32_t n,
                                                const uint64_t* __restrict__ off, uint32_t n_bags, uint32_t* s_end, uint32_t* s_bag) {
     if (threadIdx.x == 0) {   // segment ends, never past n whatever the counts say
@@ -214,7 +230,7 @@ __device__ __forceinline__ RunPos run_position(const int64_t* __restrict__ perm,
         }
     }
     __syncthreads();
-    const uint32_t q = blockIdx.x * kRunBlock + threadIdx.x;
+    const uint32_t q = blockIdx.x * kPartBlock + threadIdx.x;
     const bool inb = q < s_end[g - 1];
     uint32_t seg = 0;
     while (seg + 1 < g && s_end[seg] <= q) ++seg;   // g <= 64 LDS words
@@ -226,48 +242,30 @@ __device__ __forceinline__ RunPos run_position(const int64_t* __restrict__ perm,
     if (inb && q > seg_begin) prev = threadIdx.x ? s_bag[threadIdx.x - 1] : last_not_above(off, n_bags, (uint64_t)perm[q - 1]);
     RunPos r;
     r.head = inb && (q == seg_begin || bag != prev);
-    r.seg = r.head ? seg : 0xFFFFFFFFu;
+    r.seg = r.head ? seg : kNoOwner;
     r.bag = bag;
     r.seg_end = s_end[seg];
     return r;
 }
 
-__global__ __launch_bounds__(kRunBlock) void run_count_kernel(const int64_t* __restrict__ perm, const uint64_t* __restrict__ counts, uint32_t g, uint32_t n,
+__global__ __launch_bounds__(kPartBlock) void run_count_kernel(const int64_t* __restrict__ perm, const uint64_t* __restrict__ counts, uint32_t g, uint32_t n,
                                                               const uint64_t* __restrict__ off, uint32_t n_bags, uint32_t* blockcnt) {
-    __shared__ uint32_t s_end[kMaxShards], s_bag[kRunBlock], wcnt[kRunBlock / 64][kMaxShards];
+    __shared__ uint32_t s_end[kMaxShards], s_bag[kPartBlock], wcnt[kPartBlock / 64][kMaxShards];
     const RunPos r = run_position(perm, counts, g, n, off, n_bags, s_end, s_bag);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (uint32_t p = 0; p < g; ++p) {
-        const uint64_t m = __ballot(r.seg == p);
-        if (lane == 0) wcnt[w][p] = (uint32_t)__popcll(m);
-    }
-    __syncthreads();
-    if (threadIdx.x < g) {
-        uint32_t c = 0;
-#pragma unroll
-        for (int ww = 0; ww < kRunBlock / 64; ++ww) c += wcnt[ww][threadIdx.x];
-        blockcnt[(uint64_t)blockIdx.x * g + threadIdx.x] = c;
-    }
+    count_owners<false>(r.seg, g, wcnt);
+    store_block_counts(wcnt, g, blockcnt);
 }
 
-__global__ __launch_bounds__(kRunBlock) void run_scatter_kernel(const int64_t* __restrict__ perm, const uint64_t* __restrict__ counts, uint32_t g, uint32_t n,
+__global__ __launch_bounds__(kPartBlock) void run_scatter_kernel(const int64_t* __restrict__ perm, const uint64_t* __restrict__ counts, uint32_t g, uint32_t n,
                                                                 const uint64_t* __restrict__ off, uint32_t n_bags, const uint32_t* __restrict__ blockoff,
                                                                 const uint64_t* __restrict__ run_base, uint32_t* __restrict__ run_bag,
                                                                 uint32_t* __restrict__ run_len) {
-    __shared__ uint32_t s_end[kMaxShards], s_bag[kRunBlock], wcnt[kRunBlock / 64][kMaxShards];
+    __shared__ uint32_t s_end[kMaxShards], s_bag[kPartBlock], wcnt[kPartBlock / 64][kMaxShards];
     const RunPos r = run_position(perm, counts, g, n, off, n_bags, s_end, s_bag);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t rank = 0;
-    for (uint32_t p = 0; p < g; ++p) {
-        const uint64_t m = __ballot(r.seg == p);
-        if (r.seg == p) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1));
-        if (lane == 0) wcnt[w][p] = (uint32_t)__popcll(m);
-    }
-    __syncthreads();
+    const uint32_t rank = count_owners<true>(r.seg, g, wcnt);
     if (r.head) {
-        for (int ww = 0; ww < w; ++ww) rank += wcnt[ww][r.seg];
         const uint64_t dst = run_base[r.seg] + blockoff[(uint64_t)blockIdx.x * g + r.seg] + rank;   // < the number of run starts <= n
-        const uint32_t q = blockIdx.x * kRunBlock + threadIdx.x;
+        const uint32_t q = blockIdx.x * kPartBlock + threadIdx.x;
         // the run ends at the segment's first position of a later bag: positions ascend inside a segment
         const uint64_t bag_end = off[r.bag + 1];
         uint32_t lo = q + 1, hi = r.seg_end;
@@ -283,12 +281,7 @@ __global__ __launch_bounds__(kRunBlock) void run_scatter_kernel(const int64_t* _
 // exclusive scan of one value per thread over the block; `total` = the block's sum.  s_w: blockDim.x / 64 words of LDS
 __device__ __forceinline__ uint64_t block_scan_exclusive(uint64_t v, uint64_t* s_w, uint64_t& total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint64_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
+    const uint64_t incl = wave_scan_inclusive(v, lane);
     if (lane == 63) s_w[w] = incl;
     __syncthreads();
     uint64_t before = 0;
@@ -301,19 +294,19 @@ __device__ __forceinline__ uint64_t block_scan_exclusive(uint64_t v, uint64_t* s
     return before + incl - v;
 }
 
-__global__ __launch_bounds__(kRunBlock) void run_len_sum_kernel(const uint32_t* __restrict__ run_len, uint64_t n_runs, uint64_t* __restrict__ sums) {
-    __shared__ uint64_t s_w[kRunBlock / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
+__global__ __launch_bounds__(kPartBlock) void run_len_sum_kernel(const uint32_t* __restrict__ run_len, uint64_t n_runs, uint64_t* __restrict__ sums) {
+    __shared__ uint64_t s_w[kPartBlock / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kPartBlock + threadIdx.x;
     uint64_t total;
     (void)block_scan_exclusive(i < n_runs ? run_len[i] : 0, s_w, total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
 // one block: the block sums become their exclusive prefix
-__global__ __launch_bounds__(kRunBlock) void run_len_scan_kernel(uint64_t* sums, uint32_t n_blocks) {
-    __shared__ uint64_t s_w[kRunBlock / 64];
+__global__ __launch_bounds__(kPartBlock) void run_len_scan_kernel(uint64_t* sums, uint32_t n_blocks) {
+    __shared__ uint64_t s_w[kPartBlock / 64];
     uint64_t carry = 0;
-    for (uint32_t b0 = 0; b0 < n_blocks; b0 += kRunBlock) {   // block-uniform
+    for (uint32_t b0 = 0; b0 < n_blocks; b0 += kPartBlock) {   // block-uniform
         const uint32_t b = b0 + threadIdx.x;
         uint64_t total;
         const uint64_t ex = block_scan_exclusive(b < n_blocks ? sums[b] : 0, s_w, total);
@@ -322,10 +315,10 @@ __global__ __launch_bounds__(kRunBlock) void run_len_scan_kernel(uint64_t* sums,
     }
 }
 
-__global__ __launch_bounds__(kRunBlock) void run_offsets_kernel(const uint32_t* __restrict__ run_len, uint64_t n_runs, const uint64_t* __restrict__ sums,
+__global__ __launch_bounds__(kPartBlock) void run_offsets_kernel(const uint32_t* __restrict__ run_len, uint64_t n_runs, const uint64_t* __restrict__ sums,
                                                                 uint64_t* __restrict__ offsets) {
-    __shared__ uint64_t s_w[kRunBlock / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * kRunBlock + threadIdx.x;
+    __shared__ uint64_t s_w[kPartBlock / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kPartBlock + threadIdx.x;
     const uint64_t len = i < n_runs ? run_len[i] : 0;
     uint64_t total;
     const uint64_t ex = sums[blockIdx.x] + block_scan_exclusive(len, s_w, total);
@@ -354,17 +347,9 @@ __global__ __launch_bounds__(256) void combine_bag_runs_kernel(const float4* __r
     const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
     const uint32_t dim4 = DIM4 ? DIM4 : dim4_rt;
     // lane l holds the run range of segment l (g <= 64), never past n_runs
-    uint64_t seg_hi = 0;
-    {
-        const uint64_t c = (uint32_t)lane < g ? run_counts[lane] : 0;
-        uint64_t incl = c < n_runs ? c : n_runs;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t t = __shfl_up(incl, d);
-            if (lane >= d) incl += t;
-        }
-        seg_hi = incl < n_runs ? incl : n_runs;
-    }
+    const uint64_t seg_c = (uint32_t)lane < g ? run_counts[lane] : 0;
+    const uint64_t seg_incl = wave_scan_inclusive(seg_c < n_runs ? seg_c : n_runs, lane);
+    const uint64_t seg_hi = seg_incl < n_runs ? seg_incl : n_runs;
     const uint64_t seg_lo_all = __shfl_up(seg_hi, 1);
     const uint64_t seg_lo = lane ? seg_lo_all : 0;
     for (uint64_t b0 = wave * 4; b0 < n_bags; b0 += n_waves * 4) {   // wave-uniform
@@ -536,23 +521,7 @@ __global__ __launch_bounds__(256) void p2p_find_kernel(const int64_t* __restrict
             kb[r] = (inb[r] && !reserved_key(key[r])) ? tkeys[b[r] * kW + tl] : kEmpty;
         }
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            slot[r] = -1;
-            bool pend = inb[r] && !reserved_key(key[r]);
-            uint64_t bb = b[r], steps = 0;
-            int64_t k = kb[r];
-            while (true) {
-                const uint32_t tm = tile_bits(__ballot(pend && k == key[r]), tile);
-                const uint32_t te = tile_bits(__ballot(pend && k == kEmpty), tile);
-                if (pend) {
-                    if (tm) { slot[r] = (int64_t)(bb * kW) + (__ffs(tm) - 1); pend = false; }
-                    else if (te || ++steps >= nb) pend = false;
-                    else bb = next_bucket(bb, step_of(key[r], nb), nb);
-                }
-                if (!__any(pend)) break;
-                k = pend ? tkeys[bb * kW + tl] : kEmpty;
-            }
-        }
+        for (int r = 0; r < R; ++r) slot[r] = tile_probe(tkeys, nb, key[r], inb[r] && !reserved_key(key[r]), b[r], kb[r], tile, tl);
         if constexpr (DIM4 != 0) {
             constexpr int C = DIM4 / 16;
             float4 row[R][C];
@@ -668,10 +637,10 @@ int mee_bag_runs(mee_router* r, const int64_t* d_perm, const uint64_t* d_counts,
     if (n_bags > 0xFFFFFFFFull || (n && n_bags == 0)) return fail(MEE_ERR_INVALID_ARG, "mee_bag_runs: n_bags must be in [1, 2^32) when there are positions (the bags partition them)");
     DeviceGuard g(r->device);
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t nblk = (uint32_t)((n + kRunBlock - 1) / kRunBlock);
-    if (nblk) run_count_kernel<<<nblk, kRunBlock, 0, st>>>(d_perm, d_counts, r->n_shards, (uint32_t)n, d_bag_offsets, (uint32_t)n_bags, r->blockcnt);
+    const uint32_t nblk = (uint32_t)((n + kPartBlock - 1) / kPartBlock);
+    if (nblk) run_count_kernel<<<nblk, kPartBlock, 0, st>>>(d_perm, d_counts, r->n_shards, (uint32_t)n, d_bag_offsets, (uint32_t)n_bags, r->blockcnt);
     part_scan_kernel<<<1, 1024, 0, st>>>(r->blockcnt, nblk, r->n_shards, r->run_base, d_run_counts);
-    if (nblk) run_scatter_kernel<<<nblk, kRunBlock, 0, st>>>(d_perm, d_counts, r->n_shards, (uint32_t)n, d_bag_offsets, (uint32_t)n_bags, r->blockcnt, r->run_base, d_run_bag, d_run_len);
+    if (nblk) run_scatter_kernel<<<nblk, kPartBlock, 0, st>>>(d_perm, d_counts, r->n_shards, (uint32_t)n, d_bag_offsets, (uint32_t)n_bags, r->blockcnt, r->run_base, d_run_bag, d_run_len);
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -689,10 +658,10 @@ int mee_run_offsets(mee_router* r, const uint32_t* d_run_len, size_t n_runs, uin
         MEE_HIP(hipMemsetAsync(d_offsets, 0, 8, st));
         return MEE_OK;
     }
-    const uint32_t nblk = (uint32_t)((n_runs + kRunBlock - 1) / kRunBlock);   // <= max_blocks * n_shards
-    run_len_sum_kernel<<<nblk, kRunBlock, 0, st>>>(d_run_len, n_runs, r->run_sums);
-    run_len_scan_kernel<<<1, kRunBlock, 0, st>>>(r->run_sums, nblk);
-    run_offsets_kernel<<<nblk, kRunBlock, 0, st>>>(d_run_len, n_runs, r->run_sums, d_offsets);
+    const uint32_t nblk = (uint32_t)((n_runs + kPartBlock - 1) / kPartBlock);   // <= max_blocks * n_shards
+    run_len_sum_kernel<<<nblk, kPartBlock, 0, st>>>(d_run_len, n_runs, r->run_sums);
+    run_len_scan_kernel<<<1, kPartBlock, 0, st>>>(r->run_sums, nblk);
+    run_offsets_kernel<<<nblk, kPartBlock, 0, st>>>(d_run_len, n_runs, r->run_sums, d_offsets);
     if (d_run_of_key && n_keys) run_of_key_kernel<<<grid_for(n_keys, 256, 1u << 16), 256, 0, st>>>(d_offsets, (uint32_t)n_runs, n_keys, d_run_of_key);
     MEE_HIP(hipGetLastError());
     return MEE_OK;

@@ -336,29 +336,8 @@ __global__ __launch_bounds__(256) void remove_locate_kernel(const int64_t* __res
             kb[r] = valid[r] ? tkeys[b[r] * kW + tl] : kEmpty;
         }
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            slot[r] = -1;
-            bool pend = valid[r];
-            uint64_t bb = b[r], steps = 0;
-            int64_t k = kb[r];
-            while (true) {
-                const uint32_t tm = tile_bits(__ballot(pend && k == key[r]), tile);
-                const uint32_t te = tile_bits(__ballot(pend && k == kEmpty), tile);
-                if (pend) {
-                    if (tm) { slot[r] = (int64_t)(bb * kW) + (__ffs(tm) - 1); pend = false; }
-                    else if (te || ++steps >= nb) pend = false;
-                    else bb = next_bucket(bb, step_of(key[r], nb), nb);
-                }
-                if (!__any(pend)) break;
-                k = pend ? tkeys[bb * kW + tl] : kEmpty;
-            }
-        }
-        long long my_slot = -1;   // lane j < 4R collects the slot of position base + j (round j / 4, tile j % 4)
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const long long v = __shfl((long long)slot[r], (lane & 3) * kW);
-            if ((lane >> 2) == r) my_slot = v;
-        }
+        for (int r = 0; r < R; ++r) slot[r] = tile_probe(tkeys, nb, key[r], valid[r], b[r], kb[r], tile, tl);
+        const long long my_slot = collect_slots(slot, lane);
         if (mine) {
             slot_out[base + lane] = my_slot;
             if (found) found[base + lane] = my_slot >= 0;

@@ -214,6 +214,50 @@ def test_high_load_long_probes(dev):
     assert t.size() == n and np.array_equal(found.cpu().numpy(), ef) and np.array_equal(out.cpu().numpy(), eo)
 
 
+@pytest.mark.parametrize("dim", [64, 24])
+def test_long_probes_through_every_reader(dev, dim):
+    """A table filled to its last slot: every reader of the read-only probe (find, located find, pooled on its one-tile and four-tile
+    paths, grouped find, remove) walks multi-bucket chains, and an absent key ends only after all the buckets were visited, since no
+    EMPTY slot is left to stop at.  Bit-exact against the oracle; slots are placement-dependent, so the located find is compared by its
+    rows and found mask."""
+    from meepoembedding_amd import TableGroup
+    t = LookupTable(16 * 64, dim, device=dev, max_batch=4096, default_value=0.25)
+    o = oracle.OracleTable(16 * 64, dim, default_value=0.25)
+    cap = t.capacity                       # the bucket count is rounded to a prime
+    assert cap == o.capacity
+    keys = synth.keys_np(61, 0, 2 * cap); rows = synth.rows_np(keys[:cap], dim, 4)
+    t.insert(T(keys[:cap], dev), T(rows, dev)); o.insert(keys[:cap], rows)
+    assert t.size() == o.size() == cap and t.status() == o.status() == 0
+    rng = np.random.default_rng(61)
+    q = np.concatenate([keys, [oracle.EMPTY_KEY, oracle.RECLAIMED_KEY]])[rng.permutation(2 * cap + 2)]
+    eo, ef = o.find(q)
+    assert int(ef.sum()) == cap
+    out, found = t.find(T(q, dev))
+    assert np.array_equal(found.cpu().numpy(), ef) and np.array_equal(out.cpu().numpy(), eo)
+    out, found, slots = t.find_located(T(q, dev))
+    assert np.array_equal(found.cpu().numpy(), ef) and np.array_equal(out.cpu().numpy(), eo)
+    assert np.array_equal(slots.cpu().numpy() >= 0, ef.astype(bool))
+    # bags of 1..20 keys: below 16 a tile takes the bag, from 16 on the wave's four tiles share it
+    off = np.concatenate([[0], np.minimum(np.cumsum(np.tile(np.arange(1, 21), q.size // 210 + 1)), q.size)])
+    off = off[: int(np.argmax(off == q.size)) + 1].astype(np.int64)
+    for mode in ("sum", "mean"):
+        pout, pfound = t.find_pooled(T(q, dev), T(off, dev), mode)
+        assert np.array_equal(pfound.cpu().numpy(), ef) and np.array_equal(pout.cpu().numpy(), oracle.pool_rows(eo, off, mode))
+    # a group of this table and a half-empty one
+    t2 = LookupTable(16 * 64, dim, device=dev, max_batch=4096, default_value=-1.0)
+    o2 = oracle.OracleTable(16 * 64, dim, default_value=-1.0)
+    k2 = synth.keys_np(62, 0, cap); r2 = synth.rows_np(k2[: cap // 2], dim, 5)
+    t2.insert(T(k2[: cap // 2], dev), T(r2, dev)); o2.insert(k2[: cap // 2], r2)
+    q2 = k2[rng.permutation(cap)]
+    eo2, ef2 = o2.find(q2)
+    grp = TableGroup([t, t2])
+    gout, gfound = grp.find(T(np.concatenate([q, q2]), dev), torch.tensor([0, q.size, q.size + q2.size], dtype=torch.int64, device=dev))
+    assert np.array_equal(gfound.cpu().numpy(), np.concatenate([ef, ef2])) and np.array_equal(gout.cpu().numpy(), np.concatenate([eo, eo2]))
+    grp.close()
+    fg = t.remove(T(q.copy(), dev)); fo = o.remove(q)
+    assert np.array_equal(fg.cpu().numpy(), fo) and int(fo.sum()) == cap and t.size() == o.size() == 0
+
+
 def test_remove_and_churn(dev):
     """remove + tombstone reuse vs the oracle: found-masks, survivors, re-insertion, a table kept ~full under churn."""
     dim, cap = 16, 16 * 300
