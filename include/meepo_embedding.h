@@ -459,6 +459,27 @@ int mee_run_offsets(mee_router* r, const uint32_t* d_run_len, size_t n_runs, uin
 int mee_combine_bag_runs(mee_router* r, const float* d_partials, const uint32_t* d_run_bag, const uint64_t* d_run_counts, size_t n_runs,
                          const uint64_t* d_bag_offsets, size_t n_bags, uint32_t dim, int mode, void* d_out, uint32_t out_dtype, void* stream);
 
+/* ---- table groups over sharded tables (SPEC.md §5 "Groups"): owner(key) does not depend on the table and the partition is stable, so ONE mee_partition
+ * serves the whole jagged batch of a group, and inside every owner segment the entries of member 0 come before those of member 1, and so on.  Both calls
+ * take a stream, never synchronise, read nothing back and can be captured; caller data is never used as an address unchecked.
+ *
+ * mee_segment_counts — the source's side.  d_perm[n] / d_counts[n_shards] are what mee_partition wrote, d_offsets[n_tables + 1] the member segments of
+ * the batch (non-decreasing).  d_cell_counts[n_shards, n_tables] (uint64): cell (p, j) = the number of entries of owner segment p whose batch position
+ * lies in [offsets[j], offsets[j + 1]).  Positions outside [offsets[0], offsets[n_tables]) belong to no cell.  Row p is what rank p is sent as counts;
+ * its sum is the number of keys it is sent.  n <= the router's max_batch (MEE_ERR_BATCH_TOO_LARGE), 1 <= n_tables <= 1024. */
+int mee_segment_counts(mee_router* r, const int64_t* d_perm, const uint64_t* d_counts, size_t n, const uint64_t* d_offsets, size_t n_tables,
+                       uint64_t* d_cell_counts, void* stream);
+/* mee_regroup — the owner's side.  d_recv_keys[n_recv] = the keys received from all ranks, source-major: source 0's members 0 … n_tables - 1, then
+ * source 1's, …; d_recv_cells[n_shards, n_tables] (uint64) = the received cell counts, row s from source rank s.  Writes the batch TABLE-MAJOR, the
+ * order the mee_group_* operators take: member j, inside it source rank ascending, inside that arrival order.
+ *   d_keys_out[n_recv]     the keys           d_order_out[n_recv]  (int64) order[q] = the source-major index of table-major position q, the convention
+ *   d_offsets_out[n_tables + 1] (uint64) the member offsets        of d_perm: mee_gather_rows brings received rows into table-major order,
+ *                                                                  mee_scatter_rows brings result rows back into source-major order
+ * Positions past the sum of the cells are left alone.  n_recv <= n_shards x max_batch and < 2^32 - 2048 (MEE_ERR_BATCH_TOO_LARGE); 1 <= n_tables <= 1024
+ * and n_shards x n_tables <= 8128.  16-byte accesses when d_recv_keys, d_keys_out and d_order_out are 16-byte aligned. */
+int mee_regroup(mee_router* r, const int64_t* d_recv_keys, const uint64_t* d_recv_cells, size_t n_recv, size_t n_tables, int64_t* d_keys_out,
+                int64_t* d_order_out, uint64_t* d_offsets_out, void* stream);
+
 /* ---- sharded find over peer-mapped memory (README.md:2 "distributed"; SPEC.md §5) ---------------------------------
  * One context per rank; all ranks use the same n_shards / slots_per_peer / max_batch / dim.  The local buffers
  * (key inbox, destination inbox, fill counts, result rows, found bytes, and the payload-row inbox if any) are exported as HIP IPC handles, the caller

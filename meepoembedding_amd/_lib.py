@@ -172,6 +172,8 @@ PROTOTYPES = {
     "mee_bag_runs": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
     "mee_run_offsets": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp]),
     "mee_combine_bag_runs": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _u32, C.c_int, _vp, _u32, _vp]),
+    "mee_segment_counts": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "mee_regroup": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     # row-sharded table over RCCL (meepo_sharded.hip)
     "mee_comm_unique_id": (C.c_int, [_vp]),
     "mee_comm_create": (C.c_int, [_vp, _u32, _u32, _i32, C.POINTER(_vp)]),

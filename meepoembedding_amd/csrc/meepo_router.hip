@@ -6,8 +6,8 @@
 // scan over blocks (one wave per shard, shuffle prefix-sum), and a scatter that recomputes each key's rank
 // from the same ballots.  The run bookkeeping of the sharded embedding bags (bag_runs) is the same sort with
 // "first position of a run in segment p" in the place of "key owned by p": both go through count_owners.
-// Further down: the run offsets and the combination of the owners' partial bag rows, and the peer-to-peer
-// sharded find, whose owner-side kernel probes with the lookups' tile_probe (meepo_device.h).
+// Further down: the run offsets and the combination of the owners' partial bag rows, the cells and the regrouping
+// of a sharded table group's jagged batch (segment_counts, regroup), and the peer-to-peer sharded find, whose owner-side kernel probes with the lookups' tile_probe (meepo_device.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -407,6 +407,139 @@ __global__ __launch_bounds__(256) void combine_bag_runs_kernel(const float4* __r
     }
 }
 
+// ---- sharded table groups (SPEC.md §5 "Groups"): the cells of a partitioned jagged batch, and the owner's source-major -> table-major regrouping ----
+// owner(key, G) does not depend on the table and the partition is stable, so one partition serves a whole jagged batch: inside owner segment p the
+// positions ascend, hence the entries of table segment j are one contiguous CELL (p, j) of it, bounded by two binary searches in perm.
+// grid: x = owner segment, y = 256 cells of it.  The 257 bounds of a block's cells go through LDS: one search per bound, G (T + 1) in all (+ one per
+// further 256 cells).  perm entries are only compared; a segment never reaches past n whatever the counts say.
+__global__ __launch_bounds__(256) void segment_counts_kernel(const int64_t* __restrict__ perm, const uint64_t* __restrict__ counts, uint32_t n,
+                                                            const uint64_t* __restrict__ offsets, uint32_t n_tables, uint64_t* __restrict__ cells) {
+    __shared__ uint32_t s_bound[257];
+    const uint32_t p = blockIdx.x, j0 = blockIdx.y * 256;
+    uint64_t acc = 0;
+    uint32_t seg_begin = 0;
+    for (uint32_t pp = 0; pp <= p; ++pp) {   // block-uniform
+        seg_begin = (uint32_t)acc;
+        const uint64_t c = counts[pp];
+        acc += c < n ? c : n;
+        acc = acc < n ? acc : n;
+    }
+    const uint32_t seg_end = (uint32_t)acc;
+    for (uint32_t k = threadIdx.x; k < 257; k += 256) {
+        const uint32_t j = j0 + k;
+        if (j > n_tables) continue;
+        const uint64_t bound = offsets[j];
+        uint32_t lo = seg_begin, hi = seg_end;   // the first entry of the segment whose position is not below the bound
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if ((uint64_t)perm[mid] < bound) lo = mid + 1; else hi = mid;
+        }
+        s_bound[k] = lo;
+    }
+    __syncthreads();
+    const uint32_t j = j0 + threadIdx.x;
+    if (j < n_tables) {
+        const uint32_t b = s_bound[threadIdx.x], e = s_bound[threadIdx.x + 1];
+        cells[(uint64_t)p * n_tables + j] = e > b ? e - b : 0;   // (offsets that decrease: an empty cell)
+    }
+}
+
+// The owner's side.  What arrived is source-major: cell (s, j) = the keys of source rank s for member table j, at cell index s T + j.  The group kernels
+// take the batch table-major: cell (s, j) at cell index j G + s.  Every block scans the G T cell lengths twice (source-major and table-major, into LDS:
+// two block scans per 512 cells, nothing next to the copy) and then copies its own tile of V x 512 consecutive TABLE-MAJOR positions: a thread finds
+// the cell of its first position by binary search in the LDS offsets (empty cells are skipped by the search itself), so consecutive lanes write
+// consecutive positions and read consecutive positions of one cell.  V = 2 (all three arrays 16-byte aligned): a thread owns an aligned pair of
+// positions, stores keys and order as 16 bytes each and loads the keys as 16 bytes when the pair lies in one cell at an even source position.
+// Cell lengths are caller data: every offset is kept inside [0, n_recv] and a source position is only used below n_recv; positions past the cells' sum
+// are left alone.  No atomics, no workspace: the launch only reads the cells and the keys.
+constexpr int kRegroupMaxCells = 8128;   // 2 x (cells + 1) 32-bit offsets in LDS
+constexpr int kRegroupBlock = 512;       // threads per block: a tile of V x 512 positions per scan of the cells
+
+__device__ __forceinline__ uint32_t lds_last_not_above(const uint32_t* off, uint32_t m, uint32_t q) {   // the last c in [0, m) with off[c] <= q (off[0] = 0)
+    uint32_t lo = 0, hi = m - 1;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (off[mid] <= q) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+template <int V>
+__global__ __launch_bounds__(kRegroupBlock) void regroup_kernel(const int64_t* __restrict__ recv_keys, const uint64_t* __restrict__ recv_cells, uint32_t n_recv,
+                                                             uint32_t g, uint32_t n_tables, int64_t* __restrict__ keys_out, int64_t* __restrict__ order_out,
+                                                             uint64_t* __restrict__ offsets_out) {
+    extern __shared__ uint32_t s_off[];   // [cells + 1] table-major offsets (by j G + s), then [cells + 1] source-major offsets (by s T + j)
+    __shared__ uint64_t s_w[kRegroupBlock / 64];
+    const uint32_t n_cells = g * n_tables;
+    uint32_t* dst_off = s_off;
+    uint32_t* src_off = s_off + n_cells + 1;
+    uint64_t carry_d = 0, carry_s = 0;
+    for (uint32_t c0 = 0; c0 < n_cells; c0 += kRegroupBlock) {   // block-uniform
+        const uint32_t c = c0 + threadIdx.x;
+        uint64_t len_d = 0, len_s = 0;
+        if (c < n_cells) {
+            const uint32_t j = c / g, s = c - j * g;
+            len_d = recv_cells[(uint64_t)s * n_tables + j];
+            len_s = recv_cells[c];
+            len_d = len_d < n_recv ? len_d : n_recv;
+            len_s = len_s < n_recv ? len_s : n_recv;
+        }
+        uint64_t total_d, total_s;
+        const uint64_t ex_d = carry_d + block_scan_exclusive(len_d, s_w, total_d);
+        const uint64_t ex_s = carry_s + block_scan_exclusive(len_s, s_w, total_s);
+        if (c < n_cells) {
+            dst_off[c] = (uint32_t)(ex_d < n_recv ? ex_d : n_recv);
+            src_off[c] = (uint32_t)(ex_s < n_recv ? ex_s : n_recv);
+        }
+        carry_d += total_d;
+        carry_s += total_s;
+        carry_d = carry_d < n_recv ? carry_d : n_recv;
+        carry_s = carry_s < n_recv ? carry_s : n_recv;
+    }
+    if (threadIdx.x == 0) {
+        dst_off[n_cells] = (uint32_t)carry_d;
+        src_off[n_cells] = (uint32_t)carry_s;
+    }
+    __syncthreads();
+    const uint32_t total = dst_off[n_cells];
+    if (blockIdx.x == 0)
+        for (uint32_t j = threadIdx.x; j <= n_tables; j += kRegroupBlock) offsets_out[j] = dst_off[j * g];   // (j = T: the cells' sum)
+
+    const uint32_t q0 = (blockIdx.x * kRegroupBlock + threadIdx.x) * V;
+    if (q0 >= total) return;
+    const uint32_t c = lds_last_not_above(dst_off, n_cells, q0);   // table-major cell j G + s
+    const uint32_t j = c / g, s = c - j * g;
+    const uint64_t src = (uint64_t)src_off[s * n_tables + j] + (q0 - dst_off[c]);
+    if constexpr (V == 1) {
+        if (src < n_recv) {
+            keys_out[q0] = recv_keys[src];
+            order_out[q0] = (int64_t)src;
+        }
+    } else {
+        const bool two = q0 + 1 < total;
+        uint64_t src1 = src + 1;
+        if (two && q0 + 1 >= dst_off[c + 1]) {   // the pair straddles a cell boundary (and any empty cells behind it)
+            const uint32_t c1 = lds_last_not_above(dst_off, n_cells, q0 + 1);
+            const uint32_t j1 = c1 / g, s1 = c1 - j1 * g;
+            src1 = (uint64_t)src_off[s1 * n_tables + j1] + (q0 + 1 - dst_off[c1]);
+        }
+        const bool ok0 = src < n_recv, ok1 = two && src1 < n_recv;
+        longlong2 k = make_longlong2(kEmpty, kEmpty);
+        if (ok0 && ok1 && src1 == src + 1 && (src & 1) == 0) k = *reinterpret_cast<const longlong2*>(recv_keys + src);
+        else {
+            if (ok0) k.x = recv_keys[src];
+            if (ok1) k.y = recv_keys[src1];
+        }
+        if (ok0 && ok1) {
+            *reinterpret_cast<longlong2*>(keys_out + q0) = k;
+            *reinterpret_cast<longlong2*>(order_out + q0) = make_longlong2((long long)src, (long long)src1);
+        } else {
+            if (ok0) { keys_out[q0] = k.x; order_out[q0] = (int64_t)src; }
+            if (ok1) { keys_out[q0 + 1] = k.y; order_out[q0 + 1] = (int64_t)src1; }
+        }
+    }
+}
+
 // ---- peer-to-peer sharded find (SPEC.md §5 without the all-to-alls) ---------------------------------------------
 // Every rank owns five "symmetric" buffers that its peers map through HIP IPC: an inbox of keys and of destination
 // indices with one segment per source rank, the segment fill counts, and its result rows / found bytes.  A lookup is
@@ -684,6 +817,41 @@ int mee_combine_bag_runs(mee_router* r, const float* d_partials, const uint32_t*
         combine_bag_runs_kernel<d4, bf16><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>((const float4*)d_partials, d_run_bag, d_run_counts, r->n_shards, n_runs,
                                                                                          d_bag_offsets, n_bags, dim / 4, mode == MEE_POOL_MEAN, d_out);
     }); });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+// ---- sharded table groups: the (owner, table) cells of a partitioned jagged batch, and the owner's regrouping -----------------------------------
+int mee_segment_counts(mee_router* r, const int64_t* d_perm, const uint64_t* d_counts, size_t n, const uint64_t* d_offsets, size_t n_tables,
+                       uint64_t* d_cell_counts, void* stream) {
+    MEE_RANGE("mee_segment_counts");
+    if (!r || !d_counts || !d_offsets || !d_cell_counts || (n && !d_perm)) return fail(MEE_ERR_INVALID_ARG, "mee_segment_counts: null argument");
+    if (n > r->max_batch) return fail(MEE_ERR_BATCH_TOO_LARGE, "mee_segment_counts: n=%zu exceeds max_batch=%llu", n, (unsigned long long)r->max_batch);
+    if (n_tables == 0 || n_tables > kMaxGroupTables) return fail(MEE_ERR_INVALID_ARG, "mee_segment_counts: n_tables must be in [1, %u]", kMaxGroupTables);
+    DeviceGuard g(r->device);
+    const dim3 grid(r->n_shards, (unsigned)((n_tables + 255) / 256));
+    segment_counts_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(d_perm, d_counts, (uint32_t)n, d_offsets, (uint32_t)n_tables, d_cell_counts);
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+int mee_regroup(mee_router* r, const int64_t* d_recv_keys, const uint64_t* d_recv_cells, size_t n_recv, size_t n_tables, int64_t* d_keys_out,
+                int64_t* d_order_out, uint64_t* d_offsets_out, void* stream) {
+    MEE_RANGE("mee_regroup");
+    if (!r || !d_recv_cells || !d_offsets_out || (n_recv && (!d_recv_keys || !d_keys_out || !d_order_out))) return fail(MEE_ERR_INVALID_ARG, "mee_regroup: null argument");
+    if (n_recv > (size_t)r->max_batch * r->n_shards)
+        return fail(MEE_ERR_BATCH_TOO_LARGE, "mee_regroup: n_recv=%zu exceeds n_shards x max_batch=%llu", n_recv, (unsigned long long)(r->max_batch * r->n_shards));
+    if (n_recv > 0xFFFFFFFFull - 2 * kPartBlock) return fail(MEE_ERR_BATCH_TOO_LARGE, "mee_regroup: n_recv=%zu does not fit the 32-bit position", n_recv);
+    if (n_tables == 0 || n_tables > kMaxGroupTables || n_tables * r->n_shards > (size_t)kRegroupMaxCells)
+        return fail(MEE_ERR_INVALID_ARG, "mee_regroup: n_tables must be in [1, %u] and n_shards x n_tables <= %d (the cell offsets live in LDS)", kMaxGroupTables, kRegroupMaxCells);
+    DeviceGuard g(r->device);
+    const size_t lds = 2 * (n_tables * r->n_shards + 1) * sizeof(uint32_t);
+    const bool a16 = (((uintptr_t)d_recv_keys | (uintptr_t)d_keys_out | (uintptr_t)d_order_out) & 15) == 0;
+    with_flag(a16, [&](auto wide) {
+        constexpr int V = decltype(wide)::value ? 2 : 1;
+        regroup_kernel<V><<<grid_for(n_recv, kRegroupBlock * V, 1u << 23), kRegroupBlock, lds, (hipStream_t)stream>>>(
+            d_recv_keys, d_recv_cells, (uint32_t)n_recv, r->n_shards, (uint32_t)n_tables, d_keys_out, d_order_out, d_offsets_out);
+    });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }

@@ -20,6 +20,9 @@ the backward) instead of one per key:
 
 Reference anchor: /root/reference/README.md:2 ("A distributed … Embedding"); the snapshot has no code.
 
+Table groups (ShardedTableGroup; SPEC.md §5 "Groups"): one partition and ONE exchange per operator serve the jagged batch of a whole collection of
+sharded tables — 4 collectives per find, 3 per apply, whatever the number of tables (segment_counts on the source, regroup on the owner).
+
 This module is host logic only: `local` is any object with the LookupTable operator methods and `router` any
 object with partition / gather_rows / scatter_rows (the HIP-backed LookupTable / Router in production).
 """
@@ -33,16 +36,18 @@ import torch.distributed as dist
 from .table import _out_dtype
 
 
-class ShardedLookupTable:
-    def __init__(self, local, router, group=None):
-        self.local, self.router, self.group = local, router, group
+class _Exchange:
+    """What ShardedLookupTable and ShardedTableGroup share: the process group, the all-to-alls and their counters."""
+
+    def __init__(self, router, group=None):
+        self.router, self.group = router, group
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
         # a gloo group cannot move device tensors: stage them through host memory (rehearsals of the multi-rank GPU
         # path on a single-GPU box; production uses the "nccl" backend = RCCL over xGMI, no staging)
         self._stage = dist.get_backend(group) == "gloo"
-        self.dim = local.dim
         self._sent = self._received = 0   # traffic()
+        self.collectives = 0              # every all_to_all_single this object issued
         if router.n_shards != self.world:
             raise ValueError(f"router has {router.n_shards} shards, process group has {self.world} ranks")
 
@@ -51,6 +56,7 @@ class ShardedLookupTable:
         """all-to-all of per-destination counts ([G] or [G, m] int64: m values for every rank) -> (sent, received) on the host"""
         self._sent += counts.numel() // self.world * (self.world - 1) * 8
         self._received += counts.numel() // self.world * (self.world - 1) * 8
+        self.collectives += 1
         if self._stage and counts.is_cuda:
             c_host = counts.cpu()
             r_host = torch.empty_like(c_host)
@@ -60,12 +66,6 @@ class ShardedLookupTable:
         dist.all_to_all_single(recv_counts, counts, group=self.group)
         both = torch.stack([counts, recv_counts]).cpu()  # the one host sync of the exchange
         return both[0], both[1]
-
-    def _route(self, keys: torch.Tensor):
-        """partition + counts exchange. Returns (send_keys, perm, send_splits, recv_splits)."""
-        send_keys, counts, perm = self.router.partition(keys)
-        sent, received = self._swap_counts(counts)
-        return send_keys, perm, sent.tolist(), received.tolist()
 
     def traffic(self) -> tuple[int, int]:
         """(sent, received): bytes handed to the process group for OTHER ranks since this table was made — every _a2a and every count exchange;
@@ -79,6 +79,7 @@ class ShardedLookupTable:
         row_bytes = t.element_size() * math.prod(t.shape[1:])
         self._sent += (sum(in_splits) - in_splits[self.rank]) * row_bytes
         self._received += (sum(out_splits) - out_splits[self.rank]) * row_bytes
+        self.collectives += 1
         if self._stage and t.is_cuda:
             src = t.contiguous().cpu()
             dst = torch.empty((sum(out_splits),) + tuple(t.shape[1:]), dtype=t.dtype)
@@ -88,7 +89,6 @@ class ShardedLookupTable:
         dist.all_to_all_single(out, t.contiguous(), output_split_sizes=out_splits, input_split_sizes=in_splits, group=self.group)
         return out
 
-    # -- operators ---------------------------------------------------------------------------------------
     def _typed(self, out_dtype: torch.dtype) -> dict:
         """the local lookup's out_dtype keyword (none at fp32: a `local` without the keyword keeps working); refused before anything is exchanged"""
         if _out_dtype(out_dtype) == 0:
@@ -97,6 +97,20 @@ class ShardedLookupTable:
             raise ValueError(f"{type(self.local).__name__} has no bf16 lookup: use out_dtype=torch.float32 and cast the result")
         return {"out_dtype": out_dtype}
 
+
+class ShardedLookupTable(_Exchange):
+    def __init__(self, local, router, group=None):
+        self.local = local
+        self.dim = local.dim
+        super().__init__(router, group)
+
+    def _route(self, keys: torch.Tensor):
+        """partition + counts exchange. Returns (send_keys, perm, send_splits, recv_splits)."""
+        send_keys, counts, perm = self.router.partition(keys)
+        sent, received = self._swap_counts(counts)
+        return send_keys, perm, sent.tolist(), received.tolist()
+
+    # -- operators ---------------------------------------------------------------------------------------
     def _lookup(self, keys: torch.Tensor, insert_missing: bool, dedup: bool = False, out_dtype: torch.dtype = torch.float32):
         typed = self._typed(out_dtype)
         keys = keys.contiguous().view(-1)
@@ -297,6 +311,112 @@ class ShardedLookupTable:
         return self._dev()
 
     pools_with_insert = True   # find_pooled(insert_missing=True): what DynamicEmbeddingBag(create_missing=True) calls instead of a find_or_insert of its own
+
+
+
+class ShardedTableGroup(_Exchange):
+    """A whole collection of row-sharded tables behind ONE exchange per operator (SPEC.md §5 "Groups"): every rank holds one TableGroup of its T local
+    shards (`local_group`), a call takes the rank's jagged batch (keys, offsets[T + 1] on the device, as TableGroup's operators) and is, by
+    definition, the sharded single-table operator applied to every member with its segment.  owner(key) does not depend on the table and the
+    partition is stable, so the batch is partitioned once and the members' keys stay in member order inside every owner's segment:
+
+        partition(keys)  ->  segment_counts: the [G, T] cells  ->  ONE all-to-all of the cells (the key splits are their row sums)  ->  all-to-all keys
+        owner: regroup (source-major -> table-major keys, order, member offsets), ONE local_group operator over the regrouped batch
+        find: scatter_rows(rows, order), all-to-all rows + found-mask back, scatter through perm
+        apply: the gradient rows gathered through perm, sent, gathered through order
+
+    4 collectives per find and 3 per apply whatever T is, where T ShardedLookupTable calls make 4 T and 3 T (and T host syncs); the bytes are the same
+    plus 8 T (G - 1) count bytes each way instead of 8 T (G - 1) in T pieces.  Collective: every rank calls, also with an empty batch.
+    `router`: the HIP Router (segment_counts / regroup); dedup= and grad_index= are not offered, nor are the pooled forms."""
+
+    def __init__(self, local_group, router, group=None):
+        if not hasattr(local_group, "tables"):
+            raise ValueError(f"{type(local_group).__name__} is no group of tables (a TableGroup of the rank's local shards)")
+        self.local = self.local_group = local_group
+        self.dim = local_group.dim
+        self.n_tables = len(local_group.tables)
+        super().__init__(router, group)
+
+    @property
+    def tables(self):
+        return self.local_group.tables
+
+    @property
+    def supports_out_dtype(self) -> bool:
+        return bool(getattr(self.local_group, "supports_out_dtype", False))
+
+    @property
+    def device(self):
+        return getattr(self.local_group, "device", torch.device("cpu"))
+
+    def _check(self, op: str, keys: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+        """what every rank can decide alone, before anything is exchanged"""
+        if not callable(getattr(self.local_group, op, None)):
+            raise ValueError(f"{type(self.local_group).__name__} has no {op}")
+        if not hasattr(self.router, "segment_counts") or not hasattr(self.router, "regroup"):
+            raise ValueError(f"{type(self.router).__name__} has no segment_counts / regroup: sharded groups need the HIP Router")
+        if offsets.dim() != 1 or offsets.numel() != self.n_tables + 1:
+            raise ValueError(f"offsets must hold n_tables + 1 = {self.n_tables + 1} entries (got {tuple(offsets.shape)})")
+        return keys.contiguous().view(-1)
+
+    def _route(self, keys: torch.Tensor, offsets: torch.Tensor):
+        """partition + cells + ONE count exchange -> (send_keys, perm, key splits out / in, the received cells [G, T] on the keys' device)"""
+        send_keys, counts, perm = self.router.partition(keys)
+        cells = self.router.segment_counts(perm, counts, offsets)
+        sent, received = self._swap_counts(cells)
+        ss, rs = sent.sum(dim=1).tolist(), received.sum(dim=1).tolist()
+        if sum(ss) != keys.numel():   # positions in no segment (offsets[0] > 0 or offsets[T] < n) are not sent; inside an owner segment the others stay contiguous
+            off = offsets.view(torch.int64)
+            inside = (perm >= off[0]) & (perm < off[-1])
+            send_keys, perm = send_keys[inside], perm[inside]
+        return send_keys, perm, ss, rs, received.to(keys.device)
+
+    def _lookup(self, op: str, keys: torch.Tensor, offsets: torch.Tensor, out_dtype: torch.dtype):
+        typed = self._typed(out_dtype)
+        keys = self._check(op, keys, offsets)
+        n = keys.numel()
+        send_keys, perm, ss, rs, recv_cells = self._route(keys, offsets)
+        recv_keys = self._a2a(send_keys, ss, rs)
+        keys_tm, order, offsets_tm = self.router.regroup(recv_keys, recv_cells)
+        rows, found = getattr(self.local_group, op)(keys_tm, offsets_tm, **typed)
+        rows_back = self._a2a(self.router.scatter_rows(rows, order), rs, ss)
+        found_back = self._a2a(self.router.scatter_rows(found, order), rs, ss)
+        if perm.numel() == n:
+            return self.router.scatter_rows(rows_back, perm), self.router.scatter_rows(found_back, perm)
+        out = rows_back.new_zeros((n, self.dim))   # positions in no segment: zeros, not found
+        fnd = found_back.new_zeros(n)
+        return self.router.scatter_rows(rows_back, perm, out=out), self.router.scatter_rows(found_back, perm, out=fnd)
+
+    def find(self, keys: torch.Tensor, offsets: torch.Tensor, out_dtype: torch.dtype = torch.float32):
+        """-> (rows [n, dim], found [n]) in batch order: ShardedLookupTable.find of every member with its segment.  out_dtype=torch.bfloat16: the
+        owners round before the rows travel."""
+        return self._lookup("find", keys, offsets, out_dtype)
+
+    def find_or_insert(self, keys: torch.Tensor, offsets: torch.Tensor, out_dtype: torch.dtype = torch.float32):
+        return self._lookup("find_or_insert", keys, offsets, out_dtype)
+
+    def _push(self, op: str, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor):
+        """-> (keys, member offsets, gradient rows) of everything this rank owns, table-major; duplicates are reduced by the local apply, per member,
+        over all ranks' contributions"""
+        keys = self._check(op, keys, offsets)
+        g = grads.contiguous().view(-1, self.dim)
+        if g.shape[0] != keys.numel():
+            raise ValueError(f"grads must hold one row of {self.dim} per key")
+        send_keys, perm, ss, rs, recv_cells = self._route(keys, offsets)
+        send_rows = self.router.gather_rows(g, perm)
+        recv_keys = self._a2a(send_keys, ss, rs)
+        recv_rows = self._a2a(send_rows, ss, rs)
+        keys_tm, order, offsets_tm = self.router.regroup(recv_keys, recv_cells)
+        return keys_tm, offsets_tm, self.router.gather_rows(recv_rows, order)
+
+    def apply_adagrad(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10) -> None:
+        k, off, g = self._push("apply_adagrad", keys, offsets, grads)
+        self.local_group.apply_adagrad(k, off, g, lr, eps)
+
+    def apply_adam(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999,
+                   eps: float = 1e-8, step: int = 1) -> None:
+        k, off, g = self._push("apply_adam", keys, offsets, grads)
+        self.local_group.apply_adam(k, off, g, lr, beta1, beta2, eps, step)
 
 
 class RcclShardedTable:

@@ -867,3 +867,33 @@ class Router:
         check(_lib.lib().mee_combine_bag_runs(self._h, p.data_ptr(), run_bag.data_ptr(), run_counts.data_ptr(), p.shape[0], bag_offsets.data_ptr(),
                                               n_bags, p.shape[1], {"sum": 0, "mean": 1}[mode], out.data_ptr(), dt, _stream_ptr(self.device)))
         return out
+
+    # -- table groups over sharded tables (SPEC.md §5 "Groups") ------------------------------------------------------------
+    def segment_counts(self, perm: torch.Tensor, counts: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+        """The cells of a partitioned jagged batch (mee_segment_counts) -> int64 [n_shards, n_tables]: cell (p, j) = the entries of owner segment p whose
+        batch position lies in member segment j = [offsets[j], offsets[j + 1]).  Row p is what rank p is sent as counts.  Sync-free."""
+        if offsets.device != self.device or offsets.dtype not in (torch.int64, torch.uint64) or offsets.dim() != 1 or offsets.numel() < 2 \
+                or not offsets.is_contiguous():
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"offsets must be n_tables + 1 contiguous int64 values on {self.device}")
+        n_tables = offsets.numel() - 1
+        cells = torch.empty((self.n_shards, n_tables), dtype=torch.int64, device=self.device)
+        check(_lib.lib().mee_segment_counts(self._h, perm.data_ptr(), counts.data_ptr(), perm.numel(), offsets.data_ptr(), n_tables, cells.data_ptr(),
+                                            _stream_ptr(self.device)))
+        return cells
+
+    def regroup(self, recv_keys: torch.Tensor, recv_cells: torch.Tensor):
+        """The owner's side (mee_regroup): the received keys, source-major (source 0's members 0 … T-1, then source 1's, …; recv_cells int64
+        [n_shards, T] on the device = the received cell counts) -> (keys [n] table-major = member j, inside it source rank ascending, inside that
+        arrival order; order [n] int64 = the source-major index of every table-major position, for gather_rows / scatter_rows; offsets [T + 1] int64 =
+        the member offsets of the regrouped batch, what TableGroup's operators take).  Sync-free."""
+        k = recv_keys.contiguous().view(-1)
+        c = recv_cells.contiguous()
+        if c.device != self.device or c.dtype not in (torch.int64, torch.uint64) or c.dim() != 2 or c.shape[0] != self.n_shards or c.shape[1] < 1:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"recv_cells must be int64 [{self.n_shards}, n_tables] on {self.device}")
+        n, n_tables = k.numel(), c.shape[1]
+        keys_out = torch.empty_like(k)
+        order = torch.empty(n, dtype=torch.int64, device=self.device)
+        offsets = torch.empty(n_tables + 1, dtype=torch.int64, device=self.device)
+        check(_lib.lib().mee_regroup(self._h, k.data_ptr(), c.data_ptr(), n, n_tables, keys_out.data_ptr(), order.data_ptr(), offsets.data_ptr(),
+                                     _stream_ptr(self.device)))
+        return keys_out, order, offsets
