@@ -129,27 +129,7 @@ struct ApplyLds {
     uint32_t pre_slabs[kApplyThreads + 1], pre_pos[kApplyThreads + 1], pre_a[kApplyThreads];   // (pre_a: the total of the thread's first bucket)
     alignas(16) double prow[kLdsPartRows][64];   // fp64 partial rows of the slab's long runs when there are few and the rows are short (dim <= 64): no trip through memory
     uint32_t part_lds;   // skewed batches: slabs / positions in front of each thread's buckets
-#if MEE_APPLY_TIMELINE
-    uint32_t tl_w;
-#endif
 };
-
-// MEE_APPLY_TIMELINE (diagnostic builds only: tools/apply_timeline.py): thread 0 of every block stamps the 100 MHz wall clock at the phase
-// boundaries of its bucket into a buffer the host reads back (mee_debug_timeline).
-#ifndef MEE_APPLY_TIMELINE
-#define MEE_APPLY_TIMELINE 0
-#endif
-#if MEE_APPLY_TIMELINE
-#define MEE_TL(A_, i) do { if (threadIdx.x == 0) (A_).dbg[(uint64_t)blockIdx.x * 8 + (i)] = wall_clock64(); } while (0)
-// blocks of a skewed batch (skew_units): 128 words per block behind that area — [0] entry, [1] units taken, [2] scan done, then 16 words per slab unit taken
-#define MEE_TLS(A_, e_, w_, v_) do { if (threadIdx.x == 0 && (w_) < 128) (A_).dbg[16384ull * 8 + (uint64_t)(e_) * 128 + (w_)] = (v_); } while (0)
-// ... of which process_slab stamps its own phases: words 8..11 of the slab pass, 12..15 of the latest merge pass (L.tl_w = the slab's first word)
-#define MEE_TLP(A_, L_, k_) do { if (SPLIT && threadIdx.x == 0) (A_).dbg[16384ull * 8 + (L_).tl_w + (src_rec ? 12 : 8) + (k_)] = wall_clock64(); } while (0)
-#else
-#define MEE_TL(A_, i) do { } while (0)
-#define MEE_TLS(A_, e_, w_, v_) do { } while (0)
-#define MEE_TLP(A_, L_, k_) do { } while (0)
-#endif
 
 // how an update's rows are stored: plain stores (streaming and write-through stores measured: nothing moves)
 __device__ __forceinline__ void store_row4(float4* p, const float4& v) { *p = v; }
@@ -164,9 +144,6 @@ struct ApplyArgs {
     uint32_t hot_count;                     // occurrences in one bucket or slab that make a key hot (its own bucket in the next batch)
     uint32_t* h_slabs;                      // pinned host word: the slabs this batch's split buckets were cut into (0: none)
     OpCounters* op;
-#if MEE_APPLY_TIMELINE
-    unsigned long long* dbg;
-#endif
     const GroupDesc* desc; uint32_t n_tables;   // GROUPED kernels (mee_group_apply_*): the members' planes; a "slot" is member << 48 | slot
     OptArgs a;
 };
@@ -191,7 +168,7 @@ __device__ __forceinline__ RowAt row_at(const ApplyArgs& A, const GroupDesc* gde
 // likely another XCD with its own L2.  They are written with agent-scope (sc1: write-through) stores and read with agent-scope loads; the
 // producer drains its stores (s_waitcnt vmcnt(0)) before it draws its ticket.  No release / acquire fence: an agent-scope release is a
 // write-back of the XCD's whole L2, full of the rows the batch has just updated — MI355X_MICROARCH.md "publish-large": 8.2 us against 3.0
-// for a 64 KB slab, and the hand-off of a slab measured 6-7 us with the fence pair (tools/apply_timeline.py).
+// for a 64 KB slab, and the hand-off of a slab measured 6-7 us with the fence pair (a block-timeline build; the hand-off without it: profiles/r04_apply_timeline_zipf.md).
 __device__ __forceinline__ void rec_store(double* p, double v) {
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -332,9 +309,7 @@ __device__ __forceinline__ void process_slab(ApplyLds& L, const ApplyArgs& A, co
             my_sr[u] = sl | atomicAdd(&L.cnt[sl], 1u) << 10 | (uint32_t)first_of_run << 31;
         }
     }
-    __syncthreads();
-    if constexpr (!SPLIT) MEE_TL(A, 2);   // entries fetched, keys in the LDS table
-    MEE_TLP(A, L, 0);
+    __syncthreads();   // entries fetched, keys in the LDS table
     // ---- 2. prefix sums over the runs: where each run starts in src, its work items, its number, its fp64 partial rows ----
     {
         const uint32_t s0 = 2 * t, c0 = L.cnt[s0], c1 = L.cnt[s0 + 1];
@@ -393,25 +368,18 @@ __device__ __forceinline__ void process_slab(ApplyLds& L, const ApplyArgs& A, co
             }
         }
     }
-    __syncthreads();
-    if constexpr (!SPLIT) MEE_TL(A, 3);   // scans done, sources sorted (LOCATED: slot handles arrived)
-    MEE_TLP(A, L, 1);
+    __syncthreads();   // scans done, sources sorted (LOCATED: slot handles arrived)
     const uint32_t n_items = L.n_items, n_quads = L.n_quads, n_big = L.n_big;
     const bool part_lds = L.part_lds != 0;
     const uint32_t n_turns = n_quads + (n_items + 3) / 4;
     const uint32_t rec_out0 = rec_bucket0 + (emit ? L.rec_base : 0u);   // emit: where this slab's records go
     // ---- 3. work items: a wave per turn — a quad (its four tiles sum one chunk each of ONE run) or four tile items ----
-    [[maybe_unused]] uint32_t tl_turn = 0;
     // (a wave asks for its NEXT turn before it works on the current one: the counter's answer travels while the rows do)
     uint32_t turn_next = 0;
     if (lane == 0) turn_next = atomicAdd(&L.next_turn, 1u);
     while (true) {
         const uint32_t turn = __builtin_amdgcn_readfirstlane(turn_next);
         if (turn < n_turns && lane == 0) turn_next = atomicAdd(&L.next_turn, 1u);
-#if MEE_APPLY_TIMELINE
-        if (!SPLIT && threadIdx.x == 0 && tl_turn < 16) A.dbg[16384ull * 8 + (uint64_t)blockIdx.x * 128 + 68 + 2 * tl_turn] = wall_clock64() << 8 | (turn >= n_turns ? 3u : turn < n_quads ? 1u : 2u) | (turn < n_quads ? min(255u, L.cnt[L.quad[turn] & 1023u]) : 0u) << 2 & 0xfcu;
-        ++tl_turn;
-#endif
         if (turn >= n_turns) break;   // wave-uniform: the ballots inside tile_locate and the shuffles of a quad need whole waves
         if (turn < n_quads) {
             const uint32_t e = L.quad[turn];
@@ -513,13 +481,10 @@ __device__ __forceinline__ void process_slab(ApplyLds& L, const ApplyArgs& A, co
             if constexpr (LOCATED) rec_store(bk.pend_slot + rec_out0 + L.run[s], slot);
         }
     }
-    if constexpr (!SPLIT) MEE_TL(A, 4);   // this thread's items done
-    MEE_TLP(A, L, 2);
     if (n_big == 0) return;   // block-uniform
     // ---- 4. runs of several quads: a wave adds the run's partial rows (written by this block: visible after the barrier), tile u rows u, u + 4, …,
     //         and finishes the run ----
     __syncthreads();
-    MEE_TLP(A, L, 3);
     for (uint32_t k = t >> 6; k < n_big; k += kApplyWaves) {   // wave-uniform
         const uint32_t e = L.big[k];
         const uint32_t s = e & 1023u, p0 = (e >> 10) & 4095u, nq = e >> 22;
@@ -673,7 +638,6 @@ template <int KIND, int DIM4, bool LOCATED, bool GROUPED, bool SKEW>
 __device__ __forceinline__ void run_units(ApplyLds& L, const ApplyArgs& A, const BucketScratch& bk, const uint32_t parity, SegRuns runs, const uint32_t size0, const uint32_t pre_a, const uint32_t pre_b,
                                           const GroupDesc* gdesc) {
     const uint32_t tot_base = parity * bk.n_buckets_max;
-    constexpr bool skew = SKEW;
     uint32_t S = 0, H = 0;   // slabs of split buckets, hot keys' buckets that one block takes whole: the units of a skewed batch beyond its hash buckets
     if constexpr (SKEW) {
         // ONE scan over the bucket totals: the slabs and the positions in front of each thread's buckets (the positions = where a split bucket's
@@ -693,13 +657,12 @@ __device__ __forceinline__ void run_units(ApplyLds& L, const ApplyArgs& A, const
         L.pre_slabs[threadIdx.x] = (uint32_t)ex; L.pre_pos[threadIdx.x] = (uint32_t)(ex >> 32); L.pre_a[threadIdx.x] = pre_a;   // (pre_slabs: slabs | hot keys' whole buckets << 20)
         if (threadIdx.x == 0) { L.pre_slabs[kApplyThreads] = (uint32_t)total; L.pre_pos[kApplyThreads] = (uint32_t)(total >> 32); }
         // (block-uniform.  As vector values the dozen schedule numbers derived from them below are spilled to scratch and reloaded one by one in front
-        // of every block's first unit — 3-5 us in the timeline; forced into SGPRs (readfirstlane) the blocks start their units 5 us
+        // of every block's first unit — 3-5 us in the block timeline (profiles/r04_apply.md); forced into SGPRs (readfirstlane) the blocks start their units 5 us
         // earlier, the kernel has 28 B less scratch, and the located kernel is SLOWER, 59.1 against 54.7 us, same box: the allocation of the hot
         // loops changes with it.  Measured, kept as it was.)
         S = (uint32_t)total & 0xFFFFFu; H = ((uint32_t)total >> 20) & 0xFFFu;
         // (pinned host word: the units this batch had beyond its hash buckets — the next partition sizes its bucket count by it)
         if (blockIdx.x == 0 && threadIdx.x == 0) report_units(bk, A.h_slabs, S + H);
-        MEE_TLS(A, blockIdx.x, 0, wall_clock64());
     }
     // Who takes what.  nbk_hash hash buckets, then one bucket per hot key; G = the grid = one round of the resident block slots.  The blocks
     // [0, nbk_hash) OWN a hash bucket each (its totals and run matrix came with the kernel's first round trip).  The blocks behind them are
@@ -713,7 +676,6 @@ __device__ __forceinline__ void run_units(ApplyLds& L, const ApplyArgs& A, const
     const uint32_t s_agents = min(S, n_agents), O = min(S - s_agents, NH);        // slabs [0, s_agents): agents; [s_agents, s_agents + O): blocks [0, O)
     const uint32_t h_agents = min(H, n_agents - s_agents);                        // hot keys' whole buckets [0, h_agents): agents
     const uint32_t late_slabs = S - s_agents - O, late_hot = H - h_agents, n_late = late_slabs + late_hot + O + (A.nbk_hash > G ? A.nbk_hash - G : 0u);
-    [[maybe_unused]] uint32_t tl_i = 0, tl_units = 0;
     for (uint32_t round = 0;; ++round) {
         // (the thread index is re-read through an empty asm in every turn, as in process_slab: hoisted out of this loop, the per-thread addresses
         // of everything below stayed live across the whole loop and were spilled to scratch — a memory round trip in front of every use)
@@ -739,11 +701,8 @@ __device__ __forceinline__ void run_units(ApplyLds& L, const ApplyArgs& A, const
                 else u = G + (j - late_slabs - late_hot - O);
             }
         }
-        ++tl_units;
-        if (skew && round == 0) MEE_TLS(A, blockIdx.x, 2, wall_clock64());   // (timeline) the block knows its first unit's kind
         if (SKEW && is_slab) {   // ---- a slab of a split bucket (block-uniform) ----
             __syncthreads();   // (the scan's LDS stores; L.u_* of the unit before)
-            if (skew && round == 0) MEE_TLS(A, blockIdx.x, 126, wall_clock64());
             {   // the thread whose buckets hold slab u publishes (bucket, slab of the bucket, size, first pending record)
                 const uint32_t lo = L.pre_slabs[tx] & 0xFFFFFu, hi = L.pre_slabs[tx + 1] & 0xFFFFFu;
                 if (u >= lo && u < hi) {   // exactly one thread
@@ -762,15 +721,9 @@ __device__ __forceinline__ void run_units(ApplyLds& L, const ApplyArgs& A, const
             __syncthreads();
             const uint32_t b = __builtin_amdgcn_readfirstlane(L.u_b), sub = __builtin_amdgcn_readfirstlane(L.u_sub);
             const uint32_t size = __builtin_amdgcn_readfirstlane(L.u_size), beg = __builtin_amdgcn_readfirstlane(L.u_beg);
-#if MEE_APPLY_TIMELINE
-            if (threadIdx.x == 0) L.tl_w = blockIdx.x * 128 + 4 + 16 * min(tl_i, 5u);
-#endif
-            MEE_TLS(A, blockIdx.x, 4 + 16 * tl_i + 0, wall_clock64());
-            MEE_TLS(A, blockIdx.x, 4 + 16 * tl_i + 5, (unsigned long long)b | (unsigned long long)sub << 16 | (unsigned long long)size << 32);
             seg_scan(L, seg_load(A, bk, b, tx), tx);   // the bucket's runs in the partition blocks' slices
             // the slab; the slab that finishes the bucket LAST then runs the merge passes
             process_slab<KIND, DIM4, LOCATED, kEmit, GROUPED>(L, A, bk, sub * kSlab, min(kSlab, size - sub * kSlab), b, beg, parity, gdesc);
-            MEE_TLS(A, blockIdx.x, 4 + 16 * tl_i + 1, wall_clock64());
             // ---- publish this slab's pending records, take a ticket; the slab that draws the last ticket merges the bucket.  The records were
             // written through (rec_store), every wave drains its stores, THEN the ticket; the merger reads them with agent-scope loads
             // (rec_load).  No block ever waits for another.
@@ -781,10 +734,8 @@ __device__ __forceinline__ void run_units(ApplyLds& L, const ApplyArgs& A, const
                 L.is_last = tk == (size + kSlab - 1) / kSlab - 1;
             }
             __syncthreads();
-            MEE_TLS(A, blockIdx.x, 4 + 16 * tl_i + 2, wall_clock64());
             if (L.is_last) {   // block-uniform
                 const uint32_t R = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&bk.pend_cnt[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));   // every slab added its runs before its ticket
-                MEE_TLS(A, blockIdx.x, 4 + 16 * tl_i + 6, (unsigned long long)R);
                 // Merge in passes: records of one key must meet in one pass and a pass holds kSlab records.  Usually the bucket's records fit ONE
                 // pass (a hot key's own bucket: one record per slab).  Otherwise the records are taken by the low bits of mix64b(key): `bits0`
                 // bits give passes of ~256 records; a pass that still finds more than kSlab splits on one more bit, and a pass whose records all
@@ -837,14 +788,10 @@ __device__ __forceinline__ void run_units(ApplyLds& L, const ApplyArgs& A, const
                             }
                         } else m = nc;
                     }
-                    if (m == 0) break;
-                    MEE_TLS(A, blockIdx.x, 4 + 16 * tl_i + 3, wall_clock64());   // the pass's records are collected
+                    if (m == 0) break;   // else: the pass's records are collected
                     process_slab<KIND, DIM4, LOCATED, kMerge, GROUPED>(L, A, bk, 0, m, b, beg, parity, gdesc);
-                    MEE_TLS(A, blockIdx.x, 4 + 16 * tl_i + 4, wall_clock64());
                 }
             }
-            MEE_TLS(A, blockIdx.x, 4 + 16 * tl_i + 7, wall_clock64());
-            ++tl_i;
         } else {   // ---- a bucket ----
             uint32_t b = u;
             if (SKEW && is_hot) {   // the u-th of the hot keys' buckets that one block takes whole: the thread that owns it in the scan publishes its number
@@ -877,27 +824,13 @@ __device__ __forceinline__ void run_units(ApplyLds& L, const ApplyArgs& A, const
                     size = __builtin_amdgcn_readfirstlane(bk.tot[tot_base + b]);
                 }
             }
-            if (skew) MEE_TLS(A, blockIdx.x, 100 + 4 * min(tl_units - tl_i - 1, 6u), wall_clock64());
             if (size != 0 && size <= kBucketCap) {   // (an empty bucket | a split bucket: its slabs' business)
-                MEE_TL(A, 1);   // first round trip done (size known)
-#if MEE_APPLY_TIMELINE
-                if (threadIdx.x == 0 && !skew) { A.dbg[(uint64_t)blockIdx.x * 8 + 6] = size | (unsigned long long)b << 32; unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc)); unsigned hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw)); A.dbg[(uint64_t)blockIdx.x * 8 + 7] = (unsigned long long)(xcc & 0xf) << 32 | hw; }
-#endif
                 if (SKEW) seg_scan(L, runs, tx);   // (LEAN: the caller has done it)
                 process_slab<KIND, DIM4, LOCATED, kWhole, GROUPED>(L, A, bk, 0, size, b, 0, parity, gdesc);
-                MEE_TL(A, 5);
-            }
-            if (skew) {
-                MEE_TLS(A, blockIdx.x, 101 + 4 * min(tl_units - tl_i - 1, 6u), wall_clock64());
-                MEE_TLS(A, blockIdx.x, 102 + 4 * min(tl_units - tl_i - 1, 6u), (unsigned long long)b | (unsigned long long)size << 32);
             }
         }
         if (!SKEW || n_late == 0) break;   // (block-uniform: every unit has its block — every batch without a split bucket)
         __syncthreads();   // (the unit's last readers of the LDS tables | the next unit's first writers)
-    }
-    if (skew) {
-        MEE_TLS(A, blockIdx.x, 1, (unsigned long long)(tl_i) | (unsigned long long)(tl_units) << 32);
-        MEE_TLS(A, blockIdx.x, 3, wall_clock64());
     }
 }
 
@@ -1196,7 +1129,6 @@ __global__ __launch_bounds__(kApplyThreads, kApplyWavesPerSimd) void bkt_apply_k
     // filled (bk.seq[1], meepo_apply_part.h), whether that partition met a split bucket, this block's bucket total in BOTH copies, and — lanes of
     // wave 0 — the lengths and places of the bucket's runs in the partition blocks' slices.  (As a chain seq -> total -> run lengths these were
     // three dependent loads, 2-3 us of every block's life before its first useful request.)
-    MEE_TL(A, 0);
     // (FULL: the grid is one round of the resident block slots; the blocks beyond the hash buckets have no bucket of their own)
     if (FULL && A.part_blocks == 0) return;   // (grid-uniform) no batch: the launch that makes the queue hold this kernel's scratch before a skewed batch needs it (bucket_apply_launch)
     const bool own = blockIdx.x < A.nbk_hash;
@@ -1430,13 +1362,6 @@ void bucket_scratch_free(mee_table* t) {
     }
 }
 
-#if MEE_APPLY_TIMELINE
-static unsigned long long* g_dbg = nullptr;
-extern "C" int mee_debug_timeline(unsigned long long* host_out, uint64_t n_words) {
-    if (!g_dbg) return 1;
-    return hipMemcpy(host_out, g_dbg, n_words * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
-}
-#endif
 // the partition of an apply as launches of its own: `plan` as bucket_plan(t->bk, n, st, kPartThreads) made it
 int bucket_partition_launch(mee_table* t, const int64_t* d_keys, uint32_t n, const PartPlan& plan, hipStream_t st) {
     bkt_sort_kernel<<<plan.blocks, kPartThreads, sizeof(PartHot) + plan.nbk * 4, st>>>(d_keys, n, plan.nbk_hash, plan.nbk, plan.per_block, t->bk, &t->ctr->status, t->op,
@@ -1466,11 +1391,6 @@ int bucket_apply_launch(mee_table* t, const PartPlan& plan, const float* d_grads
     A.grads = (const float4*)d_grads; A.gidx = d_gidx; A.slots = d_slots;
     A.capacity = t->capacity; A.handle_tag = (int64_t)(t->handle_epoch & kHandleEpochMask) << kHandleSlotBits; A.status = &t->ctr->status;
     A.part = t->bs.gacc; A.max_part = t->bs.max_part; A.op = t->op; A.a = a; A.h_slabs = t->bk.h_slabs_dev;
-#if MEE_APPLY_TIMELINE
-    if (!g_dbg) (void)hipMalloc((void**)&g_dbg, (16384 * 8 + 1024 * 128) * 8);
-    (void)hipMemsetAsync(g_dbg, 0, (16384 * 8 + 1024 * 128) * 8, st);
-    A.dbg = g_dbg;
-#endif
     A.desc = d_desc; A.n_tables = n_tables;   // a table group's apply (d_slots = the batch's located rows = its keys; t = the group's scratch table)
     A.hot_count = hot_count_for(n);
     A.nbk = plan.nbk; A.nbk_hash = plan.nbk_hash; A.part_blocks = plan.blocks; A.per_block = plan.per_block;

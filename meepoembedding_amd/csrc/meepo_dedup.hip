@@ -31,17 +31,6 @@ constexpr int kDedupWaves = kDedupThreads / 64;
 constexpr uint32_t kDedupSlots = 1024;        // LDS hash table of one pass
 constexpr uint32_t kDedupFill = 896;          // distinct keys a pass may hold (load 0.875); beyond: the pass is split by one more hash bit
 
-// MEE_SUM_TIMELINE (diagnostic builds only: tools/sum_timeline.py): thread 0 of every block stamps the 100 MHz wall clock at its phase boundaries
-#ifndef MEE_SUM_TIMELINE
-#define MEE_SUM_TIMELINE 0
-#endif
-#if MEE_SUM_TIMELINE
-__device__ unsigned long long* g_sum_dbg = nullptr;
-#define MEE_STL(i) do { if (threadIdx.x == 0 && g_sum_dbg && blockIdx.x < 8192) g_sum_dbg[(uint64_t)blockIdx.x * 16 + (i)] = wall_clock64(); } while (0)
-#else
-#define MEE_STL(i) do { } while (0)
-#endif
-
 struct DedupLds {
     unsigned long long key[kDedupSlots];      // key ^ kBias, 0 = empty
     uint32_t val[kDedupSlots];                // dedup: the key's index in this pass's slice of the unique list | assign: 1 + the key's last position, later its found flag
@@ -120,7 +109,6 @@ __device__ __forceinline__ bool dd_build(DedupLds& L, const BucketScratch& bk, u
     if (t == 0) { L.n_distinct = 0u; L.overflow = 0u; }
     const bool may_overflow = size > kDedupFill;   // (block-uniform) a pass over at most kDedupFill entries cannot: nobody counts its keys
     lds_barrier();
-    MEE_STL(7);   // table cleared
     const uint64_t mask = bits >= 64 ? ~0ull : (1ull << bits) - 1ull;
     constexpr int kIn = 4;   // entries a thread has in flight per step (one dependent round trip per step: a bucket of 4 000 entries takes 4 steps, not 16)
     for (uint32_t e0 = 0; e0 < size; e0 += kIn * kDedupThreads) {   // block-uniform trip count: the wave ballots below need whole waves
@@ -141,10 +129,6 @@ __device__ __forceinline__ bool dd_build(DedupLds& L, const BucketScratch& bk, u
 #pragma unroll
             for (int q = 0; q < kIn; ++q) { H.s[q] = kNoSlot; H.p[q] = pq[q]; }
         }
-#if MEE_SUM_TIMELINE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        MEE_STL(8);   // thread 0's entries are in
-#endif
 #pragma unroll
         for (int q = 0; q < kIn; ++q) {
             const int64_t key = kq[q];
@@ -668,12 +652,7 @@ __global__ __launch_bounds__(kDedupThreads, kSumBlocksPerCU) void bkt_dedup_sum_
     __shared__ SumLds L;
     uint32_t parity, before;
     HotPlan P;
-    MEE_STL(0);
     const uint32_t size = dd_bucket<true, kSumWindow>(L.d, bk, A.d, parity, P, before);
-    MEE_STL(1);   // the bucket's totals, runs and prefix are in
-#if MEE_SUM_TIMELINE
-    if (threadIdx.x == 0 && g_sum_dbg && blockIdx.x < 8192) g_sum_dbg[(uint64_t)blockIdx.x * 16 + 15] = (unsigned long long)size | (unsigned long long)(dd_unit(A.d) >= A.d.nbk) << 32;
-#endif
     const uint32_t dim4 = DIM4 ? DIM4 : A.dim4;
     const uint32_t t = threadIdx.x, lane = t & 63, tile = lane >> 4, tl = lane & 15, wv = t >> 6, T = wv * 4 + tile;
     const uint32_t unit = dd_unit(A.d);
@@ -722,14 +701,13 @@ __global__ __launch_bounds__(kDedupThreads, kSumBlocksPerCU) void bkt_dedup_sum_
         }, [&](uint32_t col, const D4& v) { store_sum4(A.gsum, P.rank, dim4, col, v); });
       };
         window();
-        MEE_STL(10);   // the block's window is done
         if (!A.handoff) return;   // (grid-uniform)
         for (;;) {   // the hash buckets' long runs, kHandChunk buckets per turn (block-uniform control flow)
             __syncthreads();   // (the window's / the previous item's last readers of the LDS list)
             if (t == 0) L.d.base = __hip_atomic_fetch_add(A.hand_head, kHandChunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __syncthreads();
             const uint32_t j0 = L.d.base;
-            if (j0 >= A.d.nbk_hash) { MEE_STL(11); return; }   // no bucket left
+            if (j0 >= A.d.nbk_hash) return;   // no bucket left
             if (t < kHandChunk) {   // a bucket's block publishes 1 + its items when its passes are done (every hash bucket's block is dispatched before the first block back here)
                 uint32_t f = 1u;
                 if (j0 + t < A.d.nbk_hash) {
@@ -791,7 +769,6 @@ __global__ __launch_bounds__(kDedupThreads, kSumBlocksPerCU) void bkt_dedup_sum_
     uint32_t slice = P.H + before, src_at = before;
     dd_passes<false>(L.d, bk, size, parity, A.d.hot_count, A.d.status, [&](uint32_t bits, uint64_t val, const DdHeld& held) {
         const uint64_t mask = bits >= 64 ? ~0ull : (1ull << bits) - 1ull;
-        MEE_STL(2);   // entries fetched, keys in the LDS table
         // -- 1. run numbers (keys that occur ONCE first, then the other short runs, then medium, then long) and the runs' places in the sorted source list: ONE block scan
         // over the table's slots
         constexpr uint32_t per = kDedupSlots / kDedupThreads;
@@ -828,7 +805,6 @@ __global__ __launch_bounds__(kDedupThreads, kSumBlocksPerCU) void bkt_dedup_sum_
             }
         }
         lds_barrier();
-        MEE_STL(3);   // scan done, keys and counts written
         // -- 2. every entry of the pass looks its key up: the key's number into d_inverse; a bucket beyond the LDS list files its positions in the global list at once
         uint32_t my_sl[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
         if (in_lds) {
@@ -855,7 +831,6 @@ __global__ __launch_bounds__(kDedupThreads, kSumBlocksPerCU) void bkt_dedup_sum_
                 }
             }
         }
-        MEE_STL(9);   // thread 0's look-ups done, inverse stores issued
         if (!A.grads) return;   // (grid-uniform) keys, counts and inverse only
         if (in_lds) lds_barrier(); else __syncthreads();   // nobody looks a key up any more: the key table's space becomes src / items / prow (beyond the LDS list: the stores of the global list are drained)
         // -- 2b. the LDS list (positions sorted by run, through each run's cursor) and the run list (run number -> slot)
@@ -866,7 +841,6 @@ __global__ __launch_bounds__(kDedupThreads, kSumBlocksPerCU) void bkt_dedup_sum_
 #pragma unroll
         for (uint32_t q = 0; q < per; ++q) { const uint32_t sl = t * per + q; if (L.d.cnt[sl]) L.items()[L.d.val[sl]] = (uint16_t)sl; }
         lds_barrier();
-        MEE_STL(4);   // look-ups, inverse, sorted source list
         // from here on run sl's sources are [L.off[sl] - cnt, L.off[sl]) of the list
         auto source = [&](uint32_t at) -> uint32_t { return in_lds ? L.src()[at] : __hip_atomic_load(&srcg[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
         // -- 3. long runs: the whole block, one after the other (the block-level sums use prow: all threads pass the barriers inside)
@@ -896,7 +870,6 @@ __global__ __launch_bounds__(kDedupThreads, kSumBlocksPerCU) void bkt_dedup_sum_
                 if (tile == 0 && col < dim4) store_sum4(A.gsum, base + idx, dim4, col, v);
             }
         }
-        MEE_STL(5);   // long and medium runs summed
         // -- 5. short runs: a tile each.  Keys that occur ONCE — the bulk of every batch, numbered first — are streamed rows in, rows out, bit for bit (no arithmetic), four
         // in flight per tile and software-pipelined: the NEXT four rows are requested before the current four are stored, so that a step waits for its loads only (the memory
         // counter retires in order: loads issued behind stores would wait for the stores' acknowledgement as well).  Runs of 2-8 sources follow, one run per step (one or two
@@ -941,10 +914,6 @@ __global__ __launch_bounds__(kDedupThreads, kSumBlocksPerCU) void bkt_dedup_sum_
             for (uint32_t col = tl; col < dim4; col += 16)
                 store_sum4(A.gsum, base + idx, dim4, col, run_sum4(0u, 4u, c, col, [&](uint32_t j, uint32_t cc) { return grad_row4(A.grads, source(f0 + j), dim4, cc); }));
         }
-#if MEE_SUM_TIMELINE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-        MEE_STL(6);   // thread 0's short runs done
     });
     publish();
 }
@@ -1001,19 +970,6 @@ int bucket_dedup_sum(mee_table* t, const int64_t* d_keys, const float* d_grads, 
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
-
-#if MEE_SUM_TIMELINE
-extern "C" int mee_debug_sum_timeline(unsigned long long* host_out, uint64_t n_words) {   // first call arms the buffer, later calls read it
-    static unsigned long long* buf = nullptr;
-    if (!buf) {
-        if (hipMalloc((void**)&buf, 8192 * 16 * 8) != hipSuccess) return 1;
-        (void)hipMemset(buf, 0, 8192 * 16 * 8);
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_sum_dbg), &buf, sizeof buf);
-        return 0;
-    }
-    return hipMemcpy(host_out, buf, n_words * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
-}
-#endif
 
 int bucket_assign(mee_table* t, float* plane, const int64_t* d_keys, const float* d_values, uint32_t n, uint8_t* d_found, hipStream_t st) {
     AssignArgs A{};

@@ -142,31 +142,13 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
     }
 }
 
-#ifndef MEE_FIND_TIMELINE
-#define MEE_FIND_TIMELINE 0
-#endif
-#if MEE_FIND_TIMELINE
-__device__ unsigned long long* g_find_dbg = nullptr;
-#endif
 template <int DIM4, int R, int NT>
 __global__ __launch_bounds__(256) void find_kernel(const int64_t* __restrict__ tkeys, const f32x4* __restrict__ values,
                                                    uint64_t nb, const int64_t* __restrict__ keys, uint64_t n,
                                                    f32x4* __restrict__ out, uint8_t* __restrict__ found, float defv,
                                                    uint32_t dim4_rt, uint32_t* hits, int64_t* __restrict__ slots_out = nullptr, int64_t handle_tag = 0) {
-#if MEE_FIND_TIMELINE   // diagnostic builds only (tools/find_timeline.py): wave 0 of every block stamps its start, its end and the XCD it ran on
-    unsigned long long t0_ = 0;
-    if (threadIdx.x == 0) t0_ = wall_clock64();
-#endif
     find_span<DIM4, R, NT>(tkeys, values, nb, keys, n, out, found, defv, dim4_rt, hits, slots_out,
                            (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (uint64_t)gridDim.x * (blockDim.x >> 6), handle_tag);
-#if MEE_FIND_TIMELINE
-    if (threadIdx.x == 0 && g_find_dbg && blockIdx.x < 16384) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_find_dbg[blockIdx.x * 4 + 0] = t0_; g_find_dbg[blockIdx.x * 4 + 1] = wall_clock64(); g_find_dbg[blockIdx.x * 4 + 2] = xcc & 0xf;
-    }
-#endif
 }
 
 // The training forward (mee_find_located_prepare): the located find whose launch gives its first `part_blocks` blocks the partition role of
@@ -187,30 +169,14 @@ __global__ __launch_bounds__(kFindPrepareThreads, 8) void find_prepare_kernel(co
                                                            BucketScratch bk, uint32_t* status, OpCounters* op, uint32_t xcd_split) {
     extern __shared__ unsigned long long part_lds[];   // PartHot, then one counter per bucket (meepo_apply_part.h)
     __shared__ unsigned long long part_wsum[kFindPrepareThreads / 64];
-#if MEE_FIND_TIMELINE   // diagnostic builds only (tools/prepare_timeline.py): thread 0 of every block stamps its start, its end and its role
-    unsigned long long t0_ = 0;
-    if (threadIdx.x == 0) t0_ = wall_clock64();
-#endif
     if (blockIdx.x < part_blocks) {   // block-uniform
         PartHot* hot = reinterpret_cast<PartHot*>(part_lds);
         sort_role<kFindPrepareThreads>(keys, (uint32_t)n, nbk_hash, nbk, per_block, blockIdx.x, part_blocks, bk, status, op, reinterpret_cast<uint32_t*>(hot + 1), part_wsum, hot, true, xcd_split);
-#if MEE_FIND_TIMELINE
-        if (threadIdx.x == 0 && g_find_dbg && blockIdx.x < 16384) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            g_find_dbg[blockIdx.x * 4 + 0] = t0_; g_find_dbg[blockIdx.x * 4 + 1] = wall_clock64(); g_find_dbg[blockIdx.x * 4 + 2] = 100;
-        }
-#endif
         return;
     }
     find_span<DIM4, R, NT>(tkeys, values, nb, keys, n, out, found, defv, dim4_rt, nullptr, slots_out,
                            (uint64_t)(blockIdx.x - part_blocks) * (blockDim.x >> 6) + (threadIdx.x >> 6), (uint64_t)(gridDim.x - part_blocks) * (blockDim.x >> 6),
                            handle_tag);
-#if MEE_FIND_TIMELINE
-    if (threadIdx.x == 0 && g_find_dbg && blockIdx.x < 16384) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        g_find_dbg[blockIdx.x * 4 + 0] = t0_; g_find_dbg[blockIdx.x * 4 + 1] = wall_clock64(); g_find_dbg[blockIdx.x * 4 + 2] = 1;
-    }
-#endif
 }
 
 // Several lookup requests of one table in ONE launch (mee_find_many): the per-launch latency floor (~5 us: dispatch + the dependent
@@ -1017,18 +983,5 @@ int mee_find_located_prepare_as(mee_table* t, const int64_t* d_keys, size_t n, v
     MEE_RANGE("mee_find_located_prepare_as");
     return find_located_prepare(t, d_keys, n, d_out, out_dtype, d_found, d_slots_out, stream, "mee_find_located_prepare_as");
 }
-
-#if MEE_FIND_TIMELINE
-int mee_debug_find_timeline(unsigned long long* host_out, uint64_t n_words) {   // first call arms the buffer, later calls read it
-    static unsigned long long* buf = nullptr;
-    if (!buf) {
-        if (hipMalloc((void**)&buf, 16384 * 4 * 8) != hipSuccess) return 1;
-        (void)hipMemset(buf, 0, 16384 * 4 * 8);
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_find_dbg), &buf, sizeof buf);
-        return 0;
-    }
-    return hipMemcpy(host_out, buf, n_words * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
-}
-#endif
 
 }  // extern "C"
