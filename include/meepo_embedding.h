@@ -314,6 +314,23 @@ int mee_group_apply_adagrad_pooled(mee_group* g, const int64_t* d_keys, const ui
 int mee_group_apply_adam_pooled(mee_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table,
                                 const float* d_bag_grads, const uint32_t* d_grad_index, const int64_t* d_located, size_t n, float lr,
                                 float beta1, float beta2, float eps, uint64_t step, void* stream);
+/* The same collection where the members' bag counts DIFFER (the owner's side of a sharded group's bags: the runs that arrive per member
+ * change from member to member and from step to step).  mee_group_find_pooled_jagged is mee_group_find_pooled except for the bag -> member
+ * map: bag b belongs to the member j with d_member_bags[j] <= b < d_member_bags[j + 1] (n_tables + 1 non-decreasing uint64 in DEVICE
+ * memory; a member may have no bags; [0, B, 2B, …] gives mee_group_find_pooled(bags_per_table = B) bit for bit, handles included).  A bag
+ * below d_member_bags[0] or at or beyond d_member_bags[n_tables] is an empty bag: a row of zeros, nothing probed.  The map is caller data
+ * and is never trusted: whatever it holds, the member used stays inside the group.  d_out [n_bags, dim] fp32 (no typed and no weighted
+ * form: the partial rows of a sharded bag travel as fp32).  Never synchronises, capturable, safe on several streams at once. */
+int mee_group_find_pooled_jagged(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
+                                 const uint64_t* d_member_bags /* [n_tables + 1], device */, float* d_out, uint8_t* d_found,
+                                 int64_t* d_located_out, int mode, void* stream);
+/* mee_apply_*_indexed on every member with its segment of the jagged batch (d_offsets = n_tables + 1 member offsets, as mee_group_apply_*),
+ * in the grouped apply's fixed number of launches: position i takes row d_grad_index[i] of d_grads [n_grad_rows, dim]; indices >=
+ * n_grad_rows are clamped.  Refusals as mee_group_apply_* and mee_apply_*_indexed. */
+int mee_group_apply_adagrad_indexed(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows,
+                                    const uint32_t* d_grad_index, size_t n, float lr, float eps, void* stream);
+int mee_group_apply_adam_indexed(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows,
+                                 const uint32_t* d_grad_index, size_t n, float lr, float beta1, float beta2, float eps, uint64_t step, void* stream);
 /* The weighted forms over the collection: mee_find_pooled_weighted / mee_pooled_weighted_backward on every member, bag b belonging to
  * member b / bags_per_table, in one launch each.  d_located_out / d_located are in the group's format (as mee_group_find_pooled's); the
  * step after the backward is mee_group_apply_*(d_keys, member offsets, d_grads_out) — the grads are per position, not per bag. */

@@ -178,6 +178,17 @@ public:
     // the weighted embedding-bag collection: bag b belongs to member b / bags_per_table (mee_group_find_pooled_weighted / mee_group_pooled_weighted_backward)
     void find_pooled_weighted(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights, float* d_out, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, void* stream = nullptr) { check(mee_group_find_pooled_weighted(g_, d_keys, n, d_bag_offsets, bags_per_table, d_weights, d_out, d_found, d_located_out, stream)); }
     void pooled_weighted_backward(const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights, const float* d_bag_grads, float* d_grads_out, float* d_weight_grads_out = nullptr, void* stream = nullptr) { check(mee_group_pooled_weighted_backward(g_, d_keys, d_located, n, d_bag_offsets, bags_per_table, d_weights, d_bag_grads, d_grads_out, d_weight_grads_out, stream)); }
+    // the collection with a different number of bags per member: bag b belongs to member j with d_member_bags[j] <= b < d_member_bags[j + 1]
+    // (mee_group_find_pooled_jagged), and its backward, mee_apply_*_indexed per member (mee_group_apply_*_indexed)
+    void find_pooled_jagged(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const uint64_t* d_member_bags, float* d_out, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, int mode = MEE_POOL_SUM, void* stream = nullptr) {
+        check(mee_group_find_pooled_jagged(g_, d_keys, n, d_bag_offsets, n_bags, d_member_bags, d_out, d_found, d_located_out, mode, stream));
+    }
+    void apply_adagrad_indexed(const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index, size_t n, float lr, float eps = 1e-10f, void* stream = nullptr) {
+        check(mee_group_apply_adagrad_indexed(g_, d_keys, d_offsets, d_grads, n_grad_rows, d_grad_index, n, lr, eps, stream));
+    }
+    void apply_adam_indexed(const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index, size_t n, float lr, uint64_t step, float beta1 = 0.9f, float beta2 = 0.999f, float eps = 1e-8f, void* stream = nullptr) {
+        check(mee_group_apply_adam_indexed(g_, d_keys, d_offsets, d_grads, n_grad_rows, d_grad_index, n, lr, beta1, beta2, eps, step, stream));
+    }
 private:
     mee_group* g_ = nullptr;
 };

@@ -111,6 +111,9 @@ PROTOTYPES = {
     "mee_group_find_pooled": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, C.c_int, _vp]),
     "mee_group_apply_adagrad_pooled": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _f32, _f32, _vp]),
     "mee_group_apply_adam_pooled": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32, _u64, _vp]),
+    "mee_group_find_pooled_jagged": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "mee_group_apply_adagrad_indexed": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _f32, _f32, _vp]),
+    "mee_group_apply_adam_indexed": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _f32, _f32, _f32, _f32, _u64, _vp]),
     "mee_group_find_or_insert": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "mee_group_apply_adagrad": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _f32, _f32, _vp]),
     "mee_group_apply_adam": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32, _u64, _vp]),

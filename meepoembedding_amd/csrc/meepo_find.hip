@@ -279,6 +279,19 @@ __device__ __forceinline__ void pooled_fetch(const int64_t* __restrict__ tkeys, 
     }
 }
 
+// JAGGED bag -> member map (mee_group_find_pooled_jagged): the member j with member_bags[j] <= bag < member_bags[j + 1], by an upper-bound
+// search over member_bags[1 .. n_members] (at most ten dependent reads of an L2-resident array for 1024 members).  The array is the
+// caller's: whatever it holds, the member stays inside [0, n_members); false = the bag lies outside [member_bags[0], member_bags[n_members]).
+__device__ __forceinline__ bool jagged_member(const uint64_t* __restrict__ member_bags, uint32_t n_members, uint64_t bag, uint64_t& member) {
+    uint32_t lo = 0, hi = n_members;   // lo ends as the number of entries member_bags[1 .. n_members] that are <= bag
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (member_bags[mid + 1] <= bag) lo = mid + 1; else hi = mid;
+    }
+    member = lo < n_members ? lo : (n_members ? n_members - 1 : 0);   // (a group has at least one table: mee_group_create refuses none; the launch checks again)
+    return lo < n_members && bag >= member_bags[0];
+}
+
 // BPW = bags per wave: 4 = the hybrid above (batches of mostly short bags), 1 = every bag gets a whole wave (batches whose
 // AVERAGE bag is long: a wave that had to walk four long bags one after the other would be latency-bound).
 // GROUPED (mee_group_find_pooled): bag b belongs to member table b / bags_per_table; the planes come from its descriptor.
@@ -286,7 +299,10 @@ __device__ __forceinline__ void pooled_fetch(const int64_t* __restrict__ tkeys, 
 // the sum (no fma; the first position's product is the initial sum); SUM only.  A single table's located rows then carry its handle tag.
 // BF16: `out` holds bf16 rows — the FINISHED bag row (after the mean's division) is rounded once at its store (SPEC.md §3 "Output type");
 // the accumulation is the same fp32 code, and the fp32 instances (BF16 = false) are the code they were before the parameter existed.
-template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false>
+// JAGGED (mee_group_find_pooled_jagged; GROUPED, fp32, unweighted): the members' bag counts differ — bag b belongs to the member that
+// jagged_member finds in member_bags, and a bag outside the map is an empty bag (a row of zeros, nothing probed).  The instances
+// with JAGGED = false are the code they were before the parameter existed.
+template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false, bool JAGGED = false>
 __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restrict__ tkeys_, const float4* __restrict__ values_,
                                                           uint64_t nb_, const int64_t* __restrict__ keys,
                                                           const uint64_t* __restrict__ offsets, uint64_t n_bags,
@@ -294,7 +310,9 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                                                           uint32_t dim4_rt, int mean, const GroupDesc* __restrict__ desc = nullptr,
                                                           uint64_t bags_per_table = 1, int64_t* __restrict__ located = nullptr,
                                                           uint64_t n_keys = ~0ull, const float* __restrict__ weights = nullptr,
-                                                          int64_t handle_tag = 0) {
+                                                          int64_t handle_tag = 0, const uint64_t* __restrict__ member_bags = nullptr,
+                                                          uint32_t n_members = 0) {
+    static_assert(!JAGGED || (GROUPED && !WEIGHTED && !BF16), "the jagged map is the group's plain fp32 lookup");
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
@@ -313,7 +331,9 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
         float4 def4 = make_float4(defv, defv, defv, defv);
         uint64_t member = 0;
         if constexpr (GROUPED) {
-            member = (has ? bag : 0) / bags_per_table;
+            if constexpr (JAGGED) {
+                if (!jagged_member(member_bags, n_members, has ? bag : 0, member)) begin = end = 0;   // a bag outside the map: empty
+            } else member = (has ? bag : 0) / bags_per_table;
             const GroupDesc d = desc[member];
             tkeys = d.tkeys; values = d.values; nb = d.nb; def4 = make_float4(d.defv, d.defv, d.defv, d.defv);
         }
@@ -381,7 +401,8 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
             if (!((long_mask >> (q * 16)) & 1)) continue;   // wave-uniform
             const uint64_t bq = __shfl(begin, q * 16), eq = __shfl(end, q * 16);
             if constexpr (GROUPED && BPW == 4) {   // all four tiles work for bag q's table now
-                member = (b0 + q) / bags_per_table;
+                if constexpr (JAGGED) (void)jagged_member(member_bags, n_members, b0 + q, member);   // (a long bag is not empty: it lies inside the map)
+                else member = (b0 + q) / bags_per_table;
                 const GroupDesc d = desc[member];
                 tkeys = d.tkeys; values = d.values; nb = d.nb; def4 = make_float4(d.defv, d.defv, d.defv, d.defv);
             }
@@ -817,7 +838,7 @@ static int find_pooled_common(const mee_table* t, const int64_t* d_keys, size_t 
     with_pooled_shape(t->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(d_weights != nullptr, [&](auto weighted) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
         auto launch = [&](auto kernel) {
             kernel<<<grid, 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, t->default_value, t->dim4,
-                                         mode == MEE_POOL_MEAN, nullptr, 1, weighted ? d_located_out : nullptr, n, d_weights, weighted ? tag : 0);
+                                         mode == MEE_POOL_MEAN, nullptr, 1, weighted ? d_located_out : nullptr, n, d_weights, weighted ? tag : 0, nullptr, 0);
         };
         launch(find_pooled_kernel<d4, u, bpw, false, weighted, bf16>);
     }); }); });
@@ -888,7 +909,7 @@ static int group_find_pooled_common(mee_group* g, const int64_t* d_keys, size_t 
     with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(d_weights != nullptr, [&](auto weighted) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
         auto launch = [&](auto kernel) {
             kernel<<<grid, 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, mode == MEE_POOL_MEAN, g->d_desc, bags_per_table,
-                                         d_located_out, n, d_weights, 0);
+                                         d_located_out, n, d_weights, 0, nullptr, 0);
         };
         launch(find_pooled_kernel<d4, u, bpw, true, weighted, bf16>);
     }); }); });
@@ -902,6 +923,25 @@ int mee_group_find_pooled(mee_group* g, const int64_t* d_keys, size_t n, const u
     if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled: null argument");
     if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
     return group_find_pooled_common(g, d_keys, n, d_bag_offsets, bags_per_table, nullptr, d_out, MEE_DTYPE_F32, d_found, d_located_out, mode, stream);
+}
+
+// the same lookup with the members' bag counts read from d_member_bags (the owner's side of a sharded group: the runs that arrive per member)
+int mee_group_find_pooled_jagged(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
+                                 const uint64_t* d_member_bags, float* d_out, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
+    MEE_RANGE("mee_group_find_pooled_jagged");
+    if (!g || (n_bags && (!d_bag_offsets || !d_member_bags || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_jagged: null argument");
+    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_jagged: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
+    if (n_bags == 0) return MEE_OK;
+    if (g->n_tables == 0) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_jagged: the group has no tables");   // the kernel keeps the member inside [0, n_tables)
+    if (int rc = group_refresh(g, stream)) return rc;
+    DeviceGuard guard(g->device);
+    hipStream_t st = as_stream(stream);
+    with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
+        find_pooled_kernel<d4, u, bpw, true, false, false, true><<<grid, 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4,
+                                                                                       mode == MEE_POOL_MEAN, g->d_desc, 1, d_located_out, n, nullptr, 0, d_member_bags, g->n_tables);
+    });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
 }
 
 int mee_group_find_pooled_weighted(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,

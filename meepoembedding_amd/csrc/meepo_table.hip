@@ -894,6 +894,27 @@ int mee_group_apply_adam_pooled(mee_group* g, const int64_t* d_keys, const uint6
                               d_located);
 }
 
+// mee_apply_*_indexed on every member with its segment [d_offsets[j], d_offsets[j + 1]) of keys and index entries: position i takes row
+// d_grad_index[i] of d_grads (the owner's backward of a sharded group's bags: one gradient row per run that arrived)
+static int check_grad_rows(size_t n, const uint32_t* d_grad_index, size_t n_grad_rows, const char* name);
+int mee_group_apply_adagrad_indexed(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows,
+                                    const uint32_t* d_grad_index, size_t n, float lr, float eps, void* stream) {
+    MEE_RANGE("mee_group_apply_adagrad_indexed");
+    if (int rc = check_grad_rows(n, d_grad_index, n_grad_rows, "mee_group_apply_adagrad_indexed")) return rc;
+    OptArgs a{};
+    a.kind = MEE_OPT_ADAGRAD; a.lr = lr; a.eps = eps; a.grad_rows = (uint32_t)n_grad_rows;
+    return group_apply_common(g, d_keys, d_offsets, d_grads, n, a, stream, "mee_group_apply_adagrad_indexed", 1, d_grad_index);
+}
+int mee_group_apply_adam_indexed(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows,
+                                 const uint32_t* d_grad_index, size_t n, float lr, float beta1, float beta2, float eps, uint64_t step, void* stream) {
+    MEE_RANGE("mee_group_apply_adam_indexed");
+    if (step == 0) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_adam_indexed: step must be >= 1");
+    if (int rc = check_grad_rows(n, d_grad_index, n_grad_rows, "mee_group_apply_adam_indexed")) return rc;
+    OptArgs a = adam_args(lr, beta1, beta2, eps, step);
+    a.grad_rows = (uint32_t)n_grad_rows;
+    return group_apply_common(g, d_keys, d_offsets, d_grads, n, a, stream, "mee_group_apply_adam_indexed", 1, d_grad_index);
+}
+
 int mee_apply_prepare(mee_table* t, const int64_t* d_keys, size_t n, void* stream) {
     MEE_RANGE("mee_apply_prepare");
     if (!t || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_apply_prepare: null argument");

@@ -165,13 +165,19 @@ def _backward_located(ctx, grad_out, _grad_located):
 lookup_located.register_autograd(_backward_located, setup_context=_setup_located)
 
 
+def _hands_located(table) -> bool:
+    """does lookup_pooled over this table return the located rows of its keys (a TableGroup on one device) or an empty tensor (one table; the
+    sharded tables and groups, whose pooled lookup creates unseen ids itself and whose handles do not cross the exchange)?"""
+    return hasattr(table, "apply_pooled") and not getattr(table, "pools_with_insert", False)
+
+
 # ---- pooled: sum / mean per bag fused into the lookup, the bag's grad row indexed in the update ---------------------------
 @torch.library.custom_op("meepo::lookup_pooled", mutates_args=())
 def lookup_pooled(keys: torch.Tensor, bag_offsets: torch.Tensor, anchor: torch.Tensor, table_id: int, mean: bool) -> tuple[torch.Tensor, torch.Tensor]:
     """-> (pooled rows [n_bags, dim], located rows [n] — per-position handles the backward of this step reuses; empty for a
     single table, whose apply probes for itself)"""
     layer = _layer(table_id)
-    if getattr(layer.table, "pools_with_insert", False):   # a ShardedLookupTable: the owners create unseen ids inside the pooled lookup's own exchange
+    if getattr(layer.table, "pools_with_insert", False):   # a ShardedLookupTable / ShardedTableGroup: the owners create unseen ids inside the pooled lookup's own exchange
         out, _ = layer.table.find_pooled(keys, bag_offsets, "mean" if mean else "sum", insert_missing=layer.create_missing and layer.training,
                                          **_dtype_kw(layer))
         return out, keys.new_empty(0)
@@ -194,7 +200,7 @@ def lookup_pooled(keys: torch.Tensor, bag_offsets: torch.Tensor, anchor: torch.T
 def _(keys, bag_offsets, anchor, table_id, mean):
     layer = _layer(table_id)
     return (keys.new_empty((bag_offsets.numel() - 1, layer.table.dim), dtype=layer.out_dtype),
-            keys.new_empty(keys.numel() if hasattr(layer.table, "apply_pooled") else 0))
+            keys.new_empty(keys.numel() if _hands_located(layer.table) else 0))
 
 
 @torch.library.custom_op("meepo::apply_grad_pooled", mutates_args=())
@@ -408,6 +414,8 @@ class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
             return lookup_pooled(keys, bag_offsets, self._anchor, self.table_id, self.mode == "mean")[0]
         if self.mode != "sum":
             raise ValueError("per_sample_weights are only supported for mode='sum', as in torch.nn.EmbeddingBag")
+        if not getattr(self.table, "weighted_bags", True):   # (a ShardedTableGroup) refused on every rank alike, before anything is exchanged
+            raise ValueError(f"{type(self.table).__name__} has no weighted bags: per_sample_weights are not offered over a sharded group")
         return lookup_pooled_weighted(keys, bag_offsets, per_sample_weights, self._anchor, self.table_id)[0]
 
 

@@ -327,7 +327,17 @@ class ShardedTableGroup(_Exchange):
 
     4 collectives per find and 3 per apply whatever T is, where T ShardedLookupTable calls make 4 T and 3 T (and T host syncs); the bytes are the same
     plus 8 T (G - 1) count bytes each way instead of 8 T (G - 1) in T pieces.  Collective: every rank calls, also with an empty batch.
-    `router`: the HIP Router (segment_counts / regroup); dedup= and grad_index= are not offered, nor are the pooled forms."""
+    `router`: the HIP Router (segment_counts / regroup); dedup= and grad_index= are not offered.
+
+    Embedding bags (find_pooled / apply_pooled; SPEC.md §5 "Pooled lookups over a group"): the collection's bags, B per member, bag b belonging to
+    member b // B — ShardedLookupTable.find_pooled of every member with its B bags.  The owners pool, one fp32 row per (bag, owner) run travels:
+
+        partition(keys)  ->  bag_runs  ->  segment_counts twice: the key cells and the run cells  ->  ONE all-to-all of the [G, 2 T] cells
+        all-to-all keys (8 B) and run lengths (4 B);  owner: regroup the keys AND the runs, run_offsets, ONE find_pooled_jagged over the runs
+        lookup: all-to-all partial rows (4 dim B per RUN) + found-mask back, combine_bag_runs (rank order; mean / bf16 here, at the source)
+        step: the runs' gradient rows travel with the keys, ONE apply_indexed on the owner; nothing comes back
+
+    5 collectives per pooled lookup and 4 per pooled step, whatever T is; weighted bags and dedup= are not offered."""
 
     def __init__(self, local_group, router, group=None):
         if not hasattr(local_group, "tables"):
@@ -408,6 +418,101 @@ class ShardedTableGroup(_Exchange):
         recv_rows = self._a2a(send_rows, ss, rs)
         keys_tm, order, offsets_tm = self.router.regroup(recv_keys, recv_cells)
         return keys_tm, offsets_tm, self.router.gather_rows(recv_rows, order)
+
+    # -- embedding bags over the collection (SPEC.md §5 "Pooled lookups over a group") ----------------------------------------------
+    pools_with_insert = True   # find_pooled(insert_missing=True): what DynamicEmbeddingBag(create_missing=True) calls instead of a find_or_insert of its own
+    weighted_bags = False      # no per_sample_weights over a sharded group: DynamicEmbeddingBag refuses them before anything is exchanged
+
+    def _check_bags(self, ops, keys: torch.Tensor, bag_offsets: torch.Tensor):
+        """what every rank can decide alone, before anything is exchanged -> (keys [n], bags per member)"""
+        for op in ops:
+            if not callable(getattr(self.local_group, op, None)):
+                raise ValueError(f"{type(self.local_group).__name__} has no {op}: pooled forms over a sharded group need a TableGroup of the local shards")
+        for m in ("bag_runs", "run_offsets", "combine_bag_runs", "segment_counts", "regroup"):
+            if not hasattr(self.router, m):
+                raise ValueError(f"{type(self.router).__name__} has no {m}: pooled forms over a sharded group need the HIP Router")
+        n_bags = bag_offsets.numel() - 1
+        if bag_offsets.dim() != 1 or n_bags < 0 or n_bags % self.n_tables:
+            raise ValueError(f"bag_offsets must hold n_tables x bags_per_table + 1 entries, n_tables = {self.n_tables} (got {tuple(bag_offsets.shape)})")
+        if keys.numel() and n_bags == 0:
+            raise ValueError("there are keys but no bags (the bags partition the batch)")
+        return keys.contiguous().view(-1), n_bags // self.n_tables
+
+    def _bag_route(self, keys: torch.Tensor, bag_offsets: torch.Tensor, bpt: int):
+        """partition + the runs + the key cells and the run cells + ONE count exchange of [G, 2 T].
+        -> (send_keys, perm, key splits out / in, run_bag [R], run_len [R], run_counts, run splits out / in, received key cells, received run cells)"""
+        T = self.n_tables
+        send_keys, counts, perm = self.router.partition(keys)
+        run_bag, run_len, run_counts = self.router.bag_runs(perm, counts, bag_offsets)
+        member_off = bag_offsets[::bpt].contiguous() if bpt else bag_offsets.new_zeros(T + 1)
+        key_cells = self.router.segment_counts(perm, counts, member_off)
+        # the runs of an owner segment ascend by bag as its positions do: the same operator counts the runs per member (it only compares the entries)
+        member_bags = torch.arange(T + 1, dtype=torch.int64, device=keys.device) * bpt
+        run_cells = self.router.segment_counts(run_bag.to(torch.int64), run_counts, member_bags)
+        sent, received = self._swap_counts(torch.cat([key_cells, run_cells], dim=1))
+        ss, rss = sent[:, :T].sum(dim=1).tolist(), sent[:, T:].sum(dim=1).tolist()
+        rs, rrs = received[:, :T].sum(dim=1).tolist(), received[:, T:].sum(dim=1).tolist()
+        r = sum(rss)
+        received = received.to(keys.device)
+        return send_keys, perm, ss, rs, run_bag[:r], run_len[:r], run_counts, rss, rrs, received[:, :T].contiguous(), received[:, T:].contiguous()
+
+    def _regroup_runs(self, recv_keys: torch.Tensor, recv_len: torch.Tensor, key_cells: torch.Tensor, run_cells: torch.Tensor):
+        """the owner's side: keys and runs source-major -> table-major.  A run's keys are contiguous in keys_tm, in the runs' table-major order.
+        -> (keys_tm, order, offsets_tm, order_r, member_bags, run_len_tm)"""
+        keys_tm, order, offsets_tm = self.router.regroup(recv_keys, key_cells)
+        # only the order and the offsets of the runs' regrouping are used: any int64 array of R entries serves as its keys (R <= received keys)
+        _, order_r, member_bags = self.router.regroup(recv_keys[:recv_len.numel()], run_cells)
+        return keys_tm, order, offsets_tm, order_r, member_bags, self.router.gather_rows(recv_len, order_r)
+
+    def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", insert_missing: bool = False,
+                    out_dtype: torch.dtype = torch.float32):
+        """Embedding-bag lookup over the sharded collection -> ([T B, dim] sums or means, per-key found mask [n]): bag_offsets holds T B + 1 offsets
+        that partition this rank's batch, bag b belongs to member b // B (B may differ from rank to rank).  ShardedLookupTable.find_pooled of every
+        member with its B bags: the same partial rows, added up in rank order; one rank: bit-identical to TableGroup.find_pooled.
+        insert_missing: the owners find_or_insert the received keys first (found = existed before).  Collective, also without keys or bags."""
+        if mode not in ("sum", "mean"):
+            raise ValueError(f"mode must be 'sum' or 'mean' (got {mode!r})")
+        _out_dtype(out_dtype)
+        keys, bpt = self._check_bags(("find_pooled_jagged",) + (("find_or_insert",) if insert_missing else ()), keys, bag_offsets)
+        send_keys, perm, ss, rs, run_bag, run_len, run_counts, rss, rrs, key_cells, run_cells = self._bag_route(keys, bag_offsets, bpt)
+        recv_keys = self._a2a(send_keys, ss, rs)
+        recv_len = self._a2a(run_len, rss, rrs)
+        keys_tm, order, offsets_tm, order_r, member_bags, run_len_tm = self._regroup_runs(recv_keys, recv_len, key_cells, run_cells)
+        run_off, _ = self.router.run_offsets(run_len_tm)
+        if insert_missing:
+            _, found = self.local_group.find_or_insert(keys_tm, offsets_tm)
+            partial, _ = self.local_group.find_pooled_jagged(keys_tm, run_off, member_bags, "sum")
+        else:
+            partial, found = self.local_group.find_pooled_jagged(keys_tm, run_off, member_bags, "sum")
+        partial_back = self._a2a(self.router.scatter_rows(partial, order_r), rrs, rss)      # fp32: rounding at the owner would round twice
+        found_back = self._a2a(self.router.scatter_rows(found, order), rs, ss)
+        out = self.router.combine_bag_runs(partial_back, run_bag, run_counts, bag_offsets, mode, out_dtype=out_dtype)
+        return out, self.router.scatter_rows(found_back, perm)
+
+    def apply_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, bag_grads: torch.Tensor, bag_of_position: torch.Tensor,
+                     optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1,
+                     located: torch.Tensor | None = None) -> None:
+        """Backward of find_pooled, with the signature of TableGroup.apply_pooled: one optimizer step, every key of bag b takes row b of bag_grads
+        [T B, dim] (pre-scaled by 1 / length for a mean).  One gradient row per run travels with the keys; the owner reduces duplicates per member
+        over all ranks' contributions in one indexed apply.  bag_of_position [n] is the bag of every position as bag_offsets defines it;
+        `located` is accepted and ignored (handles do not cross the two exchanges)."""
+        if optimizer not in ("adagrad", "adam"):
+            raise ValueError(f"optimizer must be 'adagrad' or 'adam' (got {optimizer!r})")
+        keys, bpt = self._check_bags(("apply_indexed",), keys, bag_offsets)
+        if bag_of_position.numel() != keys.numel():
+            raise ValueError("bag_of_position must hold one entry per key")
+        g = bag_grads.contiguous().view(-1, self.dim)
+        if g.shape[0] != bpt * self.n_tables:
+            raise ValueError(f"bag_grads must hold one row of {self.dim} per bag")
+        send_keys, perm, ss, rs, run_bag, run_len, run_counts, rss, rrs, key_cells, run_cells = self._bag_route(keys, bag_offsets, bpt)
+        run_rows = self.router.gather_rows(g, run_bag.to(torch.int64))
+        recv_keys = self._a2a(send_keys, ss, rs)
+        recv_len = self._a2a(run_len, rss, rrs)
+        recv_rows = self._a2a(run_rows, rss, rrs)
+        keys_tm, _, offsets_tm, order_r, _, run_len_tm = self._regroup_runs(recv_keys, recv_len, key_cells, run_cells)
+        _, run_of_key = self.router.run_offsets(run_len_tm, keys_tm.numel())
+        self.local_group.apply_indexed(keys_tm, offsets_tm, self.router.gather_rows(recv_rows, order_r), run_of_key, optimizer, lr, eps=eps,
+                                       beta1=beta1, beta2=beta2, step=step)
 
     def apply_adagrad(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10) -> None:
         k, off, g = self._push("apply_adagrad", keys, offsets, grads)

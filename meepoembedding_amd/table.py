@@ -713,6 +713,57 @@ class TableGroup:
             check(L.mee_group_apply_adam_pooled(self._h, k.data_ptr(), bag_offsets.data_ptr(), bpt, g.data_ptr(), gi.data_ptr(), loc, k.numel(),
                                                 lr, beta1, beta2, 1e-8 if eps is None else eps, step, s))
 
+    # -- the same collection with a different number of bags per member (the owner's side of ShardedTableGroup's bags) --------
+    def find_pooled_jagged(self, keys: torch.Tensor, bag_offsets: torch.Tensor, member_bags: torch.Tensor, mode: str = "sum",
+                           out: torch.Tensor | None = None, found: torch.Tensor | None = None, located: torch.Tensor | None = None):
+        """find_pooled where bag b belongs to the member j with member_bags[j] <= b < member_bags[j + 1] (n_tables + 1 non-decreasing int64 on the
+        device; members may have no bags; bags outside the map are empty) -> ([n_bags, dim] fp32, per-key found mask).  Sync-free."""
+        _fp32_only(out, "find_pooled_jagged")
+        self._check_offsets(member_bags)
+        nb = bag_offsets.numel() - 1
+        if bag_offsets.device != self.device or bag_offsets.dtype not in (torch.int64, torch.uint64) or not bag_offsets.is_contiguous() or nb < 0:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_offsets must be contiguous int64 on {self.device} with n_bags + 1 entries")
+        if mode not in ("sum", "mean"):
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"mode must be 'sum' or 'mean' (got {mode!r})")
+        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        if out is None:
+            out = torch.empty((nb, self.dim), dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or out.device != self.device or out.numel() != nb * self.dim or not out.is_contiguous():
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"out must be a contiguous float32 buffer [{nb}, {self.dim}] on {self.device}")
+        if found is None:
+            found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
+        elif found.dtype != torch.uint8 or found.device != self.device or found.numel() != k.numel() or not found.is_contiguous():
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"found must be a contiguous uint8 buffer of {k.numel()} entries on {self.device}")
+        if located is not None and (located.dtype != torch.int64 or located.device != self.device or located.numel() != k.numel()
+                                    or not located.is_contiguous()):
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"located must be a contiguous int64 buffer of {k.numel()} entries on {self.device}")
+        if k.numel() and nb == 0:
+            raise MeepoError(_lib.ERR_INVALID_ARG, "there are keys but no bags: no bag would report them")
+        check(_lib.lib().mee_group_find_pooled_jagged(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), nb, member_bags.data_ptr(), out.data_ptr(),
+                                                      found.data_ptr(), located.data_ptr() if located is not None else None,
+                                                      {"sum": 0, "mean": 1}[mode], _stream_ptr(self.device)))
+        return out, found
+
+    def apply_indexed(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, grad_index: torch.Tensor, optimizer: str, lr: float,
+                      eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1) -> None:
+        """One optimizer step over the jagged batch == LookupTable.apply_*(grad_index=...) per member with its segment: position i takes row
+        grad_index[i] of grads [rows, dim]."""
+        self._check_offsets(offsets)
+        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        gi = self.tables[0]._grad_index(grad_index, k.numel())
+        g = grads.contiguous()
+        if g.dtype != torch.float32 or g.dim() != 2 or g.shape[1] != self.dim or g.device != self.device:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"grads must be float32 [rows, {self.dim}] on {self.device}")
+        L, s = _lib.lib(), _stream_ptr(self.device)
+        if optimizer == "adagrad":
+            check(L.mee_group_apply_adagrad_indexed(self._h, k.data_ptr(), offsets.data_ptr(), g.data_ptr(), g.shape[0], gi.data_ptr(), k.numel(),
+                                                    lr, 1e-10 if eps is None else eps, s))
+        elif optimizer == "adam":
+            check(L.mee_group_apply_adam_indexed(self._h, k.data_ptr(), offsets.data_ptr(), g.data_ptr(), g.shape[0], gi.data_ptr(), k.numel(),
+                                                 lr, beta1, beta2, 1e-8 if eps is None else eps, step, s))
+        else:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"optimizer must be 'adagrad' or 'adam' (got {optimizer!r})")
+
     def pooled_weighted_backward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, weights: torch.Tensor, bag_grads: torch.Tensor,
                                  located: torch.Tensor | None = None, want_weight_grads: bool = True, grads: torch.Tensor | None = None,
                                  weight_grads: torch.Tensor | None = None):
