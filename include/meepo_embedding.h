@@ -379,6 +379,39 @@ int mee_group_find_or_insert_as(mee_group* g, const int64_t* d_keys, const uint6
 int mee_group_find_pooled_as(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
                              const float* d_weights, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream);
 
+/* ---- mixed groups: an embedding-bag collection whose tables differ in dim (SPEC.md §3 "Mixed groups") ------------------------
+ * The members share a device (and, with max_apply_batch, an optimizer); every dim is a multiple of 4.  Pooled lookups only: bag b belongs
+ * to member b / bags_per_table, and by definition every operator is the single-table operator of each member with its bags.
+ * Output layout ("class-major"): a class = the members of one dim; classes by ascending dim, members inside a class in the caller's order.
+ * Member j's bags_per_table bag rows are one contiguous [bags_per_table, dim_j] block and the blocks follow each other class by class, so
+ * a class is one [T_c * bags_per_table, dim_c] array.  mee_mixed_group_layout reports every block's element offset (the same for fp32
+ * and bf16 elements) and the total element count; d_bag_grads of the step has the same layout, fp32.  d_keys, d_bag_offsets, d_found
+ * and d_located keep the caller's member order; d_located[i] = member << 48 | slot with the caller's member index (EMPTY when absent).
+ *   mee_mixed_group_find_pooled   one launch.  insert_missing != 0: absent keys are first created in their member tables (initial row /
+ *                                 state, as mee_group_find_or_insert; two more launches), d_found (required then) = present before the
+ *                                 call, TABLE_FULL / RESERVED_KEY land on the member.  d_found / d_located nullable otherwise.
+ *   mee_mixed_group_apply_*       mee_apply_*_indexed per member: position i takes the row of bag d_bag_of_position[i] (its index in the
+ *                                 caller's order, as mee_group_apply_*_pooled) — per class one select launch and the grouped apply of
+ *                                 mee_group_apply_*_pooled.  d_located (nullable): the handles mee_mixed_group_find_pooled of the SAME step filled.
+ * A group whose members all share one dim runs the launches of mee_group_find_pooled_as / mee_group_apply_*_pooled, bit for bit.
+ * Refusals as mee_group_create / mee_group_apply_*.  No weighted, jagged or unpooled form.  Calls that use the group's step buffers
+ * (mee_mixed_group_apply_*) must be ordered by the caller. */
+typedef struct mee_mixed_group mee_mixed_group;
+int mee_mixed_group_create(mee_table* const* tables, uint32_t n_tables, uint64_t max_apply_batch, mee_mixed_group** out);
+int mee_mixed_group_destroy(mee_mixed_group* g);
+int mee_mixed_group_layout(const mee_mixed_group* g, uint64_t bags_per_table, uint64_t* elem_offsets /* [n_tables], nullable */,
+                           uint64_t* total_elems /* nullable */);
+int mee_mixed_group_find_pooled(mee_mixed_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                                void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_located /* nullable */, int mode,
+                                int insert_missing, void* stream);
+int mee_mixed_group_apply_adagrad_pooled(mee_mixed_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                                         const float* d_bag_grads, const uint32_t* d_bag_of_position, const int64_t* d_located /* nullable */,
+                                         size_t n, float lr, float eps, void* stream);
+int mee_mixed_group_apply_adam_pooled(mee_mixed_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                                      const float* d_bag_grads, const uint32_t* d_bag_of_position, const int64_t* d_located /* nullable */,
+                                      size_t n, float lr, float beta1, float beta2, float eps, uint64_t step, void* stream);
+int mee_mixed_group_set_tuning(mee_mixed_group* g, const char* name, int value);   /* forwarded to every class's apply */
+
 /* ---- sparse optimizers (north_star "sparse-optimizer (Adagrad/Adam) scatter-update"; SPEC.md §4) -------- */
 int mee_apply_adagrad(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, float lr, float eps,
                       void* stream);

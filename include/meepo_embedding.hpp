@@ -193,6 +193,40 @@ private:
     mee_group* g_ = nullptr;
 };
 
+// An embedding-bag collection whose tables differ in dim: one pooled-lookup launch, class-major output (mee_mixed_group_*).
+class MixedGroup {
+public:
+    MixedGroup(Table* const* tables, uint32_t n, uint64_t max_apply_batch = 0) : n_(n) {
+        std::string h(n * sizeof(mee_table*), '\0');
+        auto** raw = reinterpret_cast<mee_table**>(&h[0]);
+        for (uint32_t j = 0; j < n; ++j) raw[j] = tables[j]->handle();
+        check(mee_mixed_group_create(raw, n, max_apply_batch, &g_));
+    }
+    ~MixedGroup() { if (g_) mee_mixed_group_destroy(g_); }
+    MixedGroup(const MixedGroup&) = delete;
+    MixedGroup& operator=(const MixedGroup&) = delete;
+    uint32_t size() const { return n_; }
+    // element offset of every member's [bags_per_table, dim_j] block (elem_offsets: size() entries, nullable) -> the total element count
+    uint64_t layout(uint64_t bags_per_table, uint64_t* elem_offsets = nullptr) const {
+        uint64_t total = 0;
+        check(mee_mixed_group_layout(g_, bags_per_table, elem_offsets, &total));
+        return total;
+    }
+    void find_pooled(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, uint8_t* d_found = nullptr, int64_t* d_located = nullptr, int mode = MEE_POOL_SUM, bool insert_missing = false, void* stream = nullptr) {
+        check(mee_mixed_group_find_pooled(g_, d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, d_found, d_located, mode, insert_missing, stream));
+    }
+    void apply_adagrad_pooled(const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_bag_grads, const uint32_t* d_bag_of_position, const int64_t* d_located, size_t n, float lr, float eps = 1e-10f, void* stream = nullptr) {
+        check(mee_mixed_group_apply_adagrad_pooled(g_, d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_bag_of_position, d_located, n, lr, eps, stream));
+    }
+    void apply_adam_pooled(const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_bag_grads, const uint32_t* d_bag_of_position, const int64_t* d_located, size_t n, float lr, uint64_t step, float beta1 = 0.9f, float beta2 = 0.999f, float eps = 1e-8f, void* stream = nullptr) {
+        check(mee_mixed_group_apply_adam_pooled(g_, d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_bag_of_position, d_located, n, lr, beta1, beta2, eps, step, stream));
+    }
+    void set_tuning(const char* name, int value) { check(mee_mixed_group_set_tuning(g_, name, value)); }
+private:
+    mee_mixed_group* g_ = nullptr;
+    uint32_t n_ = 0;
+};
+
 // Hot (HBM) table backed by a cold table whose rows live in pinned host DRAM: one logical table, sync-free lookup.
 class TieredTable {
 public:

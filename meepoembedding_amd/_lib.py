@@ -120,6 +120,14 @@ PROTOTYPES = {
     "mee_group_destroy": (C.c_int, [_vp]),
     "mee_group_set_tuning": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "mee_find_grouped": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    # mixed groups: members of different dims, class-major output (meepo_mixed.hip)
+    "mee_mixed_group_create": (C.c_int, [C.POINTER(_vp), _u32, _u64, C.POINTER(_vp)]),
+    "mee_mixed_group_destroy": (C.c_int, [_vp]),
+    "mee_mixed_group_layout": (C.c_int, [_vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "mee_mixed_group_find_pooled": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "mee_mixed_group_apply_adagrad_pooled": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _f32, _f32, _vp]),
+    "mee_mixed_group_apply_adam_pooled": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32, _u64, _vp]),
+    "mee_mixed_group_set_tuning": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "mee_find_pooled": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, C.c_int, _vp]),
     "mee_find_pooled_weighted": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "mee_pooled_weighted_backward": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),

@@ -151,6 +151,41 @@ __device__ __forceinline__ int64_t collect_slots(const int64_t (&slot)[R], int l
     return mine;
 }
 
+// ---- pooled lookups (meepo_find.hip: one table and the uniform group; meepo_mixed.hip: the mixed group) ------------------------------
+// a bag of this many keys or more is served by the wave's four tiles together (find_pooled_kernel)
+constexpr uint32_t kPoolLong = 16;
+
+// probe + row load of up to U keys per tile (the find_kernel pattern); row[u] is only defined where inb[u].
+// located (nullable) receives tag | slot per position: tag = member << kGroupSlotBits for a group (EMPTY when absent), or the table's
+// handle tag (handle_tag_of) for one table with TAGGED (-1 when absent: the format of mee_find_located)
+template <int DIM4, int U, int C, bool TAGGED = false>
+__device__ __forceinline__ void pooled_fetch(const int64_t* __restrict__ tkeys, const float4* __restrict__ values, uint64_t nb,
+                                             uint32_t dim4, const int64_t (&key)[U], const uint64_t (&pos)[U],
+                                             const bool (&inb)[U], int tile, int tl, float4 def4, float4 (&row)[U][C],
+                                             uint8_t* __restrict__ found, int64_t* __restrict__ located = nullptr, uint64_t tag = 0) {
+    int64_t slot[U], kb[U];
+    uint64_t bk[U];
+    bool act[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        act[u] = inb[u] && !reserved_key(key[u]);
+        bk[u] = bucket_of(key[u], nb);
+        kb[u] = act[u] ? tkeys[bk[u] * kW + tl] : kEmpty;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) slot[u] = tile_probe(tkeys, nb, key[u], act[u], bk[u], kb[u], tile, tl);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4)
+                row[u][c] = slot[u] >= 0 ? values[(uint64_t)slot[u] * dim4 + c * 16 + tl] : def4;
+        if (found && inb[u] && tl == 0) found[pos[u]] = slot[u] >= 0;
+        // the located row: lets the backward skip its own probe pass
+        if (located && inb[u] && tl == 0) located[pos[u]] = slot[u] >= 0 ? (int64_t)(tag | (uint64_t)slot[u]) : (TAGGED ? -1 : kEmpty);
+    }
+}
+
 // ---- bf16 output of the lookups (SPEC.md §3 "Output type") ------------------------------------------------------------------
 // A lane that holds a float4 of a row stores it as 4 bf16 = 8 bytes; a row of dim bf16 is dim4 such 8-byte groups, so group g of
 // output row i sits at index i * dim4 + g of a u32x2 array — the SAME index the fp32 kernels use on their f32x4 array.

@@ -246,39 +246,6 @@ __global__ __launch_bounds__(256) void find_missing_kernel(const int64_t* __rest
 // flight (all bucket lines requested, then all rows).  Bags of kPoolLong keys or more: the four tiles work on ONE bag
 // together — tile t probes positions i + 4u + t — and every tile then adds the 4U rows in position order out of the
 // other tiles' registers (shuffles), so a long bag has 4U keys in flight instead of U.
-constexpr uint32_t kPoolLong = 16;
-
-// probe + row load of up to U keys per tile (the find_kernel pattern); row[u] is only defined where inb[u].
-// located (nullable) receives tag | slot per position: tag = member << kGroupSlotBits for a group (EMPTY when absent), or the table's
-// handle tag (handle_tag_of) for one table with TAGGED (-1 when absent: the format of mee_find_located)
-template <int DIM4, int U, int C, bool TAGGED = false>
-__device__ __forceinline__ void pooled_fetch(const int64_t* __restrict__ tkeys, const float4* __restrict__ values, uint64_t nb,
-                                             uint32_t dim4, const int64_t (&key)[U], const uint64_t (&pos)[U],
-                                             const bool (&inb)[U], int tile, int tl, float4 def4, float4 (&row)[U][C],
-                                             uint8_t* __restrict__ found, int64_t* __restrict__ located = nullptr, uint64_t tag = 0) {
-    int64_t slot[U], kb[U];
-    uint64_t bk[U];
-    bool act[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        act[u] = inb[u] && !reserved_key(key[u]);
-        bk[u] = bucket_of(key[u], nb);
-        kb[u] = act[u] ? tkeys[bk[u] * kW + tl] : kEmpty;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) slot[u] = tile_probe(tkeys, nb, key[u], act[u], bk[u], kb[u], tile, tl);
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-            if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4)
-                row[u][c] = slot[u] >= 0 ? values[(uint64_t)slot[u] * dim4 + c * 16 + tl] : def4;
-        if (found && inb[u] && tl == 0) found[pos[u]] = slot[u] >= 0;
-        // the located row: lets the backward skip its own probe pass
-        if (located && inb[u] && tl == 0) located[pos[u]] = slot[u] >= 0 ? (int64_t)(tag | (uint64_t)slot[u]) : (TAGGED ? -1 : kEmpty);
-    }
-}
-
 // JAGGED bag -> member map (mee_group_find_pooled_jagged): the member j with member_bags[j] <= bag < member_bags[j + 1], by an upper-bound
 // search over member_bags[1 .. n_members] (at most ten dependent reads of an L2-resident array for 1024 members).  The array is the
 // caller's: whatever it holds, the member stays inside [0, n_members); false = the bag lies outside [member_bags[0], member_bags[n_members]).
@@ -302,6 +269,9 @@ __device__ __forceinline__ bool jagged_member(const uint64_t* __restrict__ membe
 // JAGGED (mee_group_find_pooled_jagged; GROUPED, fp32, unweighted): the members' bag counts differ — bag b belongs to the member that
 // jagged_member finds in member_bags, and a bag outside the map is an empty bag (a row of zeros, nothing probed).  The instances
 // with JAGGED = false are the code they were before the parameter existed.
+// The loop body below has a COPY in mixed_bags (meepo_mixed.hip: the group whose members differ in dim; only the member lookup and the output
+// index differ there).  SPEC.md §3 defines the mixed group's result through this kernel's, so a change to the order of the additions, the
+// mean's division, the long-bag rule or the clamping of the offsets here has to be made there too (tests/test_mixed_groups.py compares them).
 template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false, bool JAGGED = false>
 __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restrict__ tkeys_, const float4* __restrict__ values_,
                                                           uint64_t nb_, const int64_t* __restrict__ keys,

@@ -247,6 +247,64 @@ def _backward_pooled(ctx, grad_out, _grad_located):
 lookup_pooled.register_autograd(_backward_pooled, setup_context=_setup_pooled)
 
 
+# ---- pooled over a MixedTableGroup (members of different dims): one lookup op whose flat class-major buffer the layer views per member --------
+@torch.library.custom_op("meepo::lookup_pooled_mixed", mutates_args=())
+def lookup_pooled_mixed(keys: torch.Tensor, bag_offsets: torch.Tensor, anchor: torch.Tensor, table_id: int, mean: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    """-> (the flat class-major buffer of every member's pooled rows (table.mixed_layout), located rows [n] for the backward of this step)"""
+    layer = _layer(table_id)
+    group = layer.table
+    located = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
+    flat = torch.empty(_mixed_total(group, bag_offsets), dtype=layer.out_dtype, device=keys.device)
+    group.find_pooled(keys, bag_offsets, "mean" if mean else "sum", out=flat, located=located, out_dtype=layer.out_dtype,
+                      insert_missing=layer.create_missing and layer.training)
+    return flat, located
+
+
+def _mixed_total(group, bag_offsets) -> int:
+    from .table import mixed_layout
+    return mixed_layout(group.dims, (bag_offsets.numel() - 1) // len(group.tables))[2]
+
+
+@lookup_pooled_mixed.register_fake
+def _(keys, bag_offsets, anchor, table_id, mean):
+    layer = _layer(table_id)
+    return keys.new_empty(_mixed_total(layer.table, bag_offsets), dtype=layer.out_dtype), keys.new_empty(keys.numel())
+
+
+@torch.library.custom_op("meepo::apply_grad_pooled_mixed", mutates_args=())
+def apply_grad_pooled_mixed(keys: torch.Tensor, bag_offsets: torch.Tensor, grad_flat: torch.Tensor, located: torch.Tensor, table_id: int, mean: bool) -> None:
+    layer = _layer(table_id)
+    group = layer.table
+    lens = bag_offsets[1:] - bag_offsets[:-1]
+    bag_of = torch.repeat_interleave(torch.arange(lens.numel(), device=keys.device), lens, output_size=keys.numel())
+    g = grad_flat.contiguous()
+    if mean:   # d mean / d row = 1 / length for every member of the bag; the bags of member j are rows of its own block
+        bpt = lens.numel() // len(group.tables)
+        inv = lens.clamp(min=1).to(torch.float32)
+        g = g.clone()
+        for j, v in enumerate(group.views(g, bpt)):
+            v /= inv[j * bpt:(j + 1) * bpt, None]
+    layer.step += 1
+    group.apply_pooled(keys, bag_offsets, g, bag_of, layer.optimizer, lr=layer.lr, eps=layer.eps, beta1=layer.betas[0], beta2=layer.betas[1],
+                       step=layer.step, located=located if located.numel() == keys.numel() else None)
+
+
+@apply_grad_pooled_mixed.register_fake
+def _(keys, bag_offsets, grad_flat, located, table_id, mean):
+    return None
+
+
+def _backward_pooled_mixed(ctx, grad_flat, _grad_located):
+    keys, bag_offsets, located = ctx.saved_tensors
+    if getattr(_layer(ctx.table_id).table, "layout_epoch", None) != ctx.layout_epoch:
+        located = located.new_empty(0)   # a table changed between forward and backward: the step probes for itself
+    apply_grad_pooled_mixed(keys, bag_offsets, grad_flat.contiguous().to(torch.float32), located, ctx.table_id, ctx.mean)
+    return None, None, None, None, None
+
+
+lookup_pooled_mixed.register_autograd(_backward_pooled_mixed, setup_context=_setup_pooled)
+
+
 # ---- weighted pooled (torch.nn.EmbeddingBag's per_sample_weights; SUM only): bag = sum of w_i * row_i ----------------------
 # forward = find_pooled(weights=...), which also hands every position's handle to the backward; backward = pooled_weighted_backward
 # (grads [n, dim] = w_i * the bag's grad row, and the grad of the weights when they need one), then the table's step on those grads
@@ -394,6 +452,7 @@ class DynamicEmbeddingCollection(torch.nn.Module, _SparseOptimizerSettings):
 class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
     """torch.nn.EmbeddingBag over a lookup table — or over a TableGroup, which makes it an embedding-bag COLLECTION: bag b
     then belongs to member b // bags_per_table and the whole model's sparse forward is one launch, its backward seven.
+    Over a MixedTableGroup (members of different dims) forward returns a list: member j's [bags_per_table, dim_j] tensor, views of one buffer.
     (keys [n], bag_offsets [n_bags + 1], both on the device) -> [n_bags, dim] sums or means; backward runs the table's sparse optimizer with the bag's grad row for every member (no [n, dim]
     tensor exists in either direction).  create_missing=True (training mode only): unseen ids are inserted with their
     hashed initial row first (one more pass over the ids); otherwise absent ids read the default row and are not trained."""
@@ -410,6 +469,11 @@ class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
     def forward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, per_sample_weights: torch.Tensor | None = None) -> torch.Tensor:
         """per_sample_weights (fp32 [n], mode "sum" only): the bag is the sum of w_i * row_i; backward also yields their grad.
         The weighted backward updates every position, so its bags must partition the keys: bag_offsets[0] = 0, bag_offsets[-1] = n."""
+        if getattr(self.table, "mixed_dims", False):   # a MixedTableGroup: one tensor per member, views of the one buffer the lookup wrote
+            if per_sample_weights is not None:
+                raise ValueError(f"{type(self.table).__name__} has no weighted bags: per_sample_weights are not offered over members of different dims")
+            flat = lookup_pooled_mixed(keys, bag_offsets, self._anchor, self.table_id, self.mode == "mean")[0]
+            return self.table.views(flat, (bag_offsets.numel() - 1) // len(self.table.tables))
         if per_sample_weights is None:
             return lookup_pooled(keys, bag_offsets, self._anchor, self.table_id, self.mode == "mean")[0]
         if self.mode != "sum":

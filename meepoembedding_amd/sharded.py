@@ -342,6 +342,9 @@ class ShardedTableGroup(_Exchange):
     def __init__(self, local_group, router, group=None):
         if not hasattr(local_group, "tables"):
             raise ValueError(f"{type(local_group).__name__} is no group of tables (a TableGroup of the rank's local shards)")
+        if getattr(local_group, "mixed_dims", False):
+            raise ValueError(f"{type(local_group).__name__} has members of different dims: a sharded group exchanges rows of one width "
+                             "(one ShardedTableGroup per width, each over a TableGroup)")
         self.local = self.local_group = local_group
         self.dim = local_group.dim
         self.n_tables = len(local_group.tables)

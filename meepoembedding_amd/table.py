@@ -808,6 +808,136 @@ class TableGroup:
         return out, found
 
 
+def mixed_layout(dims, bags_per_table: int):
+    """The output layout of a mixed group (SPEC.md §3 "Mixed groups"), as mee_mixed_group_layout reports it: a class = the members of one dim,
+    classes by ascending dim, members inside a class in the caller's order; member j's block is [bags_per_table, dims[j]] and the blocks
+    follow each other class by class.  -> (class order: the member indices in block order, element offset of every member's block, total elements)."""
+    dims = [int(d) for d in dims]
+    order = sorted(range(len(dims)), key=lambda j: (dims[j], j))
+    offsets, total = [0] * len(dims), 0
+    for j in order:
+        offsets[j] = total
+        total += int(bags_per_table) * dims[j]
+    return order, offsets, total
+
+
+class MixedTableGroup:
+    """An embedding-bag collection whose tables differ in dim (same device): ONE pooled-lookup launch for all members, one optimizer step
+    (per dim class a select launch + the TableGroup step).  Pooled lookups only: bag b belongs to member b // bags_per_table.  The output is
+    one flat buffer in the class-major layout of mixed_layout(); find_pooled hands back per-member [bags_per_table, dim_j] views of it in the
+    caller's order.  Equal dims: the launches of TableGroup, bit for bit."""
+    supports_out_dtype = True
+    weighted_bags = False
+    mixed_dims = True
+
+    def __init__(self, tables, max_apply_batch: int = 0):
+        self.tables = list(tables)
+        if not self.tables:
+            raise ValueError("a group needs at least one table")
+        self.device = self.tables[0].device
+        self.dims = [t.dim for t in self.tables]
+        arr = (C.c_void_p * len(self.tables))(*[t._h for t in self.tables])
+        h = C.c_void_p()
+        self._h = None
+        with torch.cuda.device(self.device):
+            check(_lib.lib().mee_mixed_group_create(arr, len(self.tables), int(max_apply_batch), C.byref(h)))
+        self._h = h
+
+    @property
+    def layout_epoch(self):
+        """Changes whenever a member table removed, cleared or rehashed rows: located handles from before are stale."""
+        return tuple(t.layout_epoch for t in self.tables)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _lib.lib().mee_mixed_group_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_tuning(self, name: str, value: int) -> None:
+        """Performance knobs of every class's apply (mee_set_tuning); never change results."""
+        check(_lib.lib().mee_mixed_group_set_tuning(self._h, name.encode(), int(value)))
+
+    def layout(self, bags_per_table: int):
+        """-> (element offset of every member's [bags_per_table, dim_j] block, total elements), from the library (== mixed_layout(dims, B)[1:])."""
+        offs = (C.c_uint64 * len(self.tables))()
+        total = C.c_uint64()
+        check(_lib.lib().mee_mixed_group_layout(self._h, int(bags_per_table), offs, C.byref(total)))
+        return list(offs), int(total.value)
+
+    def views(self, flat: torch.Tensor, bags_per_table: int):
+        """the per-member [bags_per_table, dim_j] views of a flat class-major buffer, in the caller's member order (no copy)"""
+        _, offs, _ = mixed_layout(self.dims, bags_per_table)
+        return [flat[o:o + bags_per_table * d].view(bags_per_table, d) for o, d in zip(offs, self.dims)]
+
+    def _check_bags(self, bag_offsets: torch.Tensor) -> int:
+        nb = bag_offsets.numel() - 1
+        if bag_offsets.device != self.device or bag_offsets.dtype not in (torch.int64, torch.uint64) or not bag_offsets.is_contiguous() \
+                or nb < 0 or nb % len(self.tables):
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_offsets must be contiguous int64 on {self.device} with n_tables * bags_per_table + 1 entries")
+        return nb // len(self.tables)
+
+    def _buffer(self, t: torch.Tensor | None, name: str, dtype: torch.dtype, numel: int) -> torch.Tensor:
+        if t is None:
+            return torch.empty(numel, dtype=dtype, device=self.device)
+        if t.dtype != dtype or t.device != self.device or t.numel() != numel or not t.is_contiguous():
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"{name} must be a contiguous {dtype} buffer of {numel} elements on {self.device}")
+        return t
+
+    def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
+                    found: torch.Tensor | None = None, located: torch.Tensor | None = None, weights: torch.Tensor | None = None,
+                    out_dtype: torch.dtype = torch.float32, insert_missing: bool = False):
+        """LookupTable.find_pooled of every member with its bags, in one launch -> (views, per-key found mask): views[j] is member j's
+        [bags_per_table, dim_j] view of the flat class-major buffer (`out`, or a fresh one: views[j]._base).  located (optional int64[n]
+        buffer) receives the located rows for apply_pooled(located=...) of the same step.  insert_missing: absent keys are created in their
+        member first (initial row / state); found = present before the call."""
+        if weights is not None:
+            raise ValueError("a mixed group has no weighted bags (per_sample_weights): use one TableGroup per width")
+        if mode not in ("sum", "mean"):
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"mode must be 'sum' or 'mean' (got {mode!r})")
+        dt = _out_dtype(out_dtype, out)
+        bpt = self._check_bags(bag_offsets)
+        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        if k.numel() and bpt == 0:
+            raise MeepoError(_lib.ERR_INVALID_ARG, "there are keys but no bags: no bag would report them")
+        total = mixed_layout(self.dims, bpt)[2]
+        out = self._buffer(out, "out", out_dtype, total)
+        found = self._buffer(found, "found", torch.uint8, k.numel())
+        if located is not None:
+            located = self._buffer(located, "located", torch.int64, k.numel())
+        check(_lib.lib().mee_mixed_group_find_pooled(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, found.data_ptr(),
+                                                     located.data_ptr() if located is not None else None, {"sum": 0, "mean": 1}[mode],
+                                                     int(bool(insert_missing)), _stream_ptr(self.device)))
+        return self.views(out.view(-1), bpt), found
+
+    def apply_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, bag_grads: torch.Tensor, bag_of_position: torch.Tensor,
+                     optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1,
+                     located: torch.Tensor | None = None) -> None:
+        """Backward of find_pooled: one optimizer step, position i takes the row of bag bag_of_position[i] (its index in the caller's order)
+        of bag_grads — a flat fp32 buffer in the lookup's class-major layout.  located = the buffer the forward of this step filled."""
+        if optimizer not in ("adagrad", "adam"):
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"optimizer must be 'adagrad' or 'adam' (got {optimizer!r})")
+        bpt = self._check_bags(bag_offsets)
+        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        gi = self.tables[0]._grad_index(bag_of_position, k.numel())
+        g = self._buffer(bag_grads.contiguous(), "bag_grads", torch.float32, mixed_layout(self.dims, bpt)[2])
+        if located is not None:
+            located = self._buffer(located, "located", torch.int64, k.numel())
+        L, s = _lib.lib(), _stream_ptr(self.device)
+        loc = located.data_ptr() if located is not None else None
+        if optimizer == "adagrad":
+            check(L.mee_mixed_group_apply_adagrad_pooled(self._h, k.data_ptr(), bag_offsets.data_ptr(), bpt, g.data_ptr(), gi.data_ptr(), loc, k.numel(),
+                                                         lr, 1e-10 if eps is None else eps, s))
+        else:
+            check(L.mee_mixed_group_apply_adam_pooled(self._h, k.data_ptr(), bag_offsets.data_ptr(), bpt, g.data_ptr(), gi.data_ptr(), loc, k.numel(),
+                                                      lr, beta1, beta2, 1e-8 if eps is None else eps, step, s))
+
+
 def hash_batch(keys: torch.Tensor, n_buckets: int, n_shards: int):
     """SPEC.md §1 on device: (mix64, bucket, owner) as int64/int64/int32 tensors (bit patterns of the unsigned values)."""
     k = keys.contiguous().view(-1)
