@@ -9,7 +9,7 @@ import __graft_entry__
 
 __graft_entry__.build()
 from meepoembedding_amd import INIT_UNIFORM, OPT_ADAGRAD, LookupTable, _lib  # noqa: E402
-from meepoembedding_amd.nn import DynamicEmbedding  # noqa: E402
+from meepoembedding_amd.nn import DynamicEmbedding, DynamicEmbeddingBag  # noqa: E402
 from meepoembedding_amd.tiered import TieredLookupTable  # noqa: E402
 
 dev = torch.device("cuda", 0)
@@ -44,3 +44,14 @@ tiered.insert(keys, rows)                                   # 50K new keys > the
 for _ in range(8):
     tiered.find(keys[torch.randint(0, 5000, (20_000,), device=dev)])   # a hot working set of 5000 keys
 print("rebalance (promoted, demoted):", tiered.rebalance(), "| hot", hot.size(), "cold", cold.size())
+
+# 4. embedding bags over the pair: one launch probes both tiers per position; the backward is the sparse Adagrad step on both tiers
+hot_t = LookupTable(1 << 16, 64, device=dev, max_batch=1 << 16, optimizer=OPT_ADAGRAD, initializer=INIT_UNIFORM, init_scale=0.05)
+cold_t = LookupTable(1 << 20, 64, device=dev, max_batch=1 << 16, optimizer=OPT_ADAGRAD, initializer=INIT_UNIFORM, init_scale=0.05,
+                     value_memory=_lib.MEM_HOST_PINNED)
+bags = DynamicEmbeddingBag(TieredLookupTable(hot_t, cold_t, hot_key_limit=8192), mode="mean", lr=0.05, create_missing=True).to(dev).train()
+bag_ids = keys[torch.randint(0, 5000, (4096,), device=dev)]                  # ids no tier has seen: created on the way, hot while there is room
+offsets = torch.arange(0, 4097, 8, dtype=torch.int64, device=dev)           # 512 bags of 8
+pooled = bags(bag_ids, offsets)
+pooled.square().mean().backward()
+print("bag layer output", tuple(pooled.shape), "| hot", hot_t.size(), "cold", cold_t.size())

@@ -208,6 +208,20 @@ int mee_find_pooled_weighted(const mee_table* t, const int64_t* d_keys, size_t n
 int mee_pooled_weighted_backward(const mee_table* t, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,
                                  size_t n_bags, const float* d_weights, const float* d_bag_grads, float* d_grads_out, float* d_weight_grads_out,
                                  void* stream);
+/* Pooled lookup over a hot/cold PAIR of tables (a key lives in exactly one of them; meepoembedding_amd/tiered.py): mee_find_pooled on the
+ * union, bit for bit — the rows of a bag's positions added in position order in fp32 (the first copied, each later one added, no fma),
+ * MEE_POOL_MEAN divides by (float)length, an empty bag gives zeros, offsets past n are cut at n, a decreasing pair is an empty bag.  The
+ * row of a position is the hot table's if `hot` holds the key, else the cold table's if `cold` holds it, else a row of HOT's default_value
+ * (reserved keys too); d_found[i] (nullable: not written) = 1 iff either table holds d_keys[i].  d_out = [n_bags, dim] fp32, or bf16
+ * (out_dtype = MEE_DTYPE_BF16, 8-byte aligned: the finished bag row rounded once).  flags: MEE_TIER_COUNT_COLD adds 1 to the cold table's
+ * hit counter for every position found there, MEE_TIER_COUNT_HOT the same for the hot table (meant for sampled calls); each needs its
+ * table created with MEE_FLAG_TRACK_HITS.  ONE launch that probes both tables per position, no host synchronisation, capturable like
+ * mee_find_pooled; `cold` may be a MEE_MEM_HOST_PINNED table (its rows are read over PCIe by the same launch).  MEE_ERR_INVALID_ARG: a
+ * null table, hot == cold, different devices or dims, unknown flag bits, a count flag without the counters, an unknown out_dtype / mode,
+ * a misaligned bf16 d_out.  n_bags == 0 writes nothing; bags over n == 0 keys are empty bags. */
+enum { MEE_TIER_COUNT_COLD = 1, MEE_TIER_COUNT_HOT = 2 };
+int mee_find_pooled_tiered(const mee_table* hot, const mee_table* cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
+                           void* d_out, uint32_t out_dtype, uint8_t* d_found /* nullable: not written */, int mode, uint32_t flags, void* stream);
 /* upsert; duplicate keys: last occurrence wins. */
 int mee_insert(mee_table* t, const int64_t* d_keys, const float* d_values, size_t n, void* stream);
 /* overwrite only if present; d_found nullable; duplicates: last occurrence wins. */

@@ -25,6 +25,7 @@ HANDLE_SLOT_MASK = (1 << 40) - 1   # a located-find handle: bits 0..39 the slot 
 MEM_HBM, MEM_HOST_PINNED = 0, 1
 DTYPE_F32, DTYPE_BF16 = 0, 1   # MEE_DTYPE_*: the row type of a typed-output lookup (mee_*_as)
 FLAG_TRACK_HITS, FLAG_ADMISSION = 1, 2
+TIER_COUNT_COLD, TIER_COUNT_HOT = 1, 2   # mee_find_pooled_tiered flags
 ABI_VERSION = 2   # MEE_ABI_VERSION of include/meepo_embedding.h this loader was written against
 EMPTY_KEY = -(1 << 63)
 RECLAIMED_KEY = EMPTY_KEY + 1
@@ -130,6 +131,7 @@ PROTOTYPES = {
     "mee_mixed_group_set_tuning": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "mee_find_pooled": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, C.c_int, _vp]),
     "mee_find_pooled_weighted": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "mee_find_pooled_tiered": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, C.c_int, _u32, _vp]),   # a hot/cold pair (tiered.py)
     "mee_pooled_weighted_backward": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "mee_group_find_pooled_weighted": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "mee_group_pooled_weighted_backward": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),

@@ -186,6 +186,83 @@ __device__ __forceinline__ void pooled_fetch(const int64_t* __restrict__ tkeys, 
     }
 }
 
+// The cold table of a hot/cold pair (mee_find_pooled_tiered), as the pooled kernel receives it beside the hot table's own planes.
+struct TierArgs {
+    const int64_t* tkeys;    // the cold index (HBM)
+    const float4* values;    // the cold rows: device-mapped pinned host memory for a cold tier, read with plain loads (as find_missing_kernel does)
+    uint64_t nb;
+    uint32_t* hot_hits;      // per-slot hit counters of the two tables; null = that tier's hits are not counted
+    uint32_t* cold_hits;
+};
+
+// pooled_fetch over a hot/cold pair: the row of a position is the hot table's if the hot table holds the key, else the cold table's if that
+// one does, else def4 (the HOT table's default row); found = either tier holds it.  The U hot bucket lines are requested back to back and
+// probed as in pooled_fetch; then ONE wave-uniform decision: a wave whose positions were all served by the hot table (the working set of a
+// well-placed pair) pays that ballot and runs pooled_fetch's row loads.  Otherwise the cold index is probed for the positions the hot probe
+// missed — by all 64 lanes in convergent control flow, tiles without a miss pass act = false — and each row is loaded from the plane that
+// holds it (one load per row: the address is selected, not the data).  Counting (nullable counters, wave-uniform branches): one atomicAdd
+// per found position by the tile's first lane, as find_kernel (NT & 16) and find_missing_kernel (FLAGS & 2) do it.
+template <int DIM4, int U, int C>
+__device__ __forceinline__ void pooled_fetch_tiered(const int64_t* __restrict__ tkeys, const float4* __restrict__ values, uint64_t nb,
+                                                    const TierArgs& cold, uint32_t dim4, const int64_t (&key)[U], const uint64_t (&pos)[U],
+                                                    const bool (&inb)[U], int tile, int tl, float4 def4, float4 (&row)[U][C],
+                                                    uint8_t* __restrict__ found) {
+    int64_t slot[U], kb[U];
+    uint64_t bk[U];
+    bool act[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        act[u] = inb[u] && !reserved_key(key[u]);
+        bk[u] = bucket_of(key[u], nb);
+        kb[u] = act[u] ? tkeys[bk[u] * kW + tl] : kEmpty;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) slot[u] = tile_probe(tkeys, nb, key[u], act[u], bk[u], kb[u], tile, tl);
+    bool missed = false;
+#pragma unroll
+    for (int u = 0; u < U; ++u) missed = missed || (act[u] && slot[u] < 0);
+    if (!__any(missed)) {   // wave-uniform: nothing for the cold tier
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+                if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4)
+                    row[u][c] = slot[u] >= 0 ? values[(uint64_t)slot[u] * dim4 + c * 16 + tl] : def4;
+            if (found && inb[u] && tl == 0) found[pos[u]] = slot[u] >= 0;
+        }
+    } else {
+        int64_t cslot[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            act[u] = act[u] && slot[u] < 0;   // from here on: the positions the cold index is asked about
+            bk[u] = bucket_of(key[u], cold.nb);
+            kb[u] = act[u] ? cold.tkeys[bk[u] * kW + tl] : kEmpty;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) cslot[u] = tile_probe(cold.tkeys, cold.nb, key[u], act[u], bk[u], kb[u], tile, tl);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const bool hit = slot[u] >= 0 || cslot[u] >= 0;
+            const float4* src = slot[u] >= 0 ? values + (uint64_t)slot[u] * dim4 : cold.values + (uint64_t)(cslot[u] >= 0 ? cslot[u] : 0) * dim4;
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+                if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4)
+                    row[u][c] = hit ? src[c * 16 + tl] : def4;
+            if (found && inb[u] && tl == 0) found[pos[u]] = hit;
+        }
+        if (cold.cold_hits) {   // wave-uniform
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (cslot[u] >= 0 && tl == 0) atomicAdd(&cold.cold_hits[cslot[u]], 1u);
+        }
+    }
+    if (cold.hot_hits) {   // wave-uniform (sampled calls)
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (slot[u] >= 0 && tl == 0) atomicAdd(&cold.hot_hits[slot[u]], 1u);
+    }
+}
+
 // ---- bf16 output of the lookups (SPEC.md §3 "Output type") ------------------------------------------------------------------
 // A lane that holds a float4 of a row stores it as 4 bf16 = 8 bytes; a row of dim bf16 is dim4 such 8-byte groups, so group g of
 // output row i sits at index i * dim4 + g of a u32x2 array — the SAME index the fp32 kernels use on their f32x4 array.

@@ -272,7 +272,10 @@ __device__ __forceinline__ bool jagged_member(const uint64_t* __restrict__ membe
 // The loop body below has a COPY in mixed_bags (meepo_mixed.hip: the group whose members differ in dim; only the member lookup and the output
 // index differ there).  SPEC.md §3 defines the mixed group's result through this kernel's, so a change to the order of the additions, the
 // mean's division, the long-bag rule or the clamping of the offsets here has to be made there too (tests/test_mixed_groups.py compares them).
-template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false, bool JAGGED = false>
+// TIERED (mee_find_pooled_tiered; one hot/cold pair, unweighted): the table arguments are the HOT table's, `tier` brings the cold one — the
+// fetch step probes both per position (pooled_fetch_tiered, meepo_device.h); the accumulation below is the same code.  The instances with
+// TIERED = false never read `tier` and are the code they were before the parameter existed.
+template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false, bool JAGGED = false, bool TIERED = false>
 __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restrict__ tkeys_, const float4* __restrict__ values_,
                                                           uint64_t nb_, const int64_t* __restrict__ keys,
                                                           const uint64_t* __restrict__ offsets, uint64_t n_bags,
@@ -281,8 +284,9 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                                                           uint64_t bags_per_table = 1, int64_t* __restrict__ located = nullptr,
                                                           uint64_t n_keys = ~0ull, const float* __restrict__ weights = nullptr,
                                                           int64_t handle_tag = 0, const uint64_t* __restrict__ member_bags = nullptr,
-                                                          uint32_t n_members = 0) {
+                                                          uint32_t n_members = 0, TierArgs tier = {}) {
     static_assert(!JAGGED || (GROUPED && !WEIGHTED && !BF16), "the jagged map is the group's plain fp32 lookup");
+    static_assert(!TIERED || (!GROUPED && !WEIGHTED && !JAGGED), "the tiered form is one pair's plain sum / mean");
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
@@ -331,8 +335,9 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                     kv[u] = __shfl(kpre, tile * 16 + (int)((pos[u] - begin) & 15));
                     if constexpr (WEIGHTED) wv[u] = __shfl(wpre, tile * 16 + (int)((pos[u] - begin) & 15));
                 }
-                pooled_fetch<DIM4, U, C, TAGGED>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located,
-                                                 GROUPED ? member << kGroupSlotBits : (TAGGED ? (uint64_t)handle_tag : 0));
+                if constexpr (TIERED) pooled_fetch_tiered<DIM4, U, C>(tkeys, values, nb, tier, dim4, kv, pos, inb, tile, tl, def4, row, found);
+                else pooled_fetch<DIM4, U, C, TAGGED>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located,
+                                                      GROUPED ? member << kGroupSlotBits : (TAGGED ? (uint64_t)handle_tag : 0));
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     if (!inb[u]) continue;
@@ -389,8 +394,9 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                     pos[u] = i + (uint64_t)u * 4 + tile; inb[u] = pos[u] < eq; kv[u] = inb[u] ? keys[pos[u]] : kEmpty;
                     if constexpr (WEIGHTED) wv[u] = inb[u] ? weights[pos[u]] : 0.f;   // next to the key
                 }
-                pooled_fetch<DIM4, U, C, TAGGED>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located,
-                                                 GROUPED ? member << kGroupSlotBits : (TAGGED ? (uint64_t)handle_tag : 0));
+                if constexpr (TIERED) pooled_fetch_tiered<DIM4, U, C>(tkeys, values, nb, tier, dim4, kv, pos, inb, tile, tl, def4, row, found);
+                else pooled_fetch<DIM4, U, C, TAGGED>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located,
+                                                      GROUPED ? member << kGroupSlotBits : (TAGGED ? (uint64_t)handle_tag : 0));
 #pragma unroll
                 for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -808,7 +814,7 @@ static int find_pooled_common(const mee_table* t, const int64_t* d_keys, size_t 
     with_pooled_shape(t->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(d_weights != nullptr, [&](auto weighted) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
         auto launch = [&](auto kernel) {
             kernel<<<grid, 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, t->default_value, t->dim4,
-                                         mode == MEE_POOL_MEAN, nullptr, 1, weighted ? d_located_out : nullptr, n, d_weights, weighted ? tag : 0, nullptr, 0);
+                                         mode == MEE_POOL_MEAN, nullptr, 1, weighted ? d_located_out : nullptr, n, d_weights, weighted ? tag : 0, nullptr, 0, TierArgs{});
         };
         launch(find_pooled_kernel<d4, u, bpw, false, weighted, bf16>);
     }); }); });
@@ -841,6 +847,34 @@ int mee_find_pooled_as(const mee_table* t, const int64_t* d_keys, size_t n, cons
     if (d_weights && mode != MEE_POOL_SUM) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: weighted pooling is MEE_POOL_SUM only");
     if (d_located_out && !d_weights) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: d_located_out is the weighted form's output (pass weights of 1.0f for a plain sum)");
     return find_pooled_common(t, d_keys, n, d_bag_offsets, n_bags, d_weights, d_out, out_dtype, d_found, d_located_out, mode, stream);
+}
+
+// the pooled lookup of a hot/cold pair: find_pooled_kernel's TIERED instances, the hot table in the table arguments, the cold one in TierArgs
+int mee_find_pooled_tiered(const mee_table* hot, const mee_table* cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
+                           void* d_out, uint32_t out_dtype, uint8_t* d_found, int mode, uint32_t flags, void* stream) {
+    MEE_RANGE("mee_find_pooled_tiered");
+    if (!hot || !cold || (n_bags && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: null argument");
+    if (hot == cold) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: hot and cold are the same table (a key lives in exactly one tier)");
+    if (hot->device != cold->device || hot->dim != cold->dim)
+        return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: the tiers differ in device (%d, %d) or dim (%u, %u)", hot->device, cold->device, hot->dim, cold->dim);
+    if (flags & ~(uint32_t)(MEE_TIER_COUNT_COLD | MEE_TIER_COUNT_HOT)) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: unknown flag bits 0x%x", flags);
+    if (((flags & MEE_TIER_COUNT_COLD) && !cold->hits) || ((flags & MEE_TIER_COUNT_HOT) && !hot->hits))
+        return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: a count flag needs that tier created with MEE_FLAG_TRACK_HITS");
+    if (int rc = check_out_dtype(d_out, out_dtype, "mee_find_pooled_tiered")) return rc;
+    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
+    if (n_bags == 0) return MEE_OK;
+    DeviceGuard g(hot->device);
+    hipStream_t st = as_stream(stream);
+    const TierArgs tier{cold->keys, (const float4*)cold->values, cold->nb, (flags & MEE_TIER_COUNT_HOT) ? hot->hits : nullptr,
+                        (flags & MEE_TIER_COUNT_COLD) ? cold->hits : nullptr};
+    with_pooled_shape(hot->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
+        constexpr int ut = (bpw == 1 && u > 2) ? 2 : u;   // a wave per bag at dim 64: two keys in flight per tile — 66 VGPRs / 7 waves where the one-table kernel's four take 93 / 5 here, at the same measured time (profiles/tiered_bags.md)
+        find_pooled_kernel<d4, ut, bpw, false, false, bf16, false, true><<<grid, 256, 0, st>>>(
+            hot->keys, (const float4*)hot->values, hot->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, hot->default_value, hot->dim4,
+            mode == MEE_POOL_MEAN, nullptr, 1, nullptr, n, nullptr, 0, nullptr, 0, tier);
+    }); });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
 }
 
 int mee_pooled_weighted_backward(const mee_table* t, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,
@@ -879,7 +913,7 @@ static int group_find_pooled_common(mee_group* g, const int64_t* d_keys, size_t 
     with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(d_weights != nullptr, [&](auto weighted) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
         auto launch = [&](auto kernel) {
             kernel<<<grid, 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, mode == MEE_POOL_MEAN, g->d_desc, bags_per_table,
-                                         d_located_out, n, d_weights, 0, nullptr, 0);
+                                         d_located_out, n, d_weights, 0, nullptr, 0, TierArgs{});
         };
         launch(find_pooled_kernel<d4, u, bpw, true, weighted, bf16>);
     }); }); });

@@ -29,11 +29,12 @@ _LAYERS: "weakref.WeakValueDictionary[int, DynamicEmbedding]" = weakref.WeakValu
 _IDS = itertools.count(1)
 
 
-def _check_out_dtype(table, out_dtype: torch.dtype) -> torch.dtype:
-    """A layer's out_dtype: fp32, or bf16 where the table's lookups can write it (LookupTable, TableGroup).  Refused at construction."""
+def _check_out_dtype(table, out_dtype: torch.dtype, pooled: bool = False) -> torch.dtype:
+    """A layer's out_dtype: fp32, or bf16 where the table's lookups can write it (LookupTable, TableGroup; pooled = a bag layer, whose lookup is
+    find_pooled: also a TieredLookupTable, which pools to bf16 while its find returns fp32 rows).  Refused at construction."""
     if out_dtype not in (torch.float32, torch.bfloat16):
         raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16 (got {out_dtype})")
-    if out_dtype != torch.float32 and not getattr(table, "supports_out_dtype", False):
+    if out_dtype != torch.float32 and not (getattr(table, "supports_out_dtype", False) or (pooled and getattr(table, "supports_pooled_out_dtype", False))):
         raise ValueError(f"{type(table).__name__} has no bf16 lookup (tiered, sharded and peer-mapped tables return fp32 rows): use out_dtype=torch.float32 and "
                          "cast in the model")
     return out_dtype
@@ -419,10 +420,10 @@ lookup_jagged.register_autograd(_backward_jagged, setup_context=_setup_jagged)
 
 
 class _SparseOptimizerSettings:
-    def _init_settings(self, optimizer, lr, eps, betas, table=None, out_dtype: torch.dtype = torch.float32):
+    def _init_settings(self, optimizer, lr, eps, betas, table=None, out_dtype: torch.dtype = torch.float32, pooled: bool = False):
         if optimizer not in ("adagrad", "adam"):
             raise ValueError("optimizer must be 'adagrad' or 'adam'")
-        self.out_dtype = _check_out_dtype(table, out_dtype)
+        self.out_dtype = _check_out_dtype(table, out_dtype, pooled)
         self.optimizer, self.lr, self.betas = optimizer, lr, betas
         self.eps = eps if eps is not None else (1e-10 if optimizer == "adagrad" else 1e-8)
         self.step = 0
@@ -464,7 +465,7 @@ class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
         if mode not in ("sum", "mean"):
             raise ValueError("mode must be 'sum' or 'mean'")
         self.table, self.mode, self.create_missing = table, mode, create_missing
-        self._init_settings(optimizer, lr, eps, betas, table, out_dtype)
+        self._init_settings(optimizer, lr, eps, betas, table, out_dtype, pooled=True)
 
     def forward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, per_sample_weights: torch.Tensor | None = None) -> torch.Tensor:
         """per_sample_weights (fp32 [n], mode "sum" only): the bag is the sum of w_i * row_i; backward also yields their grad.
@@ -478,8 +479,8 @@ class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
             return lookup_pooled(keys, bag_offsets, self._anchor, self.table_id, self.mode == "mean")[0]
         if self.mode != "sum":
             raise ValueError("per_sample_weights are only supported for mode='sum', as in torch.nn.EmbeddingBag")
-        if not getattr(self.table, "weighted_bags", True):   # (a ShardedTableGroup) refused on every rank alike, before anything is exchanged
-            raise ValueError(f"{type(self.table).__name__} has no weighted bags: per_sample_weights are not offered over a sharded group")
+        if not getattr(self.table, "weighted_bags", True):   # (a ShardedTableGroup: refused on every rank alike, before anything is exchanged; a TieredLookupTable)
+            raise ValueError(f"{type(self.table).__name__} has no weighted bags: per_sample_weights are not offered over a sharded group or a hot/cold pair")
         return lookup_pooled_weighted(keys, bag_offsets, per_sample_weights, self._anchor, self.table_id)[0]
 
 

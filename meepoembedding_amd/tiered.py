@@ -18,6 +18,9 @@ Design (host logic only; every row still moves through the HIP kernels):
     per-batch scratch with the step's operators and read rows the next update writes), so they are ordered with them, not beside them.
   * in a training loop (`rebalance_every` = K): the pair runs `rebalance()` itself behind every K-th optimizer step — the
     forward lookups of those K steps are the observation window.
+  * embedding bags (`find_pooled`): ONE launch that probes both tiers per position (mee_find_pooled_tiered) — a bag is summed in
+    position order and hot and cold keys interleave inside it, so two pooled passes, one per tier, could not rebuild the result bit
+    for bit.  The launch feeds the policy's counters like `find` does (cold hits always, hot hits on every sample_every-th call).
 
 `hot` / `cold` are any objects with the LookupTable methods, so the logic also runs on the CPU test adapters.
 """
@@ -26,12 +29,38 @@ from __future__ import annotations
 import torch
 
 
+def _pool_rows(rows: torch.Tensor, bag_offsets: torch.Tensor, mode: str) -> torch.Tensor:
+    """SPEC.md §3 find_pooled given find's rows [n, dim]: per bag fp32 additions in position order (the first row copied, each later one
+    added), 'mean' divides by (float)length, an empty bag is zeros; offsets past n are cut at n, a decreasing pair is an empty bag.
+    Only the path of tiers that are not native tables takes it (the native pair pools inside its one launch)."""
+    n = rows.shape[0]
+    off = bag_offsets.to(torch.int64)
+    end = off[1:].clamp(0, n)
+    begin = torch.minimum(off[:-1].clamp(min=0), end)
+    lens = end - begin
+    out = torch.zeros((lens.numel(), rows.shape[1]), dtype=torch.float32, device=rows.device)
+    for j in range(int(lens.max()) if lens.numel() else 0):
+        m = lens > j
+        r = rows[begin[m] + j]
+        out[m] = r if j == 0 else out[m] + r
+    if mode == "mean":
+        nz = lens > 0
+        out[nz] = out[nz] / lens[nz].to(torch.float32)[:, None]
+    return out
+
+
 class TieredLookupTable:
+    weighted_bags = False   # no per_sample_weights over the pair (nn.DynamicEmbeddingBag refuses them)
+
     def __init__(self, hot, cold, hot_key_limit: int | None = None, sample_every: int = 8, promote_threshold: int = 2,
                  rebalance_every: int = 0, rebalance_max_moves: int = 1 << 20):
         if hot.dim != cold.dim:
             raise ValueError("hot and cold tables must have the same dim")
         self.hot, self.cold, self.dim = hot, cold, hot.dim
+        # find_pooled can write bf16 bag rows (a bag layer may ask for them); find / find_or_insert return fp32 rows, so there is no
+        # supports_out_dtype.  An instance attribute only because tests/test_bf16_out.py makes a pair with __new__ (no __init__) and expects
+        # the bag layer to refuse bf16 over it: on the class, that object would be accepted
+        self.supports_pooled_out_dtype = True
         self.optimizer = getattr(hot, "optimizer", 0)
         # keep the hot table at a load it probes fast at (SPEC.md §2: probe length grows with load)
         self.hot_key_limit = int(hot_key_limit if hot_key_limit is not None else getattr(hot, "capacity", 0) * 0.75)
@@ -68,6 +97,61 @@ class TieredLookupTable:
         else:
             out, found = self.hot.find(keys)
         self.cold.find_counted(keys, out, found, missing_only=True)  # cold hits are always counted (they are PCIe-bound anyway)
+        return out, found
+
+    def _native(self) -> bool:
+        from .table import LookupTable
+        return isinstance(self.hot, LookupTable) and isinstance(self.cold, LookupTable)
+
+    def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
+                    found: torch.Tensor | None = None, insert_missing: bool = False, out_dtype: torch.dtype = torch.float32):
+        """Embedding-bag lookup over the pair (SPEC.md §3 find_pooled on the union): bag b = keys[bag_offsets[b]:bag_offsets[b+1]] ->
+        ([n_bags, dim] sums or means in position order, per-key found mask).  An absent key reads the HOT table's default row, as in find.
+        Two native tables: one launch (mee_find_pooled_tiered), which also feeds the placement policy's hit counters.
+        insert_missing: absent keys are created first, in the tier find_or_insert would pick; `found` stays "present before the call".
+        out_dtype=torch.bfloat16: the finished bag row is rounded once."""
+        if mode not in ("sum", "mean"):
+            raise ValueError(f"mode must be 'sum' or 'mean' (got {mode!r})")
+        if not self._native():   # any objects with the LookupTable methods: their find, pooled here in position order
+            if out_dtype not in (torch.float32, torch.bfloat16):
+                raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16 (got {out_dtype})")
+            flat = keys.contiguous().view(-1)
+            rows, fnd = self.find_or_insert(flat) if insert_missing else self.find(flat)
+            pooled = _pool_rows(rows, bag_offsets, mode).to(out_dtype)
+            if out is not None:
+                out.copy_(pooled)
+            if found is not None:
+                found.copy_(fnd)
+            return (out if out is not None else pooled), (found if found is not None else fnd)
+        from . import _lib
+        from .table import _n_bags, _out_dtype
+        hot, cold = self.hot, self.cold
+        dt = _out_dtype(out_dtype, out)
+        k = hot._keys(keys) if keys.numel() else keys
+        n = k.numel()
+        n_bags = _n_bags(bag_offsets, hot.device)
+        if out is None:
+            out = torch.empty((n_bags, self.dim), dtype=out_dtype, device=hot.device)
+        if found is None:
+            found = torch.empty(n, dtype=torch.uint8, device=hot.device)
+        if insert_missing and n:
+            # the found mask alone, from a probe of both indexes (no row is read, nothing is written to a table) ...
+            found.copy_(hot.locate(k)[1] | cold.locate(k)[1])
+            # ... then the absent keys are created exactly as find_or_insert creates them (their rows land in a scratch nobody reads)
+            rows = torch.empty((n, self.dim), dtype=torch.float32, device=hot.device)
+            if self._room_for(n):
+                hot.find_or_insert_missing(k, rows, found)
+                self._hot_keys_ub += n
+            else:
+                cold.find_or_insert_missing(k, rows, found)
+        flags = 0
+        if self.policy:
+            self._calls += 1
+            flags = _lib.TIER_COUNT_COLD | (_lib.TIER_COUNT_HOT if self._calls % self.sample_every == 0 else 0)
+        # with insert_missing the launch writes no found bytes: `found` keeps meaning "present before the call", also for a key repeated in the batch
+        _lib.check(_lib.lib().mee_find_pooled_tiered(hot._h, cold._h, k.data_ptr(), n, bag_offsets.data_ptr(), n_bags, out.data_ptr(), dt,
+                                                     None if (insert_missing and n) else found.data_ptr(), {"sum": 0, "mean": 1}[mode], flags,
+                                                     hot._s()))
         return out, found
 
     def rebalance(self, max_moves: int = 1 << 20) -> tuple[int, int]:
@@ -132,16 +216,19 @@ class TieredLookupTable:
             p, d = self.rebalance(self.rebalance_max_moves)
             self.rebalance_log.append((self._train_steps, int(p), int(d)))
 
-    def apply_adagrad(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10) -> None:
-        # a key lives in one tier and each table ignores keys it does not hold: both see the whole batch
-        self.hot.apply_adagrad(keys, grads, lr, eps)
-        self.cold.apply_adagrad(keys, grads, lr, eps)
+    def apply_adagrad(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10, grad_index: torch.Tensor | None = None) -> None:
+        # a key lives in one tier and each table ignores keys it does not hold: both see the whole batch.  grad_index (one int per key: position i
+        # takes row grad_index[i] of grads — a pooled lookup's bag) goes to both as well; a key's duplicates are reduced in the one tier that holds it
+        kw = {} if grad_index is None else {"grad_index": grad_index}
+        self.hot.apply_adagrad(keys, grads, lr, eps, **kw)
+        self.cold.apply_adagrad(keys, grads, lr, eps, **kw)
         self._after_optimizer_step()
 
     def apply_adam(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999,
-                   eps: float = 1e-8, step: int = 1) -> None:
-        self.hot.apply_adam(keys, grads, lr, beta1, beta2, eps, step)
-        self.cold.apply_adam(keys, grads, lr, beta1, beta2, eps, step)
+                   eps: float = 1e-8, step: int = 1, grad_index: torch.Tensor | None = None) -> None:
+        kw = {} if grad_index is None else {"grad_index": grad_index}
+        self.hot.apply_adam(keys, grads, lr, beta1, beta2, eps, step, **kw)
+        self.cold.apply_adam(keys, grads, lr, beta1, beta2, eps, step, **kw)
         self._after_optimizer_step()
 
     # duplicate reductions touch no table row, only a table's per-batch scratch: the hot table lends its own
