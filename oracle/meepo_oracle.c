@@ -404,22 +404,26 @@ uint64_t meo_dedup_sum(const int64_t* keys, const float* grads, size_t n, uint32
     if (gmap_init(&g, n)) return 0;
     double* acc = (double*)calloc((n ? n : 1) * (size_t)dim, sizeof(double));
     uint32_t* cnt = (uint32_t*)calloc(n ? n : 1, sizeof(uint32_t));
+    size_t* first = (size_t*)calloc(n ? n : 1, sizeof(size_t));   /* the position of a key's first occurrence */
     uint64_t U = 0;
     for (size_t i = 0; i < n; ++i) {
         if (reserved(keys[i])) { if (inverse) inverse[i] = -1; continue; }
         int fresh; int64_t* cell = gmap_get(&g, keys[i], &fresh);
-        if (fresh) { *cell = (int64_t)U; uniq[U] = keys[i]; ++U; }
+        if (fresh) { *cell = (int64_t)U; uniq[U] = keys[i]; first[U] = i; ++U; }
         int64_t u = *cell;
         if (inverse) inverse[i] = u;
         cnt[u]++;
         if (grads) for (uint32_t j = 0; j < dim; ++j) acc[u * dim + j] += (double)grads[i * dim + j];
     }
     if (grads && gsum)
-        for (uint64_t u = 0; u < U; ++u)
+        for (uint64_t u = 0; u < U; ++u) {
+            /* SPEC 4: a key that occurs once uses its grad row unchanged: a copy, so that a -0 keeps its sign (the sum would make it
+               0.0 + -0.0 = +0.0).  Two or more occurrences are summed from +0.0: a group of -0 alone gives +0. */
+            if (cnt[u] == 1) { memcpy(gsum + u * dim, grads + first[u] * dim, dim * sizeof(float)); continue; }
             for (uint32_t j = 0; j < dim; ++j) gsum[u * dim + j] = (float)acc[u * dim + j];
-    /* single-occurrence keys: (float)(double)x == x, so "grad row unchanged" holds automatically */
+        }
     if (counts) memcpy(counts, cnt, U * sizeof(uint32_t));
-    free(acc); free(cnt); gmap_free(&g);
+    free(acc); free(cnt); free(first); gmap_free(&g);
     return U;
 }
 

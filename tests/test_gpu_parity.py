@@ -1,7 +1,6 @@
 """GPU parity: every operator of the HIP backend through the C-ABI vs the CPU oracle on the same seeded inputs.
 Bar: bit-exact for hashing / found-masks / copied rows / size / key-sorted export; ≤1e-6 relative (atol 1e-9) for
 fp32 optimizer state (SPEC.md §4)."""
-import functools
 import json
 import os
 
@@ -10,6 +9,7 @@ import pytest
 import torch
 
 import oracle
+from _apply_cases import EXTREME_CASES, bucketed_apply_extremes, every_group_size_batch, keys_of_apply_bucket_zero
 from meepoembedding_amd import _lib
 from meepoembedding_amd import (INIT_UNIFORM, OPT_ADAGRAD, OPT_ADAM, STATUS_RESERVED_KEY, STATUS_TABLE_FULL, LookupTable,
                                 MeepoError, Router, hash_batch, synth)
@@ -443,34 +443,15 @@ def test_optimizer_every_group_size(dev, opt, dim, layout):
     keeps a key's occurrences adjacent (one block of the grouping kernel sees them all), 'spread' puts them 1031 positions apart
     (every occurrence in another block), 'mixed' does both at random.  Plain, located and indexed applies must all match the oracle."""
     rng = np.random.default_rng(7 + dim)
-    sizes = list(range(1, 45)) + [64, 65, 100, 333, 2100]
-    n_keys = len(sizes) * 3
-    keys = synth.keys_np(123, 0, n_keys + 500); rows = synth.rows_np(keys, dim, 2)
-    reps = np.array(sizes * 3)
-    bk = np.repeat(keys[:n_keys], reps)
-    filler = keys[n_keys:n_keys + 400]                       # single keys between the groups
-    n = 1031 * ((bk.size + filler.size) // 1031 + 1)
-    batch = np.full(n, oracle.EMPTY_KEY, dtype=np.int64)    # padding where nothing lands
-    if layout == "clustered":
-        order = np.arange(bk.size)
-    elif layout == "spread":
-        k = np.arange(bk.size)
-        order = (k % (n // 1031)) * 1031 + k // (n // 1031)  # neighbours in bk land 1031 positions apart
-        assert np.unique(order).size == bk.size
-    else:
-        order = rng.permutation(n)[:bk.size]
-        half = rng.random(bk.size) < 0.5                     # half of the occurrences stay next to their neighbours
-        order[half] = np.sort(order[half])
-    batch[order] = bk
-    free = np.flatnonzero(batch == oracle.EMPTY_KEY)
-    batch[free[:filler.size]] = filler
+    keys, rows, filler, batch = every_group_size_batch(rng, dim, layout)     # (tests/_apply_cases.py)
+    n = batch.size
     kind, okind = (OPT_ADAGRAD, oracle.OPT_ADAGRAD) if opt == "adagrad" else (OPT_ADAM, oracle.OPT_ADAM)
     mk = lambda: LookupTable(4096, dim, device=dev, optimizer=kind, max_batch=n, initial_accumulator=0.1)
     ta, tb, tc = mk(), mk(), mk()
     o = oracle.OracleTable(4096, dim, optimizer=okind, initial_accumulator=0.1)
     for t in (ta, tb, tc):
-        t.insert(T(keys[:n_keys + 400], dev), T(rows[:n_keys + 400], dev))
-    o.insert(keys[:n_keys + 400], rows[:n_keys + 400])
+        t.insert(T(keys, dev), T(rows, dev))
+    o.insert(keys, rows)
     bkt = T(batch, dev)
     for s in range(2):
         pool = (rng.standard_normal((n // 3 + 1, dim)) * 0.02).astype(np.float32)     # indexed apply: three positions share a grad row
@@ -509,111 +490,12 @@ def test_optimizer_every_group_size(dev, opt, dim, layout):
     np.testing.assert_allclose(got.cpu().numpy(), exp, rtol=RTOL, atol=ATOL)
 
 
-@functools.lru_cache(maxsize=None)
-def _keys_of_apply_bucket_zero(count, seed):
-    """Distinct keys whose mix64 has 13 leading zero bits: for ANY bucket count up to 8192 the bucketed apply puts them all into bucket 0
-    (and the table into the first 1/8192 of its buckets).  Cached per (count, seed), read-only: the search hashes millions of candidates."""
-    rng = np.random.default_rng(seed)
-    got = []
-    while sum(len(g) for g in got) < count:
-        cand = rng.integers(-(1 << 62), 1 << 62, size=1 << 22, dtype=np.int64)
-        mix, _, _ = oracle.hash_batch(cand, 1, 1)
-        got.append(cand[mix < (np.uint64(1) << np.uint64(51))])
-    keys = np.unique(np.concatenate(got))[:count]
-    keys.flags.writeable = False
-    return keys
-
-
-EXTREME_CASES = ["one_key", "one_bucket_many_keys", "forty_hot_keys", "one_bucket_two_keys", "bucket_of_900_distinct", "bucket_of_300_warm"]
-
-
-def _bucketed_apply_extremes(dev, case, opt, kernel, dim):
-    """The rare ways through the bucketed apply (meepo_apply.hip), each forced by construction, plain and located, against the oracle:
-    one_key — a single key fills 400K of a 410K-position batch: ~780 slabs of one bucket each emit a record of that key, more records of ONE key
-    than a merge pass holds (mono_pass);  one_bucket_many_keys — 3000 keys that all fall into apply bucket 0, 100+ occurrences each: every slab
-    emits hundreds of records, the merge has far more records than one pass holds and splits them by hash prefix (the DFS stack);
-    forty_hot_keys — 40 keys of ~6000 occurrences in a uniform batch: forty split buckets merge side by side, spare blocks loop over slabs;
-    one_bucket_two_keys — two keys of one bucket, 150K occurrences each: the prefix split must separate exactly two keys;
-    bucket_of_900_distinct — 900 keys of apply bucket 0, once each, in a small batch: ONE block takes a bucket of ~1000 positions whole (two positions
-    per thread) with its LDS hash table filled almost to the last slot;  bucket_of_300_warm — 300 keys of bucket 0 with 1..6 occurrences each: the
-    same path with runs.
-    kernel: which apply kernel takes the batches — "lean" (block = bucket; a split bucket is taken by its own block one key at a time: what the
-    FIRST skewed batch of a stream gets), "full" (slabs, pending records, merges; from the second step on also the hot keys' own buckets, which the
-    first step's kernel reported), "auto" (the library's choice: lean for step 0, full for step 1).
-    Rows wider than 64 draw their gradients on the device (host normals of 100M values cost seconds per step) and forty_hot_keys gets a smaller
-    uniform part; the hot keys' counts, which make each case what it is, are the same at every dim."""
-    n_bg = 20000
-    rng = np.random.default_rng(5)
-    bg = synth.keys_np(321, 0, n_bg)
-    if case == "one_key":
-        hot = synth.keys_np(322, 0, 1); reps = np.array([400_000]); n_fill = 10_000
-    elif case == "one_bucket_many_keys":
-        hot = _keys_of_apply_bucket_zero(3000, 7); reps = rng.integers(100, 140, size=3000); n_fill = 20_000
-    elif case == "forty_hot_keys":
-        hot = synth.keys_np(323, 0, 40); reps = rng.integers(5000, 7000, size=40); n_fill = 150_000 if dim <= 64 else 30_000
-    elif case == "one_bucket_two_keys":
-        hot = _keys_of_apply_bucket_zero(2, 9); reps = np.array([150_000, 150_001]); n_fill = 5_000
-    elif case == "bucket_of_900_distinct":
-        hot = _keys_of_apply_bucket_zero(900, 11); reps = np.ones(900, dtype=np.int64); n_fill = 5_000
-    else:
-        hot = _keys_of_apply_bucket_zero(300, 12); reps = rng.integers(1, 7, size=300); n_fill = 3_000
-    keys = np.unique(np.concatenate([bg, hot]))
-    rows = synth.rows_np(keys, dim, 2)
-    bk = np.concatenate([np.repeat(hot, reps), bg[rng.integers(0, n_bg, n_fill)], synth.keys_np(324, 0, 50)])   # + 50 absent keys
-    rng.shuffle(bk)
-    n = bk.size
-    kind, okind = (OPT_ADAGRAD, oracle.OPT_ADAGRAD) if opt == "adagrad" else (OPT_ADAM, oracle.OPT_ADAM)
-    mk = lambda: LookupTable(1 << 17, dim, device=dev, optimizer=kind, max_batch=max(n, keys.size), initial_accumulator=0.1)
-    ta, tb = mk(), mk()
-    o = oracle.OracleTable(1 << 17, dim, optimizer=okind, initial_accumulator=0.1)
-    for t in (ta, tb):
-        t.insert(T(keys, dev), T(rows, dev))
-        t.set_tuning("apply_kernel", {"auto": -1, "lean": 0, "full": 1}[kernel])
-    o.insert(keys, rows)
-    bkt = T(bk, dev)
-    gen = torch.Generator(device=dev); gen.manual_seed(dim)
-    for s in range(3 if kernel == "full" else 2):
-        torch.cuda.synchronize()   # (the host sizes step s + 1 by what step s reported: hot keys' buckets exist from the second full step on)
-        if dim <= 64:
-            g = (rng.standard_normal((n, dim)) * 0.01).astype(np.float32)
-            gt = T(g, dev)
-        else:
-            gt = torch.randn(n, dim, device=dev, generator=gen) * 0.01
-            g = gt.cpu().numpy()
-        _, _, slots = tb.find_located(bkt, prepare_apply=(s == 1))
-        if opt == "adagrad":
-            ta.apply_adagrad(bkt, gt, lr=0.05); tb.apply_adagrad(bkt, gt, lr=0.05, slots=slots); o.apply_adagrad(bk, g, 0.05, 1e-10)
-        else:
-            ta.apply_adam(bkt, gt, lr=0.01, step=s + 1); tb.apply_adam(bkt, gt, lr=0.01, step=s + 1, slots=slots)
-            o.apply_adam(bk, g, 0.01, 0.9, 0.999, 1e-8, s + 1)
-    eo = o.export(with_state=True)
-    io = np.argsort(eo[0])
-    for t in (ta, tb):
-        assert t.status() == 0
-        e = [x.cpu().numpy() if x is not None else None for x in t.export(with_state=True)]
-        it = np.argsort(e[0])
-        assert np.array_equal(e[0][it], eo[0][io])
-        for x, z in zip(e[1:], eo[1:]):
-            if z is not None:
-                np.testing.assert_allclose(x[it], z[io], rtol=RTOL, atol=ATOL)
-    # the scratch is left clean: a batch of distinct keys right behind it, bit-exact
-    g1 = (rng.standard_normal((n_bg, dim)) * 0.02).astype(np.float32)
-    if opt == "adagrad":
-        ta.apply_adagrad(T(bg, dev), T(g1, dev), lr=0.05); o.apply_adagrad(bg, g1, 0.05, 1e-10)
-    else:
-        ta.apply_adam(T(bg, dev), T(g1, dev), lr=0.01, step=3); o.apply_adam(bg, g1, 0.01, 0.9, 0.999, 1e-8, 3)
-    got, found = ta.find(T(bg, dev))
-    exp, _ = o.find(bg)
-    assert bool(found.all()) and ta.status() == 0
-    np.testing.assert_allclose(got.cpu().numpy(), exp, rtol=RTOL, atol=ATOL)
-
-
 @pytest.mark.parametrize("opt", ["adagrad", "adam"])
 @pytest.mark.parametrize("kernel", ["auto", "lean", "full"])
 @pytest.mark.parametrize("case", EXTREME_CASES)
 def test_bucketed_apply_extremes(dev, case, opt, kernel):
-    """The rare ways through the bucketed apply at dim 64, the compile-time instance DIM4 = 16 (_bucketed_apply_extremes)."""
-    _bucketed_apply_extremes(dev, case, opt, kernel, 64)
+    """The rare ways through the bucketed apply at dim 64, the compile-time instance DIM4 = 16 (tests/_apply_cases.py: bucketed_apply_extremes)."""
+    bucketed_apply_extremes(dev, case, opt, kernel, 64)
 
 
 @pytest.mark.parametrize("opt,dim", [("adagrad", 128), ("adam", 128), ("adam", 100), ("adagrad", 260), ("adam", 32)])
@@ -623,7 +505,7 @@ def test_bucketed_apply_extremes_wide(dev, case, kernel, opt, dim):
     """The same rare ways through the other instances of the row shape, LEAN and FULL forced: dim 128 = DIM4 32, both optimizers (two full 16-lane
     column chunks, fp64 partial rows in memory); the run-time instance DIM4 = 0 at dim 100 (a second chunk with 9 of 16 lanes live, partial rows in
     memory), 260 (five chunks, the last with one live lane) and 32 (one chunk with 8 idle lanes, partial rows in LDS)."""
-    _bucketed_apply_extremes(dev, case, opt, kernel, dim)
+    bucketed_apply_extremes(dev, case, opt, kernel, dim)
 
 
 @pytest.mark.parametrize("sync_every_step", [True, False], ids=["host_in_step", "host_runs_ahead"])
@@ -1497,7 +1379,7 @@ def test_grouped_apply_forced_kernels(dev, opt, dim):
     rng = np.random.default_rng(17 + dim)
     kind, okind = (OPT_ADAGRAD, oracle.OPT_ADAGRAD) if opt == "adagrad" else (OPT_ADAM, oracle.OPT_ADAM)
     n_tables, cap, max_apply = 3, 1 << 15, 1 << 18
-    hot, warm = synth.keys_np(561, 0, 1), _keys_of_apply_bucket_zero(300, 12)
+    hot, warm = synth.keys_np(561, 0, 1), keys_of_apply_bucket_zero(300, 12)
     grouped, solo, oracles, universes = [], [], [], []
     for j in range(n_tables):
         u = synth.keys_np(570 + j, 0, 12_000)
