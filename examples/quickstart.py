@@ -1,6 +1,7 @@
 """Quick tour of the Python host layer on one MI355X (run on the GPU box: python examples/quickstart.py)."""
 import os
 import sys
+import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -28,6 +29,15 @@ print("bf16 rows equal the cast fp32 rows:", torch.equal(out16, out[:5].to(torch
 table.remove(keys[:1000])
 ek, ev = table.export()                                    # checkpoint: int64 keys[N], fp32 values[N, 64]
 print("after remove:", table.size(), "exported", tuple(ev.shape))
+
+# 1b. train -> serve: the trained fp32 table, saved, loaded into a table that stores its rows as bf16 (half the bytes per key) and served in bf16
+with tempfile.TemporaryDirectory() as ckpt:
+    table.save(ckpt)
+    serving = LookupTable(1 << 20, 64, device=dev, max_batch=1 << 16, value_dtype=torch.bfloat16)
+    serving.load(ckpt)                                     # every row rounded once to bf16 on the way in; optimizer state stays behind
+served, _ = serving.find(keys[1000:1005], out_dtype=torch.bfloat16)            # the stored bits, no second rounding
+print("serving table:", serving.size(), "keys,", serving.table_bytes >> 20, "MiB against", table.table_bytes >> 20, "MiB | same bf16 rows:",
+      torch.equal(served, table.find(keys[1000:1005], out_dtype=torch.bfloat16)[0]))
 
 # 2. the same table as a torch layer (forward = find_or_insert, backward = the table's sparse Adagrad)
 layer = DynamicEmbedding(table, optimizer="adagrad", lr=0.01)

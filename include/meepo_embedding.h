@@ -58,7 +58,15 @@ enum { MEE_MEM_HBM = 0, MEE_MEM_HOST_PINNED = 1 };
  * the statistics a hot/cold placement policy needs. */
 /* MEE_FLAG_ADMISSION: keep a count-min sketch (3 x max(2^12, capacity / 16 rounded up to a power of two) 32-bit counters) of how
  * often ABSENT keys were asked for — the state of the admission policy of mee_find_or_insert_admit (SPEC.md §3). */
-enum { MEE_FLAG_TRACK_HITS = 1u, MEE_FLAG_ADMISSION = 2u };
+/* MEE_FLAG_BF16_ROWS: the value plane holds bf16 rows, 2 x dim bytes per slot — a SERVING table (SPEC.md §3 "Row storage type"): writes round
+ * each fp32 element once to bfloat16 (the rule of "typed output" below), reads widen exactly, and everything observable is that of an fp32
+ * table that was handed the rounded rows and created with the rounded default_value.  Needs optimizer = MEE_OPT_NONE, dim a multiple of 8,
+ * MEE_MEM_HBM and neither of the two flags above (MEE_ERR_INVALID_ARG otherwise).  The operators it has: mee_find / _ex / _as, mee_find_pooled
+ * and mee_find_pooled_as without weights, mee_insert / mee_assign and their _as forms, mee_remove, mee_locate, mee_export / _range (fp32 out,
+ * widened), mee_reserve, mee_clear, mee_size / mee_status / mee_clear_status, mee_probe_length / _histogram, mee_dedup_keys, mee_table_info_get
+ * (table_bytes = capacity x (8 + 2 x dim)), mee_set_tuning, mee_table_plane (plane 0, row_stride_bytes = 2 x dim) and mee_table_value_dtype.
+ * Every other operator handed such a table — and every create that takes tables — returns MEE_ERR_UNSUPPORTED, launches nothing and writes nothing. */
+enum { MEE_FLAG_TRACK_HITS = 1u, MEE_FLAG_ADMISSION = 2u, MEE_FLAG_BF16_ROWS = 4u };
 
 typedef struct mee_table  mee_table;  /* one HBM-resident hash table (one shard) */
 typedef struct mee_router mee_router; /* workspace for the shard partition / un-permute kernels */
@@ -70,7 +78,7 @@ typedef struct mee_config {
     uint32_t struct_size;         /* = sizeof(mee_config); ABI guard */
     int32_t  device;              /* HIP device ordinal */
     uint64_t capacity;            /* requested slots; rounded up to 16 x (smallest prime >= capacity/16) (SPEC.md §2) */
-    uint32_t dim;                 /* floats per row: multiple of 4, 4..1024 */
+    uint32_t dim;                 /* floats per row: multiple of 4, 4..1024 (MEE_FLAG_BF16_ROWS: multiple of 8) */
     uint32_t optimizer;           /* MEE_OPT_*: which state planes to allocate */
     uint64_t max_batch;           /* largest n of any mutating op: sizes the workspace — with an optimizer ~(56 + 10 dim) B per position of HBM
                                    * (0.7 GB at 1M x dim 64: the pending records of a skewed batch's worst case); see mee_table_info.workspace_bytes */
@@ -86,7 +94,7 @@ typedef struct mee_config {
 typedef struct mee_table_info {
     uint64_t capacity, n_buckets, max_batch;
     uint32_t dim, optimizer;
-    uint64_t table_bytes;     /* keys + all planes resident in HBM */
+    uint64_t table_bytes;     /* keys + all planes resident in HBM (a bf16-row table: capacity x (8 + 2 x dim)) */
     uint64_t workspace_bytes;
 } mee_table_info;
 
@@ -375,6 +383,13 @@ int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, cons
  * row and found byte back) instead of 8 + 4·dim + 1: 137 instead of 265 B at dim 64. */
 enum { MEE_DTYPE_F32 = 0, MEE_DTYPE_BF16 = 1 };
 int mee_find_as(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, uint32_t flags, void* stream);
+/* Typed INPUT: mee_insert / mee_assign whose d_values holds rows of in_dtype.  MEE_DTYPE_F32: they ARE mee_insert / mee_assign.  MEE_DTYPE_BF16 on a
+ * table created with MEE_FLAG_BF16_ROWS: d_values is [n, dim] bf16, 16-byte aligned, and the rows are stored VERBATIM (no rounding, NaN payloads
+ * included); on an fp32 table it is MEE_ERR_UNSUPPORTED.  An unknown in_dtype or a misaligned bf16 buffer is MEE_ERR_INVALID_ARG. */
+int mee_insert_as(mee_table* t, const int64_t* d_keys, const void* d_values, uint32_t in_dtype, size_t n, void* stream);
+int mee_assign_as(mee_table* t, const int64_t* d_keys, const void* d_values, uint32_t in_dtype, size_t n, uint8_t* d_found, void* stream);
+/* MEE_DTYPE_F32, or MEE_DTYPE_BF16 for a table created with MEE_FLAG_BF16_ROWS (mee_table_info is a fixed 48 bytes: the row type has its own call) */
+int mee_table_value_dtype(const mee_table* t, uint32_t* out);
 int mee_find_located_as(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out,
                         void* stream);
 int mee_find_located_prepare_as(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out,

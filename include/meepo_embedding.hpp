@@ -40,6 +40,7 @@ struct TableOptions {
     float init_scale = 0.0f;
     uint64_t init_seed = 0;
     uint32_t value_memory = MEE_MEM_HBM;  // MEE_MEM_HOST_PINNED = cold tier (rows in pinned host DRAM)
+    bool bf16_rows = false;     // MEE_FLAG_BF16_ROWS: a serving table that stores its rows as bf16 (no optimizer, dim % 8 == 0, HBM)
 };
 
 // One HBM-resident shard (SPEC.md §2-§4).  Move-only.
@@ -50,6 +51,7 @@ public:
         c.struct_size = sizeof c; c.device = o.device; c.capacity = o.capacity; c.dim = o.dim; c.optimizer = o.optimizer;
         c.max_batch = o.max_batch; c.default_value = o.default_value; c.initial_accumulator = o.initial_accumulator;
         c.initializer = o.initializer; c.init_scale = o.init_scale; c.init_seed = o.init_seed; c.value_memory = o.value_memory;
+        c.flags = o.bf16_rows ? MEE_FLAG_BF16_ROWS : 0u;
         check(mee_table_create(&c, &t_));
     }
     ~Table() { if (t_) mee_table_destroy(t_); }
@@ -60,6 +62,7 @@ public:
 
     mee_table* handle() const noexcept { return t_; }
     mee_table_info info() const { mee_table_info i{}; check(mee_table_info_get(t_, &i)); return i; }
+    uint32_t value_dtype() const { uint32_t d = MEE_DTYPE_F32; check(mee_table_value_dtype(t_, &d)); return d; }   // MEE_DTYPE_BF16: a bf16-row table
 
     void find(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream = nullptr) const { check(mee_find(t_, d_keys, n, d_out, d_found, stream)); }
     // ... with this call's cache policy (MEE_FIND_* flags)
@@ -76,6 +79,9 @@ public:
     void find_missing(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream = nullptr) const { check(mee_find_missing(t_, d_keys, n, d_out, d_found, stream)); }
     void insert(const int64_t* d_keys, const float* d_values, size_t n, void* stream = nullptr) { check(mee_insert(t_, d_keys, d_values, n, stream)); }
     void assign(const int64_t* d_keys, const float* d_values, size_t n, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_assign(t_, d_keys, d_values, n, d_found, stream)); }
+    // rows of in_dtype (MEE_DTYPE_BF16: a bf16-row table stores the caller's bf16 rows verbatim; d_values 16-byte aligned)
+    void insert_as(const int64_t* d_keys, const void* d_values, uint32_t in_dtype, size_t n, void* stream = nullptr) { check(mee_insert_as(t_, d_keys, d_values, in_dtype, n, stream)); }
+    void assign_as(const int64_t* d_keys, const void* d_values, uint32_t in_dtype, size_t n, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_assign_as(t_, d_keys, d_values, in_dtype, n, d_found, stream)); }
     void remove(const int64_t* d_keys, size_t n, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_remove(t_, d_keys, n, d_found, stream)); }
     void find_or_insert(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_find_or_insert(t_, d_keys, n, d_out, d_found, stream)); }
     // the forward of a training step over a growing vocabulary: rows + the slot of every key, for apply_*_located of the same step

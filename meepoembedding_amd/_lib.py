@@ -24,7 +24,7 @@ FIND_DEFAULT, FIND_STREAM_STORES, FIND_CACHED_STORES, FIND_STREAM_ROWS, FIND_STR
 HANDLE_SLOT_MASK = (1 << 40) - 1   # a located-find handle: bits 0..39 the slot (as mee_locate reports it), bits 40..61 the table's layout epoch
 MEM_HBM, MEM_HOST_PINNED = 0, 1
 DTYPE_F32, DTYPE_BF16 = 0, 1   # MEE_DTYPE_*: the row type of a typed-output lookup (mee_*_as)
-FLAG_TRACK_HITS, FLAG_ADMISSION = 1, 2
+FLAG_TRACK_HITS, FLAG_ADMISSION, FLAG_BF16_ROWS = 1, 2, 4   # BF16_ROWS: a serving table whose value plane holds bf16 rows (SPEC.md §3 "Row storage type")
 TIER_COUNT_COLD, TIER_COUNT_HOT = 1, 2   # mee_find_pooled_tiered flags
 ABI_VERSION = 2   # MEE_ABI_VERSION of include/meepo_embedding.h this loader was written against
 EMPTY_KEY = -(1 << 63)
@@ -87,6 +87,10 @@ PROTOTYPES = {
     "mee_find_ex": (C.c_int, [_vp, _vp, _sz, _vp, _vp, C.c_uint32, _vp]),
     # typed output (fp32 | bf16 rows): d_out is followed by out_dtype
     "mee_find_as": (C.c_int, [_vp, _vp, _sz, _vp, _u32, _vp, _u32, _vp]),
+    # typed input (fp32 | bf16 rows): d_values is followed by in_dtype; bf16 rows go verbatim into a bf16-row table
+    "mee_insert_as": (C.c_int, [_vp, _vp, _vp, _u32, _sz, _vp]),
+    "mee_assign_as": (C.c_int, [_vp, _vp, _vp, _u32, _sz, _vp, _vp]),
+    "mee_table_value_dtype": (C.c_int, [_vp, C.POINTER(_u32)]),
     "mee_find_located_as": (C.c_int, [_vp, _vp, _sz, _vp, _u32, _vp, _vp, _vp]),
     "mee_find_located_prepare_as": (C.c_int, [_vp, _vp, _sz, _vp, _u32, _vp, _vp, _vp]),
     "mee_find_or_insert_as": (C.c_int, [_vp, _vp, _sz, _vp, _u32, _vp, _vp]),
@@ -210,6 +214,18 @@ PROTOTYPES = {
     "mee_sharded_size": (C.c_int, [_vp, C.POINTER(_sz), _vp]),
     "mee_sharded_status": (C.c_int, [_vp, C.POINTER(_u32), _vp]),
 }
+
+def refuse_bf16_rows(who: str, *tables) -> None:
+    """Groups, tiered pairs, sharded / peer tables and the nn layers are built over fp32 tables: a bf16-row table (LookupTable(value_dtype=torch.bfloat16),
+    a serving table) — alone or as a member of a group handed in — is refused at construction, before anything is created."""
+    for t in tables:
+        if t is None:
+            continue
+        for m in [t, *getattr(t, "tables", ())]:
+            if getattr(m, "value_dtype", torch.float32) == torch.bfloat16:
+                raise MeepoError(ERR_UNSUPPORTED, f"{who}: a bf16-row table (value_dtype=torch.bfloat16) is a serving table with find, find_pooled, insert, assign, "
+                                                  "remove, export and reserve of its own; it cannot be a member of a group, a tier, a shard or a trained layer")
+
 
 _lib = None
 

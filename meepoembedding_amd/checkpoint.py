@@ -3,6 +3,8 @@
 A checkpoint is a DIRECTORY:
 
     meta.json     {"format": "meepo-table-v1", "dim", "optimizer", "n", "planes": ["values", "state1", ...], "extra": {...}}
+                  ("extra" carries "value_dtype": "bfloat16" when a bf16-row table wrote it; values.f32 holds its rows widened, and
+                  loading an fp32 checkpoint into a bf16-row table — train, then serve — rounds every row once)
     keys.i64      n little-endian int64 keys, in export order (unspecified, stable within the checkpoint)
     values.f32    n x dim little-endian fp32 rows, same order
     state1.f32    n x dim Adagrad accumulator / Adam m      (tables with an optimizer)
@@ -46,7 +48,12 @@ def save_table(table, path: str, chunk_slots: int = 1 << 22, extra: dict | None 
     finally:
         for f in files:
             f.close()
-    meta = {"format": FORMAT, "dim": table.dim, "optimizer": int(table.optimizer), "n": n, "planes": list(planes), "extra": extra or {}}
+    # the files hold fp32 rows whatever the table stores (a bf16-row table's export widens, exactly): the format is the same; that the rows came out of
+    # a bf16-row table is a note in "extra" (absent = fp32 rows)
+    extra = dict(extra or {})
+    if getattr(table, "value_dtype", torch.float32) == torch.bfloat16:
+        extra["value_dtype"] = "bfloat16"
+    meta = {"format": FORMAT, "dim": table.dim, "optimizer": int(table.optimizer), "n": n, "planes": list(planes), "extra": extra}
     tmp = os.path.join(path, "meta.json.tmp")
     with open(tmp, "w") as f:
         json.dump(meta, f)

@@ -976,9 +976,9 @@ int bucket_assign(mee_table* t, float* plane, const int64_t* d_keys, const float
     // (rounds of the kernel's own resident blocks — five per CU — with buckets of up to ~683 positions: 1M keys = 2560 buckets of ~410 instead of the apply's 3072 of 341;
     // kernel 142.7 -> 140.0 us uniform, 61.5 -> 57.5 us Zipf(1.05) per 1M keys; one round of 1280 buckets of 820: slower; the uniform case is the rows' traffic)
     if (int rc = dedup_partition(t, d_keys, n, st, A.d, nullptr, nullptr, 0, d_found, nullptr, t->bk_dd.slots / kApplyBlocksPerCU * kAssignBlocksPerCU, kSumBucketMax)) return rc;
-    A.tkeys = t->keys; A.rows = (float4*)plane; A.nb = t->nb; A.dim4 = t->dim4; A.values = (const float4*)d_values; A.found = d_found;
+    A.tkeys = t->keys; A.rows = (float4*)plane; A.nb = t->nb; A.dim4 = t->mv_dim4; A.values = (const float4*)d_values; A.found = d_found;
     const uint32_t grid = A.d.nbk + hot_window_blocks(A.d, n);
-    with_row_shape(t->dim4, [&](auto d4) { bkt_assign_kernel<d4><<<grid, kDedupThreads, 0, st>>>(A, t->bk_dd); });
+    with_row_shape(t->mv_dim4, [&](auto d4) { bkt_assign_kernel<d4><<<grid, kDedupThreads, 0, st>>>(A, t->bk_dd); });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }

@@ -151,6 +151,18 @@ __device__ __forceinline__ int64_t collect_slots(const int64_t (&slot)[R], int l
     return mine;
 }
 
+// ---- bf16 ROWS (SPEC.md §3 "Row storage type"): a table whose value plane holds bf16 ----------------------------------------------
+// The element group a lane owns — 4 elements — is 8 bytes there: group g of slot s sits at index s * dim4 + g of a u32x2 array, the SAME index
+// the fp32 kernels use on their float4 array.  Widening is exact: the 16 stored bits become the upper half of the fp32 word.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u32x2 bf16x4_of(float a, float b, float c, float d);   // (below: the rounding every bf16 value of this library goes through)
+__device__ __forceinline__ f32x4 widen_bf16x4(const u32x2 p) {
+    f32x4 v;
+    v.x = __builtin_bit_cast(float, p.x << 16); v.y = __builtin_bit_cast(float, (p.x >> 16) << 16);
+    v.z = __builtin_bit_cast(float, p.y << 16); v.w = __builtin_bit_cast(float, (p.y >> 16) << 16);
+    return v;
+}
+
 // ---- pooled lookups (meepo_find.hip: one table and the uniform group; meepo_mixed.hip: the mixed group) ------------------------------
 // a bag of this many keys or more is served by the wave's four tiles together (find_pooled_kernel)
 constexpr uint32_t kPoolLong = 16;
@@ -158,7 +170,8 @@ constexpr uint32_t kPoolLong = 16;
 // probe + row load of up to U keys per tile (the find_kernel pattern); row[u] is only defined where inb[u].
 // located (nullable) receives tag | slot per position: tag = member << kGroupSlotBits for a group (EMPTY when absent), or the table's
 // handle tag (handle_tag_of) for one table with TAGGED (-1 when absent: the format of mee_find_located)
-template <int DIM4, int U, int C, bool TAGGED = false>
+// BROWS: `values` is a bf16-row plane (u32x2 groups): the row is widened at its load, everything behind the load is the fp32 code
+template <int DIM4, int U, int C, bool TAGGED = false, bool BROWS = false>
 __device__ __forceinline__ void pooled_fetch(const int64_t* __restrict__ tkeys, const float4* __restrict__ values, uint64_t nb,
                                              uint32_t dim4, const int64_t (&key)[U], const uint64_t (&pos)[U],
                                              const bool (&inb)[U], int tile, int tl, float4 def4, float4 (&row)[U][C],
@@ -178,8 +191,13 @@ __device__ __forceinline__ void pooled_fetch(const int64_t* __restrict__ tkeys, 
     for (int u = 0; u < U; ++u) {
 #pragma unroll
         for (int c = 0; c < C; ++c)
-            if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4)
-                row[u][c] = slot[u] >= 0 ? values[(uint64_t)slot[u] * dim4 + c * 16 + tl] : def4;
+            if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
+                if constexpr (BROWS) {   // (the table's default value is a bf16 value: packing it loses nothing)
+                    const u32x2 def2 = bf16x4_of(def4.x, def4.y, def4.z, def4.w);
+                    const f32x4 v = widen_bf16x4(slot[u] >= 0 ? reinterpret_cast<const u32x2*>(values)[(uint64_t)slot[u] * dim4 + c * 16 + tl] : def2);
+                    row[u][c] = make_float4(v.x, v.y, v.z, v.w);
+                } else row[u][c] = slot[u] >= 0 ? values[(uint64_t)slot[u] * dim4 + c * 16 + tl] : def4;
+            }
         if (found && inb[u] && tl == 0) found[pos[u]] = slot[u] >= 0;
         // the located row: lets the backward skip its own probe pass
         if (located && inb[u] && tl == 0) located[pos[u]] = slot[u] >= 0 ? (int64_t)(tag | (uint64_t)slot[u]) : (TAGGED ? -1 : kEmpty);
@@ -266,7 +284,6 @@ __device__ __forceinline__ void pooled_fetch_tiered(const int64_t* __restrict__ 
 // ---- bf16 output of the lookups (SPEC.md §3 "Output type") ------------------------------------------------------------------
 // A lane that holds a float4 of a row stores it as 4 bf16 = 8 bytes; a row of dim bf16 is dim4 such 8-byte groups, so group g of
 // output row i sits at index i * dim4 + g of a u32x2 array — the SAME index the fp32 kernels use on their f32x4 array.
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 // two fp32 -> two bfloat16 in one word, round to nearest even: plain casts, which gfx950 does with its packed convert (v_cvt_pk_bf16_f32).  It agrees
 // with the integer rule of the spec on every finite value, denormals included (HIP kernels run with fp32 denormals on), sends a finite value beyond
 // the largest bf16 to inf and a NaN to a NaN: tests/test_bf16_out.py checks exactly these on the device.  (The integer rule written out costs ~30

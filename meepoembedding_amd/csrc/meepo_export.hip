@@ -154,8 +154,11 @@ __global__ __launch_bounds__(256) void rehash_kernel(const int64_t* __restrict__
 // A wave owns a chunk of 1024 consecutive slots.  Pass A: 16 coalesced key loads, ballot + popcount -> occupied
 // count, ONE atomic reserves the chunk's output range.  Pass B: per 64-slot group, ranks from the ballot mask;
 // keys are written by their own lane, rows are copied four at a time (one per 16-lane tile).
+// BROWS: `values` is a bf16-row plane (SPEC.md §3 "Row storage type"; no state planes): each 8-byte group is widened on its way into the fp32 values_out —
+// source and destination are different buffers, so nothing is expanded in place.
 constexpr int kExportGroups = 16;
 
+template <bool BROWS>
 __global__ __launch_bounds__(256) void export_kernel(const int64_t* __restrict__ tkeys, const float4* __restrict__ values,
                                                      const float4* __restrict__ s1, const float4* __restrict__ s2,
                                                      uint64_t begin, uint64_t capacity /* = end of the slot range */, uint32_t dim4,
@@ -198,7 +201,12 @@ __global__ __launch_bounds__(256) void export_kernel(const int64_t* __restrict__
                 if (p >= 0 && pos < cap) {
                     const uint64_t src = (c0 + (uint64_t)j * 64 + p) * dim4, dst = pos * dim4;
                     for (uint32_t c = tl; c < dim4; c += 16) {
-                        if (values_out) values_out[dst + c] = values[src + c];
+                        if constexpr (BROWS) {
+                            if (values_out) {
+                                const f32x4 v = widen_bf16x4(reinterpret_cast<const u32x2*>(values)[src + c]);
+                                values_out[dst + c] = make_float4(v.x, v.y, v.z, v.w);
+                            }
+                        } else if (values_out) values_out[dst + c] = values[src + c];
                         if (s1_out) s1_out[dst + c] = s1[src + c];
                         if (s2_out) s2_out[dst + c] = s2[src + c];
                     }
@@ -234,7 +242,7 @@ int mee_reserve(mee_table* t, uint64_t new_capacity, void* stream) {
     hipStream_t st = as_stream(stream);
     int64_t* nkeys = nullptr; uint32_t* nhits = nullptr;
     float *nv = nullptr, *n1 = nullptr, *n2 = nullptr;
-    const uint64_t plane = ncap * (uint64_t)t->dim * sizeof(float);
+    const uint64_t plane = ncap * (uint64_t)t->dim * (t->bf16_rows ? 2 : sizeof(float));
     hipError_t e = hipMalloc((void**)&nkeys, ncap * sizeof(int64_t));
     if (e == hipSuccess && t->hits) e = hipMalloc((void**)&nhits, ncap * sizeof(uint32_t));
     if (e == hipSuccess) e = plane_alloc(t->value_memory, &nv, plane);
@@ -248,7 +256,7 @@ int mee_reserve(mee_table* t, uint64_t new_capacity, void* stream) {
     if (e == hipSuccess) {
         rehash_kernel<<<grid_for(t->capacity, 256, 1u << 16), 256, 0, st>>>(t->keys, (const float4*)t->values, (const float4*)t->s1, (const float4*)t->s2,
                                                                           t->hits, t->capacity, nkeys, (float4*)nv, (float4*)n1, (float4*)n2, nhits, nnb,
-                                                                          t->dim4, t->ctr);
+                                                                          t->mv_dim4, t->ctr);   // (rows move bit for bit, as opaque 16-byte groups)
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -271,6 +279,7 @@ int mee_reserve(mee_table* t, uint64_t new_capacity, void* stream) {
 int mee_hits_scan(mee_table* t, uint32_t min_hits, uint32_t max_hits, int reset, int64_t* d_keys_out, size_t cap, size_t* n_out,
                   void* stream) {
     MEE_RANGE("mee_hits_scan");
+    MEE_FP32_ROWS_ONLY(t, "mee_hits_scan");
     if (!t || !n_out || (cap && !d_keys_out)) return fail(MEE_ERR_INVALID_ARG, "mee_hits_scan: null argument");
     if (!t->hits) return fail(MEE_ERR_UNSUPPORTED, "mee_hits_scan: table was created without MEE_FLAG_TRACK_HITS");
     DeviceGuard g(t->device);
@@ -300,9 +309,11 @@ int mee_export_range(const mee_table* t, uint64_t slot_begin, uint64_t slot_end,
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
     zero_words(&t->op->n_export, sizeof(unsigned long long), st);
-    export_kernel<<<grid_for(slot_end - slot_begin, 4 * 64 * kExportGroups, 256 * 16), 256, 0, st>>>(
-        t->keys, (const float4*)t->values, (const float4*)t->s1, (const float4*)t->s2, slot_begin, slot_end, t->dim4, d_keys_out,
-        (float4*)d_values_out, t->s1 ? (float4*)d_state1_out : nullptr, t->s2 ? (float4*)d_state2_out : nullptr, cap, t->op);
+    with_flag(t->bf16_rows, [&](auto brows) {
+        export_kernel<decltype(brows)::value><<<grid_for(slot_end - slot_begin, 4 * 64 * kExportGroups, 256 * 16), 256, 0, st>>>(
+            t->keys, (const float4*)t->values, (const float4*)t->s1, (const float4*)t->s2, slot_begin, slot_end, t->dim4, d_keys_out,
+            (float4*)d_values_out, t->s1 ? (float4*)d_state1_out : nullptr, t->s2 ? (float4*)d_state2_out : nullptr, cap, t->op);
+    });
     MEE_HIP(hipGetLastError());
     MEE_HIP(hipMemcpyAsync(t->h_op, t->op, sizeof(OpCounters), hipMemcpyDeviceToHost, st));
     MEE_HIP(hipStreamSynchronize(st));
@@ -334,7 +345,7 @@ int mee_table_plane(const mee_table* t, uint32_t plane, void** ptr_out, uint64_t
     const float* p = plane_of(t, plane);
     if (!p) return fail(MEE_ERR_UNSUPPORTED, "mee_table_plane: plane %u does not exist (optimizer=%u)", plane, t->optimizer);
     *ptr_out = const_cast<float*>(p);
-    if (row_stride_bytes) *row_stride_bytes = (uint64_t)t->dim * sizeof(float);
+    if (row_stride_bytes) *row_stride_bytes = (uint64_t)t->dim * (t->bf16_rows ? 2 : sizeof(float));
     if (value_memory) *value_memory = t->value_memory;
     return MEE_OK;
 }

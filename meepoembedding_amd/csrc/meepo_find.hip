@@ -17,9 +17,27 @@ namespace mee {
 // One tile per key, R keys in flight per tile: the R bucket lines are requested back to back, then the R rows.
 // DIM4 = dim/4 when it is a multiple of 16 (each lane moves DIM4/16 float4 per row), 0 = any dim at run time.
 // NT & 256: `out` is a bf16 array (SPEC.md §3 "Output type") — the lane's float4 leaves as 4 bf16 in one 8-byte store (store_bf16x4); nothing else differs.
+// BROWS: `values` is a bf16-row plane (SPEC.md §3 "Row storage type"; mee_find / _ex / _as only: NT holds policy bits and 256).  Same tiles, same index
+// arithmetic; the element group a lane loads is 8 bytes (u32x2) instead of 16, so a dim-64 row is one 128-byte line per tile instruction.  With bf16 out
+// the 8 bytes leave as they came (no second rounding); with fp32 out they are widened in registers.  The policy bits 1 (streaming row loads) and 4
+// (cached stores) act in the compiled shapes (DIM4 16 / 32); the run-time shape (DIM4 = 0) loads and stores cached whatever they say, as the fp32
+// run-time path does (bit 2, the bucket loads, acts in every shape).  The instances with BROWS = false are the code they were before the parameter existed.
+
+// the store of one element group of a bf16 ROW: verbatim into a bf16 output, widened into an fp32 one; CACHED as store_bf16x4
+template <int NT, bool CACHED>
+__device__ __forceinline__ void store_brow(f32x4* __restrict__ out, uint64_t idx, const u32x2 p) {
+    if constexpr ((NT & 256) != 0) {
+        if constexpr (CACHED) reinterpret_cast<u32x2*>(out)[idx] = p;
+        else __builtin_nontemporal_store(p, reinterpret_cast<u32x2*>(out) + idx);
+    } else {
+        const f32x4 v = widen_bf16x4(p);
+        if constexpr (CACHED) out[idx] = v;
+        else __builtin_nontemporal_store(v, &out[idx]);
+    }
+}
 
 // the find of n positions by `n_waves` waves of which this is wave `wave` (each wave step takes 4R consecutive positions)
-template <int DIM4, int R, int NT>
+template <int DIM4, int R, int NT, bool BROWS = false>
 __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, const f32x4* __restrict__ values, uint64_t nb,
                                           const int64_t* __restrict__ keys, uint64_t n, f32x4* __restrict__ out,
                                           uint8_t* __restrict__ found, float defv, uint32_t dim4_rt, uint32_t* hits,
@@ -66,7 +84,52 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
             for (int r = 0; r < R; ++r)
                 if (slot[r] >= 0 && tl == 0) atomicAdd(&hits[slot[r]], 1u);
         }
-        if constexpr (DIM4 != 0) {
+        if constexpr (BROWS) {
+            static_assert((NT & ~(7 | 256)) == 0, "bf16 rows: the plain find only");
+            const u32x2* __restrict__ brows = reinterpret_cast<const u32x2*>(values);
+            const u32x2 def2 = bf16x4_of(defv, defv, defv, defv);   // (the table's default value is a bf16 value: packing it loses nothing)
+            if constexpr (DIM4 != 0) {
+                constexpr int C = DIM4 / 16;
+                u32x2 row[R][C];
+                bool all_hit = true;   // the wave-uniform common case, as below
+#pragma unroll
+                for (int r = 0; r < R; ++r) all_hit = all_hit && inb[r] && slot[r] >= 0;
+                if (__all(all_hit)) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+#pragma unroll
+                        for (int c = 0; c < C; ++c)
+                            row[r][c] = (NT & 1) ? __builtin_nontemporal_load(&brows[(uint64_t)slot[r] * DIM4 + c * 16 + tl]) : brows[(uint64_t)slot[r] * DIM4 + c * 16 + tl];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const uint64_t i = base + r * 4 + tile;
+#pragma unroll
+                        for (int c = 0; c < C; ++c) store_brow<NT, (NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, row[r][c]);
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+#pragma unroll
+                        for (int c = 0; c < C; ++c)
+                            row[r][c] = slot[r] >= 0 ? ((NT & 1) ? __builtin_nontemporal_load(&brows[(uint64_t)slot[r] * DIM4 + c * 16 + tl]) : brows[(uint64_t)slot[r] * DIM4 + c * 16 + tl]) : def2;
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const uint64_t i = base + r * 4 + tile;
+                        if (inb[r]) {
+#pragma unroll
+                            for (int c = 0; c < C; ++c) store_brow<NT, (NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, row[r][c]);
+                        }
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const uint64_t i = base + r * 4 + tile;
+                    if (inb[r])
+                        for (uint32_t c = tl; c < dim4; c += 16) store_brow<NT, true>(out, i * dim4 + c, slot[r] >= 0 ? brows[(uint64_t)slot[r] * dim4 + c] : def2);
+                }
+            }
+        } else if constexpr (DIM4 != 0) {
             constexpr int C = DIM4 / 16;
             f32x4 row[R][C];
             // Common case, decided per wave: every position of the wave step is inside the batch and was found.  Then the R row loads
@@ -142,12 +205,12 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
     }
 }
 
-template <int DIM4, int R, int NT>
+template <int DIM4, int R, int NT, bool BROWS = false>
 __global__ __launch_bounds__(256) void find_kernel(const int64_t* __restrict__ tkeys, const f32x4* __restrict__ values,
                                                    uint64_t nb, const int64_t* __restrict__ keys, uint64_t n,
                                                    f32x4* __restrict__ out, uint8_t* __restrict__ found, float defv,
                                                    uint32_t dim4_rt, uint32_t* hits, int64_t* __restrict__ slots_out = nullptr, int64_t handle_tag = 0) {
-    find_span<DIM4, R, NT>(tkeys, values, nb, keys, n, out, found, defv, dim4_rt, hits, slots_out,
+    find_span<DIM4, R, NT, BROWS>(tkeys, values, nb, keys, n, out, found, defv, dim4_rt, hits, slots_out,
                            (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (uint64_t)gridDim.x * (blockDim.x >> 6), handle_tag);
 }
 
@@ -275,7 +338,9 @@ __device__ __forceinline__ bool jagged_member(const uint64_t* __restrict__ membe
 // TIERED (mee_find_pooled_tiered; one hot/cold pair, unweighted): the table arguments are the HOT table's, `tier` brings the cold one — the
 // fetch step probes both per position (pooled_fetch_tiered, meepo_device.h); the accumulation below is the same code.  The instances with
 // TIERED = false never read `tier` and are the code they were before the parameter existed.
-template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false, bool JAGGED = false, bool TIERED = false>
+// BROWS (one bf16-row table, unweighted: SPEC.md §3 "Row storage type"): `values_` is a bf16-row plane — pooled_fetch widens each row at its load; the
+// accumulation below is the same code.  The instances with BROWS = false are the code they were before the parameter existed.
+template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false, bool JAGGED = false, bool TIERED = false, bool BROWS = false>
 __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restrict__ tkeys_, const float4* __restrict__ values_,
                                                           uint64_t nb_, const int64_t* __restrict__ keys,
                                                           const uint64_t* __restrict__ offsets, uint64_t n_bags,
@@ -287,6 +352,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                                                           uint32_t n_members = 0, TierArgs tier = {}) {
     static_assert(!JAGGED || (GROUPED && !WEIGHTED && !BF16), "the jagged map is the group's plain fp32 lookup");
     static_assert(!TIERED || (!GROUPED && !WEIGHTED && !JAGGED), "the tiered form is one pair's plain sum / mean");
+    static_assert(!BROWS || (!GROUPED && !WEIGHTED && !JAGGED && !TIERED), "bf16 rows: one table's plain sum / mean");
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
@@ -336,7 +402,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                     if constexpr (WEIGHTED) wv[u] = __shfl(wpre, tile * 16 + (int)((pos[u] - begin) & 15));
                 }
                 if constexpr (TIERED) pooled_fetch_tiered<DIM4, U, C>(tkeys, values, nb, tier, dim4, kv, pos, inb, tile, tl, def4, row, found);
-                else pooled_fetch<DIM4, U, C, TAGGED>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located,
+                else pooled_fetch<DIM4, U, C, TAGGED, BROWS>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located,
                                                       GROUPED ? member << kGroupSlotBits : (TAGGED ? (uint64_t)handle_tag : 0));
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
@@ -395,7 +461,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                     if constexpr (WEIGHTED) wv[u] = inb[u] ? weights[pos[u]] : 0.f;   // next to the key
                 }
                 if constexpr (TIERED) pooled_fetch_tiered<DIM4, U, C>(tkeys, values, nb, tier, dim4, kv, pos, inb, tile, tl, def4, row, found);
-                else pooled_fetch<DIM4, U, C, TAGGED>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located,
+                else pooled_fetch<DIM4, U, C, TAGGED, BROWS>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located,
                                                       GROUPED ? member << kGroupSlotBits : (TAGGED ? (uint64_t)handle_tag : 0));
 #pragma unroll
                 for (int u = 0; u < U; ++u)
@@ -640,7 +706,16 @@ int find_plane(const mee_table* t, const float* plane, float miss_value, const i
         with_value<3, 1>(path.kind == FindPath::CountedMissing ? 3 : 1, [&](auto flags) {
             find_missing_kernel<flags><<<grid_for(n, 256, 8192), 256, 0, st>>>(t->keys, (const float4*)plane, t->nb, t->dim4, d_keys, n, (float4*)d_out, d_found, t->hits);
         });
-    } else if (bf16) with_row_shape(t->dim4, [&](auto d4) {
+    } else if (t->bf16_rows) with_row_shape(t->dim4, [&](auto d4) {
+        // a bf16-ROW table (Plain only: the entry points see to that): find_span's BROWS instances, per row shape at its default keys in flight, fp32 or bf16 out
+        constexpr int D4 = d4;
+        constexpr int R = RowShape<D4>::rows_per_tile;
+        const unsigned grid = grid_for(n, (fblock / 64u) * 4u * (unsigned)R, t->find_grid_cap > 0 ? (unsigned)t->find_grid_cap : (1u << 22));
+        with_flag(bf16, [&](auto b16) { with_value<0, 1, 2, 3, 4, 5, 6, 7>(nt, [&](auto ntc) {
+            find_kernel<D4, R, (decltype(b16)::value ? 256 : 0) | decltype(ntc)::value, true><<<grid, fblock, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, nullptr, nullptr, 0);
+        }); });
+    });
+    else if (bf16) with_row_shape(t->dim4, [&](auto d4) {
         // bf16 rows: the same kernel with NT | 256, instantiated for each row shape's default keys in flight only ("find_rounds" does not apply)
         constexpr int D4 = d4;
         constexpr int R = RowShape<D4>::rows_per_tile;
@@ -744,11 +819,13 @@ extern "C" {
 
 int mee_find_located(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, int64_t* d_slots_out, void* stream) {
     MEE_RANGE("mee_find_located");
+    MEE_FP32_ROWS_ONLY(t, "mee_find_located");
     if (!t || (n && (!d_keys || !d_out || !d_slots_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_located: null argument");
     return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {FindPath::Located, d_slots_out});
 }
 int mee_find_located_as(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out, void* stream) {
     MEE_RANGE("mee_find_located_as");
+    MEE_FP32_ROWS_ONLY(t, "mee_find_located_as");
     if (!t || (n && (!d_keys || !d_out || !d_slots_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_located_as: null argument");
     if (int rc = check_out_dtype(d_out, out_dtype, "mee_find_located_as")) return rc;
     return find_plane(t, t->values, t->default_value, d_keys, n, (float*)d_out, d_found, stream, {FindPath::Located, d_slots_out, -1, out_dtype});
@@ -756,6 +833,7 @@ int mee_find_located_as(const mee_table* t, const int64_t* d_keys, size_t n, voi
 
 int mee_find_many(const mee_table* t, const mee_find_request* reqs, uint32_t count, void* stream) {
     MEE_RANGE("mee_find_many");
+    MEE_FP32_ROWS_ONLY(t, "mee_find_many");
     if (!t || !reqs) return fail(MEE_ERR_INVALID_ARG, "mee_find_many: null argument");
     if (count == 0) return MEE_OK;
     if (count > (uint32_t)kMaxFindRequests) return fail(MEE_ERR_INVALID_ARG, "mee_find_many: %u requests (at most %d per call)", count, kMaxFindRequests);
@@ -787,18 +865,21 @@ int mee_find_many(const mee_table* t, const mee_find_request* reqs, uint32_t cou
 
 int mee_find_unordered(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream) {
     MEE_RANGE("mee_find_unordered");
+    MEE_FP32_ROWS_ONLY(t, "mee_find_unordered");
     if (!t || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_unordered: null argument");
     return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {FindPath::Unordered});
 }
 
 int mee_find_missing(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream) {
     MEE_RANGE("mee_find_missing");
+    MEE_FP32_ROWS_ONLY(t, "mee_find_missing");
     if (!t || (n && (!d_keys || !d_out || !d_found))) return fail(MEE_ERR_INVALID_ARG, "mee_find_missing: null argument");
     return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {FindPath::Missing});
 }
 
 int mee_find_counted(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, int missing_only, void* stream) {
     MEE_RANGE("mee_find_counted");
+    MEE_FP32_ROWS_ONLY(t, "mee_find_counted");
     if (!t || (n && (!d_keys || !d_out || !d_found))) return fail(MEE_ERR_INVALID_ARG, "mee_find_counted: null argument");
     if (!t->hits) return fail(MEE_ERR_UNSUPPORTED, "mee_find_counted: table was created without MEE_FLAG_TRACK_HITS");
     return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {missing_only ? FindPath::CountedMissing : FindPath::Counted});
@@ -816,6 +897,7 @@ static int find_pooled_common(const mee_table* t, const int64_t* d_keys, size_t 
             kernel<<<grid, 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, t->default_value, t->dim4,
                                          mode == MEE_POOL_MEAN, nullptr, 1, weighted ? d_located_out : nullptr, n, d_weights, weighted ? tag : 0, nullptr, 0, TierArgs{});
         };
+        if constexpr (!weighted) { if (t->bf16_rows) { launch(find_pooled_kernel<d4, u, bpw, false, false, bf16, false, false, true>); return; } }   // (weighted: refused at the entry points)
         launch(find_pooled_kernel<d4, u, bpw, false, weighted, bf16>);
     }); }); });
     MEE_HIP(hipGetLastError());
@@ -833,6 +915,7 @@ int mee_find_pooled(const mee_table* t, const int64_t* d_keys, size_t n, const u
 int mee_find_pooled_weighted(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
                              const float* d_weights, float* d_out, uint8_t* d_found, int64_t* d_located_out, void* stream) {
     MEE_RANGE("mee_find_pooled_weighted");
+    MEE_FP32_ROWS_ONLY(t, "mee_find_pooled_weighted");
     if (!t || (n_bags && (!d_bag_offsets || !d_out)) || (n && (!d_keys || !d_weights)))
         return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_weighted: null argument");
     return find_pooled_common(t, d_keys, n, d_bag_offsets, n_bags, d_weights /* null only with n = 0: every bag is empty, the plain sum's zeros */, d_out, MEE_DTYPE_F32, d_found, d_located_out, MEE_POOL_SUM, stream);
@@ -841,6 +924,7 @@ int mee_find_pooled_weighted(const mee_table* t, const int64_t* d_keys, size_t n
 int mee_find_pooled_as(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const float* d_weights,
                        void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
     MEE_RANGE("mee_find_pooled_as");
+    if (d_weights) MEE_FP32_ROWS_ONLY(t, "mee_find_pooled_as");
     if (!t || (n_bags && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: null argument");
     if (int rc = check_out_dtype(d_out, out_dtype, "mee_find_pooled_as")) return rc;
     if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
@@ -853,6 +937,8 @@ int mee_find_pooled_as(const mee_table* t, const int64_t* d_keys, size_t n, cons
 int mee_find_pooled_tiered(const mee_table* hot, const mee_table* cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
                            void* d_out, uint32_t out_dtype, uint8_t* d_found, int mode, uint32_t flags, void* stream) {
     MEE_RANGE("mee_find_pooled_tiered");
+    MEE_FP32_ROWS_ONLY(hot, "mee_find_pooled_tiered");
+    MEE_FP32_ROWS_ONLY(cold, "mee_find_pooled_tiered");
     if (!hot || !cold || (n_bags && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: null argument");
     if (hot == cold) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: hot and cold are the same table (a key lives in exactly one tier)");
     if (hot->device != cold->device || hot->dim != cold->dim)
@@ -881,6 +967,7 @@ int mee_pooled_weighted_backward(const mee_table* t, const int64_t* d_keys, cons
                                  size_t n_bags, const float* d_weights, const float* d_bag_grads, float* d_grads_out, float* d_weight_grads_out,
                                  void* stream) {
     MEE_RANGE("mee_pooled_weighted_backward");
+    MEE_FP32_ROWS_ONLY(t, "mee_pooled_weighted_backward");
     if (!t || (n_bags && (!d_bag_offsets || !d_bag_grads)) || (n && (!d_keys || !d_weights || !d_grads_out)))
         return fail(MEE_ERR_INVALID_ARG, "mee_pooled_weighted_backward: null argument");
     if (n_bags == 0) return MEE_OK;
@@ -896,6 +983,7 @@ int mee_pooled_weighted_backward(const mee_table* t, const int64_t* d_keys, cons
 
 int mee_find_plane(const mee_table* t, uint32_t plane, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream) {
     MEE_RANGE("mee_find_plane");
+    MEE_FP32_ROWS_ONLY(t, "mee_find_plane");
     if (!t || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_plane: null argument");
     const float* p = plane_of(t, plane);
     if (!p) return fail(MEE_ERR_UNSUPPORTED, "mee_find_plane: plane %u does not exist (optimizer=%u)", plane, t->optimizer);
@@ -989,6 +1077,7 @@ int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, cons
 // The training forward: mee_find_located whose launch also carries mee_apply_prepare for the SAME keys (the partition half of the bucketed
 // apply, run by the launch's first blocks beside the row gather).  (Table without optimizer: plain mee_find_located.)
 int mee::find_located_prepare(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out, void* stream, const char* name) {
+    MEE_FP32_ROWS_ONLY(t, name);
     if (!t || (n && (!d_keys || !d_out || !d_slots_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
     if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
     if (t->pending.n) return fail(MEE_ERR_INVALID_ARG, "%s: a prepared apply is already pending", name);

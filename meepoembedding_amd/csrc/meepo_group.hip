@@ -219,6 +219,7 @@ int mee_group_create(mee_table* const* tables, uint32_t n_tables, uint64_t max_a
     *out = nullptr;
     for (uint32_t j = 0; j < n_tables; ++j)
         if (!tables[j]) return fail(MEE_ERR_INVALID_ARG, "mee_group_create: table %u is null", j);
+    for (uint32_t j = 0; j < n_tables; ++j) MEE_FP32_ROWS_ONLY(tables[j], "mee_group_create");   // covers every mee_group_* operator
     const TableView v0 = table_view(tables[0]);
     for (uint32_t j = 1; j < n_tables; ++j) {
         const TableView v = table_view(tables[j]);

@@ -82,6 +82,10 @@ struct TableView {
     uint32_t* hits;
 };
 TableView table_view(const mee_table* t);
+// The operators a bf16-row table does not have (include/meepo_embedding.h, MEE_FLAG_BF16_ROWS) — and every create that takes tables — say so through
+// this one check, before they launch or write anything: MEE_ERR_UNSUPPORTED naming `op`, MEE_OK for an fp32 table or a null one (defined in meepo_table.hip)
+int refuse_bf16_rows(const mee_table* t, const char* op);
+#define MEE_FP32_ROWS_ONLY(t, op) do { if (int rc_ = ::mee::refuse_bf16_rows((t), (op))) return rc_; } while (0)
 int find_skip_padding(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint8_t* d_found, void* stream, uint32_t out_dtype = MEE_DTYPE_F32);   // meepo_find.hip
 
 // ---- table groups (meepo_group.hip: grouped find / locate; meepo_table.hip: grouped apply) ---------------------------------

@@ -339,6 +339,7 @@ int mee_mixed_group_create(mee_table* const* tables, uint32_t n_tables, uint64_t
     *out = nullptr;
     for (uint32_t j = 0; j < n_tables; ++j)
         if (!tables[j]) return fail(MEE_ERR_INVALID_ARG, "mee_mixed_group_create: table %u is null", j);
+    for (uint32_t j = 0; j < n_tables; ++j) MEE_FP32_ROWS_ONLY(tables[j], "mee_mixed_group_create");   // covers every mee_mixed_group_* operator
     const TableView v0 = table_view(tables[0]);
     std::vector<uint32_t> dim4(n_tables);
     for (uint32_t j = 0; j < n_tables; ++j) {

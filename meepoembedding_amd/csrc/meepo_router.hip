@@ -1014,6 +1014,7 @@ int mee_p2p_inbox(mee_p2p* c, int64_t** d_keys, float** d_rows, uint64_t* n_slot
 int mee_p2p_find(mee_p2p* c, const mee_table* t, void* stream) {
     MEE_RANGE("mee_p2p_find");
     if (!c || !t) return fail(MEE_ERR_INVALID_ARG, "mee_p2p_find: null argument");
+    MEE_FP32_ROWS_ONLY(t, "mee_p2p_find");
     if (!c->connected) return fail(MEE_ERR_INVALID_ARG, "mee_p2p_find: not connected");
     const TableView v = table_view(t);
     if (v.dim != c->dim || v.device != c->device) return fail(MEE_ERR_INVALID_ARG, "mee_p2p_find: table dim/device mismatch");

@@ -693,6 +693,8 @@ int mee_sharded_create_ex(mee_table* local, void* nccl_comm, const mee_sharded_o
     *out = nullptr;
     if (!opt || opt->struct_size != sizeof(mee_sharded_options))
         return fail(MEE_ERR_INVALID_ARG, "mee_sharded_create_ex: null options or struct_size != %zu (ABI mismatch)", sizeof(mee_sharded_options));
+    MEE_FP32_ROWS_ONLY(local, "mee_sharded_create");   // covers every mee_sharded_* operator
+    MEE_FP32_ROWS_ONLY(opt->cold, "mee_sharded_create");
     const uint64_t max_batch = opt->max_batch;
     const double pad_slack = opt->pad_slack;
     if (!local || !nccl_comm || max_batch == 0 || max_batch > (1ull << 30) || pad_slack < 0.0 || (pad_slack > 0.0 && pad_slack < 1.0) ||

@@ -77,6 +77,16 @@ __global__ void fill_i64_kernel(int64_t* p, uint64_t n, int64_t v) {
 
 void fill_keys(int64_t* p, uint64_t n, int64_t v, hipStream_t st) { fill_i64_kernel<<<2048, 256, 0, st>>>(p, n, v); }
 
+// ---- bf16-row tables (SPEC.md §3 "Row storage type"): the one place where a written row is rounded ---------------------------------
+// fp32 [n][dim] -> bf16 [n][dim] in the table's pack scratch, one 8-byte group (4 elements, bf16x4_of) per thread and step; the movers then take the
+// packed rows as opaque 16-byte groups.  n_groups = n * dim / 4.
+__global__ __launch_bounds__(256) void pack_rows_kernel(const f32x4* __restrict__ rows, u32x2* __restrict__ packed, uint64_t n_groups) {
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_groups; i += (uint64_t)gridDim.x * blockDim.x) {
+        const f32x4 v = __builtin_nontemporal_load(&rows[i]);   // read exactly once
+        packed[i] = bf16x4_of(v.x, v.y, v.z, v.w);
+    }
+}
+
 // ---- group table: one entry per distinct key of the batch ---------------------------------------------------
 __device__ __forceinline__ uint32_t group_claim(const GroupTable& g, int64_t key, bool& claimed) {
     const unsigned long long bk = (unsigned long long)key ^ kBias;  // != 0 because key != kEmpty
@@ -426,6 +436,23 @@ TableView table_view(const mee_table* t) {
                      t->initializer, t->init_scale, t->init_acc, t->init_seed, &t->ctr->status, t->hits};
 }
 
+int refuse_bf16_rows(const mee_table* t, const char* op) {
+    if (t && t->bf16_rows)
+        return fail(MEE_ERR_UNSUPPORTED, "%s: not available on a bf16-row table (MEE_FLAG_BF16_ROWS: a serving table has find, find_pooled, insert, assign, remove, locate, export and reserve)", op);
+    return MEE_OK;
+}
+
+// SPEC.md §3 "Output type": one fp32 value rounded to bfloat16 (round to nearest even; a NaN stays a NaN), as an fp32 value — a bf16-row table's default value
+static float bf16_value_of(float x) {
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) u |= 0x00400000u;   // NaN: quiet, payload cut
+    else u += 0x7FFFu + ((u >> 16) & 1u);
+    u &= 0xFFFF0000u;
+    memcpy(&x, &u, 4);
+    return x;
+}
+
 // SPEC.md §2: the bucket count is prime, so every double-hashing stride visits all buckets
 uint64_t next_prime(uint64_t n) {
     if (n <= 2) return 2;
@@ -477,7 +504,7 @@ int mee_table_destroy(mee_table* t) {
     float* planes[] = {t->values, t->s1, t->s2};
     for (float* p : planes)
         if (p) { if (t->value_memory == MEE_MEM_HOST_PINNED) (void)hipHostFree(p); else (void)hipFree(p); }
-    void* dev[] = {t->keys, t->hits, t->sketch, t->g.ent, t->g.sres, t->bs.hidx, t->bs.occ, t->bs.fmask, t->bs.gacc, t->ctr, t->op};
+    void* dev[] = {t->keys, t->hits, t->sketch, t->g.ent, t->g.sres, t->bs.hidx, t->bs.occ, t->bs.fmask, t->bs.gacc, t->ctr, t->op, t->pack};
     for (void* p : dev) if (p) (void)hipFree(p);
     bucket_scratch_free(t);
     if (t->h_ctr) (void)hipHostFree(t->h_ctr);
@@ -495,8 +522,18 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
     if (cfg->capacity == 0 || cfg->dim < 4 || cfg->dim > 1024 || (cfg->dim & 3))
         return fail(MEE_ERR_INVALID_ARG, "mee_table_create: capacity must be >0 and dim a multiple of 4 in [4,1024]");
     if (cfg->optimizer > MEE_OPT_ADAM || cfg->initializer > MEE_INIT_UNIFORM || cfg->value_memory > MEE_MEM_HOST_PINNED ||
-        (cfg->flags & ~(uint32_t)(MEE_FLAG_TRACK_HITS | MEE_FLAG_ADMISSION)) != 0)
+        (cfg->flags & ~(uint32_t)(MEE_FLAG_TRACK_HITS | MEE_FLAG_ADMISSION | MEE_FLAG_BF16_ROWS)) != 0)
         return fail(MEE_ERR_INVALID_ARG, "mee_table_create: bad optimizer/initializer/value_memory");
+    if (cfg->flags & MEE_FLAG_BF16_ROWS) {   // a serving table: SPEC.md §3 "Row storage type"
+        if (cfg->optimizer != MEE_OPT_NONE)
+            return fail(MEE_ERR_INVALID_ARG, "mee_table_create: MEE_FLAG_BF16_ROWS with optimizer=%u (a bf16-row table is a serving table: it has no optimizer)", cfg->optimizer);
+        if (cfg->dim & 7)
+            return fail(MEE_ERR_INVALID_ARG, "mee_table_create: MEE_FLAG_BF16_ROWS needs dim to be a multiple of 8 (dim=%u: a bf16 row must be whole 16-byte groups)", cfg->dim);
+        if (cfg->flags & (MEE_FLAG_TRACK_HITS | MEE_FLAG_ADMISSION))
+            return fail(MEE_ERR_INVALID_ARG, "mee_table_create: MEE_FLAG_BF16_ROWS excludes MEE_FLAG_TRACK_HITS and MEE_FLAG_ADMISSION (flags=0x%x)", cfg->flags);
+        if (cfg->value_memory != MEE_MEM_HBM)
+            return fail(MEE_ERR_INVALID_ARG, "mee_table_create: MEE_FLAG_BF16_ROWS needs value_memory = MEE_MEM_HBM (a bf16-row table is no cold tier)");
+    }
     if (cfg->max_batch == 0 || cfg->max_batch > (1ull << 30))
         return fail(MEE_ERR_INVALID_ARG, "mee_table_create: max_batch must be in [1, 2^30]");
     int ndev = 0;
@@ -519,9 +556,11 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
     t->nb = next_prime((cfg->capacity + kW - 1) / kW);
     t->capacity = t->nb * kW;
     t->dim = cfg->dim; t->dim4 = cfg->dim / 4;
+    t->bf16_rows = (cfg->flags & MEE_FLAG_BF16_ROWS) != 0;
+    t->mv_dim4 = t->bf16_rows ? cfg->dim / 8 : t->dim4;
     t->optimizer = cfg->optimizer; t->initializer = cfg->initializer; t->value_memory = cfg->value_memory;
     t->max_batch = cfg->max_batch;
-    t->default_value = cfg->default_value; t->init_acc = cfg->initial_accumulator;
+    t->default_value = t->bf16_rows ? bf16_value_of(cfg->default_value) : cfg->default_value; t->init_acc = cfg->initial_accumulator;
     t->init_scale = cfg->init_scale; t->init_seed = cfg->init_seed;
     uint64_t S = 1024;
     while (S < 2 * cfg->max_batch) S <<= 1;
@@ -530,7 +569,7 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
     t->find_grid_cap = 0;
     t->find_nt = -1;  // auto
 
-    const uint64_t plane = t->capacity * (uint64_t)t->dim * sizeof(float);
+    const uint64_t plane = t->capacity * (uint64_t)t->dim * (t->bf16_rows ? 2 : sizeof(float));
     const uint64_t mb = t->max_batch;
     int rc = MEE_OK;
 #define ALLOC(ptr, bytes)                                                                                     \
@@ -574,8 +613,9 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
     t->bs.max_part = (uint32_t)t->max_part;
     if (t->optimizer != MEE_OPT_NONE) ALLOC(t->bs.gacc, t->max_part * (uint64_t)t->dim * sizeof(double));
     ALLOC(t->ctr, sizeof(Counters)); ALLOC(t->op, sizeof(OpCounters));
+    if (t->bf16_rows) ALLOC(t->pack, mb * (uint64_t)t->dim * 2);   // the rounded rows of one insert / assign batch
 #undef ALLOC
-    t->workspace_bytes = S * 24 + mb * 9 + (t->bs.gacc ? t->max_part * (uint64_t)t->dim * sizeof(double) : 0) + sizeof(Counters) + sizeof(OpCounters);
+    t->workspace_bytes = (t->pack ? mb * (uint64_t)t->dim * 2 : 0) + S * 24 + mb * 9 + (t->bs.gacc ? t->max_part * (uint64_t)t->dim * sizeof(double) : 0) + sizeof(Counters) + sizeof(OpCounters);
     if ((rc = bucket_scratch_alloc(t)) != MEE_OK) goto bad;   // the bucketed machinery's scratch: partition (every table), pending records (tables with an optimizer); adds to workspace_bytes
     if (hipHostMalloc((void**)&t->h_ctr, sizeof(Counters)) != hipSuccess || hipHostMalloc((void**)&t->h_op, sizeof(OpCounters)) != hipSuccess) {
         rc = fail(MEE_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
@@ -636,26 +676,36 @@ int mee_clear(mee_table* t, void* stream) {
 }
 
 // `skip` (nullable): positions whose byte is non-zero take no part (they were served by another table of a tiered pair)
+// in_dtype: the type of d_values' rows (mee_insert_as / mee_assign_as).  A bf16-row table takes fp32 rows through pack_rows_kernel (the one rounding) and
+// bf16 rows as they are; behind that the movers see rows of mv_dim4 opaque 16-byte groups, whatever they hold.
 static int upsert_common(mee_table* t, float* plane, const int64_t* d_keys, const float* d_values, size_t n, uint8_t* d_found,
-                         void* stream, bool claim, const char* name, const uint8_t* skip = nullptr) {
+                         void* stream, bool claim, const char* name, const uint8_t* skip = nullptr, uint32_t in_dtype = MEE_DTYPE_F32) {
     if (!t || !plane || (n && (!d_keys || !d_values))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (in_dtype != MEE_DTYPE_F32 && in_dtype != MEE_DTYPE_BF16) return fail(MEE_ERR_INVALID_ARG, "%s: unknown in_dtype %u (MEE_DTYPE_F32 or MEE_DTYPE_BF16)", name, in_dtype);
+    if (in_dtype == MEE_DTYPE_BF16 && !t->bf16_rows) return fail(MEE_ERR_UNSUPPORTED, "%s: bf16 input rows need a table created with MEE_FLAG_BF16_ROWS (an fp32 table stores fp32 rows)", name);
+    if (in_dtype == MEE_DTYPE_BF16 && ((uintptr_t)d_values & 15)) return fail(MEE_ERR_INVALID_ARG, "%s: a bf16 input must be 16-byte aligned", name);
     if (int rc = check_batch(t, n, name, stream)) return rc;
     if (n == 0) return MEE_OK;
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
     const uint32_t nn = (uint32_t)n;
     const unsigned gl = grid_for(n, 256, 1u << 22);
+    if (t->bf16_rows && in_dtype == MEE_DTYPE_F32) {
+        const uint64_t n_groups = (uint64_t)n * t->dim4;
+        pack_rows_kernel<<<grid_for(n_groups, 1024, 4096), 256, 0, st>>>((const f32x4*)d_values, (u32x2*)t->pack, n_groups);
+        d_values = (const float*)t->pack;
+    }
     if (claim) {   // insert: creators write at once, an election only among positions that found their key present (see insert_direct_kernel)
         next_epoch(t, st);
         long long* slotof = t->g.sres;   // S >= 2 * max_batch entries: lent as the per-position slot list (as mee_remove does)
         const unsigned gd = grid_for(n, 32, 1u << 16);
-        with_row_shape(t->dim4, [&](auto d4) {
-            insert_direct_kernel<d4><<<gd, 256, 0, st>>>(t->keys, (float4*)plane, (float4*)t->s1, (float4*)t->s2, t->nb, t->dim4, d_keys, (const float4*)d_values,
+        with_row_shape(t->mv_dim4, [&](auto d4) {
+            insert_direct_kernel<d4><<<gd, 256, 0, st>>>(t->keys, (float4*)plane, (float4*)t->s1, (float4*)t->s2, t->nb, t->mv_dim4, d_keys, (const float4*)d_values,
                                                          nn, skip, t->bs.fmask, slotof, t->bs.hidx, t->optimizer, t->init_acc, t->ctr, t->hits, t->epoch);
         });
         group_last_kernel<<<gl, 256, 0, st>>>(d_keys, nn, t->g, t->bs, t->ctr, t->bs.fmask, t->epoch, &t->ctr->election);
         insert_join_kernel<<<grid_for(n, 256, 2048), 256, 0, st>>>(d_keys, nn, t->bs.fmask, slotof, t->g, t->bs.hidx, t->ctr, t->epoch);
-        insert_settle_kernel<<<grid_for(n, 16, 2048), 256, 0, st>>>((float4*)plane, t->dim4, (const float4*)d_values, nn, slotof, t->bs.hidx, t->g, t->ctr, t->epoch);
+        insert_settle_kernel<<<grid_for(n, 16, 2048), 256, 0, st>>>((float4*)plane, t->mv_dim4, (const float4*)d_values, nn, slotof, t->bs.hidx, t->g, t->ctr, t->epoch);
         MEE_HIP(hipGetLastError());
         return MEE_OK;
     }
@@ -670,6 +720,7 @@ int mee_insert(mee_table* t, const int64_t* d_keys, const float* d_values, size_
 }
 int mee_insert_missing(mee_table* t, const int64_t* d_keys, const float* d_values, size_t n, const uint8_t* d_found, void* stream) {
     MEE_RANGE("mee_insert_missing");
+    MEE_FP32_ROWS_ONLY(t, "mee_insert_missing");
     if (!d_found && n) return fail(MEE_ERR_INVALID_ARG, "mee_insert_missing: null found mask");
     return upsert_common(t, t ? t->values : nullptr, d_keys, d_values, n, nullptr, stream, true, "mee_insert_missing", d_found);
 }
@@ -677,9 +728,23 @@ int mee_assign(mee_table* t, const int64_t* d_keys, const float* d_values, size_
     MEE_RANGE("mee_assign");
     return upsert_common(t, t ? t->values : nullptr, d_keys, d_values, n, d_found, stream, false, "mee_assign");
 }
+int mee_insert_as(mee_table* t, const int64_t* d_keys, const void* d_values, uint32_t in_dtype, size_t n, void* stream) {
+    MEE_RANGE("mee_insert_as");
+    return upsert_common(t, t ? t->values : nullptr, d_keys, (const float*)d_values, n, nullptr, stream, true, "mee_insert_as", nullptr, in_dtype);
+}
+int mee_assign_as(mee_table* t, const int64_t* d_keys, const void* d_values, uint32_t in_dtype, size_t n, uint8_t* d_found, void* stream) {
+    MEE_RANGE("mee_assign_as");
+    return upsert_common(t, t ? t->values : nullptr, d_keys, (const float*)d_values, n, d_found, stream, false, "mee_assign_as", nullptr, in_dtype);
+}
+int mee_table_value_dtype(const mee_table* t, uint32_t* out) {
+    if (!t || !out) return fail(MEE_ERR_INVALID_ARG, "mee_table_value_dtype: null argument");
+    *out = t->bf16_rows ? MEE_DTYPE_BF16 : MEE_DTYPE_F32;
+    return MEE_OK;
+}
 int mee_assign_plane(mee_table* t, uint32_t plane, const int64_t* d_keys, const float* d_values, size_t n, uint8_t* d_found,
                      void* stream) {
     MEE_RANGE("mee_assign_plane");
+    MEE_FP32_ROWS_ONLY(t, "mee_assign_plane");
     if (!t) return fail(MEE_ERR_INVALID_ARG, "mee_assign_plane: null table");
     float* p = const_cast<float*>(plane_of(t, plane));
     if (!p) return fail(MEE_ERR_UNSUPPORTED, "mee_assign_plane: plane %u does not exist (optimizer=%u)", plane, t->optimizer);
@@ -716,6 +781,7 @@ static void launch_ensure(mee_table* t, const int64_t* d_keys, uint32_t n, const
 
 static int find_or_insert_common(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint8_t* d_found, void* stream,
                                  bool own_find_pass, const char* name, int64_t* d_slots_out = nullptr, uint32_t out_dtype = MEE_DTYPE_F32) {
+    MEE_FP32_ROWS_ONLY(t, name);
     if (!t || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
     if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
     if (int rc = check_batch(t, n, name, stream)) return rc;
@@ -755,6 +821,7 @@ int mee_find_or_insert_located_as(mee_table* t, const int64_t* d_keys, size_t n,
 }
 int mee_find_or_insert_admit(mee_table* t, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, uint32_t min_count, void* stream) {
     MEE_RANGE("mee_find_or_insert_admit");
+    MEE_FP32_ROWS_ONLY(t, "mee_find_or_insert_admit");
     if (!t || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "mee_find_or_insert_admit: null argument");
     if (!t->sketch) return fail(MEE_ERR_UNSUPPORTED, "mee_find_or_insert_admit: table was created without MEE_FLAG_ADMISSION");
     if (int rc = check_batch(t, n, "mee_find_or_insert_admit", stream)) return rc;
@@ -775,6 +842,7 @@ int mee_find_or_insert_admit(mee_table* t, const int64_t* d_keys, size_t n, floa
 }
 int mee_admission_decay(mee_table* t, uint32_t shift, void* stream) {
     MEE_RANGE("mee_admission_decay");
+    MEE_FP32_ROWS_ONLY(t, "mee_admission_decay");
     if (!t) return fail(MEE_ERR_INVALID_ARG, "mee_admission_decay: null table");
     if (!t->sketch) return fail(MEE_ERR_UNSUPPORTED, "mee_admission_decay: table was created without MEE_FLAG_ADMISSION");
     DeviceGuard g(t->device);
@@ -806,6 +874,7 @@ int mee_locate(const mee_table* t, const int64_t* d_keys, size_t n, int64_t* d_s
 // `d_slots` (nullable): the slot of every position as mee_find_located of the same step reported it.
 static int apply_common(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, const OptArgs& a, void* stream,
                         const char* name, const uint32_t* d_gidx = nullptr, const int64_t* d_slots = nullptr) {
+    MEE_FP32_ROWS_ONLY(t, name);
     if (!t || (n && (!d_keys || !d_grads))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
     if (t->optimizer != a.kind) return fail(MEE_ERR_UNSUPPORTED, "%s: table was created with optimizer=%u", name, t->optimizer);
     if (int rc = check_batch(t, n, name, stream, false)) return rc;
@@ -917,6 +986,7 @@ int mee_group_apply_adam_indexed(mee_group* g, const int64_t* d_keys, const uint
 
 int mee_apply_prepare(mee_table* t, const int64_t* d_keys, size_t n, void* stream) {
     MEE_RANGE("mee_apply_prepare");
+    MEE_FP32_ROWS_ONLY(t, "mee_apply_prepare");
     if (!t || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_apply_prepare: null argument");
     if (t->optimizer == MEE_OPT_NONE) return fail(MEE_ERR_UNSUPPORTED, "mee_apply_prepare: table has no optimizer");
     if (t->pending.n) return fail(MEE_ERR_INVALID_ARG, "mee_apply_prepare: a prepared apply is already pending");
@@ -957,6 +1027,7 @@ int mee_find_or_insert_located_prepare_as(mee_table* t, const int64_t* d_keys, s
 
 int mee_apply_discard(mee_table* t, void* stream) {
     MEE_RANGE("mee_apply_discard");
+    MEE_FP32_ROWS_ONLY(t, "mee_apply_discard");
     if (!t) return fail(MEE_ERR_INVALID_ARG, "mee_apply_discard: null table");
     if (!t->pending.n) return MEE_OK;
     DeviceGuard g(t->device);
@@ -1029,6 +1100,7 @@ int mee_apply_adam_indexed(mee_table* t, const int64_t* d_keys, const float* d_g
 int mee_dedup_sum(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, int64_t* d_uniq_out, float* d_gsum_out,
                   uint32_t* d_counts_out, int64_t* d_inverse_out, int64_t miss_index, void* stream) {
     MEE_RANGE("mee_dedup_sum");
+    MEE_FP32_ROWS_ONLY(t, "mee_dedup_sum");
     if (!t || (n && (!d_keys || !d_uniq_out))) return fail(MEE_ERR_INVALID_ARG, "mee_dedup_sum: null argument");
     if ((d_grads == nullptr) != (d_gsum_out == nullptr)) return fail(MEE_ERR_INVALID_ARG, "mee_dedup_sum: d_grads and d_gsum_out go together (both or neither)");
     if (int rc = check_batch(t, n, "mee_dedup_sum", stream)) return rc;

@@ -59,13 +59,30 @@ def _fp32_only(out: torch.Tensor | None, op: str) -> None:
 
 
 class LookupTable:
-    """One HBM-resident shard: int64 key -> fp32[dim] row (+ optimizer state planes)."""
+    """One HBM-resident shard: int64 key -> fp32[dim] row (+ optimizer state planes).
+
+    value_dtype=torch.bfloat16: a SERVING table whose rows are stored as bf16, 2·dim bytes per slot (SPEC.md §3 "Row storage type").  insert / assign /
+    import_ round fp32 rows once (or store bf16 rows verbatim), every read widens exactly, find(out_dtype=torch.bfloat16) returns the stored bits: the
+    table is indistinguishable from an fp32 table fed the rounded rows.  No optimizer, hit counters, admission or host memory; dim a multiple of 8;
+    the operators outside find / find_pooled (unweighted) / insert / assign / remove / locate / export / reserve / clear raise MeepoError(ERR_UNSUPPORTED)."""
     supports_out_dtype = True   # its lookups can write bf16 rows (out_dtype=torch.bfloat16); the tiered / sharded / peer tables cannot
 
     def __init__(self, capacity: int, dim: int, *, device: int | torch.device = 0, optimizer: int = OPT_NONE,
                  max_batch: int = 1 << 20, default_value: float = 0.0, initial_accumulator: float = 0.0,
                  initializer: int = INIT_CONSTANT, init_scale: float = 0.0, init_seed: int = 0, value_memory: int = 0, track_hits: bool = False,
-                 admission: bool = False):
+                 admission: bool = False, value_dtype: torch.dtype = torch.float32):
+        if value_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"value_dtype must be torch.float32 or torch.bfloat16 (got {value_dtype}): rows are stored as fp32 or as bf16")
+        if value_dtype == torch.bfloat16:   # a serving table: checked here, before any device is needed (the library checks again)
+            if optimizer != OPT_NONE:
+                raise ValueError("value_dtype=torch.bfloat16 is a serving table: it has no optimizer (train in fp32, then checkpoint.load_into a bf16-row table)")
+            if track_hits or admission:
+                raise ValueError("value_dtype=torch.bfloat16 excludes track_hits and admission")
+            if value_memory != _lib.MEM_HBM:
+                raise ValueError("value_dtype=torch.bfloat16 needs value_memory = MEM_HBM (a bf16-row table is no cold tier)")
+            if dim % 8:
+                raise ValueError(f"value_dtype=torch.bfloat16 needs dim to be a multiple of 8 (got {dim})")
+        self.value_dtype = value_dtype
         L = _lib.lib()
         dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         if dev.type != "cuda":
@@ -75,16 +92,18 @@ class LookupTable:
                           optimizer=optimizer, max_batch=max_batch, default_value=default_value,
                           initial_accumulator=initial_accumulator, initializer=initializer, init_scale=init_scale,
                           init_seed=init_seed, value_memory=value_memory,
-                          flags=(_lib.FLAG_TRACK_HITS if track_hits else 0) | (_lib.FLAG_ADMISSION if admission else 0))
+                          flags=(_lib.FLAG_TRACK_HITS if track_hits else 0) | (_lib.FLAG_ADMISSION if admission else 0)
+                          | (_lib.FLAG_BF16_ROWS if value_dtype == torch.bfloat16 else 0))
         self.track_hits = track_hits
-        self.default_value = float(default_value)
+        # (a bf16-row table's default row is the rounded value)
+        self.default_value = float(default_value) if value_dtype == torch.float32 else float(torch.tensor(default_value, dtype=torch.float32).to(torch.bfloat16))
         h = C.c_void_p()
         self._h = None
         check(L.mee_table_create(C.byref(cfg), C.byref(h)))
         self._h = h
         self._opts = dict(device=self.device, optimizer=optimizer, max_batch=max_batch, default_value=default_value,
                           initial_accumulator=initial_accumulator, initializer=initializer, init_scale=init_scale, init_seed=init_seed,
-                          value_memory=value_memory, track_hits=track_hits, admission=admission)
+                          value_memory=value_memory, track_hits=track_hits, admission=admission, value_dtype=value_dtype)
         info = _lib.TableInfo()
         check(L.mee_table_info_get(self._h, C.byref(info)))
         self.capacity, self.n_buckets, self.max_batch = info.capacity, info.n_buckets, info.max_batch
@@ -119,6 +138,19 @@ class LookupTable:
 
     def _s(self) -> int:
         return _stream_ptr(self.device)
+
+    def _in_rows(self, rows: torch.Tensor, n: int):
+        """the rows of insert / assign -> (contiguous tensor, MEE_DTYPE_* of its elements).  fp32 always; bf16 for a bf16-row table, which stores them verbatim."""
+        if rows.dtype == torch.bfloat16 and self.value_dtype == torch.bfloat16:
+            if rows.device != self.device or rows.numel() != n * self.dim:
+                raise MeepoError(_lib.ERR_INVALID_ARG, f"rows must be [{n},{self.dim}] on {self.device}")
+            r = rows.contiguous()
+            if r.data_ptr() % 16:   # mee_*_as: a bf16 input is read in 16-byte groups
+                r = r.clone()
+            return r, _lib.DTYPE_BF16
+        if rows.dtype == torch.bfloat16:
+            raise MeepoError(_lib.ERR_UNSUPPORTED, "bf16 rows need a table created with value_dtype=torch.bfloat16 (an fp32 table stores fp32 rows)")
+        return self._rows(rows, n), _lib.DTYPE_F32
 
     # -- operators (SPEC.md §3) ----------------------------------------------------------------------------
     def find(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
@@ -253,8 +285,12 @@ class LookupTable:
         return out[: min(n.value, cap)]
 
     def insert(self, keys: torch.Tensor, values: torch.Tensor) -> None:
+        """values: fp32 rows (a bf16-row table rounds them once), or bf16 rows for a bf16-row table (stored verbatim, mee_insert_as)."""
         k = self._keys(keys)
-        v = self._rows(values, k.numel())
+        v, dt = self._in_rows(values, k.numel())
+        if dt != _lib.DTYPE_F32:
+            check(_lib.lib().mee_insert_as(self._h, k.data_ptr(), v.data_ptr(), dt, k.numel(), self._s()))
+            return
         check(_lib.lib().mee_insert(self._h, k.data_ptr(), v.data_ptr(), k.numel(), self._s()))
 
     def insert_missing(self, keys: torch.Tensor, values: torch.Tensor, found: torch.Tensor) -> None:
@@ -270,9 +306,13 @@ class LookupTable:
         check(_lib.lib().mee_find_or_insert_missing(self._h, k.data_ptr(), k.numel(), out.data_ptr(), found.data_ptr(), self._s()))
 
     def assign(self, keys: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
+        """values as in insert()."""
         k = self._keys(keys)
-        v = self._rows(values, k.numel())
+        v, dt = self._in_rows(values, k.numel())
         found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
+        if dt != _lib.DTYPE_F32:
+            check(_lib.lib().mee_assign_as(self._h, k.data_ptr(), v.data_ptr(), dt, k.numel(), found.data_ptr(), self._s()))
+            return found
         check(_lib.lib().mee_assign(self._h, k.data_ptr(), v.data_ptr(), k.numel(), found.data_ptr(), self._s()))
         return found
 
@@ -467,7 +507,7 @@ class LookupTable:
         The on-disk checkpoint format is exactly export's arrays: int64 keys[N], fp32 values[N, dim] (+ state planes)."""
         k = self._keys(keys)
         n = k.numel()
-        v = self._rows(values, n)
+        v, _ = self._in_rows(values, n)
         planes = [(1, state1), (2, state2)]
         for s in range(0, n, self.max_batch):
             e = min(n, s + self.max_batch)
@@ -608,6 +648,7 @@ class TableGroup:
         self.tables = list(tables)
         if not self.tables:
             raise ValueError("a group needs at least one table")
+        _lib.refuse_bf16_rows("TableGroup", *self.tables)
         self.device, self.dim = self.tables[0].device, self.tables[0].dim
         arr = (C.c_void_p * len(self.tables))(*[t._h for t in self.tables])
         h = C.c_void_p()
@@ -834,6 +875,7 @@ class MixedTableGroup:
         self.tables = list(tables)
         if not self.tables:
             raise ValueError("a group needs at least one table")
+        _lib.refuse_bf16_rows("MixedTableGroup", *self.tables)
         self.device = self.tables[0].device
         self.dims = [t.dim for t in self.tables]
         arr = (C.c_void_p * len(self.tables))(*[t._h for t in self.tables])
