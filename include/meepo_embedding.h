@@ -65,7 +65,8 @@ enum { MEE_MEM_HBM = 0, MEE_MEM_HOST_PINNED = 1 };
  * and mee_find_pooled_as without weights, mee_insert / mee_assign and their _as forms, mee_remove, mee_locate, mee_export / _range (fp32 out,
  * widened), mee_reserve, mee_clear, mee_size / mee_status / mee_clear_status, mee_probe_length / _histogram, mee_dedup_keys, mee_table_info_get
  * (table_bytes = capacity x (8 + 2 x dim)), mee_set_tuning, mee_table_plane (plane 0, row_stride_bytes = 2 x dim) and mee_table_value_dtype.
- * Every other operator handed such a table — and every create that takes tables — returns MEE_ERR_UNSUPPORTED, launches nothing and writes nothing. */
+ * Every other operator handed such a table — and every other create that takes tables — returns MEE_ERR_UNSUPPORTED, launches nothing and writes
+ * nothing.  The one create that takes them is mee_group_create, for a group whose members are ALL bf16-row tables (a serving group: see "table groups"). */
 enum { MEE_FLAG_TRACK_HITS = 1u, MEE_FLAG_ADMISSION = 2u, MEE_FLAG_BF16_ROWS = 4u };
 
 typedef struct mee_table  mee_table;  /* one HBM-resident hash table (one shard) */
@@ -299,13 +300,27 @@ int mee_probe_histogram(const mee_table* t, const int64_t* d_keys, size_t n, uin
  * instead of n_tables times.  Asynchronous on `stream`; after mee_reserve on a member the next call re-reads that
  * table's planes (one stream synchronisation).  The group does not own the tables: destroy it before them.  Calls on one
  * group that use its scratch (mee_group_find_or_insert without d_found, mee_group_apply_*) must be ordered by the caller;
- * mee_find_grouped / mee_group_find_pooled calls may run concurrently on several streams. */
+ * mee_find_grouped / mee_group_find_pooled calls may run concurrently on several streams.
+ *
+ * Row storage: a group holds fp32-row tables, or ONLY tables created with MEE_FLAG_BF16_ROWS — a bf16-row group, the serving form of a collection.  A
+ * mix of the two is MEE_ERR_UNSUPPORTED (one storage type per group: the row type is a compile-time property of every launch, not a per-member branch
+ * in the row fetch), and a bf16-row group needs max_apply_batch = 0 (MEE_ERR_INVALID_ARG otherwise: it has no step and no scratch table).  Each lookup
+ * of a bf16-row group is, bit for bit, that lookup on each bf16-row member — hence the fp32 group over fp32 tables that were handed the rounded rows
+ * and created with the rounded default_value; found masks, reserved keys, positions outside the segments, empty bags, the clamping of the offsets and
+ * each member's own default row included.  The operators it has: mee_find_grouped / _as (fp32 out widens exactly, bf16 out returns the stored bits),
+ * mee_group_find_pooled / _as without weights (SUM | MEAN; rows widened and added in fp32 in position order, the finished bag row rounded once for bf16
+ * out), mee_group_find_pooled_jagged, mee_group_value_dtype, mee_group_destroy; mee_reserve on a member between lookups keeps working.  Everything else
+ * — mee_group_find_or_insert / _as, every mee_group_apply_*, mee_group_find_pooled_weighted and a non-null d_weights of mee_group_find_pooled_as,
+ * mee_group_pooled_weighted_backward, and a non-null d_located_out of any pooled form (located rows exist for the backward, which this group does not
+ * have) — returns MEE_ERR_UNSUPPORTED before anything is launched or written; mee_group_set_tuning answers as for any group without an apply. */
 typedef struct mee_group mee_group;
 int mee_group_create(mee_table* const* tables, uint32_t n_tables, uint64_t max_apply_batch, mee_group** out);
 int mee_group_destroy(mee_group* g);
 /* mee_set_tuning for the group's own apply ("apply_bucket_max", "apply_kernel", …: as for a table; groups created with
  * max_apply_batch = 0 have nothing to tune: MEE_ERR_UNSUPPORTED). */
 int mee_group_set_tuning(mee_group* g, const char* name, int value);
+/* the members' row storage type: MEE_DTYPE_F32, or MEE_DTYPE_BF16 for a bf16-row group */
+int mee_group_value_dtype(const mee_group* g, uint32_t* out);
 int mee_find_grouped(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, float* d_out, uint8_t* d_found,
                      void* stream);
 /* mee_find_or_insert over the jagged layout (three launches): absent keys are created in their member table with that

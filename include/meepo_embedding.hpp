@@ -153,6 +153,9 @@ private:
 };
 
 // Many tables (same device, same dim) served by ONE find launch over their concatenated ("jagged") key batches.
+// Members that are all bf16-row tables (TableOptions::bf16_rows) make a bf16-row group, the serving form of a collection: max_apply_batch must be 0, the
+// lookups (find, find_pooled without weights or located rows, the jagged form) are bit for bit the per-member lookups, and everything that trains —
+// find_or_insert, apply_*, the weighted forms — throws MEE_ERR_UNSUPPORTED.  fp32-row and bf16-row tables never share a group.
 class Group {
 public:
     Group(Table* const* tables, uint32_t n, uint64_t max_apply_batch = 0) {
@@ -164,6 +167,7 @@ public:
     ~Group() { if (g_) mee_group_destroy(g_); }
     Group(const Group&) = delete;
     Group& operator=(const Group&) = delete;
+    uint32_t value_dtype() const { uint32_t d = MEE_DTYPE_F32; check(mee_group_value_dtype(g_, &d)); return d; }   // MEE_DTYPE_BF16: a bf16-row group
     // segment j = d_keys[d_offsets[j] .. d_offsets[j+1]); d_offsets: n_tables + 1 values in DEVICE memory; n = total positions
     void find(const int64_t* d_keys, const uint64_t* d_offsets, size_t n, float* d_out, uint8_t* d_found, void* stream = nullptr) {
         check(mee_find_grouped(g_, d_keys, d_offsets, n, d_out, d_found, stream));

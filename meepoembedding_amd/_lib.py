@@ -124,6 +124,7 @@ PROTOTYPES = {
     "mee_group_apply_adam": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32, _u64, _vp]),
     "mee_group_destroy": (C.c_int, [_vp]),
     "mee_group_set_tuning": (C.c_int, [_vp, C.c_char_p, C.c_int]),
+    "mee_group_value_dtype": (C.c_int, [_vp, C.POINTER(_u32)]),
     "mee_find_grouped": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     # mixed groups: members of different dims, class-major output (meepo_mixed.hip)
     "mee_mixed_group_create": (C.c_int, [C.POINTER(_vp), _u32, _u64, C.POINTER(_vp)]),
@@ -225,6 +226,18 @@ def refuse_bf16_rows(who: str, *tables) -> None:
             if getattr(m, "value_dtype", torch.float32) == torch.bfloat16:
                 raise MeepoError(ERR_UNSUPPORTED, f"{who}: a bf16-row table (value_dtype=torch.bfloat16) is a serving table with find, find_pooled, insert, assign, "
                                                   "remove, export and reserve of its own; it cannot be a member of a group, a tier, a shard or a trained layer")
+
+
+def group_row_dtype(who: str, *tables) -> torch.dtype:
+    """The row storage type of a uniform group: torch.float32, or torch.bfloat16 when EVERY member is a bf16-row table (a serving group: lookups only).
+    A mix is refused as refuse_bf16_rows refuses a bf16-row table — one storage type per group.  Only .value_dtype is looked at (absent: fp32)."""
+    kinds = {getattr(t, "value_dtype", torch.float32) == torch.bfloat16 for t in tables}
+    if kinds == {True}:
+        return torch.bfloat16
+    if True in kinds:
+        raise MeepoError(ERR_UNSUPPORTED, f"{who}: a bf16-row table (value_dtype=torch.bfloat16) and an fp32-row table cannot share a group — "
+                                          "a group holds fp32-row tables or bf16-row tables, never both (serving_copy() makes the bf16-row twin of a whole group)")
+    return torch.float32
 
 
 _lib = None

@@ -306,6 +306,20 @@ __device__ __forceinline__ void store_bf16x4(void* out, uint64_t idx, const V4& 
     else __builtin_nontemporal_store(p, reinterpret_cast<u32x2*>(out) + idx);
 }
 
+// the store of one element group of a bf16 ROW (u32x2 as loaded from a bf16-row plane): verbatim into a bf16 output (BF16_OUT: no second rounding), widened
+// exactly into an fp32 one; CACHED as store_bf16x4
+template <bool BF16_OUT, bool CACHED>
+__device__ __forceinline__ void store_brow_as(void* __restrict__ out, uint64_t idx, const u32x2 p) {
+    if constexpr (BF16_OUT) {
+        if constexpr (CACHED) reinterpret_cast<u32x2*>(out)[idx] = p;
+        else __builtin_nontemporal_store(p, reinterpret_cast<u32x2*>(out) + idx);
+    } else {
+        const f32x4 v = widen_bf16x4(p);
+        if constexpr (CACHED) reinterpret_cast<f32x4*>(out)[idx] = v;
+        else __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out) + idx);
+    }
+}
+
 // SPEC.md §3 "Initial row", four consecutive elements starting at j0
 __device__ __forceinline__ float4 initial_row4(int64_t key, uint32_t j0, uint32_t initializer, float init_scale,
                                                uint64_t init_seed, float default_value) {

@@ -23,17 +23,10 @@ namespace mee {
 // (cached stores) act in the compiled shapes (DIM4 16 / 32); the run-time shape (DIM4 = 0) loads and stores cached whatever they say, as the fp32
 // run-time path does (bit 2, the bucket loads, acts in every shape).  The instances with BROWS = false are the code they were before the parameter existed.
 
-// the store of one element group of a bf16 ROW: verbatim into a bf16 output, widened into an fp32 one; CACHED as store_bf16x4
+// the store of one element group of a bf16 ROW (store_brow_as, meepo_device.h) under find_span's NT bits
 template <int NT, bool CACHED>
 __device__ __forceinline__ void store_brow(f32x4* __restrict__ out, uint64_t idx, const u32x2 p) {
-    if constexpr ((NT & 256) != 0) {
-        if constexpr (CACHED) reinterpret_cast<u32x2*>(out)[idx] = p;
-        else __builtin_nontemporal_store(p, reinterpret_cast<u32x2*>(out) + idx);
-    } else {
-        const f32x4 v = widen_bf16x4(p);
-        if constexpr (CACHED) out[idx] = v;
-        else __builtin_nontemporal_store(v, &out[idx]);
-    }
+    store_brow_as<(NT & 256) != 0, CACHED>(out, idx, p);
 }
 
 // the find of n positions by `n_waves` waves of which this is wave `wave` (each wave step takes 4R consecutive positions)
@@ -338,8 +331,10 @@ __device__ __forceinline__ bool jagged_member(const uint64_t* __restrict__ membe
 // TIERED (mee_find_pooled_tiered; one hot/cold pair, unweighted): the table arguments are the HOT table's, `tier` brings the cold one — the
 // fetch step probes both per position (pooled_fetch_tiered, meepo_device.h); the accumulation below is the same code.  The instances with
 // TIERED = false never read `tier` and are the code they were before the parameter existed.
-// BROWS (one bf16-row table, unweighted: SPEC.md §3 "Row storage type"): `values_` is a bf16-row plane — pooled_fetch widens each row at its load; the
-// accumulation below is the same code.  The instances with BROWS = false are the code they were before the parameter existed.
+// BROWS (one bf16-row table, or with GROUPED a bf16-row group — every member's plane, JAGGED included; unweighted: SPEC.md §3 "Row storage type"): the
+// value plane (`values_`, or the member descriptor's) is a bf16-row plane — pooled_fetch widens each row at its load; the accumulation below is the same
+// code.  One storage type per group, so this is a property of the launch, never a per-member branch in the fetch.  The instances with BROWS = false are
+// the code they were before the parameter existed.
 template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false, bool JAGGED = false, bool TIERED = false, bool BROWS = false>
 __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restrict__ tkeys_, const float4* __restrict__ values_,
                                                           uint64_t nb_, const int64_t* __restrict__ keys,
@@ -352,7 +347,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                                                           uint32_t n_members = 0, TierArgs tier = {}) {
     static_assert(!JAGGED || (GROUPED && !WEIGHTED && !BF16), "the jagged map is the group's plain fp32 lookup");
     static_assert(!TIERED || (!GROUPED && !WEIGHTED && !JAGGED), "the tiered form is one pair's plain sum / mean");
-    static_assert(!BROWS || (!GROUPED && !WEIGHTED && !JAGGED && !TIERED), "bf16 rows: one table's plain sum / mean");
+    static_assert(!BROWS || (!WEIGHTED && !TIERED), "bf16 rows: the plain sum / mean of one table or of a bf16-row group (jagged map included)");
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
@@ -402,7 +397,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                     if constexpr (WEIGHTED) wv[u] = __shfl(wpre, tile * 16 + (int)((pos[u] - begin) & 15));
                 }
                 if constexpr (TIERED) pooled_fetch_tiered<DIM4, U, C>(tkeys, values, nb, tier, dim4, kv, pos, inb, tile, tl, def4, row, found);
-                else pooled_fetch<DIM4, U, C, TAGGED, BROWS>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located,
+                else pooled_fetch<DIM4, U, C, TAGGED, BROWS>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, (GROUPED && BROWS) ? nullptr : located,   // (a bf16-row group hands out no located rows: refused at the entry points)
                                                       GROUPED ? member << kGroupSlotBits : (TAGGED ? (uint64_t)handle_tag : 0));
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
@@ -461,7 +456,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                     if constexpr (WEIGHTED) wv[u] = inb[u] ? weights[pos[u]] : 0.f;   // next to the key
                 }
                 if constexpr (TIERED) pooled_fetch_tiered<DIM4, U, C>(tkeys, values, nb, tier, dim4, kv, pos, inb, tile, tl, def4, row, found);
-                else pooled_fetch<DIM4, U, C, TAGGED, BROWS>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located,
+                else pooled_fetch<DIM4, U, C, TAGGED, BROWS>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, (GROUPED && BROWS) ? nullptr : located,   // (a bf16-row group hands out no located rows: refused at the entry points)
                                                       GROUPED ? member << kGroupSlotBits : (TAGGED ? (uint64_t)handle_tag : 0));
 #pragma unroll
                 for (int u = 0; u < U; ++u)
@@ -1003,6 +998,7 @@ static int group_find_pooled_common(mee_group* g, const int64_t* d_keys, size_t 
             kernel<<<grid, 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, mode == MEE_POOL_MEAN, g->d_desc, bags_per_table,
                                          d_located_out, n, d_weights, 0, nullptr, 0, TierArgs{});
         };
+        if constexpr (!weighted) { if (g->bf16_rows) { launch(find_pooled_kernel<d4, u, bpw, true, false, bf16, false, false, true>); return; } }   // (weighted: refused at the entry points)
         launch(find_pooled_kernel<d4, u, bpw, true, weighted, bf16>);
     }); }); });
     MEE_HIP(hipGetLastError());
@@ -1012,6 +1008,7 @@ static int group_find_pooled_common(mee_group* g, const int64_t* d_keys, size_t 
 int mee_group_find_pooled(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
                           float* d_out, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
     MEE_RANGE("mee_group_find_pooled");
+    if (d_located_out) MEE_FP32_GROUP_ONLY(g, "mee_group_find_pooled", "d_located_out (the located rows serve the backward) is");
     if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled: null argument");
     if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
     return group_find_pooled_common(g, d_keys, n, d_bag_offsets, bags_per_table, nullptr, d_out, MEE_DTYPE_F32, d_found, d_located_out, mode, stream);
@@ -1021,6 +1018,7 @@ int mee_group_find_pooled(mee_group* g, const int64_t* d_keys, size_t n, const u
 int mee_group_find_pooled_jagged(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
                                  const uint64_t* d_member_bags, float* d_out, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
     MEE_RANGE("mee_group_find_pooled_jagged");
+    if (d_located_out) MEE_FP32_GROUP_ONLY(g, "mee_group_find_pooled_jagged", "d_located_out (the located rows serve the backward) is");
     if (!g || (n_bags && (!d_bag_offsets || !d_member_bags || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_jagged: null argument");
     if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_jagged: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
     if (n_bags == 0) return MEE_OK;
@@ -1028,10 +1026,10 @@ int mee_group_find_pooled_jagged(mee_group* g, const int64_t* d_keys, size_t n, 
     if (int rc = group_refresh(g, stream)) return rc;
     DeviceGuard guard(g->device);
     hipStream_t st = as_stream(stream);
-    with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
-        find_pooled_kernel<d4, u, bpw, true, false, false, true><<<grid, 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4,
-                                                                                       mode == MEE_POOL_MEAN, g->d_desc, 1, d_located_out, n, nullptr, 0, d_member_bags, g->n_tables);
-    });
+    with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(g->bf16_rows, [&](auto brows) {
+        find_pooled_kernel<d4, u, bpw, true, false, false, true, false, brows><<<grid, 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4,
+                                                                                                     mode == MEE_POOL_MEAN, g->d_desc, 1, d_located_out, n, nullptr, 0, d_member_bags, g->n_tables);
+    }); });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -1039,6 +1037,7 @@ int mee_group_find_pooled_jagged(mee_group* g, const int64_t* d_keys, size_t n, 
 int mee_group_find_pooled_weighted(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
                                    const float* d_weights, float* d_out, uint8_t* d_found, int64_t* d_located_out, void* stream) {
     MEE_RANGE("mee_group_find_pooled_weighted");
+    MEE_FP32_GROUP_ONLY(g, "mee_group_find_pooled_weighted");
     if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && (!d_keys || !d_weights)))
         return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_weighted: null argument");
     return group_find_pooled_common(g, d_keys, n, d_bag_offsets, bags_per_table, d_weights /* null only with n = 0 */, d_out, MEE_DTYPE_F32, d_found, d_located_out, MEE_POOL_SUM, stream);
@@ -1047,6 +1046,8 @@ int mee_group_find_pooled_weighted(mee_group* g, const int64_t* d_keys, size_t n
 int mee_group_find_pooled_as(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights,
                              void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
     MEE_RANGE("mee_group_find_pooled_as");
+    if (d_weights) MEE_FP32_GROUP_ONLY(g, "mee_group_find_pooled_as", "the weighted form (d_weights) is");
+    if (d_located_out) MEE_FP32_GROUP_ONLY(g, "mee_group_find_pooled_as", "d_located_out (the located rows serve the backward) is");
     if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_as: null argument");
     if (int rc = check_out_dtype(d_out, out_dtype, "mee_group_find_pooled_as")) return rc;
     if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_as: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
@@ -1058,6 +1059,7 @@ int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, cons
                                        size_t bags_per_table, const float* d_weights, const float* d_bag_grads, float* d_grads_out,
                                        float* d_weight_grads_out, void* stream) {
     MEE_RANGE("mee_group_pooled_weighted_backward");
+    MEE_FP32_GROUP_ONLY(g, "mee_group_pooled_weighted_backward");
     if (!g || (bags_per_table && (!d_bag_offsets || !d_bag_grads)) || (n && (!d_keys || !d_weights || !d_grads_out)))
         return fail(MEE_ERR_INVALID_ARG, "mee_group_pooled_weighted_backward: null argument");
     if (bags_per_table == 0) return MEE_OK;

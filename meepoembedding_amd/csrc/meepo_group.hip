@@ -23,7 +23,11 @@ namespace mee {
 // LOCATE: no rows move; gslot[i] = member << 48 | slot of the key (kEmpty when absent / reserved / outside the segments) —
 // the first pass of a grouped apply.
 // BF16: `out` holds bf16 rows (SPEC.md §3 "Output type"): the lane's float4 leaves as 4 bf16 in one 8-byte store; BF16 = false is the code it was.
-template <int DIM4, int R, bool STREAM_OUT, bool LOCATE = false, bool BF16 = false>
+// BROWS: a bf16-row group (SPEC.md §3 "Row storage type") — every member's `values` is a bf16-row plane.  Same tiles, same index arithmetic as find_span's
+// BROWS path: the lane's element group is 8 bytes (u32x2) at slot * dim4 + c * 16 + tl; with bf16 out the 8 bytes leave as they came (no second rounding),
+// with fp32 out they are widened in registers; a member's default row is packed from its defv, which is a bf16 value already.  One storage type per group:
+// a property of the launch, not a per-member branch.  The instances with BROWS = false are the code they were before the parameter existed.
+template <int DIM4, int R, bool STREAM_OUT, bool LOCATE = false, bool BF16 = false, bool BROWS = false>
 __global__ __launch_bounds__(256) void find_grouped_kernel(const GroupDesc* __restrict__ desc, uint32_t n_tables,
                                                            const uint64_t* __restrict__ offsets, const int64_t* __restrict__ keys,
                                                            uint64_t n, float4* __restrict__ out, uint8_t* __restrict__ found,
@@ -74,7 +78,34 @@ __global__ __launch_bounds__(256) void find_grouped_kernel(const GroupDesc* __re
             }
             continue;
         }
-        if constexpr (DIM4 != 0) {
+        if constexpr (BROWS) {
+            static_assert(!LOCATE, "bf16 rows: the lookups only");
+            if constexpr (DIM4 != 0) {
+                u32x2 row[R][C];
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+#pragma unroll
+                    for (int c = 0; c < C; ++c)
+                        row[r][c] = slot[r] >= 0 ? reinterpret_cast<const u32x2*>(d[r].values)[(uint64_t)slot[r] * DIM4 + c * 16 + tl]
+                                                 : bf16x4_of(d[r].defv, d[r].defv, d[r].defv, d[r].defv);
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const uint64_t i = base + r * 4 + tile;
+                    if (inb[r])
+#pragma unroll
+                        for (int c = 0; c < C; ++c) store_brow_as<BF16, !STREAM_OUT>(out, i * DIM4 + c * 16 + tl, row[r][c]);
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const uint64_t i = base + r * 4 + tile;
+                    if (inb[r])
+                        for (uint32_t c = tl; c < dim4; c += 16)
+                            store_brow_as<BF16, true>(out, i * dim4 + c, slot[r] >= 0 ? reinterpret_cast<const u32x2*>(d[r].values)[(uint64_t)slot[r] * dim4 + c]
+                                                                                       : bf16x4_of(d[r].defv, d[r].defv, d[r].defv, d[r].defv));
+                }
+            }
+        } else if constexpr (DIM4 != 0) {
             float4 row[R][C];
 #pragma unroll
             for (int r = 0; r < R; ++r)
@@ -184,7 +215,7 @@ static int upload_descriptors(mee_group* g) {
     std::vector<GroupInit> hi(g->n_tables);
     for (uint32_t j = 0; j < g->n_tables; ++j) {
         const TableView v = table_view(g->tables[j]);
-        h[j] = GroupDesc{v.keys, (float4*)v.values, (float4*)v.s1, (float4*)v.s2, v.nb, v.default_value, 0};
+        h[j] = GroupDesc{v.keys, (float4*)v.values, (float4*)v.s1, (float4*)v.s2, v.nb, v.default_value, 0};   // (a bf16-row member: its bf16 plane behind the same pointer — the launch knows, g->bf16_rows)
         hi[j] = GroupInit{v.init_seed, v.status, v.hits, v.initializer, v.optimizer, v.init_scale, v.init_acc};
         g->generations[j] = v.generation;
     }
@@ -219,8 +250,14 @@ int mee_group_create(mee_table* const* tables, uint32_t n_tables, uint64_t max_a
     *out = nullptr;
     for (uint32_t j = 0; j < n_tables; ++j)
         if (!tables[j]) return fail(MEE_ERR_INVALID_ARG, "mee_group_create: table %u is null", j);
-    for (uint32_t j = 0; j < n_tables; ++j) MEE_FP32_ROWS_ONLY(tables[j], "mee_group_create");   // covers every mee_group_* operator
     const TableView v0 = table_view(tables[0]);
+    // one row storage type per group: it is a compile-time property of every launch (the BROWS instances), not a per-member branch in the row fetch
+    for (uint32_t j = 1; j < n_tables; ++j)
+        if (table_view(tables[j]).bf16_rows != v0.bf16_rows)
+            return fail(MEE_ERR_UNSUPPORTED, "mee_group_create: table %u is %s and table 0 is %s — a group holds fp32-row tables or bf16-row table members (MEE_FLAG_BF16_ROWS), never both",
+                        j, v0.bf16_rows ? "an fp32-row table" : "a bf16-row table", v0.bf16_rows ? "a bf16-row table" : "an fp32-row table");
+    if (v0.bf16_rows && max_apply_batch)
+        return fail(MEE_ERR_INVALID_ARG, "mee_group_create: max_apply_batch must be 0 for a group of bf16-row tables (a serving group has no step and no scratch table)");
     for (uint32_t j = 1; j < n_tables; ++j) {
         const TableView v = table_view(tables[j]);
         if (v.device != v0.device || v.dim != v0.dim)
@@ -231,7 +268,7 @@ int mee_group_create(mee_table* const* tables, uint32_t n_tables, uint64_t max_a
     if (max_apply_batch > (1ull << 30)) return fail(MEE_ERR_INVALID_ARG, "mee_group_create: max_apply_batch must be <= 2^30");
     mee_group* g = new (std::nothrow) mee_group();
     if (!g) return fail(MEE_ERR_OUT_OF_MEMORY, "host allocation failed");
-    g->device = v0.device; g->n_tables = n_tables; g->dim = v0.dim; g->dim4 = v0.dim4; g->d_desc = nullptr;
+    g->device = v0.device; g->n_tables = n_tables; g->dim = v0.dim; g->dim4 = v0.dim4; g->bf16_rows = v0.bf16_rows; g->d_desc = nullptr;
     g->optimizer = v0.optimizer; g->max_apply_batch = max_apply_batch; g->scratch = nullptr; g->d_gslot = nullptr;
     g->d_init = nullptr; g->d_fmask = nullptr;
     g->tables.assign(tables, tables + n_tables);
@@ -252,6 +289,12 @@ int mee_group_create(mee_table* const* tables, uint32_t n_tables, uint64_t max_a
         if (rc != MEE_OK) { mee_group_destroy(g); return rc; }
     }
     *out = g;
+    return MEE_OK;
+}
+
+int mee_group_value_dtype(const mee_group* g, uint32_t* out) {
+    if (!g || !out) return fail(MEE_ERR_INVALID_ARG, "mee_group_value_dtype: null argument");
+    *out = g->bf16_rows ? MEE_DTYPE_BF16 : MEE_DTYPE_F32;
     return MEE_OK;
 }
 
@@ -286,7 +329,10 @@ static int launch_find_grouped(mee_group* g, const int64_t* d_keys, const uint64
     const unsigned grid_cap = 8192;
     with_row_shape(g->dim4, [&](auto d4) { with_flag(stream_out, [&](auto so) {
         constexpr int R = RowShape<d4>::rows_per_tile;   // (a block: 16 tiles of R keys in flight)
-        if (bf16) find_grouped_kernel<d4, R, so, false, true><<<grid_for(n, 16 * R, grid_cap), 256, 0, st>>>(g->d_desc, g->n_tables, d_offsets, d_keys, n, (float4*)d_out, d_found, g->dim4);
+        if (g->bf16_rows) with_flag(bf16, [&](auto b16) {   // a bf16-row group: the BROWS instances, fp32 or bf16 out
+            find_grouped_kernel<d4, R, so, false, b16, true><<<grid_for(n, 16 * R, grid_cap), 256, 0, st>>>(g->d_desc, g->n_tables, d_offsets, d_keys, n, (float4*)d_out, d_found, g->dim4);
+        });
+        else if (bf16) find_grouped_kernel<d4, R, so, false, true><<<grid_for(n, 16 * R, grid_cap), 256, 0, st>>>(g->d_desc, g->n_tables, d_offsets, d_keys, n, (float4*)d_out, d_found, g->dim4);
         else find_grouped_kernel<d4, R, so><<<grid_for(n, 16 * R, grid_cap), 256, 0, st>>>(g->d_desc, g->n_tables, d_offsets, d_keys, n, (float4*)d_out, d_found, g->dim4);
     }); });
     MEE_HIP(hipGetLastError());
@@ -305,6 +351,7 @@ static int find_grouped_common(mee_group* g, const int64_t* d_keys, const uint64
 
 static int group_find_or_insert_common(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
                                        void* stream, const char* name) {
+    MEE_FP32_GROUP_ONLY(g, name);
     if (!g || !d_offsets || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
     if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
     if (n == 0) return MEE_OK;

@@ -80,6 +80,7 @@ struct TableView {
     uint64_t init_seed;
     uint32_t* status;
     uint32_t* hits;
+    bool bf16_rows;        // the value plane holds bf16 rows (MEE_FLAG_BF16_ROWS): `values` is then dim4 8-byte groups per slot
 };
 TableView table_view(const mee_table* t);
 // The operators a bf16-row table does not have (include/meepo_embedding.h, MEE_FLAG_BF16_ROWS) — and every create that takes tables — say so through
@@ -144,6 +145,7 @@ template <int DIM4> struct RowShape {   // what the row kernels' launches share 
 struct mee_group {
     int device;
     uint32_t n_tables, dim, dim4, optimizer;
+    bool bf16_rows;        // every member is a bf16-row table (a serving group: lookups only); false: every member stores fp32 rows.  Never mixed (mee_group_create)
     std::vector<mee_table*> tables;
     std::vector<uint64_t> generations;   // of each table when its descriptor was last uploaded (mee_reserve moves planes)
     mee::GroupDesc* d_desc;
@@ -158,4 +160,9 @@ struct mee_group {
 namespace mee {
 int group_refresh(mee_group* g, void* stream);   // re-upload descriptors of members whose planes moved
 int group_locate(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, uint64_t off_stride, size_t n, int64_t* d_gslot, hipStream_t st);
+// refuse_bf16_rows for a group: the operators a bf16-row group does not have (include/meepo_embedding.h, the group section) say so through this one check,
+// before they launch or write anything: MEE_ERR_UNSUPPORTED naming `op` (and `what` of it, when only an argument is refused), MEE_OK for an fp32 group or a
+// null one (defined next to refuse_bf16_rows in meepo_table.hip)
+int refuse_bf16_group(const mee_group* g, const char* op, const char* what = nullptr);
+#define MEE_FP32_GROUP_ONLY(g, ...) do { if (int rc_ = ::mee::refuse_bf16_group((g), __VA_ARGS__)) return rc_; } while (0)
 }

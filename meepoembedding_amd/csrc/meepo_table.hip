@@ -433,12 +433,18 @@ template <int P> __global__ __launch_bounds__(256) void ensure_direct_bf16_kerne
 // =========================================================================================================
 TableView table_view(const mee_table* t) {
     return TableView{t->device, t->keys, t->values, t->nb, t->dim, t->dim4, t->default_value, t->generation, t->s1, t->s2, t->optimizer,
-                     t->initializer, t->init_scale, t->init_acc, t->init_seed, &t->ctr->status, t->hits};
+                     t->initializer, t->init_scale, t->init_acc, t->init_seed, &t->ctr->status, t->hits, t->bf16_rows};
 }
 
 int refuse_bf16_rows(const mee_table* t, const char* op) {
     if (t && t->bf16_rows)
         return fail(MEE_ERR_UNSUPPORTED, "%s: not available on a bf16-row table (MEE_FLAG_BF16_ROWS: a serving table has find, find_pooled, insert, assign, remove, locate, export and reserve)", op);
+    return MEE_OK;
+}
+int refuse_bf16_group(const mee_group* g, const char* op, const char* what) {
+    if (g && g->bf16_rows)
+        return fail(MEE_ERR_UNSUPPORTED, "%s: %s not available on a group of bf16-row table members (a serving group has find_grouped, group_find_pooled unweighted and group_find_pooled_jagged)",
+                    op, what ? what : "the operator is");
     return MEE_OK;
 }
 
@@ -928,6 +934,7 @@ static int group_apply_common(mee_group* g, const int64_t* d_keys, const uint64_
 int mee_group_apply_adagrad(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr,
                             float eps, void* stream) {
     MEE_RANGE("mee_group_apply_adagrad");
+    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_adagrad");
     OptArgs a{};
     a.kind = MEE_OPT_ADAGRAD; a.lr = lr; a.eps = eps;
     return group_apply_common(g, d_keys, d_offsets, d_grads, n, a, stream, "mee_group_apply_adagrad");
@@ -935,6 +942,7 @@ int mee_group_apply_adagrad(mee_group* g, const int64_t* d_keys, const uint64_t*
 int mee_group_apply_adam(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr,
                          float beta1, float beta2, float eps, uint64_t step, void* stream) {
     MEE_RANGE("mee_group_apply_adam");
+    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_adam");
     if (step == 0) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_adam: step must be >= 1");
     return group_apply_common(g, d_keys, d_offsets, d_grads, n, adam_args(lr, beta1, beta2, eps, step), stream, "mee_group_apply_adam");
 }
@@ -943,6 +951,7 @@ int mee_group_apply_adagrad_pooled(mee_group* g, const int64_t* d_keys, const ui
                                    const float* d_bag_grads, const uint32_t* d_grad_index, const int64_t* d_located, size_t n, float lr,
                                    float eps, void* stream) {
     MEE_RANGE("mee_group_apply_adagrad_pooled");
+    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_adagrad_pooled");
     if (n && (!d_grad_index || !bags_per_table)) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_adagrad_pooled: null index / zero bags_per_table");
     OptArgs a{};
     a.kind = MEE_OPT_ADAGRAD; a.lr = lr; a.eps = eps;
@@ -955,6 +964,7 @@ int mee_group_apply_adam_pooled(mee_group* g, const int64_t* d_keys, const uint6
                                 const float* d_bag_grads, const uint32_t* d_grad_index, const int64_t* d_located, size_t n, float lr,
                                 float beta1, float beta2, float eps, uint64_t step, void* stream) {
     MEE_RANGE("mee_group_apply_adam_pooled");
+    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_adam_pooled");
     if (step == 0) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_adam_pooled: step must be >= 1");
     if (n && (!d_grad_index || !bags_per_table)) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_adam_pooled: null index / zero bags_per_table");
     OptArgs a = adam_args(lr, beta1, beta2, eps, step);
@@ -969,6 +979,7 @@ static int check_grad_rows(size_t n, const uint32_t* d_grad_index, size_t n_grad
 int mee_group_apply_adagrad_indexed(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows,
                                     const uint32_t* d_grad_index, size_t n, float lr, float eps, void* stream) {
     MEE_RANGE("mee_group_apply_adagrad_indexed");
+    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_adagrad_indexed");
     if (int rc = check_grad_rows(n, d_grad_index, n_grad_rows, "mee_group_apply_adagrad_indexed")) return rc;
     OptArgs a{};
     a.kind = MEE_OPT_ADAGRAD; a.lr = lr; a.eps = eps; a.grad_rows = (uint32_t)n_grad_rows;
@@ -977,6 +988,7 @@ int mee_group_apply_adagrad_indexed(mee_group* g, const int64_t* d_keys, const u
 int mee_group_apply_adam_indexed(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows,
                                  const uint32_t* d_grad_index, size_t n, float lr, float beta1, float beta2, float eps, uint64_t step, void* stream) {
     MEE_RANGE("mee_group_apply_adam_indexed");
+    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_adam_indexed");
     if (step == 0) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_adam_indexed: step must be >= 1");
     if (int rc = check_grad_rows(n, d_grad_index, n_grad_rows, "mee_group_apply_adam_indexed")) return rc;
     OptArgs a = adam_args(lr, beta1, beta2, eps, step);

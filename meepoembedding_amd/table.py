@@ -641,14 +641,20 @@ class TableGroup:
     """One find launch for the lookups of many tables (same device, same dim): mee_find_grouped.
 
     keys = the tables' key batches concatenated, offsets = n_tables + 1 int64/uint64 bounds ON THE DEVICE (segment j =
-    keys[offsets[j]:offsets[j+1]]).  Returns (rows [n, dim], found [n]) — identical to find() per table."""
+    keys[offsets[j]:offsets[j+1]]).  Returns (rows [n, dim], found [n]) — identical to find() per table.
+
+    Members that are ALL bf16-row tables (value_dtype == torch.bfloat16) make a bf16-row group, the serving form of a collection (serving_copy() builds
+    it from a trained group): find, find_pooled (unweighted, no located buffer) and find_pooled_jagged, each bit for bit the per-member lookup; every
+    training method raises MeepoError(ERR_UNSUPPORTED).  fp32-row and bf16-row tables never share a group."""
     supports_out_dtype = True
 
     def __init__(self, tables, max_apply_batch: int = 0):
         self.tables = list(tables)
         if not self.tables:
             raise ValueError("a group needs at least one table")
-        _lib.refuse_bf16_rows("TableGroup", *self.tables)
+        self.value_dtype = _lib.group_row_dtype("TableGroup", *self.tables)
+        if self.value_dtype == torch.bfloat16 and max_apply_batch != 0:   # before any device is needed (the library checks again)
+            raise ValueError("a group of bf16-row tables is a serving group: max_apply_batch must be 0 (it has no optimizer step)")
         self.device, self.dim = self.tables[0].device, self.tables[0].dim
         arr = (C.c_void_p * len(self.tables))(*[t._h for t in self.tables])
         h = C.c_void_p()
@@ -676,6 +682,22 @@ class TableGroup:
     def set_tuning(self, name: str, value: int) -> None:
         """Performance knobs of the group's own apply ("apply_kernel", "apply_skew_adapt", …: mee_set_tuning); never change results."""
         check(_lib.lib().mee_group_set_tuning(self._h, name.encode(), int(value)))
+
+    def serving_copy(self, chunk: int = 1 << 22) -> "TableGroup":
+        """The train -> serve step in memory: a bf16-row TableGroup over NEW tables, one per member, of the member's capacity, device and default value
+        (rounded), filled with the member's rows — values only, rounded once on the way in — one `chunk`-slot export piece at a time, the way
+        LookupTable.resized() copies.  This group and its members are left as they are.  dim must be a multiple of 8, the members in HBM."""
+        if self.dim % 8:
+            raise ValueError(f"serving_copy needs dim to be a multiple of 8 (got {self.dim}): a bf16 row is dim / 8 16-byte groups")
+        if any(t._opts["value_memory"] != _lib.MEM_HBM for t in self.tables):
+            raise ValueError("serving_copy needs every member in HBM (value_memory = MEM_HBM): a bf16-row table is no cold tier")
+        copies = []
+        for t in self.tables:
+            new = LookupTable(t.capacity, t.dim, device=t.device, max_batch=t.max_batch, default_value=t._opts["default_value"], value_dtype=torch.bfloat16)
+            for ek, ev, _, _ in t.iter_export(chunk, with_state=False):   # bounded scratch: one slot range at a time
+                new.import_(ek, ev)
+            copies.append(new)
+        return TableGroup(copies)
 
     def _check_offsets(self, offsets: torch.Tensor) -> None:
         if offsets.device != self.device or offsets.dtype not in (torch.int64, torch.uint64) or offsets.numel() != len(self.tables) + 1 \
