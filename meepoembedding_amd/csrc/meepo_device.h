@@ -164,7 +164,7 @@ __device__ __forceinline__ f32x4 widen_bf16x4(const u32x2 p) {
 }
 
 // ---- pooled lookups (meepo_find.hip: one table and the uniform group; meepo_mixed.hip: the mixed group) ------------------------------
-// a bag of this many keys or more is served by the wave's four tiles together (find_pooled_kernel)
+// a bag of this many keys or more is served by the wave's four tiles together (pooled_bags)
 constexpr uint32_t kPoolLong = 16;
 
 // probe + row load of up to U keys per tile (the find_kernel pattern); row[u] is only defined where inb[u].
@@ -317,6 +317,185 @@ __device__ __forceinline__ void store_brow_as(void* __restrict__ out, uint64_t i
         const f32x4 v = widen_bf16x4(p);
         if constexpr (CACHED) reinterpret_cast<f32x4*>(out)[idx] = v;
         else __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out) + idx);
+    }
+}
+
+// ---- the bag walk of the pooled lookups and of their backward ------------------------------------------------------------------
+// Geometry: a wave step serves BPW consecutive bags.  BPW = 4: tile t takes bag `bag0 + t`; a bag of fewer than kPoolLong keys is walked by its
+// tile alone, U positions a round (its keys and weights come with ONE coalesced load per tile, lane tl holds position begin + tl, and reach the
+// rounds by shuffles); then every bag of kPoolLong keys or more is walked by the four tiles together, tile t on positions i + 4u + t.  BPW = 1: the
+// wave walks bag0 that way whatever its length.  Three callers: find_pooled_kernel and pooled_weighted_backward_kernel (meepo_find.hip),
+// mixed_find_pooled_kernel (meepo_mixed.hip).
+
+// what a walk needs of the table a bag belongs to: its planes, its default row, and the tag of its located rows (pooled_fetch)
+struct PooledTable {
+    const int64_t* tkeys;
+    const float4* values;
+    uint64_t nb;
+    float4 def4;
+    uint64_t tag;
+};
+
+// ... of a group member: Desc = GroupDesc (meepo_host.h); its located rows carry the member above the slot bits
+template <class Desc>
+__device__ __forceinline__ PooledTable pooled_table(const Desc& d, uint64_t member, int slot_bits) {
+    return PooledTable{d.tkeys, d.values, d.nb, make_float4(d.defv, d.defv, d.defv, d.defv), member << slot_bits};
+}
+
+// the key span of a bag.  Offsets are the caller's: a bag never reaches past the key array, and a decreasing pair is an empty bag
+__device__ __forceinline__ void pooled_span(const uint64_t* __restrict__ offsets, uint64_t bag, bool has, uint64_t n_keys, uint64_t& begin, uint64_t& end) {
+    begin = has ? offsets[bag] : 0; end = has ? offsets[bag + 1] : 0;
+    end = end < n_keys ? end : n_keys;
+    begin = begin < end ? begin : end;
+}
+
+// a short bag [begin, end) has fewer than 16 keys: lane tl of its tile loads key (and weight) begin + tl ...
+template <bool WEIGHTED>
+__device__ __forceinline__ void pooled_short_prefetch(const int64_t* __restrict__ keys, const float* __restrict__ weights, uint64_t begin, uint64_t end,
+                                                      bool is_long, int tl, int64_t& kpre, float& wpre) {
+    kpre = (!is_long && begin + tl < end) ? keys[begin + tl] : kEmpty;
+    wpre = 0.f;
+    if constexpr (WEIGHTED) wpre = (!is_long && begin + tl < end) ? weights[begin + tl] : 0.f;
+}
+// ... and a round of the tile takes positions i .. i + U - 1 out of those registers (wv only with WEIGHTED)
+template <int U, bool WEIGHTED>
+__device__ __forceinline__ void pooled_short_positions(uint64_t i, uint64_t begin, uint64_t end, int64_t kpre, float wpre, int tile, uint64_t (&pos)[U],
+                                                       int64_t (&kv)[U], float (&wv)[U], bool (&inb)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        pos[u] = i + u; inb[u] = pos[u] < end;
+        kv[u] = __shfl(kpre, tile * 16 + (int)((pos[u] - begin) & 15));
+        if constexpr (WEIGHTED) wv[u] = __shfl(wpre, tile * 16 + (int)((pos[u] - begin) & 15));
+    }
+}
+// a round of the four tiles on one long bag: positions i .. i + 4U - 1 (< eq), tile t takes i + 4u + t, the weight loaded next to the key
+template <int U, bool WEIGHTED>
+__device__ __forceinline__ void pooled_long_positions(uint64_t i, uint64_t eq, const int64_t* __restrict__ keys, const float* __restrict__ weights, int tile,
+                                                      uint64_t (&pos)[U], int64_t (&kv)[U], float (&wv)[U], bool (&inb)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        pos[u] = i + (uint64_t)u * 4 + tile; inb[u] = pos[u] < eq; kv[u] = inb[u] ? keys[pos[u]] : kEmpty;
+        if constexpr (WEIGHTED) wv[u] = inb[u] ? weights[pos[u]] : 0.f;
+    }
+}
+
+// one element group of the next row joins the running sum: the product rounded first (WEIGHTED), then the sum, no fma (the library is built with
+// -ffp-contract=off); the first row is ASSIGNED — a bag whose first row holds -0.0 keeps it
+template <bool WEIGHTED>
+__device__ __forceinline__ void pooled_add(float4& acc, float4 v, float w, bool first) {
+    if constexpr (WEIGHTED) { v.x = w * v.x; v.y = w * v.y; v.z = w * v.z; v.w = w * v.w; }
+    if (first) acc = v;
+    else { acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w; }
+}
+
+// the finished row of a bag of `len` keys goes to the element groups out[o ...]: the mean's division only for a bag that has keys, and a bf16 row
+// is rounded here, once
+template <int DIM4, int C, bool BF16>
+__device__ __forceinline__ void pooled_store(float4* __restrict__ out, uint64_t o, const float4 (&acc)[C], uint64_t len, int mean, uint32_t dim4, int tl) {
+    const float flen = (float)len;
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+        if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
+            float4 v = acc[c];
+            if (mean && len > 0) { v.x = v.x / flen; v.y = v.y / flen; v.z = v.z / flen; v.w = v.w / flen; }
+            if constexpr (BF16) store_bf16x4<true>(out, o + c * 16 + tl, v); else out[o + c * 16 + tl] = v;
+        }
+}
+
+// The bags one wave serves in one step of a pooled lookup (SPEC.md §3): bags bag0 .. bag0 + nvalid - 1 (nvalid <= BPW; bag0 exists), the row of bag b =
+// the rows of its keys added up in position order (pooled_add), divided for the mean, stored at out[row_of(b) ...] (pooled_store).  The partial sum of
+// a bag lives in registers, so a bag costs ONE output row.  In the long phase every tile adds the 4U rows of a round in position order out of the other
+// tiles' registers (shuffles), so all four keep the same running sum and a long bag has 4U keys in flight instead of U.
+// What differs between the callers comes in two callables:
+//   table_of(b, PooledTable&) -> bool   fills in the table of bag b; false = the bag is to be treated as empty (a row of zeros, nothing probed)
+//   row_of(b) -> uint64_t               the index of bag b's output row, in element groups
+// With BPW = 4 the tiles of a wave may get different tables in the short phase; the long phase asks again for bag q and all four tiles switch to it.
+// C: float4 per lane per row.  TAGGED: absent keys leave -1 in `located` (the format of mee_find_located), otherwise EMPTY.  TIERED: `tier` brings the
+// cold table of a hot/cold pair, `located` is never read.  BROWS: the value planes hold bf16 rows, widened at their load (pooled_fetch).
+template <int DIM4, int U, int BPW, int C, bool WEIGHTED, bool BF16, bool TIERED, bool BROWS, bool TAGGED, class TableOf, class RowOf>
+__device__ __forceinline__ void pooled_bags(uint64_t bag0, uint32_t nvalid, uint32_t dim4, const int64_t* __restrict__ keys, const uint64_t* __restrict__ offsets,
+                                            uint64_t n_keys, const float* __restrict__ weights, float4* __restrict__ out, uint8_t* __restrict__ found,
+                                            int64_t* __restrict__ located, int mean, const TierArgs& tier, int tile, int tl, TableOf&& table_of, RowOf&& row_of) {
+    const uint64_t bag = BPW == 4 ? bag0 + tile : bag0;
+    const bool has = BPW == 4 ? (uint32_t)tile < nvalid : true;
+    uint64_t begin, end;
+    pooled_span(offsets, bag, has, n_keys, begin, end);
+    PooledTable t;
+    if (!table_of(has ? bag : bag0, t)) begin = end = 0;
+    const bool is_long = BPW == 1 || end - begin >= kPoolLong;
+    float4 acc[C];
+    float4 row[U][C];
+    auto fetch = [&](const int64_t (&kv)[U], const uint64_t (&pos)[U], const bool (&inb)[U]) {
+        if constexpr (TIERED) pooled_fetch_tiered<DIM4, U, C>(t.tkeys, t.values, t.nb, tier, dim4, kv, pos, inb, tile, tl, t.def4, row, found);
+        else pooled_fetch<DIM4, U, C, TAGGED, BROWS>(t.tkeys, t.values, t.nb, dim4, kv, pos, inb, tile, tl, t.def4, row, found, located, t.tag);
+    };
+    // ---- short bags: one tile per bag ----
+    if constexpr (BPW == 4) {
+        uint64_t i = is_long ? end : begin;
+        bool first = true;
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+        int64_t kpre;
+        float wpre;
+        pooled_short_prefetch<WEIGHTED>(keys, weights, begin, end, is_long, tl, kpre, wpre);
+        while (__any(i < end)) {  // wave-uniform; tiles whose bag is done idle through the ballots
+            uint64_t pos[U];
+            int64_t kv[U];
+            float wv[U];
+            bool inb[U];
+            pooled_short_positions<U, WEIGHTED>(i, begin, end, kpre, wpre, tile, pos, kv, wv, inb);
+            fetch(kv, pos, inb);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (!inb[u]) continue;
+#pragma unroll
+                for (int c = 0; c < C; ++c)
+                    if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) pooled_add<WEIGHTED>(acc[c], row[u][c], WEIGHTED ? wv[u] : 0.f, first);
+                first = false;
+            }
+            i += U;
+        }
+        if (has && !is_long) pooled_store<DIM4, C, BF16>(out, row_of(bag), acc, end - begin, mean, dim4, tl);
+    }
+    // ---- long bags: the four tiles share one bag at a time ----
+    const uint64_t long_mask = __ballot(is_long && has);
+    if (!long_mask) return;   // wave-uniform
+    for (int q = 0; q < BPW; ++q) {
+        if (!((long_mask >> (q * 16)) & 1)) continue;   // wave-uniform
+        // the span of bag q to every lane.  BPW = 1: every lane holds bag0's span already; using it without the broadcast is what keeps the bf16-row
+        // group's dim-128 instance at 7 waves per SIMD.  Not for the tiered instances: without the broadcast, as it is or as a scalar (readfirstlane),
+        // the pair's lookup on bags of 20 measures 5 % slower than with it — same occupancy, cause not found (profiles/pooled_shared_body.md §2)
+        constexpr bool OWN_SPAN = BPW == 1 && !TIERED;
+        const uint64_t bq = OWN_SPAN ? begin : __shfl(begin, q * 16), eq = OWN_SPAN ? end : __shfl(end, q * 16);
+        if constexpr (BPW == 4) (void)table_of(bag0 + q, t);   // all four tiles work for bag q's table now (a long bag is not empty)
+        bool first = true;
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (uint64_t i = bq; i < eq; i += 4 * U) {   // wave-uniform
+            uint64_t pos[U];
+            int64_t kv[U];
+            float wv[U];
+            bool inb[U];
+            pooled_long_positions<U, WEIGHTED>(i, eq, keys, weights, tile, pos, kv, wv, inb);
+            fetch(kv, pos, inb);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int src = 0; src < 4; ++src) {
+                    if (i + (uint64_t)u * 4 + src >= eq) continue;   // wave-uniform
+                    float w = 0.f;
+                    if constexpr (WEIGHTED) w = __shfl(wv[u], src * 16 + tl);
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        float4 v;   // every tile reads the row tile `src` fetched
+                        v.x = __shfl(row[u][c].x, src * 16 + tl); v.y = __shfl(row[u][c].y, src * 16 + tl);
+                        v.z = __shfl(row[u][c].z, src * 16 + tl); v.w = __shfl(row[u][c].w, src * 16 + tl);
+                        pooled_add<WEIGHTED>(acc[c], v, w, first);
+                    }
+                    first = false;
+                }
+        }
+        if (tile == 0) pooled_store<DIM4, C, BF16>(out, row_of(bag0 + q), acc, eq - bq, mean, dim4, tl);
     }
 }
 

@@ -296,12 +296,9 @@ __global__ __launch_bounds__(256) void find_missing_kernel(const int64_t* __rest
 }
 
 // ---- pooled find (SPEC.md §3): out[b,:] = the rows of bag b's keys added up in position order (sum | mean) ----------------
-// The partial sum of a bag lives in registers, so a bag costs ONE output row instead of one per key: with L keys per bag
-// the write traffic of the lookup drops from 256 B per key to 256/L.  Additions happen in position order (bit-exact
-// against a sequential sum).  A wave takes four consecutive bags.  Short bags: one tile per bag, U keys of the bag in
-// flight (all bucket lines requested, then all rows).  Bags of kPoolLong keys or more: the four tiles work on ONE bag
-// together — tile t probes positions i + 4u + t — and every tile then adds the 4U rows in position order out of the
-// other tiles' registers (shuffles), so a long bag has 4U keys in flight instead of U.
+// A bag costs ONE output row instead of one per key: with L keys per bag the write traffic of the lookup drops from 256 B per key
+// to 256/L.  The walk over a wave's bags and the accumulation are pooled_bags (meepo_device.h); the kernels here say which table a bag
+// belongs to and where its row goes.
 // JAGGED bag -> member map (mee_group_find_pooled_jagged): the member j with member_bags[j] <= bag < member_bags[j + 1], by an upper-bound
 // search over member_bags[1 .. n_members] (at most ten dependent reads of an L2-resident array for 1024 members).  The array is the
 // caller's: whatever it holds, the member stays inside [0, n_members); false = the bag lies outside [member_bags[0], member_bags[n_members]).
@@ -315,26 +312,19 @@ __device__ __forceinline__ bool jagged_member(const uint64_t* __restrict__ membe
     return lo < n_members && bag >= member_bags[0];
 }
 
-// BPW = bags per wave: 4 = the hybrid above (batches of mostly short bags), 1 = every bag gets a whole wave (batches whose
-// AVERAGE bag is long: a wave that had to walk four long bags one after the other would be latency-bound).
-// GROUPED (mee_group_find_pooled): bag b belongs to member table b / bags_per_table; the planes come from its descriptor.
-// WEIGHTED (mee_find_pooled_weighted / mee_group_find_pooled_weighted): position i adds weights[i] * row_i — the product rounded, then
-// the sum (no fma; the first position's product is the initial sum); SUM only.  A single table's located rows then carry its handle tag.
-// BF16: `out` holds bf16 rows — the FINISHED bag row (after the mean's division) is rounded once at its store (SPEC.md §3 "Output type");
-// the accumulation is the same fp32 code, and the fp32 instances (BF16 = false) are the code they were before the parameter existed.
-// JAGGED (mee_group_find_pooled_jagged; GROUPED, fp32, unweighted): the members' bag counts differ — bag b belongs to the member that
-// jagged_member finds in member_bags, and a bag outside the map is an empty bag (a row of zeros, nothing probed).  The instances
-// with JAGGED = false are the code they were before the parameter existed.
-// The loop body below has a COPY in mixed_bags (meepo_mixed.hip: the group whose members differ in dim; only the member lookup and the output
-// index differ there).  SPEC.md §3 defines the mixed group's result through this kernel's, so a change to the order of the additions, the
-// mean's division, the long-bag rule or the clamping of the offsets here has to be made there too (tests/test_mixed_groups.py compares them).
-// TIERED (mee_find_pooled_tiered; one hot/cold pair, unweighted): the table arguments are the HOT table's, `tier` brings the cold one — the
-// fetch step probes both per position (pooled_fetch_tiered, meepo_device.h); the accumulation below is the same code.  The instances with
-// TIERED = false never read `tier` and are the code they were before the parameter existed.
-// BROWS (one bf16-row table, or with GROUPED a bf16-row group — every member's plane, JAGGED included; unweighted: SPEC.md §3 "Row storage type"): the
-// value plane (`values_`, or the member descriptor's) is a bf16-row plane — pooled_fetch widens each row at its load; the accumulation below is the same
-// code.  One storage type per group, so this is a property of the launch, never a per-member branch in the fetch.  The instances with BROWS = false are
-// the code they were before the parameter existed.
+// BPW = bags per wave: 4 = a tile per short bag, the four tiles together on a long one (batches of mostly short bags), 1 = every bag gets
+// a whole wave (batches whose AVERAGE bag is long: a wave that had to walk four long bags one after the other would be latency-bound).
+// The body is pooled_bags per wave step (a group's four-bags-per-wave instances excepted: they keep a copy of the walk, see the loop), with two callables: table_of — the kernel's own table arguments for one table; with GROUPED
+// (mee_group_find_pooled) the descriptor of member b / bags_per_table; with JAGGED (mee_group_find_pooled_jagged: the members' bag counts
+// differ) that of the member jagged_member finds, and a bag outside the map is empty — and row_of, b * dim4.  The other parameters go
+// through to the walk:
+// WEIGHTED (mee_find_pooled_weighted / mee_group_find_pooled_weighted): position i adds weights[i] * row_i; SUM only.  A single table's
+// located rows then carry its handle tag and -1 for an absent key (TAGGED), a group's the member and EMPTY.
+// BF16: `out` holds bf16 rows (SPEC.md §3 "Output type").
+// TIERED (mee_find_pooled_tiered; one hot/cold pair, unweighted): the table arguments are the HOT table's, `tier` brings the cold one.
+// BROWS (one bf16-row table, or with GROUPED a bf16-row group — every member's plane, JAGGED included; unweighted: SPEC.md §3 "Row
+// storage type"): the value planes hold bf16 rows.  One storage type per group, so this is a property of the launch, never a per-member
+// branch in the fetch.
 template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false, bool JAGGED = false, bool TIERED = false, bool BROWS = false>
 __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restrict__ tkeys_, const float4* __restrict__ values_,
                                                           uint64_t nb_, const int64_t* __restrict__ keys,
@@ -354,138 +344,155 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
     const uint32_t dim4 = DIM4 ? DIM4 : dim4_rt;
     constexpr int C = DIM4 ? DIM4 / 16 : 16;   // float4 per lane per row (any dim: up to 1024 floats = 16 per lane)
     constexpr bool TAGGED = WEIGHTED && !GROUPED;
-    for (uint64_t b0 = wave * BPW; b0 < n_bags; b0 += n_waves * BPW) {
-        const uint64_t bag = BPW == 4 ? b0 + tile : b0;
-        const bool has = bag < n_bags;
-        uint64_t begin = has ? offsets[bag] : 0, end = has ? offsets[bag + 1] : 0;
-        end = end < n_keys ? end : n_keys;          // offsets are the caller's: never read past the key array,
-        begin = begin < end ? begin : end;          // and a decreasing pair is an empty bag
-        const int64_t* tkeys = tkeys_;
-        const float4* values = values_;
-        uint64_t nb = nb_;
-        float4 def4 = make_float4(defv, defv, defv, defv);
-        uint64_t member = 0;
+    auto table_of = [&](uint64_t b, PooledTable& t) {
         if constexpr (GROUPED) {
+            uint64_t member;
+            bool in_map = true;
+            if constexpr (JAGGED) in_map = jagged_member(member_bags, n_members, b, member);
+            else member = b / bags_per_table;
+            t = pooled_table(desc[member], member, kGroupSlotBits);
+            return in_map;
+        } else {
+            t = PooledTable{tkeys_, values_, nb_, make_float4(defv, defv, defv, defv), TAGGED ? (uint64_t)handle_tag : 0};
+            return true;
+        }
+    };
+    auto row_of = [&](uint64_t b) { return b * dim4; };
+    for (uint64_t b0 = wave * BPW; b0 < n_bags; b0 += n_waves * BPW) {
+        if constexpr (!(GROUPED && BPW == 4)) {
+            pooled_bags<DIM4, U, BPW, C, WEIGHTED, BF16, TIERED, BROWS, TAGGED>(b0, (uint32_t)(n_bags - b0 < BPW ? n_bags - b0 : BPW), dim4, keys, offsets, n_keys, weights, out, found,
+                                                                                (GROUPED && BROWS) ? nullptr : located,   // (a bf16-row group hands out no located rows: refused at the entry points)
+                                                                                mean, tier, tile, tl, table_of, row_of);
+        } else {
+            // NOT converted: a group's four-bags-per-wave instances keep their own copy of the walk.  Through pooled_bags the collection step's
+            // lookup (find_pooled_kernel<16, 2, 4, true>) measured 1 % above its time before (profiles/pooled_shared_body.md §2), and no way of
+            // writing the callables brought it back.  A change to the order of the additions, the mean's division, the long-bag rule or the
+            // clamping of the offsets in pooled_bags has to be made here too (tests/test_gpu_parity.py and test_mixed_groups.py compare the two).
+            const uint64_t bag = b0 + tile;
+            const bool has = bag < n_bags;
+            uint64_t begin = has ? offsets[bag] : 0, end = has ? offsets[bag + 1] : 0;
+            end = end < n_keys ? end : n_keys;          // offsets are the caller's: never read past the key array,
+            begin = begin < end ? begin : end;          // and a decreasing pair is an empty bag
+            uint64_t member = 0;
             if constexpr (JAGGED) {
                 if (!jagged_member(member_bags, n_members, has ? bag : 0, member)) begin = end = 0;   // a bag outside the map: empty
             } else member = (has ? bag : 0) / bags_per_table;
-            const GroupDesc d = desc[member];
-            tkeys = d.tkeys; values = d.values; nb = d.nb; def4 = make_float4(d.defv, d.defv, d.defv, d.defv);
-        }
-        const bool is_long = BPW == 1 || end - begin >= kPoolLong;
-        float4 acc[C];
-        float4 row[U][C];
-        // ---- short bags: one tile per bag ----
-        if constexpr (BPW == 4) {
-            uint64_t i = is_long ? end : begin;
-            bool first = true;
-#pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-            // a short bag has fewer than 16 keys: its tile fetches them all with one coalesced load, lane tl holds key begin + tl
-            const int64_t kpre = (!is_long && begin + tl < end) ? keys[begin + tl] : kEmpty;
-            float wpre = 0.f;   // the same for the weights
-            if constexpr (WEIGHTED) wpre = (!is_long && begin + tl < end) ? weights[begin + tl] : 0.f;
-            while (__any(i < end)) {  // wave-uniform; tiles whose bag is done idle through the ballots
-                uint64_t pos[U];
-                int64_t kv[U];
-                float wv[U];
-                bool inb[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    pos[u] = i + u; inb[u] = pos[u] < end;
-                    kv[u] = __shfl(kpre, tile * 16 + (int)((pos[u] - begin) & 15));
-                    if constexpr (WEIGHTED) wv[u] = __shfl(wpre, tile * 16 + (int)((pos[u] - begin) & 15));
-                }
-                if constexpr (TIERED) pooled_fetch_tiered<DIM4, U, C>(tkeys, values, nb, tier, dim4, kv, pos, inb, tile, tl, def4, row, found);
-                else pooled_fetch<DIM4, U, C, TAGGED, BROWS>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, (GROUPED && BROWS) ? nullptr : located,   // (a bf16-row group hands out no located rows: refused at the entry points)
-                                                      GROUPED ? member << kGroupSlotBits : (TAGGED ? (uint64_t)handle_tag : 0));
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (!inb[u]) continue;
-#pragma unroll
-                    for (int c = 0; c < C; ++c)
-                        if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
-                            if constexpr (WEIGHTED) {   // (the unweighted instances keep their code exactly)
-                                float4 v = row[u][c];
-                                v.x = wv[u] * v.x; v.y = wv[u] * v.y; v.z = wv[u] * v.z; v.w = wv[u] * v.w;
-                                if (first) acc[c] = v;
-                                else { acc[c].x += v.x; acc[c].y += v.y; acc[c].z += v.z; acc[c].w += v.w; }
-                            } else {
-                                if (first) acc[c] = row[u][c];
-                                else { acc[c].x += row[u][c].x; acc[c].y += row[u][c].y; acc[c].z += row[u][c].z; acc[c].w += row[u][c].w; }
-                            }
-                        }
-                    first = false;
-                }
-                i += U;
-            }
-            if (has && !is_long) {
-                const float len = (float)(end - begin);
-#pragma unroll
-                for (int c = 0; c < C; ++c)
-                    if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
-                        float4 v = acc[c];
-                        if (mean && end > begin) { v.x = v.x / len; v.y = v.y / len; v.z = v.z / len; v.w = v.w / len; }
-                        if constexpr (BF16) store_bf16x4<true>(out, bag * dim4 + c * 16 + tl, v); else out[bag * dim4 + c * 16 + tl] = v;
+            GroupDesc d = desc[member];
+            const int64_t* tkeys = d.tkeys;
+            const float4* values = d.values;
+            uint64_t nb = d.nb;
+            float4 def4 = make_float4(d.defv, d.defv, d.defv, d.defv);
+            const bool is_long = end - begin >= kPoolLong;
+            float4 acc[C];
+            float4 row[U][C];
+            // ---- short bags: one tile per bag ----
+            if constexpr (BPW == 4) {
+                uint64_t i = is_long ? end : begin;
+                bool first = true;
+    #pragma unroll
+                for (int c = 0; c < C; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                // a short bag has fewer than 16 keys: its tile fetches them all with one coalesced load, lane tl holds key begin + tl
+                const int64_t kpre = (!is_long && begin + tl < end) ? keys[begin + tl] : kEmpty;
+                float wpre = 0.f;   // the same for the weights
+                if constexpr (WEIGHTED) wpre = (!is_long && begin + tl < end) ? weights[begin + tl] : 0.f;
+                while (__any(i < end)) {  // wave-uniform; tiles whose bag is done idle through the ballots
+                    uint64_t pos[U];
+                    int64_t kv[U];
+                    float wv[U];
+                    bool inb[U];
+    #pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        pos[u] = i + u; inb[u] = pos[u] < end;
+                        kv[u] = __shfl(kpre, tile * 16 + (int)((pos[u] - begin) & 15));
+                        if constexpr (WEIGHTED) wv[u] = __shfl(wpre, tile * 16 + (int)((pos[u] - begin) & 15));
                     }
-            }
-        }
-        // ---- long bags: the four tiles share one bag at a time ----
-        const uint64_t long_mask = __ballot(is_long && has);
-        if (!long_mask) continue;   // wave-uniform
-        for (int q = 0; q < BPW; ++q) {
-            if (!((long_mask >> (q * 16)) & 1)) continue;   // wave-uniform
-            const uint64_t bq = __shfl(begin, q * 16), eq = __shfl(end, q * 16);
-            if constexpr (GROUPED && BPW == 4) {   // all four tiles work for bag q's table now
-                if constexpr (JAGGED) (void)jagged_member(member_bags, n_members, b0 + q, member);   // (a long bag is not empty: it lies inside the map)
-                else member = (b0 + q) / bags_per_table;
-                const GroupDesc d = desc[member];
-                tkeys = d.tkeys; values = d.values; nb = d.nb; def4 = make_float4(d.defv, d.defv, d.defv, d.defv);
-            }
-            bool first = true;
-#pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (uint64_t i = bq; i < eq; i += 4 * U) {   // wave-uniform
-                uint64_t pos[U];
-                int64_t kv[U];
-                float wv[U];
-                bool inb[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    pos[u] = i + (uint64_t)u * 4 + tile; inb[u] = pos[u] < eq; kv[u] = inb[u] ? keys[pos[u]] : kEmpty;
-                    if constexpr (WEIGHTED) wv[u] = inb[u] ? weights[pos[u]] : 0.f;   // next to the key
-                }
-                if constexpr (TIERED) pooled_fetch_tiered<DIM4, U, C>(tkeys, values, nb, tier, dim4, kv, pos, inb, tile, tl, def4, row, found);
-                else pooled_fetch<DIM4, U, C, TAGGED, BROWS>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, (GROUPED && BROWS) ? nullptr : located,   // (a bf16-row group hands out no located rows: refused at the entry points)
-                                                      GROUPED ? member << kGroupSlotBits : (TAGGED ? (uint64_t)handle_tag : 0));
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int src = 0; src < 4; ++src) {
-                        if (i + (uint64_t)u * 4 + src >= eq) continue;   // wave-uniform
-                        float w = 0.f;
-                        if constexpr (WEIGHTED) w = __shfl(wv[u], src * 16 + tl);
-#pragma unroll
-                        for (int c = 0; c < C; ++c) {
-                            float4 v;   // every tile reads the row tile `src` fetched: all four keep the same running sum
-                            v.x = __shfl(row[u][c].x, src * 16 + tl); v.y = __shfl(row[u][c].y, src * 16 + tl);
-                            v.z = __shfl(row[u][c].z, src * 16 + tl); v.w = __shfl(row[u][c].w, src * 16 + tl);
-                            if constexpr (WEIGHTED) { v.x = w * v.x; v.y = w * v.y; v.z = w * v.z; v.w = w * v.w; }
-                            if (first) acc[c] = v;
-                            else { acc[c].x += v.x; acc[c].y += v.y; acc[c].z += v.z; acc[c].w += v.w; }
-                        }
+                    pooled_fetch<DIM4, U, C, TAGGED, BROWS>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, (GROUPED && BROWS) ? nullptr : located,   // (a bf16-row group hands out no located rows: refused at the entry points)
+                                                          member << kGroupSlotBits);
+    #pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        if (!inb[u]) continue;
+    #pragma unroll
+                        for (int c = 0; c < C; ++c)
+                            if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
+                                if constexpr (WEIGHTED) {   // (the unweighted instances keep their code exactly)
+                                    float4 v = row[u][c];
+                                    v.x = wv[u] * v.x; v.y = wv[u] * v.y; v.z = wv[u] * v.z; v.w = wv[u] * v.w;
+                                    if (first) acc[c] = v;
+                                    else { acc[c].x += v.x; acc[c].y += v.y; acc[c].z += v.z; acc[c].w += v.w; }
+                                } else {
+                                    if (first) acc[c] = row[u][c];
+                                    else { acc[c].x += row[u][c].x; acc[c].y += row[u][c].y; acc[c].z += row[u][c].z; acc[c].w += row[u][c].w; }
+                                }
+                            }
                         first = false;
                     }
+                    i += U;
+                }
+                if (has && !is_long) {
+                    const float len = (float)(end - begin);
+    #pragma unroll
+                    for (int c = 0; c < C; ++c)
+                        if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
+                            float4 v = acc[c];
+                            if (mean && end > begin) { v.x = v.x / len; v.y = v.y / len; v.z = v.z / len; v.w = v.w / len; }
+                            if constexpr (BF16) store_bf16x4<true>(out, bag * dim4 + c * 16 + tl, v); else out[bag * dim4 + c * 16 + tl] = v;
+                        }
+                }
             }
-            if (tile == 0) {
-                const float len = (float)(eq - bq);
-#pragma unroll
-                for (int c = 0; c < C; ++c)
-                    if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
-                        float4 v = acc[c];
-                        if (mean && eq > bq) { v.x = v.x / len; v.y = v.y / len; v.z = v.z / len; v.w = v.w / len; }
-                        if constexpr (BF16) store_bf16x4<true>(out, (b0 + q) * dim4 + c * 16 + tl, v); else out[(b0 + q) * dim4 + c * 16 + tl] = v;
+            // ---- long bags: the four tiles share one bag at a time ----
+            const uint64_t long_mask = __ballot(is_long && has);
+            if (!long_mask) continue;   // wave-uniform
+            for (int q = 0; q < BPW; ++q) {
+                if (!((long_mask >> (q * 16)) & 1)) continue;   // wave-uniform
+                const uint64_t bq = __shfl(begin, q * 16), eq = __shfl(end, q * 16);
+                if constexpr (JAGGED) (void)jagged_member(member_bags, n_members, b0 + q, member);   // (a long bag is not empty: it lies inside the map)
+                else member = (b0 + q) / bags_per_table;
+                d = desc[member];   // all four tiles work for bag q's table now
+                tkeys = d.tkeys; values = d.values; nb = d.nb; def4 = make_float4(d.defv, d.defv, d.defv, d.defv);
+                bool first = true;
+    #pragma unroll
+                for (int c = 0; c < C; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                for (uint64_t i = bq; i < eq; i += 4 * U) {   // wave-uniform
+                    uint64_t pos[U];
+                    int64_t kv[U];
+                    float wv[U];
+                    bool inb[U];
+    #pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        pos[u] = i + (uint64_t)u * 4 + tile; inb[u] = pos[u] < eq; kv[u] = inb[u] ? keys[pos[u]] : kEmpty;
+                        if constexpr (WEIGHTED) wv[u] = inb[u] ? weights[pos[u]] : 0.f;   // next to the key
                     }
+                    pooled_fetch<DIM4, U, C, TAGGED, BROWS>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, (GROUPED && BROWS) ? nullptr : located,   // (a bf16-row group hands out no located rows: refused at the entry points)
+                                                          member << kGroupSlotBits);
+    #pragma unroll
+                    for (int u = 0; u < U; ++u)
+    #pragma unroll
+                        for (int src = 0; src < 4; ++src) {
+                            if (i + (uint64_t)u * 4 + src >= eq) continue;   // wave-uniform
+                            float w = 0.f;
+                            if constexpr (WEIGHTED) w = __shfl(wv[u], src * 16 + tl);
+    #pragma unroll
+                            for (int c = 0; c < C; ++c) {
+                                float4 v;   // every tile reads the row tile `src` fetched: all four keep the same running sum
+                                v.x = __shfl(row[u][c].x, src * 16 + tl); v.y = __shfl(row[u][c].y, src * 16 + tl);
+                                v.z = __shfl(row[u][c].z, src * 16 + tl); v.w = __shfl(row[u][c].w, src * 16 + tl);
+                                if constexpr (WEIGHTED) { v.x = w * v.x; v.y = w * v.y; v.z = w * v.z; v.w = w * v.w; }
+                                if (first) acc[c] = v;
+                                else { acc[c].x += v.x; acc[c].y += v.y; acc[c].z += v.z; acc[c].w += v.w; }
+                            }
+                            first = false;
+                        }
+                }
+                if (tile == 0) {
+                    const float len = (float)(eq - bq);
+    #pragma unroll
+                    for (int c = 0; c < C; ++c)
+                        if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
+                            float4 v = acc[c];
+                            if (mean && eq > bq) { v.x = v.x / len; v.y = v.y / len; v.z = v.z / len; v.w = v.w / len; }
+                            if constexpr (BF16) store_bf16x4<true>(out, (b0 + q) * dim4 + c * 16 + tl, v); else out[(b0 + q) * dim4 + c * 16 + tl] = v;
+                        }
+                }
             }
         }
     }
@@ -493,20 +500,19 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
 
 // ---- backward of the weighted pooled lookup (SPEC.md §3) ------------------------------------------------------------------
 // grads[i] = weights[i] * bag_grads[bag(i)] (one fp32 multiply per element) and, when weight_grads is given, weight_grads[i] =
-// sum_j bag_grads[bag(i), j] * row_i[j] in fp64, rounded once.  The bag-to-wave geometry of find_pooled_kernel: a tile per short bag,
-// the wave's four tiles on one long bag (tile t takes positions i + 4u + t), or a wave per bag (BPW 1).  The bag's grad row is loaded
-// into registers once.  Nothing here depends on the order of positions, so a long bag needs no exchange between tiles.
+// sum_j bag_grads[bag(i), j] * row_i[j] in fp64, rounded once.  The bag-to-wave geometry of the forward, from the same pieces (pooled_span,
+// pooled_short_* and pooled_long_positions, meepo_device.h): a tile per short bag, the wave's four tiles on one long bag, or a wave per
+// bag (BPW 1).  The bag's grad row is loaded into registers once.  Nothing here depends on the order of positions or is carried from
+// round to round, so each round of positions goes straight to pooled_bwd_positions.
 
 // the U positions one tile handles in one round: store w * G, then (weight_grads) fetch the rows and reduce the dot products across
 // the tile's 16 lanes.  A row comes through its handle when the caller passed one (`handles`), otherwise from a probe (pooled_fetch);
 // a handle of an absent key reads the default row, a handle the table cannot vouch for (another layout epoch, out of range, another
 // member) falls back to the probe.
 template <int DIM4, int U, int C, bool GROUPED>
-__device__ __forceinline__ void pooled_bwd_positions(const int64_t* __restrict__ tkeys, const float4* __restrict__ values, uint64_t nb,
-                                                     uint64_t capacity, uint32_t dim4, const int64_t (&key)[U], const uint64_t (&pos)[U],
-                                                     const bool (&inb)[U], const float (&w)[U], const int64_t* __restrict__ handles,
-                                                     int64_t handle_tag, uint64_t member, int tile, int tl, float4 def4, const float4 (&g)[C],
-                                                     float4* __restrict__ grads, float* __restrict__ weight_grads) {
+__device__ __forceinline__ void pooled_bwd_positions(const PooledTable& t, uint64_t capacity, uint32_t dim4, const int64_t (&key)[U], const uint64_t (&pos)[U],
+                                                     const bool (&inb)[U], const float (&w)[U], const int64_t* __restrict__ handles, int tile, int tl,
+                                                     const float4 (&g)[C], float4* __restrict__ grads, float* __restrict__ weight_grads) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         if (!inb[u]) continue;
@@ -527,22 +533,22 @@ __device__ __forceinline__ void pooled_bwd_positions(const int64_t* __restrict__
             if (h < 0) probe[u] = false;   // absent when the forward ran: the default row
             else if constexpr (GROUPED) {
                 const uint64_t s = (uint64_t)h & ((1ull << kGroupSlotBits) - 1);
-                if (((uint64_t)h >> kGroupSlotBits) == member && s < capacity) { hs[u] = (int64_t)s; probe[u] = false; }
+                if (((uint64_t)h >> kGroupSlotBits) == (t.tag >> kGroupSlotBits) && s < capacity) { hs[u] = (int64_t)s; probe[u] = false; }
             } else {
                 bool stale;
-                hs[u] = handle_slot(h, handle_tag, capacity, stale);
+                hs[u] = handle_slot(h, (int64_t)t.tag, capacity, stale);
                 probe[u] = hs[u] < 0;
             }
         }
     }
     float4 row[U][C];
-    pooled_fetch<DIM4, U, C>(tkeys, values, nb, dim4, key, pos, probe, tile, tl, def4, row, nullptr);
+    pooled_fetch<DIM4, U, C>(t.tkeys, t.values, t.nb, dim4, key, pos, probe, tile, tl, t.def4, row, nullptr);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         if (hs[u] >= 0) {
 #pragma unroll
             for (int c = 0; c < C; ++c)
-                if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) row[u][c] = values[(uint64_t)hs[u] * dim4 + c * 16 + tl];
+                if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) row[u][c] = t.values[(uint64_t)hs[u] * dim4 + c * 16 + tl];
         }
         double s = 0.0;
 #pragma unroll
@@ -571,47 +577,38 @@ __global__ __launch_bounds__(256) void pooled_weighted_backward_kernel(const int
     const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
     const uint32_t dim4 = DIM4 ? DIM4 : dim4_rt;
     constexpr int C = DIM4 ? DIM4 / 16 : 16;
+    auto table_of = [&](uint64_t b, PooledTable& t) {
+        if constexpr (GROUPED) {
+            t = pooled_table(desc[b / bags_per_table], b / bags_per_table, kGroupSlotBits);
+        } else t = PooledTable{tkeys_, values_, nb_, make_float4(defv, defv, defv, defv), (uint64_t)handle_tag};
+    };
+    auto grad_row = [&](uint64_t b, bool live, float4 (&g)[C]) {   // the bag's grad row, once into registers
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            g[c] = (live && (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4)) ? bag_grads[b * dim4 + c * 16 + tl] : make_float4(0.f, 0.f, 0.f, 0.f);
+    };
     for (uint64_t b0 = wave * BPW; b0 < n_bags; b0 += n_waves * BPW) {
         const uint64_t bag = BPW == 4 ? b0 + tile : b0;
         const bool has = bag < n_bags;
-        uint64_t begin = has ? offsets[bag] : 0, end = has ? offsets[bag + 1] : 0;
-        end = end < n_keys ? end : n_keys;          // the forward's clamps: never past the key array,
-        begin = begin < end ? begin : end;          // and a decreasing pair is an empty bag
-        const int64_t* tkeys = tkeys_;
-        const float4* values = values_;
-        uint64_t nb = nb_, capacity = capacity_;
-        float4 def4 = make_float4(defv, defv, defv, defv);
-        uint64_t member = 0;
-        if constexpr (GROUPED) {
-            member = (has ? bag : 0) / bags_per_table;
-            const GroupDesc d = desc[member];
-            tkeys = d.tkeys; values = d.values; nb = d.nb; capacity = d.nb * kW; def4 = make_float4(d.defv, d.defv, d.defv, d.defv);
-        }
+        uint64_t begin, end;
+        pooled_span(offsets, bag, has, n_keys, begin, end);
+        PooledTable t;
+        table_of(has ? bag : b0, t);
         const bool is_long = BPW == 1 || end - begin >= kPoolLong;
         float4 g[C];
+        uint64_t pos[U];
+        int64_t kv[U];
+        float wv[U];
+        bool inb[U];
         // ---- short bags: one tile per bag ----
         if constexpr (BPW == 4) {
-#pragma unroll
-            for (int c = 0; c < C; ++c)
-                g[c] = (has && !is_long && end > begin && (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4)) ? bag_grads[bag * dim4 + c * 16 + tl]
-                                                                                                         : make_float4(0.f, 0.f, 0.f, 0.f);
-            uint64_t i = is_long ? end : begin;
-            const int64_t kpre = (!is_long && begin + tl < end) ? keys[begin + tl] : kEmpty;
-            const float wpre = (!is_long && begin + tl < end) ? weights[begin + tl] : 0.f;
-            while (__any(i < end)) {  // wave-uniform
-                uint64_t pos[U];
-                int64_t kv[U];
-                float wv[U];
-                bool inb[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    pos[u] = i + u; inb[u] = pos[u] < end;
-                    kv[u] = __shfl(kpre, tile * 16 + (int)((pos[u] - begin) & 15));
-                    wv[u] = __shfl(wpre, tile * 16 + (int)((pos[u] - begin) & 15));
-                }
-                pooled_bwd_positions<DIM4, U, C, GROUPED>(tkeys, values, nb, capacity, dim4, kv, pos, inb, wv, handles, handle_tag, member,
-                                                          tile, tl, def4, g, grads, weight_grads);
-                i += U;
+            grad_row(bag, has && !is_long && end > begin, g);
+            int64_t kpre;
+            float wpre;
+            pooled_short_prefetch<true>(keys, weights, begin, end, is_long, tl, kpre, wpre);
+            for (uint64_t i = is_long ? end : begin; __any(i < end); i += U) {  // wave-uniform
+                pooled_short_positions<U, true>(i, begin, end, kpre, wpre, tile, pos, kv, wv, inb);
+                pooled_bwd_positions<DIM4, U, C, GROUPED>(t, GROUPED ? t.nb * kW : capacity_, dim4, kv, pos, inb, wv, handles, tile, tl, g, grads, weight_grads);
             }
         }
         // ---- long bags: the four tiles share one bag at a time ----
@@ -620,26 +617,11 @@ __global__ __launch_bounds__(256) void pooled_weighted_backward_kernel(const int
         for (int q = 0; q < BPW; ++q) {
             if (!((long_mask >> (q * 16)) & 1)) continue;   // wave-uniform
             const uint64_t bq = __shfl(begin, q * 16), eq = __shfl(end, q * 16);
-            if constexpr (GROUPED && BPW == 4) {
-                member = (b0 + q) / bags_per_table;
-                const GroupDesc d = desc[member];
-                tkeys = d.tkeys; values = d.values; nb = d.nb; capacity = d.nb * kW; def4 = make_float4(d.defv, d.defv, d.defv, d.defv);
-            }
-#pragma unroll
-            for (int c = 0; c < C; ++c)
-                g[c] = (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) ? bag_grads[(b0 + q) * dim4 + c * 16 + tl] : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (BPW == 4) table_of(b0 + q, t);
+            grad_row(b0 + q, true, g);
             for (uint64_t i = bq; i < eq; i += 4 * U) {   // wave-uniform
-                uint64_t pos[U];
-                int64_t kv[U];
-                float wv[U];
-                bool inb[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    pos[u] = i + (uint64_t)u * 4 + tile; inb[u] = pos[u] < eq;
-                    kv[u] = inb[u] ? keys[pos[u]] : kEmpty; wv[u] = inb[u] ? weights[pos[u]] : 0.f;
-                }
-                pooled_bwd_positions<DIM4, U, C, GROUPED>(tkeys, values, nb, capacity, dim4, kv, pos, inb, wv, handles, handle_tag, member,
-                                                          tile, tl, def4, g, grads, weight_grads);
+                pooled_long_positions<U, true>(i, eq, keys, weights, tile, pos, kv, wv, inb);
+                pooled_bwd_positions<DIM4, U, C, GROUPED>(t, GROUPED ? t.nb * kW : capacity_, dim4, kv, pos, inb, wv, handles, tile, tl, g, grads, weight_grads);
             }
         }
     }

@@ -1,5 +1,6 @@
 // meepo_mixed.hip — a table group whose members differ in row width (SPEC.md §3 "Mixed groups"): the embedding-bag collection of a model
-// with per-feature widths.  One pooled-lookup launch serves every member; the optimizer step is the uniform group's grouped apply
+// with per-feature widths.  One pooled-lookup launch serves every member through the bag walk all pooled lookups share (pooled_bags,
+// meepo_device.h); the optimizer step is the uniform group's grouped apply
 // (meepo_table.hip / meepo_apply.hip, untouched) run once per width class on handles a small select launch re-bases to that class.
 //
 // Output layout ("class-major"): a class = the members of one dim, classes by ascending dim, members inside a class in the caller's order;
@@ -20,125 +21,13 @@ struct MixedDesc {   // per member, device resident, beside its GroupDesc / Grou
     uint32_t dim4, cls, rank, pad;
 };
 
-// The bags of ONE member a wave serves in one step — the body of find_pooled_kernel (meepo_find.hip) with the member's planes and row
-// shape: BPW = 4: tile t takes bag `bag0 + t` (t < nvalid), a bag of kPoolLong keys or more is served by the four tiles together;
-// BPW = 1: the wave takes bag0.  Additions in position order, no fma; the row of bag0 + q goes to out[row0 + q * dim4 ...].
-// CW: float4 per lane per row of the run-time shape (DIM4 = 0), which then serves dim4 <= 16 * CW.
-template <int DIM4, int U, int BPW, bool BF16, int CW = 16>
-__device__ __forceinline__ void mixed_bags(const GroupDesc& d, uint32_t dim4_rt, uint64_t member, uint64_t bag0, uint32_t nvalid, uint64_t row0,
-                                           const int64_t* __restrict__ keys, const uint64_t* __restrict__ offsets, float4* __restrict__ out,
-                                           uint8_t* __restrict__ found, int64_t* __restrict__ located, uint64_t n_keys, int mean, int tile, int tl) {
-    const uint32_t dim4 = DIM4 ? DIM4 : dim4_rt;
-    constexpr int C = DIM4 ? DIM4 / 16 : CW;   // float4 per lane per row
-    const uint64_t bag = BPW == 4 ? bag0 + tile : bag0;
-    const bool has = BPW == 4 ? (uint32_t)tile < nvalid : true;
-    uint64_t begin = has ? offsets[bag] : 0, end = has ? offsets[bag + 1] : 0;
-    end = end < n_keys ? end : n_keys;          // offsets are the caller's: never read past the key array,
-    begin = begin < end ? begin : end;          // and a decreasing pair is an empty bag
-    const int64_t* tkeys = d.tkeys;
-    const float4* values = d.values;
-    const uint64_t nb = d.nb, tag = member << kGroupSlotBits;
-    const float4 def4 = make_float4(d.defv, d.defv, d.defv, d.defv);
-    const bool is_long = BPW == 1 || end - begin >= kPoolLong;
-    float4 acc[C];
-    float4 row[U][C];
-    // ---- short bags: one tile per bag ----
-    if constexpr (BPW == 4) {
-        uint64_t i = is_long ? end : begin;
-        bool first = true;
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-        // a short bag has fewer than 16 keys: its tile fetches them all with one coalesced load, lane tl holds key begin + tl
-        const int64_t kpre = (!is_long && begin + tl < end) ? keys[begin + tl] : kEmpty;
-        while (__any(i < end)) {  // wave-uniform; tiles whose bag is done idle through the ballots
-            uint64_t pos[U];
-            int64_t kv[U];
-            bool inb[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                pos[u] = i + u; inb[u] = pos[u] < end;
-                kv[u] = __shfl(kpre, tile * 16 + (int)((pos[u] - begin) & 15));
-            }
-            pooled_fetch<DIM4, U, C>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located, tag);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (!inb[u]) continue;
-#pragma unroll
-                for (int c = 0; c < C; ++c)
-                    if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
-                        if (first) acc[c] = row[u][c];
-                        else { acc[c].x += row[u][c].x; acc[c].y += row[u][c].y; acc[c].z += row[u][c].z; acc[c].w += row[u][c].w; }
-                    }
-                first = false;
-            }
-            i += U;
-        }
-        if (has && !is_long) {
-            const float len = (float)(end - begin);
-#pragma unroll
-            for (int c = 0; c < C; ++c)
-                if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
-                    float4 v = acc[c];
-                    if (mean && end > begin) { v.x = v.x / len; v.y = v.y / len; v.z = v.z / len; v.w = v.w / len; }
-                    const uint64_t o = row0 + (uint64_t)tile * dim4 + c * 16 + tl;
-                    if constexpr (BF16) store_bf16x4<true>(out, o, v); else out[o] = v;
-                }
-        }
-    }
-    // ---- long bags: the four tiles share one bag at a time ----
-    const uint64_t long_mask = __ballot(is_long && has);
-    if (!long_mask) return;   // wave-uniform
-    for (int q = 0; q < BPW; ++q) {
-        if (!((long_mask >> (q * 16)) & 1)) continue;   // wave-uniform
-        const uint64_t bq = __shfl(begin, q * 16), eq = __shfl(end, q * 16);
-        bool first = true;
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (uint64_t i = bq; i < eq; i += 4 * U) {   // wave-uniform
-            uint64_t pos[U];
-            int64_t kv[U];
-            bool inb[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                pos[u] = i + (uint64_t)u * 4 + tile; inb[u] = pos[u] < eq; kv[u] = inb[u] ? keys[pos[u]] : kEmpty;
-            }
-            pooled_fetch<DIM4, U, C>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, located, tag);
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int src = 0; src < 4; ++src) {
-                    if (i + (uint64_t)u * 4 + src >= eq) continue;   // wave-uniform
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        float4 v;   // every tile reads the row tile `src` fetched: all four keep the same running sum
-                        v.x = __shfl(row[u][c].x, src * 16 + tl); v.y = __shfl(row[u][c].y, src * 16 + tl);
-                        v.z = __shfl(row[u][c].z, src * 16 + tl); v.w = __shfl(row[u][c].w, src * 16 + tl);
-                        if (first) acc[c] = v;
-                        else { acc[c].x += v.x; acc[c].y += v.y; acc[c].z += v.z; acc[c].w += v.w; }
-                    }
-                    first = false;
-                }
-        }
-        if (tile == 0) {
-            const float len = (float)(eq - bq);
-#pragma unroll
-            for (int c = 0; c < C; ++c)
-                if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
-                    float4 v = acc[c];
-                    if (mean && eq > bq) { v.x = v.x / len; v.y = v.y / len; v.z = v.z / len; v.w = v.w / len; }
-                    const uint64_t o = row0 + (uint64_t)q * dim4 + c * 16 + tl;
-                    if constexpr (BF16) store_bf16x4<true>(out, o, v); else out[o] = v;
-                }
-        }
-    }
-}
-
 // The pooled lookup of a mixed group, one launch.  Waves are mapped to bags PER MEMBER: with BPW = 4 a member's B bags take Bp / 4 wave
 // steps (Bp = B rounded up to a multiple of 4, in this mapping only), so the four bags of a wave never straddle two members and the
 // member — its planes, its dim4, its output block — is wave-uniform: the branch to the row shape (DIM4 16 / 32 / run time) does not
 // diverge.  BPW = 1 (the batch's average bag is long): a wave per bag.  The unrolls per shape are those of RowShape.
 // A kernel's register budget is that of its widest path, and the run-time shape at its full width (16 float4 per lane: any dim up to 1024)
-// takes 256 VGPRs — one wave per SIMD for the dim-64 members too.  CW = 2 is the instance for groups whose run-time widths are all <= 128
+// takes 256 VGPRs — one wave per SIMD for the dim-64 members too.  CW = float4 per lane per row of the run-time shape (DIM4 = 0), which then serves
+// dim4 <= 16 * CW; CW = 2 is the instance for groups whose run-time widths are all <= 128
 // (8, 16, 32, 100, ...): the run-time path then holds no more row registers than the dim-128 path (82 VGPRs, 5 waves per SIMD with four bags
 // per wave), and the launch picks it.  All instances beside the uniform group's: profiles/mixed_groups.md.
 template <int BPW, bool BF16, int CW>
@@ -161,12 +50,19 @@ __global__ __launch_bounds__(256) void mixed_find_pooled_kernel(const GroupDesc*
         const uint32_t nvalid = rest < (uint64_t)BPW ? (uint32_t)rest : (uint32_t)BPW;
         const uint64_t bag0 = (uint64_t)member * B + local0;
         const uint64_t row0 = (md.off4 * B) + local0 * md.dim4;
-        if (md.dim4 == 16)
-            mixed_bags<16, BPW == 4 ? RowShape<16>::pooled_unroll_4 : RowShape<16>::pooled_unroll_1, BPW, BF16>(d, 16, member, bag0, nvalid, row0, keys, offsets, out, found, located, n_keys, mean, tile, tl);
-        else if (md.dim4 == 32)
-            mixed_bags<32, BPW == 4 ? RowShape<32>::pooled_unroll_4 : RowShape<32>::pooled_unroll_1, BPW, BF16>(d, 32, member, bag0, nvalid, row0, keys, offsets, out, found, located, n_keys, mean, tile, tl);
-        else
-            mixed_bags<0, BPW == 4 ? RowShape<0>::pooled_unroll_4 : RowShape<0>::pooled_unroll_1, BPW, BF16, CW>(d, md.dim4, member, bag0, nvalid, row0, keys, offsets, out, found, located, n_keys, mean, tile, tl);
+        const PooledTable t = pooled_table(d, member, kGroupSlotBits);
+        // the bags of ONE member through the shared walk (pooled_bags, meepo_device.h) at the member's row shape: C = float4 per lane per row
+        auto bags = [&](auto d4) {
+            constexpr int C = d4 ? d4 / 16 : CW;
+            constexpr int U = BPW == 4 ? RowShape<d4>::pooled_unroll_4 : RowShape<d4>::pooled_unroll_1;
+            const uint32_t dim4 = d4 ? (uint32_t)d4 : md.dim4;
+            pooled_bags<d4, U, BPW, C, false, BF16, false, false, false>(
+                bag0, nvalid, dim4, keys, offsets, n_keys, nullptr, out, found, located, mean, TierArgs{}, tile, tl,
+                [&](uint64_t, PooledTable& bt) { bt = t; return true; }, [&](uint64_t b) { return row0 + (b - bag0) * dim4; });
+        };
+        if (md.dim4 == 16) bags(std::integral_constant<int, 16>{});
+        else if (md.dim4 == 32) bags(std::integral_constant<int, 32>{});
+        else bags(std::integral_constant<int, 0>{});
     }
 }
 
