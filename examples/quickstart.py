@@ -35,6 +35,11 @@ with tempfile.TemporaryDirectory() as ckpt:
     table.save(ckpt)
     serving = LookupTable(1 << 20, 64, device=dev, max_batch=1 << 16, value_dtype=torch.bfloat16)
     serving.load(ckpt)                                     # every row rounded once to bf16 on the way in; optimizer state stays behind
+    serving8 = LookupTable(1 << 20, 64, device=dev, max_batch=1 << 16, int8_rows=True)   # ... or as int8 codes + one fp32 scale per row
+    serving8.load(ckpt)                                    # every row quantized once (scale = max|x| / 127)
+rows8, rows32 = serving8.find(keys[1000:1005])[0], table.find(keys[1000:1005])[0]
+print("int8-row table:", serving8.table_bytes >> 20, "MiB | largest error in units of the row's step:",
+      float(((rows8 - rows32).abs().max(dim=1).values / (rows32.abs().max(dim=1).values / 127)).max()))
 served, _ = serving.find(keys[1000:1005], out_dtype=torch.bfloat16)            # the stored bits, no second rounding
 print("serving table:", serving.size(), "keys,", serving.table_bytes >> 20, "MiB against", table.table_bytes >> 20, "MiB | same bf16 rows:",
       torch.equal(served, table.find(keys[1000:1005], out_dtype=torch.bfloat16)[0]))

@@ -67,7 +67,19 @@ enum { MEE_MEM_HBM = 0, MEE_MEM_HOST_PINNED = 1 };
  * (table_bytes = capacity x (8 + 2 x dim)), mee_set_tuning, mee_table_plane (plane 0, row_stride_bytes = 2 x dim) and mee_table_value_dtype.
  * Every other operator handed such a table — and every other create that takes tables — returns MEE_ERR_UNSUPPORTED, launches nothing and writes
  * nothing.  The one create that takes them is mee_group_create, for a group whose members are ALL bf16-row tables (a serving group: see "table groups"). */
-enum { MEE_FLAG_TRACK_HITS = 1u, MEE_FLAG_ADMISSION = 2u, MEE_FLAG_BF16_ROWS = 4u };
+/* MEE_FLAG_INT8_ROWS: the value plane holds int8 rows — dim two's-complement codes followed by a 16-byte tail (the row's fp32 scale, then twelve zero
+ * bytes), dim + 16 bytes per slot: the other SERVING table (SPEC.md §3 "Row storage type").  A written fp32 row x is quantized once, in fp32, nothing
+ * contracted: scale = max|x_i| / 127 (one correctly rounded division), q_i = clamp(rint(x_i / scale), -127, 127) with ties to even, every code 0 when
+ * scale == 0; a read gives y_i = (float)q_i * scale.  Everything observable is that of an fp32 table that was handed the rows D(Q(x)) and created with the
+ * same default_value (fp32, not quantized: a missing key's row).  Rows must be finite: a row holding NaN or +-inf gives unspecified values in that row and
+ * touches nothing else.  Create-time rules as for MEE_FLAG_BF16_ROWS (MEE_ERR_INVALID_ARG otherwise): optimizer = MEE_OPT_NONE, MEE_MEM_HBM, neither
+ * MEE_FLAG_TRACK_HITS nor MEE_FLAG_ADMISSION, not together with MEE_FLAG_BF16_ROWS, and dim a multiple of 16.  The operators it has are those of a
+ * bf16-row table WITHOUT the pooled lookups (mee_find_pooled / _as: MEE_ERR_UNSUPPORTED), and with fp32 input only: mee_insert_as / mee_assign_as take
+ * MEE_DTYPE_F32 (MEE_DTYPE_BF16: MEE_ERR_UNSUPPORTED), mee_find / _ex / _as write fp32 or bf16 rows (a bf16 result rounds y once, by the rule of
+ * "typed output"), mee_export / _range write dequantized fp32 rows, mee_reserve moves rows verbatim; mee_table_info_get: table_bytes = capacity x (8 + dim + 16), workspace_bytes = an fp32 table's
+ * + max_batch x (dim + 16); mee_table_plane: plane 0, row_stride_bytes = dim + 16; mee_table_value_dtype: MEE_DTYPE_INT8.  Every other operator handed
+ * such a table — and EVERY create that takes tables, mee_group_create included — returns MEE_ERR_UNSUPPORTED, launches nothing and writes nothing. */
+enum { MEE_FLAG_TRACK_HITS = 1u, MEE_FLAG_ADMISSION = 2u, MEE_FLAG_BF16_ROWS = 4u, MEE_FLAG_INT8_ROWS = 8u };
 
 typedef struct mee_table  mee_table;  /* one HBM-resident hash table (one shard) */
 typedef struct mee_router mee_router; /* workspace for the shard partition / un-permute kernels */
@@ -79,7 +91,7 @@ typedef struct mee_config {
     uint32_t struct_size;         /* = sizeof(mee_config); ABI guard */
     int32_t  device;              /* HIP device ordinal */
     uint64_t capacity;            /* requested slots; rounded up to 16 x (smallest prime >= capacity/16) (SPEC.md §2) */
-    uint32_t dim;                 /* floats per row: multiple of 4, 4..1024 (MEE_FLAG_BF16_ROWS: multiple of 8) */
+    uint32_t dim;                 /* floats per row: multiple of 4, 4..1024 (MEE_FLAG_BF16_ROWS: multiple of 8; MEE_FLAG_INT8_ROWS: of 16) */
     uint32_t optimizer;           /* MEE_OPT_*: which state planes to allocate */
     uint64_t max_batch;           /* largest n of any mutating op: sizes the workspace — with an optimizer ~(56 + 10 dim) B per position of HBM
                                    * (0.7 GB at 1M x dim 64: the pending records of a skewed batch's worst case); see mee_table_info.workspace_bytes */
@@ -95,7 +107,7 @@ typedef struct mee_config {
 typedef struct mee_table_info {
     uint64_t capacity, n_buckets, max_batch;
     uint32_t dim, optimizer;
-    uint64_t table_bytes;     /* keys + all planes resident in HBM (a bf16-row table: capacity x (8 + 2 x dim)) */
+    uint64_t table_bytes;     /* keys + all planes resident in HBM (a bf16-row table: capacity x (8 + 2 x dim); an int8-row table: capacity x (8 + dim + 16)) */
     uint64_t workspace_bytes;
 } mee_table_info;
 
@@ -396,14 +408,16 @@ int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, cons
  * The sharded lookups have typed forms of their own, mee_sharded_find_as / mee_sharded_find_or_insert_as (declared with the other mee_sharded_*
  * operators): there the OWNER of a key rounds its row, before the rows travel — a lookup then puts 8 + 2·dim + 1 bytes on the wire (key out, bf16
  * row and found byte back) instead of 8 + 4·dim + 1: 137 instead of 265 B at dim 64. */
-enum { MEE_DTYPE_F32 = 0, MEE_DTYPE_BF16 = 1 };
+/* MEE_DTYPE_INT8 names a ROW STORAGE type only (mee_table_value_dtype of a table created with MEE_FLAG_INT8_ROWS): as an out_dtype or an in_dtype it is
+ * MEE_ERR_INVALID_ARG. */
+enum { MEE_DTYPE_F32 = 0, MEE_DTYPE_BF16 = 1, MEE_DTYPE_INT8 = 2 };
 int mee_find_as(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, uint32_t flags, void* stream);
 /* Typed INPUT: mee_insert / mee_assign whose d_values holds rows of in_dtype.  MEE_DTYPE_F32: they ARE mee_insert / mee_assign.  MEE_DTYPE_BF16 on a
  * table created with MEE_FLAG_BF16_ROWS: d_values is [n, dim] bf16, 16-byte aligned, and the rows are stored VERBATIM (no rounding, NaN payloads
  * included); on an fp32 table it is MEE_ERR_UNSUPPORTED.  An unknown in_dtype or a misaligned bf16 buffer is MEE_ERR_INVALID_ARG. */
 int mee_insert_as(mee_table* t, const int64_t* d_keys, const void* d_values, uint32_t in_dtype, size_t n, void* stream);
 int mee_assign_as(mee_table* t, const int64_t* d_keys, const void* d_values, uint32_t in_dtype, size_t n, uint8_t* d_found, void* stream);
-/* MEE_DTYPE_F32, or MEE_DTYPE_BF16 for a table created with MEE_FLAG_BF16_ROWS (mee_table_info is a fixed 48 bytes: the row type has its own call) */
+/* MEE_DTYPE_F32, MEE_DTYPE_BF16 for a table created with MEE_FLAG_BF16_ROWS, or MEE_DTYPE_INT8 for one created with MEE_FLAG_INT8_ROWS (mee_table_info is a fixed 48 bytes: the row type has its own call) */
 int mee_table_value_dtype(const mee_table* t, uint32_t* out);
 int mee_find_located_as(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out,
                         void* stream);

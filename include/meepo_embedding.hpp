@@ -41,6 +41,7 @@ struct TableOptions {
     uint64_t init_seed = 0;
     uint32_t value_memory = MEE_MEM_HBM;  // MEE_MEM_HOST_PINNED = cold tier (rows in pinned host DRAM)
     bool bf16_rows = false;     // MEE_FLAG_BF16_ROWS: a serving table that stores its rows as bf16 (no optimizer, dim % 8 == 0, HBM)
+    bool int8_rows = false;     // MEE_FLAG_INT8_ROWS: a serving table that stores its rows as int8 codes + one fp32 scale (no optimizer, dim % 16 == 0, HBM; not with bf16_rows)
 };
 
 // One HBM-resident shard (SPEC.md §2-§4).  Move-only.
@@ -51,7 +52,7 @@ public:
         c.struct_size = sizeof c; c.device = o.device; c.capacity = o.capacity; c.dim = o.dim; c.optimizer = o.optimizer;
         c.max_batch = o.max_batch; c.default_value = o.default_value; c.initial_accumulator = o.initial_accumulator;
         c.initializer = o.initializer; c.init_scale = o.init_scale; c.init_seed = o.init_seed; c.value_memory = o.value_memory;
-        c.flags = o.bf16_rows ? MEE_FLAG_BF16_ROWS : 0u;
+        c.flags = (o.bf16_rows ? MEE_FLAG_BF16_ROWS : 0u) | (o.int8_rows ? MEE_FLAG_INT8_ROWS : 0u);
         check(mee_table_create(&c, &t_));
     }
     ~Table() { if (t_) mee_table_destroy(t_); }
@@ -62,7 +63,7 @@ public:
 
     mee_table* handle() const noexcept { return t_; }
     mee_table_info info() const { mee_table_info i{}; check(mee_table_info_get(t_, &i)); return i; }
-    uint32_t value_dtype() const { uint32_t d = MEE_DTYPE_F32; check(mee_table_value_dtype(t_, &d)); return d; }   // MEE_DTYPE_BF16: a bf16-row table
+    uint32_t value_dtype() const { uint32_t d = MEE_DTYPE_F32; check(mee_table_value_dtype(t_, &d)); return d; }   // MEE_DTYPE_BF16: a bf16-row table, MEE_DTYPE_INT8: an int8-row table
 
     void find(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream = nullptr) const { check(mee_find(t_, d_keys, n, d_out, d_found, stream)); }
     // ... with this call's cache policy (MEE_FIND_* flags)

@@ -24,6 +24,8 @@ FIND_DEFAULT, FIND_STREAM_STORES, FIND_CACHED_STORES, FIND_STREAM_ROWS, FIND_STR
 HANDLE_SLOT_MASK = (1 << 40) - 1   # a located-find handle: bits 0..39 the slot (as mee_locate reports it), bits 40..61 the table's layout epoch
 MEM_HBM, MEM_HOST_PINNED = 0, 1
 DTYPE_F32, DTYPE_BF16 = 0, 1   # MEE_DTYPE_*: the row type of a typed-output lookup (mee_*_as)
+DTYPE_INT8 = 2                 # ... a row STORAGE type only (mee_table_value_dtype of an int8-row table), never an out / in dtype
+FLAG_INT8_ROWS = 8   # a serving table whose value plane holds int8 codes and one fp32 scale per row (SPEC.md §3 "Row storage type")
 FLAG_TRACK_HITS, FLAG_ADMISSION, FLAG_BF16_ROWS = 1, 2, 4   # BF16_ROWS: a serving table whose value plane holds bf16 rows (SPEC.md §3 "Row storage type")
 TIER_COUNT_COLD, TIER_COUNT_HOT = 1, 2   # mee_find_pooled_tiered flags
 ABI_VERSION = 2   # MEE_ABI_VERSION of include/meepo_embedding.h this loader was written against
@@ -216,21 +218,28 @@ PROTOTYPES = {
     "mee_sharded_status": (C.c_int, [_vp, C.POINTER(_u32), _vp]),
 }
 
-def refuse_bf16_rows(who: str, *tables) -> None:
-    """Groups, tiered pairs, sharded / peer tables and the nn layers are built over fp32 tables: a bf16-row table (LookupTable(value_dtype=torch.bfloat16),
-    a serving table) — alone or as a member of a group handed in — is refused at construction, before anything is created."""
+_NARROW_ROWS = {torch.bfloat16: "a bf16-row table (value_dtype=torch.bfloat16) is a serving table with find, find_pooled, insert, assign, ",
+                torch.int8: "an int8-row table (int8_rows=True) is a serving table with find, insert, assign, "}
+
+
+def refuse_narrow_rows(who: str, *tables) -> None:
+    """Groups, tiered pairs, sharded / peer tables and the nn layers are built over fp32 tables: a serving table — LookupTable(value_dtype=torch.bfloat16) or
+    LookupTable(int8_rows=True), whose .value_dtype is torch.int8 — alone or as a member of a group handed in — is refused at construction, before anything is created; the message
+    names the row type."""
     for t in tables:
         if t is None:
             continue
         for m in [t, *getattr(t, "tables", ())]:
-            if getattr(m, "value_dtype", torch.float32) == torch.bfloat16:
-                raise MeepoError(ERR_UNSUPPORTED, f"{who}: a bf16-row table (value_dtype=torch.bfloat16) is a serving table with find, find_pooled, insert, assign, "
-                                                  "remove, export and reserve of its own; it cannot be a member of a group, a tier, a shard or a trained layer")
+            kind = _NARROW_ROWS.get(getattr(m, "value_dtype", torch.float32))
+            if kind:
+                raise MeepoError(ERR_UNSUPPORTED, f"{who}: {kind}remove, export and reserve of its own; it cannot be a member of a group, a tier, a shard or a trained layer")
 
 
 def group_row_dtype(who: str, *tables) -> torch.dtype:
     """The row storage type of a uniform group: torch.float32, or torch.bfloat16 when EVERY member is a bf16-row table (a serving group: lookups only).
-    A mix is refused as refuse_bf16_rows refuses a bf16-row table — one storage type per group.  Only .value_dtype is looked at (absent: fp32)."""
+    A mix is refused as refuse_narrow_rows refuses a bf16-row table — one storage type per group; an int8-row table is no member of any group (refused
+    through refuse_narrow_rows).  Only .value_dtype is looked at (absent: fp32)."""
+    refuse_narrow_rows(who, *[t for t in tables if getattr(t, "value_dtype", torch.float32) == torch.int8])
     kinds = {getattr(t, "value_dtype", torch.float32) == torch.bfloat16 for t in tables}
     if kinds == {True}:
         return torch.bfloat16

@@ -4,7 +4,8 @@ A checkpoint is a DIRECTORY:
 
     meta.json     {"format": "meepo-table-v1", "dim", "optimizer", "n", "planes": ["values", "state1", ...], "extra": {...}}
                   ("extra" carries "value_dtype": "bfloat16" when a bf16-row table wrote it; values.f32 holds its rows widened, and
-                  loading an fp32 checkpoint into a bf16-row table — train, then serve — rounds every row once)
+                  loading an fp32 checkpoint into a bf16-row table — train, then serve — rounds every row once; "int8" when an
+                  int8-row table wrote it: values.f32 holds its rows dequantized, and loading into one quantizes every row once)
     keys.i64      n little-endian int64 keys, in export order (unspecified, stable within the checkpoint)
     values.f32    n x dim little-endian fp32 rows, same order
     state1.f32    n x dim Adagrad accumulator / Adam m      (tables with an optimizer)
@@ -53,6 +54,8 @@ def save_table(table, path: str, chunk_slots: int = 1 << 22, extra: dict | None 
     extra = dict(extra or {})
     if getattr(table, "value_dtype", torch.float32) == torch.bfloat16:
         extra["value_dtype"] = "bfloat16"
+    if getattr(table, "value_dtype", torch.float32) == torch.int8:   # (values.f32 holds its rows dequantized)
+        extra["value_dtype"] = "int8"
     meta = {"format": FORMAT, "dim": table.dim, "optimizer": int(table.optimizer), "n": n, "planes": list(planes), "extra": extra}
     tmp = os.path.join(path, "meta.json.tmp")
     with open(tmp, "w") as f:

@@ -163,6 +163,34 @@ __device__ __forceinline__ f32x4 widen_bf16x4(const u32x2 p) {
     return v;
 }
 
+// ---- int8 ROWS (SPEC.md §3 "Row storage type"): a table whose value plane holds int8 codes and one fp32 scale per row --------------------
+// A slot's row is dim two's-complement codes followed by a 16-byte tail (the scale, then twelve zero bytes): dim4 + 4 words of 32 bits.  The element
+// group a lane owns — 4 elements — is ONE word there: group g of slot s is word s * (dim4 + 4) + g, the row's scale is word s * (dim4 + 4) + dim4 (the
+// same address in every lane of the tile, asked for next to the groups, never behind them).  All of it in 64 bits.
+// The row storage type of a lookup instance: kRowsF32 / kRowsBF16 are what `false` / `true` of the earlier bf16-rows flag convert to.
+constexpr int kRowsF32 = 0, kRowsBF16 = 1, kRowsI8 = 2;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // one 16-byte group of a packed row
+__device__ __forceinline__ uint64_t i8_row_word(int64_t slot, uint32_t dim4) { return (uint64_t)slot * ((uint64_t)dim4 + 4u); }
+// D of the spec: y = (float)q * scale, one multiply per element (the library is built with -ffp-contract=off)
+__device__ __forceinline__ f32x4 dequant_i8x4(uint32_t w, float scale) {
+    f32x4 v;
+    v.x = (float)(int8_t)(w & 0xFFu) * scale; v.y = (float)(int8_t)((w >> 8) & 0xFFu) * scale;
+    v.z = (float)(int8_t)((w >> 16) & 0xFFu) * scale; v.w = (float)(int8_t)(w >> 24) * scale;
+    return v;
+}
+// Q of the spec for four elements under the row's scale: a true division (no reciprocal), rint = ties to even, clamped to [-127, 127]; scale == 0: codes 0
+__device__ __forceinline__ uint32_t quant_i8x4(const f32x4 x, float scale) {
+    if (scale == 0.f) return 0u;
+    const float e[4] = {x.x, x.y, x.z, x.w};
+    uint32_t w = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float r = fminf(fmaxf(__builtin_rintf(e[k] / scale), -127.f), 127.f);
+        w |= ((uint32_t)(int)r & 0xFFu) << (8 * k);
+    }
+    return w;
+}
+
 // ---- pooled lookups (meepo_find.hip: one table and the uniform group; meepo_mixed.hip: the mixed group) ------------------------------
 // a bag of this many keys or more is served by the wave's four tiles together (pooled_bags)
 constexpr uint32_t kPoolLong = 16;

@@ -155,10 +155,11 @@ __global__ __launch_bounds__(256) void rehash_kernel(const int64_t* __restrict__
 // count, ONE atomic reserves the chunk's output range.  Pass B: per 64-slot group, ranks from the ballot mask;
 // keys are written by their own lane, rows are copied four at a time (one per 16-lane tile).
 // BROWS: `values` is a bf16-row plane (SPEC.md §3 "Row storage type"; no state planes): each 8-byte group is widened on its way into the fp32 values_out —
-// source and destination are different buffers, so nothing is expanded in place.
+// source and destination are different buffers, so nothing is expanded in place.  As a row storage type (ROWS): false = kRowsF32, true = kRowsBF16;
+// kRowsI8: an int8-row plane (dim4 + 4 words per slot, no state planes) — the tile loads the row's scale with its words and dequantizes on the way out.
 constexpr int kExportGroups = 16;
 
-template <bool BROWS>
+template <int ROWS>
 __global__ __launch_bounds__(256) void export_kernel(const int64_t* __restrict__ tkeys, const float4* __restrict__ values,
                                                      const float4* __restrict__ s1, const float4* __restrict__ s2,
                                                      uint64_t begin, uint64_t capacity /* = end of the slot range */, uint32_t dim4,
@@ -200,8 +201,19 @@ __global__ __launch_bounds__(256) void export_kernel(const int64_t* __restrict__
                 const uint64_t pos = pos0 + done + tile;
                 if (p >= 0 && pos < cap) {
                     const uint64_t src = (c0 + (uint64_t)j * 64 + p) * dim4, dst = pos * dim4;
+                    [[maybe_unused]] const uint32_t* __restrict__ qrow = nullptr;   // int8 rows: the row's words, and its scale loaded with them
+                    [[maybe_unused]] float scale = 0.f;
+                    if constexpr (ROWS == kRowsI8) {
+                        qrow = reinterpret_cast<const uint32_t*>(values) + i8_row_word((int64_t)(c0 + (uint64_t)j * 64 + p), dim4);
+                        scale = __builtin_bit_cast(float, qrow[dim4]);
+                    }
                     for (uint32_t c = tl; c < dim4; c += 16) {
-                        if constexpr (BROWS) {
+                        if constexpr (ROWS == kRowsI8) {
+                            if (values_out) {
+                                const f32x4 v = dequant_i8x4(qrow[c], scale);
+                                values_out[dst + c] = make_float4(v.x, v.y, v.z, v.w);
+                            }
+                        } else if constexpr (ROWS == kRowsBF16) {
                             if (values_out) {
                                 const f32x4 v = widen_bf16x4(reinterpret_cast<const u32x2*>(values)[src + c]);
                                 values_out[dst + c] = make_float4(v.x, v.y, v.z, v.w);
@@ -242,7 +254,7 @@ int mee_reserve(mee_table* t, uint64_t new_capacity, void* stream) {
     hipStream_t st = as_stream(stream);
     int64_t* nkeys = nullptr; uint32_t* nhits = nullptr;
     float *nv = nullptr, *n1 = nullptr, *n2 = nullptr;
-    const uint64_t plane = ncap * (uint64_t)t->dim * (t->bf16_rows ? 2 : sizeof(float));
+    const uint64_t plane = ncap * (uint64_t)t->row_bytes;
     hipError_t e = hipMalloc((void**)&nkeys, ncap * sizeof(int64_t));
     if (e == hipSuccess && t->hits) e = hipMalloc((void**)&nhits, ncap * sizeof(uint32_t));
     if (e == hipSuccess) e = plane_alloc(t->value_memory, &nv, plane);
@@ -309,8 +321,8 @@ int mee_export_range(const mee_table* t, uint64_t slot_begin, uint64_t slot_end,
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
     zero_words(&t->op->n_export, sizeof(unsigned long long), st);
-    with_flag(t->bf16_rows, [&](auto brows) {
-        export_kernel<decltype(brows)::value><<<grid_for(slot_end - slot_begin, 4 * 64 * kExportGroups, 256 * 16), 256, 0, st>>>(
+    with_value<kRowsI8, kRowsBF16, kRowsF32>(t->int8_rows ? kRowsI8 : t->bf16_rows ? kRowsBF16 : kRowsF32, [&](auto rows) {
+        export_kernel<decltype(rows)::value><<<grid_for(slot_end - slot_begin, 4 * 64 * kExportGroups, 256 * 16), 256, 0, st>>>(
             t->keys, (const float4*)t->values, (const float4*)t->s1, (const float4*)t->s2, slot_begin, slot_end, t->dim4, d_keys_out,
             (float4*)d_values_out, t->s1 ? (float4*)d_state1_out : nullptr, t->s2 ? (float4*)d_state2_out : nullptr, cap, t->op);
     });
@@ -345,7 +357,7 @@ int mee_table_plane(const mee_table* t, uint32_t plane, void** ptr_out, uint64_t
     const float* p = plane_of(t, plane);
     if (!p) return fail(MEE_ERR_UNSUPPORTED, "mee_table_plane: plane %u does not exist (optimizer=%u)", plane, t->optimizer);
     *ptr_out = const_cast<float*>(p);
-    if (row_stride_bytes) *row_stride_bytes = (uint64_t)t->dim * (t->bf16_rows ? 2 : sizeof(float));
+    if (row_stride_bytes) *row_stride_bytes = t->row_bytes;   // 4 x dim, 2 x dim (bf16 rows) or dim + 16 (int8 rows)
     if (value_memory) *value_memory = t->value_memory;
     return MEE_OK;
 }

@@ -22,6 +22,11 @@ namespace mee {
 // the 8 bytes leave as they came (no second rounding); with fp32 out they are widened in registers.  The policy bits 1 (streaming row loads) and 4
 // (cached stores) act in the compiled shapes (DIM4 16 / 32); the run-time shape (DIM4 = 0) loads and stores cached whatever they say, as the fp32
 // run-time path does (bit 2, the bucket loads, acts in every shape).  The instances with BROWS = false are the code they were before the parameter existed.
+// ROWS is that parameter as a row storage type: kRowsF32 (false), kRowsBF16 (true) and kRowsI8 — `values` is an int8-row plane (meepo_device.h: dim4 + 4
+// words per slot).  Same tiles, same R keys in flight, same index arithmetic on the output; the element group a lane loads is ONE word, and every lane of
+// the tile loads the row's scale word with it (one address per tile, issued with the row loads, never behind them).  The lane dequantizes in registers
+// (dequant_i8x4) and stores a float4, or 8 bytes through the library's bf16 rounding (store_bf16x4) — what the fp32 twin's bf16-out find does with the same
+// values.  A missing key gets the fp32 default as it is.  Policy bits as in the bf16-row branch.
 
 // the store of one element group of a bf16 ROW (store_brow_as, meepo_device.h) under find_span's NT bits
 template <int NT, bool CACHED>
@@ -30,7 +35,15 @@ __device__ __forceinline__ void store_brow(f32x4* __restrict__ out, uint64_t idx
 }
 
 // the find of n positions by `n_waves` waves of which this is wave `wave` (each wave step takes 4R consecutive positions)
-template <int DIM4, int R, int NT, bool BROWS = false>
+// the store of one dequantized element group of an int8 ROW under find_span's NT bits: a float4, or 4 bf16 rounded here, once
+template <int NT, bool CACHED>
+__device__ __forceinline__ void store_qrow(f32x4* __restrict__ out, uint64_t idx, const f32x4 v) {
+    if constexpr ((NT & 256) != 0) store_bf16x4<CACHED>(out, idx, v);
+    else if constexpr (CACHED) out[idx] = v;
+    else __builtin_nontemporal_store(v, &out[idx]);
+}
+
+template <int DIM4, int R, int NT, int ROWS = kRowsF32>
 __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, const f32x4* __restrict__ values, uint64_t nb,
                                           const int64_t* __restrict__ keys, uint64_t n, f32x4* __restrict__ out,
                                           uint8_t* __restrict__ found, float defv, uint32_t dim4_rt, uint32_t* hits,
@@ -77,7 +90,59 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
             for (int r = 0; r < R; ++r)
                 if (slot[r] >= 0 && tl == 0) atomicAdd(&hits[slot[r]], 1u);
         }
-        if constexpr (BROWS) {
+        if constexpr (ROWS == kRowsI8) {
+            static_assert((NT & ~(7 | 256)) == 0, "int8 rows: the plain find only");
+            const uint32_t* __restrict__ qrows = reinterpret_cast<const uint32_t*>(values);
+            if constexpr (DIM4 != 0) {
+                constexpr int C = DIM4 / 16;
+                uint32_t row[R][C], sc[R];
+                bool all_hit = true;   // the wave-uniform common case, as below
+#pragma unroll
+                for (int r = 0; r < R; ++r) all_hit = all_hit && inb[r] && slot[r] >= 0;
+                if (__all(all_hit)) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const uint32_t* __restrict__ q = qrows + i8_row_word(slot[r], DIM4);
+#pragma unroll
+                        for (int c = 0; c < C; ++c) row[r][c] = (NT & 1) ? __builtin_nontemporal_load(&q[c * 16 + tl]) : q[c * 16 + tl];
+                        sc[r] = (NT & 1) ? __builtin_nontemporal_load(&q[DIM4]) : q[DIM4];
+                    }
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const uint64_t i = base + r * 4 + tile;
+#pragma unroll
+                        for (int c = 0; c < C; ++c) store_qrow<NT, (NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, dequant_i8x4(row[r][c], __builtin_bit_cast(float, sc[r])));
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const uint32_t* __restrict__ q = qrows + i8_row_word(slot[r] >= 0 ? slot[r] : 0, DIM4);
+#pragma unroll
+                        for (int c = 0; c < C; ++c) row[r][c] = slot[r] >= 0 ? ((NT & 1) ? __builtin_nontemporal_load(&q[c * 16 + tl]) : q[c * 16 + tl]) : 0u;
+                        sc[r] = slot[r] >= 0 ? ((NT & 1) ? __builtin_nontemporal_load(&q[DIM4]) : q[DIM4]) : 0u;
+                    }
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const uint64_t i = base + r * 4 + tile;
+                        if (inb[r]) {
+#pragma unroll
+                            for (int c = 0; c < C; ++c)
+                                store_qrow<NT, (NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, slot[r] >= 0 ? dequant_i8x4(row[r][c], __builtin_bit_cast(float, sc[r])) : def4);
+                        }
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const uint64_t i = base + r * 4 + tile;
+                    if (inb[r]) {
+                        const uint32_t* __restrict__ q = qrows + i8_row_word(slot[r] >= 0 ? slot[r] : 0, dim4);
+                        const float scale = slot[r] >= 0 ? __builtin_bit_cast(float, q[dim4]) : 0.f;
+                        for (uint32_t c = tl; c < dim4; c += 16) store_qrow<NT, true>(out, i * dim4 + c, slot[r] >= 0 ? dequant_i8x4(q[c], scale) : def4);
+                    }
+                }
+            }
+        } else if constexpr (ROWS == kRowsBF16) {
             static_assert((NT & ~(7 | 256)) == 0, "bf16 rows: the plain find only");
             const u32x2* __restrict__ brows = reinterpret_cast<const u32x2*>(values);
             const u32x2 def2 = bf16x4_of(defv, defv, defv, defv);   // (the table's default value is a bf16 value: packing it loses nothing)
@@ -198,12 +263,12 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
     }
 }
 
-template <int DIM4, int R, int NT, bool BROWS = false>
+template <int DIM4, int R, int NT, int ROWS = kRowsF32>
 __global__ __launch_bounds__(256) void find_kernel(const int64_t* __restrict__ tkeys, const f32x4* __restrict__ values,
                                                    uint64_t nb, const int64_t* __restrict__ keys, uint64_t n,
                                                    f32x4* __restrict__ out, uint8_t* __restrict__ found, float defv,
                                                    uint32_t dim4_rt, uint32_t* hits, int64_t* __restrict__ slots_out = nullptr, int64_t handle_tag = 0) {
-    find_span<DIM4, R, NT, BROWS>(tkeys, values, nb, keys, n, out, found, defv, dim4_rt, hits, slots_out,
+    find_span<DIM4, R, NT, ROWS>(tkeys, values, nb, keys, n, out, found, defv, dim4_rt, hits, slots_out,
                            (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), (uint64_t)gridDim.x * (blockDim.x >> 6), handle_tag);
 }
 
@@ -683,14 +748,15 @@ int find_plane(const mee_table* t, const float* plane, float miss_value, const i
         with_value<3, 1>(path.kind == FindPath::CountedMissing ? 3 : 1, [&](auto flags) {
             find_missing_kernel<flags><<<grid_for(n, 256, 8192), 256, 0, st>>>(t->keys, (const float4*)plane, t->nb, t->dim4, d_keys, n, (float4*)d_out, d_found, t->hits);
         });
-    } else if (t->bf16_rows) with_row_shape(t->dim4, [&](auto d4) {
-        // a bf16-ROW table (Plain only: the entry points see to that): find_span's BROWS instances, per row shape at its default keys in flight, fp32 or bf16 out
+    } else if (t->bf16_rows || t->int8_rows) with_row_shape(t->dim4, [&](auto d4) {
+        // a bf16-ROW or int8-ROW table (Plain only: the entry points see to that): find_span's kRowsBF16 / kRowsI8 instances, per row shape at its default keys
+        // in flight, fp32 or bf16 out
         constexpr int D4 = d4;
         constexpr int R = RowShape<D4>::rows_per_tile;
         const unsigned grid = grid_for(n, (fblock / 64u) * 4u * (unsigned)R, t->find_grid_cap > 0 ? (unsigned)t->find_grid_cap : (1u << 22));
-        with_flag(bf16, [&](auto b16) { with_value<0, 1, 2, 3, 4, 5, 6, 7>(nt, [&](auto ntc) {
-            find_kernel<D4, R, (decltype(b16)::value ? 256 : 0) | decltype(ntc)::value, true><<<grid, fblock, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, nullptr, nullptr, 0);
-        }); });
+        with_flag(t->int8_rows, [&](auto i8) { with_flag(bf16, [&](auto b16) { with_value<0, 1, 2, 3, 4, 5, 6, 7>(nt, [&](auto ntc) {
+            find_kernel<D4, R, (decltype(b16)::value ? 256 : 0) | decltype(ntc)::value, decltype(i8)::value ? kRowsI8 : kRowsBF16><<<grid, fblock, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, nullptr, nullptr, 0);
+        }); }); });
     });
     else if (bf16) with_row_shape(t->dim4, [&](auto d4) {
         // bf16 rows: the same kernel with NT | 256, instantiated for each row shape's default keys in flight only ("find_rounds" does not apply)
@@ -884,6 +950,7 @@ static int find_pooled_common(const mee_table* t, const int64_t* d_keys, size_t 
 int mee_find_pooled(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, float* d_out,
                     uint8_t* d_found, int mode, void* stream) {
     MEE_RANGE("mee_find_pooled");
+    MEE_NO_INT8_ROWS(t, "mee_find_pooled");   // (an int8-row table has no pooled lookup yet)
     if (!t || (n_bags && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled: null argument");
     if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
     return find_pooled_common(t, d_keys, n, d_bag_offsets, n_bags, nullptr, d_out, MEE_DTYPE_F32, d_found, nullptr, mode, stream);
@@ -902,6 +969,7 @@ int mee_find_pooled_as(const mee_table* t, const int64_t* d_keys, size_t n, cons
                        void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
     MEE_RANGE("mee_find_pooled_as");
     if (d_weights) MEE_FP32_ROWS_ONLY(t, "mee_find_pooled_as");
+    MEE_NO_INT8_ROWS(t, "mee_find_pooled_as");
     if (!t || (n_bags && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: null argument");
     if (int rc = check_out_dtype(d_out, out_dtype, "mee_find_pooled_as")) return rc;
     if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");

@@ -250,6 +250,7 @@ int mee_group_create(mee_table* const* tables, uint32_t n_tables, uint64_t max_a
     *out = nullptr;
     for (uint32_t j = 0; j < n_tables; ++j)
         if (!tables[j]) return fail(MEE_ERR_INVALID_ARG, "mee_group_create: table %u is null", j);
+    for (uint32_t j = 0; j < n_tables; ++j) MEE_NO_INT8_ROWS(tables[j], "mee_group_create");   // (an int8-row table is no member: covers every mee_group_* operator)
     const TableView v0 = table_view(tables[0]);
     // one row storage type per group: it is a compile-time property of every launch (the BROWS instances), not a per-member branch in the row fetch
     for (uint32_t j = 1; j < n_tables; ++j)

@@ -29,7 +29,8 @@ inline int fail(int code, const char* fmt, ...) {
 
 // the typed-output forms (mee_*_as): fp32 or bf16 rows; a bf16 row group is one 8-byte store, so the buffer is 8-byte aligned
 inline int check_out_dtype(const void* d_out, uint32_t out_dtype, const char* name) {
-    if (out_dtype != MEE_DTYPE_F32 && out_dtype != MEE_DTYPE_BF16) return fail(MEE_ERR_INVALID_ARG, "%s: unknown out_dtype %u (MEE_DTYPE_F32 or MEE_DTYPE_BF16)", name, out_dtype);
+    if (out_dtype != MEE_DTYPE_F32 && out_dtype != MEE_DTYPE_BF16)   // (MEE_DTYPE_INT8 names a row storage type only)
+        return fail(MEE_ERR_INVALID_ARG, "%s: unknown out_dtype %u (MEE_DTYPE_F32 or MEE_DTYPE_BF16)", name, out_dtype);
     if (out_dtype == MEE_DTYPE_BF16 && ((uintptr_t)d_out & 7)) return fail(MEE_ERR_INVALID_ARG, "%s: a bf16 output must be 8-byte aligned", name);
     return MEE_OK;
 }
@@ -83,10 +84,13 @@ struct TableView {
     bool bf16_rows;        // the value plane holds bf16 rows (MEE_FLAG_BF16_ROWS): `values` is then dim4 8-byte groups per slot
 };
 TableView table_view(const mee_table* t);
-// The operators a bf16-row table does not have (include/meepo_embedding.h, MEE_FLAG_BF16_ROWS) — and every create that takes tables — say so through
-// this one check, before they launch or write anything: MEE_ERR_UNSUPPORTED naming `op`, MEE_OK for an fp32 table or a null one (defined in meepo_table.hip)
-int refuse_bf16_rows(const mee_table* t, const char* op);
-#define MEE_FP32_ROWS_ONLY(t, op) do { if (int rc_ = ::mee::refuse_bf16_rows((t), (op))) return rc_; } while (0)
+// The operators a serving table — bf16 rows or int8 rows — does not have (include/meepo_embedding.h, MEE_FLAG_BF16_ROWS / MEE_FLAG_INT8_ROWS) — and every
+// create that takes tables — say so through this one check, before they launch or write anything: MEE_ERR_UNSUPPORTED naming `op` and the table's row
+// type, MEE_OK for an fp32 table or a null one (defined in meepo_table.hip).  bf16_too = false: only an int8-row table is refused (mee_group_create, which
+// takes bf16-row members).
+int refuse_narrow_rows(const mee_table* t, const char* op, bool bf16_too = true);
+#define MEE_FP32_ROWS_ONLY(t, op) do { if (int rc_ = ::mee::refuse_narrow_rows((t), (op))) return rc_; } while (0)
+#define MEE_NO_INT8_ROWS(t, op) do { if (int rc_ = ::mee::refuse_narrow_rows((t), (op), false)) return rc_; } while (0)
 int find_skip_padding(const mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint8_t* d_found, void* stream, uint32_t out_dtype = MEE_DTYPE_F32);   // meepo_find.hip
 
 // ---- table groups (meepo_group.hip: grouped find / locate; meepo_table.hip: grouped apply) ---------------------------------
@@ -160,9 +164,9 @@ struct mee_group {
 namespace mee {
 int group_refresh(mee_group* g, void* stream);   // re-upload descriptors of members whose planes moved
 int group_locate(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, uint64_t off_stride, size_t n, int64_t* d_gslot, hipStream_t st);
-// refuse_bf16_rows for a group: the operators a bf16-row group does not have (include/meepo_embedding.h, the group section) say so through this one check,
+// refuse_narrow_rows for a group: the operators a bf16-row group does not have (include/meepo_embedding.h, the group section) say so through this one check,
 // before they launch or write anything: MEE_ERR_UNSUPPORTED naming `op` (and `what` of it, when only an argument is refused), MEE_OK for an fp32 group or a
-// null one (defined next to refuse_bf16_rows in meepo_table.hip)
+// null one (defined next to refuse_narrow_rows in meepo_table.hip)
 int refuse_bf16_group(const mee_group* g, const char* op, const char* what = nullptr);
 #define MEE_FP32_GROUP_ONLY(g, ...) do { if (int rc_ = ::mee::refuse_bf16_group((g), __VA_ARGS__)) return rc_; } while (0)
 }

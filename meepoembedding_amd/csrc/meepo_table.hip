@@ -87,6 +87,45 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const f32x4* __restrict_
     }
 }
 
+// ---- int8-row tables (SPEC.md §3 "Row storage type"): the one place where a written row is quantized ------------------------------
+// fp32 [n][dim] -> [n][dim + 16] in the table's pack scratch: a 16-lane tile per row (four rows per wave step).  Lane tl holds the 16 consecutive
+// elements of the row's code groups tl, tl + 16, tl + 32, tl + 48 (those below dim / 16 = n_cg: dim <= 1024) in registers; the row's max |x| is reduced
+// across the tile with lane shuffles, the scale is ONE correctly rounded division, and every code group leaves as one 16-byte store; lane 0 writes the
+// tail group (scale, twelve zero bytes).  The movers then take the packed rows as n_cg + 1 opaque 16-byte groups.
+__global__ __launch_bounds__(256) void quantize_rows_kernel(const f32x4* __restrict__ rows, u32x4* __restrict__ packed, uint64_t n, uint32_t n_cg) {
+    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t r0 = wave * 4; r0 < n; r0 += n_waves * 4) {   // wave-uniform
+        const uint64_t r = r0 + tile;
+        f32x4 x[4][4];
+        float m = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t cg = (uint32_t)tl + 16u * j;
+            const bool has = r < n && cg < n_cg;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                x[j][k] = has ? __builtin_nontemporal_load(&rows[(r * n_cg + cg) * 4 + k]) : f32x4{0.f, 0.f, 0.f, 0.f};   // read exactly once
+                m = fmaxf(m, fmaxf(fmaxf(fabsf(x[j][k].x), fabsf(x[j][k].y)), fmaxf(fabsf(x[j][k].z), fabsf(x[j][k].w))));
+            }
+        }
+#pragma unroll
+        for (int d = 8; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));   // (a mask below 16 stays inside the tile)
+        const float scale = m / 127.0f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t cg = (uint32_t)tl + 16u * j;
+            if (r < n && cg < n_cg) {
+                u32x4 q;
+                q.x = quant_i8x4(x[j][0], scale); q.y = quant_i8x4(x[j][1], scale); q.z = quant_i8x4(x[j][2], scale); q.w = quant_i8x4(x[j][3], scale);
+                packed[r * ((uint64_t)n_cg + 1) + cg] = q;
+            }
+        }
+        if (r < n && tl == 0) packed[r * ((uint64_t)n_cg + 1) + n_cg] = u32x4{__builtin_bit_cast(uint32_t, scale), 0u, 0u, 0u};
+    }
+}
+
 // ---- group table: one entry per distinct key of the batch ---------------------------------------------------
 __device__ __forceinline__ uint32_t group_claim(const GroupTable& g, int64_t key, bool& claimed) {
     const unsigned long long bk = (unsigned long long)key ^ kBias;  // != 0 because key != kEmpty
@@ -436,8 +475,10 @@ TableView table_view(const mee_table* t) {
                      t->initializer, t->init_scale, t->init_acc, t->init_seed, &t->ctr->status, t->hits, t->bf16_rows};
 }
 
-int refuse_bf16_rows(const mee_table* t, const char* op) {
-    if (t && t->bf16_rows)
+int refuse_narrow_rows(const mee_table* t, const char* op, bool bf16_too) {
+    if (t && t->int8_rows)
+        return fail(MEE_ERR_UNSUPPORTED, "%s: not available on an int8-row table (MEE_FLAG_INT8_ROWS: such a serving table has find, insert, assign, remove, locate, export and reserve)", op);
+    if (t && t->bf16_rows && bf16_too)
         return fail(MEE_ERR_UNSUPPORTED, "%s: not available on a bf16-row table (MEE_FLAG_BF16_ROWS: a serving table has find, find_pooled, insert, assign, remove, locate, export and reserve)", op);
     return MEE_OK;
 }
@@ -528,8 +569,20 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
     if (cfg->capacity == 0 || cfg->dim < 4 || cfg->dim > 1024 || (cfg->dim & 3))
         return fail(MEE_ERR_INVALID_ARG, "mee_table_create: capacity must be >0 and dim a multiple of 4 in [4,1024]");
     if (cfg->optimizer > MEE_OPT_ADAM || cfg->initializer > MEE_INIT_UNIFORM || cfg->value_memory > MEE_MEM_HOST_PINNED ||
-        (cfg->flags & ~(uint32_t)(MEE_FLAG_TRACK_HITS | MEE_FLAG_ADMISSION | MEE_FLAG_BF16_ROWS)) != 0)
+        (cfg->flags & ~(uint32_t)(MEE_FLAG_TRACK_HITS | MEE_FLAG_ADMISSION | MEE_FLAG_BF16_ROWS | MEE_FLAG_INT8_ROWS)) != 0)
         return fail(MEE_ERR_INVALID_ARG, "mee_table_create: bad optimizer/initializer/value_memory");
+    if (cfg->flags & MEE_FLAG_INT8_ROWS) {   // a serving table: SPEC.md §3 "Row storage type" (the rules of MEE_FLAG_BF16_ROWS, and dim % 16)
+        if (cfg->flags & MEE_FLAG_BF16_ROWS)
+            return fail(MEE_ERR_INVALID_ARG, "mee_table_create: MEE_FLAG_INT8_ROWS excludes MEE_FLAG_BF16_ROWS (a table has one row storage type; flags=0x%x)", cfg->flags);
+        if (cfg->optimizer != MEE_OPT_NONE)
+            return fail(MEE_ERR_INVALID_ARG, "mee_table_create: MEE_FLAG_INT8_ROWS with optimizer=%u (an int8-row table is a serving table: it has no optimizer)", cfg->optimizer);
+        if (cfg->dim & 15)
+            return fail(MEE_ERR_INVALID_ARG, "mee_table_create: MEE_FLAG_INT8_ROWS needs dim to be a multiple of 16 (dim=%u: the codes of an int8 row must be whole 16-byte groups)", cfg->dim);
+        if (cfg->flags & (MEE_FLAG_TRACK_HITS | MEE_FLAG_ADMISSION))
+            return fail(MEE_ERR_INVALID_ARG, "mee_table_create: MEE_FLAG_INT8_ROWS excludes MEE_FLAG_TRACK_HITS and MEE_FLAG_ADMISSION (flags=0x%x)", cfg->flags);
+        if (cfg->value_memory != MEE_MEM_HBM)
+            return fail(MEE_ERR_INVALID_ARG, "mee_table_create: MEE_FLAG_INT8_ROWS needs value_memory = MEE_MEM_HBM (an int8-row table is no cold tier)");
+    }
     if (cfg->flags & MEE_FLAG_BF16_ROWS) {   // a serving table: SPEC.md §3 "Row storage type"
         if (cfg->optimizer != MEE_OPT_NONE)
             return fail(MEE_ERR_INVALID_ARG, "mee_table_create: MEE_FLAG_BF16_ROWS with optimizer=%u (a bf16-row table is a serving table: it has no optimizer)", cfg->optimizer);
@@ -563,7 +616,9 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
     t->capacity = t->nb * kW;
     t->dim = cfg->dim; t->dim4 = cfg->dim / 4;
     t->bf16_rows = (cfg->flags & MEE_FLAG_BF16_ROWS) != 0;
-    t->mv_dim4 = t->bf16_rows ? cfg->dim / 8 : t->dim4;
+    t->int8_rows = (cfg->flags & MEE_FLAG_INT8_ROWS) != 0;
+    t->mv_dim4 = t->int8_rows ? cfg->dim / 16 + 1 : t->bf16_rows ? cfg->dim / 8 : t->dim4;
+    t->row_bytes = t->mv_dim4 * 16u;   // (the default value of an int8-row table stays the fp32 value it was given: a missing key's row is not quantized)
     t->optimizer = cfg->optimizer; t->initializer = cfg->initializer; t->value_memory = cfg->value_memory;
     t->max_batch = cfg->max_batch;
     t->default_value = t->bf16_rows ? bf16_value_of(cfg->default_value) : cfg->default_value; t->init_acc = cfg->initial_accumulator;
@@ -575,7 +630,7 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
     t->find_grid_cap = 0;
     t->find_nt = -1;  // auto
 
-    const uint64_t plane = t->capacity * (uint64_t)t->dim * (t->bf16_rows ? 2 : sizeof(float));
+    const uint64_t plane = t->capacity * (uint64_t)t->row_bytes;
     const uint64_t mb = t->max_batch;
     int rc = MEE_OK;
 #define ALLOC(ptr, bytes)                                                                                     \
@@ -619,9 +674,9 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
     t->bs.max_part = (uint32_t)t->max_part;
     if (t->optimizer != MEE_OPT_NONE) ALLOC(t->bs.gacc, t->max_part * (uint64_t)t->dim * sizeof(double));
     ALLOC(t->ctr, sizeof(Counters)); ALLOC(t->op, sizeof(OpCounters));
-    if (t->bf16_rows) ALLOC(t->pack, mb * (uint64_t)t->dim * 2);   // the rounded rows of one insert / assign batch
+    if (t->bf16_rows || t->int8_rows) ALLOC(t->pack, mb * (uint64_t)t->row_bytes);   // the rounded / quantized rows of one insert / assign batch
 #undef ALLOC
-    t->workspace_bytes = (t->pack ? mb * (uint64_t)t->dim * 2 : 0) + S * 24 + mb * 9 + (t->bs.gacc ? t->max_part * (uint64_t)t->dim * sizeof(double) : 0) + sizeof(Counters) + sizeof(OpCounters);
+    t->workspace_bytes = (t->pack ? mb * (uint64_t)t->row_bytes : 0) + S * 24 + mb * 9 + (t->bs.gacc ? t->max_part * (uint64_t)t->dim * sizeof(double) : 0) + sizeof(Counters) + sizeof(OpCounters);
     if ((rc = bucket_scratch_alloc(t)) != MEE_OK) goto bad;   // the bucketed machinery's scratch: partition (every table), pending records (tables with an optimizer); adds to workspace_bytes
     if (hipHostMalloc((void**)&t->h_ctr, sizeof(Counters)) != hipSuccess || hipHostMalloc((void**)&t->h_op, sizeof(OpCounters)) != hipSuccess) {
         rc = fail(MEE_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
@@ -683,12 +738,15 @@ int mee_clear(mee_table* t, void* stream) {
 
 // `skip` (nullable): positions whose byte is non-zero take no part (they were served by another table of a tiered pair)
 // in_dtype: the type of d_values' rows (mee_insert_as / mee_assign_as).  A bf16-row table takes fp32 rows through pack_rows_kernel (the one rounding) and
-// bf16 rows as they are; behind that the movers see rows of mv_dim4 opaque 16-byte groups, whatever they hold.
+// bf16 rows as they are; an int8-row table takes fp32 rows only, through quantize_rows_kernel (the one quantization).  Behind that the movers see rows
+// of mv_dim4 opaque 16-byte groups, whatever they hold.
 static int upsert_common(mee_table* t, float* plane, const int64_t* d_keys, const float* d_values, size_t n, uint8_t* d_found,
                          void* stream, bool claim, const char* name, const uint8_t* skip = nullptr, uint32_t in_dtype = MEE_DTYPE_F32) {
     if (!t || !plane || (n && (!d_keys || !d_values))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
     if (in_dtype != MEE_DTYPE_F32 && in_dtype != MEE_DTYPE_BF16) return fail(MEE_ERR_INVALID_ARG, "%s: unknown in_dtype %u (MEE_DTYPE_F32 or MEE_DTYPE_BF16)", name, in_dtype);
-    if (in_dtype == MEE_DTYPE_BF16 && !t->bf16_rows) return fail(MEE_ERR_UNSUPPORTED, "%s: bf16 input rows need a table created with MEE_FLAG_BF16_ROWS (an fp32 table stores fp32 rows)", name);
+    if (in_dtype == MEE_DTYPE_BF16 && !t->bf16_rows)
+        return fail(MEE_ERR_UNSUPPORTED, "%s: bf16 input rows need a table created with MEE_FLAG_BF16_ROWS (%s)", name,
+                    t->int8_rows ? "an int8-row table quantizes fp32 rows" : "an fp32 table stores fp32 rows");
     if (in_dtype == MEE_DTYPE_BF16 && ((uintptr_t)d_values & 15)) return fail(MEE_ERR_INVALID_ARG, "%s: a bf16 input must be 16-byte aligned", name);
     if (int rc = check_batch(t, n, name, stream)) return rc;
     if (n == 0) return MEE_OK;
@@ -699,6 +757,10 @@ static int upsert_common(mee_table* t, float* plane, const int64_t* d_keys, cons
     if (t->bf16_rows && in_dtype == MEE_DTYPE_F32) {
         const uint64_t n_groups = (uint64_t)n * t->dim4;
         pack_rows_kernel<<<grid_for(n_groups, 1024, 4096), 256, 0, st>>>((const f32x4*)d_values, (u32x2*)t->pack, n_groups);
+        d_values = (const float*)t->pack;
+    }
+    if (t->int8_rows) {   // (in_dtype is MEE_DTYPE_F32 here) the one quantization: a tile per row, four rows per wave
+        quantize_rows_kernel<<<grid_for(n, 16, 4096), 256, 0, st>>>((const f32x4*)d_values, (u32x4*)t->pack, (uint64_t)n, t->dim / 16);
         d_values = (const float*)t->pack;
     }
     if (claim) {   // insert: creators write at once, an election only among positions that found their key present (see insert_direct_kernel)
@@ -744,7 +806,7 @@ int mee_assign_as(mee_table* t, const int64_t* d_keys, const void* d_values, uin
 }
 int mee_table_value_dtype(const mee_table* t, uint32_t* out) {
     if (!t || !out) return fail(MEE_ERR_INVALID_ARG, "mee_table_value_dtype: null argument");
-    *out = t->bf16_rows ? MEE_DTYPE_BF16 : MEE_DTYPE_F32;
+    *out = t->int8_rows ? MEE_DTYPE_INT8 : t->bf16_rows ? MEE_DTYPE_BF16 : MEE_DTYPE_F32;
     return MEE_OK;
 }
 int mee_assign_plane(mee_table* t, uint32_t plane, const int64_t* d_keys, const float* d_values, size_t n, uint8_t* d_found,

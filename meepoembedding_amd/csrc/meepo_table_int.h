@@ -99,8 +99,12 @@ struct mee_table {
     // read them as such (find_span / pooled_fetch with BROWS: the lane's element group is 8 bytes).  The MOVERS — insert, assign, rehash, remove — only
     // copy or drop rows: they run unchanged on a row as mv_dim4 opaque 16-byte groups (dim / 8 for bf16 rows, which is why dim % 8 == 0; dim4 otherwise),
     // fed with rows that pack_rows_kernel rounded into `pack` ([max_batch][dim] bf16, allocated at create) or with the caller's own bf16 rows.
-    bool bf16_rows;
-    uint32_t mv_dim4;
+    // int8_rows = the value plane holds int8 rows (MEE_FLAG_INT8_ROWS; never together with bf16_rows): dim codes and a 16-byte tail that starts with the
+    // row's fp32 scale, dim + 16 bytes per slot.  The lookups read them with ROWS = kRowsI8 (the lane's element group is one word); the movers see
+    // mv_dim4 = dim / 16 + 1 opaque groups (which is why dim % 16 == 0), fed with rows that quantize_rows_kernel wrote into `pack` ([max_batch][dim + 16]).
+    // row_bytes: the bytes of a slot's row in the value plane, whatever it holds (4·dim, 2·dim or dim + 16).
+    bool bf16_rows, int8_rows;
+    uint32_t mv_dim4, row_bytes;
     uint32_t* pack;
     float default_value, init_acc, init_scale;
     uint64_t init_seed;

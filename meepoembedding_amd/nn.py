@@ -25,7 +25,7 @@ import weakref
 
 import torch
 
-from ._lib import refuse_bf16_rows as _refuse_bf16_rows
+from ._lib import refuse_narrow_rows as _refuse_narrow_rows
 
 _LAYERS: "weakref.WeakValueDictionary[int, DynamicEmbedding]" = weakref.WeakValueDictionary()
 _IDS = itertools.count(1)
@@ -445,7 +445,7 @@ class DynamicEmbeddingCollection(torch.nn.Module, _SparseOptimizerSettings):
     def __init__(self, group, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
                  out_dtype: torch.dtype = torch.float32):
         super().__init__()
-        _refuse_bf16_rows("DynamicEmbeddingCollection", group)
+        _refuse_narrow_rows("DynamicEmbeddingCollection", group)
         self.group = group
         self._init_settings(optimizer, lr, eps, betas, group, out_dtype)
 
@@ -465,7 +465,7 @@ class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
                  create_missing: bool = False, out_dtype: torch.dtype = torch.float32):
         """out_dtype=torch.bfloat16: the bag is accumulated in fp32 and the finished row rounded once by the lookup; backward widens the bf16 grad."""
         super().__init__()
-        _refuse_bf16_rows("DynamicEmbeddingBag", table)
+        _refuse_narrow_rows("DynamicEmbeddingBag", table)
         if mode not in ("sum", "mean"):
             raise ValueError("mode must be 'sum' or 'mean'")
         self.table, self.mode, self.create_missing = table, mode, create_missing
@@ -496,7 +496,7 @@ class DynamicEmbedding(torch.nn.Module):
     def __init__(self, table, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
                  out_dtype: torch.dtype = torch.float32):
         super().__init__()
-        _refuse_bf16_rows("DynamicEmbedding", table)
+        _refuse_narrow_rows("DynamicEmbedding", table)
         if optimizer not in ("adagrad", "adam"):
             raise ValueError("optimizer must be 'adagrad' or 'adam'")
         self.out_dtype = _check_out_dtype(table, out_dtype)

@@ -37,7 +37,7 @@ class _Raw:
 class PeerShardedFind:
     def __init__(self, local, router, max_batch: int, group=None, slack: float = 1.25, payload: bool = False,
                  device_barrier: bool = True):
-        _lib.refuse_bf16_rows("PeerShardedFind", local)
+        _lib.refuse_narrow_rows("PeerShardedFind", local)
         self.local, self.router, self.group = local, router, group
         self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
         self.device, self.dim, self.max_batch = local.device, local.dim, max_batch

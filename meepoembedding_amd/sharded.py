@@ -33,7 +33,7 @@ import math
 import torch
 import torch.distributed as dist
 
-from ._lib import refuse_bf16_rows
+from ._lib import refuse_narrow_rows
 from .table import _out_dtype
 
 
@@ -101,7 +101,7 @@ class _Exchange:
 
 class ShardedLookupTable(_Exchange):
     def __init__(self, local, router, group=None):
-        refuse_bf16_rows("ShardedLookupTable", local)
+        refuse_narrow_rows("ShardedLookupTable", local)
         self.local = local
         self.dim = local.dim
         super().__init__(router, group)
@@ -347,7 +347,7 @@ class ShardedTableGroup(_Exchange):
         if getattr(local_group, "mixed_dims", False):
             raise ValueError(f"{type(local_group).__name__} has members of different dims: a sharded group exchanges rows of one width "
                              "(one ShardedTableGroup per width, each over a TableGroup)")
-        refuse_bf16_rows("ShardedTableGroup", local_group)
+        refuse_narrow_rows("ShardedTableGroup", local_group)
         self.local = self.local_group = local_group
         self.dim = local_group.dim
         self.n_tables = len(local_group.tables)
@@ -547,7 +547,7 @@ class RcclShardedTable:
         from . import _lib
         from ._lib import check
         self._lib, self._check, self._C = _lib, check, C
-        refuse_bf16_rows("RcclShardedTable", local, cold)
+        refuse_narrow_rows("RcclShardedTable", local, cold)
         self.local, self.group = local, group
         self.dedup = bool(dedup)
         self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)

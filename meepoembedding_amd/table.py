@@ -64,15 +64,21 @@ class LookupTable:
     value_dtype=torch.bfloat16: a SERVING table whose rows are stored as bf16, 2·dim bytes per slot (SPEC.md §3 "Row storage type").  insert / assign /
     import_ round fp32 rows once (or store bf16 rows verbatim), every read widens exactly, find(out_dtype=torch.bfloat16) returns the stored bits: the
     table is indistinguishable from an fp32 table fed the rounded rows.  No optimizer, hit counters, admission or host memory; dim a multiple of 8;
-    the operators outside find / find_pooled (unweighted) / insert / assign / remove / locate / export / reserve / clear raise MeepoError(ERR_UNSUPPORTED)."""
+    the operators outside find / find_pooled (unweighted) / insert / assign / remove / locate / export / reserve / clear raise MeepoError(ERR_UNSUPPORTED).
+
+    int8_rows=True (value_dtype stays torch.float32 in the call; the table then reports .value_dtype == torch.int8): the other serving table — a row is stored as dim int8 codes and one fp32 scale, dim + 16 bytes per slot.  insert / assign /
+    import_ take fp32 rows and quantize each once (scale = max|x| / 127, codes rounded to nearest even), every read gives code x scale: the table is
+    indistinguishable from an fp32 table fed the dequantized rows (a missing key returns default_value as it is).  Rows must be finite.  Same restrictions
+    and operators as a bf16-row table, dim a multiple of 16; it has no find_pooled (ERR_UNSUPPORTED) and is a member of no group."""
     supports_out_dtype = True   # its lookups can write bf16 rows (out_dtype=torch.bfloat16); the tiered / sharded / peer tables cannot
 
     def __init__(self, capacity: int, dim: int, *, device: int | torch.device = 0, optimizer: int = OPT_NONE,
                  max_batch: int = 1 << 20, default_value: float = 0.0, initial_accumulator: float = 0.0,
                  initializer: int = INIT_CONSTANT, init_scale: float = 0.0, init_seed: int = 0, value_memory: int = 0, track_hits: bool = False,
-                 admission: bool = False, value_dtype: torch.dtype = torch.float32):
+                 admission: bool = False, value_dtype: torch.dtype = torch.float32, int8_rows: bool = False):
         if value_dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError(f"value_dtype must be torch.float32 or torch.bfloat16 (got {value_dtype}): rows are stored as fp32 or as bf16")
+            raise ValueError(f"value_dtype must be torch.float32 or torch.bfloat16 (got {value_dtype}): rows are stored as fp32 or as bf16"
+                             + (" — int8 row storage is asked for with int8_rows=True" if value_dtype == torch.int8 else ""))
         if value_dtype == torch.bfloat16:   # a serving table: checked here, before any device is needed (the library checks again)
             if optimizer != OPT_NONE:
                 raise ValueError("value_dtype=torch.bfloat16 is a serving table: it has no optimizer (train in fp32, then checkpoint.load_into a bf16-row table)")
@@ -82,7 +88,18 @@ class LookupTable:
                 raise ValueError("value_dtype=torch.bfloat16 needs value_memory = MEM_HBM (a bf16-row table is no cold tier)")
             if dim % 8:
                 raise ValueError(f"value_dtype=torch.bfloat16 needs dim to be a multiple of 8 (got {dim})")
-        self.value_dtype = value_dtype
+        if int8_rows:   # the same rules, and whole 16-byte groups of codes
+            if value_dtype != torch.float32:
+                raise ValueError("int8_rows=True excludes value_dtype=torch.bfloat16: a table has one row storage type")
+            if optimizer != OPT_NONE:
+                raise ValueError("int8_rows=True is a serving table: it has no optimizer (train in fp32, then checkpoint.load_into an int8-row table)")
+            if track_hits or admission:
+                raise ValueError("int8_rows=True excludes track_hits and admission")
+            if value_memory != _lib.MEM_HBM:
+                raise ValueError("int8_rows=True needs value_memory = MEM_HBM (an int8-row table is no cold tier)")
+            if dim % 16:
+                raise ValueError(f"int8_rows=True needs dim to be a multiple of 16 (got {dim})")
+        self.value_dtype = torch.int8 if int8_rows else value_dtype   # the row storage type, as mee_table_value_dtype reports it
         L = _lib.lib()
         dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         if dev.type != "cuda":
@@ -93,17 +110,17 @@ class LookupTable:
                           initial_accumulator=initial_accumulator, initializer=initializer, init_scale=init_scale,
                           init_seed=init_seed, value_memory=value_memory,
                           flags=(_lib.FLAG_TRACK_HITS if track_hits else 0) | (_lib.FLAG_ADMISSION if admission else 0)
-                          | (_lib.FLAG_BF16_ROWS if value_dtype == torch.bfloat16 else 0))
+                          | (_lib.FLAG_BF16_ROWS if value_dtype == torch.bfloat16 else 0) | (_lib.FLAG_INT8_ROWS if int8_rows else 0))
         self.track_hits = track_hits
-        # (a bf16-row table's default row is the rounded value)
-        self.default_value = float(default_value) if value_dtype == torch.float32 else float(torch.tensor(default_value, dtype=torch.float32).to(torch.bfloat16))
+        # (a bf16-row table's default row is the rounded value; an int8-row table's is the fp32 value as given)
+        self.default_value = float(default_value) if value_dtype != torch.bfloat16 else float(torch.tensor(default_value, dtype=torch.float32).to(torch.bfloat16))
         h = C.c_void_p()
         self._h = None
         check(L.mee_table_create(C.byref(cfg), C.byref(h)))
         self._h = h
         self._opts = dict(device=self.device, optimizer=optimizer, max_batch=max_batch, default_value=default_value,
                           initial_accumulator=initial_accumulator, initializer=initializer, init_scale=init_scale, init_seed=init_seed,
-                          value_memory=value_memory, track_hits=track_hits, admission=admission, value_dtype=value_dtype)
+                          value_memory=value_memory, track_hits=track_hits, admission=admission, value_dtype=value_dtype, int8_rows=int8_rows)
         info = _lib.TableInfo()
         check(L.mee_table_info_get(self._h, C.byref(info)))
         self.capacity, self.n_buckets, self.max_batch = info.capacity, info.n_buckets, info.max_batch
@@ -149,7 +166,7 @@ class LookupTable:
                 r = r.clone()
             return r, _lib.DTYPE_BF16
         if rows.dtype == torch.bfloat16:
-            raise MeepoError(_lib.ERR_UNSUPPORTED, "bf16 rows need a table created with value_dtype=torch.bfloat16 (an fp32 table stores fp32 rows)")
+            raise MeepoError(_lib.ERR_UNSUPPORTED, "bf16 rows need a table created with value_dtype=torch.bfloat16 (an fp32 table stores fp32 rows, an int8-row table quantizes fp32 rows)")
         return self._rows(rows, n), _lib.DTYPE_F32
 
     # -- operators (SPEC.md §3) ----------------------------------------------------------------------------
@@ -897,7 +914,7 @@ class MixedTableGroup:
         self.tables = list(tables)
         if not self.tables:
             raise ValueError("a group needs at least one table")
-        _lib.refuse_bf16_rows("MixedTableGroup", *self.tables)
+        _lib.refuse_narrow_rows("MixedTableGroup", *self.tables)
         self.device = self.tables[0].device
         self.dims = [t.dim for t in self.tables]
         arr = (C.c_void_p * len(self.tables))(*[t._h for t in self.tables])

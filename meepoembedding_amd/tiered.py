@@ -54,8 +54,8 @@ class TieredLookupTable:
 
     def __init__(self, hot, cold, hot_key_limit: int | None = None, sample_every: int = 8, promote_threshold: int = 2,
                  rebalance_every: int = 0, rebalance_max_moves: int = 1 << 20):
-        from ._lib import refuse_bf16_rows
-        refuse_bf16_rows("TieredLookupTable", hot, cold)
+        from ._lib import refuse_narrow_rows
+        refuse_narrow_rows("TieredLookupTable", hot, cold)
         if hot.dim != cold.dim:
             raise ValueError("hot and cold tables must have the same dim")
         self.hot, self.cold, self.dim = hot, cold, hot.dim
