@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import oracle
-from _apply_cases import EXTREME_CASES, bucketed_apply_extremes, every_group_size_batch, keys_of_apply_bucket_zero
+from _apply_cases import EXTREME_CASES, assert_bits_equal_nan_aware, bucketed_apply_extremes, every_group_size_batch, keys_of_apply_bucket_zero
 from meepoembedding_amd import _lib
 from meepoembedding_amd import (INIT_UNIFORM, OPT_ADAGRAD, OPT_ADAM, STATUS_RESERVED_KEY, STATUS_TABLE_FULL, LookupTable,
                                 MeepoError, Router, hash_batch, synth)
@@ -1515,7 +1515,7 @@ def test_find_pooled_bit_exact(dev, dim, mode):
         out, found = t.find_pooled(T(keys, dev), T(off, dev), mode)
         er, ef = o.find(keys)
         assert np.array_equal(found.cpu().numpy(), ef)
-        assert np.array_equal(out.cpu().numpy(), oracle.pool_rows(er, off, mode))
+        assert_bits_equal_nan_aware(out.cpu().numpy(), oracle.pool_rows(er, off, mode), f"find_pooled {mode} dim {dim}")
     # the unpooled find of the same keys, pooled by torch in fp64, agrees to rounding (sanity of the oracle helper itself)
     ref = torch.zeros(lens.size, dim, dtype=torch.float64).index_add_(0, torch.repeat_interleave(torch.arange(lens.size), torch.from_numpy(lens)), torch.from_numpy(er).double())
     if mode == "mean":

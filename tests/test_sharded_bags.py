@@ -13,6 +13,7 @@ import torch
 import torch.distributed as dist
 
 import oracle
+from _apply_cases import assert_bits_equal_nan_aware
 from meepoembedding_amd import _lib, synth
 from meepoembedding_amd.sharded import ShardedLookupTable
 from test_sharded_bf16 import _launch, assert_bf16_of
@@ -372,7 +373,8 @@ def test_one_shard_is_bit_identical_to_find_pooled(dev, dim):
         b16 = torch.full((n_bags + 2, dim), 7.5, dtype=BF16, device=dev)
         o32, f = emulated_find_pooled(tables, router, kt, ot, mode, torch.float32, out=b32[:n_bags])
         o16, _ = emulated_find_pooled(tables, router, kt, ot, mode, BF16, out=b16[:n_bags])
-        assert torch.equal(o32.view(torch.int32), e32.view(torch.int32)) and torch.equal(f, ef), mode
+        assert_bits_equal_nan_aware(o32.cpu().numpy(), e32.cpu().numpy(), mode)
+        assert torch.equal(f, ef), mode
         assert torch.equal(o16.view(torch.int16), e16.view(torch.int16)), mode
         assert bool((b32[n_bags:] == 7.5).all()) and bool((b16[n_bags:] == 7.5).all())     # nothing behind the outputs is touched
 

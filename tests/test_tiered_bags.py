@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import oracle
+from _apply_cases import assert_bits_equal_nan_aware
 from _cpu_backend import CpuTable
 from meepoembedding_amd import synth
 from meepoembedding_amd.tiered import TieredLookupTable
@@ -212,11 +213,13 @@ def test_tiered_find_pooled_is_the_union_bit_for_bit(dev, dim, mode):
     for bname, (keys, off, rows, ef) in exp.items():
         want = oracle.pool_rows(rows, off.cpu().numpy(), mode)
         uo, uf = union.find_pooled(keys, off, mode)
-        assert np.array_equal(_np(uo), want) and np.array_equal(_np(uf), ef)
+        assert_bits_equal_nan_aware(_np(uo), want, f"union {bname}")
+        assert np.array_equal(_np(uf), ef)
         for pname, pair in pairs.items():
             out, found = pair.find_pooled(keys, off, mode)
-            assert np.array_equal(_np(out), want), (pname, bname)
-            assert np.array_equal(_np(out), _np(uo)) and np.array_equal(_np(found), _np(uf)) and np.array_equal(_np(found), ef), (pname, bname)
+            assert_bits_equal_nan_aware(_np(out), want, f"{pname} {bname}")
+            assert_bits_equal_nan_aware(_np(out), _np(uo), f"{pname} {bname} against the union")
+            assert np.array_equal(_np(found), _np(uf)) and np.array_equal(_np(found), ef), (pname, bname)
     keys, off, _, _ = exp["A"]
     for pname, pair in pairs.items():
         # zero bags: nothing is written
