@@ -152,7 +152,8 @@ int mee_find(const mee_table* t, const int64_t* d_keys, size_t n, float* d_out, 
 /* mee_find with the cache policy of THIS call in `flags` (never changes results).  Hints are per request, not per table: two request
  * queues with different access patterns share one table without touching anything the other one's calls read (mee_set_tuning("find_nt")
  * stays as the table's default for callers that pass MEE_FIND_DEFAULT and for mee_find).
- *   MEE_FIND_STREAM_STORES  the dense output is not re-read from cache (result buffers that rotate, outputs beyond the Infinity Cache)
+ *   MEE_FIND_STREAM_STORES  the dense output is not re-read from cache (result buffers that rotate, outputs beyond the Infinity Cache): the rows
+ *                           leave as non-temporal stores (write-through stores were measured and are slower: profiles/find_write_through.md)
  *   MEE_FIND_CACHED_STORES  the opposite: keep the output cached whatever its size (at most one of the two; neither = the library's rule: cached
  *                           while one call's output is <= 128 MB and the table's latest lookups did not rotate over output buffers)
  *   MEE_FIND_STREAM_ROWS    rows are not looked up again soon (uniform streams over a table far larger than the caches); a skewed stream

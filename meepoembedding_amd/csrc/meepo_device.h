@@ -348,6 +348,24 @@ __device__ __forceinline__ void store_brow_as(void* __restrict__ out, uint64_t i
     }
 }
 
+// ---- the 16-byte result stores of the find family (fp32 output, compiled row shapes) ----------------------------------------------
+// One wave step of find_span writes 4R consecutive result rows.  RowStore is those rows as a store target, and the ONE place that says how
+// a 16-byte element group of a result row leaves under the call's policy: CACHED, a plain store (the line stays in the XCD's L2 for whoever
+// reads the rows next), or streaming, a non-temporal global store.  Write-through forms of the streaming store were measured and lost
+// (profiles/find_write_through.md): `sc1` and `sc0 sc1` take 1.5 us off a launch's floor, as the dirty lines they do not leave behind
+// predict, and add 4.2 us per 256K keys to its slope; `sc1 nt` is `nt`; write-through for the batch's tail alone gains nothing either.
+template <bool CACHED>
+struct RowStore {
+    f32x4* first;   // group 0 of the step's first row
+    // first_group: the index in `out` of the step's first element group
+    __device__ __forceinline__ RowStore(f32x4* __restrict__ out, uint64_t first_group) : first(out + first_group) {}
+    // group g of the step (row-in-step * dim4 + group-in-row)
+    __device__ __forceinline__ void operator()(uint32_t g, const f32x4 v) const {
+        if constexpr (CACHED) first[g] = v;
+        else __builtin_nontemporal_store(v, first + g);
+    }
+};
+
 // ---- the bag walk of the pooled lookups and of their backward ------------------------------------------------------------------
 // Geometry: a wave step serves BPW consecutive bags.  BPW = 4: tile t takes bag `bag0 + t`; a bag of fewer than kPoolLong keys is walked by its
 // tile alone, U positions a round (its keys and weights come with ONE coalesced load per tile, lane tl holds position begin + tl, and reach the

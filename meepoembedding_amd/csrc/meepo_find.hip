@@ -36,11 +36,11 @@ __device__ __forceinline__ void store_brow(f32x4* __restrict__ out, uint64_t idx
 
 // the find of n positions by `n_waves` waves of which this is wave `wave` (each wave step takes 4R consecutive positions)
 // the store of one dequantized element group of an int8 ROW under find_span's NT bits: a float4, or 4 bf16 rounded here, once
+// (compiled shapes: group g of the wave step `st`, which is index `first + g` of `out`)
 template <int NT, bool CACHED>
-__device__ __forceinline__ void store_qrow(f32x4* __restrict__ out, uint64_t idx, const f32x4 v) {
-    if constexpr ((NT & 256) != 0) store_bf16x4<CACHED>(out, idx, v);
-    else if constexpr (CACHED) out[idx] = v;
-    else __builtin_nontemporal_store(v, &out[idx]);
+__device__ __forceinline__ void store_qrow(f32x4* __restrict__ out, uint64_t first, const RowStore<CACHED>& st, uint32_t g, const f32x4 v) {
+    if constexpr ((NT & 256) != 0) store_bf16x4<CACHED>(out, first + g, v);
+    else st(g, v);
 }
 
 template <int DIM4, int R, int NT, int ROWS = kRowsF32>
@@ -53,7 +53,9 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
     constexpr int KPW = 4 * R;
     const f32x4 def4 = {defv, defv, defv, defv};
 
+
     for (uint64_t base = wave * KPW; base < n; base += n_waves * KPW) {
+        const RowStore<(NT & 4) != 0> st(out, base * DIM4);   // the step's fp32 result rows (compiled shapes; bf16 out and the run-time shape store for themselves)
         int64_t key[R];
         int64_t slot[R];
         uint64_t b[R];
@@ -109,9 +111,8 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
                     }
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
-                        const uint64_t i = base + r * 4 + tile;
 #pragma unroll
-                        for (int c = 0; c < C; ++c) store_qrow<NT, (NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, dequant_i8x4(row[r][c], __builtin_bit_cast(float, sc[r])));
+                        for (int c = 0; c < C; ++c) store_qrow<NT>(out, base * DIM4, st, (r * 4 + tile) * DIM4 + c * 16 + tl, dequant_i8x4(row[r][c], __builtin_bit_cast(float, sc[r])));
                     }
                 } else {
 #pragma unroll
@@ -123,11 +124,10 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
                     }
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
-                        const uint64_t i = base + r * 4 + tile;
                         if (inb[r]) {
 #pragma unroll
                             for (int c = 0; c < C; ++c)
-                                store_qrow<NT, (NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, slot[r] >= 0 ? dequant_i8x4(row[r][c], __builtin_bit_cast(float, sc[r])) : def4);
+                                store_qrow<NT>(out, base * DIM4, st, (r * 4 + tile) * DIM4 + c * 16 + tl, slot[r] >= 0 ? dequant_i8x4(row[r][c], __builtin_bit_cast(float, sc[r])) : def4);
                         }
                     }
                 }
@@ -138,7 +138,10 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
                     if (inb[r]) {
                         const uint32_t* __restrict__ q = qrows + i8_row_word(slot[r] >= 0 ? slot[r] : 0, dim4);
                         const float scale = slot[r] >= 0 ? __builtin_bit_cast(float, q[dim4]) : 0.f;
-                        for (uint32_t c = tl; c < dim4; c += 16) store_qrow<NT, true>(out, i * dim4 + c, slot[r] >= 0 ? dequant_i8x4(q[c], scale) : def4);
+                        for (uint32_t c = tl; c < dim4; c += 16) {
+                            const f32x4 v = slot[r] >= 0 ? dequant_i8x4(q[c], scale) : def4;
+                            if constexpr ((NT & 256) != 0) store_bf16x4<true>(out, i * dim4 + c, v); else out[i * dim4 + c] = v;
+                        }
                     }
                 }
             }
@@ -208,9 +211,14 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
 #pragma unroll
                     for (int c = 0; c < C; ++c) {
                         if constexpr ((NT & 256) != 0) store_bf16x4<(NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, row[r][c]);
-                        else { if (NT & 4) out[i * DIM4 + c * 16 + tl] = row[r][c]; else __builtin_nontemporal_store(row[r][c], &out[i * DIM4 + c * 16 + tl]); }
+                        else st((r * 4 + tile) * DIM4 + c * 16 + tl, row[r][c]);
                     }
                 }
+                // An empty statement that keeps this block's tail its own.  The compiler merged the step's last store with the last store of the per-lane
+                // path below, and the merged block waits with vmcnt(0): for the row it stores, and with it for every store of the step issued before it.
+                // Apart, the stores leave behind a vmcnt(k) ladder, each as its own row arrives: 32.1 -> 31.2 us per 256K-key launch into rotating buffers
+                // (profiles/find_write_through.md).  Streaming fp32 stores only: the cached and the bf16-out instances are the code they were.
+                if constexpr ((NT & (4 | 256)) == 0) asm volatile("; find_span: end of the all-hit stores");
             } else {
 #pragma unroll
                 for (int r = 0; r < R; ++r)
@@ -224,7 +232,7 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
 #pragma unroll
                         for (int c = 0; c < C; ++c) {
                             if constexpr ((NT & 256) != 0) store_bf16x4<(NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, row[r][c]);
-                            else { if (NT & 4) out[i * DIM4 + c * 16 + tl] = row[r][c]; else __builtin_nontemporal_store(row[r][c], &out[i * DIM4 + c * 16 + tl]); }
+                            else st((r * 4 + tile) * DIM4 + c * 16 + tl, row[r][c]);
                         }
                     }
                 }
