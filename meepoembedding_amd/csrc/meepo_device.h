@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace mee {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));   // what __builtin_nontemporal_load / _store move as one dwordx4
@@ -151,11 +153,53 @@ __device__ __forceinline__ int64_t collect_slots(const int64_t (&slot)[R], int l
     return mine;
 }
 
+// ---- bf16 output of the lookups (SPEC.md §3 "Output type") ------------------------------------------------------------------
+// A lane that holds a float4 of a row stores it as 4 bf16 = 8 bytes; a row of dim bf16 is dim4 such 8-byte groups, so group g of
+// output row i sits at index i * dim4 + g of a u32x2 array — the SAME index the fp32 kernels use on their f32x4 array.
+// two fp32 -> two bfloat16 in one word, round to nearest even: plain casts, which gfx950 does with its packed convert (v_cvt_pk_bf16_f32).  It agrees
+// with the integer rule of the spec on every finite value, denormals included (HIP kernels run with fp32 denormals on), sends a finite value beyond
+// the largest bf16 to inf and a NaN to a NaN: tests/test_bf16_out.py checks exactly these on the device.  (The integer rule written out costs ~30
+// VALU instructions per float4 in the wave's dependent tail — +0.4 us on a latency-bound dim-16 lookup — and a __builtin_convertvector of float2
+// pairs made two pooled instances spill 32 B: profiles/bf16_out.md, profiles/bf16_out_resource_usage.txt.)
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t bf16x2_of(float a, float b) {
+    return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)a) | ((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)b) << 16);
+}
+__device__ __forceinline__ u32x2 bf16x4_of(float a, float b, float c, float d) {
+    u32x2 p;
+    p.x = bf16x2_of(a, b);
+    p.y = bf16x2_of(c, d);
+    return p;
+}
+// the store of one such group; CACHED = false: a streaming (non-temporal) store, as the fp32 kernels use for outputs nothing re-reads from cache
+template <bool CACHED, class V4>
+__device__ __forceinline__ void store_bf16x4(void* out, uint64_t idx, const V4& v) {
+    const u32x2 p = bf16x4_of(v.x, v.y, v.z, v.w);
+    if constexpr (CACHED) reinterpret_cast<u32x2*>(out)[idx] = p;
+    else __builtin_nontemporal_store(p, reinterpret_cast<u32x2*>(out) + idx);
+}
+
+// ---- the 16-byte result stores of the find family (fp32 output, compiled row shapes) ----------------------------------------------
+// One wave step of find_span writes 4R consecutive result rows.  RowStore is those rows as a store target, and the ONE place that says how
+// a 16-byte element group of a result row leaves under the call's policy: CACHED, a plain store (the line stays in the XCD's L2 for whoever
+// reads the rows next), or streaming, a non-temporal global store.  Write-through forms of the streaming store were measured and lost
+// (profiles/find_write_through.md): `sc1` and `sc0 sc1` take 1.5 us off a launch's floor, as the dirty lines they do not leave behind
+// predict, and add 4.2 us per 256K keys to its slope; `sc1 nt` is `nt`; write-through for the batch's tail alone gains nothing either.
+template <bool CACHED>
+struct RowStore {
+    f32x4* first;   // group 0 of the step's first row
+    // first_group: the index in `out` of the step's first element group
+    __device__ __forceinline__ RowStore(f32x4* __restrict__ out, uint64_t first_group) : first(out + first_group) {}
+    // group g of the step (row-in-step * dim4 + group-in-row)
+    __device__ __forceinline__ void operator()(uint32_t g, const f32x4 v) const {
+        if constexpr (CACHED) first[g] = v;
+        else __builtin_nontemporal_store(v, first + g);
+    }
+};
+
 // ---- bf16 ROWS (SPEC.md §3 "Row storage type"): a table whose value plane holds bf16 ----------------------------------------------
 // The element group a lane owns — 4 elements — is 8 bytes there: group g of slot s sits at index s * dim4 + g of a u32x2 array, the SAME index
 // the fp32 kernels use on their float4 array.  Widening is exact: the 16 stored bits become the upper half of the fp32 word.
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u32x2 bf16x4_of(float a, float b, float c, float d);   // (below: the rounding every bf16 value of this library goes through)
 __device__ __forceinline__ f32x4 widen_bf16x4(const u32x2 p) {
     f32x4 v;
     v.x = __builtin_bit_cast(float, p.x << 16); v.y = __builtin_bit_cast(float, (p.x >> 16) << 16);
@@ -167,8 +211,6 @@ __device__ __forceinline__ f32x4 widen_bf16x4(const u32x2 p) {
 // A slot's row is dim two's-complement codes followed by a 16-byte tail (the scale, then twelve zero bytes): dim4 + 4 words of 32 bits.  The element
 // group a lane owns — 4 elements — is ONE word there: group g of slot s is word s * (dim4 + 4) + g, the row's scale is word s * (dim4 + 4) + dim4 (the
 // same address in every lane of the tile, asked for next to the groups, never behind them).  All of it in 64 bits.
-// The row storage type of a lookup instance: kRowsF32 / kRowsBF16 are what `false` / `true` of the earlier bf16-rows flag convert to.
-constexpr int kRowsF32 = 0, kRowsBF16 = 1, kRowsI8 = 2;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // one 16-byte group of a packed row
 __device__ __forceinline__ uint64_t i8_row_word(int64_t slot, uint32_t dim4) { return (uint64_t)slot * ((uint64_t)dim4 + 4u); }
 // D of the spec: y = (float)q * scale, one multiply per element (the library is built with -ffp-contract=off)
@@ -191,6 +233,66 @@ __device__ __forceinline__ uint32_t quant_i8x4(const f32x4 x, float scale) {
     return w;
 }
 
+// ---- the row storage type of a lookup instance (SPEC.md §3 "Row storage type") -------------------------------------------------------
+// A kernel's `bool BROWS` converts to kRowsF32 (false) / kRowsBF16 (true).  RowType<ROWS> is everything a lookup or the export knows about how a
+// plane of that type holds a row; the geometry is the same for all three: a 16-lane tile per row, lane tl owns element group c * 16 + tl.
+constexpr int kRowsF32 = 0, kRowsBF16 = 1, kRowsI8 = 2;
+template <int ROWS>
+struct RowType {
+    static constexpr bool kI8 = ROWS == kRowsI8;
+    static_assert(ROWS == kRowsF32 || ROWS == kRowsBF16 || kI8, "a row storage type");
+    // the element group a lane loads — 4 elements: 16, 8 or 4 bytes
+    using Group = std::conditional_t<ROWS == kRowsF32, f32x4, std::conditional_t<ROWS == kRowsBF16, u32x2, uint32_t>>;
+    static __device__ __forceinline__ const Group* plane(const void* values) { return reinterpret_cast<const Group*>(values); }
+    // group g of slot s is plane[first(s, dim4) + g]
+    static __device__ __forceinline__ uint64_t first(int64_t slot, uint32_t dim4) {
+        if constexpr (kI8) return i8_row_word(slot, dim4); else return (uint64_t)slot * dim4;
+    }
+    // STREAM: the streaming-rows policy of the find, a non-temporal load
+    template <bool STREAM>
+    static __device__ __forceinline__ Group load(const Group* p) {
+        if constexpr (STREAM) return __builtin_nontemporal_load(p); else return *p;
+    }
+    // what a row needs loaded beside its groups: the scale word of an int8 row, by every lane of the tile (one address per tile) and issued WITH the
+    // row's groups, never behind them; nothing (0) for the others.  HIT: the caller knows that the key was found (the load is unconditional), otherwise a
+    // missing key (slot < 0) loads nothing
+    template <bool STREAM, bool HIT>
+    static __device__ __forceinline__ uint32_t load_tail(const Group* plane, int64_t slot, uint32_t dim4) {
+        if constexpr (kI8) return (HIT || slot >= 0) ? load<STREAM>(plane + first(slot, dim4) + dim4) : 0u; else return 0u;
+    }
+    // What a missing key yields is the table's default row, def4.  An fp32 or bf16 plane can hold it as a Group (a bf16 table's default is a bf16 value:
+    // packing it loses nothing), selected where the row would have been loaded; no scale makes int8 codes of it, so there the Group is 0 and value() puts
+    // def4 in its place (`hit` and `def4` matter to an int8 row only).
+    static __device__ __forceinline__ Group missing(const f32x4 def4) {
+        if constexpr (ROWS == kRowsF32) return def4;
+        else if constexpr (ROWS == kRowsBF16) return bf16x4_of(def4.x, def4.y, def4.z, def4.w);
+        else return 0u;
+    }
+    // a group as fp32: as it is, widened (exact), or dequantized under the row's scale word
+    static __device__ __forceinline__ f32x4 value(const Group g, uint32_t tail, bool hit, const f32x4 def4) {
+        if constexpr (ROWS == kRowsF32) return g;
+        else if constexpr (ROWS == kRowsBF16) return widen_bf16x4(g);
+        else return hit ? dequant_i8x4(g, __builtin_bit_cast(float, tail)) : def4;
+    }
+    // the store of a group as element group idx of a bf16 output: a bf16 row's 8 bytes leave as they came (no second rounding), the others are rounded
+    // here, once (store_bf16x4); CACHED as there
+    template <bool CACHED>
+    static __device__ __forceinline__ void store_bf16(void* __restrict__ out, uint64_t idx, const Group g, uint32_t tail, bool hit, const f32x4 def4) {
+        if constexpr (ROWS != kRowsBF16) store_bf16x4<CACHED>(out, idx, value(g, tail, hit, def4));
+        else if constexpr (CACHED) reinterpret_cast<u32x2*>(out)[idx] = g;
+        else __builtin_nontemporal_store(g, reinterpret_cast<u32x2*>(out) + idx);
+    }
+    // ... of an fp32 or (BF16_OUT) bf16 output
+    template <bool BF16_OUT, bool CACHED>
+    static __device__ __forceinline__ void store(void* __restrict__ out, uint64_t idx, const Group g, uint32_t tail, bool hit, const f32x4 def4) {
+        if constexpr (BF16_OUT) store_bf16<CACHED>(out, idx, g, tail, hit, def4);
+        else {
+            const f32x4 v = value(g, tail, hit, def4);
+            RowStore<CACHED>(reinterpret_cast<f32x4*>(out), idx)(0, v);
+        }
+    }
+};
+
 // ---- pooled lookups (meepo_find.hip: one table and the uniform group; meepo_mixed.hip: the mixed group) ------------------------------
 // a bag of this many keys or more is served by the wave's four tiles together (pooled_bags)
 constexpr uint32_t kPoolLong = 16;
@@ -198,12 +300,14 @@ constexpr uint32_t kPoolLong = 16;
 // probe + row load of up to U keys per tile (the find_kernel pattern); row[u] is only defined where inb[u].
 // located (nullable) receives tag | slot per position: tag = member << kGroupSlotBits for a group (EMPTY when absent), or the table's
 // handle tag (handle_tag_of) for one table with TAGGED (-1 when absent: the format of mee_find_located)
-// BROWS: `values` is a bf16-row plane (u32x2 groups): the row is widened at its load, everything behind the load is the fp32 code
-template <int DIM4, int U, int C, bool TAGGED = false, bool BROWS = false>
+// ROWS: the storage type of `values` (RowType): a bf16 row is widened at its load, everything behind the load is the fp32 code
+template <int DIM4, int U, int C, bool TAGGED = false, int ROWS = kRowsF32>
 __device__ __forceinline__ void pooled_fetch(const int64_t* __restrict__ tkeys, const float4* __restrict__ values, uint64_t nb,
                                              uint32_t dim4, const int64_t (&key)[U], const uint64_t (&pos)[U],
                                              const bool (&inb)[U], int tile, int tl, float4 def4, float4 (&row)[U][C],
                                              uint8_t* __restrict__ found, int64_t* __restrict__ located = nullptr, uint64_t tag = 0) {
+    static_assert(ROWS != kRowsI8, "no int8 pooled lookup: it faulted on the GPU and the cause is open (an int8 row also needs its scale word loaded and its default kept in fp32)");
+    using RT = RowType<ROWS>;
     int64_t slot[U], kb[U];
     uint64_t bk[U];
     bool act[U];
@@ -220,11 +324,11 @@ __device__ __forceinline__ void pooled_fetch(const int64_t* __restrict__ tkeys, 
 #pragma unroll
         for (int c = 0; c < C; ++c)
             if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
-                if constexpr (BROWS) {   // (the table's default value is a bf16 value: packing it loses nothing)
-                    const u32x2 def2 = bf16x4_of(def4.x, def4.y, def4.z, def4.w);
-                    const f32x4 v = widen_bf16x4(slot[u] >= 0 ? reinterpret_cast<const u32x2*>(values)[(uint64_t)slot[u] * dim4 + c * 16 + tl] : def2);
+                if constexpr (ROWS == kRowsF32) row[u][c] = slot[u] >= 0 ? values[(uint64_t)slot[u] * dim4 + c * 16 + tl] : def4;   // (a float4 plane as it is)
+                else {
+                    const f32x4 v = RT::value(slot[u] >= 0 ? RT::plane(values)[RT::first(slot[u], dim4) + c * 16 + tl] : RT::missing(f32x4{def4.x, def4.y, def4.z, def4.w}), 0u, true, f32x4{});
                     row[u][c] = make_float4(v.x, v.y, v.z, v.w);
-                } else row[u][c] = slot[u] >= 0 ? values[(uint64_t)slot[u] * dim4 + c * 16 + tl] : def4;
+                }
             }
         if (found && inb[u] && tl == 0) found[pos[u]] = slot[u] >= 0;
         // the located row: lets the backward skip its own probe pass
@@ -247,7 +351,7 @@ struct TierArgs {
 // well-placed pair) pays that ballot and runs pooled_fetch's row loads.  Otherwise the cold index is probed for the positions the hot probe
 // missed — by all 64 lanes in convergent control flow, tiles without a miss pass act = false — and each row is loaded from the plane that
 // holds it (one load per row: the address is selected, not the data).  Counting (nullable counters, wave-uniform branches): one atomicAdd
-// per found position by the tile's first lane, as find_kernel (NT & 16) and find_missing_kernel (FLAGS & 2) do it.
+// per found position by the tile's first lane, as find_kernel (kFindCountHits, meepo_find.hip) and find_missing_kernel (FLAGS & 2) do it.
 template <int DIM4, int U, int C>
 __device__ __forceinline__ void pooled_fetch_tiered(const int64_t* __restrict__ tkeys, const float4* __restrict__ values, uint64_t nb,
                                                     const TierArgs& cold, uint32_t dim4, const int64_t (&key)[U], const uint64_t (&pos)[U],
@@ -308,63 +412,6 @@ __device__ __forceinline__ void pooled_fetch_tiered(const int64_t* __restrict__ 
             if (slot[u] >= 0 && tl == 0) atomicAdd(&cold.hot_hits[slot[u]], 1u);
     }
 }
-
-// ---- bf16 output of the lookups (SPEC.md §3 "Output type") ------------------------------------------------------------------
-// A lane that holds a float4 of a row stores it as 4 bf16 = 8 bytes; a row of dim bf16 is dim4 such 8-byte groups, so group g of
-// output row i sits at index i * dim4 + g of a u32x2 array — the SAME index the fp32 kernels use on their f32x4 array.
-// two fp32 -> two bfloat16 in one word, round to nearest even: plain casts, which gfx950 does with its packed convert (v_cvt_pk_bf16_f32).  It agrees
-// with the integer rule of the spec on every finite value, denormals included (HIP kernels run with fp32 denormals on), sends a finite value beyond
-// the largest bf16 to inf and a NaN to a NaN: tests/test_bf16_out.py checks exactly these on the device.  (The integer rule written out costs ~30
-// VALU instructions per float4 in the wave's dependent tail — +0.4 us on a latency-bound dim-16 lookup — and a __builtin_convertvector of float2
-// pairs made two pooled instances spill 32 B: profiles/bf16_out.md, profiles/bf16_out_resource_usage.txt.)
-__device__ __forceinline__ uint32_t bf16x2_of(float a, float b) {
-    return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)a) | ((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)b) << 16);
-}
-__device__ __forceinline__ u32x2 bf16x4_of(float a, float b, float c, float d) {
-    u32x2 p;
-    p.x = bf16x2_of(a, b);
-    p.y = bf16x2_of(c, d);
-    return p;
-}
-// the store of one such group; CACHED = false: a streaming (non-temporal) store, as the fp32 kernels use for outputs nothing re-reads from cache
-template <bool CACHED, class V4>
-__device__ __forceinline__ void store_bf16x4(void* out, uint64_t idx, const V4& v) {
-    const u32x2 p = bf16x4_of(v.x, v.y, v.z, v.w);
-    if constexpr (CACHED) reinterpret_cast<u32x2*>(out)[idx] = p;
-    else __builtin_nontemporal_store(p, reinterpret_cast<u32x2*>(out) + idx);
-}
-
-// the store of one element group of a bf16 ROW (u32x2 as loaded from a bf16-row plane): verbatim into a bf16 output (BF16_OUT: no second rounding), widened
-// exactly into an fp32 one; CACHED as store_bf16x4
-template <bool BF16_OUT, bool CACHED>
-__device__ __forceinline__ void store_brow_as(void* __restrict__ out, uint64_t idx, const u32x2 p) {
-    if constexpr (BF16_OUT) {
-        if constexpr (CACHED) reinterpret_cast<u32x2*>(out)[idx] = p;
-        else __builtin_nontemporal_store(p, reinterpret_cast<u32x2*>(out) + idx);
-    } else {
-        const f32x4 v = widen_bf16x4(p);
-        if constexpr (CACHED) reinterpret_cast<f32x4*>(out)[idx] = v;
-        else __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out) + idx);
-    }
-}
-
-// ---- the 16-byte result stores of the find family (fp32 output, compiled row shapes) ----------------------------------------------
-// One wave step of find_span writes 4R consecutive result rows.  RowStore is those rows as a store target, and the ONE place that says how
-// a 16-byte element group of a result row leaves under the call's policy: CACHED, a plain store (the line stays in the XCD's L2 for whoever
-// reads the rows next), or streaming, a non-temporal global store.  Write-through forms of the streaming store were measured and lost
-// (profiles/find_write_through.md): `sc1` and `sc0 sc1` take 1.5 us off a launch's floor, as the dirty lines they do not leave behind
-// predict, and add 4.2 us per 256K keys to its slope; `sc1 nt` is `nt`; write-through for the batch's tail alone gains nothing either.
-template <bool CACHED>
-struct RowStore {
-    f32x4* first;   // group 0 of the step's first row
-    // first_group: the index in `out` of the step's first element group
-    __device__ __forceinline__ RowStore(f32x4* __restrict__ out, uint64_t first_group) : first(out + first_group) {}
-    // group g of the step (row-in-step * dim4 + group-in-row)
-    __device__ __forceinline__ void operator()(uint32_t g, const f32x4 v) const {
-        if constexpr (CACHED) first[g] = v;
-        else __builtin_nontemporal_store(v, first + g);
-    }
-};
 
 // ---- the bag walk of the pooled lookups and of their backward ------------------------------------------------------------------
 // Geometry: a wave step serves BPW consecutive bags.  BPW = 4: tile t takes bag `bag0 + t`; a bag of fewer than kPoolLong keys is walked by its
@@ -473,7 +520,7 @@ __device__ __forceinline__ void pooled_bags(uint64_t bag0, uint32_t nvalid, uint
     float4 row[U][C];
     auto fetch = [&](const int64_t (&kv)[U], const uint64_t (&pos)[U], const bool (&inb)[U]) {
         if constexpr (TIERED) pooled_fetch_tiered<DIM4, U, C>(t.tkeys, t.values, t.nb, tier, dim4, kv, pos, inb, tile, tl, t.def4, row, found);
-        else pooled_fetch<DIM4, U, C, TAGGED, BROWS>(t.tkeys, t.values, t.nb, dim4, kv, pos, inb, tile, tl, t.def4, row, found, located, t.tag);
+        else pooled_fetch<DIM4, U, C, TAGGED, BROWS ? kRowsBF16 : kRowsF32>(t.tkeys, t.values, t.nb, dim4, kv, pos, inb, tile, tl, t.def4, row, found, located, t.tag);
     };
     // ---- short bags: one tile per bag ----
     if constexpr (BPW == 4) {

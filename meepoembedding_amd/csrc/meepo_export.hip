@@ -154,9 +154,9 @@ __global__ __launch_bounds__(256) void rehash_kernel(const int64_t* __restrict__
 // A wave owns a chunk of 1024 consecutive slots.  Pass A: 16 coalesced key loads, ballot + popcount -> occupied
 // count, ONE atomic reserves the chunk's output range.  Pass B: per 64-slot group, ranks from the ballot mask;
 // keys are written by their own lane, rows are copied four at a time (one per 16-lane tile).
-// BROWS: `values` is a bf16-row plane (SPEC.md §3 "Row storage type"; no state planes): each 8-byte group is widened on its way into the fp32 values_out —
-// source and destination are different buffers, so nothing is expanded in place.  As a row storage type (ROWS): false = kRowsF32, true = kRowsBF16;
-// kRowsI8: an int8-row plane (dim4 + 4 words per slot, no state planes) — the tile loads the row's scale with its words and dequantizes on the way out.
+// ROWS: the storage type of `values` (RowType, meepo_device.h).  A bf16-row or int8-row plane has no state planes; its groups are widened or dequantized
+// (the tile loads the row's scale with its words) on their way into the fp32 values_out — source and destination are different buffers, so nothing is
+// expanded in place.
 constexpr int kExportGroups = 16;
 
 template <int ROWS>
@@ -201,24 +201,15 @@ __global__ __launch_bounds__(256) void export_kernel(const int64_t* __restrict__
                 const uint64_t pos = pos0 + done + tile;
                 if (p >= 0 && pos < cap) {
                     const uint64_t src = (c0 + (uint64_t)j * 64 + p) * dim4, dst = pos * dim4;
-                    [[maybe_unused]] const uint32_t* __restrict__ qrow = nullptr;   // int8 rows: the row's words, and its scale loaded with them
-                    [[maybe_unused]] float scale = 0.f;
-                    if constexpr (ROWS == kRowsI8) {
-                        qrow = reinterpret_cast<const uint32_t*>(values) + i8_row_word((int64_t)(c0 + (uint64_t)j * 64 + p), dim4);
-                        scale = __builtin_bit_cast(float, qrow[dim4]);
-                    }
+                    using RT = RowType<ROWS>;
+                    const uint32_t tail = RT::template load_tail<false, true>(RT::plane(values), (int64_t)(c0 + (uint64_t)j * 64 + p), dim4);
                     for (uint32_t c = tl; c < dim4; c += 16) {
-                        if constexpr (ROWS == kRowsI8) {
-                            if (values_out) {
-                                const f32x4 v = dequant_i8x4(qrow[c], scale);
-                                values_out[dst + c] = make_float4(v.x, v.y, v.z, v.w);
-                            }
-                        } else if constexpr (ROWS == kRowsBF16) {
-                            if (values_out) {
-                                const f32x4 v = widen_bf16x4(reinterpret_cast<const u32x2*>(values)[src + c]);
-                                values_out[dst + c] = make_float4(v.x, v.y, v.z, v.w);
-                            }
-                        } else if (values_out) values_out[dst + c] = values[src + c];
+                        if constexpr (ROWS == kRowsF32) {   // (a float4 plane as it is)
+                            if (values_out) values_out[dst + c] = values[src + c];
+                        } else if (values_out) {
+                            const f32x4 v = RT::value(RT::plane(values)[RT::first((int64_t)(c0 + (uint64_t)j * 64 + p), dim4) + c], tail, true, f32x4{});
+                            values_out[dst + c] = make_float4(v.x, v.y, v.z, v.w);
+                        }
                         if (s1_out) s1_out[dst + c] = s1[src + c];
                         if (s2_out) s2_out[dst + c] = s2[src + c];
                     }

@@ -15,47 +15,50 @@ namespace mee {
 
 // ---- find (SPEC.md §3) — the headline kernel --------------------------------------------------------------
 // One tile per key, R keys in flight per tile: the R bucket lines are requested back to back, then the R rows.
-// DIM4 = dim/4 when it is a multiple of 16 (each lane moves DIM4/16 float4 per row), 0 = any dim at run time.
-// NT & 256: `out` is a bf16 array (SPEC.md §3 "Output type") — the lane's float4 leaves as 4 bf16 in one 8-byte store (store_bf16x4); nothing else differs.
-// BROWS: `values` is a bf16-row plane (SPEC.md §3 "Row storage type"; mee_find / _ex / _as only: NT holds policy bits and 256).  Same tiles, same index
-// arithmetic; the element group a lane loads is 8 bytes (u32x2) instead of 16, so a dim-64 row is one 128-byte line per tile instruction.  With bf16 out
-// the 8 bytes leave as they came (no second rounding); with fp32 out they are widened in registers.  The policy bits 1 (streaming row loads) and 4
-// (cached stores) act in the compiled shapes (DIM4 16 / 32); the run-time shape (DIM4 = 0) loads and stores cached whatever they say, as the fp32
-// run-time path does (bit 2, the bucket loads, acts in every shape).  The instances with BROWS = false are the code they were before the parameter existed.
-// ROWS is that parameter as a row storage type: kRowsF32 (false), kRowsBF16 (true) and kRowsI8 — `values` is an int8-row plane (meepo_device.h: dim4 + 4
-// words per slot).  Same tiles, same R keys in flight, same index arithmetic on the output; the element group a lane loads is ONE word, and every lane of
-// the tile loads the row's scale word with it (one address per tile, issued with the row loads, never behind them).  The lane dequantizes in registers
-// (dequant_i8x4) and stores a float4, or 8 bytes through the library's bf16 rounding (store_bf16x4) — what the fp32 twin's bf16-out find does with the same
-// values.  A missing key gets the fp32 default as it is.  Policy bits as in the bf16-row branch.
+// DIM4 = dim/4 when it is a multiple of 16 (each lane moves DIM4/16 element groups per row), 0 = any dim at run time.
+// ROWS: the storage type of `values` (RowType, meepo_device.h).  Every type has the same tiles, the same R keys in flight and the same index arithmetic on
+// the output; what a lane loads per element group (16, 8 or 4 bytes, an int8 row's scale word beside them), what a missing key reads and how a group leaves
+// as fp32 or bf16 is RowType's.  fp32 and bf16 rows share one gather written through it; the int8 gather is a block of its own in find_span (the same
+// steps spelled out: through the shared blocks its dim-64 instances measured slower).  A bf16-row or int8-row plane is served by the plain find only
+// (mee_find / _ex / _as: the hint bits and kFindBF16Out).
+//
+// NT: the policy bits of an instance.  The numbers are part of the kernels' names (find_kernel<16, 2, 64>), which profiles/ and tools/ key on.
+constexpr int kFindStreamRows = 1;      // row loads are non-temporal (a stream without reuse).  Compiled row shapes only: the run-time shape (DIM4 = 0) loads cached
+constexpr int kFindStreamBuckets = 2;   // the first bucket line of every key is loaded non-temporal; every shape
+constexpr int kFindCachedStores = 4;    // the result rows leave as plain stores (they stay in L2 / the Infinity Cache for whoever reads them next); without it
+                                        // as streaming stores (RowStore).  Compiled row shapes only: the run-time shape stores cached
+constexpr int kFindCountHits = 16;      // one atomicAdd to hits[slot] per found position: access statistics for the hot/cold policy (sampled calls)
+constexpr int kFindLocated = 64;        // mee_find_located: slots_out[i] = the slot handle of position i (-1 = absent), for the apply of the same step
+constexpr int kFindSkipPadding = 128;   // owner side of a padded sharded exchange: an EMPTY position is padding nobody reads: no row, found byte 1
+constexpr int kFindBF16Out = 256;       // `out` is a bf16 array (SPEC.md §3 "Output type"): an element group leaves as 4 bf16 in one 8-byte store
+// the three bits a caller's hint carries: the table's "find_nt" setting and the MEE_FIND_* flags of mee_find_ex / mee_find_as
+constexpr int kFindHintBits = kFindStreamRows | kFindStreamBuckets | kFindCachedStores;
 
-// the store of one element group of a bf16 ROW (store_brow_as, meepo_device.h) under find_span's NT bits
-template <int NT, bool CACHED>
-__device__ __forceinline__ void store_brow(f32x4* __restrict__ out, uint64_t idx, const u32x2 p) {
-    store_brow_as<(NT & 256) != 0, CACHED>(out, idx, p);
-}
-
-// the find of n positions by `n_waves` waves of which this is wave `wave` (each wave step takes 4R consecutive positions)
 // the store of one dequantized element group of an int8 ROW under find_span's NT bits: a float4, or 4 bf16 rounded here, once
 // (compiled shapes: group g of the wave step `st`, which is index `first + g` of `out`)
 template <int NT, bool CACHED>
 __device__ __forceinline__ void store_qrow(f32x4* __restrict__ out, uint64_t first, const RowStore<CACHED>& st, uint32_t g, const f32x4 v) {
-    if constexpr ((NT & 256) != 0) store_bf16x4<CACHED>(out, first + g, v);
+    if constexpr ((NT & kFindBF16Out) != 0) store_bf16x4<CACHED>(out, first + g, v);
     else st(g, v);
 }
 
+// the find of n positions by `n_waves` waves of which this is wave `wave` (each wave step takes 4R consecutive positions)
 template <int DIM4, int R, int NT, int ROWS = kRowsF32>
 __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, const f32x4* __restrict__ values, uint64_t nb,
                                           const int64_t* __restrict__ keys, uint64_t n, f32x4* __restrict__ out,
                                           uint8_t* __restrict__ found, float defv, uint32_t dim4_rt, uint32_t* hits,
                                           int64_t* __restrict__ slots_out, uint64_t wave, uint64_t n_waves, int64_t handle_tag = 0) {
+    static_assert(ROWS == kRowsF32 || (NT & ~(kFindHintBits | kFindBF16Out)) == 0, "bf16 rows and int8 rows: the plain find only");
+    using RT = RowType<ROWS>;
+    constexpr bool STREAM_ROWS = (NT & kFindStreamRows) != 0, CACHED = (NT & kFindCachedStores) != 0, BF16_OUT = (NT & kFindBF16Out) != 0;
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint32_t dim4 = DIM4 ? DIM4 : dim4_rt;
     constexpr int KPW = 4 * R;
     const f32x4 def4 = {defv, defv, defv, defv};
-
+    const typename RT::Group* __restrict__ plane = RT::plane(values);
 
     for (uint64_t base = wave * KPW; base < n; base += n_waves * KPW) {
-        const RowStore<(NT & 4) != 0> st(out, base * DIM4);   // the step's fp32 result rows (compiled shapes; bf16 out and the run-time shape store for themselves)
+        const RowStore<CACHED> st(out, base * DIM4);   // the step's fp32 result rows (compiled shapes; bf16 out and the run-time shape store for themselves)
         int64_t key[R];
         int64_t slot[R];
         uint64_t b[R];
@@ -70,12 +73,8 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
             inb[r] = i < n;
             key[r] = __shfl(kmine, r * 4 + tile);
             act[r] = inb[r] && !reserved_key(key[r]);
-            if constexpr ((NT & 8) != 0) {  // second-tier pass: only positions an earlier find left as missing
-                inb[r] = act[r] = act[r] && found[i] == 0;
-            }
-            if constexpr ((NT & 128) != 0) {  // owner side of a padded sharded exchange: EMPTY positions are padding nobody reads — no row; their
-                // found byte says "served" so that a second-tier pass over the same buffers (mee_find_missing / mee_find_or_insert_missing on the
-                // cold table of a tiered shard) leaves them alone instead of reading a byte nobody wrote
+            if constexpr ((NT & kFindSkipPadding) != 0) {  // the found byte of padding says "served" so that a second-tier pass over the same buffers (mee_find_missing
+                // / mee_find_or_insert_missing on the cold table of a tiered shard) leaves it alone instead of reading a byte nobody wrote
                 if (inb[r] && !act[r] && tl == 0 && found) found[i] = 1;
                 inb[r] = act[r];
             }
@@ -83,17 +82,17 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             b[r] = bucket_of(key[r], nb);
-            kb[r] = act[r] ? ((NT & 2) ? __builtin_nontemporal_load(&tkeys[b[r] * kW + tl]) : tkeys[b[r] * kW + tl]) : kEmpty;
+            kb[r] = act[r] ? ((NT & kFindStreamBuckets) ? __builtin_nontemporal_load(&tkeys[b[r] * kW + tl]) : tkeys[b[r] * kW + tl]) : kEmpty;
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) slot[r] = tile_probe(tkeys, nb, key[r], act[r], b[r], kb[r], tile, tl);
-        if constexpr ((NT & 16) != 0) {  // access statistics for the hot/cold policy (sampled calls only)
+        if constexpr ((NT & kFindCountHits) != 0) {
 #pragma unroll
             for (int r = 0; r < R; ++r)
                 if (slot[r] >= 0 && tl == 0) atomicAdd(&hits[slot[r]], 1u);
         }
         if constexpr (ROWS == kRowsI8) {
-            static_assert((NT & ~(7 | 256)) == 0, "int8 rows: the plain find only");
+            // The parent text of the int8 gather: through the shared blocks below the dim-64 instances measured 6-11 % slower (profiles/find_row_types.md)
             const uint32_t* __restrict__ qrows = reinterpret_cast<const uint32_t*>(values);
             if constexpr (DIM4 != 0) {
                 constexpr int C = DIM4 / 16;
@@ -106,8 +105,8 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
                     for (int r = 0; r < R; ++r) {
                         const uint32_t* __restrict__ q = qrows + i8_row_word(slot[r], DIM4);
 #pragma unroll
-                        for (int c = 0; c < C; ++c) row[r][c] = (NT & 1) ? __builtin_nontemporal_load(&q[c * 16 + tl]) : q[c * 16 + tl];
-                        sc[r] = (NT & 1) ? __builtin_nontemporal_load(&q[DIM4]) : q[DIM4];
+                        for (int c = 0; c < C; ++c) row[r][c] = STREAM_ROWS ? __builtin_nontemporal_load(&q[c * 16 + tl]) : q[c * 16 + tl];
+                        sc[r] = STREAM_ROWS ? __builtin_nontemporal_load(&q[DIM4]) : q[DIM4];
                     }
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
@@ -119,8 +118,8 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
                     for (int r = 0; r < R; ++r) {
                         const uint32_t* __restrict__ q = qrows + i8_row_word(slot[r] >= 0 ? slot[r] : 0, DIM4);
 #pragma unroll
-                        for (int c = 0; c < C; ++c) row[r][c] = slot[r] >= 0 ? ((NT & 1) ? __builtin_nontemporal_load(&q[c * 16 + tl]) : q[c * 16 + tl]) : 0u;
-                        sc[r] = slot[r] >= 0 ? ((NT & 1) ? __builtin_nontemporal_load(&q[DIM4]) : q[DIM4]) : 0u;
+                        for (int c = 0; c < C; ++c) row[r][c] = slot[r] >= 0 ? (STREAM_ROWS ? __builtin_nontemporal_load(&q[c * 16 + tl]) : q[c * 16 + tl]) : 0u;
+                        sc[r] = slot[r] >= 0 ? (STREAM_ROWS ? __builtin_nontemporal_load(&q[DIM4]) : q[DIM4]) : 0u;
                     }
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
@@ -140,59 +139,15 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
                         const float scale = slot[r] >= 0 ? __builtin_bit_cast(float, q[dim4]) : 0.f;
                         for (uint32_t c = tl; c < dim4; c += 16) {
                             const f32x4 v = slot[r] >= 0 ? dequant_i8x4(q[c], scale) : def4;
-                            if constexpr ((NT & 256) != 0) store_bf16x4<true>(out, i * dim4 + c, v); else out[i * dim4 + c] = v;
+                            if constexpr (BF16_OUT) store_bf16x4<true>(out, i * dim4 + c, v); else out[i * dim4 + c] = v;
                         }
                     }
-                }
-            }
-        } else if constexpr (ROWS == kRowsBF16) {
-            static_assert((NT & ~(7 | 256)) == 0, "bf16 rows: the plain find only");
-            const u32x2* __restrict__ brows = reinterpret_cast<const u32x2*>(values);
-            const u32x2 def2 = bf16x4_of(defv, defv, defv, defv);   // (the table's default value is a bf16 value: packing it loses nothing)
-            if constexpr (DIM4 != 0) {
-                constexpr int C = DIM4 / 16;
-                u32x2 row[R][C];
-                bool all_hit = true;   // the wave-uniform common case, as below
-#pragma unroll
-                for (int r = 0; r < R; ++r) all_hit = all_hit && inb[r] && slot[r] >= 0;
-                if (__all(all_hit)) {
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-#pragma unroll
-                        for (int c = 0; c < C; ++c)
-                            row[r][c] = (NT & 1) ? __builtin_nontemporal_load(&brows[(uint64_t)slot[r] * DIM4 + c * 16 + tl]) : brows[(uint64_t)slot[r] * DIM4 + c * 16 + tl];
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        const uint64_t i = base + r * 4 + tile;
-#pragma unroll
-                        for (int c = 0; c < C; ++c) store_brow<NT, (NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, row[r][c]);
-                    }
-                } else {
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-#pragma unroll
-                        for (int c = 0; c < C; ++c)
-                            row[r][c] = slot[r] >= 0 ? ((NT & 1) ? __builtin_nontemporal_load(&brows[(uint64_t)slot[r] * DIM4 + c * 16 + tl]) : brows[(uint64_t)slot[r] * DIM4 + c * 16 + tl]) : def2;
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        const uint64_t i = base + r * 4 + tile;
-                        if (inb[r]) {
-#pragma unroll
-                            for (int c = 0; c < C; ++c) store_brow<NT, (NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, row[r][c]);
-                        }
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const uint64_t i = base + r * 4 + tile;
-                    if (inb[r])
-                        for (uint32_t c = tl; c < dim4; c += 16) store_brow<NT, true>(out, i * dim4 + c, slot[r] >= 0 ? brows[(uint64_t)slot[r] * dim4 + c] : def2);
                 }
             }
         } else if constexpr (DIM4 != 0) {
             constexpr int C = DIM4 / 16;
-            f32x4 row[R][C];
+            typename RT::Group row[R][C];
+            uint32_t tail[R];
             // Common case, decided per wave: every position of the wave step is inside the batch and was found.  Then the R row loads
             // and the R stores are straight-line code and leave back to back; with a per-lane condition around each load the compiler
             // waited for round r's row before it requested round r + 1's (seen in the ISA of the located variant: +8 us per 256K keys).
@@ -201,38 +156,41 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
             for (int r = 0; r < R; ++r) all_hit = all_hit && inb[r] && slot[r] >= 0;
             if (__all(all_hit)) {
 #pragma unroll
-                for (int r = 0; r < R; ++r)
+                for (int r = 0; r < R; ++r) {
 #pragma unroll
-                    for (int c = 0; c < C; ++c)
-                        row[r][c] = (NT & 1) ? __builtin_nontemporal_load(&values[(uint64_t)slot[r] * DIM4 + c * 16 + tl]) : values[(uint64_t)slot[r] * DIM4 + c * 16 + tl];
+                    for (int c = 0; c < C; ++c) row[r][c] = RT::template load<STREAM_ROWS>(&plane[RT::first(slot[r], DIM4) + c * 16 + tl]);
+                    tail[r] = RT::template load_tail<STREAM_ROWS, true>(plane, slot[r], DIM4);
+                }
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     const uint64_t i = base + r * 4 + tile;
 #pragma unroll
                     for (int c = 0; c < C; ++c) {
-                        if constexpr ((NT & 256) != 0) store_bf16x4<(NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, row[r][c]);
-                        else st((r * 4 + tile) * DIM4 + c * 16 + tl, row[r][c]);
+                        if constexpr (BF16_OUT) RT::template store_bf16<CACHED>(out, i * DIM4 + c * 16 + tl, row[r][c], tail[r], true, def4);
+                        else st((r * 4 + tile) * DIM4 + c * 16 + tl, RT::value(row[r][c], tail[r], true, def4));
                     }
                 }
                 // An empty statement that keeps this block's tail its own.  The compiler merged the step's last store with the last store of the per-lane
                 // path below, and the merged block waits with vmcnt(0): for the row it stores, and with it for every store of the step issued before it.
                 // Apart, the stores leave behind a vmcnt(k) ladder, each as its own row arrives: 32.1 -> 31.2 us per 256K-key launch into rotating buffers
-                // (profiles/find_write_through.md).  Streaming fp32 stores only: the cached and the bf16-out instances are the code they were.
-                if constexpr ((NT & (4 | 256)) == 0) asm volatile("; find_span: end of the all-hit stores");
+                // (profiles/find_write_through.md).  Streaming fp32 stores only: the cached and the bf16-out instances go without.
+                if constexpr (!CACHED && !BF16_OUT) asm volatile("; find_span: end of the all-hit stores");
             } else {
 #pragma unroll
-                for (int r = 0; r < R; ++r)
+                for (int r = 0; r < R; ++r) {
 #pragma unroll
                     for (int c = 0; c < C; ++c)
-                        row[r][c] = slot[r] >= 0 ? ((NT & 1) ? __builtin_nontemporal_load(&values[(uint64_t)slot[r] * DIM4 + c * 16 + tl]) : values[(uint64_t)slot[r] * DIM4 + c * 16 + tl]) : def4;
+                        row[r][c] = slot[r] >= 0 ? RT::template load<STREAM_ROWS>(&plane[RT::first(slot[r], DIM4) + c * 16 + tl]) : RT::missing(def4);
+                    tail[r] = RT::template load_tail<STREAM_ROWS, false>(plane, slot[r], DIM4);
+                }
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     const uint64_t i = base + r * 4 + tile;
-                    if (inb[r] && (!(NT & 8) || slot[r] >= 0)) {
+                    if (inb[r]) {
 #pragma unroll
                         for (int c = 0; c < C; ++c) {
-                            if constexpr ((NT & 256) != 0) store_bf16x4<(NT & 4) != 0>(out, i * DIM4 + c * 16 + tl, row[r][c]);
-                            else st((r * 4 + tile) * DIM4 + c * 16 + tl, row[r][c]);
+                            if constexpr (BF16_OUT) RT::template store_bf16<CACHED>(out, i * DIM4 + c * 16 + tl, row[r][c], tail[r], slot[r] >= 0, def4);
+                            else st((r * 4 + tile) * DIM4 + c * 16 + tl, RT::value(row[r][c], tail[r], slot[r] >= 0, def4));
                         }
                     }
                 }
@@ -241,22 +199,22 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const uint64_t i = base + r * 4 + tile;
-                if (inb[r] && (!(NT & 8) || slot[r] >= 0))
-                    for (uint32_t c = tl; c < dim4; c += 16) {
-                        if constexpr ((NT & 256) != 0) store_bf16x4<true>(out, i * dim4 + c, slot[r] >= 0 ? values[(uint64_t)slot[r] * dim4 + c] : def4);
-                        else out[i * dim4 + c] = slot[r] >= 0 ? values[(uint64_t)slot[r] * dim4 + c] : def4;
-                    }
+                if (inb[r]) {
+                    const uint32_t tail = RT::template load_tail<false, false>(plane, slot[r], dim4);
+                    for (uint32_t c = tl; c < dim4; c += 16)
+                        RT::template store<BF16_OUT, true>(out, i * dim4 + c, slot[r] >= 0 ? plane[RT::first(slot[r], dim4) + c] : RT::missing(def4), tail, slot[r] >= 0, def4);
+                }
             }
         }
-        if constexpr ((NT & 64) != 0) {  // mee_find_located: the slot of every position (-1 = absent), for the apply of the same step
+        if constexpr ((NT & kFindLocated) != 0) {
             const int64_t mine = collect_slots(slot, lane);   // ONE coalesced store per wave step
             if (lane < KPW && base + lane < n) slots_out[base + lane] = mine >= 0 ? (mine | handle_tag) : mine;   // tag: the table's layout epoch (see handle_tag_of)
         }
-        if (found && !(NT & 32)) {  // NT&32: rows only (last pass of find_or_insert: found keeps meaning "present before")
+        if (found) {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const uint64_t i0 = base + r * 4;
-                if ((NT & (8 | 128)) == 0 && i0 + 4 <= n && (reinterpret_cast<uintptr_t>(found) & 3) == 0) {
+                if ((NT & kFindSkipPadding) == 0 && i0 + 4 <= n && (reinterpret_cast<uintptr_t>(found) & 3) == 0) {
                     // the four tiles' found bytes of this round leave as ONE aligned 4-byte store
                     const uint64_t m = __ballot(slot[r] >= 0);
                     const uint32_t w = (uint32_t)(m & 1) | ((uint32_t)((m >> 16) & 1) << 8) | ((uint32_t)((m >> 32) & 1) << 16) |
@@ -264,7 +222,7 @@ __device__ __forceinline__ void find_span(const int64_t* __restrict__ tkeys, con
                     if (lane == 0) *reinterpret_cast<uint32_t*>(found + i0) = w;
                 } else {
                     const uint64_t i = i0 + tile;
-                    if (inb[r] && tl == 0 && (!(NT & 8) || slot[r] >= 0)) found[i] = slot[r] >= 0;   // (NT & 128: inb excludes padding)
+                    if (inb[r] && tl == 0) found[i] = slot[r] >= 0;   // (kFindSkipPadding: inb excludes padding)
                 }
             }
         }
@@ -479,7 +437,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                         kv[u] = __shfl(kpre, tile * 16 + (int)((pos[u] - begin) & 15));
                         if constexpr (WEIGHTED) wv[u] = __shfl(wpre, tile * 16 + (int)((pos[u] - begin) & 15));
                     }
-                    pooled_fetch<DIM4, U, C, TAGGED, BROWS>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, (GROUPED && BROWS) ? nullptr : located,   // (a bf16-row group hands out no located rows: refused at the entry points)
+                    pooled_fetch<DIM4, U, C, TAGGED, BROWS ? kRowsBF16 : kRowsF32>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, (GROUPED && BROWS) ? nullptr : located,   // (a bf16-row group hands out no located rows: refused at the entry points)
                                                           member << kGroupSlotBits);
     #pragma unroll
                     for (int u = 0; u < U; ++u) {
@@ -535,7 +493,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                         pos[u] = i + (uint64_t)u * 4 + tile; inb[u] = pos[u] < eq; kv[u] = inb[u] ? keys[pos[u]] : kEmpty;
                         if constexpr (WEIGHTED) wv[u] = inb[u] ? weights[pos[u]] : 0.f;   // next to the key
                     }
-                    pooled_fetch<DIM4, U, C, TAGGED, BROWS>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, (GROUPED && BROWS) ? nullptr : located,   // (a bf16-row group hands out no located rows: refused at the entry points)
+                    pooled_fetch<DIM4, U, C, TAGGED, BROWS ? kRowsBF16 : kRowsF32>(tkeys, values, nb, dim4, kv, pos, inb, tile, tl, def4, row, found, (GROUPED && BROWS) ? nullptr : located,   // (a bf16-row group hands out no located rows: refused at the entry points)
                                                           member << kGroupSlotBits);
     #pragma unroll
                     for (int u = 0; u < U; ++u)
@@ -750,8 +708,9 @@ int find_plane(const mee_table* t, const float* plane, float miss_value, const i
     const unsigned fblock = t->find_block == 64 || t->find_block == 128 ? (unsigned)t->find_block : 256u;   // (launch bound of find_kernel: 256)
     const bool bf16 = path.out_dtype == MEE_DTYPE_BF16;   // d_out holds bf16 rows (Plain, Located and SkipPadding only: the entry points see to that)
     const uint64_t out_bytes = (uint64_t)n * t->dim * (bf16 ? 2 : 4);   // what the call really writes
-    const int nt = path.nt >= 0 ? path.nt : t->find_nt >= 0 ? (t->find_nt & 7)
-                 : (out_bytes <= kCachedOutputBytes && !outputs_rotate(t, d_out, out_bytes) ? 4 : 0);
+    const int nt = path.nt >= 0 ? path.nt : t->find_nt >= 0 ? (t->find_nt & kFindHintBits)
+                 : (out_bytes <= kCachedOutputBytes && !outputs_rotate(t, d_out, out_bytes) ? kFindCachedStores : 0);
+    const bool located_cached = t->find_nt >= 0 && (t->find_nt & kFindCachedStores);   // the located find streams its output unless "find_nt" asks otherwise (below)
     if (path.kind == FindPath::Missing || path.kind == FindPath::CountedMissing) {
         with_value<3, 1>(path.kind == FindPath::CountedMissing ? 3 : 1, [&](auto flags) {
             find_missing_kernel<flags><<<grid_for(n, 256, 8192), 256, 0, st>>>(t->keys, (const float4*)plane, t->nb, t->dim4, d_keys, n, (float4*)d_out, d_found, t->hits);
@@ -763,24 +722,23 @@ int find_plane(const mee_table* t, const float* plane, float miss_value, const i
         constexpr int R = RowShape<D4>::rows_per_tile;
         const unsigned grid = grid_for(n, (fblock / 64u) * 4u * (unsigned)R, t->find_grid_cap > 0 ? (unsigned)t->find_grid_cap : (1u << 22));
         with_flag(t->int8_rows, [&](auto i8) { with_flag(bf16, [&](auto b16) { with_value<0, 1, 2, 3, 4, 5, 6, 7>(nt, [&](auto ntc) {
-            find_kernel<D4, R, (decltype(b16)::value ? 256 : 0) | decltype(ntc)::value, decltype(i8)::value ? kRowsI8 : kRowsBF16><<<grid, fblock, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, nullptr, nullptr, 0);
+            find_kernel<D4, R, (decltype(b16)::value ? kFindBF16Out : 0) | decltype(ntc)::value, decltype(i8)::value ? kRowsI8 : kRowsBF16><<<grid, fblock, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, nullptr, nullptr, 0);
         }); }); });
     });
     else if (bf16) with_row_shape(t->dim4, [&](auto d4) {
-        // bf16 rows: the same kernel with NT | 256, instantiated for each row shape's default keys in flight only ("find_rounds" does not apply)
+        // bf16 out: the same kernel with kFindBF16Out, instantiated for each row shape's default keys in flight only ("find_rounds" does not apply)
         constexpr int D4 = d4;
         constexpr int R = RowShape<D4>::rows_per_tile;
         const unsigned grid = grid_for(n, (fblock / 64u) * 4u * (unsigned)R, t->find_grid_cap > 0 ? (unsigned)t->find_grid_cap : (1u << 22));
         auto find = [&](auto ntc, int64_t* slots_out, int64_t tag) {
-            find_kernel<D4, R, ntc><<<grid, fblock, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, nullptr, slots_out, tag);
+            find_kernel<D4, R, kFindBF16Out | ntc><<<grid, fblock, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, nullptr, slots_out, tag);
         };
         if (path.kind == FindPath::Located) {   // (the store policy of the fp32 located find)
-            const bool cached_out = t->find_nt >= 0 && (t->find_nt & 4);
-            with_value<256 + 68, 256 + 64>(cached_out ? 256 + 68 : 256 + 64, [&](auto ntc) { find(ntc, path.slots_out, handle_tag_of(t)); });
+            with_value<kFindLocated | kFindCachedStores, kFindLocated>(located_cached ? kFindLocated | kFindCachedStores : kFindLocated, [&](auto ntc) { find(ntc, path.slots_out, handle_tag_of(t)); });
         } else if (path.kind == FindPath::SkipPadding) {   // owner pass of a padded sharded exchange whose rows travel as bf16 (the fp32 one's store policy)
-            with_value<256 + 132, 256 + 128>(nt & 4 ? 256 + 132 : 256 + 128, [&](auto ntc) { find(ntc, nullptr, 0); });
+            with_value<kFindSkipPadding | kFindCachedStores, kFindSkipPadding>(kFindSkipPadding | (nt & kFindCachedStores), [&](auto ntc) { find(ntc, nullptr, 0); });
         } else {
-            with_value<256, 257, 258, 259, 260, 261, 262, 263>(256 | nt, [&](auto ntc) { find(ntc, nullptr, 0); });
+            with_value<0, 1, 2, 3, 4, 5, 6, 7>(nt, [&](auto ntc) { find(ntc, nullptr, 0); });
         }
     });
     else with_row_shape(t->dim4, [&](auto d4) {
@@ -794,14 +752,13 @@ int find_plane(const mee_table* t, const float* plane, float miss_value, const i
             find_kernel<D4, rr, ntc><<<grid_x, block, 0, st>>>(t->keys, (const f32x4*)plane, t->nb, d_keys, n, (f32x4*)d_out, d_found, miss_value, t->dim4, hits, slots_out, tag);
         };
         if (path.kind == FindPath::SkipPadding) {   // owner pass of a padded sharded exchange: EMPTY positions get neither a row nor a found byte (nobody reads them)
-            with_value<2, 1>(R >= 2 ? 2 : 1, [&](auto rr) { with_value<132, 128>(nt & 4 ? 132 : 128, [&](auto ntc) { find(rr, ntc, grid, 256); }); });
+            with_value<2, 1>(R >= 2 ? 2 : 1, [&](auto rr) { with_value<kFindSkipPadding | kFindCachedStores, kFindSkipPadding>(kFindSkipPadding | (nt & kFindCachedStores), [&](auto ntc) { find(rr, ntc, grid, 256); }); });
         } else if (path.kind == FindPath::Located) {   // located find: the plain kernel + one 8-byte store per key
             // cache policy of `out`: this is the forward of a TRAINING step — the apply that follows sweeps the Infinity Cache before the next
             // forward, so keeping the dense output cached buys nothing and streaming stores win (136.9 -> 132.5 us per find + Adagrad step)
-            const bool cached_out = t->find_nt >= 0 && (t->find_nt & 4);
-            with_value<2, 1>(R >= 2 ? 2 : 1, [&](auto rr) { with_value<68, 64>(cached_out ? 68 : 64, [&](auto ntc) { find(rr, ntc, grid, fblock, nullptr, path.slots_out, handle_tag_of(t)); }); });
+            with_value<2, 1>(R >= 2 ? 2 : 1, [&](auto rr) { with_value<kFindLocated | kFindCachedStores, kFindLocated>(located_cached ? kFindLocated | kFindCachedStores : kFindLocated, [&](auto ntc) { find(rr, ntc, grid, fblock, nullptr, path.slots_out, handle_tag_of(t)); }); });
         } else if (path.kind == FindPath::Counted) {   // sampled statistics pass: one key in flight per tile
-            find(std::integral_constant<int, 1>{}, std::integral_constant<int, 20>{}, grid_for(n, 16, 1u << 22), 256, t->hits);
+            find(std::integral_constant<int, 1>{}, std::integral_constant<int, kFindCountHits | kFindCachedStores>{}, grid_for(n, 16, 1u << 22), 256, t->hits);
         } else {
             auto plain = [&](auto rr) { with_value<0, 1, 2, 3, 4, 5, 6, 7>(nt, [&](auto ntc) {
                 if (path.kind == FindPath::Unordered)   // (any block order, at find_kernel's launch bound; the launch takes the parameters' exact types)
@@ -831,11 +788,10 @@ static int find_hinted(const mee_table* t, const int64_t* d_keys, size_t n, void
     if ((flags & MEE_FIND_STREAM_STORES) && (flags & MEE_FIND_CACHED_STORES))
         return fail(MEE_ERR_INVALID_ARG, "%s: MEE_FIND_STREAM_STORES and MEE_FIND_CACHED_STORES exclude each other", name);
     if (flags == MEE_FIND_DEFAULT) return find_plane(t, t->values, t->default_value, d_keys, n, (float*)d_out, d_found, stream, {FindPath::Plain, nullptr, -1, out_dtype});
-    // the kernel's policy bits: 1 = streaming row loads, 2 = streaming bucket loads, 4 = cached stores of the dense output
     const uint64_t out_bytes = (uint64_t)n * t->dim * (out_dtype == MEE_DTYPE_BF16 ? 2 : 4);
     const bool cached_out = (flags & MEE_FIND_CACHED_STORES) ||
                             (!(flags & MEE_FIND_STREAM_STORES) && out_bytes <= kCachedOutputBytes && !outputs_rotate(t, d_out, out_bytes));
-    const int nt = (flags & MEE_FIND_STREAM_ROWS ? 1 : 0) | (flags & MEE_FIND_STREAM_BUCKETS ? 2 : 0) | (cached_out ? 4 : 0);
+    const int nt = (flags & MEE_FIND_STREAM_ROWS ? kFindStreamRows : 0) | (flags & MEE_FIND_STREAM_BUCKETS ? kFindStreamBuckets : 0) | (cached_out ? kFindCachedStores : 0);
     return find_plane(t, t->values, t->default_value, d_keys, n, (float*)d_out, d_found, stream, {FindPath::Plain, nullptr, nt, out_dtype});
 }
 
@@ -907,7 +863,7 @@ int mee_find_many(const mee_table* t, const mee_find_request* reqs, uint32_t cou
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
     const bool cached_out = out_bytes <= kCachedOutputBytes;   // same policy as mee_find, on the total output of the launch
-    with_row_shape(t->dim4, [&](auto d4) { with_value<4, 0>(cached_out ? 4 : 0, [&](auto ntc) {
+    with_row_shape(t->dim4, [&](auto d4) { with_value<kFindCachedStores, 0>(cached_out ? kFindCachedStores : 0, [&](auto ntc) {
         find_many_kernel<d4, RowShape<d4>::rows_per_tile, ntc><<<(unsigned)blocks, 256, 0, st>>>(t->keys, (const f32x4*)t->values, t->nb, m, t->default_value, t->dim4);
     }); });
     MEE_HIP(hipGetLastError());
@@ -1149,17 +1105,16 @@ int mee::find_located_prepare(mee_table* t, const int64_t* d_keys, size_t n, voi
     const bool separate = t->prepare_debug & 1;   // the partition as launches of its own behind the find
     const PartPlan plan = bucket_plan(t->bk, n, st, separate ? kPartThreads : kFindPrepareThreads);
     const uint32_t part_blocks = separate ? 0u : plan.blocks;
-    const bool cached_out = t->find_nt >= 0 && (t->find_nt & 4);
+    const int nt = kFindLocated | (t->find_nt >= 0 ? t->find_nt & kFindCachedStores : 0);   // the located find's store policy (find_plane)
     with_row_shape(t->dim4, [&](auto d4) {
         constexpr int R = d4 == 16 ? kFindPrepareR : d4 == 32 ? 2 : 1;
         const unsigned find_cap = t->prepare_debug >> 8;
         const unsigned find_blocks = grid_for(n, (kFindPrepareThreads / 64) * 4u * (unsigned)R, find_cap ? find_cap : 1u << 22);
-        auto launch = [&](auto ntc) {
-            find_prepare_kernel<d4, R, ntc><<<part_blocks + find_blocks, kFindPrepareThreads, sizeof(PartHot) + plan.nbk * 4, st>>>(t->keys, (const f32x4*)t->values, t->nb, d_keys, n,
+        auto launch = [&](auto bf16, auto ntc) {
+            find_prepare_kernel<d4, R, (bf16 ? kFindBF16Out : 0) | ntc><<<part_blocks + find_blocks, kFindPrepareThreads, sizeof(PartHot) + plan.nbk * 4, st>>>(t->keys, (const f32x4*)t->values, t->nb, d_keys, n,
                 (f32x4*)d_out, d_found, t->default_value, t->dim4, d_slots_out, handle_tag_of(t), part_blocks, plan.nbk_hash, plan.nbk, plan.per_block, t->bk, &t->ctr->status, t->op, t->bk.xcd_split);
         };
-        if (out_dtype == MEE_DTYPE_BF16) with_value<256 + 68, 256 + 64>(cached_out ? 256 + 68 : 256 + 64, launch);   // NT | 256: bf16 rows (find_span)
-        else with_value<68, 64>(cached_out ? 68 : 64, launch);
+        with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) { with_value<kFindLocated | kFindCachedStores, kFindLocated>(nt, [&](auto ntc) { launch(bf16, ntc); }); });
     });
     MEE_HIP(hipGetLastError());
     if (separate) { if (int rc = bucket_partition_launch(t, d_keys, (uint32_t)n, plan, st)) return rc; }

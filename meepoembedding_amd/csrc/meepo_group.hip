@@ -23,10 +23,10 @@ namespace mee {
 // LOCATE: no rows move; gslot[i] = member << 48 | slot of the key (kEmpty when absent / reserved / outside the segments) —
 // the first pass of a grouped apply.
 // BF16: `out` holds bf16 rows (SPEC.md §3 "Output type"): the lane's float4 leaves as 4 bf16 in one 8-byte store; BF16 = false is the code it was.
-// BROWS: a bf16-row group (SPEC.md §3 "Row storage type") — every member's `values` is a bf16-row plane.  Same tiles, same index arithmetic as find_span's
-// BROWS path: the lane's element group is 8 bytes (u32x2) at slot * dim4 + c * 16 + tl; with bf16 out the 8 bytes leave as they came (no second rounding),
-// with fp32 out they are widened in registers; a member's default row is packed from its defv, which is a bf16 value already.  One storage type per group:
-// a property of the launch, not a per-member branch.  The instances with BROWS = false are the code they were before the parameter existed.
+// BROWS: a bf16-row group (SPEC.md §3 "Row storage type") — every member's `values` is a bf16-row plane, read and stored through RowType (meepo_device.h) as
+// find_span does it: same tiles, same index arithmetic; a member's default row is packed from its defv, which is a bf16 value already.  One storage type per
+// group: a property of the launch, not a per-member branch.  The fp32 arm keeps its float4 loads and stores: through RowType's f32x4 its instances come out
+// as other code (profiles/find_row_types.md).
 template <int DIM4, int R, bool STREAM_OUT, bool LOCATE = false, bool BF16 = false, bool BROWS = false>
 __global__ __launch_bounds__(256) void find_grouped_kernel(const GroupDesc* __restrict__ desc, uint32_t n_tables,
                                                            const uint64_t* __restrict__ offsets, const int64_t* __restrict__ keys,
@@ -80,20 +80,20 @@ __global__ __launch_bounds__(256) void find_grouped_kernel(const GroupDesc* __re
         }
         if constexpr (BROWS) {
             static_assert(!LOCATE, "bf16 rows: the lookups only");
+            using RT = RowType<kRowsBF16>;
             if constexpr (DIM4 != 0) {
-                u32x2 row[R][C];
+                RT::Group row[R][C];
 #pragma unroll
                 for (int r = 0; r < R; ++r)
 #pragma unroll
                     for (int c = 0; c < C; ++c)
-                        row[r][c] = slot[r] >= 0 ? reinterpret_cast<const u32x2*>(d[r].values)[(uint64_t)slot[r] * DIM4 + c * 16 + tl]
-                                                 : bf16x4_of(d[r].defv, d[r].defv, d[r].defv, d[r].defv);
+                        row[r][c] = slot[r] >= 0 ? RT::plane(d[r].values)[RT::first(slot[r], DIM4) + c * 16 + tl] : RT::missing(f32x4{d[r].defv, d[r].defv, d[r].defv, d[r].defv});
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     const uint64_t i = base + r * 4 + tile;
                     if (inb[r])
 #pragma unroll
-                        for (int c = 0; c < C; ++c) store_brow_as<BF16, !STREAM_OUT>(out, i * DIM4 + c * 16 + tl, row[r][c]);
+                        for (int c = 0; c < C; ++c) RT::store<BF16, !STREAM_OUT>(out, i * DIM4 + c * 16 + tl, row[r][c], 0u, true, f32x4{});
                 }
             } else {
 #pragma unroll
@@ -101,8 +101,8 @@ __global__ __launch_bounds__(256) void find_grouped_kernel(const GroupDesc* __re
                     const uint64_t i = base + r * 4 + tile;
                     if (inb[r])
                         for (uint32_t c = tl; c < dim4; c += 16)
-                            store_brow_as<BF16, true>(out, i * dim4 + c, slot[r] >= 0 ? reinterpret_cast<const u32x2*>(d[r].values)[(uint64_t)slot[r] * dim4 + c]
-                                                                                       : bf16x4_of(d[r].defv, d[r].defv, d[r].defv, d[r].defv));
+                            RT::store<BF16, true>(out, i * dim4 + c, slot[r] >= 0 ? RT::plane(d[r].values)[RT::first(slot[r], dim4) + c] : RT::missing(f32x4{d[r].defv, d[r].defv, d[r].defv, d[r].defv}),
+                                                  0u, true, f32x4{});
                 }
             }
         } else if constexpr (DIM4 != 0) {

@@ -96,7 +96,7 @@ struct mee_table {
     uint64_t capacity, nb, max_batch;
     uint32_t dim, dim4, optimizer, initializer, value_memory;
     // Row storage type (SPEC.md §3): bf16_rows = the value plane holds bf16 rows of 2·dim bytes (MEE_FLAG_BF16_ROWS; no optimizer planes).  The lookups
-    // read them as such (find_span / pooled_fetch with BROWS: the lane's element group is 8 bytes).  The MOVERS — insert, assign, rehash, remove — only
+    // read them as such (find_span / pooled_fetch through RowType<kRowsBF16>: the lane's element group is 8 bytes).  The MOVERS — insert, assign, rehash, remove — only
     // copy or drop rows: they run unchanged on a row as mv_dim4 opaque 16-byte groups (dim / 8 for bf16 rows, which is why dim % 8 == 0; dim4 otherwise),
     // fed with rows that pack_rows_kernel rounded into `pack` ([max_batch][dim] bf16, allocated at create) or with the caller's own bf16 rows.
     // int8_rows = the value plane holds int8 rows (MEE_FLAG_INT8_ROWS; never together with bf16_rows): dim codes and a 16-byte tail that starts with the

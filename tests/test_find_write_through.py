@@ -10,6 +10,8 @@ import pytest
 import torch
 
 from meepoembedding_amd import LookupTable, _lib, synth
+from test_bf16_rows import rnd
+from test_int8_rows import DQ
 
 pytestmark = pytest.mark.gpu
 
@@ -20,6 +22,9 @@ MIXES = ("present", "absent", "reserved")
 STREAM3 = _lib.FIND_STREAM_STORES | _lib.FIND_STREAM_ROWS | _lib.FIND_STREAM_BUCKETS
 FLAG_SETS = (_lib.FIND_DEFAULT, _lib.FIND_STREAM_STORES, _lib.FIND_STREAM_STORES | _lib.FIND_STREAM_ROWS, STREAM3, _lib.FIND_CACHED_STORES)
 SENT, SENT_U8 = -777.25, 0xAB
+BF16 = torch.bfloat16
+# the serving row types: how such a table is made, and what it stores of fp32 rows, as fp32 (what its fp32 twin is fed)
+NARROW_ROWS = {"int8": (dict(int8_rows=True), DQ), "bf16": (dict(value_dtype=BF16), rnd)}
 
 
 def make_tables(dev):
@@ -97,24 +102,36 @@ def test_other_entry_points_give_the_same_rows(tables, dev, dim):
         assert torch.equal(out, ref_rows) and torch.equal(found, ref_found), (dim, mix)
 
 
-@pytest.mark.parametrize("dim", (64, 128))
-def test_int8_rows_with_fp32_output(dev, dim):
-    """an int8-row table dequantizes in registers and stores 16 bytes per lane: the same rows under every flag set"""
+@pytest.mark.parametrize("out_dtype", (torch.float32, BF16), ids=("f32_out", "bf16_out"))
+@pytest.mark.parametrize("rows", sorted(NARROW_ROWS))
+@pytest.mark.parametrize("dim", DIMS)
+def test_narrow_rows_give_the_twins_bytes_under_every_policy(dev, dim, rows, out_dtype):
+    """An int8-row table dequantizes in registers, a bf16-row table widens (or hands its 8 bytes on as they are): under every flag set the same
+    bytes as under CACHED_STORES, and those are the bytes of the fp32 twin (tests/test_int8_rows.py, tests/test_bf16_rows.py: an fp32 table of
+    the same default, fed what the narrow table stores) looked up into the same output type.  The planted position is the default row, found 0."""
+    table_kw, stored = NARROW_ROWS[rows]
     keys = synth.keys_t(1, 0, N_KEYS, dev)
-    t = LookupTable(2 * N_KEYS, dim, device=dev, default_value=DEFAULT, int8_rows=True)
-    t.insert(keys, synth.rows_t(keys, dim, SEED))
+    fed = synth.rows_t(keys, dim, SEED)
+    t = LookupTable(2 * N_KEYS, dim, device=dev, default_value=DEFAULT, **table_kw)
+    tw = LookupTable(2 * N_KEYS, dim, device=dev, default_value=DEFAULT)   # (0.625 is a bf16 value)
+    t.insert(keys, fed)
+    tw.insert(keys, stored(fed).to(dev))
+    bits = (lambda x: x.view(torch.int16)) if out_dtype == BF16 else (lambda x: x.view(torch.int32))
     for n in NS:
         for mix in MIXES:
             k = batch_of(keys, n, mix, dev, start=n)
-            cached, cfound = t.find(k, flags=_lib.FIND_CACHED_STORES)
-            _, ref_found = expected(k, mix, dim)
-            assert torch.equal(cfound, ref_found)
+            ref, ref_found = tw.find(k, flags=_lib.FIND_CACHED_STORES, out_dtype=out_dtype)
+            assert torch.equal(ref_found, expected(k, mix, dim)[1])
             if mix != "present":
-                assert torch.equal(cached[n // 2], torch.full((dim,), DEFAULT, device=dev))
+                assert torch.equal(ref[n // 2], torch.full((dim,), DEFAULT, dtype=out_dtype, device=dev))
+            cached, cfound = t.find(k, flags=_lib.FIND_CACHED_STORES, out_dtype=out_dtype)
             for flags in FLAG_SETS:
-                out, found = t.find(k, flags=flags)
-                assert torch.equal(out, cached) and torch.equal(found, cfound), (dim, n, mix, flags)
+                out, found = t.find(k, flags=flags, out_dtype=out_dtype)
+                what = f"{rows} rows dim {dim} {out_dtype} n {n} {mix} flags {flags}"
+                assert out.dtype == out_dtype and torch.equal(bits(out), bits(cached)) and torch.equal(found, cfound), what
+                assert torch.equal(bits(out), bits(ref)) and torch.equal(found, ref_found), what
     t.close()
+    tw.close()
 
 
 @pytest.mark.parametrize("dim", DIMS)
