@@ -1,0 +1,48 @@
+"""A recommender's sparse part whose tables do not fit HBM: 8 tables, each a hot/cold pair (hot rows in HBM, cold rows in pinned host
+memory), served by ONE pooled lookup launch and trained by two grouped optimizer steps per batch, whatever the number of tables
+(run on the GPU box: python examples/tiered_collection.py)."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+import __graft_entry__
+
+__graft_entry__.build()
+from meepoembedding_amd import INIT_UNIFORM, OPT_ADAGRAD, LookupTable, TieredLookupTable, TieredTableGroup, _lib  # noqa: E402
+from meepoembedding_amd.nn import DynamicEmbeddingBag  # noqa: E402
+
+dev = torch.device("cuda", 0)
+n_tables, dim, batch, ids_per_bag, vocab = 8, 64, 2048, 5, 400_000
+max_ids = n_tables * batch * 2 * ids_per_bag       # an upper bound on the ids of one step
+
+
+def table(capacity, j, **kw):
+    return LookupTable(capacity, dim, device=dev, optimizer=OPT_ADAGRAD, max_batch=max_ids, initializer=INIT_UNIFORM, init_scale=0.05,
+                       init_seed=j, track_hits=True, **kw)      # track_hits on both tiers: the placement policy
+
+
+# New ids are created hot while a pair has room for a whole batch of them (the host's only bound on a member's new ids is the size of the batch:
+# conservative, and free of synchronisation), then cold; rebalance() promotes the cold ids the lookups keep hitting.
+pairs = [TieredLookupTable(table(1 << 18, j), table(2 * vocab, j, value_memory=_lib.MEM_HOST_PINNED), hot_key_limit=120_000)
+         for j in range(n_tables)]
+group = TieredTableGroup(pairs, max_apply_batch=max_ids)
+sparse = DynamicEmbeddingBag(group, mode="sum", optimizer="adagrad", lr=0.05, create_missing=True).to(dev)   # bag b -> pair b // batch
+dense = torch.nn.Sequential(torch.nn.Linear(n_tables * dim, 256), torch.nn.ReLU(), torch.nn.Linear(256, 1)).to(dev)
+dense_opt = torch.optim.SGD(dense.parameters(), lr=0.01)
+
+for step in range(8):
+    lens = torch.randint(1, 2 * ids_per_bag, (n_tables * batch,), device=dev)
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(lens, 0)])
+    ids = (torch.rand(int(offsets[-1]), device=dev) ** 3 * vocab).long()      # a skewed stream: small ids are popular
+    labels = torch.rand(batch, 1, device=dev)
+    pooled = sparse(ids, offsets)        # three launches: found mask, creation of unseen ids (hot while there is room, else cold), pooled lookup
+    features = pooled.view(n_tables, batch, dim).transpose(0, 1).reshape(batch, n_tables * dim)
+    loss = torch.nn.functional.binary_cross_entropy_with_logits(dense(features), labels)
+    dense_opt.zero_grad()
+    loss.backward()                      # the sparse update: one grouped step over the hot tables, one over the cold tables
+    dense_opt.step()
+    moved = group.rebalance() if step % 2 == 1 else None      # between steps: promote the cold ids the lookups hit, per pair
+    print(f"step {step}: loss {loss.item():.4f}, ids {ids.numel()}, keys hot {sum(p.hot.size() for p in pairs)} / cold {sum(p.cold.size() for p in pairs)}"
+          + (f", rebalanced: promoted {sum(m[0] for m in moved)}, demoted {sum(m[1] for m in moved)}" if moved else ""))

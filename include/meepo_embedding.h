@@ -389,6 +389,30 @@ int mee_group_find_pooled_weighted(mee_group* g, const int64_t* d_keys, size_t n
 int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,
                                        size_t bags_per_table, const float* d_weights, const float* d_bag_grads, float* d_grads_out,
                                        float* d_weight_grads_out, void* stream);
+/* The embedding-bag collection over hot/cold PAIRS: member j of hot_group and member j of cold_group are the two tiers of pair j (a key lives in
+ * exactly one of them; meepoembedding_amd/tiered.py, TieredTableGroup).  mee_group_find_pooled_tiered is, by definition, mee_find_pooled_tiered(hot
+ * member b / bags_per_table, cold member b / bags_per_table) on every bag b, bit for bit, in ONE launch for all n_tables x bags_per_table bags: a
+ * position is probed in its member's hot index, in the cold one only where a wave missed, the row comes from the plane that holds it, an absent or
+ * reserved key reads that member's HOT table's default row, d_found[i] (nullable: not written) = 1 iff either tier holds the key; SUM | MEAN, offsets
+ * past n cut at n, a decreasing pair an empty bag; d_out = [n_tables x bags_per_table, dim] fp32 or bf16 (the finished bag row rounded once).  No
+ * weights, no jagged map, no located rows.  flags = MEE_TIER_COUNT_COLD | MEE_TIER_COUNT_HOT: every position found in that tier adds 1 to its slot's
+ * hit counter in that member's table; EVERY member of the tier must have been created with MEE_FLAG_TRACK_HITS.
+ * mee_group_ensure_tiered creates, for every position with d_found[i] == 0 (a mask an earlier lookup wrote: "in neither tier"), the key in ONE tier of
+ * its member — the cold table where d_to_cold[member] != 0 (n_tables bytes in DEVICE memory; null: every member creates hot) — exactly as
+ * mee_find_or_insert_missing on that table does: initial row from that table's initializer, initial optimizer state, a zero hit counter, TABLE_FULL /
+ * RESERVED_KEY (a tombstone value in the batch) on that table's status word, one creation per distinct key.  Member segments are every
+ * bags_per_table-th bag offset, cut at n.  No row is returned: there is no [n, dim] buffer.  d_found is only read.
+ * Both: no host synchronisation and no allocation, capturable like mee_find_pooled_tiered; after mee_reserve on a member of either group the next call
+ * re-reads that table's planes (one stream synchronisation).  bags_per_table == 0 succeeds and writes nothing.  MEE_ERR_INVALID_ARG before anything
+ * is launched or written: a null group, hot_group == cold_group, groups that differ in device, dim or number of tables, a member that is the same
+ * table in both, an unknown mode / out_dtype / flag bit, a misaligned bf16 d_out, a count flag when a member of that tier has no counters;
+ * MEE_ERR_UNSUPPORTED: a bf16-row group. */
+int mee_group_find_pooled_tiered(mee_group* hot_group, mee_group* cold_group, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets,
+                                 size_t bags_per_table, void* d_out, uint32_t out_dtype, uint8_t* d_found /* nullable: not written */, int mode,
+                                 uint32_t flags, void* stream);
+int mee_group_ensure_tiered(mee_group* hot_group, mee_group* cold_group, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets,
+                            size_t bags_per_table, const uint8_t* d_found, const uint8_t* d_to_cold /* [n_tables], device; nullable: all hot */,
+                            void* stream);
 
 /* ---- typed output: the lookups above with fp32 OR bf16 result rows (SPEC.md §3 "Output type") --------------------------------
  * The models these tables feed run in bf16; a lookup that writes bf16 itself saves the cast in front of the first dense layer and half

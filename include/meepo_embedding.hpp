@@ -200,6 +200,15 @@ public:
     void apply_adam_indexed(const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index, size_t n, float lr, uint64_t step, float beta1 = 0.9f, float beta2 = 0.999f, float eps = 1e-8f, void* stream = nullptr) {
         check(mee_group_apply_adam_indexed(g_, d_keys, d_offsets, d_grads, n_grad_rows, d_grad_index, n, lr, beta1, beta2, eps, step, stream));
     }
+    // a collection of hot/cold pairs: this group holds the HOT tables, `cold` the cold ones, member j of both = pair j (mee_group_find_pooled_tiered /
+    // mee_group_ensure_tiered).  One pooled launch over both tiers of every member; flags = MEE_TIER_COUNT_*.  ensure_tiered creates the keys d_found
+    // marks as missing, member j in its cold table where d_to_cold[j] != 0 (null: all hot).
+    void find_pooled_tiered(Group& cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, uint8_t* d_found = nullptr, int mode = MEE_POOL_SUM, uint32_t flags = 0, void* stream = nullptr) {
+        check(mee_group_find_pooled_tiered(g_, cold.g_, d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, d_found, mode, flags, stream));
+    }
+    void ensure_tiered(Group& cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const uint8_t* d_found, const uint8_t* d_to_cold = nullptr, void* stream = nullptr) {
+        check(mee_group_ensure_tiered(g_, cold.g_, d_keys, n, d_bag_offsets, bags_per_table, d_found, d_to_cold, stream));
+    }
 private:
     mee_group* g_ = nullptr;
 };

@@ -352,11 +352,17 @@ struct TierArgs {
 // missed — by all 64 lanes in convergent control flow, tiles without a miss pass act = false — and each row is loaded from the plane that
 // holds it (one load per row: the address is selected, not the data).  Counting (nullable counters, wave-uniform branches): one atomicAdd
 // per found position by the tile's first lane, as find_kernel (kFindCountHits, meepo_find.hip) and find_missing_kernel (FLAGS & 2) do it.
-template <int DIM4, int U, int C>
+// BY_FLAGS (a GROUP of pairs: the tiles of a wave may work for different members, so the hot planes, `cold` and its counters differ from tile to
+// tile): whether a tier is counted is then read from the launch's `count` bits (kTierCountCold | kTierCountHot), never from a member's pointer —
+// every wave-uniform branch stays on a fact of the whole launch.
+constexpr uint32_t kTierCountCold = 1, kTierCountHot = 2;   // = MEE_TIER_COUNT_COLD / MEE_TIER_COUNT_HOT (include/meepo_embedding.h)
+template <int DIM4, int U, int C, bool BY_FLAGS = false>
 __device__ __forceinline__ void pooled_fetch_tiered(const int64_t* __restrict__ tkeys, const float4* __restrict__ values, uint64_t nb,
                                                     const TierArgs& cold, uint32_t dim4, const int64_t (&key)[U], const uint64_t (&pos)[U],
                                                     const bool (&inb)[U], int tile, int tl, float4 def4, float4 (&row)[U][C],
-                                                    uint8_t* __restrict__ found) {
+                                                    uint8_t* __restrict__ found, uint32_t count = 0) {
+    const bool count_cold = BY_FLAGS ? (count & kTierCountCold) != 0 : cold.cold_hits != nullptr;
+    const bool count_hot = BY_FLAGS ? (count & kTierCountHot) != 0 : cold.hot_hits != nullptr;
     int64_t slot[U], kb[U];
     uint64_t bk[U];
     bool act[U];
@@ -400,13 +406,13 @@ __device__ __forceinline__ void pooled_fetch_tiered(const int64_t* __restrict__ 
                     row[u][c] = hit ? src[c * 16 + tl] : def4;
             if (found && inb[u] && tl == 0) found[pos[u]] = hit;
         }
-        if (cold.cold_hits) {   // wave-uniform
+        if (count_cold) {   // wave-uniform
 #pragma unroll
             for (int u = 0; u < U; ++u)
                 if (cslot[u] >= 0 && tl == 0) atomicAdd(&cold.cold_hits[cslot[u]], 1u);
         }
     }
-    if (cold.hot_hits) {   // wave-uniform (sampled calls)
+    if (count_hot) {   // wave-uniform (sampled calls)
 #pragma unroll
         for (int u = 0; u < U; ++u)
             if (slot[u] >= 0 && tl == 0) atomicAdd(&cold.hot_hits[slot[u]], 1u);
@@ -505,21 +511,33 @@ __device__ __forceinline__ void pooled_store(float4* __restrict__ out, uint64_t 
 // With BPW = 4 the tiles of a wave may get different tables in the short phase; the long phase asks again for bag q and all four tiles switch to it.
 // C: float4 per lane per row.  TAGGED: absent keys leave -1 in `located` (the format of mee_find_located), otherwise EMPTY.  TIERED: `tier` brings the
 // cold table of a hot/cold pair, `located` is never read.  BROWS: the value planes hold bf16 rows, widened at their load (pooled_fetch).
+// TIERED over a GROUP of pairs: the cold table belongs to the bag like the hot one, so table_of takes a third argument —
+//   table_of(b, PooledTable&, TierArgs&) -> bool   also fills in the cold table (and, under the launch's count bits, the counters) of bag b's member
+// — and `tier` is not read; `tier_count` carries the launch's count bits (kTierCountCold | kTierCountHot), the one thing about the tiers that is the
+// same for every bag.  The cold table then switches wherever the hot one does: per tile in the short phase, to bag q's for all four tiles in the long one.
 template <int DIM4, int U, int BPW, int C, bool WEIGHTED, bool BF16, bool TIERED, bool BROWS, bool TAGGED, class TableOf, class RowOf>
 __device__ __forceinline__ void pooled_bags(uint64_t bag0, uint32_t nvalid, uint32_t dim4, const int64_t* __restrict__ keys, const uint64_t* __restrict__ offsets,
                                             uint64_t n_keys, const float* __restrict__ weights, float4* __restrict__ out, uint8_t* __restrict__ found,
-                                            int64_t* __restrict__ located, int mean, const TierArgs& tier, int tile, int tl, TableOf&& table_of, RowOf&& row_of) {
+                                            int64_t* __restrict__ located, int mean, const TierArgs& tier, int tile, int tl, TableOf&& table_of, RowOf&& row_of,
+                                            uint32_t tier_count = 0) {
+    constexpr bool TIER_PER_BAG = TIERED && std::is_invocable_v<TableOf&, uint64_t, PooledTable&, TierArgs&>;
     const uint64_t bag = BPW == 4 ? bag0 + tile : bag0;
     const bool has = BPW == 4 ? (uint32_t)tile < nvalid : true;
     uint64_t begin, end;
     pooled_span(offsets, bag, has, n_keys, begin, end);
     PooledTable t;
-    if (!table_of(has ? bag : bag0, t)) begin = end = 0;
+    TierArgs cold_of_bag;   // (TIER_PER_BAG only)
+    auto table = [&](uint64_t b) {
+        if constexpr (TIER_PER_BAG) return table_of(b, t, cold_of_bag);
+        else return table_of(b, t);
+    };
+    if (!table(has ? bag : bag0)) begin = end = 0;
     const bool is_long = BPW == 1 || end - begin >= kPoolLong;
     float4 acc[C];
     float4 row[U][C];
     auto fetch = [&](const int64_t (&kv)[U], const uint64_t (&pos)[U], const bool (&inb)[U]) {
-        if constexpr (TIERED) pooled_fetch_tiered<DIM4, U, C>(t.tkeys, t.values, t.nb, tier, dim4, kv, pos, inb, tile, tl, t.def4, row, found);
+        if constexpr (TIER_PER_BAG) pooled_fetch_tiered<DIM4, U, C, true>(t.tkeys, t.values, t.nb, cold_of_bag, dim4, kv, pos, inb, tile, tl, t.def4, row, found, tier_count);
+        else if constexpr (TIERED) pooled_fetch_tiered<DIM4, U, C>(t.tkeys, t.values, t.nb, tier, dim4, kv, pos, inb, tile, tl, t.def4, row, found);
         else pooled_fetch<DIM4, U, C, TAGGED, BROWS ? kRowsBF16 : kRowsF32>(t.tkeys, t.values, t.nb, dim4, kv, pos, inb, tile, tl, t.def4, row, found, located, t.tag);
     };
     // ---- short bags: one tile per bag ----
@@ -560,7 +578,7 @@ __device__ __forceinline__ void pooled_bags(uint64_t bag0, uint32_t nvalid, uint
         // the pair's lookup on bags of 20 measures 5 % slower than with it — same occupancy, cause not found (profiles/pooled_shared_body.md §2)
         constexpr bool OWN_SPAN = BPW == 1 && !TIERED;
         const uint64_t bq = OWN_SPAN ? begin : __shfl(begin, q * 16), eq = OWN_SPAN ? end : __shfl(end, q * 16);
-        if constexpr (BPW == 4) (void)table_of(bag0 + q, t);   // all four tiles work for bag q's table now (a long bag is not empty)
+        if constexpr (BPW == 4) (void)table(bag0 + q);   // all four tiles work for bag q's table now (a long bag is not empty)
         bool first = true;
 #pragma unroll
         for (int c = 0; c < C; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -353,9 +353,21 @@ __device__ __forceinline__ bool jagged_member(const uint64_t* __restrict__ membe
 // located rows then carry its handle tag and -1 for an absent key (TAGGED), a group's the member and EMPTY.
 // BF16: `out` holds bf16 rows (SPEC.md §3 "Output type").
 // TIERED (mee_find_pooled_tiered; one hot/cold pair, unweighted): the table arguments are the HOT table's, `tier` brings the cold one.
+// GROUPED && TIERED (mee_group_find_pooled_tiered; a collection of pairs, unweighted, no jagged map, no located rows): `desc` holds the HOT
+// members, `tier` is a GroupTier — the cold members' descriptors, both groups' GroupInit (for the hit counters) and the launch's count bits.
+// Bag b's hot AND cold table are member b / bags_per_table's: table_of fills in both, per tile in the short phase of a four-bags-per-wave
+// step (bags_per_table need not be a multiple of 4: one wave may serve two members) and again for bag q in the long phase.  Both launch
+// shapes go through pooled_bags; a member's counters are read only under the launch's count bit.
 // BROWS (one bf16-row table, or with GROUPED a bf16-row group — every member's plane, JAGGED included; unweighted: SPEC.md §3 "Row
 // storage type"): the value planes hold bf16 rows.  One storage type per group, so this is a property of the launch, never a per-member
 // branch in the fetch.
+struct GroupTier {   // what a launch over a group of hot/cold pairs knows about the tiers (find_pooled_kernel<..., GROUPED, ..., TIERED>)
+    const GroupDesc* cold_desc;   // [n_tables] the cold members (device)
+    const GroupInit* hot_init;    // [n_tables] of the two groups: a member's `hits`
+    const GroupInit* cold_init;
+    uint32_t count;               // kTierCountCold | kTierCountHot
+};
+static_assert(kTierCountCold == MEE_TIER_COUNT_COLD && kTierCountHot == MEE_TIER_COUNT_HOT, "the kernels read the C-ABI's flag bits as they come");
 template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false, bool JAGGED = false, bool TIERED = false, bool BROWS = false>
 __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restrict__ tkeys_, const float4* __restrict__ values_,
                                                           uint64_t nb_, const int64_t* __restrict__ keys,
@@ -365,9 +377,9 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                                                           uint64_t bags_per_table = 1, int64_t* __restrict__ located = nullptr,
                                                           uint64_t n_keys = ~0ull, const float* __restrict__ weights = nullptr,
                                                           int64_t handle_tag = 0, const uint64_t* __restrict__ member_bags = nullptr,
-                                                          uint32_t n_members = 0, TierArgs tier = {}) {
+                                                          uint32_t n_members = 0, std::conditional_t<GROUPED && TIERED, GroupTier, TierArgs> tier = {}) {
     static_assert(!JAGGED || (GROUPED && !WEIGHTED && !BF16), "the jagged map is the group's plain fp32 lookup");
-    static_assert(!TIERED || (!GROUPED && !WEIGHTED && !JAGGED), "the tiered form is one pair's plain sum / mean");
+    static_assert(!TIERED || (!WEIGHTED && !JAGGED), "the tiered form is the plain sum / mean of one pair or of a group of pairs");
     static_assert(!BROWS || (!WEIGHTED && !TIERED), "bf16 rows: the plain sum / mean of one table or of a bf16-row group (jagged map included)");
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -390,7 +402,18 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
     };
     auto row_of = [&](uint64_t b) { return b * dim4; };
     for (uint64_t b0 = wave * BPW; b0 < n_bags; b0 += n_waves * BPW) {
-        if constexpr (!(GROUPED && BPW == 4)) {
+        if constexpr (GROUPED && TIERED) {
+            auto pair_of = [&](uint64_t b, PooledTable& t, TierArgs& cold) {   // the hot and the cold table of bag b's member
+                const uint64_t member = b / bags_per_table;
+                t = pooled_table(desc[member], member, kGroupSlotBits);
+                const GroupDesc c = tier.cold_desc[member];
+                cold = TierArgs{c.tkeys, c.values, c.nb, (tier.count & kTierCountHot) ? tier.hot_init[member].hits : nullptr,
+                                (tier.count & kTierCountCold) ? tier.cold_init[member].hits : nullptr};
+                return true;
+            };
+            pooled_bags<DIM4, U, BPW, C, false, BF16, true, false, false>(b0, (uint32_t)(n_bags - b0 < BPW ? n_bags - b0 : BPW), dim4, keys, offsets, n_keys, nullptr, out, found,
+                                                                          nullptr, mean, TierArgs{}, tile, tl, pair_of, row_of, tier.count);
+        } else if constexpr (!(GROUPED && BPW == 4)) {
             pooled_bags<DIM4, U, BPW, C, WEIGHTED, BF16, TIERED, BROWS, TAGGED>(b0, (uint32_t)(n_bags - b0 < BPW ? n_bags - b0 : BPW), dim4, keys, offsets, n_keys, weights, out, found,
                                                                                 (GROUPED && BROWS) ? nullptr : located,   // (a bf16-row group hands out no located rows: refused at the entry points)
                                                                                 mean, tier, tile, tl, table_of, row_of);
@@ -1067,6 +1090,32 @@ int mee_group_find_pooled_as(mee_group* g, const int64_t* d_keys, size_t n, cons
     if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_as: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
     if (d_weights && mode != MEE_POOL_SUM) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_as: weighted pooling is MEE_POOL_SUM only");
     return group_find_pooled_common(g, d_keys, n, d_bag_offsets, bags_per_table, d_weights, d_out, out_dtype, d_found, d_located_out, mode, stream);
+}
+
+// the pooled lookup of a GROUP of hot/cold pairs: find_pooled_kernel's GROUPED && TIERED instances, the hot group's descriptors in `desc`, the cold group's
+// (and both groups' GroupInit, for the hit counters) in GroupTier
+int mee_group_find_pooled_tiered(mee_group* hot, mee_group* cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                                 void* d_out, uint32_t out_dtype, uint8_t* d_found, int mode, uint32_t flags, void* stream) {
+    MEE_RANGE("mee_group_find_pooled_tiered");
+    if (!hot || !cold || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_tiered: null argument");
+    if (int rc = tiered_groups_check(hot, cold, flags, "mee_group_find_pooled_tiered")) return rc;
+    if (int rc = check_out_dtype(d_out, out_dtype, "mee_group_find_pooled_tiered")) return rc;
+    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_tiered: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
+    if (bags_per_table == 0) return MEE_OK;
+    if (int rc = group_refresh(hot, stream)) return rc;
+    if (int rc = group_refresh(cold, stream)) return rc;
+    DeviceGuard guard(hot->device);
+    hipStream_t st = as_stream(stream);
+    const uint64_t n_bags = (uint64_t)hot->n_tables * bags_per_table;
+    const GroupTier tier{cold->d_desc, hot->d_init, cold->d_init, flags};
+    with_pooled_shape(hot->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
+        constexpr int ut = (bpw == 1 && u > 2) ? 2 : u;   // the keys in flight of the pair's launch (mee_find_pooled_tiered); four at dim 64 measured no better (profiles/tiered_groups.md)
+        find_pooled_kernel<d4, ut, bpw, true, false, bf16, false, true><<<grid, 256, 0, st>>>(
+            nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, hot->dim4, mode == MEE_POOL_MEAN, hot->d_desc, bags_per_table,
+            nullptr, n, nullptr, 0, nullptr, 0, tier);
+    }); });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
 }
 
 int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,

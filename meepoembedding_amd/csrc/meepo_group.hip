@@ -205,6 +205,61 @@ __global__ __launch_bounds__(256) void ensure_grouped_kernel(const GroupDesc* __
     }
 }
 
+// ensure_grouped_kernel's sibling for a GROUP of hot/cold pairs (mee_group_ensure_tiered): every position the found mask leaves missing claims (or
+// finds, when a duplicate got there first) its key's slot in ONE tier of its member — the cold table where to_cold[member] != 0 (null: every member
+// creates hot) — and the tile whose CAS created the key writes what mee_find_or_insert_missing on that table writes: the initial row from THAT table's
+// initializer, its initial optimizer state, a zero hit counter; TABLE_FULL and RESERVED_KEY (a tombstone value in the batch) go to that table's status
+// word.  Member segments are every bags_per_table-th bag offset (the off_stride of group_locate), cut at n as the lookups cut them: no key past the array
+// is read.  No row is written back — the pooled lookup that follows reads the tables — so no [n, dim] buffer exists.  One tile per position.
+__global__ __launch_bounds__(256) void ensure_tiered_grouped_kernel(const GroupDesc* __restrict__ hot_desc, const GroupInit* __restrict__ hot_init,
+                                                                    const GroupDesc* __restrict__ cold_desc, const GroupInit* __restrict__ cold_init,
+                                                                    uint32_t n_tables, const uint64_t* __restrict__ offsets, uint64_t bags_per_table,
+                                                                    const int64_t* __restrict__ keys, uint64_t n, const uint8_t* __restrict__ found,
+                                                                    const uint8_t* __restrict__ to_cold, uint32_t dim4) {
+    __shared__ uint64_t loff[kMaxGroupTables + 1];
+    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) {
+        const uint64_t o = offsets[(uint64_t)j * bags_per_table];
+        loff[j] = o < n ? o : n;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t base = wave * 4; base < n; base += n_waves * 4) {
+        const uint64_t i = base + tile;
+        bool act = i < n && i >= loff[0] && i < loff[n_tables] && found[i] == 0;
+        const int64_t key = act ? keys[i] : kEmpty;
+        const bool tomb = act && key == kReclaimed;   // a reserved key in the batch: flagged like mee_find_or_insert_missing does (EMPTY = padding, silent)
+        act = act && !reserved_key(key);
+        if (!__any(act || tomb)) continue;  // wave-uniform: nothing missing here (the steady state of a trained vocabulary)
+        uint32_t lo = 0, hi = n_tables;     // the last member whose segment starts at or before i (always inside [0, n_tables))
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (loff[mid] <= i) lo = mid; else hi = mid;
+        }
+        const bool goes_cold = to_cold && (act || tomb) && to_cold[lo] != 0;
+        const GroupDesc d = goes_cold ? cold_desc[lo] : hot_desc[lo];
+        const GroupInit in = goes_cold ? cold_init[lo] : hot_init[lo];
+        if (tomb && tl == 0) atomicOr(in.status, (uint32_t)MEE_STATUS_RESERVED_KEY);
+        bool is_new, full;
+        const int64_t slot = tile_locate<true, true>(const_cast<int64_t*>(d.tkeys), d.nb, key, act, tile, tl, is_new, full);
+        if (act) {
+            if (slot >= 0 && is_new) {
+                for (uint32_t c = tl; c < dim4; c += 16) {
+                    d.values[(uint64_t)slot * dim4 + c] = initial_row4(key, c * 4, in.initializer, in.init_scale, in.init_seed, d.defv);
+                    if (in.optimizer == MEE_OPT_ADAGRAD) d.s1[(uint64_t)slot * dim4 + c] = make_float4(in.init_acc, in.init_acc, in.init_acc, in.init_acc);
+                    if (in.optimizer == MEE_OPT_ADAM) {
+                        d.s1[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                        d.s2[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
+                }
+                if (in.hits && tl == 0) in.hits[slot] = 0;
+            }
+            if (full && tl == 0) atomicOr(in.status, (uint32_t)MEE_STATUS_TABLE_FULL);
+        }
+    }
+}
+
 }  // namespace mee
 
 using namespace mee;
@@ -320,6 +375,39 @@ int mee_group_destroy(mee_group* g) {
 }
 
 }  // extern "C"
+
+// ---- a group of hot/cold pairs: member j of `hot` and member j of `cold` are the two tiers of pair j (a key lives in exactly one of them) ----
+int mee::tiered_groups_check(const mee_group* hot, const mee_group* cold, uint32_t count_flags, const char* name) {
+    MEE_FP32_GROUP_ONLY(hot, name);
+    MEE_FP32_GROUP_ONLY(cold, name);
+    if (!hot || !cold) return fail(MEE_ERR_INVALID_ARG, "%s: null group", name);
+    if (hot == cold) return fail(MEE_ERR_INVALID_ARG, "%s: hot and cold are the same group (a key lives in exactly one tier)", name);
+    if (hot->device != cold->device || hot->dim != cold->dim || hot->n_tables != cold->n_tables)
+        return fail(MEE_ERR_INVALID_ARG, "%s: the groups differ in device (%d, %d), dim (%u, %u) or number of tables (%u, %u)", name, hot->device, cold->device,
+                    hot->dim, cold->dim, hot->n_tables, cold->n_tables);
+    for (uint32_t j = 0; j < hot->n_tables; ++j)
+        if (hot->tables[j] == cold->tables[j]) return fail(MEE_ERR_INVALID_ARG, "%s: member %u is the same table in both groups (a key lives in exactly one tier)", name, j);
+    if (count_flags & ~(uint32_t)(MEE_TIER_COUNT_COLD | MEE_TIER_COUNT_HOT)) return fail(MEE_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x", name, count_flags);
+    for (uint32_t j = 0; j < hot->n_tables; ++j)   // (only under a count bit: the plain lookup does not walk the members)
+        if (((count_flags & MEE_TIER_COUNT_COLD) && !table_view(cold->tables[j]).hits) || ((count_flags & MEE_TIER_COUNT_HOT) && !table_view(hot->tables[j]).hits))
+            return fail(MEE_ERR_INVALID_ARG, "%s: a count flag needs every member of that tier created with MEE_FLAG_TRACK_HITS (member %u has no counters)", name, j);
+    return MEE_OK;
+}
+
+extern "C" int mee_group_ensure_tiered(mee_group* hot, mee_group* cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                                       const uint8_t* d_found, const uint8_t* d_to_cold, void* stream) {
+    MEE_RANGE("mee_group_ensure_tiered");
+    if (!hot || !cold || (bags_per_table && !d_bag_offsets) || (n && (!d_keys || !d_found))) return fail(MEE_ERR_INVALID_ARG, "mee_group_ensure_tiered: null argument");
+    if (int rc = tiered_groups_check(hot, cold, 0, "mee_group_ensure_tiered")) return rc;
+    if (bags_per_table == 0 || n == 0) return MEE_OK;
+    if (int rc = group_refresh(hot, stream)) return rc;
+    if (int rc = group_refresh(cold, stream)) return rc;
+    DeviceGuard guard(hot->device);
+    ensure_tiered_grouped_kernel<<<grid_for(n, 16, 8192), 256, 0, (hipStream_t)stream>>>(hot->d_desc, hot->d_init, cold->d_desc, cold->d_init, hot->n_tables, d_bag_offsets,
+                                                                                        bags_per_table, d_keys, n, d_found, d_to_cold, hot->dim4);
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
 
 static int launch_find_grouped(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
                                hipStream_t st) {

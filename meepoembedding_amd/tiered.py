@@ -349,3 +349,163 @@ class TieredLookupTable:
         moved = self._move(self.hot, self.cold, keys)
         self._hot_keys_ub = max(0, self._hot_keys_ub - moved)
         return moved
+
+
+class TieredTableGroup:
+    """An embedding-bag COLLECTION of hot/cold pairs (SPEC.md §3 "Tiering"): `pairs` are TieredLookupTables of one device and one dim, bag b of a
+    batch of n_tables * bags_per_table bags belongs to pair b // bags_per_table, and the group's pooled lookup is, by definition,
+    pairs[b // bags_per_table].find_pooled on that pair's bags — in ONE launch for the whole collection (mee_group_find_pooled_tiered) where a loop
+    over the pairs pays one launch per table.  Underneath: a TableGroup over the hot tables and one over the cold tables (`hot_group`, `cold_group`,
+    both with max_apply_batch), so the step is two grouped steps whatever the number of tables.
+
+    The placement policy is on when EVERY pair has it (both tiers created with track_hits=True); the launch then counts cold hits always and hot
+    hits on every sample_every-th call, as a pair does.  Some pairs with it and some without is a ValueError.
+
+    The pairs stay usable on their own (rebalance, promote, demote, export, checkpoints).  Pairs that are not native tables (any objects with the
+    LookupTable methods) are served by a loop over the pairs with the same results."""
+    pools_with_insert = True            # nn.DynamicEmbeddingBag: unseen ids are created inside find_pooled(insert_missing=True)
+    weighted_bags = False               # no per_sample_weights over the tiers
+    supports_pooled_out_dtype = True    # find_pooled can write bf16 bag rows
+
+    def __init__(self, pairs, max_apply_batch: int = 0, sample_every: int = 8):
+        self.tables = list(pairs)
+        if not self.tables:
+            raise ValueError("a tiered group needs at least one hot/cold pair")
+        if len({int(p.dim) for p in self.tables}) != 1:
+            raise ValueError(f"the pairs of a tiered group must have one dim (got {[int(p.dim) for p in self.tables]})")
+        with_policy = [bool(p.policy) for p in self.tables]
+        if any(with_policy) and not all(with_policy):
+            raise ValueError("the placement policy is a property of the whole tiered group: every pair needs both tiers created with track_hits=True, "
+                             f"or none (pairs with it: {[j for j, w in enumerate(with_policy) if w]})")
+        if len({str(p.device) for p in self.tables}) != 1:
+            raise ValueError("the pairs of a tiered group must live on one device")
+        self.dim, self.policy = int(self.tables[0].dim), all(with_policy)
+        self.optimizer = self.tables[0].optimizer
+        self.sample_every, self._calls = max(1, int(sample_every)), 0
+        self.hot_group = self.cold_group = None
+        self._native = all(p._native() for p in self.tables)
+        if self._native:
+            from .table import TableGroup
+            self.hot_group = TableGroup([p.hot for p in self.tables], max_apply_batch)
+            self.cold_group = TableGroup([p.cold for p in self.tables], max_apply_batch)
+            # where member j's new keys go (1 = cold): on the device for the creation launch, rewritten only when a member's choice changes
+            self._goes_cold = [False] * len(self.tables)
+            self._d_goes_cold = torch.zeros(len(self.tables), dtype=torch.uint8, device=self.device)
+
+    @property
+    def device(self) -> torch.device:
+        return self.tables[0].device
+
+    @property
+    def layout_epoch(self):
+        """Changes whenever a tier of a member removed, cleared or rehashed rows."""
+        return tuple(getattr(t, "layout_epoch", None) for p in self.tables for t in (p.hot, p.cold))
+
+    def close(self) -> None:
+        for g in (self.hot_group, self.cold_group):
+            if g is not None:
+                g.close()
+        self.hot_group = self.cold_group = None
+
+    def size(self) -> int:
+        return sum(p.size() for p in self.tables)
+
+    def rebalance(self, max_moves: int = 1 << 20) -> list[tuple[int, int]]:
+        """TieredLookupTable.rebalance() of every pair -> [(promoted, demoted)] per pair.  Between steps, like the pair's own."""
+        return [p.rebalance(max_moves) for p in self.tables]
+
+    def _member_slices(self, bag_offsets: torch.Tensor, n: int):
+        """(non-native path) -> bags_per_table, [(first bag, key begin, key end)] per member; offsets past n are cut at n"""
+        nb = bag_offsets.numel() - 1
+        if nb < 0 or nb % len(self.tables):
+            raise ValueError("bag_offsets must hold n_tables * bags_per_table + 1 entries")
+        bpt = nb // len(self.tables)
+        cut = bag_offsets.to(torch.int64).clamp(0, n).tolist()
+        return bpt, [(j * bpt, cut[j * bpt], max(cut[j * bpt], cut[(j + 1) * bpt])) for j in range(len(self.tables))]
+
+    def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
+                    found: torch.Tensor | None = None, insert_missing: bool = False, out_dtype: torch.dtype = torch.float32):
+        """TieredLookupTable.find_pooled of every pair on its bags, in one launch -> ([n_tables * bags_per_table, dim] sums or means in position
+        order, per-key found mask).  An absent key reads its member's HOT table's default row.  With the policy on the launch feeds the
+        members' hit counters (cold hits always, hot hits on every sample_every-th call).
+        insert_missing: three launches whatever the number of tables, and no [n, dim] tensor — the found pass (it finishes before anything is
+        created, so `found` means "present before the call" also for a key repeated in the batch), ONE creation launch (member j's new keys go
+        to its hot table while pairs[j]._room_for(n) holds, else to its cold table, created as find_or_insert_missing creates them), then the
+        pooled launch, which writes no found bytes.  n, the size of the WHOLE batch, is the only bound the host has on a member's new keys:
+        it is conservative — a member is charged n keys per call, goes cold (after one refresh of its hot table's size, which synchronises)
+        earlier than the pair on its own slice would, never later.
+        out_dtype=torch.bfloat16: the finished bag row is rounded once."""
+        if mode not in ("sum", "mean"):
+            raise ValueError(f"mode must be 'sum' or 'mean' (got {mode!r})")
+        if not self._native:   # a loop over the pairs, member j on its slice of the keys and its bags_per_table bags
+            if out_dtype not in (torch.float32, torch.bfloat16):
+                raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16 (got {out_dtype})")
+            flat = keys.contiguous().view(-1)
+            bpt, members = self._member_slices(bag_offsets, flat.numel())
+            pooled = torch.zeros((bpt * len(self.tables), self.dim), dtype=out_dtype, device=flat.device)
+            fnd = torch.zeros(flat.numel(), dtype=torch.uint8, device=flat.device)
+            for pair, (b0, s, e) in zip(self.tables, members):
+                o, f = pair.find_pooled(flat[s:e], bag_offsets[b0:b0 + bpt + 1].to(torch.int64) - s, mode, insert_missing=insert_missing, out_dtype=out_dtype)
+                pooled[b0:b0 + bpt] = o
+                fnd[s:e] = f
+            if out is not None:
+                out.copy_(pooled)
+            if found is not None:
+                found.copy_(fnd)
+            return (out if out is not None else pooled), (found if found is not None else fnd)
+        from . import _lib
+        from .table import _out_dtype, _stream_ptr
+        dt = _out_dtype(out_dtype, out)
+        bpt = self.hot_group._check_bags(bag_offsets)
+        k = self.tables[0].hot._keys(keys) if keys.numel() else keys
+        n = k.numel()
+        if out is None:
+            out = torch.empty((bpt * len(self.tables), self.dim), dtype=out_dtype, device=self.device)
+        if found is None:
+            found = torch.empty(n, dtype=torch.uint8, device=self.device)
+        L, s, m = _lib.lib(), _stream_ptr(self.device), {"sum": 0, "mean": 1}[mode]
+        hot, cold = self.hot_group._h, self.cold_group._h
+        creates = bool(insert_missing and n and bpt)
+        if creates:
+            # the found mask of the whole batch first (no counters: this pass is not a lookup of the model's) ...
+            _lib.check(L.mee_group_find_pooled_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, found.data_ptr(), m, 0, s))
+            # ... then every member creates its absent keys in the tier its pair would pick
+            goes_cold = []
+            for p in self.tables:
+                room = p._room_for(n)
+                if room:
+                    p._hot_keys_ub += n
+                goes_cold.append(not room)
+            if goes_cold != self._goes_cold:
+                self._d_goes_cold.copy_(torch.tensor(goes_cold, dtype=torch.uint8))
+                self._goes_cold = goes_cold
+            _lib.check(L.mee_group_ensure_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, found.data_ptr(), self._d_goes_cold.data_ptr(), s))
+        flags = 0
+        if self.policy:
+            self._calls += 1
+            flags = _lib.TIER_COUNT_COLD | (_lib.TIER_COUNT_HOT if self._calls % self.sample_every == 0 else 0)
+        _lib.check(L.mee_group_find_pooled_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt,
+                                                  None if creates else found.data_ptr(), m, flags, s))
+        return out, found
+
+    def apply_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, bag_grads: torch.Tensor, bag_of_position: torch.Tensor,
+                     optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1,
+                     located: torch.Tensor | None = None) -> None:
+        """Backward of find_pooled: the pair's step per member — position i takes row bag_of_position[i] of bag_grads — as TWO grouped steps, the hot
+        group's and the cold group's (a key lives in one tier, and a group ignores the keys its member does not hold), then every pair's
+        rebalance_every bookkeeping.  `located` is accepted for the bag layer's sake and not used: the tiered lookup hands out no located rows."""
+        if optimizer not in ("adagrad", "adam"):
+            raise ValueError("optimizer must be 'adagrad' or 'adam'")
+        if not self._native:
+            flat = keys.contiguous().view(-1)
+            _, members = self._member_slices(bag_offsets, flat.numel())
+            for pair, (_, s, e) in zip(self.tables, members):
+                if optimizer == "adagrad":
+                    pair.apply_adagrad(flat[s:e], bag_grads, lr, 1e-10 if eps is None else eps, grad_index=bag_of_position[s:e])
+                else:
+                    pair.apply_adam(flat[s:e], bag_grads, lr, beta1, beta2, 1e-8 if eps is None else eps, step, grad_index=bag_of_position[s:e])
+            return
+        for g in (self.hot_group, self.cold_group):
+            g.apply_pooled(keys, bag_offsets, bag_grads, bag_of_position, optimizer, lr, eps=eps, beta1=beta1, beta2=beta2, step=step)
+        for p in self.tables:
+            p._after_optimizer_step()
