@@ -1,5 +1,6 @@
 """A recommender's sparse part whose tables do not fit HBM: 8 tables, each a hot/cold pair (hot rows in HBM, cold rows in pinned host
-memory), served by ONE pooled lookup launch and trained by two grouped optimizer steps per batch, whatever the number of tables
+memory), served by ONE pooled lookup launch and trained by two grouped optimizer steps per batch, whatever the number of tables; then the
+same pairs behind a DynamicEmbeddingCollection, which returns a row per id (a sequence feature) from one launch
 (run on the GPU box: python examples/tiered_collection.py)."""
 import os
 import sys
@@ -11,7 +12,7 @@ import __graft_entry__
 
 __graft_entry__.build()
 from meepoembedding_amd import INIT_UNIFORM, OPT_ADAGRAD, LookupTable, TieredLookupTable, TieredTableGroup, _lib  # noqa: E402
-from meepoembedding_amd.nn import DynamicEmbeddingBag  # noqa: E402
+from meepoembedding_amd.nn import DynamicEmbeddingBag, DynamicEmbeddingCollection  # noqa: E402
 
 dev = torch.device("cuda", 0)
 n_tables, dim, batch, ids_per_bag, vocab = 8, 64, 2048, 5, 400_000
@@ -46,3 +47,17 @@ for step in range(8):
     moved = group.rebalance() if step % 2 == 1 else None      # between steps: promote the cold ids the lookups hit, per pair
     print(f"step {step}: loss {loss.item():.4f}, ids {ids.numel()}, keys hot {sum(p.hot.size() for p in pairs)} / cold {sum(p.cold.size() for p in pairs)}"
           + (f", rebalanced: promoted {sum(m[0] for m in moved)}, demoted {sum(m[1] for m in moved)}" if moved else ""))
+
+# A sequence feature over the same pairs: a row per id (a behaviour history fed to attention), bf16 rows.  Forward is the one-launch find over both
+# tiers of every pair plus one creation launch, backward the same two grouped steps.
+history = DynamicEmbeddingCollection(group, optimizer="adagrad", lr=0.05, out_dtype=torch.bfloat16).to(dev)
+seq_len = 8
+scorer = torch.nn.Linear(dim, 1).to(dev).to(torch.bfloat16)
+seq_offsets = torch.arange(n_tables + 1, dtype=torch.int64, device=dev) * batch * seq_len      # segment j: the ids of pair j
+for step in range(4):
+    ids = (torch.rand(n_tables * batch * seq_len, device=dev) ** 3 * vocab).long()
+    rows = history(ids, seq_offsets)                                  # [n_tables * batch * seq_len, dim] bf16
+    loss = scorer(rows).float().view(n_tables, batch, seq_len).mean(dim=2).square().mean()
+    loss.backward()                                                   # the sparse update happens here; the scorer is not trained in this sketch
+    print(f"sequence step {step}: loss {loss.item():.5f}, rows {tuple(rows.shape)} {rows.dtype}, keys hot {sum(p.hot.size() for p in pairs)} / cold "
+          f"{sum(p.cold.size() for p in pairs)}")

@@ -413,6 +413,27 @@ int mee_group_find_pooled_tiered(mee_group* hot_group, mee_group* cold_group, co
 int mee_group_ensure_tiered(mee_group* hot_group, mee_group* cold_group, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets,
                             size_t bags_per_table, const uint8_t* d_found, const uint8_t* d_to_cold /* [n_tables], device; nullable: all hot */,
                             void* stream);
+/* The UNPOOLED lookups over the same two groups — a row per position of the jagged batch (d_offsets = n_tables + 1 member offsets in DEVICE memory,
+ * as mee_find_grouped; sequence features, whose model wants every id's row).  mee_group_find_tiered is, by definition and bit for bit, on every
+ * member's segment: mee_find on hot member j, then mee_find_missing on cold member j over the same buffers (with count flags the mee_find_counted
+ * forms) — TieredLookupTable.find — in ONE launch for the whole collection: a position is probed in its member's hot index, in the cold one only
+ * where a wave missed, the row comes from the plane that holds it, an absent or reserved key reads that member's HOT table's default row,
+ * d_found[i] (nullable: not written) = 1 iff either tier holds the key; positions outside [d_offsets[0], d_offsets[n_tables]) or at or past n are
+ * left alone, as mee_find_grouped leaves them.  d_out = [n, dim] fp32 or bf16 (every element rounded once).  flags = MEE_TIER_COUNT_COLD |
+ * MEE_TIER_COUNT_HOT as above.
+ * mee_group_find_or_insert_tiered is that lookup, flags included, followed by mee_find_or_insert_missing on the tier d_to_cold selects for the
+ * member (null: every member creates hot), in ONE more launch: two launches whatever the number of tables.  d_found (required) = present before the
+ * call; every position it leaves missing receives its key's initial row — the same row at every occurrence of a repeated new key, rounded for a
+ * bf16 d_out while the stored row is not — and TABLE_FULL / RESERVED_KEY go to the status word of the table that was asked to create.
+ * Both: no host synchronisation and no allocation, capturable; after mee_reserve on a member of either group the next call re-reads that table's
+ * planes (one stream synchronisation).  n == 0 succeeds and writes nothing.  MEE_ERR_INVALID_ARG before anything is launched or written: a null
+ * pointer, hot_group == cold_group, groups that differ in device, dim or number of tables, a member that is the same table in both, an unknown
+ * out_dtype / flag bit, a misaligned bf16 d_out, a count flag when a member of that tier has no counters; MEE_ERR_UNSUPPORTED: a bf16-row group. */
+int mee_group_find_tiered(mee_group* hot_group, mee_group* cold_group, const int64_t* d_keys, const uint64_t* d_offsets, size_t n,
+                          void* d_out, uint32_t out_dtype, uint8_t* d_found /* nullable: not written */, uint32_t flags, void* stream);
+int mee_group_find_or_insert_tiered(mee_group* hot_group, mee_group* cold_group, const int64_t* d_keys, const uint64_t* d_offsets, size_t n,
+                                    void* d_out, uint32_t out_dtype, uint8_t* d_found /* required: present before the call */,
+                                    const uint8_t* d_to_cold /* [n_tables], device; nullable: all hot */, uint32_t flags, void* stream);
 
 /* ---- typed output: the lookups above with fp32 OR bf16 result rows (SPEC.md §3 "Output type") --------------------------------
  * The models these tables feed run in bf16; a lookup that writes bf16 itself saves the cast in front of the first dense layer and half

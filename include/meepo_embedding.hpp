@@ -209,6 +209,14 @@ public:
     void ensure_tiered(Group& cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const uint8_t* d_found, const uint8_t* d_to_cold = nullptr, void* stream = nullptr) {
         check(mee_group_ensure_tiered(g_, cold.g_, d_keys, n, d_bag_offsets, bags_per_table, d_found, d_to_cold, stream));
     }
+    // the unpooled lookups over the same collection of pairs, a row per position of the jagged batch (mee_group_find_tiered: one launch;
+    // mee_group_find_or_insert_tiered: two, d_found required = present before the call)
+    void find_tiered(Group& cold, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, uint8_t* d_found = nullptr, uint32_t flags = 0, void* stream = nullptr) {
+        check(mee_group_find_tiered(g_, cold.g_, d_keys, d_offsets, n, d_out, out_dtype, d_found, flags, stream));
+    }
+    void find_or_insert_tiered(Group& cold, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, const uint8_t* d_to_cold = nullptr, uint32_t flags = 0, void* stream = nullptr) {
+        check(mee_group_find_or_insert_tiered(g_, cold.g_, d_keys, d_offsets, n, d_out, out_dtype, d_found, d_to_cold, flags, stream));
+    }
 private:
     mee_group* g_ = nullptr;
 };

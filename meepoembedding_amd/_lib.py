@@ -142,6 +142,9 @@ PROTOTYPES = {
     # a group of hot/cold pairs (tiered.py, TieredTableGroup): hot group, cold group, ...
     "mee_group_find_pooled_tiered": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, C.c_int, _u32, _vp]),
     "mee_group_ensure_tiered": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    # ... the unpooled forms: keys, member offsets, n, out, out_dtype, found, [to_cold,] flags, stream
+    "mee_group_find_tiered": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _u32, _vp, _u32, _vp]),
+    "mee_group_find_or_insert_tiered": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _u32, _vp, _vp, _u32, _vp]),
     "mee_pooled_weighted_backward": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "mee_group_find_pooled_weighted": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "mee_group_pooled_weighted_backward": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),

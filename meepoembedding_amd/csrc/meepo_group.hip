@@ -151,6 +151,155 @@ __global__ __launch_bounds__(256) void find_grouped_kernel(const GroupDesc* __re
     }
 }
 
+// The row gather and the stores of one wave step of the grouped finds over fp32 rows, for a step whose rows may come from either plane of a pair: `src[r]` is
+// the first element group of position r's row in the plane that holds it (any valid address where !hit[r]: it is not read), an absent key reads
+// defv[r].  Straight-line per round, the R x C loads back to back before the first store, as in find_grouped_kernel.
+template <int DIM4, int R, bool STREAM_OUT, bool BF16>
+__device__ __forceinline__ void grouped_rows_out(const float4* const (&src)[R], const bool (&hit)[R], const float (&defv)[R], const bool (&inb)[R],
+                                                 float4* __restrict__ out, uint64_t base, int tile, int tl, uint32_t dim4) {
+    if constexpr (DIM4 != 0) {
+        constexpr int C = DIM4 / 16;
+        float4 row[R][C];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int c = 0; c < C; ++c) row[r][c] = hit[r] ? src[r][c * 16 + tl] : make_float4(defv[r], defv[r], defv[r], defv[r]);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const uint64_t i = base + r * 4 + tile;
+            if (inb[r])
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    if constexpr (BF16) {
+                        store_bf16x4<!STREAM_OUT>(out, i * DIM4 + c * 16 + tl, row[r][c]);
+                    } else if constexpr (STREAM_OUT) {
+                        const f32x4 v = {row[r][c].x, row[r][c].y, row[r][c].z, row[r][c].w};
+                        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out) + i * DIM4 + c * 16 + tl);
+                    } else {
+                        out[i * DIM4 + c * 16 + tl] = row[r][c];
+                    }
+                }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const uint64_t i = base + r * 4 + tile;
+            if (inb[r])
+                for (uint32_t c = tl; c < dim4; c += 16) {
+                    const float4 v = hit[r] ? src[r][c] : make_float4(defv[r], defv[r], defv[r], defv[r]);
+                    if constexpr (BF16) store_bf16x4<true>(out, i * dim4 + c, v); else out[i * dim4 + c] = v;
+                }
+        }
+    }
+}
+
+// find_grouped_kernel over a GROUP of hot/cold pairs (mee_group_find_tiered): `hot` holds the HOT member of every pair, `cold` the cold one, a key lives
+// in exactly one of them.  Same tiles, same segment search (offsets stride 1), same first probe — member j's hot index, the R bucket lines requested
+// back to back.  Then ONE wave-uniform decision: a wave step in which no active position missed runs find_grouped_kernel's row gather and stores and
+// never looks at a cold descriptor (the steady state of a well-placed collection).  Otherwise the cold descriptor of every missed position's member
+// is loaded — inside this branch only — and the cold index probed by all 64 lanes in convergent control flow, tiles without a miss pass act = false;
+// each row is then loaded ONCE, from the plane that holds it (the address is selected, not the data; slot 0 of a cold plane where neither tier
+// holds the key: a valid address that is not read).  The cold plane may be pinned host memory: plain loads.  An absent or reserved key reads the HOT
+// member's defv; found[i] (nullable) = either tier holds the key; positions outside the segments or at or past n are left alone, as there.
+// count (kTierCountCold | kTierCountHot, the launch's bits — never a member's pointer — so every wave-uniform branch is on a fact of the launch): one
+// atomicAdd per found position by the tile's first lane on that member's counter, as find_kernel (kFindCountHits) and find_missing_kernel do it.
+template <int DIM4, int R, bool STREAM_OUT, bool BF16 = false>
+__global__ __launch_bounds__(256) void find_grouped_tiered_kernel(const GroupDesc* __restrict__ hot, const GroupInit* __restrict__ hot_init,
+                                                                  const GroupDesc* __restrict__ cold, const GroupInit* __restrict__ cold_init,
+                                                                  uint32_t n_tables, const uint64_t* __restrict__ offsets,
+                                                                  const int64_t* __restrict__ keys, uint64_t n, float4* __restrict__ out,
+                                                                  uint8_t* __restrict__ found, uint32_t dim4_rt, uint32_t count) {
+    __shared__ uint64_t loff[kMaxGroupTables + 1];
+    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) loff[j] = offsets[j];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    const uint32_t dim4 = DIM4 ? DIM4 : dim4_rt;
+    for (uint64_t base = wave * 4 * R; base < n; base += n_waves * 4 * R) {
+        int64_t key[R], slot[R], kb[R];
+        uint64_t b[R];
+        const int64_t* tkeys[R];
+        uint64_t nb[R];
+        const float4* src[R];   // first the hot plane, then the row
+        float defv[R];
+        uint32_t member[R];
+        bool inb[R], act[R], hit[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const uint64_t i = base + r * 4 + tile;
+            uint32_t lo = 0, hi = n_tables;   // as find_grouped_kernel: the last j with loff[j] <= i
+            inb[r] = i < n && i >= loff[0] && i < loff[n_tables];
+            while (hi - lo > 1) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (loff[mid] <= i) lo = mid; else hi = mid;
+            }
+            member[r] = inb[r] ? lo : 0;
+            const GroupDesc d = hot[member[r]];
+            tkeys[r] = d.tkeys; nb[r] = d.nb; src[r] = d.values; defv[r] = d.defv;
+            key[r] = inb[r] ? keys[i] : kEmpty;
+            act[r] = inb[r] && !reserved_key(key[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            b[r] = bucket_of(key[r], nb[r]);
+            kb[r] = act[r] ? tkeys[r][b[r] * kW + tl] : kEmpty;
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) slot[r] = tile_probe(tkeys[r], nb[r], key[r], act[r], b[r], kb[r], tile, tl);
+        bool missed = false;
+#pragma unroll
+        for (int r = 0; r < R; ++r) missed = missed || (act[r] && slot[r] < 0);
+        if (!__any(missed)) {   // wave-uniform: nothing for the cold tier
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                hit[r] = slot[r] >= 0;
+                src[r] += (uint64_t)(hit[r] ? slot[r] : 0) * dim4;
+            }
+            grouped_rows_out<DIM4, R, STREAM_OUT, BF16>(src, hit, defv, inb, out, base, tile, tl, dim4);
+        } else {
+            int64_t cslot[R];
+            const float4* cvalues[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                act[r] = act[r] && slot[r] < 0;   // from here on: the positions the cold index is asked about
+                const GroupDesc* c = cold + (act[r] ? member[r] : 0);
+                tkeys[r] = c->tkeys; nb[r] = c->nb; cvalues[r] = c->values;
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                b[r] = bucket_of(key[r], nb[r]);
+                kb[r] = act[r] ? tkeys[r][b[r] * kW + tl] : kEmpty;
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) cslot[r] = tile_probe(tkeys[r], nb[r], key[r], act[r], b[r], kb[r], tile, tl);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                hit[r] = slot[r] >= 0 || cslot[r] >= 0;
+                src[r] = slot[r] >= 0 ? src[r] + (uint64_t)slot[r] * dim4 : cvalues[r] + (uint64_t)(cslot[r] >= 0 ? cslot[r] : 0) * dim4;
+            }
+            grouped_rows_out<DIM4, R, STREAM_OUT, BF16>(src, hit, defv, inb, out, base, tile, tl, dim4);
+            if (count & kTierCountCold) {   // wave-uniform
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    if (cslot[r] >= 0 && tl == 0) atomicAdd(&cold_init[member[r]].hits[cslot[r]], 1u);
+            }
+        }
+        if (found) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const uint64_t i = base + r * 4 + tile;
+                if (inb[r] && tl == 0) found[i] = hit[r];
+            }
+        }
+        if (count & kTierCountHot) {   // wave-uniform (sampled calls)
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (slot[r] >= 0 && tl == 0) atomicAdd(&hot_init[member[r]].hits[slot[r]], 1u);
+        }
+    }
+}
+
 // Second pass of a grouped find_or_insert: every position the find pass left missing claims (or finds, when a duplicate
 // got there first) its key's slot in its member table; the tile whose CAS created the key writes the initial row, the
 // initial optimizer state and a zero hit counter, and every such tile writes that same initial row — a function of the
@@ -254,6 +403,66 @@ __global__ __launch_bounds__(256) void ensure_tiered_grouped_kernel(const GroupD
                     }
                 }
                 if (in.hits && tl == 0) in.hits[slot] = 0;
+            }
+            if (full && tl == 0) atomicOr(in.status, (uint32_t)MEE_STATUS_TABLE_FULL);
+        }
+    }
+}
+
+// ensure_tiered_grouped_kernel's sibling for the unpooled find_or_insert over a group of pairs (mee_group_find_or_insert_tiered), which returns a row per
+// position: what ensure_grouped_kernel<BF16> does, in the tier to_cold selects.  Every tile that obtained a slot for a position the mask left missing —
+// the one whose CAS created the key and one that met a duplicate's creation alike — writes initial_row4(key, …) of the table it created in into
+// out[i] (BF16: that copy is rounded, the stored row is not); the creator also writes the table's row, state and a zero hit counter.  Member offsets
+// are the n_tables + 1 jagged offsets of the lookup (cut at n: no key past the array is read).  A sibling, not an instance: the kernel above keeps
+// its name, its arguments and its machine code.
+template <bool BF16>
+__global__ __launch_bounds__(256) void ensure_tiered_grouped_rows_kernel(const GroupDesc* __restrict__ hot_desc, const GroupInit* __restrict__ hot_init,
+                                                                         const GroupDesc* __restrict__ cold_desc, const GroupInit* __restrict__ cold_init,
+                                                                         uint32_t n_tables, const uint64_t* __restrict__ offsets,
+                                                                         const int64_t* __restrict__ keys, uint64_t n, const uint8_t* __restrict__ found,
+                                                                         const uint8_t* __restrict__ to_cold, uint32_t dim4, float4* __restrict__ out) {
+    __shared__ uint64_t loff[kMaxGroupTables + 1];
+    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) {
+        const uint64_t o = offsets[j];
+        loff[j] = o < n ? o : n;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t base = wave * 4; base < n; base += n_waves * 4) {
+        const uint64_t i = base + tile;
+        bool act = i < n && i >= loff[0] && i < loff[n_tables] && found[i] == 0;
+        const int64_t key = act ? keys[i] : kEmpty;
+        const bool tomb = act && key == kReclaimed;   // a reserved key in the batch: flagged like mee_find_or_insert_missing does (EMPTY = padding, silent)
+        act = act && !reserved_key(key);
+        if (!__any(act || tomb)) continue;  // wave-uniform: nothing missing here (the steady state of a trained vocabulary)
+        uint32_t lo = 0, hi = n_tables;     // the last member whose segment starts at or before i (always inside [0, n_tables))
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (loff[mid] <= i) lo = mid; else hi = mid;
+        }
+        const bool goes_cold = to_cold && (act || tomb) && to_cold[lo] != 0;
+        const GroupDesc d = goes_cold ? cold_desc[lo] : hot_desc[lo];
+        const GroupInit in = goes_cold ? cold_init[lo] : hot_init[lo];
+        if (tomb && tl == 0) atomicOr(in.status, (uint32_t)MEE_STATUS_RESERVED_KEY);
+        bool is_new, full;
+        const int64_t slot = tile_locate<true, true>(const_cast<int64_t*>(d.tkeys), d.nb, key, act, tile, tl, is_new, full);
+        if (act) {
+            if (slot >= 0) {
+                for (uint32_t c = tl; c < dim4; c += 16) {
+                    const float4 row = initial_row4(key, c * 4, in.initializer, in.init_scale, in.init_seed, d.defv);
+                    if constexpr (BF16) store_bf16x4<true>(out, i * dim4 + c, row); else out[i * dim4 + c] = row;
+                    if (is_new) {
+                        d.values[(uint64_t)slot * dim4 + c] = row;
+                        if (in.optimizer == MEE_OPT_ADAGRAD) d.s1[(uint64_t)slot * dim4 + c] = make_float4(in.init_acc, in.init_acc, in.init_acc, in.init_acc);
+                        if (in.optimizer == MEE_OPT_ADAM) {
+                            d.s1[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                            d.s2[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                        }
+                    }
+                }
+                if (is_new && in.hits && tl == 0) in.hits[slot] = 0;
             }
             if (full && tl == 0) atomicOr(in.status, (uint32_t)MEE_STATUS_TABLE_FULL);
         }
@@ -461,7 +670,55 @@ static int group_find_or_insert_common(mee_group* g, const int64_t* d_keys, cons
     return MEE_OK;
 }
 
+// the one launch of the unpooled lookup over a group of pairs; the store policy is launch_find_grouped's, on the bytes really written
+static int launch_find_grouped_tiered(mee_group* hot, mee_group* cold, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype,
+                                      uint8_t* d_found, uint32_t count, hipStream_t st) {
+    const bool bf16 = out_dtype == MEE_DTYPE_BF16;
+    const bool stream_out = (uint64_t)n * hot->dim * (bf16 ? 2 : 4) > kCachedOutputBytes;
+    with_row_shape(hot->dim4, [&](auto d4) { with_flag(stream_out, [&](auto so) { with_flag(bf16, [&](auto b16) {
+        constexpr int R = RowShape<d4>::rows_per_tile;
+        find_grouped_tiered_kernel<d4, R, so, b16><<<grid_for(n, 16 * R, 8192), 256, 0, st>>>(hot->d_desc, hot->d_init, cold->d_desc, cold->d_init, hot->n_tables, d_offsets, d_keys, n,
+                                                                                             (float4*)d_out, d_found, hot->dim4, count);
+    }); }); });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+// creates: mee_group_find_or_insert_tiered (d_found required, d_to_cold read); otherwise mee_group_find_tiered
+static int group_find_tiered_common(mee_group* hot, mee_group* cold, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype,
+                                    uint8_t* d_found, bool creates, const uint8_t* d_to_cold, uint32_t flags, void* stream, const char* name) {
+    if (!hot || !cold || !d_offsets || (n && (!d_keys || !d_out || (creates && !d_found)))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (int rc = tiered_groups_check(hot, cold, flags, name)) return rc;
+    if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
+    if (n == 0) return MEE_OK;
+    if (int rc = group_refresh(hot, stream)) return rc;
+    if (int rc = group_refresh(cold, stream)) return rc;
+    DeviceGuard guard(hot->device);
+    hipStream_t st = (hipStream_t)stream;
+    // 1) the lookup over both tiers serves every stored key and yields the present-before mask
+    if (int rc = launch_find_grouped_tiered(hot, cold, d_keys, d_offsets, n, d_out, out_dtype, d_found, flags, st)) return rc;
+    if (!creates) return MEE_OK;
+    // 2) missing positions create their key in the tier their member was told (one creator per distinct key: the CAS decides) and return its initial row
+    with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto b16) {
+        ensure_tiered_grouped_rows_kernel<b16><<<grid_for(n, 16, 8192), 256, 0, st>>>(hot->d_desc, hot->d_init, cold->d_desc, cold->d_init, hot->n_tables, d_offsets, d_keys, n, d_found,
+                                                                                     d_to_cold, hot->dim4, (float4*)d_out);
+    });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
 extern "C" {
+
+int mee_group_find_tiered(mee_group* hot, mee_group* cold, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
+                          uint32_t flags, void* stream) {
+    MEE_RANGE("mee_group_find_tiered");
+    return group_find_tiered_common(hot, cold, d_keys, d_offsets, n, d_out, out_dtype, d_found, false, nullptr, flags, stream, "mee_group_find_tiered");
+}
+int mee_group_find_or_insert_tiered(mee_group* hot, mee_group* cold, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype,
+                                    uint8_t* d_found, const uint8_t* d_to_cold, uint32_t flags, void* stream) {
+    MEE_RANGE("mee_group_find_or_insert_tiered");
+    return group_find_tiered_common(hot, cold, d_keys, d_offsets, n, d_out, out_dtype, d_found, true, d_to_cold, flags, stream, "mee_group_find_or_insert_tiered");
+}
 
 int mee_find_grouped(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, float* d_out, uint8_t* d_found,
                      void* stream) {

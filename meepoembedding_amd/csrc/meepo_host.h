@@ -169,7 +169,7 @@ int group_locate(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets,
 // null one (defined next to refuse_narrow_rows in meepo_table.hip)
 int refuse_bf16_group(const mee_group* g, const char* op, const char* what = nullptr);
 #define MEE_FP32_GROUP_ONLY(g, ...) do { if (int rc_ = ::mee::refuse_bf16_group((g), __VA_ARGS__)) return rc_; } while (0)
-// what the operators over a GROUP of hot/cold pairs (mee_group_find_pooled_tiered, mee_group_ensure_tiered) check about their two groups before anything
+// what the operators over a GROUP of hot/cold pairs (mee_group_find_pooled_tiered, mee_group_ensure_tiered, mee_group_find_tiered, mee_group_find_or_insert_tiered) check about their two groups before anything
 // is launched or written: fp32 rows (MEE_ERR_UNSUPPORTED), two different groups of one device, dim and number of tables, no table that is member j of
 // both, only known count bits (MEE_TIER_COUNT_*) and the counters they need in EVERY member of that tier (MEE_ERR_INVALID_ARG).  Host only;
 // defined in meepo_group.hip.

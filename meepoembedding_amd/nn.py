@@ -440,7 +440,8 @@ class DynamicEmbeddingCollection(torch.nn.Module, _SparseOptimizerSettings):
     n_tables + 1 segment bounds (int64, on the device) -> fp32 [len(keys), dim].  Forward is ONE grouped find_or_insert
     (find in eval mode), backward ONE grouped optimizer step, whatever the number of tables (TableGroup in table.py).
     out_dtype=torch.bfloat16: the lookup itself writes bf16 rows (the tables stay fp32; a bf16 grad is widened, which is exact).
-    `group` may be a ShardedTableGroup (sharded.py): the same two ops, then ONE exchange per lookup and per step over the process group."""
+    `group` may be a ShardedTableGroup (sharded.py): the same two ops, then ONE exchange per lookup and per step over the process group; or a
+    TieredTableGroup (tiered.py), a collection of hot/cold pairs: forward is one launch (two in training), backward two grouped steps."""
 
     def __init__(self, group, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
                  out_dtype: torch.dtype = torch.float32):

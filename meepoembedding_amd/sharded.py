@@ -347,6 +347,9 @@ class ShardedTableGroup(_Exchange):
         if getattr(local_group, "mixed_dims", False):
             raise ValueError(f"{type(local_group).__name__} has members of different dims: a sharded group exchanges rows of one width "
                              "(one ShardedTableGroup per width, each over a TableGroup)")
+        if hasattr(local_group, "cold_group"):   # a TieredTableGroup: before its unpooled operators existed every sharded operator refused it (_check)
+            raise ValueError(f"{type(local_group).__name__} is a group of hot/cold pairs: a sharded group over tiers is not offered "
+                             "(a ShardedLookupTable over a TieredLookupTable shards one pair)")
         refuse_narrow_rows("ShardedTableGroup", local_group)
         self.local = self.local_group = local_group
         self.dim = local_group.dim

@@ -358,6 +358,11 @@ class TieredTableGroup:
     over the pairs pays one launch per table.  Underneath: a TableGroup over the hot tables and one over the cold tables (`hot_group`, `cold_group`,
     both with max_apply_batch), so the step is two grouped steps whatever the number of tables.
 
+    The same collection without pooling — a row per id, for sequence features: find / find_or_insert / apply_adagrad / apply_adam over a jagged batch
+    (keys, offsets[n_tables + 1] on the device) with TableGroup's signatures, each by definition the pair's operator per member on its segment: one
+    launch (mee_group_find_tiered), two (mee_group_find_or_insert_tiered) and two grouped steps.  nn.DynamicEmbeddingCollection trains over it.
+    Weighted bags, located rows and a jagged bag map are not offered over tiers.
+
     The placement policy is on when EVERY pair has it (both tiers created with track_hits=True); the launch then counts cold hits always and hot
     hits on every sample_every-th call, as a pair does.  Some pairs with it and some without is a ValueError.
 
@@ -366,6 +371,7 @@ class TieredTableGroup:
     pools_with_insert = True            # nn.DynamicEmbeddingBag: unseen ids are created inside find_pooled(insert_missing=True)
     weighted_bags = False               # no per_sample_weights over the tiers
     supports_pooled_out_dtype = True    # find_pooled can write bf16 bag rows
+    supports_out_dtype = True           # ... and find / find_or_insert bf16 rows (nn.DynamicEmbeddingCollection(out_dtype=torch.bfloat16))
 
     def __init__(self, pairs, max_apply_batch: int = 0, sample_every: int = 8):
         self.tables = list(pairs)
@@ -480,13 +486,119 @@ class TieredTableGroup:
                 self._d_goes_cold.copy_(torch.tensor(goes_cold, dtype=torch.uint8))
                 self._goes_cold = goes_cold
             _lib.check(L.mee_group_ensure_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, found.data_ptr(), self._d_goes_cold.data_ptr(), s))
-        flags = 0
-        if self.policy:
-            self._calls += 1
-            flags = _lib.TIER_COUNT_COLD | (_lib.TIER_COUNT_HOT if self._calls % self.sample_every == 0 else 0)
         _lib.check(L.mee_group_find_pooled_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt,
-                                                  None if creates else found.data_ptr(), m, flags, s))
+                                                  None if creates else found.data_ptr(), m, self._count_flags(), s))
         return out, found
+
+    # -- the unpooled collection: a row per position of the jagged batch (keys = the members' id batches concatenated, offsets = n_tables + 1 bounds) ----
+    def _segments(self, offsets: torch.Tensor, n: int):
+        """(non-native path) -> [(key begin, key end)] per member; offsets past n are cut at n"""
+        if offsets.dim() != 1 or offsets.numel() != len(self.tables) + 1:
+            raise ValueError(f"offsets must hold n_tables + 1 = {len(self.tables) + 1} entries (got {tuple(offsets.shape)})")
+        cut = offsets.to(torch.int64).clamp(0, n).tolist()
+        return [(cut[j], max(cut[j], cut[j + 1])) for j in range(len(self.tables))]
+
+    def _count_flags(self) -> int:
+        """the count bits of one lookup of the model's: cold hits always, hot hits on every sample_every-th call (the counter find_pooled shares)"""
+        if not self.policy:
+            return 0
+        from . import _lib
+        self._calls += 1
+        return _lib.TIER_COUNT_COLD | (_lib.TIER_COUNT_HOT if self._calls % self.sample_every == 0 else 0)
+
+    def _find_loop(self, keys, offsets, out, found, out_dtype, insert: bool):
+        """pairs that are not native tables: member j's find / find_or_insert on its slice; the fp32 rows are rounded once for bf16"""
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16 (got {out_dtype})")
+        flat = keys.contiguous().view(-1)
+        n = flat.numel()
+        if out is None:
+            out = torch.zeros((n, self.dim), dtype=out_dtype, device=flat.device)
+        if found is None:
+            found = torch.zeros(n, dtype=torch.uint8, device=flat.device)
+        for pair, (s, e) in zip(self.tables, self._segments(offsets, n)):
+            if e > s:
+                rows, fnd = pair.find_or_insert(flat[s:e]) if insert else pair.find(flat[s:e])
+                out[s:e] = rows.to(out.dtype)
+                found[s:e] = fnd
+        return out, found
+
+    def _lookup_args(self, keys, offsets, out, found, out_dtype):
+        from .table import _out_dtype
+        dt = _out_dtype(out_dtype, out)
+        self.hot_group._check_offsets(offsets)
+        k = self.tables[0].hot._keys(keys) if keys.numel() else keys
+        n = k.numel()
+        if out is None:
+            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
+        if found is None:
+            found = torch.empty(n, dtype=torch.uint8, device=self.device)
+        return dt, k, n, out, found
+
+    def find(self, keys: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
+             out_dtype: torch.dtype = torch.float32):
+        """TieredLookupTable.find of every pair on its segment, in ONE launch (mee_group_find_tiered) -> (rows [n, dim], found [n]).  An absent key
+        reads its member's HOT table's default row; positions outside the segments are left alone, as TableGroup.find leaves them.  With the policy
+        on the launch feeds the members' hit counters (cold hits always, hot hits on every sample_every-th call).
+        out_dtype=torch.bfloat16: every element rounded once."""
+        if not self._native:
+            return self._find_loop(keys, offsets, out, found, out_dtype, insert=False)
+        from . import _lib
+        from .table import _stream_ptr
+        dt, k, n, out, found = self._lookup_args(keys, offsets, out, found, out_dtype)
+        _lib.check(_lib.lib().mee_group_find_tiered(self.hot_group._h, self.cold_group._h, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), dt,
+                                                    found.data_ptr(), self._count_flags(), _stream_ptr(self.device)))
+        return out, found
+
+    def find_or_insert(self, keys: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
+                       out_dtype: torch.dtype = torch.float32):
+        """TieredLookupTable.find_or_insert of every pair on its segment, in TWO launches whatever the number of tables
+        (mee_group_find_or_insert_tiered): find, then one creation launch that also returns the created keys' initial rows.  found = present before
+        the call.  Member j's new keys go to its hot table while pairs[j]._room_for(n) holds, else to its cold table; n is the size of the WHOLE
+        batch, as in find_pooled(insert_missing=True): conservative, a member goes cold earlier than the pair on its own slice would, never later."""
+        if not self._native:
+            return self._find_loop(keys, offsets, out, found, out_dtype, insert=True)
+        from . import _lib
+        from .table import _stream_ptr
+        dt, k, n, out, found = self._lookup_args(keys, offsets, out, found, out_dtype)
+        if n:
+            goes_cold = []
+            for p in self.tables:
+                room = p._room_for(n)
+                if room:
+                    p._hot_keys_ub += n
+                goes_cold.append(not room)
+            if goes_cold != self._goes_cold:
+                self._d_goes_cold.copy_(torch.tensor(goes_cold, dtype=torch.uint8))
+                self._goes_cold = goes_cold
+        _lib.check(_lib.lib().mee_group_find_or_insert_tiered(self.hot_group._h, self.cold_group._h, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), dt,
+                                                              found.data_ptr(), self._d_goes_cold.data_ptr(), self._count_flags(), _stream_ptr(self.device)))
+        return out, found
+
+    def apply_adagrad(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10) -> None:
+        """The pair's sparse-Adagrad step per member over the jagged batch, as TWO grouped steps — the hot group's, then the cold group's: a key lives in
+        one tier and a group ignores the keys its member does not hold — then every pair's rebalance_every bookkeeping."""
+        if not self._native:
+            flat = keys.contiguous().view(-1)
+            for pair, (s, e) in zip(self.tables, self._segments(offsets, flat.numel())):
+                pair.apply_adagrad(flat[s:e], grads[s:e], lr, eps)
+            return
+        for g in (self.hot_group, self.cold_group):
+            g.apply_adagrad(keys, offsets, grads, lr, eps)
+        for p in self.tables:
+            p._after_optimizer_step()
+
+    def apply_adam(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999,
+                   eps: float = 1e-8, step: int = 1) -> None:
+        if not self._native:
+            flat = keys.contiguous().view(-1)
+            for pair, (s, e) in zip(self.tables, self._segments(offsets, flat.numel())):
+                pair.apply_adam(flat[s:e], grads[s:e], lr, beta1, beta2, eps, step)
+            return
+        for g in (self.hot_group, self.cold_group):
+            g.apply_adam(keys, offsets, grads, lr, beta1, beta2, eps, step)
+        for p in self.tables:
+            p._after_optimizer_step()
 
     def apply_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, bag_grads: torch.Tensor, bag_of_position: torch.Tensor,
                      optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1,

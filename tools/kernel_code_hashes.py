@@ -34,7 +34,7 @@ def hashes(co):
         if m:
             name = m.group(1)
             kernels[name] = []
-        elif name and line.strip():
+        elif name and line.strip() and line.strip() != "...":   # "...": the padding up to the next kernel's alignment, which the last kernel of a code object lacks
             kernels[name].append(re.sub(r"\s*//.*$", "", line).strip())
     names = list(kernels)
     demangled = subprocess.run(["c++filt"], input="\n".join(names), check=True, capture_output=True, text=True).stdout.splitlines()
