@@ -413,6 +413,22 @@ int mee_group_find_pooled_tiered(mee_group* hot_group, mee_group* cold_group, co
 int mee_group_ensure_tiered(mee_group* hot_group, mee_group* cold_group, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets,
                             size_t bags_per_table, const uint8_t* d_found, const uint8_t* d_to_cold /* [n_tables], device; nullable: all hot */,
                             void* stream);
+/* mee_group_find_pooled_tiered where the members' bag counts DIFFER (the owner's side of a sharded group of pairs: the runs that arrive per member
+ * change from member to member and from step to step).  mee_group_find_pooled_tiered_jagged is mee_group_find_pooled_tiered except for the bag ->
+ * member map, which is mee_group_find_pooled_jagged's: bag b belongs to the member j with d_member_bags[j] <= b < d_member_bags[j + 1] (n_tables + 1
+ * non-decreasing uint64 in DEVICE memory; a member may have no bags; [0, B, 2B, …] gives mee_group_find_pooled_tiered(bags_per_table = B,
+ * MEE_DTYPE_F32) bit for bit).  A bag below d_member_bags[0] or at or beyond d_member_bags[n_tables] is an empty bag: a row of zeros, nothing probed,
+ * the d_found bytes of its positions not written.  On every other bag the result is, bit for bit, mee_find_pooled_tiered(hot member j, cold member
+ * j) on that bag: the hot index first, the cold one only where a wave missed, the row from the plane that holds it, fp32 sums in position order
+ * without fma, MEAN's division by (float)length, that member's HOT default row for an absent or reserved key, offsets past n cut at n, a decreasing
+ * pair an empty bag.  The map is caller data and is never trusted: whatever it holds, the member used stays inside the group.  d_out [n_bags, dim]
+ * fp32 only (the partial rows of a sharded bag travel as fp32); d_found nullable: not written.  flags = MEE_TIER_COUNT_*, as above.  One launch,
+ * no host synchronisation, no allocation, capturable.  n_bags == 0 succeeds and writes nothing.  MEE_ERR_INVALID_ARG before anything is launched: a
+ * null pointer, an unknown mode, and what mee_group_find_pooled_tiered refuses about its two groups and its flags; MEE_ERR_UNSUPPORTED: a bf16-row
+ * group. */
+int mee_group_find_pooled_tiered_jagged(mee_group* hot_group, mee_group* cold_group, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets,
+                                        size_t n_bags, const uint64_t* d_member_bags /* [n_tables + 1], device */, float* d_out,
+                                        uint8_t* d_found /* nullable: not written */, int mode, uint32_t flags, void* stream);
 /* The UNPOOLED lookups over the same two groups — a row per position of the jagged batch (d_offsets = n_tables + 1 member offsets in DEVICE memory,
  * as mee_find_grouped; sequence features, whose model wants every id's row).  mee_group_find_tiered is, by definition and bit for bit, on every
  * member's segment: mee_find on hot member j, then mee_find_missing on cold member j over the same buffers (with count flags the mee_find_counted

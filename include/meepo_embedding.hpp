@@ -206,6 +206,10 @@ public:
     void find_pooled_tiered(Group& cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, uint8_t* d_found = nullptr, int mode = MEE_POOL_SUM, uint32_t flags = 0, void* stream = nullptr) {
         check(mee_group_find_pooled_tiered(g_, cold.g_, d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, d_found, mode, flags, stream));
     }
+    // ... with the members' bag counts read from d_member_bags [n_tables + 1] on the device (mee_group_find_pooled_tiered_jagged; fp32 out)
+    void find_pooled_tiered_jagged(Group& cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const uint64_t* d_member_bags, float* d_out, uint8_t* d_found = nullptr, int mode = MEE_POOL_SUM, uint32_t flags = 0, void* stream = nullptr) {
+        check(mee_group_find_pooled_tiered_jagged(g_, cold.g_, d_keys, n, d_bag_offsets, n_bags, d_member_bags, d_out, d_found, mode, flags, stream));
+    }
     void ensure_tiered(Group& cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const uint8_t* d_found, const uint8_t* d_to_cold = nullptr, void* stream = nullptr) {
         check(mee_group_ensure_tiered(g_, cold.g_, d_keys, n, d_bag_offsets, bags_per_table, d_found, d_to_cold, stream));
     }

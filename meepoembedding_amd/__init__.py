@@ -10,4 +10,11 @@ from .table import LookupTable, MixedTableGroup, Router, TableGroup, hash_batch,
 from .tiered import TieredLookupTable, TieredTableGroup
 
 __all__ = ["LookupTable", "Router", "TableGroup", "MixedTableGroup", "TieredLookupTable", "TieredTableGroup", "mixed_layout", "hash_batch", "MeepoError", "OPT_NONE", "OPT_ADAGRAD", "OPT_ADAM",
-           "INIT_CONSTANT", "INIT_UNIFORM", "STATUS_TABLE_FULL", "STATUS_RESERVED_KEY", "EMPTY_KEY", "RECLAIMED_KEY"]
+           "INIT_CONSTANT", "INIT_UNIFORM", "STATUS_TABLE_FULL", "STATUS_RESERVED_KEY", "EMPTY_KEY", "RECLAIMED_KEY", "ShardedTieredTableGroup"]
+
+
+def __getattr__(name):
+    if name == "ShardedTieredTableGroup":   # sharded.py imports torch.distributed: only when the class is asked for
+        from .sharded import ShardedTieredTableGroup
+        return ShardedTieredTableGroup
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -141,6 +141,8 @@ PROTOTYPES = {
     "mee_find_pooled_tiered": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, C.c_int, _u32, _vp]),   # a hot/cold pair (tiered.py)
     # a group of hot/cold pairs (tiered.py, TieredTableGroup): hot group, cold group, ...
     "mee_group_find_pooled_tiered": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, C.c_int, _u32, _vp]),
+    # ... with a jagged bag -> member map: keys, n, bag offsets, n_bags, member_bags, out (fp32), found, mode, flags, stream
+    "mee_group_find_pooled_tiered_jagged": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, C.c_int, _u32, _vp]),
     "mee_group_ensure_tiered": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     # ... the unpooled forms: keys, member offsets, n, out, out_dtype, found, [to_cold,] flags, stream
     "mee_group_find_tiered": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _u32, _vp, _u32, _vp]),

@@ -357,7 +357,9 @@ __device__ __forceinline__ bool jagged_member(const uint64_t* __restrict__ membe
 // members, `tier` is a GroupTier — the cold members' descriptors, both groups' GroupInit (for the hit counters) and the launch's count bits.
 // Bag b's hot AND cold table are member b / bags_per_table's: table_of fills in both, per tile in the short phase of a four-bags-per-wave
 // step (bags_per_table need not be a multiple of 4: one wave may serve two members) and again for bag q in the long phase.  Both launch
-// shapes go through pooled_bags; a member's counters are read only under the launch's count bit.
+// shapes go through pooled_bags; a member's counters are read only under the launch's count bit.  With JAGGED as well
+// (mee_group_find_pooled_tiered_jagged: the owner's side of a sharded group of pairs) the member is jagged_member's instead of b / bags_per_table
+// and a bag outside the map is empty; fp32 out only.
 // BROWS (one bf16-row table, or with GROUPED a bf16-row group — every member's plane, JAGGED included; unweighted: SPEC.md §3 "Row
 // storage type"): the value planes hold bf16 rows.  One storage type per group, so this is a property of the launch, never a per-member
 // branch in the fetch.
@@ -379,7 +381,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                                                           int64_t handle_tag = 0, const uint64_t* __restrict__ member_bags = nullptr,
                                                           uint32_t n_members = 0, std::conditional_t<GROUPED && TIERED, GroupTier, TierArgs> tier = {}) {
     static_assert(!JAGGED || (GROUPED && !WEIGHTED && !BF16), "the jagged map is the group's plain fp32 lookup");
-    static_assert(!TIERED || (!WEIGHTED && !JAGGED), "the tiered form is the plain sum / mean of one pair or of a group of pairs");
+    static_assert(!TIERED || (!WEIGHTED && (!JAGGED || GROUPED)), "the tiered form is the plain sum / mean of one pair or of a group of pairs (the group's also with a jagged map)");
     static_assert(!BROWS || (!WEIGHTED && !TIERED), "bf16 rows: the plain sum / mean of one table or of a bf16-row group (jagged map included)");
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -404,12 +406,15 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
     for (uint64_t b0 = wave * BPW; b0 < n_bags; b0 += n_waves * BPW) {
         if constexpr (GROUPED && TIERED) {
             auto pair_of = [&](uint64_t b, PooledTable& t, TierArgs& cold) {   // the hot and the cold table of bag b's member
-                const uint64_t member = b / bags_per_table;
+                uint64_t member;
+                bool in_map = true;
+                if constexpr (JAGGED) in_map = jagged_member(member_bags, n_members, b, member);   // (outside the map: an empty bag, the member still inside the group)
+                else member = b / bags_per_table;
                 t = pooled_table(desc[member], member, kGroupSlotBits);
                 const GroupDesc c = tier.cold_desc[member];
                 cold = TierArgs{c.tkeys, c.values, c.nb, (tier.count & kTierCountHot) ? tier.hot_init[member].hits : nullptr,
                                 (tier.count & kTierCountCold) ? tier.cold_init[member].hits : nullptr};
-                return true;
+                return in_map;
             };
             pooled_bags<DIM4, U, BPW, C, false, BF16, true, false, false>(b0, (uint32_t)(n_bags - b0 < BPW ? n_bags - b0 : BPW), dim4, keys, offsets, n_keys, nullptr, out, found,
                                                                           nullptr, mean, TierArgs{}, tile, tl, pair_of, row_of, tier.count);
@@ -1114,6 +1119,32 @@ int mee_group_find_pooled_tiered(mee_group* hot, mee_group* cold, const int64_t*
             nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, hot->dim4, mode == MEE_POOL_MEAN, hot->d_desc, bags_per_table,
             nullptr, n, nullptr, 0, nullptr, 0, tier);
     }); });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+// the same lookup with the members' bag counts read from d_member_bags, as mee_group_find_pooled_jagged reads them: find_pooled_kernel's GROUPED && JAGGED && TIERED
+// instances (fp32 out: the partial rows of a sharded bag travel as fp32)
+int mee_group_find_pooled_tiered_jagged(mee_group* hot, mee_group* cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
+                                        const uint64_t* d_member_bags, float* d_out, uint8_t* d_found, int mode, uint32_t flags, void* stream) {
+    MEE_RANGE("mee_group_find_pooled_tiered_jagged");
+    if (!hot || !cold || (n_bags && (!d_bag_offsets || !d_member_bags || !d_out)) || (n && !d_keys))
+        return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_tiered_jagged: null argument");
+    if (int rc = tiered_groups_check(hot, cold, flags, "mee_group_find_pooled_tiered_jagged")) return rc;
+    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_tiered_jagged: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
+    if (hot->n_tables == 0) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_tiered_jagged: the group has no tables");   // the kernel keeps the member inside [0, n_tables)
+    if (n_bags == 0) return MEE_OK;
+    if (int rc = group_refresh(hot, stream)) return rc;
+    if (int rc = group_refresh(cold, stream)) return rc;
+    DeviceGuard guard(hot->device);
+    hipStream_t st = as_stream(stream);
+    const GroupTier tier{cold->d_desc, hot->d_init, cold->d_init, flags};
+    with_pooled_shape(hot->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
+        constexpr int ut = (bpw == 1 && u > 2) ? 2 : u;   // the keys in flight of mee_group_find_pooled_tiered
+        find_pooled_kernel<d4, ut, bpw, true, false, false, true, true><<<grid, 256, 0, st>>>(
+            nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, hot->dim4, mode == MEE_POOL_MEAN, hot->d_desc, 1,
+            nullptr, n, nullptr, 0, d_member_bags, hot->n_tables, tier);
+    });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }

@@ -441,7 +441,8 @@ class DynamicEmbeddingCollection(torch.nn.Module, _SparseOptimizerSettings):
     (find in eval mode), backward ONE grouped optimizer step, whatever the number of tables (TableGroup in table.py).
     out_dtype=torch.bfloat16: the lookup itself writes bf16 rows (the tables stay fp32; a bf16 grad is widened, which is exact).
     `group` may be a ShardedTableGroup (sharded.py): the same two ops, then ONE exchange per lookup and per step over the process group; or a
-    TieredTableGroup (tiered.py), a collection of hot/cold pairs: forward is one launch (two in training), backward two grouped steps."""
+    TieredTableGroup (tiered.py), a collection of hot/cold pairs: forward is one launch (two in training), backward two grouped steps; or a
+    ShardedTieredTableGroup, both at once (this layer and DynamicEmbeddingBag need nothing of their own for it)."""
 
     def __init__(self, group, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
                  out_dtype: torch.dtype = torch.float32):

@@ -22,6 +22,7 @@ Reference anchor: /root/reference/README.md:2 ("A distributed … Embedding"); t
 
 Table groups (ShardedTableGroup; SPEC.md §5 "Groups"): one partition and ONE exchange per operator serve the jagged batch of a whole collection of
 sharded tables — 4 collectives per find, 3 per apply, whatever the number of tables (segment_counts on the source, regroup on the owner).
+ShardedTieredTableGroup (SPEC.md §5 "Groups of pairs") is the same over a collection of hot/cold pairs (a TieredTableGroup per rank).
 
 This module is host logic only: `local` is any object with the LookupTable operator methods and `router` any
 object with partition / gather_rows / scatter_rows (the HIP-backed LookupTable / Router in production).
@@ -341,15 +342,17 @@ class ShardedTableGroup(_Exchange):
 
     5 collectives per pooled lookup and 4 per pooled step, whatever T is; weighted bags and dedup= are not offered."""
 
+    _over_pairs = False   # ShardedTieredTableGroup: the local group is a TieredTableGroup
+
     def __init__(self, local_group, router, group=None):
         if not hasattr(local_group, "tables"):
             raise ValueError(f"{type(local_group).__name__} is no group of tables (a TableGroup of the rank's local shards)")
         if getattr(local_group, "mixed_dims", False):
             raise ValueError(f"{type(local_group).__name__} has members of different dims: a sharded group exchanges rows of one width "
                              "(one ShardedTableGroup per width, each over a TableGroup)")
-        if hasattr(local_group, "cold_group"):   # a TieredTableGroup: before its unpooled operators existed every sharded operator refused it (_check)
-            raise ValueError(f"{type(local_group).__name__} is a group of hot/cold pairs: a sharded group over tiers is not offered "
-                             "(a ShardedLookupTable over a TieredLookupTable shards one pair)")
+        if hasattr(local_group, "cold_group") and not self._over_pairs:   # a TieredTableGroup
+            raise ValueError(f"{type(local_group).__name__} is a group of hot/cold pairs: the sharded group over tiers is a class of its own, "
+                             "ShardedTieredTableGroup (a ShardedLookupTable over a TieredLookupTable shards one pair)")
         refuse_narrow_rows("ShardedTableGroup", local_group)
         self.local = self.local_group = local_group
         self.dim = local_group.dim
@@ -531,6 +534,44 @@ class ShardedTableGroup(_Exchange):
                    eps: float = 1e-8, step: int = 1) -> None:
         k, off, g = self._push("apply_adam", keys, offsets, grads)
         self.local_group.apply_adam(k, off, g, lr, beta1, beta2, eps, step)
+
+
+class ShardedTieredTableGroup(ShardedTableGroup):
+    """ShardedTableGroup whose local members are hot/cold PAIRS (SPEC.md §5 "Groups of pairs"): every rank holds one TieredTableGroup of its T local
+    shards, each shard an HBM table in front of a table whose rows live in pinned host memory.  A pair is indistinguishable from one table holding
+    the union of its tiers (SPEC.md §3 "Tiering"), so this is, by definition, the sharded group over the T union tables: every operator, the exchange,
+    the collectives (4 per find, 3 per step, 5 per pooled lookup, 4 per pooled step, whatever T is) and traffic() are ShardedTableGroup's, unchanged;
+    the owner's calls land on the tiered group's operators of the same names — find / find_or_insert (one / two launches over both tiers of every
+    member, bf16 rows rounded before they travel), apply_adagrad / apply_adam and apply_indexed (two grouped steps), find_pooled_jagged (ONE launch
+    over the runs of every member, mee_group_find_pooled_tiered_jagged).  Weighted bags, dedup= and located rows are not offered.
+
+    Creation: the owner's pair picks the tier of a new key, and is charged with the size of the whole regrouped batch the owner received
+    (TieredTableGroup.find_or_insert's conservative bound: a member goes cold earlier than the pair on its own segment would, never later).
+    Placement policy: with find_pooled(insert_missing=True) the owner looks the received keys up twice — the unpooled find_or_insert in front, then
+    the pooled launch — and both feed the hit counters: that step's hits count twice (as under nn.DynamicEmbeddingBag(create_missing=True) over a pair).
+
+    rebalance() and size() are passed through; the pairs stay usable on their own (promote, demote, export, checkpoints) between steps."""
+    _over_pairs = True
+
+    def __init__(self, local_group, router, group=None):
+        from .tiered import TieredTableGroup
+        if not isinstance(local_group, TieredTableGroup):
+            raise ValueError(f"{type(local_group).__name__} is no TieredTableGroup: ShardedTieredTableGroup shards a collection of hot/cold pairs "
+                             "(a TableGroup of HBM-only shards goes under ShardedTableGroup)")
+        # a pair carries no row type of its own: its two tables are looked at
+        refuse_narrow_rows("ShardedTieredTableGroup", *[t for p in local_group.tables for t in (p.hot, p.cold)])
+        super().__init__(local_group, router, group)
+
+    def rebalance(self, max_moves: int = 1 << 20) -> list[tuple[int, int]]:
+        """TieredTableGroup.rebalance of this rank's pairs -> [(promoted, demoted)] per pair.  Between steps; rank-local: there is no collective in it,
+        so the ranks need not call it together."""
+        return self.local_group.rebalance(max_moves)
+
+    def size(self) -> int:
+        """keys over all ranks and both tiers (collective: one all-reduce), like ShardedLookupTable.size"""
+        t = torch.tensor([self.local_group.size()], dtype=torch.int64, device="cpu" if self._stage else self.device)
+        dist.all_reduce(t, group=self.group)
+        return int(t.item())
 
 
 class RcclShardedTable:

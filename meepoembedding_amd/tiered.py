@@ -361,7 +361,10 @@ class TieredTableGroup:
     The same collection without pooling — a row per id, for sequence features: find / find_or_insert / apply_adagrad / apply_adam over a jagged batch
     (keys, offsets[n_tables + 1] on the device) with TableGroup's signatures, each by definition the pair's operator per member on its segment: one
     launch (mee_group_find_tiered), two (mee_group_find_or_insert_tiered) and two grouped steps.  nn.DynamicEmbeddingCollection trains over it.
-    Weighted bags, located rows and a jagged bag map are not offered over tiers.
+    Weighted bags and located rows are not offered over tiers.
+
+    The owner's side of a sharded group of pairs (ShardedTieredTableGroup): find_pooled_jagged — the pooled lookup with the members' bag counts read
+    from the device, one launch (mee_group_find_pooled_tiered_jagged) — and apply_indexed, two grouped indexed steps.
 
     The placement policy is on when EVERY pair has it (both tiers created with track_hits=True); the launch then counts cold hits always and hot
     hits on every sample_every-th call, as a pair does.  Some pairs with it and some without is a ValueError.
@@ -619,5 +622,88 @@ class TieredTableGroup:
             return
         for g in (self.hot_group, self.cold_group):
             g.apply_pooled(keys, bag_offsets, bag_grads, bag_of_position, optimizer, lr, eps=eps, beta1=beta1, beta2=beta2, step=step)
+        for p in self.tables:
+            p._after_optimizer_step()
+
+    # -- the owner's side of a sharded group of pairs (sharded.py, ShardedTieredTableGroup): the runs that arrive per member differ in number ----
+    def find_pooled_jagged(self, keys: torch.Tensor, bag_offsets: torch.Tensor, member_bags: torch.Tensor, mode: str = "sum",
+                           out: torch.Tensor | None = None, found: torch.Tensor | None = None):
+        """find_pooled where bag b belongs to the pair j with member_bags[j] <= b < member_bags[j + 1] (n_tables + 1 non-decreasing int64 on the
+        device; a pair may have no bags; a bag outside the map is empty: a row of zeros, nothing probed, its positions' found bytes not written)
+        -> ([n_bags, dim] fp32, per-key found mask).  TableGroup.find_pooled_jagged's arguments and checks without `located`; on every bag inside the
+        map the pair's find_pooled on that bag, bit for bit.  ONE launch (mee_group_find_pooled_tiered_jagged), sync-free, which feeds the members'
+        hit counters as find_pooled does."""
+        from . import _lib
+        from .table import _fp32_only
+        _fp32_only(out, "find_pooled_jagged")
+        nb = bag_offsets.numel() - 1
+        if not self._native:   # a loop over the pairs, member j on its bags (a host read of member_bags)
+            if mode not in ("sum", "mean"):
+                raise ValueError(f"mode must be 'sum' or 'mean' (got {mode!r})")
+            if member_bags.dim() != 1 or member_bags.numel() != len(self.tables) + 1:
+                raise ValueError(f"member_bags must hold n_tables + 1 = {len(self.tables) + 1} entries (got {tuple(member_bags.shape)})")
+            flat = keys.contiguous().view(-1)
+            n = flat.numel()
+            if nb < 0 or (n and nb == 0):
+                raise ValueError("bag_offsets must hold n_bags + 1 entries, and keys need bags to report them")
+            off = bag_offsets.to(torch.int64)
+            cut = off.clamp(0, n).tolist()
+            mb = member_bags.to(torch.int64).clamp(0, nb).tolist()
+            pooled = torch.zeros((nb, self.dim), dtype=torch.float32, device=flat.device)
+            fnd = torch.zeros(n, dtype=torch.uint8, device=flat.device)
+            for j, pair in enumerate(self.tables):
+                b0, b1 = mb[j], max(mb[j], mb[j + 1])
+                if b1 == b0:
+                    continue
+                s, e = min(cut[b0:b1 + 1]), max(cut[b0:b1 + 1])
+                o, f = pair.find_pooled(flat[s:e], off[b0:b1 + 1] - s, mode)
+                pooled[b0:b1] = o
+                fnd[s:e] = f
+            if out is not None:
+                out.copy_(pooled)
+            if found is not None:
+                found.copy_(fnd)
+            return (out if out is not None else pooled), (found if found is not None else fnd)
+        from ._lib import MeepoError
+        from .table import _stream_ptr
+        self.hot_group._check_offsets(member_bags)
+        if bag_offsets.device != self.device or bag_offsets.dtype not in (torch.int64, torch.uint64) or not bag_offsets.is_contiguous() or nb < 0:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_offsets must be contiguous int64 on {self.device} with n_bags + 1 entries")
+        if mode not in ("sum", "mean"):
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"mode must be 'sum' or 'mean' (got {mode!r})")
+        k = self.tables[0].hot._keys(keys) if keys.numel() else keys
+        n = k.numel()
+        if out is None:
+            out = torch.empty((nb, self.dim), dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or out.device != self.device or out.numel() != nb * self.dim or not out.is_contiguous():
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"out must be a contiguous float32 buffer [{nb}, {self.dim}] on {self.device}")
+        if found is None:
+            found = torch.empty(n, dtype=torch.uint8, device=self.device)
+        elif found.dtype != torch.uint8 or found.device != self.device or found.numel() != n or not found.is_contiguous():
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"found must be a contiguous uint8 buffer of {n} entries on {self.device}")
+        if n and nb == 0:
+            raise MeepoError(_lib.ERR_INVALID_ARG, "there are keys but no bags: no bag would report them")
+        _lib.check(_lib.lib().mee_group_find_pooled_tiered_jagged(self.hot_group._h, self.cold_group._h, k.data_ptr(), n, bag_offsets.data_ptr(), nb,
+                                                                  member_bags.data_ptr(), out.data_ptr(), found.data_ptr(), {"sum": 0, "mean": 1}[mode],
+                                                                  self._count_flags(), _stream_ptr(self.device)))
+        return out, found
+
+    def apply_indexed(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, grad_index: torch.Tensor, optimizer: str, lr: float,
+                      eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1) -> None:
+        """One optimizer step over the jagged batch == the pair's apply_*(grad_index=...) per member with its segment: position i takes row
+        grad_index[i] of grads [rows, dim].  TWO grouped indexed steps, the hot group's and the cold group's (a key lives in one tier, and a group
+        ignores the keys its member does not hold — apply_pooled's argument), then every pair's rebalance_every bookkeeping."""
+        if optimizer not in ("adagrad", "adam"):
+            raise ValueError(f"optimizer must be 'adagrad' or 'adam' (got {optimizer!r})")
+        if not self._native:
+            flat = keys.contiguous().view(-1)
+            for pair, (s, e) in zip(self.tables, self._segments(offsets, flat.numel())):
+                if optimizer == "adagrad":
+                    pair.apply_adagrad(flat[s:e], grads, lr, 1e-10 if eps is None else eps, grad_index=grad_index[s:e])
+                else:
+                    pair.apply_adam(flat[s:e], grads, lr, beta1, beta2, 1e-8 if eps is None else eps, step, grad_index=grad_index[s:e])
+            return
+        for g in (self.hot_group, self.cold_group):
+            g.apply_indexed(keys, offsets, grads, grad_index, optimizer, lr, eps=eps, beta1=beta1, beta2=beta2, step=step)
         for p in self.tables:
             p._after_optimizer_step()
