@@ -44,7 +44,7 @@ for step in range(8):
     dense_opt.zero_grad()
     loss.backward()                      # the sparse update: one grouped step over the hot tables, one over the cold tables
     dense_opt.step()
-    moved = group.rebalance() if step % 2 == 1 else None      # between steps: promote the cold ids the lookups hit, per pair
+    moved = group.rebalance() if step % 2 == 1 else None      # between steps: promote the cold ids the lookups hit — at most two grouped moves for all pairs
     print(f"step {step}: loss {loss.item():.4f}, ids {ids.numel()}, keys hot {sum(p.hot.size() for p in pairs)} / cold {sum(p.cold.size() for p in pairs)}"
           + (f", rebalanced: promoted {sum(m[0] for m in moved)}, demoted {sum(m[1] for m in moved)}" if moved else ""))
 

@@ -451,6 +451,37 @@ int mee_group_find_or_insert_tiered(mee_group* hot_group, mee_group* cold_group,
                                     void* d_out, uint32_t out_dtype, uint8_t* d_found /* required: present before the call */,
                                     const uint8_t* d_to_cold /* [n_tables], device; nullable: all hot */, uint32_t flags, void* stream);
 
+/* ---- tier migration (SPEC.md §3 move): "this key, with everything it owns, now lives in that table" --------------------------------------
+ * Let P be the batch positions whose key is not reserved and is stored in `src` when the call starts, in ascending order; the first max_moves of them
+ * are SERVED (UINT64_MAX: all).  Every key at a served position ends the call stored in `dst` and absent from `src`: its values row and every
+ * optimizer plane (acc | m, v) copied bit for bit; a key `dst` already held has its row and state overwritten there (an upsert) and keeps its hit
+ * counter, a slot created in `dst` starts with hit counter 0; the `src` slot becomes RECLAIMED.  Duplicates are legal: every occurrence counts
+ * against max_moves, the key moves once.  d_moved[i] (nullable: not written) = 1 for served positions whose key got a slot in `dst`, 0 for every
+ * other i < n; *d_n_moved (DEVICE memory, nullable) = the number of DISTINCT keys moved.  A key for which `dst` has no room STAYS IN `src`,
+ * untouched, and MEE_STATUS_TABLE_FULL goes to dst's status word (which of several such keys find room is decided by the race of the claims, as
+ * for mee_insert).  RECLAIMED in the batch sets MEE_STATUS_RESERVED_KEY on `src`, as mee_remove does; EMPTY is padding.  In everything else both
+ * tables are left as the sequence  mee_insert(dst, k, mee_find(src, k)); mee_assign_plane(dst, p, k, mee_find_plane(src, p, k)) per state plane;
+ * mee_remove(src, k)  over the moved keys leaves them: size, probe rule, tombstone reuse, key-sorted export.
+ * Either table may be MEE_MEM_HBM or MEE_MEM_HOST_PINNED, with or without MEE_FLAG_TRACK_HITS.  Two launches (four when max_moves < n), no
+ * [n, dim] buffer, no allocation, no host synchronisation and nothing read back: capturable.  Host side as mee_remove on `src` and mee_insert on
+ * `dst`: a partition a training forward left pending on either is dropped, slot handles taken from `src` before the call are stale.
+ * Refused before anything is launched or written — MEE_ERR_INVALID_ARG: a null table (or null d_keys with n > 0), src == dst, different device,
+ * dim or optimizer, a partition of mee_apply_prepare pending on either; MEE_ERR_UNSUPPORTED: a bf16-row or int8-row table on either side;
+ * MEE_ERR_BATCH_TOO_LARGE: n above either table's max_batch.  n == 0 writes 0 to *d_n_moved.
+ * mee_group_move is, by definition, mee_move(src_group member j, dst_group member j, segment j, d_max_moves[j]) for every member, segment j =
+ * positions d_offsets[j] .. d_offsets[j + 1] - 1 (n_tables + 1 offsets in DEVICE memory, cut at n), in ONE launch sequence whatever the number of
+ * members.  d_max_moves: n_tables limits in DEVICE memory (null: no limit); d_n_moved: n_tables counts in DEVICE memory (nullable).  Positions
+ * outside [d_offsets[0], d_offsets[n_tables]) or at or past n are not looked at and their d_moved bytes are not written.  Refused like the other
+ * operators over two groups (null, the same group twice, groups that differ in device, dim or number of tables, a member that is the same table in
+ * both, a bf16-row group), plus per member what mee_move refuses (messages name the member), plus a table that is a member more than once across
+ * the two groups.  The offsets are never read by the host, so the batch bound is on n: n above the max_batch of any member of either group is
+ * MEE_ERR_BATCH_TOO_LARGE.  After mee_reserve on a member the next call re-reads that table's planes (one stream synchronisation). */
+int mee_move(mee_table* src, mee_table* dst, const int64_t* d_keys, size_t n, uint64_t max_moves, uint8_t* d_moved /* [n], nullable */,
+             uint64_t* d_n_moved /* device, one word, nullable */, void* stream);
+int mee_group_move(mee_group* src_group, mee_group* dst_group, const int64_t* d_keys, const uint64_t* d_offsets, size_t n,
+                   const uint64_t* d_max_moves /* device [n_tables], nullable = no limit */, uint8_t* d_moved /* [n], nullable */,
+                   uint64_t* d_n_moved /* device [n_tables], nullable */, void* stream);
+
 /* ---- typed output: the lookups above with fp32 OR bf16 result rows (SPEC.md §3 "Output type") --------------------------------
  * The models these tables feed run in bf16; a lookup that writes bf16 itself saves the cast in front of the first dense layer and half
  * of its own store traffic.  Tables, optimizer state and every accumulation stay fp32: with out_dtype = MEE_DTYPE_BF16 the result is, by

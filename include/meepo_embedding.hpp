@@ -84,6 +84,8 @@ public:
     void insert_as(const int64_t* d_keys, const void* d_values, uint32_t in_dtype, size_t n, void* stream = nullptr) { check(mee_insert_as(t_, d_keys, d_values, in_dtype, n, stream)); }
     void assign_as(const int64_t* d_keys, const void* d_values, uint32_t in_dtype, size_t n, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_assign_as(t_, d_keys, d_values, in_dtype, n, d_found, stream)); }
     void remove(const int64_t* d_keys, size_t n, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_remove(t_, d_keys, n, d_found, stream)); }
+    // tier migration (mee_move): the batch's keys that this table holds leave it for dst, rows and optimizer state; d_n_moved: one device word
+    void move_to(Table& dst, const int64_t* d_keys, size_t n, uint64_t max_moves = UINT64_MAX, uint8_t* d_moved = nullptr, uint64_t* d_n_moved = nullptr, void* stream = nullptr) { check(mee_move(t_, dst.t_, d_keys, n, max_moves, d_moved, d_n_moved, stream)); }
     void find_or_insert(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_find_or_insert(t_, d_keys, n, d_out, d_found, stream)); }
     // the forward of a training step over a growing vocabulary: rows + the slot of every key, for apply_*_located of the same step
     void find_or_insert_located(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, int64_t* d_slots_out, void* stream = nullptr) { check(mee_find_or_insert_located(t_, d_keys, n, d_out, d_found, d_slots_out, stream)); }
@@ -220,6 +222,10 @@ public:
     }
     void find_or_insert_tiered(Group& cold, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, const uint8_t* d_to_cold = nullptr, uint32_t flags = 0, void* stream = nullptr) {
         check(mee_group_find_or_insert_tiered(g_, cold.g_, d_keys, d_offsets, n, d_out, out_dtype, d_found, d_to_cold, flags, stream));
+    }
+    // mee_move per member on its segment of the jagged batch (mee_group_move); d_max_moves / d_n_moved: n_tables device words each, nullable
+    void move_to(Group& dst, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, const uint64_t* d_max_moves = nullptr, uint8_t* d_moved = nullptr, uint64_t* d_n_moved = nullptr, void* stream = nullptr) {
+        check(mee_group_move(g_, dst.g_, d_keys, d_offsets, n, d_max_moves, d_moved, d_n_moved, stream));
     }
 private:
     mee_group* g_ = nullptr;

@@ -147,6 +147,9 @@ PROTOTYPES = {
     # ... the unpooled forms: keys, member offsets, n, out, out_dtype, found, [to_cold,] flags, stream
     "mee_group_find_tiered": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _u32, _vp, _u32, _vp]),
     "mee_group_find_or_insert_tiered": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _u32, _vp, _vp, _u32, _vp]),
+    # tier migration: src, dst, keys, [member offsets,] n, max_moves (a value | per-member limits on the device), moved mask, moved count(s), stream
+    "mee_move": (C.c_int, [_vp, _vp, _vp, _sz, _u64, _vp, _vp, _vp]),
+    "mee_group_move": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "mee_pooled_weighted_backward": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "mee_group_find_pooled_weighted": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "mee_group_pooled_weighted_backward": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),

@@ -477,14 +477,17 @@ using namespace mee;
 static int upload_descriptors(mee_group* g) {
     std::vector<GroupDesc> h(g->n_tables);
     std::vector<GroupInit> hi(g->n_tables);
+    std::vector<MoveTable> hm(g->n_tables);
     for (uint32_t j = 0; j < g->n_tables; ++j) {
         const TableView v = table_view(g->tables[j]);
         h[j] = GroupDesc{v.keys, (float4*)v.values, (float4*)v.s1, (float4*)v.s2, v.nb, v.default_value, 0};   // (a bf16-row member: its bf16 plane behind the same pointer — the launch knows, g->bf16_rows)
         hi[j] = GroupInit{v.init_seed, v.status, v.hits, v.initializer, v.optimizer, v.init_scale, v.init_acc};
+        hm[j] = MoveTable{const_cast<int64_t*>(v.keys), {(float4*)v.values, (float4*)v.s1, (float4*)v.s2}, v.nb, v.status, v.hits, v.batch_slots};
         g->generations[j] = v.generation;
     }
     MEE_HIP(hipMemcpy(g->d_desc, h.data(), h.size() * sizeof(GroupDesc), hipMemcpyHostToDevice));  // synchronous, rare
     MEE_HIP(hipMemcpy(g->d_init, hi.data(), hi.size() * sizeof(GroupInit), hipMemcpyHostToDevice));
+    MEE_HIP(hipMemcpy(g->d_move, hm.data(), hm.size() * sizeof(MoveTable), hipMemcpyHostToDevice));
     return MEE_OK;
 }
 
@@ -535,12 +538,13 @@ int mee_group_create(mee_table* const* tables, uint32_t n_tables, uint64_t max_a
     if (!g) return fail(MEE_ERR_OUT_OF_MEMORY, "host allocation failed");
     g->device = v0.device; g->n_tables = n_tables; g->dim = v0.dim; g->dim4 = v0.dim4; g->bf16_rows = v0.bf16_rows; g->d_desc = nullptr;
     g->optimizer = v0.optimizer; g->max_apply_batch = max_apply_batch; g->scratch = nullptr; g->d_gslot = nullptr;
-    g->d_init = nullptr; g->d_fmask = nullptr;
+    g->d_init = nullptr; g->d_move = nullptr; g->d_fmask = nullptr;
     g->tables.assign(tables, tables + n_tables);
     g->generations.assign(n_tables, 0);
     DeviceGuard guard(g->device);
     hipError_t e = hipMalloc((void**)&g->d_desc, n_tables * sizeof(GroupDesc));
     if (e == hipSuccess) e = hipMalloc((void**)&g->d_init, n_tables * sizeof(GroupInit));
+    if (e == hipSuccess) e = hipMalloc((void**)&g->d_move, n_tables * sizeof(MoveTable));
     if (e == hipSuccess && max_apply_batch) e = hipMalloc((void**)&g->d_fmask, max_apply_batch);
     if (e != hipSuccess) { mee_group_destroy(g); return fail(MEE_ERR_OUT_OF_MEMORY, "hipMalloc(group descriptors): %s", hipGetErrorString(e)); }
     if (int rc = upload_descriptors(g)) { mee_group_destroy(g); return rc; }
@@ -576,6 +580,7 @@ int mee_group_destroy(mee_group* g) {
     (void)hipDeviceSynchronize();
     (void)hipFree(g->d_desc);
     (void)hipFree(g->d_init);
+    (void)hipFree(g->d_move);
     (void)hipFree(g->d_fmask);
     (void)hipFree(g->d_gslot);
     if (g->scratch) mee_table_destroy(g->scratch);

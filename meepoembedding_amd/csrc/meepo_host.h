@@ -82,6 +82,7 @@ struct TableView {
     uint32_t* status;
     uint32_t* hits;
     bool bf16_rows;        // the value plane holds bf16 rows (MEE_FLAG_BF16_ROWS): `values` is then dim4 8-byte groups per slot
+    long long* batch_slots;   // the per-position slot list of the table's per-batch scratch (>= 2 * max_batch entries: insert, remove and move borrow it)
 };
 TableView table_view(const mee_table* t);
 // The operators a serving table — bf16 rows or int8 rows — does not have (include/meepo_embedding.h, MEE_FLAG_BF16_ROWS / MEE_FLAG_INT8_ROWS) — and every
@@ -109,6 +110,14 @@ struct GroupInit {   // per member, device resident: what creating a key in that
     uint32_t* hits;
     uint32_t initializer, optimizer;
     float init_scale, init_acc;
+};
+struct MoveTable {   // one side of a move (meepo_move.hip): a kernel argument for mee_move, per member and device resident for mee_group_move
+    int64_t* tkeys;
+    float4* plane[3];    // values, acc | m, v (null where the optimizer has none)
+    uint64_t nb;
+    uint32_t* status;
+    uint32_t* hits;      // null without MEE_FLAG_TRACK_HITS
+    long long* slots;    // the table's per-batch slot list (TableView::batch_slots): a move keeps the src slot of every position there between its launches
 };
 constexpr int kGroupSlotBits = 48;   // grouped apply names a row by (member << 48 | slot): unique per (table, key), never a reserved key
 constexpr uint32_t kMaxGroupTables = 1024;   // offsets staged in LDS: (1024 + 1) x 8 B
@@ -154,6 +163,7 @@ struct mee_group {
     std::vector<uint64_t> generations;   // of each table when its descriptor was last uploaded (mee_reserve moves planes)
     mee::GroupDesc* d_desc;
     mee::GroupInit* d_init;
+    mee::MoveTable* d_move;   // the members as mee_group_move sees them, uploaded with the descriptors
     uint8_t* d_fmask;      // [max_apply_batch] found mask of grouped find_or_insert when the caller passes none
     // grouped apply (max_apply_batch > 0): a scratch-only table whose group table / per-position arrays serve the whole
     // jagged batch, and the located rows of the batch

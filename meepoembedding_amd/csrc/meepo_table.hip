@@ -472,7 +472,7 @@ template <int P> __global__ __launch_bounds__(256) void ensure_direct_bf16_kerne
 // =========================================================================================================
 TableView table_view(const mee_table* t) {
     return TableView{t->device, t->keys, t->values, t->nb, t->dim, t->dim4, t->default_value, t->generation, t->s1, t->s2, t->optimizer,
-                     t->initializer, t->init_scale, t->init_acc, t->init_seed, &t->ctr->status, t->hits, t->bf16_rows};
+                     t->initializer, t->init_scale, t->init_acc, t->init_seed, &t->ctr->status, t->hits, t->bf16_rows, t->g.sres};
 }
 
 int refuse_narrow_rows(const mee_table* t, const char* op, bool bf16_too) {

@@ -356,6 +356,23 @@ class LookupTable:
         self.layout_epoch += 1
         return found
 
+    def move_to(self, dst: "LookupTable", keys: torch.Tensor, max_moves: int | None = None, want_moved: bool = False):
+        """SPEC.md §3 move (mee_move): the keys of the batch that this table holds leave it for `dst` — the values row and every optimizer plane, bit for
+        bit; a key `dst` already holds is overwritten there, a key `dst` has no room for stays here (TABLE_FULL on dst).  max_moves: only the first
+        max_moves batch positions whose key is stored here are served (None: all).  -> (n_moved: int64 device tensor [1], the number of DISTINCT keys
+        moved; moved mask [n] uint8 | None).  Two launches (four under a limit below n), no [n, dim] buffer, no synchronisation: the count stays on the
+        device.  Slot handles taken from this table before the call are stale afterwards."""
+        if not isinstance(dst, LookupTable):
+            raise MeepoError(_lib.ERR_INVALID_ARG, "move_to: dst must be a LookupTable")
+        k = self._keys(keys)
+        n = k.numel()
+        n_moved = torch.empty(1, dtype=torch.int64, device=self.device)
+        moved = torch.empty(n, dtype=torch.uint8, device=self.device) if want_moved else None
+        limit = 0xFFFFFFFFFFFFFFFF if max_moves is None else max(0, int(max_moves))
+        check(_lib.lib().mee_move(self._h, dst._h, k.data_ptr(), n, limit, None if moved is None else moved.data_ptr(), n_moved.data_ptr(), self._s()))
+        self.layout_epoch += 1
+        return n_moved, moved
+
     def find_or_insert(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
                        min_count: int | None = None, out_dtype: torch.dtype = torch.float32):
         """min_count (tables created with admission=True): an absent key is created only once the table's count-min sketch has seen it
@@ -720,6 +737,29 @@ class TableGroup:
         if offsets.device != self.device or offsets.dtype not in (torch.int64, torch.uint64) or offsets.numel() != len(self.tables) + 1 \
                 or not offsets.is_contiguous():
             raise MeepoError(_lib.ERR_INVALID_ARG, f"offsets must be {len(self.tables) + 1} contiguous int64 values on {self.device}")
+
+    def move_to(self, dst_group: "TableGroup", keys: torch.Tensor, offsets: torch.Tensor, max_moves=None, want_moved: bool = False):
+        """LookupTable.move_to per member on its segment of the jagged batch (mee_group_move): member j's keys leave tables[j] for dst_group.tables[j],
+        in one launch sequence whatever the number of members.  max_moves: None (no limit), or one limit per member — a list, or an int64 / uint64
+        tensor of n_tables entries on the device.  -> (n_moved: int64 device tensor [n_tables], distinct keys moved per member; moved mask [n] uint8 |
+        None — bytes of positions outside the segments are not written).  keys.numel() may not exceed any member's max_batch.  No synchronisation."""
+        if not isinstance(dst_group, TableGroup):
+            raise MeepoError(_lib.ERR_INVALID_ARG, "move_to: dst_group must be a TableGroup")
+        self._check_offsets(offsets)
+        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        n, nt = k.numel(), len(self.tables)
+        limits = None
+        if max_moves is not None:
+            limits = max_moves if isinstance(max_moves, torch.Tensor) else torch.tensor([max(0, int(m)) for m in max_moves], dtype=torch.int64).to(self.device)
+            if limits.device != self.device or limits.dtype not in (torch.int64, torch.uint64) or limits.numel() != nt or not limits.is_contiguous():
+                raise MeepoError(_lib.ERR_INVALID_ARG, f"max_moves must hold {nt} int64 limits (a list, or a contiguous tensor on {self.device})")
+        n_moved = torch.empty(nt, dtype=torch.int64, device=self.device)
+        moved = torch.empty(n, dtype=torch.uint8, device=self.device) if want_moved else None
+        check(_lib.lib().mee_group_move(self._h, dst_group._h, k.data_ptr(), offsets.data_ptr(), n, None if limits is None else limits.data_ptr(),
+                                        None if moved is None else moved.data_ptr(), n_moved.data_ptr(), _stream_ptr(self.device)))
+        for t in self.tables:
+            t.layout_epoch += 1
+        return n_moved, moved
 
     def apply_adagrad(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10) -> None:
         """One sparse-Adagrad step over the jagged batch == apply_adagrad per table (max_apply_batch >= keys.numel())."""

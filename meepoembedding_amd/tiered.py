@@ -284,8 +284,21 @@ class TieredLookupTable:
         return checkpoint.load_into(self, path, chunk_pairs, keep)
 
     # -- tier migration ------------------------------------------------------------------------------------
+    def _moves_natively(self) -> bool:
+        """migration goes through mee_move (two native tables); otherwise through the operator sequence of _move_by_operators"""
+        return self._native()
+
     def _move(self, src, dst, keys: torch.Tensor) -> int:
-        """Move the keys that `src` holds into `dst`, rows and optimizer state; returns how many were moved."""
+        """Move the keys that `src` holds into `dst`, rows and optimizer state; returns how many (distinct keys) were moved.  Two native tables: ONE
+        move (SPEC.md §3 move, LookupTable.move_to: no [n, dim] buffer, a key `dst` has no room for stays in `src`) and one read-back, the count."""
+        if not self._moves_natively():
+            return self._move_by_operators(src, dst, keys)
+        n_moved, _ = src.move_to(dst, keys.contiguous().view(-1))
+        return int(n_moved.item())
+
+    def _move_by_operators(self, src, dst, keys: torch.Tensor) -> int:
+        """_move for tiers that are not native tables (any objects with the LookupTable methods): find, insert, find_plane / assign_plane per state
+        plane, remove — the definition SPEC.md §3 gives move, spelled out with the generic operators."""
         keys = torch.unique(keys.contiguous().view(-1))
         vals, found = src.find(keys)
         idx = self._idx(found != 0)
@@ -333,6 +346,15 @@ class TieredLookupTable:
         """cold -> hot for the given keys (those that are cold), as many as the hot tier has room for.  staged=True: host-side gather +
         one asynchronous copy on a side stream instead of zero-copy reads by the find kernel (see _move_staged)."""
         keys = torch.unique(keys.contiguous().view(-1))
+        if self._moves_natively() and not staged:
+            # the move serves the first `room` cold keys in sorted order itself (max_moves): no lookup of the cold rows for their found mask, no compaction
+            if not keys.numel():
+                return 0
+            self._hot_keys_ub = self.hot.size()
+            room = max(0, self.hot_key_limit - self._hot_keys_ub)
+            moved = int(self.cold.move_to(self.hot, keys, max_moves=room)[0].item()) if room else 0
+            self._hot_keys_ub += moved
+            return moved
         _, in_cold = self.cold.find(keys)
         cand = keys[self._idx(in_cold != 0)]
         if not cand.numel():
@@ -368,6 +390,9 @@ class TieredTableGroup:
 
     The placement policy is on when EVERY pair has it (both tiers created with track_hits=True); the launch then counts cold hits always and hot
     hits on every sample_every-th call, as a pair does.  Some pairs with it and some without is a ValueError.
+
+    Migration over the collection: promote / demote over a jagged batch and rebalance() are the pair's per member, with all members' keys moved by
+    ONE grouped move per direction (mee_group_move: the hot group and the cold group are its two sides).
 
     The pairs stay usable on their own (rebalance, promote, demote, export, checkpoints).  Pairs that are not native tables (any objects with the
     LookupTable methods) are served by a loop over the pairs with the same results."""
@@ -420,8 +445,99 @@ class TieredTableGroup:
         return sum(p.size() for p in self.tables)
 
     def rebalance(self, max_moves: int = 1 << 20) -> list[tuple[int, int]]:
-        """TieredLookupTable.rebalance() of every pair -> [(promoted, demoted)] per pair.  Between steps, like the pair's own."""
-        return [p.rebalance(max_moves) for p in self.tables]
+        """TieredLookupTable.rebalance() of every pair -> [(promoted, demoted)] per pair.  Between steps, like the pair's own.  Native pairs: every
+        member still scans its two tiers' counters (hits_scan), then ALL members' victims move in one grouped move and all their sliced candidates in
+        another (mee_group_move): at most two launch sequences and two read-backs for the collection, the list and the placement those of the loop."""
+        if not (self._native and self.policy and all(p._moves_natively() for p in self.tables)):
+            return [p.rebalance(max_moves) for p in self.tables]
+        cands, victims, rooms = [], [], []
+        for p in self.tables:
+            cand = p.cold.hits_scan(p.promote_threshold, 0xFFFFFFFF, max_moves, reset=True)
+            p._hot_keys_ub = p.hot.size()
+            room = max(0, p.hot_key_limit - p._hot_keys_ub)
+            need = max(0, int(cand.numel()) - room)
+            vict = p.hot.hits_scan(0, 0, need, reset=True)   # also restarts the hot tier's window
+            cands.append(cand)
+            victims.append(vict if need else vict[:0])
+            rooms.append(room)
+        demoted = self._move_lists(self.hot_group, self.cold_group, victims)
+        for p, d in zip(self.tables, demoted):
+            p._hot_keys_ub -= d
+        rooms = [r + d for r, d in zip(rooms, demoted)]
+        promoted = self._move_lists(self.cold_group, self.hot_group, [c[:r] for c, r in zip(cands, rooms)])
+        for p, m in zip(self.tables, promoted):
+            p._hot_keys_ub += m
+        return list(zip(promoted, demoted))
+
+    def _move_lists(self, src_group, dst_group, lists) -> list[int]:
+        """member j's key list moves from src_group.tables[j] to dst_group.tables[j]: the lists concatenated into one jagged batch, ONE grouped move, one
+        read-back -> distinct keys moved per member.  A batch beyond a member's max_batch goes member by member instead."""
+        sizes = [int(k.numel()) for k in lists]
+        total = sum(sizes)
+        if total == 0:
+            return [0] * len(lists)
+        if not self._moves_grouped(total):
+            return [int(s.move_to(d, k)[0].item()) if k.numel() else 0 for s, d, k in zip(src_group.tables, dst_group.tables, lists)]
+        bounds = [0]
+        for s in sizes:
+            bounds.append(bounds[-1] + s)
+        offsets = torch.tensor(bounds, dtype=torch.int64).to(self.device)
+        n_moved, _ = src_group.move_to(dst_group, torch.cat([k.view(-1) for k in lists]), offsets)
+        return [int(m) for m in n_moved.tolist()]
+
+    def _moves_grouped(self, n: int) -> bool:
+        """a jagged batch of n keys can go through one grouped move: native pairs, and n within every member's max_batch (mee_group_move's bound)"""
+        return bool(self._native and all(p._moves_natively() for p in self.tables) and n <= min(p.max_batch for p in self.tables))
+
+    def _dedup_segments(self, keys: torch.Tensor, offsets: torch.Tensor):
+        """every segment's keys sorted and made distinct (what TieredLookupTable.promote does to its batch), for all members at once -> (keys, offsets)"""
+        flat = keys.contiguous().view(-1)
+        n, nt = flat.numel(), len(self.tables)
+        off = offsets.to(torch.int64).clamp(0, n)
+        pos = torch.arange(n, device=flat.device)
+        seg = torch.searchsorted(off[1:].contiguous(), pos, right=True)   # the member whose segment holds the position; n_tables: behind the last one
+        inside = (pos >= off[0]) & (seg < nt)
+        k, s = flat[inside], seg[inside]
+        order = torch.argsort(k, stable=True)
+        order = order[torch.argsort(s[order], stable=True)]             # by member, then by key
+        k, s = k[order], s[order]
+        keep = torch.ones_like(k, dtype=torch.bool)
+        keep[1:] = (k[1:] != k[:-1]) | (s[1:] != s[:-1])
+        k, s = k[keep], s[keep]
+        bounds = torch.zeros(nt + 1, dtype=torch.int64, device=flat.device)
+        bounds[1:] = torch.cumsum(torch.bincount(s, minlength=nt), 0)
+        return k, bounds
+
+    def promote(self, keys: torch.Tensor, offsets: torch.Tensor) -> list[int]:
+        """TieredLookupTable.promote of every pair on its segment of the jagged batch (keys, offsets[n_tables + 1] on the device) -> keys moved per pair:
+        cold -> hot, per member the first keys in sorted order that its hot tier has room for.  Native pairs: one grouped move with the members' room as
+        device-side limits and one read-back of the counts (each member's hot size is refreshed first, as the pair's promote does)."""
+        if not self._moves_grouped(keys.numel()):
+            flat = keys.contiguous().view(-1)
+            return [pair.promote(flat[s:e]) for pair, (s, e) in zip(self.tables, self._segments(offsets, flat.numel()))]
+        self.hot_group._check_offsets(offsets)
+        k, bounds = self._dedup_segments(keys, offsets)
+        if not k.numel():
+            return [0] * len(self.tables)
+        rooms = []
+        for p in self.tables:
+            p._hot_keys_ub = p.hot.size()
+            rooms.append(max(0, p.hot_key_limit - p._hot_keys_ub))
+        moved = [int(m) for m in self.cold_group.move_to(self.hot_group, k, bounds, max_moves=rooms)[0].tolist()]
+        for p, m in zip(self.tables, moved):
+            p._hot_keys_ub += m
+        return moved
+
+    def demote(self, keys: torch.Tensor, offsets: torch.Tensor) -> list[int]:
+        """TieredLookupTable.demote of every pair on its segment of the jagged batch -> keys moved per pair (hot -> cold).  Native pairs: one grouped
+        move and one read-back."""
+        if not self._moves_grouped(keys.numel()):
+            flat = keys.contiguous().view(-1)
+            return [pair.demote(flat[s:e]) for pair, (s, e) in zip(self.tables, self._segments(offsets, flat.numel()))]
+        moved = [int(m) for m in self.hot_group.move_to(self.cold_group, keys, offsets)[0].tolist()]
+        for p, m in zip(self.tables, moved):
+            p._hot_keys_ub = max(0, p._hot_keys_ub - m)
+        return moved
 
     def _member_slices(self, bag_offsets: torch.Tensor, n: int):
         """(non-native path) -> bags_per_table, [(first bag, key begin, key end)] per member; offsets past n are cut at n"""
