@@ -59,6 +59,10 @@ tiered.insert(keys, rows)                                   # 50K new keys > the
 for _ in range(8):
     tiered.find(keys[torch.randint(0, 5000, (20_000,), device=dev)])   # a hot working set of 5000 keys
 print("rebalance (promoted, demoted):", tiered.rebalance(), "| hot", hot.size(), "cold", cold.size())
+for _ in range(2):
+    tiered.find(keys[torch.randint(0, 25_000, (20_000,), device=dev)])  # a new window (rebalance restarted it): half of the keys may be hit
+sk, sv, _, _, sh = tiered.evict_cold(10_000, spill=True)    # the cold tier is filling up: its 10K least-hit keys leave, rows handed out for a tier behind it
+print("evicted from the cold tier:", sk.numel(), "keys with rows", tuple(sv.shape), "| most hits among them:", int(sh.cpu().numpy().max()), "| cold", cold.size())
 
 # 4. embedding bags over the pair: one launch probes both tiers per position; the backward is the sparse Adagrad step on both tiers
 hot_t = LookupTable(1 << 16, 64, device=dev, max_batch=1 << 16, optimizer=OPT_ADAGRAD, initializer=INIT_UNIFORM, init_scale=0.05)

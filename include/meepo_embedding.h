@@ -201,6 +201,37 @@ int mee_find_counted(const mee_table* t, const int64_t* d_keys, size_t n, float*
  * reset != 0 zeroes every counter, which starts a new observation window. */
 int mee_hits_scan(mee_table* t, uint32_t min_hits, uint32_t max_hits, int reset, int64_t* d_keys_out, size_t cap, size_t* n_out,
                   void* stream);
+/* Eviction by the hit counters (SPEC.md §3 evict; tables created with MEE_FLAG_TRACK_HITS): make room in a table that is filling up, and hand the
+ * evicted keys' rows and optimizer state out so that a tier behind this one can take them.
+ * C = the stored keys whose counter is <= max_hits when the call starts; L = max_evict, or min(max_evict, cap) when at least one of the five output
+ * buffers is non-null (a key is never evicted without its row being handed out when a row was asked for); m = min(|C|, L).  The call evicts a set
+ * E of m keys of C.  Without MEE_EVICT_LEAST which keys of C are taken is unspecified when |C| > m (as for mee_hits_scan's cap).  With
+ * MEE_EVICT_LEAST every evicted counter is <= every counter of C \ E, compared as full 32-bit values: the evicted counters are exactly the m
+ * smallest of C, and only the choice among keys that tie at the cut is unspecified.
+ * An evicted key's slot becomes RECLAIMED and its counter 0: mee_find reports it absent, mee_size drops by m, and the table is otherwise what
+ * mee_remove(E) leaves (probe rule, tombstone reuse, key-sorted export with state); the keys that stay keep rows, state and counters bit for bit.
+ * MEE_EVICT_RESET: every counter is zero after the selection has been made (a new observation window).
+ * Outputs (all DEVICE memory, all nullable, `cap` entries / rows each): positions 0 .. m-1 of every non-null buffer describe E, each key once, in one
+ * unspecified order shared by all buffers — the key, its values row, its acc | m and v rows bit for bit, its counter before the call.  A state
+ * buffer for a plane the table lacks is ignored, as mee_export ignores it.  *d_n_out (one DEVICE word, nullable) = m.  max_evict == 0 evicts
+ * nothing, writes 0 and still honours MEE_EVICT_RESET.  The status word is not touched.
+ * Host side as mee_remove: slot handles taken before the call are stale, a partition a training forward left pending is dropped; a pending
+ * mee_apply_prepare is MEE_ERR_INVALID_ARG, like unknown flag bits and a null table; a table without MEE_FLAG_TRACK_HITS, or with bf16 or int8
+ * rows, is MEE_ERR_UNSUPPORTED — all refused before anything is launched or written.  MEE_MEM_HBM or MEE_MEM_HOST_PINNED.
+ * No host synchronisation, no allocation, nothing read back: capturable.  Launches: the zeroing of the operator's counter words and ONE launch that
+ * selects, hands out and tombstones; with MEE_EVICT_LEAST the zeroing and FOUR launches (three histogram passes of an exact radix select over the
+ * counters, 10 + 11 + 11 bits from the top, then the eviction), whatever the table holds.  Each pass reads the key and counter planes once. */
+enum { MEE_EVICT_LEAST = 1u, MEE_EVICT_RESET = 2u };
+int mee_evict(mee_table* t, uint32_t max_hits, uint64_t max_evict, uint32_t flags, int64_t* d_keys_out, float* d_values_out,
+              float* d_state1_out, float* d_state2_out, uint32_t* d_hits_out /* all five nullable */, size_t cap,
+              uint64_t* d_n_out /* device, one word, nullable */, void* stream);
+/* The hit counters by key (MEE_FLAG_TRACK_HITS tables; n <= max_batch; no synchronisation) — what carries LFU state through a checkpoint or a tier
+ * move, and ages it.  mee_hits_find: d_hits_out[i] = the counter of d_keys[i], 0 for an absent or reserved key.  mee_hits_assign: the counter of
+ * every present key becomes d_hits[i]; absent and reserved keys are ignored; a key twice in the batch keeps one of its values, which is
+ * unspecified.  mee_hits_decay: every counter becomes c >> shift (shift >= 32: 0), as mee_admission_decay ages the sketch. */
+int mee_hits_find(const mee_table* t, const int64_t* d_keys, size_t n, uint32_t* d_hits_out, void* stream);
+int mee_hits_assign(mee_table* t, const int64_t* d_keys, size_t n, const uint32_t* d_hits, void* stream);
+int mee_hits_decay(mee_table* t, uint32_t shift, void* stream);
 /* Pooled lookup ("embedding bag"): bag b = d_keys[d_bag_offsets[b] .. d_bag_offsets[b+1]) (n_bags+1 uint64 offsets in DEVICE
  * memory); d_out[b,:] = the rows mee_find would return for the bag's positions, added in position order in fp32
  * (MEE_POOL_SUM) and divided by the bag length (MEE_POOL_MEAN); an empty bag gives zeros.  d_found (nullable) is per KEY,

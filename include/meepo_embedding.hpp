@@ -86,6 +86,11 @@ public:
     void remove(const int64_t* d_keys, size_t n, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_remove(t_, d_keys, n, d_found, stream)); }
     // tier migration (mee_move): the batch's keys that this table holds leave it for dst, rows and optimizer state; d_n_moved: one device word
     void move_to(Table& dst, const int64_t* d_keys, size_t n, uint64_t max_moves = UINT64_MAX, uint8_t* d_moved = nullptr, uint64_t* d_n_moved = nullptr, void* stream = nullptr) { check(mee_move(t_, dst.t_, d_keys, n, max_moves, d_moved, d_n_moved, stream)); }
+    // eviction by the hit counters (mee_evict; MEE_FLAG_TRACK_HITS tables): up to max_evict keys hit at most max_hits times leave, their rows and state handed out; d_n_out: one device word
+    void evict(uint32_t max_hits, uint64_t max_evict, uint32_t flags = 0, int64_t* d_keys_out = nullptr, float* d_values_out = nullptr, float* d_state1_out = nullptr, float* d_state2_out = nullptr, uint32_t* d_hits_out = nullptr, size_t cap = 0, uint64_t* d_n_out = nullptr, void* stream = nullptr) { check(mee_evict(t_, max_hits, max_evict, flags, d_keys_out, d_values_out, d_state1_out, d_state2_out, d_hits_out, cap, d_n_out, stream)); }
+    void hits_find(const int64_t* d_keys, size_t n, uint32_t* d_hits_out, void* stream = nullptr) const { check(mee_hits_find(t_, d_keys, n, d_hits_out, stream)); }
+    void hits_assign(const int64_t* d_keys, size_t n, const uint32_t* d_hits, void* stream = nullptr) { check(mee_hits_assign(t_, d_keys, n, d_hits, stream)); }
+    void hits_decay(uint32_t shift = 1, void* stream = nullptr) { check(mee_hits_decay(t_, shift, stream)); }
     void find_or_insert(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found = nullptr, void* stream = nullptr) { check(mee_find_or_insert(t_, d_keys, n, d_out, d_found, stream)); }
     // the forward of a training step over a growing vocabulary: rows + the slot of every key, for apply_*_located of the same step
     void find_or_insert_located(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, int64_t* d_slots_out, void* stream = nullptr) { check(mee_find_or_insert_located(t_, d_keys, n, d_out, d_found, d_slots_out, stream)); }

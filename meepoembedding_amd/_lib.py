@@ -28,6 +28,7 @@ DTYPE_INT8 = 2                 # ... a row STORAGE type only (mee_table_value_dt
 FLAG_INT8_ROWS = 8   # a serving table whose value plane holds int8 codes and one fp32 scale per row (SPEC.md §3 "Row storage type")
 FLAG_TRACK_HITS, FLAG_ADMISSION, FLAG_BF16_ROWS = 1, 2, 4   # BF16_ROWS: a serving table whose value plane holds bf16 rows (SPEC.md §3 "Row storage type")
 TIER_COUNT_COLD, TIER_COUNT_HOT = 1, 2   # mee_find_pooled_tiered flags
+EVICT_LEAST, EVICT_RESET = 1, 2          # mee_evict flags
 ABI_VERSION = 2   # MEE_ABI_VERSION of include/meepo_embedding.h this loader was written against
 EMPTY_KEY = -(1 << 63)
 RECLAIMED_KEY = EMPTY_KEY + 1
@@ -105,6 +106,11 @@ PROTOTYPES = {
     "mee_find_missing": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "mee_find_counted": (C.c_int, [_vp, _vp, _sz, _vp, _vp, C.c_int, _vp]),
     "mee_hits_scan": (C.c_int, [_vp, _u32, _u32, C.c_int, _vp, _sz, C.POINTER(_sz), _vp]),
+    # eviction by the hit counters: (t, max_hits, max_evict, flags, keys_out, values_out, state1_out, state2_out, hits_out, cap, d_n_out, stream)
+    "mee_evict": (C.c_int, [_vp, _u32, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "mee_hits_find": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
+    "mee_hits_assign": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
+    "mee_hits_decay": (C.c_int, [_vp, _u32, _vp]),
     "mee_insert": (C.c_int, [_vp, _vp, _vp, _sz, _vp]),
     "mee_insert_missing": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "mee_find_or_insert_missing": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),

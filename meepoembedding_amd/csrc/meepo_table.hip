@@ -551,7 +551,7 @@ int mee_table_destroy(mee_table* t) {
     float* planes[] = {t->values, t->s1, t->s2};
     for (float* p : planes)
         if (p) { if (t->value_memory == MEE_MEM_HOST_PINNED) (void)hipHostFree(p); else (void)hipFree(p); }
-    void* dev[] = {t->keys, t->hits, t->sketch, t->g.ent, t->g.sres, t->bs.hidx, t->bs.occ, t->bs.fmask, t->bs.gacc, t->ctr, t->op, t->pack};
+    void* dev[] = {t->keys, t->hits, t->evict, t->sketch, t->g.ent, t->g.sres, t->bs.hidx, t->bs.occ, t->bs.fmask, t->bs.gacc, t->ctr, t->op, t->pack};
     for (void* p : dev) if (p) (void)hipFree(p);
     bucket_scratch_free(t);
     if (t->h_ctr) (void)hipHostFree(t->h_ctr);
@@ -656,6 +656,7 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
     ALLOC(t->keys, t->capacity * sizeof(int64_t));
     t->table_bytes = t->capacity * sizeof(int64_t);
     if (cfg->flags & MEE_FLAG_TRACK_HITS) { ALLOC(t->hits, t->capacity * sizeof(uint32_t)); t->table_bytes += t->capacity * sizeof(uint32_t); }
+    if (t->hits) ALLOC(t->evict, sizeof(EvictScratch));   // mee_evict's scratch: nothing is allocated when an eviction runs
     if (cfg->flags & MEE_FLAG_ADMISSION) {   // SPEC.md §3: W = max(2^12, 2^ceil(log2(capacity / 16)))
         t->sketch_log2w = 12;
         while ((1ull << t->sketch_log2w) < (t->capacity + 15) / 16 && t->sketch_log2w < 30) ++t->sketch_log2w;
@@ -676,7 +677,8 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
     ALLOC(t->ctr, sizeof(Counters)); ALLOC(t->op, sizeof(OpCounters));
     if (t->bf16_rows || t->int8_rows) ALLOC(t->pack, mb * (uint64_t)t->row_bytes);   // the rounded / quantized rows of one insert / assign batch
 #undef ALLOC
-    t->workspace_bytes = (t->pack ? mb * (uint64_t)t->row_bytes : 0) + S * 24 + mb * 9 + (t->bs.gacc ? t->max_part * (uint64_t)t->dim * sizeof(double) : 0) + sizeof(Counters) + sizeof(OpCounters);
+    t->workspace_bytes = (t->pack ? mb * (uint64_t)t->row_bytes : 0) + S * 24 + mb * 9 + (t->bs.gacc ? t->max_part * (uint64_t)t->dim * sizeof(double) : 0) + sizeof(Counters) + sizeof(OpCounters) +
+                         (t->evict ? sizeof(EvictScratch) : 0);
     if ((rc = bucket_scratch_alloc(t)) != MEE_OK) goto bad;   // the bucketed machinery's scratch: partition (every table), pending records (tables with an optimizer); adds to workspace_bytes
     if (hipHostMalloc((void**)&t->h_ctr, sizeof(Counters)) != hipSuccess || hipHostMalloc((void**)&t->h_op, sizeof(OpCounters)) != hipSuccess) {
         rc = fail(MEE_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
@@ -687,6 +689,7 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
         fill_i64_kernel<<<2048, 256, 0, 0>>>(t->keys, t->capacity, kEmpty);
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess && t->hits) e = hipMemsetAsync(t->hits, 0, t->capacity * sizeof(uint32_t), 0);
+        if (e == hipSuccess && t->evict) e = hipMemsetAsync(t->evict, 0, sizeof(EvictScratch), 0);
         if (e == hipSuccess && t->sketch) e = hipMemsetAsync(t->sketch, 0, 3ull * sizeof(uint32_t) << t->sketch_log2w, 0);
         if (e == hipSuccess) e = hipMemsetAsync(t->g.ent, 0, S * 16, 0);
         if (e == hipSuccess) e = hipMemsetAsync(t->g.sres, 0, S * 8, 0);

@@ -17,6 +17,26 @@ struct OpCounters {          // device-resident, zeroed at the start of each op 
     uint32_t pad;
     unsigned long long hist[4];   // mee_probe_histogram: lookups that visit 1 / 2 / 3 / 4 or more buckets
 };
+// ---- eviction by the hit counters (meepo_export.hip, mee_evict): device-resident scratch of a MEE_FLAG_TRACK_HITS table --------------------------
+// MEE_EVICT_LEAST selects by an exact radix select over the 32-bit counters, most significant digit first: 10 + 11 + 11 bits, one histogram launch
+// per digit.  hist[p] = candidates per value of digit p among those the cuts of the digits before p left; cut[p] = what the launch behind histogram p
+// derived from it (every block for itself; block 0 stores it for the launch after that).
+constexpr int kEvictDigits = 3;
+constexpr uint32_t kEvictBins = 2048;   // of the widest digit
+__host__ __device__ constexpr int evict_shift(int digit) { return digit == 0 ? 22 : digit == 1 ? 11 : 0; }
+__host__ __device__ constexpr uint32_t evict_bins(int digit) { return digit == 0 ? 1024u : 2048u; }
+struct EvictCut {
+    unsigned long long k;      // rank still wanted inside the class `prefix` names (1-based); behind the last digit: how many of the tied class to take
+    uint32_t prefix;           // the digits fixed so far, in place; behind the last digit: the threshold value
+    uint32_t valid;            // 0: nothing is evicted (no candidate, or a limit of 0)
+};
+struct EvictScratch {
+    unsigned long long out_ticket, tie_ticket;   // output positions handed out; members of the tied class seen
+    EvictCut cut[kEvictDigits];
+    unsigned long long hist[kEvictDigits][kEvictBins];
+};
+constexpr size_t kEvictTicketBytes = 2 * sizeof(unsigned long long);   // what the threshold form zeroes in front of itself
+
 struct GroupTable {            // S entries, indexed by h
     // One 16-byte entry per h: ent[2h] = key ^ kBias (0 = empty), ent[2h+1] = the count word below.  Key and count share a 64-byte sector,
     // so the claim and the count store of group_kernel, the count load of the apply's main pass and the release (ONE 16-byte store) touch
@@ -112,6 +132,7 @@ struct mee_table {
     int64_t* keys;
     float *values, *s1, *s2;
     uint32_t* hits;             // per-slot access counter (config.flags & MEE_FLAG_TRACK_HITS), else null
+    mee::EvictScratch* evict;   // mee_evict's tickets, histograms and cuts: allocated with `hits`, kept across mee_reserve
     uint32_t* sketch;           // admission policy (config.flags & MEE_FLAG_ADMISSION): count-min sketch, 3 rows of 2^sketch_log2w counters
     uint32_t sketch_log2w;
     // per-batch scratch: group table (S entries) and per-position arrays (max_batch entries)

@@ -514,16 +514,57 @@ class LookupTable:
             if piece[0].numel():
                 yield piece
 
-    def evict(self, max_hits: int = 0, limit: int = 1 << 20, reset: bool = True) -> int:
-        """Eviction by the hit counters (track_hits tables): remove up to `limit` keys looked up at most `max_hits`
-        times since the counters were last reset; returns how many were removed.  Slots become reusable tombstones."""
-        victims = self.hits_scan(0, max_hits, limit, reset=False)
-        removed = 0
-        for s in range(0, victims.numel(), self.max_batch):
-            removed += int(self.remove(victims[s:s + self.max_batch]).sum().item())
-        if reset:
-            self.hits_scan(1, 0, 0, reset=True)   # empty range: nothing listed, counters zeroed
-        return removed
+    def evict(self, max_hits: int = 0, limit: int = 1 << 20, reset: bool = True, *, least: bool = False, spill: bool = False, with_state: bool = True):
+        """Eviction by the hit counters (track_hits tables; SPEC.md §3 evict, mee_evict): up to `limit` keys looked up at most `max_hits` times since
+        the counters were last reset leave the table; their slots become reusable tombstones.  reset: every counter is zeroed afterwards (a new window).
+        least=True: the keys taken are the `limit` LEAST-hit ones among them (exact; ties at the cut unspecified) — what frees n slots of a table
+        near its load limit: evict(0xFFFFFFFF, n, reset=False, least=True).
+        -> how many keys left (one native call, one read-back of the count); spill=True: (keys, values, state1 | None, state2 | None, hits), the
+        evicted keys with their rows, optimizer planes (with_state) and counters before the call, in one shared unspecified order — what a tier
+        behind this table is fed with.  Slot handles taken before the call are stale."""
+        max_hits, limit = int(max_hits), int(limit)
+        if limit < 0 or max_hits < 0:
+            raise ValueError(f"evict: max_hits and limit must be >= 0 (got {max_hits}, {limit})")
+        cap = min(limit, self.capacity) if spill else 0
+        bufs = [None] * 5
+        if spill:
+            rows = lambda: torch.empty((cap, self.dim), dtype=torch.float32, device=self.device)
+            bufs = [torch.empty(cap, dtype=torch.int64, device=self.device), rows(),
+                    rows() if with_state and self.optimizer != OPT_NONE else None, rows() if with_state and self.optimizer == OPT_ADAM else None,
+                    torch.empty(cap, dtype=torch.uint32, device=self.device)]
+        n_out = torch.empty(1, dtype=torch.int64, device=self.device)
+        flags = (_lib.EVICT_LEAST if least else 0) | (_lib.EVICT_RESET if reset else 0)
+        check(_lib.lib().mee_evict(self._h, min(max_hits, 0xFFFFFFFF), min(limit, 0xFFFFFFFFFFFFFFFF), flags, *[None if b is None else b.data_ptr() for b in bufs], cap,
+                                   n_out.data_ptr(), self._s()))
+        self.layout_epoch += 1
+        n = int(n_out.item())
+        return tuple(None if b is None else b[:n] for b in bufs) if spill else n
+
+    def _counts(self, counts: torch.Tensor, n: int) -> torch.Tensor:
+        """the counters of set_hits, checked before any launch: one 32-bit word per key (torch.uint32, or torch.int32 read as its bit pattern)"""
+        if counts.dtype not in (torch.uint32, torch.int32) or counts.device != self.device or counts.numel() != n or not counts.is_contiguous():
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"counts must be contiguous uint32 (or int32) with one entry per key ({n}) on {self.device}")
+        return counts.view(-1)
+
+    def hits_of(self, keys: torch.Tensor) -> torch.Tensor:
+        """The hit counter of each key (track_hits tables; mee_hits_find) -> uint32 [n]; 0 for an absent or reserved key."""
+        k = self._keys(keys)
+        out = torch.empty(k.numel(), dtype=torch.uint32, device=self.device)
+        check(_lib.lib().mee_hits_find(self._h, k.data_ptr(), k.numel(), out.data_ptr(), self._s()))
+        return out
+
+    def set_hits(self, keys: torch.Tensor, counts: torch.Tensor) -> None:
+        """Set the hit counter of each present key (mee_hits_assign): LFU state restored from a checkpoint or carried over a tier move.  Absent and
+        reserved keys are ignored; of a key that occurs twice one value stays."""
+        k = self._keys(keys)
+        c = self._counts(counts, k.numel())
+        check(_lib.lib().mee_hits_assign(self._h, k.data_ptr(), k.numel(), c.data_ptr(), self._s()))
+
+    def hits_decay(self, shift: int = 1) -> None:
+        """Every hit counter >>= shift (>= 32: zero): ages the counters instead of resetting them, so that least-hit eviction sees more than one window."""
+        if int(shift) < 0:
+            raise ValueError(f"hits_decay: shift must be >= 0 (got {shift})")
+        check(_lib.lib().mee_hits_decay(self._h, min(int(shift), 32), self._s()))
 
     def save(self, path: str, chunk_slots: int = 1 << 22, extra: dict | None = None) -> int:
         """Write a checkpoint directory (see checkpoint.py for the format); returns the number of pairs written."""

@@ -372,6 +372,14 @@ class TieredLookupTable:
         self._hot_keys_ub = max(0, self._hot_keys_ub - moved)
         return moved
 
+    def evict_cold(self, n: int, spill: bool = False):
+        """When the cold tier is full too: its `n` least-hit keys leave the pair (LookupTable.evict(least=True) on the cold table; the counters stay
+        as they are, age them with cold.hits_decay).  -> how many left; spill=True: (keys, values, state1 | None, state2 | None, hits) of the evicted
+        keys, for a tier behind this pair.  Needs a cold table with hit counters."""
+        if not getattr(self.cold, "track_hits", False):
+            raise RuntimeError("evict_cold() needs a cold table created with track_hits=True")
+        return self.cold.evict(0xFFFFFFFF, int(n), reset=False, least=True, spill=spill)
+
 
 class TieredTableGroup:
     """An embedding-bag COLLECTION of hot/cold pairs (SPEC.md §3 "Tiering"): `pairs` are TieredLookupTables of one device and one dim, bag b of a
@@ -443,6 +451,11 @@ class TieredTableGroup:
 
     def size(self) -> int:
         return sum(p.size() for p in self.tables)
+
+    def evict_cold(self, n_per_pair: int, spill: bool = False) -> list:
+        """TieredLookupTable.evict_cold(n_per_pair, spill) of every pair -> its result per pair.  A loop over the pairs: eviction is rare, unlike
+        the step, and every member scans its own cold table anyway."""
+        return [p.evict_cold(n_per_pair, spill) for p in self.tables]
 
     def rebalance(self, max_moves: int = 1 << 20) -> list[tuple[int, int]]:
         """TieredLookupTable.rebalance() of every pair -> [(promoted, demoted)] per pair.  Between steps, like the pair's own.  Native pairs: every
