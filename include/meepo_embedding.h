@@ -343,7 +343,7 @@ int mee_probe_histogram(const mee_table* t, const int64_t* d_keys, size_t n, uin
  * untouched).  Results are identical to mee_find on each table with its segment; the launch latency floor is paid once
  * instead of n_tables times.  Asynchronous on `stream`; after mee_reserve on a member the next call re-reads that
  * table's planes (one stream synchronisation).  The group does not own the tables: destroy it before them.  Calls on one
- * group that use its scratch (mee_group_find_or_insert without d_found, mee_group_apply_*) must be ordered by the caller;
+ * group that use its scratch (mee_group_find_or_insert / _admit without d_found, mee_group_apply_*) must be ordered by the caller;
  * mee_find_grouped / mee_group_find_pooled calls may run concurrently on several streams.
  *
  * Row storage: a group holds fp32-row tables, or ONLY tables created with MEE_FLAG_BF16_ROWS — a bf16-row group, the serving form of a collection.  A
@@ -354,7 +354,7 @@ int mee_probe_histogram(const mee_table* t, const int64_t* d_keys, size_t n, uin
  * each member's own default row included.  The operators it has: mee_find_grouped / _as (fp32 out widens exactly, bf16 out returns the stored bits),
  * mee_group_find_pooled / _as without weights (SUM | MEAN; rows widened and added in fp32 in position order, the finished bag row rounded once for bf16
  * out), mee_group_find_pooled_jagged, mee_group_value_dtype, mee_group_destroy; mee_reserve on a member between lookups keeps working.  Everything else
- * — mee_group_find_or_insert / _as, every mee_group_apply_*, mee_group_find_pooled_weighted and a non-null d_weights of mee_group_find_pooled_as,
+ * — mee_group_find_or_insert / _as / _admit, mee_group_admission_decay, every mee_group_apply_*, mee_group_find_pooled_weighted and a non-null d_weights of mee_group_find_pooled_as,
  * mee_group_pooled_weighted_backward, and a non-null d_located_out of any pooled form (located rows exist for the backward, which this group does not
  * have) — returns MEE_ERR_UNSUPPORTED before anything is launched or written; mee_group_set_tuning answers as for any group without an apply. */
 typedef struct mee_group mee_group;
@@ -371,6 +371,22 @@ int mee_find_grouped(mee_group* g, const int64_t* d_keys, const uint64_t* d_offs
  * table's initial row / optimizer state first; d_found (nullable when n <= max_apply_batch) = present before the call. */
 int mee_group_find_or_insert(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, float* d_out, uint8_t* d_found,
                              void* stream);
+/* Admission over the jagged layout: mee_find_or_insert_admit of every member on its segment, each member counting in ITS OWN sketch (the group
+ * keeps none), in three launches whatever the number of tables — the grouped find, one counting launch, one creation launch that reads the
+ * final counters itself.  A position inside [d_offsets[0], d_offsets[n_tables]) and below n whose key is absent and not reserved adds 1 to its
+ * member's three counters (a key that occurs c times adds c); then the key is created — initial row, initial optimizer state, all its
+ * occurrences return that row — when the minimum of the three is >= the member's threshold, and returns the default row and stays absent
+ * otherwise.  Positions outside the segments are neither written, counted nor created.  The threshold is min_count, or d_min_counts[member]
+ * when d_min_counts (DEVICE memory, n_tables entries, nullable) is given; 0 or 1 admits at first sight: that segment gets
+ * mee_group_find_or_insert's result and its sketch still counts.  out_dtype: MEE_DTYPE_F32 or MEE_DTYPE_BF16 (the fp32 result rounded once;
+ * the tables stay fp32).  d_found (nullable when n <= max_apply_batch, else MEE_ERR_BATCH_TOO_LARGE) = present before the call.  A tombstone
+ * value in a segment sets MEE_STATUS_RESERVED_KEY on that member, MEE_STATUS_TABLE_FULL lands on the member that had no room.  No host
+ * synchronisation, no allocation, capturable; no limit on n beyond mee_group_find_or_insert's.  Refused before anything is launched or written:
+ * a bf16-row group and a member created without MEE_FLAG_ADMISSION (MEE_ERR_UNSUPPORTED, the message names the member), null arguments
+ * (MEE_ERR_INVALID_ARG).  mee_group_admission_decay: mee_admission_decay of every member, one launch. */
+int mee_group_find_or_insert_admit(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype,
+                                   uint8_t* d_found, uint32_t min_count, const uint32_t* d_min_counts, void* stream);
+int mee_group_admission_decay(mee_group* g, uint32_t shift, void* stream);
 /* One sparse-optimizer step over the same jagged layout (groups created with max_apply_batch >= n; all members have the
  * same optimizer): identical to mee_apply_* on each table with its segment of keys and grads (absent keys ignored,
  * duplicates of a key inside its segment summed in fp64 and applied once), in a fixed number of launches whatever the

@@ -41,6 +41,7 @@ struct TableOptions {
     uint64_t init_seed = 0;
     uint32_t value_memory = MEE_MEM_HBM;  // MEE_MEM_HOST_PINNED = cold tier (rows in pinned host DRAM)
     bool bf16_rows = false;     // MEE_FLAG_BF16_ROWS: a serving table that stores its rows as bf16 (no optimizer, dim % 8 == 0, HBM)
+    bool admission = false;     // MEE_FLAG_ADMISSION: the table keeps a count-min sketch (mee_find_or_insert_admit, Group::find_or_insert_admit)
     bool int8_rows = false;     // MEE_FLAG_INT8_ROWS: a serving table that stores its rows as int8 codes + one fp32 scale (no optimizer, dim % 16 == 0, HBM; not with bf16_rows)
 };
 
@@ -52,7 +53,7 @@ public:
         c.struct_size = sizeof c; c.device = o.device; c.capacity = o.capacity; c.dim = o.dim; c.optimizer = o.optimizer;
         c.max_batch = o.max_batch; c.default_value = o.default_value; c.initial_accumulator = o.initial_accumulator;
         c.initializer = o.initializer; c.init_scale = o.init_scale; c.init_seed = o.init_seed; c.value_memory = o.value_memory;
-        c.flags = (o.bf16_rows ? MEE_FLAG_BF16_ROWS : 0u) | (o.int8_rows ? MEE_FLAG_INT8_ROWS : 0u);
+        c.flags = (o.bf16_rows ? MEE_FLAG_BF16_ROWS : 0u) | (o.int8_rows ? MEE_FLAG_INT8_ROWS : 0u) | (o.admission ? MEE_FLAG_ADMISSION : 0u);
         check(mee_table_create(&c, &t_));
     }
     ~Table() { if (t_) mee_table_destroy(t_); }
@@ -183,6 +184,13 @@ public:
     // the grouped lookups with fp32 or bf16 result rows (MEE_DTYPE_*): mee_find_grouped_as / mee_group_find_or_insert_as / mee_group_find_pooled_as
     void find_as(const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, void* stream = nullptr) { check(mee_find_grouped_as(g_, d_keys, d_offsets, n, d_out, out_dtype, d_found, stream)); }
     void find_or_insert_as(const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, void* stream = nullptr) { check(mee_group_find_or_insert_as(g_, d_keys, d_offsets, n, d_out, out_dtype, d_found, stream)); }
+    // admission over the collection (mee_group_find_or_insert_admit): every member counts absent keys in its own sketch and creates a key once its
+    // estimate reached min_count — or d_min_counts[member] (device, n_tables entries) when given; admission_decay ages every member's sketch
+    void find_or_insert_admit(const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, uint32_t min_count,
+                              const uint32_t* d_min_counts = nullptr, void* stream = nullptr) {
+        check(mee_group_find_or_insert_admit(g_, d_keys, d_offsets, n, d_out, out_dtype, d_found, min_count, d_min_counts, stream));
+    }
+    void admission_decay(uint32_t shift = 1, void* stream = nullptr) { check(mee_group_admission_decay(g_, shift, stream)); }
     void find_pooled_as(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights, void* d_out, uint32_t out_dtype, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, int mode = MEE_POOL_SUM, void* stream = nullptr) {
         check(mee_group_find_pooled_as(g_, d_keys, n, d_bag_offsets, bags_per_table, d_weights, d_out, out_dtype, d_found, d_located_out, mode, stream));
     }

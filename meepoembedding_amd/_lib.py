@@ -177,6 +177,8 @@ PROTOTYPES = {
     "mee_apply_adam_located": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32, _u64, _vp]),
     "mee_find_or_insert_admit": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _u32, _vp]),
     "mee_admission_decay": (C.c_int, [_vp, _u32, _vp]),
+    "mee_group_find_or_insert_admit": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "mee_group_admission_decay": (C.c_int, [_vp, _u32, _vp]),
     "mee_locate": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "mee_table_plane": (C.c_int, [_vp, _u32, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_u32)]),
     "mee_device_calibration": (C.c_int, [C.c_int32, C.POINTER(Calibration)]),

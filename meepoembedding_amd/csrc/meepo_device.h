@@ -45,6 +45,11 @@ __host__ __device__ __forceinline__ uint64_t mix64b(uint64_t x) {
     x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
     x ^= x >> 33; return x;
 }
+// admission policy (SPEC.md §3 find_or_insert_admit): the counter of `key` in row 0..2 of a count-min sketch of 3 rows of 2^log2w counters
+__device__ __forceinline__ uint32_t sketch_index(int64_t key, int row, uint32_t log2w) {
+    constexpr uint64_t A[3] = {0x9E3779B97F4A7C15ull, 0xC2B2AE3D27D4EB4Full, 0x165667B19E3779F9ull};
+    return (uint32_t)(mix64((uint64_t)key ^ A[row]) >> (64 - log2w)) + ((uint32_t)row << log2w);
+}
 __device__ __forceinline__ uint64_t bucket_of(int64_t key, uint64_t nb) { return __umul64hi(mix64((uint64_t)key), nb); }
 // SPEC.md §1/§2: stride (in buckets) of a key's probe sequence — double hashing, 1 <= stride < nb
 __device__ __forceinline__ uint64_t step_of(int64_t key, uint64_t nb) { return nb > 1 ? 1 + __umul64hi(mix64b((uint64_t)key), nb - 1) : 1; }

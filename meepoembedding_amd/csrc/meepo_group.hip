@@ -10,6 +10,7 @@
 // Reference anchor: /root/reference/README.md:2 ("lookuptable-style … Embedding designed for recommendation systems").
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <new>
 
@@ -354,6 +355,100 @@ __global__ __launch_bounds__(256) void ensure_grouped_kernel(const GroupDesc* __
     }
 }
 
+// ensure_grouped_kernel's sibling for mee_group_find_or_insert_admit, the creation with the decision fused in: the tile of a missing position first
+// reads its member's three sketch counters — final since the kernel boundary behind sketch_add_grouped_kernel, and not written here — and goes on to
+// tile_locate only when their minimum reached that member's threshold (min_counts[member] when given, else min_count); otherwise the position keeps
+// the default row the find pass wrote.  Everything else is ensure_grouped_kernel's.  A sibling, not an instance: the kernel above keeps its name,
+// its arguments and its machine code.
+template <bool BF16>
+__global__ __launch_bounds__(256) void ensure_admit_grouped_kernel(const GroupDesc* __restrict__ desc, const GroupInit* __restrict__ init,
+                                                                   const GroupAdmit* __restrict__ admit, uint32_t n_tables,
+                                                                   const uint64_t* __restrict__ offsets, const int64_t* __restrict__ keys, uint64_t n,
+                                                                   const uint8_t* __restrict__ found, uint32_t dim4, float4* __restrict__ out,
+                                                                   uint32_t min_count, const uint32_t* __restrict__ min_counts) {
+    __shared__ uint64_t loff[kMaxGroupTables + 1];
+    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) loff[j] = offsets[j];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t base = wave * 4; base < n; base += n_waves * 4) {
+        const uint64_t i = base + tile;
+        bool act = i < n && i >= loff[0] && i < loff[n_tables] && found[i] == 0;
+        const int64_t key = act ? keys[i] : kEmpty;
+        const bool tomb = act && key == kReclaimed;   // a reserved key in the batch: flagged like mee_find_or_insert does (EMPTY = padding, silent)
+        act = act && !reserved_key(key);
+        if (!__any(act || tomb)) continue;  // wave-uniform: nothing missing here (the steady state of a trained vocabulary)
+        uint32_t lo = 0, hi = n_tables;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (loff[mid] <= i) lo = mid; else hi = mid;
+        }
+        if (tomb && tl == 0) atomicOr(init[lo].status, (uint32_t)MEE_STATUS_RESERVED_KEY);
+        if (act) {   // the 16 lanes of a tile read the same three counters: one request each
+            const GroupAdmit a = admit[lo];
+            uint32_t est = 0xFFFFFFFFu;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) est = min(est, a.sketch[sketch_index(key, r, a.log2w)]);
+            act = est >= (min_counts ? min_counts[lo] : min_count);
+        }
+        if (!__any(act)) continue;  // wave-uniform: counted, nobody admitted
+        const GroupDesc d = desc[act ? lo : 0];
+        bool is_new, full;
+        const int64_t slot = tile_locate<true, true>(const_cast<int64_t*>(d.tkeys), d.nb, key, act, tile, tl, is_new, full);
+        if (act) {
+            const GroupInit in = init[lo];
+            if (slot >= 0) {
+                for (uint32_t c = tl; c < dim4; c += 16) {
+                    const float4 row = initial_row4(key, c * 4, in.initializer, in.init_scale, in.init_seed, d.defv);
+                    if constexpr (BF16) store_bf16x4<true>(out, i * dim4 + c, row); else out[i * dim4 + c] = row;
+                    if (is_new) {
+                        d.values[(uint64_t)slot * dim4 + c] = row;
+                        if (in.optimizer == MEE_OPT_ADAGRAD) d.s1[(uint64_t)slot * dim4 + c] = make_float4(in.init_acc, in.init_acc, in.init_acc, in.init_acc);
+                        if (in.optimizer == MEE_OPT_ADAM) {
+                            d.s1[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                            d.s2[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                        }
+                    }
+                }
+                if (is_new && in.hits && tl == 0) in.hits[slot] = 0;
+            }
+            if (full && tl == 0) atomicOr(in.status, (uint32_t)MEE_STATUS_TABLE_FULL);
+        }
+    }
+}
+
+// Grouped admission, the counting launch (between the find and the creation of mee_group_find_or_insert_admit): one thread per position of the jagged
+// batch, positions indexed in 64 bits.  A position inside [offsets[0], offsets[n_tables]) and below n whose found byte is 0 and whose key is not
+// reserved adds 1 to the three counters of ITS member's sketch (the segment search of ensure_grouped_kernel, offsets staged in LDS); a key that occurs
+// c times adds c.  Integer atomicAdd commutes: the sketch after the launch does not depend on the order.
+__global__ __launch_bounds__(256) void sketch_add_grouped_kernel(const GroupAdmit* __restrict__ admit, uint32_t n_tables, const uint64_t* __restrict__ offsets,
+                                                                 const int64_t* __restrict__ keys, uint64_t n, const uint8_t* __restrict__ found) {
+    __shared__ uint64_t loff[kMaxGroupTables + 1];
+    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) loff[j] = offsets[j];
+    __syncthreads();
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        if (i < loff[0] || i >= loff[n_tables] || found[i]) continue;
+        const int64_t k = keys[i];
+        if (reserved_key(k)) continue;
+        uint32_t lo = 0, hi = n_tables;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (loff[mid] <= i) lo = mid; else hi = mid;
+        }
+        const GroupAdmit a = admit[lo];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) atomicAdd(&a.sketch[sketch_index(k, r, a.log2w)], 1u);
+    }
+}
+// mee_group_admission_decay: blockIdx.y = member, every counter of its sketch >>= shift (>= 32: zero), as sketch_decay_kernel ages one table's
+__global__ __launch_bounds__(256) void sketch_decay_grouped_kernel(const GroupAdmit* __restrict__ admit, uint32_t shift) {
+    const GroupAdmit a = admit[blockIdx.y];
+    const uint64_t n = 3ull << a.log2w;
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        a.sketch[i] = shift >= 32 ? 0u : a.sketch[i] >> shift;
+}
+
 // ensure_grouped_kernel's sibling for a GROUP of hot/cold pairs (mee_group_ensure_tiered): every position the found mask leaves missing claims (or
 // finds, when a duplicate got there first) its key's slot in ONE tier of its member — the cold table where to_cold[member] != 0 (null: every member
 // creates hot) — and the tile whose CAS created the key writes what mee_find_or_insert_missing on that table writes: the initial row from THAT table's
@@ -478,16 +573,19 @@ static int upload_descriptors(mee_group* g) {
     std::vector<GroupDesc> h(g->n_tables);
     std::vector<GroupInit> hi(g->n_tables);
     std::vector<MoveTable> hm(g->n_tables);
+    std::vector<GroupAdmit> ha(g->n_tables);
     for (uint32_t j = 0; j < g->n_tables; ++j) {
         const TableView v = table_view(g->tables[j]);
         h[j] = GroupDesc{v.keys, (float4*)v.values, (float4*)v.s1, (float4*)v.s2, v.nb, v.default_value, 0};   // (a bf16-row member: its bf16 plane behind the same pointer — the launch knows, g->bf16_rows)
         hi[j] = GroupInit{v.init_seed, v.status, v.hits, v.initializer, v.optimizer, v.init_scale, v.init_acc};
         hm[j] = MoveTable{const_cast<int64_t*>(v.keys), {(float4*)v.values, (float4*)v.s1, (float4*)v.s2}, v.nb, v.status, v.hits, v.batch_slots};
+        ha[j] = GroupAdmit{v.sketch, v.sketch_log2w, 0};
         g->generations[j] = v.generation;
     }
     MEE_HIP(hipMemcpy(g->d_desc, h.data(), h.size() * sizeof(GroupDesc), hipMemcpyHostToDevice));  // synchronous, rare
     MEE_HIP(hipMemcpy(g->d_init, hi.data(), hi.size() * sizeof(GroupInit), hipMemcpyHostToDevice));
     MEE_HIP(hipMemcpy(g->d_move, hm.data(), hm.size() * sizeof(MoveTable), hipMemcpyHostToDevice));
+    MEE_HIP(hipMemcpy(g->d_admit, ha.data(), ha.size() * sizeof(GroupAdmit), hipMemcpyHostToDevice));
     return MEE_OK;
 }
 
@@ -538,13 +636,16 @@ int mee_group_create(mee_table* const* tables, uint32_t n_tables, uint64_t max_a
     if (!g) return fail(MEE_ERR_OUT_OF_MEMORY, "host allocation failed");
     g->device = v0.device; g->n_tables = n_tables; g->dim = v0.dim; g->dim4 = v0.dim4; g->bf16_rows = v0.bf16_rows; g->d_desc = nullptr;
     g->optimizer = v0.optimizer; g->max_apply_batch = max_apply_batch; g->scratch = nullptr; g->d_gslot = nullptr;
-    g->d_init = nullptr; g->d_move = nullptr; g->d_fmask = nullptr;
+    g->d_init = nullptr; g->d_move = nullptr; g->d_fmask = nullptr; g->d_admit = nullptr; g->no_admission = -1;
+    for (uint32_t j = n_tables; j-- > 0;)
+        if (!table_view(tables[j]).sketch) g->no_admission = (int)j;
     g->tables.assign(tables, tables + n_tables);
     g->generations.assign(n_tables, 0);
     DeviceGuard guard(g->device);
     hipError_t e = hipMalloc((void**)&g->d_desc, n_tables * sizeof(GroupDesc));
     if (e == hipSuccess) e = hipMalloc((void**)&g->d_init, n_tables * sizeof(GroupInit));
     if (e == hipSuccess) e = hipMalloc((void**)&g->d_move, n_tables * sizeof(MoveTable));
+    if (e == hipSuccess) e = hipMalloc((void**)&g->d_admit, n_tables * sizeof(GroupAdmit));
     if (e == hipSuccess && max_apply_batch) e = hipMalloc((void**)&g->d_fmask, max_apply_batch);
     if (e != hipSuccess) { mee_group_destroy(g); return fail(MEE_ERR_OUT_OF_MEMORY, "hipMalloc(group descriptors): %s", hipGetErrorString(e)); }
     if (int rc = upload_descriptors(g)) { mee_group_destroy(g); return rc; }
@@ -581,6 +682,7 @@ int mee_group_destroy(mee_group* g) {
     (void)hipFree(g->d_desc);
     (void)hipFree(g->d_init);
     (void)hipFree(g->d_move);
+    (void)hipFree(g->d_admit);
     (void)hipFree(g->d_fmask);
     (void)hipFree(g->d_gslot);
     if (g->scratch) mee_table_destroy(g->scratch);
@@ -671,6 +773,57 @@ static int group_find_or_insert_common(mee_group* g, const int64_t* d_keys, cons
     // 2) missing positions create their key (one creator per distinct key: the CAS decides) and return its initial row
     if (out_dtype == MEE_DTYPE_BF16) ensure_grouped_kernel<true><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_init, g->n_tables, d_offsets, d_keys, n, d_found, g->dim4, (float4*)d_out);
     else ensure_grouped_kernel<false><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_init, g->n_tables, d_offsets, d_keys, n, d_found, g->dim4, (float4*)d_out);
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+// every member has a sketch, or MEE_ERR_UNSUPPORTED naming the first that has none
+static int group_admission_check(const mee_group* g, const char* name) {
+    MEE_FP32_GROUP_ONLY(g, name);
+    if (g && g->no_admission >= 0)
+        return fail(MEE_ERR_UNSUPPORTED, "%s: member %d was created without MEE_FLAG_ADMISSION (every member needs its own sketch)", name, g->no_admission);
+    return MEE_OK;
+}
+
+extern "C" int mee_group_find_or_insert_admit(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
+                                              uint32_t min_count, const uint32_t* d_min_counts, void* stream) {
+    MEE_RANGE("mee_group_find_or_insert_admit");
+    const char* name = "mee_group_find_or_insert_admit";
+    if (int rc = group_admission_check(g, name)) return rc;
+    if (!g || !d_offsets || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
+    if (n == 0) return MEE_OK;
+    if (!d_found) {
+        if (n > g->max_apply_batch)
+            return fail(MEE_ERR_BATCH_TOO_LARGE, "%s: without a found buffer n=%zu must be <= max_apply_batch=%llu", name, n, (unsigned long long)g->max_apply_batch);
+        d_found = g->d_fmask;
+    }
+    if (int rc = group_refresh(g, stream)) return rc;
+    DeviceGuard guard(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    // 1) the ordinary grouped find serves every stored key and yields the present-before mask
+    if (int rc = launch_find_grouped(g, d_keys, d_offsets, n, d_out, out_dtype, d_found, st)) return rc;
+    // 2) every missing position counts its key in its member's sketch
+    sketch_add_grouped_kernel<<<grid_for(n, 256, 4096), 256, 0, st>>>(g->d_admit, g->n_tables, d_offsets, d_keys, n, d_found);
+    // 3) the creation of mee_group_find_or_insert, for the positions whose estimate reached their member's threshold
+    with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto b16) {
+        ensure_admit_grouped_kernel<b16><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_init, g->d_admit, g->n_tables, d_offsets, d_keys, n, d_found, g->dim4, (float4*)d_out,
+                                                                               min_count, d_min_counts);
+    });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+extern "C" int mee_group_admission_decay(mee_group* g, uint32_t shift, void* stream) {
+    MEE_RANGE("mee_group_admission_decay");
+    if (int rc = group_admission_check(g, "mee_group_admission_decay")) return rc;
+    if (!g) return fail(MEE_ERR_INVALID_ARG, "mee_group_admission_decay: null group");
+    if (int rc = group_refresh(g, stream)) return rc;
+    DeviceGuard guard(g->device);
+    uint32_t log2w = 0;
+    for (mee_table* t : g->tables) log2w = std::max(log2w, table_view(t).sketch_log2w);
+    const unsigned per_member = g->n_tables >= 2048 / 4 ? 4 : 2048 / g->n_tables;   // ~2048 blocks in all, as mee_admission_decay launches for one table
+    sketch_decay_grouped_kernel<<<dim3(grid_for(3ull << log2w, 256, per_member), g->n_tables), 256, 0, (hipStream_t)stream>>>(g->d_admit, shift);
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }

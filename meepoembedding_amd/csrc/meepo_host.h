@@ -83,6 +83,8 @@ struct TableView {
     uint32_t* hits;
     bool bf16_rows;        // the value plane holds bf16 rows (MEE_FLAG_BF16_ROWS): `values` is then dim4 8-byte groups per slot
     long long* batch_slots;   // the per-position slot list of the table's per-batch scratch (>= 2 * max_batch entries: insert, remove and move borrow it)
+    uint32_t* sketch;         // the admission sketch (MEE_FLAG_ADMISSION; null without): 3 rows of 2^sketch_log2w counters
+    uint32_t sketch_log2w;
 };
 TableView table_view(const mee_table* t);
 // The operators a serving table — bf16 rows or int8 rows — does not have (include/meepo_embedding.h, MEE_FLAG_BF16_ROWS / MEE_FLAG_INT8_ROWS) — and every
@@ -110,6 +112,10 @@ struct GroupInit {   // per member, device resident: what creating a key in that
     uint32_t* hits;
     uint32_t initializer, optimizer;
     float init_scale, init_acc;
+};
+struct GroupAdmit {   // per member, device resident: its admission sketch (grouped find_or_insert_admit / admission_decay); null without MEE_FLAG_ADMISSION
+    uint32_t* sketch;
+    uint32_t log2w, pad;
 };
 struct MoveTable {   // one side of a move (meepo_move.hip): a kernel argument for mee_move, per member and device resident for mee_group_move
     int64_t* tkeys;
@@ -164,6 +170,8 @@ struct mee_group {
     mee::GroupDesc* d_desc;
     mee::GroupInit* d_init;
     mee::MoveTable* d_move;   // the members as mee_group_move sees them, uploaded with the descriptors
+    mee::GroupAdmit* d_admit; // the members' admission sketches, uploaded with the descriptors
+    int no_admission;      // the first member created without MEE_FLAG_ADMISSION, -1 when every member has a sketch
     uint8_t* d_fmask;      // [max_apply_batch] found mask of grouped find_or_insert when the caller passes none
     // grouped apply (max_apply_batch > 0): a scratch-only table whose group table / per-position arrays serve the whole
     // jagged batch, and the located rows of the batch

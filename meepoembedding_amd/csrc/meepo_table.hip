@@ -321,10 +321,7 @@ __global__ __launch_bounds__(256) void insert_settle_kernel(float4* values, uint
 }
 
 // ---- admission policy (SPEC.md §3 find_or_insert_admit): a count-min sketch of how often ABSENT keys were asked for ------------
-__device__ __forceinline__ uint32_t sketch_index(int64_t key, int row, uint32_t log2w) {
-    constexpr uint64_t A[3] = {0x9E3779B97F4A7C15ull, 0xC2B2AE3D27D4EB4Full, 0x165667B19E3779F9ull};
-    return (uint32_t)(mix64((uint64_t)key ^ A[row]) >> (64 - log2w)) + ((uint32_t)row << log2w);
-}
+// (sketch_index, the counter of a key in row 0..2: meepo_device.h — the grouped admission of meepo_group.hip shares it)
 // every position whose key is absent (found byte 0, key not reserved) adds 1 to its three counters
 __global__ __launch_bounds__(256) void sketch_add_kernel(const int64_t* __restrict__ keys, const uint8_t* __restrict__ found, uint64_t n,
                                                          uint32_t* sketch, uint32_t log2w) {
@@ -472,7 +469,7 @@ template <int P> __global__ __launch_bounds__(256) void ensure_direct_bf16_kerne
 // =========================================================================================================
 TableView table_view(const mee_table* t) {
     return TableView{t->device, t->keys, t->values, t->nb, t->dim, t->dim4, t->default_value, t->generation, t->s1, t->s2, t->optimizer,
-                     t->initializer, t->init_scale, t->init_acc, t->init_seed, &t->ctr->status, t->hits, t->bf16_rows, t->g.sres};
+                     t->initializer, t->init_scale, t->init_acc, t->init_seed, &t->ctr->status, t->hits, t->bf16_rows, t->g.sres, t->sketch, t->sketch_log2w};
 }
 
 int refuse_narrow_rows(const mee_table* t, const char* op, bool bf16_too) {

@@ -42,6 +42,36 @@ def _check_out_dtype(table, out_dtype: torch.dtype, pooled: bool = False) -> tor
     return out_dtype
 
 
+def _check_min_count(table, min_count, layer: str, creates: bool = True):
+    """A layer's min_count (admission, SPEC.md §3 find_or_insert_admit): None, or a threshold for a LookupTable or a uniform fp32 TableGroup whose
+    tables were all created with admission=True.  Everything else is refused at construction, before any launch, saying which case it is."""
+    if min_count is None:
+        return None
+    from .table import LookupTable, TableGroup
+    name = type(table).__name__
+    if not creates:
+        raise ValueError(f"{layer}: min_count needs create_missing=True (admission decides when an unseen id is created; without creation there is nothing to decide)")
+    if isinstance(min_count, bool) or not isinstance(min_count, int) or not 0 <= min_count < 1 << 32:
+        raise ValueError(f"{layer}: min_count must be an int in [0, 2^32) (got {min_count!r})")
+    if "Tiered" in name:
+        raise ValueError(f"{layer}: min_count over {name}: a hot/cold pair has no admission (TieredLookupTable has none, so a group of pairs has no per-member definition)")
+    if getattr(table, "mixed_dims", False):
+        raise ValueError(f"{layer}: min_count over {name}: a mixed-width group creates unseen ids inside its pooled launch, which has no admission")
+    if not isinstance(table, (LookupTable, TableGroup)):
+        raise ValueError(f"{layer}: min_count over {name}: admission exists on a LookupTable and on a TableGroup on one device, not on sharded or peer-mapped tables")
+    members = table.tables if isinstance(table, TableGroup) else [table]
+    for j, t in enumerate(members):
+        if not t._opts["admission"]:
+            raise ValueError(f"{layer}: min_count needs every table created with admission=True (" +
+                             (f"member {j} of the group has no sketch)" if isinstance(table, TableGroup) else "this table has no sketch)"))
+    return min_count
+
+
+def _admit_kw(layer) -> dict:
+    """the creating lookup's min_count keyword — only when the layer has one, so tables without the keyword keep working"""
+    return {} if layer.min_count is None else {"min_count": layer.min_count}
+
+
 def _dtype_kw(layer) -> dict:
     """the lookup's out_dtype keyword — only when it is not the default, so tables without the keyword keep working at fp32"""
     return {} if layer.out_dtype == torch.float32 else {"out_dtype": layer.out_dtype}
@@ -58,7 +88,7 @@ def _layer(table_id: int) -> "DynamicEmbedding":
 def lookup(keys: torch.Tensor, anchor: torch.Tensor, table_id: int, insert_missing: bool) -> torch.Tensor:
     layer = _layer(table_id)
     flat = keys.reshape(-1)
-    rows, _ = layer.table.find_or_insert(flat) if insert_missing else layer.table.find(flat)
+    rows, _ = layer.table.find_or_insert(flat, **_admit_kw(layer)) if insert_missing else layer.table.find(flat)
     return rows.reshape(*keys.shape, layer.table.dim).clone()   # never alias the table's / exchange's buffers
 
 
@@ -188,9 +218,9 @@ def lookup_pooled(keys: torch.Tensor, bag_offsets: torch.Tensor, anchor: torch.T
         # dynamic vocabulary: unseen ids enter their table (hashed initial row + optimizer state) before the pooled lookup
         if hasattr(layer.table, "apply_pooled"):
             bpt = (bag_offsets.numel() - 1) // len(layer.table.tables)
-            layer.table.find_or_insert(keys, bag_offsets[::bpt].contiguous())
+            layer.table.find_or_insert(keys, bag_offsets[::bpt].contiguous(), **_admit_kw(layer))
         else:
-            layer.table.find_or_insert(keys)
+            layer.table.find_or_insert(keys, **_admit_kw(layer))
     if hasattr(layer.table, "apply_pooled"):   # a TableGroup
         located = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
         out, _ = layer.table.find_pooled(keys, bag_offsets, "mean" if mean else "sum", located=located, **_dtype_kw(layer))
@@ -319,9 +349,9 @@ def lookup_pooled_weighted(keys: torch.Tensor, bag_offsets: torch.Tensor, weight
     if layer.create_missing and layer.training and keys.numel():
         if hasattr(layer.table, "apply_pooled"):
             bpt = (bag_offsets.numel() - 1) // len(layer.table.tables)
-            layer.table.find_or_insert(keys, bag_offsets[::bpt].contiguous())
+            layer.table.find_or_insert(keys, bag_offsets[::bpt].contiguous(), **_admit_kw(layer))
         else:
-            layer.table.find_or_insert(keys)
+            layer.table.find_or_insert(keys, **_admit_kw(layer))
     located = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
     out, _ = layer.table.find_pooled(keys, bag_offsets, "sum", weights=weights.contiguous(), located=located, **_dtype_kw(layer))
     return out, located
@@ -380,7 +410,8 @@ lookup_pooled_weighted.register_autograd(_backward_pooled_weighted, setup_contex
 @torch.library.custom_op("meepo::lookup_jagged", mutates_args=())
 def lookup_jagged(keys: torch.Tensor, offsets: torch.Tensor, anchor: torch.Tensor, table_id: int, insert_missing: bool) -> torch.Tensor:
     layer = _layer(table_id)
-    rows, _ = layer.group.find_or_insert(keys, offsets, **_dtype_kw(layer)) if insert_missing else layer.group.find(keys, offsets, **_dtype_kw(layer))
+    rows, _ = (layer.group.find_or_insert(keys, offsets, **_dtype_kw(layer), **_admit_kw(layer)) if insert_missing
+               else layer.group.find(keys, offsets, **_dtype_kw(layer)))
     return rows
 
 
@@ -442,13 +473,17 @@ class DynamicEmbeddingCollection(torch.nn.Module, _SparseOptimizerSettings):
     out_dtype=torch.bfloat16: the lookup itself writes bf16 rows (the tables stay fp32; a bf16 grad is widened, which is exact).
     `group` may be a ShardedTableGroup (sharded.py): the same two ops, then ONE exchange per lookup and per step over the process group; or a
     TieredTableGroup (tiered.py), a collection of hot/cold pairs: forward is one launch (two in training), backward two grouped steps; or a
-    ShardedTieredTableGroup, both at once (this layer and DynamicEmbeddingBag need nothing of their own for it)."""
+    ShardedTieredTableGroup, both at once (this layer and DynamicEmbeddingBag need nothing of their own for it).
+    min_count (a TableGroup whose tables were all created with admission=True): the training forward is the admitting grouped lookup — an unseen
+    id is created only once its table's sketch has seen it min_count times; until then it reads the default row and its gradient is dropped by
+    the step, which ignores absent keys.  Eval mode counts and creates nothing."""
 
     def __init__(self, group, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
-                 out_dtype: torch.dtype = torch.float32):
+                 out_dtype: torch.dtype = torch.float32, min_count: int | None = None):
         super().__init__()
         _refuse_narrow_rows("DynamicEmbeddingCollection", group)
         self.group = group
+        self.min_count = _check_min_count(group, min_count, "DynamicEmbeddingCollection")
         self._init_settings(optimizer, lr, eps, betas, group, out_dtype)
 
     def forward(self, keys: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
@@ -461,16 +496,19 @@ class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
     Over a MixedTableGroup (members of different dims) forward returns a list: member j's [bags_per_table, dim_j] tensor, views of one buffer.
     (keys [n], bag_offsets [n_bags + 1], both on the device) -> [n_bags, dim] sums or means; backward runs the table's sparse optimizer with the bag's grad row for every member (no [n, dim]
     tensor exists in either direction).  create_missing=True (training mode only): unseen ids are inserted with their
-    hashed initial row first (one more pass over the ids); otherwise absent ids read the default row and are not trained."""
+    hashed initial row first (one more pass over the ids); otherwise absent ids read the default row and are not trained.
+    min_count (with create_missing=True; a LookupTable or TableGroup created with admission=True): that creation pass admits — an unseen id is
+    created only once its table's sketch has seen it min_count times, and pools as the default row, untrained, until then."""
 
     def __init__(self, table, mode: str = "sum", optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
-                 create_missing: bool = False, out_dtype: torch.dtype = torch.float32):
+                 create_missing: bool = False, out_dtype: torch.dtype = torch.float32, min_count: int | None = None):
         """out_dtype=torch.bfloat16: the bag is accumulated in fp32 and the finished row rounded once by the lookup; backward widens the bf16 grad."""
         super().__init__()
         _refuse_narrow_rows("DynamicEmbeddingBag", table)
         if mode not in ("sum", "mean"):
             raise ValueError("mode must be 'sum' or 'mean'")
         self.table, self.mode, self.create_missing = table, mode, create_missing
+        self.min_count = _check_min_count(table, min_count, "DynamicEmbeddingBag", creates=create_missing)
         self._init_settings(optimizer, lr, eps, betas, table, out_dtype, pooled=True)
 
     def forward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, per_sample_weights: torch.Tensor | None = None) -> torch.Tensor:
@@ -493,12 +531,17 @@ class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
 class DynamicEmbedding(torch.nn.Module):
     """ids (any int64 tensor) -> fp32 [..., dim].  The table must have been created with the matching optimizer planes.
     out_dtype=torch.bfloat16 (a LookupTable in HBM only): the lookup writes bf16 rows — what `.to(torch.bfloat16)` on the fp32 rows would give —
-    and backward widens the bf16 grad before the table's fp32 step."""
+    and backward widens the bf16 grad before the table's fp32 step.
+    min_count (a LookupTable created with admission=True; fp32 out): the training forward is find_or_insert(min_count=) and the backward the plain
+    apply_* — the located forward has no admitting form; an id not yet admitted reads the default row and its gradient is dropped."""
 
     def __init__(self, table, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
-                 out_dtype: torch.dtype = torch.float32):
+                 out_dtype: torch.dtype = torch.float32, min_count: int | None = None):
         super().__init__()
         _refuse_narrow_rows("DynamicEmbedding", table)
+        self.min_count = _check_min_count(table, min_count, "DynamicEmbedding")
+        if self.min_count is not None and out_dtype != torch.float32:
+            raise ValueError("DynamicEmbedding: min_count has no bf16 form on one table (mee_find_or_insert_admit returns fp32 rows): use out_dtype=torch.float32")
         if optimizer not in ("adagrad", "adam"):
             raise ValueError("optimizer must be 'adagrad' or 'adam'")
         self.out_dtype = _check_out_dtype(table, out_dtype)
@@ -512,7 +555,7 @@ class DynamicEmbedding(torch.nn.Module):
         self._anchor = torch.nn.Parameter(torch.zeros(()), requires_grad=True)
 
     def forward(self, keys: torch.Tensor) -> torch.Tensor:
-        if hasattr(self.table, "find_or_insert_located"):   # one HBM table: the backward updates the rows at the slots this lookup found
+        if self.min_count is None and hasattr(self.table, "find_or_insert_located"):   # one HBM table: the backward updates the rows at the slots this lookup found
             # training: the lookup's launch also partitions the batch for the backward's apply (nothing else may change the table in between:
             # the C-ABI refuses mutators while that partition is pending — table.apply_discard() drops it)
             return lookup_located(keys, self._anchor, self.table_id, self.training, self.training and torch.is_grad_enabled() and self.fuse_backward_partition)[0]

@@ -731,6 +731,7 @@ class TableGroup:
         if self.value_dtype == torch.bfloat16 and max_apply_batch != 0:   # before any device is needed (the library checks again)
             raise ValueError("a group of bf16-row tables is a serving group: max_apply_batch must be 0 (it has no optimizer step)")
         self.device, self.dim = self.tables[0].device, self.tables[0].dim
+        self._min_count_cache = {}   # find_or_insert(min_count=[...]): the device copy of every per-member threshold list seen so far
         arr = (C.c_void_p * len(self.tables))(*[t._h for t in self.tables])
         h = C.c_void_p()
         self._h = None
@@ -945,9 +946,46 @@ class TableGroup:
         return grads, weight_grads
 
     def find_or_insert(self, keys: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
-                       out_dtype: torch.dtype = torch.float32):
-        """find that first creates absent keys in their member table (initial row / state); found = present before."""
-        return self.find(keys, offsets, out, found, _fn="mee_group_find_or_insert", out_dtype=out_dtype)
+                       out_dtype: torch.dtype = torch.float32, min_count=None):
+        """find that first creates absent keys in their member table (initial row / state); found = present before.
+        min_count (every member created with admission=True; mee_group_find_or_insert_admit, three launches): LookupTable.find_or_insert(min_count=)
+        per member on its segment, each member counting in its own sketch — an absent key is created only once that sketch has seen it asked for
+        min_count times, and returns the default row until then.  An int, or one threshold per member (a sequence of n_tables ints; 0 or 1 = at
+        first sight); out_dtype=torch.bfloat16 rounds the returned copy."""
+        if min_count is None:
+            return self.find(keys, offsets, out, found, _fn="mee_group_find_or_insert", out_dtype=out_dtype)
+        scalar, per_member = self._min_counts(min_count)
+        dt = _out_dtype(out_dtype, out)
+        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        n = k.numel()
+        self._check_offsets(offsets)
+        if out is None:
+            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
+        if found is None:
+            found = torch.empty(n, dtype=torch.uint8, device=self.device)
+        check(_lib.lib().mee_group_find_or_insert_admit(self._h, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(), scalar,
+                                                        per_member.data_ptr() if per_member is not None else None, _stream_ptr(self.device)))
+        return out, found
+
+    def _min_counts(self, min_count):
+        """-> (scalar threshold, None) or (0, the device copy of a per-member list — made once per value, so a step uploads nothing)"""
+        if isinstance(min_count, int):
+            if not 0 <= min_count < 1 << 32:
+                raise ValueError(f"min_count must be in [0, 2^32) (got {min_count})")
+            return min_count, None
+        key = tuple(int(c) for c in min_count)
+        if len(key) != len(self.tables):
+            raise ValueError(f"min_count must be an int or one threshold per member: {len(self.tables)} values (got {len(key)})")
+        if any(not 0 <= c < 1 << 32 for c in key):
+            raise ValueError(f"every min_count must be in [0, 2^32) (got {list(key)})")
+        if key not in self._min_count_cache:
+            import numpy as np
+            self._min_count_cache[key] = torch.from_numpy(np.array(key, dtype=np.uint32).view(np.int32)).to(self.device)   # uint32 bits behind an int32 tensor
+        return 0, self._min_count_cache[key]
+
+    def admission_decay(self, shift: int = 1) -> None:
+        """LookupTable.admission_decay of every member in one launch (mee_group_admission_decay): every sketch counter >>= shift (>= 32: reset)."""
+        check(_lib.lib().mee_group_admission_decay(self._h, int(shift), _stream_ptr(self.device)))
 
     def find(self, keys: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
              _fn: str = "mee_find_grouped", out_dtype: torch.dtype = torch.float32):
