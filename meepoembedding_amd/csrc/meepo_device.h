@@ -12,6 +12,8 @@
 
 #include <type_traits>
 
+#include "../../include/meepo_embedding.h"   // MEE_OPT_*, MEE_STATUS_*: what creating a key writes
+
 namespace mee {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));   // what __builtin_nontemporal_load / _store move as one dwordx4
@@ -143,6 +145,29 @@ __device__ __forceinline__ int64_t tile_probe(const int64_t* __restrict__ tkeys,
         k = pend ? tkeys[b * kW + tl] : kEmpty;
     }
     return slot;
+}
+
+// ---- jagged batches over the members of a group: segment j = positions [offsets[j * stride], offsets[(j + 1) * stride]) of the n keys ------------
+// Stages the n_tables + 1 segment bounds in LDS (loff: kMaxGroupTables + 1 entries) and ends with the barrier.  stride = 1, or bags_per_table
+// where the bounds are every stride-th entry of a bag-offset array.  The offsets are the caller's: a bound beyond n is stored as n, which
+// changes nothing for a position i < n (min(o, n) <= i iff o <= i) and keeps every bound, and every difference of two, at or below n.
+__device__ __forceinline__ void stage_offsets(uint64_t* loff, const uint64_t* __restrict__ offsets, uint64_t stride, uint32_t n_tables, uint64_t n) {
+    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) {
+        const uint64_t o = offsets[(uint64_t)j * stride];
+        loff[j] = o < n ? o : n;
+    }
+    __syncthreads();
+}
+// The member of position i: the last j < n_tables with loff[j] <= i (0 when there is none), so empty segments are skipped by the search
+// itself and the result always names a member.  Whether i lies inside the segments at all — loff[0] <= i < loff[n_tables], and i < n — is
+// the caller's test.
+__device__ __forceinline__ uint32_t member_of_position(const uint64_t* loff, uint32_t n_tables, uint64_t i) {
+    uint32_t lo = 0, hi = n_tables;   // invariant: loff[lo] <= i < loff[hi] once i is inside [loff[0], loff[n_tables])
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (loff[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 
 // A wave step of a 4R-position kernel leaves tile t's result of round r in slot[r] of that tile's lanes; lane j < 4R collects the slot of
@@ -644,6 +669,73 @@ __device__ __forceinline__ void adam1(float& w, float& m, float& v, float g, flo
     const float q = mn / (__builtin_sqrtf(vn) + eps);
     w = __builtin_fmaf(-step_size, q, w);
     m = mn; v = vn;
+}
+
+// ---- the creation of a key, said once -----------------------------------------------------------------------------------------------------------
+// What a tile does once tile_locate<claim> has given it `slot` (>= 0) of `key` in the table (d: its planes and default value — GroupDesc; in: its
+// initializer, optimizer and hit counters — GroupInit, meepo_host.h): with ROWS_OUT every such tile — the one whose CAS created the key and one that met
+// a duplicate's creation alike — writes the key's initial row, a function of the key and the table's initializer alone, into row i of `out` (BF16: that
+// copy is rounded, the stored row is not), so nothing has to read the created rows back; the creator (is_new) also writes the table's row, the
+// initial Adagrad or Adam state and a zero hit counter.
+template <bool ROWS_OUT, bool BF16, class Desc, class Init>
+__device__ __forceinline__ void creation_write(const Desc& d, const Init& in, uint32_t dim4, int64_t key, int64_t slot, bool is_new, float4* __restrict__ out,
+                                               uint64_t i, int tl) {
+    if (ROWS_OUT || is_new) {
+        for (uint32_t c = tl; c < dim4; c += 16) {
+            const float4 row = initial_row4(key, c * 4, in.initializer, in.init_scale, in.init_seed, d.defv);
+            if constexpr (ROWS_OUT) {
+                if constexpr (BF16) store_bf16x4<true>(out, i * dim4 + c, row); else out[i * dim4 + c] = row;
+            }
+            if (is_new) {
+                d.values[(uint64_t)slot * dim4 + c] = row;
+                if (in.optimizer == MEE_OPT_ADAGRAD) d.s1[(uint64_t)slot * dim4 + c] = make_float4(in.init_acc, in.init_acc, in.init_acc, in.init_acc);
+                if (in.optimizer == MEE_OPT_ADAM) {
+                    d.s1[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    d.s2[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+            }
+        }
+    }
+    if (is_new && in.hits && tl == 0) in.hits[slot] = 0;
+}
+
+// The creation pass of every grouped find_or_insert (the kernels are thin wrappers: meepo_group.hip, meepo_mixed.hip): each position of the jagged
+// batch that the found mask leaves missing claims (or finds, when a duplicate got there first) its key's slot in its member's table — one creator per
+// distinct key, the CAS decides — and creation_write does the rest.  One tile per position; a wave with nothing missing leaves at the first
+// wave-uniform `continue` (the steady state of a trained vocabulary).  What differs between the operators comes in as a callable:
+//   member_of(lo, live) -> {d, in, dim4}: pointers to the descriptor and the init record member lo creates in (for a group of pairs: of the tier
+//                          to_cold selects) and its row width; `live` = the position has a key to create or a tombstone to flag.  RESERVED_KEY (a
+//                          RECLAIMED key in the batch; EMPTY is padding, silent) and TABLE_FULL go to that record's status word.
+// A gate in front of tile_locate (admission) belongs behind the tombstone's flag and in front of the second `continue`: ensure_admit_grouped_kernel
+// (meepo_group.hip) keeps its own text there.
+template <bool ROWS_OUT, bool BF16, class MemberOf>
+__device__ __forceinline__ void ensure_grouped_body(uint64_t* loff, uint32_t n_tables, const uint64_t* __restrict__ offsets, uint64_t off_stride,
+                                                    const int64_t* __restrict__ keys, uint64_t n, const uint8_t* __restrict__ found,
+                                                    float4* __restrict__ out, MemberOf&& member_of) {
+    stage_offsets(loff, offsets, off_stride, n_tables, n);
+    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t base = wave * 4; base < n; base += n_waves * 4) {
+        const uint64_t i = base + tile;
+        bool act = i < n && i >= loff[0] && i < loff[n_tables] && found[i] == 0;
+        const int64_t key = act ? keys[i] : kEmpty;
+        const bool tomb = act && key == kReclaimed;
+        act = act && !reserved_key(key);
+        if (!__any(act || tomb)) continue;  // wave-uniform: nothing missing here
+        const uint32_t lo = member_of_position(loff, n_tables, i);
+        const auto m = member_of(lo, act || tomb);
+        if (tomb && tl == 0) atomicOr(m.in->status, (uint32_t)MEE_STATUS_RESERVED_KEY);
+        if (!__any(act)) continue;  // wave-uniform: a tombstone was all there was
+        const auto d = *m.d;
+        bool is_new, full;
+        const int64_t slot = tile_locate<true, true>(const_cast<int64_t*>(d.tkeys), d.nb, key, act, tile, tl, is_new, full);
+        if (act) {
+            const auto in = *m.in;
+            if (slot >= 0) creation_write<ROWS_OUT, BF16>(d, in, m.dim4, key, slot, is_new, out, i, tl);
+            if (full && tl == 0) atomicOr(in.status, (uint32_t)MEE_STATUS_TABLE_FULL);
+        }
+    }
 }
 
 }  // namespace mee

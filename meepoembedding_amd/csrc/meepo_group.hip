@@ -35,6 +35,7 @@ __global__ __launch_bounds__(256) void find_grouped_kernel(const GroupDesc* __re
                                                            uint32_t dim4_rt, int64_t* __restrict__ gslot = nullptr,
                                                            const GroupInit* __restrict__ init = nullptr, uint64_t off_stride = 1) {
     __shared__ uint64_t loff[kMaxGroupTables + 1];
+    // mirrors stage_offsets (meepo_device.h) without its cut at n: the lookup path keeps its machine code
     for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) loff[j] = offsets[(uint64_t)j * off_stride];  // stride > 1: the
     __syncthreads();                                                     // segment bounds are every stride-th entry of a bag-offset array
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(256) void find_grouped_kernel(const GroupDesc* __re
         for (int r = 0; r < R; ++r) {
             const uint64_t i = base + r * 4 + tile;
             // segment of position i: the last j with loff[j] <= i (empty segments are skipped by the search itself)
-            uint32_t lo = 0, hi = n_tables;   // invariant: loff[lo] <= i < loff[hi] once i is inside [loff[0], loff[n_tables])
+            uint32_t lo = 0, hi = n_tables;   // mirrors member_of_position (meepo_device.h): the lookup path keeps its machine code
             inb[r] = i < n && i >= loff[0] && i < loff[n_tables];
             while (hi - lo > 1) {
                 const uint32_t mid = (lo + hi) >> 1;
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(256) void find_grouped_tiered_kernel(const GroupDes
                                                                   const int64_t* __restrict__ keys, uint64_t n, float4* __restrict__ out,
                                                                   uint8_t* __restrict__ found, uint32_t dim4_rt, uint32_t count) {
     __shared__ uint64_t loff[kMaxGroupTables + 1];
-    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) loff[j] = offsets[j];
+    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) loff[j] = offsets[j];   // mirrors stage_offsets (meepo_device.h), as find_grouped_kernel
     __syncthreads();
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(256) void find_grouped_tiered_kernel(const GroupDes
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const uint64_t i = base + r * 4 + tile;
-            uint32_t lo = 0, hi = n_tables;   // as find_grouped_kernel: the last j with loff[j] <= i
+            uint32_t lo = 0, hi = n_tables;   // mirrors member_of_position (meepo_device.h), as find_grouped_kernel
             inb[r] = i < n && i >= loff[0] && i < loff[n_tables];
             while (hi - lo > 1) {
                 const uint32_t mid = (lo + hi) >> 1;
@@ -301,65 +302,24 @@ __global__ __launch_bounds__(256) void find_grouped_tiered_kernel(const GroupDes
     }
 }
 
-// Second pass of a grouped find_or_insert: every position the find pass left missing claims (or finds, when a duplicate
-// got there first) its key's slot in its member table; the tile whose CAS created the key writes the initial row, the
-// initial optimizer state and a zero hit counter, and every such tile writes that same initial row — a function of the
-// key and its table's initializer alone — into `out`, so nothing has to read the created rows back.  One tile per position.
-// BF16: `out` holds bf16 rows — the returned copy is rounded, the table's row is not.
+// Second pass of a grouped find_or_insert: ensure_grouped_body (meepo_device.h) with member j creating in desc[j] / init[j], and the
+// initial row of every position that obtained a slot written into `out`.  BF16: `out` holds bf16 rows — the returned copy is rounded, the table's row is not.
 template <bool BF16 = false>
 __global__ __launch_bounds__(256) void ensure_grouped_kernel(const GroupDesc* __restrict__ desc, const GroupInit* __restrict__ init,
                                                              uint32_t n_tables, const uint64_t* __restrict__ offsets,
                                                              const int64_t* __restrict__ keys, uint64_t n,
                                                              const uint8_t* __restrict__ found, uint32_t dim4, float4* __restrict__ out) {
     __shared__ uint64_t loff[kMaxGroupTables + 1];
-    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) loff[j] = offsets[j];
-    __syncthreads();
-    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
-    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-    for (uint64_t base = wave * 4; base < n; base += n_waves * 4) {
-        const uint64_t i = base + tile;
-        bool act = i < n && i >= loff[0] && i < loff[n_tables] && found[i] == 0;
-        const int64_t key = act ? keys[i] : kEmpty;
-        const bool tomb = act && key == kReclaimed;   // a reserved key in the batch: flagged like mee_find_or_insert does (EMPTY = padding, silent)
-        act = act && !reserved_key(key);
-        if (!__any(act || tomb)) continue;  // wave-uniform: nothing missing here (the steady state of a trained vocabulary)
-        uint32_t lo = 0, hi = n_tables;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (loff[mid] <= i) lo = mid; else hi = mid;
-        }
-        if (tomb && tl == 0) atomicOr(init[lo].status, (uint32_t)MEE_STATUS_RESERVED_KEY);
-        const GroupDesc d = desc[act ? lo : 0];
-        bool is_new, full;
-        const int64_t slot = tile_locate<true, true>(const_cast<int64_t*>(d.tkeys), d.nb, key, act, tile, tl, is_new, full);
-        if (act) {
-            const GroupInit in = init[lo];
-            if (slot >= 0) {
-                for (uint32_t c = tl; c < dim4; c += 16) {
-                    const float4 row = initial_row4(key, c * 4, in.initializer, in.init_scale, in.init_seed, d.defv);
-                    if constexpr (BF16) store_bf16x4<true>(out, i * dim4 + c, row); else out[i * dim4 + c] = row;
-                    if (is_new) {
-                        d.values[(uint64_t)slot * dim4 + c] = row;
-                        if (in.optimizer == MEE_OPT_ADAGRAD) d.s1[(uint64_t)slot * dim4 + c] = make_float4(in.init_acc, in.init_acc, in.init_acc, in.init_acc);
-                        if (in.optimizer == MEE_OPT_ADAM) {
-                            d.s1[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
-                            d.s2[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
-                        }
-                    }
-                }
-                if (is_new && in.hits && tl == 0) in.hits[slot] = 0;
-            }
-            if (full && tl == 0) atomicOr(in.status, (uint32_t)MEE_STATUS_TABLE_FULL);
-        }
-    }
+    ensure_grouped_body<true, BF16>(loff, n_tables, offsets, 1, keys, n, found, out,
+                                    [&](uint32_t lo, bool) { return GroupMember{desc + lo, init + lo, dim4}; });
 }
 
-// ensure_grouped_kernel's sibling for mee_group_find_or_insert_admit, the creation with the decision fused in: the tile of a missing position first
-// reads its member's three sketch counters — final since the kernel boundary behind sketch_add_grouped_kernel, and not written here — and goes on to
-// tile_locate only when their minimum reached that member's threshold (min_counts[member] when given, else min_count); otherwise the position keeps
-// the default row the find pass wrote.  Everything else is ensure_grouped_kernel's.  A sibling, not an instance: the kernel above keeps its name,
-// its arguments and its machine code.
+// The creation of mee_group_find_or_insert_admit, the decision fused in: the tile of a missing position first reads its member's three sketch
+// counters — final since the kernel boundary behind sketch_add_grouped_kernel, and not written here — and goes on to tile_locate only when their
+// minimum reached that member's threshold (min_counts[member] when given, else min_count); otherwise the position keeps the default row the find
+// pass wrote.  Everything else is ensure_grouped_kernel's.  This kernel keeps its own text — it mirrors ensure_grouped_body (meepo_device.h:
+// stage_offsets, member_of_position, creation_write) with the gate in front of tile_locate: as a wrapper around that body it measured about
+// 1 us per call slower with a tenth of the batch admitted, in two series (profiles/grouped_creation.md).
 template <bool BF16>
 __global__ __launch_bounds__(256) void ensure_admit_grouped_kernel(const GroupDesc* __restrict__ desc, const GroupInit* __restrict__ init,
                                                                    const GroupAdmit* __restrict__ admit, uint32_t n_tables,
@@ -420,23 +380,17 @@ __global__ __launch_bounds__(256) void ensure_admit_grouped_kernel(const GroupDe
 
 // Grouped admission, the counting launch (between the find and the creation of mee_group_find_or_insert_admit): one thread per position of the jagged
 // batch, positions indexed in 64 bits.  A position inside [offsets[0], offsets[n_tables]) and below n whose found byte is 0 and whose key is not
-// reserved adds 1 to the three counters of ITS member's sketch (the segment search of ensure_grouped_kernel, offsets staged in LDS); a key that occurs
+// reserved adds 1 to the three counters of ITS member's sketch (stage_offsets / member_of_position, meepo_device.h); a key that occurs
 // c times adds c.  Integer atomicAdd commutes: the sketch after the launch does not depend on the order.
 __global__ __launch_bounds__(256) void sketch_add_grouped_kernel(const GroupAdmit* __restrict__ admit, uint32_t n_tables, const uint64_t* __restrict__ offsets,
                                                                  const int64_t* __restrict__ keys, uint64_t n, const uint8_t* __restrict__ found) {
     __shared__ uint64_t loff[kMaxGroupTables + 1];
-    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) loff[j] = offsets[j];
-    __syncthreads();
+    stage_offsets(loff, offsets, 1, n_tables, n);
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         if (i < loff[0] || i >= loff[n_tables] || found[i]) continue;
         const int64_t k = keys[i];
         if (reserved_key(k)) continue;
-        uint32_t lo = 0, hi = n_tables;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (loff[mid] <= i) lo = mid; else hi = mid;
-        }
-        const GroupAdmit a = admit[lo];
+        const GroupAdmit a = admit[member_of_position(loff, n_tables, i)];
 #pragma unroll
         for (int r = 0; r < 3; ++r) atomicAdd(&a.sketch[sketch_index(k, r, a.log2w)], 1u);
     }
@@ -449,67 +403,34 @@ __global__ __launch_bounds__(256) void sketch_decay_grouped_kernel(const GroupAd
         a.sketch[i] = shift >= 32 ? 0u : a.sketch[i] >> shift;
 }
 
-// ensure_grouped_kernel's sibling for a GROUP of hot/cold pairs (mee_group_ensure_tiered): every position the found mask leaves missing claims (or
-// finds, when a duplicate got there first) its key's slot in ONE tier of its member — the cold table where to_cold[member] != 0 (null: every member
-// creates hot) — and the tile whose CAS created the key writes what mee_find_or_insert_missing on that table writes: the initial row from THAT table's
-// initializer, its initial optimizer state, a zero hit counter; TABLE_FULL and RESERVED_KEY (a tombstone value in the batch) go to that table's status
-// word.  Member segments are every bags_per_table-th bag offset (the off_stride of group_locate), cut at n as the lookups cut them: no key past the array
-// is read.  No row is written back — the pooled lookup that follows reads the tables — so no [n, dim] buffer exists.  One tile per position.
+// The creation passes over a GROUP of hot/cold pairs: ensure_grouped_body with member j creating in ONE tier of its pair — the cold table where
+// to_cold[j] != 0 (null: every member creates hot) — as mee_find_or_insert_missing on that table creates: the initial row from THAT table's
+// initializer, its initial optimizer state, a zero hit counter; TABLE_FULL and RESERVED_KEY (a tombstone value in the batch) go to that table's status word.
+struct TierOf {
+    const GroupDesc *hot_desc, *cold_desc;
+    const GroupInit *hot_init, *cold_init;
+    const uint8_t* to_cold;
+    uint32_t dim4;
+    __device__ GroupMember operator()(uint32_t lo, bool live) const {
+        const bool goes_cold = to_cold && live && to_cold[lo] != 0;
+        return GroupMember{(goes_cold ? cold_desc : hot_desc) + lo, (goes_cold ? cold_init : hot_init) + lo, dim4};
+    }
+};
+
+// mee_group_ensure_tiered (the pooled lookup with insert_missing): member segments are every bags_per_table-th bag offset (the off_stride of
+// group_locate).  No row is written back — the pooled lookup that follows reads the tables — so no [n, dim] buffer exists.
 __global__ __launch_bounds__(256) void ensure_tiered_grouped_kernel(const GroupDesc* __restrict__ hot_desc, const GroupInit* __restrict__ hot_init,
                                                                     const GroupDesc* __restrict__ cold_desc, const GroupInit* __restrict__ cold_init,
                                                                     uint32_t n_tables, const uint64_t* __restrict__ offsets, uint64_t bags_per_table,
                                                                     const int64_t* __restrict__ keys, uint64_t n, const uint8_t* __restrict__ found,
                                                                     const uint8_t* __restrict__ to_cold, uint32_t dim4) {
     __shared__ uint64_t loff[kMaxGroupTables + 1];
-    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) {
-        const uint64_t o = offsets[(uint64_t)j * bags_per_table];
-        loff[j] = o < n ? o : n;
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
-    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-    for (uint64_t base = wave * 4; base < n; base += n_waves * 4) {
-        const uint64_t i = base + tile;
-        bool act = i < n && i >= loff[0] && i < loff[n_tables] && found[i] == 0;
-        const int64_t key = act ? keys[i] : kEmpty;
-        const bool tomb = act && key == kReclaimed;   // a reserved key in the batch: flagged like mee_find_or_insert_missing does (EMPTY = padding, silent)
-        act = act && !reserved_key(key);
-        if (!__any(act || tomb)) continue;  // wave-uniform: nothing missing here (the steady state of a trained vocabulary)
-        uint32_t lo = 0, hi = n_tables;     // the last member whose segment starts at or before i (always inside [0, n_tables))
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (loff[mid] <= i) lo = mid; else hi = mid;
-        }
-        const bool goes_cold = to_cold && (act || tomb) && to_cold[lo] != 0;
-        const GroupDesc d = goes_cold ? cold_desc[lo] : hot_desc[lo];
-        const GroupInit in = goes_cold ? cold_init[lo] : hot_init[lo];
-        if (tomb && tl == 0) atomicOr(in.status, (uint32_t)MEE_STATUS_RESERVED_KEY);
-        bool is_new, full;
-        const int64_t slot = tile_locate<true, true>(const_cast<int64_t*>(d.tkeys), d.nb, key, act, tile, tl, is_new, full);
-        if (act) {
-            if (slot >= 0 && is_new) {
-                for (uint32_t c = tl; c < dim4; c += 16) {
-                    d.values[(uint64_t)slot * dim4 + c] = initial_row4(key, c * 4, in.initializer, in.init_scale, in.init_seed, d.defv);
-                    if (in.optimizer == MEE_OPT_ADAGRAD) d.s1[(uint64_t)slot * dim4 + c] = make_float4(in.init_acc, in.init_acc, in.init_acc, in.init_acc);
-                    if (in.optimizer == MEE_OPT_ADAM) {
-                        d.s1[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
-                        d.s2[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    }
-                }
-                if (in.hits && tl == 0) in.hits[slot] = 0;
-            }
-            if (full && tl == 0) atomicOr(in.status, (uint32_t)MEE_STATUS_TABLE_FULL);
-        }
-    }
+    ensure_grouped_body<false, false>(loff, n_tables, offsets, bags_per_table, keys, n, found, nullptr,
+                                      TierOf{hot_desc, cold_desc, hot_init, cold_init, to_cold, dim4});
 }
 
-// ensure_tiered_grouped_kernel's sibling for the unpooled find_or_insert over a group of pairs (mee_group_find_or_insert_tiered), which returns a row per
-// position: what ensure_grouped_kernel<BF16> does, in the tier to_cold selects.  Every tile that obtained a slot for a position the mask left missing —
-// the one whose CAS created the key and one that met a duplicate's creation alike — writes initial_row4(key, …) of the table it created in into
-// out[i] (BF16: that copy is rounded, the stored row is not); the creator also writes the table's row, state and a zero hit counter.  Member offsets
-// are the n_tables + 1 jagged offsets of the lookup (cut at n: no key past the array is read).  A sibling, not an instance: the kernel above keeps
-// its name, its arguments and its machine code.
+// mee_group_find_or_insert_tiered (the unpooled find_or_insert over a group of pairs), which returns a row per position: what ensure_grouped_kernel<BF16>
+// does, in the tier to_cold selects, over the n_tables + 1 jagged offsets of the lookup.
 template <bool BF16>
 __global__ __launch_bounds__(256) void ensure_tiered_grouped_rows_kernel(const GroupDesc* __restrict__ hot_desc, const GroupInit* __restrict__ hot_init,
                                                                          const GroupDesc* __restrict__ cold_desc, const GroupInit* __restrict__ cold_init,
@@ -517,51 +438,7 @@ __global__ __launch_bounds__(256) void ensure_tiered_grouped_rows_kernel(const G
                                                                          const int64_t* __restrict__ keys, uint64_t n, const uint8_t* __restrict__ found,
                                                                          const uint8_t* __restrict__ to_cold, uint32_t dim4, float4* __restrict__ out) {
     __shared__ uint64_t loff[kMaxGroupTables + 1];
-    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) {
-        const uint64_t o = offsets[j];
-        loff[j] = o < n ? o : n;
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
-    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-    for (uint64_t base = wave * 4; base < n; base += n_waves * 4) {
-        const uint64_t i = base + tile;
-        bool act = i < n && i >= loff[0] && i < loff[n_tables] && found[i] == 0;
-        const int64_t key = act ? keys[i] : kEmpty;
-        const bool tomb = act && key == kReclaimed;   // a reserved key in the batch: flagged like mee_find_or_insert_missing does (EMPTY = padding, silent)
-        act = act && !reserved_key(key);
-        if (!__any(act || tomb)) continue;  // wave-uniform: nothing missing here (the steady state of a trained vocabulary)
-        uint32_t lo = 0, hi = n_tables;     // the last member whose segment starts at or before i (always inside [0, n_tables))
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (loff[mid] <= i) lo = mid; else hi = mid;
-        }
-        const bool goes_cold = to_cold && (act || tomb) && to_cold[lo] != 0;
-        const GroupDesc d = goes_cold ? cold_desc[lo] : hot_desc[lo];
-        const GroupInit in = goes_cold ? cold_init[lo] : hot_init[lo];
-        if (tomb && tl == 0) atomicOr(in.status, (uint32_t)MEE_STATUS_RESERVED_KEY);
-        bool is_new, full;
-        const int64_t slot = tile_locate<true, true>(const_cast<int64_t*>(d.tkeys), d.nb, key, act, tile, tl, is_new, full);
-        if (act) {
-            if (slot >= 0) {
-                for (uint32_t c = tl; c < dim4; c += 16) {
-                    const float4 row = initial_row4(key, c * 4, in.initializer, in.init_scale, in.init_seed, d.defv);
-                    if constexpr (BF16) store_bf16x4<true>(out, i * dim4 + c, row); else out[i * dim4 + c] = row;
-                    if (is_new) {
-                        d.values[(uint64_t)slot * dim4 + c] = row;
-                        if (in.optimizer == MEE_OPT_ADAGRAD) d.s1[(uint64_t)slot * dim4 + c] = make_float4(in.init_acc, in.init_acc, in.init_acc, in.init_acc);
-                        if (in.optimizer == MEE_OPT_ADAM) {
-                            d.s1[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
-                            d.s2[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
-                        }
-                    }
-                }
-                if (is_new && in.hits && tl == 0) in.hits[slot] = 0;
-            }
-            if (full && tl == 0) atomicOr(in.status, (uint32_t)MEE_STATUS_TABLE_FULL);
-        }
-    }
+    ensure_grouped_body<true, BF16>(loff, n_tables, offsets, 1, keys, n, found, out, TierOf{hot_desc, cold_desc, hot_init, cold_init, to_cold, dim4});
 }
 
 }  // namespace mee
@@ -754,8 +631,12 @@ static int find_grouped_common(mee_group* g, const int64_t* d_keys, const uint64
     return launch_find_grouped(g, d_keys, d_offsets, n, d_out, out_dtype, d_found, (hipStream_t)stream);
 }
 
-static int group_find_or_insert_common(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
-                                       void* stream, const char* name) {
+// What every grouped find_or_insert does in front of its creation launches: the argument checks, the group's own found mask where the caller gave none
+// (n <= max_apply_batch then), the descriptor refresh, and the ordinary grouped find, which serves every stored key and yields the present-before
+// mask.  Then create(st, d_found) launches what creates the missing keys, on the same stream and device.
+template <class Create>
+static int group_find_then_create(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
+                                  void* stream, const char* name, Create&& create) {
     MEE_FP32_GROUP_ONLY(g, name);
     if (!g || !d_offsets || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
     if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
@@ -768,13 +649,20 @@ static int group_find_or_insert_common(mee_group* g, const int64_t* d_keys, cons
     if (int rc = group_refresh(g, stream)) return rc;
     DeviceGuard guard(g->device);
     hipStream_t st = (hipStream_t)stream;
-    // 1) the ordinary grouped find serves every stored key and yields the present-before mask
     if (int rc = launch_find_grouped(g, d_keys, d_offsets, n, d_out, out_dtype, d_found, st)) return rc;
-    // 2) missing positions create their key (one creator per distinct key: the CAS decides) and return its initial row
-    if (out_dtype == MEE_DTYPE_BF16) ensure_grouped_kernel<true><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_init, g->n_tables, d_offsets, d_keys, n, d_found, g->dim4, (float4*)d_out);
-    else ensure_grouped_kernel<false><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_init, g->n_tables, d_offsets, d_keys, n, d_found, g->dim4, (float4*)d_out);
+    create(st, d_found);
     MEE_HIP(hipGetLastError());
     return MEE_OK;
+}
+
+static int group_find_or_insert_common(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found,
+                                       void* stream, const char* name) {
+    // missing positions create their key (one creator per distinct key: the CAS decides) and return its initial row
+    return group_find_then_create(g, d_keys, d_offsets, n, d_out, out_dtype, d_found, stream, name, [&](hipStream_t st, uint8_t* found) {
+        with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto b16) {
+            ensure_grouped_kernel<b16><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_init, g->n_tables, d_offsets, d_keys, n, found, g->dim4, (float4*)d_out);
+        });
+    });
 }
 
 // every member has a sketch, or MEE_ERR_UNSUPPORTED naming the first that has none
@@ -790,28 +678,15 @@ extern "C" int mee_group_find_or_insert_admit(mee_group* g, const int64_t* d_key
     MEE_RANGE("mee_group_find_or_insert_admit");
     const char* name = "mee_group_find_or_insert_admit";
     if (int rc = group_admission_check(g, name)) return rc;
-    if (!g || !d_offsets || (n && (!d_keys || !d_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
-    if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
-    if (n == 0) return MEE_OK;
-    if (!d_found) {
-        if (n > g->max_apply_batch)
-            return fail(MEE_ERR_BATCH_TOO_LARGE, "%s: without a found buffer n=%zu must be <= max_apply_batch=%llu", name, n, (unsigned long long)g->max_apply_batch);
-        d_found = g->d_fmask;
-    }
-    if (int rc = group_refresh(g, stream)) return rc;
-    DeviceGuard guard(g->device);
-    hipStream_t st = (hipStream_t)stream;
-    // 1) the ordinary grouped find serves every stored key and yields the present-before mask
-    if (int rc = launch_find_grouped(g, d_keys, d_offsets, n, d_out, out_dtype, d_found, st)) return rc;
-    // 2) every missing position counts its key in its member's sketch
-    sketch_add_grouped_kernel<<<grid_for(n, 256, 4096), 256, 0, st>>>(g->d_admit, g->n_tables, d_offsets, d_keys, n, d_found);
-    // 3) the creation of mee_group_find_or_insert, for the positions whose estimate reached their member's threshold
-    with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto b16) {
-        ensure_admit_grouped_kernel<b16><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_init, g->d_admit, g->n_tables, d_offsets, d_keys, n, d_found, g->dim4, (float4*)d_out,
-                                                                               min_count, d_min_counts);
+    return group_find_then_create(g, d_keys, d_offsets, n, d_out, out_dtype, d_found, stream, name, [&](hipStream_t st, uint8_t* found) {
+        // every missing position counts its key in its member's sketch ...
+        sketch_add_grouped_kernel<<<grid_for(n, 256, 4096), 256, 0, st>>>(g->d_admit, g->n_tables, d_offsets, d_keys, n, found);
+        // ... then the creation of mee_group_find_or_insert, for the positions whose estimate reached their member's threshold
+        with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto b16) {
+            ensure_admit_grouped_kernel<b16><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_init, g->d_admit, g->n_tables, d_offsets, d_keys, n, found, g->dim4, (float4*)d_out,
+                                                                                   min_count, d_min_counts);
+        });
     });
-    MEE_HIP(hipGetLastError());
-    return MEE_OK;
 }
 
 extern "C" int mee_group_admission_decay(mee_group* g, uint32_t shift, void* stream) {

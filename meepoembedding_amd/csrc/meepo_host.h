@@ -113,6 +113,11 @@ struct GroupInit {   // per member, device resident: what creating a key in that
     uint32_t initializer, optimizer;
     float init_scale, init_acc;
 };
+struct GroupMember {   // what ensure_grouped_body (meepo_device.h) asks of a member: the table a position creates in, and its row width in float4
+    const GroupDesc* d;
+    const GroupInit* in;
+    uint32_t dim4;
+};
 struct GroupAdmit {   // per member, device resident: its admission sketch (grouped find_or_insert_admit / admission_decay); null without MEE_FLAG_ADMISSION
     uint32_t* sketch;
     uint32_t log2w, pad;

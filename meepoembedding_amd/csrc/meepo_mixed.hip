@@ -66,16 +66,6 @@ __global__ __launch_bounds__(256) void mixed_find_pooled_kernel(const GroupDesc*
     }
 }
 
-// the member of key position i: the last j with loff[j] <= i, loff[j] = bag_offsets[j * B] staged in LDS (find_grouped_kernel's search)
-__device__ __forceinline__ uint32_t member_of_position(const uint64_t* loff, uint32_t n_tables, uint64_t i) {
-    uint32_t lo = 0, hi = n_tables;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (loff[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // One tile per key position, read-only.
 // SELECT = false: found[i] = the key is stored in its member (the present-before mask of a lookup with insert_missing).
 // SELECT = true (the class select of the step): a position of one of class `cls`'s members gets its handle with the member re-based to
@@ -108,8 +98,7 @@ __global__ __launch_bounds__(256) void mixed_locate_kernel(const GroupDesc* __re
         }
         return;
     }
-    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) loff[j] = offsets[(uint64_t)j * B];
-    __syncthreads();
+    stage_offsets(loff, offsets, B, n_tables, n);   // member j's keys: from bag offset j * B on
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
     for (uint64_t base = wave * 4; base < n; base += n_waves * 4) {
@@ -134,48 +123,15 @@ __global__ __launch_bounds__(256) void mixed_locate_kernel(const GroupDesc* __re
     }
 }
 
-// The ensure pass of ensure_grouped_kernel (meepo_group.hip) with the member's own dim4: every position the probe pass left missing claims
-// (or finds, when a duplicate got there first) its key's slot in its member table; the tile whose CAS created the key writes the initial
-// row, the initial optimizer state and a zero hit counter.  Nothing else is written: the lookup that follows reads the rows.
+// The creation pass of a lookup with insert_missing: ensure_grouped_body (meepo_device.h) with member j creating in desc[j] / init[j] at the member's
+// own dim4, over the segments that begin at every bags_per_table-th bag offset.  No row is written back: the lookup that follows reads the tables.
 __global__ __launch_bounds__(256) void mixed_ensure_kernel(const GroupDesc* __restrict__ desc, const MixedDesc* __restrict__ mdesc,
                                                            const GroupInit* __restrict__ init, uint32_t n_tables, const uint64_t* __restrict__ offsets,
                                                            uint64_t bags_per_table, const int64_t* __restrict__ keys, uint64_t n,
                                                            const uint8_t* __restrict__ found) {
     __shared__ uint64_t loff[kMaxGroupTables + 1];
-    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) loff[j] = offsets[(uint64_t)j * bags_per_table];
-    __syncthreads();
-    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
-    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-    for (uint64_t base = wave * 4; base < n; base += n_waves * 4) {
-        const uint64_t i = base + tile;
-        bool act = i < n && i >= loff[0] && i < loff[n_tables] && found[i] == 0;
-        const int64_t key = act ? keys[i] : kEmpty;
-        const bool tomb = act && key == kReclaimed;   // a reserved key in the batch: flagged like mee_find_or_insert does (EMPTY = padding, silent)
-        act = act && !reserved_key(key);
-        if (!__any(act || tomb)) continue;  // wave-uniform: nothing missing here (the steady state of a trained vocabulary)
-        const uint32_t m = (act || tomb) ? member_of_position(loff, n_tables, i) : 0;
-        if (tomb && tl == 0) atomicOr(init[m].status, (uint32_t)MEE_STATUS_RESERVED_KEY);
-        const GroupDesc d = desc[m];
-        const uint32_t dim4 = mdesc[m].dim4;
-        bool is_new, full;
-        const int64_t slot = tile_locate<true, true>(const_cast<int64_t*>(d.tkeys), d.nb, key, act, tile, tl, is_new, full);
-        if (act) {
-            const GroupInit in = init[m];
-            if (slot >= 0 && is_new) {
-                for (uint32_t c = tl; c < dim4; c += 16) {
-                    d.values[(uint64_t)slot * dim4 + c] = initial_row4(key, c * 4, in.initializer, in.init_scale, in.init_seed, d.defv);
-                    if (in.optimizer == MEE_OPT_ADAGRAD) d.s1[(uint64_t)slot * dim4 + c] = make_float4(in.init_acc, in.init_acc, in.init_acc, in.init_acc);
-                    if (in.optimizer == MEE_OPT_ADAM) {
-                        d.s1[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
-                        d.s2[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    }
-                }
-                if (in.hits && tl == 0) in.hits[slot] = 0;
-            }
-            if (full && tl == 0) atomicOr(in.status, (uint32_t)MEE_STATUS_TABLE_FULL);
-        }
-    }
+    ensure_grouped_body<false, false>(loff, n_tables, offsets, bags_per_table, keys, n, found, nullptr,
+                                      [&](uint32_t lo, bool) { return GroupMember{desc + lo, init + lo, mdesc[lo].dim4}; });
 }
 
 }  // namespace mee

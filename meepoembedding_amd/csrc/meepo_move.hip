@@ -107,24 +107,12 @@ __device__ __forceinline__ void move_body(const int64_t* __restrict__ keys, uint
     }
 }
 
-// the segment of a batch position in a jagged batch whose n_tables + 1 offsets (cut at n) are staged in LDS: the last member whose segment starts at or
-// before i.  The offsets are caller data and are never trusted: a position is served only where loff[lo] <= i < loff[lo + 1], so that its index in
-// the member's slot list, i - loff[lo], stays below n whatever the array holds.
+// the segment of a batch position in a jagged batch whose n_tables + 1 offsets are staged in LDS (stage_offsets, meepo_device.h: cut at n).  The offsets
+// are caller data and are never trusted: a position is served only where loff[lo] <= i < loff[lo + 1], so that its index in the member's slot
+// list, i - loff[lo], stays below n whatever the array holds.
 __device__ __forceinline__ bool member_of(const uint64_t* loff, uint32_t n_tables, uint64_t i, uint32_t& lo) {
-    uint32_t hi = n_tables;
-    lo = 0;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (loff[mid] <= i) lo = mid; else hi = mid;
-    }
+    lo = member_of_position(loff, n_tables, i);
     return loff[lo] <= i && i < loff[lo + 1];
-}
-__device__ __forceinline__ void stage_offsets(uint64_t* loff, const uint64_t* __restrict__ offsets, uint32_t n_tables, uint64_t n) {
-    for (uint32_t j = threadIdx.x; j <= n_tables; j += blockDim.x) {
-        const uint64_t o = offsets[j];
-        loff[j] = o < n ? o : n;
-    }
-    __syncthreads();
 }
 
 template <int DIM4, int NP, bool LOCATED = false>
@@ -144,7 +132,7 @@ __global__ __launch_bounds__(256) void move_grouped_kernel(const MoveTable* __re
     __shared__ uint64_t loff[kMaxGroupTables + 1];
     if (n_moved && blockIdx.x == 0)
         for (uint32_t j = threadIdx.x; j < n_tables; j += blockDim.x) n_moved[j] = 0;
-    stage_offsets(loff, offsets, n_tables, n);
+    stage_offsets(loff, offsets, 1, n_tables, n);
     move_body<DIM4, NP, LOCATED>(keys, n, dim4_rt, moved, [&](uint64_t i, MoveTable& s, MoveTable& d, uint64_t& loc) {
         uint32_t lo;
         const bool in = i < n && member_of(loff, n_tables, i, lo);
@@ -189,7 +177,7 @@ __global__ __launch_bounds__(256) void move_locate_kernel(MoveTable src, const i
 __global__ __launch_bounds__(256) void move_locate_grouped_kernel(const MoveTable* __restrict__ src, uint32_t n_tables, const uint64_t* __restrict__ offsets,
                                                                   const int64_t* __restrict__ keys, uint64_t n) {
     __shared__ uint64_t loff[kMaxGroupTables + 1];
-    stage_offsets(loff, offsets, n_tables, n);
+    stage_offsets(loff, offsets, 1, n_tables, n);
     move_locate_body(keys, n, [&](uint64_t i, MoveTable& s, MoveTable&, uint64_t& loc) {
         uint32_t lo;
         const bool in = i < n && member_of(loff, n_tables, i, lo);
@@ -252,7 +240,7 @@ __global__ __launch_bounds__(256) void move_mark_kernel(MoveTable src, uint32_t 
 __global__ __launch_bounds__(256) void move_mark_grouped_kernel(const MoveTable* __restrict__ src, uint32_t n_tables, const uint64_t* __restrict__ offsets, uint64_t n,
                                                                 unsigned long long* __restrict__ n_moved) {
     __shared__ uint64_t loff[kMaxGroupTables + 1];
-    stage_offsets(loff, offsets, n_tables, n);
+    stage_offsets(loff, offsets, 1, n_tables, n);
     const int lane = threadIdx.x & 63;
     for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x; i0 < n; i0 += (uint64_t)gridDim.x * blockDim.x) {   // block-uniform
         const uint64_t i = i0 + threadIdx.x;

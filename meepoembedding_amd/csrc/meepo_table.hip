@@ -433,6 +433,7 @@ __device__ __forceinline__ void ensure_direct_body(int64_t* tkeys, float4* value
                 // A position that was missing and whose key is stored now — created by this tile or by another occurrence in this batch —
                 // returns the key's initial row, which is a function of the key alone: every such tile writes it straight into `out`
                 // (bit-identical to what the creator stores), so no third pass has to read the created rows back.
+                // mirrors creation_write (meepo_device.h) with a run-time `out`: the tuned single-table pass keeps its machine code
                 for (uint32_t c = tl; c < dim4; c += 16) {
                     const float4 row = initial_row4(key, c * 4, initializer, init_scale, init_seed, default_value);
                     if (out) { if constexpr (BF16) store_bf16x4<true>(out, (uint64_t)(base + p) * dim4 + c, row); else out[(uint64_t)(base + p) * dim4 + c] = row; }
