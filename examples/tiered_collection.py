@@ -1,7 +1,8 @@
 """A recommender's sparse part whose tables do not fit HBM: 8 tables, each a hot/cold pair (hot rows in HBM, cold rows in pinned host
 memory), served by ONE pooled lookup launch and trained by two grouped optimizer steps per batch, whatever the number of tables; then the
-same pairs behind a DynamicEmbeddingCollection, which returns a row per id (a sequence feature) from one launch
-(run on the GPU box: python examples/tiered_collection.py)."""
+same pairs behind a DynamicEmbeddingCollection, which returns a row per id (a sequence feature) from one launch.  Both layers admit: an unseen id enters its pair only once the pair's hot table's sketch has
+seen it asked for min_count times — a skewed stream's once-seen tail stays out of both tiers
+(run on the GPU box: python examples/tiered_collection.py [min_count, default 2; 0 = create at first sight, no admission])."""
 import os
 import sys
 
@@ -17,6 +18,7 @@ from meepoembedding_amd.nn import DynamicEmbeddingBag, DynamicEmbeddingCollectio
 dev = torch.device("cuda", 0)
 n_tables, dim, batch, ids_per_bag, vocab = 8, 64, 2048, 5, 400_000
 max_ids = n_tables * batch * 2 * ids_per_bag       # an upper bound on the ids of one step
+min_count = (int(sys.argv[1]) if len(sys.argv) > 1 else 2) or None
 
 
 def table(capacity, j, **kw):
@@ -26,10 +28,11 @@ def table(capacity, j, **kw):
 
 # New ids are created hot while a pair has room for a whole batch of them (the host's only bound on a member's new ids is the size of the batch:
 # conservative, and free of synchronisation), then cold; rebalance() promotes the cold ids the lookups keep hitting.
-pairs = [TieredLookupTable(table(1 << 18, j), table(2 * vocab, j, value_memory=_lib.MEM_HOST_PINNED), hot_key_limit=120_000)
+# Admission: the pair's sketch is its HOT table's, so only the hot tables are created with one.
+pairs = [TieredLookupTable(table(1 << 18, j, admission=True), table(2 * vocab, j, value_memory=_lib.MEM_HOST_PINNED), hot_key_limit=120_000)
          for j in range(n_tables)]
 group = TieredTableGroup(pairs, max_apply_batch=max_ids)
-sparse = DynamicEmbeddingBag(group, mode="sum", optimizer="adagrad", lr=0.05, create_missing=True).to(dev)   # bag b -> pair b // batch
+sparse = DynamicEmbeddingBag(group, mode="sum", optimizer="adagrad", lr=0.05, create_missing=True, min_count=min_count).to(dev)   # bag b -> pair b // batch
 dense = torch.nn.Sequential(torch.nn.Linear(n_tables * dim, 256), torch.nn.ReLU(), torch.nn.Linear(256, 1)).to(dev)
 dense_opt = torch.optim.SGD(dense.parameters(), lr=0.01)
 
@@ -38,7 +41,7 @@ for step in range(8):
     offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(lens, 0)])
     ids = (torch.rand(int(offsets[-1]), device=dev) ** 3 * vocab).long()      # a skewed stream: small ids are popular
     labels = torch.rand(batch, 1, device=dev)
-    pooled = sparse(ids, offsets)        # three launches: found mask, creation of unseen ids (hot while there is room, else cold), pooled lookup
+    pooled = sparse(ids, offsets)        # found mask, count + creation of the admitted unseen ids (hot while there is room, else cold), pooled lookup
     features = pooled.view(n_tables, batch, dim).transpose(0, 1).reshape(batch, n_tables * dim)
     loss = torch.nn.functional.binary_cross_entropy_with_logits(dense(features), labels)
     dense_opt.zero_grad()
@@ -49,8 +52,8 @@ for step in range(8):
           + (f", rebalanced: promoted {sum(m[0] for m in moved)}, demoted {sum(m[1] for m in moved)}" if moved else ""))
 
 # A sequence feature over the same pairs: a row per id (a behaviour history fed to attention), bf16 rows.  Forward is the one-launch find over both
-# tiers of every pair plus one creation launch, backward the same two grouped steps.
-history = DynamicEmbeddingCollection(group, optimizer="adagrad", lr=0.05, out_dtype=torch.bfloat16).to(dev)
+# tiers of every pair, the count and one gated creation launch, backward the same two grouped steps.
+history = DynamicEmbeddingCollection(group, optimizer="adagrad", lr=0.05, out_dtype=torch.bfloat16, min_count=min_count).to(dev)
 seq_len = 8
 scorer = torch.nn.Linear(dim, 1).to(dev).to(torch.bfloat16)
 seq_offsets = torch.arange(n_tables + 1, dtype=torch.int64, device=dev) * batch * seq_len      # segment j: the ids of pair j

@@ -305,6 +305,16 @@ int mee_admission_decay(mee_table* t, uint32_t shift, void* stream);
  * d_found byte is 0, i.e. keys that an earlier pass found in NEITHER table.  d_found is only read. */
 int mee_insert_missing(mee_table* t, const int64_t* d_keys, const float* d_values, size_t n, const uint8_t* d_found, void* stream);
 int mee_find_or_insert_missing(mee_table* t, const int64_t* d_keys, size_t n, float* d_out, const uint8_t* d_found, void* stream);
+/* Admission into a tiered pair (SPEC.md §3 "Tiering": the pair's sketch is its HOT table's): the admitting sibling of mee_find_or_insert_missing, on
+ * buffers a find over both tiers already filled.  Every position with d_found[i] == 0 and a non-reserved key adds 1 to its key's counters in
+ * `counts`'s sketch (the pair's hot table); a key whose estimate — after ALL additions of this batch — is >= min_count is created in `t` (the tier
+ * the pair picked: `counts` itself, or the cold table) exactly as mee_find_or_insert_missing creates it, and all its occurrences receive its initial
+ * row in d_out; every other position of d_out is left untouched, and d_found is only read.  RECLAIMED among the missing positions sets
+ * MEE_STATUS_RESERVED_KEY on t, TABLE_FULL lands on t, as there.  counts == t is legal.  fp32 rows, one dim and one device for both tables,
+ * n <= t's max_batch (MEE_ERR_BATCH_TOO_LARGE); MEE_ERR_UNSUPPORTED when `counts` was created without MEE_FLAG_ADMISSION (t needs no sketch) or
+ * either table stores narrow rows.  Three launches (count, decide, create) on t's scratch; no host synchronisation, no allocation, capturable. */
+int mee_find_or_insert_admit_missing(mee_table* t, mee_table* counts, const int64_t* d_keys, size_t n, float* d_out, const uint8_t* d_found,
+                                     uint32_t min_count, void* stream);
 /* [syncs] all stored pairs, unspecified order; d_state1/d_state2 (nullable) receive acc|m and v rows in the
  * same order.  At most `cap` pairs are written; *n_out = number stored in the table. */
 int mee_export(const mee_table* t, int64_t* d_keys_out, float* d_values_out, float* d_state1_out,
@@ -497,6 +507,29 @@ int mee_group_find_tiered(mee_group* hot_group, mee_group* cold_group, const int
 int mee_group_find_or_insert_tiered(mee_group* hot_group, mee_group* cold_group, const int64_t* d_keys, const uint64_t* d_offsets, size_t n,
                                     void* d_out, uint32_t out_dtype, uint8_t* d_found /* required: present before the call */,
                                     const uint8_t* d_to_cold /* [n_tables], device; nullable: all hot */, uint32_t flags, void* stream);
+/* Admission over a group of pairs (SPEC.md §3 "Tiering"): a pair's sketch is its HOT table's, so every member of hot_group must have been created with
+ * MEE_FLAG_ADMISSION (MEE_ERR_UNSUPPORTED naming the first that was not); the cold members need no sketch, and one they have is never touched.
+ * mee_group_find_or_insert_admit_tiered is mee_group_find_or_insert_tiered with the creation behind the sketches, THREE launches whatever the number of
+ * pairs: (1) that lookup, flags included; (2) every position inside the segments whose d_found byte is 0 and whose key is not reserved adds 1 to its
+ * key's three counters in its member's hot sketch (a key that occurs c times adds c); (3) one creation launch in which a missing key goes on only when
+ * the minimum of its counters — after ALL additions of the batch — reached the member's threshold: min_count, or d_min_counts[member] when
+ * d_min_counts (DEVICE memory, n_tables entries, nullable) is given.  An admitted key is created once, in the tier d_to_cold selects for its member, as
+ * mee_find_or_insert_missing on that table creates it, and all its occurrences return that initial row; every other absent key keeps the hot default
+ * row and stays absent.  0 and 1 admit at first sight: the result, the tables and the status words are mee_group_find_or_insert_tiered's, and the
+ * sketch still counts.  TABLE_FULL / RESERVED_KEY go to the status word of the table that was asked to create.  Positions outside
+ * [d_offsets[0], d_offsets[n_tables]) or at or past n are not written, not counted and create nothing.  out_dtype = MEE_DTYPE_BF16 rounds the returned
+ * copy once.  The groups keep no counters: these calls and mee_find_or_insert_admit / mee_find_or_insert_admit_missing / mee_admission_decay on the
+ * tables interleave freely.
+ * mee_group_ensure_admit_tiered is mee_group_ensure_tiered behind the same gate, TWO launches (count, then the gated creation with no rows out): member
+ * segments are every bags_per_table-th bag offset, cut at n.
+ * Both: no host synchronisation, no allocation, capturable; the argument checks are those of the non-admitting forms. */
+int mee_group_find_or_insert_admit_tiered(mee_group* hot_group, mee_group* cold_group, const int64_t* d_keys, const uint64_t* d_offsets, size_t n,
+                                          void* d_out, uint32_t out_dtype, uint8_t* d_found /* required: present before the call */,
+                                          const uint8_t* d_to_cold /* [n_tables], device; nullable: all hot */, uint32_t min_count,
+                                          const uint32_t* d_min_counts /* [n_tables], device; nullable */, uint32_t flags, void* stream);
+int mee_group_ensure_admit_tiered(mee_group* hot_group, mee_group* cold_group, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets,
+                                  size_t bags_per_table, const uint8_t* d_found, const uint8_t* d_to_cold /* [n_tables], device; nullable: all hot */,
+                                  uint32_t min_count, const uint32_t* d_min_counts /* [n_tables], device; nullable */, void* stream);
 
 /* ---- tier migration (SPEC.md §3 move): "this key, with everything it owns, now lives in that table" --------------------------------------
  * Let P be the batch positions whose key is not reserved and is stored in `src` when the call starts, in ascending order; the first max_moves of them

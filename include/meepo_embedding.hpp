@@ -236,6 +236,14 @@ public:
     void find_or_insert_tiered(Group& cold, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, const uint8_t* d_to_cold = nullptr, uint32_t flags = 0, void* stream = nullptr) {
         check(mee_group_find_or_insert_tiered(g_, cold.g_, d_keys, d_offsets, n, d_out, out_dtype, d_found, d_to_cold, flags, stream));
     }
+    // admission over the collection of pairs (each pair counts in its HOT table's sketch: this group's members need MEE_FLAG_ADMISSION, `cold`'s do not):
+    // mee_group_find_or_insert_admit_tiered, three launches, and mee_group_ensure_admit_tiered, two; min_count, or d_min_counts[member] when given
+    void find_or_insert_admit_tiered(Group& cold, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, uint32_t min_count, const uint32_t* d_min_counts = nullptr, const uint8_t* d_to_cold = nullptr, uint32_t flags = 0, void* stream = nullptr) {
+        check(mee_group_find_or_insert_admit_tiered(g_, cold.g_, d_keys, d_offsets, n, d_out, out_dtype, d_found, d_to_cold, min_count, d_min_counts, flags, stream));
+    }
+    void ensure_admit_tiered(Group& cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const uint8_t* d_found, uint32_t min_count, const uint32_t* d_min_counts = nullptr, const uint8_t* d_to_cold = nullptr, void* stream = nullptr) {
+        check(mee_group_ensure_admit_tiered(g_, cold.g_, d_keys, n, d_bag_offsets, bags_per_table, d_found, d_to_cold, min_count, d_min_counts, stream));
+    }
     // mee_move per member on its segment of the jagged batch (mee_group_move); d_max_moves / d_n_moved: n_tables device words each, nullable
     void move_to(Group& dst, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, const uint64_t* d_max_moves = nullptr, uint8_t* d_moved = nullptr, uint64_t* d_n_moved = nullptr, void* stream = nullptr) {
         check(mee_group_move(g_, dst.g_, d_keys, d_offsets, n, d_max_moves, d_moved, d_n_moved, stream));

@@ -179,6 +179,12 @@ PROTOTYPES = {
     "mee_admission_decay": (C.c_int, [_vp, _u32, _vp]),
     "mee_group_find_or_insert_admit": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _u32, _vp, _u32, _vp, _vp]),
     "mee_group_admission_decay": (C.c_int, [_vp, _u32, _vp]),
+    # admission into a hot/cold pair (the sketch is the hot table's): creating table, counting table, keys, n, out, found, min_count, stream
+    "mee_find_or_insert_admit_missing": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _u32, _vp]),
+    # ... over a group of pairs: hot, cold, keys, member offsets, n, out, out_dtype, found, to_cold, min_count, min_counts, flags, stream
+    "mee_group_find_or_insert_admit_tiered": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp]),
+    # ... in front of the pooled launch: hot, cold, keys, n, bag offsets, bags_per_table, found, to_cold, min_count, min_counts, stream
+    "mee_group_ensure_admit_tiered": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _u32, _vp, _vp]),
     "mee_locate": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "mee_table_plane": (C.c_int, [_vp, _u32, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_u32)]),
     "mee_device_calibration": (C.c_int, [C.c_int32, C.POINTER(Calibration)]),

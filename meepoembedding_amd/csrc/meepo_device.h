@@ -706,12 +706,15 @@ __device__ __forceinline__ void creation_write(const Desc& d, const Init& in, ui
 //   member_of(lo, live) -> {d, in, dim4}: pointers to the descriptor and the init record member lo creates in (for a group of pairs: of the tier
 //                          to_cold selects) and its row width; `live` = the position has a key to create or a tombstone to flag.  RESERVED_KEY (a
 //                          RECLAIMED key in the batch; EMPTY is padding, silent) and TABLE_FULL go to that record's status word.
-// A gate in front of tile_locate (admission) belongs behind the tombstone's flag and in front of the second `continue`: ensure_admit_grouped_kernel
-// (meepo_group.hip) keeps its own text there.
-template <bool ROWS_OUT, bool BF16, class MemberOf>
+//   gate(lo, key) -> bool:  whether a missing key of member lo may be created at all (admission: the creations over a group of pairs, meepo_group.hip).
+//                          It stands behind the tombstone's flag and in front of the second `continue`, so a wave whose missing keys were all turned
+//                          away leaves there; a position turned away keeps what the lookup wrote.  NoGate, the default, is no code at all.
+//                          (ensure_admit_grouped_kernel, meepo_group.hip, keeps its own text with its gate in the same place.)
+struct NoGate {};
+template <bool ROWS_OUT, bool BF16, class MemberOf, class Gate = NoGate>
 __device__ __forceinline__ void ensure_grouped_body(uint64_t* loff, uint32_t n_tables, const uint64_t* __restrict__ offsets, uint64_t off_stride,
                                                     const int64_t* __restrict__ keys, uint64_t n, const uint8_t* __restrict__ found,
-                                                    float4* __restrict__ out, MemberOf&& member_of) {
+                                                    float4* __restrict__ out, MemberOf&& member_of, Gate gate = Gate{}) {
     stage_offsets(loff, offsets, off_stride, n_tables, n);
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -726,7 +729,10 @@ __device__ __forceinline__ void ensure_grouped_body(uint64_t* loff, uint32_t n_t
         const uint32_t lo = member_of_position(loff, n_tables, i);
         const auto m = member_of(lo, act || tomb);
         if (tomb && tl == 0) atomicOr(m.in->status, (uint32_t)MEE_STATUS_RESERVED_KEY);
-        if (!__any(act)) continue;  // wave-uniform: a tombstone was all there was
+        if constexpr (!std::is_same_v<Gate, NoGate>) {
+            if (act) act = gate(lo, key);
+        }
+        if (!__any(act)) continue;  // wave-uniform: a tombstone was all there was (or nobody passed the gate)
         const auto d = *m.d;
         bool is_new, full;
         const int64_t slot = tile_locate<true, true>(const_cast<int64_t*>(d.tkeys), d.nb, key, act, tile, tl, is_new, full);

@@ -381,11 +381,13 @@ __global__ __launch_bounds__(256) void ensure_admit_grouped_kernel(const GroupDe
 // Grouped admission, the counting launch (between the find and the creation of mee_group_find_or_insert_admit): one thread per position of the jagged
 // batch, positions indexed in 64 bits.  A position inside [offsets[0], offsets[n_tables]) and below n whose found byte is 0 and whose key is not
 // reserved adds 1 to the three counters of ITS member's sketch (stage_offsets / member_of_position, meepo_device.h); a key that occurs
-// c times adds c.  Integer atomicAdd commutes: the sketch after the launch does not depend on the order.
+// c times adds c.  Integer atomicAdd commutes: the sketch after the launch does not depend on the order.  off_stride: stage_offsets' — 1 for a jagged
+// batch, bags_per_table where the members' bounds are every bags_per_table-th entry of a bag-offset array (mee_group_ensure_admit_tiered).
 __global__ __launch_bounds__(256) void sketch_add_grouped_kernel(const GroupAdmit* __restrict__ admit, uint32_t n_tables, const uint64_t* __restrict__ offsets,
-                                                                 const int64_t* __restrict__ keys, uint64_t n, const uint8_t* __restrict__ found) {
+                                                                 uint64_t off_stride, const int64_t* __restrict__ keys, uint64_t n,
+                                                                 const uint8_t* __restrict__ found) {
     __shared__ uint64_t loff[kMaxGroupTables + 1];
-    stage_offsets(loff, offsets, 1, n_tables, n);
+    stage_offsets(loff, offsets, off_stride, n_tables, n);
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         if (i < loff[0] || i >= loff[n_tables] || found[i]) continue;
         const int64_t k = keys[i];
@@ -439,6 +441,51 @@ __global__ __launch_bounds__(256) void ensure_tiered_grouped_rows_kernel(const G
                                                                          const uint8_t* __restrict__ to_cold, uint32_t dim4, float4* __restrict__ out) {
     __shared__ uint64_t loff[kMaxGroupTables + 1];
     ensure_grouped_body<true, BF16>(loff, n_tables, offsets, 1, keys, n, found, out, TierOf{hot_desc, cold_desc, hot_init, cold_init, to_cold, dim4});
+}
+
+// Admission over a group of pairs (SPEC.md §3 "Tiering": the pair's sketch is its HOT table's).  The gate of the two creations below: the tile of a
+// missing position reads the three counters of its member's hot sketch — `admit` is the HOT group's d_admit whatever to_cold says, final since the
+// kernel boundary behind sketch_add_grouped_kernel and not written here; the 16 lanes of a tile read the same three words, one request each — and
+// the key goes on to tile_locate only when their minimum reached min_counts[member] (when given, else min_count).
+struct AdmitGate {
+    const GroupAdmit* admit;
+    uint32_t min_count;
+    const uint32_t* min_counts;
+    __device__ bool operator()(uint32_t lo, int64_t key) const {
+        const GroupAdmit a = admit[lo];
+        uint32_t est = 0xFFFFFFFFu;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) est = min(est, a.sketch[sketch_index(key, r, a.log2w)]);
+        return est >= (min_counts ? min_counts[lo] : min_count);
+    }
+};
+
+// mee_group_ensure_admit_tiered: ensure_tiered_grouped_kernel behind the gate (no rows out; member bounds every bags_per_table-th bag offset)
+__global__ __launch_bounds__(256) void ensure_admit_tiered_grouped_kernel(const GroupDesc* __restrict__ hot_desc, const GroupInit* __restrict__ hot_init,
+                                                                          const GroupDesc* __restrict__ cold_desc, const GroupInit* __restrict__ cold_init,
+                                                                          const GroupAdmit* __restrict__ hot_admit, uint32_t n_tables,
+                                                                          const uint64_t* __restrict__ offsets, uint64_t bags_per_table,
+                                                                          const int64_t* __restrict__ keys, uint64_t n, const uint8_t* __restrict__ found,
+                                                                          const uint8_t* __restrict__ to_cold, uint32_t dim4, uint32_t min_count,
+                                                                          const uint32_t* __restrict__ min_counts) {
+    __shared__ uint64_t loff[kMaxGroupTables + 1];
+    ensure_grouped_body<false, false>(loff, n_tables, offsets, bags_per_table, keys, n, found, nullptr,
+                                      TierOf{hot_desc, cold_desc, hot_init, cold_init, to_cold, dim4}, AdmitGate{hot_admit, min_count, min_counts});
+}
+
+// mee_group_find_or_insert_admit_tiered: ensure_tiered_grouped_rows_kernel<BF16> behind the gate; a position turned away keeps the hot default row
+// the lookup wrote
+template <bool BF16>
+__global__ __launch_bounds__(256) void ensure_admit_tiered_grouped_rows_kernel(const GroupDesc* __restrict__ hot_desc, const GroupInit* __restrict__ hot_init,
+                                                                               const GroupDesc* __restrict__ cold_desc, const GroupInit* __restrict__ cold_init,
+                                                                               const GroupAdmit* __restrict__ hot_admit, uint32_t n_tables,
+                                                                               const uint64_t* __restrict__ offsets, const int64_t* __restrict__ keys,
+                                                                               uint64_t n, const uint8_t* __restrict__ found,
+                                                                               const uint8_t* __restrict__ to_cold, uint32_t dim4, float4* __restrict__ out,
+                                                                               uint32_t min_count, const uint32_t* __restrict__ min_counts) {
+    __shared__ uint64_t loff[kMaxGroupTables + 1];
+    ensure_grouped_body<true, BF16>(loff, n_tables, offsets, 1, keys, n, found, out, TierOf{hot_desc, cold_desc, hot_init, cold_init, to_cold, dim4},
+                                    AdmitGate{hot_admit, min_count, min_counts});
 }
 
 }  // namespace mee
@@ -680,7 +727,7 @@ extern "C" int mee_group_find_or_insert_admit(mee_group* g, const int64_t* d_key
     if (int rc = group_admission_check(g, name)) return rc;
     return group_find_then_create(g, d_keys, d_offsets, n, d_out, out_dtype, d_found, stream, name, [&](hipStream_t st, uint8_t* found) {
         // every missing position counts its key in its member's sketch ...
-        sketch_add_grouped_kernel<<<grid_for(n, 256, 4096), 256, 0, st>>>(g->d_admit, g->n_tables, d_offsets, d_keys, n, found);
+        sketch_add_grouped_kernel<<<grid_for(n, 256, 4096), 256, 0, st>>>(g->d_admit, g->n_tables, d_offsets, 1, d_keys, n, found);
         // ... then the creation of mee_group_find_or_insert, for the positions whose estimate reached their member's threshold
         with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto b16) {
             ensure_admit_grouped_kernel<b16><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_init, g->d_admit, g->n_tables, d_offsets, d_keys, n, found, g->dim4, (float4*)d_out,
@@ -717,11 +764,21 @@ static int launch_find_grouped_tiered(mee_group* hot, mee_group* cold, const int
     return MEE_OK;
 }
 
-// creates: mee_group_find_or_insert_tiered (d_found required, d_to_cold read); otherwise mee_group_find_tiered
+// what admits of a group of pairs: a threshold for all members or one per member (device, n_tables entries); null = the call does not admit
+struct TierAdmission {
+    uint32_t min_count;
+    const uint32_t* d_min_counts;
+};
+
+// creates: mee_group_find_or_insert_tiered (d_found required, d_to_cold read); with `admits` mee_group_find_or_insert_admit_tiered, whose creation
+// stands behind the hot sketches; otherwise mee_group_find_tiered
 static int group_find_tiered_common(mee_group* hot, mee_group* cold, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype,
-                                    uint8_t* d_found, bool creates, const uint8_t* d_to_cold, uint32_t flags, void* stream, const char* name) {
+                                    uint8_t* d_found, bool creates, const uint8_t* d_to_cold, uint32_t flags, void* stream, const char* name,
+                                    const TierAdmission* admits = nullptr) {
     if (!hot || !cold || !d_offsets || (n && (!d_keys || !d_out || (creates && !d_found)))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
     if (int rc = tiered_groups_check(hot, cold, flags, name)) return rc;
+    if (admits)   // the pair's sketch is its hot table's: the cold members need none
+        if (int rc = group_admission_check(hot, name)) return rc;
     if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
     if (n == 0) return MEE_OK;
     if (int rc = group_refresh(hot, stream)) return rc;
@@ -732,10 +789,40 @@ static int group_find_tiered_common(mee_group* hot, mee_group* cold, const int64
     if (int rc = launch_find_grouped_tiered(hot, cold, d_keys, d_offsets, n, d_out, out_dtype, d_found, flags, st)) return rc;
     if (!creates) return MEE_OK;
     // 2) missing positions create their key in the tier their member was told (one creator per distinct key: the CAS decides) and return its initial row
-    with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto b16) {
-        ensure_tiered_grouped_rows_kernel<b16><<<grid_for(n, 16, 8192), 256, 0, st>>>(hot->d_desc, hot->d_init, cold->d_desc, cold->d_init, hot->n_tables, d_offsets, d_keys, n, d_found,
-                                                                                     d_to_cold, hot->dim4, (float4*)d_out);
-    });
+    if (!admits) {
+        with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto b16) {
+            ensure_tiered_grouped_rows_kernel<b16><<<grid_for(n, 16, 8192), 256, 0, st>>>(hot->d_desc, hot->d_init, cold->d_desc, cold->d_init, hot->n_tables, d_offsets, d_keys, n, d_found,
+                                                                                         d_to_cold, hot->dim4, (float4*)d_out);
+        });
+    } else {
+        // 2a) every position in neither tier counts its key in its member's HOT sketch ...
+        sketch_add_grouped_kernel<<<grid_for(n, 256, 4096), 256, 0, st>>>(hot->d_admit, hot->n_tables, d_offsets, 1, d_keys, n, d_found);
+        // 2b) ... then the same creation, for the positions whose estimate reached their member's threshold
+        with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto b16) {
+            ensure_admit_tiered_grouped_rows_kernel<b16><<<grid_for(n, 16, 8192), 256, 0, st>>>(hot->d_desc, hot->d_init, cold->d_desc, cold->d_init, hot->d_admit, hot->n_tables, d_offsets,
+                                                                                               d_keys, n, d_found, d_to_cold, hot->dim4, (float4*)d_out, admits->min_count,
+                                                                                               admits->d_min_counts);
+        });
+    }
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+extern "C" int mee_group_ensure_admit_tiered(mee_group* hot, mee_group* cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                                             const uint8_t* d_found, const uint8_t* d_to_cold, uint32_t min_count, const uint32_t* d_min_counts, void* stream) {
+    MEE_RANGE("mee_group_ensure_admit_tiered");
+    const char* name = "mee_group_ensure_admit_tiered";
+    if (!hot || !cold || (bags_per_table && !d_bag_offsets) || (n && (!d_keys || !d_found))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (int rc = tiered_groups_check(hot, cold, 0, name)) return rc;
+    if (int rc = group_admission_check(hot, name)) return rc;
+    if (bags_per_table == 0 || n == 0) return MEE_OK;
+    if (int rc = group_refresh(hot, stream)) return rc;
+    if (int rc = group_refresh(cold, stream)) return rc;
+    DeviceGuard guard(hot->device);
+    hipStream_t st = (hipStream_t)stream;
+    sketch_add_grouped_kernel<<<grid_for(n, 256, 4096), 256, 0, st>>>(hot->d_admit, hot->n_tables, d_bag_offsets, bags_per_table, d_keys, n, d_found);
+    ensure_admit_tiered_grouped_kernel<<<grid_for(n, 16, 8192), 256, 0, st>>>(hot->d_desc, hot->d_init, cold->d_desc, cold->d_init, hot->d_admit, hot->n_tables, d_bag_offsets,
+                                                                             bags_per_table, d_keys, n, d_found, d_to_cold, hot->dim4, min_count, d_min_counts);
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
@@ -751,6 +838,13 @@ int mee_group_find_or_insert_tiered(mee_group* hot, mee_group* cold, const int64
                                     uint8_t* d_found, const uint8_t* d_to_cold, uint32_t flags, void* stream) {
     MEE_RANGE("mee_group_find_or_insert_tiered");
     return group_find_tiered_common(hot, cold, d_keys, d_offsets, n, d_out, out_dtype, d_found, true, d_to_cold, flags, stream, "mee_group_find_or_insert_tiered");
+}
+int mee_group_find_or_insert_admit_tiered(mee_group* hot, mee_group* cold, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* d_out, uint32_t out_dtype,
+                                          uint8_t* d_found, const uint8_t* d_to_cold, uint32_t min_count, const uint32_t* d_min_counts, uint32_t flags, void* stream) {
+    MEE_RANGE("mee_group_find_or_insert_admit_tiered");
+    const TierAdmission admits{min_count, d_min_counts};
+    return group_find_tiered_common(hot, cold, d_keys, d_offsets, n, d_out, out_dtype, d_found, true, d_to_cold, flags, stream, "mee_group_find_or_insert_admit_tiered",
+                                    &admits);
 }
 
 int mee_find_grouped(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, size_t n, float* d_out, uint8_t* d_found,

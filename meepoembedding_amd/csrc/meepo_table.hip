@@ -333,6 +333,9 @@ __global__ __launch_bounds__(256) void sketch_add_kernel(const int64_t* __restri
     }
 }
 // after all additions of the batch: skip[i] = 1 unless the position's key is absent AND its estimate reached min_count
+// TOMB_THROUGH (mee_find_or_insert_admit_missing): a missing RECLAIMED key is not skipped either — the ensure pass creates nothing for a reserved key
+// and flags it on its table's status word, exactly where mee_find_or_insert_missing flags it; false is the kernel as it was
+template <bool TOMB_THROUGH = false>
 __global__ __launch_bounds__(256) void sketch_decide_kernel(const int64_t* __restrict__ keys, const uint8_t* __restrict__ found, uint64_t n,
                                                             const uint32_t* __restrict__ sketch, uint32_t log2w, uint32_t min_count,
                                                             uint8_t* __restrict__ skip) {
@@ -344,6 +347,9 @@ __global__ __launch_bounds__(256) void sketch_decide_kernel(const int64_t* __res
 #pragma unroll
             for (int r = 0; r < 3; ++r) est = min(est, sketch[sketch_index(k, r, log2w)]);
             s = est >= min_count ? 0 : 1;
+        }
+        if constexpr (TOMB_THROUGH) {
+            if (!found[i] && k == kReclaimed) s = 0;
         }
         skip[i] = s;
     }
@@ -902,7 +908,33 @@ int mee_find_or_insert_admit(mee_table* t, const int64_t* d_keys, size_t n, floa
     if (int rc = find_plane(t, t->values, t->default_value, d_keys, n, d_out, fmask, stream)) return rc;
     const unsigned gl = grid_for(n, 256, 4096);
     sketch_add_kernel<<<gl, 256, 0, st>>>(d_keys, fmask, n, t->sketch, t->sketch_log2w);
-    sketch_decide_kernel<<<gl, 256, 0, st>>>(d_keys, fmask, n, t->sketch, t->sketch_log2w, min_count, skip);
+    sketch_decide_kernel<false><<<gl, 256, 0, st>>>(d_keys, fmask, n, t->sketch, t->sketch_log2w, min_count, skip);
+    ensure_direct_kernel<64><<<grid_for(n, 256, 8192), 256, 0, st>>>(t->keys, (float4*)t->values, (float4*)t->s1, (float4*)t->s2, t->nb, t->dim4,
+                                                                d_keys, (uint32_t)n, skip, t->optimizer, t->init_acc, t->initializer, t->init_scale,
+                                                                t->init_seed, t->default_value, t->ctr, t->hits, (float4*)d_out);   // admitted positions get their initial row here
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+// the admitting sibling of mee_find_or_insert_missing (a hot/cold pair: `counts` is the pair's hot table, `t` the tier that creates): the last three
+// launches of mee_find_or_insert_admit on buffers a find over both tiers already filled, counting in counts' sketch and creating in t
+int mee_find_or_insert_admit_missing(mee_table* t, mee_table* counts, const int64_t* d_keys, size_t n, float* d_out, const uint8_t* d_found, uint32_t min_count,
+                                     void* stream) {
+    MEE_RANGE("mee_find_or_insert_admit_missing");
+    const char* name = "mee_find_or_insert_admit_missing";
+    MEE_FP32_ROWS_ONLY(t, name);
+    MEE_FP32_ROWS_ONLY(counts, name);
+    if (!t || !counts || (n && (!d_keys || !d_out || !d_found))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (!counts->sketch) return fail(MEE_ERR_UNSUPPORTED, "%s: the counting table was created without MEE_FLAG_ADMISSION", name);
+    if (t->device != counts->device || t->dim != counts->dim)
+        return fail(MEE_ERR_INVALID_ARG, "%s: the two tables differ in device (%d, %d) or dim (%u, %u)", name, t->device, counts->device, t->dim, counts->dim);
+    if (int rc = check_batch(t, n, name, stream)) return rc;
+    if (n == 0) return MEE_OK;
+    DeviceGuard g(t->device);
+    hipStream_t st = as_stream(stream);
+    uint8_t* skip = reinterpret_cast<uint8_t*>(t->bs.occ);     // t's own scratch (max_batch x 4 bytes), as mee_find_or_insert_admit uses it
+    const unsigned gl = grid_for(n, 256, 4096);
+    sketch_add_kernel<<<gl, 256, 0, st>>>(d_keys, d_found, n, counts->sketch, counts->sketch_log2w);
+    sketch_decide_kernel<true><<<gl, 256, 0, st>>>(d_keys, d_found, n, counts->sketch, counts->sketch_log2w, min_count, skip);
     ensure_direct_kernel<64><<<grid_for(n, 256, 8192), 256, 0, st>>>(t->keys, (float4*)t->values, (float4*)t->s1, (float4*)t->s2, t->nb, t->dim4,
                                                                 d_keys, (uint32_t)n, skip, t->optimizer, t->init_acc, t->initializer, t->init_scale,
                                                                 t->init_seed, t->default_value, t->ctr, t->hits, (float4*)d_out);   // admitted positions get their initial row here

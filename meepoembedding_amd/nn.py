@@ -44,17 +44,33 @@ def _check_out_dtype(table, out_dtype: torch.dtype, pooled: bool = False) -> tor
 
 def _check_min_count(table, min_count, layer: str, creates: bool = True):
     """A layer's min_count (admission, SPEC.md §3 find_or_insert_admit): None, or a threshold for a LookupTable or a uniform fp32 TableGroup whose
-    tables were all created with admission=True.  Everything else is refused at construction, before any launch, saying which case it is."""
+    tables were all created with admission=True, or for a TieredTableGroup (and, under a bag layer, a TieredLookupTable) of native pairs whose HOT
+    tables were (SPEC.md §3 "Tiering": a pair counts in its hot table's sketch).  Everything else is refused at construction, before any launch,
+    saying which case it is."""
     if min_count is None:
         return None
     from .table import LookupTable, TableGroup
+    from .tiered import TieredLookupTable, TieredTableGroup
     name = type(table).__name__
     if not creates:
         raise ValueError(f"{layer}: min_count needs create_missing=True (admission decides when an unseen id is created; without creation there is nothing to decide)")
     if isinstance(min_count, bool) or not isinstance(min_count, int) or not 0 <= min_count < 1 << 32:
         raise ValueError(f"{layer}: min_count must be an int in [0, 2^32) (got {min_count!r})")
-    if "Tiered" in name:
-        raise ValueError(f"{layer}: min_count over {name}: a hot/cold pair has no admission (TieredLookupTable has none, so a group of pairs has no per-member definition)")
+    if "Sharded" in name:   # ShardedTieredTableGroup too: before the tiered cases
+        raise ValueError(f"{layer}: min_count over {name}: admission exists on one device — a LookupTable, a TableGroup, a hot/cold pair or a TieredTableGroup — not on sharded or peer-mapped tables")
+    if isinstance(table, TieredLookupTable) and layer == "DynamicEmbedding":
+        raise ValueError(f"{layer}: min_count over {name}: this layer has no admitting forward over a hot/cold pair; use a DynamicEmbeddingCollection over "
+                         "TieredTableGroup([pair]) (one segment), whose training forward admits")
+    if isinstance(table, (TieredLookupTable, TieredTableGroup)):
+        pairs = table.tables if isinstance(table, TieredTableGroup) else [table]
+        for j, p in enumerate(pairs):
+            if not p._native():
+                raise ValueError(f"{layer}: min_count over {name}: admission needs hot/cold pairs of native LookupTables" +
+                                 (f" (member {j} holds other objects)" if isinstance(table, TieredTableGroup) else ""))
+            if not p.admission:
+                raise ValueError(f"{layer}: min_count over {name}: a hot/cold pair counts in its hot table's sketch, so every hot table needs admission=True (" +
+                                 (f"the hot table of member {j} has no sketch)" if isinstance(table, TieredTableGroup) else "this pair's hot table has no sketch)"))
+        return min_count
     if getattr(table, "mixed_dims", False):
         raise ValueError(f"{layer}: min_count over {name}: a mixed-width group creates unseen ids inside its pooled launch, which has no admission")
     if not isinstance(table, (LookupTable, TableGroup)):
@@ -211,8 +227,9 @@ def lookup_pooled(keys: torch.Tensor, bag_offsets: torch.Tensor, anchor: torch.T
     single table, whose apply probes for itself)"""
     layer = _layer(table_id)
     if getattr(layer.table, "pools_with_insert", False):   # a ShardedLookupTable / ShardedTableGroup: the owners create unseen ids inside the pooled lookup's own exchange
-        out, _ = layer.table.find_pooled(keys, bag_offsets, "mean" if mean else "sum", insert_missing=layer.create_missing and layer.training,
-                                         **_dtype_kw(layer))
+        creates = layer.create_missing and layer.training
+        out, _ = layer.table.find_pooled(keys, bag_offsets, "mean" if mean else "sum", insert_missing=creates, **_dtype_kw(layer),
+                                         **(_admit_kw(layer) if creates else {}))   # (min_count: a TieredTableGroup, whose creation pass admits)
         return out, keys.new_empty(0)
     if layer.create_missing and layer.training and keys.numel():
         # dynamic vocabulary: unseen ids enter their table (hashed initial row + optimizer state) before the pooled lookup
@@ -474,9 +491,9 @@ class DynamicEmbeddingCollection(torch.nn.Module, _SparseOptimizerSettings):
     `group` may be a ShardedTableGroup (sharded.py): the same two ops, then ONE exchange per lookup and per step over the process group; or a
     TieredTableGroup (tiered.py), a collection of hot/cold pairs: forward is one launch (two in training), backward two grouped steps; or a
     ShardedTieredTableGroup, both at once (this layer and DynamicEmbeddingBag need nothing of their own for it).
-    min_count (a TableGroup whose tables were all created with admission=True): the training forward is the admitting grouped lookup — an unseen
-    id is created only once its table's sketch has seen it min_count times; until then it reads the default row and its gradient is dropped by
-    the step, which ignores absent keys.  Eval mode counts and creates nothing."""
+    min_count (a TableGroup whose tables were all created with admission=True, or a TieredTableGroup whose HOT tables were): the training forward is
+    the admitting grouped lookup — an unseen id is created only once its table's (its pair's hot table's) sketch has seen it min_count times; until
+    then it reads the default row and its gradient is dropped by the step, which ignores absent keys.  Eval mode counts and creates nothing."""
 
     def __init__(self, group, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
                  out_dtype: torch.dtype = torch.float32, min_count: int | None = None):
@@ -497,8 +514,9 @@ class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
     (keys [n], bag_offsets [n_bags + 1], both on the device) -> [n_bags, dim] sums or means; backward runs the table's sparse optimizer with the bag's grad row for every member (no [n, dim]
     tensor exists in either direction).  create_missing=True (training mode only): unseen ids are inserted with their
     hashed initial row first (one more pass over the ids); otherwise absent ids read the default row and are not trained.
-    min_count (with create_missing=True; a LookupTable or TableGroup created with admission=True): that creation pass admits — an unseen id is
-    created only once its table's sketch has seen it min_count times, and pools as the default row, untrained, until then."""
+    min_count (with create_missing=True; a LookupTable or TableGroup created with admission=True, or a TieredLookupTable / TieredTableGroup whose hot
+    tables were): that creation pass admits — an unseen id is created only once its table's sketch has seen it min_count times, and pools as the
+    default row, untrained, until then."""
 
     def __init__(self, table, mode: str = "sum", optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
                  create_missing: bool = False, out_dtype: torch.dtype = torch.float32, min_count: int | None = None):
@@ -533,7 +551,8 @@ class DynamicEmbedding(torch.nn.Module):
     out_dtype=torch.bfloat16 (a LookupTable in HBM only): the lookup writes bf16 rows — what `.to(torch.bfloat16)` on the fp32 rows would give —
     and backward widens the bf16 grad before the table's fp32 step.
     min_count (a LookupTable created with admission=True; fp32 out): the training forward is find_or_insert(min_count=) and the backward the plain
-    apply_* — the located forward has no admitting form; an id not yet admitted reads the default row and its gradient is dropped."""
+    apply_* — the located forward has no admitting form; an id not yet admitted reads the default row and its gradient is dropped.  Not over a
+    hot/cold pair: a DynamicEmbeddingCollection over TieredTableGroup([pair]) admits."""
 
     def __init__(self, table, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
                  out_dtype: torch.dtype = torch.float32, min_count: int | None = None):

@@ -22,6 +22,10 @@ Design (host logic only; every row still moves through the HIP kernels):
     position order and hot and cold keys interleave inside it, so two pooled passes, one per tier, could not rebuild the result bit
     for bit.  The launch feeds the policy's counters like `find` does (cold hits always, hot hits on every sample_every-th call).
 
+  * admission (`find_or_insert(min_count=)`, `find_pooled(insert_missing=True, min_count=)`, `admission_decay`; native tables): the pair's sketch is
+    its HOT table's — an id in neither tier is counted there and created, in the tier find_or_insert would pick, only once it has been asked for
+    min_count times (mee_find_or_insert_admit_missing); a sketch the cold table may have is never touched.
+
 `hot` / `cold` are any objects with the LookupTable methods, so the logic also runs on the CPU test adapters.
 """
 from __future__ import annotations
@@ -106,14 +110,20 @@ class TieredLookupTable:
         return isinstance(self.hot, LookupTable) and isinstance(self.cold, LookupTable)
 
     def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
-                    found: torch.Tensor | None = None, insert_missing: bool = False, out_dtype: torch.dtype = torch.float32):
+                    found: torch.Tensor | None = None, insert_missing: bool = False, out_dtype: torch.dtype = torch.float32,
+                    min_count: int | None = None):
         """Embedding-bag lookup over the pair (SPEC.md §3 find_pooled on the union): bag b = keys[bag_offsets[b]:bag_offsets[b+1]] ->
         ([n_bags, dim] sums or means in position order, per-key found mask).  An absent key reads the HOT table's default row, as in find.
         Two native tables: one launch (mee_find_pooled_tiered), which also feeds the placement policy's hit counters.
         insert_missing: absent keys are created first, in the tier find_or_insert would pick; `found` stays "present before the call".
+        min_count (with insert_missing): that creation admits as find_or_insert(min_count=) does; a key not yet admitted pools as the hot default row.
         out_dtype=torch.bfloat16: the finished bag row is rounded once."""
         if mode not in ("sum", "mean"):
             raise ValueError(f"mode must be 'sum' or 'mean' (got {mode!r})")
+        if min_count is not None:
+            if not insert_missing:
+                raise ValueError("min_count needs insert_missing=True (admission decides when an absent key is created)")
+            min_count = self._check_min_count(min_count)
         if not self._native():   # any objects with the LookupTable methods: their find, pooled here in position order
             if out_dtype not in (torch.float32, torch.bfloat16):
                 raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16 (got {out_dtype})")
@@ -141,11 +151,7 @@ class TieredLookupTable:
             found.copy_(hot.locate(k)[1] | cold.locate(k)[1])
             # ... then the absent keys are created exactly as find_or_insert creates them (their rows land in a scratch nobody reads)
             rows = torch.empty((n, self.dim), dtype=torch.float32, device=hot.device)
-            if self._room_for(n):
-                hot.find_or_insert_missing(k, rows, found)
-                self._hot_keys_ub += n
-            else:
-                cold.find_or_insert_missing(k, rows, found)
+            self._create_missing(k, rows, found, min_count)
         flags = 0
         if self.policy:
             self._calls += 1
@@ -199,16 +205,55 @@ class TieredLookupTable:
         keys = keys.contiguous().view(-1)
         return self.hot.remove(keys) | self.cold.remove(keys)
 
-    def find_or_insert(self, keys: torch.Tensor):
+    @property
+    def admission(self) -> bool:
+        """the pair admits iff its HOT table was created with admission=True: the pair's sketch is the hot table's (SPEC.md §3 "Tiering")"""
+        return bool(getattr(self.hot, "_opts", {}).get("admission", False))
+
+    def _check_min_count(self, min_count) -> int:
+        """the threshold of an admitting call on this pair, or the reason there is none"""
+        if not self._native():
+            raise ValueError("min_count needs a pair of native LookupTables (admission counts in the hot table's sketch on the device); "
+                             f"this pair holds {type(self.hot).__name__} / {type(self.cold).__name__}")
+        if isinstance(min_count, bool) or not isinstance(min_count, int) or not 0 <= min_count < 1 << 32:
+            raise ValueError(f"min_count must be an int in [0, 2^32) (got {min_count!r})")
+        if not self.admission:
+            raise ValueError("min_count needs the pair's hot table created with admission=True (the pair counts in the hot table's sketch; "
+                             "the hot table has no sketch)")
+        return min_count
+
+    def _create_missing(self, keys: torch.Tensor, out: torch.Tensor, found: torch.Tensor, min_count) -> None:
+        """the creation pass of find_or_insert / find_pooled(insert_missing=True) on buffers a lookup over both tiers filled: the positions `found`
+        leaves missing create their key in ONE tier — hot while _room_for(n) holds, charged with the whole n — and receive its initial row.
+        min_count: only the keys the HOT table's sketch admits (mee_find_or_insert_admit_missing), whichever tier creates."""
+        n = keys.numel()
+        room = self._room_for(n)
+        target = self.hot if room else self.cold
+        if room:
+            self._hot_keys_ub += n
+        if min_count is None:
+            target.find_or_insert_missing(keys, out, found)   # inserts the hashed initial row once per distinct new key
+            return
+        from . import _lib
+        k = target._keys(keys)
+        _lib.check(_lib.lib().mee_find_or_insert_admit_missing(target._h, self.hot._h, k.data_ptr(), k.numel(), out.data_ptr(), found.data_ptr(),
+                                                               int(min_count), target._s()))
+
+    def find_or_insert(self, keys: torch.Tensor, min_count: int | None = None):
+        """min_count (native tables, the hot one created with admission=True; SPEC.md §3 "Tiering"): an absent key is created — in the tier
+        find_or_insert would pick — only once the HOT table's sketch has seen it asked for min_count times, this batch included; until then its
+        positions return the hot default row.  0 and 1 admit at first sight (and still count)."""
+        if min_count is not None:
+            min_count = self._check_min_count(min_count)
         keys = keys.contiguous().view(-1)
         out, found = self.find(keys)
-        n = keys.numel()
-        if self._room_for(n):
-            self.hot.find_or_insert_missing(keys, out, found)   # inserts the hashed initial row once per distinct new key
-            self._hot_keys_ub += n
-        else:
-            self.cold.find_or_insert_missing(keys, out, found)
+        self._create_missing(keys, out, found, min_count)
         return out, found
+
+    def admission_decay(self, shift: int = 1) -> None:
+        """admission_decay of the hot table: the pair's sketch (a sketch the cold table may have is not the pair's)"""
+        self._check_min_count(0)
+        self.hot.admission_decay(shift)
 
     def _after_optimizer_step(self) -> None:
         if not (self.policy and self.rebalance_every):
@@ -393,6 +438,10 @@ class TieredTableGroup:
     launch (mee_group_find_tiered), two (mee_group_find_or_insert_tiered) and two grouped steps.  nn.DynamicEmbeddingCollection trains over it.
     Weighted bags and located rows are not offered over tiers.
 
+    Admission (every pair's hot table created with admission=True): find_or_insert(min_count=) and find_pooled(insert_missing=True, min_count=) are
+    the pair's admitting operators per member, each member counting in its own hot sketch, in three launches (mee_group_find_or_insert_admit_tiered)
+    and four (mee_group_ensure_admit_tiered in front of the pooled launch); admission_decay() is the hot group's.  The group keeps no counters.
+
     The owner's side of a sharded group of pairs (ShardedTieredTableGroup): find_pooled_jagged — the pooled lookup with the members' bag counts read
     from the device, one launch (mee_group_find_pooled_tiered_jagged) — and apply_indexed, two grouped indexed steps.
 
@@ -561,8 +610,36 @@ class TieredTableGroup:
         cut = bag_offsets.to(torch.int64).clamp(0, n).tolist()
         return bpt, [(j * bpt, cut[j * bpt], max(cut[j * bpt], cut[(j + 1) * bpt])) for j in range(len(self.tables))]
 
+    def _admission(self, min_count):
+        """-> (scalar threshold, device list | None) of an admitting call over the group, TableGroup._min_counts's rules and caching; or the reason
+        there is no such call: pairs that are not native tables, a member whose hot table has no sketch (named)"""
+        if not self._native:
+            raise ValueError("min_count needs pairs of native LookupTables (every pair counts in its hot table's sketch on the device)")
+        for j, p in enumerate(self.tables):
+            if not p.admission:
+                raise ValueError(f"min_count needs every pair's hot table created with admission=True (the hot table of member {j} has no sketch)")
+        return self.hot_group._min_counts(min_count)
+
+    def admission_decay(self, shift: int = 1) -> None:
+        """TieredLookupTable.admission_decay of every pair, one launch: the hot group's (the pairs' sketches are their hot tables')"""
+        self._admission(0)
+        self.hot_group.admission_decay(shift)
+
+    def _place_new_keys(self, n: int) -> None:
+        """where every member's new keys of a batch of n go: hot while pairs[j]._room_for(n) holds (charged with the whole n), else cold — onto the
+        device for the creation launch, rewritten only when a member's choice changes"""
+        goes_cold = []
+        for p in self.tables:
+            room = p._room_for(n)
+            if room:
+                p._hot_keys_ub += n
+            goes_cold.append(not room)
+        if goes_cold != self._goes_cold:
+            self._d_goes_cold.copy_(torch.tensor(goes_cold, dtype=torch.uint8))
+            self._goes_cold = goes_cold
+
     def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
-                    found: torch.Tensor | None = None, insert_missing: bool = False, out_dtype: torch.dtype = torch.float32):
+                    found: torch.Tensor | None = None, insert_missing: bool = False, out_dtype: torch.dtype = torch.float32, min_count=None):
         """TieredLookupTable.find_pooled of every pair on its bags, in one launch -> ([n_tables * bags_per_table, dim] sums or means in position
         order, per-key found mask).  An absent key reads its member's HOT table's default row.  With the policy on the launch feeds the
         members' hit counters (cold hits always, hot hits on every sample_every-th call).
@@ -572,9 +649,16 @@ class TieredTableGroup:
         pooled launch, which writes no found bytes.  n, the size of the WHOLE batch, is the only bound the host has on a member's new keys:
         it is conservative — a member is charged n keys per call, goes cold (after one refresh of its hot table's size, which synchronises)
         earlier than the pair on its own slice would, never later.
+        min_count (with insert_missing; an int or one threshold per member): the creation admits, each member counting in its hot table's sketch
+        (mee_group_ensure_admit_tiered: one launch more, the count); a key not yet admitted pools as its member's hot default row.
         out_dtype=torch.bfloat16: the finished bag row is rounded once."""
         if mode not in ("sum", "mean"):
             raise ValueError(f"mode must be 'sum' or 'mean' (got {mode!r})")
+        admits = None
+        if min_count is not None:
+            if not insert_missing:
+                raise ValueError("min_count needs insert_missing=True (admission decides when an absent key is created)")
+            admits = self._admission(min_count)
         if not self._native:   # a loop over the pairs, member j on its slice of the keys and its bags_per_table bags
             if out_dtype not in (torch.float32, torch.bfloat16):
                 raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16 (got {out_dtype})")
@@ -608,16 +692,12 @@ class TieredTableGroup:
             # the found mask of the whole batch first (no counters: this pass is not a lookup of the model's) ...
             _lib.check(L.mee_group_find_pooled_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, found.data_ptr(), m, 0, s))
             # ... then every member creates its absent keys in the tier its pair would pick
-            goes_cold = []
-            for p in self.tables:
-                room = p._room_for(n)
-                if room:
-                    p._hot_keys_ub += n
-                goes_cold.append(not room)
-            if goes_cold != self._goes_cold:
-                self._d_goes_cold.copy_(torch.tensor(goes_cold, dtype=torch.uint8))
-                self._goes_cold = goes_cold
-            _lib.check(L.mee_group_ensure_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, found.data_ptr(), self._d_goes_cold.data_ptr(), s))
+            self._place_new_keys(n)
+            if admits is None:
+                _lib.check(L.mee_group_ensure_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, found.data_ptr(), self._d_goes_cold.data_ptr(), s))
+            else:   # ... those that its hot sketch admits
+                _lib.check(L.mee_group_ensure_admit_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, found.data_ptr(), self._d_goes_cold.data_ptr(),
+                                                           admits[0], admits[1].data_ptr() if admits[1] is not None else None, s))
         _lib.check(L.mee_group_find_pooled_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt,
                                                   None if creates else found.data_ptr(), m, self._count_flags(), s))
         return out, found
@@ -683,28 +763,30 @@ class TieredTableGroup:
         return out, found
 
     def find_or_insert(self, keys: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
-                       out_dtype: torch.dtype = torch.float32):
+                       out_dtype: torch.dtype = torch.float32, min_count=None):
         """TieredLookupTable.find_or_insert of every pair on its segment, in TWO launches whatever the number of tables
         (mee_group_find_or_insert_tiered): find, then one creation launch that also returns the created keys' initial rows.  found = present before
         the call.  Member j's new keys go to its hot table while pairs[j]._room_for(n) holds, else to its cold table; n is the size of the WHOLE
-        batch, as in find_pooled(insert_missing=True): conservative, a member goes cold earlier than the pair on its own slice would, never later."""
+        batch, as in find_pooled(insert_missing=True): conservative, a member goes cold earlier than the pair on its own slice would, never later.
+        min_count (every pair's hot table created with admission=True; mee_group_find_or_insert_admit_tiered, THREE launches):
+        TieredLookupTable.find_or_insert(min_count=) per member on its segment, each member counting in its own hot sketch — an int, or one
+        threshold per member (TableGroup.find_or_insert's rules); the members are charged with n as without it, admitted or not."""
+        admits = None if min_count is None else self._admission(min_count)
         if not self._native:
             return self._find_loop(keys, offsets, out, found, out_dtype, insert=True)
         from . import _lib
         from .table import _stream_ptr
         dt, k, n, out, found = self._lookup_args(keys, offsets, out, found, out_dtype)
         if n:
-            goes_cold = []
-            for p in self.tables:
-                room = p._room_for(n)
-                if room:
-                    p._hot_keys_ub += n
-                goes_cold.append(not room)
-            if goes_cold != self._goes_cold:
-                self._d_goes_cold.copy_(torch.tensor(goes_cold, dtype=torch.uint8))
-                self._goes_cold = goes_cold
-        _lib.check(_lib.lib().mee_group_find_or_insert_tiered(self.hot_group._h, self.cold_group._h, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), dt,
-                                                              found.data_ptr(), self._d_goes_cold.data_ptr(), self._count_flags(), _stream_ptr(self.device)))
+            self._place_new_keys(n)
+        hot, cold, to_cold = self.hot_group._h, self.cold_group._h, self._d_goes_cold.data_ptr()
+        if admits is None:
+            _lib.check(_lib.lib().mee_group_find_or_insert_tiered(hot, cold, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(), to_cold,
+                                                                  self._count_flags(), _stream_ptr(self.device)))
+        else:
+            _lib.check(_lib.lib().mee_group_find_or_insert_admit_tiered(hot, cold, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(), to_cold,
+                                                                        admits[0], admits[1].data_ptr() if admits[1] is not None else None,
+                                                                        self._count_flags(), _stream_ptr(self.device)))
         return out, found
 
     def apply_adagrad(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10) -> None:
