@@ -14,73 +14,66 @@
 
 The update happens INSIDE backward, so the layer has no torch parameters and needs no torch optimizer.  Both ops have
 fake (meta) kernels, so a model containing the layer traces and exports; they are opaque to the tracer (the table is
-state outside the graph, addressed by `table_id`).  Works with a LookupTable, a TieredLookupTable, a ShardedLookupTable
-or a PeerShardedTable (same method names).  Plumbing only: no kernel lives here.
+state outside the graph, addressed by `table_id`).  Plumbing only: no kernel lives here.
 Reference anchor: /root/reference/README.md:2 ("Embedding designed for recommendation … systems").
+
+What a table declares (tables are duck-typed; _traits() reads all of it once, when a layer is built, and nothing else here looks at a table's
+type or attributes).  Always: dim, find, find_or_insert, apply_adagrad, apply_adam with LookupTable's (a group: TableGroup's) parameters.
+Class-level flags, with the default that holds when a class says nothing:
+    supports_out_dtype = False          its lookups take out_dtype=torch.bfloat16
+    supports_pooled_out_dtype = False   its find_pooled does, though its find does not (may be set per instance: TieredLookupTable)
+    weighted_bags = True                find_pooled(weights=, located=) and pooled_weighted_backward exist
+    pools_with_insert = False           find_pooled(insert_missing=[, min_count=]) creates unseen ids itself and hands out no located rows
+    mixed_dims = False                  members of different dims: find_pooled(out=flat, located=, insert_missing=), views(), dims
+    hot_cold_pair = False               a hot/cold pair: DynamicEmbedding has no admitting forward over it
+Optional methods:
+    apply_pooled                        a group: bag b belongs to member b // bags_per_table, `tables` lists the members, the step is apply_pooled
+    find_located, find_or_insert_located, apply_discard, max_batch      ONE table whose lookups hand out slot handles for apply_*(slots=)
+    layout_epoch                        changes when stored rows move: handles a forward took are dropped by its backward
+    admission_refusal() -> str | None   why a layer's min_count is refused over this table (None: it admits); a class without the method has
+                                        no admission
+`_nn_prepared` on a table with find_located is this module's: the (tensor, length) whose apply partition the last training forward left pending.
 """
 from __future__ import annotations
 
 import itertools
 import weakref
+from typing import Callable, NamedTuple
 
 import torch
 
 from ._lib import refuse_narrow_rows as _refuse_narrow_rows
+from .table import SparseStep, mixed_layout
 
-_LAYERS: "weakref.WeakValueDictionary[int, DynamicEmbedding]" = weakref.WeakValueDictionary()
+_LAYERS: "weakref.WeakValueDictionary[int, _SparseLayer]" = weakref.WeakValueDictionary()
 _IDS = itertools.count(1)
 
 
-def _check_out_dtype(table, out_dtype: torch.dtype, pooled: bool = False) -> torch.dtype:
-    """A layer's out_dtype: fp32, or bf16 where the table's lookups can write it (LookupTable, TableGroup; pooled = a bag layer, whose lookup is
-    find_pooled: also a TieredLookupTable, which pools to bf16 while its find returns fp32 rows).  Refused at construction."""
-    if out_dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16 (got {out_dtype})")
-    if out_dtype != torch.float32 and not (getattr(table, "supports_out_dtype", False) or (pooled and getattr(table, "supports_pooled_out_dtype", False))):
-        raise ValueError(f"{type(table).__name__} has no bf16 lookup (tiered, sharded and peer-mapped tables return fp32 rows): use out_dtype=torch.float32 and "
-                         "cast in the model")
-    return out_dtype
+class _Traits(NamedTuple):
+    grouped: bool             # bags belong to members; the pooled step is apply_pooled
+    hands_located: bool       # lookup_pooled returns the located rows of its keys (a TableGroup on one device), not an empty tensor
+    located_table: bool       # one table whose lookups hand out slot handles
+    pools_with_insert: bool
+    weighted_bags: bool
+    mixed_dims: bool
+    bf16_rows: bool
+    bf16_bags: bool
+    hot_cold_pair: bool
+    has_epoch: bool
+    admission_refusal: Callable[[], str | None] | None
 
 
-def _check_min_count(table, min_count, layer: str, creates: bool = True):
-    """A layer's min_count (admission, SPEC.md §3 find_or_insert_admit): None, or a threshold for a LookupTable or a uniform fp32 TableGroup whose
-    tables were all created with admission=True, or for a TieredTableGroup (and, under a bag layer, a TieredLookupTable) of native pairs whose HOT
-    tables were (SPEC.md §3 "Tiering": a pair counts in its hot table's sketch).  Everything else is refused at construction, before any launch,
-    saying which case it is."""
-    if min_count is None:
-        return None
-    from .table import LookupTable, TableGroup
-    from .tiered import TieredLookupTable, TieredTableGroup
-    name = type(table).__name__
-    if not creates:
-        raise ValueError(f"{layer}: min_count needs create_missing=True (admission decides when an unseen id is created; without creation there is nothing to decide)")
-    if isinstance(min_count, bool) or not isinstance(min_count, int) or not 0 <= min_count < 1 << 32:
-        raise ValueError(f"{layer}: min_count must be an int in [0, 2^32) (got {min_count!r})")
-    if "Sharded" in name:   # ShardedTieredTableGroup too: before the tiered cases
-        raise ValueError(f"{layer}: min_count over {name}: admission exists on one device — a LookupTable, a TableGroup, a hot/cold pair or a TieredTableGroup — not on sharded or peer-mapped tables")
-    if isinstance(table, TieredLookupTable) and layer == "DynamicEmbedding":
-        raise ValueError(f"{layer}: min_count over {name}: this layer has no admitting forward over a hot/cold pair; use a DynamicEmbeddingCollection over "
-                         "TieredTableGroup([pair]) (one segment), whose training forward admits")
-    if isinstance(table, (TieredLookupTable, TieredTableGroup)):
-        pairs = table.tables if isinstance(table, TieredTableGroup) else [table]
-        for j, p in enumerate(pairs):
-            if not p._native():
-                raise ValueError(f"{layer}: min_count over {name}: admission needs hot/cold pairs of native LookupTables" +
-                                 (f" (member {j} holds other objects)" if isinstance(table, TieredTableGroup) else ""))
-            if not p.admission:
-                raise ValueError(f"{layer}: min_count over {name}: a hot/cold pair counts in its hot table's sketch, so every hot table needs admission=True (" +
-                                 (f"the hot table of member {j} has no sketch)" if isinstance(table, TieredTableGroup) else "this pair's hot table has no sketch)"))
-        return min_count
-    if getattr(table, "mixed_dims", False):
-        raise ValueError(f"{layer}: min_count over {name}: a mixed-width group creates unseen ids inside its pooled launch, which has no admission")
-    if not isinstance(table, (LookupTable, TableGroup)):
-        raise ValueError(f"{layer}: min_count over {name}: admission exists on a LookupTable and on a TableGroup on one device, not on sharded or peer-mapped tables")
-    members = table.tables if isinstance(table, TableGroup) else [table]
-    for j, t in enumerate(members):
-        if not t._opts["admission"]:
-            raise ValueError(f"{layer}: min_count needs every table created with admission=True (" +
-                             (f"member {j} of the group has no sketch)" if isinstance(table, TableGroup) else "this table has no sketch)"))
-    return min_count
+def _traits(table) -> _Traits:
+    """The protocol of the module docstring, read off a table once.  Only class-level things are looked at (and supports_pooled_out_dtype, which a
+    pair sets in __init__), so an object made without __init__ has its class's traits."""
+    grouped, inserts = hasattr(table, "apply_pooled"), bool(getattr(table, "pools_with_insert", False))
+    located_table = hasattr(table, "find_or_insert_located")
+    if located_table and not hasattr(table, "_nn_prepared"):
+        table._nn_prepared = None   # kept on the table, not on a layer: two layers over one table see each other's pending partition
+    bf16_rows = bool(getattr(table, "supports_out_dtype", False))
+    return _Traits(grouped, grouped and not inserts, located_table, inserts, bool(getattr(table, "weighted_bags", True)),
+                   bool(getattr(table, "mixed_dims", False)), bf16_rows, bf16_rows or bool(getattr(table, "supports_pooled_out_dtype", False)),
+                   bool(getattr(table, "hot_cold_pair", False)), hasattr(table, "layout_epoch"), getattr(table, "admission_refusal", None))
 
 
 def _admit_kw(layer) -> dict:
@@ -93,11 +86,52 @@ def _dtype_kw(layer) -> dict:
     return {} if layer.out_dtype == torch.float32 else {"out_dtype": layer.out_dtype}
 
 
-def _layer(table_id: int) -> "DynamicEmbedding":
+def _layer(table_id: int) -> "_SparseLayer":
     try:
         return _LAYERS[table_id]
     except KeyError:
         raise RuntimeError(f"meepo: no live DynamicEmbedding with table_id {table_id}") from None
+
+
+def _step_now(layer) -> SparseStep:
+    """the optimizer step a backward takes: the layer's settings as they are now (a schedule may have changed lr) and its next step number"""
+    layer.step += 1
+    return SparseStep(layer.optimizer, layer.lr, layer.eps, layer.betas[0], layer.betas[1], layer.step)
+
+
+def _bag_of(keys, bag_offsets):
+    """-> (length of every bag, bag index of every position)"""
+    lens = bag_offsets[1:] - bag_offsets[:-1]
+    return lens, torch.repeat_interleave(torch.arange(lens.numel(), device=keys.device), lens, output_size=keys.numel())
+
+
+def _member_offsets(group, bag_offsets):
+    """the members' key offsets of a bag batch over a group: member j holds the bags [j * bags_per_table, (j + 1) * bags_per_table)"""
+    return bag_offsets[::(bag_offsets.numel() - 1) // len(group.tables)].contiguous()
+
+
+def _create_unseen(layer, keys, bag_offsets) -> None:
+    """dynamic vocabulary (create_missing, training): unseen ids enter their table (hashed initial row + optimizer state) before the pooled lookup"""
+    if layer.create_missing and layer.training and keys.numel():
+        if layer.traits.grouped:
+            layer.table.find_or_insert(keys, _member_offsets(layer.table, bag_offsets), **_admit_kw(layer))
+        else:
+            layer.table.find_or_insert(keys, **_admit_kw(layer))
+
+
+def _epoch(table_id: int):
+    layer = _layer(table_id)
+    return layer.table.layout_epoch if layer.traits.has_epoch else None
+
+
+def _save_epoch(ctx, table_id: int) -> None:
+    """setup of a forward that hands slot handles to its backward: they are valid only while no table removes / clears / rehashes rows"""
+    ctx.table_id, ctx.layout_epoch = table_id, _epoch(table_id)
+
+
+def _fresh(ctx, located):
+    """the forward's handles, or an empty tensor when a table changed between forward and backward: the step then probes for itself"""
+    return located if _epoch(ctx.table_id) == ctx.layout_epoch else located.new_empty(0)
 
 
 @torch.library.custom_op("meepo::lookup", mutates_args=())
@@ -117,11 +151,7 @@ def _(keys, anchor, table_id, insert_missing):
 def apply_grad(keys: torch.Tensor, grad_rows: torch.Tensor, table_id: int) -> None:
     layer = _layer(table_id)
     g = grad_rows.reshape(-1, layer.table.dim).contiguous()
-    layer.step += 1
-    if layer.optimizer == "adagrad":
-        layer.table.apply_adagrad(keys.reshape(-1), g, lr=layer.lr, eps=layer.eps)
-    else:
-        layer.table.apply_adam(keys.reshape(-1), g, lr=layer.lr, beta1=layer.betas[0], beta2=layer.betas[1], eps=layer.eps, step=layer.step)
+    _step_now(layer).apply_to(layer.table, keys.reshape(-1), g)
 
 
 @apply_grad.register_fake
@@ -154,7 +184,7 @@ def lookup_located(keys: torch.Tensor, anchor: torch.Tensor, table_id: int, inse
     layer = _layer(table_id)
     table = layer.table
     flat = keys.reshape(-1)
-    if getattr(table, "_nn_prepared", None) is not None:   # an earlier forward's partition that no backward used
+    if table._nn_prepared is not None:   # an earlier forward's partition that no backward used
         table.apply_discard()
         table._nn_prepared = None
     prepare = prepare and flat.is_contiguous() and flat.numel() > 0 and flat.numel() <= table.max_batch
@@ -176,18 +206,14 @@ def apply_grad_located(keys: torch.Tensor, grad_rows: torch.Tensor, located: tor
     layer = _layer(table_id)
     g = grad_rows.reshape(-1, layer.table.dim).contiguous()
     slots = located if located.numel() == keys.numel() else None
-    layer.step += 1
-    prepared = getattr(layer.table, "_nn_prepared", None)
+    step = _step_now(layer)
+    prepared = layer.table._nn_prepared
     if prepared is not None:   # the forward's partition is for exactly (this tensor, this length), or it is dropped
         flat = keys.reshape(-1)
         if prepared != (flat.data_ptr(), flat.numel()):
             layer.table.apply_discard()
         layer.table._nn_prepared = None
-    if layer.optimizer == "adagrad":
-        layer.table.apply_adagrad(keys.reshape(-1), g, lr=layer.lr, eps=layer.eps, slots=slots)
-    else:
-        layer.table.apply_adam(keys.reshape(-1), g, lr=layer.lr, beta1=layer.betas[0], beta2=layer.betas[1], eps=layer.eps, step=layer.step,
-                               slots=slots)
+    step.apply_to(layer.table, keys.reshape(-1), g, slots=slots)
 
 
 @apply_grad_located.register_fake
@@ -198,26 +224,17 @@ def _(keys, grad_rows, located, table_id):
 def _setup_located(ctx, inputs, output):
     keys, _, table_id = inputs[:3]
     ctx.save_for_backward(keys, output[1])
-    ctx.table_id = table_id
-    ctx.layout_epoch = getattr(_layer(table_id).table, "layout_epoch", None)   # handles are slot numbers: stale once rows move
+    _save_epoch(ctx, table_id)
     ctx.mark_non_differentiable(output[1])
 
 
 def _backward_located(ctx, grad_out, _grad_located):
     keys, located = ctx.saved_tensors
-    if getattr(_layer(ctx.table_id).table, "layout_epoch", None) != ctx.layout_epoch:
-        located = located.new_empty(0)   # the table changed between forward and backward: the apply probes for itself
-    apply_grad_located(keys, grad_out.contiguous().to(torch.float32), located, ctx.table_id)   # a bf16 layer's grad is widened (exact): the step is the fp32 step
+    apply_grad_located(keys, grad_out.contiguous().to(torch.float32), _fresh(ctx, located), ctx.table_id)   # a bf16 layer's grad is widened (exact): the step is the fp32 step
     return None, None, None, None, None
 
 
 lookup_located.register_autograd(_backward_located, setup_context=_setup_located)
-
-
-def _hands_located(table) -> bool:
-    """does lookup_pooled over this table return the located rows of its keys (a TableGroup on one device) or an empty tensor (one table; the
-    sharded tables and groups, whose pooled lookup creates unseen ids itself and whose handles do not cross the exchange)?"""
-    return hasattr(table, "apply_pooled") and not getattr(table, "pools_with_insert", False)
 
 
 # ---- pooled: sum / mean per bag fused into the lookup, the bag's grad row indexed in the update ---------------------------
@@ -226,19 +243,13 @@ def lookup_pooled(keys: torch.Tensor, bag_offsets: torch.Tensor, anchor: torch.T
     """-> (pooled rows [n_bags, dim], located rows [n] — per-position handles the backward of this step reuses; empty for a
     single table, whose apply probes for itself)"""
     layer = _layer(table_id)
-    if getattr(layer.table, "pools_with_insert", False):   # a ShardedLookupTable / ShardedTableGroup: the owners create unseen ids inside the pooled lookup's own exchange
+    if layer.traits.pools_with_insert:   # a ShardedLookupTable / ShardedTableGroup: the owners create unseen ids inside the pooled lookup's own exchange
         creates = layer.create_missing and layer.training
         out, _ = layer.table.find_pooled(keys, bag_offsets, "mean" if mean else "sum", insert_missing=creates, **_dtype_kw(layer),
                                          **(_admit_kw(layer) if creates else {}))   # (min_count: a TieredTableGroup, whose creation pass admits)
         return out, keys.new_empty(0)
-    if layer.create_missing and layer.training and keys.numel():
-        # dynamic vocabulary: unseen ids enter their table (hashed initial row + optimizer state) before the pooled lookup
-        if hasattr(layer.table, "apply_pooled"):
-            bpt = (bag_offsets.numel() - 1) // len(layer.table.tables)
-            layer.table.find_or_insert(keys, bag_offsets[::bpt].contiguous(), **_admit_kw(layer))
-        else:
-            layer.table.find_or_insert(keys, **_admit_kw(layer))
-    if hasattr(layer.table, "apply_pooled"):   # a TableGroup
+    _create_unseen(layer, keys, bag_offsets)
+    if layer.traits.grouped:   # a TableGroup
         located = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
         out, _ = layer.table.find_pooled(keys, bag_offsets, "mean" if mean else "sum", located=located, **_dtype_kw(layer))
         return out, located
@@ -250,26 +261,21 @@ def lookup_pooled(keys: torch.Tensor, bag_offsets: torch.Tensor, anchor: torch.T
 def _(keys, bag_offsets, anchor, table_id, mean):
     layer = _layer(table_id)
     return (keys.new_empty((bag_offsets.numel() - 1, layer.table.dim), dtype=layer.out_dtype),
-            keys.new_empty(keys.numel() if _hands_located(layer.table) else 0))
+            keys.new_empty(keys.numel() if layer.traits.hands_located else 0))
 
 
 @torch.library.custom_op("meepo::apply_grad_pooled", mutates_args=())
 def apply_grad_pooled(keys: torch.Tensor, bag_offsets: torch.Tensor, grad_bags: torch.Tensor, located: torch.Tensor, table_id: int, mean: bool) -> None:
     layer = _layer(table_id)
-    lens = bag_offsets[1:] - bag_offsets[:-1]
-    bag_of = torch.repeat_interleave(torch.arange(lens.numel(), device=keys.device), lens, output_size=keys.numel())
+    lens, bag_of = _bag_of(keys, bag_offsets)
     g = grad_bags.contiguous()
     if mean:   # d mean / d row = 1 / length for every member of the bag
         g = g / lens.clamp(min=1).to(torch.float32)[:, None]
-    layer.step += 1
-    if hasattr(layer.table, "apply_pooled"):   # a TableGroup: the whole collection in one step, on the rows the forward located
-        layer.table.apply_pooled(keys, bag_offsets, g, bag_of, layer.optimizer, lr=layer.lr, eps=layer.eps, beta1=layer.betas[0],
-                                 beta2=layer.betas[1], step=layer.step, located=located if located.numel() == keys.numel() else None)
-    elif layer.optimizer == "adagrad":
-        layer.table.apply_adagrad(keys, g, lr=layer.lr, eps=layer.eps, grad_index=bag_of)
+    step = _step_now(layer)
+    if layer.traits.grouped:   # a TableGroup: the whole collection in one step, on the rows the forward located
+        layer.table.apply_pooled(keys, bag_offsets, g, bag_of, *step, located=located if located.numel() == keys.numel() else None)
     else:
-        layer.table.apply_adam(keys, g, lr=layer.lr, beta1=layer.betas[0], beta2=layer.betas[1], eps=layer.eps, step=layer.step,
-                               grad_index=bag_of)
+        step.apply_to(layer.table, keys, g, grad_index=bag_of)
 
 
 @apply_grad_pooled.register_fake
@@ -280,17 +286,14 @@ def _(keys, bag_offsets, grad_bags, located, table_id, mean):
 def _setup_pooled(ctx, inputs, output):
     keys, bag_offsets, _, table_id, mean = inputs
     ctx.save_for_backward(keys, bag_offsets, output[1])
-    ctx.table_id, ctx.mean = table_id, mean
-    # the located handles are slot numbers: valid only while no member table removes / clears / rehashes rows
-    ctx.layout_epoch = getattr(_layer(table_id).table, "layout_epoch", None)
+    ctx.mean = mean
+    _save_epoch(ctx, table_id)
     ctx.mark_non_differentiable(output[1])
 
 
 def _backward_pooled(ctx, grad_out, _grad_located):
     keys, bag_offsets, located = ctx.saved_tensors
-    if getattr(_layer(ctx.table_id).table, "layout_epoch", None) != ctx.layout_epoch:
-        located = located.new_empty(0)   # a table changed between forward and backward: the apply probes for itself
-    apply_grad_pooled(keys, bag_offsets, grad_out.contiguous().to(torch.float32), located, ctx.table_id, ctx.mean)   # widened BEFORE the mean's division
+    apply_grad_pooled(keys, bag_offsets, grad_out.contiguous().to(torch.float32), _fresh(ctx, located), ctx.table_id, ctx.mean)   # widened BEFORE the mean's division
     return None, None, None, None, None
 
 
@@ -311,7 +314,6 @@ def lookup_pooled_mixed(keys: torch.Tensor, bag_offsets: torch.Tensor, anchor: t
 
 
 def _mixed_total(group, bag_offsets) -> int:
-    from .table import mixed_layout
     return mixed_layout(group.dims, (bag_offsets.numel() - 1) // len(group.tables))[2]
 
 
@@ -325,8 +327,7 @@ def _(keys, bag_offsets, anchor, table_id, mean):
 def apply_grad_pooled_mixed(keys: torch.Tensor, bag_offsets: torch.Tensor, grad_flat: torch.Tensor, located: torch.Tensor, table_id: int, mean: bool) -> None:
     layer = _layer(table_id)
     group = layer.table
-    lens = bag_offsets[1:] - bag_offsets[:-1]
-    bag_of = torch.repeat_interleave(torch.arange(lens.numel(), device=keys.device), lens, output_size=keys.numel())
+    lens, bag_of = _bag_of(keys, bag_offsets)
     g = grad_flat.contiguous()
     if mean:   # d mean / d row = 1 / length for every member of the bag; the bags of member j are rows of its own block
         bpt = lens.numel() // len(group.tables)
@@ -334,9 +335,7 @@ def apply_grad_pooled_mixed(keys: torch.Tensor, bag_offsets: torch.Tensor, grad_
         g = g.clone()
         for j, v in enumerate(group.views(g, bpt)):
             v /= inv[j * bpt:(j + 1) * bpt, None]
-    layer.step += 1
-    group.apply_pooled(keys, bag_offsets, g, bag_of, layer.optimizer, lr=layer.lr, eps=layer.eps, beta1=layer.betas[0], beta2=layer.betas[1],
-                       step=layer.step, located=located if located.numel() == keys.numel() else None)
+    group.apply_pooled(keys, bag_offsets, g, bag_of, *_step_now(layer), located=located if located.numel() == keys.numel() else None)
 
 
 @apply_grad_pooled_mixed.register_fake
@@ -346,9 +345,7 @@ def _(keys, bag_offsets, grad_flat, located, table_id, mean):
 
 def _backward_pooled_mixed(ctx, grad_flat, _grad_located):
     keys, bag_offsets, located = ctx.saved_tensors
-    if getattr(_layer(ctx.table_id).table, "layout_epoch", None) != ctx.layout_epoch:
-        located = located.new_empty(0)   # a table changed between forward and backward: the step probes for itself
-    apply_grad_pooled_mixed(keys, bag_offsets, grad_flat.contiguous().to(torch.float32), located, ctx.table_id, ctx.mean)
+    apply_grad_pooled_mixed(keys, bag_offsets, grad_flat.contiguous().to(torch.float32), _fresh(ctx, located), ctx.table_id, ctx.mean)
     return None, None, None, None, None
 
 
@@ -363,12 +360,7 @@ def lookup_pooled_weighted(keys: torch.Tensor, bag_offsets: torch.Tensor, weight
                            table_id: int) -> tuple[torch.Tensor, torch.Tensor]:
     """-> (pooled rows [n_bags, dim], located rows [n] — per-position handles the backward of this step reuses)"""
     layer = _layer(table_id)
-    if layer.create_missing and layer.training and keys.numel():
-        if hasattr(layer.table, "apply_pooled"):
-            bpt = (bag_offsets.numel() - 1) // len(layer.table.tables)
-            layer.table.find_or_insert(keys, bag_offsets[::bpt].contiguous(), **_admit_kw(layer))
-        else:
-            layer.table.find_or_insert(keys, **_admit_kw(layer))
+    _create_unseen(layer, keys, bag_offsets)
     located = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
     out, _ = layer.table.find_pooled(keys, bag_offsets, "sum", weights=weights.contiguous(), located=located, **_dtype_kw(layer))
     return out, located
@@ -388,14 +380,10 @@ def apply_grad_pooled_weighted(keys: torch.Tensor, bag_offsets: torch.Tensor, we
     loc = located if located.numel() == keys.numel() else None
     grads, wg = layer.table.pooled_weighted_backward(keys, bag_offsets, weights.contiguous(), grad_bags.contiguous(), located=loc,
                                                      want_weight_grads=weight_grad)
-    layer.step += 1
-    kw = dict(lr=layer.lr, eps=layer.eps) if layer.optimizer == "adagrad" else \
-        dict(lr=layer.lr, beta1=layer.betas[0], beta2=layer.betas[1], eps=layer.eps, step=layer.step)
-    apply = layer.table.apply_adagrad if layer.optimizer == "adagrad" else layer.table.apply_adam
-    if hasattr(layer.table, "apply_pooled"):   # a TableGroup: one grouped step over the members' key segments (it probes for itself)
-        apply(keys, bag_offsets[::(bag_offsets.numel() - 1) // len(layer.table.tables)].contiguous(), grads, **kw)
+    if layer.traits.grouped:   # a TableGroup: one grouped step over the members' key segments (it probes for itself)
+        _step_now(layer).apply_to(layer.table, keys, _member_offsets(layer.table, bag_offsets), grads)
     else:
-        apply(keys, grads, slots=loc, **kw)
+        _step_now(layer).apply_to(layer.table, keys, grads, slots=loc)
     return wg if wg is not None else grads.new_empty(0)
 
 
@@ -407,16 +395,13 @@ def _(keys, bag_offsets, weights, grad_bags, located, table_id, weight_grad):
 def _setup_pooled_weighted(ctx, inputs, output):
     keys, bag_offsets, weights, _, table_id = inputs
     ctx.save_for_backward(keys, bag_offsets, weights, output[1])
-    ctx.table_id = table_id
-    ctx.layout_epoch = getattr(_layer(table_id).table, "layout_epoch", None)   # as _setup_pooled
+    _save_epoch(ctx, table_id)
     ctx.mark_non_differentiable(output[1])
 
 
 def _backward_pooled_weighted(ctx, grad_out, _grad_located):
     keys, bag_offsets, weights, located = ctx.saved_tensors
-    if getattr(_layer(ctx.table_id).table, "layout_epoch", None) != ctx.layout_epoch:
-        located = located.new_empty(0)   # a table changed between forward and backward: the backward probes for itself
-    wg = apply_grad_pooled_weighted(keys, bag_offsets, weights, grad_out.contiguous().to(torch.float32), located, ctx.table_id, ctx.needs_input_grad[2])
+    wg = apply_grad_pooled_weighted(keys, bag_offsets, weights, grad_out.contiguous().to(torch.float32), _fresh(ctx, located), ctx.table_id, ctx.needs_input_grad[2])
     return None, None, (wg.view(weights.shape) if ctx.needs_input_grad[2] else None), None, None
 
 
@@ -441,12 +426,7 @@ def _(keys, offsets, anchor, table_id, insert_missing):
 @torch.library.custom_op("meepo::apply_grad_jagged", mutates_args=())
 def apply_grad_jagged(keys: torch.Tensor, offsets: torch.Tensor, grad_rows: torch.Tensor, table_id: int) -> None:
     layer = _layer(table_id)
-    layer.step += 1
-    if layer.optimizer == "adagrad":
-        layer.group.apply_adagrad(keys, offsets, grad_rows.contiguous(), lr=layer.lr, eps=layer.eps)
-    else:
-        layer.group.apply_adam(keys, offsets, grad_rows.contiguous(), lr=layer.lr, beta1=layer.betas[0], beta2=layer.betas[1],
-                               eps=layer.eps, step=layer.step)
+    _step_now(layer).apply_to(layer.group, keys, offsets, grad_rows.contiguous())
 
 
 @apply_grad_jagged.register_fake
@@ -469,21 +449,54 @@ def _backward_jagged(ctx, grad_out):
 lookup_jagged.register_autograd(_backward_jagged, setup_context=_setup_jagged)
 
 
-class _SparseOptimizerSettings:
-    def _init_settings(self, optimizer, lr, eps, betas, table=None, out_dtype: torch.dtype = torch.float32, pooled: bool = False):
-        if optimizer not in ("adagrad", "adam"):
-            raise ValueError("optimizer must be 'adagrad' or 'adam'")
-        self.out_dtype = _check_out_dtype(table, out_dtype, pooled)
-        self.optimizer, self.lr, self.betas = optimizer, lr, betas
-        self.eps = eps if eps is not None else (1e-10 if optimizer == "adagrad" else 1e-8)
-        self.step = 0
+def _check_min_count(layer: str, table, traits: _Traits, min_count, creates: bool = True, rows_layer: bool = False,
+                     out_dtype: torch.dtype = torch.float32):
+    """A layer's min_count (admission, SPEC.md §3 find_or_insert_admit): None, or a threshold over a table that admits.  The layer's own rules are
+    here; whether the table admits is the table's to say (admission_refusal).  Refused at construction, before any launch, saying which case it is."""
+    if min_count is None:
+        return None
+    if not creates:
+        raise ValueError(f"{layer}: min_count needs create_missing=True (admission decides when an unseen id is created; without creation there is nothing to decide)")
+    if type(min_count) is not int or not 0 <= min_count < 1 << 32:   # (a bool is no int here)
+        raise ValueError(f"{layer}: min_count must be an int in [0, 2^32) (got {min_count!r})")
+    over = f"{layer}: min_count over {type(table).__name__}: "
+    if rows_layer and traits.hot_cold_pair:
+        raise ValueError(over + "this layer has no admitting forward over a hot/cold pair; use a DynamicEmbeddingCollection over "
+                         "TieredTableGroup([pair]) (one segment), whose training forward admits")
+    reason = traits.admission_refusal() if traits.admission_refusal is not None else \
+        "admission exists on a LookupTable and on a TableGroup on one device, not on sharded or peer-mapped tables"
+    if reason:
+        raise ValueError(over + reason)
+    if rows_layer and out_dtype != torch.float32:
+        raise ValueError(f"{layer}: min_count has no bf16 form on one table (mee_find_or_insert_admit returns fp32 rows): use out_dtype=torch.float32")
+    return min_count
+
+
+class _SparseLayer(torch.nn.Module):
+    """What the three layers share: the registration under a table_id, the anchor that makes autograd run the backward, the table's traits, the
+    checked out_dtype and min_count, and the optimizer step's settings with its counter (_step_now)."""
+
+    def __init__(self, table, optimizer, lr, eps, betas, out_dtype, min_count, pooled: bool = False, creates: bool = True, rows_layer: bool = False):
+        super().__init__()
+        name = type(self).__name__
+        _refuse_narrow_rows(name, table)
+        self.table, self.traits = table, _traits(table)
+        self.min_count = _check_min_count(name, table, self.traits, min_count, creates, rows_layer, out_dtype)
+        first = SparseStep.of(optimizer, lr, eps, *betas, error=ValueError)   # checks the name, resolves the default eps
+        self.optimizer, self.lr, self.eps, self.betas, self.step = optimizer, lr, first.eps, betas, 0
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16 (got {out_dtype})")
+        if out_dtype != torch.float32 and not (self.traits.bf16_bags if pooled else self.traits.bf16_rows):
+            raise ValueError(f"{type(table).__name__} has no bf16 lookup (tiered, sharded and peer-mapped tables return fp32 rows): use out_dtype=torch.float32 and "
+                             "cast in the model")
+        self.out_dtype = out_dtype
         self.table_id = next(_IDS)
         _LAYERS[self.table_id] = self
         # autograd only runs backward for ops with an input that requires grad
         self._anchor = torch.nn.Parameter(torch.zeros(()), requires_grad=True)
 
 
-class DynamicEmbeddingCollection(torch.nn.Module, _SparseOptimizerSettings):
+class DynamicEmbeddingCollection(_SparseLayer):
     """All embedding tables of a model behind one module: keys = the tables' id batches concatenated, offsets = the
     n_tables + 1 segment bounds (int64, on the device) -> fp32 [len(keys), dim].  Forward is ONE grouped find_or_insert
     (find in eval mode), backward ONE grouped optimizer step, whatever the number of tables (TableGroup in table.py).
@@ -497,17 +510,14 @@ class DynamicEmbeddingCollection(torch.nn.Module, _SparseOptimizerSettings):
 
     def __init__(self, group, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
                  out_dtype: torch.dtype = torch.float32, min_count: int | None = None):
-        super().__init__()
-        _refuse_narrow_rows("DynamicEmbeddingCollection", group)
+        super().__init__(group, optimizer, lr, eps, betas, out_dtype, min_count)
         self.group = group
-        self.min_count = _check_min_count(group, min_count, "DynamicEmbeddingCollection")
-        self._init_settings(optimizer, lr, eps, betas, group, out_dtype)
 
     def forward(self, keys: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
         return lookup_jagged(keys, offsets, self._anchor, self.table_id, self.training)
 
 
-class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
+class DynamicEmbeddingBag(_SparseLayer):
     """torch.nn.EmbeddingBag over a lookup table — or over a TableGroup, which makes it an embedding-bag COLLECTION: bag b
     then belongs to member b // bags_per_table and the whole model's sparse forward is one launch, its backward seven.
     Over a MixedTableGroup (members of different dims) forward returns a list: member j's [bags_per_table, dim_j] tensor, views of one buffer.
@@ -521,18 +531,15 @@ class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
     def __init__(self, table, mode: str = "sum", optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
                  create_missing: bool = False, out_dtype: torch.dtype = torch.float32, min_count: int | None = None):
         """out_dtype=torch.bfloat16: the bag is accumulated in fp32 and the finished row rounded once by the lookup; backward widens the bf16 grad."""
-        super().__init__()
-        _refuse_narrow_rows("DynamicEmbeddingBag", table)
         if mode not in ("sum", "mean"):
             raise ValueError("mode must be 'sum' or 'mean'")
-        self.table, self.mode, self.create_missing = table, mode, create_missing
-        self.min_count = _check_min_count(table, min_count, "DynamicEmbeddingBag", creates=create_missing)
-        self._init_settings(optimizer, lr, eps, betas, table, out_dtype, pooled=True)
+        super().__init__(table, optimizer, lr, eps, betas, out_dtype, min_count, pooled=True, creates=create_missing)
+        self.mode, self.create_missing = mode, create_missing
 
     def forward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, per_sample_weights: torch.Tensor | None = None) -> torch.Tensor:
         """per_sample_weights (fp32 [n], mode "sum" only): the bag is the sum of w_i * row_i; backward also yields their grad.
         The weighted backward updates every position, so its bags must partition the keys: bag_offsets[0] = 0, bag_offsets[-1] = n."""
-        if getattr(self.table, "mixed_dims", False):   # a MixedTableGroup: one tensor per member, views of the one buffer the lookup wrote
+        if self.traits.mixed_dims:   # a MixedTableGroup: one tensor per member, views of the one buffer the lookup wrote
             if per_sample_weights is not None:
                 raise ValueError(f"{type(self.table).__name__} has no weighted bags: per_sample_weights are not offered over members of different dims")
             flat = lookup_pooled_mixed(keys, bag_offsets, self._anchor, self.table_id, self.mode == "mean")[0]
@@ -541,12 +548,12 @@ class DynamicEmbeddingBag(torch.nn.Module, _SparseOptimizerSettings):
             return lookup_pooled(keys, bag_offsets, self._anchor, self.table_id, self.mode == "mean")[0]
         if self.mode != "sum":
             raise ValueError("per_sample_weights are only supported for mode='sum', as in torch.nn.EmbeddingBag")
-        if not getattr(self.table, "weighted_bags", True):   # (a ShardedTableGroup: refused on every rank alike, before anything is exchanged; a TieredLookupTable)
+        if not self.traits.weighted_bags:   # (a ShardedTableGroup: refused on every rank alike, before anything is exchanged; a TieredLookupTable)
             raise ValueError(f"{type(self.table).__name__} has no weighted bags: per_sample_weights are not offered over a sharded group or a hot/cold pair")
         return lookup_pooled_weighted(keys, bag_offsets, per_sample_weights, self._anchor, self.table_id)[0]
 
 
-class DynamicEmbedding(torch.nn.Module):
+class DynamicEmbedding(_SparseLayer):
     """ids (any int64 tensor) -> fp32 [..., dim].  The table must have been created with the matching optimizer planes.
     out_dtype=torch.bfloat16 (a LookupTable in HBM only): the lookup writes bf16 rows — what `.to(torch.bfloat16)` on the fp32 rows would give —
     and backward widens the bf16 grad before the table's fp32 step.
@@ -556,25 +563,11 @@ class DynamicEmbedding(torch.nn.Module):
 
     def __init__(self, table, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
                  out_dtype: torch.dtype = torch.float32, min_count: int | None = None):
-        super().__init__()
-        _refuse_narrow_rows("DynamicEmbedding", table)
-        self.min_count = _check_min_count(table, min_count, "DynamicEmbedding")
-        if self.min_count is not None and out_dtype != torch.float32:
-            raise ValueError("DynamicEmbedding: min_count has no bf16 form on one table (mee_find_or_insert_admit returns fp32 rows): use out_dtype=torch.float32")
-        if optimizer not in ("adagrad", "adam"):
-            raise ValueError("optimizer must be 'adagrad' or 'adam'")
-        self.out_dtype = _check_out_dtype(table, out_dtype)
-        self.table, self.optimizer, self.lr, self.betas = table, optimizer, lr, betas
-        self.eps = eps if eps is not None else (1e-10 if optimizer == "adagrad" else 1e-8)
-        self.step = 0
+        super().__init__(table, optimizer, lr, eps, betas, out_dtype, min_count, rows_layer=True)
         self.fuse_backward_partition = True   # see forward()
-        self.table_id = next(_IDS)
-        _LAYERS[self.table_id] = self
-        # autograd only runs backward for ops with an input that requires grad
-        self._anchor = torch.nn.Parameter(torch.zeros(()), requires_grad=True)
 
     def forward(self, keys: torch.Tensor) -> torch.Tensor:
-        if self.min_count is None and hasattr(self.table, "find_or_insert_located"):   # one HBM table: the backward updates the rows at the slots this lookup found
+        if self.min_count is None and self.traits.located_table:   # one HBM table: the backward updates the rows at the slots this lookup found
             # training: the lookup's launch also partitions the batch for the backward's apply (nothing else may change the table in between:
             # the C-ABI refuses mutators while that partition is pending — table.apply_discard() drops it)
             return lookup_located(keys, self._anchor, self.table_id, self.training, self.training and torch.is_grad_enabled() and self.fuse_backward_partition)[0]

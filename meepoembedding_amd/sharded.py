@@ -35,7 +35,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import refuse_narrow_rows
-from .table import _out_dtype
+from .table import SparseStep, _out_dtype
 
 
 class _Exchange:
@@ -90,6 +90,9 @@ class _Exchange:
         out = torch.empty((sum(out_splits),) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
         dist.all_to_all_single(out, t.contiguous(), output_split_sizes=out_splits, input_split_sizes=in_splits, group=self.group)
         return out
+
+    def admission_refusal(self) -> str:
+        return "admission exists on one device — a LookupTable, a TableGroup, a hot/cold pair or a TieredTableGroup — not on sharded or peer-mapped tables"
 
     def _typed(self, out_dtype: torch.dtype) -> dict:
         """the local lookup's out_dtype keyword (none at fp32: a `local` without the keyword keeps working); refused before anything is exchanged"""
@@ -263,26 +266,24 @@ class ShardedLookupTable(_Exchange):
                       grad_index: torch.Tensor | None = None) -> None:
         """grad_index (the pooled backward): position i takes row grad_index[i] of grads, the bag's gradient row — non-decreasing over the batch.
         One row per (bag, owner) run travels; the owner reduces duplicates over all ranks' contributions in one indexed apply."""
-        if grad_index is not None:
-            rk, rg, run_of_key = self._apply_bags(keys, grads, grad_index, dedup)
-            self.local.apply_adagrad(rk, rg, lr, eps, grad_index=run_of_key)
-            return
-        if dedup:
-            keys, grads = self._aggregate(keys, grads)
-        rk, rg, *_ = self._push(keys, grads)
-        self.local.apply_adagrad(rk, rg, lr, eps)
+        self._apply(SparseStep("adagrad", lr, eps), keys, grads, dedup, grad_index, aggregate=dedup)
 
     def apply_adam(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999,
                    eps: float = 1e-8, step: int = 1, dedup: bool = False, grad_index: torch.Tensor | None = None) -> None:
         """dedup is accepted like apply_adagrad's, but Adam's pairs are never aggregated before the exchange: its update barely depends on the size of
         g, so the rounding of a rank's partial sum, where the ranks' sums cancel, would reach the row as a large relative error (SPEC.md §5).
         grad_index: as apply_adagrad's."""
+        self._apply(SparseStep("adam", lr, eps, beta1, beta2, step), keys, grads, dedup, grad_index, aggregate=False)
+
+    def _apply(self, step: SparseStep, keys, grads, dedup: bool, grad_index, aggregate: bool) -> None:
         if grad_index is not None:
             rk, rg, run_of_key = self._apply_bags(keys, grads, grad_index, dedup)
-            self.local.apply_adam(rk, rg, lr, beta1, beta2, eps, step, grad_index=run_of_key)
+            step.apply_to(self.local, rk, rg, grad_index=run_of_key)
             return
+        if aggregate:
+            keys, grads = self._aggregate(keys, grads)
         rk, rg, *_ = self._push(keys, grads)
-        self.local.apply_adam(rk, rg, lr, beta1, beta2, eps, step)
+        step.apply_to(self.local, rk, rg)
 
     def size(self) -> int:
         t = torch.tensor([self.local.size()], dtype=torch.int64, device="cpu" if self._stage else self._dev())
@@ -508,8 +509,7 @@ class ShardedTableGroup(_Exchange):
         [T B, dim] (pre-scaled by 1 / length for a mean).  One gradient row per run travels with the keys; the owner reduces duplicates per member
         over all ranks' contributions in one indexed apply.  bag_of_position [n] is the bag of every position as bag_offsets defines it;
         `located` is accepted and ignored (handles do not cross the two exchanges)."""
-        if optimizer not in ("adagrad", "adam"):
-            raise ValueError(f"optimizer must be 'adagrad' or 'adam' (got {optimizer!r})")
+        step = SparseStep.of(optimizer, lr, eps, beta1, beta2, step, error=ValueError)
         keys, bpt = self._check_bags(("apply_indexed",), keys, bag_offsets)
         if bag_of_position.numel() != keys.numel():
             raise ValueError("bag_of_position must hold one entry per key")
@@ -523,17 +523,14 @@ class ShardedTableGroup(_Exchange):
         recv_rows = self._a2a(run_rows, rss, rrs)
         keys_tm, _, offsets_tm, order_r, _, run_len_tm = self._regroup_runs(recv_keys, recv_len, key_cells, run_cells)
         _, run_of_key = self.router.run_offsets(run_len_tm, keys_tm.numel())
-        self.local_group.apply_indexed(keys_tm, offsets_tm, self.router.gather_rows(recv_rows, order_r), run_of_key, optimizer, lr, eps=eps,
-                                       beta1=beta1, beta2=beta2, step=step)
+        self.local_group.apply_indexed(keys_tm, offsets_tm, self.router.gather_rows(recv_rows, order_r), run_of_key, *step)
 
     def apply_adagrad(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10) -> None:
-        k, off, g = self._push("apply_adagrad", keys, offsets, grads)
-        self.local_group.apply_adagrad(k, off, g, lr, eps)
+        SparseStep("adagrad", lr, eps).apply_to(self.local_group, *self._push("apply_adagrad", keys, offsets, grads))
 
     def apply_adam(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999,
                    eps: float = 1e-8, step: int = 1) -> None:
-        k, off, g = self._push("apply_adam", keys, offsets, grads)
-        self.local_group.apply_adam(k, off, g, lr, beta1, beta2, eps, step)
+        SparseStep("adam", lr, eps, beta1, beta2, step).apply_to(self.local_group, *self._push("apply_adam", keys, offsets, grads))
 
 
 class ShardedTieredTableGroup(ShardedTableGroup):
@@ -695,15 +692,16 @@ class RcclShardedTable:
         return found
 
     def apply_adagrad(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10) -> None:
-        k = self._k(keys)
-        g = self._r(grads, k.numel())
-        self._check(self._lib.lib().mee_sharded_apply_adagrad(self._h, k.data_ptr(), g.data_ptr(), k.numel(), lr, eps, self._s()))
+        self._apply(SparseStep("adagrad", lr, eps), keys, grads)
 
     def apply_adam(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999,
                    eps: float = 1e-8, step: int = 1) -> None:
+        self._apply(SparseStep("adam", lr, eps, beta1, beta2, step), keys, grads)
+
+    def _apply(self, step: SparseStep, keys, grads) -> None:
         k = self._k(keys)
         g = self._r(grads, k.numel())
-        self._check(self._lib.lib().mee_sharded_apply_adam(self._h, k.data_ptr(), g.data_ptr(), k.numel(), lr, beta1, beta2, eps, step, self._s()))
+        step.launch("mee_sharded_apply", "", self._h, k.data_ptr(), g.data_ptr(), k.numel(), stream=self._s())
 
     def size(self) -> int:
         n = self._C.c_size_t()

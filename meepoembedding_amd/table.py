@@ -10,6 +10,7 @@ tensors on the table's device and enqueues on torch's current stream; nothing he
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import torch
 
@@ -56,6 +57,42 @@ def _fp32_only(out: torch.Tensor | None, op: str) -> None:
     if out is not None and out.dtype != torch.float32:
         raise ValueError(f"{op} returns fp32 rows only (out has dtype {out.dtype}); bf16 output exists for find, find_located, find_or_insert, "
                          "find_or_insert_located, find_pooled and the TableGroup lookups")
+
+
+class SparseStep(NamedTuple):
+    """One sparse optimizer step as a value: which optimizer and its scalars.  The table classes build it once per call and forward it; nothing
+    else in the package tells the optimizers apart.  The fields stand in the order of apply_pooled / apply_indexed's loose form, so `*step` is it."""
+    kind: str            # "adagrad" | "adam"
+    lr: float
+    eps: float
+    beta1: float = 0.9   # (Adam only, like beta2 and step)
+    beta2: float = 0.999
+    step: int = 1
+
+    @classmethod
+    def of(cls, optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1, error=None) -> "SparseStep":
+        """from the loose form apply_pooled / apply_indexed and the nn layers take: the one place that checks the optimizer's name and resolves
+        the default eps (1e-10 for Adagrad, 1e-8 for Adam).  error: the caller's exception class for an unknown name (ValueError in the host-logic
+        classes); without it MeepoError(ERR_INVALID_ARG), as the library's wrappers raise."""
+        if optimizer not in ("adagrad", "adam"):
+            msg = f"optimizer must be 'adagrad' or 'adam' (got {optimizer!r})"
+            raise error(msg) if error is not None else MeepoError(_lib.ERR_INVALID_ARG, msg)
+        if eps is None:
+            eps = 1e-10 if optimizer == "adagrad" else 1e-8
+        return cls(optimizer, lr, eps, beta1, beta2, step)
+
+    def tail(self) -> tuple:
+        """the step's own arguments in the order of the C-ABI — and of apply_adagrad / apply_adam's positional parameters"""
+        return (self.lr, self.eps) if self.kind == "adagrad" else (self.lr, self.beta1, self.beta2, self.eps, self.step)
+
+    def launch(self, stem: str, form: str, *args, stream: int) -> None:
+        """the C entry point {stem}_{kind}{form} — mee_apply_adam_located, mee_group_apply_adagrad_pooled, … — on (args…, tail…, stream)"""
+        check(getattr(_lib.lib(), f"{stem}_{self.kind}{form}")(*args, *self.tail(), stream))
+
+    def apply_to(self, table, *args, **kw) -> None:
+        """table.apply_adagrad / table.apply_adam(args…, tail…, **kw): any object with the two methods (a CPU test adapter, a peer-mapped table, a
+        foreign `local`) takes the step by their positional order"""
+        getattr(table, "apply_" + self.kind)(*args, *self.tail(), **kw)
 
 
 class LookupTable:
@@ -146,7 +183,7 @@ class LookupTable:
     def _keys(self, keys: torch.Tensor) -> torch.Tensor:
         if keys.dtype != torch.int64 or keys.device != self.device:
             raise MeepoError(_lib.ERR_INVALID_ARG, f"keys must be int64 on {self.device}")
-        return keys.contiguous().view(-1)
+        return keys if keys.dim() == 1 and keys.is_contiguous() else keys.contiguous().view(-1)   # (no view object per call for a batch that is flat already)
 
     def _rows(self, rows: torch.Tensor, n: int) -> torch.Tensor:
         if rows.dtype != torch.float32 or rows.device != self.device or rows.numel() != n * self.dim:
@@ -419,6 +456,10 @@ class LookupTable:
             check(getattr(_lib.lib(), fn)(self._h, k.data_ptr(), n, out.data_ptr(), found.data_ptr(), slots.data_ptr(), self._s()))
         return out, found, slots
 
+    def admission_refusal(self) -> str | None:
+        """why an admitting call (min_count) is refused on this table, or None: what the nn layers ask before they take a min_count"""
+        return None if self._opts["admission"] else "the table was not created with admission=True (it has no sketch)"
+
     def admission_decay(self, shift: int = 1) -> None:
         """Every counter of the admission sketch >>= shift (>= 32: reset): starts a new observation window."""
         check(_lib.lib().mee_admission_decay(self._h, int(shift), self._s()))
@@ -639,35 +680,26 @@ class LookupTable:
                       grad_index: torch.Tensor | None = None, slots: torch.Tensor | None = None) -> None:
         """grad_index (optional, one int per key): position i takes row grad_index[i] of grads (pooled lookups: the bag).
         slots (optional): the handles find_located returned for `keys` in this step's forward (skips the probe)."""
-        k = self._keys(keys)
-        if slots is not None:
-            g = self._rows(grads, k.numel())
-            check(_lib.lib().mee_apply_adagrad_located(self._h, k.data_ptr(), self._slots(slots, k.numel()).data_ptr(), g.data_ptr(), k.numel(), lr, eps, self._s()))
-            return
-        if grad_index is not None:
-            gi = self._grad_index(grad_index, k.numel())
-            g = grads.contiguous().view(-1, self.dim)
-            check(_lib.lib().mee_apply_adagrad_indexed(self._h, k.data_ptr(), g.data_ptr(), g.shape[0], gi.data_ptr(), k.numel(), lr, eps, self._s()))
-            return
-        g = self._rows(grads, k.numel())
-        check(_lib.lib().mee_apply_adagrad(self._h, k.data_ptr(), g.data_ptr(), k.numel(), lr, eps, self._s()))
+        self._apply(SparseStep("adagrad", lr, eps), keys, grads, grad_index, slots)
 
     def apply_adam(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999,
                    eps: float = 1e-8, step: int = 1, grad_index: torch.Tensor | None = None, slots: torch.Tensor | None = None) -> None:
+        self._apply(SparseStep("adam", lr, eps, beta1, beta2, step), keys, grads, grad_index, slots)
+
+    def _apply(self, step: SparseStep, keys, grads, grad_index, slots) -> None:
+        """the three forms of the step: on the forward's slot handles, on indexed gradient rows, or plain"""
         k = self._keys(keys)
+        n = k.numel()
         if slots is not None:
-            g = self._rows(grads, k.numel())
-            check(_lib.lib().mee_apply_adam_located(self._h, k.data_ptr(), self._slots(slots, k.numel()).data_ptr(), g.data_ptr(), k.numel(), lr, beta1,
-                                                    beta2, eps, step, self._s()))
-            return
-        if grad_index is not None:
-            gi = self._grad_index(grad_index, k.numel())
+            g = self._rows(grads, n)
+            step.launch("mee_apply", "_located", self._h, k.data_ptr(), self._slots(slots, n).data_ptr(), g.data_ptr(), n, stream=self._s())
+        elif grad_index is not None:
+            gi = self._grad_index(grad_index, n)
             g = grads.contiguous().view(-1, self.dim)
-            check(_lib.lib().mee_apply_adam_indexed(self._h, k.data_ptr(), g.data_ptr(), g.shape[0], gi.data_ptr(), k.numel(), lr, beta1, beta2,
-                                                    eps, step, self._s()))
-            return
-        g = self._rows(grads, k.numel())
-        check(_lib.lib().mee_apply_adam(self._h, k.data_ptr(), g.data_ptr(), k.numel(), lr, beta1, beta2, eps, step, self._s()))
+            step.launch("mee_apply", "_indexed", self._h, k.data_ptr(), g.data_ptr(), g.shape[0], gi.data_ptr(), n, stream=self._s())
+        else:
+            g = self._rows(grads, n)
+            step.launch("mee_apply", "", self._h, k.data_ptr(), g.data_ptr(), n, stream=self._s())
 
     def apply_prepare(self, keys: torch.Tensor) -> None:
         """Group + plan the next apply of `keys` ahead of time (needs no grads; may run on a side stream).  The next
@@ -805,19 +837,31 @@ class TableGroup:
 
     def apply_adagrad(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10) -> None:
         """One sparse-Adagrad step over the jagged batch == apply_adagrad per table (max_apply_batch >= keys.numel())."""
-        self._check_offsets(offsets)
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
-        g = self.tables[0]._rows(grads, k.numel())
-        check(_lib.lib().mee_group_apply_adagrad(self._h, k.data_ptr(), offsets.data_ptr(), g.data_ptr(), k.numel(), lr, eps,
-                                                 _stream_ptr(self.device)))
+        self._apply(SparseStep("adagrad", lr, eps), keys, offsets, grads)
 
     def apply_adam(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, beta1: float = 0.9,
                    beta2: float = 0.999, eps: float = 1e-8, step: int = 1) -> None:
-        self._check_offsets(offsets)
+        self._apply(SparseStep("adam", lr, eps, beta1, beta2, step), keys, offsets, grads)
+
+    def _apply(self, step: SparseStep, keys, offsets, grads, index=None, pooled: bool = False, located=None) -> None:
+        """the three forms of the grouped step: a gradient row per position over member segments (`offsets` = the n_tables + 1 bounds), indexed rows
+        over member segments, or a pooled lookup's backward (`offsets` = its bag_offsets, index = the bag of every position)"""
+        bpt = self._check_bags(offsets) if pooled else self._check_offsets(offsets)
         k = self.tables[0]._keys(keys) if keys.numel() else keys
-        g = self.tables[0]._rows(grads, k.numel())
-        check(_lib.lib().mee_group_apply_adam(self._h, k.data_ptr(), offsets.data_ptr(), g.data_ptr(), k.numel(), lr, beta1, beta2,
-                                              eps, step, _stream_ptr(self.device)))
+        n, s = k.numel(), _stream_ptr(self.device)
+        if index is None:
+            g = self.tables[0]._rows(grads, n)
+            step.launch("mee_group_apply", "", self._h, k.data_ptr(), offsets.data_ptr(), g.data_ptr(), n, stream=s)
+            return
+        gi = self.tables[0]._grad_index(index, n)
+        g = grads.contiguous()
+        if pooled:
+            step.launch("mee_group_apply", "_pooled", self._h, k.data_ptr(), offsets.data_ptr(), bpt, g.data_ptr(), gi.data_ptr(),
+                        located.data_ptr() if located is not None else None, n, stream=s)
+            return
+        if g.dtype != torch.float32 or g.dim() != 2 or g.shape[1] != self.dim or g.device != self.device:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"grads must be float32 [rows, {self.dim}] on {self.device}")
+        step.launch("mee_group_apply", "_indexed", self._h, k.data_ptr(), offsets.data_ptr(), g.data_ptr(), g.shape[0], gi.data_ptr(), n, stream=s)
 
     # -- the embedding-bag collection: bags_per_table bags per member, bag b belongs to member b // bags_per_table ---------
     def _check_bags(self, bag_offsets: torch.Tensor) -> int:
@@ -862,18 +906,7 @@ class TableGroup:
                      located: torch.Tensor | None = None) -> None:
         """Backward of find_pooled over the group: one optimizer step, position i takes row bag_of_position[i] of bag_grads.
         located = the buffer the forward find_pooled of this step filled: skips the probe pass."""
-        bpt = self._check_bags(bag_offsets)
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
-        gi = self.tables[0]._grad_index(bag_of_position, k.numel())
-        g = bag_grads.contiguous()
-        L, s = _lib.lib(), _stream_ptr(self.device)
-        loc = located.data_ptr() if located is not None else None
-        if optimizer == "adagrad":
-            check(L.mee_group_apply_adagrad_pooled(self._h, k.data_ptr(), bag_offsets.data_ptr(), bpt, g.data_ptr(), gi.data_ptr(), loc, k.numel(),
-                                                   lr, 1e-10 if eps is None else eps, s))
-        else:
-            check(L.mee_group_apply_adam_pooled(self._h, k.data_ptr(), bag_offsets.data_ptr(), bpt, g.data_ptr(), gi.data_ptr(), loc, k.numel(),
-                                                lr, beta1, beta2, 1e-8 if eps is None else eps, step, s))
+        self._apply(SparseStep.of(optimizer, lr, eps, beta1, beta2, step), keys, bag_offsets, bag_grads, bag_of_position, pooled=True, located=located)
 
     # -- the same collection with a different number of bags per member (the owner's side of ShardedTableGroup's bags) --------
     def find_pooled_jagged(self, keys: torch.Tensor, bag_offsets: torch.Tensor, member_bags: torch.Tensor, mode: str = "sum",
@@ -910,21 +943,7 @@ class TableGroup:
                       eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1) -> None:
         """One optimizer step over the jagged batch == LookupTable.apply_*(grad_index=...) per member with its segment: position i takes row
         grad_index[i] of grads [rows, dim]."""
-        self._check_offsets(offsets)
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
-        gi = self.tables[0]._grad_index(grad_index, k.numel())
-        g = grads.contiguous()
-        if g.dtype != torch.float32 or g.dim() != 2 or g.shape[1] != self.dim or g.device != self.device:
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"grads must be float32 [rows, {self.dim}] on {self.device}")
-        L, s = _lib.lib(), _stream_ptr(self.device)
-        if optimizer == "adagrad":
-            check(L.mee_group_apply_adagrad_indexed(self._h, k.data_ptr(), offsets.data_ptr(), g.data_ptr(), g.shape[0], gi.data_ptr(), k.numel(),
-                                                    lr, 1e-10 if eps is None else eps, s))
-        elif optimizer == "adam":
-            check(L.mee_group_apply_adam_indexed(self._h, k.data_ptr(), offsets.data_ptr(), g.data_ptr(), g.shape[0], gi.data_ptr(), k.numel(),
-                                                 lr, beta1, beta2, 1e-8 if eps is None else eps, step, s))
-        else:
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"optimizer must be 'adagrad' or 'adam' (got {optimizer!r})")
+        self._apply(SparseStep.of(optimizer, lr, eps, beta1, beta2, step), keys, offsets, grads, grad_index)
 
     def pooled_weighted_backward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, weights: torch.Tensor, bag_grads: torch.Tensor,
                                  located: torch.Tensor | None = None, want_weight_grads: bool = True, grads: torch.Tensor | None = None,
@@ -982,6 +1001,10 @@ class TableGroup:
             import numpy as np
             self._min_count_cache[key] = torch.from_numpy(np.array(key, dtype=np.uint32).view(np.int32)).to(self.device)   # uint32 bits behind an int32 tensor
         return 0, self._min_count_cache[key]
+
+    def admission_refusal(self) -> str | None:
+        """LookupTable.admission_refusal of the first member that has one, named"""
+        return next((f"member {j} of the group: {r}" for j, r in enumerate(t.admission_refusal() for t in self.tables) if r), None)
 
     def admission_decay(self, shift: int = 1) -> None:
         """LookupTable.admission_decay of every member in one launch (mee_group_admission_decay): every sketch counter >>= shift (>= 32: reset)."""
@@ -1063,6 +1086,9 @@ class MixedTableGroup:
         """Performance knobs of every class's apply (mee_set_tuning); never change results."""
         check(_lib.lib().mee_mixed_group_set_tuning(self._h, name.encode(), int(value)))
 
+    def admission_refusal(self) -> str:
+        return "a mixed-width group creates unseen ids inside its pooled launch, which has no admission"
+
     def layout(self, bags_per_table: int):
         """-> (element offset of every member's [bags_per_table, dim_j] block, total elements), from the library (== mixed_layout(dims, B)[1:])."""
         offs = (C.c_uint64 * len(self.tables))()
@@ -1120,22 +1146,15 @@ class MixedTableGroup:
                      located: torch.Tensor | None = None) -> None:
         """Backward of find_pooled: one optimizer step, position i takes the row of bag bag_of_position[i] (its index in the caller's order)
         of bag_grads — a flat fp32 buffer in the lookup's class-major layout.  located = the buffer the forward of this step filled."""
-        if optimizer not in ("adagrad", "adam"):
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"optimizer must be 'adagrad' or 'adam' (got {optimizer!r})")
+        step = SparseStep.of(optimizer, lr, eps, beta1, beta2, step)
         bpt = self._check_bags(bag_offsets)
         k = self.tables[0]._keys(keys) if keys.numel() else keys
         gi = self.tables[0]._grad_index(bag_of_position, k.numel())
         g = self._buffer(bag_grads.contiguous(), "bag_grads", torch.float32, mixed_layout(self.dims, bpt)[2])
         if located is not None:
             located = self._buffer(located, "located", torch.int64, k.numel())
-        L, s = _lib.lib(), _stream_ptr(self.device)
-        loc = located.data_ptr() if located is not None else None
-        if optimizer == "adagrad":
-            check(L.mee_mixed_group_apply_adagrad_pooled(self._h, k.data_ptr(), bag_offsets.data_ptr(), bpt, g.data_ptr(), gi.data_ptr(), loc, k.numel(),
-                                                         lr, 1e-10 if eps is None else eps, s))
-        else:
-            check(L.mee_mixed_group_apply_adam_pooled(self._h, k.data_ptr(), bag_offsets.data_ptr(), bpt, g.data_ptr(), gi.data_ptr(), loc, k.numel(),
-                                                      lr, beta1, beta2, 1e-8 if eps is None else eps, step, s))
+        step.launch("mee_mixed_group_apply", "_pooled", self._h, k.data_ptr(), bag_offsets.data_ptr(), bpt, g.data_ptr(), gi.data_ptr(),
+                    located.data_ptr() if located is not None else None, k.numel(), stream=_stream_ptr(self.device))
 
 
 def hash_batch(keys: torch.Tensor, n_buckets: int, n_shards: int):

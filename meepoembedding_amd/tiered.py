@@ -32,6 +32,8 @@ from __future__ import annotations
 
 import torch
 
+from .table import SparseStep
+
 
 def _pool_rows(rows: torch.Tensor, bag_offsets: torch.Tensor, mode: str) -> torch.Tensor:
     """SPEC.md §3 find_pooled given find's rows [n, dim]: per bag fp32 additions in position order (the first row copied, each later one
@@ -55,6 +57,7 @@ def _pool_rows(rows: torch.Tensor, bag_offsets: torch.Tensor, mode: str) -> torc
 
 class TieredLookupTable:
     weighted_bags = False   # no per_sample_weights over the pair (nn.DynamicEmbeddingBag refuses them)
+    hot_cold_pair = True    # nn.DynamicEmbedding has no admitting forward over a pair
 
     def __init__(self, hot, cold, hot_key_limit: int | None = None, sample_every: int = 8, promote_threshold: int = 2,
                  rebalance_every: int = 0, rebalance_max_moves: int = 1 << 20):
@@ -210,16 +213,22 @@ class TieredLookupTable:
         """the pair admits iff its HOT table was created with admission=True: the pair's sketch is the hot table's (SPEC.md §3 "Tiering")"""
         return bool(getattr(self.hot, "_opts", {}).get("admission", False))
 
+    def admission_refusal(self) -> str | None:
+        """why an admitting call (min_count) is refused on this pair, or None: its own operators and the nn layers ask here"""
+        if not self._native():
+            return ("admission needs a hot/cold pair of native LookupTables (it counts in the hot table's sketch on the device); "
+                    f"this pair holds {type(self.hot).__name__} / {type(self.cold).__name__}")
+        if not self.admission:
+            return "a hot/cold pair counts in its hot table's sketch, so the hot table needs admission=True (this pair's hot table has no sketch)"
+        return None
+
     def _check_min_count(self, min_count) -> int:
         """the threshold of an admitting call on this pair, or the reason there is none"""
-        if not self._native():
-            raise ValueError("min_count needs a pair of native LookupTables (admission counts in the hot table's sketch on the device); "
-                             f"this pair holds {type(self.hot).__name__} / {type(self.cold).__name__}")
+        reason = self.admission_refusal()
+        if reason:
+            raise ValueError("min_count: " + reason)
         if isinstance(min_count, bool) or not isinstance(min_count, int) or not 0 <= min_count < 1 << 32:
             raise ValueError(f"min_count must be an int in [0, 2^32) (got {min_count!r})")
-        if not self.admission:
-            raise ValueError("min_count needs the pair's hot table created with admission=True (the pair counts in the hot table's sketch; "
-                             "the hot table has no sketch)")
         return min_count
 
     def _create_missing(self, keys: torch.Tensor, out: torch.Tensor, found: torch.Tensor, min_count) -> None:
@@ -264,18 +273,18 @@ class TieredLookupTable:
             self.rebalance_log.append((self._train_steps, int(p), int(d)))
 
     def apply_adagrad(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10, grad_index: torch.Tensor | None = None) -> None:
-        # a key lives in one tier and each table ignores keys it does not hold: both see the whole batch.  grad_index (one int per key: position i
-        # takes row grad_index[i] of grads — a pooled lookup's bag) goes to both as well; a key's duplicates are reduced in the one tier that holds it
-        kw = {} if grad_index is None else {"grad_index": grad_index}
-        self.hot.apply_adagrad(keys, grads, lr, eps, **kw)
-        self.cold.apply_adagrad(keys, grads, lr, eps, **kw)
-        self._after_optimizer_step()
+        self._apply(SparseStep("adagrad", lr, eps), keys, grads, grad_index)
 
     def apply_adam(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999,
                    eps: float = 1e-8, step: int = 1, grad_index: torch.Tensor | None = None) -> None:
+        self._apply(SparseStep("adam", lr, eps, beta1, beta2, step), keys, grads, grad_index)
+
+    def _apply(self, step: SparseStep, keys, grads, grad_index) -> None:
+        # a key lives in one tier and each table ignores keys it does not hold: both see the whole batch.  grad_index (one int per key: position i
+        # takes row grad_index[i] of grads — a pooled lookup's bag) goes to both as well; a key's duplicates are reduced in the one tier that holds it
         kw = {} if grad_index is None else {"grad_index": grad_index}
-        self.hot.apply_adam(keys, grads, lr, beta1, beta2, eps, step, **kw)
-        self.cold.apply_adam(keys, grads, lr, beta1, beta2, eps, step, **kw)
+        step.apply_to(self.hot, keys, grads, **kw)
+        step.apply_to(self.cold, keys, grads, **kw)
         self._after_optimizer_step()
 
     # duplicate reductions touch no table row, only a table's per-batch scratch: the hot table lends its own
@@ -610,14 +619,16 @@ class TieredTableGroup:
         cut = bag_offsets.to(torch.int64).clamp(0, n).tolist()
         return bpt, [(j * bpt, cut[j * bpt], max(cut[j * bpt], cut[(j + 1) * bpt])) for j in range(len(self.tables))]
 
+    def admission_refusal(self) -> str | None:
+        """TieredLookupTable.admission_refusal of the first member that has one, named"""
+        return next((f"member {j}: {r}" for j, r in enumerate(p.admission_refusal() for p in self.tables) if r), None)
+
     def _admission(self, min_count):
         """-> (scalar threshold, device list | None) of an admitting call over the group, TableGroup._min_counts's rules and caching; or the reason
-        there is no such call: pairs that are not native tables, a member whose hot table has no sketch (named)"""
-        if not self._native:
-            raise ValueError("min_count needs pairs of native LookupTables (every pair counts in its hot table's sketch on the device)")
-        for j, p in enumerate(self.tables):
-            if not p.admission:
-                raise ValueError(f"min_count needs every pair's hot table created with admission=True (the hot table of member {j} has no sketch)")
+        there is no such call"""
+        reason = self.admission_refusal()
+        if reason:
+            raise ValueError("min_count: " + reason)
         return self.hot_group._min_counts(min_count)
 
     def admission_decay(self, shift: int = 1) -> None:
@@ -792,27 +803,11 @@ class TieredTableGroup:
     def apply_adagrad(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, eps: float = 1e-10) -> None:
         """The pair's sparse-Adagrad step per member over the jagged batch, as TWO grouped steps — the hot group's, then the cold group's: a key lives in
         one tier and a group ignores the keys its member does not hold — then every pair's rebalance_every bookkeeping."""
-        if not self._native:
-            flat = keys.contiguous().view(-1)
-            for pair, (s, e) in zip(self.tables, self._segments(offsets, flat.numel())):
-                pair.apply_adagrad(flat[s:e], grads[s:e], lr, eps)
-            return
-        for g in (self.hot_group, self.cold_group):
-            g.apply_adagrad(keys, offsets, grads, lr, eps)
-        for p in self.tables:
-            p._after_optimizer_step()
+        self._apply(SparseStep("adagrad", lr, eps), keys, offsets, grads)
 
     def apply_adam(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, beta1: float = 0.9, beta2: float = 0.999,
                    eps: float = 1e-8, step: int = 1) -> None:
-        if not self._native:
-            flat = keys.contiguous().view(-1)
-            for pair, (s, e) in zip(self.tables, self._segments(offsets, flat.numel())):
-                pair.apply_adam(flat[s:e], grads[s:e], lr, beta1, beta2, eps, step)
-            return
-        for g in (self.hot_group, self.cold_group):
-            g.apply_adam(keys, offsets, grads, lr, beta1, beta2, eps, step)
-        for p in self.tables:
-            p._after_optimizer_step()
+        self._apply(SparseStep("adam", lr, eps, beta1, beta2, step), keys, offsets, grads)
 
     def apply_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, bag_grads: torch.Tensor, bag_of_position: torch.Tensor,
                      optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1,
@@ -820,19 +815,26 @@ class TieredTableGroup:
         """Backward of find_pooled: the pair's step per member — position i takes row bag_of_position[i] of bag_grads — as TWO grouped steps, the hot
         group's and the cold group's (a key lives in one tier, and a group ignores the keys its member does not hold), then every pair's
         rebalance_every bookkeeping.  `located` is accepted for the bag layer's sake and not used: the tiered lookup hands out no located rows."""
-        if optimizer not in ("adagrad", "adam"):
-            raise ValueError("optimizer must be 'adagrad' or 'adam'")
+        self._apply(SparseStep.of(optimizer, lr, eps, beta1, beta2, step, error=ValueError), keys, bag_offsets, bag_grads, bag_of_position, pooled=True)
+
+    def _apply(self, step: SparseStep, keys, offsets, grads, index=None, pooled: bool = False) -> None:
+        """the step's three forms (TableGroup._apply's) on both tiers; pairs that are not native tables take the pair's step on their slices"""
         if not self._native:
             flat = keys.contiguous().view(-1)
-            _, members = self._member_slices(bag_offsets, flat.numel())
-            for pair, (_, s, e) in zip(self.tables, members):
-                if optimizer == "adagrad":
-                    pair.apply_adagrad(flat[s:e], bag_grads, lr, 1e-10 if eps is None else eps, grad_index=bag_of_position[s:e])
+            slices = [m[1:] for m in self._member_slices(offsets, flat.numel())[1]] if pooled else self._segments(offsets, flat.numel())
+            for pair, (s, e) in zip(self.tables, slices):
+                if index is None:
+                    step.apply_to(pair, flat[s:e], grads[s:e])
                 else:
-                    pair.apply_adam(flat[s:e], bag_grads, lr, beta1, beta2, 1e-8 if eps is None else eps, step, grad_index=bag_of_position[s:e])
+                    step.apply_to(pair, flat[s:e], grads, grad_index=index[s:e])
             return
         for g in (self.hot_group, self.cold_group):
-            g.apply_pooled(keys, bag_offsets, bag_grads, bag_of_position, optimizer, lr, eps=eps, beta1=beta1, beta2=beta2, step=step)
+            if index is None:
+                step.apply_to(g, keys, offsets, grads)
+            elif pooled:
+                g.apply_pooled(keys, offsets, grads, index, *step)
+            else:
+                g.apply_indexed(keys, offsets, grads, index, *step)
         for p in self.tables:
             p._after_optimizer_step()
 
@@ -904,17 +906,4 @@ class TieredTableGroup:
         """One optimizer step over the jagged batch == the pair's apply_*(grad_index=...) per member with its segment: position i takes row
         grad_index[i] of grads [rows, dim].  TWO grouped indexed steps, the hot group's and the cold group's (a key lives in one tier, and a group
         ignores the keys its member does not hold — apply_pooled's argument), then every pair's rebalance_every bookkeeping."""
-        if optimizer not in ("adagrad", "adam"):
-            raise ValueError(f"optimizer must be 'adagrad' or 'adam' (got {optimizer!r})")
-        if not self._native:
-            flat = keys.contiguous().view(-1)
-            for pair, (s, e) in zip(self.tables, self._segments(offsets, flat.numel())):
-                if optimizer == "adagrad":
-                    pair.apply_adagrad(flat[s:e], grads, lr, 1e-10 if eps is None else eps, grad_index=grad_index[s:e])
-                else:
-                    pair.apply_adam(flat[s:e], grads, lr, beta1, beta2, 1e-8 if eps is None else eps, step, grad_index=grad_index[s:e])
-            return
-        for g in (self.hot_group, self.cold_group):
-            g.apply_indexed(keys, offsets, grads, grad_index, optimizer, lr, eps=eps, beta1=beta1, beta2=beta2, step=step)
-        for p in self.tables:
-            p._after_optimizer_step()
+        self._apply(SparseStep.of(optimizer, lr, eps, beta1, beta2, step, error=ValueError), keys, offsets, grads, grad_index)
