@@ -610,6 +610,46 @@ int mee_group_find_or_insert_as(mee_group* g, const int64_t* d_keys, const uint6
 int mee_group_find_pooled_as(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
                              const float* d_weights, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream);
 
+/* ---- padded sequence lookup (SPEC.md §3 "find_padded") ------------------------------------------------------------------------
+ * What a sequence model reads: d_out[b, j, :] for b < n_bags, j < max_len — one slot per history position, zeros behind the end of a short
+ * history, a long history cut to max_len — written by ONE launch, with no [n, dim] array in between.  Bags are mee_find_pooled's, clamped the
+ * same way: end = min(d_bag_offsets[b+1], n), begin = min(d_bag_offsets[b], end), len = end - begin (a decreasing pair is an empty bag).
+ * kept = min(len, max_len); flags = MEE_PAD_KEEP_FIRST keeps positions begin .. begin+kept-1, MEE_PAD_KEEP_LAST end-kept .. end-1; the j-th
+ * kept position (batch order) fills slot j.
+ *   d_out            [n_bags, max_len, dim] of out_dtype (MEE_DTYPE_F32 | MEE_DTYPE_BF16, a bf16 buffer 8-byte aligned).  A kept slot holds, bit
+ *                    for bit, the row mee_find / mee_find_as returns for that key (the stored row, or the default row for an absent or reserved
+ *                    key); every other slot is +0.0 in every element (bf16: 0x0000).  EVERY element is written: the caller never clears it.
+ *   d_found          [n] nullable.  A kept position: as mee_find.  A position inside a bag that is not kept (truncated): not probed, 0.
+ *   d_lengths_out    [n_bags] nullable: kept, per bag — the mask of the block.
+ *   d_step_keys_out  [n] int64 and
+ *   d_grad_index_out [n] uint32, both nullable: what the backward needs.  A kept position i in slot j of bag b: step key = d_keys[i], grad index =
+ *                    b * max_len + j; a truncated one: EMPTY (padding, skipped by every operator) and 0.  The table step of the lookup is then
+ *                    mee_apply_*_indexed(d_step_keys_out, the dense grad as [n_bags * max_len, dim], d_grad_index_out).  With d_grad_index_out
+ *                    and n_bags * max_len >= 2^31 the call is MEE_ERR_INVALID_ARG (the indexed apply reads indices below 2^31).
+ * A position that lies in no bag (before d_bag_offsets[0], at or after d_bag_offsets[n_bags]) is written in no per-position output.  Bags that
+ * overlap (offsets that go down and up again) are served one by one; a position two bags share gets the per-position values of either.
+ * Nothing is read past d_keys[n-1].  The table, its hit counters, its admission sketch and its status word are not touched.  mee_find_padded_as
+ * never synchronises or allocates, can be captured, and may run on several streams at once.  mee_group_find_padded_as is the same EXCEPT in the
+ * first call after mee_reserve on a member (below): that call synchronises the stream once and must not be captured — a group form is capturable
+ * only while no member has been reserved since the group's last call.
+ * Row storage: fp32 rows (HBM or pinned host memory) and bf16 rows (MEE_FLAG_BF16_ROWS: fp32 out widens exactly, bf16 out returns the stored
+ * bits); an int8-row table is MEE_ERR_UNSUPPORTED.
+ * mee_group_find_padded_as: n_bags = n_tables * bags_per_table, bag b belongs to member b / bags_per_table (bags_per_table need not be a multiple
+ * of 4) and is, by definition, that member's mee_find_padded_as bag: its rows, its default row.  A uniform fp32 group or a bf16-row group; one
+ * launch whatever the number of tables.  After mee_reserve on a member the next call re-reads that table's planes (one stream synchronisation).
+ * MEE_ERR_INVALID_ARG, before anything is launched or written: a null table or group, null d_bag_offsets or d_out with bags to serve, null d_keys
+ * with n > 0, max_len == 0, an unknown flag bit, an unknown out_dtype (MEE_DTYPE_INT8 included), a misaligned bf16 d_out, n_bags * max_len beyond
+ * 2^56, the 2^31 rule above.  Zero bags succeed and write nothing.
+ * Not served: hot/cold pairs and their groups, mixed groups, the sharded and peer-mapped forms, left padding or a pad value other than zero, hit
+ * counting, located rows. */
+enum { MEE_PAD_KEEP_FIRST = 0, MEE_PAD_KEEP_LAST = 1 };
+int mee_find_padded_as(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, size_t max_len,
+                       uint32_t flags, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_lengths_out, int64_t* d_step_keys_out,
+                       uint32_t* d_grad_index_out, void* stream);
+int mee_group_find_padded_as(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, size_t max_len,
+                             uint32_t flags, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_lengths_out, int64_t* d_step_keys_out,
+                             uint32_t* d_grad_index_out, void* stream);
+
 /* ---- mixed groups: an embedding-bag collection whose tables differ in dim (SPEC.md §3 "Mixed groups") ------------------------
  * The members share a device (and, with max_apply_batch, an optimizer); every dim is a multiple of 4.  Pooled lookups only: bag b belongs
  * to member b / bags_per_table, and by definition every operator is the single-table operator of each member with its bags.

@@ -114,6 +114,11 @@ public:
     void find_pooled_as(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const float* d_weights, void* d_out, uint32_t out_dtype, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, int mode = MEE_POOL_SUM, void* stream = nullptr) const {
         check(mee_find_pooled_as(t_, d_keys, n, d_bag_offsets, n_bags, d_weights, d_out, out_dtype, d_found, d_located_out, mode, stream));
     }
+    // padded sequence lookup: d_out [n_bags, max_len, dim] of out_dtype, zeros behind a short bag, a long bag cut to its first / last (flags = MEE_PAD_KEEP_*)
+    // max_len keys; d_step_keys_out / d_grad_index_out are what apply_*_indexed over the dense grad needs.  Every output but d_out is nullable
+    void find_padded_as(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, size_t max_len, uint32_t flags, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, uint8_t* d_found = nullptr, int64_t* d_lengths_out = nullptr, int64_t* d_step_keys_out = nullptr, uint32_t* d_grad_index_out = nullptr, void* stream = nullptr) const {
+        check(mee_find_padded_as(t_, d_keys, n, d_bag_offsets, n_bags, max_len, flags, d_out, out_dtype, d_found, d_lengths_out, d_step_keys_out, d_grad_index_out, stream));
+    }
     void apply_adagrad_located(const int64_t* d_keys, const int64_t* d_slots, const float* d_grads, size_t n, float lr, float eps = 1e-10f, void* stream = nullptr) { check(mee_apply_adagrad_located(t_, d_keys, d_slots, d_grads, n, lr, eps, stream)); }
     void apply_adam_located(const int64_t* d_keys, const int64_t* d_slots, const float* d_grads, size_t n, float lr, uint64_t step, float beta1 = 0.9f, float beta2 = 0.999f, float eps = 1e-8f, void* stream = nullptr) {
         check(mee_apply_adam_located(t_, d_keys, d_slots, d_grads, n, lr, beta1, beta2, eps, step, stream));
@@ -193,6 +198,10 @@ public:
     void admission_decay(uint32_t shift = 1, void* stream = nullptr) { check(mee_group_admission_decay(g_, shift, stream)); }
     void find_pooled_as(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights, void* d_out, uint32_t out_dtype, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, int mode = MEE_POOL_SUM, void* stream = nullptr) {
         check(mee_group_find_pooled_as(g_, d_keys, n, d_bag_offsets, bags_per_table, d_weights, d_out, out_dtype, d_found, d_located_out, mode, stream));
+    }
+    // Table::find_padded_as of every member on its bags_per_table bags, one launch (bag b belongs to member b / bags_per_table)
+    void find_padded_as(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, size_t max_len, uint32_t flags, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, uint8_t* d_found = nullptr, int64_t* d_lengths_out = nullptr, int64_t* d_step_keys_out = nullptr, uint32_t* d_grad_index_out = nullptr, void* stream = nullptr) {
+        check(mee_group_find_padded_as(g_, d_keys, n, d_bag_offsets, bags_per_table, max_len, flags, d_out, out_dtype, d_found, d_lengths_out, d_step_keys_out, d_grad_index_out, stream));
     }
     void set_tuning(const char* name, int value) { check(mee_group_set_tuning(g_, name, value)); }   // knobs of the group's own apply; never change results
     void apply_adagrad(const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr, float eps = 1e-10f, void* stream = nullptr) {

@@ -29,6 +29,7 @@ FLAG_INT8_ROWS = 8   # a serving table whose value plane holds int8 codes and on
 FLAG_TRACK_HITS, FLAG_ADMISSION, FLAG_BF16_ROWS = 1, 2, 4   # BF16_ROWS: a serving table whose value plane holds bf16 rows (SPEC.md §3 "Row storage type")
 TIER_COUNT_COLD, TIER_COUNT_HOT = 1, 2   # mee_find_pooled_tiered flags
 EVICT_LEAST, EVICT_RESET = 1, 2          # mee_evict flags
+PAD_KEEP_FIRST, PAD_KEEP_LAST = 0, 1     # mee_find_padded_as flags: which end of a bag longer than max_len is kept
 ABI_VERSION = 2   # MEE_ABI_VERSION of include/meepo_embedding.h this loader was written against
 EMPTY_KEY = -(1 << 63)
 RECLAIMED_KEY = EMPTY_KEY + 1
@@ -103,6 +104,9 @@ PROTOTYPES = {
     "mee_find_grouped_as": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _u32, _vp, _vp]),
     "mee_group_find_or_insert_as": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _u32, _vp, _vp]),
     "mee_group_find_pooled_as": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _u32, _vp, _vp, C.c_int, _vp]),
+    # padded sequence lookup: (table | group), keys, n, bag offsets, (n_bags | bags_per_table), max_len, flags, out, out_dtype, found, lengths, step_keys, grad_index, stream
+    "mee_find_padded_as": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "mee_group_find_padded_as": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "mee_find_missing": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "mee_find_counted": (C.c_int, [_vp, _vp, _sz, _vp, _vp, C.c_int, _vp]),
     "mee_hits_scan": (C.c_int, [_vp, _u32, _u32, C.c_int, _vp, _sz, C.POINTER(_sz), _vp]),

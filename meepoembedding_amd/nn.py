@@ -9,6 +9,7 @@
     meepo::lookup_located / meepo::apply_grad_located                 the same pair over ONE HBM table: the forward
                                                                                  (find[_or_insert]_located) hands every key's slot
                                                                                  to the backward, whose apply then does not probe
+    meepo::lookup_padded / meepo::apply_grad_padded                   padded sequences: [n_bags, max_len, dim], the backward an indexed step
     meepo::lookup_pooled[_weighted] / meepo::apply_grad_pooled[_weighted]   embedding bags (sum / mean; weighted sum with the grad of
                                                                                  the per-sample weights)
 
@@ -30,6 +31,8 @@ Optional methods:
     apply_pooled                        a group: bag b belongs to member b // bags_per_table, `tables` lists the members, the step is apply_pooled
     find_located, find_or_insert_located, apply_discard, max_batch      ONE table whose lookups hand out slot handles for apply_*(slots=)
     layout_epoch                        changes when stored rows move: handles a forward took are dropped by its backward
+    find_padded                         the padded sequence lookup in one launch (LookupTable, TableGroup); without it DynamicEmbeddingSequence
+                                        composes it from find
     admission_refusal() -> str | None   why a layer's min_count is refused over this table (None: it admits); a class without the method has
                                         no admission
 `_nn_prepared` on a table with find_located is this module's: the (tensor, length) whose apply partition the last training forward left pending.
@@ -61,6 +64,7 @@ class _Traits(NamedTuple):
     hot_cold_pair: bool
     has_epoch: bool
     admission_refusal: Callable[[], str | None] | None
+    native_padded: bool = False   # find_padded exists (one launch); without it DynamicEmbeddingSequence composes find and a placement
 
 
 def _traits(table) -> _Traits:
@@ -73,7 +77,8 @@ def _traits(table) -> _Traits:
     bf16_rows = bool(getattr(table, "supports_out_dtype", False))
     return _Traits(grouped, grouped and not inserts, located_table, inserts, bool(getattr(table, "weighted_bags", True)),
                    bool(getattr(table, "mixed_dims", False)), bf16_rows, bf16_rows or bool(getattr(table, "supports_pooled_out_dtype", False)),
-                   bool(getattr(table, "hot_cold_pair", False)), hasattr(table, "layout_epoch"), getattr(table, "admission_refusal", None))
+                   bool(getattr(table, "hot_cold_pair", False)), hasattr(table, "layout_epoch"), getattr(table, "admission_refusal", None),
+                   hasattr(table, "find_padded"))
 
 
 def _admit_kw(layer) -> dict:
@@ -449,6 +454,109 @@ def _backward_jagged(ctx, grad_out):
 lookup_jagged.register_autograd(_backward_jagged, setup_context=_setup_jagged)
 
 
+# ---- padded sequences (SPEC.md §3 "find_padded"): [n_bags, max_len, dim] with zeros behind a short bag, a long bag cut to max_len --------------
+# forward = the table's (the group's) find_padded, which also says which slot every kept position went to; backward = the indexed step on exactly
+# that: position i takes row grad_index[i] of the dense grad viewed as [n_bags * max_len, dim], cut-off positions are EMPTY and take no step.
+# A table without find_padded (traits.native_padded False: a CPU adapter, a hot/cold pair, a sharded or tiered group) is served by composition:
+# find on the kept keys and a placement into a zeroed block; its backward gathers the kept slots' grad rows and runs the plain step.
+def _padded_places(keys, bag_offsets, max_len: int, keep_last: bool):
+    """find_padded's bookkeeping in torch, the ONE place the composition gets it from -> (lengths [n_bags] int64, step_keys [n] int64, grad_index [n]
+    int32, the kept positions in slot order): the bags clamped as the library clamps them, kept = min(len, max_len) positions from the bag's front or
+    back, slot b * max_len + j for the j-th of them; EMPTY / 0 everywhere else.  The kept positions come from the placement, never from the keys: a
+    kept position whose key is EMPTY still fills its slot (with the default row)."""
+    n = keys.numel()
+    off = bag_offsets.to(torch.int64).clamp(min=0, max=n)
+    end = off[1:]
+    begin = torch.minimum(off[:-1], end)
+    kept = (end - begin).clamp(max=max_len)
+    first = end - kept if keep_last else begin
+    j = torch.arange(max_len, device=keys.device)[None, :]
+    live = j < kept[:, None]                                   # [n_bags, max_len]: the slots that hold a row
+    pos = (first[:, None] + j)[live]
+    slot = torch.nonzero(live.reshape(-1)).view(-1)
+    step_keys = torch.full((n,), -(1 << 63), dtype=torch.int64, device=keys.device)
+    grad_index = torch.zeros(n, dtype=torch.int32, device=keys.device)
+    step_keys[pos] = keys[pos]
+    grad_index[pos] = slot.to(torch.int32)
+    return kept, step_keys, grad_index, pos
+
+
+def _kept_segments(layer, pos, bag_offsets, n: int):
+    """the composition's compact batch is keys[pos] (pos ascending); for a group -> the members' offsets into it, else None"""
+    if not layer.traits.grouped:
+        return None
+    bounds = _member_offsets(layer.table, bag_offsets).to(torch.int64).clamp(min=0, max=n)
+    return torch.searchsorted(pos, bounds).contiguous()
+
+
+@torch.library.custom_op("meepo::lookup_padded", mutates_args=())
+def lookup_padded(keys: torch.Tensor, bag_offsets: torch.Tensor, anchor: torch.Tensor, table_id: int, max_len: int,
+                  keep_last: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (padded [n_bags, max_len, dim], lengths [n_bags], step_keys [n], grad_index [n]: what the backward of this step applies)"""
+    layer = _layer(table_id)
+    table = layer.table
+    _create_unseen(layer, keys, bag_offsets)
+    if layer.traits.native_padded:
+        out, _, lengths, step_keys, grad_index = table.find_padded(keys, bag_offsets, max_len, "last" if keep_last else "first", with_step=True, **_dtype_kw(layer))
+        return out, lengths, step_keys, grad_index
+    lengths, step_keys, grad_index, pos = _padded_places(keys, bag_offsets, max_len, keep_last)
+    seg = _kept_segments(layer, pos, bag_offsets, keys.numel())
+    out = torch.zeros((lengths.numel() * max_len, table.dim), dtype=layer.out_dtype, device=keys.device)
+    if pos.numel():
+        kk = keys[pos].contiguous()
+        rows, _ = table.find(kk, seg, **_dtype_kw(layer)) if seg is not None else table.find(kk, **_dtype_kw(layer))
+        out[grad_index[pos].to(torch.int64)] = rows.to(out.device)
+    return out.view(lengths.numel(), max_len, table.dim), lengths, step_keys, grad_index
+
+
+@lookup_padded.register_fake
+def _(keys, bag_offsets, anchor, table_id, max_len, keep_last):
+    layer = _layer(table_id)
+    n_bags = bag_offsets.numel() - 1
+    return (keys.new_empty((n_bags, max_len, layer.table.dim), dtype=layer.out_dtype), keys.new_empty(n_bags), keys.new_empty(keys.numel()),
+            keys.new_empty(keys.numel(), dtype=torch.int32))
+
+
+@torch.library.custom_op("meepo::apply_grad_padded", mutates_args=())
+def apply_grad_padded(step_keys: torch.Tensor, bag_offsets: torch.Tensor, grad_index: torch.Tensor, grad_padded: torch.Tensor, table_id: int) -> None:
+    layer = _layer(table_id)
+    table = layer.table
+    g = grad_padded.contiguous().view(-1, table.dim)
+    step = _step_now(layer)
+    if layer.traits.native_padded:
+        if layer.traits.grouped:
+            seg = _member_offsets(table, bag_offsets).to(torch.int64).clamp(min=0, max=step_keys.numel()).contiguous()
+            table.apply_indexed(step_keys, seg, g, grad_index, *step)
+        else:
+            step.apply_to(table, step_keys, g, grad_index=grad_index)
+        return
+    pos = torch.nonzero(step_keys != -(1 << 63)).view(-1)   # (a kept EMPTY key takes no step anyway: every apply skips it)
+    seg = _kept_segments(layer, pos, bag_offsets, step_keys.numel())
+    if pos.numel():
+        kk, gg = step_keys[pos].contiguous(), g[grad_index[pos].to(torch.int64)].contiguous()
+        step.apply_to(table, kk, *(() if seg is None else (seg,)), gg)
+
+
+@apply_grad_padded.register_fake
+def _(step_keys, bag_offsets, grad_index, grad_padded, table_id):
+    return None
+
+
+def _setup_padded(ctx, inputs, output):
+    ctx.save_for_backward(output[2], inputs[1], output[3])
+    ctx.table_id = inputs[3]
+    ctx.mark_non_differentiable(output[1], output[2], output[3])
+
+
+def _backward_padded(ctx, grad_out, _g_lengths, _g_keys, _g_index):
+    step_keys, bag_offsets, grad_index = ctx.saved_tensors
+    apply_grad_padded(step_keys, bag_offsets, grad_index, grad_out.contiguous().to(torch.float32), ctx.table_id)   # a bf16 layer's grad is widened (exact)
+    return None, None, None, None, None, None
+
+
+lookup_padded.register_autograd(_backward_padded, setup_context=_setup_padded)
+
+
 def _check_min_count(layer: str, table, traits: _Traits, min_count, creates: bool = True, rows_layer: bool = False,
                      out_dtype: torch.dtype = torch.float32):
     """A layer's min_count (admission, SPEC.md §3 find_or_insert_admit): None, or a threshold over a table that admits.  The layer's own rules are
@@ -551,6 +659,30 @@ class DynamicEmbeddingBag(_SparseLayer):
         if not self.traits.weighted_bags:   # (a ShardedTableGroup: refused on every rank alike, before anything is exchanged; a TieredLookupTable)
             raise ValueError(f"{type(self.table).__name__} has no weighted bags: per_sample_weights are not offered over a sharded group or a hot/cold pair")
         return lookup_pooled_weighted(keys, bag_offsets, per_sample_weights, self._anchor, self.table_id)[0]
+
+
+class DynamicEmbeddingSequence(_SparseLayer):
+    """Sequence features as a sequence model reads them: (keys [n], bag_offsets [n_bags + 1], both on the device) -> (padded [n_bags, max_len, dim],
+    lengths [n_bags] int64).  padded[b, j] is the row of bag b's j-th kept id, zeros behind the end of a short bag; a bag longer than max_len keeps
+    its first (keep="first") or its last (keep="last") max_len ids; lengths is the mask.  Over a LookupTable or a TableGroup (bag b then belongs to
+    member b // bags_per_table) the forward is ONE launch that writes the block directly and the backward the table's indexed step on the dense grad
+    — no [n, dim] tensor exists in either direction, and ids that were cut off are neither looked up nor trained.  Any other table with find /
+    find_or_insert / apply_* (a hot/cold pair, a sharded or tiered group) is served by composition, with the same results.
+    create_missing=True (training mode only): unseen ids — cut-off ones too — are inserted with their hashed initial row first (one more pass over
+    the ids); otherwise absent ids read the default row and are not trained."""
+
+    def __init__(self, table_or_group, max_len: int, keep: str = "first", optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None,
+                 betas=(0.9, 0.999), create_missing: bool = True, out_dtype: torch.dtype = torch.float32):
+        if keep not in ("first", "last"):
+            raise ValueError(f"keep must be 'first' or 'last' (got {keep!r})")
+        if int(max_len) < 1:
+            raise ValueError(f"max_len must be at least 1 (got {max_len})")
+        super().__init__(table_or_group, optimizer, lr, eps, betas, out_dtype, None)
+        self.max_len, self.keep, self.create_missing = int(max_len), keep, create_missing
+
+    def forward(self, keys: torch.Tensor, bag_offsets: torch.Tensor):
+        padded, lengths, _, _ = lookup_padded(keys, bag_offsets, self._anchor, self.table_id, self.max_len, self.keep == "last")
+        return padded, lengths
 
 
 class DynamicEmbedding(_SparseLayer):

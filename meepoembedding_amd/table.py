@@ -59,6 +59,38 @@ def _fp32_only(out: torch.Tensor | None, op: str) -> None:
                          "find_or_insert_located, find_pooled and the TableGroup lookups")
 
 
+_PAD_KEEP = {"first": _lib.PAD_KEEP_FIRST, "last": _lib.PAD_KEEP_LAST}
+
+
+def _find_padded(fn, handle, device: torch.device, dim: int, k: torch.Tensor, bag_offsets: torch.Tensor, n_bags: int, bags_arg: int, max_len: int,
+                 keep: str, out, found, out_dtype: torch.dtype, with_step: bool):
+    """the padded lookup of a table (fn = mee_find_padded_as, bags_arg = n_bags) or a group (mee_group_find_padded_as, bags_arg = bags_per_table):
+    arguments checked before any launch, buffers allocated here — the per-position ones pre-set to what a position in no bag reports (not found,
+    EMPTY, index 0), since the launch leaves those alone."""
+    dt = _out_dtype(out_dtype, out)
+    if keep not in _PAD_KEEP:
+        raise ValueError(f"keep must be 'first' or 'last' (got {keep!r})")
+    max_len = int(max_len)
+    if max_len < 1:
+        raise ValueError(f"max_len must be at least 1 (got {max_len})")
+    n = k.numel()
+    if out is None:
+        out = torch.empty((n_bags, max_len, dim), dtype=out_dtype, device=device)
+    elif out.device != device or out.numel() != n_bags * max_len * dim or not out.is_contiguous():
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"out must be a contiguous buffer [{n_bags}, {max_len}, {dim}] on {device}")
+    if found is None:
+        found = torch.zeros(n, dtype=torch.uint8, device=device)
+    elif found.dtype != torch.uint8 or found.device != device or found.numel() != n or not found.is_contiguous():
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"found must be a contiguous uint8 buffer of {n} entries on {device}")
+    lengths = torch.empty(n_bags, dtype=torch.int64, device=device)
+    step_keys = torch.full((n,), _lib.EMPTY_KEY, dtype=torch.int64, device=device) if with_step else None
+    grad_index = torch.zeros(n, dtype=torch.int32, device=device) if with_step else None   # (uint32 to the library: a slot number below 2^31)
+    check(fn(handle, k.data_ptr(), n, bag_offsets.data_ptr(), bags_arg, max_len, _PAD_KEEP[keep], out.data_ptr(), dt, found.data_ptr(), lengths.data_ptr(),
+             step_keys.data_ptr() if with_step else None, grad_index.data_ptr() if with_step else None, _stream_ptr(device)))
+    out = out.view(n_bags, max_len, dim)
+    return (out, found, lengths, step_keys, grad_index) if with_step else (out, found, lengths)
+
+
 class SparseStep(NamedTuple):
     """One sparse optimizer step as a value: which optimizer and its scalars.  The table classes build it once per call and forward it; nothing
     else in the package tells the optimizers apart.  The fields stand in the order of apply_pooled / apply_indexed's loose form, so `*step` is it."""
@@ -290,6 +322,19 @@ class LookupTable:
         check(_lib.lib().mee_find_pooled(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), n_bags, out.data_ptr(), found.data_ptr(),
                                          {"sum": 0, "mean": 1}[mode], self._s()))
         return out, found
+
+    def find_padded(self, keys: torch.Tensor, bag_offsets: torch.Tensor, max_len: int, keep: str = "first", out: torch.Tensor | None = None,
+                    found: torch.Tensor | None = None, out_dtype: torch.dtype = torch.float32, with_step: bool = False):
+        """Padded sequence lookup (mee_find_padded_as): bag b = keys[bag_offsets[b]:bag_offsets[b+1]] -> (out [n_bags, max_len, dim], per-key found
+        mask, lengths [n_bags] int64).  out[b, j] is the row find() returns for the bag's j-th kept key, zeros behind the end of a short bag; a bag
+        longer than max_len keeps its first (keep="first") or its last (keep="last") max_len keys, and a key that is cut off is not looked up
+        (found 0).  Every element of `out` is written, in one launch, with no [n, dim] array in between.
+        with_step=True also returns (step_keys int64 [n], grad_index int32 [n]): the table step of the lookup is
+        apply_*(step_keys, dense_grad.view(n_bags * max_len, dim), grad_index=grad_index) — cut-off keys are EMPTY there and take no step."""
+        k = self._keys(keys) if keys.numel() else keys
+        n_bags = self._bag_offsets(bag_offsets)
+        return _find_padded(_lib.lib().mee_find_padded_as, self._h, self.device, self.dim, k, bag_offsets, n_bags, n_bags, max_len, keep, out, found,
+                            out_dtype, with_step)
 
     def pooled_weighted_backward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, weights: torch.Tensor, bag_grads: torch.Tensor,
                                  located: torch.Tensor | None = None, want_weight_grads: bool = True, grads: torch.Tensor | None = None,
@@ -900,6 +945,16 @@ class TableGroup:
                                                located.data_ptr() if located is not None else None,
                                                {"sum": 0, "mean": 1}[mode], _stream_ptr(self.device)))
         return out, found
+
+    def find_padded(self, keys: torch.Tensor, bag_offsets: torch.Tensor, max_len: int, keep: str = "first", out: torch.Tensor | None = None,
+                    found: torch.Tensor | None = None, out_dtype: torch.dtype = torch.float32, with_step: bool = False):
+        """LookupTable.find_padded of every member on its bags_per_table bags, in one launch (mee_group_find_padded_as) ->
+        (out [n_tables * bags_per_table, max_len, dim], per-key found mask, lengths) and, with_step=True, (step_keys, grad_index): the step is
+        apply_indexed(step_keys, bag_offsets[::bags_per_table].contiguous(), dense_grad.view(-1, dim), grad_index, ...)."""
+        bpt = self._check_bags(bag_offsets)
+        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        return _find_padded(_lib.lib().mee_group_find_padded_as, self._h, self.device, self.dim, k, bag_offsets, bpt * len(self.tables), bpt, max_len, keep, out,
+                            found, out_dtype, with_step)
 
     def apply_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, bag_grads: torch.Tensor, bag_of_position: torch.Tensor,
                      optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1,
