@@ -1,6 +1,7 @@
 """A recommender's sparse part whose tables do not fit HBM: 8 tables, each a hot/cold pair (hot rows in HBM, cold rows in pinned host
 memory), served by ONE pooled lookup launch and trained by two grouped optimizer steps per batch, whatever the number of tables; then the
-same pairs behind a DynamicEmbeddingCollection, which returns a row per id (a sequence feature) from one launch.  Both layers admit: an unseen id enters its pair only once the pair's hot table's sketch has
+same pairs behind a DynamicEmbeddingCollection, which returns a row per id (a sequence feature) from one launch, and behind a
+DynamicEmbeddingSequence, which returns the padded [n_bags, max_len, dim] block of histories of different lengths from one launch.  The first two layers admit: an unseen id enters its pair only once the pair's hot table's sketch has
 seen it asked for min_count times — a skewed stream's once-seen tail stays out of both tiers
 (run on the GPU box: python examples/tiered_collection.py [min_count, default 2; 0 = create at first sight, no admission])."""
 import os
@@ -13,7 +14,7 @@ import __graft_entry__
 
 __graft_entry__.build()
 from meepoembedding_amd import INIT_UNIFORM, OPT_ADAGRAD, LookupTable, TieredLookupTable, TieredTableGroup, _lib  # noqa: E402
-from meepoembedding_amd.nn import DynamicEmbeddingBag, DynamicEmbeddingCollection  # noqa: E402
+from meepoembedding_amd.nn import DynamicEmbeddingBag, DynamicEmbeddingCollection, DynamicEmbeddingSequence  # noqa: E402
 
 dev = torch.device("cuda", 0)
 n_tables, dim, batch, ids_per_bag, vocab = 8, 64, 2048, 5, 400_000
@@ -64,3 +65,17 @@ for step in range(4):
     loss.backward()                                                   # the sparse update happens here; the scorer is not trained in this sketch
     print(f"sequence step {step}: loss {loss.item():.5f}, rows {tuple(rows.shape)} {rows.dtype}, keys hot {sum(p.hot.size() for p in pairs)} / cold "
           f"{sum(p.cold.size() for p in pairs)}")
+
+# Histories of different lengths, as a sequence model reads them: one padded [n_bags, max_len, dim] block and the lengths for the mask.  Forward is ONE
+# launch over both tiers of every pair (no [n, dim] rows in between; an id that is cut off is neither looked up nor counted nor trained), backward
+# two grouped indexed steps on the dense grad of the block.
+padded_history = DynamicEmbeddingSequence(group, max_len=6, keep="last", optimizer="adagrad", lr=0.05, create_missing=True).to(dev)
+for step in range(4):
+    lens = torch.randint(0, 12, (n_tables * batch,), device=dev)          # bag b -> pair b // batch; histories past max_len keep their last 6 ids
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(lens, 0)])
+    ids = (torch.rand(int(offsets[-1]), device=dev) ** 3 * vocab).long()
+    block, lengths = padded_history(ids, offsets)                           # [n_tables * batch, 6, dim] fp32, [n_tables * batch]
+    mask = (torch.arange(6, device=dev)[None, :] < lengths[:, None]).unsqueeze(-1)
+    loss = (block * mask).sum(dim=1).square().mean()
+    loss.backward()
+    print(f"padded step {step}: loss {loss.item():.5f}, block {tuple(block.shape)}, mean kept length {lengths.float().mean().item():.2f}")

@@ -640,8 +640,8 @@ int mee_group_find_pooled_as(mee_group* g, const int64_t* d_keys, size_t n, cons
  * MEE_ERR_INVALID_ARG, before anything is launched or written: a null table or group, null d_bag_offsets or d_out with bags to serve, null d_keys
  * with n > 0, max_len == 0, an unknown flag bit, an unknown out_dtype (MEE_DTYPE_INT8 included), a misaligned bf16 d_out, n_bags * max_len beyond
  * 2^56, the 2^31 rule above.  Zero bags succeed and write nothing.
- * Not served: hot/cold pairs and their groups, mixed groups, the sharded and peer-mapped forms, left padding or a pad value other than zero, hit
- * counting, located rows. */
+ * Not served: mixed groups, int8-row tables, the sharded and peer-mapped forms, left padding or a pad value other than zero, located rows
+ * (DESIGN.md §6).  Hot/cold pairs and groups of pairs: mee_find_padded_tiered / mee_group_find_padded_tiered below; only those count hits. */
 enum { MEE_PAD_KEEP_FIRST = 0, MEE_PAD_KEEP_LAST = 1 };
 int mee_find_padded_as(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, size_t max_len,
                        uint32_t flags, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_lengths_out, int64_t* d_step_keys_out,
@@ -649,6 +649,28 @@ int mee_find_padded_as(const mee_table* t, const int64_t* d_keys, size_t n, cons
 int mee_group_find_padded_as(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, size_t max_len,
                              uint32_t flags, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_lengths_out, int64_t* d_step_keys_out,
                              uint32_t* d_grad_index_out, void* stream);
+
+/* The padded lookup over a hot/cold pair (SPEC.md §3 "Tiering") and over a group of pairs: mee_find_padded_as on the UNION of the two tables, bit
+ * for bit, in ONE launch that probes the hot index, then the cold index for what the hot one missed, and takes each row from the plane that holds
+ * it.  A kept position reads the hot table's row if `hot` holds its key, else the cold table's row if `cold` holds it, else a row of HOT's
+ * default_value (reserved keys too); d_found[i] = 1 iff either tier holds the key.  d_out, d_lengths_out, d_step_keys_out, d_grad_index_out, the
+ * truncated positions (found 0, step key EMPTY, grad index 0, no probe), the clamping of the offsets and the positions in no bag (left alone) are
+ * mee_find_padded_as's.  flags = MEE_PAD_KEEP_*; count_flags = MEE_TIER_COUNT_COLD | MEE_TIER_COUNT_HOT, a word of its own because
+ * MEE_PAD_KEEP_LAST and MEE_TIER_COUNT_COLD are both 1: every KEPT position found in a tier adds 1 to that slot's hit counter when that tier's bit
+ * is set; a truncated position counts nothing.  fp32 rows only (a pair takes no narrow rows: MEE_ERR_UNSUPPORTED); fp32 or bf16 out.
+ * mee_group_find_padded_tiered: member j of `hot` and member j of `cold` are the two tiers of pair j; n_bags = n_tables * bags_per_table, bag b is,
+ * by definition, the pair form of pair b / bags_per_table on that bag (its rows, its hot default, its counters).
+ * MEE_ERR_INVALID_ARG, before anything is launched or written: a null table or group; hot == cold (a group: also a table that is member j of both);
+ * tiers that differ in device or dim (groups: or number of tables); an unknown bit in either flag word; a count bit without that tier's
+ * MEE_FLAG_TRACK_HITS (a group: in EVERY member of that tier); and every refusal of mee_find_padded_as about the call's shape.  Zero bags succeed
+ * and write nothing.  Both are one launch, never allocate and never synchronise — the group form EXCEPT in the first call after mee_reserve on a
+ * member of either group, which re-reads that table's planes (one stream synchronisation, not capturable). */
+int mee_find_padded_tiered(const mee_table* hot, const mee_table* cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
+                           size_t max_len, uint32_t flags, uint32_t count_flags, void* d_out, uint32_t out_dtype, uint8_t* d_found,
+                           int64_t* d_lengths_out, int64_t* d_step_keys_out, uint32_t* d_grad_index_out, void* stream);
+int mee_group_find_padded_tiered(mee_group* hot, mee_group* cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets,
+                                 size_t bags_per_table, size_t max_len, uint32_t flags, uint32_t count_flags, void* d_out, uint32_t out_dtype,
+                                 uint8_t* d_found, int64_t* d_lengths_out, int64_t* d_step_keys_out, uint32_t* d_grad_index_out, void* stream);
 
 /* ---- mixed groups: an embedding-bag collection whose tables differ in dim (SPEC.md §3 "Mixed groups") ------------------------
  * The members share a device (and, with max_apply_batch, an optimizer); every dim is a multiple of 4.  Pooled lookups only: bag b belongs

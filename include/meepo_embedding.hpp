@@ -119,6 +119,11 @@ public:
     void find_padded_as(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, size_t max_len, uint32_t flags, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, uint8_t* d_found = nullptr, int64_t* d_lengths_out = nullptr, int64_t* d_step_keys_out = nullptr, uint32_t* d_grad_index_out = nullptr, void* stream = nullptr) const {
         check(mee_find_padded_as(t_, d_keys, n, d_bag_offsets, n_bags, max_len, flags, d_out, out_dtype, d_found, d_lengths_out, d_step_keys_out, d_grad_index_out, stream));
     }
+    // ... over a hot/cold pair: this table is the HOT tier, `cold` the cold one (mee_find_padded_tiered): find_padded_as on the union of the two, one launch;
+    // count_flags = MEE_TIER_COUNT_* (a word of its own: MEE_PAD_KEEP_LAST and MEE_TIER_COUNT_COLD are both 1)
+    void find_padded_tiered(const Table& cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, size_t max_len, uint32_t flags, uint32_t count_flags, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, uint8_t* d_found = nullptr, int64_t* d_lengths_out = nullptr, int64_t* d_step_keys_out = nullptr, uint32_t* d_grad_index_out = nullptr, void* stream = nullptr) const {
+        check(mee_find_padded_tiered(t_, cold.t_, d_keys, n, d_bag_offsets, n_bags, max_len, flags, count_flags, d_out, out_dtype, d_found, d_lengths_out, d_step_keys_out, d_grad_index_out, stream));
+    }
     void apply_adagrad_located(const int64_t* d_keys, const int64_t* d_slots, const float* d_grads, size_t n, float lr, float eps = 1e-10f, void* stream = nullptr) { check(mee_apply_adagrad_located(t_, d_keys, d_slots, d_grads, n, lr, eps, stream)); }
     void apply_adam_located(const int64_t* d_keys, const int64_t* d_slots, const float* d_grads, size_t n, float lr, uint64_t step, float beta1 = 0.9f, float beta2 = 0.999f, float eps = 1e-8f, void* stream = nullptr) {
         check(mee_apply_adam_located(t_, d_keys, d_slots, d_grads, n, lr, beta1, beta2, eps, step, stream));
@@ -233,6 +238,11 @@ public:
     // ... with the members' bag counts read from d_member_bags [n_tables + 1] on the device (mee_group_find_pooled_tiered_jagged; fp32 out)
     void find_pooled_tiered_jagged(Group& cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const uint64_t* d_member_bags, float* d_out, uint8_t* d_found = nullptr, int mode = MEE_POOL_SUM, uint32_t flags = 0, void* stream = nullptr) {
         check(mee_group_find_pooled_tiered_jagged(g_, cold.g_, d_keys, n, d_bag_offsets, n_bags, d_member_bags, d_out, d_found, mode, flags, stream));
+    }
+    // the padded sequence lookup over the same collection of pairs, one launch (mee_group_find_padded_tiered): Table::find_padded_tiered of pair
+    // b / bags_per_table on bag b; flags = MEE_PAD_KEEP_*, count_flags = MEE_TIER_COUNT_*
+    void find_padded_tiered(Group& cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, size_t max_len, uint32_t flags, uint32_t count_flags, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, uint8_t* d_found = nullptr, int64_t* d_lengths_out = nullptr, int64_t* d_step_keys_out = nullptr, uint32_t* d_grad_index_out = nullptr, void* stream = nullptr) {
+        check(mee_group_find_padded_tiered(g_, cold.g_, d_keys, n, d_bag_offsets, bags_per_table, max_len, flags, count_flags, d_out, out_dtype, d_found, d_lengths_out, d_step_keys_out, d_grad_index_out, stream));
     }
     void ensure_tiered(Group& cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const uint8_t* d_found, const uint8_t* d_to_cold = nullptr, void* stream = nullptr) {
         check(mee_group_ensure_tiered(g_, cold.g_, d_keys, n, d_bag_offsets, bags_per_table, d_found, d_to_cold, stream));

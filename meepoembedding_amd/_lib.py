@@ -107,6 +107,9 @@ PROTOTYPES = {
     # padded sequence lookup: (table | group), keys, n, bag offsets, (n_bags | bags_per_table), max_len, flags, out, out_dtype, found, lengths, step_keys, grad_index, stream
     "mee_find_padded_as": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "mee_group_find_padded_as": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    # ... over a hot/cold pair or a group of pairs: (hot, cold), then the same with count_flags (TIER_COUNT_*) behind flags (PAD_KEEP_*)
+    "mee_find_padded_tiered": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "mee_group_find_padded_tiered": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "mee_find_missing": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "mee_find_counted": (C.c_int, [_vp, _vp, _sz, _vp, _vp, C.c_int, _vp]),
     "mee_hits_scan": (C.c_int, [_vp, _u32, _u32, C.c_int, _vp, _sz, C.POINTER(_sz), _vp]),

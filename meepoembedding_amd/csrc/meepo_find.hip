@@ -363,13 +363,7 @@ __device__ __forceinline__ bool jagged_member(const uint64_t* __restrict__ membe
 // BROWS (one bf16-row table, or with GROUPED a bf16-row group — every member's plane, JAGGED included; unweighted: SPEC.md §3 "Row
 // storage type"): the value planes hold bf16 rows.  One storage type per group, so this is a property of the launch, never a per-member
 // branch in the fetch.
-struct GroupTier {   // what a launch over a group of hot/cold pairs knows about the tiers (find_pooled_kernel<..., GROUPED, ..., TIERED>)
-    const GroupDesc* cold_desc;   // [n_tables] the cold members (device)
-    const GroupInit* hot_init;    // [n_tables] of the two groups: a member's `hits`
-    const GroupInit* cold_init;
-    uint32_t count;               // kTierCountCold | kTierCountHot
-};
-static_assert(kTierCountCold == MEE_TIER_COUNT_COLD && kTierCountHot == MEE_TIER_COUNT_HOT, "the kernels read the C-ABI's flag bits as they come");
+// (GroupTier and group_pair_tables, the pair of a member: meepo_table_int.h — the padded lookup of a group of pairs reads them too)
 template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false, bool JAGGED = false, bool TIERED = false, bool BROWS = false>
 __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restrict__ tkeys_, const float4* __restrict__ values_,
                                                           uint64_t nb_, const int64_t* __restrict__ keys,
@@ -410,10 +404,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                 bool in_map = true;
                 if constexpr (JAGGED) in_map = jagged_member(member_bags, n_members, b, member);   // (outside the map: an empty bag, the member still inside the group)
                 else member = b / bags_per_table;
-                t = pooled_table(desc[member], member, kGroupSlotBits);
-                const GroupDesc c = tier.cold_desc[member];
-                cold = TierArgs{c.tkeys, c.values, c.nb, (tier.count & kTierCountHot) ? tier.hot_init[member].hits : nullptr,
-                                (tier.count & kTierCountCold) ? tier.cold_init[member].hits : nullptr};
+                group_pair_tables(desc, tier, member, t, cold);
                 return in_map;
             };
             pooled_bags<DIM4, U, BPW, C, false, BF16, true, false, false>(b0, (uint32_t)(n_bags - b0 < BPW ? n_bags - b0 : BPW), dim4, keys, offsets, n_keys, nullptr, out, found,

@@ -178,6 +178,23 @@ struct mee_table {
 
 namespace mee {
 
+// ---- a GROUP of hot/cold pairs as a lookup kernel sees it (find_pooled_kernel<..., GROUPED, ..., TIERED> in meepo_find.hip, find_padded_tiered_kernel in
+// meepo_padded.hip): the hot members come in the kernel's `desc`, the rest in a GroupTier
+struct GroupTier {
+    const GroupDesc* cold_desc;   // [n_tables] the cold members (device)
+    const GroupInit* hot_init;    // [n_tables] of the two groups: a member's `hits`
+    const GroupInit* cold_init;
+    uint32_t count;               // kTierCountCold | kTierCountHot
+};
+static_assert(kTierCountCold == MEE_TIER_COUNT_COLD && kTierCountHot == MEE_TIER_COUNT_HOT, "the kernels read the C-ABI's flag bits as they come");
+// the hot and the cold table of pair `member`: `desc` holds the hot members; a member's counters are read only under the launch's count bit
+__device__ __forceinline__ void group_pair_tables(const GroupDesc* __restrict__ desc, const GroupTier& tier, uint64_t member, PooledTable& t, TierArgs& cold) {
+    t = pooled_table(desc[member], member, kGroupSlotBits);
+    const GroupDesc c = tier.cold_desc[member];
+    cold = TierArgs{c.tkeys, c.values, c.nb, (tier.count & kTierCountHot) ? tier.hot_init[member].hits : nullptr,
+                    (tier.count & kTierCountCold) ? tier.cold_init[member].hits : nullptr};
+}
+
 // ---- sparse optimizers (SPEC.md §4) ------------------------------------------------------------------------
 struct OptArgs {
     uint32_t kind;       // MEE_OPT_*

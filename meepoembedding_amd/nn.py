@@ -31,8 +31,8 @@ Optional methods:
     apply_pooled                        a group: bag b belongs to member b // bags_per_table, `tables` lists the members, the step is apply_pooled
     find_located, find_or_insert_located, apply_discard, max_batch      ONE table whose lookups hand out slot handles for apply_*(slots=)
     layout_epoch                        changes when stored rows move: handles a forward took are dropped by its backward
-    find_padded                         the padded sequence lookup in one launch (LookupTable, TableGroup); without it DynamicEmbeddingSequence
-                                        composes it from find
+    find_padded                         the padded sequence lookup in one launch (LookupTable, TableGroup, TieredLookupTable, TieredTableGroup; the step
+                                        is then apply_*(grad_index=) / a group's apply_indexed); without it DynamicEmbeddingSequence composes it from find
     admission_refusal() -> str | None   why a layer's min_count is refused over this table (None: it admits); a class without the method has
                                         no admission
 `_nn_prepared` on a table with find_located is this module's: the (tensor, length) whose apply partition the last training forward left pending.
@@ -46,7 +46,7 @@ from typing import Callable, NamedTuple
 import torch
 
 from ._lib import refuse_narrow_rows as _refuse_narrow_rows
-from .table import SparseStep, mixed_layout
+from .table import SparseStep, _padded_places, mixed_layout
 
 _LAYERS: "weakref.WeakValueDictionary[int, _SparseLayer]" = weakref.WeakValueDictionary()
 _IDS = itertools.count(1)
@@ -64,7 +64,7 @@ class _Traits(NamedTuple):
     hot_cold_pair: bool
     has_epoch: bool
     admission_refusal: Callable[[], str | None] | None
-    native_padded: bool = False   # find_padded exists (one launch); without it DynamicEmbeddingSequence composes find and a placement
+    native_padded: bool = False   # find_padded exists (one launch; pairs and tiered groups too); without it DynamicEmbeddingSequence composes find and a placement
 
 
 def _traits(table) -> _Traits:
@@ -457,30 +457,11 @@ lookup_jagged.register_autograd(_backward_jagged, setup_context=_setup_jagged)
 # ---- padded sequences (SPEC.md §3 "find_padded"): [n_bags, max_len, dim] with zeros behind a short bag, a long bag cut to max_len --------------
 # forward = the table's (the group's) find_padded, which also says which slot every kept position went to; backward = the indexed step on exactly
 # that: position i takes row grad_index[i] of the dense grad viewed as [n_bags * max_len, dim], cut-off positions are EMPTY and take no step.
-# A table without find_padded (traits.native_padded False: a CPU adapter, a hot/cold pair, a sharded or tiered group) is served by composition:
-# find on the kept keys and a placement into a zeroed block; its backward gathers the kept slots' grad rows and runs the plain step.
-def _padded_places(keys, bag_offsets, max_len: int, keep_last: bool):
-    """find_padded's bookkeeping in torch, the ONE place the composition gets it from -> (lengths [n_bags] int64, step_keys [n] int64, grad_index [n]
-    int32, the kept positions in slot order): the bags clamped as the library clamps them, kept = min(len, max_len) positions from the bag's front or
-    back, slot b * max_len + j for the j-th of them; EMPTY / 0 everywhere else.  The kept positions come from the placement, never from the keys: a
-    kept position whose key is EMPTY still fills its slot (with the default row)."""
-    n = keys.numel()
-    off = bag_offsets.to(torch.int64).clamp(min=0, max=n)
-    end = off[1:]
-    begin = torch.minimum(off[:-1], end)
-    kept = (end - begin).clamp(max=max_len)
-    first = end - kept if keep_last else begin
-    j = torch.arange(max_len, device=keys.device)[None, :]
-    live = j < kept[:, None]                                   # [n_bags, max_len]: the slots that hold a row
-    pos = (first[:, None] + j)[live]
-    slot = torch.nonzero(live.reshape(-1)).view(-1)
-    step_keys = torch.full((n,), -(1 << 63), dtype=torch.int64, device=keys.device)
-    grad_index = torch.zeros(n, dtype=torch.int32, device=keys.device)
-    step_keys[pos] = keys[pos]
-    grad_index[pos] = slot.to(torch.int32)
-    return kept, step_keys, grad_index, pos
-
-
+# A hot/cold pair and a TieredTableGroup have find_padded too (one launch over both tiers, mee_find_padded_tiered / mee_group_find_padded_tiered; tiers
+# that are not native tables compose it themselves): their backward is the pair's apply_*(grad_index=) and the group's apply_indexed.
+# A table without find_padded (traits.native_padded False: a CPU adapter, a sharded table or group, a sharded group of pairs) is served by composition:
+# find on the kept keys and a placement into a zeroed block (_padded_places, table.py: the one place the tiered classes' composition gets it from
+# too); its backward gathers the kept slots' grad rows and runs the plain step.
 def _kept_segments(layer, pos, bag_offsets, n: int):
     """the composition's compact batch is keys[pos] (pos ascending); for a group -> the members' offsets into it, else None"""
     if not layer.traits.grouped:
@@ -665,9 +646,10 @@ class DynamicEmbeddingSequence(_SparseLayer):
     """Sequence features as a sequence model reads them: (keys [n], bag_offsets [n_bags + 1], both on the device) -> (padded [n_bags, max_len, dim],
     lengths [n_bags] int64).  padded[b, j] is the row of bag b's j-th kept id, zeros behind the end of a short bag; a bag longer than max_len keeps
     its first (keep="first") or its last (keep="last") max_len ids; lengths is the mask.  Over a LookupTable or a TableGroup (bag b then belongs to
-    member b // bags_per_table) the forward is ONE launch that writes the block directly and the backward the table's indexed step on the dense grad
-    — no [n, dim] tensor exists in either direction, and ids that were cut off are neither looked up nor trained.  Any other table with find /
-    find_or_insert / apply_* (a hot/cold pair, a sharded or tiered group) is served by composition, with the same results.
+    member b // bags_per_table), and over a hot/cold pair or a TieredTableGroup of native tables (one launch over both tiers, which also feeds the
+    placement policy's hit counters), the forward is ONE launch that writes the block directly and the backward the table's indexed step on the
+    dense grad — no [n, dim] tensor exists in either direction, and ids that were cut off are neither looked up nor trained.  Any other table with
+    find / find_or_insert / apply_* (a sharded table or group, a sharded group of pairs, CPU adapters) is served by composition, with the same results.
     create_missing=True (training mode only): unseen ids — cut-off ones too — are inserted with their hashed initial row first (one more pass over
     the ids); otherwise absent ids read the default row and are not trained."""
 

@@ -91,6 +91,67 @@ def _find_padded(fn, handle, device: torch.device, dim: int, k: torch.Tensor, ba
     return (out, found, lengths, step_keys, grad_index) if with_step else (out, found, lengths)
 
 
+def _padded_places(keys, bag_offsets, max_len: int, keep_last: bool):
+    """find_padded's bookkeeping in torch, the ONE place a composition gets it from (nn.lookup_padded over a table without find_padded; the tiered
+    classes over tiers that are not native tables) -> (lengths [n_bags] int64, step_keys [n] int64, grad_index [n] int32, the kept positions in slot
+    order): the bags clamped as the library clamps them, kept = min(len, max_len) positions from the bag's front or back, slot b * max_len + j for
+    the j-th of them; EMPTY / 0 everywhere else.  The kept positions come from the placement, never from the keys: a kept position whose key is
+    EMPTY still fills its slot (with the default row)."""
+    n = keys.numel()
+    off = bag_offsets.to(torch.int64).clamp(min=0, max=n)
+    end = off[1:]
+    begin = torch.minimum(off[:-1], end)
+    kept = (end - begin).clamp(max=max_len)
+    first = end - kept if keep_last else begin
+    j = torch.arange(max_len, device=keys.device)[None, :]
+    live = j < kept[:, None]                                   # [n_bags, max_len]: the slots that hold a row
+    pos = (first[:, None] + j)[live]
+    slot = torch.nonzero(live.reshape(-1)).view(-1)
+    step_keys = torch.full((n,), -(1 << 63), dtype=torch.int64, device=keys.device)
+    grad_index = torch.zeros(n, dtype=torch.int32, device=keys.device)
+    step_keys[pos] = keys[pos]
+    grad_index[pos] = slot.to(torch.int32)
+    return kept, step_keys, grad_index, pos
+
+
+def _find_padded_composed(find_kept, dim: int, keys: torch.Tensor, bag_offsets: torch.Tensor, max_len: int, keep: str, out, found,
+                          out_dtype: torch.dtype, with_step: bool):
+    """find_padded's results by composition, for tables that have no launch of their own for it: _padded_places, then find_kept(kept keys, their
+    positions) -> (rows [n_kept, dim] fp32, found [n_kept]) placed into a zeroed block, the rows rounded once for a bf16 block.  A truncated position
+    reports found 0; a position in no bag keeps what the caller's `found` holds."""
+    _out_dtype(out_dtype, out)   # the refusals of _find_padded, in its order, before anything is looked up or written
+    if keep not in _PAD_KEEP:
+        raise ValueError(f"keep must be 'first' or 'last' (got {keep!r})")
+    max_len = int(max_len)
+    if max_len < 1:
+        raise ValueError(f"max_len must be at least 1 (got {max_len})")
+    flat = keys.contiguous().view(-1)
+    n, n_bags, device = flat.numel(), _n_bags(bag_offsets, flat.device), flat.device
+    if out is not None and (out.device != device or out.numel() != n_bags * max_len * dim or not out.is_contiguous()):
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"out must be a contiguous buffer [{n_bags}, {max_len}, {dim}] on {device}")
+    if found is not None and (found.dtype != torch.uint8 or found.device != device or found.numel() != n or not found.is_contiguous()):
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"found must be a contiguous uint8 buffer of {n} entries on {device}")
+    lengths, step_keys, grad_index, pos = _padded_places(flat, bag_offsets, max_len, keep == "last")
+    block = torch.zeros((n_bags * max_len, dim), dtype=out_dtype, device=device)
+    fnd = torch.zeros(n, dtype=torch.uint8, device=device) if found is None else found.view(-1)
+    # every position inside a bag: not found unless kept and held (a position in no bag keeps the caller's byte).  No host read-back: the bags'
+    # clamped spans as +1 / -1 marks, summed up
+    off = bag_offsets.to(torch.int64).clamp(min=0, max=n)
+    marks = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    marks.index_add_(0, torch.minimum(off[:-1], off[1:]), torch.ones(n_bags, dtype=torch.int64, device=device))
+    marks.index_add_(0, off[1:], -torch.ones(n_bags, dtype=torch.int64, device=device))
+    fnd[torch.cumsum(marks, 0)[:n] > 0] = 0
+    if pos.numel():
+        rows, f = find_kept(flat[pos].contiguous(), pos)
+        block[grad_index[pos].to(torch.int64)] = rows.to(block.device).to(out_dtype)
+        fnd[pos] = f.to(fnd.device).to(torch.uint8)
+    block = block.view(n_bags, max_len, dim)
+    if out is not None:
+        out.view(n_bags, max_len, dim).copy_(block)
+        block = out.view(n_bags, max_len, dim)
+    return (block, fnd, lengths, step_keys, grad_index) if with_step else (block, fnd, lengths)
+
+
 class SparseStep(NamedTuple):
     """One sparse optimizer step as a value: which optimizer and its scalars.  The table classes build it once per call and forward it; nothing
     else in the package tells the optimizers apart.  The fields stand in the order of apply_pooled / apply_indexed's loose form, so `*step` is it."""

@@ -55,6 +55,15 @@ def _pool_rows(rows: torch.Tensor, bag_offsets: torch.Tensor, mode: str) -> torc
     return out
 
 
+def _takes_grad_index(table) -> bool:
+    """the table's apply_adagrad declares grad_index (LookupTable's does; an adapter's need not)"""
+    import inspect
+    try:
+        return "grad_index" in inspect.signature(table.apply_adagrad).parameters
+    except (TypeError, ValueError):
+        return False
+
+
 class TieredLookupTable:
     weighted_bags = False   # no per_sample_weights over the pair (nn.DynamicEmbeddingBag refuses them)
     hot_cold_pair = True    # nn.DynamicEmbedding has no admitting forward over a pair
@@ -164,6 +173,31 @@ class TieredLookupTable:
                                                      None if (insert_missing and n) else found.data_ptr(), {"sum": 0, "mean": 1}[mode], flags,
                                                      hot._s()))
         return out, found
+
+    def find_padded(self, keys: torch.Tensor, bag_offsets: torch.Tensor, max_len: int, keep: str = "first", out: torch.Tensor | None = None,
+                    found: torch.Tensor | None = None, out_dtype: torch.dtype = torch.float32, with_step: bool = False):
+        """Padded sequence lookup over the pair (SPEC.md §3 "Tiering"): LookupTable.find_padded on the union of the two tiers, bit for bit ->
+        (out [n_bags, max_len, dim], per-key found, lengths [n_bags]) and, with_step=True, (step_keys [n], grad_index [n]) for apply_*(grad_index=).
+        A kept position reads the hot table's row, else the cold table's, else the HOT table's default row; a cut-off position is not probed.
+        Two native tables: ONE launch (mee_find_padded_tiered), which feeds the placement policy's hit counters like find_pooled does (cold hits
+        always, hot hits on every sample_every-th call; a cut-off position counts nothing).  Other tiers: find on the kept keys, placed into a
+        zeroed block."""
+        if not self._native():
+            from .table import _find_padded_composed
+            return _find_padded_composed(lambda kk, pos: self.find(kk), self.dim, keys, bag_offsets, max_len, keep, out, found, out_dtype, with_step)
+        from . import _lib
+        from .table import _find_padded, _n_bags
+        hot, cold = self.hot, self.cold
+        k = hot._keys(keys) if keys.numel() else keys
+        n_bags = _n_bags(bag_offsets, hot.device)
+
+        def launch(h, *args):   # _find_padded's call with the cold table and the count bits put in: (hot, cold, ..., flags, count_flags, ...)
+            count = 0
+            if self.policy:   # (here, behind _find_padded's checks: a refused call is not one of the policy's calls)
+                self._calls += 1
+                count = _lib.TIER_COUNT_COLD | (_lib.TIER_COUNT_HOT if self._calls % self.sample_every == 0 else 0)
+            return _lib.lib().mee_find_padded_tiered(h, cold._h, *args[:6], count, *args[6:])
+        return _find_padded(launch, hot._h, hot.device, self.dim, k, bag_offsets, n_bags, n_bags, max_len, keep, out, found, out_dtype, with_step)
 
     def rebalance(self, max_moves: int = 1 << 20) -> tuple[int, int]:
         """One policy step: promote cold keys hit >= promote_threshold times since the last call, demoting untouched hot
@@ -283,6 +317,11 @@ class TieredLookupTable:
         # a key lives in one tier and each table ignores keys it does not hold: both see the whole batch.  grad_index (one int per key: position i
         # takes row grad_index[i] of grads — a pooled lookup's bag) goes to both as well; a key's duplicates are reduced in the one tier that holds it
         kw = {} if grad_index is None else {"grad_index": grad_index}
+        if grad_index is not None and not all(_takes_grad_index(t) for t in (self.hot, self.cold)):
+            # only for tiers whose apply_* have no grad_index (plain adapters; whichever lookup the index came from, padded or pooled): the rows
+            # gathered here, padding (EMPTY) left out.  Tiers that take the index — native tables, adapters that declare it — get it as before
+            live = keys != -(1 << 63)
+            keys, grads, kw = keys[live], grads[grad_index[live].to(torch.int64)], {}
         step.apply_to(self.hot, keys, grads, **kw)
         step.apply_to(self.cold, keys, grads, **kw)
         self._after_optimizer_step()
@@ -772,6 +811,39 @@ class TieredTableGroup:
         _lib.check(_lib.lib().mee_group_find_tiered(self.hot_group._h, self.cold_group._h, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), dt,
                                                     found.data_ptr(), self._count_flags(), _stream_ptr(self.device)))
         return out, found
+
+    def find_padded(self, keys: torch.Tensor, bag_offsets: torch.Tensor, max_len: int, keep: str = "first", out: torch.Tensor | None = None,
+                    found: torch.Tensor | None = None, out_dtype: torch.dtype = torch.float32, with_step: bool = False):
+        """TieredLookupTable.find_padded of every pair on its bags_per_table bags, in ONE launch (mee_group_find_padded_tiered) ->
+        (out [n_tables * bags_per_table, max_len, dim], found [n], lengths) and, with_step=True, (step_keys, grad_index) for apply_indexed.  An absent
+        key reads its member's HOT table's default row.  With the policy on the launch feeds the members' hit counters (cold hits always, hot hits on
+        every sample_every-th call; a cut-off position counts nothing).  Pairs that are not native tables: member j's find on its kept keys, placed
+        into a zeroed block."""
+        if not self._native:
+            from .table import _find_padded_composed
+            flat = keys.contiguous().view(-1)
+            bpt, members = self._member_slices(bag_offsets, flat.numel())
+
+            def find_kept(kk, pos):   # the kept keys are in position order: member j's are those inside its key slice
+                rows = torch.zeros((kk.numel(), self.dim), dtype=torch.float32, device=kk.device)
+                fnd = torch.zeros(kk.numel(), dtype=torch.uint8, device=kk.device)
+                for pair, (_, s, e) in zip(self.tables, members):
+                    m = (pos >= s) & (pos < e)
+                    if bool(m.any()):
+                        r, f = pair.find(kk[m])
+                        rows[m], fnd[m] = r.to(rows.device), f.to(fnd.device).to(torch.uint8)
+                return rows, fnd
+            return _find_padded_composed(find_kept, self.dim, flat, bag_offsets, max_len, keep, out, found, out_dtype, with_step)
+        from . import _lib
+        from .table import _find_padded
+        bpt = self.hot_group._check_bags(bag_offsets)
+        k = self.tables[0].hot._keys(keys) if keys.numel() else keys
+        cold = self.cold_group._h
+
+        def launch(h, *args):   # _find_padded's call with the cold group and the count bits put in: (hot, cold, ..., flags, count_flags, ...)
+            return _lib.lib().mee_group_find_padded_tiered(h, cold, *args[:6], self._count_flags(), *args[6:])
+        return _find_padded(launch, self.hot_group._h, self.device, self.dim, k, bag_offsets, bpt * len(self.tables), bpt, max_len, keep, out, found, out_dtype,
+                            with_step)
 
     def find_or_insert(self, keys: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
                        out_dtype: torch.dtype = torch.float32, min_count=None):
