@@ -18,7 +18,8 @@ n_tables, dim, batch, ids_per_bag, vocab = 26, 64, 2048, 5, 10**6
 tables = [LookupTable(2 * vocab, dim, device=dev, optimizer=OPT_ADAGRAD, max_batch=1 << 18, initializer=INIT_UNIFORM,
                       init_scale=0.05, init_seed=j) for j in range(n_tables)]
 group = TableGroup(tables, max_apply_batch=n_tables * batch * 2 * ids_per_bag)   # an upper bound on the ids of one step
-sparse = DynamicEmbeddingBag(group, mode="sum", optimizer="adagrad", lr=0.05, create_missing=True).to(dev)   # bag b -> table b // batch; new ids enter their tables in forward
+# bag b -> table b // batch; new ids enter their tables in forward; layout="keyed": forward returns the [batch, n_tables * dim] block the dense net reads
+sparse = DynamicEmbeddingBag(group, mode="sum", optimizer="adagrad", lr=0.05, create_missing=True, layout="keyed").to(dev)
 dense = torch.nn.Sequential(torch.nn.Linear(n_tables * dim, 256), torch.nn.ReLU(), torch.nn.Linear(256, 1)).to(dev)
 dense_opt = torch.optim.SGD(dense.parameters(), lr=0.01)
 
@@ -28,10 +29,9 @@ for step in range(5):
     offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(lens, 0)])
     ids = torch.randint(0, vocab, (int(offsets[-1]),), device=dev)
     labels = torch.rand(batch, 1, device=dev)
-    pooled = sparse(ids, offsets)                                        # [n_tables * batch, dim]: 3 launches create new ids, ONE does the pooled lookup
-    features = pooled.view(n_tables, batch, dim).transpose(0, 1).reshape(batch, n_tables * dim)
+    features = sparse(ids, offsets)                                      # [batch, n_tables * dim]: 3 launches create new ids, ONE does the pooled lookup and writes this block
     loss = torch.nn.functional.binary_cross_entropy_with_logits(dense(features), labels)
     dense_opt.zero_grad()
-    loss.backward()                                                      # the sparse update (7 launches) happens in here
+    loss.backward()                                                      # the sparse update happens in here, on the features' gradient where it lies
     dense_opt.step()
     print(f"step {step}: loss {loss.item():.4f}, ids {ids.numel()}, keys stored {sum(t.size() for t in tables)}")

@@ -1,5 +1,6 @@
 """Train -> serve for a recommender's sparse part on one MI355X: a collection trained in fp32 is copied into bf16-row tables, half the row
-bytes per key, and served by ONE pooled lookup launch that writes bf16 bag rows (run on the GPU box: python examples/serve_collection.py)."""
+bytes per key, and served by ONE pooled lookup launch that writes bf16 bag rows straight into the columns of a preallocated feature block (run on
+the GPU box: python examples/serve_collection.py)."""
 import os
 import sys
 
@@ -33,10 +34,13 @@ for step in range(3):
 
 serve = train.serving_copy()                                             # 26 bf16-row tables in a group of their own; `train` is untouched
 ids, offsets = request()
-pooled, found = serve.find_pooled(ids, offsets, mode="sum", out_dtype=torch.bfloat16)   # ONE launch for the 26 tables, bf16 bag rows
-want, _ = train.find_pooled(ids, offsets, mode="sum")
-features = pooled.view(n_tables, batch, dim).transpose(0, 1).reshape(batch, n_tables * dim)   # what the bf16 dense layers take
-print(f"served {ids.numel()} ids in {pooled.shape[0]} bags -> features {tuple(features.shape)} {features.dtype}, {int(found.sum())} ids known; "
-      f"max |bf16-row sum - fp32 sum| = {(pooled.float() - want).abs().max().item():.3g}")
+# the server's feature block, allocated once: 16 dense features in front, then the sparse part — the lookup writes its columns in place
+n_dense = 16
+feature_block = torch.zeros((batch, n_dense + n_tables * dim), dtype=torch.bfloat16, device=dev)
+sparse_part = feature_block[:, n_dense:]                                 # a strided view: stride(1) == 1, row stride = the block's width
+_, found = serve.find_pooled(ids, offsets, mode="sum", out=sparse_part, out_dtype=torch.bfloat16, layout="keyed")   # ONE launch for the 26 tables
+want, _ = train.find_pooled(ids, offsets, mode="sum", layout="keyed")    # the trained fp32 rows, the same [batch, n_tables * dim] layout
+print(f"served {ids.numel()} ids in {n_tables * batch} bags -> features {tuple(feature_block.shape)} {feature_block.dtype}, {int(found.sum())} ids known; "
+      f"max |bf16-row sum - fp32 sum| = {(sparse_part.float() - want).abs().max().item():.3g}; dense columns untouched: {bool((feature_block[:, :n_dense] == 0).all())}")
 print(f"table_bytes: trained fp32 group {sum(t.table_bytes for t in train.tables)} (+ optimizer state), "
       f"bf16-row serving group {sum(t.table_bytes for t in serve.tables)}; keys stored {sum(t.size() for t in serve.tables)}")

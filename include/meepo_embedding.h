@@ -705,6 +705,46 @@ int mee_mixed_group_apply_adam_pooled(mee_mixed_group* g, const int64_t* d_keys,
                                       size_t n, float lr, float beta1, float beta2, float eps, uint64_t step, void* stream);
 int mee_mixed_group_set_tuning(mee_mixed_group* g, const char* name, int value);   /* forwarded to every class's apply */
 
+/* ---- keyed output of the pooled group lookups (SPEC.md §3 "Keyed output") ------------------------------------------------------
+ * The table-major lookups above write bag b = j * B + s (member j's sample s, B = bags_per_table, T = n_tables) as row b.  The keyed forms write
+ * the SAME pooled rows, bit for bit, one row per sample with the members side by side, which is what a dense network reads:
+ *     out[s * out_row_stride + col_j ... + dim_j)    col_j = the sum of dim_i over the members i < j in the caller's order (j * dim for a uniform group)
+ * out_row_stride is in ELEMENTS, a multiple of 4, at least the width W = col_T; 0 means W.  A larger stride writes into a wider feature row: the
+ * columns outside [0, W) of a row are never written.  d_out must be 16-byte aligned for fp32, 8-byte for bf16.
+ * d_step_index_out (nullable, uint32 [n]): for every key position a bag covers, the row of the gradient that the pooled step reads for it —
+ *     s * T + j  (uniform and tiered groups): mee_group_apply_*_pooled takes the keyed gradient [B, T * dim] (contiguous) AS IT IS, viewed [B * T, dim],
+ *                with this array as d_grad_index — no gradient copy;
+ *     b          (mixed groups): d_bag_of_position of mee_mixed_group_apply_*_pooled, whose class-major d_bag_grads mee_mixed_group_keyed_grads makes.
+ * Positions no bag covers are not written.  d_found, d_located(_out), mode, insert_missing and flags are the table-major sibling's.
+ *   mee_group_find_pooled_keyed          = mee_group_find_pooled_as without weights (fp32-row and bf16-row groups)
+ *   mee_group_find_pooled_tiered_keyed   = mee_group_find_pooled_tiered, hit counting included; no located rows, as there
+ *   mee_mixed_group_find_pooled_keyed    = mee_mixed_group_find_pooled
+ *   mee_mixed_group_keyed_layout         host only: col_offsets[n_tables] (nullable) and W (nullable), in elements
+ *   mee_mixed_group_keyed_grads          one launch: the keyed gradient [B, row_stride] (in_dtype MEE_DTYPE_F32 or MEE_DTYPE_BF16, widened) taken apart
+ *                                        into the class-major fp32 buffer d_bag_grads_out (mee_mixed_group_layout); MEE_POOL_MEAN divides row b by
+ *                                        (float)max(d_bag_offsets[b + 1] - d_bag_offsets[b], 1) (d_bag_offsets is read with MEE_POOL_MEAN only)
+ * MEE_ERR_INVALID_ARG, before anything is launched or written: a null pointer where rows are due, an unknown mode or dtype, a stride below W or not a
+ * multiple of 4, a misaligned d_out, T * B >= 2^32 with d_step_index_out.  MEE_ERR_UNSUPPORTED wherever the sibling is (d_located_out or
+ * d_step_index_out on a bf16-row group: both serve a backward).  bags_per_table == 0 succeeds and writes nothing.  Sync-free and capturable.
+ * No weighted, jagged, sharded or single-table form (a single table's [n_bags, dim] is keyed already). */
+int mee_group_find_pooled_keyed(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out,
+                                uint32_t out_dtype, size_t out_row_stride, uint8_t* d_found, int64_t* d_located_out /* nullable */,
+                                uint32_t* d_step_index_out /* nullable */, int mode, void* stream);
+int mee_group_find_pooled_tiered_keyed(mee_group* hot_group, mee_group* cold_group, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets,
+                                       size_t bags_per_table, void* d_out, uint32_t out_dtype, size_t out_row_stride, uint8_t* d_found,
+                                       uint32_t* d_step_index_out /* nullable */, int mode, uint32_t flags, void* stream);
+/* (the mixed group's three: the return type on a line of its own — tests/test_mixed_groups.py pins the list of the class-major operators, which it
+ * reads off the one-line declarations above) */
+int
+mee_mixed_group_find_pooled_keyed(mee_mixed_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                                      void* d_out, uint32_t out_dtype, size_t out_row_stride, uint8_t* d_found, int64_t* d_located /* nullable */,
+                                      uint32_t* d_step_index_out /* nullable */, int mode, int insert_missing, void* stream);
+int
+mee_mixed_group_keyed_layout(const mee_mixed_group* g, uint64_t* col_offsets /* [n_tables], nullable */, uint64_t* width /* nullable */);
+int
+mee_mixed_group_keyed_grads(mee_mixed_group* g, const void* d_keyed_grads, uint32_t in_dtype, size_t row_stride, size_t bags_per_table,
+                                const uint64_t* d_bag_offsets /* MEE_POOL_MEAN only */, int mode, float* d_bag_grads_out, void* stream);
+
 /* ---- sparse optimizers (north_star "sparse-optimizer (Adagrad/Adam) scatter-update"; SPEC.md §4) -------- */
 int mee_apply_adagrad(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, float lr, float eps,
                       void* stream);

@@ -208,6 +208,15 @@ public:
     void find_padded_as(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, size_t max_len, uint32_t flags, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, uint8_t* d_found = nullptr, int64_t* d_lengths_out = nullptr, int64_t* d_step_keys_out = nullptr, uint32_t* d_grad_index_out = nullptr, void* stream = nullptr) {
         check(mee_group_find_padded_as(g_, d_keys, n, d_bag_offsets, bags_per_table, max_len, flags, d_out, out_dtype, d_found, d_lengths_out, d_step_keys_out, d_grad_index_out, stream));
     }
+    // the keyed layout: one row per sample, the members' pooled vectors side by side ([bags_per_table, n_tables * dim]; out_row_stride in elements, 0 = that
+    // width); d_step_index_out = the d_grad_index with which apply_*_pooled reads the keyed gradient in place (mee_group_find_pooled_keyed)
+    void find_pooled_keyed(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, size_t out_row_stride = 0, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, uint32_t* d_step_index_out = nullptr, int mode = MEE_POOL_SUM, void* stream = nullptr) {
+        check(mee_group_find_pooled_keyed(g_, d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, out_row_stride, d_found, d_located_out, d_step_index_out, mode, stream));
+    }
+    // ... over a collection of hot/cold pairs (mee_group_find_pooled_tiered_keyed)
+    void find_pooled_tiered_keyed(Group& cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, size_t out_row_stride = 0, uint8_t* d_found = nullptr, uint32_t* d_step_index_out = nullptr, int mode = MEE_POOL_SUM, uint32_t flags = 0, void* stream = nullptr) {
+        check(mee_group_find_pooled_tiered_keyed(g_, cold.g_, d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, out_row_stride, d_found, d_step_index_out, mode, flags, stream));
+    }
     void set_tuning(const char* name, int value) { check(mee_group_set_tuning(g_, name, value)); }   // knobs of the group's own apply; never change results
     void apply_adagrad(const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr, float eps = 1e-10f, void* stream = nullptr) {
         check(mee_group_apply_adagrad(g_, d_keys, d_offsets, d_grads, n, lr, eps, stream));
@@ -298,6 +307,19 @@ public:
     }
     void apply_adam_pooled(const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_bag_grads, const uint32_t* d_bag_of_position, const int64_t* d_located, size_t n, float lr, uint64_t step, float beta1 = 0.9f, float beta2 = 0.999f, float eps = 1e-8f, void* stream = nullptr) {
         check(mee_mixed_group_apply_adam_pooled(g_, d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_bag_of_position, d_located, n, lr, beta1, beta2, eps, step, stream));
+    }
+    // the keyed layout: member j's pooled vector at column col_offsets[j] of its sample's row (mee_mixed_group_keyed_layout -> the row's width in elements)
+    uint64_t keyed_layout(uint64_t* col_offsets = nullptr) const {
+        uint64_t width = 0;
+        check(mee_mixed_group_keyed_layout(g_, col_offsets, &width));
+        return width;
+    }
+    void find_pooled_keyed(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, size_t out_row_stride = 0, uint8_t* d_found = nullptr, int64_t* d_located = nullptr, uint32_t* d_step_index_out = nullptr, int mode = MEE_POOL_SUM, bool insert_missing = false, void* stream = nullptr) {
+        check(mee_mixed_group_find_pooled_keyed(g_, d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, out_row_stride, d_found, d_located, d_step_index_out, mode, insert_missing, stream));
+    }
+    // the keyed gradient taken apart into the class-major fp32 buffer the step reads (mee_mixed_group_keyed_grads; d_bag_offsets with MEE_POOL_MEAN only)
+    void keyed_grads(const void* d_keyed_grads, uint32_t in_dtype, size_t row_stride, size_t bags_per_table, const uint64_t* d_bag_offsets, int mode, float* d_bag_grads_out, void* stream = nullptr) {
+        check(mee_mixed_group_keyed_grads(g_, d_keyed_grads, in_dtype, row_stride, bags_per_table, d_bag_offsets, mode, d_bag_grads_out, stream));
     }
     void set_tuning(const char* name, int value) { check(mee_mixed_group_set_tuning(g_, name, value)); }
 private:

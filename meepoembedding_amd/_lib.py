@@ -149,6 +149,14 @@ PROTOTYPES = {
     "mee_mixed_group_apply_adagrad_pooled": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _f32, _f32, _vp]),
     "mee_mixed_group_apply_adam_pooled": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32, _u64, _vp]),
     "mee_mixed_group_set_tuning": (C.c_int, [_vp, C.c_char_p, C.c_int]),
+    # keyed output of the pooled group lookups ([bags_per_table, sum of dims]): ..., out, out_dtype, out_row_stride (elements; 0 = the width), found,
+    # [located,] step_index, mode, [insert_missing | flags,] stream
+    "mee_group_find_pooled_keyed": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _u32, _sz, _vp, _vp, _vp, C.c_int, _vp]),
+    "mee_group_find_pooled_tiered_keyed": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _sz, _vp, _vp, C.c_int, _u32, _vp]),
+    "mee_mixed_group_find_pooled_keyed": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _u32, _sz, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "mee_mixed_group_keyed_layout": (C.c_int, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    # the keyed gradient taken apart into the class-major step buffer: group, keyed grads, in_dtype, row_stride, bags_per_table, bag offsets (mean), mode, out, stream
+    "mee_mixed_group_keyed_grads": (C.c_int, [_vp, _vp, _u32, _sz, _sz, _vp, C.c_int, _vp, _vp]),
     "mee_find_pooled": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, C.c_int, _vp]),
     "mee_find_pooled_weighted": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "mee_find_pooled_tiered": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, C.c_int, _u32, _vp]),   # a hot/cold pair (tiered.py)

@@ -640,6 +640,36 @@ __device__ __forceinline__ void pooled_bags(uint64_t bag0, uint32_t nvalid, uint
     }
 }
 
+// ---- the keyed layout of the pooled group lookups (SPEC.md §3 "Keyed output") ---------------------------------------------------------
+// What a keyed launch gets beside the table-major launch's arguments: the output's row stride in element groups (float4 for fp32, 8 bytes for bf16),
+// the step index array (nullable) and the two factors of its value, step = sample * step_sample + member * step_member — (T, 1) for the uniform
+// step, which reads the keyed gradient as [B * T, dim]; (1, B) = the bag itself for a mixed group's.
+struct KeyedOut {
+    uint64_t stride4;
+    uint32_t* step_index;
+    uint64_t step_sample, step_member;
+};
+// a kernel's last argument T with KeyedOut behind it (KEYED), or T itself: the table-major instances keep their argument list
+template <class T> struct WithKeyed : T { KeyedOut keyed; };
+template <bool KEYED, class T> using KeyedArg = std::conditional_t<KEYED, WithKeyed<T>, T>;
+
+// The step index of the bags one wave serves in one step (pooled_bags' geometry: BPW = 4, tile t has bag0 + t; BPW = 1, the wave has bag0): every key
+// position the bag covers — its span as the walk clamps it (pooled_span) — gets the bag's `row`, 16 (64) consecutive positions per store.  Written
+// beside the walk, not inside it: pooled_bags and the instances without a step index stay the code they were.  row_of_bag(b) -> uint32_t.
+template <int BPW, class RowOfBag>
+__device__ __forceinline__ void keyed_step_index(uint64_t bag0, uint32_t nvalid, const uint64_t* __restrict__ offsets, uint64_t n_keys, int tile, int tl,
+                                                 uint32_t* __restrict__ step_index, RowOfBag&& row_of_bag) {
+    const uint64_t bag = BPW == 4 ? bag0 + tile : bag0;
+    const bool has = BPW == 4 ? (uint32_t)tile < nvalid : true;
+    uint64_t begin = has ? offsets[bag] : 0, end = has ? offsets[bag + 1] : 0;
+    end = end < n_keys ? end : n_keys;
+    begin = begin < end ? begin : end;
+    if (begin == end) return;
+    const uint32_t row = row_of_bag(bag);
+    const int lanes = BPW == 4 ? 16 : 64, l = BPW == 4 ? tl : tile * 16 + tl;
+    for (uint64_t i = begin + l; i < end; i += lanes) step_index[i] = row;
+}
+
 // SPEC.md §3 "Initial row", four consecutive elements starting at j0
 __device__ __forceinline__ float4 initial_row4(int64_t key, uint32_t j0, uint32_t initializer, float init_scale,
                                                uint64_t init_seed, float default_value) {

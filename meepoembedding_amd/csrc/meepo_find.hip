@@ -363,8 +363,13 @@ __device__ __forceinline__ bool jagged_member(const uint64_t* __restrict__ membe
 // BROWS (one bf16-row table, or with GROUPED a bf16-row group — every member's plane, JAGGED included; unweighted: SPEC.md §3 "Row
 // storage type"): the value planes hold bf16 rows.  One storage type per group, so this is a property of the launch, never a per-member
 // branch in the fetch.
+// KEYED (mee_group_find_pooled_keyed / mee_group_find_pooled_tiered_keyed; a uniform group or a group of pairs, unweighted, no jagged map: SPEC.md §3
+// "Keyed output"): bag b = member j's sample s (j = b / bags_per_table) is written to out[s * stride4 + j * dim4 ...] — one row per sample, the members'
+// pooled vectors side by side — instead of out[b * dim4 ...], and tier.keyed (KeyedOut, meepo_device.h) also brings the step index, written per wave step
+// beside the walk.  Only row_of differs inside it: the order of the additions and the mean's division are the table-major instances'.  KeyedOut rides
+// behind the last argument (KeyedArg), so the table-major instances keep their argument list as it was.
 // (GroupTier and group_pair_tables, the pair of a member: meepo_table_int.h — the padded lookup of a group of pairs reads them too)
-template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false, bool JAGGED = false, bool TIERED = false, bool BROWS = false>
+template <int DIM4, int U, int BPW, bool GROUPED = false, bool WEIGHTED = false, bool BF16 = false, bool JAGGED = false, bool TIERED = false, bool BROWS = false, bool KEYED = false>
 __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restrict__ tkeys_, const float4* __restrict__ values_,
                                                           uint64_t nb_, const int64_t* __restrict__ keys,
                                                           const uint64_t* __restrict__ offsets, uint64_t n_bags,
@@ -373,8 +378,9 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                                                           uint64_t bags_per_table = 1, int64_t* __restrict__ located = nullptr,
                                                           uint64_t n_keys = ~0ull, const float* __restrict__ weights = nullptr,
                                                           int64_t handle_tag = 0, const uint64_t* __restrict__ member_bags = nullptr,
-                                                          uint32_t n_members = 0, std::conditional_t<GROUPED && TIERED, GroupTier, TierArgs> tier = {}) {
+                                                          uint32_t n_members = 0, KeyedArg<KEYED, std::conditional_t<GROUPED && TIERED, GroupTier, TierArgs>> tier = {}) {
     static_assert(!JAGGED || (GROUPED && !WEIGHTED && !BF16), "the jagged map is the group's plain fp32 lookup");
+    static_assert(!KEYED || (GROUPED && !WEIGHTED && !JAGGED), "the keyed layout is the plain sum / mean of a group with bags_per_table bags per member");
     static_assert(!TIERED || (!WEIGHTED && (!JAGGED || GROUPED)), "the tiered form is the plain sum / mean of one pair or of a group of pairs (the group's also with a jagged map)");
     static_assert(!BROWS || (!WEIGHTED && !TIERED), "bf16 rows: the plain sum / mean of one table or of a bf16-row group (jagged map included)");
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
@@ -396,8 +402,18 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
             return true;
         }
     };
-    auto row_of = [&](uint64_t b) { return b * dim4; };
+    auto row_of = [&](uint64_t b) {
+        if constexpr (KEYED) { const uint64_t j = b / bags_per_table; return (b - j * bags_per_table) * tier.keyed.stride4 + j * dim4; }   // sample b mod B, member b / B
+        else return b * dim4;
+    };
     for (uint64_t b0 = wave * BPW; b0 < n_bags; b0 += n_waves * BPW) {
+        if constexpr (KEYED) {   // the step index of this step's bags, beside the walk (keyed_step_index, meepo_device.h)
+            if (tier.keyed.step_index)   // kernel-uniform
+                keyed_step_index<BPW>(b0, (uint32_t)(n_bags - b0 < BPW ? n_bags - b0 : BPW), offsets, n_keys, tile, tl, tier.keyed.step_index, [&](uint64_t b) {
+                    const uint64_t j = b / bags_per_table;
+                    return (uint32_t)((b - j * bags_per_table) * tier.keyed.step_sample + j * tier.keyed.step_member);
+                });
+        }
         if constexpr (GROUPED && TIERED) {
             auto pair_of = [&](uint64_t b, PooledTable& t, TierArgs& cold) {   // the hot and the cold table of bag b's member
                 uint64_t member;
@@ -485,7 +501,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                         if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
                             float4 v = acc[c];
                             if (mean && end > begin) { v.x = v.x / len; v.y = v.y / len; v.z = v.z / len; v.w = v.w / len; }
-                            if constexpr (BF16) store_bf16x4<true>(out, bag * dim4 + c * 16 + tl, v); else out[bag * dim4 + c * 16 + tl] = v;
+                            if constexpr (BF16) store_bf16x4<true>(out, row_of(bag) + c * 16 + tl, v); else out[row_of(bag) + c * 16 + tl] = v;
                         }
                 }
             }
@@ -540,7 +556,7 @@ __global__ __launch_bounds__(256) void find_pooled_kernel(const int64_t* __restr
                         if (DIM4 != 0 || (uint32_t)(c * 16 + tl) < dim4) {
                             float4 v = acc[c];
                             if (mean && eq > bq) { v.x = v.x / len; v.y = v.y / len; v.z = v.z / len; v.w = v.w / len; }
-                            if constexpr (BF16) store_bf16x4<true>(out, (b0 + q) * dim4 + c * 16 + tl, v); else out[(b0 + q) * dim4 + c * 16 + tl] = v;
+                            if constexpr (BF16) store_bf16x4<true>(out, row_of(b0 + q) + c * 16 + tl, v); else out[row_of(b0 + q) + c * 16 + tl] = v;
                         }
                 }
             }
@@ -1136,6 +1152,88 @@ int mee_group_find_pooled_tiered_jagged(mee_group* hot, mee_group* cold, const i
             nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, hot->dim4, mode == MEE_POOL_MEAN, hot->d_desc, 1,
             nullptr, n, nullptr, 0, d_member_bags, hot->n_tables, tier);
     });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+}  // extern "C"
+
+// ---- the keyed layout (SPEC.md §3 "Keyed output"): out[s, j * dim ...] = the pooled row of member j's sample s, one row per sample --------------
+// What every keyed entry point checks about its output before anything is launched or written; -> the row stride in element groups.
+// width = the elements a row holds (T * dim, a mixed group's sum of dims); out_row_stride in elements, 0 = width.
+int mee::keyed_out_check(const char* name, uint64_t width, uint64_t n_tables, uint64_t bags_per_table, const void* d_out, uint32_t out_dtype,
+                         uint64_t out_row_stride, bool want_index, uint64_t* stride4) {
+    if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
+    if (out_dtype == MEE_DTYPE_F32 && ((uintptr_t)d_out & 15)) return fail(MEE_ERR_INVALID_ARG, "%s: an fp32 keyed output must be 16-byte aligned", name);
+    const uint64_t stride = out_row_stride ? out_row_stride : width;
+    if (stride < width || (stride & 3))
+        return fail(MEE_ERR_INVALID_ARG, "%s: out_row_stride = %llu elements must be a multiple of 4 and at least the row's width %llu", name,
+                    (unsigned long long)stride, (unsigned long long)width);
+    if (want_index && (bags_per_table > 0xFFFFFFFFull || n_tables * bags_per_table >= (1ull << 32)))
+        return fail(MEE_ERR_INVALID_ARG, "%s: the step index is 32 bits: n_tables * bags_per_table must stay below 2^32", name);
+    *stride4 = stride / 4;
+    return MEE_OK;
+}
+
+int mee::group_find_pooled_keyed(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out,
+                                 uint32_t out_dtype, uint64_t out_row_stride, uint8_t* d_found, int64_t* d_located_out, uint32_t* d_step_index_out,
+                                 bool index_by_bag, int mode, void* stream, const char* name) {
+    if (g && d_located_out) MEE_FP32_GROUP_ONLY(g, name, "d_located_out (the located rows serve the backward) is");
+    if (g && d_step_index_out) MEE_FP32_GROUP_ONLY(g, name, "d_step_index_out (the step index serves the backward) is");
+    if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "%s: mode must be MEE_POOL_SUM or MEE_POOL_MEAN", name);
+    uint64_t stride4 = 0;
+    if (int rc = keyed_out_check(name, (uint64_t)g->n_tables * g->dim4 * 4, g->n_tables, bags_per_table, d_out, out_dtype, out_row_stride, d_step_index_out != nullptr, &stride4)) return rc;
+    if (bags_per_table == 0) return MEE_OK;
+    if (int rc = group_refresh(g, stream)) return rc;
+    DeviceGuard guard(g->device);
+    hipStream_t st = as_stream(stream);
+    const uint64_t n_bags = (uint64_t)g->n_tables * bags_per_table;
+    const KeyedOut keyed{stride4, d_step_index_out, index_by_bag ? 1ull : g->n_tables, index_by_bag ? (uint64_t)bags_per_table : 1ull};
+    with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) { with_flag(g->bf16_rows, [&](auto brows) {
+        find_pooled_kernel<d4, u, bpw, true, false, bf16, false, false, brows, true><<<grid, 256, 0, st>>>(
+            nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, mode == MEE_POOL_MEAN, g->d_desc, bags_per_table,
+            d_located_out, n, nullptr, 0, nullptr, 0, WithKeyed<TierArgs>{{}, keyed});
+    }); }); });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+extern "C" {
+
+int mee_group_find_pooled_keyed(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out,
+                                uint32_t out_dtype, size_t out_row_stride, uint8_t* d_found, int64_t* d_located_out, uint32_t* d_step_index_out, int mode,
+                                void* stream) {
+    MEE_RANGE("mee_group_find_pooled_keyed");
+    return group_find_pooled_keyed(g, d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, out_row_stride, d_found, d_located_out, d_step_index_out,
+                                   false, mode, stream, "mee_group_find_pooled_keyed");
+}
+
+// mee_group_find_pooled_tiered with the keyed store: the same GROUPED && TIERED instances and keys in flight, KEYED
+int mee_group_find_pooled_tiered_keyed(mee_group* hot, mee_group* cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                                       void* d_out, uint32_t out_dtype, size_t out_row_stride, uint8_t* d_found, uint32_t* d_step_index_out, int mode,
+                                       uint32_t flags, void* stream) {
+    MEE_RANGE("mee_group_find_pooled_tiered_keyed");
+    const char* name = "mee_group_find_pooled_tiered_keyed";
+    if (!hot || !cold || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (int rc = tiered_groups_check(hot, cold, flags, name)) return rc;
+    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "%s: mode must be MEE_POOL_SUM or MEE_POOL_MEAN", name);
+    uint64_t stride4 = 0;
+    if (int rc = keyed_out_check(name, (uint64_t)hot->n_tables * hot->dim4 * 4, hot->n_tables, bags_per_table, d_out, out_dtype, out_row_stride, d_step_index_out != nullptr, &stride4)) return rc;
+    if (bags_per_table == 0) return MEE_OK;
+    if (int rc = group_refresh(hot, stream)) return rc;
+    if (int rc = group_refresh(cold, stream)) return rc;
+    DeviceGuard guard(hot->device);
+    hipStream_t st = as_stream(stream);
+    const uint64_t n_bags = (uint64_t)hot->n_tables * bags_per_table;
+    const GroupTier tier{cold->d_desc, hot->d_init, cold->d_init, flags};
+    const KeyedOut keyed{stride4, d_step_index_out, hot->n_tables, 1ull};
+    with_pooled_shape(hot->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
+        constexpr int ut = (bpw == 1 && u > 2) ? 2 : u;   // the keys in flight of mee_group_find_pooled_tiered
+        find_pooled_kernel<d4, ut, bpw, true, false, bf16, false, true, false, true><<<grid, 256, 0, st>>>(
+            nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, hot->dim4, mode == MEE_POOL_MEAN, hot->d_desc, bags_per_table,
+            nullptr, n, nullptr, 0, nullptr, 0, WithKeyed<GroupTier>{tier, keyed});
+    }); });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }

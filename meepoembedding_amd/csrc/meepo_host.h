@@ -197,4 +197,14 @@ int refuse_bf16_group(const mee_group* g, const char* op, const char* what = nul
 // both, only known count bits (MEE_TIER_COUNT_*) and the counters they need in EVERY member of that tier (MEE_ERR_INVALID_ARG).  Host only;
 // defined in meepo_group.hip.
 int tiered_groups_check(const mee_group* hot, const mee_group* cold, uint32_t count_flags, const char* name);
+// The keyed pooled lookups (SPEC.md §3 "Keyed output"; defined in meepo_find.hip).  keyed_out_check: what every keyed entry point checks about its output
+// before anything is launched or written — dtype and alignment (16 bytes for fp32, 8 for bf16), out_row_stride (elements; 0 = width) a multiple of 4 and
+// at least `width`, and n_tables * bags_per_table < 2^32 when a step index is asked for; -> the stride in element groups.
+// group_find_pooled_keyed: mee_group_find_pooled_keyed under the caller's name; index_by_bag: the step index holds the bag (a mixed group of one class,
+// whose step reads class-major gradient rows) instead of sample * n_tables + member.
+int keyed_out_check(const char* name, uint64_t width, uint64_t n_tables, uint64_t bags_per_table, const void* d_out, uint32_t out_dtype,
+                    uint64_t out_row_stride, bool want_index, uint64_t* stride4);
+int group_find_pooled_keyed(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out,
+                            uint32_t out_dtype, uint64_t out_row_stride, uint8_t* d_found, int64_t* d_located_out, uint32_t* d_step_index_out,
+                            bool index_by_bag, int mode, void* stream, const char* name);
 }

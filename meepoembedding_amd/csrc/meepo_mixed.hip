@@ -18,7 +18,12 @@ namespace mee {
 
 struct MixedDesc {   // per member, device resident, beside its GroupDesc / GroupInit (caller's member order)
     uint64_t off4;   // the sum of dim4 over the blocks before this member's: its block starts at float4 (bf16: 8-byte group) B * off4
-    uint32_t dim4, cls, rank, pad;
+    uint32_t dim4, cls, rank;
+    uint32_t col4;   // keyed layout (SPEC.md §3 "Keyed output"): the sum of dim4 over the members before this one in the CALLER's order — its column in a sample's row
+};
+struct KeyedMean {   // the last argument of the keyed lookup's instances
+    int mean;
+    KeyedOut keyed;
 };
 
 // The pooled lookup of a mixed group, one launch.  Waves are mapped to bags PER MEMBER: with BPW = 4 a member's B bags take Bp / 4 wave
@@ -30,11 +35,15 @@ struct MixedDesc {   // per member, device resident, beside its GroupDesc / Grou
 // dim4 <= 16 * CW; CW = 2 is the instance for groups whose run-time widths are all <= 128
 // (8, 16, 32, 100, ...): the run-time path then holds no more row registers than the dim-128 path (82 VGPRs, 5 waves per SIMD with four bags
 // per wave), and the launch picks it.  All instances beside the uniform group's: profiles/mixed_groups.md.
-template <int BPW, bool BF16, int CW>
+// KEYED (mee_mixed_group_find_pooled_keyed): member j's sample s goes to out[s * stride4 + col4_j ...] instead of its class-major block, and the walk also
+// writes the step index beside the walk — the bag itself, the row of the class-major gradient the step reads (KeyedOut, meepo_device.h).
+template <int BPW, bool BF16, int CW, bool KEYED = false>
 __global__ __launch_bounds__(256) void mixed_find_pooled_kernel(const GroupDesc* __restrict__ desc, const MixedDesc* __restrict__ mdesc, uint32_t n_tables,
                                                                 const int64_t* __restrict__ keys, const uint64_t* __restrict__ offsets,
                                                                 uint64_t bags_per_table, float4* __restrict__ out, uint8_t* __restrict__ found,
-                                                                int64_t* __restrict__ located, uint64_t n_keys, int mean) {
+                                                                int64_t* __restrict__ located, uint64_t n_keys, std::conditional_t<KEYED, KeyedMean, int> mean_) {
+    int mean;   // (the table-major instances keep their argument list: the keyed ones get KeyedOut behind the mean flag)
+    if constexpr (KEYED) mean = mean_.mean; else mean = mean_;
     const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
@@ -56,10 +65,18 @@ __global__ __launch_bounds__(256) void mixed_find_pooled_kernel(const GroupDesc*
             constexpr int C = d4 ? d4 / 16 : CW;
             constexpr int U = BPW == 4 ? RowShape<d4>::pooled_unroll_4 : RowShape<d4>::pooled_unroll_1;
             const uint32_t dim4 = d4 ? (uint32_t)d4 : md.dim4;
+            if constexpr (KEYED)
+                pooled_bags<d4, U, BPW, C, false, BF16, false, false, false>(
+                    bag0, nvalid, dim4, keys, offsets, n_keys, nullptr, out, found, located, mean, TierArgs{}, tile, tl,
+                    [&](uint64_t, PooledTable& bt) { bt = t; return true; }, [&](uint64_t b) { return (b - bag0 + local0) * mean_.keyed.stride4 + md.col4; });
+            else
             pooled_bags<d4, U, BPW, C, false, BF16, false, false, false>(
                 bag0, nvalid, dim4, keys, offsets, n_keys, nullptr, out, found, located, mean, TierArgs{}, tile, tl,
                 [&](uint64_t, PooledTable& bt) { bt = t; return true; }, [&](uint64_t b) { return row0 + (b - bag0) * dim4; });
         };
+        if constexpr (KEYED) {   // the step index of this step's bags: the bag itself (keyed_step_index, meepo_device.h)
+            if (mean_.keyed.step_index) keyed_step_index<BPW>(bag0, nvalid, offsets, n_keys, tile, tl, mean_.keyed.step_index, [](uint64_t b) { return (uint32_t)b; });
+        }
         if (md.dim4 == 16) bags(std::integral_constant<int, 16>{});
         else if (md.dim4 == 32) bags(std::integral_constant<int, 32>{});
         else bags(std::integral_constant<int, 0>{});
@@ -134,6 +151,38 @@ __global__ __launch_bounds__(256) void mixed_ensure_kernel(const GroupDesc* __re
                                       [&](uint32_t lo, bool) { return GroupMember{desc + lo, init + lo, mdesc[lo].dim4}; });
 }
 
+// The backward's side of the keyed layout: a keyed gradient [B, stride] (fp32, or BF16 widened — exact) is taken apart into the class-major fp32
+// blocks the step reads, member j's row s from in[s * stride4 + col4_j ...] to out[(B * off4_j + s * dim4_j) ...].  One tile per bag row, one element
+// group per lane and round.  MEAN: every element is divided by (float)max(len, 1), len = offsets[b + 1] - offsets[b] as the caller wrote them (a
+// division, not a multiplication by the reciprocal: what `g / lens.clamp(min=1)` gives).
+template <bool BF16>
+__global__ __launch_bounds__(256) void mixed_keyed_grads_kernel(const MixedDesc* __restrict__ mdesc, uint32_t n_tables, uint64_t bags_per_table,
+                                                                const void* __restrict__ in, uint64_t stride4, const uint64_t* __restrict__ offsets, int mean,
+                                                                float4* __restrict__ out) {
+    const uint64_t B = bags_per_table, n_bags = (uint64_t)n_tables * B;
+    const int tl = threadIdx.x & 15;
+    const uint64_t tile0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4, n_tiles = ((uint64_t)gridDim.x * blockDim.x) >> 4;
+    for (uint64_t b = tile0; b < n_bags; b += n_tiles) {
+        const uint64_t j = b / B, s = b - j * B;
+        const MixedDesc md = mdesc[j];
+        float len = 1.f;
+        if (mean) {
+            const int64_t l = (int64_t)(offsets[b + 1] - offsets[b]);
+            len = (float)(l > 1 ? l : 1);
+        }
+        const uint64_t src = s * stride4 + md.col4, dst = md.off4 * B + s * md.dim4;
+        for (uint32_t c = tl; c < md.dim4; c += 16) {
+            float4 v;
+            if constexpr (BF16) {
+                const f32x4 w = widen_bf16x4(reinterpret_cast<const u32x2*>(in)[src + c]);
+                v = make_float4(w.x, w.y, w.z, w.w);
+            } else v = reinterpret_cast<const float4*>(in)[src + c];
+            if (mean) { v.x = v.x / len; v.y = v.y / len; v.z = v.z / len; v.w = v.w / len; }
+            out[dst + c] = v;
+        }
+    }
+}
+
 }  // namespace mee
 
 using namespace mee;
@@ -158,11 +207,13 @@ static int mixed_upload(mee_mixed_group* g) {
     std::vector<GroupDesc> h(g->n_tables);
     std::vector<GroupInit> hi(g->n_tables);
     std::vector<MixedDesc> hm(g->n_tables);
+    uint32_t col4 = 0;
     for (uint32_t j = 0; j < g->n_tables; ++j) {
         const TableView v = table_view(g->tables[j]);
         h[j] = GroupDesc{v.keys, (float4*)v.values, (float4*)v.s1, (float4*)v.s2, v.nb, v.default_value, 0};
         hi[j] = GroupInit{v.init_seed, v.status, v.hits, v.initializer, v.optimizer, v.init_scale, v.init_acc};
-        hm[j] = MixedDesc{g->plan.off4[j], v.dim4, g->plan.cls[j], g->plan.rank[j], 0};
+        hm[j] = MixedDesc{g->plan.off4[j], v.dim4, g->plan.cls[j], g->plan.rank[j], col4};
+        col4 += v.dim4;
         g->generations[j] = v.generation;
     }
     MEE_HIP(hipMemcpy(g->d_desc, h.data(), h.size() * sizeof(GroupDesc), hipMemcpyHostToDevice));  // synchronous, rare
@@ -295,6 +346,84 @@ int mee_mixed_group_find_pooled(mee_mixed_group* g, const int64_t* d_keys, size_
         mixed_find_pooled_kernel<wpb ? 1 : 4, bf16, cw><<<grid_for(units, 4, 1u << 20), 256, 0, st>>>(g->d_desc, g->d_mdesc, g->n_tables, d_keys, d_bag_offsets, B, (float4*)d_out,
                                                                                                   d_found, d_located, n, mode == MEE_POOL_MEAN);
     }); }); });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+// ---- the keyed layout (SPEC.md §3 "Keyed output"): one row per sample, member j's pooled vector at column col_j = the sum of the dims before it ----
+static uint64_t mixed_width(const mee_mixed_group* g) {
+    uint64_t w = 0;
+    for (mee_table* t : g->tables) w += (uint64_t)table_view(t).dim4 * 4;
+    return w;
+}
+
+int mee_mixed_group_keyed_layout(const mee_mixed_group* g, uint64_t* col_offsets, uint64_t* width) {
+    if (!g) return fail(MEE_ERR_INVALID_ARG, "mee_mixed_group_keyed_layout: null group");
+    uint64_t w = 0;
+    for (uint32_t j = 0; j < g->n_tables; ++j) {
+        if (col_offsets) col_offsets[j] = w;
+        w += (uint64_t)table_view(g->tables[j]).dim4 * 4;
+    }
+    if (width) *width = w;
+    return MEE_OK;
+}
+
+int mee_mixed_group_find_pooled_keyed(mee_mixed_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                                      void* d_out, uint32_t out_dtype, size_t out_row_stride, uint8_t* d_found, int64_t* d_located,
+                                      uint32_t* d_step_index_out, int mode, int insert_missing, void* stream) {
+    MEE_RANGE("mee_mixed_group_find_pooled_keyed");
+    const char* name = "mee_mixed_group_find_pooled_keyed";
+    if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "%s: mode must be MEE_POOL_SUM or MEE_POOL_MEAN", name);
+    if (insert_missing && n && !d_found) return fail(MEE_ERR_INVALID_ARG, "%s: insert_missing needs d_found (the present-before mask)", name);
+    uint64_t stride4 = 0;
+    if (int rc = keyed_out_check(name, mixed_width(g), g->n_tables, bags_per_table, d_out, out_dtype, out_row_stride, d_step_index_out != nullptr, &stride4)) return rc;
+    if (bags_per_table == 0) return MEE_OK;
+    if (int rc = mixed_refresh(g, stream)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t B = bags_per_table;
+    if (insert_missing && n) {   // as mee_mixed_group_find_pooled: the present-before mask, then the creation pass; the lookup leaves the mask alone
+        DeviceGuard guard(g->device);
+        mixed_locate_kernel<false><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_mdesc, g->d_init, g->n_tables, d_bag_offsets, B, d_keys, n, d_found,
+                                                                          nullptr, nullptr, 0, nullptr, nullptr);
+        mixed_ensure_kernel<<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_mdesc, g->d_init, g->n_tables, d_bag_offsets, B, d_keys, n, d_found);
+        MEE_HIP(hipGetLastError());
+        d_found = nullptr;
+    }
+    if (g->sub.size() == 1)   // one width: the uniform group's keyed launch; the step index names the bag, as the mixed step reads class-major rows
+        return group_find_pooled_keyed(g->sub[0], d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, stride4 * 4, d_found, d_located, d_step_index_out,
+                                       true, mode, stream, name);
+    DeviceGuard guard(g->device);
+    const uint64_t n_bags = (uint64_t)g->n_tables * B;
+    const bool wave_per_bag = n / n_bags >= 12;   // with_pooled_shape's rule (meepo_find.hip)
+    const uint64_t units = (uint64_t)g->n_tables * (wave_per_bag ? B : (B + 3) / 4);
+    const KeyedOut keyed{stride4, d_step_index_out, 1ull, B};
+    with_flag(wave_per_bag, [&](auto wpb) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) { with_value<2, 16>(g->run_time_cw, [&](auto cw) {
+        mixed_find_pooled_kernel<wpb ? 1 : 4, bf16, cw, true><<<grid_for(units, 4, 1u << 20), 256, 0, st>>>(g->d_desc, g->d_mdesc, g->n_tables, d_keys, d_bag_offsets, B,
+                                                                                                        (float4*)d_out, d_found, d_located, n, KeyedMean{mode == MEE_POOL_MEAN, keyed});
+    }); }); });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+int mee_mixed_group_keyed_grads(mee_mixed_group* g, const void* d_keyed_grads, uint32_t in_dtype, size_t row_stride, size_t bags_per_table,
+                                const uint64_t* d_bag_offsets, int mode, float* d_bag_grads_out, void* stream) {
+    MEE_RANGE("mee_mixed_group_keyed_grads");
+    const char* name = "mee_mixed_group_keyed_grads";
+    if (!g || (bags_per_table && (!d_keyed_grads || !d_bag_grads_out))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "%s: mode must be MEE_POOL_SUM or MEE_POOL_MEAN", name);
+    if (mode == MEE_POOL_MEAN && bags_per_table && !d_bag_offsets) return fail(MEE_ERR_INVALID_ARG, "%s: MEE_POOL_MEAN needs d_bag_offsets (the bags' lengths)", name);
+    if ((uintptr_t)d_bag_grads_out & 15) return fail(MEE_ERR_INVALID_ARG, "%s: d_bag_grads_out must be 16-byte aligned", name);
+    uint64_t stride4 = 0;
+    if (int rc = keyed_out_check(name, mixed_width(g), g->n_tables, bags_per_table, d_keyed_grads, in_dtype, row_stride, false, &stride4)) return rc;
+    if (bags_per_table == 0) return MEE_OK;
+    DeviceGuard guard(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t n_bags = (uint64_t)g->n_tables * bags_per_table;
+    with_flag(in_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
+        mixed_keyed_grads_kernel<bf16><<<grid_for(n_bags, 16, 1u << 20), 256, 0, st>>>(g->d_mdesc, g->n_tables, bags_per_table, d_keyed_grads, stride4, d_bag_offsets,
+                                                                                       mode == MEE_POOL_MEAN, (float4*)d_bag_grads_out);
+    });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }

@@ -12,6 +12,8 @@
     meepo::lookup_padded / meepo::apply_grad_padded                   padded sequences: [n_bags, max_len, dim], the backward an indexed step
     meepo::lookup_pooled[_weighted] / meepo::apply_grad_pooled[_weighted]   embedding bags (sum / mean; weighted sum with the grad of
                                                                                  the per-sample weights)
+    meepo::lookup_pooled_keyed / meepo::apply_grad_pooled_keyed       a group's bags as [bags_per_table, sum of dims] (layout="keyed"): the lookup
+                                                                                 writes that block and the index its step reads the gradient with
 
 The update happens INSIDE backward, so the layer has no torch parameters and needs no torch optimizer.  Both ops have
 fake (meta) kernels, so a model containing the layer traces and exports; they are opaque to the tracer (the table is
@@ -27,6 +29,8 @@ Class-level flags, with the default that holds when a class says nothing:
     pools_with_insert = False           find_pooled(insert_missing=[, min_count=]) creates unseen ids itself and hands out no located rows
     mixed_dims = False                  members of different dims: find_pooled(out=flat, located=, insert_missing=), views(), dims
     hot_cold_pair = False               a hot/cold pair: DynamicEmbedding has no admitting forward over it
+    keyed_bags = False                  a group whose find_pooled takes layout="keyed", step_index= (and a mixed group's apply_pooled layout="keyed",
+                                        mean_offsets=); without it DynamicEmbeddingBag(layout="keyed") composes the table-major lookup and one permute
 Optional methods:
     apply_pooled                        a group: bag b belongs to member b // bags_per_table, `tables` lists the members, the step is apply_pooled
     find_located, find_or_insert_located, apply_discard, max_batch      ONE table whose lookups hand out slot handles for apply_*(slots=)
@@ -65,6 +69,7 @@ class _Traits(NamedTuple):
     has_epoch: bool
     admission_refusal: Callable[[], str | None] | None
     native_padded: bool = False   # find_padded exists (one launch; pairs and tiered groups too); without it DynamicEmbeddingSequence composes find and a placement
+    native_keyed: bool = False    # find_pooled(layout="keyed") exists (one launch writes [bags_per_table, sum of dims]); without it the bag layer composes a permute
 
 
 def _traits(table) -> _Traits:
@@ -78,7 +83,7 @@ def _traits(table) -> _Traits:
     return _Traits(grouped, grouped and not inserts, located_table, inserts, bool(getattr(table, "weighted_bags", True)),
                    bool(getattr(table, "mixed_dims", False)), bf16_rows, bf16_rows or bool(getattr(table, "supports_pooled_out_dtype", False)),
                    bool(getattr(table, "hot_cold_pair", False)), hasattr(table, "layout_epoch"), getattr(table, "admission_refusal", None),
-                   hasattr(table, "find_padded"))
+                   hasattr(table, "find_padded"), bool(getattr(table, "keyed_bags", False)))
 
 
 def _admit_kw(layer) -> dict:
@@ -357,6 +362,85 @@ def _backward_pooled_mixed(ctx, grad_flat, _grad_located):
 lookup_pooled_mixed.register_autograd(_backward_pooled_mixed, setup_context=_setup_pooled)
 
 
+# ---- pooled over a group in the keyed layout (SPEC.md §3 "Keyed output"): [bags_per_table, sum of dims], a sample's pooled vectors side by side ------
+# forward = the group's find_pooled(layout="keyed"), which writes that block and, per position, the row of the gradient its step reads (step_index);
+# backward = apply_pooled on the keyed gradient where it lies, viewed [B * T, dim], through that index (a mixed group: its apply_pooled(layout="keyed"),
+# one launch that takes the gradient apart into the class-major step buffer) — no permute in either direction and no _bag_of.
+@torch.library.custom_op("meepo::lookup_pooled_keyed", mutates_args=())
+def lookup_pooled_keyed(keys: torch.Tensor, bag_offsets: torch.Tensor, anchor: torch.Tensor, table_id: int, mean: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (keyed rows [bags_per_table, sum of dims], located rows [n] (empty where the group hands none out), step index [n] int32)"""
+    layer = _layer(table_id)
+    group, mode = layer.table, "mean" if mean else "sum"
+    index = torch.zeros(keys.numel(), dtype=torch.int32, device=keys.device)
+    creates = layer.create_missing and layer.training
+    if layer.traits.pools_with_insert:   # a TieredTableGroup: unseen ids are created inside the pooled lookup
+        out, _ = group.find_pooled(keys, bag_offsets, mode, insert_missing=creates, layout="keyed", step_index=index, **_dtype_kw(layer),
+                                   **(_admit_kw(layer) if creates else {}))
+        return out, keys.new_empty(0), index
+    located = torch.empty(keys.numel(), dtype=torch.int64, device=keys.device)
+    if layer.traits.mixed_dims:
+        out, _ = group.find_pooled(keys, bag_offsets, mode, located=located, out_dtype=layer.out_dtype, insert_missing=creates, layout="keyed", step_index=index)
+        return out, located, index
+    _create_unseen(layer, keys, bag_offsets)
+    out, _ = group.find_pooled(keys, bag_offsets, mode, located=located, layout="keyed", step_index=index, **_dtype_kw(layer))
+    return out, located, index
+
+
+def _keyed_width(group) -> int:
+    return sum(group.dims) if hasattr(group, "dims") else len(group.tables) * group.dim
+
+
+@lookup_pooled_keyed.register_fake
+def _(keys, bag_offsets, anchor, table_id, mean):
+    layer = _layer(table_id)
+    bpt = (bag_offsets.numel() - 1) // len(layer.table.tables)
+    return (keys.new_empty((bpt, _keyed_width(layer.table)), dtype=layer.out_dtype),
+            keys.new_empty(0 if layer.traits.pools_with_insert else keys.numel()), keys.new_empty(keys.numel(), dtype=torch.int32))
+
+
+@torch.library.custom_op("meepo::apply_grad_pooled_keyed", mutates_args=())
+def apply_grad_pooled_keyed(keys: torch.Tensor, bag_offsets: torch.Tensor, grad_keyed: torch.Tensor, located: torch.Tensor, step_index: torch.Tensor,
+                            table_id: int, mean: bool) -> None:
+    layer = _layer(table_id)
+    group = layer.table
+    loc = located if located.numel() == keys.numel() else None
+    step = _step_now(layer)
+    if layer.traits.mixed_dims:   # fp32 or bf16 as it came: the de-interleave launch widens and, for the mean, divides
+        group.apply_pooled(keys, bag_offsets, grad_keyed, step_index, *step, located=loc, layout="keyed", mean_offsets=bag_offsets if mean else None)
+        return
+    nt, bpt = len(group.tables), grad_keyed.shape[0]
+    g = grad_keyed.view(bpt, nt, group.dim)
+    if mean:   # d mean / d row = 1 / length: one division of the keyed block, bag j * B + s sits at [s, j]
+        lens = (bag_offsets[1:] - bag_offsets[:-1]).clamp(min=1).to(torch.float32)
+        g = g / lens.view(nt, bpt).t()[:, :, None]
+    group.apply_pooled(keys, bag_offsets, g.view(bpt * nt, group.dim), step_index, *step, located=loc)
+
+
+@apply_grad_pooled_keyed.register_fake
+def _(keys, bag_offsets, grad_keyed, located, step_index, table_id, mean):
+    return None
+
+
+def _setup_pooled_keyed(ctx, inputs, output):
+    keys, bag_offsets, _, table_id, mean = inputs
+    ctx.save_for_backward(keys, bag_offsets, output[1], output[2])
+    ctx.mean = mean
+    _save_epoch(ctx, table_id)
+    ctx.mark_non_differentiable(output[1], output[2])
+
+
+def _backward_pooled_keyed(ctx, grad_out, _grad_located, _grad_index):
+    keys, bag_offsets, located, step_index = ctx.saved_tensors
+    g = grad_out.contiguous()
+    if not (_layer(ctx.table_id).traits.mixed_dims and g.dtype == torch.bfloat16):
+        g = g.to(torch.float32)   # widened BEFORE the mean's division (a mixed group's de-interleave launch widens a bf16 grad itself)
+    apply_grad_pooled_keyed(keys, bag_offsets, g, _fresh(ctx, located), step_index, ctx.table_id, ctx.mean)
+    return None, None, None, None, None
+
+
+lookup_pooled_keyed.register_autograd(_backward_pooled_keyed, setup_context=_setup_pooled_keyed)
+
+
 # ---- weighted pooled (torch.nn.EmbeddingBag's per_sample_weights; SUM only): bag = sum of w_i * row_i ----------------------
 # forward = find_pooled(weights=...), which also hands every position's handle to the backward; backward = pooled_weighted_backward
 # (grads [n, dim] = w_i * the bag's grad row, and the grad of the weights when they need one), then the table's step on those grads
@@ -615,19 +699,38 @@ class DynamicEmbeddingBag(_SparseLayer):
     hashed initial row first (one more pass over the ids); otherwise absent ids read the default row and are not trained.
     min_count (with create_missing=True; a LookupTable or TableGroup created with admission=True, or a TieredLookupTable / TieredTableGroup whose hot
     tables were): that creation pass admits — an unseen id is created only once its table's sketch has seen it min_count times, and pools as the
-    default row, untrained, until then."""
+    default row, untrained, until then.
+    layout="keyed" (groups only): forward returns ONE [bags_per_table, sum of dims] tensor — row s holds sample s of every member side by side (member j
+    at column sum(dims[:j])), the block a dense network reads — for a MixedTableGroup too.  Over a TableGroup, TieredTableGroup or MixedTableGroup the
+    lookup writes that block itself and the step reads the gradient where it lies; over any other group (sharded groups, CPU adapters) the layer
+    composes the table-major lookup and one permute, with the same results."""
 
     def __init__(self, table, mode: str = "sum", optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
-                 create_missing: bool = False, out_dtype: torch.dtype = torch.float32, min_count: int | None = None):
+                 create_missing: bool = False, out_dtype: torch.dtype = torch.float32, min_count: int | None = None, layout: str = "table"):
         """out_dtype=torch.bfloat16: the bag is accumulated in fp32 and the finished row rounded once by the lookup; backward widens the bf16 grad."""
         if mode not in ("sum", "mean"):
             raise ValueError("mode must be 'sum' or 'mean'")
+        if layout not in ("table", "keyed"):
+            raise ValueError(f"layout must be 'table' or 'keyed' (got {layout!r})")
         super().__init__(table, optimizer, lr, eps, betas, out_dtype, min_count, pooled=True, creates=create_missing)
-        self.mode, self.create_missing = mode, create_missing
+        if layout == "keyed" and not self.traits.grouped:
+            raise ValueError(f"layout='keyed' is a group's layout: {type(table).__name__} is one table (or one pair), whose [n_bags, dim] is keyed already")
+        self.mode, self.create_missing, self.layout = mode, create_missing, layout
 
     def forward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, per_sample_weights: torch.Tensor | None = None) -> torch.Tensor:
         """per_sample_weights (fp32 [n], mode "sum" only): the bag is the sum of w_i * row_i; backward also yields their grad.
         The weighted backward updates every position, so its bags must partition the keys: bag_offsets[0] = 0, bag_offsets[-1] = n."""
+        if self.layout == "keyed":
+            if per_sample_weights is not None:
+                raise ValueError("layout='keyed' has no weighted bags: per_sample_weights are offered in the table-major layout only")
+            if self.traits.native_keyed:
+                return lookup_pooled_keyed(keys, bag_offsets, self._anchor, self.table_id, self.mode == "mean")[0]
+            nt = len(self.table.tables)   # composition: the table-major lookup and one permute (autograd runs the inverse on the gradient)
+            if self.traits.mixed_dims:
+                flat = lookup_pooled_mixed(keys, bag_offsets, self._anchor, self.table_id, self.mode == "mean")[0]
+                return torch.cat(self.table.views(flat, (bag_offsets.numel() - 1) // nt), dim=1)
+            pooled = lookup_pooled(keys, bag_offsets, self._anchor, self.table_id, self.mode == "mean")[0]
+            return pooled.view(nt, -1, pooled.shape[1]).transpose(0, 1).reshape(-1, nt * pooled.shape[1])
         if self.traits.mixed_dims:   # a MixedTableGroup: one tensor per member, views of the one buffer the lookup wrote
             if per_sample_weights is not None:
                 raise ValueError(f"{type(self.table).__name__} has no weighted bags: per_sample_weights are not offered over members of different dims")

@@ -62,6 +62,42 @@ def _fp32_only(out: torch.Tensor | None, op: str) -> None:
 _PAD_KEEP = {"first": _lib.PAD_KEEP_FIRST, "last": _lib.PAD_KEEP_LAST}
 
 
+def keyed_layout(dims):
+    """The keyed layout of a group's pooled lookup (SPEC.md §3 "Keyed output"): one row per sample, member j's pooled vector at column col_offsets[j] =
+    the sum of the dims before it in the caller's order -> (col_offsets, width).  A uniform group: col_offsets[j] = j * dim."""
+    cols, width = [], 0
+    for d in dims:
+        cols.append(width)
+        width += int(d)
+    return cols, width
+
+
+def _check_layout(layout: str) -> bool:
+    """-> whether a find_pooled call asks for the keyed layout"""
+    if layout not in ("table", "keyed"):
+        raise ValueError(f"layout must be 'table' or 'keyed' (got {layout!r})")
+    return layout == "keyed"
+
+
+def _keyed_out(out: torch.Tensor | None, bags_per_table: int, width: int, out_dtype: torch.dtype, device: torch.device):
+    """the [bags_per_table, width] block of a keyed lookup -> (out, its row stride in elements): a fresh one, or the caller's 2-D tensor with
+    stride(1) == 1 and any row stride the library takes (a view into a wider feature block)"""
+    if out is None:
+        return torch.empty((bags_per_table, width), dtype=out_dtype, device=device), width
+    if out.dim() != 2 or tuple(out.shape) != (bags_per_table, width) or out.dtype != out_dtype or out.device != device or (width > 1 and out.stride(1) != 1):
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"a keyed out must be a {out_dtype} [{bags_per_table}, {width}] tensor on {device} with stride(1) == 1")
+    return out, (out.stride(0) if bags_per_table > 1 else width)
+
+
+def _step_index(step_index: torch.Tensor | None, n: int, device: torch.device):
+    """the data pointer of a keyed lookup's step_index buffer (None: not asked for)"""
+    if step_index is None:
+        return None
+    if step_index.dtype not in (torch.uint32, torch.int32) or step_index.device != device or step_index.numel() != n or not step_index.is_contiguous():
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"step_index must be a contiguous uint32 or int32 buffer of {n} entries on {device}")
+    return step_index.data_ptr()
+
+
 def _find_padded(fn, handle, device: torch.device, dim: int, k: torch.Tensor, bag_offsets: torch.Tensor, n_bags: int, bags_arg: int, max_len: int,
                  keep: str, out, found, out_dtype: torch.dtype, with_step: bool):
     """the padded lookup of a table (fn = mee_find_padded_as, bags_arg = n_bags) or a group (mee_group_find_padded_as, bags_arg = bags_per_table):
@@ -860,6 +896,7 @@ class TableGroup:
     it from a trained group): find, find_pooled (unweighted, no located buffer) and find_pooled_jagged, each bit for bit the per-member lookup; every
     training method raises MeepoError(ERR_UNSUPPORTED).  fp32-row and bf16-row tables never share a group."""
     supports_out_dtype = True
+    keyed_bags = True   # find_pooled(layout="keyed", step_index=)
 
     def __init__(self, tables, max_apply_batch: int = 0):
         self.tables = list(tables)
@@ -979,13 +1016,32 @@ class TableGroup:
 
     def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
                     found: torch.Tensor | None = None, located: torch.Tensor | None = None, weights: torch.Tensor | None = None,
-                    out_dtype: torch.dtype = torch.float32):
+                    out_dtype: torch.dtype = torch.float32, layout: str = "table", step_index: torch.Tensor | None = None):
         """find_pooled of every member in one launch -> ([n_tables * bags_per_table, dim], per-key found mask).
         located (optional int64[n] buffer) receives the located rows for apply_pooled(located=...) of the same step.
-        weights (fp32 [n], mode "sum" only): the weighted form, LookupTable.find_pooled(weights=...) per member."""
-        dt = _out_dtype(out_dtype, out)
+        weights (fp32 [n], mode "sum" only): the weighted form, LookupTable.find_pooled(weights=...) per member.
+        layout="keyed" (unweighted): the same rows as [bags_per_table, n_tables * dim] — row s holds sample s of every member side by side, what a
+        dense network reads — written by the one launch (mee_group_find_pooled_keyed); `out` may be any 2-D view with stride(1) == 1, e.g. a column
+        range of a wider feature block.  step_index (a uint32 / int32 [n] buffer, keyed only) receives the bag_of_position with which apply_pooled
+        reads the keyed gradient in place."""
+        keyed = _check_layout(layout)
+        dt = _out_dtype(out_dtype, None if keyed else out)
         bpt = self._check_bags(bag_offsets)
         k = self.tables[0]._keys(keys) if keys.numel() else keys
+        if keyed:
+            if weights is not None:
+                raise ValueError("layout='keyed' has no weighted form (per-sample weights): use the table-major lookup")
+            if mode not in ("sum", "mean"):
+                raise MeepoError(_lib.ERR_INVALID_ARG, f"mode must be 'sum' or 'mean' (got {mode!r})")
+            out, stride = _keyed_out(out, bpt, len(self.tables) * self.dim, out_dtype, self.device)
+            if found is None:
+                found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
+            check(_lib.lib().mee_group_find_pooled_keyed(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, stride, found.data_ptr(),
+                                                         located.data_ptr() if located is not None else None, _step_index(step_index, k.numel(), self.device),
+                                                         {"sum": 0, "mean": 1}[mode], _stream_ptr(self.device)))
+            return out, found
+        if step_index is not None:
+            raise ValueError("step_index is the keyed layout's (layout='keyed'): the table-major step takes the bag of every position")
         if out is None:
             out = torch.empty((bpt * len(self.tables), self.dim), dtype=out_dtype, device=self.device)
         if found is None:
@@ -1021,7 +1077,11 @@ class TableGroup:
                      optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1,
                      located: torch.Tensor | None = None) -> None:
         """Backward of find_pooled over the group: one optimizer step, position i takes row bag_of_position[i] of bag_grads.
-        located = the buffer the forward find_pooled of this step filled: skips the probe pass."""
+        located = the buffer the forward find_pooled of this step filled: skips the probe pass.
+        After find_pooled(layout="keyed", step_index=idx): bag_grads = the keyed gradient [bags_per_table, n_tables * dim] viewed
+        .view(bags_per_table * n_tables, dim), bag_of_position = idx — the step reads the keyed gradient where it lies."""
+        if bag_grads.dim() == 2 and bag_grads.shape[1] != self.dim:   # (a keyed gradient handed over without its view would be read as rows of `dim`)
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_grads must be [rows, {self.dim}] (a keyed gradient: .view(-1, {self.dim}))")
         self._apply(SparseStep.of(optimizer, lr, eps, beta1, beta2, step), keys, bag_offsets, bag_grads, bag_of_position, pooled=True, located=located)
 
     # -- the same collection with a different number of bags per member (the owner's side of ShardedTableGroup's bags) --------
@@ -1167,6 +1227,7 @@ class MixedTableGroup:
     supports_out_dtype = True
     weighted_bags = False
     mixed_dims = True
+    keyed_bags = True   # find_pooled(layout="keyed", step_index=), apply_pooled(layout="keyed")
 
     def __init__(self, tables, max_apply_batch: int = 0):
         self.tables = list(tables)
@@ -1212,6 +1273,13 @@ class MixedTableGroup:
         check(_lib.lib().mee_mixed_group_layout(self._h, int(bags_per_table), offs, C.byref(total)))
         return list(offs), int(total.value)
 
+    def keyed_layout(self):
+        """-> (the column of every member in a keyed row, the row's width), from the library (== keyed_layout(dims))."""
+        cols = (C.c_uint64 * len(self.tables))()
+        width = C.c_uint64()
+        check(_lib.lib().mee_mixed_group_keyed_layout(self._h, cols, C.byref(width)))
+        return list(cols), int(width.value)
+
     def views(self, flat: torch.Tensor, bags_per_table: int):
         """the per-member [bags_per_table, dim_j] views of a flat class-major buffer, in the caller's member order (no copy)"""
         _, offs, _ = mixed_layout(self.dims, bags_per_table)
@@ -1233,20 +1301,37 @@ class MixedTableGroup:
 
     def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
                     found: torch.Tensor | None = None, located: torch.Tensor | None = None, weights: torch.Tensor | None = None,
-                    out_dtype: torch.dtype = torch.float32, insert_missing: bool = False):
+                    out_dtype: torch.dtype = torch.float32, insert_missing: bool = False, layout: str = "table",
+                    step_index: torch.Tensor | None = None):
         """LookupTable.find_pooled of every member with its bags, in one launch -> (views, per-key found mask): views[j] is member j's
         [bags_per_table, dim_j] view of the flat class-major buffer (`out`, or a fresh one: views[j]._base).  located (optional int64[n]
         buffer) receives the located rows for apply_pooled(located=...) of the same step.  insert_missing: absent keys are created in their
-        member first (initial row / state); found = present before the call."""
+        member first (initial row / state); found = present before the call.
+        layout="keyed": the first result is ONE [bags_per_table, sum(dims)] tensor instead of the views — torch.cat(views, dim=1), written by the
+        launch itself (mee_mixed_group_find_pooled_keyed; `out` may be any 2-D view with stride(1) == 1); step_index (uint32 / int32 [n], keyed
+        only) receives the bag of every position, the bag_of_position of apply_pooled(layout="keyed")."""
+        keyed = _check_layout(layout)
         if weights is not None:
             raise ValueError("a mixed group has no weighted bags (per_sample_weights): use one TableGroup per width")
         if mode not in ("sum", "mean"):
             raise MeepoError(_lib.ERR_INVALID_ARG, f"mode must be 'sum' or 'mean' (got {mode!r})")
-        dt = _out_dtype(out_dtype, out)
+        if step_index is not None and not keyed:
+            raise ValueError("step_index is the keyed layout's (layout='keyed')")
+        dt = _out_dtype(out_dtype, None if keyed else out)
         bpt = self._check_bags(bag_offsets)
         k = self.tables[0]._keys(keys) if keys.numel() else keys
         if k.numel() and bpt == 0:
             raise MeepoError(_lib.ERR_INVALID_ARG, "there are keys but no bags: no bag would report them")
+        if keyed:
+            out, stride = _keyed_out(out, bpt, sum(self.dims), out_dtype, self.device)
+            found = self._buffer(found, "found", torch.uint8, k.numel())
+            if located is not None:
+                located = self._buffer(located, "located", torch.int64, k.numel())
+            check(_lib.lib().mee_mixed_group_find_pooled_keyed(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, stride,
+                                                               found.data_ptr(), located.data_ptr() if located is not None else None,
+                                                               _step_index(step_index, k.numel(), self.device), {"sum": 0, "mean": 1}[mode],
+                                                               int(bool(insert_missing)), _stream_ptr(self.device)))
+            return out, found
         total = mixed_layout(self.dims, bpt)[2]
         out = self._buffer(out, "out", out_dtype, total)
         found = self._buffer(found, "found", torch.uint8, k.numel())
@@ -1259,14 +1344,34 @@ class MixedTableGroup:
 
     def apply_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, bag_grads: torch.Tensor, bag_of_position: torch.Tensor,
                      optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1,
-                     located: torch.Tensor | None = None) -> None:
+                     located: torch.Tensor | None = None, layout: str = "table", mean_offsets: torch.Tensor | None = None) -> None:
         """Backward of find_pooled: one optimizer step, position i takes the row of bag bag_of_position[i] (its index in the caller's order)
-        of bag_grads — a flat fp32 buffer in the lookup's class-major layout.  located = the buffer the forward of this step filled."""
+        of bag_grads — a flat fp32 buffer in the lookup's class-major layout.  located = the buffer the forward of this step filled.
+        layout="keyed": bag_grads is the keyed gradient [bags_per_table, sum(dims)] (fp32 or bf16, stride(1) == 1), bag_of_position the step_index of
+        the keyed lookup; one launch (mee_mixed_group_keyed_grads) takes it apart into the group's class-major step buffer first.  mean_offsets (the
+        lookup's bag_offsets; keyed only): the backward of mode "mean" — row b is divided by max(len(b), 1) on the way."""
         step = SparseStep.of(optimizer, lr, eps, beta1, beta2, step)
+        keyed = _check_layout(layout)
         bpt = self._check_bags(bag_offsets)
         k = self.tables[0]._keys(keys) if keys.numel() else keys
         gi = self.tables[0]._grad_index(bag_of_position, k.numel())
-        g = self._buffer(bag_grads.contiguous(), "bag_grads", torch.float32, mixed_layout(self.dims, bpt)[2])
+        total = mixed_layout(self.dims, bpt)[2]
+        if keyed:
+            width = sum(self.dims)
+            if bag_grads.dtype not in _OUT_DTYPES:
+                raise MeepoError(_lib.ERR_INVALID_ARG, "a keyed gradient must be float32 or bfloat16")
+            kg, stride = _keyed_out(bag_grads, bpt, width, bag_grads.dtype, self.device)
+            if mean_offsets is not None:
+                self._check_bags(mean_offsets)
+            if getattr(self, "_step_grads", None) is None or self._step_grads.numel() < total:   # the group's step buffer: the launches that use it are stream-ordered
+                self._step_grads = torch.empty(total, dtype=torch.float32, device=self.device)
+            check(_lib.lib().mee_mixed_group_keyed_grads(self._h, kg.data_ptr(), _OUT_DTYPES[kg.dtype], stride, bpt,
+                                                         mean_offsets.data_ptr() if mean_offsets is not None else None, 0 if mean_offsets is None else 1,
+                                                         self._step_grads.data_ptr(), _stream_ptr(self.device)))
+            bag_grads = self._step_grads[:total]
+        elif mean_offsets is not None:
+            raise ValueError("mean_offsets is the keyed layout's (layout='keyed')")
+        g = self._buffer(bag_grads.contiguous(), "bag_grads", torch.float32, total)
         if located is not None:
             located = self._buffer(located, "located", torch.int64, k.numel())
         step.launch("mee_mixed_group_apply", "_pooled", self._h, k.data_ptr(), bag_offsets.data_ptr(), bpt, g.data_ptr(), gi.data_ptr(),

@@ -505,6 +505,7 @@ class TieredTableGroup:
     weighted_bags = False               # no per_sample_weights over the tiers
     supports_pooled_out_dtype = True    # find_pooled can write bf16 bag rows
     supports_out_dtype = True           # ... and find / find_or_insert bf16 rows (nn.DynamicEmbeddingCollection(out_dtype=torch.bfloat16))
+    keyed_bags = True                   # find_pooled(layout="keyed", step_index=)
 
     def __init__(self, pairs, max_apply_batch: int = 0, sample_every: int = 8):
         self.tables = list(pairs)
@@ -689,7 +690,8 @@ class TieredTableGroup:
             self._goes_cold = goes_cold
 
     def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
-                    found: torch.Tensor | None = None, insert_missing: bool = False, out_dtype: torch.dtype = torch.float32, min_count=None):
+                    found: torch.Tensor | None = None, insert_missing: bool = False, out_dtype: torch.dtype = torch.float32, min_count=None,
+                    layout: str = "table", step_index: torch.Tensor | None = None):
         """TieredLookupTable.find_pooled of every pair on its bags, in one launch -> ([n_tables * bags_per_table, dim] sums or means in position
         order, per-key found mask).  An absent key reads its member's HOT table's default row.  With the policy on the launch feeds the
         members' hit counters (cold hits always, hot hits on every sample_every-th call).
@@ -701,9 +703,28 @@ class TieredTableGroup:
         earlier than the pair on its own slice would, never later.
         min_count (with insert_missing; an int or one threshold per member): the creation admits, each member counting in its hot table's sketch
         (mee_group_ensure_admit_tiered: one launch more, the count); a key not yet admitted pools as its member's hot default row.
-        out_dtype=torch.bfloat16: the finished bag row is rounded once."""
+        out_dtype=torch.bfloat16: the finished bag row is rounded once.
+        layout="keyed": the same rows as [bags_per_table, n_tables * dim], sample s of every pair side by side in row s, written by the launch itself
+        (mee_group_find_pooled_tiered_keyed; `out` may be any 2-D view with stride(1) == 1); step_index (uint32 / int32 [n], keyed only) receives
+        the bag_of_position with which apply_pooled reads the keyed gradient, viewed [bags_per_table * n_tables, dim], in place."""
+        from .table import _check_layout
+        keyed = _check_layout(layout)
+        if step_index is not None and not keyed:
+            raise ValueError("step_index is the keyed layout's (layout='keyed')")
         if mode not in ("sum", "mean"):
             raise ValueError(f"mode must be 'sum' or 'mean' (got {mode!r})")
+        if keyed and not self._native:   # the loop below, then one permute: what the launch writes directly over native pairs
+            pooled, fnd = self.find_pooled(keys, bag_offsets, mode, None, found, insert_missing, out_dtype, min_count)
+            nt, bpt = len(self.tables), pooled.shape[0] // len(self.tables)
+            rows = pooled.view(nt, bpt, self.dim).transpose(0, 1).reshape(bpt, nt * self.dim)
+            if step_index is not None:
+                o = bag_offsets.to(torch.int64).clamp(0, keys.numel())
+                lens = (o[1:] - o[:-1]).clamp(min=0)
+                bag = torch.repeat_interleave(torch.arange(lens.numel(), device=lens.device), lens)
+                step_index[int(o[0]):int(o[0]) + bag.numel()] = ((bag % bpt) * nt + bag // bpt).to(step_index.dtype)
+            if out is not None:
+                out.copy_(rows)
+            return (out if out is not None else rows), fnd
         admits = None
         if min_count is not None:
             if not insert_missing:
@@ -726,18 +747,34 @@ class TieredTableGroup:
                 found.copy_(fnd)
             return (out if out is not None else pooled), (found if found is not None else fnd)
         from . import _lib
-        from .table import _out_dtype, _stream_ptr
-        dt = _out_dtype(out_dtype, out)
+        from .table import _keyed_out, _out_dtype, _step_index, _stream_ptr
+        dt = _out_dtype(out_dtype, None if keyed else out)
         bpt = self.hot_group._check_bags(bag_offsets)
         k = self.tables[0].hot._keys(keys) if keys.numel() else keys
         n = k.numel()
-        if out is None:
+        if keyed:
+            out, stride = _keyed_out(out, bpt, len(self.tables) * self.dim, out_dtype, self.device)
+        elif out is None:
             out = torch.empty((bpt * len(self.tables), self.dim), dtype=out_dtype, device=self.device)
         if found is None:
             found = torch.empty(n, dtype=torch.uint8, device=self.device)
         L, s, m = _lib.lib(), _stream_ptr(self.device), {"sum": 0, "mean": 1}[mode]
         hot, cold = self.hot_group._h, self.cold_group._h
         creates = bool(insert_missing and n and bpt)
+        if keyed:   # the found pass of a creating lookup writes no rows the caller sees: it goes to a scratch block, the keyed launch writes `out`
+            index = _step_index(step_index, n, self.device)
+            if creates:
+                scratch = torch.empty((bpt * len(self.tables), self.dim), dtype=out_dtype, device=self.device)
+                _lib.check(L.mee_group_find_pooled_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, scratch.data_ptr(), dt, found.data_ptr(), m, 0, s))
+                self._place_new_keys(n)
+                if admits is None:
+                    _lib.check(L.mee_group_ensure_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, found.data_ptr(), self._d_goes_cold.data_ptr(), s))
+                else:
+                    _lib.check(L.mee_group_ensure_admit_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, found.data_ptr(), self._d_goes_cold.data_ptr(),
+                                                               admits[0], admits[1].data_ptr() if admits[1] is not None else None, s))
+            _lib.check(L.mee_group_find_pooled_tiered_keyed(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, stride,
+                                                            None if creates else found.data_ptr(), index, m, self._count_flags(), s))
+            return out, found
         if creates:
             # the found mask of the whole batch first (no counters: this pass is not a lookup of the model's) ...
             _lib.check(L.mee_group_find_pooled_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, found.data_ptr(), m, 0, s))
