@@ -44,7 +44,7 @@ enum { MEE_OK = 0, MEE_ERR_INVALID_ARG = -1, MEE_ERR_OUT_OF_MEMORY = -2, MEE_ERR
        MEE_ERR_NO_DEVICE = -4, MEE_ERR_BATCH_TOO_LARGE = -5, MEE_ERR_UNSUPPORTED = -6,
        MEE_ERR_RCCL = -7 /* an RCCL call failed, or librccl.so.1 could not be loaded */ };
 
-enum { MEE_OPT_NONE = 0, MEE_OPT_ADAGRAD = 1, MEE_OPT_ADAM = 2 };
+enum { MEE_OPT_NONE = 0, MEE_OPT_ADAGRAD = 1, MEE_OPT_ADAM = 2, MEE_OPT_FTRL = 3 };   /* state planes: none | acc | m, v | z, n (FTRL-Proximal: mee_apply_ftrl) */
 enum { MEE_INIT_CONSTANT = 0, MEE_INIT_UNIFORM = 1 };
 /* MEE_STATUS_STALE_HANDLE: mee_apply_*_located met a slot handle made before the table's latest mee_remove / mee_clear / mee_reserve; such
  * positions receive no update (the slot may hold another key by now).
@@ -92,11 +92,11 @@ typedef struct mee_config {
     int32_t  device;              /* HIP device ordinal */
     uint64_t capacity;            /* requested slots; rounded up to 16 x (smallest prime >= capacity/16) (SPEC.md §2) */
     uint32_t dim;                 /* floats per row: multiple of 4, 4..1024 (MEE_FLAG_BF16_ROWS: multiple of 8; MEE_FLAG_INT8_ROWS: of 16) */
-    uint32_t optimizer;           /* MEE_OPT_*: which state planes to allocate */
+    uint32_t optimizer;           /* MEE_OPT_*: which state planes to allocate (Adagrad one; Adam and FTRL two) */
     uint64_t max_batch;           /* largest n of any mutating op: sizes the workspace — with an optimizer ~(56 + 10 dim) B per position of HBM
                                    * (0.7 GB at 1M x dim 64: the pending records of a skewed batch's worst case); see mee_table_info.workspace_bytes */
     float    default_value;       /* fill for rows of absent keys */
-    float    initial_accumulator; /* Adagrad acc of a newly inserted key */
+    float    initial_accumulator; /* Adagrad acc, FTRL n of a newly inserted key */
     uint32_t initializer;         /* MEE_INIT_*: initial row for find_or_insert */
     float    init_scale;
     uint64_t init_seed;
@@ -438,6 +438,15 @@ int mee_group_apply_adagrad_indexed(mee_group* g, const int64_t* d_keys, const u
                                     const uint32_t* d_grad_index, size_t n, float lr, float eps, void* stream);
 int mee_group_apply_adam_indexed(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows,
                                  const uint32_t* d_grad_index, size_t n, float lr, float beta1, float beta2, float eps, uint64_t step, void* stream);
+/* The FTRL-Proximal step (mee_apply_ftrl, below) over a group whose members were created with MEE_OPT_FTRL: mee_group_apply_adagrad,
+ * mee_group_apply_adagrad_pooled and mee_group_apply_adagrad_indexed with (beta, l1, l2) after lr; the same launches, refusals and argument checks. */
+int mee_group_apply_ftrl(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr, float beta,
+                         float l1, float l2, void* stream);
+int mee_group_apply_ftrl_pooled(mee_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_bag_grads,
+                                const uint32_t* d_grad_index, const int64_t* d_located, size_t n, float lr, float beta, float l1, float l2,
+                                void* stream);
+int mee_group_apply_ftrl_indexed(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows,
+                                 const uint32_t* d_grad_index, size_t n, float lr, float beta, float l1, float l2, void* stream);
 /* The weighted forms over the collection: mee_find_pooled_weighted / mee_pooled_weighted_backward on every member, bag b belonging to
  * member b / bags_per_table, in one launch each.  d_located_out / d_located are in the group's format (as mee_group_find_pooled's); the
  * step after the backward is mee_group_apply_*(d_keys, member offsets, d_grads_out) — the grads are per position, not per bag. */
@@ -744,6 +753,11 @@ mee_mixed_group_keyed_layout(const mee_mixed_group* g, uint64_t* col_offsets /* 
 int
 mee_mixed_group_keyed_grads(mee_mixed_group* g, const void* d_keyed_grads, uint32_t in_dtype, size_t row_stride, size_t bags_per_table,
                                 const uint64_t* d_bag_offsets /* MEE_POOL_MEAN only */, int mode, float* d_bag_grads_out, void* stream);
+/* mee_mixed_group_apply_adagrad_pooled with the FTRL-Proximal rule (mee_apply_ftrl, below): (beta, l1, l2) after lr, checked before the first launch */
+int
+mee_mixed_group_apply_ftrl_pooled(mee_mixed_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                                      const float* d_bag_grads, const uint32_t* d_bag_of_position, const int64_t* d_located /* nullable */,
+                                      size_t n, float lr, float beta, float l1, float l2, void* stream);
 
 /* ---- sparse optimizers (north_star "sparse-optimizer (Adagrad/Adam) scatter-update"; SPEC.md §4) -------- */
 int mee_apply_adagrad(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, float lr, float eps,
@@ -764,6 +778,21 @@ int mee_apply_adagrad_indexed(mee_table* t, const int64_t* d_keys, const float* 
                               size_t n, float lr, float eps, void* stream);
 int mee_apply_adam_indexed(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index,
                            size_t n, float lr, float beta1, float beta2, float eps, uint64_t step, void* stream);
+/* FTRL-Proximal (SPEC.md §4 "FTRL-Proximal"; McMahan et al. 2013, Algorithm 1) on a table created with MEE_OPT_FTRL: three fp32 planes per key,
+ * the row w (plane 0), z (plane 1, +0.0 at creation) and n (plane 2, config.initial_accumulator at creation).  lr is the paper's alpha, beta its
+ * beta, l1 / l2 its lambda1 / lambda2; g is the key's reduced gradient (duplicates summed in fp64 and applied once, as for the other rules):
+ *     n' = n + g*g;  sig = (sqrt(n') - sqrt(n)) / lr;  z' = (z + g) - sig*w;
+ *     w' = |z'| <= l1 ? +0.0 : (copysign(l1, z') - z') / ((beta + sqrt(n')) / lr + l2)
+ * every operation rounded to fp32 on its own, no fma: a coordinate whose |z'| stays within l1 is exactly +0.0.  The three forms (by key, located,
+ * indexed) are the Adagrad entry points' with (beta, l1, l2) after lr: absent keys ignored, the same handles, clamping, pending partition and capture.
+ * MEE_ERR_INVALID_ARG before anything is launched or written: lr not finite or <= 0; beta, l1 or l2 NaN or negative.  MEE_ERR_UNSUPPORTED on a
+ * table (or a group, below) of another optimizer.  Out of scope: the sharded step (mee_sharded_apply_*) and the peer-mapped mutators know
+ * Adagrad and Adam only. */
+int mee_apply_ftrl(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, float lr, float beta, float l1, float l2, void* stream);
+int mee_apply_ftrl_located(mee_table* t, const int64_t* d_keys, const int64_t* d_slots, const float* d_grads, size_t n, float lr, float beta,
+                           float l1, float l2, void* stream);
+int mee_apply_ftrl_indexed(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index, size_t n,
+                           float lr, float beta, float l1, float l2, void* stream);
 /* Optional split of an apply: mee_apply_prepare groups the batch's keys (occurrence counts, per-key position lists) — everything
  * that does not need the grads — so it can run early (e.g. on a side stream beside the forward lookup and the dense
  * model); the following mee_apply_adagrad / mee_apply_adam with the SAME d_keys / n then only streams the updates.

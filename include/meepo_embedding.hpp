@@ -142,6 +142,14 @@ public:
     void apply_adam_indexed(const int64_t* d_keys, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index, size_t n, float lr, uint64_t step, float beta1 = 0.9f, float beta2 = 0.999f, float eps = 1e-8f, void* stream = nullptr) {
         check(mee_apply_adam_indexed(t_, d_keys, d_grads, n_grad_rows, d_grad_index, n, lr, beta1, beta2, eps, step, stream));
     }
+    // FTRL-Proximal (a table created with MEE_OPT_FTRL): by key, on the forward's slot handles, on indexed gradient rows
+    void apply_ftrl(const int64_t* d_keys, const float* d_grads, size_t n, float lr, float beta = 1.0f, float l1 = 0.0f, float l2 = 0.0f, void* stream = nullptr) { check(mee_apply_ftrl(t_, d_keys, d_grads, n, lr, beta, l1, l2, stream)); }
+    void apply_ftrl_located(const int64_t* d_keys, const int64_t* d_slots, const float* d_grads, size_t n, float lr, float beta = 1.0f, float l1 = 0.0f, float l2 = 0.0f, void* stream = nullptr) {
+        check(mee_apply_ftrl_located(t_, d_keys, d_slots, d_grads, n, lr, beta, l1, l2, stream));
+    }
+    void apply_ftrl_indexed(const int64_t* d_keys, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index, size_t n, float lr, float beta = 1.0f, float l1 = 0.0f, float l2 = 0.0f, void* stream = nullptr) {
+        check(mee_apply_ftrl_indexed(t_, d_keys, d_grads, n_grad_rows, d_grad_index, n, lr, beta, l1, l2, stream));
+    }
     // the next four synchronise the stream (they return host values)
     size_t size(void* stream = nullptr) const { size_t n = 0; check(mee_size(t_, &n, stream)); return n; }
     uint32_t status(void* stream = nullptr) const { uint32_t b = 0; check(mee_status(t_, &b, stream)); return b; }
@@ -238,6 +246,16 @@ public:
     void apply_adam_indexed(const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index, size_t n, float lr, uint64_t step, float beta1 = 0.9f, float beta2 = 0.999f, float eps = 1e-8f, void* stream = nullptr) {
         check(mee_group_apply_adam_indexed(g_, d_keys, d_offsets, d_grads, n_grad_rows, d_grad_index, n, lr, beta1, beta2, eps, step, stream));
     }
+    // FTRL-Proximal over a group of MEE_OPT_FTRL tables: per position, pooled (a bag's grad row for each of its keys), indexed
+    void apply_ftrl(const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr, float beta = 1.0f, float l1 = 0.0f, float l2 = 0.0f, void* stream = nullptr) {
+        check(mee_group_apply_ftrl(g_, d_keys, d_offsets, d_grads, n, lr, beta, l1, l2, stream));
+    }
+    void apply_ftrl_pooled(const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_bag_grads, const uint32_t* d_grad_index, const int64_t* d_located, size_t n, float lr, float beta = 1.0f, float l1 = 0.0f, float l2 = 0.0f, void* stream = nullptr) {
+        check(mee_group_apply_ftrl_pooled(g_, d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_grad_index, d_located, n, lr, beta, l1, l2, stream));
+    }
+    void apply_ftrl_indexed(const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index, size_t n, float lr, float beta = 1.0f, float l1 = 0.0f, float l2 = 0.0f, void* stream = nullptr) {
+        check(mee_group_apply_ftrl_indexed(g_, d_keys, d_offsets, d_grads, n_grad_rows, d_grad_index, n, lr, beta, l1, l2, stream));
+    }
     // a collection of hot/cold pairs: this group holds the HOT tables, `cold` the cold ones, member j of both = pair j (mee_group_find_pooled_tiered /
     // mee_group_ensure_tiered).  One pooled launch over both tiers of every member; flags = MEE_TIER_COUNT_*.  ensure_tiered creates the keys d_found
     // marks as missing, member j in its cold table where d_to_cold[j] != 0 (null: all hot).
@@ -308,6 +326,9 @@ public:
     void apply_adam_pooled(const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_bag_grads, const uint32_t* d_bag_of_position, const int64_t* d_located, size_t n, float lr, uint64_t step, float beta1 = 0.9f, float beta2 = 0.999f, float eps = 1e-8f, void* stream = nullptr) {
         check(mee_mixed_group_apply_adam_pooled(g_, d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_bag_of_position, d_located, n, lr, beta1, beta2, eps, step, stream));
     }
+    void apply_ftrl_pooled(const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_bag_grads, const uint32_t* d_bag_of_position, const int64_t* d_located, size_t n, float lr, float beta = 1.0f, float l1 = 0.0f, float l2 = 0.0f, void* stream = nullptr) {
+        check(mee_mixed_group_apply_ftrl_pooled(g_, d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_bag_of_position, d_located, n, lr, beta, l1, l2, stream));
+    }
     // the keyed layout: member j's pooled vector at column col_offsets[j] of its sample's row (mee_mixed_group_keyed_layout -> the row's width in elements)
     uint64_t keyed_layout(uint64_t* col_offsets = nullptr) const {
         uint64_t width = 0;
@@ -340,6 +361,10 @@ public:
     void apply_adagrad(const int64_t* d_keys, const float* d_grads, size_t n, float lr, float eps = 1e-10f, void* stream = nullptr) {
         hot_.apply_adagrad(d_keys, d_grads, n, lr, eps, stream);  // a key lives in one tier; each table ignores keys it does not hold
         cold_.apply_adagrad(d_keys, d_grads, n, lr, eps, stream);
+    }
+    void apply_ftrl(const int64_t* d_keys, const float* d_grads, size_t n, float lr, float beta = 1.0f, float l1 = 0.0f, float l2 = 0.0f, void* stream = nullptr) {
+        hot_.apply_ftrl(d_keys, d_grads, n, lr, beta, l1, l2, stream);
+        cold_.apply_ftrl(d_keys, d_grads, n, lr, beta, l1, l2, stream);
     }
     size_t size(void* stream = nullptr) const { return hot_.size(stream) + cold_.size(stream); }
 private:

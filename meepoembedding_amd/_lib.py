@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MEE_LIB_PATH") or os.path.join(_HERE, "libmeepo_hip.s
 
 OK = 0
 ERR_INVALID_ARG, ERR_OUT_OF_MEMORY, ERR_HIP, ERR_NO_DEVICE, ERR_BATCH_TOO_LARGE, ERR_UNSUPPORTED, ERR_RCCL = -1, -2, -3, -4, -5, -6, -7
-OPT_NONE, OPT_ADAGRAD, OPT_ADAM = 0, 1, 2
+OPT_NONE, OPT_ADAGRAD, OPT_ADAM, OPT_FTRL = 0, 1, 2, 3
 INIT_CONSTANT, INIT_UNIFORM = 0, 1
 STATUS_TABLE_FULL, STATUS_RESERVED_KEY, STATUS_STALE_HANDLE, STATUS_INTERNAL = 1, 2, 4, 8
 FIND_DEFAULT, FIND_STREAM_STORES, FIND_CACHED_STORES, FIND_STREAM_ROWS, FIND_STREAM_BUCKETS = 0, 1, 2, 4, 8   # mee_find_ex flags
@@ -207,6 +207,14 @@ PROTOTYPES = {
     "mee_probe_histogram": (C.c_int, [_vp, _vp, _sz, C.POINTER(C.c_uint64), _vp]),
     "mee_apply_adagrad": (C.c_int, [_vp, _vp, _vp, _sz, _f32, _f32, _vp]),
     "mee_apply_adam": (C.c_int, [_vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32, _u64, _vp]),
+    # FTRL-Proximal: the Adagrad forms with (beta, l1, l2) after lr
+    "mee_apply_ftrl": (C.c_int, [_vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32, _vp]),
+    "mee_apply_ftrl_located": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32, _vp]),
+    "mee_apply_ftrl_indexed": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _f32, _f32, _f32, _f32, _vp]),
+    "mee_group_apply_ftrl": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32, _vp]),
+    "mee_group_apply_ftrl_pooled": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32, _vp]),
+    "mee_group_apply_ftrl_indexed": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _f32, _f32, _f32, _f32, _vp]),
+    "mee_mixed_group_apply_ftrl_pooled": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32, _vp]),
     "mee_apply_prepare": (C.c_int, [_vp, _vp, _sz, _vp]),
     "mee_apply_discard": (C.c_int, [_vp, _vp]),
     "mee_dedup_sum": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, C.c_int64, _vp]),

@@ -8,8 +8,8 @@ A checkpoint is a DIRECTORY:
                   int8-row table wrote it: values.f32 holds its rows dequantized, and loading into one quantizes every row once)
     keys.i64      n little-endian int64 keys, in export order (unspecified, stable within the checkpoint)
     values.f32    n x dim little-endian fp32 rows, same order
-    state1.f32    n x dim Adagrad accumulator / Adam m      (tables with an optimizer)
-    state2.f32    n x dim Adam v                             (Adam tables)
+    state1.f32    n x dim Adagrad accumulator / Adam m / FTRL z   (tables with an optimizer)
+    state2.f32    n x dim Adam v / FTRL n                    (Adam and FTRL tables)
 
 The table is walked in slot ranges (`mee_export_range`), so saving needs scratch for one range, not a second copy of the
 table, and the pieces go to disk in order; loading reads the files back `chunk_pairs` at a time and re-inserts them
@@ -32,7 +32,7 @@ _PLANES = ("values", "state1", "state2")
 
 
 def _n_planes(optimizer: int) -> int:
-    return 1 + (optimizer != 0) + (optimizer == 2)
+    return 1 + (optimizer != 0) + (optimizer in (2, 3))   # Adam and FTRL keep two state planes
 
 
 def save_table(table, path: str, chunk_slots: int = 1 << 22, extra: dict | None = None) -> int:

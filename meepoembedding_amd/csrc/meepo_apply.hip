@@ -404,7 +404,7 @@ __device__ __forceinline__ void process_slab(ApplyLds& L, const ApplyArgs& A, co
                 float4 w = make_float4(0.f, 0.f, 0.f, 0.f), x1 = w, x2 = w;
                 if (upd) {   // the run's row is requested before its sources are summed: the update's round trip overlaps with the sum's
                     w = at.values[o]; x1 = at.s1[o];
-                    if (KIND == MEE_OPT_ADAM) x2 = at.s2[o];
+                    if (opt_has_s2(KIND)) x2 = at.s2[o];
                 }
                 double sx = 0.0, sy = 0.0, sz = 0.0, sw = 0.0;
                 sum_sources<src_rec>(L, A, bk, rec_bucket0, run0, nh, dim4, col, sx, sy, sz, sw);
@@ -413,7 +413,7 @@ __device__ __forceinline__ void process_slab(ApplyLds& L, const ApplyArgs& A, co
                 if (upd) {
                     opt_update4(a, w, x1, x2, make_float4((float)sx, (float)sy, (float)sz, (float)sw));
                     store_row4(&at.values[o], w); store_row4(&at.s1[o], x1);
-                    if (KIND == MEE_OPT_ADAM) store_row4(&at.s2[o], x2);
+                    if (opt_has_s2(KIND)) store_row4(&at.s2[o], x2);
                 } else if (!fin) {   // a quad of a longer run -> one fp64 partial row of this block | a whole run of a split bucket's slab -> its pending record
                     if (one) rec_store_row4(bk.pend_row + ((uint64_t)(rec_out0 + L.run[s]) * dim4 + col) * 4, sx, sy, sz, sw);
                     else {
@@ -455,14 +455,14 @@ __device__ __forceinline__ void process_slab(ApplyLds& L, const ApplyArgs& A, co
             float4 w = make_float4(0.f, 0.f, 0.f, 0.f), x1 = w, x2 = w;
             if (upd) {
                 w = at.values[o]; x1 = at.s1[o];
-                if (KIND == MEE_OPT_ADAM) x2 = at.s2[o];
+                if (opt_has_s2(KIND)) x2 = at.s2[o];
             }
             if (single) {   // gradient row (already requested) + the key's row -> update -> store; nothing else is live here
                 if (upd) {
                     const float4 g = col == (uint32_t)tl ? make_float4(gpre.x, gpre.y, gpre.z, gpre.w) : A.grads[(uint64_t)src0 * dim4 + col];
                     opt_update4(a, w, x1, x2, g);
                     store_row4(&at.values[o], w); store_row4(&at.s1[o], x1);
-                    if (KIND == MEE_OPT_ADAM) store_row4(&at.s2[o], x2);
+                    if (opt_has_s2(KIND)) store_row4(&at.s2[o], x2);
                 }
                 continue;
             }
@@ -472,7 +472,7 @@ __device__ __forceinline__ void process_slab(ApplyLds& L, const ApplyArgs& A, co
                 if (upd) {
                     opt_update4(a, w, x1, x2, make_float4((float)sx, (float)sy, (float)sz, (float)sw));
                     store_row4(&at.values[o], w); store_row4(&at.s1[o], x1);
-                    if (KIND == MEE_OPT_ADAM) store_row4(&at.s2[o], x2);
+                    if (opt_has_s2(KIND)) store_row4(&at.s2[o], x2);
                 }
             } else rec_store_row4(bk.pend_row + ((uint64_t)(rec_out0 + L.run[s]) * dim4 + col) * 4, sx, sy, sz, sw);   // a whole run of a split bucket's slab -> its pending record
         }
@@ -503,7 +503,7 @@ __device__ __forceinline__ void process_slab(ApplyLds& L, const ApplyArgs& A, co
             float4 w = make_float4(0.f, 0.f, 0.f, 0.f), x1 = w, x2 = w;
             if (upd) {
                 w = at.values[o]; x1 = at.s1[o];
-                if (KIND == MEE_OPT_ADAM) x2 = at.s2[o];
+                if (opt_has_s2(KIND)) x2 = at.s2[o];
             }
             double sx = 0.0, sy = 0.0, sz = 0.0, sw = 0.0;
             for (uint32_t q0 = (uint32_t)tile; q0 < nq; q0 += 8) {   // two rows in flight per tile (nq <= 8: one round trip)
@@ -521,7 +521,7 @@ __device__ __forceinline__ void process_slab(ApplyLds& L, const ApplyArgs& A, co
             if (upd) {
                 opt_update4(a, w, x1, x2, make_float4((float)sx, (float)sy, (float)sz, (float)sw));
                 store_row4(&at.values[o], w); store_row4(&at.s1[o], x1);
-                if (KIND == MEE_OPT_ADAM) store_row4(&at.s2[o], x2);
+                if (opt_has_s2(KIND)) store_row4(&at.s2[o], x2);
             } else if (!fin) rec_store_row4(bk.pend_row + ((uint64_t)(rec_out0 + L.run[s]) * dim4 + col) * 4, sx, sy, sz, sw);
         }
         if (!fin && lane == 0) {
@@ -585,10 +585,10 @@ __device__ __forceinline__ void mono_pass(ApplyLds& L, const ApplyArgs& A, const
             }
             const uint64_t o = at.row * dim4 + col;
             float4 w = at.values[o], x1 = at.s1[o], x2 = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (KIND == MEE_OPT_ADAM) x2 = at.s2[o];
+            if (opt_has_s2(KIND)) x2 = at.s2[o];
             opt_update4(a, w, x1, x2, make_float4((float)sx, (float)sy, (float)sz, (float)sw));
             store_row4(&at.values[o], w); store_row4(&at.s1[o], x1);
-            if (KIND == MEE_OPT_ADAM) store_row4(&at.s2[o], x2);
+            if (opt_has_s2(KIND)) store_row4(&at.s2[o], x2);
         }
     }
     __syncthreads();
@@ -938,10 +938,10 @@ __device__ __forceinline__ void slow_update(ApplyLds& L, const ApplyArgs& A, con
         const uint64_t o = at.row * dim4 + col;
         const double* r = &L.prow[8][tl * 4];
         float4 w = at.values[o], x1 = at.s1[o], x2 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (KIND == MEE_OPT_ADAM) x2 = at.s2[o];
+        if (opt_has_s2(KIND)) x2 = at.s2[o];
         opt_update4(a, w, x1, x2, make_float4((float)r[0], (float)r[1], (float)r[2], (float)r[3]));
         store_row4(&at.values[o], w); store_row4(&at.s1[o], x1);
-        if (KIND == MEE_OPT_ADAM) store_row4(&at.s2[o], x2);
+        if (opt_has_s2(KIND)) store_row4(&at.s2[o], x2);
     }
 }
 
@@ -1401,7 +1401,7 @@ int bucket_apply_launch(mee_table* t, const PartPlan& plan, const float* d_grads
     // from device memory (t->bk.dev_copy), LEAN takes it as kernel arguments.
     const int rows = d_desc ? 2 : d_slots ? 1 : 0;
     auto apply = [&](bool full, uint32_t grid) {
-        with_value<MEE_OPT_ADAGRAD, MEE_OPT_ADAM>(a.kind, [&](auto kind) { with_row_shape(t->dim4, [&](auto d4) { with_value<2, 1, 0>(rows, [&](auto r) { with_flag(full, [&](auto f) {
+        with_value<MEE_OPT_ADAGRAD, MEE_OPT_ADAM, MEE_OPT_FTRL>(a.kind, [&](auto kind) { with_row_shape(t->dim4, [&](auto d4) { with_value<2, 1, 0>(rows, [&](auto r) { with_flag(full, [&](auto f) {
             auto bk = [&] { if constexpr (f) return t->bk.dev_copy; else return t->bk; };
             bkt_apply_kernel<kind, d4, (r >= 1), (r == 2), f><<<grid, kApplyThreads, 0, st>>>(A, bk());
         }); }); }); });

@@ -700,13 +700,27 @@ __device__ __forceinline__ void adam1(float& w, float& m, float& v, float g, flo
     w = __builtin_fmaf(-step_size, q, w);
     m = mn; v = vn;
 }
+// FTRL-Proximal (SPEC.md §4): z in plane 1, n in plane 2; every line one fp32 operation rounded on its own, no fma
+__device__ __forceinline__ void ftrl1(float& w, float& z, float& n, float g, float lr, float beta, float l1, float l2) {
+    const float gg = g * g;
+    const float nn = n + gg;
+    const float sn = __builtin_sqrtf(nn);
+    const float sig = (sn - __builtin_sqrtf(n)) / lr;
+    const float sw = sig * w;
+    const float zn = (z + g) - sw;
+    const float den = (beta + sn) / lr + l2;
+    w = __builtin_fabsf(zn) <= l1 ? 0.0f : (__builtin_copysignf(l1, zn) - zn) / den;   // (a NaN z' fails the comparison and propagates)
+    z = zn; n = nn;
+}
+// an optimizer with a second state plane (s2): Adam's v, FTRL's n
+__host__ __device__ constexpr bool opt_has_s2(uint32_t kind) { return kind == MEE_OPT_ADAM || kind == MEE_OPT_FTRL; }
 
 // ---- the creation of a key, said once -----------------------------------------------------------------------------------------------------------
 // What a tile does once tile_locate<claim> has given it `slot` (>= 0) of `key` in the table (d: its planes and default value — GroupDesc; in: its
 // initializer, optimizer and hit counters — GroupInit, meepo_host.h): with ROWS_OUT every such tile — the one whose CAS created the key and one that met
 // a duplicate's creation alike — writes the key's initial row, a function of the key and the table's initializer alone, into row i of `out` (BF16: that
 // copy is rounded, the stored row is not), so nothing has to read the created rows back; the creator (is_new) also writes the table's row, the
-// initial Adagrad or Adam state and a zero hit counter.
+// initial Adagrad, Adam or FTRL state and a zero hit counter.
 template <bool ROWS_OUT, bool BF16, class Desc, class Init>
 __device__ __forceinline__ void creation_write(const Desc& d, const Init& in, uint32_t dim4, int64_t key, int64_t slot, bool is_new, float4* __restrict__ out,
                                                uint64_t i, int tl) {
@@ -719,9 +733,10 @@ __device__ __forceinline__ void creation_write(const Desc& d, const Init& in, ui
             if (is_new) {
                 d.values[(uint64_t)slot * dim4 + c] = row;
                 if (in.optimizer == MEE_OPT_ADAGRAD) d.s1[(uint64_t)slot * dim4 + c] = make_float4(in.init_acc, in.init_acc, in.init_acc, in.init_acc);
-                if (in.optimizer == MEE_OPT_ADAM) {
+                if (opt_has_s2(in.optimizer)) {   // Adam: m = v = 0; FTRL: z = 0, n = initial_accumulator
+                    const float n0 = in.optimizer == MEE_OPT_FTRL ? in.init_acc : 0.f;
                     d.s1[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    d.s2[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    d.s2[(uint64_t)slot * dim4 + c] = make_float4(n0, n0, n0, n0);
                 }
             }
         }

@@ -369,6 +369,10 @@ __global__ __launch_bounds__(256) void ensure_admit_grouped_kernel(const GroupDe
                             d.s1[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
                             d.s2[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
                         }
+                        if (in.optimizer == MEE_OPT_FTRL) {
+                            d.s1[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                            d.s2[(uint64_t)slot * dim4 + c] = make_float4(in.init_acc, in.init_acc, in.init_acc, in.init_acc);
+                        }
                     }
                 }
                 if (is_new && in.hits && tl == 0) in.hits[slot] = 0;

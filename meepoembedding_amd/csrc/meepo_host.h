@@ -162,6 +162,8 @@ template <int DIM4> struct RowShape {   // what the row kernels' launches share 
     static constexpr int pooled_unroll_1 = DIM4 == 16 ? 4 : DIM4 == 32 ? 2 : 1;   // keys in flight per tile of a pooled lookup, one bag per wave
     static constexpr int pooled_unroll_4 = DIM4 == 16 ? 2 : 1;                    // ... four bags per wave
 };
+// FTRL-Proximal's step arguments (SPEC.md §4): lr finite and > 0; beta, l1, l2 neither NaN nor negative (checked before any launch)
+inline bool ftrl_args_ok(float lr, float beta, float l1, float l2) { return lr > 0.f && lr < __builtin_inff() && beta >= 0.f && l1 >= 0.f && l2 >= 0.f; }
 
 }  // namespace mee
 

@@ -483,4 +483,17 @@ int mee_mixed_group_apply_adam_pooled(mee_mixed_group* g, const int64_t* d_keys,
                               });
 }
 
+int mee_mixed_group_apply_ftrl_pooled(mee_mixed_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table,
+                                      const float* d_bag_grads, const uint32_t* d_bag_of_position, const int64_t* d_located, size_t n, float lr,
+                                      float beta, float l1, float l2, void* stream) {
+    MEE_RANGE("mee_mixed_group_apply_ftrl_pooled");
+    if (!mee::ftrl_args_ok(lr, beta, l1, l2))   // before the first class's select launch
+        return fail(MEE_ERR_INVALID_ARG, "mee_mixed_group_apply_ftrl_pooled: lr must be finite and > 0; beta, l1 and l2 must be >= 0");
+    return mixed_apply_common(g, d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_bag_of_position, d_located, n, MEE_OPT_FTRL, stream,
+                              "mee_mixed_group_apply_ftrl_pooled",
+                              [&](mee_group* s, const int64_t* k, const uint64_t* o, const float* gr, const uint32_t* gi, const int64_t* loc) {
+                                  return mee_group_apply_ftrl_pooled(s, k, o, bags_per_table, gr, gi, loc, n, lr, beta, l1, l2, stream);
+                              });
+}
+
 }  // extern "C"

@@ -269,7 +269,7 @@ __global__ __launch_bounds__(256) void move_mark_grouped_kernel(const MoveTable*
 static MoveTable move_table_of(const mee_table* t) {
     return MoveTable{t->keys, {(float4*)t->values, (float4*)t->s1, (float4*)t->s2}, t->nb, &t->ctr->status, t->hits, t->g.sres};
 }
-static int planes_of(uint32_t optimizer) { return optimizer == MEE_OPT_ADAM ? 3 : optimizer == MEE_OPT_ADAGRAD ? 2 : 1; }
+static int planes_of(uint32_t optimizer) { return opt_has_s2(optimizer) ? 3 : optimizer == MEE_OPT_ADAGRAD ? 2 : 1; }
 
 // what a move refuses about one (src, dst) pair before anything is launched or written; `member` < 0: the pair of mee_move
 static int move_pair_check(const mee_table* s, const mee_table* d, size_t n, const char* name, int member) {

@@ -254,6 +254,7 @@ __global__ __launch_bounds__(256) void insert_direct_kernel(int64_t* tkeys, floa
                         values[o] = row[r][c];
                         if (optimizer == MEE_OPT_ADAGRAD) s1[o] = ia;
                         if (optimizer == MEE_OPT_ADAM) { s1[o] = z4; s2[o] = z4; }
+                        if (optimizer == MEE_OPT_FTRL) { s1[o] = z4; s2[o] = ia; }
                     }
                 } else {
                     for (uint32_t c = tl; c < dim4; c += 16) {
@@ -261,6 +262,7 @@ __global__ __launch_bounds__(256) void insert_direct_kernel(int64_t* tkeys, floa
                         values[o] = vals[(uint64_t)i * dim4 + c];
                         if (optimizer == MEE_OPT_ADAGRAD) s1[o] = ia;
                         if (optimizer == MEE_OPT_ADAM) { s1[o] = z4; s2[o] = z4; }
+                        if (optimizer == MEE_OPT_FTRL) { s1[o] = z4; s2[o] = ia; }
                     }
                 }
             }
@@ -450,6 +452,10 @@ __device__ __forceinline__ void ensure_direct_body(int64_t* tkeys, float4* value
                             s1[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
                             s2[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
                         }
+                        if (optimizer == MEE_OPT_FTRL) {
+                            s1[(uint64_t)slot * dim4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                            s2[(uint64_t)slot * dim4 + c] = make_float4(init_acc, init_acc, init_acc, init_acc);
+                        }
                     }
                 }
                 if (is_new && hits && tl == 0) hits[slot] = 0;
@@ -572,7 +578,7 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
         return fail(MEE_ERR_INVALID_ARG, "mee_table_create: struct_size %u != %zu (ABI mismatch)", cfg->struct_size, sizeof(mee_config));
     if (cfg->capacity == 0 || cfg->dim < 4 || cfg->dim > 1024 || (cfg->dim & 3))
         return fail(MEE_ERR_INVALID_ARG, "mee_table_create: capacity must be >0 and dim a multiple of 4 in [4,1024]");
-    if (cfg->optimizer > MEE_OPT_ADAM || cfg->initializer > MEE_INIT_UNIFORM || cfg->value_memory > MEE_MEM_HOST_PINNED ||
+    if (cfg->optimizer > MEE_OPT_FTRL || cfg->initializer > MEE_INIT_UNIFORM || cfg->value_memory > MEE_MEM_HOST_PINNED ||
         (cfg->flags & ~(uint32_t)(MEE_FLAG_TRACK_HITS | MEE_FLAG_ADMISSION | MEE_FLAG_BF16_ROWS | MEE_FLAG_INT8_ROWS)) != 0)
         return fail(MEE_ERR_INVALID_ARG, "mee_table_create: bad optimizer/initializer/value_memory");
     if (cfg->flags & MEE_FLAG_INT8_ROWS) {   // a serving table: SPEC.md §3 "Row storage type" (the rules of MEE_FLAG_BF16_ROWS, and dim % 16)
@@ -669,7 +675,7 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
     }
     ALLOC_PLANE(t->values);
     if (t->optimizer != MEE_OPT_NONE) ALLOC_PLANE(t->s1);
-    if (t->optimizer == MEE_OPT_ADAM) ALLOC_PLANE(t->s2);
+    if (opt_has_s2(t->optimizer)) ALLOC_PLANE(t->s2);
 #undef ALLOC_PLANE
     ALLOC(t->g.ent, S * 16); ALLOC(t->g.sres, S * 8);
     ALLOC(t->bs.hidx, mb * 4); ALLOC(t->bs.occ, mb * 4); ALLOC(t->bs.fmask, mb);
@@ -1201,6 +1207,68 @@ int mee_apply_adam_indexed(mee_table* t, const int64_t* d_keys, const float* d_g
     OptArgs a = adam_args(lr, beta1, beta2, eps, step);
     a.grad_rows = (uint32_t)n_grad_rows;
     return apply_common(t, d_keys, d_grads, n, a, stream, "mee_apply_adam_indexed", d_grad_index);
+}
+
+// FTRL-Proximal (SPEC.md §4): z in plane 1, n in plane 2; lr, beta, l1, l2 travel in the argument block as they are
+static int ftrl_args(OptArgs& a, float lr, float beta, float l1, float l2, const char* name) {
+    if (!ftrl_args_ok(lr, beta, l1, l2))
+        return fail(MEE_ERR_INVALID_ARG, "%s: lr must be finite and > 0; beta, l1 and l2 must be >= 0 (got lr=%g beta=%g l1=%g l2=%g)", name, lr, beta, l1, l2);
+    a = OptArgs{};
+    a.kind = MEE_OPT_FTRL; a.lr = lr; a.eps = beta; a.omb1 = l1; a.omb2 = l2;
+    return MEE_OK;
+}
+int mee_apply_ftrl(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, float lr, float beta, float l1, float l2, void* stream) {
+    MEE_RANGE("mee_apply_ftrl");
+    OptArgs a;
+    if (int rc = ftrl_args(a, lr, beta, l1, l2, "mee_apply_ftrl")) return rc;
+    return apply_common(t, d_keys, d_grads, n, a, stream, "mee_apply_ftrl");
+}
+int mee_apply_ftrl_located(mee_table* t, const int64_t* d_keys, const int64_t* d_slots, const float* d_grads, size_t n, float lr, float beta, float l1,
+                           float l2, void* stream) {
+    MEE_RANGE("mee_apply_ftrl_located");
+    if (n && !d_slots) return fail(MEE_ERR_INVALID_ARG, "mee_apply_ftrl_located: null slots");
+    OptArgs a;
+    if (int rc = ftrl_args(a, lr, beta, l1, l2, "mee_apply_ftrl_located")) return rc;
+    return apply_common(t, d_keys, d_grads, n, a, stream, "mee_apply_ftrl_located", nullptr, d_slots);
+}
+int mee_apply_ftrl_indexed(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index, size_t n,
+                           float lr, float beta, float l1, float l2, void* stream) {
+    MEE_RANGE("mee_apply_ftrl_indexed");
+    if (int rc = check_grad_rows(n, d_grad_index, n_grad_rows, "mee_apply_ftrl_indexed")) return rc;
+    OptArgs a;
+    if (int rc = ftrl_args(a, lr, beta, l1, l2, "mee_apply_ftrl_indexed")) return rc;
+    a.grad_rows = (uint32_t)n_grad_rows;
+    return apply_common(t, d_keys, d_grads, n, a, stream, "mee_apply_ftrl_indexed", d_grad_index);
+}
+int mee_group_apply_ftrl(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr, float beta,
+                         float l1, float l2, void* stream) {
+    MEE_RANGE("mee_group_apply_ftrl");
+    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_ftrl");
+    OptArgs a;
+    if (int rc = ftrl_args(a, lr, beta, l1, l2, "mee_group_apply_ftrl")) return rc;
+    return group_apply_common(g, d_keys, d_offsets, d_grads, n, a, stream, "mee_group_apply_ftrl");
+}
+int mee_group_apply_ftrl_pooled(mee_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_bag_grads,
+                                const uint32_t* d_grad_index, const int64_t* d_located, size_t n, float lr, float beta, float l1, float l2,
+                                void* stream) {
+    MEE_RANGE("mee_group_apply_ftrl_pooled");
+    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_ftrl_pooled");
+    if (n && (!d_grad_index || !bags_per_table)) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_ftrl_pooled: null index / zero bags_per_table");
+    OptArgs a;
+    if (int rc = ftrl_args(a, lr, beta, l1, l2, "mee_group_apply_ftrl_pooled")) return rc;
+    a.grad_rows = g ? (uint32_t)(g->n_tables * bags_per_table) : 0;   // one grad row per bag
+    return group_apply_common(g, d_keys, d_bag_offsets, d_bag_grads, n, a, stream, "mee_group_apply_ftrl_pooled", bags_per_table, d_grad_index,
+                              d_located);
+}
+int mee_group_apply_ftrl_indexed(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows,
+                                 const uint32_t* d_grad_index, size_t n, float lr, float beta, float l1, float l2, void* stream) {
+    MEE_RANGE("mee_group_apply_ftrl_indexed");
+    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_ftrl_indexed");
+    if (int rc = check_grad_rows(n, d_grad_index, n_grad_rows, "mee_group_apply_ftrl_indexed")) return rc;
+    OptArgs a;
+    if (int rc = ftrl_args(a, lr, beta, l1, l2, "mee_group_apply_ftrl_indexed")) return rc;
+    a.grad_rows = (uint32_t)n_grad_rows;
+    return group_apply_common(g, d_keys, d_offsets, d_grads, n, a, stream, "mee_group_apply_ftrl_indexed", 1, d_grad_index);
 }
 
 /* duplicate-key reduction with row sums, sync-free (meepo_dedup.hip): see include/meepo_embedding.h */

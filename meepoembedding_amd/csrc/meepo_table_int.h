@@ -198,8 +198,8 @@ __device__ __forceinline__ void group_pair_tables(const GroupDesc* __restrict__ 
 // ---- sparse optimizers (SPEC.md §4) ------------------------------------------------------------------------
 struct OptArgs {
     uint32_t kind;       // MEE_OPT_*
-    float lr, eps;       // adagrad: lr; adam: lr unused (step_size)
-    float step_size, omb1, omb2;
+    float lr, eps;       // adagrad: lr; adam: lr unused (step_size); ftrl: lr, eps = beta
+    float step_size, omb1, omb2;   // ftrl: omb1 = l1, omb2 = l2 (fields it has no other use for: the Adagrad and Adam kernels' argument block stays as it is)
     uint32_t grad_rows;  // indexed apply: rows of the grad array (indices are clamped to it: caller data never reads out of bounds)
 };
 
@@ -207,6 +207,9 @@ __device__ __forceinline__ void opt_update4(const OptArgs& a, float4& w, float4&
     if (a.kind == MEE_OPT_ADAGRAD) {
         adagrad1(w.x, x1.x, g.x, a.lr, a.eps); adagrad1(w.y, x1.y, g.y, a.lr, a.eps);
         adagrad1(w.z, x1.z, g.z, a.lr, a.eps); adagrad1(w.w, x1.w, g.w, a.lr, a.eps);
+    } else if (a.kind == MEE_OPT_FTRL) {
+        ftrl1(w.x, x1.x, x2.x, g.x, a.lr, a.eps, a.omb1, a.omb2); ftrl1(w.y, x1.y, x2.y, g.y, a.lr, a.eps, a.omb1, a.omb2);
+        ftrl1(w.z, x1.z, x2.z, g.z, a.lr, a.eps, a.omb1, a.omb2); ftrl1(w.w, x1.w, x2.w, g.w, a.lr, a.eps, a.omb1, a.omb2);
     } else {
         adam1(w.x, x1.x, x2.x, g.x, a.step_size, a.omb1, a.omb2, a.eps);
         adam1(w.y, x1.y, x2.y, g.y, a.step_size, a.omb1, a.omb2, a.eps);
@@ -217,10 +220,10 @@ __device__ __forceinline__ void opt_update4(const OptArgs& a, float4& w, float4&
 
 __device__ __forceinline__ void update_row(const OptArgs& a, float4* values, float4* s1, float4* s2, uint64_t o, const float4 g) {
     float4 w = values[o], x1 = s1[o], x2 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.kind == MEE_OPT_ADAM) x2 = s2[o];
+    if (opt_has_s2(a.kind)) x2 = s2[o];
     opt_update4(a, w, x1, x2, g);
     values[o] = w; s1[o] = x1;
-    if (a.kind == MEE_OPT_ADAM) s2[o] = x2;
+    if (opt_has_s2(a.kind)) s2[o] = x2;
 }
 // the bucketed apply path (meepo_apply.hip)
 uint32_t xcd_split_for_device(int device);   // the calibrated share of a bucket pair's hash range that goes to the even bucket (0 = even halves)

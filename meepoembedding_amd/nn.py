@@ -22,6 +22,8 @@ Reference anchor: /root/reference/README.md:2 ("Embedding designed for recommend
 
 What a table declares (tables are duck-typed; _traits() reads all of it once, when a layer is built, and nothing else here looks at a table's
 type or attributes).  Always: dim, find, find_or_insert, apply_adagrad, apply_adam with LookupTable's (a group: TableGroup's) parameters.
+    apply_ftrl                          optimizer="ftrl" can be served (a group instead: its apply_pooled / apply_indexed take l1=, l2=, and apply_ftrl serves
+                                        the collection layer); without it a layer built with optimizer="ftrl" is refused at construction
 Class-level flags, with the default that holds when a class says nothing:
     supports_out_dtype = False          its lookups take out_dtype=torch.bfloat16
     supports_pooled_out_dtype = False   its find_pooled does, though its find does not (may be set per instance: TieredLookupTable)
@@ -43,6 +45,7 @@ Optional methods:
 """
 from __future__ import annotations
 
+import inspect
 import itertools
 import weakref
 from typing import Callable, NamedTuple
@@ -68,6 +71,7 @@ class _Traits(NamedTuple):
     hot_cold_pair: bool
     has_epoch: bool
     admission_refusal: Callable[[], str | None] | None
+    ftrl: bool                # optimizer="ftrl" can be served: apply_ftrl exists (a group: its apply_pooled takes l1= / l2=)
     native_padded: bool = False   # find_padded exists (one launch; pairs and tiered groups too); without it DynamicEmbeddingSequence composes find and a placement
     native_keyed: bool = False    # find_pooled(layout="keyed") exists (one launch writes [bags_per_table, sum of dims]); without it the bag layer composes a permute
 
@@ -80,10 +84,18 @@ def _traits(table) -> _Traits:
     if located_table and not hasattr(table, "_nn_prepared"):
         table._nn_prepared = None   # kept on the table, not on a layer: two layers over one table see each other's pending partition
     bf16_rows = bool(getattr(table, "supports_out_dtype", False))
+    ftrl = _takes_keyword(table.apply_pooled, "l1") if grouped else hasattr(table, "apply_ftrl")   # (a MixedTableGroup has the loose form alone)
     return _Traits(grouped, grouped and not inserts, located_table, inserts, bool(getattr(table, "weighted_bags", True)),
                    bool(getattr(table, "mixed_dims", False)), bf16_rows, bf16_rows or bool(getattr(table, "supports_pooled_out_dtype", False)),
-                   bool(getattr(table, "hot_cold_pair", False)), hasattr(table, "layout_epoch"), getattr(table, "admission_refusal", None),
+                   bool(getattr(table, "hot_cold_pair", False)), hasattr(table, "layout_epoch"), getattr(table, "admission_refusal", None), ftrl,
                    hasattr(table, "find_padded"), bool(getattr(table, "keyed_bags", False)))
+
+
+def _takes_keyword(fn, name: str) -> bool:
+    try:
+        return name in inspect.signature(fn).parameters
+    except (TypeError, ValueError):
+        return False
 
 
 def _admit_kw(layer) -> dict:
@@ -106,6 +118,8 @@ def _layer(table_id: int) -> "_SparseLayer":
 def _step_now(layer) -> SparseStep:
     """the optimizer step a backward takes: the layer's settings as they are now (a schedule may have changed lr) and its next step number"""
     layer.step += 1
+    if layer.optimizer == "ftrl":   # eps is beta; the regularisation strengths stand in the beta slots
+        return SparseStep("ftrl", layer.lr, layer.eps, layer.l1, layer.l2, layer.step)
     return SparseStep(layer.optimizer, layer.lr, layer.eps, layer.betas[0], layer.betas[1], layer.step)
 
 
@@ -283,7 +297,7 @@ def apply_grad_pooled(keys: torch.Tensor, bag_offsets: torch.Tensor, grad_bags: 
         g = g / lens.clamp(min=1).to(torch.float32)[:, None]
     step = _step_now(layer)
     if layer.traits.grouped:   # a TableGroup: the whole collection in one step, on the rows the forward located
-        layer.table.apply_pooled(keys, bag_offsets, g, bag_of, *step, located=located if located.numel() == keys.numel() else None)
+        layer.table.apply_pooled(keys, bag_offsets, g, bag_of, *step, located=located if located.numel() == keys.numel() else None, **step.loose_kw())
     else:
         step.apply_to(layer.table, keys, g, grad_index=bag_of)
 
@@ -345,7 +359,8 @@ def apply_grad_pooled_mixed(keys: torch.Tensor, bag_offsets: torch.Tensor, grad_
         g = g.clone()
         for j, v in enumerate(group.views(g, bpt)):
             v /= inv[j * bpt:(j + 1) * bpt, None]
-    group.apply_pooled(keys, bag_offsets, g, bag_of, *_step_now(layer), located=located if located.numel() == keys.numel() else None)
+    step = _step_now(layer)
+    group.apply_pooled(keys, bag_offsets, g, bag_of, *step, located=located if located.numel() == keys.numel() else None, **step.loose_kw())
 
 
 @apply_grad_pooled_mixed.register_fake
@@ -406,14 +421,14 @@ def apply_grad_pooled_keyed(keys: torch.Tensor, bag_offsets: torch.Tensor, grad_
     loc = located if located.numel() == keys.numel() else None
     step = _step_now(layer)
     if layer.traits.mixed_dims:   # fp32 or bf16 as it came: the de-interleave launch widens and, for the mean, divides
-        group.apply_pooled(keys, bag_offsets, grad_keyed, step_index, *step, located=loc, layout="keyed", mean_offsets=bag_offsets if mean else None)
+        group.apply_pooled(keys, bag_offsets, grad_keyed, step_index, *step, located=loc, layout="keyed", mean_offsets=bag_offsets if mean else None, **step.loose_kw())
         return
     nt, bpt = len(group.tables), grad_keyed.shape[0]
     g = grad_keyed.view(bpt, nt, group.dim)
     if mean:   # d mean / d row = 1 / length: one division of the keyed block, bag j * B + s sits at [s, j]
         lens = (bag_offsets[1:] - bag_offsets[:-1]).clamp(min=1).to(torch.float32)
         g = g / lens.view(nt, bpt).t()[:, :, None]
-    group.apply_pooled(keys, bag_offsets, g.view(bpt * nt, group.dim), step_index, *step, located=loc)
+    group.apply_pooled(keys, bag_offsets, g.view(bpt * nt, group.dim), step_index, *step, located=loc, **step.loose_kw())
 
 
 @apply_grad_pooled_keyed.register_fake
@@ -591,7 +606,7 @@ def apply_grad_padded(step_keys: torch.Tensor, bag_offsets: torch.Tensor, grad_i
     if layer.traits.native_padded:
         if layer.traits.grouped:
             seg = _member_offsets(table, bag_offsets).to(torch.int64).clamp(min=0, max=step_keys.numel()).contiguous()
-            table.apply_indexed(step_keys, seg, g, grad_index, *step)
+            table.apply_indexed(step_keys, seg, g, grad_index, *step, **step.loose_kw())
         else:
             step.apply_to(table, step_keys, g, grad_index=grad_index)
         return
@@ -649,14 +664,19 @@ class _SparseLayer(torch.nn.Module):
     """What the three layers share: the registration under a table_id, the anchor that makes autograd run the backward, the table's traits, the
     checked out_dtype and min_count, and the optimizer step's settings with its counter (_step_now)."""
 
-    def __init__(self, table, optimizer, lr, eps, betas, out_dtype, min_count, pooled: bool = False, creates: bool = True, rows_layer: bool = False):
+    def __init__(self, table, optimizer, lr, eps, betas, out_dtype, min_count, pooled: bool = False, creates: bool = True, rows_layer: bool = False,
+                 l1: float = 0.0, l2: float = 0.0):
         super().__init__()
         name = type(self).__name__
         _refuse_narrow_rows(name, table)
         self.table, self.traits = table, _traits(table)
         self.min_count = _check_min_count(name, table, self.traits, min_count, creates, rows_layer, out_dtype)
-        first = SparseStep.of(optimizer, lr, eps, *betas, error=ValueError)   # checks the name, resolves the default eps
+        first = SparseStep.of(optimizer, lr, eps, *betas, error=ValueError, l1=l1, l2=l2)   # checks the name, resolves the default eps (ftrl: beta)
+        if optimizer == "ftrl" and not self.traits.ftrl:
+            raise ValueError(f"{name}: optimizer='ftrl' needs a table with apply_ftrl (a group: apply_pooled / apply_indexed with l1= and l2=); "
+                             f"{type(table).__name__} has none (the sharded tables keep Adagrad and Adam)")
         self.optimizer, self.lr, self.eps, self.betas, self.step = optimizer, lr, first.eps, betas, 0
+        self.l1, self.l2 = l1, l2   # FTRL's regularisation strengths (read by optimizer="ftrl" alone)
         if out_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16 (got {out_dtype})")
         if out_dtype != torch.float32 and not (self.traits.bf16_bags if pooled else self.traits.bf16_rows):
@@ -682,8 +702,9 @@ class DynamicEmbeddingCollection(_SparseLayer):
     then it reads the default row and its gradient is dropped by the step, which ignores absent keys.  Eval mode counts and creates nothing."""
 
     def __init__(self, group, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
-                 out_dtype: torch.dtype = torch.float32, min_count: int | None = None):
-        super().__init__(group, optimizer, lr, eps, betas, out_dtype, min_count)
+                 out_dtype: torch.dtype = torch.float32, min_count: int | None = None, l1: float = 0.0, l2: float = 0.0):
+        """optimizer="ftrl" (tables created with OPT_FTRL): eps is FTRL's beta (default 1.0), l1 / l2 its regularisation strengths; betas is not read."""
+        super().__init__(group, optimizer, lr, eps, betas, out_dtype, min_count, l1=l1, l2=l2)
         self.group = group
 
     def forward(self, keys: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
@@ -706,13 +727,15 @@ class DynamicEmbeddingBag(_SparseLayer):
     composes the table-major lookup and one permute, with the same results."""
 
     def __init__(self, table, mode: str = "sum", optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
-                 create_missing: bool = False, out_dtype: torch.dtype = torch.float32, min_count: int | None = None, layout: str = "table"):
-        """out_dtype=torch.bfloat16: the bag is accumulated in fp32 and the finished row rounded once by the lookup; backward widens the bf16 grad."""
+                 create_missing: bool = False, out_dtype: torch.dtype = torch.float32, min_count: int | None = None, layout: str = "table",
+                 l1: float = 0.0, l2: float = 0.0):
+        """out_dtype=torch.bfloat16: the bag is accumulated in fp32 and the finished row rounded once by the lookup; backward widens the bf16 grad.
+        optimizer="ftrl" (tables created with OPT_FTRL): eps is FTRL's beta (default 1.0), l1 / l2 its regularisation strengths; betas is not read."""
         if mode not in ("sum", "mean"):
             raise ValueError("mode must be 'sum' or 'mean'")
         if layout not in ("table", "keyed"):
             raise ValueError(f"layout must be 'table' or 'keyed' (got {layout!r})")
-        super().__init__(table, optimizer, lr, eps, betas, out_dtype, min_count, pooled=True, creates=create_missing)
+        super().__init__(table, optimizer, lr, eps, betas, out_dtype, min_count, pooled=True, creates=create_missing, l1=l1, l2=l2)
         if layout == "keyed" and not self.traits.grouped:
             raise ValueError(f"layout='keyed' is a group's layout: {type(table).__name__} is one table (or one pair), whose [n_bags, dim] is keyed already")
         self.mode, self.create_missing, self.layout = mode, create_missing, layout
@@ -757,12 +780,12 @@ class DynamicEmbeddingSequence(_SparseLayer):
     the ids); otherwise absent ids read the default row and are not trained."""
 
     def __init__(self, table_or_group, max_len: int, keep: str = "first", optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None,
-                 betas=(0.9, 0.999), create_missing: bool = True, out_dtype: torch.dtype = torch.float32):
+                 betas=(0.9, 0.999), create_missing: bool = True, out_dtype: torch.dtype = torch.float32, l1: float = 0.0, l2: float = 0.0):
         if keep not in ("first", "last"):
             raise ValueError(f"keep must be 'first' or 'last' (got {keep!r})")
         if int(max_len) < 1:
             raise ValueError(f"max_len must be at least 1 (got {max_len})")
-        super().__init__(table_or_group, optimizer, lr, eps, betas, out_dtype, None)
+        super().__init__(table_or_group, optimizer, lr, eps, betas, out_dtype, None, l1=l1, l2=l2)
         self.max_len, self.keep, self.create_missing = int(max_len), keep, create_missing
 
     def forward(self, keys: torch.Tensor, bag_offsets: torch.Tensor):
@@ -779,8 +802,9 @@ class DynamicEmbedding(_SparseLayer):
     hot/cold pair: a DynamicEmbeddingCollection over TieredTableGroup([pair]) admits."""
 
     def __init__(self, table, optimizer: str = "adagrad", lr: float = 0.01, eps: float | None = None, betas=(0.9, 0.999),
-                 out_dtype: torch.dtype = torch.float32, min_count: int | None = None):
-        super().__init__(table, optimizer, lr, eps, betas, out_dtype, min_count, rows_layer=True)
+                 out_dtype: torch.dtype = torch.float32, min_count: int | None = None, l1: float = 0.0, l2: float = 0.0):
+        """optimizer="ftrl" (a table created with OPT_FTRL): eps is FTRL's beta (default 1.0), l1 / l2 its regularisation strengths; betas is not read."""
+        super().__init__(table, optimizer, lr, eps, betas, out_dtype, min_count, rows_layer=True, l1=l1, l2=l2)
         self.fuse_backward_partition = True   # see forward()
 
     def forward(self, keys: torch.Tensor) -> torch.Tensor:

@@ -15,7 +15,7 @@ from typing import NamedTuple
 import torch
 
 from . import _lib
-from ._lib import (INIT_CONSTANT, INIT_UNIFORM, OPT_ADAGRAD, OPT_ADAM, OPT_NONE, STATUS_RESERVED_KEY,  # noqa: F401
+from ._lib import (INIT_CONSTANT, INIT_UNIFORM, OPT_ADAGRAD, OPT_ADAM, OPT_FTRL, OPT_NONE, STATUS_RESERVED_KEY,  # noqa: F401
                    STATUS_TABLE_FULL, MeepoError, check)
 
 
@@ -190,37 +190,67 @@ def _find_padded_composed(find_kept, dim: int, keys: torch.Tensor, bag_offsets: 
 
 class SparseStep(NamedTuple):
     """One sparse optimizer step as a value: which optimizer and its scalars.  The table classes build it once per call and forward it; nothing
-    else in the package tells the optimizers apart.  The fields stand in the order of apply_pooled / apply_indexed's loose form, so `*step` is it."""
-    kind: str            # "adagrad" | "adam"
+    else in the package tells the optimizers apart.  The fields stand in the order of apply_pooled / apply_indexed's loose form, so `*step` is it.
+    FTRL-Proximal (kind "ftrl") has four scalars and uses the same six fields: eps carries beta, the two beta slots carry l1 and l2 (read them as
+    .l1 / .l2), step is unused."""
+    kind: str            # "adagrad" | "adam" | "ftrl"
     lr: float
-    eps: float
-    beta1: float = 0.9   # (Adam only, like beta2 and step)
-    beta2: float = 0.999
+    eps: float           # (ftrl: beta)
+    beta1: float = 0.9   # (Adam only, like beta2 and step; ftrl: l1)
+    beta2: float = 0.999   # (ftrl: l2)
     step: int = 1
 
     @classmethod
-    def of(cls, optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1, error=None) -> "SparseStep":
+    def of(cls, optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1, error=None, *,
+           l1: float = 0.0, l2: float = 0.0) -> "SparseStep":
         """from the loose form apply_pooled / apply_indexed and the nn layers take: the one place that checks the optimizer's name and resolves
-        the default eps (1e-10 for Adagrad, 1e-8 for Adam).  error: the caller's exception class for an unknown name (ValueError in the host-logic
-        classes); without it MeepoError(ERR_INVALID_ARG), as the library's wrappers raise."""
-        if optimizer not in ("adagrad", "adam"):
-            msg = f"optimizer must be 'adagrad' or 'adam' (got {optimizer!r})"
+        the default eps (1e-10 for Adagrad, 1e-8 for Adam; FTRL's beta: 1.0).  For "ftrl" the regularisation strengths come from l1 / l2 alone:
+        beta1 / beta2 are ignored, so that Adam's defaults can never become one.  error: the caller's exception class for an unknown name
+        (ValueError in the host-logic classes); without it MeepoError(ERR_INVALID_ARG), as the library's wrappers raise."""
+        if optimizer not in ("adagrad", "adam", "ftrl"):
+            msg = f"optimizer must be 'adagrad' or 'adam' or 'ftrl' (got {optimizer!r})"
             raise error(msg) if error is not None else MeepoError(_lib.ERR_INVALID_ARG, msg)
+        if optimizer == "ftrl":
+            return cls("ftrl", lr, 1.0 if eps is None else eps, l1, l2, step)
         if eps is None:
             eps = 1e-10 if optimizer == "adagrad" else 1e-8
         return cls(optimizer, lr, eps, beta1, beta2, step)
 
+    @classmethod
+    def ftrl(cls, lr: float, beta: float = 1.0, l1: float = 0.0, l2: float = 0.0) -> "SparseStep":
+        """the FTRL-Proximal step of apply_ftrl's direct form"""
+        return cls("ftrl", lr, beta, l1, l2)
+
+    @property
+    def l1(self) -> float:
+        """FTRL's lambda1 (the beta1 slot)"""
+        return self.beta1
+
+    @property
+    def l2(self) -> float:
+        """FTRL's lambda2 (the beta2 slot)"""
+        return self.beta2
+
+    def loose_kw(self) -> dict:
+        """the keywords the loose form needs beside `*step`: FTRL's l1 / l2 (its beta slots are not read there); nothing for the other two"""
+        return {"l1": self.beta1, "l2": self.beta2} if self.kind == "ftrl" else {}
+
     def tail(self) -> tuple:
-        """the step's own arguments in the order of the C-ABI — and of apply_adagrad / apply_adam's positional parameters"""
-        return (self.lr, self.eps) if self.kind == "adagrad" else (self.lr, self.beta1, self.beta2, self.eps, self.step)
+        """the step's own arguments in the order of the C-ABI — and of apply_adagrad / apply_adam / apply_ftrl's positional parameters
+        (ftrl: lr, beta, l1, l2)"""
+        if self.kind == "adagrad":
+            return (self.lr, self.eps)
+        if self.kind == "ftrl":
+            return (self.lr, self.eps, self.beta1, self.beta2)
+        return (self.lr, self.beta1, self.beta2, self.eps, self.step)
 
     def launch(self, stem: str, form: str, *args, stream: int) -> None:
         """the C entry point {stem}_{kind}{form} — mee_apply_adam_located, mee_group_apply_adagrad_pooled, … — on (args…, tail…, stream)"""
         check(getattr(_lib.lib(), f"{stem}_{self.kind}{form}")(*args, *self.tail(), stream))
 
     def apply_to(self, table, *args, **kw) -> None:
-        """table.apply_adagrad / table.apply_adam(args…, tail…, **kw): any object with the two methods (a CPU test adapter, a peer-mapped table, a
-        foreign `local`) takes the step by their positional order"""
+        """table.apply_adagrad / table.apply_adam / table.apply_ftrl(args…, tail…, **kw): any object with the methods (a CPU test adapter, a
+        peer-mapped table, a foreign `local`) takes the step by their positional order"""
         getattr(table, "apply_" + self.kind)(*args, *self.tail(), **kw)
 
 
@@ -513,7 +543,7 @@ class LookupTable:
         return found
 
     def find_plane(self, plane: int, keys: torch.Tensor):
-        """find on one plane: 0 = values, 1 = acc | m, 2 = v."""
+        """find on one plane: 0 = values, 1 = acc | m | z, 2 = v | n."""
         k = self._keys(keys)
         n = k.numel()
         out = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
@@ -666,7 +696,7 @@ class LookupTable:
         keys = torch.empty(n, dtype=torch.int64, device=self.device)
         vals = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
         s1 = torch.empty((n, self.dim), dtype=torch.float32, device=self.device) if with_state and self.optimizer != OPT_NONE else None
-        s2 = torch.empty((n, self.dim), dtype=torch.float32, device=self.device) if with_state and self.optimizer == OPT_ADAM else None
+        s2 = torch.empty((n, self.dim), dtype=torch.float32, device=self.device) if with_state and self.optimizer in (OPT_ADAM, OPT_FTRL) else None
         m = C.c_size_t()
         check(_lib.lib().mee_export(self._h, keys.data_ptr(), vals.data_ptr(), s1.data_ptr() if s1 is not None else None,
                                     s2.data_ptr() if s2 is not None else None, n, C.byref(m), self._s()))
@@ -682,7 +712,7 @@ class LookupTable:
         keys = torch.empty(cap, dtype=torch.int64, device=self.device)
         vals = torch.empty((cap, self.dim), dtype=torch.float32, device=self.device)
         s1 = torch.empty((cap, self.dim), dtype=torch.float32, device=self.device) if with_state and self.optimizer != OPT_NONE else None
-        s2 = torch.empty((cap, self.dim), dtype=torch.float32, device=self.device) if with_state and self.optimizer == OPT_ADAM else None
+        s2 = torch.empty((cap, self.dim), dtype=torch.float32, device=self.device) if with_state and self.optimizer in (OPT_ADAM, OPT_FTRL) else None
         m = C.c_size_t()
         check(_lib.lib().mee_export_range(self._h, slot_begin, slot_end, keys.data_ptr(), vals.data_ptr(),
                                           s1.data_ptr() if s1 is not None else None, s2.data_ptr() if s2 is not None else None,
@@ -713,7 +743,7 @@ class LookupTable:
         if spill:
             rows = lambda: torch.empty((cap, self.dim), dtype=torch.float32, device=self.device)
             bufs = [torch.empty(cap, dtype=torch.int64, device=self.device), rows(),
-                    rows() if with_state and self.optimizer != OPT_NONE else None, rows() if with_state and self.optimizer == OPT_ADAM else None,
+                    rows() if with_state and self.optimizer != OPT_NONE else None, rows() if with_state and self.optimizer in (OPT_ADAM, OPT_FTRL) else None,
                     torch.empty(cap, dtype=torch.uint32, device=self.device)]
         n_out = torch.empty(1, dtype=torch.int64, device=self.device)
         flags = (_lib.EVICT_LEAST if least else 0) | (_lib.EVICT_RESET if reset else 0)
@@ -828,6 +858,12 @@ class LookupTable:
                    eps: float = 1e-8, step: int = 1, grad_index: torch.Tensor | None = None, slots: torch.Tensor | None = None) -> None:
         self._apply(SparseStep("adam", lr, eps, beta1, beta2, step), keys, grads, grad_index, slots)
 
+    def apply_ftrl(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, beta: float = 1.0, l1: float = 0.0, l2: float = 0.0,
+                   grad_index: torch.Tensor | None = None, slots: torch.Tensor | None = None) -> None:
+        """One FTRL-Proximal step (SPEC.md §4) on a table created with optimizer=OPT_FTRL: lr and beta set the per-coordinate learning rate
+        lr / (beta + sqrt(n)), l1 drives coordinates to exactly 0.0, l2 shrinks the rest.  grad_index / slots as apply_adagrad's."""
+        self._apply(SparseStep.ftrl(lr, beta, l1, l2), keys, grads, grad_index, slots)
+
     def _apply(self, step: SparseStep, keys, grads, grad_index, slots) -> None:
         """the three forms of the step: on the forward's slot handles, on indexed gradient rows, or plain"""
         k = self._keys(keys)
@@ -845,7 +881,7 @@ class LookupTable:
 
     def apply_prepare(self, keys: torch.Tensor) -> None:
         """Group + plan the next apply of `keys` ahead of time (needs no grads; may run on a side stream).  The next
-        apply_adagrad / apply_adam must be given the same tensor."""
+        apply_adagrad / apply_adam / apply_ftrl must be given the same tensor."""
         k = self._keys(keys)
         check(_lib.lib().mee_apply_prepare(self._h, k.data_ptr(), k.numel(), self._s()))
 
@@ -986,6 +1022,11 @@ class TableGroup:
                    beta2: float = 0.999, eps: float = 1e-8, step: int = 1) -> None:
         self._apply(SparseStep("adam", lr, eps, beta1, beta2, step), keys, offsets, grads)
 
+    def apply_ftrl(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, beta: float = 1.0, l1: float = 0.0,
+                   l2: float = 0.0) -> None:
+        """One FTRL-Proximal step over the jagged batch == apply_ftrl per table (members created with optimizer=OPT_FTRL)."""
+        self._apply(SparseStep.ftrl(lr, beta, l1, l2), keys, offsets, grads)
+
     def _apply(self, step: SparseStep, keys, offsets, grads, index=None, pooled: bool = False, located=None) -> None:
         """the three forms of the grouped step: a gradient row per position over member segments (`offsets` = the n_tables + 1 bounds), indexed rows
         over member segments, or a pooled lookup's backward (`offsets` = its bag_offsets, index = the bag of every position)"""
@@ -1075,14 +1116,15 @@ class TableGroup:
 
     def apply_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, bag_grads: torch.Tensor, bag_of_position: torch.Tensor,
                      optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1,
-                     located: torch.Tensor | None = None) -> None:
+                     located: torch.Tensor | None = None, *, l1: float = 0.0, l2: float = 0.0) -> None:
         """Backward of find_pooled over the group: one optimizer step, position i takes row bag_of_position[i] of bag_grads.
+        optimizer "ftrl": eps is FTRL's beta (default 1.0), l1 / l2 its regularisation strengths; beta1 / beta2 / step are not read.
         located = the buffer the forward find_pooled of this step filled: skips the probe pass.
         After find_pooled(layout="keyed", step_index=idx): bag_grads = the keyed gradient [bags_per_table, n_tables * dim] viewed
         .view(bags_per_table * n_tables, dim), bag_of_position = idx — the step reads the keyed gradient where it lies."""
         if bag_grads.dim() == 2 and bag_grads.shape[1] != self.dim:   # (a keyed gradient handed over without its view would be read as rows of `dim`)
             raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_grads must be [rows, {self.dim}] (a keyed gradient: .view(-1, {self.dim}))")
-        self._apply(SparseStep.of(optimizer, lr, eps, beta1, beta2, step), keys, bag_offsets, bag_grads, bag_of_position, pooled=True, located=located)
+        self._apply(SparseStep.of(optimizer, lr, eps, beta1, beta2, step, l1=l1, l2=l2), keys, bag_offsets, bag_grads, bag_of_position, pooled=True, located=located)
 
     # -- the same collection with a different number of bags per member (the owner's side of ShardedTableGroup's bags) --------
     def find_pooled_jagged(self, keys: torch.Tensor, bag_offsets: torch.Tensor, member_bags: torch.Tensor, mode: str = "sum",
@@ -1116,10 +1158,10 @@ class TableGroup:
         return out, found
 
     def apply_indexed(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, grad_index: torch.Tensor, optimizer: str, lr: float,
-                      eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1) -> None:
+                      eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1, *, l1: float = 0.0, l2: float = 0.0) -> None:
         """One optimizer step over the jagged batch == LookupTable.apply_*(grad_index=...) per member with its segment: position i takes row
-        grad_index[i] of grads [rows, dim]."""
-        self._apply(SparseStep.of(optimizer, lr, eps, beta1, beta2, step), keys, offsets, grads, grad_index)
+        grad_index[i] of grads [rows, dim].  optimizer "ftrl": eps is beta, l1 / l2 as apply_pooled's."""
+        self._apply(SparseStep.of(optimizer, lr, eps, beta1, beta2, step, l1=l1, l2=l2), keys, offsets, grads, grad_index)
 
     def pooled_weighted_backward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, weights: torch.Tensor, bag_grads: torch.Tensor,
                                  located: torch.Tensor | None = None, want_weight_grads: bool = True, grads: torch.Tensor | None = None,
@@ -1344,13 +1386,14 @@ class MixedTableGroup:
 
     def apply_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, bag_grads: torch.Tensor, bag_of_position: torch.Tensor,
                      optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1,
-                     located: torch.Tensor | None = None, layout: str = "table", mean_offsets: torch.Tensor | None = None) -> None:
+                     located: torch.Tensor | None = None, l1: float = 0.0, l2: float = 0.0, layout: str = "table",
+                     mean_offsets: torch.Tensor | None = None) -> None:
         """Backward of find_pooled: one optimizer step, position i takes the row of bag bag_of_position[i] (its index in the caller's order)
         of bag_grads — a flat fp32 buffer in the lookup's class-major layout.  located = the buffer the forward of this step filled.
         layout="keyed": bag_grads is the keyed gradient [bags_per_table, sum(dims)] (fp32 or bf16, stride(1) == 1), bag_of_position the step_index of
         the keyed lookup; one launch (mee_mixed_group_keyed_grads) takes it apart into the group's class-major step buffer first.  mean_offsets (the
         lookup's bag_offsets; keyed only): the backward of mode "mean" — row b is divided by max(len(b), 1) on the way."""
-        step = SparseStep.of(optimizer, lr, eps, beta1, beta2, step)
+        step = SparseStep.of(optimizer, lr, eps, beta1, beta2, step, l1=l1, l2=l2)   # ("ftrl": eps is beta, l1 / l2 the regularisation strengths)
         keyed = _check_layout(layout)
         bpt = self._check_bags(bag_offsets)
         k = self.tables[0]._keys(keys) if keys.numel() else keys

@@ -313,6 +313,11 @@ class TieredLookupTable:
                    eps: float = 1e-8, step: int = 1, grad_index: torch.Tensor | None = None) -> None:
         self._apply(SparseStep("adam", lr, eps, beta1, beta2, step), keys, grads, grad_index)
 
+    def apply_ftrl(self, keys: torch.Tensor, grads: torch.Tensor, lr: float, beta: float = 1.0, l1: float = 0.0, l2: float = 0.0,
+                   grad_index: torch.Tensor | None = None) -> None:
+        """The FTRL-Proximal step (tiers created with OPT_FTRL) on the tier that holds each key; z and n travel with a row when it changes tier."""
+        self._apply(SparseStep.ftrl(lr, beta, l1, l2), keys, grads, grad_index)
+
     def _apply(self, step: SparseStep, keys, grads, grad_index) -> None:
         # a key lives in one tier and each table ignores keys it does not hold: both see the whole batch.  grad_index (one int per key: position i
         # takes row grad_index[i] of grads — a pooled lookup's bag) goes to both as well; a key's duplicates are reduced in the one tier that holds it
@@ -399,7 +404,7 @@ class TieredLookupTable:
             return 0
         k = keys[idx]
         dst.insert(k, vals[idx])                         # state planes of new keys start at their initial values …
-        n_planes = {0: 0, 1: 1, 2: 2}[self.optimizer]
+        n_planes = {0: 0, 1: 1, 2: 2, 3: 2}[self.optimizer]   # (Adam and FTRL keep two state planes)
         for plane in range(1, n_planes + 1):             # … and are then overwritten with the migrated state
             st, _ = src.find_plane(plane, k)
             dst.assign_plane(plane, k, st)
@@ -419,7 +424,7 @@ class TieredLookupTable:
             return 0
         k = keys[idx]
         hs = slots[idx].cpu().numpy()                     # synchronises: the host needs the slot list
-        n_planes = {0: 0, 1: 1, 2: 2}[self.optimizer]
+        n_planes = {0: 0, 1: 1, 2: 2, 3: 2}[self.optimizer]   # (Adam and FTRL keep two state planes)
         if not hasattr(self, "_side"):
             self._side = torch.cuda.Stream(self.device)
         staged = []
@@ -918,13 +923,19 @@ class TieredTableGroup:
                    eps: float = 1e-8, step: int = 1) -> None:
         self._apply(SparseStep("adam", lr, eps, beta1, beta2, step), keys, offsets, grads)
 
+    def apply_ftrl(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, lr: float, beta: float = 1.0, l1: float = 0.0,
+                   l2: float = 0.0) -> None:
+        """The pairs' FTRL-Proximal step per member over the jagged batch, as the two grouped steps of apply_adagrad."""
+        self._apply(SparseStep.ftrl(lr, beta, l1, l2), keys, offsets, grads)
+
     def apply_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, bag_grads: torch.Tensor, bag_of_position: torch.Tensor,
                      optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1,
-                     located: torch.Tensor | None = None) -> None:
+                     located: torch.Tensor | None = None, *, l1: float = 0.0, l2: float = 0.0) -> None:
         """Backward of find_pooled: the pair's step per member — position i takes row bag_of_position[i] of bag_grads — as TWO grouped steps, the hot
         group's and the cold group's (a key lives in one tier, and a group ignores the keys its member does not hold), then every pair's
-        rebalance_every bookkeeping.  `located` is accepted for the bag layer's sake and not used: the tiered lookup hands out no located rows."""
-        self._apply(SparseStep.of(optimizer, lr, eps, beta1, beta2, step, error=ValueError), keys, bag_offsets, bag_grads, bag_of_position, pooled=True)
+        rebalance_every bookkeeping.  `located` is accepted for the bag layer's sake and not used: the tiered lookup hands out no located rows.
+        optimizer "ftrl": eps is FTRL's beta (default 1.0), l1 / l2 its regularisation strengths."""
+        self._apply(SparseStep.of(optimizer, lr, eps, beta1, beta2, step, error=ValueError, l1=l1, l2=l2), keys, bag_offsets, bag_grads, bag_of_position, pooled=True)
 
     def _apply(self, step: SparseStep, keys, offsets, grads, index=None, pooled: bool = False) -> None:
         """the step's three forms (TableGroup._apply's) on both tiers; pairs that are not native tables take the pair's step on their slices"""
@@ -941,9 +952,9 @@ class TieredTableGroup:
             if index is None:
                 step.apply_to(g, keys, offsets, grads)
             elif pooled:
-                g.apply_pooled(keys, offsets, grads, index, *step)
+                g.apply_pooled(keys, offsets, grads, index, *step, **step.loose_kw())
             else:
-                g.apply_indexed(keys, offsets, grads, index, *step)
+                g.apply_indexed(keys, offsets, grads, index, *step, **step.loose_kw())
         for p in self.tables:
             p._after_optimizer_step()
 
@@ -1011,8 +1022,8 @@ class TieredTableGroup:
         return out, found
 
     def apply_indexed(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, grad_index: torch.Tensor, optimizer: str, lr: float,
-                      eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1) -> None:
+                      eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1, *, l1: float = 0.0, l2: float = 0.0) -> None:
         """One optimizer step over the jagged batch == the pair's apply_*(grad_index=...) per member with its segment: position i takes row
         grad_index[i] of grads [rows, dim].  TWO grouped indexed steps, the hot group's and the cold group's (a key lives in one tier, and a group
         ignores the keys its member does not hold — apply_pooled's argument), then every pair's rebalance_every bookkeeping."""
-        self._apply(SparseStep.of(optimizer, lr, eps, beta1, beta2, step, error=ValueError), keys, offsets, grads, grad_index)
+        self._apply(SparseStep.of(optimizer, lr, eps, beta1, beta2, step, error=ValueError, l1=l1, l2=l2), keys, offsets, grads, grad_index)
