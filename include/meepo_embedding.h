@@ -15,6 +15,12 @@
  *    stream reaches the op.  The library never frees or retains caller buffers.
  *  - All ops are asynchronous and stream-ordered unless marked [syncs].  No op allocates device memory after
  *    mee_table_create() (safe for hipGraph capture except the [syncs] ones).
+ *  - Captured finds: under stream capture, consecutive plain finds of ONE table (mee_find / mee_find_ex / mee_find_plane, fp32 rows and fp32
+ *    output) with nothing else captured on the stream between them may share ONE kernel node of the graph instead of one node each (the
+ *    per-launch latency is then paid once per node; up to 16 requests per node, and only requests whose output and key buffers are disjoint
+ *    from each other's).  What a replay leaves in memory is exactly what the chained launches leave; a capture sees fewer kernel nodes and
+ *    the kernel name find_many_kernel where an eager launch runs find_kernel.  mee_set_tuning("find_coalesce", 0), or MEE_FIND_COALESCE=0 in
+ *    the environment when the library is loaded, gives every captured find a node of its own; mee_find_capture_stats counts both kinds.
  *  - Return value: MEE_OK or a negative error code; mee_last_error() gives a thread-local message.
  *    Device-side conditions (table full, reserved key in a batch) set sticky bits read by mee_status().
  *  - Mutators (insert/assign/find_or_insert/apply_*), the duplicate reductions (dedup_keys/dedup_sum: they use the table's per-batch
@@ -123,7 +129,8 @@ int mee_clear(mee_table* t, void* stream);
  * the find grid, 0 = unbounded), "find_nt" (cache policy of a find: bit 0 streaming row loads, bit 1 streaming bucket loads, bit 2 cached
  * stores of the dense output; -1 = the library's rule: cached loads; cached stores while one call's output is <= 128 MB and the table's latest
  * lookups wrote to one buffer, streaming stores once their output buffers rotate (the distinct buffers of the last eight calls exceed 64 MB);
- * prefer mee_find_ex: the hint with the CALL),
+ * prefer mee_find_ex: the hint with the CALL), "find_coalesce" (1 = consecutive plain finds of a stream capture may share a kernel node — "captured
+ * finds" above —, 0 = one node per call; default 1),
  * "apply_bucket_max" (target positions per bucket of the apply, 1..352; 0 = the library's rule: one bucket per resident block slot, as many
  * rounds as the batch needs; the bucket COUNT never exceeds what the table's scratch was sized for at creation — the default rule at max_batch —, so a
  * small value on a batch near max_batch gives larger buckets than asked for), "apply_kernel" (-1 = the library's choice by the stream's skew, 0 = LEAN,
@@ -173,6 +180,9 @@ int mee_find_unordered(const mee_table* t, const int64_t* d_keys, size_t n, floa
  * 256K-key requests cost what one 1M-key lookup costs. */
 typedef struct mee_find_request { const int64_t* d_keys; size_t n; float* d_out; uint8_t* d_found; } mee_find_request;
 int mee_find_many(const mee_table* t, const mee_find_request* reqs, uint32_t count, void* stream);
+/* Read-only statistics of the rule "captured finds" above: how many plain finds of `t` issued under stream capture got a kernel node of their own
+ * (*nodes) and how many joined the node of the find in front of them (*merged), since the table was created.  Eager calls count as neither. */
+int mee_find_capture_stats(const mee_table* t, uint64_t* nodes, uint64_t* merged);
 /* mee_find that also reports where each key lives: d_slots_out[i] = an opaque slot handle, -1 for absent / reserved keys.  The
  * handles feed mee_apply_*_located of the SAME training step (forward find -> backward apply) and stay valid only until the next
  * call that can move or free a row of this table (mee_remove, mee_clear, mee_reserve; inserting OTHER keys is fine).  A handle carries

@@ -184,6 +184,7 @@ PROTOTYPES = {
     "mee_clear_status": (C.c_int, [_vp, _vp]),
     "mee_find_unordered": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "mee_find_many": (C.c_int, [_vp, C.POINTER(FindRequest), _u32, _vp]),
+    "mee_find_capture_stats": (C.c_int, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "mee_find_located": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "mee_find_or_insert_located": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "mee_find_located_prepare": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),

@@ -7,8 +7,10 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 
 #include "meepo_apply_part.h"
+#include "meepo_find_coalesce.h"
 
 
 namespace mee {
@@ -266,26 +268,38 @@ __global__ __launch_bounds__(kFindPrepareThreads, 8) void find_prepare_kernel(co
                            handle_tag);
 }
 
-// Several lookup requests of one table in ONE launch (mee_find_many): the per-launch latency floor (~5 us: dispatch + the dependent
-// chain of the first and last waves) is paid once for all of them, so four queued 256K-key requests run at the rate of one 1M-key
-// launch.  The request descriptors travel in the kernel argument; a block finds its request by its index (<= kMaxFindRequests entries).
-constexpr int kMaxFindRequests = 16;
-struct FindMany {
-    const int64_t* keys[kMaxFindRequests];
-    f32x4* out[kMaxFindRequests];
-    uint8_t* found[kMaxFindRequests];
-    uint64_t n[kMaxFindRequests];
-    uint32_t first_block[kMaxFindRequests + 1];
-    uint32_t count;
-};
+// Several lookup requests of one table in ONE launch (mee_find_many; consecutive finds of a stream capture: find_captured below): the per-launch
+// latency floor (~5 us: dispatch + the dependent chain of the first and last waves) is paid once for all of them, so four queued 256K-key requests
+// run at the rate of one 1M-key launch.  The request descriptors (FindMany, meepo_find_coalesce.h) travel in the kernel argument; a block finds its
+// request by its index.  A request's blocks stride over it like find_kernel's grid over its batch.
 template <int DIM4, int R, int NT>
 __global__ __launch_bounds__(256) void find_many_kernel(const int64_t* __restrict__ tkeys, const f32x4* __restrict__ values, uint64_t nb,
                                                         FindMany m, float defv, uint32_t dim4_rt) {
+    // The request of a block: how many of first_block[1..15] it has reached — behind the grid size the entries hold 0xFFFFFFFF (find_many_append) —, counted
+    // in straight-line code.  (A search loop cost a dependent scalar load per request in front of the block's own, the request's fields a round trip
+    // behind it, the block size and the table's planes two more: a launch of ONE request took 33.3 us where find_kernel takes 32.3.)  The empty asm
+    // statement wants every argument the block needs in a register: the scalar loads — request 0's fields among them — leave as ONE batch at the top
+    // and a block of request 0 starts after one round trip; the blocks of later requests load their fields in a second one, once q is known.
+    const int64_t* keys = m.keys[0];
+    uint64_t n = m.n[0];
+    f32x4* out = m.out[0];
+    uint8_t* found = m.found[0];
+    uint32_t fb[kMaxFindRequests];
+#pragma unroll
+    for (int i = 1; i < kMaxFindRequests; ++i) fb[i] = m.first_block[i];
+    uint32_t bdim = blockDim.x;
+    asm volatile("; find_many_kernel: arguments" : "+s"(tkeys), "+s"(values), "+s"(nb), "+s"(defv), "+s"(keys), "+s"(n), "+s"(out), "+s"(found), "+s"(bdim),
+                 "+s"(fb[1]), "+s"(fb[2]), "+s"(fb[3]), "+s"(fb[4]), "+s"(fb[5]), "+s"(fb[6]), "+s"(fb[7]));
     uint32_t q = 0;
-    while (q + 1 < m.count && blockIdx.x >= m.first_block[q + 1]) ++q;   // block-uniform
-    find_span<DIM4, R, NT>(tkeys, values, nb, m.keys[q], m.n[q], m.out[q], m.found[q], defv, dim4_rt, nullptr, nullptr,
-                           (uint64_t)(blockIdx.x - m.first_block[q]) * (blockDim.x >> 6) + (threadIdx.x >> 6),
-                           (uint64_t)(m.first_block[q + 1] - m.first_block[q]) * (blockDim.x >> 6));
+#pragma unroll
+    for (int i = 1; i < kMaxFindRequests; ++i) q += blockIdx.x >= fb[i];
+    uint32_t first = 0, end = fb[1];
+    if (q != 0) {   // block-uniform
+        keys = m.keys[q]; n = m.n[q]; out = m.out[q]; found = m.found[q];
+        first = m.first_block[q]; end = m.first_block[q + 1];
+    }
+    find_span<DIM4, R, NT>(tkeys, values, nb, keys, n, out, found, defv, dim4_rt, nullptr, nullptr,
+                           (uint64_t)(blockIdx.x - first) * (bdim >> 6) + (threadIdx.x >> 6), (uint64_t)(end - first) * (bdim >> 6));
 }
 
 // ---- sparse second pass (SPEC.md §3 find_missing; last pass of find_or_insert): only positions whose found byte is 0 -----
@@ -725,6 +739,101 @@ static bool outputs_rotate(const mee_table* t, const void* d_out, uint64_t bytes
     return distinct >= 2 && total > (64ull << 20);
 }
 
+// ---- captured finds: consecutive lookups of one table share a kernel node ---------------------------------------------------------------
+// A caller that records a queue of lookups into a hipGraph gets one kernel node per call, chained: each pays the per-launch floor (~4.6 us of a
+// 31 us 256K-key find), because consecutive nodes of an in-order stream do not overlap.  Under capture nothing has run yet, so the library can see
+// that a plain find's ONLY predecessor is its own earlier find of the same table, and serve both from that node: the node is a find_many_kernel
+// launch, and the later call extends its request descriptor instead of adding a node (one hipGraphKernelNodeSetParams call: the same function, the
+// by-value FindMany and the grid change).  The graph stays one linear chain with fewer, fatter nodes; what a replay leaves in memory is what the
+// chained launches leave.  A call joins the node in front of it only when
+//   - the stream's dependency set is exactly that node (nothing of ours or of anybody else's was captured in between, no fork or join),
+//   - table, plane pointers, bucket count, default value, kernel instance (row shape, keys in flight, the call's policy bits) and block size agree,
+//   - the descriptor has room and the request's buffers are disjoint from the node's (find_request_disjoint: chained launches that share a buffer
+//     have a defined winner, requests inside one kernel do not).
+// Otherwise the call starts the next node.  Any HIP error on the way: the call is launched the ordinary way and the capture is left alone from then on.
+// Eager launches never come here.  Off: mee_set_tuning("find_coalesce", 0), or MEE_FIND_COALESCE=0 in the environment (read when the library loads).
+// The two graph calls are weak references: a HIP runtime without them leaves every find a launch of its own.
+#pragma weak hipStreamGetCaptureInfo_v2
+#pragma weak hipGraphKernelNodeSetParams
+static std::mutex g_find_nodes_mu;
+static FindNodes g_find_nodes;   // (under g_find_nodes_mu)
+static const bool g_find_coalesce_env = [] { const char* e = getenv("MEE_FIND_COALESCE"); return !(e && e[0] == '0'); }();
+
+static bool stream_is_capturing(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
+}
+
+// the capturing stream's capture id and its dependency set when that is ONE node (else *dep = null); false: not capturing, or the query failed
+static bool capture_state(hipStream_t st, unsigned long long* id, hipGraph_t* graph, hipGraphNode_t* dep) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const hipGraphNode_t* deps = nullptr;
+    size_t n_deps = 0;
+    *id = 0; *graph = nullptr; *dep = nullptr;
+    if (hipStreamGetCaptureInfo_v2(st, &cs, id, graph, &deps, &n_deps) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (cs != hipStreamCaptureStatusActive || *id == 0) return false;
+    if (n_deps == 1 && deps) *dep = deps[0];
+    return true;
+}
+
+// One plain find of `n` keys on the capturing stream `st`, as `blocks` blocks of `block` threads of the find_many_kernel instance `func`.
+// true: the request is in the graph (it joined the node in front of it, or got a node of its own).  false: the caller launches find_kernel.
+static bool find_captured(const void* func, const mee_table* t, const float* plane, float defv, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found,
+                          unsigned block, unsigned blocks, hipStream_t st) {
+    mee_table* mt = const_cast<mee_table*>(t);   // (statistics only)
+    auto own_node = [&](bool launched) { __atomic_fetch_add(&mt->find_nodes, 1ull, __ATOMIC_RELAXED); return launched; };
+    if (!g_find_coalesce_env || !t->find_coalesce || !hipStreamGetCaptureInfo_v2 || !hipGraphKernelNodeSetParams) return own_node(false);
+    unsigned long long id;
+    hipGraph_t graph;
+    hipGraphNode_t dep;
+    if (!capture_state(st, &id, &graph, &dep)) return own_node(false);
+    std::lock_guard<std::mutex> lk(g_find_nodes_mu);
+    FindNode* r = g_find_nodes.get(id);
+    if (r && r->off) return own_node(false);
+    const int64_t* tkeys = t->keys;
+    const f32x4* values = (const f32x4*)plane;
+    uint64_t nb = t->nb;
+    uint32_t dim4 = t->dim4, defv_bits;
+    memcpy(&defv_bits, &defv, 4);
+    FindMany m;
+    void* args[6] = {&tkeys, &values, &nb, &m, &defv, &dim4};   // find_many_kernel's parameters, in order
+    if (r && r->node && dep == r->node && graph == r->graph && func == r->func && t == r->table && tkeys == r->tkeys && values == r->values && nb == r->nb &&
+        defv_bits == r->defv_bits && dim4 == r->dim4 && block == r->block) {
+        m = r->m;
+        if (find_request_disjoint(m, (uint64_t)t->dim * 4, d_keys, n, d_out, d_found) && find_many_append(m, d_keys, n, (f32x4*)d_out, d_found, blocks)) {
+            hipKernelNodeParams p;   // built completely before the one call that edits the node
+            memset(&p, 0, sizeof p);
+            p.func = const_cast<void*>(func);
+            p.gridDim = dim3(m.first_block[m.count]);
+            p.blockDim = dim3(block);
+            p.kernelParams = args;
+            if (hipGraphKernelNodeSetParams((hipGraphNode_t)r->node, &p) == hipSuccess) {
+                r->m = m;
+                __atomic_fetch_add(&mt->find_merged, 1ull, __ATOMIC_RELAXED);
+                return true;
+            }
+            (void)hipGetLastError();   // the node is as it was: this capture's finds are launches of their own from here on
+            r->off = true;
+            return own_node(false);
+        }
+    }
+    m = FindMany{};
+    (void)find_many_append(m, d_keys, n, (f32x4*)d_out, d_found, blocks);   // (n > 0 and 1 <= blocks <= 2^22: find_plane)
+    FindNode& e = g_find_nodes.put(id);
+    e.node = nullptr;   // whatever it named is no longer the stream's latest node
+    if (hipLaunchKernel(func, dim3(blocks), dim3(block), args, 0, st) != hipSuccess) {
+        (void)hipGetLastError();
+        e.off = true;
+        return own_node(false);
+    }
+    unsigned long long id2;
+    if (capture_state(st, &id2, &graph, &dep) && id2 == id && dep) {
+        e.graph = graph; e.node = dep; e.func = func; e.table = t; e.tkeys = tkeys; e.values = values; e.nb = nb;
+        e.defv_bits = defv_bits; e.dim4 = dim4; e.block = block; e.m = m;
+    }
+    return own_node(true);
+}
+
 // The launch shape of a pooled lookup.  n (the number of keys, a host value) only picks it: mostly short bags -> four bags per wave on a grid of
 // n_bags / 16 blocks, a long average (12 keys or more per bag) -> one bag per wave on n_bags / 4.  f(d4, unroll, bags_per_wave, grid).
 template <class F> void with_pooled_shape(uint32_t dim4, size_t n, uint64_t n_bags, F&& f) {
@@ -795,11 +904,14 @@ int find_plane(const mee_table* t, const float* plane, float miss_value, const i
         } else if (path.kind == FindPath::Counted) {   // sampled statistics pass: one key in flight per tile
             find(std::integral_constant<int, 1>{}, std::integral_constant<int, kFindCountHits | kFindCachedStores>{}, grid_for(n, 16, 1u << 22), 256, t->hits);
         } else {
+            // under stream capture a plain find joins the find node in front of it, or starts the next one (find_captured above); eager launches stay find_kernel's
+            const bool captured = path.kind == FindPath::Plain && stream_is_capturing(st);
             auto plain = [&](auto rr) { with_value<0, 1, 2, 3, 4, 5, 6, 7>(nt, [&](auto ntc) {
                 if (path.kind == FindPath::Unordered)   // (any block order, at find_kernel's launch bound; the launch takes the parameters' exact types)
                     hipExtLaunchKernelGGL((find_kernel<D4, rr, ntc>), dim3(grid), dim3(256), 0, st, nullptr, nullptr, hipExtAnyOrderLaunch, (const int64_t*)t->keys,
                                           (const f32x4*)plane, t->nb, d_keys, (uint64_t)n, (f32x4*)d_out, d_found, miss_value, t->dim4, (uint32_t*)nullptr, (int64_t*)nullptr, (int64_t)0);
-                else find(rr, ntc, grid, fblock);
+                else if (!captured || !find_captured((const void*)&find_many_kernel<D4, rr, ntc>, t, plane, miss_value, d_keys, n, d_out, d_found, fblock, grid, st))
+                    find(rr, ntc, grid, fblock);
             }); };
             if constexpr (D4 == 16) with_value<8, 4, 2, 1>(R, plain);
             else if constexpr (D4 == 32) with_value<4, 2, 1>(R, plain);
@@ -882,19 +994,16 @@ int mee_find_many(const mee_table* t, const mee_find_request* reqs, uint32_t cou
     FindMany m{};
     const int R = with_row_shape(t->dim4, [](auto d4) { return RowShape<d4>::rows_per_tile; });
     uint64_t blocks = 0, out_bytes = 0;
-    uint32_t used = 0;
     for (uint32_t q = 0; q < count; ++q) {
         if (reqs[q].n == 0) continue;
         if (!reqs[q].d_keys || !reqs[q].d_out) return fail(MEE_ERR_INVALID_ARG, "mee_find_many: request %u has a null buffer", q);
-        m.keys[used] = reqs[q].d_keys; m.out[used] = (f32x4*)reqs[q].d_out; m.found[used] = reqs[q].d_found; m.n[used] = reqs[q].n;
-        m.first_block[used] = (uint32_t)blocks;
-        blocks += (reqs[q].n + 16ull * R - 1) / (16ull * R);
+        const uint64_t req_blocks = (reqs[q].n + 16ull * R - 1) / (16ull * R);
+        blocks += req_blocks;
+        if (req_blocks >= (1ull << 31) || !find_many_append(m, reqs[q].d_keys, reqs[q].n, (f32x4*)reqs[q].d_out, reqs[q].d_found, (uint32_t)req_blocks))
+            return fail(MEE_ERR_BATCH_TOO_LARGE, "mee_find_many: %llu blocks", (unsigned long long)blocks);
         out_bytes += (uint64_t)reqs[q].n * t->dim * 4;
-        ++used;
     }
-    if (used == 0) return MEE_OK;
-    if (blocks > (1ull << 31)) return fail(MEE_ERR_BATCH_TOO_LARGE, "mee_find_many: %llu blocks", (unsigned long long)blocks);
-    m.first_block[used] = (uint32_t)blocks; m.count = used;
+    if (m.count == 0) return MEE_OK;
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
     const bool cached_out = out_bytes <= kCachedOutputBytes;   // same policy as mee_find, on the total output of the launch
@@ -902,6 +1011,13 @@ int mee_find_many(const mee_table* t, const mee_find_request* reqs, uint32_t cou
         find_many_kernel<d4, RowShape<d4>::rows_per_tile, ntc><<<(unsigned)blocks, 256, 0, st>>>(t->keys, (const f32x4*)t->values, t->nb, m, t->default_value, t->dim4);
     }); });
     MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+int mee_find_capture_stats(const mee_table* t, uint64_t* nodes, uint64_t* merged) {
+    if (!t || !nodes || !merged) return fail(MEE_ERR_INVALID_ARG, "mee_find_capture_stats: null argument");
+    *nodes = __atomic_load_n(&t->find_nodes, __ATOMIC_RELAXED);
+    *merged = __atomic_load_n(&t->find_merged, __ATOMIC_RELAXED);
     return MEE_OK;
 }
 

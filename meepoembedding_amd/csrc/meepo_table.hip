@@ -639,6 +639,7 @@ int mee_table_create(const mee_config* cfg, mee_table** out) {
     t->find_rounds = 0;  // auto: 2 for dim 64, 1 for wider rows
     t->find_grid_cap = 0;
     t->find_nt = -1;  // auto
+    t->find_coalesce = 1;
 
     const uint64_t plane = t->capacity * (uint64_t)t->row_bytes;
     const uint64_t mb = t->max_batch;
@@ -731,6 +732,7 @@ int mee_set_tuning(mee_table* t, const char* name, int value) {
     else if (!strcmp(name, "find_block")) t->find_block = value;
     else if (!strcmp(name, "prepare_debug")) t->prepare_debug = value;
     else if (!strcmp(name, "find_nt")) t->find_nt = value;
+    else if (!strcmp(name, "find_coalesce")) t->find_coalesce = value != 0;
     else if (!strcmp(name, "apply_bucket_max")) t->bk.bucket_max = value > 0 && value <= 352 ? (uint32_t)value : 0u;
     else if (!strcmp(name, "apply_skew_adapt")) t->bk.skew_adapt = t->bk_dd.skew_adapt = value != 0;
     else if (!strcmp(name, "apply_xcd_split")) t->bk.xcd_split = value < 0 ? xcd_split_for_device(t->device) : value < 1024 ? (uint32_t)value : 0u;

@@ -167,7 +167,10 @@ struct mee_table {
     // nothing but the store instruction's cache hint)
     uint64_t out_ring_ptr[8], out_ring_bytes[8];
     uint32_t out_ring_head;
-    mee::BucketScratch bk;      // bucketed apply (null pointers when the table has no optimizer)
+    // consecutive plain finds of this table under stream capture share one kernel node (find_captured, meepo_find.hip)
+    int find_coalesce;          // tuning ("find_coalesce", default 1): 0 = every captured find gets a node of its own
+    uint64_t find_nodes, find_merged;   // captured plain finds that got a node of their own | that joined an earlier node (mee_find_capture_stats; relaxed atomics)
+    mee::BucketScratch bk;     // bucketed apply (null pointers when the table has no optimizer)
     // ... and the same scratch with a skew state of its own (the pinned word, the hot-key set, the partition parity and the totals' two copies) for the operators that see the
     // RAW key stream of a batch — dedup_keys, dedup_sum, assign.  A training step on one table runs them beside an apply over the batch's DISTINCT keys (the sharded paths with
     // pre-exchange aggregation): the apply's "no skew" report sent the next dedup of the (skewed) raw stream back to its first-skewed-batch path, every step.

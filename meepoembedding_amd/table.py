@@ -412,6 +412,13 @@ class LookupTable:
         check(_lib.lib().mee_find_many(self._h, reqs, len(requests), self._s()))
         return [(o, f) for o, f, _ in res]
 
+    def find_capture_stats(self):
+        """(nodes, merged) — mee_find_capture_stats: this table's plain finds issued under stream capture that got a kernel node of their own, and
+        those that joined the node of the find in front of them."""
+        nodes, merged = C.c_uint64(0), C.c_uint64(0)
+        check(_lib.lib().mee_find_capture_stats(self._h, C.byref(nodes), C.byref(merged)))
+        return nodes.value, merged.value
+
     def _bag_offsets(self, bag_offsets: torch.Tensor) -> int:
         return _n_bags(bag_offsets, self.device)
 
