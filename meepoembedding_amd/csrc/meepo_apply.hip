@@ -53,10 +53,6 @@ constexpr uint32_t kLdsPartRows = 16;     // fp64 partial rows a slab keeps in L
 // The plan of a batch's partition (part_plan_for, meepo_apply_part.h) from the state of the stream: S, the units the latest batch had beyond its hash
 // buckets, comes back through a pinned host word the apply kernel writes — read here without any synchronisation (a stale or zero value costs time,
 // never results: the kernel works through whatever units there are).  ONE call per partition: it ages skew_sticky.
-static bool stream_is_capturing(hipStream_t st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
-}
 PartPlan bucket_plan(BucketScratch& sk, uint64_t n, hipStream_t st, uint32_t threads, uint32_t slots_of, uint32_t bucket_max_of) {
     const bool capturing = sk.skew_adapt && stream_is_capturing(st);
     const uint32_t s_prev = sk.h_slabs && sk.skew_adapt ? *(volatile uint32_t*)sk.h_slabs : 0u;

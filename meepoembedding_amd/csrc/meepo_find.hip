@@ -707,6 +707,13 @@ __global__ __launch_bounds__(256) void pooled_weighted_backward_kernel(const int
     }
 }
 
+// One instance is created here, ahead of the launch function that creates the others: one bf16-row table, bf16 out, dim 64, four bags per wave.  The compiler's
+// output for it depends on when it meets it (nothing else does: tools/kernel_code_hashes.py against the commit before the launches were unified); with it met
+// first, every kernel of this file is that commit's, byte for byte, in both orders of pooled_find's arms that were tried (profiles/host_layer.md).
+// The line serves that comparison alone — the instance is one the launch function reaches anyway, and its bytes still depend on the compiler's version: once
+// byte-identity with that commit no longer matters it may be removed.
+template __global__ void find_pooled_kernel<16, 2, 4, false, false, true, false, false, true, false>(const int64_t*, const float4*, uint64_t, const int64_t*, const uint64_t*, uint64_t, float4*, uint8_t*, float,
+                                                                                                       uint32_t, int, const GroupDesc*, uint64_t, int64_t*, uint64_t, const float*, int64_t, const uint64_t*, uint32_t, TierArgs);
 }  // namespace mee
 
 using namespace mee;
@@ -758,11 +765,6 @@ static bool outputs_rotate(const mee_table* t, const void* d_out, uint64_t bytes
 static std::mutex g_find_nodes_mu;
 static FindNodes g_find_nodes;   // (under g_find_nodes_mu)
 static const bool g_find_coalesce_env = [] { const char* e = getenv("MEE_FIND_COALESCE"); return !(e && e[0] == '0'); }();
-
-static bool stream_is_capturing(hipStream_t st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
-}
 
 // the capturing stream's capture id and its dependency set when that is ONE node (else *dep = null); false: not capturing, or the query failed
 static bool capture_state(hipStream_t st, unsigned long long* id, hipGraph_t* graph, hipGraphNode_t* dep) {
@@ -838,7 +840,7 @@ static bool find_captured(const void* func, const mee_table* t, const float* pla
 // n_bags / 16 blocks, a long average (12 keys or more per bag) -> one bag per wave on n_bags / 4.  f(d4, unroll, bags_per_wave, grid).
 template <class F> void with_pooled_shape(uint32_t dim4, size_t n, uint64_t n_bags, F&& f) {
     with_row_shape(dim4, [&](auto d4) {
-        if (n / n_bags >= 12) f(d4, std::integral_constant<int, RowShape<d4>::pooled_unroll_1>{}, std::integral_constant<int, 1>{}, grid_for(n_bags, 4, 1u << 20));
+        if (pooled_wave_per_bag(n, n_bags)) f(d4, std::integral_constant<int, RowShape<d4>::pooled_unroll_1>{}, std::integral_constant<int, 1>{}, grid_for(n_bags, 4, 1u << 20));
         else f(d4, std::integral_constant<int, RowShape<d4>::pooled_unroll_4>{}, std::integral_constant<int, 4>{}, grid_for(n_bags, 16, 1u << 20));
     });
 }
@@ -1043,41 +1045,138 @@ int mee_find_counted(const mee_table* t, const int64_t* d_keys, size_t n, float*
     return find_plane(t, t->values, t->default_value, d_keys, n, d_out, d_found, stream, {missing_only ? FindPath::CountedMissing : FindPath::Counted});
 }
 
-// every pooled lookup of one table: mode SUM | MEAN, or d_weights (SUM only; located rows in the format of mee_find_located); fp32 or bf16 bag rows
-static int find_pooled_common(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const float* d_weights, void* d_out,
-                              uint32_t out_dtype, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
-    if (n_bags == 0) return MEE_OK;
-    DeviceGuard g(t->device);
-    hipStream_t st = as_stream(stream);
-    const int64_t tag = handle_tag_of(t);   // located rows in the format of mee_find_located
-    with_pooled_shape(t->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(d_weights != nullptr, [&](auto weighted) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
-        auto launch = [&](auto kernel) {
-            kernel<<<grid, 256, 0, st>>>(t->keys, (const float4*)t->values, t->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, t->default_value, t->dim4,
-                                         mode == MEE_POOL_MEAN, nullptr, 1, weighted ? d_located_out : nullptr, n, d_weights, weighted ? tag : 0, nullptr, 0, TierArgs{});
+}  // extern "C"
+
+// What every keyed entry point checks about its output before anything is launched or written; -> the row stride in element groups.
+// width = the elements a row holds (T * dim, a mixed group's sum of dims); out_row_stride in elements, 0 = width.
+int mee::keyed_out_check(const char* name, uint64_t width, uint64_t n_tables, uint64_t bags_per_table, const void* d_out, uint32_t out_dtype,
+                         uint64_t out_row_stride, bool want_index, uint64_t* stride4) {
+    if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
+    if (out_dtype == MEE_DTYPE_F32 && ((uintptr_t)d_out & 15)) return fail(MEE_ERR_INVALID_ARG, "%s: an fp32 keyed output must be 16-byte aligned", name);
+    const uint64_t stride = out_row_stride ? out_row_stride : width;
+    if (stride < width || (stride & 3))
+        return fail(MEE_ERR_INVALID_ARG, "%s: out_row_stride = %llu elements must be a multiple of 4 and at least the row's width %llu", name,
+                    (unsigned long long)stride, (unsigned long long)width);
+    if (want_index && (bags_per_table > 0xFFFFFFFFull || n_tables * bags_per_table >= (1ull << 32)))
+        return fail(MEE_ERR_INVALID_ARG, "%s: the step index is 32 bits: n_tables * bags_per_table must stay below 2^32", name);
+    *stride4 = stride / 4;
+    return MEE_OK;
+}
+
+// ---- the pooled lookups: one table, a hot/cold pair, a group, a group of pairs — every form is a PooledCall (meepo_table_int.h) ----------------------
+// What every form refuses, once, in the order the entry points always had: null arguments, the pair's or the two groups' mismatches, out_dtype, mode,
+// weights with MEAN, a single table's located rows without weights, the keyed output's shape (-> stride4).
+static int pooled_check(const PooledCall& c, uint64_t* stride4) {
+    const char* name = c.name;
+    const bool grouped = c.source == PooledCall::Group || c.source == PooledCall::GroupOfPairs;
+    const bool null_source = grouped ? !c.group || (c.source == PooledCall::GroupOfPairs && !c.cold_group) : !c.table || (c.source == PooledCall::Pair && !c.cold);
+    if (null_source || (c.bags && (!c.offsets || !c.out || (c.jagged && !c.member_bags))) || (c.n && !c.keys)) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (c.source == PooledCall::Pair) {
+        const mee_table *hot = c.table, *cold = c.cold;
+        if (hot == cold) return fail(MEE_ERR_INVALID_ARG, "%s: hot and cold are the same table (a key lives in exactly one tier)", name);
+        if (hot->device != cold->device || hot->dim != cold->dim)
+            return fail(MEE_ERR_INVALID_ARG, "%s: the tiers differ in device (%d, %d) or dim (%u, %u)", name, hot->device, cold->device, hot->dim, cold->dim);
+        if (c.tier_flags & ~(uint32_t)(MEE_TIER_COUNT_COLD | MEE_TIER_COUNT_HOT)) return fail(MEE_ERR_INVALID_ARG, "%s: unknown flag bits 0x%x", name, c.tier_flags);
+        if (((c.tier_flags & MEE_TIER_COUNT_COLD) && !cold->hits) || ((c.tier_flags & MEE_TIER_COUNT_HOT) && !hot->hits))
+            return fail(MEE_ERR_INVALID_ARG, "%s: a count flag needs that tier created with MEE_FLAG_TRACK_HITS", name);
+    }
+    if (c.source == PooledCall::GroupOfPairs) { if (int rc = tiered_groups_check(c.group, c.cold_group, c.tier_flags, name)) return rc; }
+    if (!c.keyed) { if (int rc = check_out_dtype(c.out, c.out_dtype, name)) return rc; }   // (keyed: keyed_out_check's, behind the mode)
+    if (c.mode != MEE_POOL_SUM && c.mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "%s: mode must be MEE_POOL_SUM or MEE_POOL_MEAN", name);
+    if (c.weights && c.mode != MEE_POOL_SUM) return fail(MEE_ERR_INVALID_ARG, "%s: weighted pooling is MEE_POOL_SUM only", name);
+    if (!grouped && c.located && !c.weights) return fail(MEE_ERR_INVALID_ARG, "%s: d_located_out is the weighted form's output (pass weights of 1.0f for a plain sum)", name);
+    if (c.keyed) {
+        if (int rc = keyed_out_check(name, (uint64_t)c.group->n_tables * c.group->dim4 * 4, c.group->n_tables, c.bags, c.out, c.out_dtype, c.out_row_stride, c.step_index != nullptr, stride4)) return rc;
+    }
+    const bool tiered = c.source == PooledCall::Pair || c.source == PooledCall::GroupOfPairs;
+    if ((!grouped && (c.jagged || c.keyed)) || (c.jagged && (c.keyed || c.out_dtype != MEE_DTYPE_F32)) ||
+        (c.weights && (c.jagged || c.keyed || tiered || (grouped ? c.group->bf16_rows : c.table->bf16_rows))))
+        return fail(MEE_ERR_UNSUPPORTED, "%s: no pooled kernel serves this combination of source, weights, jagged map, keyed output and out_dtype", name);   // (no entry point asks for one)
+    if (c.jagged && c.group->n_tables == 0) return fail(MEE_ERR_INVALID_ARG, "%s: the group has no tables", name);   // the kernel keeps the member inside [0, n_tables)
+    return MEE_OK;
+}
+
+// The one launch of find_pooled_kernel.  Its instances are those the forms reach and no others: a table or a group (fp32 rows: weighted or not; bf16 rows:
+// unweighted), a group's jagged map (fp32 out; either row type; pairs too), a pair or a group of pairs (fp32 rows, unweighted), a group's or a group of
+// pairs' keyed output.  Kernel arguments a form has no use for keep the values the kernel ignores (null, 0, one bag per table).
+int mee::pooled_find(const PooledCall& c) {
+    uint64_t stride4 = 0;
+    if (int rc = pooled_check(c, &stride4)) return rc;
+    if (c.bags == 0) return MEE_OK;
+    mee_group* const g = c.group;
+    const mee_table* const t = c.table;
+    if (g) { if (int rc = group_refresh(g, c.stream)) return rc; }
+    if (c.cold_group) { if (int rc = group_refresh(c.cold_group, c.stream)) return rc; }
+    DeviceGuard guard(g ? g->device : t->device);
+    hipStream_t st = as_stream(c.stream);
+    const bool tiered = c.source == PooledCall::Pair || c.source == PooledCall::GroupOfPairs;
+    const uint32_t dim4 = g ? g->dim4 : t->dim4;
+    const uint64_t per_table = g && !c.jagged ? c.bags : 1;
+    const uint64_t n_bags = g && !c.jagged ? (uint64_t)g->n_tables * c.bags : c.bags;
+    int64_t* const located = !g && !c.weights ? nullptr : c.located;             // a table's located rows are the weighted instances' ...
+    const int64_t tag = !g && c.weights ? handle_tag_of(t) : 0;                   // ... in the format of mee_find_located
+    const bool brows_rt = g ? g->bf16_rows : t->bf16_rows;
+    const TierArgs pair_tier = c.cold ? TierArgs{c.cold->keys, (const float4*)c.cold->values, c.cold->nb, (c.tier_flags & MEE_TIER_COUNT_HOT) ? t->hits : nullptr,
+                                                 (c.tier_flags & MEE_TIER_COUNT_COLD) ? c.cold->hits : nullptr} : TierArgs{};
+    const GroupTier group_tier = c.cold_group ? GroupTier{c.cold_group->d_desc, g->d_init, c.cold_group->d_init, c.tier_flags} : GroupTier{};
+    const KeyedOut keyed{stride4, c.step_index, c.index_by_bag || !g ? 1ull : g->n_tables, c.index_by_bag ? (uint64_t)c.bags : 1ull};
+    with_pooled_shape(dim4, c.n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
+        // the kernel's arguments, once; `last` is the TierArgs | GroupTier | WithKeyed<> of either the instance takes
+        auto launch = [&](auto kernel, auto last) {
+            kernel<<<grid, 256, 0, st>>>(t ? t->keys : nullptr, t ? (const float4*)t->values : nullptr, t ? t->nb : 0, c.keys, c.offsets, n_bags, (float4*)c.out, c.found,
+                                         t ? t->default_value : 0.f, dim4, c.mode == MEE_POOL_MEAN, g ? g->d_desc : nullptr, per_table, located, c.n, c.weights, tag,
+                                         c.member_bags, c.jagged ? g->n_tables : 0, last);
         };
-        if constexpr (!weighted) { if (t->bf16_rows) { launch(find_pooled_kernel<d4, u, bpw, false, false, bf16, false, false, true>); return; } }   // (weighted: refused at the entry points)
-        launch(find_pooled_kernel<d4, u, bpw, false, weighted, bf16>);
-    }); }); });
+        // the tiered forms, a wave per bag at dim 64: two keys in flight per tile — 66 VGPRs / 7 waves where the one-table kernel's four take 93 / 5 here, at the same
+        // measured time (profiles/tiered_bags.md); four measured no better for a group of pairs either (profiles/tiered_groups.md)
+        constexpr int ut = (bpw == 1 && u > 2) ? 2 : u;
+        // one arm per form, each naming its instances; pooled_check has refused every combination of fields that has no arm
+        const bool bf16_out = c.out_dtype == MEE_DTYPE_BF16;
+        auto plain = [&](auto grouped) { with_flag(c.weights != nullptr, [&](auto weighted) { with_flag(bf16_out, [&](auto bf16) {
+            if constexpr (!weighted) { if (brows_rt) { launch(find_pooled_kernel<d4, u, bpw, grouped, false, bf16, false, false, true>, TierArgs{}); return; } }
+            launch(find_pooled_kernel<d4, u, bpw, grouped, weighted, bf16>, TierArgs{});
+        }); }); };
+        const bool is_plain = !c.jagged && !c.keyed;
+        if (!g && !tiered) plain(std::false_type{});
+        else if (!g) with_flag(bf16_out, [&](auto bf16) { launch(find_pooled_kernel<d4, ut, bpw, false, false, bf16, false, true>, pair_tier); });
+        else if (!tiered && is_plain) plain(std::true_type{});
+        else if (!tiered && c.jagged) with_flag(brows_rt, [&](auto brows) { launch(find_pooled_kernel<d4, u, bpw, true, false, false, true, false, brows>, TierArgs{}); });
+        else if (tiered && is_plain) with_flag(bf16_out, [&](auto bf16) { launch(find_pooled_kernel<d4, ut, bpw, true, false, bf16, false, true>, group_tier); });
+        else if (tiered && c.jagged) launch(find_pooled_kernel<d4, ut, bpw, true, false, false, true, true>, group_tier);
+        else if (!tiered) with_flag(bf16_out, [&](auto bf16) { with_flag(brows_rt, [&](auto brows) {
+            launch(find_pooled_kernel<d4, u, bpw, true, false, bf16, false, false, brows, true>, WithKeyed<TierArgs>{{}, keyed}); }); });
+        else with_flag(bf16_out, [&](auto bf16) { launch(find_pooled_kernel<d4, ut, bpw, true, false, bf16, false, true, false, true>, WithKeyed<GroupTier>{group_tier, keyed}); });
+    });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }
+
+// the fields every entry point of the family has
+static PooledCall pooled_call(const char* name, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags, void* d_out, uint32_t out_dtype, uint8_t* d_found,
+                              int mode, void* stream) {
+    PooledCall c{name};
+    c.keys = d_keys; c.n = n; c.offsets = d_bag_offsets; c.bags = bags; c.out = d_out; c.out_dtype = out_dtype; c.found = d_found; c.mode = mode; c.stream = stream;
+    return c;
+}
+
+extern "C" {
 
 int mee_find_pooled(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, float* d_out,
                     uint8_t* d_found, int mode, void* stream) {
     MEE_RANGE("mee_find_pooled");
     MEE_NO_INT8_ROWS(t, "mee_find_pooled");   // (an int8-row table has no pooled lookup yet)
-    if (!t || (n_bags && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled: null argument");
-    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
-    return find_pooled_common(t, d_keys, n, d_bag_offsets, n_bags, nullptr, d_out, MEE_DTYPE_F32, d_found, nullptr, mode, stream);
+    return pooled_find(pooled_call("mee_find_pooled", d_keys, n, d_bag_offsets, n_bags, d_out, MEE_DTYPE_F32, d_found, mode, stream).of(t));
 }
 
 int mee_find_pooled_weighted(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
                              const float* d_weights, float* d_out, uint8_t* d_found, int64_t* d_located_out, void* stream) {
     MEE_RANGE("mee_find_pooled_weighted");
     MEE_FP32_ROWS_ONLY(t, "mee_find_pooled_weighted");
-    if (!t || (n_bags && (!d_bag_offsets || !d_out)) || (n && (!d_keys || !d_weights)))
-        return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_weighted: null argument");
-    return find_pooled_common(t, d_keys, n, d_bag_offsets, n_bags, d_weights /* null only with n = 0: every bag is empty, the plain sum's zeros */, d_out, MEE_DTYPE_F32, d_found, d_located_out, MEE_POOL_SUM, stream);
+    if (n && !d_weights) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_weighted: null argument");
+    PooledCall c = pooled_call("mee_find_pooled_weighted", d_keys, n, d_bag_offsets, n_bags, d_out, MEE_DTYPE_F32, d_found, MEE_POOL_SUM, stream).of(t);
+    c.weights = d_weights;   // null only with n = 0: every bag is empty, the plain sum's zeros (and nothing is located)
+    c.located = d_weights ? d_located_out : nullptr;
+    return pooled_find(c);
 }
 
 int mee_find_pooled_as(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const float* d_weights,
@@ -1085,12 +1184,10 @@ int mee_find_pooled_as(const mee_table* t, const int64_t* d_keys, size_t n, cons
     MEE_RANGE("mee_find_pooled_as");
     if (d_weights) MEE_FP32_ROWS_ONLY(t, "mee_find_pooled_as");
     MEE_NO_INT8_ROWS(t, "mee_find_pooled_as");
-    if (!t || (n_bags && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: null argument");
-    if (int rc = check_out_dtype(d_out, out_dtype, "mee_find_pooled_as")) return rc;
-    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
-    if (d_weights && mode != MEE_POOL_SUM) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: weighted pooling is MEE_POOL_SUM only");
-    if (d_located_out && !d_weights) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_as: d_located_out is the weighted form's output (pass weights of 1.0f for a plain sum)");
-    return find_pooled_common(t, d_keys, n, d_bag_offsets, n_bags, d_weights, d_out, out_dtype, d_found, d_located_out, mode, stream);
+    PooledCall c = pooled_call("mee_find_pooled_as", d_keys, n, d_bag_offsets, n_bags, d_out, out_dtype, d_found, mode, stream).of(t);
+    c.weights = d_weights;
+    c.located = d_located_out;
+    return pooled_find(c);
 }
 
 // the pooled lookup of a hot/cold pair: find_pooled_kernel's TIERED instances, the hot table in the table arguments, the cold one in TierArgs
@@ -1099,28 +1196,9 @@ int mee_find_pooled_tiered(const mee_table* hot, const mee_table* cold, const in
     MEE_RANGE("mee_find_pooled_tiered");
     MEE_FP32_ROWS_ONLY(hot, "mee_find_pooled_tiered");
     MEE_FP32_ROWS_ONLY(cold, "mee_find_pooled_tiered");
-    if (!hot || !cold || (n_bags && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: null argument");
-    if (hot == cold) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: hot and cold are the same table (a key lives in exactly one tier)");
-    if (hot->device != cold->device || hot->dim != cold->dim)
-        return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: the tiers differ in device (%d, %d) or dim (%u, %u)", hot->device, cold->device, hot->dim, cold->dim);
-    if (flags & ~(uint32_t)(MEE_TIER_COUNT_COLD | MEE_TIER_COUNT_HOT)) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: unknown flag bits 0x%x", flags);
-    if (((flags & MEE_TIER_COUNT_COLD) && !cold->hits) || ((flags & MEE_TIER_COUNT_HOT) && !hot->hits))
-        return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: a count flag needs that tier created with MEE_FLAG_TRACK_HITS");
-    if (int rc = check_out_dtype(d_out, out_dtype, "mee_find_pooled_tiered")) return rc;
-    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_find_pooled_tiered: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
-    if (n_bags == 0) return MEE_OK;
-    DeviceGuard g(hot->device);
-    hipStream_t st = as_stream(stream);
-    const TierArgs tier{cold->keys, (const float4*)cold->values, cold->nb, (flags & MEE_TIER_COUNT_HOT) ? hot->hits : nullptr,
-                        (flags & MEE_TIER_COUNT_COLD) ? cold->hits : nullptr};
-    with_pooled_shape(hot->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
-        constexpr int ut = (bpw == 1 && u > 2) ? 2 : u;   // a wave per bag at dim 64: two keys in flight per tile — 66 VGPRs / 7 waves where the one-table kernel's four take 93 / 5 here, at the same measured time (profiles/tiered_bags.md)
-        find_pooled_kernel<d4, ut, bpw, false, false, bf16, false, true><<<grid, 256, 0, st>>>(
-            hot->keys, (const float4*)hot->values, hot->nb, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, hot->default_value, hot->dim4,
-            mode == MEE_POOL_MEAN, nullptr, 1, nullptr, n, nullptr, 0, nullptr, 0, tier);
-    }); });
-    MEE_HIP(hipGetLastError());
-    return MEE_OK;
+    PooledCall c = pooled_call("mee_find_pooled_tiered", d_keys, n, d_bag_offsets, n_bags, d_out, out_dtype, d_found, mode, stream).of(hot, cold);
+    c.tier_flags = flags;
+    return pooled_find(c);
 }
 
 int mee_pooled_weighted_backward(const mee_table* t, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,
@@ -1151,32 +1229,13 @@ int mee_find_plane(const mee_table* t, uint32_t plane, const int64_t* d_keys, si
 }
 
 // ---- the embedding-bag collection: pooled lookups of a whole group in one launch, and their backward -----------------------
-static int group_find_pooled_common(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights,
-                                    void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
-    if (bags_per_table == 0) return MEE_OK;
-    if (int rc = group_refresh(g, stream)) return rc;
-    DeviceGuard guard(g->device);
-    hipStream_t st = as_stream(stream);
-    const uint64_t n_bags = (uint64_t)g->n_tables * bags_per_table;
-    with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(d_weights != nullptr, [&](auto weighted) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
-        auto launch = [&](auto kernel) {
-            kernel<<<grid, 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, mode == MEE_POOL_MEAN, g->d_desc, bags_per_table,
-                                         d_located_out, n, d_weights, 0, nullptr, 0, TierArgs{});
-        };
-        if constexpr (!weighted) { if (g->bf16_rows) { launch(find_pooled_kernel<d4, u, bpw, true, false, bf16, false, false, true>); return; } }   // (weighted: refused at the entry points)
-        launch(find_pooled_kernel<d4, u, bpw, true, weighted, bf16>);
-    }); }); });
-    MEE_HIP(hipGetLastError());
-    return MEE_OK;
-}
-
 int mee_group_find_pooled(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
                           float* d_out, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
     MEE_RANGE("mee_group_find_pooled");
     if (d_located_out) MEE_FP32_GROUP_ONLY(g, "mee_group_find_pooled", "d_located_out (the located rows serve the backward) is");
-    if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled: null argument");
-    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
-    return group_find_pooled_common(g, d_keys, n, d_bag_offsets, bags_per_table, nullptr, d_out, MEE_DTYPE_F32, d_found, d_located_out, mode, stream);
+    PooledCall c = pooled_call("mee_group_find_pooled", d_keys, n, d_bag_offsets, bags_per_table, d_out, MEE_DTYPE_F32, d_found, mode, stream).of(g);
+    c.located = d_located_out;
+    return pooled_find(c);
 }
 
 // the same lookup with the members' bag counts read from d_member_bags (the owner's side of a sharded group: the runs that arrive per member)
@@ -1184,28 +1243,21 @@ int mee_group_find_pooled_jagged(mee_group* g, const int64_t* d_keys, size_t n, 
                                  const uint64_t* d_member_bags, float* d_out, uint8_t* d_found, int64_t* d_located_out, int mode, void* stream) {
     MEE_RANGE("mee_group_find_pooled_jagged");
     if (d_located_out) MEE_FP32_GROUP_ONLY(g, "mee_group_find_pooled_jagged", "d_located_out (the located rows serve the backward) is");
-    if (!g || (n_bags && (!d_bag_offsets || !d_member_bags || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_jagged: null argument");
-    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_jagged: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
-    if (n_bags == 0) return MEE_OK;
-    if (g->n_tables == 0) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_jagged: the group has no tables");   // the kernel keeps the member inside [0, n_tables)
-    if (int rc = group_refresh(g, stream)) return rc;
-    DeviceGuard guard(g->device);
-    hipStream_t st = as_stream(stream);
-    with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(g->bf16_rows, [&](auto brows) {
-        find_pooled_kernel<d4, u, bpw, true, false, false, true, false, brows><<<grid, 256, 0, st>>>(nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4,
-                                                                                                     mode == MEE_POOL_MEAN, g->d_desc, 1, d_located_out, n, nullptr, 0, d_member_bags, g->n_tables);
-    }); });
-    MEE_HIP(hipGetLastError());
-    return MEE_OK;
+    PooledCall c = pooled_call("mee_group_find_pooled_jagged", d_keys, n, d_bag_offsets, n_bags, d_out, MEE_DTYPE_F32, d_found, mode, stream).of(g);
+    c.located = d_located_out;
+    c.jagged = true; c.member_bags = d_member_bags;
+    return pooled_find(c);
 }
 
 int mee_group_find_pooled_weighted(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
                                    const float* d_weights, float* d_out, uint8_t* d_found, int64_t* d_located_out, void* stream) {
     MEE_RANGE("mee_group_find_pooled_weighted");
     MEE_FP32_GROUP_ONLY(g, "mee_group_find_pooled_weighted");
-    if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && (!d_keys || !d_weights)))
-        return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_weighted: null argument");
-    return group_find_pooled_common(g, d_keys, n, d_bag_offsets, bags_per_table, d_weights /* null only with n = 0 */, d_out, MEE_DTYPE_F32, d_found, d_located_out, MEE_POOL_SUM, stream);
+    if (n && !d_weights) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_weighted: null argument");
+    PooledCall c = pooled_call("mee_group_find_pooled_weighted", d_keys, n, d_bag_offsets, bags_per_table, d_out, MEE_DTYPE_F32, d_found, MEE_POOL_SUM, stream).of(g);
+    c.weights = d_weights;   // null only with n = 0
+    c.located = d_located_out;
+    return pooled_find(c);
 }
 
 int mee_group_find_pooled_as(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights,
@@ -1213,11 +1265,10 @@ int mee_group_find_pooled_as(mee_group* g, const int64_t* d_keys, size_t n, cons
     MEE_RANGE("mee_group_find_pooled_as");
     if (d_weights) MEE_FP32_GROUP_ONLY(g, "mee_group_find_pooled_as", "the weighted form (d_weights) is");
     if (d_located_out) MEE_FP32_GROUP_ONLY(g, "mee_group_find_pooled_as", "d_located_out (the located rows serve the backward) is");
-    if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_as: null argument");
-    if (int rc = check_out_dtype(d_out, out_dtype, "mee_group_find_pooled_as")) return rc;
-    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_as: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
-    if (d_weights && mode != MEE_POOL_SUM) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_as: weighted pooling is MEE_POOL_SUM only");
-    return group_find_pooled_common(g, d_keys, n, d_bag_offsets, bags_per_table, d_weights, d_out, out_dtype, d_found, d_located_out, mode, stream);
+    PooledCall c = pooled_call("mee_group_find_pooled_as", d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, d_found, mode, stream).of(g);
+    c.weights = d_weights;
+    c.located = d_located_out;
+    return pooled_find(c);
 }
 
 // the pooled lookup of a GROUP of hot/cold pairs: find_pooled_kernel's GROUPED && TIERED instances, the hot group's descriptors in `desc`, the cold group's
@@ -1225,25 +1276,9 @@ int mee_group_find_pooled_as(mee_group* g, const int64_t* d_keys, size_t n, cons
 int mee_group_find_pooled_tiered(mee_group* hot, mee_group* cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table,
                                  void* d_out, uint32_t out_dtype, uint8_t* d_found, int mode, uint32_t flags, void* stream) {
     MEE_RANGE("mee_group_find_pooled_tiered");
-    if (!hot || !cold || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_tiered: null argument");
-    if (int rc = tiered_groups_check(hot, cold, flags, "mee_group_find_pooled_tiered")) return rc;
-    if (int rc = check_out_dtype(d_out, out_dtype, "mee_group_find_pooled_tiered")) return rc;
-    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_tiered: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
-    if (bags_per_table == 0) return MEE_OK;
-    if (int rc = group_refresh(hot, stream)) return rc;
-    if (int rc = group_refresh(cold, stream)) return rc;
-    DeviceGuard guard(hot->device);
-    hipStream_t st = as_stream(stream);
-    const uint64_t n_bags = (uint64_t)hot->n_tables * bags_per_table;
-    const GroupTier tier{cold->d_desc, hot->d_init, cold->d_init, flags};
-    with_pooled_shape(hot->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
-        constexpr int ut = (bpw == 1 && u > 2) ? 2 : u;   // the keys in flight of the pair's launch (mee_find_pooled_tiered); four at dim 64 measured no better (profiles/tiered_groups.md)
-        find_pooled_kernel<d4, ut, bpw, true, false, bf16, false, true><<<grid, 256, 0, st>>>(
-            nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, hot->dim4, mode == MEE_POOL_MEAN, hot->d_desc, bags_per_table,
-            nullptr, n, nullptr, 0, nullptr, 0, tier);
-    }); });
-    MEE_HIP(hipGetLastError());
-    return MEE_OK;
+    PooledCall c = pooled_call("mee_group_find_pooled_tiered", d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, d_found, mode, stream).of(hot, cold);
+    c.tier_flags = flags;
+    return pooled_find(c);
 }
 
 // the same lookup with the members' bag counts read from d_member_bags, as mee_group_find_pooled_jagged reads them: find_pooled_kernel's GROUPED && JAGGED && TIERED
@@ -1251,78 +1286,23 @@ int mee_group_find_pooled_tiered(mee_group* hot, mee_group* cold, const int64_t*
 int mee_group_find_pooled_tiered_jagged(mee_group* hot, mee_group* cold, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags,
                                         const uint64_t* d_member_bags, float* d_out, uint8_t* d_found, int mode, uint32_t flags, void* stream) {
     MEE_RANGE("mee_group_find_pooled_tiered_jagged");
-    if (!hot || !cold || (n_bags && (!d_bag_offsets || !d_member_bags || !d_out)) || (n && !d_keys))
-        return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_tiered_jagged: null argument");
-    if (int rc = tiered_groups_check(hot, cold, flags, "mee_group_find_pooled_tiered_jagged")) return rc;
-    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_tiered_jagged: mode must be MEE_POOL_SUM or MEE_POOL_MEAN");
-    if (hot->n_tables == 0) return fail(MEE_ERR_INVALID_ARG, "mee_group_find_pooled_tiered_jagged: the group has no tables");   // the kernel keeps the member inside [0, n_tables)
-    if (n_bags == 0) return MEE_OK;
-    if (int rc = group_refresh(hot, stream)) return rc;
-    if (int rc = group_refresh(cold, stream)) return rc;
-    DeviceGuard guard(hot->device);
-    hipStream_t st = as_stream(stream);
-    const GroupTier tier{cold->d_desc, hot->d_init, cold->d_init, flags};
-    with_pooled_shape(hot->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) {
-        constexpr int ut = (bpw == 1 && u > 2) ? 2 : u;   // the keys in flight of mee_group_find_pooled_tiered
-        find_pooled_kernel<d4, ut, bpw, true, false, false, true, true><<<grid, 256, 0, st>>>(
-            nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, hot->dim4, mode == MEE_POOL_MEAN, hot->d_desc, 1,
-            nullptr, n, nullptr, 0, d_member_bags, hot->n_tables, tier);
-    });
-    MEE_HIP(hipGetLastError());
-    return MEE_OK;
+    PooledCall c = pooled_call("mee_group_find_pooled_tiered_jagged", d_keys, n, d_bag_offsets, n_bags, d_out, MEE_DTYPE_F32, d_found, mode, stream).of(hot, cold);
+    c.tier_flags = flags;
+    c.jagged = true; c.member_bags = d_member_bags;
+    return pooled_find(c);
 }
-
-}  // extern "C"
 
 // ---- the keyed layout (SPEC.md §3 "Keyed output"): out[s, j * dim ...] = the pooled row of member j's sample s, one row per sample --------------
-// What every keyed entry point checks about its output before anything is launched or written; -> the row stride in element groups.
-// width = the elements a row holds (T * dim, a mixed group's sum of dims); out_row_stride in elements, 0 = width.
-int mee::keyed_out_check(const char* name, uint64_t width, uint64_t n_tables, uint64_t bags_per_table, const void* d_out, uint32_t out_dtype,
-                         uint64_t out_row_stride, bool want_index, uint64_t* stride4) {
-    if (int rc = check_out_dtype(d_out, out_dtype, name)) return rc;
-    if (out_dtype == MEE_DTYPE_F32 && ((uintptr_t)d_out & 15)) return fail(MEE_ERR_INVALID_ARG, "%s: an fp32 keyed output must be 16-byte aligned", name);
-    const uint64_t stride = out_row_stride ? out_row_stride : width;
-    if (stride < width || (stride & 3))
-        return fail(MEE_ERR_INVALID_ARG, "%s: out_row_stride = %llu elements must be a multiple of 4 and at least the row's width %llu", name,
-                    (unsigned long long)stride, (unsigned long long)width);
-    if (want_index && (bags_per_table > 0xFFFFFFFFull || n_tables * bags_per_table >= (1ull << 32)))
-        return fail(MEE_ERR_INVALID_ARG, "%s: the step index is 32 bits: n_tables * bags_per_table must stay below 2^32", name);
-    *stride4 = stride / 4;
-    return MEE_OK;
-}
-
-int mee::group_find_pooled_keyed(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out,
-                                 uint32_t out_dtype, uint64_t out_row_stride, uint8_t* d_found, int64_t* d_located_out, uint32_t* d_step_index_out,
-                                 bool index_by_bag, int mode, void* stream, const char* name) {
-    if (g && d_located_out) MEE_FP32_GROUP_ONLY(g, name, "d_located_out (the located rows serve the backward) is");
-    if (g && d_step_index_out) MEE_FP32_GROUP_ONLY(g, name, "d_step_index_out (the step index serves the backward) is");
-    if (!g || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
-    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "%s: mode must be MEE_POOL_SUM or MEE_POOL_MEAN", name);
-    uint64_t stride4 = 0;
-    if (int rc = keyed_out_check(name, (uint64_t)g->n_tables * g->dim4 * 4, g->n_tables, bags_per_table, d_out, out_dtype, out_row_stride, d_step_index_out != nullptr, &stride4)) return rc;
-    if (bags_per_table == 0) return MEE_OK;
-    if (int rc = group_refresh(g, stream)) return rc;
-    DeviceGuard guard(g->device);
-    hipStream_t st = as_stream(stream);
-    const uint64_t n_bags = (uint64_t)g->n_tables * bags_per_table;
-    const KeyedOut keyed{stride4, d_step_index_out, index_by_bag ? 1ull : g->n_tables, index_by_bag ? (uint64_t)bags_per_table : 1ull};
-    with_pooled_shape(g->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) { with_flag(g->bf16_rows, [&](auto brows) {
-        find_pooled_kernel<d4, u, bpw, true, false, bf16, false, false, brows, true><<<grid, 256, 0, st>>>(
-            nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, g->dim4, mode == MEE_POOL_MEAN, g->d_desc, bags_per_table,
-            d_located_out, n, nullptr, 0, nullptr, 0, WithKeyed<TierArgs>{{}, keyed});
-    }); }); });
-    MEE_HIP(hipGetLastError());
-    return MEE_OK;
-}
-
-extern "C" {
-
 int mee_group_find_pooled_keyed(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out,
                                 uint32_t out_dtype, size_t out_row_stride, uint8_t* d_found, int64_t* d_located_out, uint32_t* d_step_index_out, int mode,
                                 void* stream) {
     MEE_RANGE("mee_group_find_pooled_keyed");
-    return group_find_pooled_keyed(g, d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, out_row_stride, d_found, d_located_out, d_step_index_out,
-                                   false, mode, stream, "mee_group_find_pooled_keyed");
+    if (d_located_out) MEE_FP32_GROUP_ONLY(g, "mee_group_find_pooled_keyed", "d_located_out (the located rows serve the backward) is");
+    if (d_step_index_out) MEE_FP32_GROUP_ONLY(g, "mee_group_find_pooled_keyed", "d_step_index_out (the step index serves the backward) is");
+    PooledCall c = pooled_call("mee_group_find_pooled_keyed", d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, d_found, mode, stream).of(g);
+    c.located = d_located_out;
+    c.keyed = true; c.out_row_stride = out_row_stride; c.step_index = d_step_index_out;
+    return pooled_find(c);
 }
 
 // mee_group_find_pooled_tiered with the keyed store: the same GROUPED && TIERED instances and keys in flight, KEYED
@@ -1330,28 +1310,10 @@ int mee_group_find_pooled_tiered_keyed(mee_group* hot, mee_group* cold, const in
                                        void* d_out, uint32_t out_dtype, size_t out_row_stride, uint8_t* d_found, uint32_t* d_step_index_out, int mode,
                                        uint32_t flags, void* stream) {
     MEE_RANGE("mee_group_find_pooled_tiered_keyed");
-    const char* name = "mee_group_find_pooled_tiered_keyed";
-    if (!hot || !cold || (bags_per_table && (!d_bag_offsets || !d_out)) || (n && !d_keys)) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
-    if (int rc = tiered_groups_check(hot, cold, flags, name)) return rc;
-    if (mode != MEE_POOL_SUM && mode != MEE_POOL_MEAN) return fail(MEE_ERR_INVALID_ARG, "%s: mode must be MEE_POOL_SUM or MEE_POOL_MEAN", name);
-    uint64_t stride4 = 0;
-    if (int rc = keyed_out_check(name, (uint64_t)hot->n_tables * hot->dim4 * 4, hot->n_tables, bags_per_table, d_out, out_dtype, out_row_stride, d_step_index_out != nullptr, &stride4)) return rc;
-    if (bags_per_table == 0) return MEE_OK;
-    if (int rc = group_refresh(hot, stream)) return rc;
-    if (int rc = group_refresh(cold, stream)) return rc;
-    DeviceGuard guard(hot->device);
-    hipStream_t st = as_stream(stream);
-    const uint64_t n_bags = (uint64_t)hot->n_tables * bags_per_table;
-    const GroupTier tier{cold->d_desc, hot->d_init, cold->d_init, flags};
-    const KeyedOut keyed{stride4, d_step_index_out, hot->n_tables, 1ull};
-    with_pooled_shape(hot->dim4, n, n_bags, [&](auto d4, auto u, auto bpw, unsigned grid) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) {
-        constexpr int ut = (bpw == 1 && u > 2) ? 2 : u;   // the keys in flight of mee_group_find_pooled_tiered
-        find_pooled_kernel<d4, ut, bpw, true, false, bf16, false, true, false, true><<<grid, 256, 0, st>>>(
-            nullptr, nullptr, 0, d_keys, d_bag_offsets, n_bags, (float4*)d_out, d_found, 0.f, hot->dim4, mode == MEE_POOL_MEAN, hot->d_desc, bags_per_table,
-            nullptr, n, nullptr, 0, nullptr, 0, WithKeyed<GroupTier>{tier, keyed});
-    }); });
-    MEE_HIP(hipGetLastError());
-    return MEE_OK;
+    PooledCall c = pooled_call("mee_group_find_pooled_tiered_keyed", d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, d_found, mode, stream).of(hot, cold);
+    c.tier_flags = flags;
+    c.keyed = true; c.out_row_stride = out_row_stride; c.step_index = d_step_index_out;
+    return pooled_find(c);
 }
 
 int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,

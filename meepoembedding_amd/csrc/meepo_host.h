@@ -162,6 +162,9 @@ template <int DIM4> struct RowShape {   // what the row kernels' launches share 
     static constexpr int pooled_unroll_1 = DIM4 == 16 ? 4 : DIM4 == 32 ? 2 : 1;   // keys in flight per tile of a pooled lookup, one bag per wave
     static constexpr int pooled_unroll_4 = DIM4 == 16 ? 2 : 1;                    // ... four bags per wave
 };
+// The launch shape of a pooled lookup, picked by the batch's average bag (n, the number of keys, is a host value): 12 keys or more per bag -> one bag per
+// wave, shorter -> four bags per wave.  with_pooled_shape (meepo_find.hip) and the mixed group's launches (meepo_mixed.hip) ask here.
+inline bool pooled_wave_per_bag(size_t n, uint64_t n_bags) { return n / n_bags >= 12; }
 // FTRL-Proximal's step arguments (SPEC.md §4): lr finite and > 0; beta, l1, l2 neither NaN nor negative (checked before any launch)
 inline bool ftrl_args_ok(float lr, float beta, float l1, float l2) { return lr > 0.f && lr < __builtin_inff() && beta >= 0.f && l1 >= 0.f && l2 >= 0.f; }
 
@@ -202,11 +205,6 @@ int tiered_groups_check(const mee_group* hot, const mee_group* cold, uint32_t co
 // The keyed pooled lookups (SPEC.md §3 "Keyed output"; defined in meepo_find.hip).  keyed_out_check: what every keyed entry point checks about its output
 // before anything is launched or written — dtype and alignment (16 bytes for fp32, 8 for bf16), out_row_stride (elements; 0 = width) a multiple of 4 and
 // at least `width`, and n_tables * bags_per_table < 2^32 when a step index is asked for; -> the stride in element groups.
-// group_find_pooled_keyed: mee_group_find_pooled_keyed under the caller's name; index_by_bag: the step index holds the bag (a mixed group of one class,
-// whose step reads class-major gradient rows) instead of sample * n_tables + member.
 int keyed_out_check(const char* name, uint64_t width, uint64_t n_tables, uint64_t bags_per_table, const void* d_out, uint32_t out_dtype,
                     uint64_t out_row_stride, bool want_index, uint64_t* stride4);
-int group_find_pooled_keyed(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out,
-                            uint32_t out_dtype, uint64_t out_row_stride, uint8_t* d_found, int64_t* d_located_out, uint32_t* d_step_index_out,
-                            bool index_by_bag, int mode, void* stream, const char* name);
 }

@@ -13,6 +13,7 @@
 #include "meepo_device.h"
 #include "meepo_host.h"
 #include "meepo_mixed_plan.h"
+#include "meepo_table_int.h"
 
 namespace mee {
 
@@ -233,6 +234,17 @@ static int mixed_refresh(mee_mixed_group* g, void* stream) {
     return MEE_OK;
 }
 
+// The prelude of a lookup with insert_missing.  `found` = present before the call, for a key repeated in the batch too: a read-only probe pass fixes the
+// mask before the ensure pass creates anything; the lookup that follows leaves the mask alone.
+static int mixed_insert_missing(mee_mixed_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, uint64_t B, uint8_t* d_found, hipStream_t st) {
+    DeviceGuard guard(g->device);
+    mixed_locate_kernel<false><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_mdesc, g->d_init, g->n_tables, d_bag_offsets, B, d_keys, n, d_found,
+                                                                      nullptr, nullptr, 0, nullptr, nullptr);
+    mixed_ensure_kernel<<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_mdesc, g->d_init, g->n_tables, d_bag_offsets, B, d_keys, n, d_found);
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
 extern "C" {
 
 int mee_mixed_group_create(mee_table* const* tables, uint32_t n_tables, uint64_t max_apply_batch, mee_mixed_group** out) {
@@ -327,20 +339,14 @@ int mee_mixed_group_find_pooled(mee_mixed_group* g, const int64_t* d_keys, size_
     hipStream_t st = (hipStream_t)stream;
     const uint64_t B = bags_per_table;
     if (insert_missing && n) {
-        // `found` = present before the call, for a key repeated in the batch too: a read-only probe pass fixes the mask before the ensure
-        // pass creates anything; the lookup then leaves the mask alone
-        DeviceGuard guard(g->device);
-        mixed_locate_kernel<false><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_mdesc, g->d_init, g->n_tables, d_bag_offsets, B, d_keys, n, d_found,
-                                                                          nullptr, nullptr, 0, nullptr, nullptr);
-        mixed_ensure_kernel<<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_mdesc, g->d_init, g->n_tables, d_bag_offsets, B, d_keys, n, d_found);
-        MEE_HIP(hipGetLastError());
+        if (int rc = mixed_insert_missing(g, d_keys, n, d_bag_offsets, B, d_found, st)) return rc;
         d_found = nullptr;
     }
     if (g->sub.size() == 1)   // one width: the uniform group's launch, bit for bit
         return mee_group_find_pooled_as(g->sub[0], d_keys, n, d_bag_offsets, bags_per_table, nullptr, d_out, out_dtype, d_found, d_located, mode, stream);
     DeviceGuard guard(g->device);
     const uint64_t n_bags = (uint64_t)g->n_tables * B;
-    const bool wave_per_bag = n / n_bags >= 12;   // with_pooled_shape's rule (meepo_find.hip)
+    const bool wave_per_bag = pooled_wave_per_bag(n, n_bags);
     const uint64_t units = (uint64_t)g->n_tables * (wave_per_bag ? B : (B + 3) / 4);
     with_flag(wave_per_bag, [&](auto wpb) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) { with_value<2, 16>(g->run_time_cw, [&](auto cw) {
         mixed_find_pooled_kernel<wpb ? 1 : 4, bf16, cw><<<grid_for(units, 4, 1u << 20), 256, 0, st>>>(g->d_desc, g->d_mdesc, g->n_tables, d_keys, d_bag_offsets, B, (float4*)d_out,
@@ -382,20 +388,20 @@ int mee_mixed_group_find_pooled_keyed(mee_mixed_group* g, const int64_t* d_keys,
     if (int rc = mixed_refresh(g, stream)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const uint64_t B = bags_per_table;
-    if (insert_missing && n) {   // as mee_mixed_group_find_pooled: the present-before mask, then the creation pass; the lookup leaves the mask alone
-        DeviceGuard guard(g->device);
-        mixed_locate_kernel<false><<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_mdesc, g->d_init, g->n_tables, d_bag_offsets, B, d_keys, n, d_found,
-                                                                          nullptr, nullptr, 0, nullptr, nullptr);
-        mixed_ensure_kernel<<<grid_for(n, 16, 8192), 256, 0, st>>>(g->d_desc, g->d_mdesc, g->d_init, g->n_tables, d_bag_offsets, B, d_keys, n, d_found);
-        MEE_HIP(hipGetLastError());
+    if (insert_missing && n) {
+        if (int rc = mixed_insert_missing(g, d_keys, n, d_bag_offsets, B, d_found, st)) return rc;
         d_found = nullptr;
     }
-    if (g->sub.size() == 1)   // one width: the uniform group's keyed launch; the step index names the bag, as the mixed step reads class-major rows
-        return group_find_pooled_keyed(g->sub[0], d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, stride4 * 4, d_found, d_located, d_step_index_out,
-                                       true, mode, stream, name);
+    if (g->sub.size() == 1) {   // one width: the uniform group's keyed launch; the step index names the bag, as the mixed step reads class-major rows
+        PooledCall c{name};
+        c.of(g->sub[0]);
+        c.keys = d_keys; c.n = n; c.offsets = d_bag_offsets; c.bags = bags_per_table; c.out = d_out; c.out_dtype = out_dtype; c.found = d_found; c.located = d_located;
+        c.mode = mode; c.keyed = true; c.out_row_stride = stride4 * 4; c.step_index = d_step_index_out; c.index_by_bag = true; c.stream = stream;
+        return pooled_find(c);
+    }
     DeviceGuard guard(g->device);
     const uint64_t n_bags = (uint64_t)g->n_tables * B;
-    const bool wave_per_bag = n / n_bags >= 12;   // with_pooled_shape's rule (meepo_find.hip)
+    const bool wave_per_bag = pooled_wave_per_bag(n, n_bags);
     const uint64_t units = (uint64_t)g->n_tables * (wave_per_bag ? B : (B + 3) / 4);
     const KeyedOut keyed{stride4, d_step_index_out, 1ull, B};
     with_flag(wave_per_bag, [&](auto wpb) { with_flag(out_dtype == MEE_DTYPE_BF16, [&](auto bf16) { with_value<2, 16>(g->run_time_cw, [&](auto cw) {
@@ -430,17 +436,20 @@ int mee_mixed_group_keyed_grads(mee_mixed_group* g, const void* d_keyed_grads, u
 
 }  // extern "C"
 
-// the step: per class, the select launch and the class group's grouped apply on the class's slice of bag_grads
-template <class Apply>
+// the step: per class, the select launch and the class group's pooled step (group_apply_pooled, meepo_table.hip) on the class's slice of bag_grads.
+// The scalars are refused before anything else, so before the first class's select launch.
 static int mixed_apply_common(mee_mixed_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_bag_grads,
-                              const uint32_t* d_bag_of_position, const int64_t* d_located, size_t n, uint32_t kind, void* stream, const char* name, Apply&& apply) {
+                              const uint32_t* d_bag_of_position, const int64_t* d_located, size_t n, uint32_t kind, const OptScalars& s, void* stream, const char* name) {
+    OptArgs a;
+    if (int rc = opt_args(kind, s, name, &a)) return rc;
     if (!g || (n && ((!d_keys && !d_located) || !d_bag_grads || !d_bag_of_position || !bags_per_table)) || (n && !d_located && !d_bag_offsets))
         return fail(MEE_ERR_INVALID_ARG, "%s: null argument / zero bags_per_table", name);
     if (!g->max_apply_batch || g->optimizer == MEE_OPT_NONE) return fail(MEE_ERR_UNSUPPORTED, "%s: group was created with max_apply_batch = 0 or its tables have no optimizer", name);
     if (g->optimizer != kind) return fail(MEE_ERR_UNSUPPORTED, "%s: the group's tables were created with optimizer=%u", name, g->optimizer);
     if (n > g->max_apply_batch) return fail(MEE_ERR_BATCH_TOO_LARGE, "%s: n=%zu exceeds the group's max_apply_batch=%llu", name, n, (unsigned long long)g->max_apply_batch);
     if (n == 0) return MEE_OK;
-    if (g->sub.size() == 1) return apply(g->sub[0], d_keys, d_bag_offsets, d_bag_grads, d_bag_of_position, d_located);   // one width: the uniform group's step
+    if (g->sub.size() == 1)   // one width: the uniform group's step
+        return group_apply_pooled(g->sub[0], d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_bag_of_position, d_located, n, a, stream, name);
     if (int rc = mixed_refresh(g, stream)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const uint64_t B = bags_per_table;
@@ -453,7 +462,7 @@ static int mixed_apply_common(mee_mixed_group* g, const int64_t* d_keys, const u
             MEE_HIP(hipGetLastError());
         }
         // the class is one [T_c * B, dim_c] array of bag_grads; positions of other classes carry EMPTY handles
-        if (int rc = apply(g->sub[c], nullptr, nullptr, d_bag_grads + B * g->plan.class_off4[c] * 4, g->d_rows, g->d_handles)) return rc;
+        if (int rc = group_apply_pooled(g->sub[c], nullptr, nullptr, bags_per_table, d_bag_grads + B * g->plan.class_off4[c] * 4, g->d_rows, g->d_handles, n, a, stream, name)) return rc;
     }
     return MEE_OK;
 }
@@ -464,36 +473,24 @@ int mee_mixed_group_apply_adagrad_pooled(mee_mixed_group* g, const int64_t* d_ke
                                          const float* d_bag_grads, const uint32_t* d_bag_of_position, const int64_t* d_located, size_t n, float lr,
                                          float eps, void* stream) {
     MEE_RANGE("mee_mixed_group_apply_adagrad_pooled");
-    return mixed_apply_common(g, d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_bag_of_position, d_located, n, MEE_OPT_ADAGRAD, stream,
-                              "mee_mixed_group_apply_adagrad_pooled",
-                              [&](mee_group* s, const int64_t* k, const uint64_t* o, const float* gr, const uint32_t* gi, const int64_t* loc) {
-                                  return mee_group_apply_adagrad_pooled(s, k, o, bags_per_table, gr, gi, loc, n, lr, eps, stream);
-                              });
+    return mixed_apply_common(g, d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_bag_of_position, d_located, n, MEE_OPT_ADAGRAD, {lr, eps}, stream,
+                              "mee_mixed_group_apply_adagrad_pooled");
 }
 
 int mee_mixed_group_apply_adam_pooled(mee_mixed_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table,
                                       const float* d_bag_grads, const uint32_t* d_bag_of_position, const int64_t* d_located, size_t n, float lr,
                                       float beta1, float beta2, float eps, uint64_t step, void* stream) {
     MEE_RANGE("mee_mixed_group_apply_adam_pooled");
-    if (step == 0) return fail(MEE_ERR_INVALID_ARG, "mee_mixed_group_apply_adam_pooled: step must be >= 1");
-    return mixed_apply_common(g, d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_bag_of_position, d_located, n, MEE_OPT_ADAM, stream,
-                              "mee_mixed_group_apply_adam_pooled",
-                              [&](mee_group* s, const int64_t* k, const uint64_t* o, const float* gr, const uint32_t* gi, const int64_t* loc) {
-                                  return mee_group_apply_adam_pooled(s, k, o, bags_per_table, gr, gi, loc, n, lr, beta1, beta2, eps, step, stream);
-                              });
+    return mixed_apply_common(g, d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_bag_of_position, d_located, n, MEE_OPT_ADAM, {lr, beta1, beta2, eps, step}, stream,
+                              "mee_mixed_group_apply_adam_pooled");
 }
 
 int mee_mixed_group_apply_ftrl_pooled(mee_mixed_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table,
                                       const float* d_bag_grads, const uint32_t* d_bag_of_position, const int64_t* d_located, size_t n, float lr,
                                       float beta, float l1, float l2, void* stream) {
     MEE_RANGE("mee_mixed_group_apply_ftrl_pooled");
-    if (!mee::ftrl_args_ok(lr, beta, l1, l2))   // before the first class's select launch
-        return fail(MEE_ERR_INVALID_ARG, "mee_mixed_group_apply_ftrl_pooled: lr must be finite and > 0; beta, l1 and l2 must be >= 0");
-    return mixed_apply_common(g, d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_bag_of_position, d_located, n, MEE_OPT_FTRL, stream,
-                              "mee_mixed_group_apply_ftrl_pooled",
-                              [&](mee_group* s, const int64_t* k, const uint64_t* o, const float* gr, const uint32_t* gi, const int64_t* loc) {
-                                  return mee_group_apply_ftrl_pooled(s, k, o, bags_per_table, gr, gi, loc, n, lr, beta, l1, l2, stream);
-                              });
+    return mixed_apply_common(g, d_keys, d_bag_offsets, bags_per_table, d_bag_grads, d_bag_of_position, d_located, n, MEE_OPT_FTRL, {lr, beta, l1, l2}, stream,
+                              "mee_mixed_group_apply_ftrl_pooled");
 }
 
 }  // extern "C"

@@ -977,12 +977,57 @@ int mee_locate(const mee_table* t, const int64_t* d_keys, size_t n, int64_t* d_s
     return MEE_OK;
 }
 
-// One sparse-optimizer step: the bucketed apply (meepo_apply.hip) — partition by hash bucket (skipped after mee_apply_prepare / a training
+}  // extern "C"
+
+// ---- the optimizer steps (SPEC.md §4): 18 entry points = {adagrad, adam, ftrl} x a form of the table's step (by key | located | indexed) or of the group's
+// (per position | pooled | indexed).  opt_args knows the rules' scalars, the form knows its own arguments, the two paths below know the rest.
+int mee::opt_args(uint32_t kind, const OptScalars& s, const char* name, OptArgs* out) {
+    OptArgs a{};
+    a.kind = kind;
+    if (kind == MEE_OPT_ADAGRAD) { a.lr = s.lr; a.eps = s.a; }
+    else if (kind == MEE_OPT_ADAM) {
+        if (s.step == 0) return fail(MEE_ERR_INVALID_ARG, "%s: step must be >= 1", name);
+        const float beta1 = s.a, beta2 = s.b;
+        a.eps = s.c;
+        const double bc1 = 1.0 - pow((double)beta1, (double)s.step), bc2 = 1.0 - pow((double)beta2, (double)s.step);
+        a.step_size = (float)((double)s.lr * sqrt(bc2) / bc1);  // SPEC.md §4
+        a.omb1 = 1.0f - beta1; a.omb2 = 1.0f - beta2;
+    } else {   // FTRL-Proximal: z in plane 1, n in plane 2; lr, beta, l1, l2 travel in the argument block as they are (eps = beta, omb1 = l1, omb2 = l2)
+        if (!ftrl_args_ok(s.lr, s.a, s.b, s.c))
+            return fail(MEE_ERR_INVALID_ARG, "%s: lr must be finite and > 0; beta, l1 and l2 must be >= 0 (got lr=%g beta=%g l1=%g l2=%g)", name, s.lr, s.a, s.b, s.c);
+        a.lr = s.lr; a.eps = s.a; a.omb1 = s.b; a.omb2 = s.c;
+    }
+    *out = a;
+    return MEE_OK;
+}
+// Which refusal wins when the scalars AND a form's own argument are wrong is part of the interface: Adam's step is refused in front of the form's arguments,
+// FTRL's scalars behind them.  So a new optimizer is a case in opt_args AND a decision here (in front, unless there is a reason): the two step paths below
+// call opt_args at one of two places by this answer, and tests/golden/host_transcript.txt pins the outcome for every entry point.
+static bool scalars_first(uint32_t kind) { return kind != MEE_OPT_FTRL; }
+
+// the grad of position i is row d_grad_index[i] of d_grads (pooled lookups: the bag's grad row serves every key of the bag)
+static int check_grad_rows(size_t n, const uint32_t* d_grad_index, size_t n_grad_rows, const char* name) {
+    if (n && (!d_grad_index || n_grad_rows == 0 || n_grad_rows > 0xFFFFFFFFull))
+        return fail(MEE_ERR_INVALID_ARG, "%s: null index, or n_grad_rows not in [1, 2^32)", name);
+    return MEE_OK;
+}
+
+// One sparse-optimizer step of a table: the bucketed apply (meepo_apply.hip) — partition by hash bucket (skipped after mee_apply_prepare / a training
 // forward that carried it), then ONE kernel of block-local LDS dedup + update.  (Rounds 1-3 kept a second implementation beside it, a global
 // group table with five launches per step; it is gone: batches of any size up to max_batch take this path.)
-// `d_slots` (nullable): the slot of every position as mee_find_located of the same step reported it.
-static int apply_common(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, const OptArgs& a, void* stream,
-                        const char* name, const uint32_t* d_gidx = nullptr, const int64_t* d_slots = nullptr) {
+struct TableStep {   // the form of the step
+    enum Kind { ByKey, Located, Indexed } kind = ByKey;
+    const int64_t* slots = nullptr;     // Located: the slot of every position as mee_find_located of the same step reported it (the main pass skips its probe)
+    const uint32_t* index = nullptr;    // Indexed: position i takes row index[i] of the grads' grad_rows rows
+    size_t grad_rows = 0;
+};
+static int apply_common(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, uint32_t kind, const OptScalars& s, const TableStep& f, void* stream, const char* name) {
+    OptArgs a;
+    if (scalars_first(kind)) { if (int rc = opt_args(kind, s, name, &a)) return rc; }
+    if (f.kind == TableStep::Located && n && !f.slots) return fail(MEE_ERR_INVALID_ARG, "%s: null slots", name);
+    if (f.kind == TableStep::Indexed) { if (int rc = check_grad_rows(n, f.index, f.grad_rows, name)) return rc; }
+    if (!scalars_first(kind)) { if (int rc = opt_args(kind, s, name, &a)) return rc; }
+    a.grad_rows = (uint32_t)f.grad_rows;
     MEE_FP32_ROWS_ONLY(t, name);
     if (!t || (n && (!d_keys || !d_grads))) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
     if (t->optimizer != a.kind) return fail(MEE_ERR_UNSUPPORTED, "%s: table was created with optimizer=%u", name, t->optimizer);
@@ -998,10 +1043,8 @@ static int apply_common(mee_table* t, const int64_t* d_keys, const float* d_grad
         plan = t->pending.plan;
         t->pending = {};
     } else if (int rc = bucket_apply_prepare(t, d_keys, nn, st, plan)) return rc;
-    return bucket_apply_launch(t, plan, d_grads, nn, a, d_gidx, d_slots, st);
+    return bucket_apply_launch(t, plan, d_grads, nn, a, f.index, f.slots, st);
 }
-
-static OptArgs adam_args(float lr, float beta1, float beta2, float eps, uint64_t step);
 
 // ---- grouped apply: ONE sparse-optimizer step over the jagged batch of a whole group (meepo_group.hip holds the group) ----
 // locate (member << 48 | slot per position) -> the bucketed apply with the located rows as "keys" (two occurrences of a key of one
@@ -1033,70 +1076,90 @@ static int group_apply_common(mee_group* g, const int64_t* d_keys, const uint64_
     if (int rc = bucket_apply_prepare(t, gslot, nn, st, plan)) return rc;
     return bucket_apply_launch(t, plan, d_grads, nn, a, d_gidx, gslot, st, g->d_desc, g->n_tables);
 }
+// the pooled form behind its scalars: one grad row per bag, the members' key segments bounded by every bags_per_table-th bag offset
+int mee::group_apply_pooled(mee_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_bag_grads, const uint32_t* d_grad_index,
+                            const int64_t* d_located, size_t n, const OptArgs& a_, void* stream, const char* name) {
+    OptArgs a = a_;
+    a.grad_rows = g ? (uint32_t)(g->n_tables * bags_per_table) : 0;
+    return group_apply_common(g, d_keys, d_bag_offsets, d_bag_grads, n, a, stream, name, bags_per_table, d_grad_index, d_located);
+}
+struct GroupStep {   // the form of the group's step
+    enum Kind { PerPosition, Pooled, Indexed } kind = PerPosition;
+    const uint32_t* index = nullptr;    // Pooled, Indexed: position i takes row index[i] of the grads
+    size_t bags_per_table = 0;          // Pooled: d_offsets are bag offsets; the backward of mee_group_find_pooled
+    const int64_t* located = nullptr;   // Pooled: the rows that lookup located (nullable)
+    size_t grad_rows = 0;               // Indexed: mee_apply_*_indexed on every member with its segment [d_offsets[j], d_offsets[j + 1]) of keys and index entries
+};
+static int group_apply_step(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, uint32_t kind, const OptScalars& s, const GroupStep& f,
+                            void* stream, const char* name) {
+    MEE_FP32_GROUP_ONLY(g, name);
+    OptArgs a;
+    if (scalars_first(kind)) { if (int rc = opt_args(kind, s, name, &a)) return rc; }
+    if (f.kind == GroupStep::Pooled && n && (!f.index || !f.bags_per_table)) return fail(MEE_ERR_INVALID_ARG, "%s: null index / zero bags_per_table", name);
+    if (f.kind == GroupStep::Indexed) { if (int rc = check_grad_rows(n, f.index, f.grad_rows, name)) return rc; }
+    if (!scalars_first(kind)) { if (int rc = opt_args(kind, s, name, &a)) return rc; }
+    if (f.kind == GroupStep::Pooled) return group_apply_pooled(g, d_keys, d_offsets, f.bags_per_table, d_grads, f.index, f.located, n, a, stream, name);
+    a.grad_rows = (uint32_t)f.grad_rows;
+    return group_apply_common(g, d_keys, d_offsets, d_grads, n, a, stream, name, 1, f.index);
+}
+
+extern "C" {
 
 int mee_group_apply_adagrad(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr,
                             float eps, void* stream) {
     MEE_RANGE("mee_group_apply_adagrad");
-    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_adagrad");
-    OptArgs a{};
-    a.kind = MEE_OPT_ADAGRAD; a.lr = lr; a.eps = eps;
-    return group_apply_common(g, d_keys, d_offsets, d_grads, n, a, stream, "mee_group_apply_adagrad");
+    return group_apply_step(g, d_keys, d_offsets, d_grads, n, MEE_OPT_ADAGRAD, {lr, eps}, {}, stream, "mee_group_apply_adagrad");
 }
 int mee_group_apply_adam(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr,
                          float beta1, float beta2, float eps, uint64_t step, void* stream) {
     MEE_RANGE("mee_group_apply_adam");
-    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_adam");
-    if (step == 0) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_adam: step must be >= 1");
-    return group_apply_common(g, d_keys, d_offsets, d_grads, n, adam_args(lr, beta1, beta2, eps, step), stream, "mee_group_apply_adam");
+    return group_apply_step(g, d_keys, d_offsets, d_grads, n, MEE_OPT_ADAM, {lr, beta1, beta2, eps, step}, {}, stream, "mee_group_apply_adam");
+}
+int mee_group_apply_ftrl(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr, float beta,
+                         float l1, float l2, void* stream) {
+    MEE_RANGE("mee_group_apply_ftrl");
+    return group_apply_step(g, d_keys, d_offsets, d_grads, n, MEE_OPT_FTRL, {lr, beta, l1, l2}, {}, stream, "mee_group_apply_ftrl");
 }
 
 int mee_group_apply_adagrad_pooled(mee_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table,
                                    const float* d_bag_grads, const uint32_t* d_grad_index, const int64_t* d_located, size_t n, float lr,
                                    float eps, void* stream) {
     MEE_RANGE("mee_group_apply_adagrad_pooled");
-    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_adagrad_pooled");
-    if (n && (!d_grad_index || !bags_per_table)) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_adagrad_pooled: null index / zero bags_per_table");
-    OptArgs a{};
-    a.kind = MEE_OPT_ADAGRAD; a.lr = lr; a.eps = eps;
-    a.grad_rows = g ? (uint32_t)(g->n_tables * bags_per_table) : 0;   // one grad row per bag
-    // the members' key segments are bounded by every bags_per_table-th bag offset
-    return group_apply_common(g, d_keys, d_bag_offsets, d_bag_grads, n, a, stream, "mee_group_apply_adagrad_pooled", bags_per_table, d_grad_index,
-                              d_located);
+    return group_apply_step(g, d_keys, d_bag_offsets, d_bag_grads, n, MEE_OPT_ADAGRAD, {lr, eps}, {GroupStep::Pooled, d_grad_index, bags_per_table, d_located}, stream,
+                            "mee_group_apply_adagrad_pooled");
 }
 int mee_group_apply_adam_pooled(mee_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table,
                                 const float* d_bag_grads, const uint32_t* d_grad_index, const int64_t* d_located, size_t n, float lr,
                                 float beta1, float beta2, float eps, uint64_t step, void* stream) {
     MEE_RANGE("mee_group_apply_adam_pooled");
-    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_adam_pooled");
-    if (step == 0) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_adam_pooled: step must be >= 1");
-    if (n && (!d_grad_index || !bags_per_table)) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_adam_pooled: null index / zero bags_per_table");
-    OptArgs a = adam_args(lr, beta1, beta2, eps, step);
-    a.grad_rows = g ? (uint32_t)(g->n_tables * bags_per_table) : 0;   // one grad row per bag
-    return group_apply_common(g, d_keys, d_bag_offsets, d_bag_grads, n, a, stream, "mee_group_apply_adam_pooled", bags_per_table, d_grad_index,
-                              d_located);
+    return group_apply_step(g, d_keys, d_bag_offsets, d_bag_grads, n, MEE_OPT_ADAM, {lr, beta1, beta2, eps, step}, {GroupStep::Pooled, d_grad_index, bags_per_table, d_located}, stream,
+                            "mee_group_apply_adam_pooled");
+}
+int mee_group_apply_ftrl_pooled(mee_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_bag_grads,
+                                const uint32_t* d_grad_index, const int64_t* d_located, size_t n, float lr, float beta, float l1, float l2,
+                                void* stream) {
+    MEE_RANGE("mee_group_apply_ftrl_pooled");
+    return group_apply_step(g, d_keys, d_bag_offsets, d_bag_grads, n, MEE_OPT_FTRL, {lr, beta, l1, l2}, {GroupStep::Pooled, d_grad_index, bags_per_table, d_located}, stream,
+                            "mee_group_apply_ftrl_pooled");
 }
 
-// mee_apply_*_indexed on every member with its segment [d_offsets[j], d_offsets[j + 1]) of keys and index entries: position i takes row
-// d_grad_index[i] of d_grads (the owner's backward of a sharded group's bags: one gradient row per run that arrived)
-static int check_grad_rows(size_t n, const uint32_t* d_grad_index, size_t n_grad_rows, const char* name);
 int mee_group_apply_adagrad_indexed(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows,
                                     const uint32_t* d_grad_index, size_t n, float lr, float eps, void* stream) {
     MEE_RANGE("mee_group_apply_adagrad_indexed");
-    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_adagrad_indexed");
-    if (int rc = check_grad_rows(n, d_grad_index, n_grad_rows, "mee_group_apply_adagrad_indexed")) return rc;
-    OptArgs a{};
-    a.kind = MEE_OPT_ADAGRAD; a.lr = lr; a.eps = eps; a.grad_rows = (uint32_t)n_grad_rows;
-    return group_apply_common(g, d_keys, d_offsets, d_grads, n, a, stream, "mee_group_apply_adagrad_indexed", 1, d_grad_index);
+    return group_apply_step(g, d_keys, d_offsets, d_grads, n, MEE_OPT_ADAGRAD, {lr, eps}, {GroupStep::Indexed, d_grad_index, 0, nullptr, n_grad_rows}, stream,
+                            "mee_group_apply_adagrad_indexed");
 }
 int mee_group_apply_adam_indexed(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows,
                                  const uint32_t* d_grad_index, size_t n, float lr, float beta1, float beta2, float eps, uint64_t step, void* stream) {
     MEE_RANGE("mee_group_apply_adam_indexed");
-    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_adam_indexed");
-    if (step == 0) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_adam_indexed: step must be >= 1");
-    if (int rc = check_grad_rows(n, d_grad_index, n_grad_rows, "mee_group_apply_adam_indexed")) return rc;
-    OptArgs a = adam_args(lr, beta1, beta2, eps, step);
-    a.grad_rows = (uint32_t)n_grad_rows;
-    return group_apply_common(g, d_keys, d_offsets, d_grads, n, a, stream, "mee_group_apply_adam_indexed", 1, d_grad_index);
+    return group_apply_step(g, d_keys, d_offsets, d_grads, n, MEE_OPT_ADAM, {lr, beta1, beta2, eps, step}, {GroupStep::Indexed, d_grad_index, 0, nullptr, n_grad_rows}, stream,
+                            "mee_group_apply_adam_indexed");
+}
+int mee_group_apply_ftrl_indexed(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows,
+                                 const uint32_t* d_grad_index, size_t n, float lr, float beta, float l1, float l2, void* stream) {
+    MEE_RANGE("mee_group_apply_ftrl_indexed");
+    return group_apply_step(g, d_keys, d_offsets, d_grads, n, MEE_OPT_FTRL, {lr, beta, l1, l2}, {GroupStep::Indexed, d_grad_index, 0, nullptr, n_grad_rows}, stream,
+                            "mee_group_apply_ftrl_indexed");
 }
 
 int mee_apply_prepare(mee_table* t, const int64_t* d_keys, size_t n, void* stream) {
@@ -1153,124 +1216,48 @@ int mee_apply_discard(mee_table* t, void* stream) {
 
 int mee_apply_adagrad(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, float lr, float eps, void* stream) {
     MEE_RANGE("mee_apply_adagrad");
-    OptArgs a{};
-    a.kind = MEE_OPT_ADAGRAD; a.lr = lr; a.eps = eps;
-    return apply_common(t, d_keys, d_grads, n, a, stream, "mee_apply_adagrad");
-}
-static OptArgs adam_args(float lr, float beta1, float beta2, float eps, uint64_t step) {
-    OptArgs a{};
-    a.kind = MEE_OPT_ADAM; a.eps = eps;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    a.step_size = (float)((double)lr * sqrt(bc2) / bc1);  // SPEC.md §4
-    a.omb1 = 1.0f - beta1; a.omb2 = 1.0f - beta2;
-    return a;
+    return apply_common(t, d_keys, d_grads, n, MEE_OPT_ADAGRAD, {lr, eps}, {}, stream, "mee_apply_adagrad");
 }
 int mee_apply_adam(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, float lr, float beta1, float beta2,
                    float eps, uint64_t step, void* stream) {
     MEE_RANGE("mee_apply_adam");
-    if (step == 0) return fail(MEE_ERR_INVALID_ARG, "mee_apply_adam: step must be >= 1");
-    return apply_common(t, d_keys, d_grads, n, adam_args(lr, beta1, beta2, eps, step), stream, "mee_apply_adam");
+    return apply_common(t, d_keys, d_grads, n, MEE_OPT_ADAM, {lr, beta1, beta2, eps, step}, {}, stream, "mee_apply_adam");
+}
+int mee_apply_ftrl(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, float lr, float beta, float l1, float l2, void* stream) {
+    MEE_RANGE("mee_apply_ftrl");
+    return apply_common(t, d_keys, d_grads, n, MEE_OPT_FTRL, {lr, beta, l1, l2}, {}, stream, "mee_apply_ftrl");
 }
 // the same with the slots the forward lookup of this step located (mee_find_located): the main pass skips its probe
 int mee_apply_adagrad_located(mee_table* t, const int64_t* d_keys, const int64_t* d_slots, const float* d_grads, size_t n, float lr, float eps,
                               void* stream) {
     MEE_RANGE("mee_apply_adagrad_located");
-    if (n && !d_slots) return fail(MEE_ERR_INVALID_ARG, "mee_apply_adagrad_located: null slots");
-    OptArgs a{};
-    a.kind = MEE_OPT_ADAGRAD; a.lr = lr; a.eps = eps;
-    return apply_common(t, d_keys, d_grads, n, a, stream, "mee_apply_adagrad_located", nullptr, d_slots);
+    return apply_common(t, d_keys, d_grads, n, MEE_OPT_ADAGRAD, {lr, eps}, {TableStep::Located, d_slots}, stream, "mee_apply_adagrad_located");
 }
 int mee_apply_adam_located(mee_table* t, const int64_t* d_keys, const int64_t* d_slots, const float* d_grads, size_t n, float lr, float beta1,
                            float beta2, float eps, uint64_t step, void* stream) {
     MEE_RANGE("mee_apply_adam_located");
-    if (step == 0) return fail(MEE_ERR_INVALID_ARG, "mee_apply_adam_located: step must be >= 1");
-    if (n && !d_slots) return fail(MEE_ERR_INVALID_ARG, "mee_apply_adam_located: null slots");
-    return apply_common(t, d_keys, d_grads, n, adam_args(lr, beta1, beta2, eps, step), stream, "mee_apply_adam_located", nullptr, d_slots);
-}
-// the grad of position i is row d_grad_index[i] of d_grads (pooled lookups: the bag's grad row serves every key of the bag)
-static int check_grad_rows(size_t n, const uint32_t* d_grad_index, size_t n_grad_rows, const char* name) {
-    if (n && (!d_grad_index || n_grad_rows == 0 || n_grad_rows > 0xFFFFFFFFull))
-        return fail(MEE_ERR_INVALID_ARG, "%s: null index, or n_grad_rows not in [1, 2^32)", name);
-    return MEE_OK;
-}
-int mee_apply_adagrad_indexed(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index,
-                              size_t n, float lr, float eps, void* stream) {
-    MEE_RANGE("mee_apply_adagrad_indexed");
-    if (int rc = check_grad_rows(n, d_grad_index, n_grad_rows, "mee_apply_adagrad_indexed")) return rc;
-    OptArgs a{};
-    a.kind = MEE_OPT_ADAGRAD; a.lr = lr; a.eps = eps; a.grad_rows = (uint32_t)n_grad_rows;
-    return apply_common(t, d_keys, d_grads, n, a, stream, "mee_apply_adagrad_indexed", d_grad_index);
-}
-int mee_apply_adam_indexed(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index,
-                           size_t n, float lr, float beta1, float beta2, float eps, uint64_t step, void* stream) {
-    MEE_RANGE("mee_apply_adam_indexed");
-    if (step == 0) return fail(MEE_ERR_INVALID_ARG, "mee_apply_adam_indexed: step must be >= 1");
-    if (int rc = check_grad_rows(n, d_grad_index, n_grad_rows, "mee_apply_adam_indexed")) return rc;
-    OptArgs a = adam_args(lr, beta1, beta2, eps, step);
-    a.grad_rows = (uint32_t)n_grad_rows;
-    return apply_common(t, d_keys, d_grads, n, a, stream, "mee_apply_adam_indexed", d_grad_index);
-}
-
-// FTRL-Proximal (SPEC.md §4): z in plane 1, n in plane 2; lr, beta, l1, l2 travel in the argument block as they are
-static int ftrl_args(OptArgs& a, float lr, float beta, float l1, float l2, const char* name) {
-    if (!ftrl_args_ok(lr, beta, l1, l2))
-        return fail(MEE_ERR_INVALID_ARG, "%s: lr must be finite and > 0; beta, l1 and l2 must be >= 0 (got lr=%g beta=%g l1=%g l2=%g)", name, lr, beta, l1, l2);
-    a = OptArgs{};
-    a.kind = MEE_OPT_FTRL; a.lr = lr; a.eps = beta; a.omb1 = l1; a.omb2 = l2;
-    return MEE_OK;
-}
-int mee_apply_ftrl(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n, float lr, float beta, float l1, float l2, void* stream) {
-    MEE_RANGE("mee_apply_ftrl");
-    OptArgs a;
-    if (int rc = ftrl_args(a, lr, beta, l1, l2, "mee_apply_ftrl")) return rc;
-    return apply_common(t, d_keys, d_grads, n, a, stream, "mee_apply_ftrl");
+    return apply_common(t, d_keys, d_grads, n, MEE_OPT_ADAM, {lr, beta1, beta2, eps, step}, {TableStep::Located, d_slots}, stream, "mee_apply_adam_located");
 }
 int mee_apply_ftrl_located(mee_table* t, const int64_t* d_keys, const int64_t* d_slots, const float* d_grads, size_t n, float lr, float beta, float l1,
                            float l2, void* stream) {
     MEE_RANGE("mee_apply_ftrl_located");
-    if (n && !d_slots) return fail(MEE_ERR_INVALID_ARG, "mee_apply_ftrl_located: null slots");
-    OptArgs a;
-    if (int rc = ftrl_args(a, lr, beta, l1, l2, "mee_apply_ftrl_located")) return rc;
-    return apply_common(t, d_keys, d_grads, n, a, stream, "mee_apply_ftrl_located", nullptr, d_slots);
+    return apply_common(t, d_keys, d_grads, n, MEE_OPT_FTRL, {lr, beta, l1, l2}, {TableStep::Located, d_slots}, stream, "mee_apply_ftrl_located");
+}
+// the grad of position i is row d_grad_index[i] of d_grads
+int mee_apply_adagrad_indexed(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index,
+                              size_t n, float lr, float eps, void* stream) {
+    MEE_RANGE("mee_apply_adagrad_indexed");
+    return apply_common(t, d_keys, d_grads, n, MEE_OPT_ADAGRAD, {lr, eps}, {TableStep::Indexed, nullptr, d_grad_index, n_grad_rows}, stream, "mee_apply_adagrad_indexed");
+}
+int mee_apply_adam_indexed(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index,
+                           size_t n, float lr, float beta1, float beta2, float eps, uint64_t step, void* stream) {
+    MEE_RANGE("mee_apply_adam_indexed");
+    return apply_common(t, d_keys, d_grads, n, MEE_OPT_ADAM, {lr, beta1, beta2, eps, step}, {TableStep::Indexed, nullptr, d_grad_index, n_grad_rows}, stream, "mee_apply_adam_indexed");
 }
 int mee_apply_ftrl_indexed(mee_table* t, const int64_t* d_keys, const float* d_grads, size_t n_grad_rows, const uint32_t* d_grad_index, size_t n,
                            float lr, float beta, float l1, float l2, void* stream) {
     MEE_RANGE("mee_apply_ftrl_indexed");
-    if (int rc = check_grad_rows(n, d_grad_index, n_grad_rows, "mee_apply_ftrl_indexed")) return rc;
-    OptArgs a;
-    if (int rc = ftrl_args(a, lr, beta, l1, l2, "mee_apply_ftrl_indexed")) return rc;
-    a.grad_rows = (uint32_t)n_grad_rows;
-    return apply_common(t, d_keys, d_grads, n, a, stream, "mee_apply_ftrl_indexed", d_grad_index);
-}
-int mee_group_apply_ftrl(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n, float lr, float beta,
-                         float l1, float l2, void* stream) {
-    MEE_RANGE("mee_group_apply_ftrl");
-    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_ftrl");
-    OptArgs a;
-    if (int rc = ftrl_args(a, lr, beta, l1, l2, "mee_group_apply_ftrl")) return rc;
-    return group_apply_common(g, d_keys, d_offsets, d_grads, n, a, stream, "mee_group_apply_ftrl");
-}
-int mee_group_apply_ftrl_pooled(mee_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_bag_grads,
-                                const uint32_t* d_grad_index, const int64_t* d_located, size_t n, float lr, float beta, float l1, float l2,
-                                void* stream) {
-    MEE_RANGE("mee_group_apply_ftrl_pooled");
-    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_ftrl_pooled");
-    if (n && (!d_grad_index || !bags_per_table)) return fail(MEE_ERR_INVALID_ARG, "mee_group_apply_ftrl_pooled: null index / zero bags_per_table");
-    OptArgs a;
-    if (int rc = ftrl_args(a, lr, beta, l1, l2, "mee_group_apply_ftrl_pooled")) return rc;
-    a.grad_rows = g ? (uint32_t)(g->n_tables * bags_per_table) : 0;   // one grad row per bag
-    return group_apply_common(g, d_keys, d_bag_offsets, d_bag_grads, n, a, stream, "mee_group_apply_ftrl_pooled", bags_per_table, d_grad_index,
-                              d_located);
-}
-int mee_group_apply_ftrl_indexed(mee_group* g, const int64_t* d_keys, const uint64_t* d_offsets, const float* d_grads, size_t n_grad_rows,
-                                 const uint32_t* d_grad_index, size_t n, float lr, float beta, float l1, float l2, void* stream) {
-    MEE_RANGE("mee_group_apply_ftrl_indexed");
-    MEE_FP32_GROUP_ONLY(g, "mee_group_apply_ftrl_indexed");
-    if (int rc = check_grad_rows(n, d_grad_index, n_grad_rows, "mee_group_apply_ftrl_indexed")) return rc;
-    OptArgs a;
-    if (int rc = ftrl_args(a, lr, beta, l1, l2, "mee_group_apply_ftrl_indexed")) return rc;
-    a.grad_rows = (uint32_t)n_grad_rows;
-    return group_apply_common(g, d_keys, d_offsets, d_grads, n, a, stream, "mee_group_apply_ftrl_indexed", 1, d_grad_index);
+    return apply_common(t, d_keys, d_grads, n, MEE_OPT_FTRL, {lr, beta, l1, l2}, {TableStep::Indexed, nullptr, d_grad_index, n_grad_rows}, stream, "mee_apply_ftrl_indexed");
 }
 
 /* duplicate-key reduction with row sums, sync-free (meepo_dedup.hip): see include/meepo_embedding.h */

@@ -228,6 +228,14 @@ __device__ __forceinline__ void update_row(const OptArgs& a, float4* values, flo
     values[o] = w; s1[o] = x1;
     if (opt_has_s2(a.kind)) s2[o] = x2;
 }
+// The one place that turns an entry point's scalars into the kernels' argument block, or refuses them under `name` (meepo_table.hip): Adam's step >= 1
+// and bias correction, FTRL's ftrl_args_ok and the fields it borrows.  scalars: adagrad (lr, eps) | adam (lr, beta1, beta2, eps) | ftrl (lr, beta, l1, l2).
+// A new optimizer is a case there, not another set of entry points' worth of checks.
+struct OptScalars { float lr, a, b, c; uint64_t step; };
+int opt_args(uint32_t kind, const OptScalars& s, const char* name, OptArgs* out);
+// mee_group_apply_*_pooled behind its scalars: the mixed group's step runs it per width class (meepo_mixed.hip)
+int group_apply_pooled(mee_group* g, const int64_t* d_keys, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_bag_grads, const uint32_t* d_grad_index,
+                       const int64_t* d_located, size_t n, const OptArgs& a, void* stream, const char* name);
 // the bucketed apply path (meepo_apply.hip)
 uint32_t xcd_split_for_device(int device);   // the calibrated share of a bucket pair's hash range that goes to the even bucket (0 = even halves)
 int bucket_scratch_alloc(mee_table* t);
@@ -248,6 +256,10 @@ int bucket_dedup_sum(mee_table* t, const int64_t* d_keys, const float* d_grads, 
 
 // ---- host helpers the table's translation units share (meepo_table.hip, meepo_find.hip, meepo_export.hip) ------------------------------
 inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
+inline bool stream_is_capturing(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
+}
 inline int64_t handle_tag_of(const mee_table* t) { return (int64_t)(t->handle_epoch & kHandleEpochMask) << kHandleSlotBits; }
 inline const float* plane_of(const mee_table* t, uint32_t plane) { return plane == 0 ? t->values : plane == 1 ? t->s1 : plane == 2 ? t->s2 : nullptr; }
 // Allocation of one value/state plane in the table's value memory (HBM, or pinned device-mapped host DRAM for a cold tier)
@@ -270,6 +282,41 @@ struct FindPath {   // which lookup find_plane runs
     int nt = -1;                    // Plain: this call's cache policy (mee_find_ex); -1: the table's
     uint32_t out_dtype = MEE_DTYPE_F32;   // Plain, Located, SkipPadding: MEE_DTYPE_BF16 = d_out holds bf16 rows
 };
+// What one pooled lookup is (find_pooled_kernel): every C entry point of the family fills one and calls pooled_find, which refuses what all of them
+// refuse — null arguments, the pair's / the two groups' mismatches, out_dtype, mode, weights with MEAN, a single table's located rows without weights, the
+// keyed output's shape — under `name`, in that order, and launches the ONE kernel instance the fields pick.  A new form of the lookup is a field here and
+// an arm in pooled_find, not another launch site.  (What a serving table or group does not have is refused by the entry point, in front of the call.)
+struct PooledCall {
+    const char* name;                    // the entry point, for the refusals
+    // the source: one table | a hot/cold pair (table = the hot one) | a group | a group of pairs (group = the hot one)
+    enum Source { Table, Pair, Group, GroupOfPairs } source = Table;
+    const mee_table *table = nullptr, *cold = nullptr;
+    mee_group *group = nullptr, *cold_group = nullptr;
+    const int64_t* keys = nullptr;
+    size_t n = 0;
+    const uint64_t* offsets = nullptr;
+    size_t bags = 0;                     // a table's or a jagged map's n_bags; a group's bags_per_table otherwise
+    const float* weights = nullptr;      // non-null: position i adds weights[i] * row_i (SUM only)
+    void* out = nullptr;
+    uint32_t out_dtype = MEE_DTYPE_F32;
+    uint8_t* found = nullptr;
+    int64_t* located = nullptr;          // a table's come with weights only; a group's with or without
+    int mode = MEE_POOL_SUM;
+    bool jagged = false;                 // a group's members' bag counts are read from member_bags (fp32 out, no weights)
+    const uint64_t* member_bags = nullptr;
+    uint32_t tier_flags = 0;             // MEE_TIER_COUNT_* of a pair or a group of pairs
+    bool keyed = false;                  // a group's keyed output (SPEC.md §3 "Keyed output"): the row stride in elements (0 = the width) and the step index
+    uint64_t out_row_stride = 0;
+    uint32_t* step_index = nullptr;
+    bool index_by_bag = false;           // the step index holds the bag (a mixed group of one class) instead of sample * n_tables + member
+    void* stream = nullptr;
+
+    PooledCall& of(const mee_table* t) { source = Table; table = t; return *this; }
+    PooledCall& of(const mee_table* hot, const mee_table* cold_) { source = Pair; table = hot; cold = cold_; return *this; }
+    PooledCall& of(mee_group* g) { source = Group; group = g; return *this; }
+    PooledCall& of(mee_group* hot, mee_group* cold_) { source = GroupOfPairs; group = hot; cold_group = cold_; return *this; }
+};
+int pooled_find(const PooledCall& c);
 // the training forward and find_or_insert with the output type as a parameter (the C-ABI's fp32 and typed forms forward here)
 int find_located_prepare(mee_table* t, const int64_t* d_keys, size_t n, void* d_out, uint32_t out_dtype, uint8_t* d_found, int64_t* d_slots_out, void* stream, const char* name);
 int find_plane(const mee_table* t, const float* plane, float miss_value, const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream, FindPath path = {});

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: build_sanitized.sh address|thread OUTDIR — TEST INFRASTRUCTURE: the HOST halves of csrc/*.hip (hipcc --cuda-host-only), the HIP stand-in
-# (hip_host_stub.cpp), the librccl stand-in (fake_rccl.cpp) and the driver (sanitize_host.cpp), all instrumented with one sanitizer.  CPU container, no GPU.
+# (hip_host_stub.cpp), the librccl stand-in (fake_rccl.cpp) and the drivers (sanitize_host.cpp, host_transcript.cpp), all instrumented with one sanitizer.  CPU container, no GPU.
 set -e
 SAN=$1; OUT=$2
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)
@@ -22,4 +22,5 @@ gcc -c -fPIC $OUT/fatbin_syms.c -o $OUT/fatbin_syms.o
 $CXX -shared -fsanitize=$SAN $OUT/meepo_*.o $OUT/hip_host_stub.o $OUT/fatbin_syms.o -ldl -lpthread -o $OUT/libmeepo_host.so
 $CXX -shared -fsanitize=$SAN $OUT/fake_rccl.o -L$OUT -lmeepo_host -lrt -Wl,-rpath,$OUT -o $OUT/libfake_rccl.so
 $CXX -std=c++17 -O1 -g -fsanitize=$SAN -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I$ROOT/include $ROOT/tests/cabi/sanitize_host.cpp -L$OUT -lmeepo_host -lpthread -Wl,-rpath,$OUT -o $OUT/sanitize_host
-echo "built $OUT/sanitize_host ($SAN)"
+$CXX -std=c++17 -O1 -g -fsanitize=$SAN -fno-omit-frame-pointer -I$ROOT/include $ROOT/tests/cabi/host_transcript.cpp -L$OUT -lmeepo_host -lpthread -Wl,-rpath,$OUT -o $OUT/host_transcript
+echo "built $OUT/sanitize_host and $OUT/host_transcript ($SAN)"
