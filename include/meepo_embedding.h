@@ -271,6 +271,25 @@ int mee_find_pooled_weighted(const mee_table* t, const int64_t* d_keys, size_t n
 int mee_pooled_weighted_backward(const mee_table* t, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,
                                  size_t n_bags, const float* d_weights, const float* d_bag_grads, float* d_grads_out, float* d_weight_grads_out,
                                  void* stream);
+/* Max pooling (torch.nn.EmbeddingBag mode="max"; fp32-row tables).  Bags and their clamping are mee_find_pooled's; the row of a position is what
+ * mee_find returns (the stored row, or the default row for an absent or reserved key — it takes part like any row).  For every element j the bag is
+ * scanned in ascending position: the first position p0 gives m = row[p0][j], a = p0; each later position p replaces them iff row[p][j] > m (the IEEE
+ * comparison).  So the first of equal values wins, +0.0 behind -0.0 does not replace it, a NaN at the first position stays and a NaN at a later one is
+ * never taken.  d_out[b, j] = m, a copy of the bits (no arithmetic: nothing is rounded in fp32); with out_dtype = MEE_DTYPE_BF16 (8-byte aligned) m is
+ * rounded once, the comparisons are still made in fp32.  d_argmax_out (nullable; [n_bags, dim] uint32, 16-byte aligned) receives a, the ABSOLUTE batch
+ * position.  An empty bag gives +0.0 everywhere and argmax 0xFFFFFFFF.  d_found (nullable) is per key, as in mee_find.  Reads only: the table, its
+ * status word, hit counters and sketch stay as they are.  One launch, no host synchronisation, no allocation.
+ * MEE_ERR_UNSUPPORTED: a bf16-row or int8-row table.  MEE_ERR_INVALID_ARG, before anything is launched or written: a null pointer where rows are
+ * due, an unknown out_dtype, a misaligned bf16 d_out or d_argmax_out, n >= 2^32 with d_argmax_out.  n_bags == 0 succeeds and writes nothing. */
+int mee_find_pooled_max(const mee_table* t, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, void* d_out,
+                        uint32_t out_dtype, uint8_t* d_found /* nullable */, uint32_t* d_argmax_out /* nullable */, void* stream);
+/* Its backward, before the table step: for every position i that bag b covers, d_grads_out[i, j] = (d_argmax[b, j] == i) ? d_bag_grads[b, j] : +0.0
+ * — a copy of the bits (a -0.0 gradient stays -0.0 at the winner).  d_argmax = what mee_find_pooled_max of this step wrote, d_bag_grads = [n_bags,
+ * dim] fp32.  Positions that no bag covers are not written; no table row and no key is read.  The table step is then mee_apply_*(d_keys,
+ * d_grads_out) when the bags partition [0, n): every key of a bag takes a step, with zeros where it did not win.  MEE_ERR_INVALID_ARG: a null
+ * pointer where rows are due, a misaligned d_argmax, n >= 2^32 (always: positions are 32 bits). */
+int mee_pooled_max_backward(const mee_table* t, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const uint32_t* d_argmax,
+                            const float* d_bag_grads, float* d_grads_out, void* stream);
 /* Pooled lookup over a hot/cold PAIR of tables (a key lives in exactly one of them; meepoembedding_amd/tiered.py): mee_find_pooled on the
  * union, bit for bit — the rows of a bag's positions added in position order in fp32 (the first copied, each later one added, no fma),
  * MEE_POOL_MEAN divides by (float)length, an empty bag gives zeros, offsets past n are cut at n, a decreasing pair is an empty bag.  The
@@ -465,6 +484,14 @@ int mee_group_find_pooled_weighted(mee_group* g, const int64_t* d_keys, size_t n
 int mee_group_pooled_weighted_backward(mee_group* g, const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets,
                                        size_t bags_per_table, const float* d_weights, const float* d_bag_grads, float* d_grads_out,
                                        float* d_weight_grads_out, void* stream);
+/* Max pooling over the collection (fp32-row groups): mee_find_pooled_max / mee_pooled_max_backward of member b / bags_per_table on its bags, in one
+ * launch each; every member uses its own default row, and the argmax positions are absolute in the whole batch.  The step after the backward is
+ * mee_group_apply_*(d_keys, member offsets, d_grads_out).  Refusals as the table forms'; MEE_ERR_UNSUPPORTED for a bf16-row group.  The lookup
+ * re-reads a member's planes in its first call after mee_reserve on that member, as every group lookup does; the backward reads no table. */
+int mee_group_find_pooled_max(mee_group* g, const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out,
+                              uint32_t out_dtype, uint8_t* d_found /* nullable */, uint32_t* d_argmax_out /* nullable */, void* stream);
+int mee_group_pooled_max_backward(mee_group* g, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const uint32_t* d_argmax,
+                                  const float* d_bag_grads, float* d_grads_out, void* stream);
 /* The embedding-bag collection over hot/cold PAIRS: member j of hot_group and member j of cold_group are the two tiers of pair j (a key lives in
  * exactly one of them; meepoembedding_amd/tiered.py, TieredTableGroup).  mee_group_find_pooled_tiered is, by definition, mee_find_pooled_tiered(hot
  * member b / bags_per_table, cold member b / bags_per_table) on every bag b, bit for bit, in ONE launch for all n_tables x bags_per_table bags: a

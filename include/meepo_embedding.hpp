@@ -77,6 +77,10 @@ public:
     void find_pooled_weighted(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const float* d_weights, float* d_out, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, void* stream = nullptr) const { check(mee_find_pooled_weighted(t_, d_keys, n, d_bag_offsets, n_bags, d_weights, d_out, d_found, d_located_out, stream)); }
     // its backward: d_grads_out[i,:] = d_weights[i] * d_bag_grads[bag(i),:] (feed to apply_*), d_weight_grads_out[i] = <d_bag_grads[bag(i)], row_i> (nullable)
     void pooled_weighted_backward(const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const float* d_weights, const float* d_bag_grads, float* d_grads_out, float* d_weight_grads_out = nullptr, void* stream = nullptr) const { check(mee_pooled_weighted_backward(t_, d_keys, d_located, n, d_bag_offsets, n_bags, d_weights, d_bag_grads, d_grads_out, d_weight_grads_out, stream)); }
+    // max pooling (torch.nn.EmbeddingBag mode="max"): d_out[b, j] = the first greatest row[p][j] over the bag's positions, d_argmax_out[b, j] = that batch position (nullable)
+    void find_pooled_max(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, uint8_t* d_found = nullptr, uint32_t* d_argmax_out = nullptr, void* stream = nullptr) const { check(mee_find_pooled_max(t_, d_keys, n, d_bag_offsets, n_bags, d_out, out_dtype, d_found, d_argmax_out, stream)); }
+    // its backward: d_grads_out[i, j] = d_argmax[bag(i), j] == i ? d_bag_grads[bag(i), j] : +0.0 (feed to apply_*)
+    void pooled_max_backward(size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const uint32_t* d_argmax, const float* d_bag_grads, float* d_grads_out, void* stream = nullptr) const { check(mee_pooled_max_backward(t_, n, d_bag_offsets, n_bags, d_argmax, d_bag_grads, d_grads_out, stream)); }
     // second-tier pass: fills only the positions an earlier find (on another table) left with d_found == 0
     void find_missing(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream = nullptr) const { check(mee_find_missing(t_, d_keys, n, d_out, d_found, stream)); }
     void insert(const int64_t* d_keys, const float* d_values, size_t n, void* stream = nullptr) { check(mee_insert(t_, d_keys, d_values, n, stream)); }
@@ -235,6 +239,9 @@ public:
     // the weighted embedding-bag collection: bag b belongs to member b / bags_per_table (mee_group_find_pooled_weighted / mee_group_pooled_weighted_backward)
     void find_pooled_weighted(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights, float* d_out, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, void* stream = nullptr) { check(mee_group_find_pooled_weighted(g_, d_keys, n, d_bag_offsets, bags_per_table, d_weights, d_out, d_found, d_located_out, stream)); }
     void pooled_weighted_backward(const int64_t* d_keys, const int64_t* d_located, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights, const float* d_bag_grads, float* d_grads_out, float* d_weight_grads_out = nullptr, void* stream = nullptr) { check(mee_group_pooled_weighted_backward(g_, d_keys, d_located, n, d_bag_offsets, bags_per_table, d_weights, d_bag_grads, d_grads_out, d_weight_grads_out, stream)); }
+    // max pooling over the collection (mee_group_find_pooled_max / mee_group_pooled_max_backward): argmax positions are absolute in the whole batch
+    void find_pooled_max(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, uint8_t* d_found = nullptr, uint32_t* d_argmax_out = nullptr, void* stream = nullptr) { check(mee_group_find_pooled_max(g_, d_keys, n, d_bag_offsets, bags_per_table, d_out, out_dtype, d_found, d_argmax_out, stream)); }
+    void pooled_max_backward(size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const uint32_t* d_argmax, const float* d_bag_grads, float* d_grads_out, void* stream = nullptr) { check(mee_group_pooled_max_backward(g_, n, d_bag_offsets, bags_per_table, d_argmax, d_bag_grads, d_grads_out, stream)); }
     // the collection with a different number of bags per member: bag b belongs to member j with d_member_bags[j] <= b < d_member_bags[j + 1]
     // (mee_group_find_pooled_jagged), and its backward, mee_apply_*_indexed per member (mee_group_apply_*_indexed)
     void find_pooled_jagged(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const uint64_t* d_member_bags, float* d_out, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, int mode = MEE_POOL_SUM, void* stream = nullptr) {

@@ -174,6 +174,12 @@ PROTOTYPES = {
     "mee_pooled_weighted_backward": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "mee_group_find_pooled_weighted": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "mee_group_pooled_weighted_backward": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    # max pooling: (table | group), keys, n, bag offsets, (n_bags | bags_per_table), out, out_dtype, found, argmax, stream; its backward: (table | group), n,
+    # bag offsets, (n_bags | bags_per_table), argmax, bag grads, grads, stream
+    "mee_find_pooled_max": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp, _vp]),
+    "mee_group_find_pooled_max": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _u32, _vp, _vp, _vp]),
+    "mee_pooled_max_backward": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "mee_group_pooled_max_backward": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
     "mee_apply_adagrad_indexed": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _f32, _f32, _vp]),
     "mee_apply_adam_indexed": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _f32, _f32, _f32, _f32, _u64, _vp]),
     "mee_dedup_keys": (C.c_int, [_vp, _vp, _sz, _vp, _vp, C.c_int64, _vp]),

@@ -836,15 +836,6 @@ static bool find_captured(const void* func, const mee_table* t, const float* pla
     return own_node(true);
 }
 
-// The launch shape of a pooled lookup.  n (the number of keys, a host value) only picks it: mostly short bags -> four bags per wave on a grid of
-// n_bags / 16 blocks, a long average (12 keys or more per bag) -> one bag per wave on n_bags / 4.  f(d4, unroll, bags_per_wave, grid).
-template <class F> void with_pooled_shape(uint32_t dim4, size_t n, uint64_t n_bags, F&& f) {
-    with_row_shape(dim4, [&](auto d4) {
-        if (pooled_wave_per_bag(n, n_bags)) f(d4, std::integral_constant<int, RowShape<d4>::pooled_unroll_1>{}, std::integral_constant<int, 1>{}, grid_for(n_bags, 4, 1u << 20));
-        else f(d4, std::integral_constant<int, RowShape<d4>::pooled_unroll_4>{}, std::integral_constant<int, 4>{}, grid_for(n_bags, 16, 1u << 20));
-    });
-}
-
 // every dense lookup of one plane (declared with FindPath in meepo_table_int.h: find_or_insert's first pass calls it too)
 int find_plane(const mee_table* t, const float* plane, float miss_value, const int64_t* d_keys, size_t n, float* d_out,
                uint8_t* d_found, void* stream, FindPath path) {

@@ -165,6 +165,14 @@ template <int DIM4> struct RowShape {   // what the row kernels' launches share 
 // The launch shape of a pooled lookup, picked by the batch's average bag (n, the number of keys, is a host value): 12 keys or more per bag -> one bag per
 // wave, shorter -> four bags per wave.  with_pooled_shape (meepo_find.hip) and the mixed group's launches (meepo_mixed.hip) ask here.
 inline bool pooled_wave_per_bag(size_t n, uint64_t n_bags) { return n / n_bags >= 12; }
+// The launch shape of a pooled lookup over one row width (meepo_find.hip, meepo_pool_max.hip).  n (the number of keys, a host value) only picks it: mostly
+// short bags -> four bags per wave on a grid of n_bags / 16 blocks, a long average -> one bag per wave on n_bags / 4.  f(d4, unroll, bags_per_wave, grid).
+template <class F> void with_pooled_shape(uint32_t dim4, size_t n, uint64_t n_bags, F&& f) {
+    with_row_shape(dim4, [&](auto d4) {
+        if (pooled_wave_per_bag(n, n_bags)) f(d4, std::integral_constant<int, RowShape<d4>::pooled_unroll_1>{}, std::integral_constant<int, 1>{}, grid_for(n_bags, 4, 1u << 20));
+        else f(d4, std::integral_constant<int, RowShape<d4>::pooled_unroll_4>{}, std::integral_constant<int, 4>{}, grid_for(n_bags, 16, 1u << 20));
+    });
+}
 // FTRL-Proximal's step arguments (SPEC.md §4): lr finite and > 0; beta, l1, l2 neither NaN nor negative (checked before any launch)
 inline bool ftrl_args_ok(float lr, float beta, float l1, float l2) { return lr > 0.f && lr < __builtin_inff() && beta >= 0.f && l1 >= 0.f && l2 >= 0.f; }
 

@@ -12,7 +12,9 @@
     meepo::lookup_padded / meepo::apply_grad_padded                   padded sequences: [n_bags, max_len, dim], the backward an indexed step
     meepo::lookup_pooled[_weighted] / meepo::apply_grad_pooled[_weighted]   embedding bags (sum / mean; weighted sum with the grad of
                                                                                  the per-sample weights)
-    meepo::lookup_pooled_keyed / meepo::apply_grad_pooled_keyed       a group's bags as [bags_per_table, sum of dims] (layout="keyed"): the lookup
+    meepo::lookup_pooled_max / meepo::apply_grad_pooled_max           embedding bags, mode "max": the lookup also hands out the winning position of
+                                                                                 every element, from which the backward builds the [n, dim] grads its step takes
+    meepo::lookup_pooled_keyed / meepo::apply_grad_pooled_keyed      a group's bags as [bags_per_table, sum of dims] (layout="keyed"): the lookup
                                                                                  writes that block and the index its step reads the gradient with
 
 The update happens INSIDE backward, so the layer has no torch parameters and needs no torch optimizer.  Both ops have
@@ -39,6 +41,7 @@ Optional methods:
     layout_epoch                        changes when stored rows move: handles a forward took are dropped by its backward
     find_padded                         the padded sequence lookup in one launch (LookupTable, TableGroup, TieredLookupTable, TieredTableGroup; the step
                                         is then apply_*(grad_index=) / a group's apply_indexed); without it DynamicEmbeddingSequence composes it from find
+    find_pooled_max, pooled_max_backward   max pooling in one launch each (LookupTable, TableGroup); without them DynamicEmbeddingBag(mode="max") is refused
     admission_refusal() -> str | None   why a layer's min_count is refused over this table (None: it admits); a class without the method has
                                         no admission
 `_nn_prepared` on a table with find_located is this module's: the (tensor, length) whose apply partition the last training forward left pending.
@@ -512,6 +515,57 @@ def _backward_pooled_weighted(ctx, grad_out, _grad_located):
 lookup_pooled_weighted.register_autograd(_backward_pooled_weighted, setup_context=_setup_pooled_weighted)
 
 
+# ---- max pooled (torch.nn.EmbeddingBag mode="max"): bag[j] = the first greatest row_i[j] over the bag ---------------------------------------
+# forward = find_pooled_max, one launch, which also says which position won every element (argmax); backward = pooled_max_backward (grads [n, dim] = the
+# bag's grad element at the winner, +0.0 elsewhere), then the table's (the group's) step on those grads, as the weighted pair's
+@torch.library.custom_op("meepo::lookup_pooled_max", mutates_args=())
+def lookup_pooled_max(keys: torch.Tensor, bag_offsets: torch.Tensor, anchor: torch.Tensor, table_id: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """-> (pooled rows [n_bags, dim], argmax [n_bags, dim] int32 — the batch position every element came from, -1 in an empty bag)"""
+    layer = _layer(table_id)
+    _create_unseen(layer, keys, bag_offsets)
+    argmax = torch.empty((bag_offsets.numel() - 1, layer.table.dim), dtype=torch.int32, device=keys.device)
+    out = layer.table.find_pooled_max(keys, bag_offsets, argmax=argmax, **_dtype_kw(layer))[0]
+    return out, argmax
+
+
+@lookup_pooled_max.register_fake
+def _(keys, bag_offsets, anchor, table_id):
+    layer = _layer(table_id)
+    n_bags = bag_offsets.numel() - 1
+    return keys.new_empty((n_bags, layer.table.dim), dtype=layer.out_dtype), keys.new_empty((n_bags, layer.table.dim), dtype=torch.int32)
+
+
+@torch.library.custom_op("meepo::apply_grad_pooled_max", mutates_args=())
+def apply_grad_pooled_max(keys: torch.Tensor, bag_offsets: torch.Tensor, argmax: torch.Tensor, grad_bags: torch.Tensor, table_id: int) -> None:
+    layer = _layer(table_id)
+    grads = layer.table.pooled_max_backward(bag_offsets, argmax, grad_bags.contiguous(), keys.numel())
+    if layer.traits.grouped:   # a TableGroup: one grouped step over the members' key segments
+        _step_now(layer).apply_to(layer.table, keys, _member_offsets(layer.table, bag_offsets), grads)
+    else:
+        _step_now(layer).apply_to(layer.table, keys, grads)
+
+
+@apply_grad_pooled_max.register_fake
+def _(keys, bag_offsets, argmax, grad_bags, table_id):
+    return None
+
+
+def _setup_pooled_max(ctx, inputs, output):
+    keys, bag_offsets, _, table_id = inputs
+    ctx.save_for_backward(keys, bag_offsets, output[1])
+    ctx.table_id = table_id
+    ctx.mark_non_differentiable(output[1])
+
+
+def _backward_pooled_max(ctx, grad_out, _grad_argmax):
+    keys, bag_offsets, argmax = ctx.saved_tensors
+    apply_grad_pooled_max(keys, bag_offsets, argmax, grad_out.contiguous().to(torch.float32), ctx.table_id)   # a bf16 layer's grad is widened (exact)
+    return None, None, None, None
+
+
+lookup_pooled_max.register_autograd(_backward_pooled_max, setup_context=_setup_pooled_max)
+
+
 # ---- the same pair of ops over a TableGroup: the whole embedding collection of a model in one lookup / one update -------
 @torch.library.custom_op("meepo::lookup_jagged", mutates_args=())
 def lookup_jagged(keys: torch.Tensor, offsets: torch.Tensor, anchor: torch.Tensor, table_id: int, insert_missing: bool) -> torch.Tensor:
@@ -721,6 +775,9 @@ class DynamicEmbeddingBag(_SparseLayer):
     min_count (with create_missing=True; a LookupTable or TableGroup created with admission=True, or a TieredLookupTable / TieredTableGroup whose hot
     tables were): that creation pass admits — an unseen id is created only once its table's sketch has seen it min_count times, and pools as the
     default row, untrained, until then.
+    mode="max" (a LookupTable or a TableGroup; table-major layout, no per_sample_weights): forward is one launch that keeps, per element, the first greatest
+    value of the bag's rows and the position it came from; backward builds the [n, dim] grads — the bag's grad element at the winning position, +0.0 at the
+    others — and runs the table's (the group's) step on them, so every id of a bag takes a step.  Bit for bit torch.nn.EmbeddingBag(mode="max") in the forward.
     layout="keyed" (groups only): forward returns ONE [bags_per_table, sum of dims] tensor — row s holds sample s of every member side by side (member j
     at column sum(dims[:j])), the block a dense network reads — for a MixedTableGroup too.  Over a TableGroup, TieredTableGroup or MixedTableGroup the
     lookup writes that block itself and the step reads the gradient where it lies; over any other group (sharded groups, CPU adapters) the layer
@@ -731,10 +788,16 @@ class DynamicEmbeddingBag(_SparseLayer):
                  l1: float = 0.0, l2: float = 0.0):
         """out_dtype=torch.bfloat16: the bag is accumulated in fp32 and the finished row rounded once by the lookup; backward widens the bf16 grad.
         optimizer="ftrl" (tables created with OPT_FTRL): eps is FTRL's beta (default 1.0), l1 / l2 its regularisation strengths; betas is not read."""
-        if mode not in ("sum", "mean"):
-            raise ValueError("mode must be 'sum' or 'mean'")
+        if mode not in ("sum", "mean", "max"):
+            raise ValueError(f"mode must be 'sum' or 'mean', or 'max' over a LookupTable or a TableGroup (got {mode!r})")
         if layout not in ("table", "keyed"):
             raise ValueError(f"layout must be 'table' or 'keyed' (got {layout!r})")
+        if mode == "max":   # before anything is registered: the class must pool by max itself, and only the table-major layout does
+            if not (hasattr(table, "find_pooled_max") and hasattr(table, "pooled_max_backward")):
+                raise ValueError(f"mode='max': {type(table).__name__} has no find_pooled_max / pooled_max_backward (a LookupTable and a TableGroup have; hot/cold "
+                                 "pairs, tiered, mixed and sharded groups pool by sum or mean)")
+            if layout == "keyed":
+                raise ValueError(f"mode='max' has no keyed layout: {type(table).__name__}.find_pooled_max writes [n_bags, dim]; use layout='table'")
         super().__init__(table, optimizer, lr, eps, betas, out_dtype, min_count, pooled=True, creates=create_missing, l1=l1, l2=l2)
         if layout == "keyed" and not self.traits.grouped:
             raise ValueError(f"layout='keyed' is a group's layout: {type(table).__name__} is one table (or one pair), whose [n_bags, dim] is keyed already")
@@ -742,7 +805,12 @@ class DynamicEmbeddingBag(_SparseLayer):
 
     def forward(self, keys: torch.Tensor, bag_offsets: torch.Tensor, per_sample_weights: torch.Tensor | None = None) -> torch.Tensor:
         """per_sample_weights (fp32 [n], mode "sum" only): the bag is the sum of w_i * row_i; backward also yields their grad.
-        The weighted backward updates every position, so its bags must partition the keys: bag_offsets[0] = 0, bag_offsets[-1] = n."""
+        The weighted backward updates every position, so its bags must partition the keys: bag_offsets[0] = 0, bag_offsets[-1] = n.
+        mode "max" takes no per_sample_weights, as in torch.nn.EmbeddingBag; its backward updates every position too (the same rule for the bags)."""
+        if self.mode == "max":
+            if per_sample_weights is not None:
+                raise ValueError("per_sample_weights are not supported for mode='max', as in torch.nn.EmbeddingBag")
+            return lookup_pooled_max(keys, bag_offsets, self._anchor, self.table_id)[0]
         if self.layout == "keyed":
             if per_sample_weights is not None:
                 raise ValueError("layout='keyed' has no weighted bags: per_sample_weights are offered in the table-major layout only")

@@ -127,6 +127,60 @@ def _find_padded(fn, handle, device: torch.device, dim: int, k: torch.Tensor, ba
     return (out, found, lengths, step_keys, grad_index) if with_step else (out, found, lengths)
 
 
+def _argmax_buffer(argmax: torch.Tensor, n_bags: int, dim: int, device: torch.device) -> torch.Tensor:
+    """the [n_bags, dim] batch positions of max pooling: uint32 to the library (int32 holds the same bits; 0xFFFFFFFF = an empty bag)"""
+    if argmax.dtype not in (torch.uint32, torch.int32) or argmax.device != device or argmax.numel() != n_bags * dim or not argmax.is_contiguous():
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"argmax must be a contiguous uint32 or int32 buffer [{n_bags}, {dim}] on {device}")
+    return argmax
+
+
+def _find_pooled_max(fn, handle, device: torch.device, dim: int, k: torch.Tensor, bag_offsets: torch.Tensor, n_bags: int, bags_arg: int, out, found, argmax,
+                     out_dtype: torch.dtype, with_argmax: bool):
+    """max pooling over a table (fn = mee_find_pooled_max, bags_arg = n_bags) or a group (mee_group_find_pooled_max, bags_arg = bags_per_table):
+    arguments checked before any launch, buffers allocated here"""
+    dt = _out_dtype(out_dtype, out)
+    n = k.numel()
+    if out is None:
+        out = torch.empty((n_bags, dim), dtype=out_dtype, device=device)
+    elif out.device != device or out.numel() != n_bags * dim or not out.is_contiguous():
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"out must be a contiguous buffer [{n_bags}, {dim}] on {device}")
+    if found is None:
+        found = torch.empty(n, dtype=torch.uint8, device=device)
+    elif found.dtype != torch.uint8 or found.device != device or found.numel() != n or not found.is_contiguous():
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"found must be a contiguous uint8 buffer of {n} entries on {device}")
+    if argmax is not None:
+        argmax = _argmax_buffer(argmax, n_bags, dim, device)
+    elif with_argmax:
+        argmax = torch.empty((n_bags, dim), dtype=torch.uint32, device=device)
+    check(fn(handle, k.data_ptr(), n, bag_offsets.data_ptr(), bags_arg, out.data_ptr(), dt, found.data_ptr(), argmax.data_ptr() if argmax is not None else None,
+             _stream_ptr(device)))
+    return out, found, argmax
+
+
+def _pooled_max_backward(fn, handle, device: torch.device, dim: int, bag_offsets: torch.Tensor, n_bags: int, bags_arg: int, argmax: torch.Tensor,
+                         bag_grads: torch.Tensor, n: int, grads):
+    """the backward of max pooling over a table (mee_pooled_max_backward) or a group (mee_group_pooled_max_backward)"""
+    a = _argmax_buffer(argmax, n_bags, dim, device)
+    n = int(n)
+    if bag_grads.dtype != torch.float32 or bag_grads.device != device or bag_grads.numel() != n_bags * dim:
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_grads must be float32 [{n_bags}, {dim}] on {device}")
+    g = bag_grads.contiguous()
+    if grads is None:
+        grads = torch.empty((n, dim), dtype=torch.float32, device=device)
+    elif grads.dtype != torch.float32 or grads.device != device or grads.numel() != n * dim or not grads.is_contiguous():
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"grads must be a contiguous float32 buffer [{n}, {dim}] on {device}")
+    check(fn(handle, n, bag_offsets.data_ptr(), bags_arg, a.data_ptr(), g.data_ptr(), grads.data_ptr(), _stream_ptr(device)))
+    return grads
+
+
+def _max_mode_only(**given) -> None:
+    """find_pooled(mode="max") is find_pooled_max: the arguments of the other forms are refused by name"""
+    for name, value in given.items():
+        if value is not None:
+            raise ValueError(f"find_pooled(mode='max') takes no {name}: max pooling has no weighted, located or keyed form (torch.nn.EmbeddingBag refuses "
+                             "per_sample_weights with mode='max' too)")
+
+
 def _padded_places(keys, bag_offsets, max_len: int, keep_last: bool):
     """find_padded's bookkeeping in torch, the ONE place a composition gets it from (nn.lookup_padded over a table without find_padded; the tiered
     classes over tiers that are not native tables) -> (lengths [n_bags] int64, step_keys [n] int64, grad_index [n] int32, the kept positions in slot
@@ -429,7 +483,11 @@ class LookupTable:
         sums or means in position order, per-key found mask).  One output row per bag is written instead of one per key.
         weights (fp32 [n], mee_find_pooled_weighted; mode "sum" only): the bag is the sum of weights[i] * row_i.  located (int64[n]
         buffer, weighted form only) receives each key's slot handle for pooled_weighted_backward / apply_*(slots=...) of the same step.
-        out_dtype=torch.bfloat16 (mee_find_pooled_as): the bag is accumulated in fp32 as always and the finished row rounded once."""
+        out_dtype=torch.bfloat16 (mee_find_pooled_as): the bag is accumulated in fp32 as always and the finished row rounded once.
+        mode="max": find_pooled_max(keys, bag_offsets, out, found, out_dtype=out_dtype) without its argmax; weights and located are refused."""
+        if mode == "max":
+            _max_mode_only(weights=weights, located=located)
+            return self.find_pooled_max(keys, bag_offsets, out=out, found=found, out_dtype=out_dtype)[:2]
         dt = _out_dtype(out_dtype, out)
         k = self._keys(keys) if keys.numel() else keys
         n_bags = self._bag_offsets(bag_offsets)
@@ -456,6 +514,25 @@ class LookupTable:
         check(_lib.lib().mee_find_pooled(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), n_bags, out.data_ptr(), found.data_ptr(),
                                          {"sum": 0, "mean": 1}[mode], self._s()))
         return out, found
+
+    def find_pooled_max(self, keys: torch.Tensor, bag_offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
+                        argmax: torch.Tensor | None = None, out_dtype: torch.dtype = torch.float32, with_argmax: bool = False):
+        """Max pooling (mee_find_pooled_max; torch.nn.EmbeddingBag mode="max"): bags as find_pooled's -> (out [n_bags, dim], per-key found mask, argmax
+        [n_bags, dim] uint32 | None).  out[b, j] is the first greatest element j among the rows find() returns for the bag's positions — a later position
+        replaces the running one only where it is greater, so ties go to the first position and a NaN counts only at the bag's first position — copied bit
+        for bit; argmax[b, j] (with_argmax=True, or a buffer passed as argmax) is the batch position it came from.  An empty bag: +0.0 and 0xFFFFFFFF.
+        out_dtype=torch.bfloat16: the maximum, decided in fp32, is rounded once.  fp32-row tables only."""
+        k = self._keys(keys) if keys.numel() else keys
+        n_bags = self._bag_offsets(bag_offsets)
+        return _find_pooled_max(_lib.lib().mee_find_pooled_max, self._h, self.device, self.dim, k, bag_offsets, n_bags, n_bags, out, found, argmax, out_dtype,
+                                with_argmax)
+
+    def pooled_max_backward(self, bag_offsets: torch.Tensor, argmax: torch.Tensor, bag_grads: torch.Tensor, n: int, grads: torch.Tensor | None = None):
+        """Backward of find_pooled_max (mee_pooled_max_backward) -> grads [n, dim]: position i of bag b gets bag_grads[b, j] where argmax[b, j] == i and +0.0
+        elsewhere; positions no bag covers are not written.  The table step is then apply_*(keys, grads) for bags that partition [0, n): every key of a
+        bag takes a step, with zeros where it did not win (SPEC.md §3 says what that means per optimizer)."""
+        n_bags = self._bag_offsets(bag_offsets)
+        return _pooled_max_backward(_lib.lib().mee_pooled_max_backward, self._h, self.device, self.dim, bag_offsets, n_bags, n_bags, argmax, bag_grads, n, grads)
 
     def find_padded(self, keys: torch.Tensor, bag_offsets: torch.Tensor, max_len: int, keep: str = "first", out: torch.Tensor | None = None,
                     found: torch.Tensor | None = None, out_dtype: torch.dtype = torch.float32, with_step: bool = False):
@@ -1071,7 +1148,12 @@ class TableGroup:
         layout="keyed" (unweighted): the same rows as [bags_per_table, n_tables * dim] — row s holds sample s of every member side by side, what a
         dense network reads — written by the one launch (mee_group_find_pooled_keyed); `out` may be any 2-D view with stride(1) == 1, e.g. a column
         range of a wider feature block.  step_index (a uint32 / int32 [n] buffer, keyed only) receives the bag_of_position with which apply_pooled
-        reads the keyed gradient in place."""
+        reads the keyed gradient in place.
+        mode="max": find_pooled_max(keys, bag_offsets, out, found, out_dtype=out_dtype) without its argmax; located, weights, layout="keyed" and
+        step_index are refused."""
+        if mode == "max":
+            _max_mode_only(weights=weights, located=located, step_index=step_index, layout="keyed" if _check_layout(layout) else None)
+            return self.find_pooled_max(keys, bag_offsets, out=out, found=found, out_dtype=out_dtype)[:2]
         keyed = _check_layout(layout)
         dt = _out_dtype(out_dtype, None if keyed else out)
         bpt = self._check_bags(bag_offsets)
@@ -1110,6 +1192,22 @@ class TableGroup:
                                                located.data_ptr() if located is not None else None,
                                                {"sum": 0, "mean": 1}[mode], _stream_ptr(self.device)))
         return out, found
+
+    def find_pooled_max(self, keys: torch.Tensor, bag_offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
+                        argmax: torch.Tensor | None = None, out_dtype: torch.dtype = torch.float32, with_argmax: bool = False):
+        """LookupTable.find_pooled_max of every member on its bags_per_table bags, in one launch (mee_group_find_pooled_max) -> (out [n_tables *
+        bags_per_table, dim], per-key found mask, argmax | None).  Every member uses its own default row; argmax holds positions in the whole batch."""
+        bpt = self._check_bags(bag_offsets)
+        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        return _find_pooled_max(_lib.lib().mee_group_find_pooled_max, self._h, self.device, self.dim, k, bag_offsets, bpt * len(self.tables), bpt, out, found,
+                                argmax, out_dtype, with_argmax)
+
+    def pooled_max_backward(self, bag_offsets: torch.Tensor, argmax: torch.Tensor, bag_grads: torch.Tensor, n: int, grads: torch.Tensor | None = None):
+        """LookupTable.pooled_max_backward per member, in one launch (mee_group_pooled_max_backward) -> grads [n, dim].  The step is then
+        apply_adagrad / apply_adam / apply_ftrl(keys, bag_offsets[::bags_per_table].contiguous(), grads): the grads are per position."""
+        bpt = self._check_bags(bag_offsets)
+        return _pooled_max_backward(_lib.lib().mee_group_pooled_max_backward, self._h, self.device, self.dim, bag_offsets, bpt * len(self.tables), bpt, argmax,
+                                    bag_grads, n, grads)
 
     def find_padded(self, keys: torch.Tensor, bag_offsets: torch.Tensor, max_len: int, keep: str = "first", out: torch.Tensor | None = None,
                     found: torch.Tensor | None = None, out_dtype: torch.dtype = torch.float32, with_step: bool = False):

@@ -19,7 +19,7 @@ LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
          "-Wno-unused-function", "-Wno-pass-failed", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"]
-TUS = ["meepo_table", "meepo_find", "meepo_export", "meepo_apply", "meepo_dedup", "meepo_router", "meepo_group", "meepo_sharded", "meepo_mixed", "meepo_move", "meepo_padded"]
+TUS = ["meepo_table", "meepo_find", "meepo_export", "meepo_apply", "meepo_dedup", "meepo_router", "meepo_group", "meepo_sharded", "meepo_mixed", "meepo_move", "meepo_padded", "meepo_pool_max"]
 
 
 def hashes(co):
