@@ -35,7 +35,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import refuse_narrow_rows
-from .table import SparseStep, _out_dtype
+from .table import SparseStep, _buffer, _out_dtype
 
 
 class _Exchange:
@@ -646,10 +646,7 @@ class RcclShardedTable:
         dt = _out_dtype(out_dtype, out)   # (ValueError before any call)
         k = self._k(keys)
         n = k.numel()
-        if out is None:
-            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
-        if found is None:
-            found = torch.empty(n, dtype=torch.uint8, device=self.device)
+        out, found = _buffer(out, "out", out_dtype, (n, self.dim), self.device), _buffer(found, "found", torch.uint8, n, self.device)
         L = self._lib.lib()
         if dt == self._lib.DTYPE_F32:   # the fp32 entry points keep their code path
             self._check(getattr(L, name)(self._h, k.data_ptr(), n, out.data_ptr(), found.data_ptr(), self._s()))

@@ -10,6 +10,7 @@ tensors on the table's device and enqueues on torch's current stream; nothing he
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import NamedTuple
 
 import torch
@@ -38,6 +39,66 @@ def _n_bags(bag_offsets: torch.Tensor, device: torch.device) -> int:
             or bag_offsets.numel() < 1:
         raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_offsets must be contiguous int64 on {device} with n_bags + 1 entries")
     return bag_offsets.numel() - 1
+
+
+def _check_bags(bag_offsets: torch.Tensor, n_tables: int, device: torch.device) -> int:
+    """the bag_offsets of a group's pooled lookup (bag b belongs to member b // bags_per_table), checked before any launch -> bags_per_table"""
+    nb = bag_offsets.numel() - 1
+    if bag_offsets.device != device or bag_offsets.dtype not in (torch.int64, torch.uint64) or not bag_offsets.is_contiguous() \
+            or nb < 0 or nb % n_tables:
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_offsets must be contiguous int64 on {device} with n_tables * bags_per_table + 1 entries")
+    return nb // n_tables
+
+
+def _buffer(t: torch.Tensor | None, name: str, dtype, shape, device: torch.device) -> torch.Tensor:
+    """THE rule for a result buffer (DESIGN.md "Result buffers"): None -> a fresh torch.empty(shape); a caller's tensor must have the dtype (one of
+    the dtypes, where `dtype` is a tuple: the uint32 / int32 pairs; a fresh one gets the first), the operator's device, exactly prod(shape)
+    elements — the shape itself is not compared, a flat buffer is legal — and be contiguous, or the call is refused before anything is launched.
+    `shape`: a tuple, or an int for a 1-D buffer."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype[0] if type(dtype) is tuple else dtype, device=device)
+    if (t.dtype != dtype and (type(dtype) is not tuple or t.dtype not in dtype)) or t.device != device \
+            or t.numel() != (shape if type(shape) is int else math.prod(shape)) or not t.is_contiguous():
+        kinds = " or ".join(str(d) for d in dtype) if type(dtype) is tuple else str(dtype)
+        raise MeepoError(_lib.ERR_INVALID_ARG, f"{name} must be a contiguous {kinds} buffer of shape {list(shape) if type(shape) is tuple else [shape]} on {device} "
+                                               f"(got {t.dtype} {list(t.shape)} on {t.device}{'' if t.is_contiguous() else ', not contiguous'})")
+    return t
+
+
+def _pool_mode(mode: str, error=None) -> int:
+    """the library's number for a pooled lookup's mode, checked before anything is allocated.  error: the caller's exception class for another
+    name (ValueError in LookupTable and the tiered classes); without it MeepoError(ERR_INVALID_ARG), as the group classes raise"""
+    if mode == "sum":
+        return 0
+    if mode == "mean":
+        return 1
+    msg = f"mode must be 'sum' or 'mean' (got {mode!r})"
+    raise error(msg) if error is not None else MeepoError(_lib.ERR_INVALID_ARG, msg)
+
+
+def _no_bags_for_keys(n: int, n_bags: int) -> None:
+    if n and n_bags == 0:
+        raise MeepoError(_lib.ERR_INVALID_ARG, "there are keys but no bags: no bag would report them")
+
+
+def _pooled_args(k: torch.Tensor, device: torch.device, out, out_shape, out_dtype: torch.dtype, found, weights=None, mode: str = "sum", located=None,
+                 keyed: bool = False):
+    """what every pooled lookup prepares between its own argument checks and its launch, given the flat keys and the checked bag_offsets of its
+    owner: the weights checked, then the result buffers by _buffer's rule — located (only where the caller passed one), out (keyed: the
+    [bags_per_table, width] block by _keyed_out's rule) and found -> (n, weights | None, located | None, out, its row stride (keyed) | 0, found)"""
+    n = k.numel()
+    w = _check_weights(weights, mode, n, device) if weights is not None else None
+    if located is not None:
+        located = _buffer(located, "located", torch.int64, n, device)
+    if keyed:
+        out, stride = _keyed_out(out, out_shape[0], out_shape[1], out_dtype, device)
+    else:
+        out, stride = _buffer(out, "out", out_dtype, out_shape, device), 0
+    return n, w, located, out, stride, _buffer(found, "found", torch.uint8, n, device)
+
+
+def _ptr(t: torch.Tensor | None):
+    return t.data_ptr() if t is not None else None
 
 
 _OUT_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16}
@@ -91,11 +152,7 @@ def _keyed_out(out: torch.Tensor | None, bags_per_table: int, width: int, out_dt
 
 def _step_index(step_index: torch.Tensor | None, n: int, device: torch.device):
     """the data pointer of a keyed lookup's step_index buffer (None: not asked for)"""
-    if step_index is None:
-        return None
-    if step_index.dtype not in (torch.uint32, torch.int32) or step_index.device != device or step_index.numel() != n or not step_index.is_contiguous():
-        raise MeepoError(_lib.ERR_INVALID_ARG, f"step_index must be a contiguous uint32 or int32 buffer of {n} entries on {device}")
-    return step_index.data_ptr()
+    return None if step_index is None else _buffer(step_index, "step_index", (torch.uint32, torch.int32), n, device).data_ptr()
 
 
 def _find_padded(fn, handle, device: torch.device, dim: int, k: torch.Tensor, bag_offsets: torch.Tensor, n_bags: int, bags_arg: int, max_len: int,
@@ -110,14 +167,8 @@ def _find_padded(fn, handle, device: torch.device, dim: int, k: torch.Tensor, ba
     if max_len < 1:
         raise ValueError(f"max_len must be at least 1 (got {max_len})")
     n = k.numel()
-    if out is None:
-        out = torch.empty((n_bags, max_len, dim), dtype=out_dtype, device=device)
-    elif out.device != device or out.numel() != n_bags * max_len * dim or not out.is_contiguous():
-        raise MeepoError(_lib.ERR_INVALID_ARG, f"out must be a contiguous buffer [{n_bags}, {max_len}, {dim}] on {device}")
-    if found is None:
-        found = torch.zeros(n, dtype=torch.uint8, device=device)
-    elif found.dtype != torch.uint8 or found.device != device or found.numel() != n or not found.is_contiguous():
-        raise MeepoError(_lib.ERR_INVALID_ARG, f"found must be a contiguous uint8 buffer of {n} entries on {device}")
+    out = _buffer(out, "out", out_dtype, (n_bags, max_len, dim), device)
+    found = torch.zeros(n, dtype=torch.uint8, device=device) if found is None else _buffer(found, "found", torch.uint8, n, device)
     lengths = torch.empty(n_bags, dtype=torch.int64, device=device)
     step_keys = torch.full((n,), _lib.EMPTY_KEY, dtype=torch.int64, device=device) if with_step else None
     grad_index = torch.zeros(n, dtype=torch.int32, device=device) if with_step else None   # (uint32 to the library: a slot number below 2^31)
@@ -127,11 +178,9 @@ def _find_padded(fn, handle, device: torch.device, dim: int, k: torch.Tensor, ba
     return (out, found, lengths, step_keys, grad_index) if with_step else (out, found, lengths)
 
 
-def _argmax_buffer(argmax: torch.Tensor, n_bags: int, dim: int, device: torch.device) -> torch.Tensor:
+def _argmax_buffer(argmax: torch.Tensor | None, n_bags: int, dim: int, device: torch.device) -> torch.Tensor:
     """the [n_bags, dim] batch positions of max pooling: uint32 to the library (int32 holds the same bits; 0xFFFFFFFF = an empty bag)"""
-    if argmax.dtype not in (torch.uint32, torch.int32) or argmax.device != device or argmax.numel() != n_bags * dim or not argmax.is_contiguous():
-        raise MeepoError(_lib.ERR_INVALID_ARG, f"argmax must be a contiguous uint32 or int32 buffer [{n_bags}, {dim}] on {device}")
-    return argmax
+    return _buffer(argmax, "argmax", (torch.uint32, torch.int32), (n_bags, dim), device)
 
 
 def _find_pooled_max(fn, handle, device: torch.device, dim: int, k: torch.Tensor, bag_offsets: torch.Tensor, n_bags: int, bags_arg: int, out, found, argmax,
@@ -139,21 +188,10 @@ def _find_pooled_max(fn, handle, device: torch.device, dim: int, k: torch.Tensor
     """max pooling over a table (fn = mee_find_pooled_max, bags_arg = n_bags) or a group (mee_group_find_pooled_max, bags_arg = bags_per_table):
     arguments checked before any launch, buffers allocated here"""
     dt = _out_dtype(out_dtype, out)
-    n = k.numel()
-    if out is None:
-        out = torch.empty((n_bags, dim), dtype=out_dtype, device=device)
-    elif out.device != device or out.numel() != n_bags * dim or not out.is_contiguous():
-        raise MeepoError(_lib.ERR_INVALID_ARG, f"out must be a contiguous buffer [{n_bags}, {dim}] on {device}")
-    if found is None:
-        found = torch.empty(n, dtype=torch.uint8, device=device)
-    elif found.dtype != torch.uint8 or found.device != device or found.numel() != n or not found.is_contiguous():
-        raise MeepoError(_lib.ERR_INVALID_ARG, f"found must be a contiguous uint8 buffer of {n} entries on {device}")
-    if argmax is not None:
+    n, _, _, out, _, found = _pooled_args(k, device, out, (n_bags, dim), out_dtype, found)
+    if argmax is not None or with_argmax:
         argmax = _argmax_buffer(argmax, n_bags, dim, device)
-    elif with_argmax:
-        argmax = torch.empty((n_bags, dim), dtype=torch.uint32, device=device)
-    check(fn(handle, k.data_ptr(), n, bag_offsets.data_ptr(), bags_arg, out.data_ptr(), dt, found.data_ptr(), argmax.data_ptr() if argmax is not None else None,
-             _stream_ptr(device)))
+    check(fn(handle, k.data_ptr(), n, bag_offsets.data_ptr(), bags_arg, out.data_ptr(), dt, found.data_ptr(), _ptr(argmax), _stream_ptr(device)))
     return out, found, argmax
 
 
@@ -165,10 +203,7 @@ def _pooled_max_backward(fn, handle, device: torch.device, dim: int, bag_offsets
     if bag_grads.dtype != torch.float32 or bag_grads.device != device or bag_grads.numel() != n_bags * dim:
         raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_grads must be float32 [{n_bags}, {dim}] on {device}")
     g = bag_grads.contiguous()
-    if grads is None:
-        grads = torch.empty((n, dim), dtype=torch.float32, device=device)
-    elif grads.dtype != torch.float32 or grads.device != device or grads.numel() != n * dim or not grads.is_contiguous():
-        raise MeepoError(_lib.ERR_INVALID_ARG, f"grads must be a contiguous float32 buffer [{n}, {dim}] on {device}")
+    grads = _buffer(grads, "grads", torch.float32, (n, dim), device)
     check(fn(handle, n, bag_offsets.data_ptr(), bags_arg, a.data_ptr(), g.data_ptr(), grads.data_ptr(), _stream_ptr(device)))
     return grads
 
@@ -217,10 +252,10 @@ def _find_padded_composed(find_kept, dim: int, keys: torch.Tensor, bag_offsets: 
         raise ValueError(f"max_len must be at least 1 (got {max_len})")
     flat = keys.contiguous().view(-1)
     n, n_bags, device = flat.numel(), _n_bags(bag_offsets, flat.device), flat.device
-    if out is not None and (out.device != device or out.numel() != n_bags * max_len * dim or not out.is_contiguous()):
-        raise MeepoError(_lib.ERR_INVALID_ARG, f"out must be a contiguous buffer [{n_bags}, {max_len}, {dim}] on {device}")
-    if found is not None and (found.dtype != torch.uint8 or found.device != device or found.numel() != n or not found.is_contiguous()):
-        raise MeepoError(_lib.ERR_INVALID_ARG, f"found must be a contiguous uint8 buffer of {n} entries on {device}")
+    if out is not None:
+        _buffer(out, "out", out_dtype, (n_bags, max_len, dim), device)
+    if found is not None:
+        _buffer(found, "found", torch.uint8, n, device)
     lengths, step_keys, grad_index, pos = _padded_places(flat, bag_offsets, max_len, keep == "last")
     block = torch.zeros((n_bags * max_len, dim), dtype=out_dtype, device=device)
     fnd = torch.zeros(n, dtype=torch.uint8, device=device) if found is None else found.view(-1)
@@ -406,6 +441,14 @@ class LookupTable:
     def _s(self) -> int:
         return _stream_ptr(self.device)
 
+    def _bag_keys(self, keys: torch.Tensor) -> torch.Tensor:
+        """_keys for the operators that take a jagged batch, which may be empty (and then of any dtype)"""
+        return self._keys(keys) if keys.numel() else keys
+
+    def _rows_found(self, out, found, n: int, out_dtype: torch.dtype = torch.float32):
+        """the two result buffers of a lookup that returns a row per key"""
+        return _buffer(out, "out", out_dtype, (n, self.dim), self.device), _buffer(found, "found", torch.uint8, n, self.device)
+
     def _in_rows(self, rows: torch.Tensor, n: int):
         """the rows of insert / assign -> (contiguous tensor, MEE_DTYPE_* of its elements).  fp32 always; bf16 for a bf16-row table, which stores them verbatim."""
         if rows.dtype == torch.bfloat16 and self.value_dtype == torch.bfloat16:
@@ -433,19 +476,17 @@ class LookupTable:
             raise ValueError("find(unordered=True) has no bf16 form: mee_find_unordered returns fp32 rows")
         k = self._keys(keys)
         n = k.numel()
-        if out is None:
-            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
-        if found is None and want_found:
-            found = torch.empty(n, dtype=torch.uint8, device=self.device)
+        out = _buffer(out, "out", out_dtype, (n, self.dim), self.device)
+        if found is not None or want_found:
+            found = _buffer(found, "found", torch.uint8, n, self.device)
         if dt != _lib.DTYPE_F32:
-            check(_lib.lib().mee_find_as(self._h, k.data_ptr(), n, out.data_ptr(), dt, found.data_ptr() if found is not None else None,
-                                         int(flags or 0), self._s()))
+            check(_lib.lib().mee_find_as(self._h, k.data_ptr(), n, out.data_ptr(), dt, _ptr(found), int(flags or 0), self._s()))
             return out, found
         if flags is not None:
-            check(_lib.lib().mee_find_ex(self._h, k.data_ptr(), n, out.data_ptr(), found.data_ptr() if found is not None else None, int(flags), self._s()))
+            check(_lib.lib().mee_find_ex(self._h, k.data_ptr(), n, out.data_ptr(), _ptr(found), int(flags), self._s()))
             return out, found
         fn = _lib.lib().mee_find_unordered if unordered else _lib.lib().mee_find
-        check(fn(self._h, k.data_ptr(), n, out.data_ptr(), found.data_ptr() if found is not None else None, self._s()))
+        check(fn(self._h, k.data_ptr(), n, out.data_ptr(), _ptr(found), self._s()))
         return out, found
 
     def find_many(self, requests):
@@ -457,10 +498,7 @@ class LookupTable:
             _fp32_only(out, "find_many")
             k = self._keys(keys)
             n = k.numel()
-            if out is None:
-                out = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
-            if found is None:
-                found = torch.empty(n, dtype=torch.uint8, device=self.device)
+            out, found = self._rows_found(out, found, n)
             reqs[q] = _lib.FindRequest(k.data_ptr(), n, out.data_ptr(), found.data_ptr())
             res.append((out, found, k))   # k: keeps a contiguous copy alive until the launch is enqueued
         check(_lib.lib().mee_find_many(self._h, reqs, len(requests), self._s()))
@@ -488,31 +526,20 @@ class LookupTable:
         if mode == "max":
             _max_mode_only(weights=weights, located=located)
             return self.find_pooled_max(keys, bag_offsets, out=out, found=found, out_dtype=out_dtype)[:2]
-        dt = _out_dtype(out_dtype, out)
-        k = self._keys(keys) if keys.numel() else keys
+        dt, m = _out_dtype(out_dtype, out), _pool_mode(mode, ValueError)
+        k = self._bag_keys(keys)
         n_bags = self._bag_offsets(bag_offsets)
-        if weights is not None:
-            w = _check_weights(weights, mode, k.numel(), self.device)
-        elif located is not None:
+        if weights is None and located is not None:
             raise ValueError("find_pooled(located=...) is the weighted form's output: pass weights (all ones for a plain sum)")
-        if located is not None and (located.dtype != torch.int64 or located.device != self.device or located.numel() != k.numel()
-                                    or not located.is_contiguous()):
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"located must be a contiguous int64 buffer of {k.numel()} entries on {self.device}")
-        if out is None:
-            out = torch.empty((n_bags, self.dim), dtype=out_dtype, device=self.device)
-        if found is None:
-            found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
+        n, w, located, out, _, found = _pooled_args(k, self.device, out, (n_bags, self.dim), out_dtype, found, weights, mode, located)
         if dt != _lib.DTYPE_F32:
-            check(_lib.lib().mee_find_pooled_as(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), n_bags, w.data_ptr() if weights is not None else None,
-                                                out.data_ptr(), dt, found.data_ptr(), located.data_ptr() if located is not None else None,
-                                                {"sum": 0, "mean": 1}[mode], self._s()))
-            return out, found
-        if weights is not None:
-            check(_lib.lib().mee_find_pooled_weighted(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), n_bags, w.data_ptr(), out.data_ptr(),
-                                                      found.data_ptr(), located.data_ptr() if located is not None else None, self._s()))
-            return out, found
-        check(_lib.lib().mee_find_pooled(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), n_bags, out.data_ptr(), found.data_ptr(),
-                                         {"sum": 0, "mean": 1}[mode], self._s()))
+            check(_lib.lib().mee_find_pooled_as(self._h, k.data_ptr(), n, bag_offsets.data_ptr(), n_bags, _ptr(w), out.data_ptr(), dt, found.data_ptr(),
+                                                _ptr(located), m, self._s()))
+        elif w is not None:
+            check(_lib.lib().mee_find_pooled_weighted(self._h, k.data_ptr(), n, bag_offsets.data_ptr(), n_bags, w.data_ptr(), out.data_ptr(), found.data_ptr(),
+                                                      _ptr(located), self._s()))
+        else:
+            check(_lib.lib().mee_find_pooled(self._h, k.data_ptr(), n, bag_offsets.data_ptr(), n_bags, out.data_ptr(), found.data_ptr(), m, self._s()))
         return out, found
 
     def find_pooled_max(self, keys: torch.Tensor, bag_offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
@@ -522,7 +549,7 @@ class LookupTable:
         replaces the running one only where it is greater, so ties go to the first position and a NaN counts only at the bag's first position — copied bit
         for bit; argmax[b, j] (with_argmax=True, or a buffer passed as argmax) is the batch position it came from.  An empty bag: +0.0 and 0xFFFFFFFF.
         out_dtype=torch.bfloat16: the maximum, decided in fp32, is rounded once.  fp32-row tables only."""
-        k = self._keys(keys) if keys.numel() else keys
+        k = self._bag_keys(keys)
         n_bags = self._bag_offsets(bag_offsets)
         return _find_pooled_max(_lib.lib().mee_find_pooled_max, self._h, self.device, self.dim, k, bag_offsets, n_bags, n_bags, out, found, argmax, out_dtype,
                                 with_argmax)
@@ -542,7 +569,7 @@ class LookupTable:
         (found 0).  Every element of `out` is written, in one launch, with no [n, dim] array in between.
         with_step=True also returns (step_keys int64 [n], grad_index int32 [n]): the table step of the lookup is
         apply_*(step_keys, dense_grad.view(n_bags * max_len, dim), grad_index=grad_index) — cut-off keys are EMPTY there and take no step."""
-        k = self._keys(keys) if keys.numel() else keys
+        k = self._bag_keys(keys)
         n_bags = self._bag_offsets(bag_offsets)
         return _find_padded(_lib.lib().mee_find_padded_as, self._h, self.device, self.dim, k, bag_offsets, n_bags, n_bags, max_len, keep, out, found,
                             out_dtype, with_step)
@@ -554,24 +581,28 @@ class LookupTable:
         weight_grads [n] = <bag_grads[bag(i)], row_i> or None).  The table step is then apply_*(keys, grads[, slots=located]) — for bags
         that partition [0, n): positions no bag covers get no grads (nor handles from the forward).
         located = the handles find_pooled(weights=..., located=...) of this step wrote (the rows are read through them)."""
-        k = self._keys(keys) if keys.numel() else keys
+        k = self._bag_keys(keys)
         n_bags = self._bag_offsets(bag_offsets)
         w = _check_weights(weights, "sum", k.numel(), self.device)
         g = self._rows(bag_grads, n_bags)
         loc = self._slots(located, k.numel()) if located is not None else None
-        if grads is None:
-            grads = torch.empty((k.numel(), self.dim), dtype=torch.float32, device=self.device)
-        if weight_grads is None and want_weight_grads:
-            weight_grads = torch.empty(k.numel(), dtype=torch.float32, device=self.device)
-        check(_lib.lib().mee_pooled_weighted_backward(self._h, k.data_ptr(), loc.data_ptr() if loc is not None else None, k.numel(),
-                                                      bag_offsets.data_ptr(), n_bags, w.data_ptr(), g.data_ptr(), grads.data_ptr(),
-                                                      weight_grads.data_ptr() if weight_grads is not None else None, self._s()))
+        grads, weight_grads = self._weighted_grads(grads, weight_grads, want_weight_grads, k.numel())
+        check(_lib.lib().mee_pooled_weighted_backward(self._h, k.data_ptr(), _ptr(loc), k.numel(), bag_offsets.data_ptr(), n_bags, w.data_ptr(), g.data_ptr(),
+                                                      grads.data_ptr(), _ptr(weight_grads), self._s()))
+        return grads, weight_grads
+
+    def _weighted_grads(self, grads, weight_grads, want_weight_grads: bool, n: int):
+        """the two result buffers of pooled_weighted_backward (a table's and a group's)"""
+        grads = _buffer(grads, "grads", torch.float32, (n, self.dim), self.device)
+        if weight_grads is not None or want_weight_grads:
+            weight_grads = _buffer(weight_grads, "weight_grads", torch.float32, n, self.device)
         return grads, weight_grads
 
     def find_missing(self, keys: torch.Tensor, out: torch.Tensor, found: torch.Tensor) -> None:
         """Second-tier pass: fill the positions an earlier find (on another table) left with found == 0."""
         _fp32_only(out, "find_missing")
         k = self._keys(keys)
+        out, found = self._rows_found(out, found, k.numel())
         check(_lib.lib().mee_find_missing(self._h, k.data_ptr(), k.numel(), out.data_ptr(), found.data_ptr(), self._s()))
 
     def find_counted(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
@@ -580,10 +611,7 @@ class LookupTable:
         _fp32_only(out, "find_counted")
         k = self._keys(keys)
         n = k.numel()
-        if out is None:
-            out = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
-        if found is None:
-            found = torch.empty(n, dtype=torch.uint8, device=self.device)
+        out, found = self._rows_found(out, found, n)
         check(_lib.lib().mee_find_counted(self._h, k.data_ptr(), n, out.data_ptr(), found.data_ptr(), int(missing_only), self._s()))
         return out, found
 
@@ -607,12 +635,14 @@ class LookupTable:
         """insert restricted to the positions with found == 0 (tiered pairs: keys found in neither table)."""
         k = self._keys(keys)
         v = self._rows(values, k.numel())
+        found = _buffer(found, "found", torch.uint8, k.numel(), self.device)
         check(_lib.lib().mee_insert_missing(self._h, k.data_ptr(), v.data_ptr(), k.numel(), found.data_ptr(), self._s()))
 
     def find_or_insert_missing(self, keys: torch.Tensor, out: torch.Tensor, found: torch.Tensor) -> None:
         """find_or_insert restricted to the positions with found == 0; rows of those positions are written into out."""
         _fp32_only(out, "find_or_insert_missing")
         k = self._keys(keys)
+        out, found = self._rows_found(out, found, k.numel())
         check(_lib.lib().mee_find_or_insert_missing(self._h, k.data_ptr(), k.numel(), out.data_ptr(), found.data_ptr(), self._s()))
 
     def assign(self, keys: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
@@ -676,10 +706,7 @@ class LookupTable:
             raise ValueError("find_or_insert(min_count=...) has no bf16 form: mee_find_or_insert_admit returns fp32 rows")
         k = self._keys(keys)
         n = k.numel()
-        if out is None:
-            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
-        if found is None:
-            found = torch.empty(n, dtype=torch.uint8, device=self.device)
+        out, found = self._rows_found(out, found, n, out_dtype)
         if dt != _lib.DTYPE_F32:
             check(_lib.lib().mee_find_or_insert_as(self._h, k.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(), self._s()))
         elif min_count is not None:
@@ -700,12 +727,9 @@ class LookupTable:
         dt = _out_dtype(out_dtype, out)
         k = self._keys(keys)
         n = k.numel()
-        if out is None:
-            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
-        if found is None:
-            found = torch.empty(n, dtype=torch.uint8, device=self.device)
-        if slots is None:
-            slots = torch.empty(n, dtype=torch.int64, device=self.device)
+        out = _buffer(out, "out", out_dtype, (n, self.dim), self.device)   # (spelled out: this is the training step's forward)
+        found = _buffer(found, "found", torch.uint8, n, self.device)
+        slots = _buffer(slots, "slots", torch.int64, n, self.device)
         if dt != _lib.DTYPE_F32:
             check(getattr(_lib.lib(), fn + "_as")(self._h, k.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(), slots.data_ptr(), self._s()))
         else:
@@ -1083,7 +1107,7 @@ class TableGroup:
         if not isinstance(dst_group, TableGroup):
             raise MeepoError(_lib.ERR_INVALID_ARG, "move_to: dst_group must be a TableGroup")
         self._check_offsets(offsets)
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        k = self.tables[0]._bag_keys(keys)
         n, nt = k.numel(), len(self.tables)
         limits = None
         if max_moves is not None:
@@ -1115,7 +1139,7 @@ class TableGroup:
         """the three forms of the grouped step: a gradient row per position over member segments (`offsets` = the n_tables + 1 bounds), indexed rows
         over member segments, or a pooled lookup's backward (`offsets` = its bag_offsets, index = the bag of every position)"""
         bpt = self._check_bags(offsets) if pooled else self._check_offsets(offsets)
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        k = self.tables[0]._bag_keys(keys)
         n, s = k.numel(), _stream_ptr(self.device)
         if index is None:
             g = self.tables[0]._rows(grads, n)
@@ -1133,11 +1157,7 @@ class TableGroup:
 
     # -- the embedding-bag collection: bags_per_table bags per member, bag b belongs to member b // bags_per_table ---------
     def _check_bags(self, bag_offsets: torch.Tensor) -> int:
-        nb = bag_offsets.numel() - 1
-        if bag_offsets.device != self.device or bag_offsets.dtype not in (torch.int64, torch.uint64) or not bag_offsets.is_contiguous() \
-                or nb < 0 or nb % len(self.tables):
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_offsets must be contiguous int64 on {self.device} with n_tables * bags_per_table + 1 entries")
-        return nb // len(self.tables)
+        return _check_bags(bag_offsets, len(self.tables), self.device)
 
     def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
                     found: torch.Tensor | None = None, located: torch.Tensor | None = None, weights: torch.Tensor | None = None,
@@ -1157,40 +1177,25 @@ class TableGroup:
         keyed = _check_layout(layout)
         dt = _out_dtype(out_dtype, None if keyed else out)
         bpt = self._check_bags(bag_offsets)
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
-        if keyed:
-            if weights is not None:
-                raise ValueError("layout='keyed' has no weighted form (per-sample weights): use the table-major lookup")
-            if mode not in ("sum", "mean"):
-                raise MeepoError(_lib.ERR_INVALID_ARG, f"mode must be 'sum' or 'mean' (got {mode!r})")
-            out, stride = _keyed_out(out, bpt, len(self.tables) * self.dim, out_dtype, self.device)
-            if found is None:
-                found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
-            check(_lib.lib().mee_group_find_pooled_keyed(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, stride, found.data_ptr(),
-                                                         located.data_ptr() if located is not None else None, _step_index(step_index, k.numel(), self.device),
-                                                         {"sum": 0, "mean": 1}[mode], _stream_ptr(self.device)))
-            return out, found
-        if step_index is not None:
+        k = self.tables[0]._bag_keys(keys)
+        if keyed and weights is not None:
+            raise ValueError("layout='keyed' has no weighted form (per-sample weights): use the table-major lookup")
+        if step_index is not None and not keyed:
             raise ValueError("step_index is the keyed layout's (layout='keyed'): the table-major step takes the bag of every position")
-        if out is None:
-            out = torch.empty((bpt * len(self.tables), self.dim), dtype=out_dtype, device=self.device)
-        if found is None:
-            found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
-        if dt != _lib.DTYPE_F32:   # mee_group_find_pooled_as: the finished bag rows rounded once to bf16
-            w = _check_weights(weights, mode, k.numel(), self.device) if weights is not None else None
-            check(_lib.lib().mee_group_find_pooled_as(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), bpt, w.data_ptr() if w is not None else None,
-                                                      out.data_ptr(), dt, found.data_ptr(), located.data_ptr() if located is not None else None,
-                                                      {"sum": 0, "mean": 1}[mode], _stream_ptr(self.device)))
-            return out, found
-        if weights is not None:
-            w = _check_weights(weights, mode, k.numel(), self.device)
-            check(_lib.lib().mee_group_find_pooled_weighted(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), bpt, w.data_ptr(), out.data_ptr(),
-                                                            found.data_ptr(), located.data_ptr() if located is not None else None,
-                                                            _stream_ptr(self.device)))
-            return out, found
-        check(_lib.lib().mee_group_find_pooled(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), bpt, out.data_ptr(), found.data_ptr(),
-                                               located.data_ptr() if located is not None else None,
-                                               {"sum": 0, "mean": 1}[mode], _stream_ptr(self.device)))
+        m, nt, s = _pool_mode(mode), len(self.tables), _stream_ptr(self.device)
+        n, w, located, out, stride, found = _pooled_args(k, self.device, out, (bpt, nt * self.dim) if keyed else (bpt * nt, self.dim), out_dtype, found, weights,
+                                                         mode, located, keyed)
+        if keyed:
+            check(_lib.lib().mee_group_find_pooled_keyed(self._h, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, stride, found.data_ptr(),
+                                                         _ptr(located), _step_index(step_index, n, self.device), m, s))
+        elif dt != _lib.DTYPE_F32:   # mee_group_find_pooled_as: the finished bag rows rounded once to bf16
+            check(_lib.lib().mee_group_find_pooled_as(self._h, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, _ptr(w), out.data_ptr(), dt, found.data_ptr(),
+                                                      _ptr(located), m, s))
+        elif w is not None:
+            check(_lib.lib().mee_group_find_pooled_weighted(self._h, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, w.data_ptr(), out.data_ptr(), found.data_ptr(),
+                                                            _ptr(located), s))
+        else:
+            check(_lib.lib().mee_group_find_pooled(self._h, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), found.data_ptr(), _ptr(located), m, s))
         return out, found
 
     def find_pooled_max(self, keys: torch.Tensor, bag_offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
@@ -1198,7 +1203,7 @@ class TableGroup:
         """LookupTable.find_pooled_max of every member on its bags_per_table bags, in one launch (mee_group_find_pooled_max) -> (out [n_tables *
         bags_per_table, dim], per-key found mask, argmax | None).  Every member uses its own default row; argmax holds positions in the whole batch."""
         bpt = self._check_bags(bag_offsets)
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        k = self.tables[0]._bag_keys(keys)
         return _find_pooled_max(_lib.lib().mee_group_find_pooled_max, self._h, self.device, self.dim, k, bag_offsets, bpt * len(self.tables), bpt, out, found,
                                 argmax, out_dtype, with_argmax)
 
@@ -1215,7 +1220,7 @@ class TableGroup:
         (out [n_tables * bags_per_table, max_len, dim], per-key found mask, lengths) and, with_step=True, (step_keys, grad_index): the step is
         apply_indexed(step_keys, bag_offsets[::bags_per_table].contiguous(), dense_grad.view(-1, dim), grad_index, ...)."""
         bpt = self._check_bags(bag_offsets)
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        k = self.tables[0]._bag_keys(keys)
         return _find_padded(_lib.lib().mee_group_find_padded_as, self._h, self.device, self.dim, k, bag_offsets, bpt * len(self.tables), bpt, max_len, keep, out,
                             found, out_dtype, with_step)
 
@@ -1238,28 +1243,12 @@ class TableGroup:
         device; members may have no bags; bags outside the map are empty) -> ([n_bags, dim] fp32, per-key found mask).  Sync-free."""
         _fp32_only(out, "find_pooled_jagged")
         self._check_offsets(member_bags)
-        nb = bag_offsets.numel() - 1
-        if bag_offsets.device != self.device or bag_offsets.dtype not in (torch.int64, torch.uint64) or not bag_offsets.is_contiguous() or nb < 0:
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_offsets must be contiguous int64 on {self.device} with n_bags + 1 entries")
-        if mode not in ("sum", "mean"):
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"mode must be 'sum' or 'mean' (got {mode!r})")
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
-        if out is None:
-            out = torch.empty((nb, self.dim), dtype=torch.float32, device=self.device)
-        elif out.dtype != torch.float32 or out.device != self.device or out.numel() != nb * self.dim or not out.is_contiguous():
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"out must be a contiguous float32 buffer [{nb}, {self.dim}] on {self.device}")
-        if found is None:
-            found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
-        elif found.dtype != torch.uint8 or found.device != self.device or found.numel() != k.numel() or not found.is_contiguous():
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"found must be a contiguous uint8 buffer of {k.numel()} entries on {self.device}")
-        if located is not None and (located.dtype != torch.int64 or located.device != self.device or located.numel() != k.numel()
-                                    or not located.is_contiguous()):
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"located must be a contiguous int64 buffer of {k.numel()} entries on {self.device}")
-        if k.numel() and nb == 0:
-            raise MeepoError(_lib.ERR_INVALID_ARG, "there are keys but no bags: no bag would report them")
-        check(_lib.lib().mee_group_find_pooled_jagged(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), nb, member_bags.data_ptr(), out.data_ptr(),
-                                                      found.data_ptr(), located.data_ptr() if located is not None else None,
-                                                      {"sum": 0, "mean": 1}[mode], _stream_ptr(self.device)))
+        nb, m = _n_bags(bag_offsets, self.device), _pool_mode(mode)
+        k = self.tables[0]._bag_keys(keys)
+        _no_bags_for_keys(k.numel(), nb)
+        n, _, located, out, _, found = _pooled_args(k, self.device, out, (nb, self.dim), torch.float32, found, located=located)
+        check(_lib.lib().mee_group_find_pooled_jagged(self._h, k.data_ptr(), n, bag_offsets.data_ptr(), nb, member_bags.data_ptr(), out.data_ptr(),
+                                                      found.data_ptr(), _ptr(located), m, _stream_ptr(self.device)))
         return out, found
 
     def apply_indexed(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, grad_index: torch.Tensor, optimizer: str, lr: float,
@@ -1274,17 +1263,13 @@ class TableGroup:
         """LookupTable.pooled_weighted_backward per member, in one launch -> (grads [n, dim], weight_grads [n] or None).  The step is
         then apply_adagrad / apply_adam(keys, bag_offsets[::bags_per_table].contiguous(), grads): the grads are per position."""
         bpt = self._check_bags(bag_offsets)
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        k = self.tables[0]._bag_keys(keys)
         w = _check_weights(weights, "sum", k.numel(), self.device)
         g = self.tables[0]._rows(bag_grads, bpt * len(self.tables))
         loc = self.tables[0]._slots(located, k.numel()) if located is not None else None
-        if grads is None:
-            grads = torch.empty((k.numel(), self.dim), dtype=torch.float32, device=self.device)
-        if weight_grads is None and want_weight_grads:
-            weight_grads = torch.empty(k.numel(), dtype=torch.float32, device=self.device)
-        check(_lib.lib().mee_group_pooled_weighted_backward(self._h, k.data_ptr(), loc.data_ptr() if loc is not None else None, k.numel(),
-                                                            bag_offsets.data_ptr(), bpt, w.data_ptr(), g.data_ptr(), grads.data_ptr(),
-                                                            weight_grads.data_ptr() if weight_grads is not None else None, _stream_ptr(self.device)))
+        grads, weight_grads = self.tables[0]._weighted_grads(grads, weight_grads, want_weight_grads, k.numel())
+        check(_lib.lib().mee_group_pooled_weighted_backward(self._h, k.data_ptr(), _ptr(loc), k.numel(), bag_offsets.data_ptr(), bpt, w.data_ptr(), g.data_ptr(),
+                                                            grads.data_ptr(), _ptr(weight_grads), _stream_ptr(self.device)))
         return grads, weight_grads
 
     def find_or_insert(self, keys: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
@@ -1298,13 +1283,10 @@ class TableGroup:
             return self.find(keys, offsets, out, found, _fn="mee_group_find_or_insert", out_dtype=out_dtype)
         scalar, per_member = self._min_counts(min_count)
         dt = _out_dtype(out_dtype, out)
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        k = self.tables[0]._bag_keys(keys)
         n = k.numel()
         self._check_offsets(offsets)
-        if out is None:
-            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
-        if found is None:
-            found = torch.empty(n, dtype=torch.uint8, device=self.device)
+        out, found = self.tables[0]._rows_found(out, found, n, out_dtype)
         check(_lib.lib().mee_group_find_or_insert_admit(self._h, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(), scalar,
                                                         per_member.data_ptr() if per_member is not None else None, _stream_ptr(self.device)))
         return out, found
@@ -1337,13 +1319,10 @@ class TableGroup:
              _fn: str = "mee_find_grouped", out_dtype: torch.dtype = torch.float32):
         """out_dtype=torch.bfloat16 (mee_find_grouped_as / mee_group_find_or_insert_as): LookupTable.find(out_dtype=...) per member."""
         dt = _out_dtype(out_dtype, out)
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        k = self.tables[0]._bag_keys(keys)
         n = k.numel()
         self._check_offsets(offsets)
-        if out is None:
-            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
-        if found is None:
-            found = torch.empty(n, dtype=torch.uint8, device=self.device)
+        out, found = self.tables[0]._rows_found(out, found, n, out_dtype)
         if dt != _lib.DTYPE_F32:
             check(getattr(_lib.lib(), _fn + "_as")(self._h, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(),
                                                    _stream_ptr(self.device)))
@@ -1433,18 +1412,7 @@ class MixedTableGroup:
         return [flat[o:o + bags_per_table * d].view(bags_per_table, d) for o, d in zip(offs, self.dims)]
 
     def _check_bags(self, bag_offsets: torch.Tensor) -> int:
-        nb = bag_offsets.numel() - 1
-        if bag_offsets.device != self.device or bag_offsets.dtype not in (torch.int64, torch.uint64) or not bag_offsets.is_contiguous() \
-                or nb < 0 or nb % len(self.tables):
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_offsets must be contiguous int64 on {self.device} with n_tables * bags_per_table + 1 entries")
-        return nb // len(self.tables)
-
-    def _buffer(self, t: torch.Tensor | None, name: str, dtype: torch.dtype, numel: int) -> torch.Tensor:
-        if t is None:
-            return torch.empty(numel, dtype=dtype, device=self.device)
-        if t.dtype != dtype or t.device != self.device or t.numel() != numel or not t.is_contiguous():
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"{name} must be a contiguous {dtype} buffer of {numel} elements on {self.device}")
-        return t
+        return _check_bags(bag_offsets, len(self.tables), self.device)
 
     def find_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, mode: str = "sum", out: torch.Tensor | None = None,
                     found: torch.Tensor | None = None, located: torch.Tensor | None = None, weights: torch.Tensor | None = None,
@@ -1460,32 +1428,21 @@ class MixedTableGroup:
         keyed = _check_layout(layout)
         if weights is not None:
             raise ValueError("a mixed group has no weighted bags (per_sample_weights): use one TableGroup per width")
-        if mode not in ("sum", "mean"):
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"mode must be 'sum' or 'mean' (got {mode!r})")
+        m = _pool_mode(mode)
         if step_index is not None and not keyed:
             raise ValueError("step_index is the keyed layout's (layout='keyed')")
         dt = _out_dtype(out_dtype, None if keyed else out)
         bpt = self._check_bags(bag_offsets)
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
-        if k.numel() and bpt == 0:
-            raise MeepoError(_lib.ERR_INVALID_ARG, "there are keys but no bags: no bag would report them")
+        k = self.tables[0]._bag_keys(keys)
+        _no_bags_for_keys(k.numel(), bpt)
+        n, _, located, out, stride, found = _pooled_args(k, self.device, out, (bpt, sum(self.dims)) if keyed else mixed_layout(self.dims, bpt)[2], out_dtype, found,
+                                                         located=located, keyed=keyed)
         if keyed:
-            out, stride = _keyed_out(out, bpt, sum(self.dims), out_dtype, self.device)
-            found = self._buffer(found, "found", torch.uint8, k.numel())
-            if located is not None:
-                located = self._buffer(located, "located", torch.int64, k.numel())
-            check(_lib.lib().mee_mixed_group_find_pooled_keyed(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, stride,
-                                                               found.data_ptr(), located.data_ptr() if located is not None else None,
-                                                               _step_index(step_index, k.numel(), self.device), {"sum": 0, "mean": 1}[mode],
-                                                               int(bool(insert_missing)), _stream_ptr(self.device)))
+            check(_lib.lib().mee_mixed_group_find_pooled_keyed(self._h, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, stride, found.data_ptr(),
+                                                               _ptr(located), _step_index(step_index, n, self.device), m, int(bool(insert_missing)),
+                                                               _stream_ptr(self.device)))
             return out, found
-        total = mixed_layout(self.dims, bpt)[2]
-        out = self._buffer(out, "out", out_dtype, total)
-        found = self._buffer(found, "found", torch.uint8, k.numel())
-        if located is not None:
-            located = self._buffer(located, "located", torch.int64, k.numel())
-        check(_lib.lib().mee_mixed_group_find_pooled(self._h, k.data_ptr(), k.numel(), bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, found.data_ptr(),
-                                                     located.data_ptr() if located is not None else None, {"sum": 0, "mean": 1}[mode],
+        check(_lib.lib().mee_mixed_group_find_pooled(self._h, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, found.data_ptr(), _ptr(located), m,
                                                      int(bool(insert_missing)), _stream_ptr(self.device)))
         return self.views(out.view(-1), bpt), found
 
@@ -1501,7 +1458,7 @@ class MixedTableGroup:
         step = SparseStep.of(optimizer, lr, eps, beta1, beta2, step, l1=l1, l2=l2)   # ("ftrl": eps is beta, l1 / l2 the regularisation strengths)
         keyed = _check_layout(layout)
         bpt = self._check_bags(bag_offsets)
-        k = self.tables[0]._keys(keys) if keys.numel() else keys
+        k = self.tables[0]._bag_keys(keys)
         gi = self.tables[0]._grad_index(bag_of_position, k.numel())
         total = mixed_layout(self.dims, bpt)[2]
         if keyed:
@@ -1519,11 +1476,11 @@ class MixedTableGroup:
             bag_grads = self._step_grads[:total]
         elif mean_offsets is not None:
             raise ValueError("mean_offsets is the keyed layout's (layout='keyed')")
-        g = self._buffer(bag_grads.contiguous(), "bag_grads", torch.float32, total)
+        g = _buffer(bag_grads.contiguous(), "bag_grads", torch.float32, total, self.device)
         if located is not None:
-            located = self._buffer(located, "located", torch.int64, k.numel())
-        step.launch("mee_mixed_group_apply", "_pooled", self._h, k.data_ptr(), bag_offsets.data_ptr(), bpt, g.data_ptr(), gi.data_ptr(),
-                    located.data_ptr() if located is not None else None, k.numel(), stream=_stream_ptr(self.device))
+            located = _buffer(located, "located", torch.int64, k.numel(), self.device)
+        step.launch("mee_mixed_group_apply", "_pooled", self._h, k.data_ptr(), bag_offsets.data_ptr(), bpt, g.data_ptr(), gi.data_ptr(), _ptr(located), k.numel(),
+                    stream=_stream_ptr(self.device))
 
 
 def hash_batch(keys: torch.Tensor, n_buckets: int, n_shards: int):
@@ -1626,15 +1583,14 @@ class Router:
                          mode: str = "sum", out: torch.Tensor | None = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
         """out[b] = the owners' partial rows of bag b added up in rank order (mee_combine_bag_runs), mean then divided by the bag length,
         bf16 then rounded once.  partials [R, dim] fp32 in the run order of bag_runs."""
-        dt = _out_dtype(out_dtype, out)
+        dt, m = _out_dtype(out_dtype, out), _pool_mode(mode, ValueError)
         n_bags = _n_bags(bag_offsets, self.device)
         p = partials.contiguous()
         if p.dtype != torch.float32 or p.dim() != 2:
             raise MeepoError(_lib.ERR_INVALID_ARG, "partials must be float32 [n_runs, dim]")
-        if out is None:
-            out = torch.empty((n_bags, p.shape[1]), dtype=out_dtype, device=self.device)
+        out = _buffer(out, "out", out_dtype, (n_bags, p.shape[1]), self.device)
         check(_lib.lib().mee_combine_bag_runs(self._h, p.data_ptr(), run_bag.data_ptr(), run_counts.data_ptr(), p.shape[0], bag_offsets.data_ptr(),
-                                              n_bags, p.shape[1], {"sum": 0, "mean": 1}[mode], out.data_ptr(), dt, _stream_ptr(self.device)))
+                                              n_bags, p.shape[1], m, out.data_ptr(), dt, _stream_ptr(self.device)))
         return out
 
     # -- table groups over sharded tables (SPEC.md §5 "Groups") ------------------------------------------------------------

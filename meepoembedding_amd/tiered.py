@@ -32,7 +32,7 @@ from __future__ import annotations
 
 import torch
 
-from .table import SparseStep
+from .table import SparseStep, _pool_mode
 
 
 def _pool_rows(rows: torch.Tensor, bag_offsets: torch.Tensor, mode: str) -> torch.Tensor:
@@ -130,8 +130,7 @@ class TieredLookupTable:
         insert_missing: absent keys are created first, in the tier find_or_insert would pick; `found` stays "present before the call".
         min_count (with insert_missing): that creation admits as find_or_insert(min_count=) does; a key not yet admitted pools as the hot default row.
         out_dtype=torch.bfloat16: the finished bag row is rounded once."""
-        if mode not in ("sum", "mean"):
-            raise ValueError(f"mode must be 'sum' or 'mean' (got {mode!r})")
+        m = _pool_mode(mode, ValueError)
         if min_count is not None:
             if not insert_missing:
                 raise ValueError("min_count needs insert_missing=True (admission decides when an absent key is created)")
@@ -148,16 +147,12 @@ class TieredLookupTable:
                 found.copy_(fnd)
             return (out if out is not None else pooled), (found if found is not None else fnd)
         from . import _lib
-        from .table import _n_bags, _out_dtype
+        from .table import _n_bags, _out_dtype, _pooled_args
         hot, cold = self.hot, self.cold
         dt = _out_dtype(out_dtype, out)
-        k = hot._keys(keys) if keys.numel() else keys
-        n = k.numel()
+        k = hot._bag_keys(keys)
         n_bags = _n_bags(bag_offsets, hot.device)
-        if out is None:
-            out = torch.empty((n_bags, self.dim), dtype=out_dtype, device=hot.device)
-        if found is None:
-            found = torch.empty(n, dtype=torch.uint8, device=hot.device)
+        n, _, _, out, _, found = _pooled_args(k, hot.device, out, (n_bags, self.dim), out_dtype, found)
         if insert_missing and n:
             # the found mask alone, from a probe of both indexes (no row is read, nothing is written to a table) ...
             found.copy_(hot.locate(k)[1] | cold.locate(k)[1])
@@ -170,8 +165,7 @@ class TieredLookupTable:
             flags = _lib.TIER_COUNT_COLD | (_lib.TIER_COUNT_HOT if self._calls % self.sample_every == 0 else 0)
         # with insert_missing the launch writes no found bytes: `found` keeps meaning "present before the call", also for a key repeated in the batch
         _lib.check(_lib.lib().mee_find_pooled_tiered(hot._h, cold._h, k.data_ptr(), n, bag_offsets.data_ptr(), n_bags, out.data_ptr(), dt,
-                                                     None if (insert_missing and n) else found.data_ptr(), {"sum": 0, "mean": 1}[mode], flags,
-                                                     hot._s()))
+                                                     None if (insert_missing and n) else found.data_ptr(), m, flags, hot._s()))
         return out, found
 
     def find_padded(self, keys: torch.Tensor, bag_offsets: torch.Tensor, max_len: int, keep: str = "first", out: torch.Tensor | None = None,
@@ -188,7 +182,7 @@ class TieredLookupTable:
         from . import _lib
         from .table import _find_padded, _n_bags
         hot, cold = self.hot, self.cold
-        k = hot._keys(keys) if keys.numel() else keys
+        k = hot._bag_keys(keys)
         n_bags = _n_bags(bag_offsets, hot.device)
 
         def launch(h, *args):   # _find_padded's call with the cold table and the count bits put in: (hot, cold, ..., flags, count_flags, ...)
@@ -716,8 +710,7 @@ class TieredTableGroup:
         keyed = _check_layout(layout)
         if step_index is not None and not keyed:
             raise ValueError("step_index is the keyed layout's (layout='keyed')")
-        if mode not in ("sum", "mean"):
-            raise ValueError(f"mode must be 'sum' or 'mean' (got {mode!r})")
+        m = _pool_mode(mode, ValueError)
         if keyed and not self._native:   # the loop below, then one permute: what the launch writes directly over native pairs
             pooled, fnd = self.find_pooled(keys, bag_offsets, mode, None, found, insert_missing, out_dtype, min_count)
             nt, bpt = len(self.tables), pooled.shape[0] // len(self.tables)
@@ -752,46 +745,35 @@ class TieredTableGroup:
                 found.copy_(fnd)
             return (out if out is not None else pooled), (found if found is not None else fnd)
         from . import _lib
-        from .table import _keyed_out, _out_dtype, _step_index, _stream_ptr
+        from .table import _out_dtype, _pooled_args, _ptr, _step_index, _stream_ptr
         dt = _out_dtype(out_dtype, None if keyed else out)
         bpt = self.hot_group._check_bags(bag_offsets)
-        k = self.tables[0].hot._keys(keys) if keys.numel() else keys
-        n = k.numel()
-        if keyed:
-            out, stride = _keyed_out(out, bpt, len(self.tables) * self.dim, out_dtype, self.device)
-        elif out is None:
-            out = torch.empty((bpt * len(self.tables), self.dim), dtype=out_dtype, device=self.device)
-        if found is None:
-            found = torch.empty(n, dtype=torch.uint8, device=self.device)
-        L, s, m = _lib.lib(), _stream_ptr(self.device), {"sum": 0, "mean": 1}[mode]
+        k = self.tables[0].hot._bag_keys(keys)
+        rows = (bpt * len(self.tables), self.dim)
+        n, _, _, out, stride, found = _pooled_args(k, self.device, out, (bpt, len(self.tables) * self.dim) if keyed else rows, out_dtype, found, keyed=keyed)
+        index = _step_index(step_index, n, self.device)
+        L, s = _lib.lib(), _stream_ptr(self.device)
         hot, cold = self.hot_group._h, self.cold_group._h
         creates = bool(insert_missing and n and bpt)
-        if keyed:   # the found pass of a creating lookup writes no rows the caller sees: it goes to a scratch block, the keyed launch writes `out`
-            index = _step_index(step_index, n, self.device)
-            if creates:
-                scratch = torch.empty((bpt * len(self.tables), self.dim), dtype=out_dtype, device=self.device)
-                _lib.check(L.mee_group_find_pooled_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, scratch.data_ptr(), dt, found.data_ptr(), m, 0, s))
-                self._place_new_keys(n)
-                if admits is None:
-                    _lib.check(L.mee_group_ensure_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, found.data_ptr(), self._d_goes_cold.data_ptr(), s))
-                else:
-                    _lib.check(L.mee_group_ensure_admit_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, found.data_ptr(), self._d_goes_cold.data_ptr(),
-                                                               admits[0], admits[1].data_ptr() if admits[1] is not None else None, s))
-            _lib.check(L.mee_group_find_pooled_tiered_keyed(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, stride,
-                                                            None if creates else found.data_ptr(), index, m, self._count_flags(), s))
-            return out, found
-        if creates:
-            # the found mask of the whole batch first (no counters: this pass is not a lookup of the model's) ...
-            _lib.check(L.mee_group_find_pooled_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, found.data_ptr(), m, 0, s))
-            # ... then every member creates its absent keys in the tier its pair would pick
+
+        def create(block):
+            """the found mask of the whole batch first, its rows written to `block` (no counters: this pass is not a lookup of the model's), then
+            every member creates its absent keys in the tier its pair would pick — those that its hot sketch admits, with min_count"""
+            _lib.check(L.mee_group_find_pooled_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, block.data_ptr(), dt, found.data_ptr(), m, 0, s))
             self._place_new_keys(n)
             if admits is None:
                 _lib.check(L.mee_group_ensure_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, found.data_ptr(), self._d_goes_cold.data_ptr(), s))
-            else:   # ... those that its hot sketch admits
+            else:
                 _lib.check(L.mee_group_ensure_admit_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, found.data_ptr(), self._d_goes_cold.data_ptr(),
-                                                           admits[0], admits[1].data_ptr() if admits[1] is not None else None, s))
-        _lib.check(L.mee_group_find_pooled_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt,
-                                                  None if creates else found.data_ptr(), m, self._count_flags(), s))
+                                                           admits[0], _ptr(admits[1]), s))
+        if creates:   # (keyed: the found pass writes no rows the caller sees — they go to a scratch block, the keyed launch writes `out`)
+            create(torch.empty(rows, dtype=out_dtype, device=self.device) if keyed else out)
+        if keyed:
+            _lib.check(L.mee_group_find_pooled_tiered_keyed(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt, stride,
+                                                            None if creates else found.data_ptr(), index, m, self._count_flags(), s))
+        else:
+            _lib.check(L.mee_group_find_pooled_tiered(hot, cold, k.data_ptr(), n, bag_offsets.data_ptr(), bpt, out.data_ptr(), dt,
+                                                      None if creates else found.data_ptr(), m, self._count_flags(), s))
         return out, found
 
     # -- the unpooled collection: a row per position of the jagged batch (keys = the members' id batches concatenated, offsets = n_tables + 1 bounds) ----
@@ -831,13 +813,9 @@ class TieredTableGroup:
         from .table import _out_dtype
         dt = _out_dtype(out_dtype, out)
         self.hot_group._check_offsets(offsets)
-        k = self.tables[0].hot._keys(keys) if keys.numel() else keys
+        k = self.tables[0].hot._bag_keys(keys)
         n = k.numel()
-        if out is None:
-            out = torch.empty((n, self.dim), dtype=out_dtype, device=self.device)
-        if found is None:
-            found = torch.empty(n, dtype=torch.uint8, device=self.device)
-        return dt, k, n, out, found
+        return (dt, k, n, *self.tables[0].hot._rows_found(out, found, n, out_dtype))
 
     def find(self, keys: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
              out_dtype: torch.dtype = torch.float32):
@@ -879,7 +857,7 @@ class TieredTableGroup:
         from . import _lib
         from .table import _find_padded
         bpt = self.hot_group._check_bags(bag_offsets)
-        k = self.tables[0].hot._keys(keys) if keys.numel() else keys
+        k = self.tables[0].hot._bag_keys(keys)
         cold = self.cold_group._h
 
         def launch(h, *args):   # _find_padded's call with the cold group and the count bits put in: (hot, cold, ..., flags, count_flags, ...)
@@ -971,8 +949,7 @@ class TieredTableGroup:
         _fp32_only(out, "find_pooled_jagged")
         nb = bag_offsets.numel() - 1
         if not self._native:   # a loop over the pairs, member j on its bags (a host read of member_bags)
-            if mode not in ("sum", "mean"):
-                raise ValueError(f"mode must be 'sum' or 'mean' (got {mode!r})")
+            _pool_mode(mode, ValueError)
             if member_bags.dim() != 1 or member_bags.numel() != len(self.tables) + 1:
                 raise ValueError(f"member_bags must hold n_tables + 1 = {len(self.tables) + 1} entries (got {tuple(member_bags.shape)})")
             flat = keys.contiguous().view(-1)
@@ -997,28 +974,15 @@ class TieredTableGroup:
             if found is not None:
                 found.copy_(fnd)
             return (out if out is not None else pooled), (found if found is not None else fnd)
-        from ._lib import MeepoError
-        from .table import _stream_ptr
+        from .table import _n_bags, _no_bags_for_keys, _pooled_args, _stream_ptr
         self.hot_group._check_offsets(member_bags)
-        if bag_offsets.device != self.device or bag_offsets.dtype not in (torch.int64, torch.uint64) or not bag_offsets.is_contiguous() or nb < 0:
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"bag_offsets must be contiguous int64 on {self.device} with n_bags + 1 entries")
-        if mode not in ("sum", "mean"):
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"mode must be 'sum' or 'mean' (got {mode!r})")
-        k = self.tables[0].hot._keys(keys) if keys.numel() else keys
-        n = k.numel()
-        if out is None:
-            out = torch.empty((nb, self.dim), dtype=torch.float32, device=self.device)
-        elif out.dtype != torch.float32 or out.device != self.device or out.numel() != nb * self.dim or not out.is_contiguous():
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"out must be a contiguous float32 buffer [{nb}, {self.dim}] on {self.device}")
-        if found is None:
-            found = torch.empty(n, dtype=torch.uint8, device=self.device)
-        elif found.dtype != torch.uint8 or found.device != self.device or found.numel() != n or not found.is_contiguous():
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"found must be a contiguous uint8 buffer of {n} entries on {self.device}")
-        if n and nb == 0:
-            raise MeepoError(_lib.ERR_INVALID_ARG, "there are keys but no bags: no bag would report them")
+        nb, m = _n_bags(bag_offsets, self.device), _pool_mode(mode)
+        k = self.tables[0].hot._bag_keys(keys)
+        _no_bags_for_keys(k.numel(), nb)
+        n, _, _, out, _, found = _pooled_args(k, self.device, out, (nb, self.dim), torch.float32, found)
         _lib.check(_lib.lib().mee_group_find_pooled_tiered_jagged(self.hot_group._h, self.cold_group._h, k.data_ptr(), n, bag_offsets.data_ptr(), nb,
-                                                                  member_bags.data_ptr(), out.data_ptr(), found.data_ptr(), {"sum": 0, "mean": 1}[mode],
-                                                                  self._count_flags(), _stream_ptr(self.device)))
+                                                                  member_bags.data_ptr(), out.data_ptr(), found.data_ptr(), m, self._count_flags(),
+                                                                  _stream_ptr(self.device)))
         return out, found
 
     def apply_indexed(self, keys: torch.Tensor, offsets: torch.Tensor, grads: torch.Tensor, grad_index: torch.Tensor, optimizer: str, lr: float,
