@@ -1069,6 +1069,51 @@ int mee_sharded_size(mee_sharded* s, size_t* n_out, void* stream);       /* [syn
 int mee_sharded_status(mee_sharded* s, uint32_t* bits_out, void* stream);
 int mee_sharded_clear_status(mee_sharded* s, void* stream);
 
+/* ---- change log and delta export (README.md:2 "dynamic lookuptable-style"; SPEC.md §3 "Change log") ------------------------------------------
+ * A change log is a SET of int64 keys on one device: a table key plane and nothing else — `capacity` rounded as mee_table_create rounds it (16 x the
+ * smallest prime >= capacity / 16), the hash and probe sequence of SPEC.md §2, 8 bytes per slot — and two device words: `size`, the distinct keys stored,
+ * and `invalid`, sticky.  It belongs to no table: the caller notes the keys of every batch that may change a table's membership, rows or optimizer
+ * planes (the Python layer does so in every mutator of a tracked table), and mee_export_changed turns the set into the table's delta.
+ *
+ * mee_changes_note adds every key of the batch that is neither MEE_EMPTY_KEY nor MEE_RECLAIMED_KEY (both are padding: ignored silently); duplicates — inside
+ * a batch and across calls — are stored once.  A key for which the set has no room is not stored and sets `invalid`; nothing else is touched.  One launch,
+ * no synchronisation, no allocation: safe under stream capture.  n = 0 succeeds and launches nothing; a null log, or null keys with n > 0, is refused.
+ * mee_changes_group_note notes position i of segment j = [d_offsets[j], d_offsets[j + 1]) of a jagged batch in logs[j], in ONE launch whatever the number
+ * of logs; d_offsets holds n_tables + 1 values on the device and is never trusted: a position outside [d_offsets[0], d_offsets[n_tables]) or at or
+ * past n is noted nowhere.  The logs of a group share one device (at most 1024 of them).
+ * mee_changes_clear empties the set and resets `invalid`; mee_changes_invalidate sets `invalid` (the caller did something the log cannot name, e.g.
+ * mee_clear); mee_changes_info_get [syncs, the whole device] reads the two words back.
+ *
+ * mee_export_changed walks the log's slots [slot_begin, min(slot_end, the log's capacity)) and probes every key stored there in `t` — read-only, as
+ * mee_find: no key of `t` or `c` may change while it runs.  A key `t` holds is appended to the upsert outputs: the key, its values row and every
+ * optimizer plane `t` has, bit for bit, in one shared unspecified order (an output for a plane `t` lacks is ignored; a null state output skips that
+ * plane).  A key `t` does not hold is appended to d_removed_out.  d_counts_out (device, 2 words, zeroed by the call first) receives the number of upserts
+ * and the number of removed keys; nothing is written at or past them; every key of the range appears exactly once, in one of the two lists.  cap and
+ * removed_cap (in keys) must both be at least the number of slots in the range: anything smaller is MEE_ERR_INVALID_ARG before any launch.  No
+ * synchronisation, no allocation.  Refused before anything is launched or written: a null table, log, keys / values / removed / counts output, a
+ * bf16-row or int8-row table (MEE_ERR_UNSUPPORTED: a serving table has no training delta), `t` and `c` on different devices.
+ * The contract (SPEC.md §3): if every key whose membership, row or state plane changed in `t` since the log was last cleared was noted and invalid == 0,
+ * then a table that equalled `t` at that moment equals `t` now after mee_insert + mee_assign_plane of the upserts and mee_remove of the removed keys,
+ * taken over a partition of the log's slots. */
+typedef struct mee_changes mee_changes;
+typedef struct mee_changes_group mee_changes_group;
+typedef struct mee_changes_info {
+    uint64_t capacity, size;
+    uint32_t invalid, pad;
+} mee_changes_info;
+int mee_changes_create(int32_t device, uint64_t capacity, mee_changes** out);
+int mee_changes_destroy(mee_changes* c);
+int mee_changes_note(mee_changes* c, const int64_t* d_keys, size_t n, void* stream);
+int mee_changes_group_create(mee_changes* const* logs, uint32_t n_tables, mee_changes_group** out);
+int mee_changes_group_destroy(mee_changes_group* g);
+int mee_changes_group_note(mee_changes_group* g, const int64_t* d_keys, const uint64_t* d_offsets /* [n_tables + 1], device */, size_t n, void* stream);
+int mee_changes_info_get(const mee_changes* c, mee_changes_info* out);   /* [syncs] */
+int mee_changes_clear(mee_changes* c, void* stream);
+int mee_changes_invalidate(mee_changes* c, void* stream);
+int mee_export_changed(const mee_table* t, const mee_changes* c, uint64_t slot_begin, uint64_t slot_end, int64_t* d_keys_out, float* d_values_out,
+                       float* d_state1_out /* nullable */, float* d_state2_out /* nullable */, size_t cap, int64_t* d_removed_out, size_t removed_cap,
+                       uint64_t* d_counts_out /* device, 2 words */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -473,4 +473,41 @@ private:
     mee_sharded* s_ = nullptr;
 };
 
+// A change log (SPEC.md §3 "Change log"): the set of keys noted since it was last cleared, and the delta of a table over it.  Move-only.
+class ChangeLog {
+public:
+    ChangeLog(int32_t device, uint64_t capacity) { check(mee_changes_create(device, capacity, &c_)); }
+    ~ChangeLog() { if (c_) mee_changes_destroy(c_); }
+    ChangeLog(ChangeLog&& other) noexcept : c_(std::exchange(other.c_, nullptr)) {}
+    ChangeLog& operator=(ChangeLog&& other) noexcept { if (this != &other) { if (c_) mee_changes_destroy(c_); c_ = std::exchange(other.c_, nullptr); } return *this; }
+    ChangeLog(const ChangeLog&) = delete;
+    ChangeLog& operator=(const ChangeLog&) = delete;
+    mee_changes* handle() const noexcept { return c_; }
+    void note(const int64_t* d_keys, size_t n, void* stream = nullptr) { check(mee_changes_note(c_, d_keys, n, stream)); }
+    mee_changes_info info() const { mee_changes_info i{}; check(mee_changes_info_get(c_, &i)); return i; }   // [syncs]
+    void clear(void* stream = nullptr) { check(mee_changes_clear(c_, stream)); }
+    void invalidate(void* stream = nullptr) { check(mee_changes_invalidate(c_, stream)); }
+    // the delta of `t` over the log's slots [slot_begin, slot_end): upserts (keys, rows, planes) and removed keys; d_counts_out: two device words
+    void export_changed(const Table& t, uint64_t slot_begin, uint64_t slot_end, int64_t* d_keys_out, float* d_values_out, float* d_state1_out, float* d_state2_out, size_t cap,
+                        int64_t* d_removed_out, size_t removed_cap, uint64_t* d_counts_out, void* stream = nullptr) const {
+        check(mee_export_changed(t.handle(), c_, slot_begin, slot_end, d_keys_out, d_values_out, d_state1_out, d_state2_out, cap, d_removed_out, removed_cap, d_counts_out, stream));
+    }
+private:
+    mee_changes* c_ = nullptr;
+};
+
+// One note launch for the logs of a table group: position i of segment j of a jagged batch is noted in logs[j].  Move-only; the logs outlive it.
+class ChangeLogGroup {
+public:
+    ChangeLogGroup(mee_changes* const* logs, uint32_t n_tables) { check(mee_changes_group_create(logs, n_tables, &g_)); }
+    ~ChangeLogGroup() { if (g_) mee_changes_group_destroy(g_); }
+    ChangeLogGroup(ChangeLogGroup&& other) noexcept : g_(std::exchange(other.g_, nullptr)) {}
+    ChangeLogGroup& operator=(ChangeLogGroup&& other) noexcept { if (this != &other) { if (g_) mee_changes_group_destroy(g_); g_ = std::exchange(other.g_, nullptr); } return *this; }
+    ChangeLogGroup(const ChangeLogGroup&) = delete;
+    ChangeLogGroup& operator=(const ChangeLogGroup&) = delete;
+    void note(const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* stream = nullptr) { check(mee_changes_group_note(g_, d_keys, d_offsets, n, stream)); }
+private:
+    mee_changes_group* g_ = nullptr;
+};
+
 }  // namespace meepo

@@ -6,10 +6,11 @@ the HIP extension or a gfx950 device is missing — there is no CPU fallback.
 """
 from ._lib import (EMPTY_KEY, INIT_CONSTANT, INIT_UNIFORM, OPT_ADAGRAD, OPT_ADAM, OPT_FTRL, OPT_NONE, RECLAIMED_KEY,
                    STATUS_RESERVED_KEY, STATUS_TABLE_FULL, MeepoError)
+from .changes import ChangeLog
 from .table import LookupTable, MixedTableGroup, Router, TableGroup, hash_batch, keyed_layout, mixed_layout
 from .tiered import TieredLookupTable, TieredTableGroup
 
-__all__ = ["LookupTable", "Router", "TableGroup", "MixedTableGroup", "TieredLookupTable", "TieredTableGroup", "mixed_layout", "keyed_layout", "hash_batch", "MeepoError", "OPT_NONE", "OPT_ADAGRAD", "OPT_ADAM", "OPT_FTRL",
+__all__ = ["LookupTable", "ChangeLog", "Router", "TableGroup", "MixedTableGroup", "TieredLookupTable", "TieredTableGroup", "mixed_layout", "keyed_layout", "hash_batch", "MeepoError", "OPT_NONE", "OPT_ADAGRAD", "OPT_ADAM", "OPT_FTRL",
            "INIT_CONSTANT", "INIT_UNIFORM", "STATUS_TABLE_FULL", "STATUS_RESERVED_KEY", "EMPTY_KEY", "RECLAIMED_KEY", "ShardedTieredTableGroup"]
 
 

@@ -76,7 +76,12 @@ class TableInfo(C.Structure):
     ]
 
 
-_vp, _sz, _u64, _u32, _i32, _f32 = C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_int32, C.c_float
+class ChangesInfo(C.Structure):
+    """mee_changes_info: a change log's capacity and its two device words"""
+    _fields_ = [("capacity", C.c_uint64), ("size", C.c_uint64), ("invalid", C.c_uint32), ("pad", C.c_uint32)]
+
+
+_vp, _sz, _u64, _u32, _i32, _f32 =C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_int32, C.c_float
 
 # name -> (restype, argtypes); this is the full export list of include/meepo_embedding.h
 PROTOTYPES = {
@@ -271,6 +276,18 @@ PROTOTYPES = {
     "mee_sharded_apply_adam": (C.c_int, [_vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32, _u64, _vp]),
     "mee_sharded_size": (C.c_int, [_vp, C.POINTER(_sz), _vp]),
     "mee_sharded_status": (C.c_int, [_vp, C.POINTER(_u32), _vp]),
+    # change log (a device key set) and the delta export: note (log, keys, n, stream); group note (group, keys, member offsets, n, stream);
+    # export_changed (table, log, slot_begin, slot_end, keys_out, values_out, state1_out, state2_out, cap, removed_out, removed_cap, counts_out [2], stream)
+    "mee_changes_create": (C.c_int, [_i32, _u64, C.POINTER(_vp)]),
+    "mee_changes_destroy": (C.c_int, [_vp]),
+    "mee_changes_note": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "mee_changes_group_create": (C.c_int, [C.POINTER(_vp), _u32, C.POINTER(_vp)]),
+    "mee_changes_group_destroy": (C.c_int, [_vp]),
+    "mee_changes_group_note": (C.c_int, [_vp, _vp, _vp, _sz, _vp]),
+    "mee_changes_info_get": (C.c_int, [_vp, C.POINTER(ChangesInfo)]),
+    "mee_changes_clear": (C.c_int, [_vp, _vp]),
+    "mee_changes_invalidate": (C.c_int, [_vp, _vp]),
+    "mee_export_changed": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
 }
 
 _NARROW_ROWS = {torch.bfloat16: "a bf16-row table (value_dtype=torch.bfloat16) is a serving table with find, find_pooled, insert, assign, ",

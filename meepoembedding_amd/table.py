@@ -356,6 +356,7 @@ class LookupTable:
     indistinguishable from an fp32 table fed the dequantized rows (a missing key returns default_value as it is).  Rows must be finite.  Same restrictions
     and operators as a bf16-row table, dim a multiple of 16; it has no find_pooled (ERR_UNSUPPORTED) and is a member of no group."""
     supports_out_dtype = True   # its lookups can write bf16 rows (out_dtype=torch.bfloat16); the tiered / sharded / peer tables cannot
+    change_log = None           # the ChangeLog track_changes() attached (SPEC.md §3 "Change log"); None: no method issues a call it did not issue before
 
     def __init__(self, capacity: int, dim: int, *, device: int | torch.device = 0, optimizer: int = OPT_NONE,
                  max_batch: int = 1 << 20, default_value: float = 0.0, initial_accumulator: float = 0.0,
@@ -440,6 +441,21 @@ class LookupTable:
 
     def _s(self) -> int:
         return _stream_ptr(self.device)
+
+    def track_changes(self, capacity: int):
+        """Attach a ChangeLog of `capacity` keys (changes.py) -> the log.  From here on every mutator — insert, insert_missing, find_or_insert_missing,
+        assign, assign_plane, remove, find_or_insert[_located], apply_*, import_, move_to (both tables), evict — notes its batch's keys in it on the
+        table's stream, before its own first library call; clear() invalidates it (a key set cannot name "everything").  reserve, the lookups and the
+        hit-counter operators note nothing: they change nothing export returns."""
+        from .changes import ChangeLog
+        _lib.refuse_narrow_rows("track_changes", self)
+        self.change_log = ChangeLog(capacity, self.device)
+        return self.change_log
+
+    def _note(self, k: torch.Tensor) -> None:
+        """the batch's keys into the attached change log, if there is one"""
+        if self.change_log is not None:
+            self.change_log.note(k)
 
     def _bag_keys(self, keys: torch.Tensor) -> torch.Tensor:
         """_keys for the operators that take a jagged batch, which may be empty (and then of any dtype)"""
@@ -626,6 +642,7 @@ class LookupTable:
         """values: fp32 rows (a bf16-row table rounds them once), or bf16 rows for a bf16-row table (stored verbatim, mee_insert_as)."""
         k = self._keys(keys)
         v, dt = self._in_rows(values, k.numel())
+        self._note(k)
         if dt != _lib.DTYPE_F32:
             check(_lib.lib().mee_insert_as(self._h, k.data_ptr(), v.data_ptr(), dt, k.numel(), self._s()))
             return
@@ -636,6 +653,7 @@ class LookupTable:
         k = self._keys(keys)
         v = self._rows(values, k.numel())
         found = _buffer(found, "found", torch.uint8, k.numel(), self.device)
+        self._note(k)
         check(_lib.lib().mee_insert_missing(self._h, k.data_ptr(), v.data_ptr(), k.numel(), found.data_ptr(), self._s()))
 
     def find_or_insert_missing(self, keys: torch.Tensor, out: torch.Tensor, found: torch.Tensor) -> None:
@@ -643,6 +661,7 @@ class LookupTable:
         _fp32_only(out, "find_or_insert_missing")
         k = self._keys(keys)
         out, found = self._rows_found(out, found, k.numel())
+        self._note(k)
         check(_lib.lib().mee_find_or_insert_missing(self._h, k.data_ptr(), k.numel(), out.data_ptr(), found.data_ptr(), self._s()))
 
     def assign(self, keys: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
@@ -650,6 +669,7 @@ class LookupTable:
         k = self._keys(keys)
         v, dt = self._in_rows(values, k.numel())
         found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
+        self._note(k)
         if dt != _lib.DTYPE_F32:
             check(_lib.lib().mee_assign_as(self._h, k.data_ptr(), v.data_ptr(), dt, k.numel(), found.data_ptr(), self._s()))
             return found
@@ -669,12 +689,14 @@ class LookupTable:
         k = self._keys(keys)
         v = self._rows(values, k.numel())
         found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
+        self._note(k)
         check(_lib.lib().mee_assign_plane(self._h, plane, k.data_ptr(), v.data_ptr(), k.numel(), found.data_ptr(), self._s()))
         return found
 
     def remove(self, keys: torch.Tensor) -> torch.Tensor:
         k = self._keys(keys)
         found = torch.empty(k.numel(), dtype=torch.uint8, device=self.device)
+        self._note(k)
         check(_lib.lib().mee_remove(self._h, k.data_ptr(), k.numel(), found.data_ptr(), self._s()))
         self.layout_epoch += 1
         return found
@@ -692,6 +714,8 @@ class LookupTable:
         n_moved = torch.empty(1, dtype=torch.int64, device=self.device)
         moved = torch.empty(n, dtype=torch.uint8, device=self.device) if want_moved else None
         limit = 0xFFFFFFFFFFFFFFFF if max_moves is None else max(0, int(max_moves))
+        self._note(k)   # the keys leave this table ...
+        dst._note(k)    # ... and appear (or are overwritten) in that one
         check(_lib.lib().mee_move(self._h, dst._h, k.data_ptr(), n, limit, None if moved is None else moved.data_ptr(), n_moved.data_ptr(), self._s()))
         self.layout_epoch += 1
         return n_moved, moved
@@ -707,6 +731,7 @@ class LookupTable:
         k = self._keys(keys)
         n = k.numel()
         out, found = self._rows_found(out, found, n, out_dtype)
+        self._note(k)
         if dt != _lib.DTYPE_F32:
             check(_lib.lib().mee_find_or_insert_as(self._h, k.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(), self._s()))
         elif min_count is not None:
@@ -730,6 +755,8 @@ class LookupTable:
         out = _buffer(out, "out", out_dtype, (n, self.dim), self.device)   # (spelled out: this is the training step's forward)
         found = _buffer(found, "found", torch.uint8, n, self.device)
         slots = _buffer(slots, "slots", torch.int64, n, self.device)
+        if fn.startswith("mee_find_or_insert"):   # the two forms that create keys; find_located is a lookup
+            self._note(k)
         if dt != _lib.DTYPE_F32:
             check(getattr(_lib.lib(), fn + "_as")(self._h, k.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(), slots.data_ptr(), self._s()))
         else:
@@ -791,6 +818,8 @@ class LookupTable:
         check(_lib.lib().mee_clear_status(self._h, self._s()))
 
     def clear(self) -> None:
+        if self.change_log is not None:   # "every key is gone" is nothing a key set can name: the next save must be a full one
+            self.change_log.invalidate()
         check(_lib.lib().mee_clear(self._h, self._s()))
         self.layout_epoch += 1
 
@@ -853,12 +882,20 @@ class LookupTable:
             bufs = [torch.empty(cap, dtype=torch.int64, device=self.device), rows(),
                     rows() if with_state and self.optimizer != OPT_NONE else None, rows() if with_state and self.optimizer in (OPT_ADAM, OPT_FTRL) else None,
                     torch.empty(cap, dtype=torch.uint32, device=self.device)]
+        tracked = self.change_log is not None
+        if tracked and not spill:   # the evicted keys must be named: an EMPTY-prefilled key buffer (EMPTY is padding to the log) takes them
+            cap = min(limit, self.capacity)
+            bufs[0] = torch.full((cap,), _lib.EMPTY_KEY, dtype=torch.int64, device=self.device)
         n_out = torch.empty(1, dtype=torch.int64, device=self.device)
         flags = (_lib.EVICT_LEAST if least else 0) | (_lib.EVICT_RESET if reset else 0)
         check(_lib.lib().mee_evict(self._h, min(max_hits, 0xFFFFFFFF), min(limit, 0xFFFFFFFFFFFFFFFF), flags, *[None if b is None else b.data_ptr() for b in bufs], cap,
                                    n_out.data_ptr(), self._s()))
         self.layout_epoch += 1
+        if tracked and not spill:
+            self._note(bufs[0])
         n = int(n_out.item())
+        if tracked and spill:
+            self._note(bufs[0][:n])
         return tuple(None if b is None else b[:n] for b in bufs) if spill else n
 
     def _counts(self, counts: torch.Tensor, n: int) -> torch.Tensor:
@@ -976,6 +1013,7 @@ class LookupTable:
         """the three forms of the step: on the forward's slot handles, on indexed gradient rows, or plain"""
         k = self._keys(keys)
         n = k.numel()
+        self._note(k)
         if slots is not None:
             g = self._rows(grads, n)
             step.launch("mee_apply", "_located", self._h, k.data_ptr(), self._slots(slots, n).data_ptr(), g.data_ptr(), n, stream=self._s())
@@ -1041,6 +1079,27 @@ class TableGroup:
     training method raises MeepoError(ERR_UNSUPPORTED).  fp32-row and bf16-row tables never share a group."""
     supports_out_dtype = True
     keyed_bags = True   # find_pooled(layout="keyed", step_index=)
+    change_logs = None      # the members' ChangeLogs once track_changes() ran, and ...
+    _change_group = None    # ... the ChangeLogGroup that notes a jagged batch in all of them with one launch
+
+    def track_changes(self, capacity):
+        """One ChangeLog per member (capacity: an int for all, or one per member) -> the list of logs.  Each is attached to its member too — a member's own
+        mutators note in the same object — and the group's mutators (find_or_insert, apply_adagrad / apply_adam / apply_ftrl, apply_pooled,
+        apply_indexed, move_to) note their jagged batch in all of them with ONE launch (mee_changes_group_note) over the member offsets they already have."""
+        from .changes import ChangeLogGroup
+        caps = [int(capacity)] * len(self.tables) if isinstance(capacity, int) else [int(c) for c in capacity]
+        if len(caps) != len(self.tables):
+            raise ValueError(f"track_changes: one capacity, or one per member: {len(self.tables)} values (got {len(caps)})")
+        _lib.refuse_narrow_rows("TableGroup.track_changes", self)
+        self.change_logs = [t.track_changes(c) for t, c in zip(self.tables, caps)]
+        self._change_group = ChangeLogGroup(self.change_logs)
+        return self.change_logs
+
+    def _note(self, k: torch.Tensor, offsets: torch.Tensor, bags_per_table: int | None = None) -> None:
+        """the jagged batch into the members' change logs, if the group is tracked.  bags_per_table: `offsets` are a pooled lookup's bag offsets, and the
+        member bounds are every bags_per_table-th of them (as nn._member_offsets takes them)"""
+        if self._change_group is not None and k.numel() and bags_per_table != 0:
+            self._change_group.note(k, offsets if bags_per_table is None else offsets[::bags_per_table].contiguous())
 
     def __init__(self, tables, max_apply_batch: int = 0):
         self.tables = list(tables)
@@ -1116,6 +1175,8 @@ class TableGroup:
                 raise MeepoError(_lib.ERR_INVALID_ARG, f"max_moves must hold {nt} int64 limits (a list, or a contiguous tensor on {self.device})")
         n_moved = torch.empty(nt, dtype=torch.int64, device=self.device)
         moved = torch.empty(n, dtype=torch.uint8, device=self.device) if want_moved else None
+        self._note(k, offsets)        # the keys leave these members ...
+        dst_group._note(k, offsets)   # ... and appear in those
         check(_lib.lib().mee_group_move(self._h, dst_group._h, k.data_ptr(), offsets.data_ptr(), n, None if limits is None else limits.data_ptr(),
                                         None if moved is None else moved.data_ptr(), n_moved.data_ptr(), _stream_ptr(self.device)))
         for t in self.tables:
@@ -1141,6 +1202,7 @@ class TableGroup:
         bpt = self._check_bags(offsets) if pooled else self._check_offsets(offsets)
         k = self.tables[0]._bag_keys(keys)
         n, s = k.numel(), _stream_ptr(self.device)
+        self._note(k, offsets, bpt if pooled else None)
         if index is None:
             g = self.tables[0]._rows(grads, n)
             step.launch("mee_group_apply", "", self._h, k.data_ptr(), offsets.data_ptr(), g.data_ptr(), n, stream=s)
@@ -1287,6 +1349,7 @@ class TableGroup:
         n = k.numel()
         self._check_offsets(offsets)
         out, found = self.tables[0]._rows_found(out, found, n, out_dtype)
+        self._note(k, offsets)
         check(_lib.lib().mee_group_find_or_insert_admit(self._h, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(), scalar,
                                                         per_member.data_ptr() if per_member is not None else None, _stream_ptr(self.device)))
         return out, found
@@ -1323,6 +1386,8 @@ class TableGroup:
         n = k.numel()
         self._check_offsets(offsets)
         out, found = self.tables[0]._rows_found(out, found, n, out_dtype)
+        if _fn == "mee_group_find_or_insert":   # the form that creates keys; the plain find is a lookup
+            self._note(k, offsets)
         if dt != _lib.DTYPE_F32:
             check(getattr(_lib.lib(), _fn + "_as")(self._h, k.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), dt, found.data_ptr(),
                                                    _stream_ptr(self.device)))
