@@ -1114,6 +1114,32 @@ int mee_export_changed(const mee_table* t, const mee_changes* c, uint64_t slot_b
                        float* d_state1_out /* nullable */, float* d_state2_out /* nullable */, size_t cap, int64_t* d_removed_out, size_t removed_cap,
                        uint64_t* d_counts_out /* device, 2 words */, void* stream);
 
+/* ---- publish: a change log's delta of a trainer table, device to device into a serving table (SPEC.md §3 "Publish") ----------------------------
+ * mee_publish_changed walks the log's slots [slot_begin, min(slot_end, the log's capacity)) and probes every key stored there in `src` — read-only, as
+ * mee_find; `src` and the log are never written.  A key `src` holds is an upsert: `dst` ends up holding it with src's VALUES row (no state plane travels) —
+ * bit for bit in an fp32-row dst, rounded once by the rule of SPEC.md "Output type" in a bf16-row dst: exactly what mee_insert(dst, key, row) stores.  A
+ * key dst lacks is placed by the placement rule of SPEC.md §2; a slot created in a dst with MEE_FLAG_TRACK_HITS starts at counter 0, an existing one keeps
+ * its counter.  A key `src` does not hold is removed from dst as mee_remove removes it (no-op if dst lacks it).  A key for which dst has no room is
+ * dropped: dst stays without it and MEE_STATUS_TABLE_FULL goes to dst's status word.
+ * d_counts_out (device, 4 words, zeroed by the call first): [0] the keys that got a slot in dst (new or overwritten), [1] the keys src does not hold,
+ * [2] the keys dropped for lack of room, [3] the log's `invalid` word as the launch read it (non-zero: the log does not name every change — rebuild dst).
+ * After the call over a partition of the log's slots dst equals — in mee_export sorted by key, mee_size and status bits — what mee_insert of
+ * mee_export_changed's upserts followed by mee_remove of its removed keys leaves; so a dst that equalled "src rounded" when the log was last cleared
+ * equals "src rounded" now.  Two launches, no [n, dim] buffer, no synchronisation, no allocation: safe under stream capture; independent of either
+ * table's max_batch.  Slot handles of dst from before the call are stale.  No lookup of dst may run concurrently (stream order).
+ * Refused before anything is launched or written: a null table, log or counts, src == dst, a dim or device mismatch among the three
+ * (MEE_ERR_INVALID_ARG); a dst with an optimizer, a src with bf16 or int8 rows, a dst with int8 rows (MEE_ERR_UNSUPPORTED).  slot_begin >= slot_end
+ * succeeds and zeroes the counts.
+ * mee_group_publish_changed is mee_publish_changed on every member j of two groups over the WHOLE of log j, in one launch sequence whatever the number
+ * of tables: src a group of fp32-row tables, dst a group of optimizer-less fp32-row tables or of bf16-row tables, logs a mee_changes_group, all three of
+ * the same n_tables, dim and device; no table may be a member twice across the two groups.  d_counts_out holds n_tables x 4 words, member j's at 4j.
+ * A member whose log is empty costs its slot scan.  Like every group operator it re-reads, behind a stream synchronisation, the planes of a member that
+ * mee_reserve moved: the first call after a reserve must not be captured. */
+int mee_publish_changed(const mee_table* src, const mee_changes* log, mee_table* dst, uint64_t slot_begin, uint64_t slot_end,
+                        uint64_t* d_counts_out /* device, 4 words */, void* stream);
+int mee_group_publish_changed(const mee_group* src, const mee_changes_group* logs, mee_group* dst,
+                              uint64_t* d_counts_out /* device, n_tables x 4 words */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,7 @@ public:
     ~Group() { if (g_) mee_group_destroy(g_); }
     Group(const Group&) = delete;
     Group& operator=(const Group&) = delete;
+    mee_group* handle() const noexcept { return g_; }
     uint32_t value_dtype() const { uint32_t d = MEE_DTYPE_F32; check(mee_group_value_dtype(g_, &d)); return d; }   // MEE_DTYPE_BF16: a bf16-row group
     // segment j = d_keys[d_offsets[j] .. d_offsets[j+1]); d_offsets: n_tables + 1 values in DEVICE memory; n = total positions
     void find(const int64_t* d_keys, const uint64_t* d_offsets, size_t n, float* d_out, uint8_t* d_found, void* stream = nullptr) {
@@ -492,6 +493,11 @@ public:
                         int64_t* d_removed_out, size_t removed_cap, uint64_t* d_counts_out, void* stream = nullptr) const {
         check(mee_export_changed(t.handle(), c_, slot_begin, slot_end, d_keys_out, d_values_out, d_state1_out, d_state2_out, cap, d_removed_out, removed_cap, d_counts_out, stream));
     }
+    // the delta of `src` over the log's slots [slot_begin, slot_end) straight into the serving table `dst` (SPEC.md §3 "Publish"): no buffer, no
+    // synchronisation; d_counts_out: four device words (placed, absent from src, dropped for lack of room, the log's invalid word)
+    void publish(const Table& src, Table& dst, uint64_t slot_begin, uint64_t slot_end, uint64_t* d_counts_out, void* stream = nullptr) const {
+        check(mee_publish_changed(src.handle(), c_, dst.handle(), slot_begin, slot_end, d_counts_out, stream));
+    }
 private:
     mee_changes* c_ = nullptr;
 };
@@ -506,6 +512,8 @@ public:
     ChangeLogGroup(const ChangeLogGroup&) = delete;
     ChangeLogGroup& operator=(const ChangeLogGroup&) = delete;
     void note(const int64_t* d_keys, const uint64_t* d_offsets, size_t n, void* stream = nullptr) { check(mee_changes_group_note(g_, d_keys, d_offsets, n, stream)); }
+    // ChangeLog::publish for every member over the whole of its log, in one launch sequence; d_counts_out: n_tables x 4 device words
+    void publish(const Group& src, Group& dst, uint64_t* d_counts_out, void* stream = nullptr) const { check(mee_group_publish_changed(src.handle(), g_, dst.handle(), d_counts_out, stream)); }
 private:
     mee_changes_group* g_ = nullptr;
 };

@@ -288,6 +288,9 @@ PROTOTYPES = {
     "mee_changes_clear": (C.c_int, [_vp, _vp]),
     "mee_changes_invalidate": (C.c_int, [_vp, _vp]),
     "mee_export_changed": (C.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    # publish (src table, log, dst table, slot_begin, slot_end, counts_out [4], stream); group form (src group, log group, dst group, counts_out [n_tables][4], stream)
+    "mee_publish_changed": (C.c_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "mee_group_publish_changed": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
 }
 
 _NARROW_ROWS = {torch.bfloat16: "a bf16-row table (value_dtype=torch.bfloat16) is a serving table with find, find_pooled, insert, assign, ",

@@ -93,6 +93,20 @@ class ChangeLog:
         n, r = (int(x) for x in counts.tolist())   # the one synchronisation, as export_range has
         return keys[:n], vals[:n], (s1[:n] if s1 is not None else None), (s2[:n] if s2 is not None else None), removed[:r]
 
+    def publish(self, table, serving, slot_begin: int = 0, slot_end: int | None = None) -> torch.Tensor:
+        """The delta of `table` over the log's slots [slot_begin, slot_end) (None: to the end) straight into `serving`, device to device (SPEC.md §3
+        "Publish", mee_publish_changed): the noted keys `table` holds end up in `serving` with the table's values row (rounded once for a bf16-row
+        serving table), the noted keys it does not hold are removed there.  -> int64 device tensor [4]: keys placed, keys absent from `table`, keys
+        dropped for lack of room (STATUS_TABLE_FULL on `serving`), the log's invalid word.  One library call, no buffer, no synchronisation."""
+        for t in (table, serving):
+            if t.device != self.device:
+                raise MeepoError(_lib.ERR_INVALID_ARG, f"publish: both tables must be on {self.device}, the log's device")
+        counts = torch.empty(4, dtype=torch.int64, device=self.device)
+        check(_lib.lib().mee_publish_changed(table._h, self._h, serving._h, int(slot_begin), 0xFFFFFFFFFFFFFFFF if slot_end is None else int(slot_end),
+                                             counts.data_ptr(), self._s()))
+        serving.layout_epoch += 1   # rows may have been freed: slot handles of `serving` from before are stale
+        return counts
+
     def iter_changed(self, table, chunk_slots: int = 1 << 22, with_state: bool = True):
         """Generator over export_changed pieces covering the whole log (pieces without a key are skipped)."""
         for b in range(0, self.capacity, int(chunk_slots)):

@@ -10,12 +10,15 @@
 //   export        mee_export_changed, per 64 slots of the log's range and wave: the stored keys are probed in the table (tile_probe: read-only, as find),
 //                 sixteen at a time; the wave then takes ONE ticket per list — held keys (upserts) and absent keys (removed) — by a ballot and a single
 //                 atomic each, writes the keys from the lanes that hold them and copies the rows of every plane, one 16-lane tile per row.
+//   publish       mee_publish_changed / mee_group_publish_changed: the same walk and probe, twice — the held keys' values rows go straight into a serving
+//                 table (claimed or found there, rounded once for bf16 rows), then the absent keys are tombstoned there (see "publish" below).
 // Why a key set and not a bitmap over the table's slots: a bitmap loses the key of a slot that was removed (the delta must name it) and dies with
 // mee_reserve, which moves every key to another slot (DESIGN.md §4 "Change log and delta export").
 //
 // The upstream snapshot has no code for checkpoints; the semantics are SPEC.md §3 "Change log".
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -131,6 +134,40 @@ __device__ __forceinline__ uint64_t drop_lowest_16(uint64_t m) {
     return m;
 }
 
+// The batched read-only probe of a wave step's keys (the export and both publish launches): lane l holds key kmine, `mask` = the lanes whose key is
+// asked about.  The keys are probed in `tkeys` 4 x kChangedProbes at a time (tile_probe: plain loads, so no key of that table may change into or out
+// of any of the asked keys while the kernel runs); the slot (or -1) comes back to the lane that holds the key.  Lanes outside the mask get -1.  Must be
+// called by ALL 64 lanes in convergent control flow; `mask` is wave-uniform.
+__device__ __forceinline__ int64_t probe_step_keys(const int64_t* __restrict__ tkeys, uint64_t nb, int64_t kmine, uint64_t mask, int lane, int tile, int tl) {
+    constexpr int P = kChangedProbes;
+    int64_t myslot = -1;
+    for (uint64_t rest = mask; rest; rest = drop_lowest_16(rest)) {   // wave-uniform
+        int from[P];
+        int64_t key[P], kb[P], slot[P];
+        uint64_t b[P];
+        bool act[P];
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+            from[r] = nth_set_lane(rest, r * 4 + tile);
+            key[r] = __shfl(kmine, from[r] >= 0 ? from[r] : 0);
+            act[r] = from[r] >= 0;
+            b[r] = bucket_of(key[r], nb);
+            kb[r] = act[r] ? tkeys[b[r] * kW + tl] : kEmpty;
+        }
+#pragma unroll
+        for (int r = 0; r < P; ++r) slot[r] = tile_probe(tkeys, nb, key[r], act[r], b[r], kb[r], tile, tl);
+#pragma unroll
+        for (int r = 0; r < P; ++r)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int owner = __shfl(from[r], q * kW);
+                const int64_t sq = __shfl(slot[r], q * kW);
+                if (lane == owner) myslot = sq;
+            }
+    }
+    return myslot;
+}
+
 // DIM4 = 16 / 32: RowShape<DIM4>::rows_per_tile rows of all NP planes are requested before the first store and move as 16-byte groups per lane;
 // DIM4 = 0 loops at run time.  All slot-to-row arithmetic in 64 bits.
 template <int DIM4, int NP>
@@ -143,38 +180,13 @@ __global__ __launch_bounds__(256) void export_changed_kernel(const int64_t* __re
     const uint32_t dim4 = DIM4 ? DIM4 : dim4_rt;
     constexpr int C = DIM4 ? DIM4 / 16 : 1;
     constexpr int R = RowShape<DIM4>::rows_per_tile;
-    constexpr int P = kChangedProbes;
     for (uint64_t s0 = begin + wave * 64; s0 < end; s0 += n_waves * 64) {   // wave-uniform
         const int64_t kmine = s0 + lane < end ? lkeys[s0 + lane] : kEmpty;   // the log's slots as they lie: one coalesced load
         const bool stored = !reserved_key(kmine);
         const uint64_t sm = __ballot(stored);
         if (!sm) continue;   // wave-uniform
         // ---- probe the table for every stored key, 4P at a time; the slot comes back to the lane that holds the key
-        int64_t myslot = -1;
-        for (uint64_t rest = sm; rest; rest = drop_lowest_16(rest)) {   // wave-uniform
-            int from[P];
-            int64_t key[P], kb[P], slot[P];
-            uint64_t b[P];
-            bool act[P];
-#pragma unroll
-            for (int r = 0; r < P; ++r) {
-                from[r] = nth_set_lane(rest, r * 4 + tile);
-                key[r] = __shfl(kmine, from[r] >= 0 ? from[r] : 0);
-                act[r] = from[r] >= 0;
-                b[r] = bucket_of(key[r], nb);
-                kb[r] = act[r] ? tkeys[b[r] * kW + tl] : kEmpty;
-            }
-#pragma unroll
-            for (int r = 0; r < P; ++r) slot[r] = tile_probe(tkeys, nb, key[r], act[r], b[r], kb[r], tile, tl);
-#pragma unroll
-            for (int r = 0; r < P; ++r)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int owner = __shfl(from[r], q * kW);
-                    const int64_t sq = __shfl(slot[r], q * kW);
-                    if (lane == owner) myslot = sq;
-                }
-        }
+        const int64_t myslot = probe_step_keys(tkeys, nb, kmine, sm, lane, tile, tl);
         // ---- one ticket per list
         const uint64_t um = __ballot(stored && myslot >= 0), rm = sm & ~um;
         unsigned long long up0 = 0, rm0 = 0;
@@ -234,6 +246,169 @@ __global__ __launch_bounds__(256) void export_changed_kernel(const int64_t* __re
     }
 }
 
+// ---- publish: log -> trainer table -> serving table (SPEC.md §3 "Publish") ----------------------------------------------------------------
+// Two launches over the same walk of the log (64 slots per wave step, the stored keys probed read-only in src as the export probes them):
+//   upsert   the keys src holds: their values rows are requested from src, 4R a round, BEFORE the first claim; each key is then claimed or found in
+//            dst (tile_locate<claim, coherent>: other tiles of this launch claim in the same table) and the row is stored — 16 bytes per lane into an
+//            fp32-row dst, the four floats rounded once (bf16x4_of) and 8 bytes per lane into a bf16-row dst.  No state plane is read.
+//   remove   behind the kernel boundary: the keys src does not hold are located in dst and tombstoned.
+// Why two: the contract is the composition "insert the upserts, THEN remove the rest".  Which keys find room in a crowded dst is part of it: a tombstone
+// written while the claims are under way frees a slot the composition's insert never saw, so a key the composition drops (TABLE_FULL) could be stored.
+// Behind the kernel boundary every claim has been made against the table as insert sees it, and the remove launch may probe with plain loads (below).
+struct PublishTables {           // wave-uniform: src as it is read, dst as it is written
+    const int64_t* skeys;
+    const float4* srows;
+    uint64_t snb;
+    int64_t* dkeys;
+    void* drows;                 // fp32 rows (float4 groups) or bf16 rows (8-byte groups)
+    uint64_t dnb;
+    uint32_t* dstatus;
+    uint32_t* dhits;             // null without MEE_FLAG_TRACK_HITS
+};
+struct PublishStep {             // the 64 log slots one wave step walks
+    const int64_t* lkeys;
+    uint64_t s0, end;            // the step's first slot and the end of the range, both in that log
+    PublishTables t;
+    unsigned long long* counts;  // the four words of that log's publish
+};
+static __device__ __forceinline__ PublishTables publish_tables_of(const MoveTable& s, const MoveTable& d) {
+    return PublishTables{s.tkeys, s.plane[0], s.nb, d.tkeys, d.plane[0], d.nb, d.status, d.hits};
+}
+
+// step_of(step, PublishStep&): what wave step `step` < n_steps works on — what differs between one table and a group.  Counts leave as one atomic per
+// wave step and list.  Must be run by ALL 64 lanes in convergent control flow.
+template <int DIM4, bool BF16, class StepOf>
+__device__ __forceinline__ void publish_upsert_body(uint64_t n_steps, uint32_t dim4_rt, StepOf&& step_of) {
+    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    const uint32_t dim4 = DIM4 ? DIM4 : dim4_rt;
+    constexpr int C = DIM4 ? DIM4 / 16 : 1;
+    constexpr int R = RowShape<DIM4>::rows_per_tile;
+    for (uint64_t step = wave; step < n_steps; step += n_waves) {   // wave-uniform
+        PublishStep p;
+        step_of(step, p);
+        const int64_t kmine = p.s0 + lane < p.end ? p.lkeys[p.s0 + lane] : kEmpty;   // the log's slots as they lie: one coalesced load
+        const bool stored = !reserved_key(kmine);
+        const uint64_t sm = __ballot(stored);
+        if (!sm) continue;   // wave-uniform
+        const int64_t myslot = probe_step_keys(p.t.skeys, p.t.snb, kmine, sm, lane, tile, tl);
+        uint32_t n_placed = 0, n_full = 0;
+        for (uint64_t rest = __ballot(stored && myslot >= 0); rest;) {   // wave-uniform: the held keys, one tile per key, 4R a round
+            int64_t key[R], sslot[R], dslot[R];
+            bool has[R], is_new[R], full[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int from = nth_set_lane(rest, r * 4 + tile);
+                has[r] = from >= 0;
+                key[r] = __shfl(kmine, has[r] ? from : 0);
+                sslot[r] = __shfl(myslot, has[r] ? from : 0);
+            }
+            float4 row[R][C];
+            if constexpr (DIM4 != 0) {   // every row of the round is in flight before the first claim
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+#pragma unroll
+                    for (int c = 0; c < C; ++c) row[r][c] = has[r] ? p.t.srows[(uint64_t)sslot[r] * DIM4 + c * 16 + tl] : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) dslot[r] = tile_locate<true, true>(p.t.dkeys, p.t.dnb, key[r], has[r], tile, tl, is_new[r], full[r]);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const bool ok = has[r] && dslot[r] >= 0;   // (a claim that found no slot reports `full`)
+                if (ok) {
+                    const uint64_t o = (uint64_t)dslot[r] * dim4;
+                    if constexpr (DIM4 != 0) {
+#pragma unroll
+                        for (int c = 0; c < C; ++c) {
+                            if constexpr (BF16) reinterpret_cast<u32x2*>(p.t.drows)[o + c * 16 + tl] = bf16x4_of(row[r][c].x, row[r][c].y, row[r][c].z, row[r][c].w);
+                            else reinterpret_cast<float4*>(p.t.drows)[o + c * 16 + tl] = row[r][c];
+                        }
+                    } else {
+                        for (uint32_t c = tl; c < dim4; c += 16) {
+                            const float4 v = p.t.srows[(uint64_t)sslot[r] * dim4 + c];
+                            if constexpr (BF16) reinterpret_cast<u32x2*>(p.t.drows)[o + c] = bf16x4_of(v.x, v.y, v.z, v.w);
+                            else reinterpret_cast<float4*>(p.t.drows)[o + c] = v;
+                        }
+                    }
+                    if (is_new[r] && p.t.dhits && tl == 0) p.t.dhits[dslot[r]] = 0;   // a created slot starts a new window; an existing one keeps its counter
+                }
+                const uint64_t fm = __ballot(has[r] && full[r] && tl == 0);
+                if (fm && lane == __ffsll((unsigned long long)fm) - 1) atomicOr(p.t.dstatus, (uint32_t)MEE_STATUS_TABLE_FULL);
+                n_placed += (uint32_t)__popcll(__ballot(ok && tl == 0));
+                n_full += (uint32_t)__popcll(fm);
+            }
+#pragma unroll
+            for (int q = 0; q < 4 * R; ++q) rest &= rest - 1;
+        }
+        if (lane == 0 && n_placed) atomicAdd(&p.counts[0], (unsigned long long)n_placed);
+        if (lane == 0 && n_full) atomicAdd(&p.counts[2], (unsigned long long)n_full);
+    }
+}
+
+// The keys of the step that src does not hold leave dst.  The probe of dst is the read-only one (plain loads) although this launch writes dst's keys,
+// because of WHAT it writes: every key of the log is handled by exactly one lane of one wave (a log holds a key once), so the only change another wave can
+// make under a probe for key K is to turn a live key OTHER than K into RECLAIMED.  A probe stops at K or at an EMPTY slot and walks past everything else:
+// whether a stale line still shows the live foreign key or already the tombstone, it is neither, and the probe's outcome is the same.  EMPTY slots are
+// never made or filled here, and the upsert launch's claims are behind a kernel boundary.
+template <class StepOf>
+__device__ __forceinline__ void publish_remove_body(uint64_t n_steps, StepOf&& step_of) {
+    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t step = wave; step < n_steps; step += n_waves) {   // wave-uniform
+        PublishStep p;
+        step_of(step, p);
+        const int64_t kmine = p.s0 + lane < p.end ? p.lkeys[p.s0 + lane] : kEmpty;
+        const bool stored = !reserved_key(kmine);
+        const uint64_t sm = __ballot(stored);
+        if (!sm) continue;   // wave-uniform
+        const int64_t sslot = probe_step_keys(p.t.skeys, p.t.snb, kmine, sm, lane, tile, tl);   // src has not changed since the upsert launch
+        const uint64_t rm = __ballot(stored && sslot < 0);
+        if (!rm) continue;   // wave-uniform
+        const int64_t dslot = probe_step_keys(p.t.dkeys, p.t.dnb, kmine, rm, lane, tile, tl);
+        if (dslot >= 0) (void)atomicExch((unsigned long long*)(p.t.dkeys + dslot), (unsigned long long)kReclaimed);   // by the lane that holds the key
+        if (lane == 0) atomicAdd(&p.counts[1], (unsigned long long)__popcll(rm));
+    }
+}
+
+template <int DIM4, bool BF16>
+__global__ __launch_bounds__(256) void publish_upsert_kernel(ChangeSet log, uint64_t begin, uint64_t end, PublishTables t, uint32_t dim4_rt,
+                                                             unsigned long long* __restrict__ counts) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) counts[3] = log.state->invalid;   // as this launch read it
+    publish_upsert_body<DIM4, BF16>((end - begin + 63) / 64, dim4_rt, [&](uint64_t step, PublishStep& p) { p = PublishStep{log.keys, begin + step * 64, end, t, counts}; });
+}
+__global__ __launch_bounds__(256) void publish_remove_kernel(ChangeSet log, uint64_t begin, uint64_t end, PublishTables t, unsigned long long* __restrict__ counts) {
+    publish_remove_body((end - begin + 63) / 64, [&](uint64_t step, PublishStep& p) { p = PublishStep{log.keys, begin + step * 64, end, t, counts}; });
+}
+
+// The group form: the flat work space is the concatenation of the members' log capacities, each rounded up to a multiple of 64, so a wave step lies in
+// one member and everything in PublishStep is wave-uniform.  lb: the n_tables + 1 bounds of that space, staged in LDS (stage_offsets).
+__device__ __forceinline__ void publish_group_step(const uint64_t* lb, uint32_t n_tables, const ChangeSet* __restrict__ logs, const MoveTable* __restrict__ src,
+                                                   const MoveTable* __restrict__ dst, unsigned long long* counts, uint64_t step, PublishStep& p) {
+    const uint64_t f = step * 64;
+    const uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)member_of_position(lb, n_tables, f));   // (the same in every lane: say so)
+    const ChangeSet lg = logs[j];
+    p = PublishStep{lg.keys, f - lb[j], lg.nb * (uint64_t)kW, publish_tables_of(src[j], dst[j]), counts + 4 * (uint64_t)j};
+}
+template <int DIM4, bool BF16>
+__global__ __launch_bounds__(256) void publish_upsert_grouped_kernel(const ChangeSet* __restrict__ logs, const uint64_t* __restrict__ bounds, uint32_t n_tables,
+                                                                     const MoveTable* __restrict__ src, const MoveTable* __restrict__ dst, uint32_t dim4_rt,
+                                                                     unsigned long long* __restrict__ counts) {
+    __shared__ uint64_t lb[kMaxGroupTables + 1];
+    if (blockIdx.x == 0)
+        for (uint32_t j = threadIdx.x; j < n_tables; j += blockDim.x) counts[4 * (uint64_t)j + 3] = logs[j].state->invalid;
+    stage_offsets(lb, bounds, 1, n_tables, ~0ull);
+    publish_upsert_body<DIM4, BF16>(lb[n_tables] / 64, dim4_rt, [&](uint64_t step, PublishStep& p) { publish_group_step(lb, n_tables, logs, src, dst, counts, step, p); });
+}
+__global__ __launch_bounds__(256) void publish_remove_grouped_kernel(const ChangeSet* __restrict__ logs, const uint64_t* __restrict__ bounds, uint32_t n_tables,
+                                                                     const MoveTable* __restrict__ src, const MoveTable* __restrict__ dst,
+                                                                     unsigned long long* __restrict__ counts) {
+    __shared__ uint64_t lb[kMaxGroupTables + 1];
+    stage_offsets(lb, bounds, 1, n_tables, ~0ull);
+    publish_remove_body(lb[n_tables] / 64, [&](uint64_t step, PublishStep& p) { publish_group_step(lb, n_tables, logs, src, dst, counts, step, p); });
+}
+
 // =========================================================================================================
 // host side
 // =========================================================================================================
@@ -260,11 +435,30 @@ struct mee_changes_group {
     int device;
     uint32_t n_tables;
     mee::ChangeSet* d_logs;   // [n_tables], device: a log's plane never moves, so this is uploaded once
+    // mee_group_publish_changed walks all the logs as one flat space: the members' capacities, each rounded up to a multiple of 64, end to end
+    uint64_t* d_bounds;       // [n_tables + 1], device, uploaded with d_logs
+    uint64_t walk_slots;      // = bounds[n_tables]
 };
 
 using namespace mee;
 
 static ChangeSet change_set_of(const mee_changes* c) { return ChangeSet{c->keys, c->nb, c->state}; }
+
+// what a publish refuses about one (src, dst) pair before anything is launched or written; `member` < 0: the pair of mee_publish_changed
+static int publish_pair_check(const mee_table* s, const mee_table* d, const char* name, int member) {
+    char who[32] = "";
+    if (member >= 0) snprintf(who, sizeof who, " (member %d)", member);
+    if (s == d) return fail(MEE_ERR_INVALID_ARG, "%s: src and dst are the same table%s", name, who);
+    if (s->device != d->device || s->dim != d->dim)
+        return fail(MEE_ERR_INVALID_ARG, "%s: src and dst differ in device (%d, %d) or dim (%u, %u)%s", name, s->device, d->device, s->dim, d->dim, who);
+    if (d->optimizer != MEE_OPT_NONE)
+        return fail(MEE_ERR_UNSUPPORTED, "%s: dst has an optimizer (%u)%s — a publish carries the values row only, into a table without state planes", name, d->optimizer, who);
+    if (s->bf16_rows || s->int8_rows)
+        return fail(MEE_ERR_UNSUPPORTED, "%s: src stores %s rows%s — the source of a publish is an fp32-row table", name, s->bf16_rows ? "bf16" : "int8", who);
+    if (d->int8_rows)
+        return fail(MEE_ERR_UNSUPPORTED, "%s: dst stores int8 rows%s — publish into fp32 or bf16 rows (an int8-row table takes the delta through mee_insert and mee_remove)", name, who);
+    return MEE_OK;
+}
 
 extern "C" {
 
@@ -322,20 +516,24 @@ int mee_changes_group_create(mee_changes* const* logs, uint32_t n_tables, mee_ch
     *out = nullptr;
     if (n_tables == 0 || n_tables > kMaxGroupTables) return fail(MEE_ERR_INVALID_ARG, "mee_changes_group_create: n_tables must be in [1, %u]", kMaxGroupTables);
     std::vector<ChangeSet> sets(n_tables);
+    std::vector<uint64_t> bounds(n_tables + 1, 0);
     for (uint32_t j = 0; j < n_tables; ++j) {
         if (!logs[j]) return fail(MEE_ERR_INVALID_ARG, "mee_changes_group_create: log %u is null", j);
         if (logs[j]->device != logs[0]->device)
             return fail(MEE_ERR_INVALID_ARG, "mee_changes_group_create: log %u is on device %d, log 0 on device %d", j, logs[j]->device, logs[0]->device);
         sets[j] = change_set_of(logs[j]);
+        bounds[j + 1] = bounds[j] + ((logs[j]->capacity + 63) & ~63ull);
     }
     DeviceGuard g(logs[0]->device);
     mee_changes_group* grp = new (std::nothrow) mee_changes_group();
     if (!grp) return fail(MEE_ERR_OUT_OF_MEMORY, "host allocation failed");
-    grp->device = logs[0]->device; grp->n_tables = n_tables; grp->d_logs = nullptr;
+    grp->device = logs[0]->device; grp->n_tables = n_tables; grp->d_logs = nullptr; grp->d_bounds = nullptr; grp->walk_slots = bounds[n_tables];
     hipError_t e = hipMalloc((void**)&grp->d_logs, n_tables * sizeof(ChangeSet));
+    if (e == hipSuccess) e = hipMalloc((void**)&grp->d_bounds, bounds.size() * sizeof(uint64_t));
     if (e == hipSuccess) e = hipMemcpy(grp->d_logs, sets.data(), n_tables * sizeof(ChangeSet), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(grp->d_bounds, bounds.data(), bounds.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        (void)hipFree(grp->d_logs);
+        (void)hipFree(grp->d_logs); (void)hipFree(grp->d_bounds);
         delete grp;
         return fail(e == hipErrorOutOfMemory ? MEE_ERR_OUT_OF_MEMORY : MEE_ERR_HIP, "mee_changes_group_create: %s", hipGetErrorString(e));
     }
@@ -346,7 +544,7 @@ int mee_changes_group_create(mee_changes* const* logs, uint32_t n_tables, mee_ch
 int mee_changes_group_destroy(mee_changes_group* g) {
     if (!g) return MEE_OK;
     DeviceGuard guard(g->device);
-    (void)hipFree(g->d_logs);
+    (void)hipFree(g->d_logs); (void)hipFree(g->d_bounds);
     delete g;
     return MEE_OK;
 }
@@ -417,6 +615,63 @@ int mee_export_changed(const mee_table* t, const mee_changes* c, uint64_t slot_b
                                                                                              d_removed_out, removed_cap, (unsigned long long*)d_counts_out);
         }); });
     }
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+int mee_publish_changed(const mee_table* src, const mee_changes* log, mee_table* dst, uint64_t slot_begin, uint64_t slot_end, uint64_t* d_counts_out, void* stream) {
+    MEE_RANGE("mee_publish_changed");
+    if (!src || !log || !dst || !d_counts_out) return fail(MEE_ERR_INVALID_ARG, "mee_publish_changed: null argument");
+    if (int rc = publish_pair_check(src, dst, "mee_publish_changed", -1)) return rc;
+    if (src->device != log->device) return fail(MEE_ERR_INVALID_ARG, "mee_publish_changed: the tables are on device %d, the change log on device %d", src->device, log->device);
+    const uint64_t end = slot_end < log->capacity ? slot_end : log->capacity;
+    const uint64_t slots = slot_begin < end ? end - slot_begin : 0;
+    DeviceGuard g(src->device);
+    hipStream_t st = as_stream(stream);
+    zero_words(d_counts_out, 4 * sizeof(uint64_t), st);
+    if (slots) {
+        ++dst->handle_epoch;   // rows are freed: slot handles handed out before this call are stale
+        const PublishTables t{src->keys, (const float4*)src->values, src->nb, dst->keys, dst->values, dst->nb, &dst->ctr->status, dst->hits};
+        const unsigned grid = grid_for(slots, 256, 1u << 16);
+        unsigned long long* counts = (unsigned long long*)d_counts_out;
+        with_row_shape(src->dim4, [&](auto d4) { with_flag(dst->bf16_rows, [&](auto bf16) {
+            publish_upsert_kernel<d4, bf16><<<grid, 256, 0, st>>>(change_set_of(log), slot_begin, end, t, src->dim4, counts);
+        }); });
+        publish_remove_kernel<<<grid, 256, 0, st>>>(change_set_of(log), slot_begin, end, t, counts);
+    }
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+int mee_group_publish_changed(const mee_group* src, const mee_changes_group* logs, mee_group* dst, uint64_t* d_counts_out, void* stream) {
+    MEE_RANGE("mee_group_publish_changed");
+    if (!src || !logs || !dst || !d_counts_out) return fail(MEE_ERR_INVALID_ARG, "mee_group_publish_changed: null argument");
+    if (src == dst) return fail(MEE_ERR_INVALID_ARG, "mee_group_publish_changed: src and dst are the same group");
+    if (src->n_tables != dst->n_tables || src->n_tables != logs->n_tables || src->dim != dst->dim || src->device != dst->device || src->device != logs->device)
+        return fail(MEE_ERR_INVALID_ARG, "mee_group_publish_changed: src, logs and dst differ in the number of tables (%u, %u, %u), dim (%u, %u) or device (%d, %d, %d)", src->n_tables,
+                    logs->n_tables, dst->n_tables, src->dim, dst->dim, src->device, logs->device, dst->device);
+    for (uint32_t j = 0; j < src->n_tables; ++j)
+        if (int rc = publish_pair_check(src->tables[j], dst->tables[j], "mee_group_publish_changed", (int)j)) return rc;
+    {   // a table that is a member twice would be probed read-only by one member's walk while another claims in it
+        std::vector<const mee_table*> all(src->tables.begin(), src->tables.end());
+        all.insert(all.end(), dst->tables.begin(), dst->tables.end());
+        std::sort(all.begin(), all.end());
+        if (std::adjacent_find(all.begin(), all.end()) != all.end())
+            return fail(MEE_ERR_INVALID_ARG, "mee_group_publish_changed: a table is a member more than once across the two groups");
+    }
+    if (int rc = group_refresh(const_cast<mee_group*>(src), stream)) return rc;   // (re-reads the planes of a member that was rehashed: a cache, not the group's value)
+    if (int rc = group_refresh(dst, stream)) return rc;
+    DeviceGuard guard(src->device);
+    hipStream_t st = as_stream(stream);
+    const uint32_t nt = src->n_tables;
+    zero_words(d_counts_out, (size_t)nt * 4 * sizeof(uint64_t), st);
+    for (mee_table* t : dst->tables) ++t->handle_epoch;
+    const unsigned grid = grid_for(logs->walk_slots, 256, 8192);
+    unsigned long long* counts = (unsigned long long*)d_counts_out;
+    with_row_shape(src->dim4, [&](auto d4) { with_flag(dst->bf16_rows, [&](auto bf16) {
+        publish_upsert_grouped_kernel<d4, bf16><<<grid, 256, 0, st>>>(logs->d_logs, logs->d_bounds, nt, src->d_move, dst->d_move, src->dim4, counts);
+    }); });
+    publish_remove_grouped_kernel<<<grid, 256, 0, st>>>(logs->d_logs, logs->d_bounds, nt, src->d_move, dst->d_move, counts);
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }

@@ -123,6 +123,18 @@ def _fp32_only(out: torch.Tensor | None, op: str) -> None:
 _PAD_KEEP = {"first": _lib.PAD_KEEP_FIRST, "last": _lib.PAD_KEEP_LAST}
 
 
+def _publish_checked(counts, who: str = "") -> tuple:
+    """the four counts of a publish, read back (upserts, removed, dropped, invalid) -> the same, or the two refusals of publish_to(check=True)"""
+    upserts, removed, dropped, invalid = (int(c) for c in counts)
+    if invalid:
+        raise RuntimeError(f"publish_to: the change log{who} is invalid — it does not name every change since it was cleared, so the serving copy may be "
+                           "stale in keys it never saw: rebuild the serving copy (serving_copy() / checkpoint.load_into) and clear() the log")
+    if dropped:
+        raise MeepoError(_lib.ERR_OUT_OF_MEMORY, f"publish_to: the serving table{who} had no room for {dropped} keys (STATUS_TABLE_FULL): they are missing "
+                                                 "there — rebuild it with a larger capacity")
+    return upserts, removed, dropped, invalid
+
+
 def keyed_layout(dims):
     """The keyed layout of a group's pooled lookup (SPEC.md §3 "Keyed output"): one row per sample, member j's pooled vector at column col_offsets[j] =
     the sum of the dims before it in the caller's order -> (col_offsets, width).  A uniform group: col_offsets[j] = j * dim."""
@@ -720,6 +732,50 @@ class LookupTable:
         self.layout_epoch += 1
         return n_moved, moved
 
+    def publish_to(self, serving: "LookupTable", check: bool = True, clear: bool = False):
+        """SPEC.md §3 "Publish": refresh the serving table `serving` from this tracked table, device to device — every key noted in the attached change
+        log that this table holds ends up in `serving` with this table's values row (bit for bit in an fp32-row table without optimizer, rounded once
+        in a bf16-row table: what serving.insert would store), every noted key this table does not hold is removed there.  A `serving` that equalled
+        this table (rounded) when the log was last cleared equals it again.  One library call (ChangeLog.publish), no [n, dim] buffer.
+        check=True: ONE read-back of the counts -> (upserts, removed, dropped) as ints; RuntimeError if the log was invalid (it does not name every
+        change), MeepoError if keys were dropped because `serving` had no room.  check=False: -> the int64 device tensor [4] (upserts, removed,
+        dropped, invalid), and nothing synchronises.  clear=True clears the log behind the publish, in stream order; the default leaves it, because
+        the same log may still owe a checkpoint.save_delta (which clears it).  Nothing is noted anywhere: `serving` must not be tracked itself.
+        An int8-row `serving` is refreshed by composition instead — iter_changed(with_state=False), serving.insert in max_batch chunks,
+        serving.remove — which synchronises once per piece of the log whatever `check` says; it returns (upserts, removed, None), and check=True
+        raises on the log's invalid word and on serving's STATUS_TABLE_FULL bit."""
+        log = self.change_log
+        if log is None:
+            raise ValueError("publish_to: this table has no change log (track_changes(capacity) first)")
+        if not isinstance(serving, LookupTable):
+            raise MeepoError(_lib.ERR_INVALID_ARG, "publish_to: serving must be a LookupTable")
+        if serving.change_log is not None:
+            raise ValueError("publish_to: the serving table is tracked itself, and a publish notes nothing in its log")
+        if serving.value_dtype == torch.int8:
+            return self._publish_composed(serving, check, clear)
+        counts = log.publish(self, serving)
+        if clear:
+            log.clear()
+        return _publish_checked(counts.tolist())[:3] if check else counts
+
+    def _publish_composed(self, serving: "LookupTable", check: bool, clear: bool):
+        """publish_to into an int8-row table: the composition the operator replaces"""
+        log = self.change_log
+        if check and log.invalid:
+            _publish_checked((0, 0, 0, 1))
+        upserts = removed = 0
+        for k, v, _, _, gone in log.iter_changed(self, with_state=False):
+            for s in range(0, k.numel(), serving.max_batch):
+                serving.insert(k[s:s + serving.max_batch], v[s:s + serving.max_batch])
+            for s in range(0, gone.numel(), serving.max_batch):
+                serving.remove(gone[s:s + serving.max_batch])
+            upserts, removed = upserts + k.numel(), removed + gone.numel()
+        if clear:
+            log.clear()
+        if check and serving.status() & _lib.STATUS_TABLE_FULL:
+            raise MeepoError(_lib.ERR_OUT_OF_MEMORY, "publish_to: the serving table had no room for some keys (STATUS_TABLE_FULL): rebuild it with a larger capacity")
+        return upserts, removed, None
+
     def find_or_insert(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
                        min_count: int | None = None, out_dtype: torch.dtype = torch.float32):
         """min_count (tables created with admission=True): an absent key is created only once the table's count-min sketch has seen it
@@ -1152,6 +1208,28 @@ class TableGroup:
                 new.import_(ek, ev)
             copies.append(new)
         return TableGroup(copies)
+
+    def publish_to(self, serving_group: "TableGroup", check: bool = True, clear: bool = False):
+        """LookupTable.publish_to for every member over the whole of its log, in ONE launch sequence whatever the number of members
+        (mee_group_publish_changed): member j of this tracked group refreshes serving_group.tables[j].  serving_group: what serving_copy() returned, or
+        a group of optimizer-less fp32 tables of the same dim.  check=True: one read-back -> a list of (upserts, removed, dropped) per member;
+        RuntimeError if a member's log was invalid, MeepoError if a member dropped keys.  check=False: -> the int64 device tensor [n_tables, 4], no
+        synchronisation.  clear=True clears every member's log behind the publish.  The first call after a reserve() of a member of either group
+        synchronises the stream once (the group re-reads that member's planes) and must not be captured."""
+        if self._change_group is None:
+            raise ValueError("publish_to: this group has no change logs (track_changes(capacity) first)")
+        if not isinstance(serving_group, TableGroup):
+            raise MeepoError(_lib.ERR_INVALID_ARG, "publish_to: serving_group must be a TableGroup")
+        if serving_group._change_group is not None or any(t.change_log is not None for t in serving_group.tables):
+            raise ValueError("publish_to: the serving group is tracked itself, and a publish notes nothing in its logs")
+        counts = torch.empty((len(self.tables), 4), dtype=torch.int64, device=self.device)
+        _lib.check(_lib.lib().mee_group_publish_changed(self._h, self._change_group._h, serving_group._h, counts.data_ptr(), _stream_ptr(self.device)))
+        for t in serving_group.tables:
+            t.layout_epoch += 1
+        if clear:
+            for log in self.change_logs:
+                log.clear()
+        return [_publish_checked(c, f" of member {j}")[:3] for j, c in enumerate(counts.tolist())] if check else counts
 
     def _check_offsets(self, offsets: torch.Tensor) -> None:
         if offsets.device != self.device or offsets.dtype not in (torch.int64, torch.uint64) or offsets.numel() != len(self.tables) + 1 \
