@@ -1,0 +1,43 @@
+"""Candidate generation on one MI355X: an item table trains, a bf16-row serving copy of it answers "which items match this user vector best" by
+an exact top-k inner-product search of the table in place, and after a publish the same search sees the new and the removed items — no [N, dim]
+matrix is ever built (run on the GPU box: python examples/retrieval.py)."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+import __graft_entry__
+
+__graft_entry__.build()
+from meepoembedding_amd import INIT_UNIFORM, OPT_ADAGRAD, LookupTable  # noqa: E402
+
+dev = torch.device("cuda", 0)
+dim, items, k = 64, 50_000, 10
+
+trainer = LookupTable(2 * items, dim, device=dev, optimizer=OPT_ADAGRAD, max_batch=1 << 16, initializer=INIT_UNIFORM, init_scale=0.1, init_seed=1)
+for step in range(5):                                           # a stand-in for training: items appear and move
+    ids = torch.randint(0, items // 2, (1 << 15,), device=dev)
+    rows, _ = trainer.find_or_insert(ids)
+    trainer.apply_adagrad(ids, 0.1 * torch.randn_like(rows), lr=0.05)
+
+trainer.track_changes(items)                                    # from here on every mutator notes its ids
+serving = LookupTable(trainer.capacity, dim, device=dev, max_batch=1 << 16, value_dtype=torch.bfloat16)
+serving.import_(*trainer.export())                              # the replica that answers: bf16 rows, equal to the trainer (rounded) NOW
+
+users = torch.randn(32, dim, device=dev)                        # the other tower's output
+keys, scores, counts = serving.search(users, k, counts=True)
+rows, found = serving.find(keys.view(-1))
+check = (users.to(torch.bfloat16).float()[:, None, :] * rows.view(32, k, dim)).sum(-1)
+assert found.all() and torch.allclose(check, scores, rtol=1e-4, atol=1e-4) and (scores[:, :-1] >= scores[:, 1:]).all()
+print(f"{serving.size()} items served; user 0's best: item {int(keys[0, 0])} at {float(scores[0, 0]):.4f}, {int(counts[0])} candidates returned")
+
+best = keys[:, 0].unique()                                      # the current winners leave the catalogue, a new item made for user 0 enters
+trainer.remove(best)
+new_id = torch.tensor([items + 7], device=dev)
+trainer.insert(new_id, users[:1] * 4)
+upserts, removed, dropped = trainer.publish_to(serving, clear=True)
+keys2, scores2 = serving.search(users, k)
+assert int(keys2[0, 0]) == items + 7 and not torch.isin(keys2, best).any()
+print(f"published {upserts} changed rows and {removed} removals; user 0's best is now item {int(keys2[0, 0])} at {float(scores2[0, 0]):.4f}; "
+      f"none of the {best.numel()} removed items is returned any more")

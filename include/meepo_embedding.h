@@ -1140,6 +1140,30 @@ int mee_publish_changed(const mee_table* src, const mee_changes* log, mee_table*
 int mee_group_publish_changed(const mee_group* src, const mee_changes_group* logs, mee_group* dst,
                               uint64_t* d_counts_out /* device, n_tables x 4 words */, void* stream);
 
+/* ---- search: the k live keys whose rows have the greatest inner product with a query (SPEC.md §3 "Search") ------------------------------------------
+ * mee_search scans the table in place — key plane and row plane once, no [N, dim] copy — and writes, for each of the n_queries rows of d_queries
+ * ([n_queries, dim] fp32 on the table's device, 16-byte aligned), the k best candidates: d_out_keys [n_queries, k] and d_out_scores [n_queries, k].
+ * score(q, key) = sum_j bf16(q_j) * bf16(row_j): both operands rounded once to bf16, ties to even (the stored bits of a bf16-row table are taken as
+ * they are), every product exact in fp32, the sum accumulated in fp32 in an unspecified order — exact whenever the products are exactly summable,
+ * otherwise within (dim - 1) * 2^-24 * sum_j |bf16(q_j) * bf16(row_j)| of their true sum.  An fp32-row table is searched at bf16 precision too: one
+ * matrix instruction per 16 columns, and the answer its bf16 replica gives.  A zero score is returned as +0.0.
+ * Candidates: every slot with a live key; tombstones and empty slots never appear; a candidate whose score is NaN is never returned.
+ * Order: greater score first; equal scores (-0.0 == +0.0) by the smaller key, signed — a function of the table's contents only, not of slots or grids.
+ * A query with fewer than k candidates has its tail filled with key INT64_MIN and score -inf; d_out_counts [n_queries] (nullable) receives the number
+ * of real entries.  d_workspace: caller-owned device memory of mee_search_workspace_bytes(t, n_queries, k) bytes, 8-byte aligned (the figure depends on
+ * the device, n_queries and k only, not on the table's capacity); two searches that may overlap need a workspace each.  Served: fp32-row tables, with or without an optimizer, and bf16-row tables.
+ * Limits, per call (anything outside is MEE_ERR_INVALID_ARG before any launch): dim % 16 == 0 and 16 <= dim <= 256; 1 <= k <= MEE_SEARCH_MAX_K;
+ * n_queries >= 1, n_queries * max(k, 8) <= MEE_SEARCH_MAX_QK, and n_queries rounded up to a multiple of 32, times dim, <= MEE_SEARCH_MAX_QUERY_ELEMS
+ * (what the scan keeps in 64 KB of LDS: the candidate buffers and the rounded queries); a larger batch is several calls over row ranges of the outputs.
+ * An int8-row table is MEE_ERR_UNSUPPORTED.  Read-only on the table, two launches, no synchronisation, no allocation, no memset: safe under stream
+ * capture; it may overlap finds and is ordered against mutators as mee_find is (stream order). */
+#define MEE_SEARCH_MAX_K 64
+#define MEE_SEARCH_MAX_QK 1536
+#define MEE_SEARCH_MAX_QUERY_ELEMS 12288
+int mee_search_workspace_bytes(const mee_table* t, size_t n_queries, uint32_t k, uint64_t* bytes_out);
+int mee_search(const mee_table* t, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
+               uint32_t* d_out_counts /* nullable */, void* d_workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

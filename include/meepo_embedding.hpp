@@ -81,6 +81,9 @@ public:
     void find_pooled_max(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t n_bags, void* d_out, uint32_t out_dtype = MEE_DTYPE_F32, uint8_t* d_found = nullptr, uint32_t* d_argmax_out = nullptr, void* stream = nullptr) const { check(mee_find_pooled_max(t_, d_keys, n, d_bag_offsets, n_bags, d_out, out_dtype, d_found, d_argmax_out, stream)); }
     // its backward: d_grads_out[i, j] = d_argmax[bag(i), j] == i ? d_bag_grads[bag(i), j] : +0.0 (feed to apply_*)
     void pooled_max_backward(size_t n, const uint64_t* d_bag_offsets, size_t n_bags, const uint32_t* d_argmax, const float* d_bag_grads, float* d_grads_out, void* stream = nullptr) const { check(mee_pooled_max_backward(t_, n, d_bag_offsets, n_bags, d_argmax, d_bag_grads, d_grads_out, stream)); }
+    // exact top-k inner-product search over the live rows (mee_search): d_out_keys / d_out_scores [n_queries, k], best first; d_workspace of search_workspace_bytes(n_queries, k) bytes
+    uint64_t search_workspace_bytes(size_t n_queries, uint32_t k) const { uint64_t b = 0; check(mee_search_workspace_bytes(t_, n_queries, k, &b)); return b; }
+    void search(const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores, uint32_t* d_out_counts, void* d_workspace, void* stream = nullptr) const { check(mee_search(t_, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream)); }
     // second-tier pass: fills only the positions an earlier find (on another table) left with d_found == 0
     void find_missing(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream = nullptr) const { check(mee_find_missing(t_, d_keys, n, d_out, d_found, stream)); }
     void insert(const int64_t* d_keys, const float* d_values, size_t n, void* stream = nullptr) { check(mee_insert(t_, d_keys, d_values, n, stream)); }

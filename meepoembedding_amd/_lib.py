@@ -30,6 +30,8 @@ FLAG_TRACK_HITS, FLAG_ADMISSION, FLAG_BF16_ROWS = 1, 2, 4   # BF16_ROWS: a servi
 TIER_COUNT_COLD, TIER_COUNT_HOT = 1, 2   # mee_find_pooled_tiered flags
 EVICT_LEAST, EVICT_RESET = 1, 2          # mee_evict flags
 PAD_KEEP_FIRST, PAD_KEEP_LAST = 0, 1     # mee_find_padded_as flags: which end of a bag longer than max_len is kept
+# mee_search's per-call limits (MEE_SEARCH_MAX_*): 1 <= k <= MAX_K, n_queries * max(k, 8) <= MAX_QK, n_queries rounded up to 32, times dim, <= MAX_QUERY_ELEMS
+SEARCH_MAX_K, SEARCH_MAX_QK, SEARCH_MAX_QUERY_ELEMS = 64, 1536, 12288
 ABI_VERSION = 2   # MEE_ABI_VERSION of include/meepo_embedding.h this loader was written against
 EMPTY_KEY = -(1 << 63)
 RECLAIMED_KEY = EMPTY_KEY + 1
@@ -291,6 +293,9 @@ PROTOTYPES = {
     # publish (src table, log, dst table, slot_begin, slot_end, counts_out [4], stream); group form (src group, log group, dst group, counts_out [n_tables][4], stream)
     "mee_publish_changed": (C.c_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
     "mee_group_publish_changed": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    # search (table, queries [n_queries, dim], n_queries, k, out_keys, out_scores, out_counts | null, workspace, stream)
+    "mee_search_workspace_bytes": (C.c_int, [_vp, _sz, _u32, C.POINTER(_u64)]),
+    "mee_search": (C.c_int, [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _NARROW_ROWS = {torch.bfloat16: "a bf16-row table (value_dtype=torch.bfloat16) is a serving table with find, find_pooled, insert, assign, ",

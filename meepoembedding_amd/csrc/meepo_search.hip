@@ -1,0 +1,371 @@
+// meepo_search.hip — exact top-k inner-product search over a table's live rows (SPEC.md §3 "Search"): "which keys match this query vector best", answered
+// by a brute-force scan of the table in place — no [N, dim] copy, never stale.  score(q, key) = sum_j bf16(q_j) * bf16(row_j), products exact, fp32 sum.
+//
+// Launches (DESIGN.md §4 "Search").
+//   scan     search_scan_kernel<KS, ROWS>, KS = dim / 16: a persistent grid of ONE-WAVE blocks, each over a contiguous range of 32-slot steps.  Per
+//            step: the 32 keys by one coalesced load (asked for one step ahead), a ballot for the live mask (a step without a live slot is skipped),
+//            the live rows straight from the row plane into the B operand of v_mfma_f32_32x32x16_bf16 — lane l holds 8 consecutive elements of row
+//            l & 31 at column 16 s + 8 (l >> 5) for k-step s: one 16-byte load of a bf16 row, two and a round-and-pack of an fp32 row; a dead lane loads
+//            nothing and feeds zeros.  The A operand — the queries, rounded once — is staged in LDS in fragment order (lane-linear 16-byte reads, no
+//            bank conflict) once per block; a row block of 32 queries is KS matrix instructions, and row blocks beyond the first reuse the step's B.
+//            The 16 accumulators of a lane are 16 queries' scores of the lane's slot.  Selection per query in LDS: the score of the current k-th best
+//            (one compare per accumulator on the hot path), its exact image and key (the contract's total order, for the rare lane that passes), a
+//            buffer of 2 max(k, 8) candidates and its counter.  Lanes that beat the threshold append by ballot ranks — a block is one wave, so there is
+//            no atomic and no barrier instruction; a full buffer is pruned to its best k by an in-wave bitonic sort, which raises the threshold.
+//            At the end the block writes its best k per query, sorted, to workspace[block][query][k].
+//   merge    search_merge_kernel, one wave per query: the running best k as one entry per lane; the heads of 64 lists are read by one load, a list
+//            whose head does not beat the current k-th is never touched, the others fold in by a bitonic merge of 128.  It writes the padded tail itself.
+// Only vector stores, no atomics, nothing of the table is written.
+//
+// The upstream snapshot has no search; the semantics are SPEC.md §3 "Search".
+#include <hip/hip_runtime.h>
+
+#include "meepo_table_int.h"
+
+namespace mee {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr uint32_t kSearchBlocksPerCU = 8;   // one-wave blocks the grid holds per CU, at most: the lists the merge reads per query
+constexpr uint32_t kSearchMinCap = 8;        // a candidate buffer holds 2 max(k, kSearchMinCap) entries
+static_assert(2 * MEE_SEARCH_MAX_K <= 128, "a prune sorts a buffer as two entries per lane");
+// the LDS of the largest call: queries (bf16) + candidates (12 B) + four words and a key per (padded) query
+static_assert(MEE_SEARCH_MAX_QUERY_ELEMS * 2 + MEE_SEARCH_MAX_QK * 2 * 12 + (MEE_SEARCH_MAX_QK / kSearchMinCap + 31) / 32 * 32 * 20 <= 65536, "the scan's LDS budget");
+
+__host__ __device__ constexpr uint32_t search_cap(uint32_t k) { return 2 * (k < kSearchMinCap ? kSearchMinCap : k); }
+
+// The order-preserving integer image of a score (never NaN here; a zero comes as +0.0): greater score <=> greater image; every image is >= 0x007FFFFF
+// (-inf), so 0 marks "no entry".
+__device__ __forceinline__ uint32_t score_image(float s) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, s);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float image_score(uint32_t m) { return __builtin_bit_cast(float, (m & 0x80000000u) ? (m ^ 0x80000000u) : ~m); }
+// the contract's total order: greater score first, equal scores by the smaller key
+__device__ __forceinline__ bool search_better(uint32_t ai, int64_t ak, uint32_t bi, int64_t bk) { return ai > bi || (ai == bi && ak < bk); }
+
+// ---- in-wave bitonic network over 64 E entries, entry idx = lane + 64 e, best first ---------------------------------------------------------------
+// One phase: the compare-exchanges of strides k2 / 2 .. 1; blocks of k2 entries come out best first where (idx & k2) == 0, worst first elsewhere.
+// k2 = 64 E alone turns a bitonic sequence into a sorted one (the merge kernel).  All 64 lanes, convergent.
+template <int E>
+__device__ __forceinline__ void bitonic_phase(uint32_t (&img)[E], int64_t (&key)[E], int lane, int k2) {
+#pragma unroll 1
+    for (int j = k2 >> 1; j >= 1; j >>= 1) {
+        if (j == 64) {   // E == 2, the last phase: the pair is the lane's own two entries, the lower index keeps the better
+            if constexpr (E == 2) {
+                if (search_better(img[1], key[1], img[0], key[0])) {
+                    const uint32_t ti = img[0]; img[0] = img[1]; img[1] = ti;
+                    const int64_t tk = key[0]; key[0] = key[1]; key[1] = tk;
+                }
+            }
+            continue;
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const int idx = lane + 64 * e;
+            const uint32_t pi = (uint32_t)__shfl_xor((int)img[e], j);
+            const int64_t pk = (int64_t)__shfl_xor((long long)key[e], j);
+            const bool keep_better = ((idx & j) == 0) == ((idx & k2) == 0);
+            if (search_better(img[e], key[e], pi, pk) != keep_better) { img[e] = pi; key[e] = pk; }   // (identical entries: either copy)
+        }
+    }
+}
+// the first n_sort entries (a power of two, 2 .. 64 E; the others must be empty) sorted best first
+template <int E>
+__device__ __forceinline__ void bitonic_sort(uint32_t (&img)[E], int64_t (&key)[E], int lane, int n_sort) {
+#pragma unroll 1
+    for (int k2 = 2; k2 <= n_sort; k2 <<= 1) bitonic_phase<E>(img, key, lane, k2);
+}
+
+// ---- the scan's selection state of one block (= one wave), in LDS ---------------------------------------------------------------------------------
+struct SearchSel {
+    int64_t* buf_key;    // [nq][cap]
+    int64_t* thr_key;    // [qp]  the k-th best entry's key and image (image 0: fewer than k entries so far) ...
+    uint32_t* buf_img;   // [nq][cap]
+    uint32_t* thr_img;   // [qp]
+    float* thr_sc;       // [qp]  ... and its score: what the hot path compares against (-inf: none yet; +inf for the padding queries past nq)
+    uint32_t* cnt;       // [qp]  entries in the buffer
+    uint32_t k, cap;
+};
+// a block is one wave: LDS traffic between its lanes needs the compiler's fence and the wave's own in-order LDS queue, no barrier instruction
+__device__ __forceinline__ void wave_lds_sync() { __syncthreads(); }
+
+// query q's buffer pruned to its best min(n, k), sorted best first; with k entries the threshold is the k-th.  q is wave-uniform.
+template <int E>
+__device__ __forceinline__ void search_prune(const SearchSel& s, uint32_t q, int lane) {
+    const uint32_t n = s.cnt[q];
+    uint32_t img[E];
+    int64_t key[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const uint32_t idx = lane + 64 * e;
+        const bool in = idx < n;
+        img[e] = in ? s.buf_img[q * s.cap + idx] : 0u;
+        key[e] = in ? s.buf_key[q * s.cap + idx] : kEmpty;
+    }
+    int n_sort = 2;
+    while ((uint32_t)n_sort < n) n_sort <<= 1;   // n <= cap <= 64 E
+    bitonic_sort<E>(img, key, lane, n_sort);
+    const uint32_t keep = n < s.k ? n : s.k;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const uint32_t idx = lane + 64 * e;
+        if (idx < keep) { s.buf_img[q * s.cap + idx] = img[e]; s.buf_key[q * s.cap + idx] = key[e]; }
+    }
+    if (n >= s.k && lane == (int)s.k - 1) {   // (k <= 64: the k-th entry is lane k - 1's first)
+        s.thr_img[q] = img[0]; s.thr_key[q] = key[0]; s.thr_sc[q] = image_score(img[0]);
+    }
+    if (lane == 0) s.cnt[q] = keep;
+    wave_lds_sync();
+}
+__device__ __forceinline__ void search_prune_any(const SearchSel& s, uint32_t q, int lane) {
+    if (s.cap > 64) search_prune<2>(s, q, lane); else search_prune<1>(s, q, lane);   // wave-uniform
+}
+
+// The lanes with `beat` append (img, key) to the buffer of their half's query q (lanes 0-31 share one query, lanes 32-63 another), in lane order, by
+// ballot ranks; a buffer that fills up is pruned, and what did not fit is tried again against the raised threshold.  All 64 lanes, convergent.
+__device__ __forceinline__ void search_append(const SearchSel& s, uint32_t q, bool beat, uint32_t img, int64_t key, int lane) {
+    const int half = lane >> 5, col = lane & 31;
+    while (true) {
+        const uint64_t m = __ballot(beat);
+        if (!m) break;   // wave-uniform
+        const uint32_t mh = (uint32_t)(m >> (32 * half));
+        const uint32_t c = mh ? s.cnt[q] : 0u;   // (a half with a candidate has q < nq)
+        const uint32_t room = s.cap - c;         // > 0: a buffer is pruned the moment it fills
+        const uint32_t rank = __popc(mh & ((1u << col) - 1u));
+        if (beat && rank < room) {
+            s.buf_img[q * s.cap + c + rank] = img;
+            s.buf_key[q * s.cap + c + rank] = key;
+            beat = false;
+        }
+        const uint32_t total = __popc(mh), taken = total < room ? total : room;
+        if (mh && col == 0) s.cnt[q] = c + taken;
+        wave_lds_sync();
+        uint64_t pm = __ballot(mh && col == 0 && c + taken >= s.cap);
+        while (pm) {   // wave-uniform: at most the two halves' queries
+            const int src = __ffsll((unsigned long long)pm) - 1;
+            pm &= pm - 1;
+            search_prune_any(s, (uint32_t)__shfl((int)q, src), lane);
+        }
+        if (beat) beat = search_better(img, key, s.thr_img[q], s.thr_key[q]);
+    }
+}
+
+// The B operand of a step: lane (half, col) holds elements [16 s + 8 half, + 8) of slot's row for k-step s, as bf16.  A dead lane loads nothing.
+template <int KS, int ROWS>
+__device__ __forceinline__ void search_load_b(const void* __restrict__ values, uint64_t slot, int half, bool live, bf16x8 (&b)[KS]) {
+    if constexpr (ROWS == kRowsBF16) {
+        const u32x4* row = reinterpret_cast<const u32x4*>(values) + slot * (uint64_t)(2 * KS) + half;   // a row is 2 KS groups of 16 bytes
+        u32x4 v[KS];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) v[s] = live ? __builtin_nontemporal_load(row + 2 * s) : u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) b[s] = __builtin_bit_cast(bf16x8, v[s]);
+    } else {
+        const f32x4* row = reinterpret_cast<const f32x4*>(values) + slot * (uint64_t)(4 * KS) + 2 * half;   // ... 4 KS groups of four floats
+        f32x4 x[KS], y[KS];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            x[s] = live ? __builtin_nontemporal_load(row + 4 * s) : f32x4{0.f, 0.f, 0.f, 0.f};
+            y[s] = live ? __builtin_nontemporal_load(row + 4 * s + 1) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const u32x4 p = {bf16x2_of(x[s].x, x[s].y), bf16x2_of(x[s].z, x[s].w), bf16x2_of(y[s].x, y[s].y), bf16x2_of(y[s].z, y[s].w)};
+            b[s] = __builtin_bit_cast(bf16x8, p);
+        }
+    }
+}
+
+// LDS (dynamic; the host computes the same sum, search_lds_bytes): A fragments [n_rb][KS][64] x 16 B | buf_key | thr_key | buf_img | thr_img | thr_sc | cnt
+template <int KS, int ROWS>
+__global__ __launch_bounds__(64) void search_scan_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
+                                                         const float* __restrict__ queries, uint32_t nq, uint32_t k, uint64_t steps_per_block,
+                                                         int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char search_lds[];
+    constexpr uint32_t dim = 16 * KS;
+    const int lane = threadIdx.x, half = lane >> 5, col = lane & 31;
+    const uint32_t n_rb = (nq + 31) / 32, qp = n_rb * 32;
+    u32x4* const afrag = reinterpret_cast<u32x4*>(search_lds);
+    SearchSel s;
+    s.k = k; s.cap = search_cap(k);
+    s.buf_key = reinterpret_cast<int64_t*>(search_lds + (size_t)qp * dim * 2);
+    s.thr_key = s.buf_key + (size_t)nq * s.cap;
+    s.buf_img = reinterpret_cast<uint32_t*>(s.thr_key + qp);
+    s.thr_img = s.buf_img + (size_t)nq * s.cap;
+    s.thr_sc = reinterpret_cast<float*>(s.thr_img + qp);
+    s.cnt = reinterpret_cast<uint32_t*>(s.thr_sc + qp);
+
+    // ---- the queries, rounded once, in fragment order: fragment (rb, ks) is 64 lanes x 16 bytes, lane (half, col) = query rb * 32 + col, elements as B's
+    for (uint32_t f = 0; f < n_rb * KS; ++f) {
+        const uint32_t q = (f / KS) * 32 + col, ks = f % KS;
+        u32x4 p = {0u, 0u, 0u, 0u};
+        if (q < nq) {
+            const f32x4* src = reinterpret_cast<const f32x4*>(queries + (size_t)q * dim + 16 * ks + 8 * half);
+            const f32x4 x = src[0], y = src[1];
+            p = u32x4{bf16x2_of(x.x, x.y), bf16x2_of(x.z, x.w), bf16x2_of(y.x, y.y), bf16x2_of(y.z, y.w)};
+        }
+        afrag[f * 64 + lane] = p;
+    }
+    for (uint32_t q = lane; q < qp; q += 64) {
+        s.thr_key[q] = kEmpty; s.thr_img[q] = 0u; s.cnt[q] = 0u;
+        s.thr_sc[q] = q < nq ? -__builtin_inff() : __builtin_inff();   // nothing beats a padding query's threshold
+    }
+    wave_lds_sync();
+
+    // ---- the block's steps: 32 consecutive slots each, the keys one step ahead
+    const uint64_t n_steps = (capacity + 31) / 32;
+    const uint64_t s0 = (uint64_t)blockIdx.x * steps_per_block, s1 = s0 + steps_per_block < n_steps ? s0 + steps_per_block : n_steps;
+    int64_t key_next = kEmpty;
+    if (s0 < s1 && s0 * 32 + col < capacity) key_next = __builtin_nontemporal_load(tkeys + s0 * 32 + col);
+    for (uint64_t step = s0; step < s1; ++step) {   // wave-uniform
+        const int64_t key = key_next;
+        const uint64_t slot = step * 32 + col;
+        key_next = kEmpty;
+        if (step + 1 < s1 && slot + 32 < capacity) key_next = __builtin_nontemporal_load(tkeys + slot + 32);   // slots at or past capacity are never addressed
+        const bool live = key > kReclaimed;
+        if (!__ballot(live)) continue;   // wave-uniform
+        bf16x8 b[KS];
+        search_load_b<KS, ROWS>(values, slot, half, live, b);
+        for (uint32_t rb = 0; rb < n_rb; ++rb) {
+            f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, afrag[(rb * KS + ks) * 64 + lane]), b[ks], acc, 0, 0, 0);
+            // accumulator r of lane (half, col): query rb * 32 + 8 (r / 4) + 4 half + r % 4 against slot col.  NaN passes no compare.
+            const uint32_t qbase = rb * 32 + 4 * half;
+            uint32_t hot = 0;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (__ballot(live && acc[r] >= s.thr_sc[qbase + 8 * (r >> 2) + (r & 3)])) hot |= 1u << r;
+            while (hot) {   // wave-uniform, rare once the thresholds have risen
+                const int r = __ffs(hot) - 1;
+                hot &= hot - 1;
+                float sc = acc[0];
+#pragma unroll
+                for (int i = 1; i < 16; ++i) sc = r == i ? acc[i] : sc;
+                sc += 0.f;   // -0.0 -> +0.0: equal scores have one image
+                const uint32_t q = qbase + 8 * (r >> 2) + (r & 3);
+                const uint32_t img = score_image(sc);
+                const bool beat = live && q < nq && sc == sc && search_better(img, key, s.thr_img[q], s.thr_key[q]);
+                search_append(s, q, beat, img, key, lane);
+            }
+        }
+    }
+
+    // ---- the block's best k per query, sorted, padded with the empty marker
+    for (uint32_t q = 0; q < nq; ++q) {   // wave-uniform
+        search_prune_any(s, q, lane);
+        const uint32_t n = s.cnt[q];
+        const size_t o = ((size_t)blockIdx.x * nq + q) * k;
+        for (uint32_t i = lane; i < k; i += 64) {
+            ws_img[o + i] = i < n ? s.buf_img[q * s.cap + i] : 0u;
+            ws_keys[o + i] = i < n ? s.buf_key[q * s.cap + i] : kEmpty;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void search_merge_kernel(const int64_t* __restrict__ ws_keys, const uint32_t* __restrict__ ws_img, uint32_t n_lists, uint32_t nq,
+                                                          uint32_t k, int64_t* __restrict__ out_keys, float* __restrict__ out_scores,
+                                                          uint32_t* __restrict__ out_counts) {
+    const uint32_t q = blockIdx.x;
+    const int lane = threadIdx.x;
+    uint32_t img[2] = {0u, 0u};            // [0]: the running best, entry `lane`, best first, empty behind the entries and at or past k
+    int64_t key[2] = {kEmpty, kEmpty};
+    uint32_t thr_i = 0u;                   // the k-th best so far (image 0: fewer than k)
+    int64_t thr_k = kEmpty;
+    for (uint32_t lb = 0; lb < n_lists; lb += 64) {   // wave-uniform
+        uint32_t hi = 0u;
+        int64_t hk = kEmpty;
+        if (lb + lane < n_lists) {
+            const size_t o = ((size_t)(lb + lane) * nq + q) * k;
+            hi = ws_img[o]; hk = ws_keys[o];
+        }
+        uint64_t m = __ballot(hi != 0u && search_better(hi, hk, thr_i, thr_k));
+        while (m) {   // wave-uniform
+            const int src = __ffsll((unsigned long long)m) - 1;
+            m &= m - 1;
+            if (!search_better((uint32_t)__shfl((int)hi, src), (int64_t)__shfl((long long)hk, src), thr_i, thr_k)) continue;   // the threshold has risen since
+            const size_t o = ((size_t)(lb + src) * nq + q) * k;
+            const uint32_t i = 63 - lane;   // the list worst first behind the running best: a bitonic sequence of 128
+            img[1] = i < k ? ws_img[o + i] : 0u;
+            key[1] = i < k ? ws_keys[o + i] : kEmpty;
+            bitonic_phase<2>(img, key, lane, 128);
+            if ((uint32_t)lane >= k) { img[0] = 0u; key[0] = kEmpty; }
+            thr_i = (uint32_t)__shfl((int)img[0], (int)k - 1);
+            thr_k = (int64_t)__shfl((long long)key[0], (int)k - 1);
+        }
+    }
+    const bool real = (uint32_t)lane < k && img[0] != 0u;
+    if ((uint32_t)lane < k) {
+        out_keys[(size_t)q * k + lane] = real ? key[0] : kEmpty;
+        out_scores[(size_t)q * k + lane] = real ? image_score(img[0]) : -__builtin_inff();
+    }
+    const uint64_t rm = __ballot(real);
+    if (out_counts && lane == 0) out_counts[q] = (uint32_t)__popcll(rm);
+}
+
+// =========================================================================================================
+// host side
+// =========================================================================================================
+static size_t search_lds_bytes(uint32_t dim, size_t nq, uint32_t k) {
+    const size_t qp = (nq + 31) / 32 * 32;
+    return qp * dim * 2 + nq * search_cap(k) * 12 + qp * 20;
+}
+// what both entry points refuse, before anything is launched; -> the blocks of the largest grid a search of this device launches
+static int search_check(const mee_table* t, size_t nq, uint32_t k, const char* name, uint32_t* max_grid) {
+    if (!t) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (t->dim % 16 || t->dim < 16 || t->dim > 256) return fail(MEE_ERR_INVALID_ARG, "%s: dim must be a multiple of 16 in [16, 256] (got %u)", name, t->dim);
+    if (k < 1 || k > MEE_SEARCH_MAX_K) return fail(MEE_ERR_INVALID_ARG, "%s: k must be in [1, %d] (got %u)", name, MEE_SEARCH_MAX_K, k);
+    const size_t kk = k < kSearchMinCap ? kSearchMinCap : k;
+    if (nq < 1 || nq > MEE_SEARCH_MAX_QK / kk || (nq + 31) / 32 * 32 * t->dim > MEE_SEARCH_MAX_QUERY_ELEMS)
+        return fail(MEE_ERR_INVALID_ARG, "%s: n_queries = %zu is outside the per-call limits for k = %u and dim = %u: n_queries >= 1, n_queries * max(k, %u) <= %d and "
+                    "n_queries rounded up to a multiple of 32, times dim, <= %d", name, nq, k, t->dim, kSearchMinCap, MEE_SEARCH_MAX_QK, MEE_SEARCH_MAX_QUERY_ELEMS);
+    if (int rc = refuse_narrow_rows(t, name, false)) return rc;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) != hipSuccess || cus <= 0) cus = 256;
+    *max_grid = (uint32_t)cus * kSearchBlocksPerCU;
+    return MEE_OK;
+}
+
+}  // namespace mee
+
+using namespace mee;
+
+extern "C" {
+
+int mee_search_workspace_bytes(const mee_table* t, size_t n_queries, uint32_t k, uint64_t* bytes_out) {
+    if (!bytes_out) return fail(MEE_ERR_INVALID_ARG, "mee_search_workspace_bytes: null argument");
+    *bytes_out = 0;
+    uint32_t max_grid = 0;
+    if (int rc = search_check(t, n_queries, k, "mee_search_workspace_bytes", &max_grid)) return rc;
+    *bytes_out = (uint64_t)max_grid * n_queries * k * 12;   // a key and an image per (block, query, rank); independent of the table's capacity
+    return MEE_OK;
+}
+
+int mee_search(const mee_table* t, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores, uint32_t* d_out_counts,
+               void* d_workspace, void* stream) {
+    MEE_RANGE("mee_search");
+    uint32_t max_grid = 0;
+    if (int rc = search_check(t, n_queries, k, "mee_search", &max_grid)) return rc;
+    if (!d_queries || !d_out_keys || !d_out_scores || !d_workspace) return fail(MEE_ERR_INVALID_ARG, "mee_search: null argument");
+    if (((uintptr_t)d_queries & 15) || ((uintptr_t)d_workspace & 7)) return fail(MEE_ERR_INVALID_ARG, "mee_search: queries must be 16-byte aligned, the workspace 8-byte aligned");
+    DeviceGuard g(t->device);
+    hipStream_t st = as_stream(stream);
+    const uint64_t n_steps = (t->capacity + 31) / 32;
+    const uint64_t per_block = (n_steps + max_grid - 1) / max_grid;
+    const uint32_t grid = (uint32_t)((n_steps + per_block - 1) / per_block);   // <= max_grid: what mee_search_workspace_bytes sized the workspace for
+    const uint32_t nq = (uint32_t)n_queries;
+    int64_t* ws_keys = (int64_t*)d_workspace;
+    uint32_t* ws_img = (uint32_t*)(ws_keys + (size_t)grid * nq * k);
+    const size_t lds = search_lds_bytes(t->dim, nq, k);
+    with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)(t->dim / 16), [&](auto ks) { with_flag(t->bf16_rows, [&](auto bf16) {
+        search_scan_kernel<ks, bf16 ? kRowsBF16 : kRowsF32><<<grid, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, k, per_block, ws_keys, ws_img);
+    }); });
+    search_merge_kernel<<<nq, 64, 0, st>>>(ws_keys, ws_img, grid, nq, k, d_out_keys, d_out_scores, d_out_counts);
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+}  // extern "C"
