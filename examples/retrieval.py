@@ -32,7 +32,15 @@ check = (users.to(torch.bfloat16).float()[:, None, :] * rows.view(32, k, dim)).s
 assert found.all() and torch.allclose(check, scores, rtol=1e-4, atol=1e-4) and (scores[:, :-1] >= scores[:, 1:]).all()
 print(f"{serving.size()} items served; user 0's best: item {int(keys[0, 0])} at {float(scores[0, 0]):.4f}, {int(counts[0])} candidates returned")
 
-best = keys[:, 0].unique()                                      # the current winners leave the catalogue, a new item made for user 0 enters
+wide, wide_scores = serving.search(users, 4 * k)                # re-ranking: a wider candidate set, mixed with ids from elsewhere (some unknown here) ...
+slate = torch.cat([wide, torch.randint(items, 2 * items, (32, k), device=dev)], dim=1)
+rescored, known = serving.score(users, slate)                   # ... scored in one launch: probe, row gather and dot product, no [32, 5k, dim] block
+assert known[:, :4 * k].all() and torch.allclose(rescored[:, :4 * k], wide_scores, rtol=1e-4, atol=1e-4)   # search's own keys score search's scores (to the bit on exactly summable data)
+assert not known[:, 4 * k:].any() and torch.isneginf(rescored[:, 4 * k:]).all()     # an id the table does not hold: -inf, found 0
+top = torch.gather(slate, 1, rescored.argsort(dim=1, descending=True)[:, :k])
+print(f"re-ranked a slate of {slate.shape[1]} ids per user ({int((~known.bool()).sum())} unknown ones scored -inf); user 0's best of it: item {int(top[0, 0])}")
+
+best = keys[:, 0].unique()                                     # the current winners leave the catalogue, a new item made for user 0 enters
 trainer.remove(best)
 new_id = torch.tensor([items + 7], device=dev)
 trainer.insert(new_id, users[:1] * 4)

@@ -1164,6 +1164,27 @@ int mee_search_workspace_bytes(const mee_table* t, size_t n_queries, uint32_t k,
 int mee_search(const mee_table* t, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
                uint32_t* d_out_counts /* nullable */, void* d_workspace, void* stream);
 
+/* ---- score: the inner products of GIVEN candidate keys with a query, probed in place (SPEC.md §3 "Score") -------------------------------------------
+ * mee_score answers "how well do these ids match this vector" — ranking and re-ranking a slate that came from mee_search, another retriever or
+ * business rules — in ONE launch that probes the index, gathers each row and reduces it against the query in registers: no [Q, C, dim] block.
+ * d_queries: [n_queries, dim] fp32 on the table's device, 16-byte aligned.  d_keys: [n_queries, n_cand] int64, row q holds query q's candidates;
+ * duplicates are allowed, within a row and across rows.  d_out_scores: [n_queries, n_cand] fp32.  d_out_found (nullable): [n_queries, n_cand]
+ * uint8, with mee_find's meaning.
+ * A live key: out[q][c] = sum_j bf16(q_j) * bf16(row_j) — exactly mee_search's score: both operands rounded once to bf16, ties to even (the stored
+ * bits of a bf16-row table are taken as they are), every product exact in fp32, the sum accumulated in fp32 in an unspecified order — exact whenever
+ * the products are exactly summable, otherwise within (dim - 1) * 2^-24 * sum_j |bf16(q_j) * bf16(row_j)| of their true sum.  A zero is returned as
+ * +0.0; a NaN score is returned as NaN (a measurement, not a selection).
+ * An absent or reserved key (key <= MEE_RECLAIMED_KEY; mee_search's padding key INT64_MIN is one): score -inf, found 0.  Hence the scores of
+ * mee_search's own output keys equal mee_search's scores: bit for bit on exactly summable data, the padded tail included, and within the sum of the
+ * two bounds otherwise.
+ * Served: fp32-row tables, with or without an optimizer, and bf16-row tables; an int8-row table is MEE_ERR_UNSUPPORTED.  dim % 16 == 0 and
+ * 16 <= dim <= 256, as mee_search; n_queries and n_cand are limited only as mee_find's n = n_queries * n_cand is; n_queries == 0 or n_cand == 0 is
+ * mee_find's n == 0 (MEE_OK, nothing launched).  A null or misaligned pointer and a bad dim are MEE_ERR_INVALID_ARG before any launch.
+ * No workspace, no host synchronisation, one launch: safe under stream capture.  Read-only on the table — hit counters are not touched — so it may
+ * overlap finds and searches and is ordered against mutators as mee_find is (stream order).  Vector stores only, no atomics. */
+int mee_score(const mee_table* t, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores,
+              uint8_t* d_out_found /* nullable */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -296,6 +296,8 @@ PROTOTYPES = {
     # search (table, queries [n_queries, dim], n_queries, k, out_keys, out_scores, out_counts | null, workspace, stream)
     "mee_search_workspace_bytes": (C.c_int, [_vp, _sz, _u32, C.POINTER(_u64)]),
     "mee_search": (C.c_int, [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _vp]),
+    # score (table, queries [n_queries, dim], n_queries, keys [n_queries, n_cand], n_cand, out_scores, out_found | null, stream)
+    "mee_score": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
 }
 
 _NARROW_ROWS = {torch.bfloat16: "a bf16-row table (value_dtype=torch.bfloat16) is a serving table with find, find_pooled, insert, assign, ",

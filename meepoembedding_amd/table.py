@@ -808,6 +808,23 @@ class LookupTable:
                                         n_real[s:s + n].data_ptr() if counts else None, ws.data_ptr(), stream))
         return (out_keys, out_scores, n_real) if counts else (out_keys, out_scores)
 
+    def score(self, queries: torch.Tensor, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None):
+        """SPEC.md §3 "Score": the inner product of each row of `queries` ([Q, dim] float32 on the table's device) with the rows of ITS candidates,
+        `keys` [Q, C] int64 — a slate from search, another retriever or business rules; duplicates allowed -> (scores [Q, C] float32, found [Q, C]
+        uint8 as find returns it).  One launch probes, gathers and reduces: no [Q, C, dim] block.  The score is search's — both operands rounded
+        once to bf16, fp32 sum — so search's own keys score search's scores; an absent or reserved key (search's INT64_MIN padding) scores -inf
+        with found 0, a NaN score is returned as NaN.  fp32-row and bf16-row tables, dim a multiple of 16 in [16, 256].  No gradient."""
+        if queries.dtype != torch.float32 or queries.device != self.device or queries.dim() != 2 or queries.shape[1] != self.dim:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"queries must be float32 [n_queries, {self.dim}] on {self.device} (got {queries.dtype} {list(queries.shape)} on {queries.device})")
+        if keys.dtype != torch.int64 or keys.device != self.device or keys.dim() != 2 or keys.shape[0] != queries.shape[0]:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"keys must be int64 [{queries.shape[0]}, n_candidates] on {self.device} (got {keys.dtype} {list(keys.shape)} on {keys.device})")
+        q, k = queries.contiguous(), keys.contiguous()
+        nq, nc = k.shape
+        out = _buffer(out, "out", torch.float32, (nq, nc), self.device)
+        found = _buffer(found, "found", torch.uint8, (nq, nc), self.device)
+        check(_lib.lib().mee_score(self._h, q.data_ptr(), nq, k.data_ptr(), nc, out.data_ptr(), found.data_ptr(), self._s()))
+        return out, found
+
     def find_or_insert(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,
                        min_count: int | None = None, out_dtype: torch.dtype = torch.float32):
         """min_count (tables created with admission=True): an absent key is created only once the table's count-min sketch has seen it
