@@ -1163,6 +1163,20 @@ int mee_group_publish_changed(const mee_group* src, const mee_changes_group* log
 int mee_search_workspace_bytes(const mee_table* t, size_t n_queries, uint32_t k, uint64_t* bytes_out);
 int mee_search(const mee_table* t, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
                uint32_t* d_out_counts /* nullable */, void* d_workspace, void* stream);
+/* mee_search_batch: mee_search's contract bit for bit — scores, candidates, order, padding, counts — for ANY 1 <= n_queries <= MEE_SEARCH_BATCH_MAX_QUERIES
+ * in one native call.  The queries are cut into tiles of at most one mee_search call's worth, the device's block budget is divided between the
+ * tiles, and a seed pass over a prefix of the slots — a uniform sample of the rows, since slot order is unrelated to row content — gives every
+ * query a threshold before the main scan starts (DESIGN.md §4 "Search", "Batched"); the answer stays a function of the table's contents only.
+ * Arguments as mee_search; d_workspace of mee_search_batch_workspace_bytes(t, n_queries, k) bytes, 8-byte aligned (device, dim, n_queries and k only:
+ * the seed area n_queries * k * 12 bytes, and the scan lists, which do not grow with n_queries beyond mee_search's largest figure and a quarter).
+ * Limits (anything outside is MEE_ERR_INVALID_ARG before any launch, as are null or misaligned pointers): dim and k as mee_search; the cap on
+ * n_queries keeps the seed area at 48 MiB for k = 64 and every product of a query index, k and a list index far inside the kernels' index arithmetic.
+ * An int8-row table is MEE_ERR_UNSUPPORTED.  Read-only on the table, four launches (two on a table too small for a seed pass), no
+ * synchronisation, no allocation, no memset, no atomics: safe under stream capture; overlap and ordering as mee_search. */
+#define MEE_SEARCH_BATCH_MAX_QUERIES 65536
+int mee_search_batch_workspace_bytes(const mee_table* t, size_t n_queries, uint32_t k, uint64_t* bytes_out);
+int mee_search_batch(const mee_table* t, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
+                     uint32_t* d_out_counts /* nullable */, void* d_workspace, void* stream);
 
 /* ---- score: the inner products of GIVEN candidate keys with a query, probed in place (SPEC.md §3 "Score") -------------------------------------------
  * mee_score answers "how well do these ids match this vector" — ranking and re-ranking a slate that came from mee_search, another retriever or

@@ -84,6 +84,9 @@ public:
     // exact top-k inner-product search over the live rows (mee_search): d_out_keys / d_out_scores [n_queries, k], best first; d_workspace of search_workspace_bytes(n_queries, k) bytes
     uint64_t search_workspace_bytes(size_t n_queries, uint32_t k) const { uint64_t b = 0; check(mee_search_workspace_bytes(t_, n_queries, k, &b)); return b; }
     void search(const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores, uint32_t* d_out_counts, void* d_workspace, void* stream = nullptr) const { check(mee_search(t_, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream)); }
+    // the same answer for any n_queries up to MEE_SEARCH_BATCH_MAX_QUERIES in one call (mee_search_batch): tiled queries, a seeded scan; d_workspace of search_batch_workspace_bytes(n_queries, k) bytes
+    uint64_t search_batch_workspace_bytes(size_t n_queries, uint32_t k) const { uint64_t b = 0; check(mee_search_batch_workspace_bytes(t_, n_queries, k, &b)); return b; }
+    void search_batch(const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores, uint32_t* d_out_counts, void* d_workspace, void* stream = nullptr) const { check(mee_search_batch(t_, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream)); }
     // the inner products of given candidate keys (mee_score): d_keys / d_out_scores / d_out_found [n_queries, n_cand]; an absent key scores -inf
     void score(const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores, uint8_t* d_out_found = nullptr, void* stream = nullptr) const { check(mee_score(t_, d_queries, n_queries, d_keys, n_cand, d_out_scores, d_out_found, stream)); }
     // second-tier pass: fills only the positions an earlier find (on another table) left with d_found == 0

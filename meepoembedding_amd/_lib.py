@@ -32,6 +32,7 @@ EVICT_LEAST, EVICT_RESET = 1, 2          # mee_evict flags
 PAD_KEEP_FIRST, PAD_KEEP_LAST = 0, 1     # mee_find_padded_as flags: which end of a bag longer than max_len is kept
 # mee_search's per-call limits (MEE_SEARCH_MAX_*): 1 <= k <= MAX_K, n_queries * max(k, 8) <= MAX_QK, n_queries rounded up to 32, times dim, <= MAX_QUERY_ELEMS
 SEARCH_MAX_K, SEARCH_MAX_QK, SEARCH_MAX_QUERY_ELEMS = 64, 1536, 12288
+SEARCH_BATCH_MAX_QUERIES = 65536   # MEE_SEARCH_BATCH_MAX_QUERIES: mee_search_batch serves any 1 <= n_queries up to it in one call
 ABI_VERSION = 2   # MEE_ABI_VERSION of include/meepo_embedding.h this loader was written against
 EMPTY_KEY = -(1 << 63)
 RECLAIMED_KEY = EMPTY_KEY + 1
@@ -296,6 +297,8 @@ PROTOTYPES = {
     # search (table, queries [n_queries, dim], n_queries, k, out_keys, out_scores, out_counts | null, workspace, stream)
     "mee_search_workspace_bytes": (C.c_int, [_vp, _sz, _u32, C.POINTER(_u64)]),
     "mee_search": (C.c_int, [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "mee_search_batch_workspace_bytes": (C.c_int, [_vp, _sz, _u32, C.POINTER(_u64)]),
+    "mee_search_batch": (C.c_int, [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _vp]),
     # score (table, queries [n_queries, dim], n_queries, keys [n_queries, n_cand], n_cand, out_scores, out_found | null, stream)
     "mee_score": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
 }

@@ -15,6 +15,10 @@
 //            At the end the block writes its best k per query, sorted, to workspace[block][query][k].
 //   merge    search_merge_kernel, one wave per query: the running best k as one entry per lane; the heads of 64 lists are read by one load, a list
 //            whose head does not beat the current k-th is never touched, the others fold in by a bitonic merge of 128.  It writes the padded tail itself.
+//   batched  mee_search_batch, any number of queries in one call: the queries in tiles of one row block, search_batch_scan_kernel — the same scan body,
+//            one (tile, step range) pair per one-wave block — first over a prefix of the slots (the seed pass), search_seed_merge_kernel for each
+//            query's best k of the prefix, then over the rest with every threshold starting at the prefix's k-th entry, and the merge above with
+//            the seed as one more list.
 // Only vector stores, no atomics, nothing of the table is written.
 //
 // The upstream snapshot has no search; the semantics are SPEC.md §3 "Search".
@@ -179,10 +183,14 @@ __device__ __forceinline__ void search_load_b(const void* __restrict__ values, u
 }
 
 // LDS (dynamic; the host computes the same sum, search_lds_bytes): A fragments [n_rb][KS][64] x 16 B | buf_key | thr_key | buf_img | thr_img | thr_sc | cnt
+// The scan of one block: `nq` queries against the steps [s0, s1) (s1 <= the table's step count); its best k per query go to rows out_row0 + q of the
+// lists.  seed_img / seed_keys: null, or the sorted best-k lists [nq][k] of slots OUTSIDE [s0, s1) — a query's thresholds then start at its k-th
+// seed entry (image 0 there: none yet) instead of at nothing, and the buffers may hold fewer than k entries while a threshold is set.
 template <int KS, int ROWS>
-__global__ __launch_bounds__(64) void search_scan_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
-                                                         const float* __restrict__ queries, uint32_t nq, uint32_t k, uint64_t steps_per_block,
-                                                         int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
+__device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
+                                                 const float* __restrict__ queries, uint32_t nq, uint32_t k, uint64_t s0, uint64_t s1,
+                                                 const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img, size_t out_row0,
+                                                 int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
     extern __shared__ __attribute__((aligned(16))) unsigned char search_lds[];
     constexpr uint32_t dim = 16 * KS;
     const int lane = threadIdx.x, half = lane >> 5, col = lane & 31;
@@ -209,14 +217,15 @@ __global__ __launch_bounds__(64) void search_scan_kernel(const int64_t* __restri
         afrag[f * 64 + lane] = p;
     }
     for (uint32_t q = lane; q < qp; q += 64) {
-        s.thr_key[q] = kEmpty; s.thr_img[q] = 0u; s.cnt[q] = 0u;
-        s.thr_sc[q] = q < nq ? -__builtin_inff() : __builtin_inff();   // nothing beats a padding query's threshold
+        uint32_t ti = 0u;
+        int64_t tk = kEmpty;
+        if (seed_img && q < nq) { ti = seed_img[(size_t)q * k + k - 1]; tk = seed_keys[(size_t)q * k + k - 1]; }
+        s.thr_key[q] = tk; s.thr_img[q] = ti; s.cnt[q] = 0u;
+        s.thr_sc[q] = q < nq ? (ti ? image_score(ti) : -__builtin_inff()) : __builtin_inff();   // nothing beats a padding query's threshold
     }
     wave_lds_sync();
 
     // ---- the block's steps: 32 consecutive slots each, the keys one step ahead
-    const uint64_t n_steps = (capacity + 31) / 32;
-    const uint64_t s0 = (uint64_t)blockIdx.x * steps_per_block, s1 = s0 + steps_per_block < n_steps ? s0 + steps_per_block : n_steps;
     int64_t key_next = kEmpty;
     if (s0 < s1 && s0 * 32 + col < capacity) key_next = __builtin_nontemporal_load(tkeys + s0 * 32 + col);
     for (uint64_t step = s0; step < s1; ++step) {   // wave-uniform
@@ -258,7 +267,7 @@ __global__ __launch_bounds__(64) void search_scan_kernel(const int64_t* __restri
     for (uint32_t q = 0; q < nq; ++q) {   // wave-uniform
         search_prune_any(s, q, lane);
         const uint32_t n = s.cnt[q];
-        const size_t o = ((size_t)blockIdx.x * nq + q) * k;
+        const size_t o = (out_row0 + q) * k;
         for (uint32_t i = lane; i < k; i += 64) {
             ws_img[o + i] = i < n ? s.buf_img[q * s.cap + i] : 0u;
             ws_keys[o + i] = i < n ? s.buf_key[q * s.cap + i] : kEmpty;
@@ -266,11 +275,37 @@ __global__ __launch_bounds__(64) void search_scan_kernel(const int64_t* __restri
     }
 }
 
-__global__ __launch_bounds__(64) void search_merge_kernel(const int64_t* __restrict__ ws_keys, const uint32_t* __restrict__ ws_img, uint32_t n_lists, uint32_t nq,
-                                                          uint32_t k, int64_t* __restrict__ out_keys, float* __restrict__ out_scores,
-                                                          uint32_t* __restrict__ out_counts) {
-    const uint32_t q = blockIdx.x;
-    const int lane = threadIdx.x;
+template <int KS, int ROWS>
+__global__ __launch_bounds__(64) void search_scan_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
+                                                         const float* __restrict__ queries, uint32_t nq, uint32_t k, uint64_t steps_per_block,
+                                                         int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
+    const uint64_t n_steps = (capacity + 31) / 32;
+    const uint64_t s0 = (uint64_t)blockIdx.x * steps_per_block, s1 = s0 + steps_per_block < n_steps ? s0 + steps_per_block : n_steps;
+    search_scan_body<KS, ROWS>(tkeys, values, capacity, queries, nq, k, s0, s1, nullptr, nullptr, (size_t)blockIdx.x * nq, ws_keys, ws_img);
+}
+
+// The batched scan (mee_search_batch): the nq_all queries are cut into n_tiles tiles of `tile` queries (the last one shorter), the steps
+// [step0, step_end) into ranges of steps_per_range; a one-wave block serves one (tile, range) pair.  The grid is flat and the tile index varies
+// fastest, so the blocks that walk one range are neighbours.  Lists: [range][nq_all][k] — a tile's block writes its own query rows of its range's
+// list, so the merge reads every query's lists at one stride whatever its tile.  seed_*: null or [nq_all][k] (search_scan_body).
+template <int KS, int ROWS>
+__global__ __launch_bounds__(64) void search_batch_scan_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
+                                                               const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
+                                                               uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
+                                                               const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
+                                                               int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
+    const uint32_t t = blockIdx.x % n_tiles, range = blockIdx.x / n_tiles;
+    const uint32_t q0 = t * tile, nq = nq_all - q0 < tile ? nq_all - q0 : tile;
+    uint64_t s0 = step0 + (uint64_t)range * steps_per_range, s1 = s0 + steps_per_range;
+    if (s1 > step_end) s1 = step_end;
+    if (s0 > s1) s0 = s1;
+    search_scan_body<KS, ROWS>(tkeys, values, capacity, queries + (size_t)q0 * (16 * KS), nq, k, s0, s1, seed_keys ? seed_keys + (size_t)q0 * k : nullptr,
+                               seed_img ? seed_img + (size_t)q0 * k : nullptr, (size_t)range * nq_all + q0, ws_keys, ws_img);
+}
+
+// Query q's best k of n_lists sorted lists, list l at [(l * nq + q) * k, + k): lane i < k ends with entry i in (img, key), image 0 behind the real ones.
+__device__ __forceinline__ void search_merge_lists(const int64_t* __restrict__ ws_keys, const uint32_t* __restrict__ ws_img, uint32_t n_lists, uint32_t nq,
+                                                   uint32_t k, uint32_t q, int lane, uint32_t& best_img, int64_t& best_key) {
     uint32_t img[2] = {0u, 0u};            // [0]: the running best, entry `lane`, best first, empty behind the entries and at or past k
     int64_t key[2] = {kEmpty, kEmpty};
     uint32_t thr_i = 0u;                   // the k-th best so far (image 0: fewer than k)
@@ -297,13 +332,38 @@ __global__ __launch_bounds__(64) void search_merge_kernel(const int64_t* __restr
             thr_k = (int64_t)__shfl((long long)key[0], (int)k - 1);
         }
     }
-    const bool real = (uint32_t)lane < k && img[0] != 0u;
+    best_img = img[0]; best_key = key[0];
+}
+
+__global__ __launch_bounds__(64) void search_merge_kernel(const int64_t* __restrict__ ws_keys, const uint32_t* __restrict__ ws_img, uint32_t n_lists, uint32_t nq,
+                                                          uint32_t k, int64_t* __restrict__ out_keys, float* __restrict__ out_scores,
+                                                          uint32_t* __restrict__ out_counts) {
+    const uint32_t q = blockIdx.x;
+    const int lane = threadIdx.x;
+    uint32_t img;
+    int64_t key;
+    search_merge_lists(ws_keys, ws_img, n_lists, nq, k, q, lane, img, key);
+    const bool real = (uint32_t)lane < k && img != 0u;
     if ((uint32_t)lane < k) {
-        out_keys[(size_t)q * k + lane] = real ? key[0] : kEmpty;
-        out_scores[(size_t)q * k + lane] = real ? image_score(img[0]) : -__builtin_inff();
+        out_keys[(size_t)q * k + lane] = real ? key : kEmpty;
+        out_scores[(size_t)q * k + lane] = real ? image_score(img) : -__builtin_inff();
     }
     const uint64_t rm = __ballot(real);
     if (out_counts && lane == 0) out_counts[q] = (uint32_t)__popcll(rm);
+}
+
+// The seed merge of the batched search: the seed pass's lists into one more list, [nq][k], sorted, padded with image 0 / the empty key.
+__global__ __launch_bounds__(64) void search_seed_merge_kernel(const int64_t* __restrict__ ws_keys, const uint32_t* __restrict__ ws_img, uint32_t n_lists,
+                                                               uint32_t nq, uint32_t k, int64_t* __restrict__ seed_keys, uint32_t* __restrict__ seed_img) {
+    const uint32_t q = blockIdx.x;
+    const int lane = threadIdx.x;
+    uint32_t img;
+    int64_t key;
+    search_merge_lists(ws_keys, ws_img, n_lists, nq, k, q, lane, img, key);
+    if ((uint32_t)lane < k) {
+        seed_img[(size_t)q * k + lane] = img;
+        seed_keys[(size_t)q * k + lane] = img != 0u ? key : kEmpty;
+    }
 }
 
 // =========================================================================================================
@@ -313,13 +373,16 @@ static size_t search_lds_bytes(uint32_t dim, size_t nq, uint32_t k) {
     const size_t qp = (nq + 31) / 32 * 32;
     return qp * dim * 2 + nq * search_cap(k) * 12 + qp * 20;
 }
-// what both entry points refuse, before anything is launched; -> the blocks of the largest grid a search of this device launches
-static int search_check(const mee_table* t, size_t nq, uint32_t k, const char* name, uint32_t* max_grid) {
+// what the entry points refuse, before anything is launched; -> the blocks of the largest grid a search of this device launches.  batch: n_queries
+// is held against mee_search_batch's cap instead of the per-call limits.
+static int search_check(const mee_table* t, size_t nq, uint32_t k, const char* name, uint32_t* max_grid, bool batch = false) {
     if (!t) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
     if (t->dim % 16 || t->dim < 16 || t->dim > 256) return fail(MEE_ERR_INVALID_ARG, "%s: dim must be a multiple of 16 in [16, 256] (got %u)", name, t->dim);
     if (k < 1 || k > MEE_SEARCH_MAX_K) return fail(MEE_ERR_INVALID_ARG, "%s: k must be in [1, %d] (got %u)", name, MEE_SEARCH_MAX_K, k);
     const size_t kk = k < kSearchMinCap ? kSearchMinCap : k;
-    if (nq < 1 || nq > MEE_SEARCH_MAX_QK / kk || (nq + 31) / 32 * 32 * t->dim > MEE_SEARCH_MAX_QUERY_ELEMS)
+    if (batch && (nq < 1 || nq > MEE_SEARCH_BATCH_MAX_QUERIES))
+        return fail(MEE_ERR_INVALID_ARG, "%s: n_queries must be in [1, %d] (got %zu)", name, MEE_SEARCH_BATCH_MAX_QUERIES, nq);
+    if (!batch && (nq < 1 || nq > MEE_SEARCH_MAX_QK / kk || (nq + 31) / 32 * 32 * t->dim > MEE_SEARCH_MAX_QUERY_ELEMS))
         return fail(MEE_ERR_INVALID_ARG, "%s: n_queries = %zu is outside the per-call limits for k = %u and dim = %u: n_queries >= 1, n_queries * max(k, %u) <= %d and "
                     "n_queries rounded up to a multiple of 32, times dim, <= %d", name, nq, k, t->dim, kSearchMinCap, MEE_SEARCH_MAX_QK, MEE_SEARCH_MAX_QUERY_ELEMS);
     if (int rc = refuse_narrow_rows(t, name, false)) return rc;
@@ -327,6 +390,54 @@ static int search_check(const mee_table* t, size_t nq, uint32_t k, const char* n
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) != hipSuccess || cus <= 0) cus = 256;
     *max_grid = (uint32_t)cus * kSearchBlocksPerCU;
     return MEE_OK;
+}
+
+// ---- the batched search's launch plan (DESIGN.md §4 "Search", "Batched") --------------------------------------------------------------------------
+// The three tuning constants can be set at build time (-D) for the measurements of profiles/search.md; the values here are the ones kept.
+#ifndef MEE_SEARCH_SEED_DIV
+#define MEE_SEARCH_SEED_DIV 32
+#endif
+#ifndef MEE_SEARCH_TILE_MAX_QUERIES
+#define MEE_SEARCH_TILE_MAX_QUERIES 32
+#endif
+constexpr uint32_t kSearchSeedDiv = MEE_SEARCH_SEED_DIV;                 // the seed pass scans the first n_steps / kSearchSeedDiv steps
+constexpr uint32_t kSearchSeedMinSteps = 64;                             // ... unless that is fewer steps than this: such a table has no seed pass
+constexpr uint32_t kSearchSeedGridDiv = 4;                               // the seed pass's share of the block budget
+constexpr uint32_t kSearchTileMaxQueries = MEE_SEARCH_TILE_MAX_QUERIES;  // a tile is at most one row block of 32 queries (MEE_SEARCH_MAX_QK: no cap)
+
+// The queries of one tile: at most what one mee_search call accepts for this k and dim, so a block's LDS stays inside search_lds_bytes' budget, and
+// at most one row block — a fraction of that LDS, so more waves stay resident; measured against tiles at the per-call limit in profiles/search.md.
+static uint32_t search_batch_tile(uint32_t dim, uint32_t k) {
+    const uint32_t by_qk = MEE_SEARCH_MAX_QK / (k < kSearchMinCap ? kSearchMinCap : k), by_elems = MEE_SEARCH_MAX_QUERY_ELEMS / dim / 32 * 32;
+    const uint32_t limit = by_qk < by_elems ? by_qk : by_elems;
+    return limit < kSearchTileMaxQueries ? limit : kSearchTileMaxQueries;
+}
+
+struct SearchBatchPlan {
+    uint32_t tile, n_tiles;
+    uint32_t ranges, seed_ranges;   // lists per query of the main scan / of the seed pass (0: no seed pass); with a table's step count the actual
+                                    // figures, without one (n_steps == UINT64_MAX) the largest any table gives: what the workspace is sized for
+    uint64_t seed_steps, per_range, per_seed_range;
+    uint64_t lists() const { return 1 + (uint64_t)ranges + seed_ranges; }   // list 0 is the seed area
+};
+static SearchBatchPlan search_batch_plan(uint32_t dim, uint32_t nq, uint32_t k, uint32_t max_grid, uint64_t n_steps) {
+    SearchBatchPlan p{};
+    p.tile = search_batch_tile(dim, k);
+    p.n_tiles = (nq + p.tile - 1) / p.tile;
+    p.ranges = max_grid / p.n_tiles > 1 ? max_grid / p.n_tiles : 1;   // the block budget divided between the tiles
+    p.seed_ranges = max_grid / kSearchSeedGridDiv / p.n_tiles > 1 ? max_grid / kSearchSeedGridDiv / p.n_tiles : 1;
+    if (n_steps == UINT64_MAX) return p;
+    p.seed_steps = n_steps / kSearchSeedDiv >= kSearchSeedMinSteps ? n_steps / kSearchSeedDiv : 0;
+    const uint64_t main_steps = n_steps - p.seed_steps;
+    p.per_range = main_steps > p.ranges ? (main_steps + p.ranges - 1) / p.ranges : 1;
+    p.ranges = main_steps > p.per_range ? (uint32_t)((main_steps + p.per_range - 1) / p.per_range) : 1;
+    if (p.seed_steps) {
+        p.per_seed_range = (p.seed_steps + p.seed_ranges - 1) / p.seed_ranges;
+        p.seed_ranges = (uint32_t)((p.seed_steps + p.per_seed_range - 1) / p.per_seed_range);
+    } else {
+        p.seed_ranges = 0;
+    }
+    return p;
 }
 
 }  // namespace mee
@@ -364,6 +475,52 @@ int mee_search(const mee_table* t, const float* d_queries, size_t n_queries, uin
         search_scan_kernel<ks, bf16 ? kRowsBF16 : kRowsF32><<<grid, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, k, per_block, ws_keys, ws_img);
     }); });
     search_merge_kernel<<<nq, 64, 0, st>>>(ws_keys, ws_img, grid, nq, k, d_out_keys, d_out_scores, d_out_counts);
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
+int mee_search_batch_workspace_bytes(const mee_table* t, size_t n_queries, uint32_t k, uint64_t* bytes_out) {
+    if (!bytes_out) return fail(MEE_ERR_INVALID_ARG, "mee_search_batch_workspace_bytes: null argument");
+    *bytes_out = 0;
+    uint32_t max_grid = 0;
+    if (int rc = search_check(t, n_queries, k, "mee_search_batch_workspace_bytes", &max_grid, true)) return rc;
+    // the seed area, the main lists and the seed pass's lists, each [n_queries][k] keys and images; the layout needs no padding
+    *bytes_out = search_batch_plan(t->dim, (uint32_t)n_queries, k, max_grid, UINT64_MAX).lists() * n_queries * k * 12;
+    return MEE_OK;
+}
+
+int mee_search_batch(const mee_table* t, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
+                     uint32_t* d_out_counts, void* d_workspace, void* stream) {
+    MEE_RANGE("mee_search_batch");
+    uint32_t max_grid = 0;
+    if (int rc = search_check(t, n_queries, k, "mee_search_batch", &max_grid, true)) return rc;
+    if (!d_queries || !d_out_keys || !d_out_scores || !d_workspace) return fail(MEE_ERR_INVALID_ARG, "mee_search_batch: null argument");
+    if (((uintptr_t)d_queries & 15) || ((uintptr_t)d_workspace & 7)) return fail(MEE_ERR_INVALID_ARG, "mee_search_batch: queries must be 16-byte aligned, the workspace 8-byte aligned");
+    DeviceGuard g(t->device);
+    hipStream_t st = as_stream(stream);
+    const uint32_t nq = (uint32_t)n_queries;
+    const uint64_t n_steps = (t->capacity + 31) / 32;
+    const SearchBatchPlan p = search_batch_plan(t->dim, nq, k, max_grid, n_steps);
+    // lists of [nq][k] entries: 0 the seed area, 1 .. ranges the main scan's, then the seed pass's; the key plane of all lists, then the image plane
+    const size_t list = (size_t)nq * k;
+    int64_t* ws_keys = (int64_t*)d_workspace;
+    uint32_t* ws_img = (uint32_t*)(ws_keys + p.lists() * list);
+    const size_t lds = search_lds_bytes(t->dim, p.tile < nq ? p.tile : nq, k);
+    const bool seeded = p.seed_ranges != 0;
+    with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)(t->dim / 16), [&](auto ks) { with_flag(t->bf16_rows, [&](auto bf16) {
+        auto scan = search_batch_scan_kernel<ks, bf16 ? kRowsBF16 : kRowsF32>;
+        if (seeded) {
+            const size_t so = (1 + (size_t)p.ranges) * list;
+            scan<<<p.n_tiles * p.seed_ranges, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, 0, p.seed_steps, p.per_seed_range,
+                                                             nullptr, nullptr, ws_keys + so, ws_img + so);
+            search_seed_merge_kernel<<<nq, 64, 0, st>>>(ws_keys + so, ws_img + so, p.seed_ranges, nq, k, ws_keys, ws_img);
+        }
+        scan<<<p.n_tiles * p.ranges, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, p.seed_steps, n_steps, p.per_range,
+                                                    seeded ? ws_keys : nullptr, seeded ? ws_img : nullptr, ws_keys + list, ws_img + list);
+    }); });
+    // the seed area is one more list in front of the main scan's: the prefix is not scanned again
+    if (seeded) search_merge_kernel<<<nq, 64, 0, st>>>(ws_keys, ws_img, 1 + p.ranges, nq, k, d_out_keys, d_out_scores, d_out_counts);
+    else search_merge_kernel<<<nq, 64, 0, st>>>(ws_keys + list, ws_img + list, p.ranges, nq, k, d_out_keys, d_out_scores, d_out_counts);
     MEE_HIP(hipGetLastError());
     return MEE_OK;
 }

@@ -782,7 +782,8 @@ class LookupTable:
         by the smaller key; counts=True adds the number of real entries per query ([Q] int32).  Both operands are rounded once to bf16 (an
         fp32-row table is searched at bf16 precision), the sum is fp32.  A query with fewer than k candidates is padded with key INT64_MIN and
         score -inf; a candidate with a NaN score is never returned.  fp32-row and bf16-row tables, dim a multiple of 16 in [16, 256], k in
-        [1, SEARCH_MAX_K]; a batch beyond the library's per-call limits is several calls over row ranges of the outputs.  The workspace is a
+        [1, SEARCH_MAX_K]; a batch beyond mee_search's per-call limits is ONE mee_search_batch call (tiled queries, a seeded scan; chunks of
+        SEARCH_BATCH_MAX_QUERIES beyond that cap) with the same answer.  The workspace is a
         tensor cached by size, one per stream that searched (the native calls of one search share it in stream order).  No gradient."""
         if queries.dtype != torch.float32 or queries.device != self.device or queries.dim() != 2 or queries.shape[1] != self.dim:
             raise MeepoError(_lib.ERR_INVALID_ARG, f"queries must be float32 [n_queries, {self.dim}] on {self.device} (got {queries.dtype} {list(queries.shape)} on {queries.device})")
@@ -792,7 +793,12 @@ class LookupTable:
         nq = q.shape[0]
         per_call = min(_lib.SEARCH_MAX_QK // max(k, 8), max(_lib.SEARCH_MAX_QUERY_ELEMS // max(self.dim, 1) // 32 * 32, 1))
         need = C.c_uint64()
-        check(_lib.lib().mee_search_workspace_bytes(self._h, min(max(nq, 1), per_call), k, C.byref(need)))   # (every refusal of the table comes from here, before any launch)
+        batched = nq > per_call   # past one call's limits: mee_search_batch, tiled and seeded, in chunks of its own cap
+        if batched:
+            per_call = _lib.SEARCH_BATCH_MAX_QUERIES
+            check(_lib.lib().mee_search_batch_workspace_bytes(self._h, min(nq, per_call), k, C.byref(need)))
+        else:
+            check(_lib.lib().mee_search_workspace_bytes(self._h, max(nq, 1), k, C.byref(need)))   # (every refusal of the table comes from here, before any launch)
         out_keys = _buffer(out_keys, "out_keys", torch.int64, (nq, k), self.device)
         out_scores = _buffer(out_scores, "out_scores", torch.float32, (nq, k), self.device)
         n_real = torch.empty(nq, dtype=torch.int32, device=self.device) if counts else None
@@ -802,10 +808,11 @@ class LookupTable:
         if ws is None or ws.numel() < need.value:
             ws = cache[stream] = torch.empty(need.value, dtype=torch.uint8, device=self.device)
         ok, osc = out_keys.view(nq, k), out_scores.view(nq, k)
+        call = _lib.lib().mee_search_batch if batched else _lib.lib().mee_search
         for s in range(0, nq, per_call):
             n = min(per_call, nq - s)
-            check(_lib.lib().mee_search(self._h, q[s:s + n].data_ptr(), n, k, ok[s:s + n].data_ptr(), osc[s:s + n].data_ptr(),
-                                        n_real[s:s + n].data_ptr() if counts else None, ws.data_ptr(), stream))
+            check(call(self._h, q[s:s + n].data_ptr(), n, k, ok[s:s + n].data_ptr(), osc[s:s + n].data_ptr(),
+                       n_real[s:s + n].data_ptr() if counts else None, ws.data_ptr(), stream))
         return (out_keys, out_scores, n_real) if counts else (out_keys, out_scores)
 
     def score(self, queries: torch.Tensor, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None):

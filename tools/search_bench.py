@@ -2,12 +2,17 @@
 
 Per shape the two paths take turns inside ONE timing loop, in chunks of 5 calls between device events; the whole sequence runs twice and the spread of
 a row is its pass-to-pass difference (the method of profiles/int8_rows.md).
-    search            table.search(queries, k): the scan of the table in place and the merge, chunked by the per-call limits where Q * k asks for it
+    search            table.search(queries, k): one mee_search call inside the per-call limits, one mee_search_batch call (tiled queries, seed pass,
+                      seeded main scan, merge) past them
+    NAME              --libs NAME=PATH,…: the same table searched through ANOTHER build of the library, loaded beside this one — the parent commit's
+                      (no mee_search_batch: the batch is split into mee_search calls by the per-call limits, as its Python layer did) or a build of
+                      this tree with another seed divisor or tile rule (-DMEE_SEARCH_SEED_DIV=…, -DMEE_SEARCH_TILE_MAX_QUERIES=32)
     matmul + topk     on a PREBUILT [N, dim] bf16 matrix of the same table: queries.bfloat16() @ M.T, torch.topk, keys[positions]
     refresh           building that matrix — export() and the cast to bf16 — timed once and reported apart: the cost the matrix path pays after every
                       publish, and the second copy of the table it keeps
-usage: python tools/search_bench.py [--keys N] [--dim D] [--reps K] [--queries 1,32,128] [--ks 10,64]"""
+usage: python tools/search_bench.py [--keys N] [--dim D] [--reps K] [--queries 1,32,128,1024] [--ks 10,64] [--libs parent=PATH,…] [--no-matmul]"""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -16,14 +21,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 import bench
-from meepoembedding_amd import LookupTable, synth
+from meepoembedding_amd import LookupTable, _lib, synth
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--keys", type=int, default=10_000_000)
 ap.add_argument("--dim", type=int, default=64)
 ap.add_argument("--reps", type=int, default=20)
-ap.add_argument("--queries", default="1,32,128")
+ap.add_argument("--queries", default="1,32,128,1024")
 ap.add_argument("--ks", default="10,64", help="one Q and one k: a shape on its own for `rocprofv3 --kernel-trace --stats`, which times the scan and the merge apart")
+ap.add_argument("--libs", default="", help="NAME=PATH,…: other builds of the library, each a row of its own")
+ap.add_argument("--no-matmul", action="store_true", help="leave the matrix path out (a kernel trace of the search alone)")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -48,6 +55,39 @@ def timed_rows(rows, reps, chunk=5):
     return {nm: total[nm] / (reps // chunk * chunk) for nm in names}
 
 
+def per_call_limit(k):
+    return min(_lib.SEARCH_MAX_QK // max(k, 8), _lib.SEARCH_MAX_QUERY_ELEMS // args.dim // 32 * 32)
+
+
+def other_build(path):
+    """-> search(t, queries, k) through the library at `path`, on the handle of this process's table (the table layout is the same in every build named
+    above): its mee_search_batch past the per-call limits if it has one, split mee_search calls otherwise; buffers and workspace allocated once"""
+    L = C.CDLL(path)
+    names = [nm for nm in _lib.PROTOTYPES if nm.startswith("mee_search") and hasattr(L, nm)]
+    for nm in names:
+        getattr(L, nm).restype, getattr(L, nm).argtypes = _lib.PROTOTYPES[nm]
+    held = {}
+
+    def search(t, queries, k):
+        nq, step = queries.shape[0], per_call_limit(k)
+        batched = nq > step and "mee_search_batch" in names
+        if batched:
+            step = _lib.SEARCH_BATCH_MAX_QUERIES
+        if (nq, k) not in held:
+            need = C.c_uint64()
+            _lib.check((L.mee_search_batch_workspace_bytes if batched else L.mee_search_workspace_bytes)(t._h, min(nq, step), k, C.byref(need)))
+            held.clear()
+            held[nq, k] = (torch.empty(nq, k, dtype=torch.int64, device=dev), torch.empty(nq, k, device=dev), torch.empty(need.value, dtype=torch.uint8, device=dev))
+        ok, osc, ws = held[nq, k]
+        for s in range(0, nq, step):
+            n = min(step, nq - s)
+            _lib.check((L.mee_search_batch if batched else L.mee_search)(t._h, queries[s:s + n].data_ptr(), n, k, ok[s:s + n].data_ptr(), osc[s:s + n].data_ptr(),
+                                                                         None, ws.data_ptr(), None))
+        return ok, osc
+    return search
+
+
+others = {nm: other_build(path) for nm, path in (x.split("=") for x in args.libs.split(",") if x)}
 results = []
 for value_dtype in (torch.float32, torch.bfloat16):
     t = LookupTable(int(args.keys / 0.75), args.dim, device=dev, max_batch=1 << 21, value_dtype=value_dtype)
@@ -72,15 +112,23 @@ for value_dtype in (torch.float32, torch.bfloat16):
 
             got = t.search(queries, k)[0]
             same = float((got == matmul_topk()).float().mean())   # (bf16 scores of the matrix path round differently: near-ties may swap)
-            rows = {"search": lambda: t.search(queries, k), "matmul + topk": matmul_topk}
+            rows = {"search": lambda: t.search(queries, k)}
+            if not args.no_matmul:
+                rows["matmul + topk"] = matmul_topk
+            for nm, fn in others.items():
+                rows[nm] = lambda fn=fn: fn(t, queries, k)
+                assert torch.equal(fn(t, queries, k)[0], got), f"{nm} and this tree's search disagree"   # exact by contract, whatever the build
             passes = [timed_rows(rows, args.reps) for _ in range(2)]
             us = {nm: (passes[0][nm] + passes[1][nm]) / 2 for nm in rows}
-            per_call = min(1536 // max(k, 8), 12288 // args.dim // 32 * 32)
-            calls = -(-nq // per_call)
-            rec = {"rows": str(value_dtype).split(".")[1], "keys": n, "dim": args.dim, "Q": nq, "k": k, "native_calls": calls,
+            # this tree: one call either way; past the limits every tile's blocks ask for the table (tiles that walk one range may meet in L2), in
+            # four launches.  A build without the batch entry point: `split` calls of two launches, each a scan of the table.
+            split = -(-nq // per_call_limit(k))
+            tiles = -(-nq // min(per_call_limit(k), 32)) if nq > per_call_limit(k) else 1   # search_batch_tile: one row block at the most
+            rec = {"rows": str(value_dtype).split(".")[1], "keys": n, "dim": args.dim, "Q": nq, "k": k, "native_calls": 1, "launches": 4 if tiles > 1 else 2,
+                   "tiles": tiles, "split_native_calls": split, "split_launches": 2 * split,
                    "us": {nm: round(v, 1) for nm, v in us.items()}, "spread_us": {nm: round(abs(passes[0][nm] - passes[1][nm]), 1) for nm in rows},
-                   "search_bytes": calls * scan_bytes, "matmul_bytes": n * args.dim * 2 + 2 * nq * n * 2,
-                   "search_fraction_of_8TBs": round(calls * scan_bytes / (us["search"] * 1e-6) / PEAK, 3), "refresh_us": round(refresh_us, 1),
+                   "search_bytes": tiles * scan_bytes, "split_bytes": split * scan_bytes, "matmul_bytes": n * args.dim * 2 + 2 * nq * n * 2,
+                   "search_fraction_of_8TBs": round(tiles * scan_bytes / (us["search"] * 1e-6) / PEAK, 3), "refresh_us": round(refresh_us, 1),
                    "refresh_extra_bytes": n * args.dim * 2, "keys_equal_fraction": round(same, 4)}
             print("SEARCH_BENCH " + json.dumps(rec), flush=True)
             results.append(rec)
