@@ -40,6 +40,13 @@ assert not known[:, 4 * k:].any() and torch.isneginf(rescored[:, 4 * k:]).all() 
 top = torch.gather(slate, 1, rescored.argsort(dim=1, descending=True)[:, :k])
 print(f"re-ranked a slate of {slate.shape[1]} ids per user ({int((~known.bool()).sum())} unknown ones scored -inf); user 0's best of it: item {int(top[0, 0])}")
 
+seeds = keys[:4, 0].contiguous()                                # item to item: "items similar to these", asked in cosine — the norms of a trained table's
+seed_rows, _ = serving.find(seeds)                              # rows are very unequal, and the table cannot be normalised without a second copy of it
+near, cos = serving.search(seed_rows, k, metric="cosine")       # both norms are taken inside the scan, from the row bytes it reads anyway
+again, known = serving.score(seed_rows, near, metric="cosine")  # the same four fp32 operations on the same operands
+assert (near[:, 0] == seeds).all() and torch.allclose(cos[:, 0], torch.ones(4, device=dev), atol=1e-5) and known.all() and torch.allclose(again, cos, atol=1e-5)
+print(f"item {int(seeds[0])}'s nearest other item by cosine: item {int(near[0, 1])} at {float(cos[0, 1]):.4f}")
+
 best = keys[:, 0].unique()                                     # the current winners leave the catalogue, a new item made for user 0 enters
 trainer.remove(best)
 new_id = torch.tensor([items + 7], device=dev)

@@ -1199,6 +1199,26 @@ int mee_search_batch(const mee_table* t, const float* d_queries, size_t n_querie
 int mee_score(const mee_table* t, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores,
               uint8_t* d_out_found /* nullable */, void* stream);
 
+/* ---- metric: search and score by cosine instead of the inner product (SPEC.md §3 "Search" / "Score", "Metric") -------------------------------------
+ * MEE_METRIC_IP is the score of mee_search / mee_score, unchanged in every bit: the three entry points forward to mee_search_batch_workspace_bytes,
+ * mee_search_batch and mee_score.  MEE_METRIC_COSINE: with dot = sum_j bf16(q_j) * bf16(row_j), rr = sum_j bf16(row_j)^2 and
+ * qq = sum_j bf16(q_j)^2 — operands rounded once as above, every product exact, each sum fp32 in an unspecified order —
+ *     cos(q, key) = dot / (sqrtf(qq) * sqrtf(rr)),
+ * four fp32 operations, each correctly rounded, none contracted; a zero is returned as +0.0, an infinite quotient as such.  The norms are computed
+ * inside the scan from the row bytes it reads anyway: no normalised copy of the table exists, so the answer is never stale.  A zero row or a zero
+ * query gives 0 / 0 = NaN: mee_search_metric never returns such a candidate (a zero query has count 0 and an all-padding answer), mee_score_metric
+ * returns the NaN with found 1.  Where the three sums are exactly summable the score is determined bit for bit; otherwise, to first order,
+ *     |computed - true| <= (dim - 1) 2^-24 sum_j |p_j| / (|q| |row|) + (dim + 3) 2^-24 |cos|.
+ * Everything else — candidates, the total order, padding, counts, limits (mee_search_metric: mee_search_batch's, 1 <= n_queries <=
+ * MEE_SEARCH_BATCH_MAX_QUERIES), refusals, workspace rules, stream capture, read-only, no atomics — is mee_search_batch's and mee_score's contract.
+ * An unknown metric is MEE_ERR_INVALID_ARG before any launch. */
+enum { MEE_METRIC_IP = 0, MEE_METRIC_COSINE = 1 };
+int mee_search_metric_workspace_bytes(const mee_table* t, int metric, size_t n_queries, uint32_t k, uint64_t* bytes_out);
+int mee_search_metric(const mee_table* t, int metric, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
+                      uint32_t* d_out_counts /* nullable */, void* d_workspace, void* stream);
+int mee_score_metric(const mee_table* t, int metric, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand,
+                     float* d_out_scores, uint8_t* d_out_found /* nullable */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

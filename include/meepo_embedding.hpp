@@ -89,6 +89,10 @@ public:
     void search_batch(const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores, uint32_t* d_out_counts, void* d_workspace, void* stream = nullptr) const { check(mee_search_batch(t_, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream)); }
     // the inner products of given candidate keys (mee_score): d_keys / d_out_scores / d_out_found [n_queries, n_cand]; an absent key scores -inf
     void score(const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores, uint8_t* d_out_found = nullptr, void* stream = nullptr) const { check(mee_score(t_, d_queries, n_queries, d_keys, n_cand, d_out_scores, d_out_found, stream)); }
+    // search and score under a metric (MEE_METRIC_IP: the calls above; MEE_METRIC_COSINE: dot / (|q| |row|), the norms computed in the scan); arguments as search_batch / score
+    uint64_t search_metric_workspace_bytes(int metric, size_t n_queries, uint32_t k) const { uint64_t b = 0; check(mee_search_metric_workspace_bytes(t_, metric, n_queries, k, &b)); return b; }
+    void search_metric(int metric, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores, uint32_t* d_out_counts, void* d_workspace, void* stream = nullptr) const { check(mee_search_metric(t_, metric, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream)); }
+    void score_metric(int metric, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores, uint8_t* d_out_found = nullptr, void* stream = nullptr) const { check(mee_score_metric(t_, metric, d_queries, n_queries, d_keys, n_cand, d_out_scores, d_out_found, stream)); }
     // second-tier pass: fills only the positions an earlier find (on another table) left with d_found == 0
     void find_missing(const int64_t* d_keys, size_t n, float* d_out, uint8_t* d_found, void* stream = nullptr) const { check(mee_find_missing(t_, d_keys, n, d_out, d_found, stream)); }
     void insert(const int64_t* d_keys, const float* d_values, size_t n, void* stream = nullptr) { check(mee_insert(t_, d_keys, d_values, n, stream)); }

@@ -33,6 +33,8 @@ PAD_KEEP_FIRST, PAD_KEEP_LAST = 0, 1     # mee_find_padded_as flags: which end o
 # mee_search's per-call limits (MEE_SEARCH_MAX_*): 1 <= k <= MAX_K, n_queries * max(k, 8) <= MAX_QK, n_queries rounded up to 32, times dim, <= MAX_QUERY_ELEMS
 SEARCH_MAX_K, SEARCH_MAX_QK, SEARCH_MAX_QUERY_ELEMS = 64, 1536, 12288
 SEARCH_BATCH_MAX_QUERIES = 65536   # MEE_SEARCH_BATCH_MAX_QUERIES: mee_search_batch serves any 1 <= n_queries up to it in one call
+METRIC_IP, METRIC_COSINE = 0, 1     # MEE_METRIC_*: what mee_search_metric / mee_score_metric rank by
+METRICS = {"ip": METRIC_IP, "cosine": METRIC_COSINE}   # the names LookupTable.search / score take
 ABI_VERSION = 2   # MEE_ABI_VERSION of include/meepo_embedding.h this loader was written against
 EMPTY_KEY = -(1 << 63)
 RECLAIMED_KEY = EMPTY_KEY + 1
@@ -301,6 +303,9 @@ PROTOTYPES = {
     "mee_search_batch": (C.c_int, [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _vp]),
     # score (table, queries [n_queries, dim], n_queries, keys [n_queries, n_cand], n_cand, out_scores, out_found | null, stream)
     "mee_score": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "mee_search_metric_workspace_bytes": (C.c_int, [_vp, C.c_int, _sz, _u32, C.POINTER(_u64)]),
+    "mee_search_metric": (C.c_int, [_vp, C.c_int, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "mee_score_metric": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
 }
 
 _NARROW_ROWS = {torch.bfloat16: "a bf16-row table (value_dtype=torch.bfloat16) is a serving table with find, find_pooled, insert, assign, ",

@@ -12,6 +12,8 @@
 //            a bf16 group is taken verbatim.  A lane whose last group lies past the row (dim not a multiple of 64) loads an address inside the row
 //            instead — the load stays unconditional — and feeds zeros on both sides.
 //   dot      one fp32 accumulator per key, fma of the rounded values (every product is exact), then the tile's 16 lanes by xor 8 / 4 / 2 / 1.
+//   cosine   score_kernel<.., MEE_METRIC_COSINE> (mee_score_metric): a second accumulator per key, the row's squares, beside the dot product and through
+//            the same shuffles; the query's squares once per unit from the kept values; then search's four operations, dot / (sqrtf(qq) * sqrtf(rr)).
 //   stores   the 4R scores of a step reach lanes 0 .. 4R - 1 by shuffle and leave as one coalesced store, the found bytes likewise.
 // Only vector stores, no atomics, no LDS, nothing of the table is written (hit counters included).
 //
@@ -54,7 +56,13 @@ __device__ __forceinline__ void score_load_rows(const typename RowType<ROWS>::Gr
     }
 }
 
-template <int C4, int ROWS>
+// the sum over a 16-lane tile, in every lane of it
+__device__ __forceinline__ float score_tile_sum(float a) {
+    a += __shfl_xor(a, 8); a += __shfl_xor(a, 4); a += __shfl_xor(a, 2); a += __shfl_xor(a, 1);   // (stays inside the 16-lane tile)
+    return a;
+}
+
+template <int C4, int ROWS, int METRIC>
 __global__ __launch_bounds__(kScoreWaves * 64) void score_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t nb, uint32_t dim4,
                                                                  const f32x4* __restrict__ queries, const int64_t* __restrict__ keys, uint64_t n_cand, uint64_t span,
                                                                  uint64_t spans_per_query, uint64_t n_units, float* __restrict__ out, uint8_t* __restrict__ found) {
@@ -77,6 +85,16 @@ __global__ __launch_bounds__(kScoreWaves * 64) void score_kernel(const int64_t* 
             qv[c] = widen_bf16x4(bf16x4_of(x.x, x.y, x.z, x.w));
         }
         if (!last_live) qv[C4 - 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        [[maybe_unused]] float qn = 0.f;   // cosine: the query's norm, from the rounded values every tile holds
+        if constexpr (METRIC == MEE_METRIC_COSINE) {
+            float qq = 0.f;
+#pragma unroll
+            for (int c = 0; c < C4; ++c) {
+                qq = __builtin_fmaf(qv[c].x, qv[c].x, qq); qq = __builtin_fmaf(qv[c].y, qv[c].y, qq);
+                qq = __builtin_fmaf(qv[c].z, qv[c].z, qq); qq = __builtin_fmaf(qv[c].w, qv[c].w, qq);
+            }
+            qn = __builtin_sqrtf(score_tile_sum(qq));
+        }
         const int64_t* __restrict__ qkeys = keys + q * n_cand;
         float* __restrict__ qout = out + q * n_cand;
         uint8_t* __restrict__ qfound = found ? found + q * n_cand : nullptr;
@@ -113,14 +131,20 @@ __global__ __launch_bounds__(kScoreWaves * 64) void score_kernel(const int64_t* 
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 float a = 0.f;
+                [[maybe_unused]] float rr = 0.f;
 #pragma unroll
                 for (int c = 0; c < C4; ++c) {
                     f32x4 v = score_operand<ROWS>(row[r][c]);
                     if (c == C4 - 1 && !last_live) v = f32x4{0.f, 0.f, 0.f, 0.f};
                     a = __builtin_fmaf(qv[c].x, v.x, a); a = __builtin_fmaf(qv[c].y, v.y, a);
                     a = __builtin_fmaf(qv[c].z, v.z, a); a = __builtin_fmaf(qv[c].w, v.w, a);
+                    if constexpr (METRIC == MEE_METRIC_COSINE) {
+                        rr = __builtin_fmaf(v.x, v.x, rr); rr = __builtin_fmaf(v.y, v.y, rr);
+                        rr = __builtin_fmaf(v.z, v.z, rr); rr = __builtin_fmaf(v.w, v.w, rr);
+                    }
                 }
                 a += __shfl_xor(a, 8); a += __shfl_xor(a, 4); a += __shfl_xor(a, 2); a += __shfl_xor(a, 1);   // (stays inside the 16-lane tile)
+                if constexpr (METRIC == MEE_METRIC_COSINE) a = a / (qn * __builtin_sqrtf(score_tile_sum(rr)));   // search's four operations; 0 / 0 = NaN is returned
                 sc[r] = slot[r] >= 0 ? a + 0.f : -__builtin_inff();   // + 0.f: a zero leaves as +0.0, as the scan's does; a NaN stays a NaN
             }
             // lane j < 4R collects position base + j (round j / 4, tile j % 4): ONE coalesced store of the scores, one of the found bytes
@@ -144,19 +168,18 @@ __global__ __launch_bounds__(kScoreWaves * 64) void score_kernel(const int64_t* 
 
 using namespace mee;
 
-extern "C" {
-
-int mee_score(const mee_table* t, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores, uint8_t* d_out_found,
-              void* stream) {
-    MEE_RANGE("mee_score");
-    if (!t) return fail(MEE_ERR_INVALID_ARG, "mee_score: null argument");
-    if (t->dim % 16 || t->dim < 16 || t->dim > 256) return fail(MEE_ERR_INVALID_ARG, "mee_score: dim must be a multiple of 16 in [16, 256] (got %u)", t->dim);
-    if (int rc = refuse_narrow_rows(t, "mee_score", false)) return rc;
+// mee_score and mee_score_metric: one check, one launch plan, the kernel of the metric
+template <int METRIC>
+static int score_launch(const mee_table* t, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores, uint8_t* d_out_found,
+                        void* stream, const char* name) {
+    if (!t) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (t->dim % 16 || t->dim < 16 || t->dim > 256) return fail(MEE_ERR_INVALID_ARG, "%s: dim must be a multiple of 16 in [16, 256] (got %u)", name, t->dim);
+    if (int rc = refuse_narrow_rows(t, name, false)) return rc;
     if (n_queries == 0 || n_cand == 0) return MEE_OK;   // as mee_find's n == 0
-    if (!d_queries || !d_keys || !d_out_scores) return fail(MEE_ERR_INVALID_ARG, "mee_score: null argument");
+    if (!d_queries || !d_keys || !d_out_scores) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
     if (((uintptr_t)d_queries & 15) || ((uintptr_t)d_keys & 7) || ((uintptr_t)d_out_scores & 3))
-        return fail(MEE_ERR_INVALID_ARG, "mee_score: queries must be 16-byte aligned, keys 8-byte aligned, scores 4-byte aligned");
-    if (n_cand > (SIZE_MAX >> 4) / n_queries) return fail(MEE_ERR_INVALID_ARG, "mee_score: n_queries * n_cand = %zu * %zu does not fit", n_queries, n_cand);
+        return fail(MEE_ERR_INVALID_ARG, "%s: queries must be 16-byte aligned, keys 8-byte aligned, scores 4-byte aligned", name);
+    if (n_cand > (SIZE_MAX >> 4) / n_queries) return fail(MEE_ERR_INVALID_ARG, "%s: n_queries * n_cand = %zu * %zu does not fit", name, n_queries, n_cand);
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
     int cus = 0;
@@ -171,11 +194,28 @@ int mee_score(const mee_table* t, const float* d_queries, size_t n_queries, cons
         if (span_steps > steps_per_query) span_steps = steps_per_query;
         const uint64_t span = span_steps * block_step, spans_per_query = (n_cand + span - 1) / span, n_units = (uint64_t)n_queries * spans_per_query;
         const uint32_t grid = n_units < kScoreMaxGrid ? (uint32_t)n_units : kScoreMaxGrid;
-        score_kernel<c4, bf16 ? kRowsBF16 : kRowsF32><<<grid, kScoreWaves * 64, 0, st>>>(t->keys, t->values, t->nb, t->dim4, (const f32x4*)d_queries, d_keys, n_cand, span,
+        score_kernel<c4, bf16 ? kRowsBF16 : kRowsF32, METRIC><<<grid, kScoreWaves * 64, 0, st>>>(t->keys, t->values, t->nb, t->dim4, (const f32x4*)d_queries, d_keys, n_cand, span,
                                                                                         spans_per_query, n_units, d_out_scores, d_out_found);
     }); });
     MEE_HIP(hipGetLastError());
     return MEE_OK;
+}
+
+extern "C" {
+
+
+int mee_score(const mee_table* t, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores, uint8_t* d_out_found,
+              void* stream) {
+    MEE_RANGE("mee_score");
+    return score_launch<MEE_METRIC_IP>(t, d_queries, n_queries, d_keys, n_cand, d_out_scores, d_out_found, stream, "mee_score");
+}
+
+int mee_score_metric(const mee_table* t, int metric, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores,
+                     uint8_t* d_out_found, void* stream) {
+    if (metric == MEE_METRIC_IP) return mee_score(t, d_queries, n_queries, d_keys, n_cand, d_out_scores, d_out_found, stream);
+    if (metric != MEE_METRIC_COSINE) return fail(MEE_ERR_INVALID_ARG, "mee_score_metric: metric must be MEE_METRIC_IP (0) or MEE_METRIC_COSINE (1) (got %d)", metric);
+    MEE_RANGE("mee_score_metric");
+    return score_launch<MEE_METRIC_COSINE>(t, d_queries, n_queries, d_keys, n_cand, d_out_scores, d_out_found, stream, "mee_score_metric");
 }
 
 }  // extern "C"

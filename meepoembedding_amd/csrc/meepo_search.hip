@@ -19,6 +19,9 @@
 //            one (tile, step range) pair per one-wave block — first over a prefix of the slots (the seed pass), search_seed_merge_kernel for each
 //            query's best k of the prefix, then over the rest with every threshold starting at the prefix's k-th entry, and the merge above with
 //            the seed as one more list.
+//   cosine   mee_search_metric(MEE_METRIC_COSINE): the batched launches with search_batch_scan_kernel<.., MEE_METRIC_COSINE> — the row norm from the B registers
+//            (one square root per lane and step), the query norms in LDS, a widened product threshold on the hot path and the exact four-operation
+//            score on the rare one (DESIGN.md §4 "Search", "Metric").  The inner-product instances do not change by it.
 // Only vector stores, no atomics, nothing of the table is written.
 //
 // The upstream snapshot has no search; the semantics are SPEC.md §3 "Search".
@@ -36,6 +39,9 @@ constexpr uint32_t kSearchMinCap = 8;        // a candidate buffer holds 2 max(k
 static_assert(2 * MEE_SEARCH_MAX_K <= 128, "a prune sorts a buffer as two entries per lane");
 // the LDS of the largest call: queries (bf16) + candidates (12 B) + four words and a key per (padded) query
 static_assert(MEE_SEARCH_MAX_QUERY_ELEMS * 2 + MEE_SEARCH_MAX_QK * 2 * 12 + (MEE_SEARCH_MAX_QK / kSearchMinCap + 31) / 32 * 32 * 20 <= 65536, "the scan's LDS budget");
+// the cosine scan keeps one more word per padded query (its norm) and is served in tiles of one row block at most
+constexpr uint32_t kSearchCosineTileMax = 32;
+static_assert(MEE_SEARCH_MAX_QUERY_ELEMS * 2 + MEE_SEARCH_MAX_QK * 2 * 12 + kSearchCosineTileMax * 24 <= 65536, "the cosine scan's LDS budget");
 
 __host__ __device__ constexpr uint32_t search_cap(uint32_t k) { return 2 * (k < kSearchMinCap ? kSearchMinCap : k); }
 
@@ -156,6 +162,49 @@ __device__ __forceinline__ void search_append(const SearchSel& s, uint32_t q, bo
     }
 }
 
+// ---- cosine (SPEC.md §3 "Search", "Metric"): score = dot / (sqrtf(qq) * sqrtf(rr)), four correctly rounded fp32 operations ---------------------------
+__device__ __forceinline__ float cosine_score(float dot, float qn, float rn) { return dot / (qn * rn) + 0.f; }   // + 0.f: a zero leaves as +0.0
+
+// A lane's share of a norm: the squares of its eight bf16 elements of one k-step on top of `a`.  Every square is exact in fp32 (16 significant bits).
+__device__ __forceinline__ float sum_squares(const u32x4 p, float a) {
+    const uint32_t w[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float lo = __builtin_bit_cast(float, w[i] << 16), hi = __builtin_bit_cast(float, w[i] & 0xFFFF0000u);
+        a = __builtin_fmaf(lo, lo, a);
+        a = __builtin_fmaf(hi, hi, a);
+    }
+    return a;
+}
+
+// The norms between which the hot path's product compare is argued below; a live row outside them takes the rare path every time, a query outside
+// them accepts every row.
+constexpr float kCosNormMin = 0x1p-50f, kCosNormMax = 0x1p50f;
+
+// The hot path's threshold for a query whose k-th best cosine is `thr` (-inf: none yet; +inf: a padding query) and whose norm is qn: the hot path
+// accepts accumulator `acc` of a row of norm rn iff  acc >= fl(pre * rn),  one multiply and one compare.  It may accept too much — the rare path
+// computes the exact score and decides — but must never reject a row whose exact score s = fl(acc / d), d = fl(qn * rn), reaches thr.
+// With u = 2^-24 and qn, rn in [kCosNormMin, kCosNormMax] (so d is a normal number, d = qn rn (1 + e1), |e1| <= u):
+//   s >= thr  =>  acc / d >= pred(thr), the next float below thr (division rounds to nearest and is monotone)  =>  acc >= pred(thr) d.
+//   P = fl(thr qn) = thr qn (1 + e3), and the compare's right side is pre rn (1 + e2); |e2|, |e3| <= u while the products are normal numbers.
+//   thr > 0: pred(thr) >= thr (1 - 2u), so pred(thr) d >= thr qn rn (1 - 2u)(1 - u).  pre = fl(P (1 - 8u)) <= thr qn (1 + u)(1 - 8u)(1 + u), and
+//            times (1 + u) rn that stays below thr qn rn (1 - 4u): the threshold is LOWERED, toward zero, by more than the roundings can raise it.
+//   thr < 0: pred(thr) >= thr (1 + 2u) (it lies further from zero), so pred(thr) d >= thr qn rn (1 + 2u)(1 + u), and pre = fl(P (1 + 8u)) is
+//            thr qn (1 + 5u) or further from zero after all three roundings: the threshold is lowered AWAY from zero.
+//   |P| < 2^-60, thr = +-0 included: relative bounds end where products turn subnormal, so the threshold is the constant -2^-58: pred(thr) d
+//            >= -(|thr| qn (1 + 4u) + 2^-149 2^50 (1 + u)) rn > -2^-58 rn, and -2^-58 rn is exact (rn >= 2^-50).  A positive such thr accepts acc >= ~0.
+//   thr = -inf: pre = -inf accepts every row with rn > 0.  thr = +inf: pre = +inf rejects everything but acc = +inf, whose score ties it.
+//   An overflowing pre rn (a threshold left by a row outside the norm range) is +inf only where the real product exceeds every finite acc, or -inf.
+//   A zero row or a dead lane: the scan hands in rn = NaN (the score 0 / 0 is NaN for every query), and a NaN accumulator or norm passes no compare.
+// A query of norm 0 or NaN has only NaN scores: +inf.  A query whose norm lies outside the range: -inf, every live row takes the rare path.
+__device__ __forceinline__ float cosine_prefilter(float thr, float qn) {
+    if (!(qn > 0.f)) return __builtin_inff();
+    if (!(qn >= kCosNormMin && qn <= kCosNormMax)) return -__builtin_inff();
+    const float P = thr * qn;
+    if (!(__builtin_fabsf(P) >= 0x1p-60f)) return -0x1p-58f;
+    return P * (P > 0.f ? 1.f - 0x1p-21f : 1.f + 0x1p-21f);
+}
+
 // The B operand of a step: lane (half, col) holds elements [16 s + 8 half, + 8) of slot's row for k-step s, as bf16.  A dead lane loads nothing.
 template <int KS, int ROWS>
 __device__ __forceinline__ void search_load_b(const void* __restrict__ values, uint64_t slot, int half, bool live, bf16x8 (&b)[KS]) {
@@ -183,10 +232,11 @@ __device__ __forceinline__ void search_load_b(const void* __restrict__ values, u
 }
 
 // LDS (dynamic; the host computes the same sum, search_lds_bytes): A fragments [n_rb][KS][64] x 16 B | buf_key | thr_key | buf_img | thr_img | thr_sc | cnt
+// | qn (cosine only: [qp] query norms).  METRIC == MEE_METRIC_COSINE: thr_sc holds cosine_prefilter of the threshold instead of the threshold's score.
 // The scan of one block: `nq` queries against the steps [s0, s1) (s1 <= the table's step count); its best k per query go to rows out_row0 + q of the
 // lists.  seed_img / seed_keys: null, or the sorted best-k lists [nq][k] of slots OUTSIDE [s0, s1) — a query's thresholds then start at its k-th
 // seed entry (image 0 there: none yet) instead of at nothing, and the buffers may hold fewer than k entries while a threshold is set.
-template <int KS, int ROWS>
+template <int KS, int ROWS, int METRIC>
 __device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
                                                  const float* __restrict__ queries, uint32_t nq, uint32_t k, uint64_t s0, uint64_t s1,
                                                  const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img, size_t out_row0,
@@ -204,8 +254,10 @@ __device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tke
     s.thr_img = s.buf_img + (size_t)nq * s.cap;
     s.thr_sc = reinterpret_cast<float*>(s.thr_img + qp);
     s.cnt = reinterpret_cast<uint32_t*>(s.thr_sc + qp);
+    [[maybe_unused]] float* const qn = reinterpret_cast<float*>(s.cnt + qp);   // (cosine only)
 
     // ---- the queries, rounded once, in fragment order: fragment (rb, ks) is 64 lanes x 16 bytes, lane (half, col) = query rb * 32 + col, elements as B's
+    [[maybe_unused]] float qq = 0.f;
     for (uint32_t f = 0; f < n_rb * KS; ++f) {
         const uint32_t q = (f / KS) * 32 + col, ks = f % KS;
         u32x4 p = {0u, 0u, 0u, 0u};
@@ -215,13 +267,23 @@ __device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tke
             p = u32x4{bf16x2_of(x.x, x.y), bf16x2_of(x.z, x.w), bf16x2_of(y.x, y.y), bf16x2_of(y.z, y.w)};
         }
         afrag[f * 64 + lane] = p;
+        if constexpr (METRIC == MEE_METRIC_COSINE) {   // the query's norm from the rounded values: this lane's eight elements of every k-step, then the other half's
+            qq = sum_squares(p, ks == 0 ? 0.f : qq);
+            if (ks == KS - 1) {
+                qq += __shfl_xor(qq, 32);
+                if (half == 0) qn[q] = __builtin_sqrtf(qq);   // (a padding query: 0)
+            }
+        }
     }
+    if constexpr (METRIC == MEE_METRIC_COSINE) wave_lds_sync();
     for (uint32_t q = lane; q < qp; q += 64) {
         uint32_t ti = 0u;
         int64_t tk = kEmpty;
         if (seed_img && q < nq) { ti = seed_img[(size_t)q * k + k - 1]; tk = seed_keys[(size_t)q * k + k - 1]; }
         s.thr_key[q] = tk; s.thr_img[q] = ti; s.cnt[q] = 0u;
-        s.thr_sc[q] = q < nq ? (ti ? image_score(ti) : -__builtin_inff()) : __builtin_inff();   // nothing beats a padding query's threshold
+        const float ts = q < nq ? (ti ? image_score(ti) : -__builtin_inff()) : __builtin_inff();   // nothing beats a padding query's threshold
+        if constexpr (METRIC == MEE_METRIC_COSINE) s.thr_sc[q] = cosine_prefilter(ts, qn[q]);
+        else s.thr_sc[q] = ts;
     }
     wave_lds_sync();
 
@@ -237,6 +299,20 @@ __device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tke
         if (!__ballot(live)) continue;   // wave-uniform
         bf16x8 b[KS];
         search_load_b<KS, ROWS>(values, slot, half, live, b);
+        // cosine: the norm of the lane's slot from the operand registers themselves (an fp32 row after its rounding) — the lane's eight elements of
+        // every k-step, the other half's share from lane ^ 32, one square root per lane and step.  All 16 accumulators of a lane belong to this slot.
+        [[maybe_unused]] float rn = 0.f;
+        [[maybe_unused]] bool wild = false;   // a live row whose norm lies outside the product compare's range: every query looks at it exactly
+        if constexpr (METRIC == MEE_METRIC_COSINE) {
+            float rr = 0.f;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) rr = sum_squares(__builtin_bit_cast(u32x4, b[ks]), rr);
+            rr += __shfl_xor(rr, 32);
+            // A zero row (and a dead lane) has the score 0 / 0 = NaN for every query.  Its norm is kept as NaN, not 0: the score stays NaN, and the
+            // hot path's compare fails at once where  0 >= thr * 0  would send the row to the rare path at every step.
+            rn = rr > 0.f ? __builtin_sqrtf(rr) : __builtin_nanf("");
+            wild = __ballot(live && (rn > kCosNormMax || (rn < kCosNormMin && rn > 0.f))) != 0;
+        }
         for (uint32_t rb = 0; rb < n_rb; ++rb) {
             f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -246,19 +322,30 @@ __device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tke
             const uint32_t qbase = rb * 32 + 4 * half;
             uint32_t hot = 0;
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (__ballot(live && acc[r] >= s.thr_sc[qbase + 8 * (r >> 2) + (r & 3)])) hot |= 1u << r;
+            for (int r = 0; r < 16; ++r) {
+                if constexpr (METRIC == MEE_METRIC_COSINE) {   // thr_sc is cosine_prefilter's value: one multiply and one compare
+                    if (__ballot(live && acc[r] >= s.thr_sc[qbase + 8 * (r >> 2) + (r & 3)] * rn)) hot |= 1u << r;
+                } else {
+                    if (__ballot(live && acc[r] >= s.thr_sc[qbase + 8 * (r >> 2) + (r & 3)])) hot |= 1u << r;
+                }
+            }
+            if constexpr (METRIC == MEE_METRIC_COSINE) hot = wild ? 0xFFFFu : hot;
             while (hot) {   // wave-uniform, rare once the thresholds have risen
                 const int r = __ffs(hot) - 1;
                 hot &= hot - 1;
                 float sc = acc[0];
 #pragma unroll
                 for (int i = 1; i < 16; ++i) sc = r == i ? acc[i] : sc;
-                sc += 0.f;   // -0.0 -> +0.0: equal scores have one image
+                if constexpr (METRIC != MEE_METRIC_COSINE) sc += 0.f;   // -0.0 -> +0.0: equal scores have one image
                 const uint32_t q = qbase + 8 * (r >> 2) + (r & 3);
+                if constexpr (METRIC == MEE_METRIC_COSINE) sc = cosine_score(sc, qn[q], rn);   // the exact score, its zero as +0.0 too; 0 / 0 = NaN is no candidate
                 const uint32_t img = score_image(sc);
                 const bool beat = live && q < nq && sc == sc && search_better(img, key, s.thr_img[q], s.thr_key[q]);
                 search_append(s, q, beat, img, key, lane);
+                if constexpr (METRIC == MEE_METRIC_COSINE) {   // the thresholds a prune may have raised, as the hot path wants them (q < qp: no query's word is a stranger's)
+                    if (col == 0) s.thr_sc[q] = cosine_prefilter(s.thr_img[q] ? image_score(s.thr_img[q]) : -__builtin_inff(), qn[q]);
+                    wave_lds_sync();
+                }
             }
         }
     }
@@ -281,14 +368,14 @@ __global__ __launch_bounds__(64) void search_scan_kernel(const int64_t* __restri
                                                          int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
     const uint64_t n_steps = (capacity + 31) / 32;
     const uint64_t s0 = (uint64_t)blockIdx.x * steps_per_block, s1 = s0 + steps_per_block < n_steps ? s0 + steps_per_block : n_steps;
-    search_scan_body<KS, ROWS>(tkeys, values, capacity, queries, nq, k, s0, s1, nullptr, nullptr, (size_t)blockIdx.x * nq, ws_keys, ws_img);
+    search_scan_body<KS, ROWS, MEE_METRIC_IP>(tkeys, values, capacity, queries, nq, k, s0, s1, nullptr, nullptr, (size_t)blockIdx.x * nq, ws_keys, ws_img);
 }
 
 // The batched scan (mee_search_batch): the nq_all queries are cut into n_tiles tiles of `tile` queries (the last one shorter), the steps
 // [step0, step_end) into ranges of steps_per_range; a one-wave block serves one (tile, range) pair.  The grid is flat and the tile index varies
 // fastest, so the blocks that walk one range are neighbours.  Lists: [range][nq_all][k] — a tile's block writes its own query rows of its range's
 // list, so the merge reads every query's lists at one stride whatever its tile.  seed_*: null or [nq_all][k] (search_scan_body).
-template <int KS, int ROWS>
+template <int KS, int ROWS, int METRIC>
 __global__ __launch_bounds__(64) void search_batch_scan_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
                                                                const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
                                                                uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
@@ -299,7 +386,7 @@ __global__ __launch_bounds__(64) void search_batch_scan_kernel(const int64_t* __
     uint64_t s0 = step0 + (uint64_t)range * steps_per_range, s1 = s0 + steps_per_range;
     if (s1 > step_end) s1 = step_end;
     if (s0 > s1) s0 = s1;
-    search_scan_body<KS, ROWS>(tkeys, values, capacity, queries + (size_t)q0 * (16 * KS), nq, k, s0, s1, seed_keys ? seed_keys + (size_t)q0 * k : nullptr,
+    search_scan_body<KS, ROWS, METRIC>(tkeys, values, capacity, queries + (size_t)q0 * (16 * KS), nq, k, s0, s1, seed_keys ? seed_keys + (size_t)q0 * k : nullptr,
                                seed_img ? seed_img + (size_t)q0 * k : nullptr, (size_t)range * nq_all + q0, ws_keys, ws_img);
 }
 
@@ -369,9 +456,9 @@ __global__ __launch_bounds__(64) void search_seed_merge_kernel(const int64_t* __
 // =========================================================================================================
 // host side
 // =========================================================================================================
-static size_t search_lds_bytes(uint32_t dim, size_t nq, uint32_t k) {
+static size_t search_lds_bytes(uint32_t dim, size_t nq, uint32_t k, int metric = MEE_METRIC_IP) {
     const size_t qp = (nq + 31) / 32 * 32;
-    return qp * dim * 2 + nq * search_cap(k) * 12 + qp * 20;
+    return qp * dim * 2 + nq * search_cap(k) * 12 + qp * (metric == MEE_METRIC_COSINE ? 24 : 20);
 }
 // what the entry points refuse, before anything is launched; -> the blocks of the largest grid a search of this device launches.  batch: n_queries
 // is held against mee_search_batch's cap instead of the per-call limits.
@@ -407,10 +494,11 @@ constexpr uint32_t kSearchTileMaxQueries = MEE_SEARCH_TILE_MAX_QUERIES;  // a ti
 
 // The queries of one tile: at most what one mee_search call accepts for this k and dim, so a block's LDS stays inside search_lds_bytes' budget, and
 // at most one row block — a fraction of that LDS, so more waves stay resident; measured against tiles at the per-call limit in profiles/search.md.
-static uint32_t search_batch_tile(uint32_t dim, uint32_t k) {
+static uint32_t search_batch_tile(uint32_t dim, uint32_t k, int metric) {
     const uint32_t by_qk = MEE_SEARCH_MAX_QK / (k < kSearchMinCap ? kSearchMinCap : k), by_elems = MEE_SEARCH_MAX_QUERY_ELEMS / dim / 32 * 32;
     const uint32_t limit = by_qk < by_elems ? by_qk : by_elems;
-    return limit < kSearchTileMaxQueries ? limit : kSearchTileMaxQueries;
+    const uint32_t cap = metric == MEE_METRIC_COSINE && kSearchCosineTileMax < kSearchTileMaxQueries ? kSearchCosineTileMax : kSearchTileMaxQueries;
+    return limit < cap ? limit : cap;
 }
 
 struct SearchBatchPlan {
@@ -420,9 +508,9 @@ struct SearchBatchPlan {
     uint64_t seed_steps, per_range, per_seed_range;
     uint64_t lists() const { return 1 + (uint64_t)ranges + seed_ranges; }   // list 0 is the seed area
 };
-static SearchBatchPlan search_batch_plan(uint32_t dim, uint32_t nq, uint32_t k, uint32_t max_grid, uint64_t n_steps) {
+static SearchBatchPlan search_batch_plan(uint32_t dim, uint32_t nq, uint32_t k, uint32_t max_grid, uint64_t n_steps, int metric) {
     SearchBatchPlan p{};
-    p.tile = search_batch_tile(dim, k);
+    p.tile = search_batch_tile(dim, k, metric);
     p.n_tiles = (nq + p.tile - 1) / p.tile;
     p.ranges = max_grid / p.n_tiles > 1 ? max_grid / p.n_tiles : 1;   // the block budget divided between the tiles
     p.seed_ranges = max_grid / kSearchSeedGridDiv / p.n_tiles > 1 ? max_grid / kSearchSeedGridDiv / p.n_tiles : 1;
@@ -443,6 +531,57 @@ static SearchBatchPlan search_batch_plan(uint32_t dim, uint32_t nq, uint32_t k, 
 }  // namespace mee
 
 using namespace mee;
+
+// the batched search of either metric: what mee_search_batch[_workspace_bytes] and mee_search_metric[_workspace_bytes] share
+static int search_batch_workspace(const mee_table* t, int metric, size_t n_queries, uint32_t k, uint64_t* bytes_out, const char* name) {
+    if (!bytes_out) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    *bytes_out = 0;
+    uint32_t max_grid = 0;
+    if (int rc = search_check(t, n_queries, k, name, &max_grid, true)) return rc;
+    // the seed area, the main lists and the seed pass's lists, each [n_queries][k] keys and images; the layout needs no padding
+    *bytes_out = search_batch_plan(t->dim, (uint32_t)n_queries, k, max_grid, UINT64_MAX, metric).lists() * n_queries * k * 12;
+    return MEE_OK;
+}
+
+template <int METRIC>
+static int search_batch_launch(const mee_table* t, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
+                               uint32_t* d_out_counts, void* d_workspace, void* stream, const char* name) {
+    uint32_t max_grid = 0;
+    if (int rc = search_check(t, n_queries, k, name, &max_grid, true)) return rc;
+    if (!d_queries || !d_out_keys || !d_out_scores || !d_workspace) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (((uintptr_t)d_queries & 15) || ((uintptr_t)d_workspace & 7)) return fail(MEE_ERR_INVALID_ARG, "%s: queries must be 16-byte aligned, the workspace 8-byte aligned", name);
+    DeviceGuard g(t->device);
+    hipStream_t st = as_stream(stream);
+    const uint32_t nq = (uint32_t)n_queries;
+    const uint64_t n_steps = (t->capacity + 31) / 32;
+    const SearchBatchPlan p = search_batch_plan(t->dim, nq, k, max_grid, n_steps, METRIC);
+    // lists of [nq][k] entries: 0 the seed area, 1 .. ranges the main scan's, then the seed pass's; the key plane of all lists, then the image plane
+    const size_t list = (size_t)nq * k;
+    int64_t* ws_keys = (int64_t*)d_workspace;
+    uint32_t* ws_img = (uint32_t*)(ws_keys + p.lists() * list);
+    const size_t lds = search_lds_bytes(t->dim, p.tile < nq ? p.tile : nq, k, METRIC);
+    const bool seeded = p.seed_ranges != 0;
+    with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)(t->dim / 16), [&](auto ks) { with_flag(t->bf16_rows, [&](auto bf16) {
+        auto scan = search_batch_scan_kernel<ks, bf16 ? kRowsBF16 : kRowsF32, METRIC>;
+        if (seeded) {
+            const size_t so = (1 + (size_t)p.ranges) * list;
+            scan<<<p.n_tiles * p.seed_ranges, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, 0, p.seed_steps, p.per_seed_range,
+                                                             nullptr, nullptr, ws_keys + so, ws_img + so);
+            search_seed_merge_kernel<<<nq, 64, 0, st>>>(ws_keys + so, ws_img + so, p.seed_ranges, nq, k, ws_keys, ws_img);
+        }
+        scan<<<p.n_tiles * p.ranges, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, p.seed_steps, n_steps, p.per_range,
+                                                    seeded ? ws_keys : nullptr, seeded ? ws_img : nullptr, ws_keys + list, ws_img + list);
+    }); });
+    // the seed area is one more list in front of the main scan's: the prefix is not scanned again
+    if (seeded) search_merge_kernel<<<nq, 64, 0, st>>>(ws_keys, ws_img, 1 + p.ranges, nq, k, d_out_keys, d_out_scores, d_out_counts);
+    else search_merge_kernel<<<nq, 64, 0, st>>>(ws_keys + list, ws_img + list, p.ranges, nq, k, d_out_keys, d_out_scores, d_out_counts);
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+static int search_metric_check(int metric, const char* name) {
+    if (metric == MEE_METRIC_IP || metric == MEE_METRIC_COSINE) return MEE_OK;
+    return fail(MEE_ERR_INVALID_ARG, "%s: metric must be MEE_METRIC_IP (0) or MEE_METRIC_COSINE (1) (got %d)", name, metric);
+}
 
 extern "C" {
 
@@ -480,49 +619,28 @@ int mee_search(const mee_table* t, const float* d_queries, size_t n_queries, uin
 }
 
 int mee_search_batch_workspace_bytes(const mee_table* t, size_t n_queries, uint32_t k, uint64_t* bytes_out) {
-    if (!bytes_out) return fail(MEE_ERR_INVALID_ARG, "mee_search_batch_workspace_bytes: null argument");
-    *bytes_out = 0;
-    uint32_t max_grid = 0;
-    if (int rc = search_check(t, n_queries, k, "mee_search_batch_workspace_bytes", &max_grid, true)) return rc;
-    // the seed area, the main lists and the seed pass's lists, each [n_queries][k] keys and images; the layout needs no padding
-    *bytes_out = search_batch_plan(t->dim, (uint32_t)n_queries, k, max_grid, UINT64_MAX).lists() * n_queries * k * 12;
-    return MEE_OK;
+    return search_batch_workspace(t, MEE_METRIC_IP, n_queries, k, bytes_out, "mee_search_batch_workspace_bytes");
 }
 
 int mee_search_batch(const mee_table* t, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
                      uint32_t* d_out_counts, void* d_workspace, void* stream) {
     MEE_RANGE("mee_search_batch");
-    uint32_t max_grid = 0;
-    if (int rc = search_check(t, n_queries, k, "mee_search_batch", &max_grid, true)) return rc;
-    if (!d_queries || !d_out_keys || !d_out_scores || !d_workspace) return fail(MEE_ERR_INVALID_ARG, "mee_search_batch: null argument");
-    if (((uintptr_t)d_queries & 15) || ((uintptr_t)d_workspace & 7)) return fail(MEE_ERR_INVALID_ARG, "mee_search_batch: queries must be 16-byte aligned, the workspace 8-byte aligned");
-    DeviceGuard g(t->device);
-    hipStream_t st = as_stream(stream);
-    const uint32_t nq = (uint32_t)n_queries;
-    const uint64_t n_steps = (t->capacity + 31) / 32;
-    const SearchBatchPlan p = search_batch_plan(t->dim, nq, k, max_grid, n_steps);
-    // lists of [nq][k] entries: 0 the seed area, 1 .. ranges the main scan's, then the seed pass's; the key plane of all lists, then the image plane
-    const size_t list = (size_t)nq * k;
-    int64_t* ws_keys = (int64_t*)d_workspace;
-    uint32_t* ws_img = (uint32_t*)(ws_keys + p.lists() * list);
-    const size_t lds = search_lds_bytes(t->dim, p.tile < nq ? p.tile : nq, k);
-    const bool seeded = p.seed_ranges != 0;
-    with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)(t->dim / 16), [&](auto ks) { with_flag(t->bf16_rows, [&](auto bf16) {
-        auto scan = search_batch_scan_kernel<ks, bf16 ? kRowsBF16 : kRowsF32>;
-        if (seeded) {
-            const size_t so = (1 + (size_t)p.ranges) * list;
-            scan<<<p.n_tiles * p.seed_ranges, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, 0, p.seed_steps, p.per_seed_range,
-                                                             nullptr, nullptr, ws_keys + so, ws_img + so);
-            search_seed_merge_kernel<<<nq, 64, 0, st>>>(ws_keys + so, ws_img + so, p.seed_ranges, nq, k, ws_keys, ws_img);
-        }
-        scan<<<p.n_tiles * p.ranges, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, p.seed_steps, n_steps, p.per_range,
-                                                    seeded ? ws_keys : nullptr, seeded ? ws_img : nullptr, ws_keys + list, ws_img + list);
-    }); });
-    // the seed area is one more list in front of the main scan's: the prefix is not scanned again
-    if (seeded) search_merge_kernel<<<nq, 64, 0, st>>>(ws_keys, ws_img, 1 + p.ranges, nq, k, d_out_keys, d_out_scores, d_out_counts);
-    else search_merge_kernel<<<nq, 64, 0, st>>>(ws_keys + list, ws_img + list, p.ranges, nq, k, d_out_keys, d_out_scores, d_out_counts);
-    MEE_HIP(hipGetLastError());
-    return MEE_OK;
+    return search_batch_launch<MEE_METRIC_IP>(t, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream, "mee_search_batch");
+}
+
+int mee_search_metric_workspace_bytes(const mee_table* t, int metric, size_t n_queries, uint32_t k, uint64_t* bytes_out) {
+    if (bytes_out) *bytes_out = 0;
+    if (int rc = search_metric_check(metric, "mee_search_metric_workspace_bytes")) return rc;
+    if (metric == MEE_METRIC_IP) return mee_search_batch_workspace_bytes(t, n_queries, k, bytes_out);
+    return search_batch_workspace(t, metric, n_queries, k, bytes_out, "mee_search_metric_workspace_bytes");
+}
+
+int mee_search_metric(const mee_table* t, int metric, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
+                      uint32_t* d_out_counts, void* d_workspace, void* stream) {
+    if (int rc = search_metric_check(metric, "mee_search_metric")) return rc;
+    if (metric == MEE_METRIC_IP) return mee_search_batch(t, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream);
+    MEE_RANGE("mee_search_metric");
+    return search_batch_launch<MEE_METRIC_COSINE>(t, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream, "mee_search_metric");
 }
 
 }  // extern "C"

@@ -776,7 +776,8 @@ class LookupTable:
             raise MeepoError(_lib.ERR_OUT_OF_MEMORY, "publish_to: the serving table had no room for some keys (STATUS_TABLE_FULL): rebuild it with a larger capacity")
         return upserts, removed, None
 
-    def search(self, queries: torch.Tensor, k: int, out_keys: torch.Tensor | None = None, out_scores: torch.Tensor | None = None, counts: bool = False):
+    def search(self, queries: torch.Tensor, k: int, out_keys: torch.Tensor | None = None, out_scores: torch.Tensor | None = None, counts: bool = False,
+               metric: str = "ip"):
         """SPEC.md §3 "Search": for each row of `queries` ([Q, dim] float32 on the table's device) the k live keys whose rows have the greatest inner
         product with it, scanned in place — no [N, dim] copy, never stale -> (keys [Q, k] int64, scores [Q, k] float32), best first, equal scores
         by the smaller key; counts=True adds the number of real entries per query ([Q] int32).  Both operands are rounded once to bf16 (an
@@ -784,7 +785,11 @@ class LookupTable:
         score -inf; a candidate with a NaN score is never returned.  fp32-row and bf16-row tables, dim a multiple of 16 in [16, 256], k in
         [1, SEARCH_MAX_K]; a batch beyond mee_search's per-call limits is ONE mee_search_batch call (tiled queries, a seeded scan; chunks of
         SEARCH_BATCH_MAX_QUERIES beyond that cap) with the same answer.  The workspace is a
-        tensor cached by size, one per stream that searched (the native calls of one search share it in stream order).  No gradient."""
+        tensor cached by size, one per stream that searched (the native calls of one search share it in stream order).  No gradient.
+        metric="cosine" (mee_search_metric): the score is dot / (|q| |row|) with both norms taken from the rounded operands inside the scan — no
+        normalised copy of the table; a zero row is never returned, a zero query has count 0.  Any Q goes through the batched launches."""
+        if metric not in _lib.METRICS:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"metric must be one of {sorted(_lib.METRICS)} (got {metric!r})")
         if queries.dtype != torch.float32 or queries.device != self.device or queries.dim() != 2 or queries.shape[1] != self.dim:
             raise MeepoError(_lib.ERR_INVALID_ARG, f"queries must be float32 [n_queries, {self.dim}] on {self.device} (got {queries.dtype} {list(queries.shape)} on {queries.device})")
         if not isinstance(k, int) or not 1 <= k <= _lib.SEARCH_MAX_K:
@@ -794,7 +799,10 @@ class LookupTable:
         per_call = min(_lib.SEARCH_MAX_QK // max(k, 8), max(_lib.SEARCH_MAX_QUERY_ELEMS // max(self.dim, 1) // 32 * 32, 1))
         need = C.c_uint64()
         batched = nq > per_call   # past one call's limits: mee_search_batch, tiled and seeded, in chunks of its own cap
-        if batched:
+        if metric != "ip":   # every Q through the batched launches of that metric
+            per_call = _lib.SEARCH_BATCH_MAX_QUERIES
+            check(_lib.lib().mee_search_metric_workspace_bytes(self._h, _lib.METRICS[metric], max(min(nq, per_call), 1), k, C.byref(need)))
+        elif batched:
             per_call = _lib.SEARCH_BATCH_MAX_QUERIES
             check(_lib.lib().mee_search_batch_workspace_bytes(self._h, min(nq, per_call), k, C.byref(need)))
         else:
@@ -808,19 +816,25 @@ class LookupTable:
         if ws is None or ws.numel() < need.value:
             ws = cache[stream] = torch.empty(need.value, dtype=torch.uint8, device=self.device)
         ok, osc = out_keys.view(nq, k), out_scores.view(nq, k)
-        call = _lib.lib().mee_search_batch if batched else _lib.lib().mee_search
+        if metric != "ip":
+            head = (_lib.lib().mee_search_metric, self._h, _lib.METRICS[metric])
+        else:
+            head = (_lib.lib().mee_search_batch if batched else _lib.lib().mee_search, self._h)
         for s in range(0, nq, per_call):
             n = min(per_call, nq - s)
-            check(call(self._h, q[s:s + n].data_ptr(), n, k, ok[s:s + n].data_ptr(), osc[s:s + n].data_ptr(),
-                       n_real[s:s + n].data_ptr() if counts else None, ws.data_ptr(), stream))
+            check(head[0](*head[1:], q[s:s + n].data_ptr(), n, k, ok[s:s + n].data_ptr(), osc[s:s + n].data_ptr(),
+                          n_real[s:s + n].data_ptr() if counts else None, ws.data_ptr(), stream))
         return (out_keys, out_scores, n_real) if counts else (out_keys, out_scores)
 
-    def score(self, queries: torch.Tensor, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None):
+    def score(self, queries: torch.Tensor, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None, metric: str = "ip"):
         """SPEC.md §3 "Score": the inner product of each row of `queries` ([Q, dim] float32 on the table's device) with the rows of ITS candidates,
         `keys` [Q, C] int64 — a slate from search, another retriever or business rules; duplicates allowed -> (scores [Q, C] float32, found [Q, C]
         uint8 as find returns it).  One launch probes, gathers and reduces: no [Q, C, dim] block.  The score is search's — both operands rounded
         once to bf16, fp32 sum — so search's own keys score search's scores; an absent or reserved key (search's INT64_MIN padding) scores -inf
-        with found 0, a NaN score is returned as NaN.  fp32-row and bf16-row tables, dim a multiple of 16 in [16, 256].  No gradient."""
+        with found 0, a NaN score is returned as NaN.  fp32-row and bf16-row tables, dim a multiple of 16 in [16, 256].  No gradient.
+        metric="cosine" (mee_score_metric): search's cosine, dot / (|q| |row|); a zero row or a zero query scores NaN with found 1."""
+        if metric not in _lib.METRICS:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"metric must be one of {sorted(_lib.METRICS)} (got {metric!r})")
         if queries.dtype != torch.float32 or queries.device != self.device or queries.dim() != 2 or queries.shape[1] != self.dim:
             raise MeepoError(_lib.ERR_INVALID_ARG, f"queries must be float32 [n_queries, {self.dim}] on {self.device} (got {queries.dtype} {list(queries.shape)} on {queries.device})")
         if keys.dtype != torch.int64 or keys.device != self.device or keys.dim() != 2 or keys.shape[0] != queries.shape[0]:
@@ -829,7 +843,10 @@ class LookupTable:
         nq, nc = k.shape
         out = _buffer(out, "out", torch.float32, (nq, nc), self.device)
         found = _buffer(found, "found", torch.uint8, (nq, nc), self.device)
-        check(_lib.lib().mee_score(self._h, q.data_ptr(), nq, k.data_ptr(), nc, out.data_ptr(), found.data_ptr(), self._s()))
+        if metric == "ip":
+            check(_lib.lib().mee_score(self._h, q.data_ptr(), nq, k.data_ptr(), nc, out.data_ptr(), found.data_ptr(), self._s()))
+        else:
+            check(_lib.lib().mee_score_metric(self._h, _lib.METRICS[metric], q.data_ptr(), nq, k.data_ptr(), nc, out.data_ptr(), found.data_ptr(), self._s()))
         return out, found
 
     def find_or_insert(self, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None,

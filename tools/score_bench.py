@@ -7,7 +7,8 @@ replaced by ids the table does not hold); score and find write into preallocated
     find + einsum     table.find(keys) into a [Q, C, dim] fp32 block, then torch.einsum on the bf16-rounded operands: what a user ran before
     find              the find of that path alone, n = Q * C: the yardstick — the same probe and gather with a larger store
 Byte model per candidate: 8 B key + 128 B bucket line + the row + what is stored (score: 4 B; find: a dim * 4 B row).
-usage: python tools/score_bench.py [--keys N] [--dim D] [--reps K] [--shapes 1x1000,256x100,...] [--absent 0.1]"""
+--metric cosine adds the row `cosine`, table.score(..., metric="cosine"), beside the inner-product rows (profiles/score.md "Metric").
+usage: python tools/score_bench.py [--metric ip|cosine] [--keys N] [--dim D] [--reps K] [--shapes 1x1000,256x100,...] [--absent 0.1]"""
 import argparse
 import json
 import os
@@ -24,6 +25,7 @@ ap.add_argument("--keys", type=int, default=10_000_000)
 ap.add_argument("--dim", type=int, default=64)
 ap.add_argument("--reps", type=int, default=40)
 ap.add_argument("--shapes", default="1x1000,256x100,4096x100,256x1000")
+ap.add_argument("--metric", default="ip", choices=["ip", "cosine"])
 ap.add_argument("--absent", type=float, default=0.1)
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -74,12 +76,14 @@ for value_dtype in (torch.float32, torch.bfloat16):
         err = float((scores[hit] - find_einsum()[hit]).abs().max()) if hit.any() else 0.0   # (two fp32 summation orders)
         rows = {"score": lambda: t.score(queries, keys, out=scores, found=sfound), "find + einsum": find_einsum,
                 "find": lambda: t.find(keys, out=block, found=ffound)}
+        if args.metric == "cosine":
+            rows["cosine"] = lambda: t.score(queries, keys, out=scores, found=sfound, metric="cosine")
         passes = [timed_rows(rows, args.reps) for _ in range(2)]
         us = {nm: (passes[0][nm] + passes[1][nm]) / 2 for nm in rows}
         n = nq * nc
         score_bytes, find_bytes = n * (8 + 128 + row_bytes + 4), n * (8 + 128 + row_bytes + 4 * args.dim)
         rate = {"score": score_bytes / us["score"] * 1e-6, "find": find_bytes / us["find"] * 1e-6}   # TB/s
-        rec = {"rows": str(value_dtype).split(".")[1], "keys": t.size(), "dim": args.dim, "Q": nq, "C": nc, "absent": round(float(miss.float().mean()), 3),
+        rec = {"metric": args.metric, "rows": str(value_dtype).split(".")[1], "keys": t.size(), "dim": args.dim, "Q": nq, "C": nc, "absent": round(float(miss.float().mean()), 3),
                "us": {nm: round(v, 1) for nm, v in us.items()}, "spread_us": {nm: round(abs(passes[0][nm] - passes[1][nm]), 1) for nm in rows},
                "speedup_over_find_einsum": round(us["find + einsum"] / us["score"], 2), "bytes_per_candidate": {"score": score_bytes // n, "find": find_bytes // n},
                "TBps": {nm: round(v, 3) for nm, v in rate.items()}, "score_rate_over_find_rate": round(rate["score"] / rate["find"], 2),

@@ -10,7 +10,11 @@ a row is its pass-to-pass difference (the method of profiles/int8_rows.md).
     matmul + topk     on a PREBUILT [N, dim] bf16 matrix of the same table: queries.bfloat16() @ M.T, torch.topk, keys[positions]
     refresh           building that matrix — export() and the cast to bf16 — timed once and reported apart: the cost the matrix path pays after every
                       publish, and the second copy of the table it keeps
-usage: python tools/search_bench.py [--keys N] [--dim D] [--reps K] [--queries 1,32,128,1024] [--ks 10,64] [--libs parent=PATH,…] [--no-matmul]"""
+--metric cosine adds two rows and changes one (profiles/search.md "Metric"):
+    cosine            table.search(queries, k, metric="cosine"): mee_search_metric, the batched launches for every Q
+    ip same launches  mee_search_batch called directly for every Q: the inner product through the very launches the cosine takes — what the norm costs
+    matmul + topk     the matrix is the NORMALISED bf16 matrix (rows / |row|), the queries are normalised per call; refresh includes the normalisation
+usage: python tools/search_bench.py [--metric ip|cosine] [--keys N] [--dim D] [--reps K] [--queries 1,32,128,1024] [--ks 10,64] [--libs parent=PATH,…] [--no-matmul]"""
 import argparse
 import ctypes as C
 import json
@@ -30,6 +34,7 @@ ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--queries", default="1,32,128,1024")
 ap.add_argument("--ks", default="10,64", help="one Q and one k: a shape on its own for `rocprofv3 --kernel-trace --stats`, which times the scan and the merge apart")
 ap.add_argument("--libs", default="", help="NAME=PATH,…: other builds of the library, each a row of its own")
+ap.add_argument("--metric", default="ip", choices=["ip", "cosine"])
 ap.add_argument("--no-matmul", action="store_true", help="leave the matrix path out (a kernel trace of the search alone)")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -87,6 +92,19 @@ def other_build(path):
     return search
 
 
+def same_launches(t, queries, k, held={}):
+    """mee_search_batch called directly, whatever Q: the launches mee_search_metric takes, ranking by the inner product"""
+    nq = queries.shape[0]
+    if (nq, k) not in held:
+        need = C.c_uint64()
+        _lib.check(_lib.lib().mee_search_batch_workspace_bytes(t._h, nq, k, C.byref(need)))
+        held.clear()
+        held[nq, k] = (torch.empty(nq, k, dtype=torch.int64, device=dev), torch.empty(nq, k, device=dev), torch.empty(need.value, dtype=torch.uint8, device=dev))
+    ok, osc, ws = held[nq, k]
+    _lib.check(_lib.lib().mee_search_batch(t._h, queries.data_ptr(), nq, k, ok.data_ptr(), osc.data_ptr(), None, ws.data_ptr(), None))
+    return ok, osc
+
+
 others = {nm: other_build(path) for nm, path in (x.split("=") for x in args.libs.split(",") if x)}
 results = []
 for value_dtype in (torch.float32, torch.bfloat16):
@@ -98,7 +116,7 @@ for value_dtype in (torch.float32, torch.bfloat16):
     torch.cuda.synchronize()
     ev[0].record()
     ekeys, erows = t.export()[:2]
-    matrix = erows.to(torch.bfloat16)
+    matrix = (erows / erows.norm(dim=1, keepdim=True) if args.metric == "cosine" else erows).to(torch.bfloat16)
     ev[1].record()
     torch.cuda.synchronize()
     refresh_us = ev[0].elapsed_time(ev[1]) * 1e3
@@ -107,15 +125,19 @@ for value_dtype in (torch.float32, torch.bfloat16):
         queries = torch.randn(nq, args.dim, device=dev)
         for k in [int(x) for x in args.ks.split(",")]:
             def matmul_topk():
-                pos = torch.topk(queries.to(torch.bfloat16) @ matrix.T, k, dim=1).indices
+                qm = queries / queries.norm(dim=1, keepdim=True) if args.metric == "cosine" else queries
+                pos = torch.topk(qm.to(torch.bfloat16) @ matrix.T, k, dim=1).indices
                 return ekeys[pos]
 
-            got = t.search(queries, k)[0]
+            got = t.search(queries, k, metric=args.metric)[0]
             same = float((got == matmul_topk()).float().mean())   # (bf16 scores of the matrix path round differently: near-ties may swap)
             rows = {"search": lambda: t.search(queries, k)}
+            if args.metric == "cosine":
+                rows = {"cosine": lambda: t.search(queries, k, metric="cosine"), "ip same launches": lambda: same_launches(t, queries, k), **rows}
+                assert torch.equal(same_launches(t, queries, k)[0], t.search(queries, k)[0])
             if not args.no_matmul:
                 rows["matmul + topk"] = matmul_topk
-            for nm, fn in others.items():
+            for nm, fn in others.items() if args.metric == "ip" else ():
                 rows[nm] = lambda fn=fn: fn(t, queries, k)
                 assert torch.equal(fn(t, queries, k)[0], got), f"{nm} and this tree's search disagree"   # exact by contract, whatever the build
             passes = [timed_rows(rows, args.reps) for _ in range(2)]
@@ -124,7 +146,7 @@ for value_dtype in (torch.float32, torch.bfloat16):
             # four launches.  A build without the batch entry point: `split` calls of two launches, each a scan of the table.
             split = -(-nq // per_call_limit(k))
             tiles = -(-nq // min(per_call_limit(k), 32)) if nq > per_call_limit(k) else 1   # search_batch_tile: one row block at the most
-            rec = {"rows": str(value_dtype).split(".")[1], "keys": n, "dim": args.dim, "Q": nq, "k": k, "native_calls": 1, "launches": 4 if tiles > 1 else 2,
+            rec = {"metric": args.metric, "rows": str(value_dtype).split(".")[1], "keys": n, "dim": args.dim, "Q": nq, "k": k, "native_calls": 1, "launches": 4 if tiles > 1 else 2,
                    "tiles": tiles, "split_native_calls": split, "split_launches": 2 * split,
                    "us": {nm: round(v, 1) for nm, v in us.items()}, "spread_us": {nm: round(abs(passes[0][nm] - passes[1][nm]), 1) for nm in rows},
                    "search_bytes": tiles * scan_bytes, "split_bytes": split * scan_bytes, "matmul_bytes": n * args.dim * 2 + 2 * nq * n * 2,
