@@ -1152,7 +1152,8 @@ int mee_group_publish_changed(const mee_group* src, const mee_changes_group* log
  * A query with fewer than k candidates has its tail filled with key INT64_MIN and score -inf; d_out_counts [n_queries] (nullable) receives the number
  * of real entries.  d_workspace: caller-owned device memory of mee_search_workspace_bytes(t, n_queries, k) bytes, 8-byte aligned (the figure depends on
  * the device, n_queries and k only, not on the table's capacity); two searches that may overlap need a workspace each.  Served: fp32-row tables, with or without an optimizer, and bf16-row tables.
- * Limits, per call (anything outside is MEE_ERR_INVALID_ARG before any launch): dim % 16 == 0 and 16 <= dim <= 256; 1 <= k <= MEE_SEARCH_MAX_K;
+ * Limits, per call (anything outside is MEE_ERR_INVALID_ARG before any launch): dim % 16 == 0 and 16 <= dim <= 256 (a wider row, up to
+ * MEE_SEARCH_MAX_DIM, is served by mee_search_batch and mee_search_metric only, for any n_queries from 1); 1 <= k <= MEE_SEARCH_MAX_K;
  * n_queries >= 1, n_queries * max(k, 8) <= MEE_SEARCH_MAX_QK, and n_queries rounded up to a multiple of 32, times dim, <= MEE_SEARCH_MAX_QUERY_ELEMS
  * (what the scan keeps in 64 KB of LDS: the candidate buffers and the rounded queries); a larger batch is several calls over row ranges of the outputs.
  * An int8-row table is MEE_ERR_UNSUPPORTED.  Read-only on the table, two launches, no synchronisation, no allocation, no memset: safe under stream
@@ -1160,6 +1161,7 @@ int mee_group_publish_changed(const mee_group* src, const mee_changes_group* log
 #define MEE_SEARCH_MAX_K 64
 #define MEE_SEARCH_MAX_QK 1536
 #define MEE_SEARCH_MAX_QUERY_ELEMS 12288
+#define MEE_SEARCH_MAX_DIM 1024 /* mee_search_batch, mee_search_metric, mee_score, mee_score_metric; mee_search itself stops at 256 */
 int mee_search_workspace_bytes(const mee_table* t, size_t n_queries, uint32_t k, uint64_t* bytes_out);
 int mee_search(const mee_table* t, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
                uint32_t* d_out_counts /* nullable */, void* d_workspace, void* stream);
@@ -1169,7 +1171,9 @@ int mee_search(const mee_table* t, const float* d_queries, size_t n_queries, uin
  * query a threshold before the main scan starts (DESIGN.md §4 "Search", "Batched"); the answer stays a function of the table's contents only.
  * Arguments as mee_search; d_workspace of mee_search_batch_workspace_bytes(t, n_queries, k) bytes, 8-byte aligned (device, dim, n_queries and k only:
  * the seed area n_queries * k * 12 bytes, and the scan lists, which do not grow with n_queries beyond mee_search's largest figure and a quarter).
- * Limits (anything outside is MEE_ERR_INVALID_ARG before any launch, as are null or misaligned pointers): dim and k as mee_search; the cap on
+ * Limits (anything outside is MEE_ERR_INVALID_ARG before any launch, as are null or misaligned pointers): k as mee_search; dim % 16 == 0 and
+ * 16 <= dim <= MEE_SEARCH_MAX_DIM — past 256 the scan walks a row in chunks of 256 columns and the tiles shrink with dim and k, to no fewer than
+ * 8 queries (DESIGN.md §4 "Search", "Wide rows"); the contract does not change with the width.  The cap on
  * n_queries keeps the seed area at 48 MiB for k = 64 and every product of a query index, k and a list index far inside the kernels' index arithmetic.
  * An int8-row table is MEE_ERR_UNSUPPORTED.  Read-only on the table, four launches (two on a table too small for a seed pass), no
  * synchronisation, no allocation, no memset, no atomics: safe under stream capture; overlap and ordering as mee_search. */
@@ -1192,7 +1196,7 @@ int mee_search_batch(const mee_table* t, const float* d_queries, size_t n_querie
  * mee_search's own output keys equal mee_search's scores: bit for bit on exactly summable data, the padded tail included, and within the sum of the
  * two bounds otherwise.
  * Served: fp32-row tables, with or without an optimizer, and bf16-row tables; an int8-row table is MEE_ERR_UNSUPPORTED.  dim % 16 == 0 and
- * 16 <= dim <= 256, as mee_search; n_queries and n_cand are limited only as mee_find's n = n_queries * n_cand is; n_queries == 0 or n_cand == 0 is
+ * 16 <= dim <= MEE_SEARCH_MAX_DIM, as mee_search_batch; n_queries and n_cand are limited only as mee_find's n = n_queries * n_cand is; n_queries == 0 or n_cand == 0 is
  * mee_find's n == 0 (MEE_OK, nothing launched).  A null or misaligned pointer and a bad dim are MEE_ERR_INVALID_ARG before any launch.
  * No workspace, no host synchronisation, one launch: safe under stream capture.  Read-only on the table — hit counters are not touched — so it may
  * overlap finds and searches and is ordered against mutators as mee_find is (stream order).  Vector stores only, no atomics. */

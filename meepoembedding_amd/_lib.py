@@ -33,6 +33,7 @@ PAD_KEEP_FIRST, PAD_KEEP_LAST = 0, 1     # mee_find_padded_as flags: which end o
 # mee_search's per-call limits (MEE_SEARCH_MAX_*): 1 <= k <= MAX_K, n_queries * max(k, 8) <= MAX_QK, n_queries rounded up to 32, times dim, <= MAX_QUERY_ELEMS
 SEARCH_MAX_K, SEARCH_MAX_QK, SEARCH_MAX_QUERY_ELEMS = 64, 1536, 12288
 SEARCH_BATCH_MAX_QUERIES = 65536   # MEE_SEARCH_BATCH_MAX_QUERIES: mee_search_batch serves any 1 <= n_queries up to it in one call
+SEARCH_MAX_DIM = 1024   # MEE_SEARCH_MAX_DIM: the widest row the batched searches and score serve; mee_search itself stops at 256
 METRIC_IP, METRIC_COSINE = 0, 1     # MEE_METRIC_*: what mee_search_metric / mee_score_metric rank by
 METRICS = {"ip": METRIC_IP, "cosine": METRIC_COSINE}   # the names LookupTable.search / score take
 ABI_VERSION = 2   # MEE_ABI_VERSION of include/meepo_embedding.h this loader was written against

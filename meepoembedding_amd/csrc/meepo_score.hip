@@ -15,6 +15,7 @@
 //   cosine   score_kernel<.., MEE_METRIC_COSINE> (mee_score_metric): a second accumulator per key, the row's squares, beside the dot product and through
 //            the same shuffles; the query's squares once per unit from the kept values; then search's four operations, dot / (sqrtf(qq) * sqrtf(rr)).
 //   stores   the 4R scores of a step reach lanes 0 .. 4R - 1 by shuffle and leave as one coalesced store, the found bytes likewise.
+//   wide     256 < dim <= MEE_SEARCH_MAX_DIM: score_wide_kernel<P, ROWS, METRIC>, a whole wave per key and four keys per wave step (below).
 // Only vector stores, no atomics, no LDS, nothing of the table is written (hit counters included).
 //
 // The upstream snapshot has no such operator; the semantics are SPEC.md §3 "Score".
@@ -164,6 +165,109 @@ __global__ __launch_bounds__(kScoreWaves * 64) void score_kernel(const int64_t* 
     }
 }
 
+// ---- wide rows, 256 < dim <= MEE_SEARCH_MAX_DIM (DESIGN.md §4 "Score", "Wide rows") -------------------------------------------------------------
+// score_wide_kernel<P, ROWS, METRIC>, P = ceil(dim / 256) in 2 .. 4: a row of 1 to 4 KB does not fit a 16-lane tile's registers R keys deep, so a WHOLE
+// WAVE reduces one key.  A row is walked in P passes of 64 element groups, one group per lane and pass: lane l owns groups l, 64 + l, ... of every
+// row and of its unit's query (P groups, rounded once, kept as fp32: at most 16 registers).  Units, spans, the step's keys and the probe are
+// score_kernel's with one key per 16-lane tile: a wave step is 4 keys — one coalesced key load, the four bucket lines back to back, the shared
+// read-only probe — then the four rows' 4 P groups are requested back to back by all 64 lanes (a pass is 1 KB of an fp32 row, contiguous), each key
+// carries one dot accumulator (cosine: and one squares accumulator) through its passes, and a wave sum (xor 32 .. 1) ends it.  A lane whose group of
+// the last pass lies past the row addresses the row's last group instead — the load stays unconditional — and feeds zeros on both sides.
+// Stores as score_kernel: the step's four scores and found bytes leave lanes 0 .. 3 as one store each.  No LDS, no atomics.
+__device__ __forceinline__ float score_wave_sum(float a) {
+    a += __shfl_xor(a, 32); a += __shfl_xor(a, 16);
+    return score_tile_sum(a);
+}
+
+template <int P, int ROWS, int METRIC>
+__global__ __launch_bounds__(kScoreWaves * 64) void score_wide_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t nb, uint32_t dim4,
+                                                                      const f32x4* __restrict__ queries, const int64_t* __restrict__ keys, uint64_t n_cand, uint64_t span,
+                                                                      uint64_t spans_per_query, uint64_t n_units, float* __restrict__ out, uint8_t* __restrict__ found) {
+    using RT = RowType<ROWS>;
+    constexpr int KPW = 4;   // keys of a wave step: one per tile of the probe
+    const int lane = threadIdx.x & 63, tile = lane >> 4, tl = lane & 15, wave = threadIdx.x >> 6;
+    const typename RT::Group* __restrict__ plane = RT::plane(values);
+    // the lane's group of pass c is 64 c + lane; all but the last pass lie inside the row (64 (P - 1) < dim4 <= 64 P)
+    const bool last_live = (uint32_t)((P - 1) * 64 + lane) < dim4;
+    const uint32_t last = last_live ? (uint32_t)((P - 1) * 64 + lane) : dim4 - 1;
+
+    for (uint64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {   // block-uniform
+        const uint64_t q = unit / spans_per_query, c0 = (unit - q * spans_per_query) * span;
+        const uint64_t c1 = n_cand - c0 < span ? n_cand : c0 + span;
+        f32x4 qv[P];
+#pragma unroll
+        for (int c = 0; c < P; ++c) {
+            const f32x4 x = queries[q * dim4 + (c < P - 1 ? (uint32_t)(c * 64 + lane) : last)];
+            qv[c] = widen_bf16x4(bf16x4_of(x.x, x.y, x.z, x.w));
+        }
+        if (!last_live) qv[P - 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        [[maybe_unused]] float qn = 0.f;   // cosine: the query's norm, from the rounded values
+        if constexpr (METRIC == MEE_METRIC_COSINE) {
+            float qq = 0.f;
+#pragma unroll
+            for (int c = 0; c < P; ++c) {
+                qq = __builtin_fmaf(qv[c].x, qv[c].x, qq); qq = __builtin_fmaf(qv[c].y, qv[c].y, qq);
+                qq = __builtin_fmaf(qv[c].z, qv[c].z, qq); qq = __builtin_fmaf(qv[c].w, qv[c].w, qq);
+            }
+            qn = __builtin_sqrtf(score_wave_sum(qq));
+        }
+        const int64_t* __restrict__ qkeys = keys + q * n_cand;
+        float* __restrict__ qout = out + q * n_cand;
+        uint8_t* __restrict__ qfound = found ? found + q * n_cand : nullptr;
+
+        for (uint64_t base = c0 + (uint64_t)wave * KPW; base < c1; base += kScoreWaves * KPW) {   // wave-uniform
+            // tile t probes position base + t, as score_kernel's round 0
+            const int64_t kmine = (lane < KPW && base + lane < c1) ? qkeys[base + lane] : kEmpty;
+            const int64_t key = __shfl(kmine, tile);
+            const bool act = !reserved_key(key);   // (a position past the span holds EMPTY)
+            const uint64_t b = bucket_of(key, nb);
+            const int64_t kb = act ? tkeys[b * kW + tl] : kEmpty;
+            const int64_t probed = tile_probe(tkeys, nb, key, act, b, kb, tile, tl);
+            int64_t slot[KPW];   // every lane learns the four slots: the whole wave walks each row
+#pragma unroll
+            for (int r = 0; r < KPW; ++r) slot[r] = __shfl(probed, r * kW);
+
+            typename RT::Group row[KPW][P];
+            const bool all_hit = slot[0] >= 0 && slot[1] >= 0 && slot[2] >= 0 && slot[3] >= 0;   // wave-uniform
+#pragma unroll
+            for (int r = 0; r < KPW; ++r) {
+                const uint64_t first = RT::first(all_hit || slot[r] >= 0 ? slot[r] : 0, dim4);
+#pragma unroll
+                for (int c = 0; c < P; ++c) {
+                    const uint32_t g = c < P - 1 ? (uint32_t)(c * 64 + lane) : last;
+                    row[r][c] = (all_hit || slot[r] >= 0) ? plane[first + g] : typename RT::Group{};
+                }
+            }
+
+            float smine = 0.f;
+            int fmine = 0;
+#pragma unroll
+            for (int r = 0; r < KPW; ++r) {
+                float a = 0.f;
+                [[maybe_unused]] float rr = 0.f;
+#pragma unroll
+                for (int c = 0; c < P; ++c) {
+                    f32x4 v = score_operand<ROWS>(row[r][c]);
+                    if (c == P - 1 && !last_live) v = f32x4{0.f, 0.f, 0.f, 0.f};
+                    a = __builtin_fmaf(qv[c].x, v.x, a); a = __builtin_fmaf(qv[c].y, v.y, a);
+                    a = __builtin_fmaf(qv[c].z, v.z, a); a = __builtin_fmaf(qv[c].w, v.w, a);
+                    if constexpr (METRIC == MEE_METRIC_COSINE) {
+                        rr = __builtin_fmaf(v.x, v.x, rr); rr = __builtin_fmaf(v.y, v.y, rr);
+                        rr = __builtin_fmaf(v.z, v.z, rr); rr = __builtin_fmaf(v.w, v.w, rr);
+                    }
+                }
+                a = score_wave_sum(a);
+                if constexpr (METRIC == MEE_METRIC_COSINE) a = a / (qn * __builtin_sqrtf(score_wave_sum(rr)));   // search's four operations; 0 / 0 = NaN is returned
+                if (lane == r) { smine = slot[r] >= 0 ? a + 0.f : -__builtin_inff(); fmine = slot[r] >= 0; }   // + 0.f: a zero leaves as +0.0; a NaN stays a NaN
+            }
+            if (lane < KPW && base + lane < c1) {
+                qout[base + lane] = smine;
+                if (qfound) qfound[base + lane] = (uint8_t)fmine;
+            }
+        }
+    }
+}
+
 }  // namespace mee
 
 using namespace mee;
@@ -173,7 +277,8 @@ template <int METRIC>
 static int score_launch(const mee_table* t, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores, uint8_t* d_out_found,
                         void* stream, const char* name) {
     if (!t) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
-    if (t->dim % 16 || t->dim < 16 || t->dim > 256) return fail(MEE_ERR_INVALID_ARG, "%s: dim must be a multiple of 16 in [16, 256] (got %u)", name, t->dim);
+    if (t->dim % 16 || t->dim < 16 || t->dim > MEE_SEARCH_MAX_DIM)
+        return fail(MEE_ERR_INVALID_ARG, "%s: dim must be a multiple of 16 in [16, %d] (got %u)", name, MEE_SEARCH_MAX_DIM, t->dim);
     if (int rc = refuse_narrow_rows(t, name, false)) return rc;
     if (n_queries == 0 || n_cand == 0) return MEE_OK;   // as mee_find's n == 0
     if (!d_queries || !d_keys || !d_out_scores) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
@@ -184,18 +289,27 @@ static int score_launch(const mee_table* t, const float* d_queries, size_t n_que
     hipStream_t st = as_stream(stream);
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) != hipSuccess || cus <= 0) cus = 256;
-    with_value<1, 2, 3, 4>((int)((t->dim + 63) / 64), [&](auto c4) { with_flag(t->bf16_rows, [&](auto bf16) {
-        // A span is a whole number of block steps: as many as leave the device kScoreBlocksPerCU blocks per CU, at least one (a small Q * C spreads
-        // over as many blocks as it has block steps), at most kScoreMaxSpanSteps and no more than a slate has.
-        const uint64_t block_step = (uint64_t)kScoreWaves * 4 * ScoreShape<c4>::R;
+    // A span is a whole number of block steps: as many as leave the device kScoreBlocksPerCU blocks per CU, at least one (a small Q * C spreads
+    // over as many blocks as it has block steps), at most kScoreMaxSpanSteps and no more than a slate has.  launch(span, spans_per_query, n_units, grid)
+    auto spans = [&](uint64_t block_step, auto launch) {
         const uint64_t steps_per_query = (n_cand + block_step - 1) / block_step;
         uint64_t span_steps = (uint64_t)n_queries * steps_per_query / ((uint64_t)cus * kScoreBlocksPerCU);
         span_steps = span_steps < 1 ? 1 : span_steps > kScoreMaxSpanSteps ? kScoreMaxSpanSteps : span_steps;
         if (span_steps > steps_per_query) span_steps = steps_per_query;
         const uint64_t span = span_steps * block_step, spans_per_query = (n_cand + span - 1) / span, n_units = (uint64_t)n_queries * spans_per_query;
-        const uint32_t grid = n_units < kScoreMaxGrid ? (uint32_t)n_units : kScoreMaxGrid;
-        score_kernel<c4, bf16 ? kRowsBF16 : kRowsF32, METRIC><<<grid, kScoreWaves * 64, 0, st>>>(t->keys, t->values, t->nb, t->dim4, (const f32x4*)d_queries, d_keys, n_cand, span,
-                                                                                        spans_per_query, n_units, d_out_scores, d_out_found);
+        launch(span, spans_per_query, n_units, n_units < kScoreMaxGrid ? (uint32_t)n_units : kScoreMaxGrid);
+    };
+    if (t->dim > 256) with_value<2, 3, 4>((int)((t->dim + 255) / 256), [&](auto p) { with_flag(t->bf16_rows, [&](auto bf16) {   // a wave per key, four keys per wave step
+        spans((uint64_t)kScoreWaves * 4, [&](uint64_t span, uint64_t spans_per_query, uint64_t n_units, uint32_t grid) {
+            score_wide_kernel<p, bf16 ? kRowsBF16 : kRowsF32, METRIC><<<grid, kScoreWaves * 64, 0, st>>>(t->keys, t->values, t->nb, t->dim4, (const f32x4*)d_queries, d_keys, n_cand,
+                                                                                                      span, spans_per_query, n_units, d_out_scores, d_out_found);
+        });
+    }); });
+    else with_value<1, 2, 3, 4>((int)((t->dim + 63) / 64), [&](auto c4) { with_flag(t->bf16_rows, [&](auto bf16) {
+        spans((uint64_t)kScoreWaves * 4 * ScoreShape<c4>::R, [&](uint64_t span, uint64_t spans_per_query, uint64_t n_units, uint32_t grid) {
+            score_kernel<c4, bf16 ? kRowsBF16 : kRowsF32, METRIC><<<grid, kScoreWaves * 64, 0, st>>>(t->keys, t->values, t->nb, t->dim4, (const f32x4*)d_queries, d_keys, n_cand, span,
+                                                                                                  spans_per_query, n_units, d_out_scores, d_out_found);
+        });
     }); });
     MEE_HIP(hipGetLastError());
     return MEE_OK;

@@ -22,6 +22,9 @@
 //   cosine   mee_search_metric(MEE_METRIC_COSINE): the batched launches with search_batch_scan_kernel<.., MEE_METRIC_COSINE> — the row norm from the B registers
 //            (one square root per lane and step), the query norms in LDS, a widened product threshold on the hot path and the exact four-operation
 //            score on the rare one (DESIGN.md §4 "Search", "Metric").  The inner-product instances do not change by it.
+//   wide     256 < dim <= MEE_SEARCH_MAX_DIM, the batched entry points only: search_wide_scan_kernel<ROWS, METRIC> in the batched launches' place — a row
+//            walked in chunks of 256 columns into the same 16 accumulators, one row block of at most 32 queries per block, the absent queries of a
+//            tile not staged (DESIGN.md §4 "Search", "Wide rows").  The selection, the seed pass and the merges are the ones above.
 // Only vector stores, no atomics, nothing of the table is written.
 //
 // The upstream snapshot has no search; the semantics are SPEC.md §3 "Search".
@@ -205,23 +208,106 @@ __device__ __forceinline__ float cosine_prefilter(float thr, float qn) {
     return P * (P > 0.f ? 1.f - 0x1p-21f : 1.f + 0x1p-21f);
 }
 
-// The B operand of a step: lane (half, col) holds elements [16 s + 8 half, + 8) of slot's row for k-step s, as bf16.  A dead lane loads nothing.
+// ---- what the scan bodies share around their matrix instructions --------------------------------------------------------------------------------
+// the selection state of nq queries, its per-query words padded to qp, from LDS at `base` (8-byte aligned): buf_key | thr_key | buf_img | thr_img |
+// thr_sc | cnt | qn (cosine only: [qp] query norms)
+__device__ __forceinline__ SearchSel search_sel_at(unsigned char* base, uint32_t nq, uint32_t qp, uint32_t k, float*& qn) {
+    SearchSel s;
+    s.k = k; s.cap = search_cap(k);
+    s.buf_key = reinterpret_cast<int64_t*>(base);
+    s.thr_key = s.buf_key + (size_t)nq * s.cap;
+    s.buf_img = reinterpret_cast<uint32_t*>(s.thr_key + qp);
+    s.thr_img = s.buf_img + (size_t)nq * s.cap;
+    s.thr_sc = reinterpret_cast<float*>(s.thr_img + qp);
+    s.cnt = reinterpret_cast<uint32_t*>(s.thr_sc + qp);
+    qn = reinterpret_cast<float*>(s.cnt + qp);
+    return s;
+}
+// empty buffers, and every threshold at its seed (search_scan_body) or at nothing; cosine: the staged norms qn[0, qp) are read
+template <int METRIC>
+__device__ __forceinline__ void search_sel_start(const SearchSel& s, const float* qn, uint32_t nq, uint32_t qp, const int64_t* __restrict__ seed_keys,
+                                                 const uint32_t* __restrict__ seed_img, int lane) {
+    const uint32_t k = s.k;
+    if constexpr (METRIC == MEE_METRIC_COSINE) wave_lds_sync();
+    for (uint32_t q = lane; q < qp; q += 64) {
+        uint32_t ti = 0u;
+        int64_t tk = kEmpty;
+        if (seed_img && q < nq) { ti = seed_img[(size_t)q * k + k - 1]; tk = seed_keys[(size_t)q * k + k - 1]; }
+        s.thr_key[q] = tk; s.thr_img[q] = ti; s.cnt[q] = 0u;
+        const float ts = q < nq ? (ti ? image_score(ti) : -__builtin_inff()) : __builtin_inff();   // nothing beats a padding query's threshold
+        if constexpr (METRIC == MEE_METRIC_COSINE) s.thr_sc[q] = cosine_prefilter(ts, qn[q]);
+        else s.thr_sc[q] = ts;
+    }
+    wave_lds_sync();
+}
+// A step's 16 accumulators against the thresholds: accumulator r of lane (half, col) is query qbase + 8 (r / 4) + r % 4 (qbase = 32 rb + 4 half) against
+// the lane's slot (key; cosine: of norm rn, `wild` as the scan bodies set it).  NaN passes no compare.
+template <int METRIC>
+__device__ __forceinline__ void search_select(const SearchSel& s, const float* qn, const f32x16& acc, uint32_t qbase, uint32_t nq, bool live, int64_t key,
+                                              float rn, bool wild, int lane) {
+    const int col = lane & 31;
+    uint32_t hot = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        if constexpr (METRIC == MEE_METRIC_COSINE) {   // thr_sc is cosine_prefilter's value: one multiply and one compare
+            if (__ballot(live && acc[r] >= s.thr_sc[qbase + 8 * (r >> 2) + (r & 3)] * rn)) hot |= 1u << r;
+        } else {
+            if (__ballot(live && acc[r] >= s.thr_sc[qbase + 8 * (r >> 2) + (r & 3)])) hot |= 1u << r;
+        }
+    }
+    if constexpr (METRIC == MEE_METRIC_COSINE) hot = wild ? 0xFFFFu : hot;
+    while (hot) {   // wave-uniform, rare once the thresholds have risen
+        const int r = __ffs(hot) - 1;
+        hot &= hot - 1;
+        float sc = acc[0];
+#pragma unroll
+        for (int i = 1; i < 16; ++i) sc = r == i ? acc[i] : sc;
+        if constexpr (METRIC != MEE_METRIC_COSINE) sc += 0.f;   // -0.0 -> +0.0: equal scores have one image
+        const uint32_t q = qbase + 8 * (r >> 2) + (r & 3);
+        if constexpr (METRIC == MEE_METRIC_COSINE) sc = cosine_score(sc, qn[q], rn);   // the exact score, its zero as +0.0 too; 0 / 0 = NaN is no candidate
+        const uint32_t img = score_image(sc);
+        const bool beat = live && q < nq && sc == sc && search_better(img, key, s.thr_img[q], s.thr_key[q]);
+        search_append(s, q, beat, img, key, lane);
+        if constexpr (METRIC == MEE_METRIC_COSINE) {   // the thresholds a prune may have raised, as the hot path wants them (q < qp: no query's word is a stranger's)
+            if (col == 0) s.thr_sc[q] = cosine_prefilter(s.thr_img[q] ? image_score(s.thr_img[q]) : -__builtin_inff(), qn[q]);
+            wave_lds_sync();
+        }
+    }
+}
+// the block's best k per query, sorted, padded with the empty marker, to rows out_row0 + q of the lists
+__device__ __forceinline__ void search_write_lists(const SearchSel& s, uint32_t nq, size_t out_row0, int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img,
+                                                   int lane) {
+    const uint32_t k = s.k;
+    for (uint32_t q = 0; q < nq; ++q) {   // wave-uniform
+        search_prune_any(s, q, lane);
+        const uint32_t n = s.cnt[q];
+        const size_t o = (out_row0 + q) * k;
+        for (uint32_t i = lane; i < k; i += 64) {
+            ws_img[o + i] = i < n ? s.buf_img[q * s.cap + i] : 0u;
+            ws_keys[o + i] = i < n ? s.buf_key[q * s.cap + i] : kEmpty;
+        }
+    }
+}
+
+// KS k-steps of the B operand from the lane's part of a row: b[s] = the eight elements at `at` + 16 s, as bf16 — one 16-byte load of a bf16 row, two and
+// a round-and-pack of an fp32 row (`at` points at the stored elements: 2 or 4 bytes each).  A dead lane loads nothing and holds zeros; so does a k-step
+// at or past n_ks (the short last chunk of a wide row; n_ks == KS elsewhere, and the test folds away).
 template <int KS, int ROWS>
-__device__ __forceinline__ void search_load_b(const void* __restrict__ values, uint64_t slot, int half, bool live, bf16x8 (&b)[KS]) {
+__device__ __forceinline__ void search_load_ksteps(const void* __restrict__ at, int n_ks, bool live, bf16x8 (&b)[KS]) {
     if constexpr (ROWS == kRowsBF16) {
-        const u32x4* row = reinterpret_cast<const u32x4*>(values) + slot * (uint64_t)(2 * KS) + half;   // a row is 2 KS groups of 16 bytes
+        const u32x4* row = reinterpret_cast<const u32x4*>(at);
         u32x4 v[KS];
 #pragma unroll
-        for (int s = 0; s < KS; ++s) v[s] = live ? __builtin_nontemporal_load(row + 2 * s) : u32x4{0u, 0u, 0u, 0u};
+        for (int s = 0; s < KS; ++s) v[s] = live && s < n_ks ? __builtin_nontemporal_load(row + 2 * s) : u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
         for (int s = 0; s < KS; ++s) b[s] = __builtin_bit_cast(bf16x8, v[s]);
     } else {
-        const f32x4* row = reinterpret_cast<const f32x4*>(values) + slot * (uint64_t)(4 * KS) + 2 * half;   // ... 4 KS groups of four floats
+        const f32x4* row = reinterpret_cast<const f32x4*>(at);
         f32x4 x[KS], y[KS];
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-            x[s] = live ? __builtin_nontemporal_load(row + 4 * s) : f32x4{0.f, 0.f, 0.f, 0.f};
-            y[s] = live ? __builtin_nontemporal_load(row + 4 * s + 1) : f32x4{0.f, 0.f, 0.f, 0.f};
+            x[s] = live && s < n_ks ? __builtin_nontemporal_load(row + 4 * s) : f32x4{0.f, 0.f, 0.f, 0.f};
+            y[s] = live && s < n_ks ? __builtin_nontemporal_load(row + 4 * s + 1) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
@@ -229,6 +315,12 @@ __device__ __forceinline__ void search_load_b(const void* __restrict__ values, u
             b[s] = __builtin_bit_cast(bf16x8, p);
         }
     }
+}
+// The B operand of a step: lane (half, col) holds elements [16 s + 8 half, + 8) of slot's row for k-step s, as bf16.  A dead lane loads nothing.
+template <int KS, int ROWS>
+__device__ __forceinline__ void search_load_b(const void* __restrict__ values, uint64_t slot, int half, bool live, bf16x8 (&b)[KS]) {
+    if constexpr (ROWS == kRowsBF16) search_load_ksteps<KS, ROWS>(reinterpret_cast<const u32x4*>(values) + slot * (uint64_t)(2 * KS) + half, KS, live, b);   // a row is 2 KS groups of 16 bytes
+    else search_load_ksteps<KS, ROWS>(reinterpret_cast<const f32x4*>(values) + slot * (uint64_t)(4 * KS) + 2 * half, KS, live, b);                             // ... 4 KS groups of four floats
 }
 
 // LDS (dynamic; the host computes the same sum, search_lds_bytes): A fragments [n_rb][KS][64] x 16 B | buf_key | thr_key | buf_img | thr_img | thr_sc | cnt
@@ -246,15 +338,8 @@ __device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tke
     const int lane = threadIdx.x, half = lane >> 5, col = lane & 31;
     const uint32_t n_rb = (nq + 31) / 32, qp = n_rb * 32;
     u32x4* const afrag = reinterpret_cast<u32x4*>(search_lds);
-    SearchSel s;
-    s.k = k; s.cap = search_cap(k);
-    s.buf_key = reinterpret_cast<int64_t*>(search_lds + (size_t)qp * dim * 2);
-    s.thr_key = s.buf_key + (size_t)nq * s.cap;
-    s.buf_img = reinterpret_cast<uint32_t*>(s.thr_key + qp);
-    s.thr_img = s.buf_img + (size_t)nq * s.cap;
-    s.thr_sc = reinterpret_cast<float*>(s.thr_img + qp);
-    s.cnt = reinterpret_cast<uint32_t*>(s.thr_sc + qp);
-    [[maybe_unused]] float* const qn = reinterpret_cast<float*>(s.cnt + qp);   // (cosine only)
+    [[maybe_unused]] float* qn;   // (cosine only)
+    const SearchSel s = search_sel_at(search_lds + (size_t)qp * dim * 2, nq, qp, k, qn);
 
     // ---- the queries, rounded once, in fragment order: fragment (rb, ks) is 64 lanes x 16 bytes, lane (half, col) = query rb * 32 + col, elements as B's
     [[maybe_unused]] float qq = 0.f;
@@ -275,17 +360,7 @@ __device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tke
             }
         }
     }
-    if constexpr (METRIC == MEE_METRIC_COSINE) wave_lds_sync();
-    for (uint32_t q = lane; q < qp; q += 64) {
-        uint32_t ti = 0u;
-        int64_t tk = kEmpty;
-        if (seed_img && q < nq) { ti = seed_img[(size_t)q * k + k - 1]; tk = seed_keys[(size_t)q * k + k - 1]; }
-        s.thr_key[q] = tk; s.thr_img[q] = ti; s.cnt[q] = 0u;
-        const float ts = q < nq ? (ti ? image_score(ti) : -__builtin_inff()) : __builtin_inff();   // nothing beats a padding query's threshold
-        if constexpr (METRIC == MEE_METRIC_COSINE) s.thr_sc[q] = cosine_prefilter(ts, qn[q]);
-        else s.thr_sc[q] = ts;
-    }
-    wave_lds_sync();
+    search_sel_start<METRIC>(s, qn, nq, qp, seed_keys, seed_img, lane);
 
     // ---- the block's steps: 32 consecutive slots each, the keys one step ahead
     int64_t key_next = kEmpty;
@@ -318,48 +393,12 @@ __device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tke
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, afrag[(rb * KS + ks) * 64 + lane]), b[ks], acc, 0, 0, 0);
-            // accumulator r of lane (half, col): query rb * 32 + 8 (r / 4) + 4 half + r % 4 against slot col.  NaN passes no compare.
-            const uint32_t qbase = rb * 32 + 4 * half;
-            uint32_t hot = 0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if constexpr (METRIC == MEE_METRIC_COSINE) {   // thr_sc is cosine_prefilter's value: one multiply and one compare
-                    if (__ballot(live && acc[r] >= s.thr_sc[qbase + 8 * (r >> 2) + (r & 3)] * rn)) hot |= 1u << r;
-                } else {
-                    if (__ballot(live && acc[r] >= s.thr_sc[qbase + 8 * (r >> 2) + (r & 3)])) hot |= 1u << r;
-                }
-            }
-            if constexpr (METRIC == MEE_METRIC_COSINE) hot = wild ? 0xFFFFu : hot;
-            while (hot) {   // wave-uniform, rare once the thresholds have risen
-                const int r = __ffs(hot) - 1;
-                hot &= hot - 1;
-                float sc = acc[0];
-#pragma unroll
-                for (int i = 1; i < 16; ++i) sc = r == i ? acc[i] : sc;
-                if constexpr (METRIC != MEE_METRIC_COSINE) sc += 0.f;   // -0.0 -> +0.0: equal scores have one image
-                const uint32_t q = qbase + 8 * (r >> 2) + (r & 3);
-                if constexpr (METRIC == MEE_METRIC_COSINE) sc = cosine_score(sc, qn[q], rn);   // the exact score, its zero as +0.0 too; 0 / 0 = NaN is no candidate
-                const uint32_t img = score_image(sc);
-                const bool beat = live && q < nq && sc == sc && search_better(img, key, s.thr_img[q], s.thr_key[q]);
-                search_append(s, q, beat, img, key, lane);
-                if constexpr (METRIC == MEE_METRIC_COSINE) {   // the thresholds a prune may have raised, as the hot path wants them (q < qp: no query's word is a stranger's)
-                    if (col == 0) s.thr_sc[q] = cosine_prefilter(s.thr_img[q] ? image_score(s.thr_img[q]) : -__builtin_inff(), qn[q]);
-                    wave_lds_sync();
-                }
-            }
+            search_select<METRIC>(s, qn, acc, rb * 32 + 4 * half, nq, live, key, rn, wild, lane);
         }
     }
 
     // ---- the block's best k per query, sorted, padded with the empty marker
-    for (uint32_t q = 0; q < nq; ++q) {   // wave-uniform
-        search_prune_any(s, q, lane);
-        const uint32_t n = s.cnt[q];
-        const size_t o = (out_row0 + q) * k;
-        for (uint32_t i = lane; i < k; i += 64) {
-            ws_img[o + i] = i < n ? s.buf_img[q * s.cap + i] : 0u;
-            ws_keys[o + i] = i < n ? s.buf_key[q * s.cap + i] : kEmpty;
-        }
-    }
+    search_write_lists(s, nq, out_row0, ws_keys, ws_img, lane);
 }
 
 template <int KS, int ROWS>
@@ -388,6 +427,119 @@ __global__ __launch_bounds__(64) void search_batch_scan_kernel(const int64_t* __
     if (s0 > s1) s0 = s1;
     search_scan_body<KS, ROWS, METRIC>(tkeys, values, capacity, queries + (size_t)q0 * (16 * KS), nq, k, s0, s1, seed_keys ? seed_keys + (size_t)q0 * k : nullptr,
                                seed_img ? seed_img + (size_t)q0 * k : nullptr, (size_t)range * nq_all + q0, ws_keys, ws_img);
+}
+
+// ---- wide rows, 256 < dim <= MEE_SEARCH_MAX_DIM (DESIGN.md §4 "Search", "Wide rows") -------------------------------------------------------------
+// A row no longer fits the registers as one B operand, and 32 queries of it no longer fit the LDS beside the selection state.  So the row is walked
+// in CHUNKS of kWideChunkKS k-steps (256 columns; the last chunk of a row may be shorter): per step a chunk of B is loaded as search_load_b loads a
+// row, its matrix instructions go into the step's 16 accumulators, and only then is the next chunk asked for — one chunk of operand registers is live
+// at a time (an fp32 chunk is 128 registers in flight before its packing, so a second one would leave no room for two waves per SIMD; the latency
+// is left to the other waves of the CU).  A block serves ONE row block: a tile of nq <= 32 queries, B is never needed twice.  The A fragments hold
+// the tile's nq queries and nothing for the absent ones: fragment (ks, half) is nq x 16 bytes, query col at [col] — lane-linear in each half — and a
+// lane whose col >= nq feeds zeros without an LDS read.
+// LDS: A fragments [dim / 16][2][nq] x 16 B | the selection state of nq queries, per-query words padded to 32 (search_sel_at).
+constexpr int kWideChunkKS = 16;
+constexpr uint32_t kWideLdsBudget = 40 * 1024;   // per block: four blocks share a CU's 160 KB (search_wide_tile)
+__host__ __device__ constexpr uint32_t search_wide_lds_bytes(uint32_t dim, uint32_t nq, uint32_t k) { return nq * (dim * 2 + search_cap(k) * 12) + 32 * 24; }
+// the queries of a tile: as many as the budget holds, in eights (a fragment's half is then whole 128-byte rows of the LDS), at most one row block
+__host__ __device__ constexpr uint32_t search_wide_tile(uint32_t dim, uint32_t k) {
+    const uint32_t t = (kWideLdsBudget - 32 * 24) / (dim * 2 + search_cap(k) * 12) / 8 * 8;
+    return t < 32 ? t : 32;
+}
+static_assert(search_wide_tile(MEE_SEARCH_MAX_DIM, MEE_SEARCH_MAX_K) >= 8, "every (dim, k) is served in tiles of at least 8 queries");
+
+// One chunk of a step: n_ks k-steps from k-step ks0 on (FULL: n_ks == kWideChunkKS, and no test of it is left in the code) of the row part at `at`
+// into acc, the squares of the operand into rr (cosine).
+template <int ROWS, int METRIC, bool FULL>
+__device__ __forceinline__ void search_wide_chunk(const void* __restrict__ at, const u32x4* afrag, uint32_t ks0, int n_ks, uint32_t nq, int half, int col, bool live,
+                                                  f32x16& acc, float& rr) {
+    bf16x8 b[kWideChunkKS];
+    search_load_ksteps<kWideChunkKS, ROWS>(at, FULL ? kWideChunkKS : n_ks, live, b);
+#pragma unroll
+    for (int s = 0; s < kWideChunkKS; ++s) {
+        if (FULL || s < n_ks) {   // wave-uniform: the fragments of a k-step past the row do not exist
+            if constexpr (METRIC == MEE_METRIC_COSINE) rr = sum_squares(__builtin_bit_cast(u32x4, b[s]), rr);
+            const u32x4 a = (uint32_t)col < nq ? afrag[((size_t)(ks0 + s) * 2 + half) * nq + col] : u32x4{0u, 0u, 0u, 0u};
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), b[s], acc, 0, 0, 0);
+        }
+    }
+}
+
+// search_scan_body for a wide row: dim is a run-time value, nq <= 32; everything else as there.
+template <int ROWS, int METRIC>
+__device__ __forceinline__ void search_wide_scan_body(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity, uint32_t dim,
+                                                      const float* __restrict__ queries, uint32_t nq, uint32_t k, uint64_t s0, uint64_t s1,
+                                                      const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img, size_t out_row0,
+                                                      int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char search_lds[];
+    const int lane = threadIdx.x, half = lane >> 5, col = lane & 31;
+    const uint32_t ks_all = dim / 16, n_full = ks_all / kWideChunkKS * kWideChunkKS;
+    constexpr uint32_t esz = ROWS == kRowsBF16 ? 2 : 4;   // bytes of a stored element
+    u32x4* const afrag = reinterpret_cast<u32x4*>(search_lds);
+    [[maybe_unused]] float* qn;   // (cosine only)
+    const SearchSel s = search_sel_at(search_lds + (size_t)nq * dim * 2, nq, 32, k, qn);
+
+    // ---- the tile's queries, rounded once; a query's norm from the rounded values, a padding query's as 0
+    [[maybe_unused]] float qq = 0.f;
+    if ((uint32_t)col < nq) {
+        const f32x4* src = reinterpret_cast<const f32x4*>(queries + (size_t)col * dim + 8 * half);
+        for (uint32_t ks = 0; ks < ks_all; ++ks) {
+            const f32x4 x = src[4 * ks], y = src[4 * ks + 1];
+            const u32x4 p = {bf16x2_of(x.x, x.y), bf16x2_of(x.z, x.w), bf16x2_of(y.x, y.y), bf16x2_of(y.z, y.w)};
+            afrag[((size_t)ks * 2 + half) * nq + col] = p;
+            if constexpr (METRIC == MEE_METRIC_COSINE) qq = sum_squares(p, qq);
+        }
+    }
+    if constexpr (METRIC == MEE_METRIC_COSINE) {
+        qq += __shfl_xor(qq, 32);
+        if (half == 0) qn[col] = __builtin_sqrtf(qq);
+    }
+    search_sel_start<METRIC>(s, qn, nq, 32, seed_keys, seed_img, lane);   // (its fence also stands between the fragments' stores and their reads)
+
+    // ---- the block's steps, as search_scan_body walks them
+    int64_t key_next = kEmpty;
+    if (s0 < s1 && s0 * 32 + col < capacity) key_next = __builtin_nontemporal_load(tkeys + s0 * 32 + col);
+    for (uint64_t step = s0; step < s1; ++step) {   // wave-uniform
+        const int64_t key = key_next;
+        const uint64_t slot = step * 32 + col;
+        key_next = kEmpty;
+        if (step + 1 < s1 && slot + 32 < capacity) key_next = __builtin_nontemporal_load(tkeys + slot + 32);   // slots at or past capacity are never addressed
+        const bool live = key > kReclaimed;
+        if (!__ballot(live)) continue;   // wave-uniform
+        const unsigned char* const row = reinterpret_cast<const unsigned char*>(values) + (slot * dim + 8 * half) * esz;   // the lane's eight elements of k-step 0
+        f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float rr = 0.f;
+#pragma unroll 1
+        for (uint32_t ks0 = 0; ks0 < n_full; ks0 += kWideChunkKS)
+            search_wide_chunk<ROWS, METRIC, true>(row + (size_t)ks0 * 16 * esz, afrag, ks0, kWideChunkKS, nq, half, col, live, acc, rr);
+        if (n_full < ks_all)
+            search_wide_chunk<ROWS, METRIC, false>(row + (size_t)n_full * 16 * esz, afrag, n_full, (int)(ks_all - n_full), nq, half, col, live, acc, rr);
+        [[maybe_unused]] float rn = 0.f;
+        [[maybe_unused]] bool wild = false;
+        if constexpr (METRIC == MEE_METRIC_COSINE) {   // as search_scan_body: one shuffle and one square root per lane and step, behind the last chunk
+            rr += __shfl_xor(rr, 32);
+            rn = rr > 0.f ? __builtin_sqrtf(rr) : __builtin_nanf("");
+            wild = __ballot(live && (rn > kCosNormMax || (rn < kCosNormMin && rn > 0.f))) != 0;
+        }
+        search_select<METRIC>(s, qn, acc, 4 * half, nq, live, key, rn, wild, lane);
+    }
+    search_write_lists(s, nq, out_row0, ws_keys, ws_img, lane);
+}
+
+// search_batch_scan_kernel's grid and lists for a wide row: tile <= 32
+template <int ROWS, int METRIC>
+__global__ __launch_bounds__(64) void search_wide_scan_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity, uint32_t dim,
+                                                              const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
+                                                              uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
+                                                              const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
+                                                              int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
+    const uint32_t t = blockIdx.x % n_tiles, range = blockIdx.x / n_tiles;
+    const uint32_t q0 = t * tile, nq = nq_all - q0 < tile ? nq_all - q0 : tile;
+    uint64_t s0 = step0 + (uint64_t)range * steps_per_range, s1 = s0 + steps_per_range;
+    if (s1 > step_end) s1 = step_end;
+    if (s0 > s1) s0 = s1;
+    search_wide_scan_body<ROWS, METRIC>(tkeys, values, capacity, dim, queries + (size_t)q0 * dim, nq, k, s0, s1, seed_keys ? seed_keys + (size_t)q0 * k : nullptr,
+                                        seed_img ? seed_img + (size_t)q0 * k : nullptr, (size_t)range * nq_all + q0, ws_keys, ws_img);
 }
 
 // Query q's best k of n_lists sorted lists, list l at [(l * nq + q) * k, + k): lane i < k ends with entry i in (img, key), image 0 behind the real ones.
@@ -464,7 +616,8 @@ static size_t search_lds_bytes(uint32_t dim, size_t nq, uint32_t k, int metric =
 // is held against mee_search_batch's cap instead of the per-call limits.
 static int search_check(const mee_table* t, size_t nq, uint32_t k, const char* name, uint32_t* max_grid, bool batch = false) {
     if (!t) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
-    if (t->dim % 16 || t->dim < 16 || t->dim > 256) return fail(MEE_ERR_INVALID_ARG, "%s: dim must be a multiple of 16 in [16, 256] (got %u)", name, t->dim);
+    const uint32_t max_dim = batch ? MEE_SEARCH_MAX_DIM : 256;   // the batched entry points alone have the wide scan
+    if (t->dim % 16 || t->dim < 16 || t->dim > max_dim) return fail(MEE_ERR_INVALID_ARG, "%s: dim must be a multiple of 16 in [16, %u] (got %u)", name, max_dim, t->dim);
     if (k < 1 || k > MEE_SEARCH_MAX_K) return fail(MEE_ERR_INVALID_ARG, "%s: k must be in [1, %d] (got %u)", name, MEE_SEARCH_MAX_K, k);
     const size_t kk = k < kSearchMinCap ? kSearchMinCap : k;
     if (batch && (nq < 1 || nq > MEE_SEARCH_BATCH_MAX_QUERIES))
@@ -495,6 +648,7 @@ constexpr uint32_t kSearchTileMaxQueries = MEE_SEARCH_TILE_MAX_QUERIES;  // a ti
 // The queries of one tile: at most what one mee_search call accepts for this k and dim, so a block's LDS stays inside search_lds_bytes' budget, and
 // at most one row block — a fraction of that LDS, so more waves stay resident; measured against tiles at the per-call limit in profiles/search.md.
 static uint32_t search_batch_tile(uint32_t dim, uint32_t k, int metric) {
+    if (dim > 256) return search_wide_tile(dim, k);   // the wide scan's own rule: its LDS budget, one row block
     const uint32_t by_qk = MEE_SEARCH_MAX_QK / (k < kSearchMinCap ? kSearchMinCap : k), by_elems = MEE_SEARCH_MAX_QUERY_ELEMS / dim / 32 * 32;
     const uint32_t limit = by_qk < by_elems ? by_qk : by_elems;
     const uint32_t cap = metric == MEE_METRIC_COSINE && kSearchCosineTileMax < kSearchTileMaxQueries ? kSearchCosineTileMax : kSearchTileMaxQueries;
@@ -559,18 +713,30 @@ static int search_batch_launch(const mee_table* t, const float* d_queries, size_
     const size_t list = (size_t)nq * k;
     int64_t* ws_keys = (int64_t*)d_workspace;
     uint32_t* ws_img = (uint32_t*)(ws_keys + p.lists() * list);
-    const size_t lds = search_lds_bytes(t->dim, p.tile < nq ? p.tile : nq, k, METRIC);
+    const bool wide = t->dim > 256;
+    const size_t lds = wide ? search_wide_lds_bytes(t->dim, p.tile < nq ? p.tile : nq, k) : search_lds_bytes(t->dim, p.tile < nq ? p.tile : nq, k, METRIC);
     const bool seeded = p.seed_ranges != 0;
-    with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)(t->dim / 16), [&](auto ks) { with_flag(t->bf16_rows, [&](auto bf16) {
-        auto scan = search_batch_scan_kernel<ks, bf16 ? kRowsBF16 : kRowsF32, METRIC>;
+    // the seed pass and its merge, then the main scan from the seed's thresholds; scan(blocks, step0, step_end, steps per range, seed lists, lists out)
+    // launches the row shape's kernel
+    auto passes = [&](auto scan) {
         if (seeded) {
             const size_t so = (1 + (size_t)p.ranges) * list;
-            scan<<<p.n_tiles * p.seed_ranges, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, 0, p.seed_steps, p.per_seed_range,
-                                                             nullptr, nullptr, ws_keys + so, ws_img + so);
+            scan(p.n_tiles * p.seed_ranges, 0, p.seed_steps, p.per_seed_range, nullptr, nullptr, ws_keys + so, ws_img + so);
             search_seed_merge_kernel<<<nq, 64, 0, st>>>(ws_keys + so, ws_img + so, p.seed_ranges, nq, k, ws_keys, ws_img);
         }
-        scan<<<p.n_tiles * p.ranges, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, p.seed_steps, n_steps, p.per_range,
-                                                    seeded ? ws_keys : nullptr, seeded ? ws_img : nullptr, ws_keys + list, ws_img + list);
+        scan(p.n_tiles * p.ranges, p.seed_steps, n_steps, p.per_range, seeded ? ws_keys : nullptr, seeded ? ws_img : nullptr, ws_keys + list, ws_img + list);
+    };
+    if (wide) with_flag(t->bf16_rows, [&](auto bf16) {
+        passes([&](uint32_t blocks, uint64_t step0, uint64_t step_end, uint64_t per_range, const int64_t* seed_keys, const uint32_t* seed_img, int64_t* out_keys, uint32_t* out_img) {
+            search_wide_scan_kernel<bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, lds, st>>>(t->keys, t->values, t->capacity, t->dim, d_queries, nq, p.tile, p.n_tiles, k, step0,
+                                                                                               step_end, per_range, seed_keys, seed_img, out_keys, out_img);
+        });
+    });
+    else with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)(t->dim / 16), [&](auto ks) { with_flag(t->bf16_rows, [&](auto bf16) {
+        passes([&](uint32_t blocks, uint64_t step0, uint64_t step_end, uint64_t per_range, const int64_t* seed_keys, const uint32_t* seed_img, int64_t* out_keys, uint32_t* out_img) {
+            search_batch_scan_kernel<ks, bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, step0, step_end,
+                                                                                                    per_range, seed_keys, seed_img, out_keys, out_img);
+        });
     }); });
     // the seed area is one more list in front of the main scan's: the prefix is not scanned again
     if (seeded) search_merge_kernel<<<nq, 64, 0, st>>>(ws_keys, ws_img, 1 + p.ranges, nq, k, d_out_keys, d_out_scores, d_out_counts);

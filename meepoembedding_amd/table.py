@@ -782,9 +782,10 @@ class LookupTable:
         product with it, scanned in place — no [N, dim] copy, never stale -> (keys [Q, k] int64, scores [Q, k] float32), best first, equal scores
         by the smaller key; counts=True adds the number of real entries per query ([Q] int32).  Both operands are rounded once to bf16 (an
         fp32-row table is searched at bf16 precision), the sum is fp32.  A query with fewer than k candidates is padded with key INT64_MIN and
-        score -inf; a candidate with a NaN score is never returned.  fp32-row and bf16-row tables, dim a multiple of 16 in [16, 256], k in
+        score -inf; a candidate with a NaN score is never returned.  fp32-row and bf16-row tables, dim a multiple of 16 in [16, SEARCH_MAX_DIM], k in
         [1, SEARCH_MAX_K]; a batch beyond mee_search's per-call limits is ONE mee_search_batch call (tiled queries, a seeded scan; chunks of
-        SEARCH_BATCH_MAX_QUERIES beyond that cap) with the same answer.  The workspace is a
+        SEARCH_BATCH_MAX_QUERIES beyond that cap) with the same answer, and so is every search of a row wider than 256, whatever Q (the scan
+        then walks a row in chunks of 256 columns: DESIGN.md §4 "Search", "Wide rows").  The workspace is a
         tensor cached by size, one per stream that searched (the native calls of one search share it in stream order).  No gradient.
         metric="cosine" (mee_search_metric): the score is dot / (|q| |row|) with both norms taken from the rounded operands inside the scan — no
         normalised copy of the table; a zero row is never returned, a zero query has count 0.  Any Q goes through the batched launches."""
@@ -796,15 +797,16 @@ class LookupTable:
             raise MeepoError(_lib.ERR_INVALID_ARG, f"k must be an int in [1, {_lib.SEARCH_MAX_K}] (got {k!r})")
         q = queries.contiguous()
         nq = q.shape[0]
-        per_call = min(_lib.SEARCH_MAX_QK // max(k, 8), max(_lib.SEARCH_MAX_QUERY_ELEMS // max(self.dim, 1) // 32 * 32, 1))
+        wide = self.dim > 256   # mee_search has no such row: every Q through the batched launches
+        per_call = 0 if wide else min(_lib.SEARCH_MAX_QK // max(k, 8), max(_lib.SEARCH_MAX_QUERY_ELEMS // max(self.dim, 1) // 32 * 32, 1))
         need = C.c_uint64()
-        batched = nq > per_call   # past one call's limits: mee_search_batch, tiled and seeded, in chunks of its own cap
+        batched = wide or nq > per_call   # past one call's limits: mee_search_batch, tiled and seeded, in chunks of its own cap
         if metric != "ip":   # every Q through the batched launches of that metric
             per_call = _lib.SEARCH_BATCH_MAX_QUERIES
             check(_lib.lib().mee_search_metric_workspace_bytes(self._h, _lib.METRICS[metric], max(min(nq, per_call), 1), k, C.byref(need)))
         elif batched:
             per_call = _lib.SEARCH_BATCH_MAX_QUERIES
-            check(_lib.lib().mee_search_batch_workspace_bytes(self._h, min(nq, per_call), k, C.byref(need)))
+            check(_lib.lib().mee_search_batch_workspace_bytes(self._h, max(min(nq, per_call), 1), k, C.byref(need)))
         else:
             check(_lib.lib().mee_search_workspace_bytes(self._h, max(nq, 1), k, C.byref(need)))   # (every refusal of the table comes from here, before any launch)
         out_keys = _buffer(out_keys, "out_keys", torch.int64, (nq, k), self.device)
@@ -831,7 +833,8 @@ class LookupTable:
         `keys` [Q, C] int64 — a slate from search, another retriever or business rules; duplicates allowed -> (scores [Q, C] float32, found [Q, C]
         uint8 as find returns it).  One launch probes, gathers and reduces: no [Q, C, dim] block.  The score is search's — both operands rounded
         once to bf16, fp32 sum — so search's own keys score search's scores; an absent or reserved key (search's INT64_MIN padding) scores -inf
-        with found 0, a NaN score is returned as NaN.  fp32-row and bf16-row tables, dim a multiple of 16 in [16, 256].  No gradient.
+        with found 0, a NaN score is returned as NaN.  fp32-row and bf16-row tables, dim a multiple of 16 in [16, SEARCH_MAX_DIM] (past 256 a
+        whole wave reduces a key: DESIGN.md §4 "Score", "Wide rows").  No gradient.
         metric="cosine" (mee_score_metric): search's cosine, dot / (|q| |row|); a zero row or a zero query scores NaN with found 1."""
         if metric not in _lib.METRICS:
             raise MeepoError(_lib.ERR_INVALID_ARG, f"metric must be one of {sorted(_lib.METRICS)} (got {metric!r})")

@@ -60,7 +60,12 @@ def timed_rows(rows, reps, chunk=5):
     return {nm: total[nm] / (reps // chunk * chunk) for nm in names}
 
 
+WIDE = args.dim > 256   # mee_search has no such row: every Q is ONE mee_search_batch call (DESIGN.md §4 "Search", "Wide rows"); no split-call row
+
+
 def per_call_limit(k):
+    if WIDE:
+        return 0
     return min(_lib.SEARCH_MAX_QK // max(k, 8), _lib.SEARCH_MAX_QUERY_ELEMS // args.dim // 32 * 32)
 
 
@@ -144,9 +149,11 @@ for value_dtype in (torch.float32, torch.bfloat16):
             us = {nm: (passes[0][nm] + passes[1][nm]) / 2 for nm in rows}
             # this tree: one call either way; past the limits every tile's blocks ask for the table (tiles that walk one range may meet in L2), in
             # four launches.  A build without the batch entry point: `split` calls of two launches, each a scan of the table.
-            split = -(-nq // per_call_limit(k))
-            tiles = -(-nq // min(per_call_limit(k), 32)) if nq > per_call_limit(k) else 1   # search_batch_tile: one row block at the most
-            rec = {"metric": args.metric, "rows": str(value_dtype).split(".")[1], "keys": n, "dim": args.dim, "Q": nq, "k": k, "native_calls": 1, "launches": 4 if tiles > 1 else 2,
+            split = -(-nq // per_call_limit(k)) if not WIDE else 0
+            tiles = -(-nq // min(per_call_limit(k), 32)) if not WIDE and nq > per_call_limit(k) else 1   # search_batch_tile: one row block at the most
+            if WIDE:   # search_wide_tile: what 40 KB of LDS hold of rounded queries and candidate buffers, in eights, one row block at the most
+                tiles = -(-nq // min((40 * 1024 - 768) // (args.dim * 2 + 2 * max(k, 8) * 12) // 8 * 8, 32))
+            rec = {"metric": args.metric, "rows": str(value_dtype).split(".")[1], "keys": n, "dim": args.dim, "Q": nq, "k": k, "native_calls": 1, "launches": 4 if tiles > 1 or WIDE else 2,
                    "tiles": tiles, "split_native_calls": split, "split_launches": 2 * split,
                    "us": {nm: round(v, 1) for nm, v in us.items()}, "spread_us": {nm: round(abs(passes[0][nm] - passes[1][nm]), 1) for nm in rows},
                    "search_bytes": tiles * scan_bytes, "split_bytes": split * scan_bytes, "matmul_bytes": n * args.dim * 2 + 2 * nq * n * 2,
