@@ -32,7 +32,12 @@ check = (users.to(torch.bfloat16).float()[:, None, :] * rows.view(32, k, dim)).s
 assert found.all() and torch.allclose(check, scores, rtol=1e-4, atol=1e-4) and (scores[:, :-1] >= scores[:, 1:]).all()
 print(f"{serving.size()} items served; user 0's best: item {int(keys[0, 0])} at {float(scores[0, 0]):.4f}, {int(counts[0])} candidates returned")
 
-wide, wide_scores = serving.search(users, 4 * k)                # re-ranking: a wider candidate set, mixed with ids from elsewhere (some unknown here) ...
+page2, scores2p = serving.search(users, k, exclude=keys)         # "more like this": the best k EXCEPT page one's keys, filtered inside the scan — ranks k .. 2k - 1
+twice = serving.search(users, 2 * k)[0]
+assert torch.equal(page2, twice[:, k:]) and not (page2[:, :, None] == keys[:, None, :]).any()
+print(f"user 0's page two starts at item {int(page2[0, 0])} ({float(scores2p[0, 0]):.4f}); a seen list of up to 4096 ids per user goes the same way")
+
+wide, wide_scores = serving.search(users, 4 * k)               # re-ranking: a wider candidate set, mixed with ids from elsewhere (some unknown here) ...
 slate = torch.cat([wide, torch.randint(items, 2 * items, (32, k), device=dev)], dim=1)
 rescored, known = serving.score(users, slate)                   # ... scored in one launch: probe, row gather and dot product, no [32, 5k, dim] block
 assert known[:, :4 * k].all() and torch.allclose(rescored[:, :4 * k], wide_scores, rtol=1e-4, atol=1e-4)   # search's own keys score search's scores (to the bit on exactly summable data)

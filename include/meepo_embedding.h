@@ -1223,6 +1223,29 @@ int mee_search_metric(const mee_table* t, int metric, const float* d_queries, si
 int mee_score_metric(const mee_table* t, int metric, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand,
                      float* d_out_scores, uint8_t* d_out_found /* nullable */, void* stream);
 
+/* ---- exclusion: "the best k except these" (SPEC.md §3 "Search", "Exclusion") ------------------------------------------------------------------------
+ * mee_search_filtered is mee_search_metric with one change: the CANDIDATES of query q are the live slots whose key is not in q's exclude row.
+ * d_exclude is [exclude_rows][n_exclude] int64 on the device, 8-byte aligned; exclude_rows == n_queries gives every query its own row,
+ * exclude_rows == 1 applies the one row to every query.  Entries may be any int64: duplicates are allowed, an absent or removed key matches
+ * nothing, and so does an entry <= MEE_RECLAIMED_KEY — INT64_MIN, search's own padding key, among them, so the keys of a previous answer are a legal
+ * exclude row as they stand (and give the next page).  INT64_MAX is an ordinary key: excluded if and only if it is listed.
+ * The score under either metric, the total order, the NaN rule, the padding, d_out_counts (now min(k, non-excluded non-NaN live rows)), the
+ * exact-sum guarantee and both error bounds are mee_search_metric's, word for word: the filter sits where a candidate is about to enter a query's
+ * buffer, so an excluded key is never kept and never raises a threshold.
+ * Launches: one preparation launch (each exclude row sorted into the workspace, entries <= MEE_RECLAIMED_KEY dropped), then mee_search_metric's.
+ * d_workspace: mee_search_filtered_workspace_bytes(...) bytes, 8-byte aligned:
+ *     exclude_rows * P * 8 + round_up(exclude_rows * 4, 8) + mee_search_metric_workspace_bytes(t, metric, n_queries, k),   P = n_exclude rounded up to a power of two.
+ * Limits: 1 <= n_exclude <= MEE_SEARCH_MAX_EXCLUDE; exclude_rows is n_queries or 1; dim, k, n_queries, the tables served (int8 rows:
+ * MEE_ERR_UNSUPPORTED) and every other refusal are mee_search_metric's.  A null or misaligned pointer, a bad limit and an unknown metric are
+ * MEE_ERR_INVALID_ARG before any launch.  No host synchronisation, no allocation, no memset, no atomics, vector stores only, nothing of the table
+ * is written: safe under stream capture; d_exclude is read by the preparation launch only. */
+#define MEE_SEARCH_MAX_EXCLUDE 4096
+int mee_search_filtered_workspace_bytes(const mee_table* t, int metric, size_t n_queries, uint32_t k, size_t exclude_rows, size_t n_exclude,
+                                        uint64_t* bytes_out);
+int mee_search_filtered(const mee_table* t, int metric, const float* d_queries, size_t n_queries, uint32_t k, const int64_t* d_exclude,
+                        size_t exclude_rows, size_t n_exclude, int64_t* d_out_keys, float* d_out_scores, uint32_t* d_out_counts /* nullable */,
+                        void* d_workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,8 @@ PAD_KEEP_FIRST, PAD_KEEP_LAST = 0, 1     # mee_find_padded_as flags: which end o
 SEARCH_MAX_K, SEARCH_MAX_QK, SEARCH_MAX_QUERY_ELEMS = 64, 1536, 12288
 SEARCH_BATCH_MAX_QUERIES = 65536   # MEE_SEARCH_BATCH_MAX_QUERIES: mee_search_batch serves any 1 <= n_queries up to it in one call
 SEARCH_MAX_DIM = 1024   # MEE_SEARCH_MAX_DIM: the widest row the batched searches and score serve; mee_search itself stops at 256
-METRIC_IP, METRIC_COSINE = 0, 1     # MEE_METRIC_*: what mee_search_metric / mee_score_metric rank by
+SEARCH_MAX_EXCLUDE = 4096   # MEE_SEARCH_MAX_EXCLUDE: the keys of one exclude row of mee_search_filtered
+METRIC_IP, METRIC_COSINE = 0, 1    # MEE_METRIC_*: what mee_search_metric / mee_score_metric rank by
 METRICS = {"ip": METRIC_IP, "cosine": METRIC_COSINE}   # the names LookupTable.search / score take
 ABI_VERSION = 2   # MEE_ABI_VERSION of include/meepo_embedding.h this loader was written against
 EMPTY_KEY = -(1 << 63)
@@ -307,6 +308,9 @@ PROTOTYPES = {
     "mee_search_metric_workspace_bytes": (C.c_int, [_vp, C.c_int, _sz, _u32, C.POINTER(_u64)]),
     "mee_search_metric": (C.c_int, [_vp, C.c_int, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _vp]),
     "mee_score_metric": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    # filtered search (table, metric, queries, n_queries, k, exclude [exclude_rows, n_exclude], exclude_rows, n_exclude, out_keys, out_scores, out_counts | null, workspace, stream)
+    "mee_search_filtered_workspace_bytes": (C.c_int, [_vp, C.c_int, _sz, _u32, _sz, _sz, C.POINTER(_u64)]),
+    "mee_search_filtered": (C.c_int, [_vp, C.c_int, _vp, _sz, _u32, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _NARROW_ROWS = {torch.bfloat16: "a bf16-row table (value_dtype=torch.bfloat16) is a serving table with find, find_pooled, insert, assign, ",

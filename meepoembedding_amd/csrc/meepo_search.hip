@@ -25,6 +25,10 @@
 //   wide     256 < dim <= MEE_SEARCH_MAX_DIM, the batched entry points only: search_wide_scan_kernel<ROWS, METRIC> in the batched launches' place — a row
 //            walked in chunks of 256 columns into the same 16 accumulators, one row block of at most 32 queries per block, the absent queries of a
 //            tile not staged (DESIGN.md §4 "Search", "Wide rows").  The selection, the seed pass and the merges are the ones above.
+//   exclude  mee_search_filtered, "the best k except these": search_exclude_prepare_kernel sorts each exclude row into the workspace (an LDS bitonic sort,
+//            one block a row), then the batched launches with the FILTER instances of the two scan bodies — a lane that is about to append first looks
+//            its key up in its query's sorted row by a lower-bound search in global memory (DESIGN.md §4 "Search", "Exclusion").  The hot path, the
+//            merges and every unfiltered instance do not change by it.
 // Only vector stores, no atomics, nothing of the table is written.
 //
 // The upstream snapshot has no search; the semantics are SPEC.md §3 "Search".
@@ -165,6 +169,69 @@ __device__ __forceinline__ void search_append(const SearchSel& s, uint32_t q, bo
     }
 }
 
+// ---- exclusion (SPEC.md §3 "Search", "Exclusion"; DESIGN.md §4 "Search", "Exclusion") ---------------------------------------------------------------
+// The exclude lists as search_exclude_prepare_kernel leaves them: row r is sorted[r * ep, + count[r]), ascending; what lies behind a row's count is never
+// read.  Query q of a block reads row q * per_query — the body is handed the lists of its tile's first query, or the one list of a broadcast.
+struct SearchFilter {
+    const int64_t* sorted;
+    const uint32_t* count;
+    uint32_t ep, per_query;   // ep: entries between two rows (a power of two); per_query: 1, or 0 where one row serves every query
+};
+// Is `key` in query q's exclude row?  A lower-bound search over the row's valid entries alone: at most 12 dependent loads and the one that compares
+// (count <= MEE_SEARCH_MAX_EXCLUDE = 2^12).  Lanes diverge in here; the caller's ballots come after.
+__device__ __forceinline__ bool search_excluded(const SearchFilter& f, uint32_t q, int64_t key) {
+    const size_t r = (size_t)q * f.per_query;
+    const int64_t* __restrict__ row = f.sorted + r * f.ep;
+    const uint32_t n = f.count[r];
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (row[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo < n && row[lo] == key;
+}
+
+// the filter as a block sees it whose first query is the call's query q0
+__device__ __forceinline__ SearchFilter search_filter_at(const SearchFilter& f, uint32_t q0) {
+    const size_t r = (size_t)q0 * f.per_query;
+    return SearchFilter{f.sorted + r * f.ep, f.count + r, f.ep, f.per_query};
+}
+
+// One exclude row per block of kExcludeThreads threads: the row's n_exclude keys into LDS — an entry <= kReclaimed (it matches no live key; search's own
+// padding key is one) and the padding up to `ep` as INT64_MAX — an LDS bitonic sort, ascending, over ep = next pow2(n_exclude) entries (32 KB at the most),
+// and the sorted row [ep] and the count n of its valid entries to the workspace.  The n valid entries are the first n of the sorted row whatever they
+// are: nothing sorts behind INT64_MAX, and an INT64_MAX among the first n is one the caller listed.  LDS (dynamic): ep x 8 B | one count per wave.
+constexpr uint32_t kExcludeThreads = 256;
+__global__ __launch_bounds__(kExcludeThreads) void search_exclude_prepare_kernel(const int64_t* __restrict__ exclude, uint32_t n_exclude, uint32_t ep,
+                                                                                 int64_t* __restrict__ sorted, uint32_t* __restrict__ count) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char search_lds[];
+    int64_t* const e = reinterpret_cast<int64_t*>(search_lds);
+    uint32_t* const wave_n = reinterpret_cast<uint32_t*>(e + ep);
+    const uint32_t tid = threadIdx.x, row = blockIdx.x;
+    uint32_t mine = 0;
+    for (uint32_t i = tid; i < ep; i += kExcludeThreads) {
+        const int64_t key = i < n_exclude ? exclude[(size_t)row * n_exclude + i] : kEmpty;
+        const bool valid = key > kReclaimed;
+        e[i] = valid ? key : INT64_MAX;
+        mine += valid;
+    }
+    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
+    if ((tid & 63) == 0) wave_n[tid >> 6] = mine;
+    __syncthreads();
+    for (uint32_t k2 = 2; k2 <= ep; k2 <<= 1) {
+        for (uint32_t j = k2 >> 1; j >= 1; j >>= 1) {
+            for (uint32_t p = tid; p < ep / 2; p += kExcludeThreads) {   // pair p: the entries i and i + j, i with bit j clear
+                const uint32_t i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
+                const int64_t a = e[i], b = e[i + j];
+                if ((a > b) == ((i & k2) == 0)) { e[i] = b; e[i + j] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    for (uint32_t i = tid; i < ep; i += kExcludeThreads) sorted[(size_t)row * ep + i] = e[i];
+    if (tid == 0) count[row] = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+}
+
 // ---- cosine (SPEC.md §3 "Search", "Metric"): score = dot / (sqrtf(qq) * sqrtf(rr)), four correctly rounded fp32 operations ---------------------------
 __device__ __forceinline__ float cosine_score(float dot, float qn, float rn) { return dot / (qn * rn) + 0.f; }   // + 0.f: a zero leaves as +0.0
 
@@ -241,10 +308,12 @@ __device__ __forceinline__ void search_sel_start(const SearchSel& s, const float
     wave_lds_sync();
 }
 // A step's 16 accumulators against the thresholds: accumulator r of lane (half, col) is query qbase + 8 (r / 4) + r % 4 (qbase = 32 rb + 4 half) against
-// the lane's slot (key; cosine: of norm rn, `wild` as the scan bodies set it).  NaN passes no compare.
-template <int METRIC>
+// the lane's slot (key; cosine: of norm rn, `wild` as the scan bodies set it).  NaN passes no compare.  FILTER: a lane that would append first looks its
+// key up in its query's exclude row (flt; unused otherwise) and appends only if it is absent — the hot path and the thresholds never see the filter,
+// and an excluded key never raises a threshold.
+template <int METRIC, bool FILTER>
 __device__ __forceinline__ void search_select(const SearchSel& s, const float* qn, const f32x16& acc, uint32_t qbase, uint32_t nq, bool live, int64_t key,
-                                              float rn, bool wild, int lane) {
+                                              float rn, bool wild, int lane, [[maybe_unused]] const SearchFilter& flt) {
     const int col = lane & 31;
     uint32_t hot = 0;
 #pragma unroll
@@ -266,7 +335,10 @@ __device__ __forceinline__ void search_select(const SearchSel& s, const float* q
         const uint32_t q = qbase + 8 * (r >> 2) + (r & 3);
         if constexpr (METRIC == MEE_METRIC_COSINE) sc = cosine_score(sc, qn[q], rn);   // the exact score, its zero as +0.0 too; 0 / 0 = NaN is no candidate
         const uint32_t img = score_image(sc);
-        const bool beat = live && q < nq && sc == sc && search_better(img, key, s.thr_img[q], s.thr_key[q]);
+        bool beat = live && q < nq && sc == sc && search_better(img, key, s.thr_img[q], s.thr_key[q]);
+        if constexpr (FILTER) {   // divergent; search_append's ballots are wave-uniform again
+            if (beat) beat = !search_excluded(flt, q, key);
+        }
         search_append(s, q, beat, img, key, lane);
         if constexpr (METRIC == MEE_METRIC_COSINE) {   // the thresholds a prune may have raised, as the hot path wants them (q < qp: no query's word is a stranger's)
             if (col == 0) s.thr_sc[q] = cosine_prefilter(s.thr_img[q] ? image_score(s.thr_img[q]) : -__builtin_inff(), qn[q]);
@@ -328,11 +400,11 @@ __device__ __forceinline__ void search_load_b(const void* __restrict__ values, u
 // The scan of one block: `nq` queries against the steps [s0, s1) (s1 <= the table's step count); its best k per query go to rows out_row0 + q of the
 // lists.  seed_img / seed_keys: null, or the sorted best-k lists [nq][k] of slots OUTSIDE [s0, s1) — a query's thresholds then start at its k-th
 // seed entry (image 0 there: none yet) instead of at nothing, and the buffers may hold fewer than k entries while a threshold is set.
-template <int KS, int ROWS, int METRIC>
+template <int KS, int ROWS, int METRIC, bool FILTER>
 __device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
                                                  const float* __restrict__ queries, uint32_t nq, uint32_t k, uint64_t s0, uint64_t s1,
                                                  const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img, size_t out_row0,
-                                                 int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
+                                                 int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, const SearchFilter& flt) {
     extern __shared__ __attribute__((aligned(16))) unsigned char search_lds[];
     constexpr uint32_t dim = 16 * KS;
     const int lane = threadIdx.x, half = lane >> 5, col = lane & 31;
@@ -393,7 +465,7 @@ __device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tke
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, afrag[(rb * KS + ks) * 64 + lane]), b[ks], acc, 0, 0, 0);
-            search_select<METRIC>(s, qn, acc, rb * 32 + 4 * half, nq, live, key, rn, wild, lane);
+            search_select<METRIC, FILTER>(s, qn, acc, rb * 32 + 4 * half, nq, live, key, rn, wild, lane, flt);
         }
     }
 
@@ -407,26 +479,45 @@ __global__ __launch_bounds__(64) void search_scan_kernel(const int64_t* __restri
                                                          int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
     const uint64_t n_steps = (capacity + 31) / 32;
     const uint64_t s0 = (uint64_t)blockIdx.x * steps_per_block, s1 = s0 + steps_per_block < n_steps ? s0 + steps_per_block : n_steps;
-    search_scan_body<KS, ROWS, MEE_METRIC_IP>(tkeys, values, capacity, queries, nq, k, s0, s1, nullptr, nullptr, (size_t)blockIdx.x * nq, ws_keys, ws_img);
+    search_scan_body<KS, ROWS, MEE_METRIC_IP, false>(tkeys, values, capacity, queries, nq, k, s0, s1, nullptr, nullptr, (size_t)blockIdx.x * nq, ws_keys, ws_img, SearchFilter{});
 }
 
 // The batched scan (mee_search_batch): the nq_all queries are cut into n_tiles tiles of `tile` queries (the last one shorter), the steps
 // [step0, step_end) into ranges of steps_per_range; a one-wave block serves one (tile, range) pair.  The grid is flat and the tile index varies
 // fastest, so the blocks that walk one range are neighbours.  Lists: [range][nq_all][k] — a tile's block writes its own query rows of its range's
 // list, so the merge reads every query's lists at one stride whatever its tile.  seed_*: null or [nq_all][k] (search_scan_body).
+template <int KS, int ROWS, int METRIC, bool FILTER>
+__device__ __forceinline__ void search_batch_scan_block(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
+                                                        const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
+                                                        uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
+                                                        const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
+                                                        int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, const SearchFilter& flt) {
+    const uint32_t t = blockIdx.x % n_tiles, range = blockIdx.x / n_tiles;
+    const uint32_t q0 = t * tile, nq = nq_all - q0 < tile ? nq_all - q0 : tile;
+    uint64_t s0 = step0 + (uint64_t)range * steps_per_range, s1 = s0 + steps_per_range;
+    if (s1 > step_end) s1 = step_end;
+    if (s0 > s1) s0 = s1;
+    search_scan_body<KS, ROWS, METRIC, FILTER>(tkeys, values, capacity, queries + (size_t)q0 * (16 * KS), nq, k, s0, s1, seed_keys ? seed_keys + (size_t)q0 * k : nullptr,
+                                               seed_img ? seed_img + (size_t)q0 * k : nullptr, (size_t)range * nq_all + q0, ws_keys, ws_img, search_filter_at(flt, q0));
+}
 template <int KS, int ROWS, int METRIC>
 __global__ __launch_bounds__(64) void search_batch_scan_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
                                                                const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
                                                                uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
                                                                const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
                                                                int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
-    const uint32_t t = blockIdx.x % n_tiles, range = blockIdx.x / n_tiles;
-    const uint32_t q0 = t * tile, nq = nq_all - q0 < tile ? nq_all - q0 : tile;
-    uint64_t s0 = step0 + (uint64_t)range * steps_per_range, s1 = s0 + steps_per_range;
-    if (s1 > step_end) s1 = step_end;
-    if (s0 > s1) s0 = s1;
-    search_scan_body<KS, ROWS, METRIC>(tkeys, values, capacity, queries + (size_t)q0 * (16 * KS), nq, k, s0, s1, seed_keys ? seed_keys + (size_t)q0 * k : nullptr,
-                               seed_img ? seed_img + (size_t)q0 * k : nullptr, (size_t)range * nq_all + q0, ws_keys, ws_img);
+    search_batch_scan_block<KS, ROWS, METRIC, false>(tkeys, values, capacity, queries, nq_all, tile, n_tiles, k, step0, step_end, steps_per_range, seed_keys, seed_img, ws_keys,
+                                                     ws_img, SearchFilter{});
+}
+// ... with exclusion: flt holds the lists of ALL the call's queries (or the one broadcast list); a tile's block addresses its own rows from q0 on
+template <int KS, int ROWS, int METRIC>
+__global__ __launch_bounds__(64) void search_batch_scan_filtered_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
+                                                                        const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
+                                                                        uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
+                                                                        const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
+                                                                        int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, SearchFilter flt) {
+    search_batch_scan_block<KS, ROWS, METRIC, true>(tkeys, values, capacity, queries, nq_all, tile, n_tiles, k, step0, step_end, steps_per_range, seed_keys, seed_img, ws_keys,
+                                                    ws_img, flt);
 }
 
 // ---- wide rows, 256 < dim <= MEE_SEARCH_MAX_DIM (DESIGN.md §4 "Search", "Wide rows") -------------------------------------------------------------
@@ -466,11 +557,11 @@ __device__ __forceinline__ void search_wide_chunk(const void* __restrict__ at, c
 }
 
 // search_scan_body for a wide row: dim is a run-time value, nq <= 32; everything else as there.
-template <int ROWS, int METRIC>
+template <int ROWS, int METRIC, bool FILTER>
 __device__ __forceinline__ void search_wide_scan_body(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity, uint32_t dim,
                                                       const float* __restrict__ queries, uint32_t nq, uint32_t k, uint64_t s0, uint64_t s1,
                                                       const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img, size_t out_row0,
-                                                      int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
+                                                      int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, const SearchFilter& flt) {
     extern __shared__ __attribute__((aligned(16))) unsigned char search_lds[];
     const int lane = threadIdx.x, half = lane >> 5, col = lane & 31;
     const uint32_t ks_all = dim / 16, n_full = ks_all / kWideChunkKS * kWideChunkKS;
@@ -521,25 +612,43 @@ __device__ __forceinline__ void search_wide_scan_body(const int64_t* __restrict_
             rn = rr > 0.f ? __builtin_sqrtf(rr) : __builtin_nanf("");
             wild = __ballot(live && (rn > kCosNormMax || (rn < kCosNormMin && rn > 0.f))) != 0;
         }
-        search_select<METRIC>(s, qn, acc, 4 * half, nq, live, key, rn, wild, lane);
+        search_select<METRIC, FILTER>(s, qn, acc, 4 * half, nq, live, key, rn, wild, lane, flt);
     }
     search_write_lists(s, nq, out_row0, ws_keys, ws_img, lane);
 }
 
 // search_batch_scan_kernel's grid and lists for a wide row: tile <= 32
+template <int ROWS, int METRIC, bool FILTER>
+__device__ __forceinline__ void search_wide_scan_block(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity, uint32_t dim,
+                                                       const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
+                                                       uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
+                                                       const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
+                                                       int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, const SearchFilter& flt) {
+    const uint32_t t = blockIdx.x % n_tiles, range = blockIdx.x / n_tiles;
+    const uint32_t q0 = t * tile, nq = nq_all - q0 < tile ? nq_all - q0 : tile;
+    uint64_t s0 = step0 + (uint64_t)range * steps_per_range, s1 = s0 + steps_per_range;
+    if (s1 > step_end) s1 = step_end;
+    if (s0 > s1) s0 = s1;
+    search_wide_scan_body<ROWS, METRIC, FILTER>(tkeys, values, capacity, dim, queries + (size_t)q0 * dim, nq, k, s0, s1, seed_keys ? seed_keys + (size_t)q0 * k : nullptr,
+                                                seed_img ? seed_img + (size_t)q0 * k : nullptr, (size_t)range * nq_all + q0, ws_keys, ws_img, search_filter_at(flt, q0));
+}
 template <int ROWS, int METRIC>
 __global__ __launch_bounds__(64) void search_wide_scan_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity, uint32_t dim,
                                                               const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
                                                               uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
                                                               const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
                                                               int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
-    const uint32_t t = blockIdx.x % n_tiles, range = blockIdx.x / n_tiles;
-    const uint32_t q0 = t * tile, nq = nq_all - q0 < tile ? nq_all - q0 : tile;
-    uint64_t s0 = step0 + (uint64_t)range * steps_per_range, s1 = s0 + steps_per_range;
-    if (s1 > step_end) s1 = step_end;
-    if (s0 > s1) s0 = s1;
-    search_wide_scan_body<ROWS, METRIC>(tkeys, values, capacity, dim, queries + (size_t)q0 * dim, nq, k, s0, s1, seed_keys ? seed_keys + (size_t)q0 * k : nullptr,
-                                        seed_img ? seed_img + (size_t)q0 * k : nullptr, (size_t)range * nq_all + q0, ws_keys, ws_img);
+    search_wide_scan_block<ROWS, METRIC, false>(tkeys, values, capacity, dim, queries, nq_all, tile, n_tiles, k, step0, step_end, steps_per_range, seed_keys, seed_img, ws_keys,
+                                                ws_img, SearchFilter{});
+}
+template <int ROWS, int METRIC>
+__global__ __launch_bounds__(64) void search_wide_scan_filtered_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity, uint32_t dim,
+                                                                       const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
+                                                                       uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
+                                                                       const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
+                                                                       int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, SearchFilter flt) {
+    search_wide_scan_block<ROWS, METRIC, true>(tkeys, values, capacity, dim, queries, nq_all, tile, n_tiles, k, step0, step_end, steps_per_range, seed_keys, seed_img, ws_keys,
+                                               ws_img, flt);
 }
 
 // Query q's best k of n_lists sorted lists, list l at [(l * nq + q) * k, + k): lane i < k ends with entry i in (img, key), image 0 behind the real ones.
@@ -697,16 +806,49 @@ static int search_batch_workspace(const mee_table* t, int metric, size_t n_queri
     return MEE_OK;
 }
 
-template <int METRIC>
+// the exclude lists of a filtered search as the caller hands them in: [rows][n] keys, rows == n_queries or 1
+struct SearchExclude {
+    const int64_t* d_keys;
+    size_t rows, n;
+};
+// the entries between two sorted rows, and the bytes of the sorted-list area in front of the metric's own workspace: the sorted rows, then one count
+// per row, rounded up to 8 bytes
+static uint32_t search_exclude_ep(size_t n) {
+    uint32_t ep = 1;
+    while (ep < n) ep <<= 1;
+    return ep;
+}
+static uint64_t search_exclude_bytes(size_t rows, size_t n) { return (uint64_t)rows * search_exclude_ep(n) * 8 + (rows + 1) / 2 * 8; }
+static int search_exclude_check(size_t n_queries, size_t rows, size_t n, const char* name) {
+    if (n < 1 || n > MEE_SEARCH_MAX_EXCLUDE) return fail(MEE_ERR_INVALID_ARG, "%s: n_exclude must be in [1, %d] (got %zu)", name, MEE_SEARCH_MAX_EXCLUDE, n);
+    if (rows != 1 && rows != n_queries) return fail(MEE_ERR_INVALID_ARG, "%s: exclude_rows must be n_queries (%zu) or 1 (got %zu)", name, n_queries, rows);
+    return MEE_OK;
+}
+
+// FILTER: `ex` is read, d_workspace begins with the sorted-list area, and one more launch — search_exclude_prepare_kernel — goes in front
+template <int METRIC, bool FILTER = false>
 static int search_batch_launch(const mee_table* t, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
-                               uint32_t* d_out_counts, void* d_workspace, void* stream, const char* name) {
+                               uint32_t* d_out_counts, void* d_workspace, void* stream, const char* name, const SearchExclude& ex = {}) {
     uint32_t max_grid = 0;
     if (int rc = search_check(t, n_queries, k, name, &max_grid, true)) return rc;
     if (!d_queries || !d_out_keys || !d_out_scores || !d_workspace) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
     if (((uintptr_t)d_queries & 15) || ((uintptr_t)d_workspace & 7)) return fail(MEE_ERR_INVALID_ARG, "%s: queries must be 16-byte aligned, the workspace 8-byte aligned", name);
+    [[maybe_unused]] SearchFilter flt{};
+    if constexpr (FILTER) {
+        if (int rc = search_exclude_check(n_queries, ex.rows, ex.n, name)) return rc;
+        if (!ex.d_keys || ((uintptr_t)ex.d_keys & 7)) return fail(MEE_ERR_INVALID_ARG, "%s: the exclude keys must be a non-null, 8-byte aligned pointer", name);
+    }
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
     const uint32_t nq = (uint32_t)n_queries;
+    if constexpr (FILTER) {   // the sorted rows and their counts, then the workspace of the unfiltered launches
+        const uint32_t ep = search_exclude_ep(ex.n);
+        int64_t* sorted = (int64_t*)d_workspace;
+        uint32_t* count = (uint32_t*)(sorted + ex.rows * ep);
+        search_exclude_prepare_kernel<<<(uint32_t)ex.rows, kExcludeThreads, (size_t)ep * 8 + 16, st>>>(ex.d_keys, (uint32_t)ex.n, ep, sorted, count);
+        flt = SearchFilter{sorted, count, ep, ex.rows == 1 ? 0u : 1u};
+        d_workspace = (unsigned char*)d_workspace + search_exclude_bytes(ex.rows, ex.n);
+    }
     const uint64_t n_steps = (t->capacity + 31) / 32;
     const SearchBatchPlan p = search_batch_plan(t->dim, nq, k, max_grid, n_steps, METRIC);
     // lists of [nq][k] entries: 0 the seed area, 1 .. ranges the main scan's, then the seed pass's; the key plane of all lists, then the image plane
@@ -728,14 +870,22 @@ static int search_batch_launch(const mee_table* t, const float* d_queries, size_
     };
     if (wide) with_flag(t->bf16_rows, [&](auto bf16) {
         passes([&](uint32_t blocks, uint64_t step0, uint64_t step_end, uint64_t per_range, const int64_t* seed_keys, const uint32_t* seed_img, int64_t* out_keys, uint32_t* out_img) {
-            search_wide_scan_kernel<bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, lds, st>>>(t->keys, t->values, t->capacity, t->dim, d_queries, nq, p.tile, p.n_tiles, k, step0,
-                                                                                               step_end, per_range, seed_keys, seed_img, out_keys, out_img);
+            if constexpr (FILTER)
+                search_wide_scan_filtered_kernel<bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, lds, st>>>(t->keys, t->values, t->capacity, t->dim, d_queries, nq, p.tile, p.n_tiles, k,
+                                                                                                            step0, step_end, per_range, seed_keys, seed_img, out_keys, out_img, flt);
+            else
+                search_wide_scan_kernel<bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, lds, st>>>(t->keys, t->values, t->capacity, t->dim, d_queries, nq, p.tile, p.n_tiles, k, step0,
+                                                                                                   step_end, per_range, seed_keys, seed_img, out_keys, out_img);
         });
     });
     else with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)(t->dim / 16), [&](auto ks) { with_flag(t->bf16_rows, [&](auto bf16) {
         passes([&](uint32_t blocks, uint64_t step0, uint64_t step_end, uint64_t per_range, const int64_t* seed_keys, const uint32_t* seed_img, int64_t* out_keys, uint32_t* out_img) {
-            search_batch_scan_kernel<ks, bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, step0, step_end,
-                                                                                                    per_range, seed_keys, seed_img, out_keys, out_img);
+            if constexpr (FILTER)
+                search_batch_scan_filtered_kernel<ks, bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, step0,
+                                                                                                                 step_end, per_range, seed_keys, seed_img, out_keys, out_img, flt);
+            else
+                search_batch_scan_kernel<ks, bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, step0, step_end,
+                                                                                                        per_range, seed_keys, seed_img, out_keys, out_img);
         });
     }); });
     // the seed area is one more list in front of the main scan's: the prefix is not scanned again
@@ -807,6 +957,27 @@ int mee_search_metric(const mee_table* t, int metric, const float* d_queries, si
     if (metric == MEE_METRIC_IP) return mee_search_batch(t, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream);
     MEE_RANGE("mee_search_metric");
     return search_batch_launch<MEE_METRIC_COSINE>(t, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream, "mee_search_metric");
+}
+
+int mee_search_filtered_workspace_bytes(const mee_table* t, int metric, size_t n_queries, uint32_t k, size_t exclude_rows, size_t n_exclude, uint64_t* bytes_out) {
+    const char* name = "mee_search_filtered_workspace_bytes";
+    if (bytes_out) *bytes_out = 0;
+    if (int rc = search_metric_check(metric, name)) return rc;
+    uint64_t base = 0;
+    if (int rc = search_batch_workspace(t, metric, n_queries, k, &base, name)) return rc;
+    if (int rc = search_exclude_check(n_queries, exclude_rows, n_exclude, name)) return rc;
+    *bytes_out = search_exclude_bytes(exclude_rows, n_exclude) + base;
+    return MEE_OK;
+}
+
+int mee_search_filtered(const mee_table* t, int metric, const float* d_queries, size_t n_queries, uint32_t k, const int64_t* d_exclude, size_t exclude_rows,
+                        size_t n_exclude, int64_t* d_out_keys, float* d_out_scores, uint32_t* d_out_counts, void* d_workspace, void* stream) {
+    if (int rc = search_metric_check(metric, "mee_search_filtered")) return rc;
+    MEE_RANGE("mee_search_filtered");
+    const SearchExclude ex{d_exclude, exclude_rows, n_exclude};
+    if (metric == MEE_METRIC_IP)
+        return search_batch_launch<MEE_METRIC_IP, true>(t, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream, "mee_search_filtered", ex);
+    return search_batch_launch<MEE_METRIC_COSINE, true>(t, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream, "mee_search_filtered", ex);
 }
 
 }  // extern "C"

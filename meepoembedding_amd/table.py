@@ -121,6 +121,9 @@ def _fp32_only(out: torch.Tensor | None, op: str) -> None:
 
 
 _PAD_KEEP = {"first": _lib.PAD_KEEP_FIRST, "last": _lib.PAD_KEEP_LAST}
+# search(exclude=[Q, E]): the sorted copies of the exclude rows one native call may hold in the workspace; a larger batch is served in chunks of queries.
+# 64 MiB is a choice, not a measurement: 2 048 queries a call at E = 4 096, no chunking at all below E = 128.
+_EXCLUDE_SORTED_BYTES = 64 << 20
 
 
 def _publish_checked(counts, who: str = "") -> tuple:
@@ -777,7 +780,7 @@ class LookupTable:
         return upserts, removed, None
 
     def search(self, queries: torch.Tensor, k: int, out_keys: torch.Tensor | None = None, out_scores: torch.Tensor | None = None, counts: bool = False,
-               metric: str = "ip"):
+               metric: str = "ip", exclude: torch.Tensor | None = None):
         """SPEC.md §3 "Search": for each row of `queries` ([Q, dim] float32 on the table's device) the k live keys whose rows have the greatest inner
         product with it, scanned in place — no [N, dim] copy, never stale -> (keys [Q, k] int64, scores [Q, k] float32), best first, equal scores
         by the smaller key; counts=True adds the number of real entries per query ([Q] int32).  Both operands are rounded once to bf16 (an
@@ -788,7 +791,12 @@ class LookupTable:
         then walks a row in chunks of 256 columns: DESIGN.md §4 "Search", "Wide rows").  The workspace is a
         tensor cached by size, one per stream that searched (the native calls of one search share it in stream order).  No gradient.
         metric="cosine" (mee_search_metric): the score is dot / (|q| |row|) with both norms taken from the rounded operands inside the scan — no
-        normalised copy of the table; a zero row is never returned, a zero query has count 0.  Any Q goes through the batched launches."""
+        normalised copy of the table; a zero row is never returned, a zero query has count 0.  Any Q goes through the batched launches.
+        exclude (mee_search_filtered): int64 [Q, E] — row q lists keys query q must never get back — or [1, E] for every query, 1 <= E <=
+        SEARCH_MAX_EXCLUDE, on the table's device: "the best k except these", filtered inside the scan, everything else as above.  Any int64 may be
+        listed; duplicates, absent keys and reserved keys (search's INT64_MIN padding) match nothing, so exclude=previous_keys gives the next page.
+        Every Q goes through the batched launches plus one that sorts the rows; with a row per query a large batch is cut into chunks of queries
+        whose sorted rows stay within _EXCLUDE_SORTED_BYTES of workspace.  exclude=None is the call without it, in every bit."""
         if metric not in _lib.METRICS:
             raise MeepoError(_lib.ERR_INVALID_ARG, f"metric must be one of {sorted(_lib.METRICS)} (got {metric!r})")
         if queries.dtype != torch.float32 or queries.device != self.device or queries.dim() != 2 or queries.shape[1] != self.dim:
@@ -797,11 +805,22 @@ class LookupTable:
             raise MeepoError(_lib.ERR_INVALID_ARG, f"k must be an int in [1, {_lib.SEARCH_MAX_K}] (got {k!r})")
         q = queries.contiguous()
         nq = q.shape[0]
+        if exclude is not None:
+            if exclude.dtype != torch.int64 or exclude.device != self.device or exclude.dim() != 2 or exclude.shape[0] not in (1, nq) or \
+                    not 1 <= exclude.shape[1] <= _lib.SEARCH_MAX_EXCLUDE:
+                raise MeepoError(_lib.ERR_INVALID_ARG, f"exclude must be int64 [{nq}, E] or [1, E] with 1 <= E <= {_lib.SEARCH_MAX_EXCLUDE} on {self.device} "
+                                                       f"(got {exclude.dtype} {list(exclude.shape)} on {exclude.device})")
+            exclude = exclude.contiguous()
         wide = self.dim > 256   # mee_search has no such row: every Q through the batched launches
         per_call = 0 if wide else min(_lib.SEARCH_MAX_QK // max(k, 8), max(_lib.SEARCH_MAX_QUERY_ELEMS // max(self.dim, 1) // 32 * 32, 1))
         need = C.c_uint64()
         batched = wide or nq > per_call   # past one call's limits: mee_search_batch, tiled and seeded, in chunks of its own cap
-        if metric != "ip":   # every Q through the batched launches of that metric
+        if exclude is not None:   # every Q through the batched launches of either metric, behind the launch that sorts the exclude rows
+            ne, shared = exclude.shape[1], exclude.shape[0] == 1 and nq != 1
+            per_call = _lib.SEARCH_BATCH_MAX_QUERIES if shared else min(_lib.SEARCH_BATCH_MAX_QUERIES, max(_EXCLUDE_SORTED_BYTES // (8 << (ne - 1).bit_length()), 1))   # (a sorted row: E rounded up to a power of two)
+            check(_lib.lib().mee_search_filtered_workspace_bytes(self._h, _lib.METRICS[metric], max(min(nq, per_call), 1), k, 1 if shared else max(min(nq, per_call), 1),
+                                                                 ne, C.byref(need)))
+        elif metric != "ip":   # every Q through the batched launches of that metric
             per_call = _lib.SEARCH_BATCH_MAX_QUERIES
             check(_lib.lib().mee_search_metric_workspace_bytes(self._h, _lib.METRICS[metric], max(min(nq, per_call), 1), k, C.byref(need)))
         elif batched:
@@ -824,6 +843,11 @@ class LookupTable:
             head = (_lib.lib().mee_search_batch if batched else _lib.lib().mee_search, self._h)
         for s in range(0, nq, per_call):
             n = min(per_call, nq - s)
+            if exclude is not None:
+                check(_lib.lib().mee_search_filtered(self._h, _lib.METRICS[metric], q[s:s + n].data_ptr(), n, k, (exclude if shared else exclude[s:s + n]).data_ptr(),
+                                                     1 if shared else n, ne, ok[s:s + n].data_ptr(), osc[s:s + n].data_ptr(),
+                                                     n_real[s:s + n].data_ptr() if counts else None, ws.data_ptr(), stream))
+                continue
             check(head[0](*head[1:], q[s:s + n].data_ptr(), n, k, ok[s:s + n].data_ptr(), osc[s:s + n].data_ptr(),
                           n_real[s:s + n].data_ptr() if counts else None, ws.data_ptr(), stream))
         return (out_keys, out_scores, n_real) if counts else (out_keys, out_scores)

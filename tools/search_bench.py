@@ -14,7 +14,13 @@ a row is its pass-to-pass difference (the method of profiles/int8_rows.md).
     cosine            table.search(queries, k, metric="cosine"): mee_search_metric, the batched launches for every Q
     ip same launches  mee_search_batch called directly for every Q: the inner product through the very launches the cosine takes — what the norm costs
     matmul + topk     the matrix is the NORMALISED bf16 matrix (rows / |row|), the queries are normalised per call; refresh includes the normalisation
-usage: python tools/search_bench.py [--metric ip|cosine] [--keys N] [--dim D] [--reps K] [--queries 1,32,128,1024] [--ks 10,64] [--libs parent=PATH,…] [--no-matmul]"""
+--exclude E,… replaces the rows by the exclusion measurement (profiles/search.md "Exclusion"), one record per E; the exclude rows are each query's own top
+E scorers (read off the matrix), the case in which the filter is asked most often:
+    search            the unfiltered search of the same shape, in the same loop
+    filtered          table.search(queries, k, exclude=[Q, E]): mee_search_filtered — the sort of the rows and the filtered launches
+    filtered shared   the same with one [1, E] row (query 0's) for every query
+    overfetch+filter  only where k + E <= 64: table.search(queries, k + E) and the filter in torch (compare, stable argsort, gather)
+usage: python tools/search_bench.py [--metric ip|cosine] [--exclude 54,64,4096] [--keys N] [--dim D] [--reps K] [--queries 1,32,128,1024] [--ks 10,64] [--libs parent=PATH,…] [--no-matmul]"""
 import argparse
 import ctypes as C
 import json
@@ -35,6 +41,7 @@ ap.add_argument("--queries", default="1,32,128,1024")
 ap.add_argument("--ks", default="10,64", help="one Q and one k: a shape on its own for `rocprofv3 --kernel-trace --stats`, which times the scan and the merge apart")
 ap.add_argument("--libs", default="", help="NAME=PATH,…: other builds of the library, each a row of its own")
 ap.add_argument("--metric", default="ip", choices=["ip", "cosine"])
+ap.add_argument("--exclude", default="", help="E,…: time search(exclude=...) with each query's top E scorers excluded against the unfiltered search")
 ap.add_argument("--no-matmul", action="store_true", help="leave the matrix path out (a kernel trace of the search alone)")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -134,6 +141,29 @@ for value_dtype in (torch.float32, torch.bfloat16):
                 pos = torch.topk(qm.to(torch.bfloat16) @ matrix.T, k, dim=1).indices
                 return ekeys[pos]
 
+            if args.exclude:
+                qm = queries / queries.norm(dim=1, keepdim=True) if args.metric == "cosine" else queries
+                top = ekeys[torch.topk(qm.to(torch.bfloat16) @ matrix.T, max(int(e) for e in args.exclude.split(",")), dim=1).indices]
+                for ne in [int(e) for e in args.exclude.split(",")]:
+                    ex = top[:, :ne].contiguous()
+                    rows = {"search": lambda: t.search(queries, k, metric=args.metric), "filtered": lambda: t.search(queries, k, metric=args.metric, exclude=ex),
+                            "filtered shared": lambda: t.search(queries, k, metric=args.metric, exclude=ex[:1])}
+                    if k + ne <= _lib.SEARCH_MAX_K:
+                        def overfetch():
+                            wk, ws = t.search(queries, k + ne, metric=args.metric)
+                            keep = ~(wk[:, :, None] == ex[:, None, :]).any(-1)
+                            at = keep.to(torch.int8).argsort(dim=1, descending=True, stable=True)[:, :k]
+                            return wk.gather(1, at), ws.gather(1, at)
+                        rows["overfetch+filter"] = overfetch
+                        assert torch.equal(overfetch()[0], rows["filtered"]()[0])
+                    assert not torch.isin(rows["filtered"]()[0], ex[:1]).logical_and(torch.arange(nq, device=dev)[:, None] == 0).any()
+                    passes = [timed_rows(rows, args.reps) for _ in range(2)]
+                    rec = {"exclude": ne, "metric": args.metric, "rows": str(value_dtype).split(".")[1], "keys": n, "dim": args.dim, "Q": nq, "k": k,
+                           "us": {nm: round((passes[0][nm] + passes[1][nm]) / 2, 1) for nm in rows}, "spread_us": {nm: round(abs(passes[0][nm] - passes[1][nm]), 1) for nm in rows}}
+                    print("SEARCH_BENCH " + json.dumps(rec), flush=True)
+                    results.append(rec)
+                del top
+                continue
             got = t.search(queries, k, metric=args.metric)[0]
             same = float((got == matmul_topk()).float().mean())   # (bf16 scores of the matrix path round differently: near-ties may swap)
             rows = {"search": lambda: t.search(queries, k)}
