@@ -63,6 +63,14 @@ __device__ __forceinline__ float score_tile_sum(float a) {
     return a;
 }
 
+// a group's four products, or its four squares, on top of `a`: every product is exact, the sum is fp32 in element order
+__device__ __forceinline__ float dot4(const f32x4 x, const f32x4 y, float a) {
+    a = __builtin_fmaf(x.x, y.x, a); a = __builtin_fmaf(x.y, y.y, a);
+    a = __builtin_fmaf(x.z, y.z, a); a = __builtin_fmaf(x.w, y.w, a);
+    return a;
+}
+__device__ __forceinline__ float squares4(const f32x4 v, float a) { return dot4(v, v, a); }
+
 template <int C4, int ROWS, int METRIC>
 __global__ __launch_bounds__(kScoreWaves * 64) void score_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t nb, uint32_t dim4,
                                                                  const f32x4* __restrict__ queries, const int64_t* __restrict__ keys, uint64_t n_cand, uint64_t span,
@@ -90,10 +98,7 @@ __global__ __launch_bounds__(kScoreWaves * 64) void score_kernel(const int64_t* 
         if constexpr (METRIC == MEE_METRIC_COSINE) {
             float qq = 0.f;
 #pragma unroll
-            for (int c = 0; c < C4; ++c) {
-                qq = __builtin_fmaf(qv[c].x, qv[c].x, qq); qq = __builtin_fmaf(qv[c].y, qv[c].y, qq);
-                qq = __builtin_fmaf(qv[c].z, qv[c].z, qq); qq = __builtin_fmaf(qv[c].w, qv[c].w, qq);
-            }
+            for (int c = 0; c < C4; ++c) qq = squares4(qv[c], qq);
             qn = __builtin_sqrtf(score_tile_sum(qq));
         }
         const int64_t* __restrict__ qkeys = keys + q * n_cand;
@@ -137,6 +142,7 @@ __global__ __launch_bounds__(kScoreWaves * 64) void score_kernel(const int64_t* 
                 for (int c = 0; c < C4; ++c) {
                     f32x4 v = score_operand<ROWS>(row[r][c]);
                     if (c == C4 - 1 && !last_live) v = f32x4{0.f, 0.f, 0.f, 0.f};
+                    // dot4 / squares4 written out: through the helpers the four C4 == 1 instances (R = 4) are allocated other registers
                     a = __builtin_fmaf(qv[c].x, v.x, a); a = __builtin_fmaf(qv[c].y, v.y, a);
                     a = __builtin_fmaf(qv[c].z, v.z, a); a = __builtin_fmaf(qv[c].w, v.w, a);
                     if constexpr (METRIC == MEE_METRIC_COSINE) {
@@ -205,10 +211,7 @@ __global__ __launch_bounds__(kScoreWaves * 64) void score_wide_kernel(const int6
         if constexpr (METRIC == MEE_METRIC_COSINE) {
             float qq = 0.f;
 #pragma unroll
-            for (int c = 0; c < P; ++c) {
-                qq = __builtin_fmaf(qv[c].x, qv[c].x, qq); qq = __builtin_fmaf(qv[c].y, qv[c].y, qq);
-                qq = __builtin_fmaf(qv[c].z, qv[c].z, qq); qq = __builtin_fmaf(qv[c].w, qv[c].w, qq);
-            }
+            for (int c = 0; c < P; ++c) qq = squares4(qv[c], qq);
             qn = __builtin_sqrtf(score_wave_sum(qq));
         }
         const int64_t* __restrict__ qkeys = keys + q * n_cand;
@@ -249,12 +252,8 @@ __global__ __launch_bounds__(kScoreWaves * 64) void score_wide_kernel(const int6
                 for (int c = 0; c < P; ++c) {
                     f32x4 v = score_operand<ROWS>(row[r][c]);
                     if (c == P - 1 && !last_live) v = f32x4{0.f, 0.f, 0.f, 0.f};
-                    a = __builtin_fmaf(qv[c].x, v.x, a); a = __builtin_fmaf(qv[c].y, v.y, a);
-                    a = __builtin_fmaf(qv[c].z, v.z, a); a = __builtin_fmaf(qv[c].w, v.w, a);
-                    if constexpr (METRIC == MEE_METRIC_COSINE) {
-                        rr = __builtin_fmaf(v.x, v.x, rr); rr = __builtin_fmaf(v.y, v.y, rr);
-                        rr = __builtin_fmaf(v.z, v.z, rr); rr = __builtin_fmaf(v.w, v.w, rr);
-                    }
+                    a = dot4(qv[c], v, a);
+                    if constexpr (METRIC == MEE_METRIC_COSINE) rr = squares4(v, rr);
                 }
                 a = score_wave_sum(a);
                 if constexpr (METRIC == MEE_METRIC_COSINE) a = a / (qn * __builtin_sqrtf(score_wave_sum(rr)));   // search's four operations; 0 / 0 = NaN is returned

@@ -15,18 +15,18 @@
 //            At the end the block writes its best k per query, sorted, to workspace[block][query][k].
 //   merge    search_merge_kernel, one wave per query: the running best k as one entry per lane; the heads of 64 lists are read by one load, a list
 //            whose head does not beat the current k-th is never touched, the others fold in by a bitonic merge of 128.  It writes the padded tail itself.
-//   batched  mee_search_batch, any number of queries in one call: the queries in tiles of one row block, search_batch_scan_kernel — the same scan body,
-//            one (tile, step range) pair per one-wave block — first over a prefix of the slots (the seed pass), search_seed_merge_kernel for each
+//   batched  mee_search_batch, any number of queries in one call: the queries in tiles of one row block, search_batch_scan_kernel<KS, ROWS, METRIC,
+//            FILTER> — the same scan body, one (tile, step range) pair per one-wave block — first over a prefix of the slots (the seed pass), search_seed_merge_kernel for each
 //            query's best k of the prefix, then over the rest with every threshold starting at the prefix's k-th entry, and the merge above with
 //            the seed as one more list.
 //   cosine   mee_search_metric(MEE_METRIC_COSINE): the batched launches with search_batch_scan_kernel<.., MEE_METRIC_COSINE> — the row norm from the B registers
 //            (one square root per lane and step), the query norms in LDS, a widened product threshold on the hot path and the exact four-operation
 //            score on the rare one (DESIGN.md §4 "Search", "Metric").  The inner-product instances do not change by it.
-//   wide     256 < dim <= MEE_SEARCH_MAX_DIM, the batched entry points only: search_wide_scan_kernel<ROWS, METRIC> in the batched launches' place — a row
+//   wide     256 < dim <= MEE_SEARCH_MAX_DIM, the batched entry points only: search_wide_scan_kernel<ROWS, METRIC, FILTER> in the batched launches' place — a row
 //            walked in chunks of 256 columns into the same 16 accumulators, one row block of at most 32 queries per block, the absent queries of a
 //            tile not staged (DESIGN.md §4 "Search", "Wide rows").  The selection, the seed pass and the merges are the ones above.
 //   exclude  mee_search_filtered, "the best k except these": search_exclude_prepare_kernel sorts each exclude row into the workspace (an LDS bitonic sort,
-//            one block a row), then the batched launches with the FILTER instances of the two scan bodies — a lane that is about to append first looks
+//            one block a row), then the batched launches with the FILTER instances of the two scan kernels — a lane that is about to append first looks
 //            its key up in its query's sorted row by a lower-bound search in global memory (DESIGN.md §4 "Search", "Exclusion").  The hot path, the
 //            merges and every unfiltered instance do not change by it.
 // Only vector stores, no atomics, nothing of the table is written.
@@ -44,13 +44,31 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr uint32_t kSearchBlocksPerCU = 8;   // one-wave blocks the grid holds per CU, at most: the lists the merge reads per query
 constexpr uint32_t kSearchMinCap = 8;        // a candidate buffer holds 2 max(k, kSearchMinCap) entries
 static_assert(2 * MEE_SEARCH_MAX_K <= 128, "a prune sorts a buffer as two entries per lane");
-// the LDS of the largest call: queries (bf16) + candidates (12 B) + four words and a key per (padded) query
-static_assert(MEE_SEARCH_MAX_QUERY_ELEMS * 2 + MEE_SEARCH_MAX_QK * 2 * 12 + (MEE_SEARCH_MAX_QK / kSearchMinCap + 31) / 32 * 32 * 20 <= 65536, "the scan's LDS budget");
-// the cosine scan keeps one more word per padded query (its norm) and is served in tiles of one row block at most
-constexpr uint32_t kSearchCosineTileMax = 32;
-static_assert(MEE_SEARCH_MAX_QUERY_ELEMS * 2 + MEE_SEARCH_MAX_QK * 2 * 12 + kSearchCosineTileMax * 24 <= 65536, "the cosine scan's LDS budget");
-
 __host__ __device__ constexpr uint32_t search_cap(uint32_t k) { return 2 * (k < kSearchMinCap ? kSearchMinCap : k); }
+
+// The bytes of a block's selection state in LDS (SearchSel below; search_sel_at lays the same regions out in this order): nq queries with a buffer of
+// search_cap(k) candidates each — a key and an image per candidate — and the per-query words, padded to qp queries: the k-th best's key, image and
+// score, and the buffer's counter; `norms`: one more word, the query's norm (the cosine scan; the wide scan keeps the room whatever its metric).
+// Every byte count of the host, every tile rule and every LDS budget below comes from here.
+__host__ __device__ constexpr size_t search_sel_bytes(size_t nq, size_t qp, uint32_t k, bool norms) {
+    return nq * search_cap(k) * sizeof(int64_t)      // buf_key
+           + qp * sizeof(int64_t)                    // thr_key
+           + nq * search_cap(k) * sizeof(uint32_t)   // buf_img
+           + qp * sizeof(uint32_t)                   // thr_img
+           + qp * sizeof(float)                      // thr_sc
+           + qp * sizeof(uint32_t)                   // cnt
+           + (norms ? qp * sizeof(float) : 0);       // qn
+}
+// the byte counts the layout has had since the first scan: 12 per candidate, 20 per padded query, 24 with a norm
+static_assert(search_sel_bytes(1, 0, MEE_SEARCH_MAX_K, false) == search_cap(MEE_SEARCH_MAX_K) * 12 && search_sel_bytes(0, 1, 1, false) == 20 &&
+              search_sel_bytes(0, 1, 1, true) == 24, "the selection state's size is part of every tile rule and LDS budget");
+__host__ __device__ constexpr size_t search_pad32(size_t nq) { return (nq + 31) / 32 * 32; }
+// the LDS of the largest call: the queries (bf16) and the state of the most queries a call takes, each with the smallest buffer
+static_assert(MEE_SEARCH_MAX_QUERY_ELEMS * 2 + search_sel_bytes(MEE_SEARCH_MAX_QK / kSearchMinCap, search_pad32(MEE_SEARCH_MAX_QK / kSearchMinCap), kSearchMinCap, false) <= 65536,
+              "the scan's LDS budget");
+// the cosine scan keeps its norms and is served in tiles of one row block at most
+constexpr uint32_t kSearchCosineTileMax = 32;
+static_assert(MEE_SEARCH_MAX_QUERY_ELEMS * 2 + search_sel_bytes(MEE_SEARCH_MAX_QK / kSearchMinCap, kSearchCosineTileMax, kSearchMinCap, true) <= 65536, "the cosine scan's LDS budget");
 
 // The order-preserving integer image of a score (never NaN here; a zero comes as +0.0): greater score <=> greater image; every image is >= 0x007FFFFF
 // (-inf), so 0 marks "no entry".
@@ -196,6 +214,11 @@ __device__ __forceinline__ SearchFilter search_filter_at(const SearchFilter& f, 
     const size_t r = (size_t)q0 * f.per_query;
     return SearchFilter{f.sorted + r * f.ep, f.count + r, f.ep, f.per_query};
 }
+// what a scan kernel carries as its last parameter: the filter's words in a FILTER instance, nothing in the others
+struct SearchNoFilter {};
+template <bool FILTER> using SearchFilterOf = std::conditional_t<FILTER, SearchFilter, SearchNoFilter>;
+__device__ __forceinline__ SearchFilter search_filter_of(const SearchFilter& f) { return f; }
+__device__ __forceinline__ SearchFilter search_filter_of(const SearchNoFilter&) { return SearchFilter{}; }   // (never read: every use sits behind FILTER)
 
 // One exclude row per block of kExcludeThreads threads: the row's n_exclude keys into LDS — an entry <= kReclaimed (it matches no live key; search's own
 // padding key is one) and the padding up to `ep` as INT64_MAX — an LDS bitonic sort, ascending, over ep = next pow2(n_exclude) entries (32 KB at the most),
@@ -276,8 +299,8 @@ __device__ __forceinline__ float cosine_prefilter(float thr, float qn) {
 }
 
 // ---- what the scan bodies share around their matrix instructions --------------------------------------------------------------------------------
-// the selection state of nq queries, its per-query words padded to qp, from LDS at `base` (8-byte aligned): buf_key | thr_key | buf_img | thr_img |
-// thr_sc | cnt | qn (cosine only: [qp] query norms)
+// the selection state of nq queries, its per-query words padded to qp, from LDS at `base` (8-byte aligned), region by region in the order
+// search_sel_bytes sums them: buf_key | thr_key | buf_img | thr_img | thr_sc | cnt | qn (cosine only: [qp] query norms)
 __device__ __forceinline__ SearchSel search_sel_at(unsigned char* base, uint32_t nq, uint32_t qp, uint32_t k, float*& qn) {
     SearchSel s;
     s.k = k; s.cap = search_cap(k);
@@ -395,13 +418,48 @@ __device__ __forceinline__ void search_load_b(const void* __restrict__ values, u
     else search_load_ksteps<KS, ROWS>(reinterpret_cast<const f32x4*>(values) + slot * (uint64_t)(4 * KS) + 2 * half, KS, live, b);                             // ... 4 KS groups of four floats
 }
 
-// LDS (dynamic; the host computes the same sum, search_lds_bytes): A fragments [n_rb][KS][64] x 16 B | buf_key | thr_key | buf_img | thr_img | thr_sc | cnt
-// | qn (cosine only: [qp] query norms).  METRIC == MEE_METRIC_COSINE: thr_sc holds cosine_prefilter of the threshold instead of the threshold's score.
-// The scan of one block: `nq` queries against the steps [s0, s1) (s1 <= the table's step count); its best k per query go to rows out_row0 + q of the
-// lists.  seed_img / seed_keys: null, or the sorted best-k lists [nq][k] of slots OUTSIDE [s0, s1) — a query's thresholds then start at its k-th
-// seed entry (image 0 there: none yet) instead of at nothing, and the buffers may hold fewer than k entries while a threshold is set.
+// ---- what a block scans (both row shapes) ---------------------------------------------------------------------------------------------------------
+// The nq_all queries of a call are cut into n_tiles tiles of `tile` queries (the last one shorter), the steps [step0, step_end) into ranges of
+// steps_per_range; a one-wave block serves one (tile, range) pair.  The grid is flat and the tile index varies fastest, so the blocks that walk one
+// range are neighbours.  Lists: [range][nq_all][k] — a tile's block writes its own query rows of its range's list, so the merge reads every
+// query's lists at one stride whatever its tile.
+// The one decoder of both row shapes: it hands SCAN, the row shape's body (search_scan_body or search_wide_scan_body), the block's queries
+// [q0, q0 + nq) (dim columns each), its steps [s0, s1), its seed lists and its exclude lists from q0 on, and the first row of its lists.
+// seed_*: null or [nq_all][k].  flt: the lists of ALL the call's queries, or the one broadcast list (unread in an instance without FILTER).
+// The two bodies share ONE signature on purpose, the narrow one's unused leading row width included: SCAN is called as a plain function with
+// __restrict__ parameters, and that call — not a lambda or a struct of the values — is what keeps each kernel's machine code as it was.
+template <auto SCAN>
+__device__ __forceinline__ void search_scan_block(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity, uint32_t dim,
+                                                  const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
+                                                  uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
+                                                  const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
+                                                  int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, const SearchFilter& flt) {
+    const uint32_t t = blockIdx.x % n_tiles, range = blockIdx.x / n_tiles;
+    const uint32_t q0 = t * tile, nq = nq_all - q0 < tile ? nq_all - q0 : tile;
+    uint64_t s0 = step0 + (uint64_t)range * steps_per_range, s1 = s0 + steps_per_range;
+    if (s1 > step_end) s1 = step_end;
+    if (s0 > s1) s0 = s1;
+    SCAN(dim, tkeys, values, capacity, queries + (size_t)q0 * dim, nq, k, s0, s1, seed_keys ? seed_keys + (size_t)q0 * k : nullptr,
+         seed_img ? seed_img + (size_t)q0 * k : nullptr, (size_t)range * nq_all + q0, ws_keys, ws_img, search_filter_at(flt, q0));
+}
+
+// cosine: the norm of the lane's slot from rr, its half's share of the squares of the operand registers themselves (an fp32 row after its rounding) —
+// the other half's share from lane ^ 32, one square root per lane and step.  All 16 accumulators of a lane belong to this slot.
+// A zero row (and a dead lane) has the score 0 / 0 = NaN for every query.  Its norm is kept as NaN, not 0: the score stays NaN, and the hot path's
+// compare fails at once where  0 >= thr * 0  would send the row to the rare path at every step.
+// wild: a live row of the step whose norm lies outside the product compare's range — every query looks at the step exactly.
+__device__ __forceinline__ float cosine_row_norm(float rr, bool live, bool& wild) {
+    rr += __shfl_xor(rr, 32);
+    const float rn = rr > 0.f ? __builtin_sqrtf(rr) : __builtin_nanf("");
+    wild = __ballot(live && (rn > kCosNormMax || (rn < kCosNormMin && rn > 0.f))) != 0;
+    return rn;
+}
+
+// The scan of one block, rows of dim = 16 KS <= 256.
+// LDS (dynamic; the host computes the same sum, search_lds_bytes): A fragments [n_rb][KS][64] x 16 B | the selection state (search_sel_at).
+// METRIC == MEE_METRIC_COSINE: thr_sc holds cosine_prefilter of the threshold instead of the threshold's score.
 template <int KS, int ROWS, int METRIC, bool FILTER>
-__device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
+__device__ __forceinline__ void search_scan_body(uint32_t /* 16 KS */, const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
                                                  const float* __restrict__ queries, uint32_t nq, uint32_t k, uint64_t s0, uint64_t s1,
                                                  const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img, size_t out_row0,
                                                  int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, const SearchFilter& flt) {
@@ -446,19 +504,13 @@ __device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tke
         if (!__ballot(live)) continue;   // wave-uniform
         bf16x8 b[KS];
         search_load_b<KS, ROWS>(values, slot, half, live, b);
-        // cosine: the norm of the lane's slot from the operand registers themselves (an fp32 row after its rounding) — the lane's eight elements of
-        // every k-step, the other half's share from lane ^ 32, one square root per lane and step.  All 16 accumulators of a lane belong to this slot.
         [[maybe_unused]] float rn = 0.f;
-        [[maybe_unused]] bool wild = false;   // a live row whose norm lies outside the product compare's range: every query looks at it exactly
-        if constexpr (METRIC == MEE_METRIC_COSINE) {
+        [[maybe_unused]] bool wild = false;
+        if constexpr (METRIC == MEE_METRIC_COSINE) {   // the lane's eight elements of every k-step
             float rr = 0.f;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) rr = sum_squares(__builtin_bit_cast(u32x4, b[ks]), rr);
-            rr += __shfl_xor(rr, 32);
-            // A zero row (and a dead lane) has the score 0 / 0 = NaN for every query.  Its norm is kept as NaN, not 0: the score stays NaN, and the
-            // hot path's compare fails at once where  0 >= thr * 0  would send the row to the rare path at every step.
-            rn = rr > 0.f ? __builtin_sqrtf(rr) : __builtin_nanf("");
-            wild = __ballot(live && (rn > kCosNormMax || (rn < kCosNormMin && rn > 0.f))) != 0;
+            rn = cosine_row_norm(rr, live, wild);
         }
         for (uint32_t rb = 0; rb < n_rb; ++rb) {
             f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -469,55 +521,28 @@ __device__ __forceinline__ void search_scan_body(const int64_t* __restrict__ tke
         }
     }
 
-    // ---- the block's best k per query, sorted, padded with the empty marker
     search_write_lists(s, nq, out_row0, ws_keys, ws_img, lane);
 }
 
+// mee_search: all nq queries in every block, block b over steps [b, b + 1) * steps_per_block, list b
 template <int KS, int ROWS>
 __global__ __launch_bounds__(64) void search_scan_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
                                                          const float* __restrict__ queries, uint32_t nq, uint32_t k, uint64_t steps_per_block,
                                                          int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
     const uint64_t n_steps = (capacity + 31) / 32;
     const uint64_t s0 = (uint64_t)blockIdx.x * steps_per_block, s1 = s0 + steps_per_block < n_steps ? s0 + steps_per_block : n_steps;
-    search_scan_body<KS, ROWS, MEE_METRIC_IP, false>(tkeys, values, capacity, queries, nq, k, s0, s1, nullptr, nullptr, (size_t)blockIdx.x * nq, ws_keys, ws_img, SearchFilter{});
+    search_scan_body<KS, ROWS, MEE_METRIC_IP, false>(16 * KS, tkeys, values, capacity, queries, nq, k, s0, s1, nullptr, nullptr, (size_t)blockIdx.x * nq, ws_keys, ws_img, SearchFilter{});
 }
 
-// The batched scan (mee_search_batch): the nq_all queries are cut into n_tiles tiles of `tile` queries (the last one shorter), the steps
-// [step0, step_end) into ranges of steps_per_range; a one-wave block serves one (tile, range) pair.  The grid is flat and the tile index varies
-// fastest, so the blocks that walk one range are neighbours.  Lists: [range][nq_all][k] — a tile's block writes its own query rows of its range's
-// list, so the merge reads every query's lists at one stride whatever its tile.  seed_*: null or [nq_all][k] (search_scan_body).
+// flt (FILTER): the lists of ALL the call's queries, or the one broadcast list; a tile's block addresses its own rows from q0 on
 template <int KS, int ROWS, int METRIC, bool FILTER>
-__device__ __forceinline__ void search_batch_scan_block(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
-                                                        const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
-                                                        uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
-                                                        const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
-                                                        int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, const SearchFilter& flt) {
-    const uint32_t t = blockIdx.x % n_tiles, range = blockIdx.x / n_tiles;
-    const uint32_t q0 = t * tile, nq = nq_all - q0 < tile ? nq_all - q0 : tile;
-    uint64_t s0 = step0 + (uint64_t)range * steps_per_range, s1 = s0 + steps_per_range;
-    if (s1 > step_end) s1 = step_end;
-    if (s0 > s1) s0 = s1;
-    search_scan_body<KS, ROWS, METRIC, FILTER>(tkeys, values, capacity, queries + (size_t)q0 * (16 * KS), nq, k, s0, s1, seed_keys ? seed_keys + (size_t)q0 * k : nullptr,
-                                               seed_img ? seed_img + (size_t)q0 * k : nullptr, (size_t)range * nq_all + q0, ws_keys, ws_img, search_filter_at(flt, q0));
-}
-template <int KS, int ROWS, int METRIC>
 __global__ __launch_bounds__(64) void search_batch_scan_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
                                                                const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
                                                                uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
                                                                const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
-                                                               int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
-    search_batch_scan_block<KS, ROWS, METRIC, false>(tkeys, values, capacity, queries, nq_all, tile, n_tiles, k, step0, step_end, steps_per_range, seed_keys, seed_img, ws_keys,
-                                                     ws_img, SearchFilter{});
-}
-// ... with exclusion: flt holds the lists of ALL the call's queries (or the one broadcast list); a tile's block addresses its own rows from q0 on
-template <int KS, int ROWS, int METRIC>
-__global__ __launch_bounds__(64) void search_batch_scan_filtered_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
-                                                                        const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
-                                                                        uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
-                                                                        const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
-                                                                        int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, SearchFilter flt) {
-    search_batch_scan_block<KS, ROWS, METRIC, true>(tkeys, values, capacity, queries, nq_all, tile, n_tiles, k, step0, step_end, steps_per_range, seed_keys, seed_img, ws_keys,
-                                                    ws_img, flt);
+                                                               int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, SearchFilterOf<FILTER> flt) {
+    search_scan_block<search_scan_body<KS, ROWS, METRIC, FILTER>>(tkeys, values, capacity, 16 * KS, queries, nq_all, tile, n_tiles, k, step0, step_end, steps_per_range, seed_keys,
+                                                                  seed_img, ws_keys, ws_img, search_filter_of(flt));
 }
 
 // ---- wide rows, 256 < dim <= MEE_SEARCH_MAX_DIM (DESIGN.md §4 "Search", "Wide rows") -------------------------------------------------------------
@@ -531,10 +556,11 @@ __global__ __launch_bounds__(64) void search_batch_scan_filtered_kernel(const in
 // LDS: A fragments [dim / 16][2][nq] x 16 B | the selection state of nq queries, per-query words padded to 32 (search_sel_at).
 constexpr int kWideChunkKS = 16;
 constexpr uint32_t kWideLdsBudget = 40 * 1024;   // per block: four blocks share a CU's 160 KB (search_wide_tile)
-__host__ __device__ constexpr uint32_t search_wide_lds_bytes(uint32_t dim, uint32_t nq, uint32_t k) { return nq * (dim * 2 + search_cap(k) * 12) + 32 * 24; }
-// the queries of a tile: as many as the budget holds, in eights (a fragment's half is then whole 128-byte rows of the LDS), at most one row block
+__host__ __device__ constexpr uint32_t search_wide_lds_bytes(uint32_t dim, uint32_t nq, uint32_t k) { return nq * dim * 2 + (uint32_t)search_sel_bytes(nq, 32, k, true); }
+// the queries of a tile: as many as the budget holds (the bytes are linear in nq), in eights (a fragment's half is then whole 128-byte rows of the
+// LDS), at most one row block
 __host__ __device__ constexpr uint32_t search_wide_tile(uint32_t dim, uint32_t k) {
-    const uint32_t t = (kWideLdsBudget - 32 * 24) / (dim * 2 + search_cap(k) * 12) / 8 * 8;
+    const uint32_t t = (kWideLdsBudget - search_wide_lds_bytes(dim, 0, k)) / (search_wide_lds_bytes(dim, 1, k) - search_wide_lds_bytes(dim, 0, k)) / 8 * 8;
     return t < 32 ? t : 32;
 }
 static_assert(search_wide_tile(MEE_SEARCH_MAX_DIM, MEE_SEARCH_MAX_K) >= 8, "every (dim, k) is served in tiles of at least 8 queries");
@@ -558,7 +584,7 @@ __device__ __forceinline__ void search_wide_chunk(const void* __restrict__ at, c
 
 // search_scan_body for a wide row: dim is a run-time value, nq <= 32; everything else as there.
 template <int ROWS, int METRIC, bool FILTER>
-__device__ __forceinline__ void search_wide_scan_body(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity, uint32_t dim,
+__device__ __forceinline__ void search_wide_scan_body(uint32_t dim, const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity,
                                                       const float* __restrict__ queries, uint32_t nq, uint32_t k, uint64_t s0, uint64_t s1,
                                                       const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img, size_t out_row0,
                                                       int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, const SearchFilter& flt) {
@@ -607,48 +633,21 @@ __device__ __forceinline__ void search_wide_scan_body(const int64_t* __restrict_
             search_wide_chunk<ROWS, METRIC, false>(row + (size_t)n_full * 16 * esz, afrag, n_full, (int)(ks_all - n_full), nq, half, col, live, acc, rr);
         [[maybe_unused]] float rn = 0.f;
         [[maybe_unused]] bool wild = false;
-        if constexpr (METRIC == MEE_METRIC_COSINE) {   // as search_scan_body: one shuffle and one square root per lane and step, behind the last chunk
-            rr += __shfl_xor(rr, 32);
-            rn = rr > 0.f ? __builtin_sqrtf(rr) : __builtin_nanf("");
-            wild = __ballot(live && (rn > kCosNormMax || (rn < kCosNormMin && rn > 0.f))) != 0;
-        }
+        if constexpr (METRIC == MEE_METRIC_COSINE) rn = cosine_row_norm(rr, live, wild);   // behind the last chunk
         search_select<METRIC, FILTER>(s, qn, acc, 4 * half, nq, live, key, rn, wild, lane, flt);
     }
     search_write_lists(s, nq, out_row0, ws_keys, ws_img, lane);
 }
 
-// search_batch_scan_kernel's grid and lists for a wide row: tile <= 32
+// the scan kernel of a wide row: search_batch_scan_kernel's parameters and the row width; tile <= 32
 template <int ROWS, int METRIC, bool FILTER>
-__device__ __forceinline__ void search_wide_scan_block(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity, uint32_t dim,
-                                                       const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
-                                                       uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
-                                                       const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
-                                                       int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, const SearchFilter& flt) {
-    const uint32_t t = blockIdx.x % n_tiles, range = blockIdx.x / n_tiles;
-    const uint32_t q0 = t * tile, nq = nq_all - q0 < tile ? nq_all - q0 : tile;
-    uint64_t s0 = step0 + (uint64_t)range * steps_per_range, s1 = s0 + steps_per_range;
-    if (s1 > step_end) s1 = step_end;
-    if (s0 > s1) s0 = s1;
-    search_wide_scan_body<ROWS, METRIC, FILTER>(tkeys, values, capacity, dim, queries + (size_t)q0 * dim, nq, k, s0, s1, seed_keys ? seed_keys + (size_t)q0 * k : nullptr,
-                                                seed_img ? seed_img + (size_t)q0 * k : nullptr, (size_t)range * nq_all + q0, ws_keys, ws_img, search_filter_at(flt, q0));
-}
-template <int ROWS, int METRIC>
 __global__ __launch_bounds__(64) void search_wide_scan_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity, uint32_t dim,
                                                               const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
                                                               uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
                                                               const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
-                                                              int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
-    search_wide_scan_block<ROWS, METRIC, false>(tkeys, values, capacity, dim, queries, nq_all, tile, n_tiles, k, step0, step_end, steps_per_range, seed_keys, seed_img, ws_keys,
-                                                ws_img, SearchFilter{});
-}
-template <int ROWS, int METRIC>
-__global__ __launch_bounds__(64) void search_wide_scan_filtered_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t capacity, uint32_t dim,
-                                                                       const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k,
-                                                                       uint64_t step0, uint64_t step_end, uint64_t steps_per_range,
-                                                                       const int64_t* __restrict__ seed_keys, const uint32_t* __restrict__ seed_img,
-                                                                       int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, SearchFilter flt) {
-    search_wide_scan_block<ROWS, METRIC, true>(tkeys, values, capacity, dim, queries, nq_all, tile, n_tiles, k, step0, step_end, steps_per_range, seed_keys, seed_img, ws_keys,
-                                               ws_img, flt);
+                                                              int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img, SearchFilterOf<FILTER> flt) {
+    search_scan_block<search_wide_scan_body<ROWS, METRIC, FILTER>>(tkeys, values, capacity, dim, queries, nq_all, tile, n_tiles, k, step0, step_end, steps_per_range, seed_keys,
+                                                                   seed_img, ws_keys, ws_img, search_filter_of(flt));
 }
 
 // Query q's best k of n_lists sorted lists, list l at [(l * nq + q) * k, + k): lane i < k ends with entry i in (img, key), image 0 behind the real ones.
@@ -717,9 +716,14 @@ __global__ __launch_bounds__(64) void search_seed_merge_kernel(const int64_t* __
 // =========================================================================================================
 // host side
 // =========================================================================================================
-static size_t search_lds_bytes(uint32_t dim, size_t nq, uint32_t k, int metric = MEE_METRIC_IP) {
-    const size_t qp = (nq + 31) / 32 * 32;
-    return qp * dim * 2 + nq * search_cap(k) * 12 + qp * (metric == MEE_METRIC_COSINE ? 24 : 20);
+static size_t search_lds_bytes(uint32_t dim, size_t nq, uint32_t k, int metric) {
+    return search_pad32(nq) * dim * 2 + search_sel_bytes(nq, search_pad32(nq), k, metric == MEE_METRIC_COSINE);
+}
+// the pointers every search entry point is handed
+static int search_pointer_check(const float* d_queries, const int64_t* d_out_keys, const float* d_out_scores, const void* d_workspace, const char* name) {
+    if (!d_queries || !d_out_keys || !d_out_scores || !d_workspace) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (((uintptr_t)d_queries & 15) || ((uintptr_t)d_workspace & 7)) return fail(MEE_ERR_INVALID_ARG, "%s: queries must be 16-byte aligned, the workspace 8-byte aligned", name);
+    return MEE_OK;
 }
 // what the entry points refuse, before anything is launched; -> the blocks of the largest grid a search of this device launches.  batch: n_queries
 // is held against mee_search_batch's cap instead of the per-call limits.
@@ -825,15 +829,34 @@ static int search_exclude_check(size_t n_queries, size_t rows, size_t n, const c
     return MEE_OK;
 }
 
+// One scan launch of the table's row shape: the call's nq queries in n_tiles tiles of `tile`, each tile against `ranges` ranges of per_range steps of
+// [step0, step_end) — one one-wave block per (tile, range) pair; seed lists (or null) in, the lists [ranges][nq][k] out.
+struct SearchTiles {
+    const float* d_queries;
+    uint32_t nq, tile, n_tiles, k;
+};
+template <int METRIC, bool FILTER>
+static void search_scan_launch(const mee_table* t, hipStream_t st, const SearchTiles& q, uint32_t ranges, uint64_t step0, uint64_t step_end, uint64_t per_range,
+                               const int64_t* seed_keys, const uint32_t* seed_img, int64_t* out_keys, uint32_t* out_img, SearchFilterOf<FILTER> flt) {
+    const uint32_t blocks = q.n_tiles * ranges, tile_nq = q.tile < q.nq ? q.tile : q.nq;
+    if (t->dim > 256) with_flag(t->bf16_rows, [&](auto bf16) {
+        search_wide_scan_kernel<bf16 ? kRowsBF16 : kRowsF32, METRIC, FILTER><<<blocks, 64, search_wide_lds_bytes(t->dim, tile_nq, q.k), st>>>(
+            t->keys, t->values, t->capacity, t->dim, q.d_queries, q.nq, q.tile, q.n_tiles, q.k, step0, step_end, per_range, seed_keys, seed_img, out_keys, out_img, flt);
+    });
+    else with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)(t->dim / 16), [&](auto ks) { with_flag(t->bf16_rows, [&](auto bf16) {
+        search_batch_scan_kernel<ks, bf16 ? kRowsBF16 : kRowsF32, METRIC, FILTER><<<blocks, 64, search_lds_bytes(t->dim, tile_nq, q.k, METRIC), st>>>(
+            t->keys, t->values, t->capacity, q.d_queries, q.nq, q.tile, q.n_tiles, q.k, step0, step_end, per_range, seed_keys, seed_img, out_keys, out_img, flt);
+    }); });
+}
+
 // FILTER: `ex` is read, d_workspace begins with the sorted-list area, and one more launch — search_exclude_prepare_kernel — goes in front
 template <int METRIC, bool FILTER = false>
 static int search_batch_launch(const mee_table* t, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
                                uint32_t* d_out_counts, void* d_workspace, void* stream, const char* name, const SearchExclude& ex = {}) {
     uint32_t max_grid = 0;
     if (int rc = search_check(t, n_queries, k, name, &max_grid, true)) return rc;
-    if (!d_queries || !d_out_keys || !d_out_scores || !d_workspace) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
-    if (((uintptr_t)d_queries & 15) || ((uintptr_t)d_workspace & 7)) return fail(MEE_ERR_INVALID_ARG, "%s: queries must be 16-byte aligned, the workspace 8-byte aligned", name);
-    [[maybe_unused]] SearchFilter flt{};
+    if (int rc = search_pointer_check(d_queries, d_out_keys, d_out_scores, d_workspace, name)) return rc;
+    SearchFilterOf<FILTER> flt{};
     if constexpr (FILTER) {
         if (int rc = search_exclude_check(n_queries, ex.rows, ex.n, name)) return rc;
         if (!ex.d_keys || ((uintptr_t)ex.d_keys & 7)) return fail(MEE_ERR_INVALID_ARG, "%s: the exclude keys must be a non-null, 8-byte aligned pointer", name);
@@ -855,39 +878,15 @@ static int search_batch_launch(const mee_table* t, const float* d_queries, size_
     const size_t list = (size_t)nq * k;
     int64_t* ws_keys = (int64_t*)d_workspace;
     uint32_t* ws_img = (uint32_t*)(ws_keys + p.lists() * list);
-    const bool wide = t->dim > 256;
-    const size_t lds = wide ? search_wide_lds_bytes(t->dim, p.tile < nq ? p.tile : nq, k) : search_lds_bytes(t->dim, p.tile < nq ? p.tile : nq, k, METRIC);
+    const SearchTiles tiles{d_queries, nq, p.tile, p.n_tiles, k};
     const bool seeded = p.seed_ranges != 0;
-    // the seed pass and its merge, then the main scan from the seed's thresholds; scan(blocks, step0, step_end, steps per range, seed lists, lists out)
-    // launches the row shape's kernel
-    auto passes = [&](auto scan) {
-        if (seeded) {
-            const size_t so = (1 + (size_t)p.ranges) * list;
-            scan(p.n_tiles * p.seed_ranges, 0, p.seed_steps, p.per_seed_range, nullptr, nullptr, ws_keys + so, ws_img + so);
-            search_seed_merge_kernel<<<nq, 64, 0, st>>>(ws_keys + so, ws_img + so, p.seed_ranges, nq, k, ws_keys, ws_img);
-        }
-        scan(p.n_tiles * p.ranges, p.seed_steps, n_steps, p.per_range, seeded ? ws_keys : nullptr, seeded ? ws_img : nullptr, ws_keys + list, ws_img + list);
-    };
-    if (wide) with_flag(t->bf16_rows, [&](auto bf16) {
-        passes([&](uint32_t blocks, uint64_t step0, uint64_t step_end, uint64_t per_range, const int64_t* seed_keys, const uint32_t* seed_img, int64_t* out_keys, uint32_t* out_img) {
-            if constexpr (FILTER)
-                search_wide_scan_filtered_kernel<bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, lds, st>>>(t->keys, t->values, t->capacity, t->dim, d_queries, nq, p.tile, p.n_tiles, k,
-                                                                                                            step0, step_end, per_range, seed_keys, seed_img, out_keys, out_img, flt);
-            else
-                search_wide_scan_kernel<bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, lds, st>>>(t->keys, t->values, t->capacity, t->dim, d_queries, nq, p.tile, p.n_tiles, k, step0,
-                                                                                                   step_end, per_range, seed_keys, seed_img, out_keys, out_img);
-        });
-    });
-    else with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)(t->dim / 16), [&](auto ks) { with_flag(t->bf16_rows, [&](auto bf16) {
-        passes([&](uint32_t blocks, uint64_t step0, uint64_t step_end, uint64_t per_range, const int64_t* seed_keys, const uint32_t* seed_img, int64_t* out_keys, uint32_t* out_img) {
-            if constexpr (FILTER)
-                search_batch_scan_filtered_kernel<ks, bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, step0,
-                                                                                                                 step_end, per_range, seed_keys, seed_img, out_keys, out_img, flt);
-            else
-                search_batch_scan_kernel<ks, bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, p.tile, p.n_tiles, k, step0, step_end,
-                                                                                                        per_range, seed_keys, seed_img, out_keys, out_img);
-        });
-    }); });
+    if (seeded) {   // the seed pass and its merge, then the main scan from the seed's thresholds
+        const size_t so = (1 + (size_t)p.ranges) * list;
+        search_scan_launch<METRIC, FILTER>(t, st, tiles, p.seed_ranges, 0, p.seed_steps, p.per_seed_range, nullptr, nullptr, ws_keys + so, ws_img + so, flt);
+        search_seed_merge_kernel<<<nq, 64, 0, st>>>(ws_keys + so, ws_img + so, p.seed_ranges, nq, k, ws_keys, ws_img);
+    }
+    search_scan_launch<METRIC, FILTER>(t, st, tiles, p.ranges, p.seed_steps, n_steps, p.per_range, seeded ? ws_keys : nullptr, seeded ? ws_img : nullptr, ws_keys + list,
+                                       ws_img + list, flt);
     // the seed area is one more list in front of the main scan's: the prefix is not scanned again
     if (seeded) search_merge_kernel<<<nq, 64, 0, st>>>(ws_keys, ws_img, 1 + p.ranges, nq, k, d_out_keys, d_out_scores, d_out_counts);
     else search_merge_kernel<<<nq, 64, 0, st>>>(ws_keys + list, ws_img + list, p.ranges, nq, k, d_out_keys, d_out_scores, d_out_counts);
@@ -915,8 +914,7 @@ int mee_search(const mee_table* t, const float* d_queries, size_t n_queries, uin
     MEE_RANGE("mee_search");
     uint32_t max_grid = 0;
     if (int rc = search_check(t, n_queries, k, "mee_search", &max_grid)) return rc;
-    if (!d_queries || !d_out_keys || !d_out_scores || !d_workspace) return fail(MEE_ERR_INVALID_ARG, "mee_search: null argument");
-    if (((uintptr_t)d_queries & 15) || ((uintptr_t)d_workspace & 7)) return fail(MEE_ERR_INVALID_ARG, "mee_search: queries must be 16-byte aligned, the workspace 8-byte aligned");
+    if (int rc = search_pointer_check(d_queries, d_out_keys, d_out_scores, d_workspace, "mee_search")) return rc;
     DeviceGuard g(t->device);
     hipStream_t st = as_stream(stream);
     const uint64_t n_steps = (t->capacity + 31) / 32;
@@ -925,7 +923,7 @@ int mee_search(const mee_table* t, const float* d_queries, size_t n_queries, uin
     const uint32_t nq = (uint32_t)n_queries;
     int64_t* ws_keys = (int64_t*)d_workspace;
     uint32_t* ws_img = (uint32_t*)(ws_keys + (size_t)grid * nq * k);
-    const size_t lds = search_lds_bytes(t->dim, nq, k);
+    const size_t lds = search_lds_bytes(t->dim, nq, k, MEE_METRIC_IP);
     with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)(t->dim / 16), [&](auto ks) { with_flag(t->bf16_rows, [&](auto bf16) {
         search_scan_kernel<ks, bf16 ? kRowsBF16 : kRowsF32><<<grid, 64, lds, st>>>(t->keys, t->values, t->capacity, d_queries, nq, k, per_block, ws_keys, ws_img);
     }); });

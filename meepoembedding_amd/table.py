@@ -779,6 +779,13 @@ class LookupTable:
             raise MeepoError(_lib.ERR_OUT_OF_MEMORY, "publish_to: the serving table had no room for some keys (STATUS_TABLE_FULL): rebuild it with a larger capacity")
         return upserts, removed, None
 
+    def _check_metric_queries(self, metric: str, queries: torch.Tensor) -> None:
+        """what search and score ask of their metric and their queries"""
+        if metric not in _lib.METRICS:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"metric must be one of {sorted(_lib.METRICS)} (got {metric!r})")
+        if queries.dtype != torch.float32 or queries.device != self.device or queries.dim() != 2 or queries.shape[1] != self.dim:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"queries must be float32 [n_queries, {self.dim}] on {self.device} (got {queries.dtype} {list(queries.shape)} on {queries.device})")
+
     def search(self, queries: torch.Tensor, k: int, out_keys: torch.Tensor | None = None, out_scores: torch.Tensor | None = None, counts: bool = False,
                metric: str = "ip", exclude: torch.Tensor | None = None):
         """SPEC.md §3 "Search": for each row of `queries` ([Q, dim] float32 on the table's device) the k live keys whose rows have the greatest inner
@@ -797,10 +804,7 @@ class LookupTable:
         listed; duplicates, absent keys and reserved keys (search's INT64_MIN padding) match nothing, so exclude=previous_keys gives the next page.
         Every Q goes through the batched launches plus one that sorts the rows; with a row per query a large batch is cut into chunks of queries
         whose sorted rows stay within _EXCLUDE_SORTED_BYTES of workspace.  exclude=None is the call without it, in every bit."""
-        if metric not in _lib.METRICS:
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"metric must be one of {sorted(_lib.METRICS)} (got {metric!r})")
-        if queries.dtype != torch.float32 or queries.device != self.device or queries.dim() != 2 or queries.shape[1] != self.dim:
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"queries must be float32 [n_queries, {self.dim}] on {self.device} (got {queries.dtype} {list(queries.shape)} on {queries.device})")
+        self._check_metric_queries(metric, queries)
         if not isinstance(k, int) or not 1 <= k <= _lib.SEARCH_MAX_K:
             raise MeepoError(_lib.ERR_INVALID_ARG, f"k must be an int in [1, {_lib.SEARCH_MAX_K}] (got {k!r})")
         q = queries.contiguous()
@@ -811,23 +815,26 @@ class LookupTable:
                 raise MeepoError(_lib.ERR_INVALID_ARG, f"exclude must be int64 [{nq}, E] or [1, E] with 1 <= E <= {_lib.SEARCH_MAX_EXCLUDE} on {self.device} "
                                                        f"(got {exclude.dtype} {list(exclude.shape)} on {exclude.device})")
             exclude = exclude.contiguous()
-        wide = self.dim > 256   # mee_search has no such row: every Q through the batched launches
-        per_call = 0 if wide else min(_lib.SEARCH_MAX_QK // max(k, 8), max(_lib.SEARCH_MAX_QUERY_ELEMS // max(self.dim, 1) // 32 * 32, 1))
-        need = C.c_uint64()
-        batched = wide or nq > per_call   # past one call's limits: mee_search_batch, tiled and seeded, in chunks of its own cap
+        # The route, chosen once: the workspace query and the native call with their leading arguments, what either takes between k and its results
+        # (ws_mid for n queries, mid for the chunk of n queries at s), and the queries one call takes.
+        L, m, cap = _lib.lib(), _lib.METRICS[metric], _lib.SEARCH_BATCH_MAX_QUERIES
+        ws_mid, mid = lambda n: (), lambda s, n: ()
+        limit = 0 if self.dim > 256 else min(_lib.SEARCH_MAX_QK // max(k, 8), max(_lib.SEARCH_MAX_QUERY_ELEMS // max(self.dim, 1) // 32 * 32, 1))   # mee_search has no row past 256
         if exclude is not None:   # every Q through the batched launches of either metric, behind the launch that sorts the exclude rows
             ne, shared = exclude.shape[1], exclude.shape[0] == 1 and nq != 1
-            per_call = _lib.SEARCH_BATCH_MAX_QUERIES if shared else min(_lib.SEARCH_BATCH_MAX_QUERIES, max(_EXCLUDE_SORTED_BYTES // (8 << (ne - 1).bit_length()), 1))   # (a sorted row: E rounded up to a power of two)
-            check(_lib.lib().mee_search_filtered_workspace_bytes(self._h, _lib.METRICS[metric], max(min(nq, per_call), 1), k, 1 if shared else max(min(nq, per_call), 1),
-                                                                 ne, C.byref(need)))
+            per_call = cap if shared else min(cap, max(_EXCLUDE_SORTED_BYTES // (8 << (ne - 1).bit_length()), 1))   # (a sorted row: E rounded up to a power of two)
+            ws_bytes, native, head = L.mee_search_filtered_workspace_bytes, L.mee_search_filtered, (self._h, m)
+            ws_mid = lambda n: (1 if shared else n, ne)
+            mid = lambda s, n: ((exclude if shared else exclude[s:s + n]).data_ptr(), *ws_mid(n))
         elif metric != "ip":   # every Q through the batched launches of that metric
-            per_call = _lib.SEARCH_BATCH_MAX_QUERIES
-            check(_lib.lib().mee_search_metric_workspace_bytes(self._h, _lib.METRICS[metric], max(min(nq, per_call), 1), k, C.byref(need)))
-        elif batched:
-            per_call = _lib.SEARCH_BATCH_MAX_QUERIES
-            check(_lib.lib().mee_search_batch_workspace_bytes(self._h, max(min(nq, per_call), 1), k, C.byref(need)))
+            ws_bytes, native, head, per_call = L.mee_search_metric_workspace_bytes, L.mee_search_metric, (self._h, m), cap
+        elif self.dim > 256 or nq > limit:   # past one call's limits, or a wide row whatever Q: mee_search_batch, tiled and seeded, in chunks of its own cap
+            ws_bytes, native, head, per_call = L.mee_search_batch_workspace_bytes, L.mee_search_batch, (self._h,), cap
         else:
-            check(_lib.lib().mee_search_workspace_bytes(self._h, max(nq, 1), k, C.byref(need)))   # (every refusal of the table comes from here, before any launch)
+            ws_bytes, native, head, per_call = L.mee_search_workspace_bytes, L.mee_search, (self._h,), limit
+        need = C.c_uint64()
+        n1 = max(min(nq, per_call), 1)
+        check(ws_bytes(*head, n1, k, *ws_mid(n1), C.byref(need)))   # (every refusal of the table comes from here, before any launch)
         out_keys = _buffer(out_keys, "out_keys", torch.int64, (nq, k), self.device)
         out_scores = _buffer(out_scores, "out_scores", torch.float32, (nq, k), self.device)
         n_real = torch.empty(nq, dtype=torch.int32, device=self.device) if counts else None
@@ -837,19 +844,10 @@ class LookupTable:
         if ws is None or ws.numel() < need.value:
             ws = cache[stream] = torch.empty(need.value, dtype=torch.uint8, device=self.device)
         ok, osc = out_keys.view(nq, k), out_scores.view(nq, k)
-        if metric != "ip":
-            head = (_lib.lib().mee_search_metric, self._h, _lib.METRICS[metric])
-        else:
-            head = (_lib.lib().mee_search_batch if batched else _lib.lib().mee_search, self._h)
         for s in range(0, nq, per_call):
             n = min(per_call, nq - s)
-            if exclude is not None:
-                check(_lib.lib().mee_search_filtered(self._h, _lib.METRICS[metric], q[s:s + n].data_ptr(), n, k, (exclude if shared else exclude[s:s + n]).data_ptr(),
-                                                     1 if shared else n, ne, ok[s:s + n].data_ptr(), osc[s:s + n].data_ptr(),
-                                                     n_real[s:s + n].data_ptr() if counts else None, ws.data_ptr(), stream))
-                continue
-            check(head[0](*head[1:], q[s:s + n].data_ptr(), n, k, ok[s:s + n].data_ptr(), osc[s:s + n].data_ptr(),
-                          n_real[s:s + n].data_ptr() if counts else None, ws.data_ptr(), stream))
+            check(native(*head, q[s:s + n].data_ptr(), n, k, *mid(s, n), ok[s:s + n].data_ptr(), osc[s:s + n].data_ptr(),
+                         n_real[s:s + n].data_ptr() if counts else None, ws.data_ptr(), stream))
         return (out_keys, out_scores, n_real) if counts else (out_keys, out_scores)
 
     def score(self, queries: torch.Tensor, keys: torch.Tensor, out: torch.Tensor | None = None, found: torch.Tensor | None = None, metric: str = "ip"):
@@ -860,10 +858,7 @@ class LookupTable:
         with found 0, a NaN score is returned as NaN.  fp32-row and bf16-row tables, dim a multiple of 16 in [16, SEARCH_MAX_DIM] (past 256 a
         whole wave reduces a key: DESIGN.md §4 "Score", "Wide rows").  No gradient.
         metric="cosine" (mee_score_metric): search's cosine, dot / (|q| |row|); a zero row or a zero query scores NaN with found 1."""
-        if metric not in _lib.METRICS:
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"metric must be one of {sorted(_lib.METRICS)} (got {metric!r})")
-        if queries.dtype != torch.float32 or queries.device != self.device or queries.dim() != 2 or queries.shape[1] != self.dim:
-            raise MeepoError(_lib.ERR_INVALID_ARG, f"queries must be float32 [n_queries, {self.dim}] on {self.device} (got {queries.dtype} {list(queries.shape)} on {queries.device})")
+        self._check_metric_queries(metric, queries)
         if keys.dtype != torch.int64 or keys.device != self.device or keys.dim() != 2 or keys.shape[0] != queries.shape[0]:
             raise MeepoError(_lib.ERR_INVALID_ARG, f"keys must be int64 [{queries.shape[0]}, n_candidates] on {self.device} (got {keys.dtype} {list(keys.shape)} on {keys.device})")
         q, k = queries.contiguous(), keys.contiguous()

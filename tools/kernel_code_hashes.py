@@ -17,9 +17,12 @@ import sys
 
 LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
-         "-Wno-unused-function", "-Wno-pass-failed", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"]
-TUS = ["meepo_table", "meepo_find", "meepo_export", "meepo_apply", "meepo_dedup", "meepo_router", "meepo_group", "meepo_sharded", "meepo_mixed", "meepo_move", "meepo_padded", "meepo_pool_max"]
+# the product's own source list and flags, per-file flags included: what is hashed here is what build() ships
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from __graft_entry__ import HIP_FILE_FLAGS, HIP_FLAGS, HIP_SOURCES  # noqa: E402
+
+FLAGS = [f for f in HIP_FLAGS if f != "-shared"] + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"]
+TUS = [s[:-len(".hip")] for s in HIP_SOURCES]
 
 
 def hashes(co):
@@ -35,7 +38,9 @@ def hashes(co):
             name = m.group(1)
             kernels[name] = []
         elif name and line.strip() and line.strip() != "...":   # "...": the padding up to the next kernel's alignment, which the last kernel of a code object lacks
-            kernels[name].append(re.sub(r"\s*//.*$", "", line).strip())
+            # a branch target reads <kernel+0x1c>: the kernel's OWN name goes (a branch into another symbol keeps its name), so that a renamed
+            # instance can hash like its predecessor
+            kernels[name].append(re.sub(r"\s*//.*$", "", line).replace("<" + name + "+", "<+").replace("<" + name + ">", "<>").strip())
     names = list(kernels)
     demangled = subprocess.run(["c++filt"], input="\n".join(names), check=True, capture_output=True, text=True).stdout.splitlines()
     rows = []
@@ -55,7 +60,7 @@ def build(src, out, tus):
     jobs = []
     for tu in tus:
         co = os.path.join(out, tu + ".co")
-        jobs.append((tu, co, subprocess.Popen([HIPCC, *FLAGS, "-c", os.path.join(src, tu + ".hip"), "-o", co], stderr=open(os.path.join(out, tu + ".remarks"), "w"))))
+        jobs.append((tu, co, subprocess.Popen([HIPCC, *FLAGS, *HIP_FILE_FLAGS.get(tu + ".hip", []), "-c", os.path.join(src, tu + ".hip"), "-o", co], stderr=open(os.path.join(out, tu + ".remarks"), "w"))))
     for tu, co, p in jobs:
         if p.wait() != 0:
             sys.exit(f"{tu}: the compiler failed, see {out}/{tu}.remarks")

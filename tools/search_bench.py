@@ -6,7 +6,11 @@ a row is its pass-to-pass difference (the method of profiles/int8_rows.md).
                       seeded main scan, merge) past them
     NAME              --libs NAME=PATH,…: the same table searched through ANOTHER build of the library, loaded beside this one — the parent commit's
                       (no mee_search_batch: the batch is split into mee_search calls by the per-call limits, as its Python layer did) or a build of
-                      this tree with another seed divisor or tile rule (-DMEE_SEARCH_SEED_DIV=…, -DMEE_SEARCH_TILE_MAX_QUERIES=32)
+                      this tree with another seed divisor or tile rule (-DMEE_SEARCH_SEED_DIV=…, -DMEE_SEARCH_TILE_MAX_QUERIES=32).  With --metric cosine the
+                      row goes through that build's mee_search_metric; with --exclude it becomes "NAME filtered" and "NAME filtered shared", through its
+                      mee_search_filtered.  Naming one build twice (parent=P,parent2=P) gives a row's noise floor: the same code against itself;
+                      naming this tree's own library too (tree=…) times like against like: the rows above go through LookupTable.search (a workspace
+                      query and result allocations per call), a NAME row through bare calls on buffers the tool holds
     matmul + topk     on a PREBUILT [N, dim] bf16 matrix of the same table: queries.bfloat16() @ M.T, torch.topk, keys[positions]
     refresh           building that matrix — export() and the cast to bf16 — timed once and reported apart: the cost the matrix path pays after every
                       publish, and the second copy of the table it keeps
@@ -77,25 +81,41 @@ def per_call_limit(k):
 
 
 def other_build(path):
-    """-> search(t, queries, k) through the library at `path`, on the handle of this process's table (the table layout is the same in every build named
-    above): its mee_search_batch past the per-call limits if it has one, split mee_search calls otherwise; buffers and workspace allocated once"""
+    """-> search(t, queries, k, metric="ip", exclude=None) through the library at `path`, on the handle of this process's table (the table layout is the
+    same in every build named above): its mee_search_batch past the per-call limits if it has one, split mee_search calls otherwise; metric="cosine"
+    and exclude=[Q or 1, E] as ONE call of its mee_search_metric / mee_search_filtered, as table.search makes it at the shapes timed here; buffers and
+    workspace allocated once per shape"""
     L = C.CDLL(path)
     names = [nm for nm in _lib.PROTOTYPES if nm.startswith("mee_search") and hasattr(L, nm)]
     for nm in names:
         getattr(L, nm).restype, getattr(L, nm).argtypes = _lib.PROTOTYPES[nm]
     held = {}
 
-    def search(t, queries, k):
+    def search(t, queries, k, metric="ip", exclude=None):
         nq, step = queries.shape[0], per_call_limit(k)
         batched = nq > step and "mee_search_batch" in names
         if batched:
             step = _lib.SEARCH_BATCH_MAX_QUERIES
-        if (nq, k) not in held:
+        shape = (nq, k, metric, None if exclude is None else tuple(exclude.shape))
+        if shape not in held:
             need = C.c_uint64()
-            _lib.check((L.mee_search_batch_workspace_bytes if batched else L.mee_search_workspace_bytes)(t._h, min(nq, step), k, C.byref(need)))
-            held.clear()
-            held[nq, k] = (torch.empty(nq, k, dtype=torch.int64, device=dev), torch.empty(nq, k, device=dev), torch.empty(need.value, dtype=torch.uint8, device=dev))
-        ok, osc, ws = held[nq, k]
+            if exclude is not None:
+                _lib.check(L.mee_search_filtered_workspace_bytes(t._h, _lib.METRICS[metric], nq, k, exclude.shape[0], exclude.shape[1], C.byref(need)))
+            elif metric != "ip":
+                _lib.check(L.mee_search_metric_workspace_bytes(t._h, _lib.METRICS[metric], nq, k, C.byref(need)))
+            else:
+                _lib.check((L.mee_search_batch_workspace_bytes if batched else L.mee_search_workspace_bytes)(t._h, min(nq, step), k, C.byref(need)))
+            if any(key[:2] != shape[:2] for key in held):   # the rows of one (Q, k) take turns: their buffers stay
+                held.clear()
+            held[shape] = (torch.empty(nq, k, dtype=torch.int64, device=dev), torch.empty(nq, k, device=dev), torch.empty(need.value, dtype=torch.uint8, device=dev))
+        ok, osc, ws = held[shape]
+        if exclude is not None:
+            _lib.check(L.mee_search_filtered(t._h, _lib.METRICS[metric], queries.data_ptr(), nq, k, exclude.data_ptr(), exclude.shape[0], exclude.shape[1], ok.data_ptr(),
+                                             osc.data_ptr(), None, ws.data_ptr(), None))
+            return ok, osc
+        if metric != "ip":
+            _lib.check(L.mee_search_metric(t._h, _lib.METRICS[metric], queries.data_ptr(), nq, k, ok.data_ptr(), osc.data_ptr(), None, ws.data_ptr(), None))
+            return ok, osc
         for s in range(0, nq, step):
             n = min(step, nq - s)
             _lib.check((L.mee_search_batch if batched else L.mee_search)(t._h, queries[s:s + n].data_ptr(), n, k, ok[s:s + n].data_ptr(), osc[s:s + n].data_ptr(),
@@ -148,6 +168,11 @@ for value_dtype in (torch.float32, torch.bfloat16):
                     ex = top[:, :ne].contiguous()
                     rows = {"search": lambda: t.search(queries, k, metric=args.metric), "filtered": lambda: t.search(queries, k, metric=args.metric, exclude=ex),
                             "filtered shared": lambda: t.search(queries, k, metric=args.metric, exclude=ex[:1])}
+                    for nm, fn in others.items():
+                        rows[nm + " filtered"] = lambda fn=fn: fn(t, queries, k, args.metric, ex)
+                        rows[nm + " filtered shared"] = lambda fn=fn: fn(t, queries, k, args.metric, ex[:1])
+                        assert torch.equal(rows[nm + " filtered"]()[0], rows["filtered"]()[0]) and torch.equal(rows[nm + " filtered shared"]()[0], rows["filtered shared"]()[0]), \
+                            f"{nm} and this tree's filtered search disagree"
                     if k + ne <= _lib.SEARCH_MAX_K:
                         def overfetch():
                             wk, ws = t.search(queries, k + ne, metric=args.metric)
@@ -172,9 +197,9 @@ for value_dtype in (torch.float32, torch.bfloat16):
                 assert torch.equal(same_launches(t, queries, k)[0], t.search(queries, k)[0])
             if not args.no_matmul:
                 rows["matmul + topk"] = matmul_topk
-            for nm, fn in others.items() if args.metric == "ip" else ():
-                rows[nm] = lambda fn=fn: fn(t, queries, k)
-                assert torch.equal(fn(t, queries, k)[0], got), f"{nm} and this tree's search disagree"   # exact by contract, whatever the build
+            for nm, fn in others.items():   # (against the first row: "search", or "cosine")
+                rows[nm] = lambda fn=fn: fn(t, queries, k, args.metric)
+                assert torch.equal(fn(t, queries, k, args.metric)[0], got), f"{nm} and this tree's search disagree"   # exact by contract, whatever the build
             passes = [timed_rows(rows, args.reps) for _ in range(2)]
             us = {nm: (passes[0][nm] + passes[1][nm]) / 2 for nm in rows}
             # this tree: one call either way; past the limits every tile's blocks ask for the table (tiles that walk one range may meet in L2), in
