@@ -10,7 +10,7 @@ import torch
 import __graft_entry__
 
 __graft_entry__.build()
-from meepoembedding_amd import INIT_UNIFORM, OPT_ADAGRAD, LookupTable  # noqa: E402
+from meepoembedding_amd import INIT_UNIFORM, OPT_ADAGRAD, LookupTable, TableGroup  # noqa: E402
 
 dev = torch.device("cuda", 0)
 dim, items, k = 64, 50_000, 10
@@ -61,3 +61,10 @@ keys2, scores2 = serving.search(users, k)
 assert int(keys2[0, 0]) == items + 7 and not torch.isin(keys2, best).any()
 print(f"published {upserts} changed rows and {removed} removals; user 0's best is now item {int(keys2[0, 0])} at {float(scores2[0, 0]):.4f}; "
       f"none of the {best.numel()} removed items is returned any more")
+
+creators = LookupTable(4096, dim, device=dev, max_batch=1 << 12, value_dtype=torch.bfloat16)   # a second, small corpus: items plus creators, searched with the
+creators.insert(torch.arange(1000, device=dev), torch.randn(1000, dim, device=dev))            # same user vectors in ONE call of three launches (TableGroup.search)
+both = TableGroup([serving, creators])
+gkeys, gscores = both.search(torch.stack([users, users]), k)    # queries [n_tables, Q, dim] -> [n_tables, Q, k]: block j is member j's own search, bit for bit
+assert torch.equal(gkeys[0], keys2) and torch.equal(gscores[0], scores2) and torch.equal(gkeys[1], creators.search(users, k)[0])
+print(f"both corpora in one call: user 0's best item {int(gkeys[0, 0, 0])}, best creator {int(gkeys[1, 0, 0])}")

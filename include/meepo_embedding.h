@@ -392,7 +392,7 @@ int mee_probe_histogram(const mee_table* t, const int64_t* d_keys, size_t n, uin
  * and created with the rounded default_value; found masks, reserved keys, positions outside the segments, empty bags, the clamping of the offsets and
  * each member's own default row included.  The operators it has: mee_find_grouped / _as (fp32 out widens exactly, bf16 out returns the stored bits),
  * mee_group_find_pooled / _as without weights (SUM | MEAN; rows widened and added in fp32 in position order, the finished bag row rounded once for bf16
- * out), mee_group_find_pooled_jagged, mee_group_value_dtype, mee_group_destroy; mee_reserve on a member between lookups keeps working.  Everything else
+ * out), mee_group_find_pooled_jagged, mee_group_search (each member's block is that member's mee_search_metric), mee_group_value_dtype, mee_group_destroy; mee_reserve on a member between lookups keeps working.  Everything else
  * — mee_group_find_or_insert / _as / _admit, mee_group_admission_decay, every mee_group_apply_*, mee_group_find_pooled_weighted and a non-null d_weights of mee_group_find_pooled_as,
  * mee_group_pooled_weighted_backward, and a non-null d_located_out of any pooled form (located rows exist for the backward, which this group does not
  * have) — returns MEE_ERR_UNSUPPORTED before anything is launched or written; mee_group_set_tuning answers as for any group without an apply. */
@@ -1245,6 +1245,29 @@ int mee_search_filtered_workspace_bytes(const mee_table* t, int metric, size_t n
 int mee_search_filtered(const mee_table* t, int metric, const float* d_queries, size_t n_queries, uint32_t k, const int64_t* d_exclude,
                         size_t exclude_rows, size_t n_exclude, int64_t* d_out_keys, float* d_out_scores, uint32_t* d_out_counts /* nullable */,
                         void* d_workspace, void* stream);
+
+/* ---- groups: every member of a table group searched with its own queries in one call (SPEC.md §3 "Search", "Groups") ---------------------------------
+ * d_queries is [n_tables][n_queries][dim] fp32 — the same number of queries for every member, as bags_per_table of the pooled lookups —
+ * d_out_keys / d_out_scores are [n_tables][n_queries][k], d_out_counts [n_tables][n_queries] or null.  Member j's block of the outputs is, bit for
+ * bit, what mee_search_metric(member j, metric, d_queries + j * n_queries * dim, n_queries, k, ...) writes: keys, score bits, counts, the
+ * INT64_MIN / -inf tail, the tie rule, NaN scores, an empty member — the single-table answer depends on the table's contents only, not on how the
+ * scan was cut.  Three launches whatever the number of members: a one-block plan that reads every member's slot count from the group's device
+ * descriptors and cuts the collection's 32-slot steps into ranges of one length, one scan over all (tile, range) pairs, one merge with a wave per
+ * (member, query).  No seed pass: a large member is answered exactly, but its thresholds start at nothing.
+ * Served: fp32-row and bf16-row groups, dim % 16 == 0 and 16 <= dim <= MEE_SEARCH_MAX_DIM, 1 <= k <= MEE_SEARCH_MAX_K, both metrics,
+ * 1 <= n_tables * n_queries <= MEE_SEARCH_BATCH_MAX_QUERIES.  Every other shape, an unknown metric and a null or misaligned pointer (queries: 16
+ * bytes, workspace: 8) are MEE_ERR_INVALID_ARG before anything is launched or written.  Not offered: exclusion lists over a group, a grouped score,
+ * mixed-width, tiered and sharded groups.
+ * d_workspace: mee_group_search_workspace_bytes(g, metric, n_queries, k) bytes, 8-byte aligned:
+ *     round_up(8 + 4 * (n_tables + 1), 16) + (R + n_tables) * n_queries * k * 12,   R = max(1, 8 * compute units / n_tiles),
+ * n_tiles = n_queries divided by the queries of one scan tile, rounded up (one row block of 32 up to dim 256, fewer past it and for large k: as
+ * mee_search_batch) — the device, the group's dim and n_tables, the metric, n_queries and k only, not the members' capacities.  Two calls that may
+ * overlap need a workspace each.  After mee_reserve on a member the next call re-reads that member's planes (one stream synchronisation, as
+ * mee_find_grouped); otherwise no host synchronisation, no allocation, no memset, no atomics, vector stores only, nothing of any table is written:
+ * safe under stream capture. */
+int mee_group_search_workspace_bytes(const mee_group* g, int metric, size_t n_queries, uint32_t k, uint64_t* bytes_out);
+int mee_group_search(mee_group* g, int metric, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
+                     uint32_t* d_out_counts /* nullable */, void* d_workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -200,7 +200,7 @@ private:
 
 // Many tables (same device, same dim) served by ONE find launch over their concatenated ("jagged") key batches.
 // Members that are all bf16-row tables (TableOptions::bf16_rows) make a bf16-row group, the serving form of a collection: max_apply_batch must be 0, the
-// lookups (find, find_pooled without weights or located rows, the jagged form) are bit for bit the per-member lookups, and everything that trains —
+// lookups (find, find_pooled without weights or located rows, the jagged form, search) are bit for bit the per-member lookups, and everything that trains —
 // find_or_insert, apply_*, the weighted forms — throws MEE_ERR_UNSUPPORTED.  fp32-row and bf16-row tables never share a group.
 class Group {
 public:
@@ -229,6 +229,9 @@ public:
         check(mee_group_find_or_insert_admit(g_, d_keys, d_offsets, n, d_out, out_dtype, d_found, min_count, d_min_counts, stream));
     }
     void admission_decay(uint32_t shift = 1, void* stream = nullptr) { check(mee_group_admission_decay(g_, shift, stream)); }
+    // Table::search_metric of every member on its own n_queries queries, three launches (mee_group_search): d_queries [n_tables][n_queries][dim], outputs [n_tables][n_queries][k]; d_workspace of search_workspace_bytes(metric, n_queries, k) bytes
+    uint64_t search_workspace_bytes(int metric, size_t n_queries, uint32_t k) const { uint64_t b = 0; check(mee_group_search_workspace_bytes(g_, metric, n_queries, k, &b)); return b; }
+    void search(int metric, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores, uint32_t* d_out_counts, void* d_workspace, void* stream = nullptr) { check(mee_group_search(g_, metric, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream)); }
     void find_pooled_as(const int64_t* d_keys, size_t n, const uint64_t* d_bag_offsets, size_t bags_per_table, const float* d_weights, void* d_out, uint32_t out_dtype, uint8_t* d_found = nullptr, int64_t* d_located_out = nullptr, int mode = MEE_POOL_SUM, void* stream = nullptr) {
         check(mee_group_find_pooled_as(g_, d_keys, n, d_bag_offsets, bags_per_table, d_weights, d_out, out_dtype, d_found, d_located_out, mode, stream));
     }

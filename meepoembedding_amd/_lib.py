@@ -311,6 +311,9 @@ PROTOTYPES = {
     # filtered search (table, metric, queries, n_queries, k, exclude [exclude_rows, n_exclude], exclude_rows, n_exclude, out_keys, out_scores, out_counts | null, workspace, stream)
     "mee_search_filtered_workspace_bytes": (C.c_int, [_vp, C.c_int, _sz, _u32, _sz, _sz, C.POINTER(_u64)]),
     "mee_search_filtered": (C.c_int, [_vp, C.c_int, _vp, _sz, _u32, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
+    # grouped search (group, metric, queries [n_tables, n_queries, dim], n_queries, k, out_keys, out_scores, out_counts | null, workspace, stream)
+    "mee_group_search_workspace_bytes": (C.c_int, [_vp, C.c_int, _sz, _u32, C.POINTER(_u64)]),
+    "mee_group_search": (C.c_int, [_vp, C.c_int, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _NARROW_ROWS = {torch.bfloat16: "a bf16-row table (value_dtype=torch.bfloat16) is a serving table with find, find_pooled, insert, assign, ",

@@ -29,6 +29,11 @@
 //            one block a row), then the batched launches with the FILTER instances of the two scan kernels — a lane that is about to append first looks
 //            its key up in its query's sorted row by a lower-bound search in global memory (DESIGN.md §4 "Search", "Exclusion").  The hot path, the
 //            merges and every unfiltered instance do not change by it.
+//   groups   mee_group_search, every member of a table group against its own queries in three launches whatever the number of members:
+//            group_search_plan_kernel (one block: the members' steps from the group's device descriptors, ONE step length for the collection, each
+//            member's ranges as a prefix array), search_group_scan_kernel<KS, ROWS, METRIC> / search_group_wide_scan_kernel<ROWS, METRIC> — the scan
+//            bodies above behind a decoder that finds its member by a binary search of the block's range index in that array — and
+//            group_search_merge_kernel, one wave per (member, query) over the member's own lists.  No seed pass (DESIGN.md §4 "Search", "Groups").
 // Only vector stores, no atomics, nothing of the table is written.
 //
 // The upstream snapshot has no search; the semantics are SPEC.md §3 "Search".
@@ -713,6 +718,115 @@ __global__ __launch_bounds__(64) void search_seed_merge_kernel(const int64_t* __
     }
 }
 
+// ---- groups: every member of a table group searched in ONE scan (SPEC.md §3 "Search", "Groups"; DESIGN.md §4 "Search", "Groups") ------------------
+// The members' steps are cut into ranges of ONE length S, so that the collection's total work, not each member's, is spread over the block budget:
+// member j owns the ranges [first[j], first[j + 1]) of a flat range index, ceil(steps_j / S) of them (the last one shorter, a small member's only one
+// shorter than S).  The plan lies at the front of the workspace: S (8 bytes), first[0 .. n_tables] (a word each), rounded up to 16 bytes; the lists
+// [range][n_queries][k] follow — a member's lists are consecutive, so its merge is search_merge_lists from list first[j] on.
+__host__ __device__ constexpr size_t group_search_plan_bytes(uint32_t n_tables) { return (8 + 4 * ((size_t)n_tables + 1) + 15) / 16 * 16; }
+__device__ __forceinline__ const uint32_t* group_search_first(const uint64_t* plan) { return reinterpret_cast<const uint32_t*>(plan + 1); }
+// the slots of a member (SPEC.md §2: capacity = buckets x bucket width, exactly — what mee_table keeps as `capacity`) and the 32-slot steps over them
+__host__ __device__ constexpr uint64_t group_search_slots(uint64_t nb) { return nb * (uint64_t)kW; }
+__host__ __device__ constexpr uint64_t group_search_steps(uint64_t nb) { return (group_search_slots(nb) + 31) / 32; }
+
+// The plan, on the device: it reads the descriptors group_refresh keeps current, so it follows mee_reserve without a host copy and stands in a captured
+// graph.  One block, thread j = member j (blockDim = n_tables rounded up to whole waves, <= kMaxGroupTables): the sum of the members' steps by a wave
+// and a block reduction, S = ceil(sum / max_ranges), each member's ranges, and their exclusive prefix by a wave scan and the waves' totals.
+// sum_j ceil(steps_j / S) <= sum / S + n_tables <= max_ranges + n_tables: what the host sized the grid and the lists for, so nothing is read back.
+__global__ __launch_bounds__(kMaxGroupTables) void group_search_plan_kernel(const GroupDesc* __restrict__ desc, uint32_t n_tables, uint32_t max_ranges,
+                                                                            uint64_t* __restrict__ plan) {
+    __shared__ uint64_t wave_steps[kMaxGroupTables / 64];
+    __shared__ uint32_t wave_ranges[kMaxGroupTables / 64];
+    const uint32_t j = threadIdx.x, lane = j & 63, w = j >> 6, n_waves = blockDim.x >> 6;
+    const uint64_t steps = j < n_tables ? group_search_steps(desc[j].nb) : 0;
+    unsigned long long sum = steps;
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+    if (lane == 0) wave_steps[w] = sum;
+    __syncthreads();
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n_waves; ++i) total += wave_steps[i];
+    const uint64_t S = total > max_ranges ? (total + max_ranges - 1) / max_ranges : 1;
+    const uint32_t ranges = j >= n_tables ? 0u : steps > S ? (uint32_t)((steps + S - 1) / S) : 1u;
+    uint32_t incl = ranges;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d);
+        if ((int)lane >= d) incl += up;
+    }
+    if (lane == 63) wave_ranges[w] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    for (uint32_t i = 0; i < w; ++i) before += wave_ranges[i];
+    uint32_t* const first = reinterpret_cast<uint32_t*>(plan + 1);
+    if (j < n_tables) first[j] = before + incl - ranges;
+    if (j == n_tables - 1) first[n_tables] = before + incl;
+    if (j == 0) plan[0] = S;
+}
+
+// search_scan_block for a group: the flat grid holds n_tiles blocks per range index r, for every r the host's bound allows; a block past the plan's
+// last range returns at once.  The member of r is the upper bound of r in first[] — first[] rises strictly, every member has a range — by one binary
+// search in global memory (a few hundred L2-resident words at the most, read once per block; the scan body owns the dynamic LDS from offset 0), the
+// same in every lane and said so.  The member's planes and slot count come from its descriptor; SCAN is called as search_scan_block calls it,
+// without seeds and without a filter.  queries: [n_tables][nq_all][dim].
+template <auto SCAN>
+__device__ __forceinline__ void search_group_scan_block(const GroupDesc* __restrict__ desc, uint32_t n_tables, uint32_t dim, const float* __restrict__ queries,
+                                                        uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k, const uint64_t* __restrict__ plan,
+                                                        int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
+    const uint32_t t = blockIdx.x % n_tiles, r = blockIdx.x / n_tiles;
+    const uint32_t* __restrict__ first = group_search_first(plan);
+    if (r >= first[n_tables]) return;   // block-uniform
+    uint32_t lo = 0, hi = n_tables;     // first[lo] <= r < first[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first[mid] <= r) lo = mid; else hi = mid;
+    }
+    const uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+    const GroupDesc d = desc[j];
+    const uint64_t capacity = group_search_slots(d.nb), n_steps = group_search_steps(d.nb), S = plan[0];
+    const uint32_t q0 = t * tile, nq = nq_all - q0 < tile ? nq_all - q0 : tile;
+    uint64_t s0 = (uint64_t)(r - first[j]) * S, s1 = s0 + S;
+    if (s1 > n_steps) s1 = n_steps;
+    if (s0 > s1) s0 = s1;
+    SCAN(dim, d.tkeys, d.values, capacity, queries + ((size_t)j * nq_all + q0) * dim, nq, k, s0, s1, nullptr, nullptr, (size_t)r * nq_all + q0, ws_keys, ws_img,
+         SearchFilter{});
+}
+
+template <int KS, int ROWS, int METRIC>
+__global__ __launch_bounds__(64) void search_group_scan_kernel(const GroupDesc* __restrict__ desc, uint32_t n_tables, const float* __restrict__ queries,
+                                                               uint32_t nq_all, uint32_t tile, uint32_t n_tiles, uint32_t k, const uint64_t* __restrict__ plan,
+                                                               int64_t* __restrict__ ws_keys, uint32_t* __restrict__ ws_img) {
+    search_group_scan_block<search_scan_body<KS, ROWS, METRIC, false>>(desc, n_tables, 16 * KS, queries, nq_all, tile, n_tiles, k, plan, ws_keys, ws_img);
+}
+template <int ROWS, int METRIC>
+__global__ __launch_bounds__(64) void search_group_wide_scan_kernel(const GroupDesc* __restrict__ desc, uint32_t n_tables, uint32_t dim,
+                                                                    const float* __restrict__ queries, uint32_t nq_all, uint32_t tile, uint32_t n_tiles,
+                                                                    uint32_t k, const uint64_t* __restrict__ plan, int64_t* __restrict__ ws_keys,
+                                                                    uint32_t* __restrict__ ws_img) {
+    search_group_scan_block<search_wide_scan_body<ROWS, METRIC, false>>(desc, n_tables, dim, queries, nq_all, tile, n_tiles, k, plan, ws_keys, ws_img);
+}
+
+// One wave per (member, query): search_merge_kernel over the member's own lists, into row member * nq + query of the outputs — its epilogue, written out
+// again: keys and scores, the padded tail and the count, no memset in front (search_merge_kernel keeps its machine code that way).
+__global__ __launch_bounds__(64) void group_search_merge_kernel(const uint64_t* __restrict__ plan, const int64_t* __restrict__ ws_keys,
+                                                                const uint32_t* __restrict__ ws_img, uint32_t nq, uint32_t k, int64_t* __restrict__ out_keys,
+                                                                float* __restrict__ out_scores, uint32_t* __restrict__ out_counts) {
+    const uint32_t j = blockIdx.x / nq, q = blockIdx.x % nq;
+    const int lane = threadIdx.x;
+    const uint32_t* __restrict__ first = group_search_first(plan);
+    const uint32_t f0 = first[j], n_lists = first[j + 1] - f0;
+    const size_t o = (size_t)f0 * nq * k;
+    uint32_t img;
+    int64_t key;
+    search_merge_lists(ws_keys + o, ws_img + o, n_lists, nq, k, q, lane, img, key);
+    const size_t row = blockIdx.x;
+    const bool real = (uint32_t)lane < k && img != 0u;
+    if ((uint32_t)lane < k) {
+        out_keys[row * k + lane] = real ? key : kEmpty;
+        out_scores[row * k + lane] = real ? image_score(img) : -__builtin_inff();
+    }
+    const uint64_t rm = __ballot(real);
+    if (out_counts && lane == 0) out_counts[row] = (uint32_t)__popcll(rm);
+}
+
 // =========================================================================================================
 // host side
 // =========================================================================================================
@@ -898,6 +1012,46 @@ static int search_metric_check(int metric, const char* name) {
     return fail(MEE_ERR_INVALID_ARG, "%s: metric must be MEE_METRIC_IP (0) or MEE_METRIC_COSINE (1) (got %d)", name, metric);
 }
 
+// ---- the grouped search's launch plan on the host: the tiles as search_batch_plan cuts them, the ranges of the WHOLE collection, and with them the
+// bound on the range indices the device-side plan can hand out — the blocks of the grid and the lists of the workspace
+struct GroupSearchShape {
+    uint32_t tile, n_tiles;
+    uint32_t max_ranges;   // R: the block budget divided between the tiles
+    uint32_t lists;        // R + n_tables
+    uint64_t bytes(uint32_t n_tables, size_t nq, uint32_t k) const { return group_search_plan_bytes(n_tables) + (uint64_t)lists * nq * k * 12; }
+};
+// what both group entry points refuse, before anything is launched or written
+static int group_search_check(const mee_group* g, int metric, size_t nq, uint32_t k, const char* name, GroupSearchShape* s) {
+    if (!g) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (int rc = search_metric_check(metric, name)) return rc;
+    if (g->dim % 16 || g->dim < 16 || g->dim > MEE_SEARCH_MAX_DIM)
+        return fail(MEE_ERR_INVALID_ARG, "%s: dim must be a multiple of 16 in [16, %d] (got %u)", name, MEE_SEARCH_MAX_DIM, g->dim);
+    if (k < 1 || k > MEE_SEARCH_MAX_K) return fail(MEE_ERR_INVALID_ARG, "%s: k must be in [1, %d] (got %u)", name, MEE_SEARCH_MAX_K, k);
+    if (nq < 1 || nq > MEE_SEARCH_BATCH_MAX_QUERIES / g->n_tables)
+        return fail(MEE_ERR_INVALID_ARG, "%s: n_tables * n_queries must be in [1, %d] (got %u tables x %zu queries)", name, MEE_SEARCH_BATCH_MAX_QUERIES, g->n_tables, nq);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess || cus <= 0) cus = 256;
+    const uint32_t max_grid = (uint32_t)cus * kSearchBlocksPerCU;
+    s->tile = search_batch_tile(g->dim, k, metric);
+    s->n_tiles = ((uint32_t)nq + s->tile - 1) / s->tile;
+    s->max_ranges = max_grid / s->n_tiles > 1 ? max_grid / s->n_tiles : 1;
+    s->lists = s->max_ranges + g->n_tables;
+    return MEE_OK;
+}
+// The one scan launch of a group's row shape: search_scan_launch's dispatch with the grouped kernels, n_tiles x lists one-wave blocks.
+template <int METRIC>
+static void group_search_scan_launch(const mee_group* g, hipStream_t st, const SearchTiles& q, uint32_t lists, const uint64_t* plan, int64_t* out_keys, uint32_t* out_img) {
+    const uint32_t blocks = q.n_tiles * lists, tile_nq = q.tile < q.nq ? q.tile : q.nq;
+    if (g->dim > 256) with_flag(g->bf16_rows, [&](auto bf16) {
+        search_group_wide_scan_kernel<bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, search_wide_lds_bytes(g->dim, tile_nq, q.k), st>>>(
+            g->d_desc, g->n_tables, g->dim, q.d_queries, q.nq, q.tile, q.n_tiles, q.k, plan, out_keys, out_img);
+    });
+    else with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)(g->dim / 16), [&](auto ks) { with_flag(g->bf16_rows, [&](auto bf16) {
+        search_group_scan_kernel<ks, bf16 ? kRowsBF16 : kRowsF32, METRIC><<<blocks, 64, search_lds_bytes(g->dim, tile_nq, q.k, METRIC), st>>>(
+            g->d_desc, g->n_tables, q.d_queries, q.nq, q.tile, q.n_tiles, q.k, plan, out_keys, out_img);
+    }); });
+}
+
 extern "C" {
 
 int mee_search_workspace_bytes(const mee_table* t, size_t n_queries, uint32_t k, uint64_t* bytes_out) {
@@ -976,6 +1130,38 @@ int mee_search_filtered(const mee_table* t, int metric, const float* d_queries, 
     if (metric == MEE_METRIC_IP)
         return search_batch_launch<MEE_METRIC_IP, true>(t, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream, "mee_search_filtered", ex);
     return search_batch_launch<MEE_METRIC_COSINE, true>(t, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream, "mee_search_filtered", ex);
+}
+
+int mee_group_search_workspace_bytes(const mee_group* g, int metric, size_t n_queries, uint32_t k, uint64_t* bytes_out) {
+    const char* name = "mee_group_search_workspace_bytes";
+    if (!bytes_out) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    *bytes_out = 0;
+    GroupSearchShape s{};
+    if (int rc = group_search_check(g, metric, n_queries, k, name, &s)) return rc;
+    *bytes_out = s.bytes(g->n_tables, n_queries, k);
+    return MEE_OK;
+}
+
+int mee_group_search(mee_group* g, int metric, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores,
+                     uint32_t* d_out_counts, void* d_workspace, void* stream) {
+    MEE_RANGE("mee_group_search");
+    GroupSearchShape s{};
+    if (int rc = group_search_check(g, metric, n_queries, k, "mee_group_search", &s)) return rc;
+    if (int rc = search_pointer_check(d_queries, d_out_keys, d_out_scores, d_workspace, "mee_group_search")) return rc;
+    if (int rc = group_refresh(g, stream)) return rc;   // a member's planes and slot count may have moved (mee_reserve)
+    DeviceGuard guard(g->device);
+    hipStream_t st = as_stream(stream);
+    const uint32_t nq = (uint32_t)n_queries;
+    uint64_t* plan = (uint64_t*)d_workspace;
+    int64_t* ws_keys = (int64_t*)((unsigned char*)d_workspace + group_search_plan_bytes(g->n_tables));
+    uint32_t* ws_img = (uint32_t*)(ws_keys + (size_t)s.lists * nq * k);
+    group_search_plan_kernel<<<1, (g->n_tables + 63) / 64 * 64, 0, st>>>(g->d_desc, g->n_tables, s.max_ranges, plan);
+    const SearchTiles tiles{d_queries, nq, s.tile, s.n_tiles, k};
+    if (metric == MEE_METRIC_COSINE) group_search_scan_launch<MEE_METRIC_COSINE>(g, st, tiles, s.lists, plan, ws_keys, ws_img);
+    else group_search_scan_launch<MEE_METRIC_IP>(g, st, tiles, s.lists, plan, ws_keys, ws_img);
+    group_search_merge_kernel<<<g->n_tables * nq, 64, 0, st>>>(plan, ws_keys, ws_img, nq, k, d_out_keys, d_out_scores, d_out_counts);
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
 }
 
 }  // extern "C"

@@ -1227,7 +1227,10 @@ class TableGroup:
 
     Members that are ALL bf16-row tables (value_dtype == torch.bfloat16) make a bf16-row group, the serving form of a collection (serving_copy() builds
     it from a trained group): find, find_pooled (unweighted, no located buffer) and find_pooled_jagged, each bit for bit the per-member lookup; every
-    training method raises MeepoError(ERR_UNSUPPORTED).  fp32-row and bf16-row tables never share a group."""
+    training method raises MeepoError(ERR_UNSUPPORTED).  fp32-row and bf16-row tables never share a group.
+
+    search(queries [n_tables, Q, dim], k) is LookupTable.search of every member with its own Q queries, in three launches for the whole collection
+    (mee_group_search); both kinds of group have it."""
     supports_out_dtype = True
     keyed_bags = True   # find_pooled(layout="keyed", step_index=)
     change_logs = None      # the members' ChangeLogs once track_changes() ran, and ...
@@ -1458,6 +1461,38 @@ class TableGroup:
         k = self.tables[0]._bag_keys(keys)
         return _find_padded(_lib.lib().mee_group_find_padded_as, self._h, self.device, self.dim, k, bag_offsets, bpt * len(self.tables), bpt, max_len, keep, out,
                             found, out_dtype, with_step)
+
+    def search(self, queries: torch.Tensor, k: int, out_keys: torch.Tensor | None = None, out_scores: torch.Tensor | None = None, counts: bool = False,
+               metric: str = "ip"):
+        """LookupTable.search(queries[j], k, metric=metric) of every member j, in three launches whatever the number of members (mee_group_search;
+        SPEC.md §3 "Search", "Groups").  queries: float32 [n_tables, Q, dim] on the group's device, the same Q for every member ->
+        (keys [n_tables, Q, k] int64, scores [n_tables, Q, k] float32) and, counts=True, the real entries per query ([n_tables, Q] int32); each
+        member's block is that member's own answer bit for bit — order, ties, padding and NaN rule included.  fp32-row and bf16-row groups, dim a
+        multiple of 16 in [16, SEARCH_MAX_DIM], k in [1, SEARCH_MAX_K], 1 <= n_tables * Q <= SEARCH_BATCH_MAX_QUERIES: a larger batch is refused,
+        not cut — the caller splits Q.  No exclusion lists and no seed pass (a very large member is scanned without the batched search's head
+        start).  The workspace is a tensor cached by size, one per stream that searched.  Sync-free unless a member was reserve()d since the last
+        call; no gradient."""
+        n_t = len(self.tables)
+        if metric not in _lib.METRICS:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"metric must be one of {sorted(_lib.METRICS)} (got {metric!r})")
+        if queries.dtype != torch.float32 or queries.device != self.device or queries.dim() != 3 or queries.shape[0] != n_t or queries.shape[2] != self.dim:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"queries must be float32 [{n_t}, n_queries, {self.dim}] on {self.device} "
+                                                   f"(got {queries.dtype} {list(queries.shape)} on {queries.device})")
+        if not isinstance(k, int) or not 1 <= k <= _lib.SEARCH_MAX_K:
+            raise MeepoError(_lib.ERR_INVALID_ARG, f"k must be an int in [1, {_lib.SEARCH_MAX_K}] (got {k!r})")
+        q, nq, m, L = queries.contiguous(), queries.shape[1], _lib.METRICS[metric], _lib.lib()
+        need = C.c_uint64()
+        check(L.mee_group_search_workspace_bytes(self._h, m, nq, k, C.byref(need)))   # (every refusal of the shape comes from here, before any launch)
+        out_keys = _buffer(out_keys, "out_keys", torch.int64, (n_t, nq, k), self.device)
+        out_scores = _buffer(out_scores, "out_scores", torch.float32, (n_t, nq, k), self.device)
+        n_real = torch.empty((n_t, nq), dtype=torch.int32, device=self.device) if counts else None
+        stream = _stream_ptr(self.device)
+        cache = self.__dict__.setdefault("_search_ws", {})   # one workspace per stream: searches on different streams may overlap
+        ws = cache.get(stream)
+        if ws is None or ws.numel() < need.value:
+            ws = cache[stream] = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        check(L.mee_group_search(self._h, m, q.data_ptr(), nq, k, out_keys.data_ptr(), out_scores.data_ptr(), _ptr(n_real), ws.data_ptr(), stream))
+        return (out_keys, out_scores, n_real) if counts else (out_keys, out_scores)
 
     def apply_pooled(self, keys: torch.Tensor, bag_offsets: torch.Tensor, bag_grads: torch.Tensor, bag_of_position: torch.Tensor,
                      optimizer: str, lr: float, eps: float | None = None, beta1: float = 0.9, beta2: float = 0.999, step: int = 1,

@@ -24,7 +24,9 @@ E scorers (read off the matrix), the case in which the filter is asked most ofte
     filtered          table.search(queries, k, exclude=[Q, E]): mee_search_filtered — the sort of the rows and the filtered launches
     filtered shared   the same with one [1, E] row (query 0's) for every query
     overfetch+filter  only where k + E <= 64: table.search(queries, k + E) and the filter in torch (compare, stable argsort, gather)
-usage: python tools/search_bench.py [--metric ip|cosine] [--exclude 54,64,4096] [--keys N] [--dim D] [--reps K] [--queries 1,32,128,1024] [--ks 10,64] [--libs parent=PATH,…] [--no-matmul]"""
+--group T replaces the rows by the grouped measurement (profiles/search.md "Groups"): `group`, one TableGroup.search over T tables of --keys keys, and
+`loop`, the T table.search calls it stands for.
+usage: python tools/search_bench.py [--group T] [--metric ip|cosine] [--exclude 54,64,4096] [--keys N] [--dim D] [--reps K] [--queries 1,32,128,1024] [--ks 10,64] [--libs parent=PATH,…] [--no-matmul]"""
 import argparse
 import ctypes as C
 import json
@@ -47,6 +49,7 @@ ap.add_argument("--libs", default="", help="NAME=PATH,…: other builds of the l
 ap.add_argument("--metric", default="ip", choices=["ip", "cosine"])
 ap.add_argument("--exclude", default="", help="E,…: time search(exclude=...) with each query's top E scorers excluded against the unfiltered search")
 ap.add_argument("--no-matmul", action="store_true", help="leave the matrix path out (a kernel trace of the search alone)")
+ap.add_argument("--group", type=int, default=0, help="T: time TableGroup.search over T tables of --keys keys each against the loop of T table.search calls, and nothing else")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -70,6 +73,41 @@ def timed_rows(rows, reps, chunk=5):
             total[nm] += ev[0].elapsed_time(ev[1]) * 1e3
     return {nm: total[nm] / (reps // chunk * chunk) for nm in names}
 
+
+def group_mode():
+    """--group T (profiles/search.md "Groups"): T tables of --keys keys each at load 0.75, fp32 rows and bf16 rows; `group` = TableGroup.search(queries
+    [T, Q, dim], k), three launches, and `loop` = T LookupTable.search(queries[j], k) calls — this tree's single-table path — take turns in one timing
+    loop, two passes.  Both are checked equal before they are timed."""
+    from meepoembedding_amd import TableGroup
+    for value_dtype in (torch.float32, torch.bfloat16):
+        tables = [LookupTable(int(args.keys / 0.75), args.dim, device=dev, max_batch=1 << 20, value_dtype=value_dtype) for _ in range(args.group)]
+        for t in tables:
+            bench.populate(t, synth, args.keys, args.dim, dev, 1 << 20)
+        group = TableGroup(tables)
+        steps = sum((t.capacity + 31) // 32 for t in tables)
+        for nq in [int(x) for x in args.queries.split(",")]:
+            queries = torch.randn(args.group, nq, args.dim, device=dev)
+            for k in [int(x) for x in args.ks.split(",")]:
+                rows = {"group": lambda: group.search(queries, k, metric=args.metric),
+                        "loop": lambda: [t.search(queries[j], k, metric=args.metric) for j, t in enumerate(tables)]}
+                got = group.search(queries, k, metric=args.metric)
+                for j, (lk, ls) in enumerate(rows["loop"]()):
+                    assert torch.equal(got[0][j], lk) and torch.equal(got[1][j].view(torch.int32), ls.view(torch.int32)), f"member {j}: group and table search disagree"
+                passes = [timed_rows(rows, args.reps) for _ in range(2)]
+                us = {nm: (passes[0][nm] + passes[1][nm]) / 2 for nm in rows}
+                rec = {"group": args.group, "metric": args.metric, "rows": str(value_dtype).split(".")[1], "keys_per_table": tables[0].size(), "steps": steps, "dim": args.dim,
+                       "Q": nq, "k": k, "us": {nm: round(v, 1) for nm, v in us.items()}, "spread_us": {nm: round(abs(passes[0][nm] - passes[1][nm]), 1) for nm in rows},
+                       "loop_over_group": round(us["loop"] / us["group"], 2)}
+                print("SEARCH_BENCH " + json.dumps(rec), flush=True)
+        group.close()
+        for t in tables:
+            t.close()
+        torch.cuda.empty_cache()
+
+
+if args.group:
+    group_mode()
+    sys.exit(0)
 
 WIDE = args.dim > 256   # mee_search has no such row: every Q is ONE mee_search_batch call (DESIGN.md §4 "Search", "Wide rows"); no split-call row
 
