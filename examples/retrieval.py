@@ -45,7 +45,12 @@ assert not known[:, 4 * k:].any() and torch.isneginf(rescored[:, 4 * k:]).all() 
 top = torch.gather(slate, 1, rescored.argsort(dim=1, descending=True)[:, :k])
 print(f"re-ranked a slate of {slate.shape[1]} ids per user ({int((~known.bool()).sum())} unknown ones scored -inf); user 0's best of it: item {int(top[0, 0])}")
 
-seeds = keys[:4, 0].contiguous()                                # item to item: "items similar to these", asked in cosine — the norms of a trained table's
+promoted = wide[0].contiguous()                                 # ONE slate for the whole batch — today's promoted items: keys of dimension 1, no [32, 4k] key block;
+boost, listed = serving.score(users, promoted)                  # a row is gathered once per tile of queries and the [32, 4k] block is a matrix product
+assert listed.all() and boost.shape == (32, 4 * k) and torch.allclose(boost[0], wide_scores[0], rtol=1e-4, atol=1e-4)
+print(f"scored {promoted.numel()} promoted items against all 32 users in one launch; user 1's best of them: item {int(promoted[boost[1].argmax()])}")
+
+seeds = keys[:4, 0].contiguous()                               # item to item: "items similar to these", asked in cosine — the norms of a trained table's
 seed_rows, _ = serving.find(seeds)                              # rows are very unequal, and the table cannot be normalised without a second copy of it
 near, cos = serving.search(seed_rows, k, metric="cosine")       # both norms are taken inside the scan, from the row bytes it reads anyway
 again, known = serving.score(seed_rows, near, metric="cosine")  # the same four fp32 operations on the same operands

@@ -1222,6 +1222,23 @@ int mee_search_metric(const mee_table* t, int metric, const float* d_queries, si
                       uint32_t* d_out_counts /* nullable */, void* d_workspace, void* stream);
 int mee_score_metric(const mee_table* t, int metric, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand,
                      float* d_out_scores, uint8_t* d_out_found /* nullable */, void* stream);
+/* mee_score_shared: every one of n_queries queries against the SAME n_cand keys — one slate for the whole batch (promoted items, sampled negatives, a
+ * category's catalogue, a ranker's shared candidates):  out[q][c] = score(q, keys[c]),  found[c] = whether the table holds keys[c].  No [Q, C] key
+ * block is needed, every key is probed once per query tile and its row gathered once per query tile instead of once per query; the Q x C block is a
+ * matrix product (v_mfma_f32_32x32x16_bf16) over rows held in registers (DESIGN.md §4 "Score", "Shared slate").
+ * d_keys: [n_cand] int64, 8-byte aligned, duplicates allowed.  d_out_scores: [n_queries, n_cand] fp32.  d_out_found (nullable): [n_cand] uint8.
+ * Everything observable about one entry is mee_score_metric's contract, word for word, under either metric: both operands rounded once to bf16, ties
+ * to even (a bf16 row's bits verbatim), every product exact, the sum fp32 in an unspecified order — so on exactly summable data the score is bit-equal
+ * to mee_score_metric's for the same (query, key), and otherwise within the same bound, (dim - 1) * 2^-24 * sum |products| or the cosine bound above;
+ * a zero leaves as +0.0, a NaN score is returned as NaN, an absent or reserved key (<= MEE_RECLAIMED_KEY, INT64_MIN among them) scores -inf for every
+ * query with found 0; cosine is the same four fp32 operations, a zero row or a zero query gives NaN with found 1.
+ * Tables and limits are mee_score_metric's: fp32-row (with or without an optimizer) and bf16-row tables, int8 rows MEE_ERR_UNSUPPORTED; dim % 16 == 0,
+ * 16 <= dim <= MEE_SEARCH_MAX_DIM; n_queries == 0 or n_cand == 0 is MEE_OK and launches nothing; a null or misaligned pointer (queries 16-byte, keys
+ * 8-byte, scores 4-byte aligned), an unknown metric and an n_queries * n_cand that does not fit are MEE_ERR_INVALID_ARG before any launch.
+ * Read-only on the table, hit counters included; one launch, no atomics, vector stores only, no workspace, no allocation, no synchronisation: safe
+ * under stream capture; ordered against mutators as mee_find is. */
+int mee_score_shared(const mee_table* t, int metric, const float* d_queries, size_t n_queries, const int64_t* d_keys /* [n_cand] */, size_t n_cand,
+                     float* d_out_scores /* [n_queries, n_cand] */, uint8_t* d_out_found /* [n_cand], nullable */, void* stream);
 
 /* ---- exclusion: "the best k except these" (SPEC.md §3 "Search", "Exclusion") ------------------------------------------------------------------------
  * mee_search_filtered is mee_search_metric with one change: the CANDIDATES of query q are the live slots whose key is not in q's exclude row.

@@ -93,6 +93,8 @@ public:
     uint64_t search_metric_workspace_bytes(int metric, size_t n_queries, uint32_t k) const { uint64_t b = 0; check(mee_search_metric_workspace_bytes(t_, metric, n_queries, k, &b)); return b; }
     void search_metric(int metric, const float* d_queries, size_t n_queries, uint32_t k, int64_t* d_out_keys, float* d_out_scores, uint32_t* d_out_counts, void* d_workspace, void* stream = nullptr) const { check(mee_search_metric(t_, metric, d_queries, n_queries, k, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream)); }
     void score_metric(int metric, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores, uint8_t* d_out_found = nullptr, void* stream = nullptr) const { check(mee_score_metric(t_, metric, d_queries, n_queries, d_keys, n_cand, d_out_scores, d_out_found, stream)); }
+    // every query against the SAME slate (mee_score_shared): d_keys / d_out_found [n_cand], d_out_scores [n_queries, n_cand]
+    void score_shared(int metric, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores, uint8_t* d_out_found = nullptr, void* stream = nullptr) const { check(mee_score_shared(t_, metric, d_queries, n_queries, d_keys, n_cand, d_out_scores, d_out_found, stream)); }
     // search_metric over the live rows whose key is not in the query's exclude row (mee_search_filtered): d_exclude [exclude_rows][n_exclude], exclude_rows == n_queries or 1
     uint64_t search_filtered_workspace_bytes(int metric, size_t n_queries, uint32_t k, size_t exclude_rows, size_t n_exclude) const { uint64_t b = 0; check(mee_search_filtered_workspace_bytes(t_, metric, n_queries, k, exclude_rows, n_exclude, &b)); return b; }
     void search_filtered(int metric, const float* d_queries, size_t n_queries, uint32_t k, const int64_t* d_exclude, size_t exclude_rows, size_t n_exclude, int64_t* d_out_keys, float* d_out_scores, uint32_t* d_out_counts, void* d_workspace, void* stream = nullptr) const { check(mee_search_filtered(t_, metric, d_queries, n_queries, k, d_exclude, exclude_rows, n_exclude, d_out_keys, d_out_scores, d_out_counts, d_workspace, stream)); }

@@ -308,6 +308,7 @@ PROTOTYPES = {
     "mee_search_metric_workspace_bytes": (C.c_int, [_vp, C.c_int, _sz, _u32, C.POINTER(_u64)]),
     "mee_search_metric": (C.c_int, [_vp, C.c_int, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _vp]),
     "mee_score_metric": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "mee_score_shared": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     # filtered search (table, metric, queries, n_queries, k, exclude [exclude_rows, n_exclude], exclude_rows, n_exclude, out_keys, out_scores, out_counts | null, workspace, stream)
     "mee_search_filtered_workspace_bytes": (C.c_int, [_vp, C.c_int, _sz, _u32, _sz, _sz, C.POINTER(_u64)]),
     "mee_search_filtered": (C.c_int, [_vp, C.c_int, _vp, _sz, _u32, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),

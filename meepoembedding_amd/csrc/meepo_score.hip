@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "meepo_table_int.h"
+#include "meepo_mma_operand.h"
 
 namespace mee {
 
@@ -267,6 +268,225 @@ __global__ __launch_bounds__(kScoreWaves * 64) void score_wide_kernel(const int6
     }
 }
 
+// ---- a shared slate: every query against the SAME keys (SPEC.md §3 "Score", "Shared slate"; DESIGN.md §4 "Score", "Shared slate") ----------------
+// out[q][c] = score(q, keys[c]) is a matrix product once a key's row is in registers, so the row bytes are paid once per QUERY TILE, not once per
+// query: the scan's operand loop (meepo_mma_operand.h) fed by probed slots, writing a dense block.
+//   units    the queries in tiles that fit the LDS as rounded bf16 fragments (shared_tile), the keys in spans of whole block steps; a block of
+//            kSharedWaves waves serves (tile, span) pairs blockIdx.x, + gridDim.x, ..., the tile index fastest: the blocks that gather one span's rows
+//            are neighbours in time.  The tile is staged once per unit in fragment order, with the queries' norms (cosine).
+//   step     a wave takes 32 consecutive keys of the span — the 32 columns of v_mfma_f32_32x32x16_bf16: one coalesced key load, eight probe rounds
+//            of four keys (one 16-lane tile each, the shared read-only probe) with the eight bucket lines requested back to back, the slots handed
+//            round by shuffle so that lane (half, col) holds the slot of key col.
+//   B        the lane's part of ITS key's row, exactly as the scan loads a slot's (search_load_b / search_wide_chunk); an absent key loads nothing
+//            and holds zeros; a step whose 32 keys were all found takes straight-line loads (wave-uniform).
+//   product  narrow rows: B stays in registers for every row block of 32 queries of the tile.  Wide rows: a tile is one row block, the row is walked
+//            in chunks of kWideChunkKS k-steps, one chunk of B live at a time.
+//   stores   accumulator i of lane (half, col) is query 32 rb + 8 (i / 4) + 4 half + i % 4 against key col: each accumulator index leaves as two
+//            runs of 32 consecutive floats, one per half.  -inf for an absent key, + 0.f on a real score, a NaN as it is.  found[c]: the first tile's
+//            blocks.  Cosine: rr from the B registers, the other half's share by shuffle; the exact four operations per output.
+// Vector stores only, no atomics, nothing of the table is written.
+constexpr int kSharedWaves = 8;                    // waves of a block: they share one staged query tile
+constexpr int kSharedWideWaves = 4;                // ... of a wide row's block: a chunk of an fp32 row in flight needs more than the 256 registers of an 8-wave block's lane
+constexpr uint32_t kSharedLdsBudget = 64 * 1024;   // A fragments and norms of a tile: two blocks fit a CU's 160 KB — and its registers up to 128 VGPRs
+constexpr uint32_t kSharedMaxSpanSteps = 16;       // block steps of a span at most, behind one staging of the tile
+// the queries of a tile: what the budget holds at dim * 2 bytes of fragments and one norm each — whole row blocks of a narrow row (at least one: 8.3 KB
+// at dim 256), one row block at most, in eights, of a wide row (24 queries at dim 1024)
+__host__ __device__ constexpr uint32_t shared_tile(uint32_t dim) {
+    const uint32_t fit = kSharedLdsBudget / (dim * 2 + 4);
+    return dim <= 256 ? fit / 32 * 32 : (fit < 32 ? fit / 8 * 8 : 32);
+}
+static_assert(shared_tile(256) >= 32 && shared_tile(MEE_SEARCH_MAX_DIM) >= 8, "every dim is served in tiles of at least 8 queries");
+
+// A step's 32 keys [base, base + 32) below c1 probed: the slot of key base + col (or -1) in lanes (0, col) and (1, col).  All 64 lanes, convergent.
+__device__ __forceinline__ int64_t shared_probe_step(const int64_t* __restrict__ tkeys, uint64_t nb, const int64_t* __restrict__ keys, uint64_t base, uint64_t c1, int lane) {
+    constexpr int R = 8;   // rounds: four keys each, key 4 r + tile by tile `tile`
+    const int tile = lane >> 4, tl = lane & 15, col = lane & 31;
+    const int64_t kmine = (lane < 32 && base + lane < c1) ? keys[base + lane] : kEmpty;
+    int64_t key[R], kb[R], slot[R];
+    uint64_t b[R];
+    bool act[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        key[r] = __shfl(kmine, r * 4 + tile);
+        act[r] = !reserved_key(key[r]);   // (a position past the span holds EMPTY)
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        b[r] = bucket_of(key[r], nb);
+        kb[r] = act[r] ? tkeys[b[r] * kW + tl] : kEmpty;
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) slot[r] = tile_probe(tkeys, nb, key[r], act[r], b[r], kb[r], tile, tl);
+    int64_t mine = -1;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int64_t v = __shfl(slot[r], (col & 3) * kW);
+        if ((col >> 2) == r) mine = v;
+    }
+    return mine;
+}
+
+// The 16 accumulators of a row block leave: accumulator i is query qb + 8 (i / 4) + i % 4 of the tile (qb = 32 rb + 4 half) against the lane's key,
+// out points at the tile's first row and the key's column.  rn (cosine): the row's norm; qn: the tile's norms in LDS.
+template <int METRIC>
+__device__ __forceinline__ void shared_store(const f32x16& acc, uint32_t qb, uint32_t nq, bool in_span, bool live, [[maybe_unused]] float rn,
+                                             [[maybe_unused]] const float* qn, float* __restrict__ out, uint64_t n_cand) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const uint32_t q = qb + 8 * (i >> 2) + (i & 3);
+        float s = acc[i];
+        if constexpr (METRIC == MEE_METRIC_COSINE) s = cosine_score(s, qn[q < nq ? q : 0], rn);   // the four operations; 0 / 0 = NaN is returned
+        else s += 0.f;                                                                            // a zero leaves as +0.0; a NaN stays a NaN
+        if (in_span && q < nq) __builtin_nontemporal_store(live ? s : -__builtin_inff(), out + (uint64_t)q * n_cand);
+    }
+}
+
+// what the two kernels' blocks share per unit: the unit's tile and span
+struct SharedUnit { uint64_t q0; uint32_t nq; uint64_t c0, c1; bool first_tile; };
+__device__ __forceinline__ SharedUnit shared_unit(uint64_t unit, uint64_t nq_all, uint32_t tile, uint64_t n_tiles, uint64_t n_cand, uint64_t span) {
+    const uint64_t t = unit % n_tiles, sp = unit / n_tiles;
+    SharedUnit u;
+    u.q0 = t * tile;
+    u.nq = nq_all - u.q0 < tile ? (uint32_t)(nq_all - u.q0) : tile;
+    u.c0 = sp * span;
+    u.c1 = n_cand - u.c0 < span ? n_cand : u.c0 + span;   // (c0 < n_cand: the spans are ceil(n_cand / span))
+    u.first_tile = t == 0;
+    return u;
+}
+
+// rows of dim = 16 KS <= 256.  LDS (dynamic): A fragments [n_rb][KS][64] x 16 B, the scan's layout | qn [32 n_rb]
+template <int KS, int ROWS, int METRIC>
+__global__ __launch_bounds__(kSharedWaves * 64) void score_shared_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t nb,
+                                                                          const float* __restrict__ queries, uint64_t nq_all, uint32_t tile, uint64_t n_tiles,
+                                                                          const int64_t* __restrict__ keys, uint64_t n_cand, uint64_t span, uint64_t n_units,
+                                                                          float* __restrict__ out, uint8_t* __restrict__ found) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char score_lds[];
+    constexpr uint32_t dim = 16 * KS;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, col = lane & 31;
+    u32x4* const afrag = reinterpret_cast<u32x4*>(score_lds);
+
+    for (uint64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {   // block-uniform
+        const SharedUnit u = shared_unit(unit, nq_all, tile, n_tiles, n_cand, span);
+        const uint32_t n_rb = (u.nq + 31) / 32;
+        float* const qn = reinterpret_cast<float*>(score_lds + (size_t)n_rb * 32 * dim * 2);
+        if (unit != blockIdx.x) __syncthreads();   // the previous unit's fragments are still being read
+        // ---- the tile's queries, rounded once, in fragment order: a wave stages whole row blocks, so a query's norm is one lane pair's sum
+        for (uint32_t rb = wave; rb < n_rb; rb += kSharedWaves) {
+            const uint32_t q = rb * 32 + col;
+            const f32x4* src = reinterpret_cast<const f32x4*>(queries + (u.q0 + (q < u.nq ? q : 0)) * dim + 8 * half);
+            [[maybe_unused]] float qq = 0.f;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                u32x4 p = {0u, 0u, 0u, 0u};
+                if (q < u.nq) {
+                    const f32x4 x = src[4 * ks], y = src[4 * ks + 1];
+                    p = u32x4{bf16x2_of(x.x, x.y), bf16x2_of(x.z, x.w), bf16x2_of(y.x, y.y), bf16x2_of(y.z, y.w)};
+                }
+                afrag[(rb * KS + ks) * 64 + lane] = p;
+                if constexpr (METRIC == MEE_METRIC_COSINE) qq = sum_squares(p, qq);
+            }
+            if constexpr (METRIC == MEE_METRIC_COSINE) {
+                qq += __shfl_xor(qq, 32);
+                if (half == 0) qn[q] = __builtin_sqrtf(qq);   // (a padding query: 0, never used)
+            }
+        }
+        __syncthreads();
+
+        for (uint64_t base = u.c0 + (uint64_t)wave * 32; base < u.c1; base += kSharedWaves * 32) {   // wave-uniform
+            const int64_t slot = shared_probe_step(tkeys, nb, keys, base, u.c1, lane);
+            const bool live = slot >= 0, in_span = base + col < u.c1;
+            bf16x8 b[KS];
+            if (__all(live)) search_load_b<KS, ROWS>(values, (uint64_t)slot, half, true, b);   // the common step: straight-line loads
+            else search_load_b<KS, ROWS>(values, (uint64_t)slot, half, live, b);
+            [[maybe_unused]] float rn = 0.f;
+            if constexpr (METRIC == MEE_METRIC_COSINE) {   // the lane's eight elements of every k-step, then the other half's
+                float rr = 0.f;
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) rr = sum_squares(__builtin_bit_cast(u32x4, b[ks]), rr);
+                rr += __shfl_xor(rr, 32);
+                rn = __builtin_sqrtf(rr);
+            }
+            if (u.first_tile && found && half == 0 && in_span) found[base + col] = (uint8_t)live;
+            float* const o = out + u.q0 * n_cand + base + col;
+            for (uint32_t rb = 0; rb < n_rb; ++rb) {
+                f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, afrag[(rb * KS + ks) * 64 + lane]), b[ks], acc, 0, 0, 0);
+                shared_store<METRIC>(acc, rb * 32 + 4 * half, u.nq, in_span, live, rn, qn, o, n_cand);
+            }
+        }
+    }
+}
+
+// rows of 256 < dim <= MEE_SEARCH_MAX_DIM: tile <= 32 queries, one row block.  LDS (dynamic): A fragments [dim / 16][2][nq] x 16 B, the wide scan's
+// layout (search_wide_chunk reads it) | qn [32]
+template <int ROWS, int METRIC>
+__global__ __launch_bounds__(kSharedWideWaves * 64) void score_shared_wide_kernel(const int64_t* __restrict__ tkeys, const void* __restrict__ values, uint64_t nb, uint32_t dim,
+                                                                               const float* __restrict__ queries, uint64_t nq_all, uint32_t tile, uint64_t n_tiles,
+                                                                               const int64_t* __restrict__ keys, uint64_t n_cand, uint64_t span, uint64_t n_units,
+                                                                               float* __restrict__ out, uint8_t* __restrict__ found) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char score_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, col = lane & 31;
+    const uint32_t ks_all = dim / 16, n_full = ks_all / kWideChunkKS * kWideChunkKS;
+    constexpr uint32_t esz = ROWS == kRowsBF16 ? 2 : 4;   // bytes of a stored element
+    u32x4* const afrag = reinterpret_cast<u32x4*>(score_lds);
+
+    for (uint64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {   // block-uniform
+        const SharedUnit u = shared_unit(unit, nq_all, tile, n_tiles, n_cand, span);
+        const uint32_t nq = u.nq;
+        float* const qn = reinterpret_cast<float*>(score_lds + (size_t)nq * dim * 2);
+        if (unit != blockIdx.x) __syncthreads();   // the previous unit's fragments are still being read
+        // ---- the tile's queries, rounded once: wave w stages k-steps w, w + kSharedWideWaves, ...
+        if ((uint32_t)col < nq) {
+            const f32x4* src = reinterpret_cast<const f32x4*>(queries + (u.q0 + col) * dim + 8 * half);
+            for (uint32_t ks = wave; ks < ks_all; ks += kSharedWideWaves) {
+                const f32x4 x = src[4 * ks], y = src[4 * ks + 1];
+                afrag[((size_t)ks * 2 + half) * nq + col] = u32x4{bf16x2_of(x.x, x.y), bf16x2_of(x.z, x.w), bf16x2_of(y.x, y.y), bf16x2_of(y.z, y.w)};
+            }
+        }
+        __syncthreads();
+        if constexpr (METRIC == MEE_METRIC_COSINE) {   // the norms from the staged fragments, by one wave in k-step order
+            if (wave == 0) {
+                float qq = 0.f;
+                if ((uint32_t)col < nq)
+                    for (uint32_t ks = 0; ks < ks_all; ++ks) qq = sum_squares(afrag[((size_t)ks * 2 + half) * nq + col], qq);
+                qq += __shfl_xor(qq, 32);
+                if (half == 0) qn[col] = __builtin_sqrtf(qq);   // (a padding query: 0, never used)
+            }
+            __syncthreads();
+        }
+
+        for (uint64_t base = u.c0 + (uint64_t)wave * 32; base < u.c1; base += kSharedWideWaves * 32) {   // wave-uniform
+            const int64_t slot = shared_probe_step(tkeys, nb, keys, base, u.c1, lane);
+            const bool live = slot >= 0, in_span = base + col < u.c1;
+            const unsigned char* const row = reinterpret_cast<const unsigned char*>(values) + ((uint64_t)slot * dim + 8 * half) * esz;   // the lane's eight elements of k-step 0
+            f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            float rr = 0.f;
+            if (__all(live)) {   // the common step: straight-line loads
+#pragma unroll 1
+                for (uint32_t ks0 = 0; ks0 < n_full; ks0 += kWideChunkKS)
+                    search_wide_chunk<ROWS, METRIC, true>(row + (size_t)ks0 * 16 * esz, afrag, ks0, kWideChunkKS, nq, half, col, true, acc, rr);
+                if (n_full < ks_all)
+                    search_wide_chunk<ROWS, METRIC, false>(row + (size_t)n_full * 16 * esz, afrag, n_full, (int)(ks_all - n_full), nq, half, col, true, acc, rr);
+            } else {
+#pragma unroll 1
+                for (uint32_t ks0 = 0; ks0 < n_full; ks0 += kWideChunkKS)
+                    search_wide_chunk<ROWS, METRIC, true>(row + (size_t)ks0 * 16 * esz, afrag, ks0, kWideChunkKS, nq, half, col, live, acc, rr);
+                if (n_full < ks_all)
+                    search_wide_chunk<ROWS, METRIC, false>(row + (size_t)n_full * 16 * esz, afrag, n_full, (int)(ks_all - n_full), nq, half, col, live, acc, rr);
+            }
+            [[maybe_unused]] float rn = 0.f;
+            if constexpr (METRIC == MEE_METRIC_COSINE) {
+                rr += __shfl_xor(rr, 32);
+                rn = __builtin_sqrtf(rr);
+            }
+            if (u.first_tile && found && half == 0 && in_span) found[base + col] = (uint8_t)live;
+            shared_store<METRIC>(acc, 4 * half, nq, in_span, live, rn, qn, out + u.q0 * n_cand + base + col, n_cand);
+        }
+    }
+}
+
 }  // namespace mee
 
 using namespace mee;
@@ -314,8 +534,69 @@ static int score_launch(const mee_table* t, const float* d_queries, size_t n_que
     return MEE_OK;
 }
 
+// mee_score_shared: score_launch's checks, then (tile, span) units over the one slate
+template <int METRIC>
+static int score_shared_launch(const mee_table* t, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores,
+                               uint8_t* d_out_found, void* stream) {
+    const char* const name = "mee_score_shared";
+    if (!t) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (t->dim % 16 || t->dim < 16 || t->dim > MEE_SEARCH_MAX_DIM)
+        return fail(MEE_ERR_INVALID_ARG, "%s: dim must be a multiple of 16 in [16, %d] (got %u)", name, MEE_SEARCH_MAX_DIM, t->dim);
+    if (int rc = refuse_narrow_rows(t, name, false)) return rc;
+    if (n_queries == 0 || n_cand == 0) return MEE_OK;   // as mee_find's n == 0
+    if (!d_queries || !d_keys || !d_out_scores) return fail(MEE_ERR_INVALID_ARG, "%s: null argument", name);
+    if (((uintptr_t)d_queries & 15) || ((uintptr_t)d_keys & 7) || ((uintptr_t)d_out_scores & 3))
+        return fail(MEE_ERR_INVALID_ARG, "%s: queries must be 16-byte aligned, keys 8-byte aligned, scores 4-byte aligned", name);
+    if (n_cand > (SIZE_MAX >> 4) / n_queries) return fail(MEE_ERR_INVALID_ARG, "%s: n_queries * n_cand = %zu * %zu does not fit", name, n_queries, n_cand);
+    DeviceGuard g(t->device);
+    hipStream_t st = as_stream(stream);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) != hipSuccess || cus <= 0) cus = 256;
+    const int waves = t->dim > 256 ? kSharedWideWaves : kSharedWaves;
+    const uint64_t block_step = (uint64_t)waves * 32;
+    const uint64_t steps = (n_cand + block_step - 1) / block_step;
+    // The tile: as many queries as the LDS holds — the slate's rows are gathered once per tile.  A slate too short to give every CU a block at
+    // that tile is served in smaller tiles of whole row blocks (its rows then come from the L2 the neighbouring blocks share).
+    uint32_t tile = shared_tile(t->dim);
+    if (t->dim <= 256) {
+        const uint64_t want = ((uint64_t)cus + steps - 1) / steps;           // tiles that give every CU a block
+        const uint64_t fair = ((n_queries + want - 1) / want + 31) / 32 * 32;   // queries of such a tile, in row blocks
+        if (fair < tile) tile = (uint32_t)fair;
+    }
+    const uint64_t n_tiles = (n_queries + tile - 1) / tile;
+    // A span is a whole number of block steps, sized as score_launch sizes it, for two blocks per CU: what the LDS holds, and what the registers hold
+    // of an instance up to 128 VGPRs.  The wider instances (fp32 rows from dim 144, cosine 112; bf16 rows from dim 208, cosine 192; the wide fp32 kernel) keep ONE block
+    // resident per CU and run this grid as two rounds of blocks
+    uint64_t span_steps = n_tiles * steps / ((uint64_t)cus * 2);
+    span_steps = span_steps < 1 ? 1 : span_steps > kSharedMaxSpanSteps ? kSharedMaxSpanSteps : span_steps;
+    if (span_steps > steps) span_steps = steps;
+    const uint64_t span = span_steps * block_step, n_units = n_tiles * ((n_cand + span - 1) / span);
+    const uint32_t grid = n_units < kScoreMaxGrid ? (uint32_t)n_units : kScoreMaxGrid;
+    const size_t lds = (size_t)tile * t->dim * 2 + (t->dim <= 256 ? tile : 32) * sizeof(float);
+    with_flag(t->bf16_rows, [&](auto bf16) {
+        constexpr int ROWS = bf16 ? kRowsBF16 : kRowsF32;
+        if (t->dim > 256)
+            score_shared_wide_kernel<ROWS, METRIC><<<grid, kSharedWideWaves * 64, lds, st>>>(t->keys, t->values, t->nb, t->dim, d_queries, n_queries, tile, n_tiles, d_keys, n_cand, span,
+                                                                                        n_units, d_out_scores, d_out_found);
+        else with_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>((int)(t->dim / 16), [&](auto ks) {
+            score_shared_kernel<ks, ROWS, METRIC><<<grid, kSharedWaves * 64, lds, st>>>(t->keys, t->values, t->nb, d_queries, n_queries, tile, n_tiles, d_keys, n_cand, span, n_units,
+                                                                                       d_out_scores, d_out_found);
+        });
+    });
+    MEE_HIP(hipGetLastError());
+    return MEE_OK;
+}
+
 extern "C" {
 
+int mee_score_shared(const mee_table* t, int metric, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores,
+                     uint8_t* d_out_found, void* stream) {
+    if (metric != MEE_METRIC_IP && metric != MEE_METRIC_COSINE)
+        return fail(MEE_ERR_INVALID_ARG, "mee_score_shared: metric must be MEE_METRIC_IP (0) or MEE_METRIC_COSINE (1) (got %d)", metric);
+    MEE_RANGE("mee_score_shared");
+    if (metric == MEE_METRIC_IP) return score_shared_launch<MEE_METRIC_IP>(t, d_queries, n_queries, d_keys, n_cand, d_out_scores, d_out_found, stream);
+    return score_shared_launch<MEE_METRIC_COSINE>(t, d_queries, n_queries, d_keys, n_cand, d_out_scores, d_out_found, stream);
+}
 
 int mee_score(const mee_table* t, const float* d_queries, size_t n_queries, const int64_t* d_keys, size_t n_cand, float* d_out_scores, uint8_t* d_out_found,
               void* stream) {

@@ -857,8 +857,24 @@ class LookupTable:
         once to bf16, fp32 sum — so search's own keys score search's scores; an absent or reserved key (search's INT64_MIN padding) scores -inf
         with found 0, a NaN score is returned as NaN.  fp32-row and bf16-row tables, dim a multiple of 16 in [16, SEARCH_MAX_DIM] (past 256 a
         whole wave reduces a key: DESIGN.md §4 "Score", "Wide rows").  No gradient.
-        metric="cosine" (mee_score_metric): search's cosine, dot / (|q| |row|); a zero row or a zero query scores NaN with found 1."""
+        metric="cosine" (mee_score_metric): search's cosine, dot / (|q| |row|); a zero row or a zero query scores NaN with found 1.
+        A shared slate (mee_score_shared): `keys` of dimension 1, int64 [C], is ONE slate for every query — promoted items, sampled negatives, a
+        category's catalogue -> (scores [Q, C] float32, found [C] uint8), entry for entry what keys.expand(Q, C) scores (bit-equal on exactly
+        summable data, the same bound otherwise) without that [Q, C] block: a key is probed and its row gathered once per tile of queries, and the
+        block is a matrix product over rows held in registers (DESIGN.md §4 "Score", "Shared slate").  Both metrics, one native call.  Measured
+        (profiles/score_shared.md): 1.3x to 35x faster than the expanded slate from Q = 256, and from Q = 32 with a slate of 65536; SLOWER at
+        Q = 1 whatever C (0.33x to 0.94x) and at Q = 32 with a slate of 1024 (0.39x to 0.88x) — at Q = 1, and below about Q * C = 100 000,
+        the expanded [Q, C] slate is still the faster call."""
         self._check_metric_queries(metric, queries)
+        if keys.dim() == 1:
+            if keys.dtype != torch.int64 or keys.device != self.device:
+                raise MeepoError(_lib.ERR_INVALID_ARG, f"a shared slate must be int64 [n_candidates] on {self.device} (got {keys.dtype} {list(keys.shape)} on {keys.device})")
+            q, k = queries.contiguous(), keys.contiguous()
+            nq, nc = q.shape[0], k.shape[0]
+            out = _buffer(out, "out", torch.float32, (nq, nc), self.device)
+            found = _buffer(found, "found", torch.uint8, (nc,), self.device)
+            check(_lib.lib().mee_score_shared(self._h, _lib.METRICS[metric], q.data_ptr(), nq, k.data_ptr(), nc, out.data_ptr(), found.data_ptr(), self._s()))
+            return out, found
         if keys.dtype != torch.int64 or keys.device != self.device or keys.dim() != 2 or keys.shape[0] != queries.shape[0]:
             raise MeepoError(_lib.ERR_INVALID_ARG, f"keys must be int64 [{queries.shape[0]}, n_candidates] on {self.device} (got {keys.dtype} {list(keys.shape)} on {keys.device})")
         q, k = queries.contiguous(), keys.contiguous()
